@@ -1,27 +1,32 @@
 #!/usr/bin/env python3
 """bench.py -- encrypted images/sec of the CrCNN evaluation path on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...)
 
 One "step" = one pass of the hot path (Network::forward: conv/pool/[bn/square]/dense over every image) over one batch of `--batch` synthetic encrypted
 MNIST-like images per GPU.  Rank 0 prints ONE JSON line.
 
+A plain run does what the headline figure needs and nothing else: the client side, one bench_host run (W untimed + K timed steps), the result line (the
+contract fields, the per-layer times and the HBM plan bench_host reports anyway).  --full adds everything below that is not the headline: verification of the
+outputs against the compiled reference's goldens and the plaintext model, the roofline, the CPU baseline, and in the default invocation the streamed, latency
+and further-workload lines.  --dump-outputs DIR writes what the last timed step computed as float64 .npy files (dump_outputs below).
+
 The measured path (N = 1).  north_star: "C++ host code calls hand-written HIP kernels through a thin C-ABI" -- so `value` is what crcnn_amd/lib/bench_host measures:
 the C++ host classes (crcnn_amd/host: CnnBuilder builds the network from the HDF5 model, Network::fuse folds it, Network::forward runs it; the reference's class names
 and signatures) over include/crcnn_hip.h.  This script is the harness around it: the client side (keys, encrypted inputs: tools/benchkit/client.py), the child process,
 the verification of the ciphertexts that come back (the compiled reference's goldens, decrypted logits), the roofline arithmetic and the CPU baseline.
-  --python-twin  additionally times the same workload through the Python twin (crcnn_amd/netrun.py, ctypes over the same C ABI) as a cross-check
+  --full --python-twin  additionally times the same workload through the Python twin (crcnn_amd/netrun.py, ctypes over the same C ABI) as a cross-check
 N > 1: the SAME measured path, one bench_host process per GPU.  Every rank of this script (started by torch.distributed.run, or by the script itself when it is
 given --gpus N without a launcher) prepares its own encrypted images on the host cores and starts its bench_host child -- the Python ranks never touch a GPU.  Rank 0's
 child makes the RCCL rendezvous id (crc_comm_unique_id) and leaves it in a file, every child joins (crc_comm_create), the encoded model goes out once with
 Network::broadcastParameters, and the children bracket their timed steps with an all-gather + stream synchronisation and gather the elapsed times: `value` = all ranks'
 images / the slowest rank's time.  The Python ranks only rendezvous over gloo (CPU) to agree on the file name and to count the ranks whose outputs verified.
-  --python-twin at N > 1: the round-4 path (every rank runs netrun.py under torch.distributed) instead
-  --stream-inputs ciphertext|plaintext|both: besides the resident measurement, passes in which every launch's images are uploaded over PCIe while the previous
+  --full --python-twin at N > 1: the round-4 path (every rank runs netrun.py under torch.distributed) instead
+  --full --stream-inputs ciphertext|plaintext|both: besides the resident measurement, passes in which every launch's images are uploaded over PCIe while the previous
                 launch is evaluated (two device buffers, a copy stream beside the compute stream); reported under "streamed"
 
-Besides the contract fields the line carries
+With --full the line carries besides the contract fields
   roofline      the dominant kernel against the roof that bounds it: int8 matrix-core TOP/s for the limb GEMM (frac = executed, useful_frac = without padding; the HBM view
                 of the same launch beside it), HBM GB/s (algorithmic bytes / measured launch duration vs the 8 TB/s peak) for everything else.  Launch durations are HIP
                 events on the launch stream inside the timed region (Network::time_with_events)
@@ -58,8 +63,8 @@ def parse():
     ap.add_argument("--distinct", type=int, default=None, help="distinct encrypted images, tiled to the batch (default: the config's -- 32 for tiny4096 = BASELINE configs[0]'s "
                     "images, every one checked against the compiled reference; 32 for approx8192; 12 for wopad16384, whose images are 784 MiB each)")
     ap.add_argument("--no-fuse", action="store_true", help="do not fold pooling / batch-norm layers (Network::fuse)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target size of the CPU-baseline sample (0 = skip)")
-    ap.add_argument("--also", default="auto", help="further workloads measured in the same invocation and reported under \"also\" (auto: AUTO_ALSO below beside the tiny4096 "
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: target size of the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--also", default="auto", help="--full: further workloads measured in the same invocation and reported under \"also\" (auto: AUTO_ALSO below beside the tiny4096 "
                     "headline -- BASELINE configs[2] and configs[4]'s per-GPU share, k = 4 at n = 8192, the no-MFMA pass, the reference's two published configurations; none: skip)")
     ap.add_argument("--also-steps", type=int, default=2)
     ap.add_argument("--also-batch", type=int, default=None)
@@ -70,18 +75,30 @@ def parse():
     ap.add_argument("--t-bits", type=int, default=None, help="twin only: override the plain modulus t = 2^bits")
     ap.add_argument("--launch-check", action="store_true", help="only start the ranks, rendezvous (gloo, no GPU call) and report: CPU test of the self-launch path")
     ap.add_argument("--stream-inputs", default="auto", choices=["auto", "none", "ciphertext", "plaintext", "both"],
-                    help="also measure with the input launches streamed over PCIe (double-buffered upload beside the kernels): 784 ciphertexts per image, or the 784 pixel "
+                    help="--full: also measure with the input launches streamed over PCIe (double-buffered upload beside the kernels): 784 ciphertexts per image, or the 784 pixel "
                          "plaintexts per image + encryption on the device (auto: both for the tiny4096 headline and ciphertext for approx8192 of the default invocation, "
                          "none otherwise)")
     ap.add_argument("--stream-steps", type=int, default=2, help="passes over the batch of the streamed measurement")
-    ap.add_argument("--latency", default="auto", choices=["auto", "on", "off"], help="single-image latency lines (batch 1, a synchronisation per image) for the headline and the "
+    ap.add_argument("--latency", default="auto", choices=["auto", "on", "off"], help="--full: single-image latency lines (batch 1, a synchronisation per image) for the headline and the "
                     "BASELINE configurations of the default invocation (auto: with the default invocation at N = 1)")
     ap.add_argument("--weights-via", default="broadcast", choices=["broadcast", "floats"], help="N > 1: how every rank gets the encoded model -- broadcast: rank 0 encodes + "
                     "transforms, Network::broadcastParameters sends the residues over RCCL; floats: every rank encodes + transforms from the model file itself (SURVEY 8e's "
                     "alternative), only the evaluation keys and the checksums travel")
     ap.add_argument("--mnist-dir", default=os.environ.get("CRC_MNIST_DIR", ""), help="directory with t10k-images-idx3-ubyte (and t10k-labels-idx1-ubyte): when present the "
                     "distinct images are real MNIST test images and the line reports agreement with the float model's predictions (utils.cpp:20-53)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="the whole record besides the headline: verification against the reference's goldens and the plaintext "
+                    "model, roofline, CPU baseline, and in the default invocation the streamed, latency and further-workload lines (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the last one computed to DIR/<name>.npy (float64): the "
+                    "decrypted logits of the distinct images and a seeded sample of the output ciphertexts' residues")
+    args = ap.parse_args()
+    if not args.full:
+        asked = [o for o, on in (("--python-twin", args.python_twin), ("--also", args.also not in ("auto", "none")), ("--latency on", args.latency == "on"),
+                                 ("--stream-inputs", args.stream_inputs not in ("auto", "none")), ("--unfused-images", args.unfused_images > 0)) if on]
+        if asked:
+            ap.error(f"{', '.join(asked)}: a measurement beside the headline, which only --full runs")
+    if args.dump_outputs and args.python_twin and args.gpus > 1:
+        ap.error("--dump-outputs: the C++ measured path only (not --python-twin at N > 1)")
+    return args
 
 
 def sizes(args, cfg, batch=None):
@@ -134,10 +151,34 @@ def client_inputs(args, cfg_name, cfg, q, D, rank, cores):
     return c, False
 
 
-def run_host(args, cfg_name, steps, warmup, batch=None, device=0, ranks=None, stream="none", over=None, extra=None, with_cpu=True):
+DUMP_CT_WORDS = 1 << 21            # output residues in the seeded sample of --dump-outputs: 2 float64 each = 32 MiB
+
+
+def dump_outputs(dir_, client, cfg, outs, r):
+    """--dump-outputs: what the last timed step computed, as float64 .npy files.  Every launch of a step evaluates the same tiled launch of the D distinct images,
+    and bench_host compares the last timed launch with the untimed first one, whose D images' outputs it wrote (`outs`, [D][10][2][k][n] u64), bit for bit --
+    through their decryptions where a client-side refresh re-encrypts every launch -- so `outs` is the last step's result.
+      logits.npy             [D, 10]  the decrypted, decoded output ciphertexts: what the client reads from the network
+      output_ct_sample.npy   [S, 2]   (high 32 bits, low 32 bits) of S residue words of `outs` at positions drawn with a fixed seed (all of them if fewer than
+                                      DUMP_CT_WORDS): exact integers.  Not written with a refresh, whose ciphertexts differ from launch to launch"""
+    if not r.get("last_timed_launch_identical_to_first"):
+        sys.stderr.write("bench.py: --dump-outputs: the last timed launch differs from the first one, whose outputs are the only ones kept: nothing written\n")
+        return
+    os.makedirs(dir_, exist_ok=True)
+    E = client.E
+    logits = np.array([[E.decode(p) for p in E.decrypt(client.sk, o)] for o in outs], dtype=np.float64)
+    np.save(os.path.join(dir_, "logits.npy"), logits)
+    if "reenc" not in cfg:
+        words = outs.reshape(-1)
+        idx = np.arange(words.size) if words.size <= DUMP_CT_WORDS else np.sort(np.random.default_rng(0).choice(words.size, DUMP_CT_WORDS, replace=False))
+        w = words[idx]
+        np.save(os.path.join(dir_, "output_ct_sample.npy"), np.stack([(w >> np.uint64(32)).astype(np.float64), (w & np.uint64(0xffffffff)).astype(np.float64)], axis=1))
+
+
+def run_host(args, cfg_name, steps, warmup, batch=None, device=0, ranks=None, stream="none", over=None, extra=None, with_cpu=True, dump=None):
     """one workload through crcnn_amd/lib/bench_host.  Returns (bench line dict, all checks ok).  ranks: benchkit.dist.HostRanks when this process is one of several
     (one bench_host per GPU); only rank 0 gets a line back.  over: chunk / tail / distinct of this run (default: the command line's, then the configuration's);
-    extra: further bench_host arguments (sync_each=1 ...)"""
+    extra: further bench_host arguments (sync_each=1 ...); dump: directory for dump_outputs (rank 0).  Without args.full: no verification, roofline or CPU baseline"""
     import crcnn_amd as ca
     from benchkit import cpu, geometry
     cfg = dict(CONFIGS[cfg_name])
@@ -157,8 +198,6 @@ def run_host(args, cfg_name, steps, warmup, batch=None, device=0, ranks=None, st
         mnist = {k_: (v[:D] if isinstance(v, list) else v) for k_, v in mnist.items()}
     client_s = 0.0 if reused else ci["client_s"]
     try:
-        ctw = 2 * cfg["k"] * cfg["n"]
-        x0 = np.fromfile(os.path.join(work, "inputs.u64"), dtype=np.uint64, count=784 * ctw).reshape(1, 28, 28, 2, cfg["k"], cfg["n"])
         exe = os.path.join(ROOT, "crcnn_amd", "lib", "bench_host")
         if not os.path.exists(exe):
             raise SystemExit("bench.py: crcnn_amd/lib/bench_host has not been built (python -c 'import __graft_entry__ as g; g.build()'); there is no fallback path")
@@ -220,8 +259,8 @@ def run_host(args, cfg_name, steps, warmup, batch=None, device=0, ranks=None, st
     except BaseException:
         drop_inputs()
         raise
-    check, ok = client.verify(cfg_name, imgs, outs, x0_sha, golden=mnist is None)
-    if mnist is not None:               # real test images: agreement of the decrypted predictions with the labels and with the float model's predictions the reference ships
+    check, ok = client.verify(cfg_name, imgs, outs, x0_sha, golden=mnist is None) if args.full else ({}, True)
+    if mnist is not None and args.full:  # real test images: agreement of the decrypted predictions with the labels and with the float model's predictions the reference ships
         preds = client.last_predictions
         mnist = dict(mnist, encrypted_predictions=preds)
         if "labels" in mnist:
@@ -247,6 +286,8 @@ def run_host(args, cfg_name, steps, warmup, batch=None, device=0, ranks=None, st
     ok = verified == world
     if ranks and rank != 0:
         return None, ok
+    if dump:
+        dump_outputs(dump, client, cfg, outs, r)
 
     # ---- per-layer figures and the roofline of the dominant kernel: algorithmic bytes per launch / measured launch duration
     L = r["layers"]
@@ -257,7 +298,7 @@ def run_host(args, cfg_name, steps, warmup, batch=None, device=0, ranks=None, st
             ms_per_layer["T_REENC"] = r["T_REENC_ms_per_image"]     # the client-side refresh, where mainparams.cpp:81 puts its column
         ms_per_layer[nm] = ms
     kernels = {nm: kn for nm, kn in zip(L, r["kernel_per_layer"]) if kn}
-    plan = None if args.no_fuse else geometry.fused_plan(client.E, cfg["model"], names=L)
+    plan = None if args.no_fuse or not args.full else geometry.fused_plan(client.E, cfg["model"], names=L)
     roofline, useful, layer_gbps = None, {}, {}
     if plan is not None and [pl[1] for pl in plan] == L:
         split = next((i for i, pl in enumerate(plan) if pl[0] == "fc" and i > 0), len(plan)) if G > 1 else len(plan)
@@ -295,7 +336,7 @@ def run_host(args, cfg_name, steps, warmup, batch=None, device=0, ranks=None, st
                         algorithmic_bytes_per_launch=int(alg_bytes), modmul_per_s=round(modmul_s, 1) if modmul_s else None)
     # ---- the reference's published run of this configuration (thesis: one image on a 40-core Xeon), column by column; fused layers take the sum of their columns
     published = None
-    if cfg.get("published") and not args.no_fuse:
+    if cfg.get("published") and not args.no_fuse and args.full:
         from crcnn_amd.netrun import TOPOLOGIES
         pub = cfg["published"]
         cols = [c_ for c_ in pub["columns"] if c_ != "T_REENC"]
@@ -315,7 +356,9 @@ def run_host(args, cfg_name, steps, warmup, batch=None, device=0, ranks=None, st
                          note="published: single-image latency on the thesis' CPU; ours: per-image time inside a batch on one MI355X (throughput), same parameters, same refresh point, "
                               "decrypted outputs equal to the compiled reference's (check.golden_match)")
     cpu_line = None
-    if with_cpu and args.cpu_seconds > 0 and world == 1:           # (the CPU baseline is timed on rank 0 at N = 1 only)
+    if with_cpu and args.full and args.cpu_seconds > 0 and world == 1:     # (the CPU baseline is timed on rank 0 at N = 1 only)
+        ctw = 2 * cfg["k"] * cfg["n"]
+        x0 = np.fromfile(os.path.join(work, "inputs.u64"), dtype=np.uint64, count=784 * ctw).reshape(1, 28, 28, 2, cfg["k"], cfg["n"])
         evk = client.evaluation_keys() if any(pl[0] in ("square", "squarepool") for pl in (plan or [])) else None
         # (--cpu-seconds >= 600 buys ONE WHOLE image through the compiled reference instead of the sampled pieces: minutes for PlainModelTiny at n = 4096 on 16 cores)
         cpu_line = (cpu.cpu_baseline_reference(cfg, q, client.W, x0, cores, evk=evk, full_image=args.cpu_seconds >= 600) or
@@ -349,6 +392,9 @@ def run_host(args, cfg_name, steps, warmup, batch=None, device=0, ranks=None, st
                                    "the two ping-pong tensors Network::forward keeps + the dense layers' group input, work_buffer = the shared scratch of the layer calls, input_launch = the "
                                    "encrypted images of one launch"),
     }
+    if not args.full:                                               # (the figures only --full computes are left out of a plain line, not set to null)
+        for k_ in ("mfma_useful_frac_per_layer", "layer_hbm_GBps", "roofline", "cpu_baseline", "vs_published", "streamed"):
+            line.pop(k_)
     return line, bool(ok)
 
 
@@ -391,6 +437,8 @@ def main():
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:      # plain `python bench.py --gpus N`: start the ranks ourselves
         sys.exit(bdist.self_launch(args))
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if not args.full:                                        # a plain run: the headline only (parse() refused the options that ask for more)
+        args.also, args.latency, args.stream_inputs = "none", "off", "none"
     also = args.also
     if also == "auto":
         # the default invocation also measures BASELINE configs[2] (ApproxPlainModel, n = 8192, k = 3) and configs[4]'s per-GPU share (PlainModelWoPad, n = 16384, k = 4,
@@ -411,7 +459,7 @@ def main():
         local = int(os.environ.get("LOCAL_RANK", "0"))
         if ranks and os.environ.get("CRC_COMM_TRANSPORT") == "shm":  # a rehearsal with more ranks than GPUs shares devices; the KFD topology is read, no HIP call is made
             local %= max(1, bdist.gpu_count_without_hip())
-        line, ok = run_host(args, args.config, args.steps, args.warmup, batch=args.batch, device=local, ranks=ranks, stream=args.stream_inputs)
+        line, ok = run_host(args, args.config, args.steps, args.warmup, batch=args.batch, device=local, ranks=ranks, stream=args.stream_inputs, dump=args.dump_outputs)
         if args.python_twin and world == 1:
             D_ = bdist.Dist(args)
             tw, ok2 = twin_line(args, D_, args.config, args.steps, args.warmup, args.batch, True)

@@ -30,6 +30,17 @@ def test_fused_plan_names_and_shapes():
     E.close()
 
 
+def test_plain_run_refuses_what_only_full_measures():
+    """a plain bench.py run times the headline only: options that ask for a measurement beside it are refused before anything starts, unless --full is given"""
+    import os
+    import subprocess
+    import sys
+    bench = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py")
+    for extra in (["--python-twin"], ["--latency", "on"], ["--also", "approx8192"], ["--stream-inputs", "both"], ["--unfused-images", "8"]):
+        out = subprocess.run([sys.executable, bench] + extra, capture_output=True, text=True, timeout=120)
+        assert out.returncode == 2 and "only --full runs" in out.stderr, (extra, out.stderr[-500:])
+
+
 def test_limb_exec_over_useful_follows_the_tiling():
     # ApproxPlainModel's conv2: 20 channels, 3 x 3, 50 filters, 5 x 5 outputs; 32 images per launch = 1600 rows (25 tiles of 64), flat form: 6 steps of 32 for 180 terms
     a = dict(zd=20, xd=11, yd=11, xs=2, ys=2, xf=3, yf=3, nf=50)

@@ -80,10 +80,38 @@ def test_comm_one_process_all_devices():
 def _run_bench(extra, env_extra=None):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env.update(env_extra or {})
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "tiny1024", "--steps", "1", "--cpu-seconds", "0", "--also", "none"] + extra,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "tiny1024", "--steps", "1", "--cpu-seconds", "0", "--also", "none", "--full"] + extra,
                          capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
     return json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """a plain run (no --full) times the headline and prints the contract fields without the figures of --full; --dump-outputs writes what the last timed step
+    computed: the output ciphertexts of image 0 hash to the compiled reference's golden, and a second run with the same arguments writes the same arrays"""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "tiny1024", "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, env=env, timeout=900)
+        assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
+        line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["metric"] == "encrypted images/sec" and line["unit"] == "images/s" and line["higher_is_better"] is True and line["dtype"] == "u64"
+        assert line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+        assert not {"roofline", "cpu_baseline", "streamed", "vs_published", "also", "latency"} & set(line)
+        assert line["check"]["last_timed_launch_identical_to_first"] is True and line["check"]["all_ok"] is True
+        files = {f: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert set(files) == {"logits.npy", "output_ct_sample.npy"} and all(a.dtype == np.float64 for a in files.values())
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        dumps.append(files)
+    g = json.load(open(os.path.join(ROOT, "tests", "golden", "net_tiny1024_eng.json")))
+    ct = dumps[0]["output_ct_sample.npy"]
+    words = ct[:, 0].astype(np.uint64) << np.uint64(32) | ct[:, 1].astype(np.uint64)        # tiny1024's 4 images fit the sample whole
+    import hashlib
+    assert hashlib.sha256(words.reshape(4, 10, 2, 2, 1024)[0].tobytes()).hexdigest() == g["out_sha256"]
+    assert np.allclose(dumps[0]["logits.npy"][0], g["logits"], rtol=0, atol=1e-6)
+    assert all(np.array_equal(dumps[0][f], dumps[1][f]) for f in dumps[0])
 
 
 def test_bench_small_workload_matches_reference_golden():
@@ -195,7 +223,7 @@ def test_bench_latency_published_and_valu_lines():
     assert line["config"]["latency_ms_single_image"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     for cfg, extra in (("tiny2048r", []), ("approx4096r", ["--batch", "128"]), ("tiny4096_valu", ["--batch", "64", "--distinct", "2"])):
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--steps", "1", "--cpu-seconds", "0", "--also", "none", "--gpus", "1"] + extra,
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--steps", "1", "--cpu-seconds", "0", "--also", "none", "--gpus", "1", "--full"] + extra,
                              capture_output=True, text=True, env=env, timeout=900)
         assert out.returncode == 0, (cfg, out.stdout[-1500:], out.stderr[-3000:])
         ln = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

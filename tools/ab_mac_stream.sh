@@ -6,7 +6,7 @@ cfgs=${@:-tiny4096 approx8192}
 : > $out
 for cfg in $cfgs; do
   for s in 0 1 2 3 4; do
-    CRC_MAC_STREAM=$s python3 bench.py --config $cfg --batch 1 --chunk 1 --distinct 1 --steps 10 --warmup 2 --cpu-seconds 0 --also none --latency off --stream-inputs none > /tmp/ab_ms.json 2>/tmp/ab_ms.err || { echo "$cfg shape $s FAILED" >> $out; tail -3 /tmp/ab_ms.err >> $out; continue; }
+    CRC_MAC_STREAM=$s python3 bench.py --config $cfg --batch 1 --chunk 1 --distinct 1 --steps 10 --warmup 2 --cpu-seconds 0 --also none --latency off --stream-inputs none --full > /tmp/ab_ms.json 2>/tmp/ab_ms.err || { echo "$cfg shape $s FAILED" >> $out; tail -3 /tmp/ab_ms.err >> $out; continue; }
     python3 - "$cfg" "$s" >> $out <<'P'
 import json, sys
 l = json.loads(open('/tmp/ab_ms.json').read().strip().splitlines()[-1])

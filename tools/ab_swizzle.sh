@@ -1,7 +1,7 @@
 #!/bin/bash
 # same-box A/B of the LDS swizzle (-DCRC_SWZ_KEEP_BIT0): bench two configurations with the shipped library, rebuild with the macro, bench again, rebuild back
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-run() { for cfg in approx8192 tiny4096; do python3 bench.py --config $cfg --steps 2 --cpu-seconds 0 --also none --latency off --stream-inputs none > /tmp/o.json 2>/tmp/o.err || { echo "$1 $cfg FAILED"; tail -3 /tmp/o.err; continue; }
+run() { for cfg in approx8192 tiny4096; do python3 bench.py --config $cfg --steps 2 --cpu-seconds 0 --also none --latency off --stream-inputs none --full > /tmp/o.json 2>/tmp/o.err || { echo "$1 $cfg FAILED"; tail -3 /tmp/o.err; continue; }
   python3 -c "
 import json; l=json.loads(open('/tmp/o.json').read().strip().splitlines()[-1]); print('$1', '$cfg', l['value'], {k: round(v, 4) for k, v in l['ms_per_layer'].items()}, 'ok', l['check']['all_ok'])"; done; }
 run shipped

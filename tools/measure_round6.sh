@@ -12,7 +12,7 @@ K=/tmp/crc_keep6
 if [ $P = first ]; then
   # the driver's invocation; CRC_BENCH_KEEP leaves every configuration's encrypted inputs and bench_host command line behind for the profiler runs below
   rm -rf $K; mkdir -p $K
-  ( time CRC_BENCH_KEEP=$K CRC_BENCH_KEEP_CONFIGS=tiny4096,approx8192,wopad16384 timeout -k 10 1100 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_invocation.json 2> $O/bench_driver_invocation.err ) 2> $O/bench_driver_invocation.time
+  ( time CRC_BENCH_KEEP=$K CRC_BENCH_KEEP_CONFIGS=tiny4096,approx8192,wopad16384 timeout -k 10 1100 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_invocation.json 2> $O/bench_driver_invocation.err ) 2> $O/bench_driver_invocation.time
   tail -3 $O/bench_driver_invocation.time
 fi
 if [ $P = first ]; then
