@@ -414,7 +414,7 @@ static size_t square_chunk(const crc_ctx *c)
 
 extern "C" size_t crc_square_relin_work_bytes(const crc_ctx *c, size_t count, int dbc)
 {
-    if (!c) return 0;
+    if (!c || !dbc_ok(dbc)) return 0;
     const size_t kSquareChunk = square_chunk(c); const size_t ch = count < kSquareChunk ? count : kSquareChunk;
     const size_t sq = k_square_work_words(c, ch), rl = k_relin_work_words(c, ch, dbc);
     // [packed keys][size-3 intermediates of one pass][scratch of the square, then of the relinearisation]
@@ -524,7 +524,7 @@ extern "C" int crc_square(crc_ctx *c, const uint64_t *d_x, size_t count, uint64_
 }
 extern "C" int crc_relinearize(crc_ctx *c, const uint64_t *d_x3, size_t count, const uint64_t *d_evk, int dbc, uint64_t *d_y, void *d_work, void *stream)
 {
-    CHECK_CTX(c); if (!d_x3 || !d_y || !d_evk || !d_work) return CRC_ERR_INVALID_ARGUMENT;
+    CHECK_CTX(c); if (!d_x3 || !d_y || !d_evk || !d_work || !dbc_ok(dbc)) return CRC_ERR_INVALID_ARGUMENT;
     u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
     const size_t kSquareChunk = square_chunk(c);
     for (size_t o = 0; o < count; o += kSquareChunk) {
@@ -537,7 +537,7 @@ extern "C" int crc_relinearize(crc_ctx *c, const uint64_t *d_x3, size_t count, c
 extern "C" int crc_square_relin_forms(crc_ctx *c, const uint64_t *d_x, int in_form, size_t count, const uint64_t *d_evk, int dbc, uint64_t *d_y, int out_form,
                                       void *d_work, void *stream)
 {
-    CHECK_CTX(c); if (!d_x || !d_y || !d_evk || !d_work || !form_ok(in_form) || !form_ok(out_form)) return CRC_ERR_INVALID_ARGUMENT;
+    CHECK_CTX(c); if (!d_x || !d_y || !d_evk || !d_work || !form_ok(in_form) || !form_ok(out_form) || !dbc_ok(dbc)) return CRC_ERR_INVALID_ARGUMENT;
     u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
     const size_t kSquareChunk = square_chunk(c);
     const size_t ch0 = count < kSquareChunk ? count : kSquareChunk;
@@ -555,11 +555,11 @@ extern "C" int crc_square_relin_forms(crc_ctx *c, const uint64_t *d_x, int in_fo
 static size_t sqpool_planes(const crc_ctx *c, int xd, int yd) { const size_t per = (size_t)xd * yd, ch = square_chunk(c); return ch / per ? ch / per : 1; }
 extern "C" int crc_square_pool_relin_supported(const crc_ctx *c, int dbc, int xf, int yf)
 {
-    return c && c->tune.sq_path != 1 && c->tune.relin_path != 1 && k_relin64_pool_supported(c, dbc, xf * yf) ? 1 : 0;
+    return c && dbc_ok(dbc) && c->tune.sq_path != 1 && c->tune.relin_path != 1 && k_relin64_pool_supported(c, dbc, xf * yf) ? 1 : 0;
 }
 extern "C" size_t crc_square_pool_relin_work_bytes(const crc_ctx *c, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int dbc)
 {
-    if (!c || xd < xf || yd < yf || xs < 1 || ys < 1) return 0;
+    if (!c || xd < xf || yd < yf || xs < 1 || ys < 1 || !dbc_ok(dbc)) return 0;
     const size_t planes = (size_t)B * zd, pp = planes < sqpool_planes(c, xd, yd) ? planes : sqpool_planes(c, xd, yd);
     const size_t xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys + 1, cin = pp * xd * yd, cout = pp * xo * yo;
     const size_t sq = k_square_work_words(c, cin), rl = k_relin_work_words(c, cout, dbc);
@@ -568,7 +568,7 @@ extern "C" size_t crc_square_pool_relin_work_bytes(const crc_ctx *c, int B, int 
 extern "C" int crc_square_pool_relin_forms(crc_ctx *c, const uint64_t *d_x, int in_form, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf,
                                            const uint64_t *d_evk, int dbc, const uint64_t *d_div_ntt, uint64_t *d_y, int out_form, void *d_work, void *stream)
 {
-    CHECK_CTX(c); if (!d_x || !d_y || !d_evk || !d_work || !form_ok(in_form) || !form_ok(out_form)) return CRC_ERR_INVALID_ARGUMENT;
+    CHECK_CTX(c); if (!d_x || !d_y || !d_evk || !d_work || !form_ok(in_form) || !form_ok(out_form) || !dbc_ok(dbc)) return CRC_ERR_INVALID_ARGUMENT;
     if (d_div_ntt && out_form != CRC_NTT) return CRC_ERR_INVALID_ARGUMENT;           // the divisor multiplies slot-wise
     if (B < 0 || zd < 1 || xd < xf || yd < yf || xs < 1 || ys < 1 || xf < 1 || yf < 1) return CRC_ERR_INVALID_ARGUMENT;
     if (!crc_square_pool_relin_supported(c, dbc, xf, yf)) return CRC_ERR_UNSUPPORTED;

@@ -121,7 +121,7 @@ extern "C" int crc_keygen(const crc_ctx *c, uint64_t seed, uint64_t *sk, uint64_
 
 static int gen_evk_impl(const crc_ctx *c, const ChaChaKey &ckey, const uint64_t *sk, int dbc, uint64_t *evk)
 {
-    if (dbc < 1 || dbc > 60) return CRC_ERR_INVALID_ARGUMENT;
+    if (!dbc_ok(dbc)) return CRC_ERR_INVALID_ARGUMENT;
     const int n = c->n, k = c->k;
     Rng r(ckey, 0, 0, (u32)CHACHA_DOM_EVK << 24);
     std::vector<u64> s2((size_t)k * n), e((size_t)k * n);

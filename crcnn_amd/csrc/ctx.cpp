@@ -54,7 +54,8 @@ ModParams make_mod(u64 q, bool no_fold)
     return m;
 }
 
-int evk_digits(u64 q, int dbc) { int L = 0; while (q) { L++; q >>= dbc; } return L; }
+// (0 for a dbc outside 1..63: the loop would never end at dbc <= 0, and a shift by 64 or more is undefined -- x86 masks it to 0)
+int evk_digits(u64 q, int dbc) { if (dbc < 1 || dbc > 63) return 0; int L = 0; while (q) { L++; q >>= dbc; } return L; }
 
 static bool is_prime(u64 n)
 {
@@ -491,6 +492,7 @@ extern "C" int crc_ctx_device(const crc_ctx *c) { return c->device; }
 extern "C" size_t crc_ct_words(const crc_ctx *c, int size) { return (size_t)size * c->k * c->n; }
 extern "C" size_t crc_evk_words(const crc_ctx *c, int dbc)
 {
+    if (!c || !dbc_ok(dbc)) return 0;
     size_t w = 0;
     for (int l = 0; l < c->k; l++) w += (size_t)2 * evk_digits(c->q[l], dbc) * c->k * c->n;
     return w;

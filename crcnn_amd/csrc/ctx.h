@@ -178,3 +178,5 @@ void h_ntt_fwd(const HostNtt &T, u64 *a, int n);      // canonical in/out
 void h_ntt_inv(const HostNtt &T, u64 *a, int n);
 ModParams make_mod(u64 q, bool no_fold = false);
 int  evk_digits(u64 q, int dbc);
+// the decomposition bit counts SEAL accepts (keygenerator.cpp: 1..60); every entry point that takes a dbc refuses the others before it sizes anything
+static inline bool dbc_ok(int dbc) { return dbc >= 1 && dbc <= 60; }

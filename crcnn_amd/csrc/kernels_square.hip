@@ -260,7 +260,7 @@ int k_square(crc_ctx *c, const u64 *x, size_t cnt, u64 *y3, u64 *work, hipStream
 int k_relinearize(crc_ctx *c, const u64 *x3, size_t cnt, const u64 *evk, int dbc, u64 *y, u64 *work, u64 *kp, hipStream_t st, bool out_ntt, bool c2_premul, bool keys_ready)
 {
     if (cnt == 0) return CRC_OK;
-    if (dbc < 1 || dbc > 60) return CRC_ERR_INVALID_ARGUMENT;
+    if (!dbc_ok(dbc)) return CRC_ERR_INVALID_ARGUMENT;
     const size_t n = c->n, k = c->k;
     // key switching over the context's two fp64 primes (kernels_relin64.hip) whenever the inner products fit below p_0 p_1 / 4 -- every parameter set of the reference
     // with 16-bit digits does; tune.relin_path = 1 keeps the transforms over the coefficient moduli (the round-2 path below)

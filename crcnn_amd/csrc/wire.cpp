@@ -90,6 +90,7 @@ extern "C" int crc_params_hash(const crc_ctx *c, uint64_t out[4])
 extern "C" size_t crc_seal_ct_bytes(const crc_ctx *c, int size) { return 32 + 12 + (size_t)size * c->k * (c->n + 1) * 8; }
 extern "C" size_t crc_seal_evk_bytes(const crc_ctx *c, int dbc)
 {
+    if (!c || !dbc_ok(dbc)) return 0;
     size_t b = 32 + 4 + 4 + 4;
     for (int l = 0; l < c->k; l++) b += crc_seal_ct_bytes(c, 2 * evk_digits(c->q[l], dbc));
     return b;
@@ -117,7 +118,7 @@ extern "C" int crc_seal_ct_load(const crc_ctx *c, const void *buf, size_t bytes,
 }
 extern "C" int crc_seal_evk_save(const crc_ctx *c, const uint64_t *h_evk, int dbc, void *buf, size_t cap, size_t *written)
 {
-    if (!c || !h_evk || !buf) return CRC_ERR_INVALID_ARGUMENT;
+    if (!c || !h_evk || !buf || !dbc_ok(dbc)) return CRC_ERR_INVALID_ARGUMENT;
     uint8_t hash[32]; crc_params_hash(c, reinterpret_cast<uint64_t *>(hash));
     Writer w{(uint8_t *)buf, cap};
     w.put(hash, 32); w.i32(dbc); w.i32(1); w.i32(c->k);              // keys_.size() = 1 (count), keys_[0].size() = k
@@ -132,7 +133,7 @@ extern "C" int crc_seal_evk_load(const crc_ctx *c, const void *buf, size_t bytes
     uint8_t hash[32], h[32]; crc_params_hash(c, reinterpret_cast<uint64_t *>(hash));
     Reader r{(const uint8_t *)buf, bytes};
     r.get(h, 32); const int d = r.i32(), dim1 = r.i32();
-    if (!r.ok || std::memcmp(h, hash, 32) || dim1 < 1 || d < 1 || d > 60) return CRC_ERR_INVALID_ARGUMENT;
+    if (!r.ok || std::memcmp(h, hash, 32) || dim1 < 1 || !dbc_ok(d)) return CRC_ERR_INVALID_ARGUMENT;
     if (r.i32() != c->k) return CRC_ERR_INVALID_ARGUMENT;
     u64 *dst = h_evk;
     for (int l = 0; l < c->k; l++) { const int L = evk_digits(c->q[l], d); int sz = 0; if (!ct_load(r, c, hash, dst, 2 * L, &sz) || sz != 2 * L) return CRC_ERR_INVALID_ARGUMENT; dst += (size_t)2 * L * c->k * c->n; }

@@ -98,7 +98,8 @@ int  crc_ctx_k(const crc_ctx *ctx);
 int  crc_ctx_kbsk(const crc_ctx *ctx);                 /* |Bsk| */
 int  crc_ctx_device(const crc_ctx *ctx);
 size_t crc_ct_words(const crc_ctx *ctx, int size);     /* size*k*n */
-size_t crc_evk_words(const crc_ctx *ctx, int dbc);     /* words of an evaluation-key blob: sum_l 2*L_l*k*n */
+size_t crc_evk_words(const crc_ctx *ctx, int dbc);     /* words of an evaluation-key blob: sum_l 2*L_l*k*n (0 for a dbc outside 1..60: every call that
+                                                          takes a dbc refuses those with CRC_ERR_INVALID_ARGUMENT, every size query gives 0) */
 /* named host-side table read-out (tests): "root","const_ratio","delta","upper_half_increment","bsk","bsk_root",
  * "root_powers:<i>","inv_root_powers_div_two:<i>", "f64_primes" (the two fp64 primes of relinearisation's key switching), "sq64_primes" (the fp64 primes that
  * carry the square's auxiliary base: B' = all but the last, m_sk' = the last; empty when the parameters do not fit twelve of them); returns word count */

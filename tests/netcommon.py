@@ -18,6 +18,22 @@ def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a)).hexdigest()          # (the array's own buffer: no second copy of a multi-GB tensor)
 
 
+_M28 = (1 << 28) - 1
+
+
+def limb_extreme(q):
+    """the residue r < q with the largest (r mod 2^28) + (r >> 28): the largest Karatsuba middle term (x0 + x1)(w0 + w1)"""
+    cands = []
+    for x1 in range((q - 1) >> 28, max(((q - 1) >> 28) - 2, -1), -1):
+        cands.append((x1 << 28) | min(_M28, q - 1 - (x1 << 28)))
+    r = max(cands, key=lambda v: (v & _M28) + (v >> 28))
+    # defining property, checked against the bound: no residue has a larger limb sum
+    top = (q - 1) >> 28
+    best = max(((q - 1) & _M28) + top, (_M28 + top - 1) if top else 0)
+    assert r < q and (r & _M28) + (r >> 28) == best
+    return r
+
+
 _PIECES = []
 
 

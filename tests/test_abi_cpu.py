@@ -188,3 +188,46 @@ def test_device_encryptor_noise_thresholds_are_the_reference_law():
         else: po += ob; pe += ex
     if pe > 0: chi += (po - pe) ** 2 / pe
     assert chi < 60, chi                                 # 99.99 % quantile of chi-square with <= 19 degrees of freedom: 51
+
+
+# every public call that takes a decomposition bit count, as a child process runs it (E: a host-only context at (4096, 2), d: the dbc under test)
+_DBC_CALLS = {
+    "crc_evk_words": ("E.L.crc_evk_words(E.c, d)", 0),
+    "crc_seal_evk_bytes": ("E.L.crc_seal_evk_bytes(E.c, d)", 0),
+    "crc_square_relin_work_bytes": ("E.square_relin_work_bytes(4, d)", 0),
+    "crc_square_pool_relin_work_bytes": ("E.square_pool_relin_work_bytes(1, 1, 4, 4, 1, 1, 2, 2, d)", 0),
+    "crc_square_pool_relin_supported": ("int(E.square_pool_relin_supported(2, 2, d))", 0),
+    "crc_seal_evk_save": ("E.L.crc_seal_evk_save(E.c, evk.ctypes.data_as(PU), d, buf.ctypes.data, buf.nbytes, None)", -1),
+    "crc_gen_evk": ("E.gen_evk(7, E.keygen(5)[0], d)", "CrcError"),
+}
+
+
+@pytest.mark.parametrize("dbc", [0, -1, 61, 64])
+def test_invalid_decomposition_bit_counts_are_refused_not_hung(dbc):
+    """A dbc outside SEAL's 1..60 is refused before anything is sized: the size queries return 0, the calls CRC_ERR_INVALID_ARGUMENT.  (evk_digits' loop
+    `while (q) { L++; q >>= dbc; }` never ends at dbc <= 0, nor at dbc = 64 on x86, so each call runs in a child process under a time limit: a regression fails
+    here instead of hanging the suite.)"""
+    import subprocess
+    import sys
+    import time
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    pre = (f"import sys, ctypes; sys.path.insert(0, {root!r}); import numpy as np; import crcnn_amd as ca; PU = ctypes.POINTER(ctypes.c_uint64)\n"
+           f"E = ca.Engine(4096, ca.default_coeff_modulus_128(4096), 1 << 20, device=-1); d = {dbc}\n"
+           "evk = np.zeros(E.L.crc_evk_words(E.c, 16), dtype=np.uint64); buf = np.zeros(E.L.crc_seal_evk_bytes(E.c, 16), dtype=np.uint8)\n"
+           "try:\n    print(repr({}))\nexcept ca.CrcError:\n    print(repr('CrcError'))\n")
+    procs = {name: subprocess.Popen([sys.executable, "-c", pre.replace("{}", call)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+             for name, (call, _) in _DBC_CALLS.items()}
+    deadline = time.monotonic() + 60
+    try:
+        for name, p in procs.items():
+            try:
+                out, err = p.communicate(timeout=max(1.0, deadline - time.monotonic()))
+            except subprocess.TimeoutExpired:
+                pytest.fail(f"{name} with dbc = {dbc} did not return within 60 s")
+            assert p.returncode == 0, (name, err[-2000:])
+            assert out.strip().splitlines()[-1] == repr(_DBC_CALLS[name][1]), (name, dbc, out)
+    finally:
+        for p in procs.values():
+            if p.poll() is None:
+                p.kill()
+                p.wait()

@@ -18,6 +18,8 @@ tile and T <= 12024 with the 6 x 16 tile; past that, and for moduli without a fo
 import numpy as np
 import pytest
 
+from netcommon import limb_extreme
+
 pytestmark = pytest.mark.gpu
 
 M28 = (1 << 28) - 1
@@ -30,19 +32,6 @@ TILES = {8: (7, 3), 16: (2, 5)}                                                #
 
 
 # ---- operands ---------------------------------------------------------------------------------------------------------------------------------------------
-def limb_extreme(q):
-    """the residue r < q with the largest (r mod 2^28) + (r >> 28): the largest Karatsuba middle term (x0 + x1)(w0 + w1)"""
-    cands = []
-    for x1 in range((q - 1) >> 28, max(((q - 1) >> 28) - 2, -1), -1):
-        cands.append((x1 << 28) | min(M28, q - 1 - (x1 << 28)))
-    r = max(cands, key=lambda v: (v & M28) + (v >> 28))
-    # defining property, checked against the bound: no residue has a larger limb sum
-    top = (q - 1) >> 28
-    best = max(((q - 1) & M28) + top, (M28 + top - 1) if top else 0)
-    assert r < q and (r & M28) + (r >> 28) == best
-    return r
-
-
 def balanced_digits(c):
     d = []
     for _ in range(7):

@@ -164,9 +164,9 @@ def test_square_pool_with_one_key_switch_per_window(gs):
 
 
 def test_square_pool_pair_with_all_eight_primes():
-    """the pooled key switch at n = 16384 with all eight primes of coeff_modulus_128(16384) -- D = 32 digit polynomials, a 2 x 2 window: the largest integers
-    the two
-    fp64 primes are asked to hold (2^91 of p_0 p_1 / 2 = 2^92.98) -- against square -> relinearise -> pool one after the other"""
+    """the pooled key switch at n = 16384 with all eight primes of coeff_modulus_128(16384) -- D = 32 digit polynomials, a 2 x 2 window: the parameter set
+    that sits exactly on the pooled predicate's limit (B = 92, |R| up to 2^91 of p_0 p_1 / 2 = 2^92.98) -- against square -> relinearise -> pool one after the
+    other.  Its keys are random, so its integers stay near 2^81; the extreme keys and digits that reach the bound are in test_gpu_relin_bounds.py"""
     import crcnn_amd as ca
     n = 16384
     q = ca.default_coeff_modulus_128(n)
