@@ -166,6 +166,9 @@ def load():
     L.crc_encrypt_dev_noise_thresholds.restype = None; L.crc_encrypt_dev_noise_thresholds.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     L.crc_decrypt_dev_work_bytes.restype = SZ; L.crc_decrypt_dev_work_bytes.argtypes = [VP, SZ, CI, CI]
     L.crc_decrypt_dev.argtypes = [VP, VP, VP, SZ, CI, CI, VP, VP, VP]
+    L.crc_noise_budget_dev_work_bytes.restype = SZ; L.crc_noise_budget_dev_work_bytes.argtypes = [VP, SZ, CI, CI]
+    L.crc_noise_budget_dev.argtypes = [VP, VP, VP, SZ, CI, CI, VP, VP, VP, VP]
+    L.crc_budget_bits_host.argtypes = [VP, PU, SZ, ctypes.POINTER(ctypes.c_int32)]
     L.crc_decode_dev.argtypes = [VP, VP, SZ, VP, VP]
     L.crc_encode_dev_f32.argtypes = [VP, VP, SZ, VP, VP]
     L.crc_encode_dev_f64.argtypes = [VP, VP, SZ, VP, VP]
@@ -535,6 +538,24 @@ class Engine:
 
     def decrypt_dev(self, d_sk, d_ct, count, d_plain, d_work, size=2, in_form=COEFF):
         _chk(self.L.crc_decrypt_dev(self.c, self.p(d_sk), self.p(d_ct), count, size, in_form, self.p(d_plain), self.p(d_work), self.stream), "crc_decrypt_dev")
+
+    # ---- Decryptor::invariant_noise_budget of whole tensors (kernels_budget.hip)
+    def noise_budget_dev_work_bytes(self, count, size=2, in_form=COEFF):
+        return self.L.crc_noise_budget_dev_work_bytes(self.c, count, size, in_form)
+
+    def noise_budget_dev(self, d_sk, d_ct, count, d_bits, d_work, size=2, in_form=COEFF, d_min=None):
+        """d_bits: int32 [count]; d_min (optional): int32 [2] = {smallest budget, index of its first occurrence}"""
+        _chk(self.L.crc_noise_budget_dev(self.c, self.p(d_sk), self.p(d_ct), count, size, in_form, self.p(d_bits), self.p(d_min), self.p(d_work), self.stream),
+             "crc_noise_budget_dev")
+
+    def budget_bits_host(self, v):
+        """v: [..., k, n] coefficient-form residues of c0 + c1 s; the budgets the device routine gives for them, computed on the host (no GPU needed)"""
+        v = np.ascontiguousarray(v, dtype=np.uint64)
+        lead = v.shape[:-2]
+        cnt = int(np.prod(lead)) if lead else 1
+        out = np.zeros(cnt, dtype=np.int32)
+        _chk(self.L.crc_budget_bits_host(self.c, _pu(v), cnt, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), "crc_budget_bits_host")
+        return out.reshape(lead) if lead else int(out[0])
 
     def decode_dev(self, d_plain, count, d_out):
         _chk(self.L.crc_decode_dev(self.c, self.p(d_plain), count, self.p(d_out), self.stream), "crc_decode_dev")

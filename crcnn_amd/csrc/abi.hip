@@ -464,6 +464,24 @@ extern "C" int crc_decrypt_dev(crc_ctx *c, const uint64_t *d_sk, const uint64_t 
     u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
     return k_decrypt(c, d_sk, d_ct, count, size, in_form == CRC_NTT, d_plain, w, S(stream));
 }
+// Decryptor::invariant_noise_budget of every ciphertext of a tensor (kernels_budget.hip)
+extern "C" size_t crc_noise_budget_dev_work_bytes(const crc_ctx *c, size_t count, int size, int in_form)
+{
+    return c && ct_form_ok(in_form) && (size == 2 || size == 3) ? 8 * k_decrypt_work_words(c, count, size, in_form == CRC_NTT) + 256 : 0;
+}
+extern "C" int crc_noise_budget_dev(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_ct, size_t count, int size, int in_form, int32_t *d_bits, int32_t *d_min,
+                                    void *d_work, void *stream)
+{
+    if (!d_sk || !d_ct || !d_bits || !d_work || !ct_form_ok(in_form) || size < 2 || size > 3) return CRC_ERR_INVALID_ARGUMENT;
+    CHECK_CTX(c);
+    u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
+    return k_noise_budget(c, d_sk, d_ct, count, size, in_form == CRC_NTT, d_bits, d_min, w, S(stream));
+}
+extern "C" int crc_budget_bits_host(const crc_ctx *c, const uint64_t *h_v, size_t count, int32_t *h_bits)
+{
+    if (!c || !h_v || !h_bits) return CRC_ERR_INVALID_ARGUMENT;
+    return k_budget_bits_host(c, h_v, count, h_bits);
+}
 extern "C" int crc_decode_dev(crc_ctx *c, const uint64_t *d_plain, size_t count, double *d_out, void *stream)
 {
     CHECK_CTX(c); if (!d_plain || !d_out) return CRC_ERR_INVALID_ARGUMENT;

@@ -60,6 +60,11 @@ int k_decrypt(crc_ctx *c, const u64 *sk, const u64 *ct, size_t cnt, int size, bo
 int k_decrypt_recode(crc_ctx *c, const u64 *sk, const u64 *ct, size_t cnt, bool in_ntt, u64 *compact, float *vals_out, u64 *work, hipStream_t st);
 int k_fra_decode(crc_ctx *c, const u64 *plain, size_t cnt, double *out, hipStream_t st);
 int k_fra_encode(crc_ctx *c, const void *src, int mode, size_t cnt, u64 *plain, float *vals_out, hipStream_t st);
+// V = work [cnt][k][n]: c0 + c1 s (+ c2 s^2) in coefficient form (work: k_decrypt_work_words)
+int k_decrypt_rows(crc_ctx *c, const u64 *sk, const u64 *ct, size_t cnt, int size, bool in_ntt, u64 *work, hipStream_t st);
+// kernels_budget.hip: Decryptor::invariant_noise_budget of every ciphertext of a tensor (work: k_decrypt_work_words)
+int k_noise_budget(crc_ctx *c, const u64 *sk, const u64 *ct, size_t cnt, int size, bool in_ntt, int32_t *bits, int32_t *min_out, u64 *work, hipStream_t st);
+int k_budget_bits_host(const crc_ctx *c, const u64 *h_v, size_t cnt, int32_t *h_bits);
 
 // kernels_mfma.hip: conv / dense multiply-accumulate as an int8 limb GEMM on the matrix cores (operand form CRC_NTTL)
 bool   k_limb_supported(const crc_ctx *c, int T);

@@ -196,7 +196,7 @@ size_t k_decrypt_work_words(const crc_ctx *c, size_t cnt, int size, bool in_ntt)
 }
 
 // V = work [cnt][k][n]: c0 + c1 s (+ c2 s^2) in coefficient form
-static int decrypt_rows(crc_ctx *c, const u64 *sk, const u64 *ct, size_t cnt, int size, bool in_ntt, u64 *work, hipStream_t st)
+int k_decrypt_rows(crc_ctx *c, const u64 *sk, const u64 *ct, size_t cnt, int size, bool in_ntt, u64 *work, hipStream_t st)
 {
     const int n = c->n, k = c->k;
     if (size < 2 || size > 3 || cnt * (size_t)k > 0x7fffffffULL || cnt > 65535u * 4096ull) return CRC_ERR_INVALID_ARGUMENT;
@@ -218,7 +218,7 @@ int k_decrypt(crc_ctx *c, const u64 *sk, const u64 *ct, size_t cnt, int size, bo
     if (cnt == 0) return CRC_OK;
     const int n = c->n, k = c->k;
     int rc;
-    if ((rc = decrypt_rows(c, sk, ct, cnt, size, in_ntt, work, st))) return rc;
+    if ((rc = k_decrypt_rows(c, sk, ct, cnt, size, in_ntt, work, st))) return rc;
     u64 *V = work;
     const DecParams dp = dec_params(c);
     const int threads = n < 256 ? n : 256;
@@ -259,7 +259,7 @@ int k_decrypt_recode(crc_ctx *c, const u64 *sk, const u64 *ct, size_t cnt, bool 
     if (cnt == 0) return CRC_OK;
     if (cnt > 0x7fffffffULL || c->n <= CRC_PLAIN_COMPACT_WORDS) return CRC_ERR_INVALID_ARGUMENT;
     int rc;
-    if ((rc = decrypt_rows(c, sk, ct, cnt, 2, in_ntt, work, st))) return rc;
+    if ((rc = k_decrypt_rows(c, sk, ct, cnt, 2, in_ntt, work, st))) return rc;
     hipLaunchKernelGGL(dec_recode_kernel, dim3((unsigned)cnt), dim3(128), 0, st, work, compact, vals_out, c->d_mods, c->n, dec_params(c));
     HIPCHK(hipGetLastError());
     return CRC_OK;

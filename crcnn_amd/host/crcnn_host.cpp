@@ -482,6 +482,54 @@ ciphertext3D refreshImages(const ciphertext3D &t, int out_form, vector<float> *v
     return out;
 }
 
+// Decryptor::invariant_noise_budget of a whole tensor on the launch stream (crc_noise_budget_dev), in passes of bounded work that share the layers' scratch
+// area.  The result buffer: one {min, first index} pair per pass, then the budgets -- so the pairs and the first ciphertext's budget are one small copy
+struct DeviceBudgets { shared_ptr<DeviceBuffer> buf; size_t passes = 0, pass = 0, count = 0;
+    int32_t *pairs() const { return (int32_t *)buf->ptr; } int32_t *bits() const { return pairs() + 2 * passes; } };
+static DeviceBudgets deviceBudgets(const ciphertext3D &t, const char *who)
+{
+    if (!t.buf || t.count() == 0) throw invalid_argument(string(who) + ": empty tensor");
+    if (t.form != CRC_COEFF && t.form != CRC_NTT) throw invalid_argument(string(who) + ": ciphertext forms only (CRC_COEFF / CRC_NTT)");
+    const uint64_t *d_sk = deviceKey(g_d_sk, g_d_sk_fp, secret_key, "secret key");
+    DeviceBudgets r;
+    r.count = t.count();
+    const size_t one = crc_noise_budget_dev_work_bytes(ctx(), 1, 2, t.form);
+    r.pass = ((size_t)4 << 30) / (one ? one : 1);
+    if (r.pass < 1024) r.pass = 1024;
+    if (r.pass > r.count) r.pass = r.count;
+    r.passes = (r.count + r.pass - 1) / r.pass;
+    ensure(g_scratch, crc_noise_budget_dev_work_bytes(ctx(), r.pass, 2, t.form));
+    r.buf = make_shared<DeviceBuffer>((2 * r.passes + r.count) * sizeof(int32_t));
+    for (size_t o = 0, pi = 0; o < r.count; o += r.pass, pi++) {
+        const size_t c = min(r.pass, r.count - o);
+        chk(crc_noise_budget_dev(ctx(), d_sk, (const uint64_t *)((const char *)t.data() + o * ctBytes()), c, 2, t.form, r.bits() + o, r.pairs() + 2 * pi,
+                                 g_scratch->ptr, stream()), "crc_noise_budget_dev");
+    }
+    return r;
+}
+vector<int> noiseBudgets(const ciphertext3D &t)
+{
+    const DeviceBudgets r = deviceBudgets(t, "noiseBudgets");
+    vector<int32_t> h(r.count);
+    chk(crc_memcpy_d2h(ctx(), h.data(), r.bits(), r.count * sizeof(int32_t), stream()), "crc_memcpy_d2h");
+    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+    return vector<int>(h.begin(), h.end());
+}
+// {min, first index} of the tensor and the budget of its ciphertext 0
+static int minAndFirstBudget(const ciphertext3D &t, const char *who, size_t *where, int *first)
+{
+    const DeviceBudgets r = deviceBudgets(t, who);
+    vector<int32_t> h(2 * r.passes + 1);
+    chk(crc_memcpy_d2h(ctx(), h.data(), r.pairs(), h.size() * sizeof(int32_t), stream()), "crc_memcpy_d2h");
+    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+    int best = h[0]; size_t at = (size_t)h[1];
+    for (size_t pi = 1; pi < r.passes; pi++) if (h[2 * pi] < best) { best = h[2 * pi]; at = pi * r.pass + (size_t)h[2 * pi + 1]; }
+    if (where) *where = at;
+    if (first) *first = h[2 * r.passes];
+    return best;
+}
+int minNoiseBudget(const ciphertext3D &t, size_t *where) { return minAndFirstBudget(t, "minNoiseBudget", where, nullptr); }
+
 static int g_expected_batch = 0;                            // images per Network::forward the caller announced (0: unknown)
 void setExpectedBatch(int images_per_forward) { g_expected_batch = images_per_forward > 0 ? images_per_forward : 0; }
 static bool tooLargeForHbm(size_t weights)
@@ -1018,6 +1066,7 @@ void Network::printNetworkStructure()
 ciphertext3D Network::forward(ciphertext3D input)
 {   // network.cpp:22-47
     const int L = (int)layers.size();
+    if (budget_scope != 0 && budget_scope != 1) throw invalid_argument("Network::budget_scope must be 0 or 1");
     // the planning flag is this forward's only: layers called directly afterwards plan with the default again
     struct Restore { bool &ref; bool old; ~Restore() { ref = old; } } restore_matrix_cores{g_matrix_cores, g_matrix_cores};
     g_matrix_cores = matrix_cores;
@@ -1071,6 +1120,18 @@ ciphertext3D Network::forward(ciphertext3D input)
     if (time_with_events && !event_pool) event_pool = make_shared<EventPool>();
     auto next_event = [&]() { auto &ev = event_pool->ev; if (ev_used == ev.size()) { void *e = nullptr; chk(crc_event_create(ctx(), &e), "crc_event_create");
         ev.push_back(e); } return ev[ev_used++]; };
+    // profile_budget: the layer's output tensor measured on the device, outside the timed region.  A later chunk of the same layer (two-level chunking) only
+    // lowers the minimum; a layer that is repeated after a refresh is measured afresh
+    last_layer_budget_min.assign(profile_budget ? L : 0, -1);
+    last_layer_budget_first.assign(profile_budget ? L : 0, -1);
+    bool later_chunk = false;
+    auto profile = [&](int i, const ciphertext3D &out) {
+        if (!profile_budget || (out.form != CRC_COEFF && out.form != CRC_NTT)) return;
+        int first = -1;
+        const int mn = minAndFirstBudget(out, "Network::forward", nullptr, &first);
+        if (later_chunk && last_layer_budget_min[i] >= 0) { last_layer_budget_min[i] = min(last_layer_budget_min[i], mn); return; }
+        last_layer_budget_min[i] = mn; last_layer_budget_first[i] = first;
+    };
     auto run_layer = [&](int i, const ciphertext3D &in) {
         last_layer_launches[i]++;
         if (time_with_events) {
@@ -1079,12 +1140,14 @@ ciphertext3D Network::forward(ciphertext3D input)
             ciphertext3D out = layers[i]->forward(in);
             chk(crc_event_record(ctx(), e1, stream()), "crc_event_record");
             timed.push_back({i, {e0, e1}});
+            profile(i, out);
             return out;
         }
         auto t0 = chrono::high_resolution_clock::now();
         ciphertext3D out = layers[i]->forward(in);
         chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
         last_layer_ms[i] += chrono::duration<double, milli>(chrono::high_resolution_clock::now() - t0).count();
+        profile(i, out);
         return out;
     };
     auto read_events = [&]() {
@@ -1120,9 +1183,13 @@ ciphertext3D Network::forward(ciphertext3D input)
     if (max_num_of_reencryptions >= 0) {                    // network.cpp:52-96
         int refreshes_left = max_num_of_reencryptions;
         for (int i = 0; i < L; i++) {
-            layers[i]->out_form = CRC_COEFF;
+            // scope 0 reads ciphertext 0 on the host: coefficient form at every boundary.  Scope 1 measures the tensor on the device in the form chosen above
+            // (CRC_COEFF or CRC_NTT: the packed and limb hand-overs are off under max_num_of_reencryptions >= 0)
+            if (budget_scope == 0) layers[i]->out_form = CRC_COEFF;
             ciphertext3D output = run_layer(i, input);
-            if (noiseBudget(output) <= 5) {
+            // (a profiled forward has just measured this tensor: its minimum is reused)
+            const int budget = budget_scope == 0 ? noiseBudget(output) : profile_budget ? last_layer_budget_min[i] : minNoiseBudget(output);
+            if (budget <= 5) {
                 if (refreshes_left <= 0) throw OutOfBudgetException(i - 1);
                 input = run_refresh(input);
                 refreshes_left--;
@@ -1141,6 +1208,7 @@ ciphertext3D Network::forward(ciphertext3D input)
         for (int b0 = 0; b0 < B; b0 += head_chunk) {
             const int Bc = min(head_chunk, B - b0);
             ciphertext3D t = input.images(b0, Bc);
+            later_chunk = b0 > 0;
             for (int i = 0; i < split; i++) {
                 if (i == layer_before_reenc) t = run_refresh(t);
                 OutHint hint(&act_slot[t.buf == act_slot[0] ? 1 : 0]); t = run_layer(i, t);
@@ -1158,6 +1226,7 @@ ciphertext3D Network::forward(ciphertext3D input)
                     "crc_memcpy_d2d");
         }
         chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+        later_chunk = false;
         input = tail_in;
         first = split;
     }

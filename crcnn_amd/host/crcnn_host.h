@@ -90,6 +90,12 @@ ciphertext3D encryptImage(floatCube image);                                     
 std::vector<floatCube> decryptImages(const ciphertext3D &encrypted);                     // one floatCube per image of the batch
 floatCube decryptImage(const ciphertext3D &encrypted_image);                             // globals.cpp:207-230 (B must be 1)
 int noiseBudget(const ciphertext3D &t, size_t index = 0);
+// Decryptor::invariant_noise_budget of EVERY ciphertext of a tensor, on the device and on the launch stream (crc_noise_budget_dev; the device copy of the secret
+// key the refresh keeps, the layers' scratch area): the integers noiseBudget(t, i) gives, in [B][zd][xd][yd] order.  CRC_COEFF and CRC_NTT tensors (an
+// NTT-resident tensor is measured as it stands); std::invalid_argument for the packed and limb forms.  Both calls wait for the stream.
+std::vector<int> noiseBudgets(const ciphertext3D &t);
+// the smallest budget of the tensor and (optionally) the index of the first ciphertext that has it: two integers come back over PCIe, not the tensor
+int minNoiseBudget(const ciphertext3D &t, size_t *where = nullptr);
 // decryptImage -> encryptImage for every image of a batch (the refresh Network::forward runs in front of layer_before_reenc, network.cpp:30-34), on the
 // device and on the launch stream: the tensor may be in coefficient or NTT form, comes back in `out_form` (CRC_COEFF / CRC_NTT) under fresh randomness, and
 // `values` (optional) receives the floats the client saw, [B][zd][xd][yd] -- asking for them makes the call wait for the stream
@@ -305,6 +311,17 @@ public:
     // noise budget of output[0][0][0] is measured (secret key, coefficient form at every boundary); at <= 5 bits the layer's input is
     // refreshed and the layer repeated while refreshes are left, then OutOfBudgetException(i - 1) is thrown.  -1: plain forward.
     int max_num_of_reencryptions = -1;
+    // what the budget-checking forward looks at.  0: noiseBudget(output), ciphertext 0 of image 0, every boundary in coefficient form (the reference ran one
+    // image at a time, so that WAS its whole check).  1: minNoiseBudget of the whole output tensor, every image of the batch, measured on the device in whatever
+    // ciphertext form the layer wrote -- the layers keep CRC_NTT output between linear layers when ntt_resident is set (the packed and limb hand-overs stay
+    // off, as in scope 0).  The output ciphertexts are the same bits in both scopes as long as no refresh is triggered.
+    int budget_scope = 0;
+    // true: every forward (plain or budget-checking) measures the output tensor of every layer on the device and fills last_layer_budget_min (smallest budget
+    // of the tensor; over all chunks under two-level chunking) and last_layer_budget_first (ciphertext 0 of image 0: what noiseBudget(output) gives), one entry
+    // per layer, -1 where the output is in a packed or limb form and cannot be measured (ntt_resident with matrix_cores; switch them off for a full profile).
+    // Costs one stream synchronisation per layer call.
+    bool profile_budget = false;
+    std::vector<int> last_layer_budget_min, last_layer_budget_first;
     std::vector<double> last_layer_ms;                      // per-layer wall milliseconds of the last forward (T_LAYER_i, mainparams.cpp:81)
     // true: last_layer_ms comes from HIP events recorded on the launch stream around every layer call -- no synchronisation between the layers, what a
     // throughput measurement wants (crcnn_amd/host/bench_host.cpp); false: wall clock around Layer::forward + a stream synchronisation, as the reference's

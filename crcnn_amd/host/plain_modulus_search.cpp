@@ -202,6 +202,7 @@ exit_status_forward PlainModulusSearch::testPlainModulus(CnnBuilder &build, uint
     else setParameters(max_poly_modulus, coeff_modulus, plain_modulus, 0);
     Network net = build.buildNetworkByName(model);
     net.max_num_of_reencryptions = max_num_of_reencryptions;             // budget-checking forward (network.cpp:52-96)
+    net.budget_scope = whole_batch_budget ? 1 : 0;
 
     vector<int> picks; vector<ciphertext3D> enc;
     for (int i = 0; i < num_images_to_test; i++) {

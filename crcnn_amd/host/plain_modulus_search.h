@@ -44,6 +44,8 @@ struct PlainModulusSearch {
     std::vector<unsigned char> predicted_labels;             // plaintext-model prediction per image
     unsigned seed = 0;
     int max_num_of_reencryptions = 0;                        // refreshes Network::forward may spend before it gives up (network.cpp:57)
+    // true: the budget-checking forward looks at every output ciphertext of every picked image (Network::budget_scope = 1) instead of ciphertext 0 of image 0
+    bool whole_batch_budget = false;
     std::vector<std::pair<uint64_t, exit_status_forward>> tried;     // every modulus tested, in order
     std::vector<double> test_seconds;                        // wall time of each test
 

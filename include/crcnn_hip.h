@@ -412,6 +412,19 @@ void crc_encrypt_dev_noise_thresholds(uint64_t *h_out19);
 size_t crc_decrypt_dev_work_bytes(const crc_ctx *ctx, size_t count, int size, int in_form);
 int crc_decrypt_dev(crc_ctx *ctx, const uint64_t *d_sk_ntt, const uint64_t *d_ct, size_t count, int size, int in_form, uint64_t *d_plain, void *d_work,
                     void *stream);
+/* Decryptor::invariant_noise_budget (SEAL decryptor.cpp:295-403) on the device, for every ciphertext of a tensor at once: d_sk_ntt and d_ct as crc_decrypt_dev
+ * takes them ([count][size][k][n], `size` 2 or 3, `in_form` CRC_COEFF or CRC_NTT).  Per ciphertext: v = c0 + c1 s (+ c2 s^2) mod q (decryptor.cpp:333-359, the
+ * decryptor's dot product and inverse transforms), per coefficient t v mod q composed from its residues as a multi-word integer and centred against
+ * floor(q/2) (:361-384), the largest significant bit count over the n coefficients (:386-399), and d_bits[m] = max(0, bits(q) - that - 1) (:400-403) -- the
+ * integer crc_noise_budget and the reference report, bit for bit.  d_min (may be NULL) receives {the smallest budget, the index of its first occurrence}: a
+ * caller who only asks whether a tensor still decrypts copies two integers back.  count == 0 is CRC_OK and writes nothing.
+ * d_work: crc_noise_budget_dev_work_bytes(count, size, in_form) (0 for a size or form the call refuses).  Asynchronous on `stream`.
+ * crc_budget_bits_host runs the same per-coefficient routine on the host (any context, device = -1 included) on coefficient-form residues of v,
+ * h_v [count][k][n]: what the device computes behind the inverse transforms, for tests of the multi-word arithmetic that need no GPU. */
+size_t crc_noise_budget_dev_work_bytes(const crc_ctx *ctx, size_t count, int size, int in_form);
+int crc_noise_budget_dev(crc_ctx *ctx, const uint64_t *d_sk_ntt, const uint64_t *d_ct, size_t count, int size, int in_form, int32_t *d_bits /*[count]*/,
+                         int32_t *d_min /*[2]: min, index; may be NULL*/, void *d_work, void *stream);
+int crc_budget_bits_host(const crc_ctx *ctx, const uint64_t *h_v /*[count][k][n], coefficient form*/, size_t count, int32_t *h_bits /*[count]*/);
 /* FractionalEncoder::decode / encode (encoder.cpp:1226-1270, 1013-1076; 64 integer + 32 fractional coefficients, base 3: CrCNN/src/globals.cpp:52) on the
  * device: the doubles crc_decode returns for d_plain [count][n], and the dense plaintexts [count][n] crc_encode_f32 / _f64 make of the values -- the same IEEE
  * operations in the same order as the host encoder, contraction off. */
