@@ -175,6 +175,14 @@ def load():
     L.crc_refresh_dev_work_bytes.restype = SZ; L.crc_refresh_dev_work_bytes.argtypes = [VP, SZ, CI]
     L.crc_refresh_dev.argtypes = [VP, VP, VP, VP, SZ, CI, u64, CI, VP, VP, VP, VP]
     L.crc_refresh_dev_key.argtypes = [VP, VP, VP, VP, SZ, CI, PB, u64, CI, VP, VP, VP, VP]
+    L.crc_encrypt_sym.argtypes = [VP, PU, PU, SZ, u64, CI, PU]
+    L.crc_encrypt_sym_key.argtypes = [VP, PU, PU, SZ, PB, u64, CI, PU]
+    L.crc_encrypt_sym_dev_work_bytes.restype = SZ; L.crc_encrypt_sym_dev_work_bytes.argtypes = [VP, SZ]
+    L.crc_encrypt_sym_dev_forms.argtypes = [VP, VP, VP, SZ, u64, CI, VP, VP, VP]
+    L.crc_encrypt_sym_dev_key_forms.argtypes = [VP, VP, VP, SZ, PB, u64, CI, VP, VP, VP]
+    L.crc_refresh_sym_dev_work_bytes.restype = SZ; L.crc_refresh_sym_dev_work_bytes.argtypes = [VP, SZ, CI]
+    L.crc_refresh_sym_dev.argtypes = [VP, VP, VP, SZ, CI, u64, CI, VP, VP, VP, VP]
+    L.crc_refresh_sym_dev_key.argtypes = [VP, VP, VP, SZ, CI, PB, u64, CI, VP, VP, VP, VP]
     L.crc_comm_unique_id.argtypes = [PB]
     L.crc_comm_create.argtypes = [VP, CI, CI, PB, ctypes.POINTER(VP)]
     L.crc_comm_create_all.argtypes = [ctypes.POINTER(VP), CI, ctypes.POINTER(VP)]
@@ -371,6 +379,18 @@ class Engine:
         cnt = int(np.prod(lead)) if lead else 1
         ct = np.zeros((cnt, 2, self.k, self.n), dtype=np.uint64)
         _chk(self.L.crc_encrypt_key(self.c, _pu(pk), _pu(plains.reshape(cnt, self.n)), cnt, self._key(key), stream_base, _pu(ct)), "crc_encrypt_key")
+        return ct.reshape(lead + (2, self.k, self.n))
+
+    def encrypt_sym(self, sk, plains, seed, out_form=COEFF, key=None, stream_base=0):
+        """encryption under the secret key on the host (crc_encrypt_sym; with `key`: crc_encrypt_sym_key) -- the bits the device entry points give"""
+        plains = np.ascontiguousarray(plains); lead = plains.shape[:-1]
+        cnt = int(np.prod(lead)) if lead else 1
+        ct = np.zeros((cnt, 2, self.k, self.n), dtype=np.uint64)
+        if key is None:
+            _chk(self.L.crc_encrypt_sym(self.c, _pu(sk), _pu(plains.reshape(cnt, self.n)), cnt, seed, out_form, _pu(ct)), "crc_encrypt_sym")
+        else:
+            _chk(self.L.crc_encrypt_sym_key(self.c, _pu(sk), _pu(plains.reshape(cnt, self.n)), cnt, self._key(key), stream_base, out_form, _pu(ct)),
+                 "crc_encrypt_sym_key")
         return ct.reshape(lead + (2, self.k, self.n))
 
     def decrypt(self, sk, cts, size=2):
@@ -574,6 +594,35 @@ class Engine:
         else:
             _chk(self.L.crc_refresh_dev_key(self.c, self.p(d_sk), self.p(d_pk), self.p(d_ct_in), count, in_form, self._key(key), stream_base, out_form,
                                             self.p(d_ct_out), self.p(d_values), self.p(d_work), self.stream), "crc_refresh_dev_key")
+
+    # ---- encryption under the secret key on the device, and the refresh that uses it
+    def encrypt_sym_dev_work_bytes(self, count):
+        return self.L.crc_encrypt_sym_dev_work_bytes(self.c, count)
+
+    def encrypt_sym_dev_forms(self, d_sk, d_plain, count, seed, out_form, d_ct, d_work):
+        _chk(self.L.crc_encrypt_sym_dev_forms(self.c, self.p(d_sk), self.p(d_plain), count, seed, out_form, self.p(d_ct), self.p(d_work), self.stream),
+             "crc_encrypt_sym_dev_forms")
+
+    def encrypt_sym_dev(self, d_sk, d_plain, count, seed, d_ct, d_work):
+        self.encrypt_sym_dev_forms(d_sk, d_plain, count, seed, COEFF, d_ct, d_work)
+
+    def encrypt_sym_dev_key_forms(self, d_sk, d_plain, count, key, stream_base, out_form, d_ct, d_work):
+        _chk(self.L.crc_encrypt_sym_dev_key_forms(self.c, self.p(d_sk), self.p(d_plain), count, self._key(key), stream_base, out_form, self.p(d_ct),
+                                                  self.p(d_work), self.stream), "crc_encrypt_sym_dev_key_forms")
+
+    def encrypt_sym_dev_key(self, d_sk, d_plain, count, key, stream_base, d_ct, d_work):
+        self.encrypt_sym_dev_key_forms(d_sk, d_plain, count, key, stream_base, COEFF, d_ct, d_work)
+
+    def refresh_sym_dev_work_bytes(self, count, in_form=COEFF):
+        return self.L.crc_refresh_sym_dev_work_bytes(self.c, count, in_form)
+
+    def refresh_sym_dev(self, d_sk, d_ct_in, count, seed, d_ct_out, d_work, in_form=COEFF, out_form=COEFF, d_values=None, key=None, stream_base=0):
+        if key is None:
+            _chk(self.L.crc_refresh_sym_dev(self.c, self.p(d_sk), self.p(d_ct_in), count, in_form, seed, out_form, self.p(d_ct_out), self.p(d_values),
+                                            self.p(d_work), self.stream), "crc_refresh_sym_dev")
+        else:
+            _chk(self.L.crc_refresh_sym_dev_key(self.c, self.p(d_sk), self.p(d_ct_in), count, in_form, self._key(key), stream_base, out_form,
+                                                self.p(d_ct_out), self.p(d_values), self.p(d_work), self.stream), "crc_refresh_sym_dev_key")
 
     def encrypt_dev_noise_thresholds(self):
         out = (ctypes.c_uint64 * 19)()

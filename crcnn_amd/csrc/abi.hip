@@ -529,6 +529,53 @@ extern "C" int crc_refresh_dev_key(crc_ctx *c, const uint64_t *d_sk, const uint6
         return CRC_ERR_INVALID_ARGUMENT;
     return refresh_impl(c, d_sk, d_pk, d_ct_in, count, in_form, chacha_load_key(key), stream_base, out_form, d_ct_out, d_values_out, d_work, S(stream));
 }
+// ---- encryption under the secret key and the refresh that uses it (kernels_client.hip: k_encrypt_sym) ----
+extern "C" size_t crc_encrypt_sym_dev_work_bytes(const crc_ctx *c, size_t count) { return c ? 8 * k_encrypt_sym_work_words(c, count) + 256 : 0; }
+extern "C" int crc_encrypt_sym_dev_key_forms(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_plain, size_t count, const uint8_t *key, uint64_t stream_base,
+                                             int out_form, uint64_t *d_ct, void *d_work, void *stream)
+{
+    if (!d_sk || !d_plain || !d_ct || !d_work || !key || !ct_form_ok(out_form)) return CRC_ERR_INVALID_ARGUMENT;
+    CHECK_CTX(c);
+    u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
+    return k_encrypt_sym(c, d_sk, d_plain, count, chacha_load_key(key), stream_base, d_ct, w, S(stream), out_form == CRC_NTT, false);
+}
+extern "C" int crc_encrypt_sym_dev_forms(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_plain, size_t count, uint64_t seed, int out_form, uint64_t *d_ct,
+                                         void *d_work, void *stream)
+{
+    if (!d_sk || !d_plain || !d_ct || !d_work || !ct_form_ok(out_form)) return CRC_ERR_INVALID_ARGUMENT;
+    CHECK_CTX(c);
+    u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
+    return k_encrypt_sym(c, d_sk, d_plain, count, chacha_seed_key(seed), 0, d_ct, w, S(stream), out_form == CRC_NTT, false);
+}
+// work of a secret-key refresh: [compact plaintexts [count][96]][the decryptor's rows, then the encryptor's]
+extern "C" size_t crc_refresh_sym_dev_work_bytes(const crc_ctx *c, size_t count, int in_form)
+{
+    if (!c || !ct_form_ok(in_form)) return 0;
+    const size_t dec = k_decrypt_work_words(c, count, 2, in_form == CRC_NTT), enc = k_encrypt_sym_work_words(c, count);
+    return 8 * (count * (size_t)CRC_PLAIN_COMPACT_WORDS + (dec > enc ? dec : enc)) + 256;
+}
+static int refresh_sym_impl(crc_ctx *c, const u64 *d_sk, const u64 *d_in, size_t count, int in_form, const ChaChaKey &key, u64 stream_base, int out_form,
+                            u64 *d_out, float *d_vals, void *d_work, hipStream_t st)
+{
+    u64 *compact = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255), *w = compact + count * (size_t)CRC_PLAIN_COMPACT_WORDS;
+    // the front end of crc_refresh_dev; the encryptor reads the compact plaintexts for either result form (the NTT form is its definition)
+    RUN(k_decrypt_recode(c, d_sk, d_in, count, in_form == CRC_NTT, compact, d_vals, w, st));
+    return k_encrypt_sym(c, d_sk, compact, count, key, stream_base, d_out, w, st, out_form == CRC_NTT, true);
+}
+extern "C" int crc_refresh_sym_dev(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_ct_in, size_t count, int in_form, uint64_t seed, int out_form,
+                                   uint64_t *d_ct_out, float *d_values_out, void *d_work, void *stream)
+{
+    if (!d_sk || !d_ct_in || !d_ct_out || !d_work || !ct_form_ok(in_form) || !ct_form_ok(out_form)) return CRC_ERR_INVALID_ARGUMENT;
+    CHECK_CTX(c);
+    return refresh_sym_impl(c, d_sk, d_ct_in, count, in_form, chacha_seed_key(seed), 0, out_form, d_ct_out, d_values_out, d_work, S(stream));
+}
+extern "C" int crc_refresh_sym_dev_key(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_ct_in, size_t count, int in_form, const uint8_t *key,
+                                       uint64_t stream_base, int out_form, uint64_t *d_ct_out, float *d_values_out, void *d_work, void *stream)
+{
+    if (!d_sk || !d_ct_in || !d_ct_out || !d_work || !key || !ct_form_ok(in_form) || !ct_form_ok(out_form)) return CRC_ERR_INVALID_ARGUMENT;
+    CHECK_CTX(c);
+    return refresh_sym_impl(c, d_sk, d_ct_in, count, in_form, chacha_load_key(key), stream_base, out_form, d_ct_out, d_values_out, d_work, S(stream));
+}
 extern "C" int crc_square(crc_ctx *c, const uint64_t *d_x, size_t count, uint64_t *d_y3, void *d_work, void *stream)
 {
     CHECK_CTX(c); if (!d_x || !d_y3 || !d_work) return CRC_ERR_INVALID_ARGUMENT;

@@ -71,4 +71,16 @@ inline ChaChaKey chacha_load_key(const uint8_t *key)
 }
 
 // stream domains (nonce word 2 carries the domain in its top byte)
-enum { CHACHA_DOM_KEYGEN = 1, CHACHA_DOM_EVK = 2, CHACHA_DOM_ENC_HOST = 3, CHACHA_DOM_ENC_DEV = 4 };
+enum { CHACHA_DOM_KEYGEN = 1, CHACHA_DOM_EVK = 2, CHACHA_DOM_ENC_HOST = 3, CHACHA_DOM_ENC_DEV = 4, CHACHA_DOM_ENC_SYM = 5 };
+
+// Streams of the secret-key encryptor (crc_encrypt_sym* on the host, enc_sym_sample_kernel on the device: the same bits).  One stream per (ciphertext,
+// coefficient pair), nonce = (stream id low, stream id high, CHACHA_DOM_ENC_SYM << 24 | even coefficient index s); its 32-bit words w[0], w[1], ... run
+// through blocks 0, 1, ... (word j of block b is w[16 b + j]):
+//   w[0..1], w[2..3]      noise magnitude words (low, high half) of coefficients s and s + 1: |e| = the number of the 19 thresholds of the clipped, truncated
+//                         normal (crc_encrypt_dev_noise_thresholds) that the 64-bit word reaches
+//   w[4]                  bit 0 / bit 1: e of coefficient s / s + 1 is negative;  w[5..7] unused
+//   w[8 + 8 i + 4 c .. 11 + 8 i + 4 c]   the 128-bit integer z = w[+0] + 2^32 w[+1] + 2^64 w[+2] + 2^96 w[+3]: the NTT-form residue of c1 under modulus i in
+//                         slot s + c (c = 0, 1) is z mod q_i (within q_i / 2^128 < 2^-66 of uniform)
+// i.e. k / 2 + 1 blocks: one at k = 1, two at k = 2 or 3; modulus i reads the upper half of block i / 2 (i even) or the lower half of block (i + 1) / 2 (i odd)
+#define CHACHA_SYM_BLOCK(i) (((i) + 1) >> 1)
+#define CHACHA_SYM_WORD(i) (((i) & 1) ? 0 : 8)

@@ -201,6 +201,63 @@ extern "C" int crc_encrypt(const crc_ctx *c, const uint64_t *pk, const uint64_t 
     return encrypt_impl(c, pk, plain, count, seed_key(seed), 0, ct);
 }
 
+// BFV encryption under the secret key: c1 = a uniform in R_q, sampled directly as NTT-form residues A; c0 = -(a s) + e + Delta m, i.e. in NTT form
+// NTT(e + Delta m) - A . s -- one forward transform per modulus, no public key.  The NTT-form result is the definition, the coefficient form its inverse
+// transform.  The host twin of enc_sym_sample_kernel (kernels_client.hip): the stream layout of chacha.h, bit for bit
+void k_encrypt_cdt(u64 *out19);                            // (kernels_client.hip: the thresholds of the noise magnitudes)
+static int encrypt_sym_impl(const crc_ctx *c, const uint64_t *sk, const uint64_t *plain, size_t count, const ChaChaKey &key, uint64_t stream_base, int out_form,
+                            uint64_t *ct)
+{
+    const int n = c->n, k = c->k;
+    u64 T[19]; k_encrypt_cdt(T);
+    crc_host::parallel_for(count, 8, [&](size_t m0, size_t m1) {
+    for (size_t m = m0; m < m1; m++) {
+        const u64 sid = stream_base + m;
+        u64 *o = ct + m * 2 * (size_t)k * n; const u64 *pl = plain + m * (size_t)n;
+        for (int s = 0; s < n; s += 2) {
+            const u32 n2 = ((u32)CHACHA_DOM_ENC_SYM << 24) | (u32)s;
+            u32 b[16];
+            chacha20_block(key, 0, (u32)sid, (u32)(sid >> 32), n2, b);
+            int e[2];
+            for (int x = 0; x < 2; x++) {
+                const u64 w = (u64)b[2 * x] | ((u64)b[2 * x + 1] << 32);
+                int a = 0; for (int j = 0; j < 19; j++) a += w >= T[j] ? 1 : 0;
+                e[x] = (b[4] >> x) & 1u ? -a : a;
+            }
+            for (int i = 0; i < k; i++) {
+                const u64 q = c->q[i];
+                if (i & 1) chacha20_block(key, (u32)CHACHA_SYM_BLOCK(i), (u32)sid, (u32)(sid >> 32), n2, b);
+                const u32 *w = b + CHACHA_SYM_WORD(i);
+                for (int x = 0; x < 2; x++) {
+                    const u128 z = (u128)w[4 * x] | ((u128)w[4 * x + 1] << 32) | ((u128)w[4 * x + 2] << 64) | ((u128)w[4 * x + 3] << 96);
+                    o[((size_t)k + i) * n + s + x] = (u64)(z % q);
+                    const u64 er = e[x] >= 0 ? (u64)e[x] : q - (u64)(-e[x]);
+                    o[(size_t)i * n + s + x] = addmod(er, delta_times(c, i, pl[s + x]), q);
+                }
+            }
+        }
+        for (int i = 0; i < k; i++) {
+            const u64 q = c->q[i]; u64 *c0 = o + (size_t)i * n, *c1 = o + ((size_t)k + i) * n; const u64 *sp = sk + (size_t)i * n;
+            h_ntt_fwd(c->tabs[i], c0, n);
+            for (int s = 0; s < n; s++) c0[s] = submod(c0[s], h_mulmod(c1[s], sp[s], q), q);
+            if (out_form == CRC_COEFF) { h_ntt_inv(c->tabs[i], c0, n); h_ntt_inv(c->tabs[i], c1, n); }
+        }
+    }
+    });
+    return CRC_OK;
+}
+extern "C" int crc_encrypt_sym_key(const crc_ctx *c, const uint64_t *sk, const uint64_t *plain, size_t count, const uint8_t *key, uint64_t stream_base, int out_form,
+                                   uint64_t *ct)
+{
+    if (!c || !sk || !plain || !ct || !key || (out_form != CRC_COEFF && out_form != CRC_NTT)) return CRC_ERR_INVALID_ARGUMENT;
+    return encrypt_sym_impl(c, sk, plain, count, load_key(key), stream_base, out_form, ct);
+}
+extern "C" int crc_encrypt_sym(const crc_ctx *c, const uint64_t *sk, const uint64_t *plain, size_t count, uint64_t seed, int out_form, uint64_t *ct)
+{
+    if (!c || !sk || !plain || !ct || (out_form != CRC_COEFF && out_form != CRC_NTT)) return CRC_ERR_INVALID_ARGUMENT;
+    return encrypt_sym_impl(c, sk, plain, count, seed_key(seed), 0, out_form, ct);
+}
+
 extern "C" int crc_decrypt(const crc_ctx *c, const uint64_t *sk, const uint64_t *ct, size_t count, int size, uint64_t *plain)
 {
     if (!c || !sk || !ct || !plain || size < 2) return CRC_ERR_INVALID_ARGUMENT;

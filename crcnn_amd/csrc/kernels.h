@@ -9,6 +9,8 @@ int k_ntt_ct(crc_ctx *c, bool inv, const u64 *src, u64 *dst, size_t count, int s
              const u64 *addend, int add_sign, size_t add_group, int add_mod = 0, int pack_out = 0);
 int k_ntt_ct_fwd_mul(crc_ctx *c, u64 *ct, size_t count, const u64 *w, size_t group, hipStream_t st);
 int k_ntt_ct_fwd_fma(crc_ctx *c, u64 *ct, size_t count, const u64 *u, const u64 *key, hipStream_t st);
+int k_ntt_ct_fwd_negmul(crc_ctx *c, u64 *ct, size_t count, const u64 *sk, hipStream_t st);
+int k_ntt_ct_poly0(crc_ctx *c, const u64 *src, u64 *dst, size_t count, hipStream_t st);
 int k_ntt_ct_addct(crc_ctx *c, const u64 *src, u64 *dst, size_t count, const u64 *addct, int add_size, hipStream_t st);
 int k_ntt_ct_head_add(crc_ctx *c, const u64 *src, int src_size, u64 *dst, size_t count, const u64 *addrows, hipStream_t st);
 int k_spread_ntt(crc_ctx *c, const u64 *src, size_t items, u64 *dst, hipStream_t st);
@@ -54,6 +56,10 @@ struct ChaChaKey;
 int k_encrypt(crc_ctx *c, const u64 *pk, const u64 *plain, size_t cnt, const ChaChaKey &key, u64 stream_base, u64 *ct, u64 *work, hipStream_t st, bool out_ntt = false,
               bool plain_compact = false);
 void k_encrypt_cdt(u64 *out19);                 // the 19 thresholds of the device encryptor's noise magnitudes (tests)
+// encryption under the secret key (sk: [k][n], NTT form); plain: dense rows or compact plaintexts, either result form
+size_t k_encrypt_sym_work_words(const crc_ctx *c, size_t cnt);
+int k_encrypt_sym(crc_ctx *c, const u64 *sk, const u64 *plain, size_t cnt, const ChaChaKey &key, u64 stream_base, u64 *ct, u64 *work, hipStream_t st, bool out_ntt,
+                  bool plain_compact);
 // kernels_decrypt.hip: Decryptor::decrypt and the fractional encoder on the device (the refresh of Network::forward)
 size_t k_decrypt_work_words(const crc_ctx *c, size_t cnt, int size, bool in_ntt);
 int k_decrypt(crc_ctx *c, const u64 *sk, const u64 *ct, size_t cnt, int size, bool in_ntt, u64 *plain, u64 *work, hipStream_t st);

@@ -50,6 +50,10 @@ struct NttArgs {
     const u64 *addend; int add_sign; int rows_per_ct; long long add_group;   // epilogue (inverse only)
     int add_mod;                                               // plaintext index = (ct / add_group) % add_mod (0: no modulo)
     int add_mode, add_size;                                    // 1: delta plaintext on poly 0 (shared by add_group cts); 2: rows of a size-add_size ct array
+    // 1 (with fma_k = the secret key [k][n], NTT form; src = dst = size-2 ciphertexts, src_ct_rows = 2 mod_count, dst_ct_rows = mod_count): the launch
+    // transforms the c0 rows IN PLACE at the ciphertext stride and they leave as  NTT(row) - c1[ct][i] . fma_k[i],  c1 = the NTT-form rows behind them in the
+    // same ciphertext (the secret-key encryptor: NTT(e + Delta m) - A . s).  (Sits in what was padding in front of pp: no other member moves)
+    int fma_neg;
     PlainParams pp;
 };
 
@@ -238,7 +242,13 @@ __global__ void __launch_bounds__(CS == 1 ? 128 : CS == 2 ? 256 : CS == 3 ? 512 
                 v.x += fma_lazy ? mulmod_fold2_lazy(uv.x, kv.x, m) : mulmod(uv.x, kv.x, m); v.y += fma_lazy ? mulmod_fold2_lazy(uv.y, kv.y, m) : mulmod(uv.y,
                     kv.y, m);
             }
+            if (FMA == 3) {     // - c1 . s: the product (below 2q either way) subtracted from 2q, into the value the one reduction takes anyway (as FMA 1)
+                const ulonglong2 av = ld2(src + (size_t)a.mod_count * n + s), kv = ld2(a.fma_k + (size_t)mloc * n + s);
+                v.x += q2 - (fma_lazy ? mulmod_fold2_lazy(av.x, kv.x, m) : mulmod(av.x, kv.x, m));
+                v.y += q2 - (fma_lazy ? mulmod_fold2_lazy(av.y, kv.y, m) : mulmod(av.y, kv.y, m));
+            }
             v.x = reduce_small(v.x, q, q2, rq); v.y = reduce_small(v.y, q, q2, rq);
+            if (FMA == 3) { st2(a.dst + srow * (size_t)n + s, v.x, v.y); continue; }      // (in place at the ciphertext stride)
             if (a.pack_out) st2(dst + s, split28v(v.x), split28v(v.y)); else st2(dst + s, v.x, v.y);
         }
     } else {
@@ -581,7 +591,8 @@ static int ntt_launch(crc_ctx *c, bool inv, NttArgs &a, size_t rows, hipStream_t
             auto kw = uns ? WAVECS(true) : WAVECS(false);
             if (a.fma_u || a.fma_k) {
                 if (inv || a.prologue || a.pack_out) return CRC_ERR_INVALID_ARGUMENT;
-                kw = a.fma_u ? WAVEF(1) : WAVEF(2);
+                if (a.fma_neg && (a.fma_u || a.src != a.dst || a.dst_ct_rows != a.mod_count || a.src_ct_rows != 2 * a.mod_count)) return CRC_ERR_INVALID_ARGUMENT;
+                kw = a.fma_neg ? WAVEF(3) : a.fma_u ? WAVEF(1) : WAVEF(2);
             }
 #undef WAVEF
 #undef WAVECS
@@ -647,6 +658,26 @@ int k_ntt_ct_fwd_fma(crc_ctx *c, u64 *ct, size_t count, const u64 *u, const u64 
     a.src = ct; a.dst = ct; a.mod_base = 0; a.mod_count = c->k; a.rows_per_ct = 2 * c->k; a.add_group = 1; a.add_mode = 1;
     a.fma_u = u; a.fma_k = key;
     return ntt_launch(c, false, a, count * 2 * c->k, st);
+}
+
+// forward NTT in place of the c0 rows of size-2 ciphertexts whose c1 rows are already NTT-form residues: c0 leaves as NTT(c0) - c1 . sk (sk: [k][n], NTT
+// form) -- the secret-key encryptor's last step, k of a ciphertext's 2k rows.  CRC_ERR_UNSUPPORTED where the ring has no wave-local kernel
+int k_ntt_ct_fwd_negmul(crc_ctx *c, u64 *ct, size_t count, const u64 *sk, hipStream_t st)
+{
+    NttArgs a{};
+    a.src = ct; a.dst = ct; a.mod_base = 0; a.mod_count = c->k; a.rows_per_ct = 2 * c->k; a.add_group = 1; a.add_mode = 1;
+    a.src_ct_rows = 2 * c->k; a.dst_ct_rows = c->k;
+    a.fma_k = sk; a.fma_neg = 1;
+    return ntt_launch(c, false, a, count * c->k, st);
+}
+
+// forward NTT of the c0 rows of size-2 ciphertexts src -> dense rows dst [count][k][n] (any ring: the two-pass form of the step above)
+int k_ntt_ct_poly0(crc_ctx *c, const u64 *src, u64 *dst, size_t count, hipStream_t st)
+{
+    NttArgs a{};
+    a.src = src; a.dst = dst; a.mod_base = 0; a.mod_count = c->k; a.rows_per_ct = c->k; a.add_group = 1; a.add_mode = 1;
+    a.src_ct_rows = 2 * c->k; a.dst_ct_rows = c->k;
+    return ntt_launch(c, false, a, count * c->k, st);
 }
 
 // forward NTT in place of size-2 ciphertexts, both polys leaving multiplied by the NTT-form plaintext row w[ct / group] ([.][k][n]) -- the first two of

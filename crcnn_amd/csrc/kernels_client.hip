@@ -212,3 +212,107 @@ int k_encrypt(crc_ctx *c, const u64 *pk, const u64 *plain, size_t cnt, const Cha
     HIPCHK(hipGetLastError());
     return CRC_OK;
 }
+
+// ---- encryption under the secret key ---------------------------------------------------------------------------------------------------------------------------
+// c1 = a uniform in R_q, c0 = -(a s) + e + Delta m: the client that holds s (the refresh of Network::forward, the encryption of an image) needs no public key,
+// no ternary sample and one noise term.  The NTT is a bijection, so a is sampled directly as NTT-form residues A and the NTT-form ciphertext
+//     c1 = A,   c0 = NTT(e + Delta m) - A . s
+// costs one forward transform per modulus (the public-key encryptor: three).  That NTT form is the definition; the coefficient form is its inverse transform.
+// Stream layout: chacha.h (CHACHA_DOM_ENC_SYM); crc_encrypt_sym on the host computes the same bits.
+
+// z = hi 2^64 + lo -> z mod q for ANY 128-bit z.  The generic Barrett path's quotient estimate is off by at most one only for z < 2^64 q: the high word is
+// reduced first there (the folding path takes any z)
+__device__ __forceinline__ u64 mod128_any(u64 lo, u64 hi, const ModParams &m)
+{
+    if (m.fold) return fold128(lo, hi, m);
+    return barrett128(lo, barrett128(hi, 0, m), m);
+}
+
+// One lane = one (ciphertext, coefficient pair), as enc_sample_kernel: ct [count][2][k][n] receives the residues of e + Delta m (+ q mod t on the upper half) in
+// the c0 rows -- coefficient form, transformed next -- and the uniform residues A in the c1 rows -- NTT form, final.  COMPACT as enc_sample_kernel
+template <bool COMPACT>
+__global__ void __launch_bounds__(256) enc_sym_sample_kernel(u64 *ct, const u64 *plain, const ModParams *mods, int n, int k, ChaChaKey key, u64 stream_base,
+                                                             EncCdt cdt, PlainParams pp)
+{
+    const int pairs = n >> 1, pblocks = (pairs + (int)blockDim.x - 1) / (int)blockDim.x;
+    const size_t m = blockIdx.x / pblocks;
+    const int pr = (blockIdx.x % pblocks) * blockDim.x + threadIdx.x;
+    if (pr >= pairs) return;
+    const int s = 2 * pr;
+    const u64 sid = stream_base + m;
+    const u32 n2 = ((u32)CHACHA_DOM_ENC_SYM << 24) | (u32)s;
+    u32 b[16];
+    chacha20_block(key, 0, (u32)sid, (u32)(sid >> 32), n2, b);
+    const int e[2] = {cdt_noise(b[0], b[1], b[4] & 1u, cdt), cdt_noise(b[2], b[3], (b[4] >> 1) & 1u, cdt)};
+    ulonglong2 pl = make_ulonglong2(0, 0);
+    if (!COMPACT) pl = *reinterpret_cast<const ulonglong2 *>(plain + m * (size_t)n + s);
+    else if (s < CRC_PLAIN_COMPACT_LOW) pl = *reinterpret_cast<const ulonglong2 *>(plain + m * (size_t)CRC_PLAIN_COMPACT_WORDS + s);
+    else if (s >= n - CRC_PLAIN_COMPACT_HIGH)
+        pl = *reinterpret_cast<const ulonglong2 *>(plain + m * (size_t)CRC_PLAIN_COMPACT_WORDS + CRC_PLAIN_COMPACT_LOW + (s - (n - CRC_PLAIN_COMPACT_HIGH)));
+    const u64 pc[2] = {pl.x, pl.y};
+    // one modulus: its two uniform residues from the eight keystream words w, e + Delta m beside them
+    auto emit = [&](int i, const u32 *w) {
+        const ModParams md = mods[i];
+        u64 r[2], a[2];
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            a[c] = mod128_any((u64)w[4 * c] | ((u64)w[4 * c + 1] << 32), (u64)w[4 * c + 2] | ((u64)w[4 * c + 3] << 32), md);
+            u64 lo, hi; mul64wide(pp.delta[i], pc[c], lo, hi);
+            if (pc[c] >= pp.threshold) { const u64 l2 = lo + pp.uhi[i]; hi += (l2 < lo); lo = l2; }
+            r[c] = addmod(e[c] >= 0 ? (u64)e[c] : md.q - (u64)(-e[c]), barrett128(lo, hi, md), md.q);
+        }
+        *reinterpret_cast<ulonglong2 *>(ct + ((m * 2) * k + i) * (size_t)n + s) = ulonglong2{r[0], r[1]};
+        *reinterpret_cast<ulonglong2 *>(ct + ((m * 2 + 1) * k + i) * (size_t)n + s) = ulonglong2{a[0], a[1]};
+    };
+    // block by block (the halves are picked with constant indices, so the block stays in registers): block j serves modulus 2j - 1 with its lower half and
+    // modulus 2j with its upper half; block 0 is the one the noise came from
+    emit(0, b + 8);
+    for (int j = 1; 2 * j - 1 < k; j++) {
+        chacha20_block(key, (u32)j, (u32)sid, (u32)(sid >> 32), n2, b);
+        emit(2 * j - 1, b);
+        if (2 * j < k) emit(2 * j, b + 8);
+    }
+}
+
+// rings without the wave-local transform: ct[m][0][i][s] = V[m][i][s] - ct[m][1][i][s] * sk[i][s]   (V = NTT(e + Delta m), dense rows); two slots per thread
+__global__ void __launch_bounds__(256) enc_sym_finish_kernel(const u64 *V, const u64 *sk, u64 *ct, const ModParams *mods, int n, int k)
+{
+    const size_t row = blockIdx.x;                // m*k + i
+    const int i = (int)(row % k);
+    const size_t m = row / k;
+    const ModParams md = mods[i];
+    const u64 *v = V + row * (size_t)n, *key = sk + (size_t)i * n, *c1 = ct + ((m * 2 + 1) * k + i) * (size_t)n;
+    u64 *c0 = ct + ((m * 2) * k + i) * (size_t)n;
+    for (int s = 2 * threadIdx.x; s < n; s += 2 * blockDim.x) {
+        const ulonglong2 vv = *reinterpret_cast<const ulonglong2 *>(v + s), av = *reinterpret_cast<const ulonglong2 *>(c1 + s);
+        const ulonglong2 kv = *reinterpret_cast<const ulonglong2 *>(key + s);
+        *reinterpret_cast<ulonglong2 *>(c0 + s) = ulonglong2{submod(vv.x, mulmod(av.x, kv.x, md), md.q), submod(vv.y, mulmod(av.y, kv.y, md), md.q)};
+    }
+}
+
+size_t k_encrypt_sym_work_words(const crc_ctx *c, size_t cnt) { return cnt * (size_t)c->n * c->k; }      // V of the two-pass form
+
+int k_encrypt_sym(crc_ctx *c, const u64 *sk, const u64 *plain, size_t cnt, const ChaChaKey &key, u64 stream_base, u64 *ct, u64 *work, hipStream_t st, bool out_ntt,
+                  bool plain_compact)
+{
+    if (cnt == 0) return CRC_OK;
+    const int n = c->n, k = c->k;
+    if (plain_compact && n <= CRC_PLAIN_COMPACT_WORDS) return CRC_ERR_INVALID_ARGUMENT;
+    const int pairs = n / 2, threads = pairs < 256 ? pairs : 256, pblocks = (pairs + threads - 1) / threads;
+    if (cnt * (size_t)pblocks > 0x7fffffffULL || cnt * (size_t)k > 0x7fffffffULL) return CRC_ERR_INVALID_ARGUMENT;
+    if (plain_compact)
+        hipLaunchKernelGGL((enc_sym_sample_kernel<true>), dim3((unsigned)(cnt * pblocks)), dim3(threads), 0, st, ct, plain, c->d_mods, n, k, key, stream_base,
+                           enc_cdt(), c->plain);
+    else
+        hipLaunchKernelGGL((enc_sym_sample_kernel<false>), dim3((unsigned)(cnt * pblocks)), dim3(threads), 0, st, ct, plain, c->d_mods, n, k, key, stream_base,
+                           enc_cdt(), c->plain);
+    HIPCHK(hipGetLastError());
+    // (the product joins in the transform's last loop where the ring has the wave-local kernel; else as a pass of its own)
+    int rc = k_ntt_ct_fwd_negmul(c, ct, cnt, sk, st);
+    if (rc == CRC_ERR_UNSUPPORTED) {
+        if ((rc = k_ntt_ct_poly0(c, ct, work, cnt, st))) return rc;
+        hipLaunchKernelGGL(enc_sym_finish_kernel, dim3((unsigned)(cnt * k)), dim3(n / 2 < 256 ? n / 2 : 256), 0, st, work, sk, ct, c->d_mods, n, k);
+        HIPCHK(hipGetLastError());
+    } else if (rc) return rc;
+    return out_ntt ? CRC_OK : k_ntt_ct(c, true, ct, ct, cnt, 2, false, st, nullptr, 0, 0, 0);
+}

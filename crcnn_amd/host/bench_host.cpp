@@ -4,7 +4,7 @@
 // Network::forward runs it.
 //
 //   bench_host model=<name> h5=<model.h5> n=<n> k=<k> t=<t> [q=<p0>,<p1>,..] inputs=<file> distinct=<D> batch=<B> chunk=<C> group=<G> steps=<K> warmup=<W>
-//              outputs=<file> [fuse=1] [matrix_cores=1] [reenc=<layer>]
+//              outputs=<file> [fuse=1] [matrix_cores=1] [reenc=<layer>] [reenc_sym=1]
 //
 // inputs        D encrypted images ([D][784][2][k][n] u64, coefficient form: bench.py's client side writes them), tiled to one launch of C * G images that
 //               every chunk of the batch re-reads (the same bytes per image as a resident batch; bench.py states it under "data")
@@ -18,6 +18,7 @@
 // reenc         >= 0: Network::layer_before_reenc (counted on the unfused network, as network.cpp:23 counts): the client-side refresh of network.cpp:30-34, on
 //               the device (refreshImages), under this process' seeded client keys; its time is reported as T_REENC (mainparams.cpp:81).  The re-encryption is
 //               randomised, so launches are compared through their DECRYPTED outputs
+// reenc_sym     1: Network::reenc_symmetric -- the refresh re-encrypts under the secret key (crc_refresh_sym_dev); default 0: Encryptor::encrypt, as the reference
 // Several ranks (world=<N> rank=<r> rendezvous=<file>; one process per GPU, started by bench.py -- the reference's driver has no counterpart:
 //               mainparams.cpp:64-116 runs one process): rank 0 makes the RCCL rendezvous id (crc_comm_unique_id) and writes it to <file>, every rank joins
 //               (crc_comm_create), the encoded model goes out once with Network::broadcastParameters (the ONE collective of the path), then every rank
@@ -100,7 +101,7 @@ int main(int argc, char **argv)
     const int distinct = (int)geti("distinct", 1), batch = (int)geti("batch", 1), head = (int)geti("chunk", 1), group = max(1, (int)geti("group", 1));
     const int steps = (int)geti("steps", 1), warmup = (int)geti("warmup", 0), fuse = (int)geti("fuse", 1);
     const int reenc = (int)geti("reenc", -1), matrix_cores = (int)geti("matrix_cores", 1);
-    const int sync_each = (int)geti("sync_each", 0);
+    const int sync_each = (int)geti("sync_each", 0), reenc_sym = (int)geti("reenc_sym", 0);
     const string weights_via = a.count("weights_via") ? a["weights_via"] : "broadcast";
     if (weights_via != "broadcast" && weights_via != "floats") { fprintf(stderr, "bench_host: weights_via= broadcast | floats\n"); return 1; }
     const int launch = head * group;                          // images per Network::forward
@@ -169,6 +170,7 @@ int main(int argc, char **argv)
         }
         net.layer_before_reenc = reenc;                       // (before fuse(): the index follows the layers it counts)
         net.matrix_cores = matrix_cores != 0;
+        net.reenc_symmetric = reenc_sym != 0;
         if (fuse) net.fuse();
         if (group > 1) net.head_chunk = head;
         net.time_with_events = true;
@@ -384,6 +386,7 @@ int main(int argc, char **argv)
         for (int i = 0; i < L; i++) printf("%s%lld", i ? ", " : "", calls[i]);
         printf("], \"layer_before_reenc\": %d, \"T_REENC_ms_per_image\": %.4f, \"matrix_cores\": %s", net.layer_before_reenc, t_reenc / images, matrix_cores ? "true" :
             "false");
+        if (reenc_sym) printf(", \"reenc_symmetric\": true");
         if (sync_each) printf(", \"ms_per_image_sync_each\": %.4f", t_sync / images);
         printf(", \"layer_timing\": \"HIP events on the launch stream around every Layer::forward inside the timed region\", ");
         printf("\"hbm\": {\"total_bytes\": %zu, \"free_before_build\": %zu, \"free_after_first_launch\": %zu, \"parameters\": %zu, \"activation_slots\": %zu, "

@@ -403,6 +403,36 @@ ciphertext3D encryptImage(floatCube image)
     for (auto &a : image) for (auto &b : a) for (float v : b) px.push_back(v);
     return encryptPixels(px, zd, xd, yd);
 }
+// encode on the host, encrypt under the secret key on the device (crc_encrypt_sym_dev); one keystream id per ciphertext from the counter encryptImage uses
+ciphertext3D encryptImageSymmetric(const vector<float> &px, int zd, int xd, int yd, int out_form)
+{
+    const size_t per = (size_t)zd * xd * yd;
+    if (zd < 1 || xd < 1 || yd < 1 || px.empty() || px.size() % per) throw invalid_argument("encryptImageSymmetric: pixels must be [B][zd][xd][yd]");
+    if (out_form != CRC_COEFF && out_form != CRC_NTT) throw invalid_argument("encryptImageSymmetric: ciphertext forms only (CRC_COEFF / CRC_NTT)");
+    const int n = N();
+    vector<uint64_t> pl(px.size() * n);
+    chk(crc_encode_f32(ctx(), px.data(), px.size(), pl.data(), nullptr), "crc_encode_f32");
+    DeviceBuffer d_pl(pl.size() * 8), d_work(crc_encrypt_sym_dev_work_bytes(ctx(), px.size()));
+    const uint64_t *d_sk = deviceKey(g_d_sk, g_d_sk_fp, secret_key, "secret key");
+    chk(crc_memcpy_h2d(ctx(), d_pl.ptr, pl.data(), pl.size() * 8, stream()), "crc_memcpy_h2d");
+    ciphertext3D out((int)(px.size() / per), zd, xd, yd, out_form);
+    if (g_det)
+        chk(crc_encrypt_sym_dev_forms(ctx(), d_sk, (const uint64_t *)d_pl.ptr, px.size(), g_det_seed + 1000003 * (g_enc_counter + 1), out_form,
+                                      (uint64_t *)out.buf->ptr, d_work.ptr, stream()), "crc_encrypt_sym_dev_forms");
+    else
+        chk(crc_encrypt_sym_dev_key_forms(ctx(), d_sk, (const uint64_t *)d_pl.ptr, px.size(), g_master_key, g_enc_counter, out_form,
+                                          (uint64_t *)out.buf->ptr, d_work.ptr, stream()), "crc_encrypt_sym_dev_key_forms");
+    g_enc_counter += px.size();
+    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+    return out;
+}
+ciphertext3D encryptImageSymmetric(floatCube image, int out_form)
+{
+    const int zd = (int)image.size(), xd = (int)image[0].size(), yd = (int)image[0][0].size();
+    vector<float> px; px.reserve((size_t)zd * xd * yd);
+    for (auto &a : image) for (auto &b : a) for (float v : b) px.push_back(v);
+    return encryptImageSymmetric(px, zd, xd, yd, out_form);
+}
 vector<floatCube> decryptImages(const ciphertext3D &t)
 {
     const int n = N();
@@ -447,18 +477,20 @@ static shared_ptr<DeviceBuffer> &ensure(shared_ptr<DeviceBuffer> &b, size_t byte
 // The client-side refresh of network.cpp:30-34 -- `floatCube image = decryptImage(input); input = encryptImage(image);` -- for a whole batch on the launch
 // stream (crc_refresh_dev: decrypt, decode, round to float, encode, encrypt; nothing crosses PCIe and the host does not wait).  Passes of bounded size share the
 // layers' scratch area.  Fresh randomness per ciphertext exactly as encryptImage draws it (deterministic only under setDeterministicSeed)
-ciphertext3D refreshImages(const ciphertext3D &t, int out_form, vector<float> *values)
+ciphertext3D refreshImages(const ciphertext3D &t, int out_form, vector<float> *values, bool symmetric)
 {
     if (!t.buf) throw invalid_argument("refreshImages: empty tensor");
     if ((t.form != CRC_COEFF && t.form != CRC_NTT) || (out_form != CRC_COEFF && out_form != CRC_NTT))
         throw invalid_argument("refreshImages: ciphertext forms only (CRC_COEFF / CRC_NTT)");
-    const uint64_t *d_sk = deviceKey(g_d_sk, g_d_sk_fp, secret_key, "secret key"), *d_pk = deviceKey(g_d_pk, g_d_pk_fp, public_key, "public key");
+    const uint64_t *d_sk = deviceKey(g_d_sk, g_d_sk_fp, secret_key, "secret key");
+    const uint64_t *d_pk = symmetric ? nullptr : deviceKey(g_d_pk, g_d_pk_fp, public_key, "public key");
+    auto work_bytes = [&](size_t c) { return symmetric ? crc_refresh_sym_dev_work_bytes(ctx(), c, t.form) : crc_refresh_dev_work_bytes(ctx(), c, t.form); };
     ciphertext3D out(t.B, t.zd, t.xd, t.yd, out_form);
-    const size_t cnt = t.count(), one = crc_refresh_dev_work_bytes(ctx(), 1, t.form);
+    const size_t cnt = t.count(), one = work_bytes(1);
     size_t pass = ((size_t)4 << 30) / (one ? one : 1);
     if (pass < 1024) pass = 1024;
     if (pass > cnt) pass = cnt;
-    ensure(g_scratch, crc_refresh_dev_work_bytes(ctx(), pass, t.form));
+    ensure(g_scratch, work_bytes(pass));
     shared_ptr<DeviceBuffer> d_vals;
     if (values) d_vals = make_shared<DeviceBuffer>(cnt * sizeof(float));
     for (size_t o = 0; o < cnt; o += pass) {
@@ -466,7 +498,13 @@ ciphertext3D refreshImages(const ciphertext3D &t, int out_form, vector<float> *v
         const uint64_t *in = (const uint64_t *)((const char *)t.data() + o * ctBytes());
         uint64_t *dst = (uint64_t *)((char *)out.data() + o * ctBytes());
         float *dv = d_vals ? (float *)d_vals->ptr + o : nullptr;
-        if (g_det)
+        if (symmetric && g_det)
+            chk(crc_refresh_sym_dev(ctx(), d_sk, in, c, t.form, g_det_seed + 1000003 * (g_enc_counter + 1), out_form, dst, dv, g_scratch->ptr, stream()),
+                "crc_refresh_sym_dev");
+        else if (symmetric)
+            chk(crc_refresh_sym_dev_key(ctx(), d_sk, in, c, t.form, g_master_key, g_enc_counter, out_form, dst, dv, g_scratch->ptr, stream()),
+                "crc_refresh_sym_dev_key");
+        else if (g_det)
             chk(crc_refresh_dev(ctx(), d_sk, d_pk, in, c, t.form, g_det_seed + 1000003 * (g_enc_counter + 1), out_form, dst, dv, g_scratch->ptr, stream()),
                 "crc_refresh_dev");
         else
@@ -1158,8 +1196,8 @@ ciphertext3D Network::forward(ciphertext3D input)
     // the refresh (network.cpp:30-34), timed like a layer: T_REENC of mainparams.cpp:81
     last_reenc_values.clear();
     auto refresh_into = [&](const ciphertext3D &in, int of) {
-        if (!keep_reenc_values) return refreshImages(in, of);
-        vector<float> v; ciphertext3D out = refreshImages(in, of, &v);
+        if (!keep_reenc_values) return refreshImages(in, of, nullptr, reenc_symmetric);
+        vector<float> v; ciphertext3D out = refreshImages(in, of, &v, reenc_symmetric);
         last_reenc_values.insert(last_reenc_values.end(), v.begin(), v.end());
         return out;
     };

@@ -99,7 +99,14 @@ int minNoiseBudget(const ciphertext3D &t, size_t *where = nullptr);
 // decryptImage -> encryptImage for every image of a batch (the refresh Network::forward runs in front of layer_before_reenc, network.cpp:30-34), on the
 // device and on the launch stream: the tensor may be in coefficient or NTT form, comes back in `out_form` (CRC_COEFF / CRC_NTT) under fresh randomness, and
 // `values` (optional) receives the floats the client saw, [B][zd][xd][yd] -- asking for them makes the call wait for the stream
-ciphertext3D refreshImages(const ciphertext3D &encrypted, int out_form = CRC_COEFF, std::vector<float> *values = nullptr);
+// `symmetric` (off by default: the reference's refresh calls Encryptor::encrypt): the re-encryption runs under the secret key the refresh holds anyway
+// (crc_refresh_sym_dev: c1 uniform in the NTT domain, one forward transform per modulus instead of three, fresh noise e alone) -- another ciphertext
+// distribution, the same plaintexts and floats; only the cached device copy of the secret key is needed
+ciphertext3D refreshImages(const ciphertext3D &encrypted, int out_form = CRC_COEFF, std::vector<float> *values = nullptr, bool symmetric = false);
+// encryptImage's sibling for a client that holds the secret key: the pixels of one image ([zd][xd][yd]) or of a batch ([B][zd][xd][yd] floats, B = size /
+// (zd xd yd)) encrypted under the secret key on the device (crc_encrypt_sym_dev); same keystream discipline as encryptImage
+ciphertext3D encryptImageSymmetric(const std::vector<float> &pixels, int zd, int xd, int yd, int out_form = CRC_COEFF);
+ciphertext3D encryptImageSymmetric(floatCube image, int out_form = CRC_COEFF);
 
 // ---- layers (CrCNN/src/layer.h:10-31) ------------------------------------------------------------------------------
 class Layer {
@@ -302,6 +309,9 @@ public:
     // network.cpp:23 hard-codes a client-side decrypt/re-encrypt "refresh" before layer 6; it needs the secret key and is off
     // the accelerated path, so it is a setting here: 6 reproduces the committed reference, -1 (default) never refreshes.
     int layer_before_reenc = -1;
+    // true: every refresh of forward() -- the fixed refresh point and the budget-checking forward's -- re-encrypts under the secret key
+    // (refreshImages(..., symmetric = true)).  Off by default: the reference's refresh calls Encryptor::encrypt
+    bool reenc_symmetric = false;
     bool ntt_resident = true;                               // keep tensors in NTT form between linear layers (bit-identical)
     // conv / dense layers with long reductions (>= 8 steps of 32 channels) run as an int8 limb GEMM on the matrix cores (CRC_NTTL, kernels_mfma.hip):
     // exact integer arithmetic, identical ciphertexts, about 4x the vector-ALU kernel.  The conversion of a layer's weights drops their canonical copy:

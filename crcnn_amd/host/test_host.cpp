@@ -106,10 +106,11 @@ static int do_net3(int argc, char **argv)
     return 0;
 }
 
-// netr <model> <h5> <dir> <batch> <layer_before_reenc> <fuse 0|1> <head_chunk>: the reference's published configurations -- Network::forward WITH the client-side
+// netr <model> <h5> <dir> <batch> <layer_before_reenc> <fuse 0|1> <head_chunk> [sym]: the reference's published configurations -- Network::forward WITH the client-side
 // refresh (network.cpp:30-34), now on the device (refreshImages).  <dir> holds params / evk / net_in as for `net` plus sk.u64 and pk.u64 (the client's keys).
 // Writes pre_<i>.u64 for the layers in front of the refresh (layer by layer, coefficient form: the reference's digests; unfused runs only), reenc_floats.f32
-// (the floats the client saw, per image), dec.u64 ([batch][10][n] decrypted output plaintexts), budget.u64, and prints the per-layer times with T_REENC
+// (the floats the client saw, per image), dec.u64 ([batch][10][n] decrypted output plaintexts), budget.u64, and prints the per-layer times with T_REENC.
+// The optional trailing `sym` (or 1) sets Network::reenc_symmetric: the refresh re-encrypts under the secret key
 static int do_netr(int argc, char **argv)
 {
     if (argc < 9) return 1;
@@ -130,6 +131,7 @@ static int do_netr(int argc, char **argv)
         for (int i = 0; i < reenc; i++) { net.getLayer(i)->out_form = CRC_COEFF; t = net.getLayer(i)->forward(t); wr(dir + "/pre_" + to_string(i) + ".u64", t.toHost()); }
     }
     net.ntt_resident = true; net.layer_before_reenc = reenc; net.keep_reenc_values = true; net.head_chunk = head_chunk;
+    if (argc > 9) net.reenc_symmetric = !strcmp(argv[9], "sym") || atoi(argv[9]) != 0;
     if (fuse) { const int removed = net.fuse(); fprintf(stderr, "fused: %d layers removed, %d left, refresh in front of layer %d\n", removed, net.getNumLayers(),
         net.layer_before_reenc); }
     vector<ciphertext3D> imgs(batch, one);
@@ -149,6 +151,86 @@ static int do_netr(int argc, char **argv)
     if (pl2 != pl) { fprintf(stderr, "second forward decrypts differently\n"); return 5; }
     delParameters();
     printf("netr ok\n");
+    return 0;
+}
+
+// encsym <n> <t>: encryptImageSymmetric on a batch (both result forms) decrypts to exactly what encryptImage decrypts to, image by image, under fresh
+// randomness per call
+static int do_encsym(int argc, char **argv)
+{
+    if (argc < 4) return 1;
+    setDeterministicSeed(99);
+    setParameters(atoi(argv[2]), strtoull(argv[3], 0, 0));
+    const int B = 3, zd = 2, xd = 5, yd = 4, per = zd * xd * yd;
+    vector<float> px((size_t)B * per);
+    for (size_t i = 0; i < px.size(); i++) px[i] = (float)((int)((i * 37) % 201) - 100) / 16.0f;
+    ciphertext3D a = encryptImageSymmetric(px, zd, xd, yd), an = encryptImageSymmetric(px, zd, xd, yd, CRC_NTT);
+    if (a.B != B || a.form != CRC_COEFF || an.form != CRC_NTT) { fprintf(stderr, "encryptImageSymmetric: wrong shape or form\n"); return 4; }
+    const vector<u64> ha = a.toHost(), hn = an.toHost();
+    vector<u64> back(hn);
+    { DeviceBuffer d(hn.size() * 8);
+      if (crc_memcpy_h2d(context, d.ptr, hn.data(), hn.size() * 8, nullptr) || crc_ntt_inv(context, (uint64_t *)d.ptr, a.count(), 2, nullptr) ||
+          crc_memcpy_d2h(context, back.data(), d.ptr, hn.size() * 8, nullptr) || crc_stream_sync(context, nullptr)) return 3; }
+    if (back == ha) { fprintf(stderr, "two calls reused their randomness\n"); return 4; }
+    const size_t n = (size_t)crc_ctx_n(context);
+    vector<u64> pa(a.count() * n), pn(pa.size());
+    if (crc_decrypt(context, secret_key.data(), ha.data(), a.count(), 2, pa.data()) || crc_decrypt(context, secret_key.data(), back.data(), a.count(), 2, pn.data())) return 3;
+    if (pa != pn) { fprintf(stderr, "the two forms decrypt differently\n"); return 5; }
+    const vector<floatCube> got = decryptImages(a);
+    for (int b = 0; b < B; b++) {
+        floatCube img(zd, vector<vector<float>>(xd, vector<float>(yd)));
+        for (int z = 0; z < zd; z++) for (int i = 0; i < xd; i++) for (int j = 0; j < yd; j++) img[z][i][j] = px[(size_t)b * per + ((size_t)z * xd + i) * yd + j];
+        const ciphertext3D pk_ct = encryptImage(img);
+        const vector<u64> hp = pk_ct.toHost(); vector<u64> pp(pk_ct.count() * n);
+        if (crc_decrypt(context, secret_key.data(), hp.data(), pk_ct.count(), 2, pp.data())) return 3;
+        if (memcmp(pp.data(), pa.data() + (size_t)b * per * n, pp.size() * 8)) { fprintf(stderr, "image %d: plaintexts differ from encryptImage's\n", b); return 6; }
+        if (decryptImage(pk_ct) != got[b]) { fprintf(stderr, "image %d: floats differ from encryptImage's\n", b); return 6; }
+        if (noiseBudget(a, (size_t)b * per) < noiseBudget(pk_ct, 0)) { fprintf(stderr, "image %d: less budget than a public-key ciphertext\n", b); return 7; }
+    }
+    delParameters();
+    printf("encsym ok\n");
+    return 0;
+}
+
+// budgetsym: the budget-checking forward (Network::max_num_of_reencryptions >= 0, network.cpp:52-96) with Network::reenc_symmetric.  Three Square layers at
+// (4096, t = 2^29) run out of budget on the way, so the forward refreshes and repeats.  With the flag set every refresh must go through the secret key alone:
+// the public key is taken away for that forward, and a public-key refresh would throw.  The result is what the arithmetic gives and what the public-key mode
+// gives, the first refresh sees the same floats in both modes, and the secret-key mode does not need more refreshes
+static int do_budgetsym(int, char **)
+{
+    setDeterministicSeed(123);
+    setParameters(4096, 1ULL << 29);
+    const float v[4] = {0.5f, -0.75f, 1.25f, 0.3f};
+    const ciphertext3D x = encryptImage(floatCube{{{v[0], v[1]}, {v[2], v[3]}}});
+    auto build = [&]() {
+        Network nn;
+        for (int i = 0; i < 3; i++) nn.getLayers().push_back(shared_ptr<Layer>(new SquareLayer("s" + to_string(i), 2)));
+        nn.max_num_of_reencryptions = 6; nn.keep_reenc_values = true;
+        return nn;
+    };
+    Network sym = build(); sym.reenc_symmetric = true;
+    const vector<u64> pk_saved = public_key;
+    public_key.clear();
+    floatCube got;
+    try { got = decryptImage(sym.forward(x)); }
+    catch (const exception &e) { public_key = pk_saved; fprintf(stderr, "budget-checking forward with reenc_symmetric: %s\n", e.what()); return 4; }
+    public_key = pk_saved;
+    if (sym.last_reenc_values.empty() || sym.last_reenc_values.size() % 4) { fprintf(stderr, "no refresh ran: the case does not reach the branch (%zu values)\n",
+        sym.last_reenc_values.size()); return 5; }
+    for (int i = 0; i < 4; i++) {
+        const double want = pow((double)v[i], 8.0), have = got[0][i / 2][i % 2];
+        if (fabs(have - want) > 1e-3) { fprintf(stderr, "value %d: %f, expected %f\n", i, have, want); return 6; }
+    }
+    Network pkn = build();
+    const floatCube ref = decryptImage(pkn.forward(x));
+    for (int i = 0; i < 4; i++) if (fabs(ref[0][i / 2][i % 2] - got[0][i / 2][i % 2]) > 1e-3) { fprintf(stderr, "the two modes decrypt differently at %d\n", i); return 7; }
+    if (pkn.last_reenc_values.size() < 4 || memcmp(pkn.last_reenc_values.data(), sym.last_reenc_values.data(), 4 * sizeof(float))) {
+        fprintf(stderr, "the first refresh saw other floats than the public-key mode's\n"); return 8; }
+    if (sym.last_reenc_values.size() > pkn.last_reenc_values.size()) { fprintf(stderr, "more refreshes with the secret key (%zu values) than with the public key (%zu)\n",
+        sym.last_reenc_values.size(), pkn.last_reenc_values.size()); return 9; }
+    fprintf(stderr, "refreshed values: secret key %zu, public key %zu\n", sym.last_reenc_values.size(), pkn.last_reenc_values.size());
+    delParameters();
+    printf("budgetsym ok\n");
     return 0;
 }
 
@@ -436,6 +518,8 @@ int main(int argc, char **argv)
         if (!strcmp(argv[1], "net")) return do_net(argc, argv);
         if (!strcmp(argv[1], "net3")) return do_net3(argc, argv);
         if (!strcmp(argv[1], "netr")) return do_netr(argc, argv);
+        if (!strcmp(argv[1], "encsym")) return do_encsym(argc, argv);
+        if (!strcmp(argv[1], "budgetsym")) return do_budgetsym(argc, argv);
         if (!strcmp(argv[1], "api")) return do_api(argc, argv);
         if (!strcmp(argv[1], "files")) return do_files(argc, argv);
         if (!strcmp(argv[1], "searchlogic")) return do_searchlogic(argc, argv);

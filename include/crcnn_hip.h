@@ -442,6 +442,51 @@ int crc_refresh_dev_key(crc_ctx *ctx, const uint64_t *d_sk_ntt, const uint64_t *
                         const uint8_t *h_key, uint64_t stream_base, int out_form, uint64_t *d_ct_out, float *d_values_out, void *d_work, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Encryption under the SECRET key (BFV "symmetric" encryption; later SEAL releases ship it as encrypt_symmetric, SEAL 2.3.1 and CrCNN do not): for a
+ * plaintext m, the secret key s, a uniform in R_q and noise e
+ *     c1 = a,    c0 = -(a s) + e + Delta m (+ q mod t on the upper half, as every encryptor here),
+ * so that c0 + c1 s = Delta m + e: the fresh noise is e alone (a public-key ciphertext carries e1 + e2 s - e u).  Whoever holds s -- the client that encrypts
+ * an image, the refresh of Network::forward -- needs no public key, and since the NTT is a bijection a is sampled directly as NTT-form residues A:
+ *     c1_ntt = A,    c0_ntt = NTT(e + Delta m) - A . s_ntt        one forward transform per modulus where Encryptor::encrypt runs three.
+ * THE NTT-FORM RESULT IS THE DEFINITION; out_form CRC_COEFF is crc_ntt_inv of it, so the ciphertexts are a function of (key / seed, stream_base) alone,
+ * whatever the form.  It is a different ciphertext distribution than Encryptor::encrypt's and OPT-IN everywhere: crc_encrypt*, crc_refresh_dev* and the
+ * host classes' defaults are what they were.
+ *
+ * Sampling: ChaCha20, domain CHACHA_DOM_ENC_SYM = 5 (a public-key and a secret-key encryption under the same (key, stream_base) never share a keystream),
+ * one stream per (ciphertext, coefficient pair): nonce = (stream id low, stream id high, 5 << 24 | s), s the even coefficient index, stream id = stream_base +
+ * ciphertext index; block counter 0, 1, ... .  With w[16 b + j] = word j of block b:
+ *   w[0..1] / w[2..3]   64-bit word (low, high half) of the noise magnitude of coefficient s / s + 1: |e| = the number of the 19 thresholds of
+ *                       crc_encrypt_dev_noise_thresholds the word reaches (0..19; the clipped, truncated normal of the reference's encryptor)
+ *   w[4]                bit 0 / bit 1 set: e of coefficient s / s + 1 is negative.   w[5..7] unused
+ *   w[8 + 8 i + 4 c .. 11 + 8 i + 4 c]   z = w[+0] + 2^32 w[+1] + 2^64 w[+2] + 2^96 w[+3];  A[i][s + c] = z mod q_i   (c = 0, 1; modulus index i)
+ * A 128-bit integer reduced modulo q_i < 2^62 is within q_i / 2^128 < 2^-66 statistical distance of uniform on [0, q_i); no rejection, no loop: k / 2 + 1
+ * blocks per coefficient pair (one at k = 1, two at k = 2 and 3).  crc_encrypt_sym[_key] (host, any context) and crc_encrypt_sym_dev[_key]_forms follow this
+ * layout bit for bit: the same (key / seed, stream_base, plaintexts) give the same ciphertexts on the host and on the device.
+ *
+ * SECURITY: as for every *_key entry point, NEVER encrypt two different batches under the same (key, stream_base) -- here a reused stream repeats a AND e and
+ * the difference of the two c0 is Delta (m - m').  The uint64 seed variants expand a PUBLIC seed: tests, bench and goldens only; anyone who knows the seed
+ * recomputes a and e, hence m.  A secret-key ciphertext is decrypted, evaluated on and measured exactly like a public-key one.
+ * ------------------------------------------------------------------------------------------------------------- */
+int crc_encrypt_sym_key(const crc_ctx *ctx, const uint64_t *h_sk_ntt, const uint64_t *h_plain /*[count][n]*/, size_t count, const uint8_t *h_key,
+                        uint64_t stream_base, int out_form, uint64_t *h_ct /*[count][2][k][n]*/);
+int crc_encrypt_sym(const crc_ctx *ctx, const uint64_t *h_sk_ntt, const uint64_t *h_plain, size_t count, uint64_t seed, int out_form, uint64_t *h_ct);
+/* the same on the device: d_sk_ntt [k][n] (the secret key of crc_keygen, NTT form), d_plain [count][n] dense plaintexts, d_ct [count][2][k][n] in out_form.
+ * A sampling kernel writes e + Delta m and A; the transform of the c0 rows subtracts A . s in its last loop where the ring has the wave-local row transform
+ * (n = 2048 .. 16384 with 45- to 57-bit moduli), else a slot-wise pass follows.  d_work: crc_encrypt_sym_dev_work_bytes(count).  Asynchronous on `stream`. */
+size_t crc_encrypt_sym_dev_work_bytes(const crc_ctx *ctx, size_t count);
+int crc_encrypt_sym_dev_key_forms(crc_ctx *ctx, const uint64_t *d_sk_ntt, const uint64_t *d_plain, size_t count, const uint8_t *h_key, uint64_t stream_base,
+                                  int out_form, uint64_t *d_ct, void *d_work, void *stream);
+int crc_encrypt_sym_dev_forms(crc_ctx *ctx, const uint64_t *d_sk_ntt, const uint64_t *d_plain, size_t count, uint64_t seed, int out_form, uint64_t *d_ct,
+                              void *d_work, void *stream);
+/* crc_refresh_dev[_key] with the re-encryption under the secret key the refresh holds anyway (no d_pk): the same decrypt -> decode -> float -> encode front end
+ * and the same d_values_out, then the encryption above.  d_ct_out may be d_ct_in.  d_work: crc_refresh_sym_dev_work_bytes(count, in_form). */
+size_t crc_refresh_sym_dev_work_bytes(const crc_ctx *ctx, size_t count, int in_form);
+int crc_refresh_sym_dev(crc_ctx *ctx, const uint64_t *d_sk_ntt, const uint64_t *d_ct_in, size_t count, int in_form, uint64_t seed, int out_form,
+                        uint64_t *d_ct_out, float *d_values_out, void *d_work, void *stream);
+int crc_refresh_sym_dev_key(crc_ctx *ctx, const uint64_t *d_sk_ntt, const uint64_t *d_ct_in, size_t count, int in_form, const uint8_t *h_key,
+                            uint64_t stream_base, int out_form, uint64_t *d_ct_out, float *d_values_out, void *d_work, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * multi-GPU (SURVEY 8e / 8b `crc_broadcast_weights`).  The reference has no analogue: its only parallelism is the
  * std::thread fan-out inside a layer (convolutionalLayer.cpp:177-191).  Here a batch of encrypted images shards over the
  * GPUs of a node with NO data-path collective; the ONE collective is the start-up broadcast of the encoded (NTT-form)
