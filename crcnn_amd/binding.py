@@ -183,6 +183,14 @@ def load():
     L.crc_refresh_sym_dev_work_bytes.restype = SZ; L.crc_refresh_sym_dev_work_bytes.argtypes = [VP, SZ, CI]
     L.crc_refresh_sym_dev.argtypes = [VP, VP, VP, SZ, CI, u64, CI, VP, VP, VP, VP]
     L.crc_refresh_sym_dev_key.argtypes = [VP, VP, VP, SZ, CI, PB, u64, CI, VP, VP, VP, VP]
+    L.crc_seeded_public_seed.argtypes = [u64, PB]
+    L.crc_encrypt_sym_seeded.argtypes = [VP, PU, PU, SZ, u64, PU]
+    L.crc_encrypt_sym_seeded_key.argtypes = [VP, PU, PU, SZ, PB, PB, u64, PU]
+    L.crc_seeded_expand.argtypes = [VP, PU, SZ, PB, u64, CI, PU]
+    L.crc_seeded_expand_dev.argtypes = [VP, VP, SZ, PB, u64, CI, VP, VP]
+    L.crc_seeded_ct_bytes.restype = SZ; L.crc_seeded_ct_bytes.argtypes = [VP, SZ]
+    L.crc_seeded_ct_save.argtypes = [VP, PU, SZ, PB, u64, VP, SZ, ctypes.POINTER(SZ)]
+    L.crc_seeded_ct_load.argtypes = [VP, VP, SZ, PU, SZ, ctypes.POINTER(SZ), PB, ctypes.POINTER(u64)]
     L.crc_comm_unique_id.argtypes = [PB]
     L.crc_comm_create.argtypes = [VP, CI, CI, PB, ctypes.POINTER(VP)]
     L.crc_comm_create_all.argtypes = [ctypes.POINTER(VP), CI, ctypes.POINTER(VP)]
@@ -393,6 +401,51 @@ class Engine:
                  "crc_encrypt_sym_key")
         return ct.reshape(lead + (2, self.k, self.n))
 
+    # seeded secret-key ciphertexts: the c0 rows [count][k][n] (NTT form) and a PUBLIC 32-byte seed; c1 is regenerated from the seed
+    def seeded_public_seed(self, seed):
+        """the public seed the uint64 seed variant of encrypt_sym_seeded uses (crc_seeded_public_seed)"""
+        buf = (ctypes.c_uint8 * 32)()
+        _chk(self.L.crc_seeded_public_seed(seed, buf), "crc_seeded_public_seed"); return bytes(buf)
+
+    def encrypt_sym_seeded(self, sk, plains, seed, key=None, public_seed=None, stream_base=0):
+        """-> (c0 rows [..][k][n], public seed, stream_base).  With `key` (PRIVATE) and `public_seed`: crc_encrypt_sym_seeded_key; else the deterministic
+        uint64 `seed` variant (tests, bench: NOT secure)"""
+        plains = np.ascontiguousarray(plains); lead = plains.shape[:-1]
+        cnt = int(np.prod(lead)) if lead else 1
+        c0 = np.zeros((cnt, self.k, self.n), dtype=np.uint64)
+        if key is None:
+            _chk(self.L.crc_encrypt_sym_seeded(self.c, _pu(sk), _pu(plains.reshape(cnt, self.n)), cnt, seed, _pu(c0)), "crc_encrypt_sym_seeded")
+            public_seed, stream_base = self.seeded_public_seed(seed), 0
+        else:
+            _chk(self.L.crc_encrypt_sym_seeded_key(self.c, _pu(sk), _pu(plains.reshape(cnt, self.n)), cnt, self._key(key), self._key(public_seed), stream_base,
+                                                   _pu(c0)), "crc_encrypt_sym_seeded_key")
+        return c0.reshape(lead + (self.k, self.n)), bytes(public_seed), stream_base
+
+    def seeded_expand(self, c0, public_seed, stream_base=0, out_form=NTT):
+        """the host twin of seeded_expand_dev: c0 [..][k][n] -> ciphertexts [..][2][k][n]"""
+        c0 = np.ascontiguousarray(c0); lead = c0.shape[:-2]
+        cnt = int(np.prod(lead)) if lead else 1
+        ct = np.zeros((cnt, 2, self.k, self.n), dtype=np.uint64)
+        _chk(self.L.crc_seeded_expand(self.c, _pu(c0), cnt, self._key(public_seed), stream_base, out_form, _pu(ct)), "crc_seeded_expand")
+        return ct.reshape(lead + (2, self.k, self.n))
+
+    def seeded_bytes(self, count):
+        return self.L.crc_seeded_ct_bytes(self.c, count)
+
+    def seeded_save(self, c0, public_seed, stream_base=0):
+        c0 = np.ascontiguousarray(c0); cnt = c0.size // (self.k * self.n)
+        buf = np.zeros(self.seeded_bytes(cnt), dtype=np.uint8); w = SZ(0)
+        _chk(self.L.crc_seeded_ct_save(self.c, _pu(c0), cnt, self._key(public_seed), stream_base, buf.ctypes.data, buf.nbytes, ctypes.byref(w)), "crc_seeded_ct_save")
+        return buf[:w.value].tobytes()
+
+    def seeded_load(self, blob):
+        """-> (c0 [count][k][n], public seed, stream_base); CrcError for a wrong hash, a short buffer or a count that does not match the length"""
+        raw = np.frombuffer(bytes(blob), dtype=np.uint8).copy(); cnt = SZ(0)
+        _chk(self.L.crc_seeded_ct_load(self.c, raw.ctypes.data, raw.nbytes, None, 0, ctypes.byref(cnt), None, None), "crc_seeded_ct_load")
+        c0 = np.zeros((cnt.value, self.k, self.n), dtype=np.uint64); sd = (ctypes.c_uint8 * 32)(); base = u64(0)
+        _chk(self.L.crc_seeded_ct_load(self.c, raw.ctypes.data, raw.nbytes, _pu(c0), cnt.value, ctypes.byref(cnt), sd, ctypes.byref(base)), "crc_seeded_ct_load")
+        return c0, bytes(sd), base.value
+
     def decrypt(self, sk, cts, size=2):
         cts = np.ascontiguousarray(cts); lead = cts.shape[:-3]
         cnt = int(np.prod(lead)) if lead else 1
@@ -596,6 +649,11 @@ class Engine:
                                             self.p(d_ct_out), self.p(d_values), self.p(d_work), self.stream), "crc_refresh_dev_key")
 
     # ---- encryption under the secret key on the device, and the refresh that uses it
+    def seeded_expand_dev(self, d_c0, count, public_seed, stream_base, out_form, d_ct):
+        """packed c0 rows [count][k][n] on the device -> ciphertexts [count][2][k][n] in out_form (crc_seeded_expand_dev; asynchronous, no work buffer)"""
+        _chk(self.L.crc_seeded_expand_dev(self.c, self.p(d_c0), count, self._key(public_seed), stream_base, out_form, self.p(d_ct), self.stream),
+             "crc_seeded_expand_dev")
+
     def encrypt_sym_dev_work_bytes(self, count):
         return self.L.crc_encrypt_sym_dev_work_bytes(self.c, count)
 

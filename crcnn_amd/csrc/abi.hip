@@ -576,6 +576,20 @@ extern "C" int crc_refresh_sym_dev_key(crc_ctx *c, const uint64_t *d_sk, const u
     CHECK_CTX(c);
     return refresh_sym_impl(c, d_sk, d_ct_in, count, in_form, chacha_load_key(key), stream_base, out_form, d_ct_out, d_values_out, d_work, S(stream));
 }
+// ---- seeded secret-key ciphertexts: the packed c0 rows and a public seed -> ordinary ciphertexts (kernels_client.hip: k_seeded_expand) ----
+extern "C" int crc_seeded_expand_dev(crc_ctx *c, const uint64_t *d_c0, size_t count, const uint8_t *seed, uint64_t stream_base, int out_form, uint64_t *d_ct,
+                                     void *stream)
+{
+    if (!d_c0 || !d_ct || !seed || !ct_form_ok(out_form)) return CRC_ERR_INVALID_ARGUMENT;
+    CHECK_CTX(c);
+    if (count == 0) return CRC_OK;
+    // every lane reads its c0 residues from the packed rows and writes them elsewhere: the two ranges must not overlap
+    const size_t row = (size_t)c->n * c->k;
+    if (count > (size_t)-1 / (16 * row)) return CRC_ERR_INVALID_ARGUMENT;
+    const uintptr_t s0 = (uintptr_t)d_c0, s1 = s0 + 8 * count * row, t0 = (uintptr_t)d_ct, t1 = t0 + 16 * count * row;
+    if ((s0 < t1 && t0 < s1) || ((s0 | t0) & 15)) return CRC_ERR_INVALID_ARGUMENT;       // (and the 16-byte accesses need their alignment)
+    return k_seeded_expand(c, d_c0, count, chacha_load_key(seed), stream_base, d_ct, S(stream), out_form == CRC_NTT);
+}
 extern "C" int crc_square(crc_ctx *c, const uint64_t *d_x, size_t count, uint64_t *d_y3, void *d_work, void *stream)
 {
     CHECK_CTX(c); if (!d_x || !d_y3 || !d_work) return CRC_ERR_INVALID_ARGUMENT;

@@ -71,7 +71,8 @@ inline ChaChaKey chacha_load_key(const uint8_t *key)
 }
 
 // stream domains (nonce word 2 carries the domain in its top byte)
-enum { CHACHA_DOM_KEYGEN = 1, CHACHA_DOM_EVK = 2, CHACHA_DOM_ENC_HOST = 3, CHACHA_DOM_ENC_DEV = 4, CHACHA_DOM_ENC_SYM = 5 };
+enum { CHACHA_DOM_KEYGEN = 1, CHACHA_DOM_EVK = 2, CHACHA_DOM_ENC_HOST = 3, CHACHA_DOM_ENC_DEV = 4, CHACHA_DOM_ENC_SYM = 5, CHACHA_DOM_SEEDED_A = 6,
+       CHACHA_DOM_SEEDED_E = 7 };
 
 // Streams of the secret-key encryptor (crc_encrypt_sym* on the host, enc_sym_sample_kernel on the device: the same bits).  One stream per (ciphertext,
 // coefficient pair), nonce = (stream id low, stream id high, CHACHA_DOM_ENC_SYM << 24 | even coefficient index s); its 32-bit words w[0], w[1], ... run
@@ -84,3 +85,15 @@ enum { CHACHA_DOM_KEYGEN = 1, CHACHA_DOM_EVK = 2, CHACHA_DOM_ENC_HOST = 3, CHACH
 // i.e. k / 2 + 1 blocks: one at k = 1, two at k = 2 or 3; modulus i reads the upper half of block i / 2 (i even) or the lower half of block (i + 1) / 2 (i odd)
 #define CHACHA_SYM_BLOCK(i) (((i) + 1) >> 1)
 #define CHACHA_SYM_WORD(i) (((i) & 1) ? 0 : 8)
+
+// Streams of a SEEDED secret-key ciphertext (crc_encrypt_sym_seeded* / crc_seeded_expand on the host, seeded_expand_kernel on the device): c1 = A is a function
+// of a PUBLIC seed, so the client ships the c0 rows and the seed and the server regenerates c1.  Two independent sources, two keys:
+//   mask stream, PUBLIC seed, CHACHA_DOM_SEEDED_A: one stream per (ciphertext, coefficient pair), nonce = (stream id low, stream id high,
+//                         CHACHA_DOM_SEEDED_A << 24 | even slot index s).  Block j serves modulus 2j with its words 0..7 and modulus 2j + 1 with its words 8..15;
+//                         within a half, words 4c .. 4c + 3 are the 128-bit integer z (little-endian words) and A[i][s + c] = z mod q_i, c = 0, 1:
+//                         (k + 1) / 2 blocks per pair, and no word of them depends on anything secret
+//   noise stream, PRIVATE key, CHACHA_DOM_SEEDED_E: one block (counter 0) per (ciphertext, coefficient pair), nonce = (stream id low, stream id high,
+//                         CHACHA_DOM_SEEDED_E << 24 | s); words 0..4 as block 0 of CHACHA_DOM_ENC_SYM (magnitude words of coefficients s, s + 1, sign bits in w[4])
+// The noise has a domain of its own, not CHACHA_DOM_ENC_SYM: one private key serving crc_encrypt_sym_key and the seeded encryptor at the same stream id would
+// give equal e under different, known A -- for equal plaintexts c0 - c0' = -(A - A') s, the secret key.
+#define CHACHA_SEEDED_BLOCKS(k) (((k) + 1) >> 1)

@@ -258,6 +258,92 @@ extern "C" int crc_encrypt_sym(const crc_ctx *c, const uint64_t *sk, const uint6
     return encrypt_sym_impl(c, sk, plain, count, seed_key(seed), 0, out_form, ct);
 }
 
+// Seeded secret-key ciphertexts: c1 = A(public seed, stream id) is regenerated by whoever holds the seed, so only the c0 rows travel.  The mask comes from the
+// PUBLIC seed (CHACHA_DOM_SEEDED_A), the noise from the PRIVATE key (CHACHA_DOM_SEEDED_E): the layouts of chacha.h, bit for bit what seeded_expand_kernel reads.
+// A of one ciphertext, NTT form: a [k][n]
+static void seeded_mask(const crc_ctx *c, const ChaChaKey &seed, u64 sid, u64 *a)
+{
+    const int n = c->n, k = c->k;
+    for (int s = 0; s < n; s += 2) {
+        const u32 n2 = ((u32)CHACHA_DOM_SEEDED_A << 24) | (u32)s;
+        u32 b[16];
+        for (int i = 0; i < k; i++) {
+            if (!(i & 1)) chacha20_block(seed, (u32)(i >> 1), (u32)sid, (u32)(sid >> 32), n2, b);
+            const u32 *w = b + 8 * (i & 1);
+            for (int x = 0; x < 2; x++) {
+                const u128 z = (u128)w[4 * x] | ((u128)w[4 * x + 1] << 32) | ((u128)w[4 * x + 2] << 64) | ((u128)w[4 * x + 3] << 96);
+                a[(size_t)i * n + s + x] = (u64)(z % c->q[i]);
+            }
+        }
+    }
+}
+static int encrypt_sym_seeded_impl(const crc_ctx *c, const uint64_t *sk, const uint64_t *plain, size_t count, const ChaChaKey &key, const ChaChaKey &seed,
+                                   uint64_t stream_base, uint64_t *c0_out)
+{
+    const int n = c->n, k = c->k;
+    u64 T[19]; k_encrypt_cdt(T);
+    crc_host::parallel_for(count, 8, [&](size_t m0, size_t m1) {
+    std::vector<u64> a((size_t)k * n);
+    for (size_t m = m0; m < m1; m++) {
+        const u64 sid = stream_base + m;
+        u64 *o = c0_out + m * (size_t)k * n; const u64 *pl = plain + m * (size_t)n;
+        seeded_mask(c, seed, sid, a.data());
+        for (int s = 0; s < n; s += 2) {
+            u32 b[16];
+            chacha20_block(key, 0, (u32)sid, (u32)(sid >> 32), ((u32)CHACHA_DOM_SEEDED_E << 24) | (u32)s, b);
+            for (int x = 0; x < 2; x++) {
+                const u64 w = (u64)b[2 * x] | ((u64)b[2 * x + 1] << 32);
+                int mag = 0; for (int j = 0; j < 19; j++) mag += w >= T[j] ? 1 : 0;
+                const int e = (b[4] >> x) & 1u ? -mag : mag;
+                for (int i = 0; i < k; i++) {
+                    const u64 q = c->q[i], er = e >= 0 ? (u64)e : q - (u64)(-e);
+                    o[(size_t)i * n + s + x] = addmod(er, delta_times(c, i, pl[s + x]), q);
+                }
+            }
+        }
+        for (int i = 0; i < k; i++) {
+            const u64 q = c->q[i]; u64 *c0 = o + (size_t)i * n; const u64 *c1 = a.data() + (size_t)i * n, *sp = sk + (size_t)i * n;
+            h_ntt_fwd(c->tabs[i], c0, n);
+            for (int s = 0; s < n; s++) c0[s] = submod(c0[s], h_mulmod(c1[s], sp[s], q), q);
+        }
+    }
+    });
+    return CRC_OK;
+}
+extern "C" int crc_seeded_public_seed(uint64_t seed, uint8_t *h_seed)
+{
+    if (!h_seed) return CRC_ERR_INVALID_ARGUMENT;
+    const ChaChaKey k = seed_key(~seed);
+    for (int i = 0; i < 8; i++) for (int b = 0; b < 4; b++) h_seed[4 * i + b] = (uint8_t)(k.w[i] >> (8 * b));
+    return CRC_OK;
+}
+extern "C" int crc_encrypt_sym_seeded_key(const crc_ctx *c, const uint64_t *sk, const uint64_t *plain, size_t count, const uint8_t *key, const uint8_t *seed,
+                                          uint64_t stream_base, uint64_t *c0)
+{
+    if (!c || !sk || !plain || !c0 || !key || !seed || !std::memcmp(key, seed, CRC_KEY_BYTES)) return CRC_ERR_INVALID_ARGUMENT;
+    return encrypt_sym_seeded_impl(c, sk, plain, count, load_key(key), load_key(seed), stream_base, c0);
+}
+extern "C" int crc_encrypt_sym_seeded(const crc_ctx *c, const uint64_t *sk, const uint64_t *plain, size_t count, uint64_t seed, uint64_t *c0)
+{
+    if (!c || !sk || !plain || !c0) return CRC_ERR_INVALID_ARGUMENT;
+    return encrypt_sym_seeded_impl(c, sk, plain, count, seed_key(seed), seed_key(~seed), 0, c0);
+}
+extern "C" int crc_seeded_expand(const crc_ctx *c, const uint64_t *c0, size_t count, const uint8_t *seed, uint64_t stream_base, int out_form, uint64_t *ct)
+{
+    if (!c || !c0 || !ct || !seed || (out_form != CRC_COEFF && out_form != CRC_NTT)) return CRC_ERR_INVALID_ARGUMENT;
+    const int n = c->n, k = c->k;
+    const ChaChaKey sd = load_key(seed);
+    crc_host::parallel_for(count, 8, [&](size_t m0, size_t m1) {
+    for (size_t m = m0; m < m1; m++) {
+        u64 *o = ct + m * 2 * (size_t)k * n;
+        std::memcpy(o, c0 + m * (size_t)k * n, 8 * (size_t)k * n);
+        seeded_mask(c, sd, stream_base + m, o + (size_t)k * n);
+        if (out_form == CRC_COEFF) for (int i = 0; i < 2 * k; i++) h_ntt_inv(c->tabs[i % k], o + (size_t)i * n, n);
+    }
+    });
+    return CRC_OK;
+}
+
 extern "C" int crc_decrypt(const crc_ctx *c, const uint64_t *sk, const uint64_t *ct, size_t count, int size, uint64_t *plain)
 {
     if (!c || !sk || !ct || !plain || size < 2) return CRC_ERR_INVALID_ARGUMENT;

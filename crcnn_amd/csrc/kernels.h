@@ -60,6 +60,8 @@ void k_encrypt_cdt(u64 *out19);                 // the 19 thresholds of the devi
 size_t k_encrypt_sym_work_words(const crc_ctx *c, size_t cnt);
 int k_encrypt_sym(crc_ctx *c, const u64 *sk, const u64 *plain, size_t cnt, const ChaChaKey &key, u64 stream_base, u64 *ct, u64 *work, hipStream_t st, bool out_ntt,
                   bool plain_compact);
+// seeded secret-key ciphertexts: c0 [cnt][k][n] packed NTT-form rows -> ct [cnt][2][k][n], c1 = A(seed, stream_base + m) regenerated (chacha.h)
+int k_seeded_expand(crc_ctx *c, const u64 *c0, size_t cnt, const ChaChaKey &seed, u64 stream_base, u64 *ct, hipStream_t st, bool out_ntt);
 // kernels_decrypt.hip: Decryptor::decrypt and the fractional encoder on the device (the refresh of Network::forward)
 size_t k_decrypt_work_words(const crc_ctx *c, size_t cnt, int size, bool in_ntt);
 int k_decrypt(crc_ctx *c, const u64 *sk, const u64 *ct, size_t cnt, int size, bool in_ntt, u64 *plain, u64 *work, hipStream_t st);

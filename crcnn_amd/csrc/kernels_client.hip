@@ -316,3 +316,47 @@ int k_encrypt_sym(crc_ctx *c, const u64 *sk, const u64 *plain, size_t cnt, const
     } else if (rc) return rc;
     return out_ntt ? CRC_OK : k_ntt_ct(c, true, ct, ct, cnt, 2, false, st, nullptr, 0, 0, 0);
 }
+
+// ---- seeded secret-key ciphertexts -----------------------------------------------------------------------------------------------------------------------------
+// c1 = A of a secret-key ciphertext is a function of a PUBLIC seed alone (chacha.h, CHACHA_DOM_SEEDED_A), so a client ships the c0 rows and 32 bytes and the
+// server regenerates c1 here: half the bytes over the link.  One lane = one (ciphertext, coefficient pair), as enc_sym_sample_kernel: per modulus it copies the
+// pair's c0 residues from the packed rows [count][k][n] into the ciphertext [count][2][k][n] and stores the two residues of A beside them.  The keystream is
+// walked block by block with constant indices into the block (it stays in registers): block j serves modulus 2j with its lower half, modulus 2j + 1 with its
+// upper half.  crc_seeded_expand on the host computes the same bits.
+__global__ void __launch_bounds__(256) seeded_expand_kernel(u64 *ct, const u64 *c0, const ModParams *mods, int n, int k, ChaChaKey seed, u64 stream_base)
+{
+    const int pairs = n >> 1, pblocks = (pairs + (int)blockDim.x - 1) / (int)blockDim.x;
+    const size_t m = blockIdx.x / pblocks;
+    const int pr = (blockIdx.x % pblocks) * blockDim.x + threadIdx.x;
+    if (pr >= pairs) return;
+    const int s = 2 * pr;
+    const u64 sid = stream_base + m;
+    const u32 n2 = ((u32)CHACHA_DOM_SEEDED_A << 24) | (u32)s;
+    u32 b[16];
+    auto emit = [&](int i, const u32 *w) {
+        const ModParams md = mods[i];
+        const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(c0 + (m * k + i) * (size_t)n + s);
+        u64 a[2];
+#pragma unroll
+        for (int c = 0; c < 2; c++) a[c] = mod128_any((u64)w[4 * c] | ((u64)w[4 * c + 1] << 32), (u64)w[4 * c + 2] | ((u64)w[4 * c + 3] << 32), md);
+        *reinterpret_cast<ulonglong2 *>(ct + ((m * 2) * k + i) * (size_t)n + s) = v;
+        *reinterpret_cast<ulonglong2 *>(ct + ((m * 2 + 1) * k + i) * (size_t)n + s) = ulonglong2{a[0], a[1]};
+    };
+    for (int j = 0; 2 * j < k; j++) {
+        chacha20_block(seed, (u32)j, (u32)sid, (u32)(sid >> 32), n2, b);
+        emit(2 * j, b);
+        if (2 * j + 1 < k) emit(2 * j + 1, b + 8);
+    }
+}
+
+int k_seeded_expand(crc_ctx *c, const u64 *c0, size_t cnt, const ChaChaKey &seed, u64 stream_base, u64 *ct, hipStream_t st, bool out_ntt)
+{
+    if (cnt == 0) return CRC_OK;
+    const int n = c->n, k = c->k;
+    const int pairs = n / 2, threads = pairs < 256 ? pairs : 256, pblocks = (pairs + threads - 1) / threads;
+    if (cnt * (size_t)pblocks > 0x7fffffffULL || cnt * (size_t)k > 0x7fffffffULL) return CRC_ERR_INVALID_ARGUMENT;
+    hipLaunchKernelGGL(seeded_expand_kernel, dim3((unsigned)(cnt * pblocks)), dim3(threads), 0, st, ct, c0, c->d_mods, n, k, seed, stream_base);
+    HIPCHK(hipGetLastError());
+    // the NTT form is the definition; the coefficient form is the inverse transform of both polynomials, in place
+    return out_ntt ? CRC_OK : k_ntt_ct(c, true, ct, ct, cnt, 2, false, st, nullptr, 0, 0, 0);
+}

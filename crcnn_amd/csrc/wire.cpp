@@ -176,3 +176,50 @@ extern "C" int crc_seal_sk_load(const crc_ctx *c, const void *buf, size_t bytes,
     if (r.i32() != c->n + 1 || r.i32() != c->k * 64 || !r.ok || std::memcmp(h, hash, 32)) return CRC_ERR_INVALID_ARGUMENT;
     return get_rows(r, c, h_sk, (size_t)c->k) ? CRC_OK : CRC_ERR_INVALID_ARGUMENT;
 }
+
+// Seeded secret-key ciphertexts (crc_encrypt_sym_seeded*): a container of the engine's own -- SEAL 2.3.1 has no seeded form, there is nothing to interchange
+// with.  Little-endian:
+//   offset  0  8 bytes   magic "CRCSEED\0"
+//           8  uint32    version = 1
+//          12  uint32    0 (reserved)
+//          16  32 bytes  crc_params_hash (SEAL's SHA3-256 parameter hash, as every object above)
+//          48  uint64    count
+//          56  uint64    stream_base
+//          64  32 bytes  the PUBLIC seed
+//          96  count * k * n uint64   the c0 rows [count][k][n], NTT form (no pad words)
+namespace {
+const char kSeededMagic[8] = {'C', 'R', 'C', 'S', 'E', 'E', 'D', 0};
+const size_t kSeededHeader = 96;
+}
+extern "C" size_t crc_seeded_ct_bytes(const crc_ctx *c, size_t count) { return c ? kSeededHeader + count * (size_t)c->k * c->n * 8 : 0; }
+extern "C" int crc_seeded_ct_save(const crc_ctx *c, const uint64_t *h_c0, size_t count, const uint8_t *h_seed, uint64_t stream_base, void *buf, size_t cap,
+                                  size_t *written)
+{
+    if (!c || (!h_c0 && count) || !h_seed || !buf) return CRC_ERR_INVALID_ARGUMENT;
+    const size_t need = crc_seeded_ct_bytes(c, count);
+    if (written) *written = need;
+    if (cap < need) return CRC_ERR_INVALID_ARGUMENT;
+    uint8_t hash[32]; crc_params_hash(c, reinterpret_cast<uint64_t *>(hash));
+    Writer w{(uint8_t *)buf, cap};
+    const u64 cnt = count; const uint32_t version = 1, zero = 0;
+    w.put(kSeededMagic, 8); w.put(&version, 4); w.put(&zero, 4); w.put(hash, 32); w.put(&cnt, 8); w.put(&stream_base, 8); w.put(h_seed, 32);
+    w.put(h_c0, need - kSeededHeader);
+    return w.ok ? CRC_OK : CRC_ERR_INVALID_ARGUMENT;
+}
+extern "C" int crc_seeded_ct_load(const crc_ctx *c, const void *buf, size_t bytes, uint64_t *h_c0, size_t max_count, size_t *count, uint8_t *h_seed,
+                                  uint64_t *stream_base)
+{
+    if (!c || !buf || !count) return CRC_ERR_INVALID_ARGUMENT;
+    uint8_t hash[32], h[32], seed[32]; char magic[8]; uint32_t version = 0, reserved = 1; u64 cnt = 0, base = 0;
+    crc_params_hash(c, reinterpret_cast<uint64_t *>(hash));
+    Reader r{(const uint8_t *)buf, bytes};
+    r.get(magic, 8); r.get(&version, 4); r.get(&reserved, 4); r.get(h, 32); r.get(&cnt, 8); r.get(&base, 8); r.get(seed, 32);
+    if (!r.ok || std::memcmp(magic, kSeededMagic, 8) || version != 1 || reserved != 0 || std::memcmp(h, hash, 32)) return CRC_ERR_INVALID_ARGUMENT;
+    const size_t row = (size_t)c->k * c->n * 8;
+    if (cnt > (bytes - kSeededHeader) / row || bytes != kSeededHeader + (size_t)cnt * row) return CRC_ERR_INVALID_ARGUMENT;    // short, or longer than its count says
+    if (!h_c0) { *count = (size_t)cnt; return CRC_OK; }                              // size query: nothing else is written
+    if (cnt > max_count || !h_seed || !stream_base) return CRC_ERR_INVALID_ARGUMENT;
+    *count = (size_t)cnt; *stream_base = base; std::memcpy(h_seed, seed, 32);
+    r.get(h_c0, (size_t)cnt * row);
+    return CRC_OK;
+}

@@ -30,7 +30,7 @@
 // sync_each     1: the stream is synchronised after every Network::forward and the wall time of forward + wait is reported (ms_per_image_sync_each): with
 //               batch=1 chunk=1 the single-image latency of mainparams.cpp:85-112's usage (one image at a time)
 // launch_check  1: rendezvous through the file only (no GPU, no RCCL): the CPU-side test of the launcher
-// stream_inputs ciphertext|plaintext: the input launch is not resident -- see stream_inputs below
+// stream_inputs ciphertext|plaintext|seeded (or a comma list of them): the input launch is not resident -- see stream_inputs below
 // Prints ONE JSON line on stdout.
 #include "crcnn_host.h"
 #include <chrono>
@@ -107,16 +107,28 @@ int main(int argc, char **argv)
     const int launch = head * group;                          // images per Network::forward
     // stream_inputs: after the resident measurement, `stream_steps` more passes in which every launch's images come over PCIe while the previous launch is
     // evaluated (mainparams.cpp:85-112 encrypts, evaluates and decrypts image after image).  ciphertext: 784 ciphertexts per image from page-locked host
-    // memory; plaintext: the 784 pixel plaintexts per image (n words each) and Encryptor::encrypt on the device (crc_encrypt_dev_forms) inside the pipeline
+    // memory; plaintext: the 784 pixel plaintexts per image (n words each) and Encryptor::encrypt on the device (crc_encrypt_dev_forms) inside the pipeline;
+    // seeded: the images of plain_inputs= encrypted under the secret key into SEEDED form on the host before the timed region (crc_encrypt_sym_seeded: the c0
+    // rows and a public seed, half a ciphertext's bytes), the packed rows uploaded per launch and expanded on the device (expandSeeded) in front of the network
     const string stream_mode = a.count("stream_inputs") ? a["stream_inputs"] : "none";
     const int stream_steps = (int)geti("stream_steps", 1);
     try {
         if (n < 1 || k < 1 || launch < 1 || batch < launch || distinct < 1 || distinct > launch || steps < 1)
             throw invalid_argument("bad sizes (need 1 <= distinct <= chunk * group <= batch)");
         {
-            bool known = false;
-            for (const char *m : {"none", "ciphertext", "plaintext", "ciphertext,plaintext", "plaintext,ciphertext"}) known = known || stream_mode == m;
-            if (!known) throw invalid_argument("stream_inputs= none | ciphertext | plaintext | ciphertext,plaintext");
+            bool known = stream_mode == "none";
+            if (!known) {                                     // any comma list of the three modes, each at most once
+                known = true; int seen[3] = {0, 0, 0};
+                for (size_t p0 = 0; p0 <= stream_mode.size();) {
+                    const size_t c = stream_mode.find(',', p0);
+                    const string m = stream_mode.substr(p0, c == string::npos ? c : c - p0);
+                    const int w = m == "ciphertext" ? 0 : m == "plaintext" ? 1 : m == "seeded" ? 2 : -1;
+                    if (w < 0 || seen[w]++) known = false;
+                    if (c == string::npos) break;
+                    p0 = c + 1;
+                }
+            }
+            if (!known) throw invalid_argument("stream_inputs= none | a comma list of ciphertext, plaintext, seeded");
         }
         uint64_t q[16];
         // explicit coefficient modulus (q=<prime>,<prime>,...); default: the first k primes of coeff_modulus_128(n)
@@ -258,23 +270,37 @@ int main(int argc, char **argv)
             modes.push_back(stream_mode.substr(p0, c == string::npos ? c : c - p0)); if (c == string::npos) break; p0 = c + 1; } }
         for (const string &mode : modes) {
             double st_dt = 0.0, st_images = 0.0, st_bytes = 0.0; bool same = true;
-            const bool pt = mode == "plaintext";
-            const size_t unit = pt ? (size_t)784 * n : imgw;                       // words uploaded per image
+            const bool pt = mode == "plaintext", sd = mode == "seeded";
+            const size_t unit = pt ? (size_t)784 * n : sd ? (size_t)784 * k * n : imgw;      // words uploaded per image
+            uint8_t sd_seed[CRC_KEY_BYTES] = {0};
+            bool dec_same = true;
             uint64_t *pinned = nullptr;
             if (crc_host_alloc(context, (size_t)distinct * unit * 8, (void **)&pinned))
                 throw runtime_error("crc_host_alloc: " + to_string((size_t)distinct * unit * 8) + " bytes of page-locked host memory for the streamed inputs");
             if (pt) {
                 ifstream f(need("plain_inputs"), ios::binary); if (!f) throw runtime_error("cannot open plain_inputs");
                 f.read((char *)pinned, (streamsize)((size_t)distinct * unit * 8)); if (!f) throw runtime_error("short read: plain_inputs");
+            } else if (sd) {
+                // the client side of this mode, before the timed region: the distinct images' pixel plaintexts under the secret key of the seeded client keys,
+                // straight into the page-locked rows (stream ids 0 .. distinct * 784 - 1 under one public seed)
+                vector<uint64_t> pl((size_t)distinct * 784 * n);
+                ifstream f(need("plain_inputs"), ios::binary); if (!f) throw runtime_error("cannot open plain_inputs");
+                f.read((char *)pl.data(), (streamsize)(pl.size() * 8)); if (!f) throw runtime_error("short read: plain_inputs");
+                const uint64_t client_seed = 0x5eeded00 + (uint64_t)geti("key_seed", 2024);
+                if (crc_seeded_public_seed(client_seed, sd_seed) ||
+                    crc_encrypt_sym_seeded(context, secret_key.data(), pl.data(), (size_t)distinct * 784, client_seed, pinned))
+                    throw runtime_error("crc_encrypt_sym_seeded");
             } else {
                 memcpy(pinned, h.data(), (size_t)distinct * unit * 8);
                 h.clear(); h.shrink_to_fit();                      // one copy of the distinct images in host memory, not two (ciphertext mode runs once)
             }
             // (plaintext mode: the device encryptor leaves NTT-form ciphertexts -- crc_encrypt_dev_forms: three forward transforms per modulus, none back --
             // and the first layer skips the transform it runs on a coefficient-form image)
-            const int xform = pt ? CRC_NTT : CRC_COEFF;
+            // (seeded mode: the NTT form is the definition of a secret-key ciphertext; the expansion leaves it as it is)
+            const int xform = pt || sd ? CRC_NTT : CRC_COEFF;
             ciphertext3D xin[2] = {ciphertext3D(launch, 1, 28, 28, xform), ciphertext3D(launch, 1, 28, 28, xform)};
             shared_ptr<DeviceBuffer> up[2], d_pk, d_encwork;
+            if (sd) for (auto &u : up) u = make_shared<DeviceBuffer>((size_t)launch * unit * 8);
             if (pt) {
                 for (auto &u : up) u = make_shared<DeviceBuffer>((size_t)launch * unit * 8);
                 d_pk = make_shared<DeviceBuffer>(public_key.size() * 8);
@@ -288,7 +314,7 @@ int main(int argc, char **argv)
             uint64_t enc_seed = 0x5eed0000;
             auto upload = [&](int slot, bool wait_consumed) {
                 if (wait_consumed && crc_stream_wait_event(context, copy, consumed[slot])) throw runtime_error("crc_stream_wait_event");
-                char *dst = pt ? (char *)up[slot]->ptr : (char *)xin[slot].data();
+                char *dst = pt || sd ? (char *)up[slot]->ptr : (char *)xin[slot].data();
                 for (int b = 0; b < launch; b++)
                     if (crc_memcpy_h2d(context, dst + (size_t)b * unit * 8, pinned + (size_t)(b % distinct) * unit, unit * 8,
                         copy)) throw runtime_error("crc_memcpy_h2d");
@@ -299,6 +325,12 @@ int main(int argc, char **argv)
                 if (pt && crc_encrypt_dev_forms(context, (const uint64_t *)d_pk->ptr, (const uint64_t *)up[slot]->ptr, (size_t)launch * 784, enc_seed++,
                     CRC_NTT,
                                                 xin[slot].data(), d_encwork->ptr, compute)) throw runtime_error("crc_encrypt_dev_forms");
+                // one expansion per run of `distinct` images: the launch tiles them, and the stream ids of a call are contiguous
+                if (sd) for (int b0 = 0; b0 < launch; b0 += distinct) {
+                    const int nb = min(distinct, launch - b0);
+                    ciphertext3D view = xin[slot].images(b0, nb);
+                    expandSeeded((const uint64_t *)up[slot]->ptr + (size_t)b0 * unit, nb, 1, 28, 28, sd_seed, 0, view);
+                }
                 ciphertext3D y = net.forward(xin[slot]);
                 if (crc_event_record(context, consumed[slot], compute)) throw runtime_error("crc_event_record");
                 return y;
@@ -307,7 +339,26 @@ int main(int argc, char **argv)
             upload(0, false);
             {
                 ciphertext3D y = run(0);
-                if (!pt) {
+                if (sd) {
+                    // other randomness than the resident launch's inputs: other ciphertexts of the same images.  Both launches' first distinct * 10 outputs
+                    // are decrypted on the device and compared plaintext polynomial for plaintext polynomial
+                    const size_t cnt = (size_t)distinct * 10;
+                    vector<uint64_t> ref(cnt * ctw);
+                    ifstream f(outputs, ios::binary); f.read((char *)ref.data(), (streamsize)(ref.size() * 8));
+                    if (!f) throw runtime_error("cannot read " + outputs);
+                    if (y.form != CRC_COEFF && y.form != CRC_NTT) throw runtime_error("seeded mode: the network's output is not in a ciphertext form");
+                    DeviceBuffer d_sk(secret_key.size() * 8), d_ref(ref.size() * 8), d_pl(2 * cnt * n * 8);
+                    const size_t wb = max(crc_decrypt_dev_work_bytes(context, cnt, 2, CRC_COEFF), crc_decrypt_dev_work_bytes(context, cnt, 2, y.form));
+                    DeviceBuffer d_w(wb);
+                    vector<uint64_t> pl(2 * cnt * n);
+                    if (crc_memcpy_h2d(context, d_sk.ptr, secret_key.data(), secret_key.size() * 8, compute) ||
+                        crc_memcpy_h2d(context, d_ref.ptr, ref.data(), ref.size() * 8, compute) ||
+                        crc_decrypt_dev(context, (const uint64_t *)d_sk.ptr, (const uint64_t *)d_ref.ptr, cnt, 2, CRC_COEFF, (uint64_t *)d_pl.ptr, d_w.ptr, compute) ||
+                        crc_decrypt_dev(context, (const uint64_t *)d_sk.ptr, y.data(), cnt, 2, y.form, (uint64_t *)d_pl.ptr + cnt * n, d_w.ptr, compute) ||
+                        crc_memcpy_d2h(context, pl.data(), d_pl.ptr, pl.size() * 8, compute) || crc_stream_sync(context, compute))
+                        throw runtime_error("seeded mode: decryption of the outputs on the device");
+                    dec_same = memcmp(pl.data(), pl.data() + cnt * n, cnt * n * 8) == 0; st_same = st_same && dec_same;
+                } else if (!pt) {
                     vector<uint64_t> yh = y.toHost(), ref((size_t)distinct * 10 * ctw);
                     ifstream f(outputs, ios::binary); f.read((char *)ref.data(), (streamsize)(ref.size() * 8));
                     same = f && memcmp(yh.data(), ref.data(), ref.size() * 8) == 0; st_same = st_same && same;
@@ -333,14 +384,17 @@ int main(int argc, char **argv)
             st_dt = m; st_images = im; st_bytes *= world;
             for (int i = 0; i < 2; i++) { crc_event_destroy(context, copied[i]); crc_event_destroy(context, consumed[i]); }
             crc_host_free(context, pinned);
-            char buf[1400];
+            char buf[1800];
             snprintf(buf, sizeof buf,
                 "%s{\"mode\": %s, \"images_per_s\": %.4f, \"elapsed_s\": %.6f, \"steps\": %d, \"h2d_GBps\": %.2f, \"bytes_per_image\": %zu, "
-                     "\"outputs_identical_to_resident\": %s, \"how\": \"two device input buffers; the next launch's images are copied from page-locked host "
+                     "\"outputs_identical_to_resident\": %s, %s\"how\": \"two device input buffers; the next launch's images are copied from page-locked host "
                          "memory on a copy stream "
                      "while the compute stream evaluates the current one (events order the two)%s\"}", streamed_json.empty() ? "" : ", ", jstr(mode).c_str(),
                          st_images / st_dt, st_dt,
-                     stream_steps, st_bytes / st_dt / 1e9, (size_t)(unit * 8), pt ? "null" : same ? "true" : "false",
+                     stream_steps, st_bytes / st_dt / 1e9, (size_t)(unit * 8), pt || sd ? "null" : same ? "true" : "false",
+                     !sd ? "" : dec_same ? "\"outputs_decrypt_identical_to_resident\": true, " : "\"outputs_decrypt_identical_to_resident\": false, ",
+                     sd ? "; the images travel in SEEDED form -- the NTT-form c0 rows of secret-key ciphertexts, encrypted on the host before the timed region; c1 "
+                         "is regenerated from the public seed on the device (crc_seeded_expand_dev) in front of the first layer" :
                      pt ? "; the 784 pixel plaintexts per image are encrypted on the device (crc_encrypt_dev_forms, NTT-form result) in front of the first "
                          "layer" : "");
             streamed_json += buf;

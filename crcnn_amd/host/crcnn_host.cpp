@@ -433,6 +433,79 @@ ciphertext3D encryptImageSymmetric(floatCube image, int out_form)
     for (auto &a : image) for (auto &b : a) for (float v : b) px.push_back(v);
     return encryptImageSymmetric(px, zd, xd, yd, out_form);
 }
+// ---- seeded images: the c0 rows and a public seed (host-side encryption; the server expands on the device) ----
+SeededImages encryptImageSeeded(const vector<float> &px, int zd, int xd, int yd)
+{
+    const size_t per = (size_t)zd * xd * yd;
+    if (zd < 1 || xd < 1 || yd < 1 || px.empty() || px.size() % per) throw invalid_argument("encryptImageSeeded: pixels must be [B][zd][xd][yd]");
+    const int n = N();
+    vector<uint64_t> pl(px.size() * n);
+    chk(crc_encode_f32(ctx(), px.data(), px.size(), pl.data(), nullptr), "crc_encode_f32");
+    SeededImages out;
+    out.B = (int)(px.size() / per); out.zd = zd; out.xd = xd; out.yd = yd;
+    out.c0.resize(px.size() * (size_t)K() * n);
+    if (g_det) {
+        const uint64_t seed = g_det_seed + 1000003 * (g_enc_counter + 1);
+        chk(crc_seeded_public_seed(seed, out.seed), "crc_seeded_public_seed");
+        out.stream_base = 0;
+        chk(crc_encrypt_sym_seeded(ctx(), secret_key.data(), pl.data(), px.size(), seed, out.c0.data()), "crc_encrypt_sym_seeded");
+    } else {
+        chk(crc_random_key(out.seed), "crc_random_key");
+        out.stream_base = g_enc_counter;
+        chk(crc_encrypt_sym_seeded_key(ctx(), secret_key.data(), pl.data(), px.size(), g_master_key, out.seed, out.stream_base, out.c0.data()),
+            "crc_encrypt_sym_seeded_key");
+    }
+    g_enc_counter += px.size();
+    return out;
+}
+SeededImages encryptImageSeeded(floatCube image)
+{
+    const int zd = (int)image.size(), xd = (int)image[0].size(), yd = (int)image[0][0].size();
+    vector<float> px; px.reserve((size_t)zd * xd * yd);
+    for (auto &a : image) for (auto &b : a) for (float v : b) px.push_back(v);
+    return encryptImageSeeded(px, zd, xd, yd);
+}
+void SeededImages::save(ostream &os) const
+{
+    if (c0.size() != count() * (size_t)K() * N()) throw invalid_argument("SeededImages::save: rows do not match the dimensions");
+    const int32_t dims[4] = {B, zd, xd, yd};
+    vector<uint8_t> b(crc_seeded_ct_bytes(ctx(), count())); size_t w = 0;
+    chk(crc_seeded_ct_save(ctx(), c0.data(), count(), seed, stream_base, b.data(), b.size(), &w), "crc_seeded_ct_save");
+    os.write((const char *)dims, sizeof dims); os.write((const char *)b.data(), (streamsize)b.size());
+    if (!os) throw runtime_error("SeededImages::save: write failed");
+}
+void SeededImages::load(istream &is)
+{
+    int32_t dims[4] = {0, 0, 0, 0};
+    is.read((char *)dims, sizeof dims);
+    if (!is || dims[0] < 1 || dims[1] < 1 || dims[2] < 1 || dims[3] < 1) throw invalid_argument("SeededImages::load: not a seeded image file");
+    const size_t cnt = (size_t)dims[0] * dims[1] * dims[2] * dims[3];
+    vector<uint8_t> b(crc_seeded_ct_bytes(ctx(), cnt));
+    is.read((char *)b.data(), (streamsize)b.size());
+    if (!is) throw invalid_argument("SeededImages::load: file shorter than its dimensions say");
+    vector<uint64_t> rows(cnt * (size_t)K() * N()); size_t got = 0; uint8_t sd[32]; uint64_t base = 0;
+    chk(crc_seeded_ct_load(ctx(), b.data(), b.size(), rows.data(), cnt, &got, sd, &base), "seeded images are not valid for encryption parameters");
+    if (got != cnt) throw invalid_argument("SeededImages::load: count does not match the dimensions");
+    B = dims[0]; zd = dims[1]; xd = dims[2]; yd = dims[3]; c0.swap(rows); memcpy(seed, sd, 32); stream_base = base;
+}
+void expandSeeded(const uint64_t *d_c0, int B, int zd, int xd, int yd, const uint8_t *seed, uint64_t stream_base, ciphertext3D &dst)
+{
+    if (!d_c0 || !seed || !dst.buf || dst.B != B || dst.zd != zd || dst.xd != xd || dst.yd != yd)
+        throw invalid_argument("expandSeeded: destination tensor does not match the dimensions");
+    if (dst.form != CRC_COEFF && dst.form != CRC_NTT) throw invalid_argument("expandSeeded: ciphertext forms only (CRC_COEFF / CRC_NTT)");
+    chk(crc_seeded_expand_dev(ctx(), d_c0, dst.count(), seed, stream_base, dst.form, dst.data(), stream()), "crc_seeded_expand_dev");
+}
+ciphertext3D expandSeeded(const SeededImages &im, int out_form)
+{
+    if (im.count() == 0 || im.c0.size() != im.count() * (size_t)K() * N()) throw invalid_argument("expandSeeded: rows do not match the dimensions");
+    if (out_form != CRC_COEFF && out_form != CRC_NTT) throw invalid_argument("expandSeeded: ciphertext forms only (CRC_COEFF / CRC_NTT)");
+    DeviceBuffer d_c0(im.c0.size() * 8);
+    chk(crc_memcpy_h2d(ctx(), d_c0.ptr, im.c0.data(), im.c0.size() * 8, stream()), "crc_memcpy_h2d");
+    ciphertext3D out(im.B, im.zd, im.xd, im.yd, out_form);
+    expandSeeded((const uint64_t *)d_c0.ptr, im.B, im.zd, im.xd, im.yd, im.seed, im.stream_base, out);
+    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");     // the packed rows and the host vector are released here
+    return out;
+}
 vector<floatCube> decryptImages(const ciphertext3D &t)
 {
     const int n = N();

@@ -107,6 +107,28 @@ ciphertext3D refreshImages(const ciphertext3D &encrypted, int out_form = CRC_COE
 // (zd xd yd)) encrypted under the secret key on the device (crc_encrypt_sym_dev); same keystream discipline as encryptImage
 ciphertext3D encryptImageSymmetric(const std::vector<float> &pixels, int zd, int xd, int yd, int out_form = CRC_COEFF);
 ciphertext3D encryptImageSymmetric(floatCube image, int out_form = CRC_COEFF);
+// SEEDED images: c1 of a secret-key ciphertext is a function of a PUBLIC seed (include/crcnn_hip.h, "SEEDED secret-key ciphertexts"), so a client sends the
+// c0 rows and 32 bytes -- half of what encryptImage's ciphertexts take over a network or PCIe -- and the server regenerates c1 on the device.
+struct SeededImages {
+    int B = 0, zd = 0, xd = 0, yd = 0;
+    std::vector<uint64_t> c0;                               // [B][zd][xd][yd][k][n], NTT form
+    uint8_t seed[32] = {0};                                 // PUBLIC
+    uint64_t stream_base = 0;
+    size_t count() const { return (size_t)B * zd * xd * yd; }
+    // four little-endian int32 (B, zd, xd, yd), then the container of crc_seeded_ct_save; load throws std::invalid_argument for anything else
+    void save(std::ostream &out) const;
+    void load(std::istream &in);
+};
+// host-side encryption under the global secret_key of one image or a batch ([B][zd][xd][yd] floats), as encryptImageSymmetric takes them.  The PRIVATE noise key
+// follows encryptImage's keystream discipline (the master key and the ciphertext counter); the PUBLIC seed is a fresh crc_random_key per call -- under
+// setDeterministicSeed both derive from the deterministic seed and the counter, so that tests reproduce
+SeededImages encryptImageSeeded(const std::vector<float> &pixels, int zd, int xd, int yd);
+SeededImages encryptImageSeeded(floatCube image);
+// upload the packed rows on the installed stream and expand them on the device (crc_seeded_expand_dev) into an ordinary tensor of `out_form` CRC_NTT / CRC_COEFF
+ciphertext3D expandSeeded(const SeededImages &images, int out_form = CRC_NTT);
+// the same for rows that are already on the device (a host that uploads on a copy stream of its own): d_c0 packed [B zd xd yd][k][n], `dst` a tensor of that
+// shape whose form says what to produce; asynchronous on the installed stream
+void expandSeeded(const uint64_t *d_c0, int B, int zd, int xd, int yd, const uint8_t *seed, uint64_t stream_base, ciphertext3D &dst);
 
 // ---- layers (CrCNN/src/layer.h:10-31) ------------------------------------------------------------------------------
 class Layer {

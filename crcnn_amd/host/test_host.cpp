@@ -5,6 +5,7 @@
 //   test_host files <dir>        CrCNN's own files: loads the encoded-model stream and the cipher_image file the REFERENCE wrote (<dir>/ref_encoded_layers.bin,
 //     ref_cipher_image.bin; cnnBuilder.cpp:181-196, globals.cpp:174-205), runs conv -> bn -> dense on them (out_from_ref_files.u64), then writes the same two
 //     files itself (our_encoded_layers.bin, our_cipher_image.bin) and runs those (out_from_our_files.u64)
+//   test_host seeded <n> <t> / netseeded <model> <h5> <dir>     seeded secret-key images through the host classes (see do_seeded / do_netseeded)
 //   test_host searchlogic <min> <max> <first_good> <last_good> <min_q>
 //     the plain-modulus search on a synthetic predicate (t < first_good: MISPREDICTED, t > last_good: OUT_OF_BUDGET); no GPU work.
 //     prints "found <t>" and one "tried <t> <status>" line per test
@@ -189,6 +190,113 @@ static int do_encsym(int argc, char **argv)
     }
     delParameters();
     printf("encsym ok\n");
+    return 0;
+}
+
+// seeded <n> <t>: a batch through encryptImageSeeded -> save -> load -> expandSeeded in both forms decrypts to the floats and plaintexts that encryptImage's
+// ciphertexts of the same pixels decrypt to, image by image; then the same once under OS entropy (fresh public seed per call, the counter as stream base)
+static int do_seeded(int argc, char **argv)
+{
+    if (argc < 4) return 1;
+    const int B = 3, zd = 2, xd = 5, yd = 4, per = zd * xd * yd;
+    vector<float> px((size_t)B * per);
+    for (size_t i = 0; i < px.size(); i++) px[i] = (float)((int)((i * 37) % 201) - 100) / 16.0f;
+    for (int pass = 0; pass < 2; pass++) {
+        if (pass == 0) setDeterministicSeed(99); else clearDeterministicSeed();
+        setParameters(atoi(argv[2]), strtoull(argv[3], 0, 0));
+        const size_t n = (size_t)crc_ctx_n(context), k = (size_t)crc_ctx_k(context);
+        const SeededImages made = encryptImageSeeded(px, zd, xd, yd);
+        if (made.B != B || made.zd != zd || made.xd != xd || made.yd != yd || made.c0.size() != (size_t)B * per * k * n) { fprintf(stderr, "encryptImageSeeded: wrong shape\n"); return 4; }
+        stringstream file;
+        made.save(file);
+        if (file.str().size() != 16 + crc_seeded_ct_bytes(context, made.count())) { fprintf(stderr, "SeededImages::save: unexpected size\n"); return 4; }
+        if (2 * file.str().size() >= 1.02 * (double)made.count() * (double)crc_ct_words(context, 2) * 8) { fprintf(stderr, "the seeded form is not half a ciphertext\n"); return 4; }
+        SeededImages im;
+        im.load(file);
+        if (im.B != B || im.zd != zd || im.xd != xd || im.yd != yd || im.c0 != made.c0 || memcmp(im.seed, made.seed, 32) || im.stream_base != made.stream_base) {
+            fprintf(stderr, "SeededImages: save -> load is not the identity\n"); return 4; }
+        { string bad = file.str(); bad[16 + 20] ^= 0x40;                        // a flipped bit in the parameter hash
+          stringstream f2(bad); SeededImages x; bool threw = false;
+          try { x.load(f2); } catch (const invalid_argument &) { threw = true; }
+          if (!threw || !x.c0.empty()) { fprintf(stderr, "SeededImages::load accepted a wrong parameter hash\n"); return 4; } }
+        { stringstream f2(file.str().substr(0, file.str().size() - 8)); SeededImages x; bool threw = false;
+          try { x.load(f2); } catch (const invalid_argument &) { threw = true; }
+          if (!threw) { fprintf(stderr, "SeededImages::load accepted a truncated file\n"); return 4; } }
+        const SeededImages again = encryptImageSeeded(px, zd, xd, yd);          // fresh randomness per call
+        if (again.c0 == made.c0) { fprintf(stderr, "two calls reused their randomness\n"); return 4; }
+        if (pass == 1 && (!memcmp(again.seed, made.seed, 32) || again.stream_base != made.stream_base + made.count())) {
+            fprintf(stderr, "OS-entropy mode: the public seed or the stream base did not move on\n"); return 4; }
+        ciphertext3D a = expandSeeded(im, CRC_COEFF), an = expandSeeded(im);
+        if (a.B != B || a.form != CRC_COEFF || an.form != CRC_NTT || an.count() != a.count()) { fprintf(stderr, "expandSeeded: wrong shape or form\n"); return 4; }
+        const vector<u64> ha = a.toHost(), hn = an.toHost();
+        if (memcmp(hn.data(), im.c0.data(), k * n * 8)) { fprintf(stderr, "the NTT-form c0 is not the row that travelled\n"); return 4; }
+        vector<u64> back(hn);
+        { DeviceBuffer d(hn.size() * 8);
+          if (crc_memcpy_h2d(context, d.ptr, hn.data(), hn.size() * 8, nullptr) || crc_ntt_inv(context, (uint64_t *)d.ptr, a.count(), 2, nullptr) ||
+              crc_memcpy_d2h(context, back.data(), d.ptr, hn.size() * 8, nullptr) || crc_stream_sync(context, nullptr)) return 3; }
+        if (back != ha) { fprintf(stderr, "the coefficient form is not the inverse transform of the NTT form\n"); return 5; }
+        vector<u64> pa(a.count() * n);
+        if (crc_decrypt(context, secret_key.data(), ha.data(), a.count(), 2, pa.data())) return 3;
+        const vector<floatCube> got = decryptImages(a);
+        for (int b = 0; b < B; b++) {
+            floatCube img(zd, vector<vector<float>>(xd, vector<float>(yd)));
+            for (int z = 0; z < zd; z++) for (int i = 0; i < xd; i++) for (int j = 0; j < yd; j++) img[z][i][j] = px[(size_t)b * per + ((size_t)z * xd + i) * yd + j];
+            const ciphertext3D pk_ct = encryptImage(img);
+            const vector<u64> hp = pk_ct.toHost(); vector<u64> pp(pk_ct.count() * n);
+            if (crc_decrypt(context, secret_key.data(), hp.data(), pk_ct.count(), 2, pp.data())) return 3;
+            if (memcmp(pp.data(), pa.data() + (size_t)b * per * n, pp.size() * 8)) { fprintf(stderr, "image %d: plaintexts differ from encryptImage's\n", b); return 6; }
+            if (decryptImage(pk_ct) != got[b]) { fprintf(stderr, "image %d: floats differ from encryptImage's\n", b); return 6; }
+            if (noiseBudget(a, (size_t)b * per) < noiseBudget(pk_ct, 0)) { fprintf(stderr, "image %d: less budget than a public-key ciphertext\n", b); return 7; }
+        }
+        delParameters();
+    }
+    printf("seeded ok\n");
+    return 0;
+}
+
+// netseeded <model> <h5> <dir>: <dir>/params.u64 and pixels.f32 ([B][28][28] normalised floats).  The fused, NTT-resident network on
+// expandSeeded(encryptImageSeeded(x)) against the same network on encryptImage(x): the decrypted output plaintexts must be equal polynomial for polynomial, and
+// every output of the seeded run must have at least the budget of its public-key counterpart.  Writes dec_seeded.u64, dec_pk.u64 and prints the budgets
+static int do_netseeded(int argc, char **argv)
+{
+    if (argc < 5) return 1;
+    string model = argv[2], h5 = argv[3], dir = argv[4];
+    setDeterministicSeed(4242);
+    setup(dir);
+    vector<float> px;
+    { ifstream f(dir + "/pixels.f32", ios::binary); if (!f) { fprintf(stderr, "missing pixels.f32\n"); return 2; }
+      f.seekg(0, ios::end); const size_t sz = f.tellg(); f.seekg(0); px.resize(sz / 4); f.read((char *)px.data(), sz); }
+    if (px.empty() || px.size() % 784) { fprintf(stderr, "pixels.f32 must hold [B][28][28] floats\n"); return 2; }
+    const int B = (int)(px.size() / 784);
+    CnnBuilder builder(h5);
+    Network net = builder.buildNetworkByName(model);
+    net.ntt_resident = true;
+    const int removed = net.fuse();
+    fprintf(stderr, "fused: %d layers removed, %d left\n", removed, net.getNumLayers());
+    vector<ciphertext3D> imgs;
+    for (int b = 0; b < B; b++) {
+        floatCube img(1, vector<vector<float>>(28, vector<float>(28)));
+        for (int i = 0; i < 28; i++) for (int j = 0; j < 28; j++) img[0][i][j] = px[(size_t)b * 784 + i * 28 + j];
+        imgs.push_back(encryptImage(img));
+    }
+    const ciphertext3D out_pk = net.forward(stackImages(imgs));
+    const SeededImages sent = encryptImageSeeded(px, 1, 28, 28);
+    const ciphertext3D out_sd = net.forward(expandSeeded(sent));
+    if (out_sd.count() != out_pk.count() || out_sd.B != B) { fprintf(stderr, "output shapes differ\n"); return 4; }
+    const size_t n = (size_t)crc_ctx_n(context);
+    const vector<u64> hp = out_pk.toHost(), hs = out_sd.toHost();
+    if (hp == hs) { fprintf(stderr, "the two runs produced the same ciphertexts: not two encryptions\n"); return 4; }
+    vector<u64> pp(out_pk.count() * n), ps(pp.size());
+    if (crc_decrypt(context, secret_key.data(), hp.data(), out_pk.count(), 2, pp.data()) || crc_decrypt(context, secret_key.data(), hs.data(), out_sd.count(), 2, ps.data())) return 3;
+    wr(dir + "/dec_pk.u64", pp); wr(dir + "/dec_seeded.u64", ps);
+    const vector<int> bp = noiseBudgets(out_pk), bs = noiseBudgets(out_sd);
+    printf("budgets public-key:"); for (int v : bp) printf(" %d", v);
+    printf("\nbudgets seeded:"); for (int v : bs) printf(" %d", v);
+    printf("\n");
+    if (pp != ps) { fprintf(stderr, "the seeded run decrypts to other plaintexts than the public-key run\n"); return 5; }
+    for (size_t i = 0; i < bp.size(); i++) if (bs[i] < bp[i] || bs[i] <= 0) { fprintf(stderr, "output %zu: budget %d under seeded inputs, %d under public-key inputs\n", i, bs[i], bp[i]); return 7; }
+    delParameters();
+    printf("netseeded ok\n");
     return 0;
 }
 
@@ -520,6 +628,8 @@ int main(int argc, char **argv)
         if (!strcmp(argv[1], "netr")) return do_netr(argc, argv);
         if (!strcmp(argv[1], "encsym")) return do_encsym(argc, argv);
         if (!strcmp(argv[1], "budgetsym")) return do_budgetsym(argc, argv);
+        if (!strcmp(argv[1], "seeded")) return do_seeded(argc, argv);
+        if (!strcmp(argv[1], "netseeded")) return do_netseeded(argc, argv);
         if (!strcmp(argv[1], "api")) return do_api(argc, argv);
         if (!strcmp(argv[1], "files")) return do_files(argc, argv);
         if (!strcmp(argv[1], "searchlogic")) return do_searchlogic(argc, argv);

@@ -487,6 +487,53 @@ int crc_refresh_sym_dev_key(crc_ctx *ctx, const uint64_t *d_sk_ntt, const uint64
                             uint64_t stream_base, int out_form, uint64_t *d_ct_out, float *d_values_out, void *d_work, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * SEEDED secret-key ciphertexts.  c1 = A of the encryption above is a pure function of a keystream and carries no information about the plaintext, so a client
+ * may ship the c0 rows and a 32-byte PUBLIC seed and let the server regenerate c1 (later SEAL releases save symmetric ciphertexts this way; SEAL 2.3.1 has no
+ * such form): half the bytes per ciphertext.  A seeded batch is `count` ciphertexts held as
+ *     c0 [count][k][n] uint64, NTT FORM (the definition of a secret-key ciphertext here),  a PUBLIC 32-byte seed,  a 64-bit stream_base;
+ * expansion gives the ordinary [count][2][k][n] ciphertexts, c1[m][i][s] = A(seed, stream_base + m, i, s), in CRC_NTT or (both polynomials inverse-transformed)
+ * CRC_COEFF, and from there on nothing knows the difference: they are decrypted, evaluated on, refreshed and budget-measured like any other ciphertext.
+ *
+ * Two INDEPENDENT keystreams (the encryptor above draws e and A from one key, which therefore can never be published):
+ *   mask,  PUBLIC seed,  domain CHACHA_DOM_SEEDED_A = 6: one stream per (ciphertext, coefficient pair), nonce = (stream id low, stream id high, 6 << 24 | s), s the
+ *          even slot index, stream id = stream_base + ciphertext index.  Block j (counter j) serves modulus 2j with its words 0..7 and modulus 2j + 1 with its
+ *          words 8..15; within a half, words 4c .. 4c + 3 are z = w[+0] + 2^32 w[+1] + 2^64 w[+2] + 2^96 w[+3] and A[i][s + c] = z mod q_i (c = 0, 1):
+ *          (k + 1) / 2 blocks per pair, none of whose words depends on anything secret; within q_i / 2^128 < 2^-66 of uniform, as above.
+ *   noise, PRIVATE key,  domain CHACHA_DOM_SEEDED_E = 7: one block (counter 0) per (ciphertext, coefficient pair), nonce = (stream id low, stream id high,
+ *          7 << 24 | s); words 0..4 as block 0 of domain 5 (w[0..1] / w[2..3] the magnitude words of coefficients s / s + 1 through the thresholds of
+ *          crc_encrypt_dev_noise_thresholds, w[4] bit 0 / bit 1 their signs).  A domain of its own ON PURPOSE: were it domain 5, one private key serving
+ *          crc_encrypt_sym_key and this encryptor at the same stream_base would give equal e under different, known A, and for equal plaintexts
+ *          c0 - c0' = -(A - A') s -- the secret key.  With its own domain, reusing a private key across the two encryptors is harmless.
+ *
+ * SECURITY: as above, never encrypt two batches under the same (private key, stream_base).  NEVER encrypt two batches under the same (public seed, stream_base)
+ * either: equal A, so c0 - c0' = Delta (m - m') + e - e'.  The public seed MUST NOT be the private key: crc_encrypt_sym_seeded_key refuses byte-equal arguments
+ * with CRC_ERR_INVALID_ARGUMENT.  crc_encrypt_sym_seeded expands a PUBLIC 64-bit seed (tests, bench; deterministic, NOT secure): private key = the expansion of
+ * `seed` that every seed variant uses, public seed = crc_seeded_public_seed(seed) = the same expansion of ~seed, stream_base = 0.
+ *
+ *   crc_encrypt_sym_seeded[_key]   host only, any context (device = -1 included), spread over the host threads like crc_encrypt_sym
+ *   crc_seeded_expand              the host twin of the kernel (any context): it pins the device's bits
+ *   crc_seeded_expand_dev          d_c0 packed [count][k][n] -> d_ct [count][2][k][n]; asynchronous on `stream`, no work buffer (the CRC_COEFF result is the
+ *                                  in-place inverse transform of the CRC_NTT one).  count == 0 is CRC_OK and writes nothing; the two ranges must not overlap and
+ *                                  must be 16-byte aligned
+ *   crc_seeded_ct_bytes / _save / _load   the container: 96 header bytes -- magic "CRCSEED\0", uint32 version 1, uint32 0, crc_params_hash (32), uint64 count,
+ *                                  uint64 stream_base, the seed (32) -- then the c0 rows, count * k * n uint64, all little-endian.  _load refuses a wrong magic /
+ *                                  version / hash, a short buffer and a count that does not match the byte length, and then writes nothing; with h_c0 = NULL it
+ *                                  only validates and reports *count (to size the rows)
+ * ------------------------------------------------------------------------------------------------------------- */
+int crc_seeded_public_seed(uint64_t seed, uint8_t *h_seed /*[CRC_KEY_BYTES]*/);
+int crc_encrypt_sym_seeded_key(const crc_ctx *ctx, const uint64_t *h_sk_ntt, const uint64_t *h_plain /*[count][n]*/, size_t count, const uint8_t *h_key /*PRIVATE*/,
+                               const uint8_t *h_seed /*PUBLIC, CRC_KEY_BYTES*/, uint64_t stream_base, uint64_t *h_c0 /*[count][k][n], NTT form*/);
+int crc_encrypt_sym_seeded(const crc_ctx *ctx, const uint64_t *h_sk_ntt, const uint64_t *h_plain, size_t count, uint64_t seed, uint64_t *h_c0);
+int crc_seeded_expand(const crc_ctx *ctx, const uint64_t *h_c0, size_t count, const uint8_t *h_seed, uint64_t stream_base, int out_form,
+                      uint64_t *h_ct /*[count][2][k][n]*/);
+int crc_seeded_expand_dev(crc_ctx *ctx, const uint64_t *d_c0, size_t count, const uint8_t *h_seed, uint64_t stream_base, int out_form, uint64_t *d_ct,
+                          void *stream);
+size_t crc_seeded_ct_bytes(const crc_ctx *ctx, size_t count);
+int crc_seeded_ct_save(const crc_ctx *ctx, const uint64_t *h_c0, size_t count, const uint8_t *h_seed, uint64_t stream_base, void *buf, size_t cap, size_t *written);
+int crc_seeded_ct_load(const crc_ctx *ctx, const void *buf, size_t bytes, uint64_t *h_c0, size_t max_count, size_t *count, uint8_t *h_seed,
+                       uint64_t *stream_base);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * multi-GPU (SURVEY 8e / 8b `crc_broadcast_weights`).  The reference has no analogue: its only parallelism is the
  * std::thread fan-out inside a layer (convolutionalLayer.cpp:177-191).  Here a batch of encrypted images shards over the
  * GPUs of a node with NO data-path collective; the ONE collective is the start-up broadcast of the encoded (NTT-form)
