@@ -188,6 +188,11 @@ def load():
     L.crc_encrypt_sym_seeded_key.argtypes = [VP, PU, PU, SZ, PB, PB, u64, PU]
     L.crc_seeded_expand.argtypes = [VP, PU, SZ, PB, u64, CI, PU]
     L.crc_seeded_expand_dev.argtypes = [VP, VP, SZ, PB, u64, CI, VP, VP]
+    L.crc_encrypt_sym_seeded_dev.argtypes = [VP, VP, VP, SZ, u64, VP, VP]
+    L.crc_encrypt_sym_seeded_dev_key.argtypes = [VP, VP, VP, SZ, PB, PB, u64, VP, VP]
+    L.crc_encrypt_f32_seeded_dev_work_bytes.restype = SZ; L.crc_encrypt_f32_seeded_dev_work_bytes.argtypes = [VP, SZ]
+    L.crc_encrypt_f32_seeded_dev.argtypes = [VP, VP, VP, SZ, u64, VP, VP, VP]
+    L.crc_encrypt_f32_seeded_dev_key.argtypes = [VP, VP, VP, SZ, PB, PB, u64, VP, VP, VP]
     L.crc_seeded_ct_bytes.restype = SZ; L.crc_seeded_ct_bytes.argtypes = [VP, SZ]
     L.crc_seeded_ct_save.argtypes = [VP, PU, SZ, PB, u64, VP, SZ, ctypes.POINTER(SZ)]
     L.crc_seeded_ct_load.argtypes = [VP, VP, SZ, PU, SZ, ctypes.POINTER(SZ), PB, ctypes.POINTER(u64)]
@@ -653,6 +658,29 @@ class Engine:
         """packed c0 rows [count][k][n] on the device -> ciphertexts [count][2][k][n] in out_form (crc_seeded_expand_dev; asynchronous, no work buffer)"""
         _chk(self.L.crc_seeded_expand_dev(self.c, self.p(d_c0), count, self._key(public_seed), stream_base, out_form, self.p(d_ct), self.stream),
              "crc_seeded_expand_dev")
+
+    def encrypt_sym_seeded_dev(self, d_sk, d_plain, count, seed, d_c0, key=None, public_seed=None, stream_base=0):
+        """dense plaintexts [count][n] on the device -> packed c0 rows [count][k][n], the bits of encrypt_sym_seeded (crc_encrypt_sym_seeded_dev; with `key`
+        (PRIVATE) and `public_seed`: crc_encrypt_sym_seeded_dev_key).  Asynchronous, no work buffer -> (public seed, stream_base)"""
+        if key is None:
+            _chk(self.L.crc_encrypt_sym_seeded_dev(self.c, self.p(d_sk), self.p(d_plain), count, seed, self.p(d_c0), self.stream), "crc_encrypt_sym_seeded_dev")
+            return self.seeded_public_seed(seed), 0
+        _chk(self.L.crc_encrypt_sym_seeded_dev_key(self.c, self.p(d_sk), self.p(d_plain), count, self._key(key), self._key(public_seed), stream_base,
+                                                   self.p(d_c0), self.stream), "crc_encrypt_sym_seeded_dev_key")
+        return bytes(public_seed), stream_base
+
+    def encrypt_f32_seeded_dev_work_bytes(self, count):
+        return self.L.crc_encrypt_f32_seeded_dev_work_bytes(self.c, count)
+
+    def encrypt_f32_seeded_dev(self, d_sk, d_values, count, seed, d_c0, d_work, key=None, public_seed=None, stream_base=0):
+        """float32 values [count] on the device -> packed c0 rows: the device encoder in compact form, then the encryptor above (crc_encrypt_f32_seeded_dev[_key])"""
+        if key is None:
+            _chk(self.L.crc_encrypt_f32_seeded_dev(self.c, self.p(d_sk), self.p(d_values), count, seed, self.p(d_c0), self.p(d_work), self.stream),
+                 "crc_encrypt_f32_seeded_dev")
+            return self.seeded_public_seed(seed), 0
+        _chk(self.L.crc_encrypt_f32_seeded_dev_key(self.c, self.p(d_sk), self.p(d_values), count, self._key(key), self._key(public_seed), stream_base,
+                                                   self.p(d_c0), self.p(d_work), self.stream), "crc_encrypt_f32_seeded_dev_key")
+        return bytes(public_seed), stream_base
 
     def encrypt_sym_dev_work_bytes(self, count):
         return self.L.crc_encrypt_sym_dev_work_bytes(self.c, count)

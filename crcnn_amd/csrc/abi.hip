@@ -1,5 +1,6 @@
 // abi.hip -- extern "C" entry points of include/crcnn_hip.h that drive the kernels (layers and Evaluator ops).
 #include <cstdlib>
+#include <cstring>
 #include "kernels.h"
 #include "chacha.h"
 
@@ -589,6 +590,65 @@ extern "C" int crc_seeded_expand_dev(crc_ctx *c, const uint64_t *d_c0, size_t co
     const uintptr_t s0 = (uintptr_t)d_c0, s1 = s0 + 8 * count * row, t0 = (uintptr_t)d_ct, t1 = t0 + 16 * count * row;
     if ((s0 < t1 && t0 < s1) || ((s0 | t0) & 15)) return CRC_ERR_INVALID_ARGUMENT;       // (and the 16-byte accesses need their alignment)
     return k_seeded_expand(c, d_c0, count, chacha_load_key(seed), stream_base, d_ct, S(stream), out_form == CRC_NTT);
+}
+// ---- the seeded form produced on the device (kernels_client.hip: k_encrypt_sym_seeded) ----
+// the source (`src_bytes` per ciphertext) and the key must not overlap the packed rows, which are formed in place; the 16-byte accesses need their alignment
+static int seeded_enc_ranges_ok(const crc_ctx *c, const void *src, size_t src_bytes, size_t src_align, const void *d_sk, const uint64_t *d_c0, size_t count)
+{
+    const size_t row = (size_t)c->n * c->k;
+    if (count > (size_t)-1 / (16 * row) || count > (size_t)-1 / (2 * src_bytes)) return 0;
+    const uintptr_t s0 = (uintptr_t)src, s1 = s0 + count * src_bytes, t0 = (uintptr_t)d_c0, t1 = t0 + 8 * count * row, k0 = (uintptr_t)d_sk, k1 = k0 + 8 * row;
+    if ((s0 < t1 && t0 < s1) || (k0 < t1 && t0 < k1)) return 0;
+    return !((t0 | k0) & 15) && !(s0 & (src_align - 1));
+}
+extern "C" int crc_encrypt_sym_seeded_dev_key(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_plain, size_t count, const uint8_t *key, const uint8_t *seed,
+                                              uint64_t stream_base, uint64_t *d_c0, void *stream)
+{
+    if (!d_sk || !d_plain || !d_c0 || !key || !seed || !std::memcmp(key, seed, CRC_KEY_BYTES)) return CRC_ERR_INVALID_ARGUMENT;
+    CHECK_CTX(c);
+    if (count == 0) return CRC_OK;
+    if (!seeded_enc_ranges_ok(c, d_plain, 8 * (size_t)c->n, 16, d_sk, d_c0, count)) return CRC_ERR_INVALID_ARGUMENT;
+    return k_encrypt_sym_seeded(c, d_sk, d_plain, count, chacha_load_key(key), chacha_load_key(seed), stream_base, d_c0, S(stream), false);
+}
+extern "C" int crc_encrypt_sym_seeded_dev(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_plain, size_t count, uint64_t seed, uint64_t *d_c0, void *stream)
+{
+    if (!d_sk || !d_plain || !d_c0) return CRC_ERR_INVALID_ARGUMENT;
+    CHECK_CTX(c);
+    if (count == 0) return CRC_OK;
+    if (!seeded_enc_ranges_ok(c, d_plain, 8 * (size_t)c->n, 16, d_sk, d_c0, count)) return CRC_ERR_INVALID_ARGUMENT;
+    // what crc_encrypt_sym_seeded derives: private key = the expansion of seed, public seed = crc_seeded_public_seed(seed) = the expansion of ~seed
+    return k_encrypt_sym_seeded(c, d_sk, d_plain, count, chacha_seed_key(seed), chacha_seed_key(~seed), 0, d_c0, S(stream), false);
+}
+// pixels in, packed rows out: work = [compact plaintexts [count][96]]
+extern "C" size_t crc_encrypt_f32_seeded_dev_work_bytes(const crc_ctx *c, size_t count) { return c ? 8 * count * (size_t)CRC_PLAIN_COMPACT_WORDS + 256 : 0; }
+static int encrypt_f32_seeded_impl(crc_ctx *c, const u64 *d_sk, const float *d_values, size_t count, const ChaChaKey &key, const ChaChaKey &seed, u64 stream_base,
+                                   u64 *d_c0, void *d_work, hipStream_t st)
+{
+    if (count == 0) return CRC_OK;
+    if (c->n <= CRC_PLAIN_COMPACT_WORDS) return CRC_ERR_INVALID_ARGUMENT;
+    if (count > (size_t)-1 / (16 * (size_t)CRC_PLAIN_COMPACT_WORDS)) return CRC_ERR_INVALID_ARGUMENT;
+    u64 *compact = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
+    // the encoder writes the compact plaintexts while other workgroups still read floats: the two must not overlap either
+    { const uintptr_t v0 = (uintptr_t)d_values, v1 = v0 + 4 * count, w0 = (uintptr_t)compact, w1 = w0 + 8 * count * (size_t)CRC_PLAIN_COMPACT_WORDS;
+      if (v0 < w1 && w0 < v1) return CRC_ERR_INVALID_ARGUMENT; }
+    if (!seeded_enc_ranges_ok(c, d_values, 4, 4, d_sk, d_c0, count) ||
+        !seeded_enc_ranges_ok(c, compact, 8 * (size_t)CRC_PLAIN_COMPACT_WORDS, 16, d_sk, d_c0, count)) return CRC_ERR_INVALID_ARGUMENT;
+    RUN(k_fra_encode_compact(c, d_values, count, compact, st));
+    return k_encrypt_sym_seeded(c, d_sk, compact, count, key, seed, stream_base, d_c0, st, true);
+}
+extern "C" int crc_encrypt_f32_seeded_dev_key(crc_ctx *c, const uint64_t *d_sk, const float *d_values, size_t count, const uint8_t *key, const uint8_t *seed,
+                                              uint64_t stream_base, uint64_t *d_c0, void *d_work, void *stream)
+{
+    if (!d_sk || !d_values || !d_c0 || !d_work || !key || !seed || !std::memcmp(key, seed, CRC_KEY_BYTES)) return CRC_ERR_INVALID_ARGUMENT;
+    CHECK_CTX(c);
+    return encrypt_f32_seeded_impl(c, d_sk, d_values, count, chacha_load_key(key), chacha_load_key(seed), stream_base, d_c0, d_work, S(stream));
+}
+extern "C" int crc_encrypt_f32_seeded_dev(crc_ctx *c, const uint64_t *d_sk, const float *d_values, size_t count, uint64_t seed, uint64_t *d_c0, void *d_work,
+                                          void *stream)
+{
+    if (!d_sk || !d_values || !d_c0 || !d_work) return CRC_ERR_INVALID_ARGUMENT;
+    CHECK_CTX(c);
+    return encrypt_f32_seeded_impl(c, d_sk, d_values, count, chacha_seed_key(seed), chacha_seed_key(~seed), 0, d_c0, d_work, S(stream));
 }
 extern "C" int crc_square(crc_ctx *c, const uint64_t *d_x, size_t count, uint64_t *d_y3, void *d_work, void *stream)
 {

@@ -62,12 +62,17 @@ int k_encrypt_sym(crc_ctx *c, const u64 *sk, const u64 *plain, size_t cnt, const
                   bool plain_compact);
 // seeded secret-key ciphertexts: c0 [cnt][k][n] packed NTT-form rows -> ct [cnt][2][k][n], c1 = A(seed, stream_base + m) regenerated (chacha.h)
 int k_seeded_expand(crc_ctx *c, const u64 *c0, size_t cnt, const ChaChaKey &seed, u64 stream_base, u64 *ct, hipStream_t st, bool out_ntt);
+// the seeded form produced on the device: c0 [cnt][k][n] = NTT(e + Delta m) - A(seed) . s, formed in place (no work buffer, no c1 row); the host twin is
+// crc_encrypt_sym_seeded_key (client.cpp)
+int k_encrypt_sym_seeded(crc_ctx *c, const u64 *sk, const u64 *plain, size_t cnt, const ChaChaKey &key, const ChaChaKey &seed, u64 stream_base, u64 *c0,
+                         hipStream_t st, bool plain_compact);
 // kernels_decrypt.hip: Decryptor::decrypt and the fractional encoder on the device (the refresh of Network::forward)
 size_t k_decrypt_work_words(const crc_ctx *c, size_t cnt, int size, bool in_ntt);
 int k_decrypt(crc_ctx *c, const u64 *sk, const u64 *ct, size_t cnt, int size, bool in_ntt, u64 *plain, u64 *work, hipStream_t st);
 int k_decrypt_recode(crc_ctx *c, const u64 *sk, const u64 *ct, size_t cnt, bool in_ntt, u64 *compact, float *vals_out, u64 *work, hipStream_t st);
 int k_fra_decode(crc_ctx *c, const u64 *plain, size_t cnt, double *out, hipStream_t st);
 int k_fra_encode(crc_ctx *c, const void *src, int mode, size_t cnt, u64 *plain, float *vals_out, hipStream_t st);
+int k_fra_encode_compact(crc_ctx *c, const float *src, size_t cnt, u64 *compact, hipStream_t st);      // floats -> compact plaintexts [cnt][96]
 // V = work [cnt][k][n]: c0 + c1 s (+ c2 s^2) in coefficient form (work: k_decrypt_work_words)
 int k_decrypt_rows(crc_ctx *c, const u64 *sk, const u64 *ct, size_t cnt, int size, bool in_ntt, u64 *work, hipStream_t st);
 // kernels_budget.hip: Decryptor::invariant_noise_budget of every ciphertext of a tensor (work: k_decrypt_work_words)

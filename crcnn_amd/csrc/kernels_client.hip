@@ -360,3 +360,95 @@ int k_seeded_expand(crc_ctx *c, const u64 *c0, size_t cnt, const ChaChaKey &seed
     // the NTT form is the definition; the coefficient form is the inverse transform of both polynomials, in place
     return out_ntt ? CRC_OK : k_ntt_ct(c, true, ct, ct, cnt, 2, false, st, nullptr, 0, 0, 0);
 }
+
+// ---- the seeded form produced on the device --------------------------------------------------------------------------------------------------------------------
+// What crc_encrypt_sym_seeded[_key] computes on the host, bit for bit: the packed rows c0 [count][k][n] = NTT(e + Delta m) - A . s, with e from the PRIVATE key
+// (CHACHA_DOM_SEEDED_E) and A from the PUBLIC seed (CHACHA_DOM_SEEDED_A).  Three steps on one stream and in place -- the sampler writes e + Delta m into the
+// packed rows, the row transform runs over them as over a size-1 "ciphertext" (what the public-key encryptor does to its U rows), and the mask kernel
+// regenerates A pair by pair in registers and subtracts A . s.  No c1 row is ever written: the server regenerates it (seeded_expand_kernel).
+
+// One lane = one (ciphertext, coefficient pair), as enc_sym_sample_kernel: ONE block of the private key's noise stream, words 0..4; per modulus one 16-byte
+// store of e + Delta m (+ q mod t on the upper half) into the packed row.  COMPACT as enc_sample_kernel
+template <bool COMPACT>
+__global__ void __launch_bounds__(256) seeded_enc_sample_kernel(u64 *c0, const u64 *plain, const ModParams *mods, int n, int k, ChaChaKey key, u64 stream_base,
+                                                                EncCdt cdt, PlainParams pp)
+{
+    const int pairs = n >> 1, pblocks = (pairs + (int)blockDim.x - 1) / (int)blockDim.x;
+    const size_t m = blockIdx.x / pblocks;
+    const int pr = (blockIdx.x % pblocks) * blockDim.x + threadIdx.x;
+    if (pr >= pairs) return;
+    const int s = 2 * pr;
+    const u64 sid = stream_base + m;
+    u32 b[16];
+    chacha20_block(key, 0, (u32)sid, (u32)(sid >> 32), ((u32)CHACHA_DOM_SEEDED_E << 24) | (u32)s, b);
+    const int e[2] = {cdt_noise(b[0], b[1], b[4] & 1u, cdt), cdt_noise(b[2], b[3], (b[4] >> 1) & 1u, cdt)};
+    ulonglong2 pl = make_ulonglong2(0, 0);
+    if (!COMPACT) pl = *reinterpret_cast<const ulonglong2 *>(plain + m * (size_t)n + s);
+    else if (s < CRC_PLAIN_COMPACT_LOW) pl = *reinterpret_cast<const ulonglong2 *>(plain + m * (size_t)CRC_PLAIN_COMPACT_WORDS + s);
+    else if (s >= n - CRC_PLAIN_COMPACT_HIGH)
+        pl = *reinterpret_cast<const ulonglong2 *>(plain + m * (size_t)CRC_PLAIN_COMPACT_WORDS + CRC_PLAIN_COMPACT_LOW + (s - (n - CRC_PLAIN_COMPACT_HIGH)));
+    const u64 pc[2] = {pl.x, pl.y};
+    for (int i = 0; i < k; i++) {
+        const ModParams md = mods[i];
+        u64 r[2];
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            u64 lo, hi; mul64wide(pp.delta[i], pc[c], lo, hi);
+            if (pc[c] >= pp.threshold) { const u64 l2 = lo + pp.uhi[i]; hi += (l2 < lo); lo = l2; }
+            r[c] = addmod(e[c] >= 0 ? (u64)e[c] : md.q - (u64)(-e[c]), barrett128(lo, hi, md), md.q);
+        }
+        *reinterpret_cast<ulonglong2 *>(c0 + (m * k + i) * (size_t)n + s) = ulonglong2{r[0], r[1]};
+    }
+}
+
+// The same lanes over the TRANSFORMED packed rows: the public seed's keystream walked as seeded_expand_kernel walks it (block j: modulus 2j from words 0..7,
+// modulus 2j + 1 from words 8..15, constant indices so the block stays in registers); per modulus one 16-byte load of the pair's c0 residues, one of the secret
+// key's, c0 <- c0 - A . s, one 16-byte store in place.  A lives in registers only
+__global__ void __launch_bounds__(256) seeded_enc_mask_kernel(u64 *c0, const u64 *sk, const ModParams *mods, int n, int k, ChaChaKey seed, u64 stream_base)
+{
+    const int pairs = n >> 1, pblocks = (pairs + (int)blockDim.x - 1) / (int)blockDim.x;
+    const size_t m = blockIdx.x / pblocks;
+    const int pr = (blockIdx.x % pblocks) * blockDim.x + threadIdx.x;
+    if (pr >= pairs) return;
+    const int s = 2 * pr;
+    const u64 sid = stream_base + m;
+    const u32 n2 = ((u32)CHACHA_DOM_SEEDED_A << 24) | (u32)s;
+    u32 b[16];
+    auto emit = [&](int i, const u32 *w) {
+        const ModParams md = mods[i];
+        u64 *dst = c0 + (m * k + i) * (size_t)n + s;
+        const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(dst), kv = *reinterpret_cast<const ulonglong2 *>(sk + (size_t)i * n + s);
+        u64 a[2];
+#pragma unroll
+        for (int c = 0; c < 2; c++) a[c] = mod128_any((u64)w[4 * c] | ((u64)w[4 * c + 1] << 32), (u64)w[4 * c + 2] | ((u64)w[4 * c + 3] << 32), md);
+        *reinterpret_cast<ulonglong2 *>(dst) = ulonglong2{submod(v.x, mulmod(a[0], kv.x, md), md.q), submod(v.y, mulmod(a[1], kv.y, md), md.q)};
+    };
+    for (int j = 0; 2 * j < k; j++) {
+        chacha20_block(seed, (u32)j, (u32)sid, (u32)(sid >> 32), n2, b);
+        emit(2 * j, b);
+        if (2 * j + 1 < k) emit(2 * j + 1, b + 8);
+    }
+}
+
+int k_encrypt_sym_seeded(crc_ctx *c, const u64 *sk, const u64 *plain, size_t cnt, const ChaChaKey &key, const ChaChaKey &seed, u64 stream_base, u64 *c0,
+                         hipStream_t st, bool plain_compact)
+{
+    if (cnt == 0) return CRC_OK;
+    const int n = c->n, k = c->k;
+    if (plain_compact && n <= CRC_PLAIN_COMPACT_WORDS) return CRC_ERR_INVALID_ARGUMENT;
+    const int pairs = n / 2, threads = pairs < 256 ? pairs : 256, pblocks = (pairs + threads - 1) / threads;
+    if (cnt * (size_t)pblocks > 0x7fffffffULL || cnt * (size_t)k > 0x7fffffffULL) return CRC_ERR_INVALID_ARGUMENT;
+    if (plain_compact)
+        hipLaunchKernelGGL((seeded_enc_sample_kernel<true>), dim3((unsigned)(cnt * pblocks)), dim3(threads), 0, st, c0, plain, c->d_mods, n, k, key, stream_base,
+                           enc_cdt(), c->plain);
+    else
+        hipLaunchKernelGGL((seeded_enc_sample_kernel<false>), dim3((unsigned)(cnt * pblocks)), dim3(threads), 0, st, c0, plain, c->d_mods, n, k, key, stream_base,
+                           enc_cdt(), c->plain);
+    HIPCHK(hipGetLastError());
+    // the packed rows are a size-1 "ciphertext" of k rows: transformed in place
+    int rc;
+    if ((rc = k_ntt_ct(c, false, c0, c0, cnt, 1, false, st, nullptr, 0, 0, 0))) return rc;
+    hipLaunchKernelGGL(seeded_enc_mask_kernel, dim3((unsigned)(cnt * pblocks)), dim3(threads), 0, st, c0, sk, c->d_mods, n, k, seed, stream_base);
+    HIPCHK(hipGetLastError());
+    return CRC_OK;
+}

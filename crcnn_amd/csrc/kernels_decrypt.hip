@@ -253,6 +253,26 @@ int k_fra_encode(crc_ctx *c, const void *src, int mode, size_t cnt, u64 *plain, 
     return CRC_OK;
 }
 
+// fra_encode_kernel<0> without the dense row: one workgroup (128 lanes) per float, lane 0 encodes into LDS and 96 lanes store the compact plaintext (96 words:
+// crc_plain_expand's layout, the words crc_encode_f32_compact gives on the host) that the encryptors' sampling kernels read as it is
+__global__ void __launch_bounds__(128) fra_encode_compact_kernel(const float *src, u64 *compact, u64 t)
+{
+    __shared__ u64 enc[CRC_PLAIN_COMPACT_WORDS];
+    const size_t m = blockIdx.x;
+    if (threadIdx.x == 0) dev_fra_encode((double)src[m], t, enc);
+    __syncthreads();
+    if (threadIdx.x < CRC_PLAIN_COMPACT_WORDS) compact[m * (size_t)CRC_PLAIN_COMPACT_WORDS + threadIdx.x] = enc[threadIdx.x];
+}
+
+int k_fra_encode_compact(crc_ctx *c, const float *src, size_t cnt, u64 *compact, hipStream_t st)
+{
+    if (cnt == 0) return CRC_OK;
+    if (cnt > 0x7fffffffULL || c->n <= CRC_PLAIN_COMPACT_WORDS) return CRC_ERR_INVALID_ARGUMENT;
+    hipLaunchKernelGGL(fra_encode_compact_kernel, dim3((unsigned)cnt), dim3(128), 0, st, src, compact, c->t);
+    HIPCHK(hipGetLastError());
+    return CRC_OK;
+}
+
 // decrypt -> decode -> float -> encode for the refresh: compact plaintexts [cnt][96] (and the floats) out; work as k_decrypt
 int k_decrypt_recode(crc_ctx *c, const u64 *sk, const u64 *ct, size_t cnt, bool in_ntt, u64 *compact, float *vals_out, u64 *work, hipStream_t st)
 {

@@ -433,17 +433,43 @@ ciphertext3D encryptImageSymmetric(floatCube image, int out_form)
     for (auto &a : image) for (auto &b : a) for (float v : b) px.push_back(v);
     return encryptImageSymmetric(px, zd, xd, yd, out_form);
 }
-// ---- seeded images: the c0 rows and a public seed (host-side encryption; the server expands on the device) ----
-SeededImages encryptImageSeeded(const vector<float> &px, int zd, int xd, int yd)
+// ---- seeded images: the c0 rows and a public seed (encryption on the host threads or on the device; the server expands on the device) ----
+// pixels up at 4 bytes each, encoded and encrypted on the installed stream (crc_encrypt_f32_seeded_dev[_key]), the packed rows down: the host path's seeds
+static void encryptSeededOnDevice(const vector<float> &px, SeededImages &out)
+{
+    DeviceBuffer d_px(px.size() * 4), d_c0(out.c0.size() * 8), d_work(crc_encrypt_f32_seeded_dev_work_bytes(ctx(), px.size()));
+    const uint64_t *d_sk = deviceKey(g_d_sk, g_d_sk_fp, secret_key, "secret key");
+    chk(crc_memcpy_h2d(ctx(), d_px.ptr, px.data(), px.size() * 4, stream()), "crc_memcpy_h2d");
+    if (g_det) {
+        const uint64_t seed = g_det_seed + 1000003 * (g_enc_counter + 1);
+        chk(crc_seeded_public_seed(seed, out.seed), "crc_seeded_public_seed");
+        out.stream_base = 0;
+        chk(crc_encrypt_f32_seeded_dev(ctx(), d_sk, (const float *)d_px.ptr, px.size(), seed, (uint64_t *)d_c0.ptr, d_work.ptr, stream()),
+            "crc_encrypt_f32_seeded_dev");
+    } else {
+        chk(crc_random_key(out.seed), "crc_random_key");
+        out.stream_base = g_enc_counter;
+        chk(crc_encrypt_f32_seeded_dev_key(ctx(), d_sk, (const float *)d_px.ptr, px.size(), g_master_key, out.seed, out.stream_base, (uint64_t *)d_c0.ptr,
+                                           d_work.ptr, stream()), "crc_encrypt_f32_seeded_dev_key");
+    }
+    chk(crc_memcpy_d2h(ctx(), out.c0.data(), d_c0.ptr, out.c0.size() * 8, stream()), "crc_memcpy_d2h");
+    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+}
+SeededImages encryptImageSeeded(const vector<float> &px, int zd, int xd, int yd, bool on_device)
 {
     const size_t per = (size_t)zd * xd * yd;
     if (zd < 1 || xd < 1 || yd < 1 || px.empty() || px.size() % per) throw invalid_argument("encryptImageSeeded: pixels must be [B][zd][xd][yd]");
     const int n = N();
-    vector<uint64_t> pl(px.size() * n);
-    chk(crc_encode_f32(ctx(), px.data(), px.size(), pl.data(), nullptr), "crc_encode_f32");
     SeededImages out;
     out.B = (int)(px.size() / per); out.zd = zd; out.xd = xd; out.yd = yd;
     out.c0.resize(px.size() * (size_t)K() * n);
+    if (on_device) {
+        encryptSeededOnDevice(px, out);
+        g_enc_counter += px.size();
+        return out;
+    }
+    vector<uint64_t> pl(px.size() * n);
+    chk(crc_encode_f32(ctx(), px.data(), px.size(), pl.data(), nullptr), "crc_encode_f32");
     if (g_det) {
         const uint64_t seed = g_det_seed + 1000003 * (g_enc_counter + 1);
         chk(crc_seeded_public_seed(seed, out.seed), "crc_seeded_public_seed");
@@ -458,12 +484,12 @@ SeededImages encryptImageSeeded(const vector<float> &px, int zd, int xd, int yd)
     g_enc_counter += px.size();
     return out;
 }
-SeededImages encryptImageSeeded(floatCube image)
+SeededImages encryptImageSeeded(floatCube image, bool on_device)
 {
     const int zd = (int)image.size(), xd = (int)image[0].size(), yd = (int)image[0][0].size();
     vector<float> px; px.reserve((size_t)zd * xd * yd);
     for (auto &a : image) for (auto &b : a) for (float v : b) px.push_back(v);
-    return encryptImageSeeded(px, zd, xd, yd);
+    return encryptImageSeeded(px, zd, xd, yd, on_device);
 }
 void SeededImages::save(ostream &os) const
 {

@@ -119,11 +119,14 @@ struct SeededImages {
     void save(std::ostream &out) const;
     void load(std::istream &in);
 };
-// host-side encryption under the global secret_key of one image or a batch ([B][zd][xd][yd] floats), as encryptImageSymmetric takes them.  The PRIVATE noise key
+// encryption under the global secret_key of one image or a batch ([B][zd][xd][yd] floats), as encryptImageSymmetric takes them.  The PRIVATE noise key
 // follows encryptImage's keystream discipline (the master key and the ciphertext counter); the PUBLIC seed is a fresh crc_random_key per call -- under
 // setDeterministicSeed both derive from the deterministic seed and the counter, so that tests reproduce
-SeededImages encryptImageSeeded(const std::vector<float> &pixels, int zd, int xd, int yd);
-SeededImages encryptImageSeeded(floatCube image);
+// `on_device` (off by default: the host encryptor, spread over the host threads): the floats go up at 4 bytes per pixel, crc_encrypt_f32_seeded_dev[_key] encodes
+// and encrypts them on the installed stream under the cached device copy of the secret key, and the packed rows come back -- the same seed, stream_base and
+// counter discipline, and under setDeterministicSeed byte for byte the same SeededImages
+SeededImages encryptImageSeeded(const std::vector<float> &pixels, int zd, int xd, int yd, bool on_device = false);
+SeededImages encryptImageSeeded(floatCube image, bool on_device = false);
 // upload the packed rows on the installed stream and expand them on the device (crc_seeded_expand_dev) into an ordinary tensor of `out_form` CRC_NTT / CRC_COEFF
 ciphertext3D expandSeeded(const SeededImages &images, int out_form = CRC_NTT);
 // the same for rows that are already on the device (a host that uploads on a copy stream of its own): d_c0 packed [B zd xd yd][k][n], `dst` a tensor of that

@@ -510,11 +510,24 @@ int crc_refresh_sym_dev_key(crc_ctx *ctx, const uint64_t *d_sk_ntt, const uint64
  * with CRC_ERR_INVALID_ARGUMENT.  crc_encrypt_sym_seeded expands a PUBLIC 64-bit seed (tests, bench; deterministic, NOT secure): private key = the expansion of
  * `seed` that every seed variant uses, public seed = crc_seeded_public_seed(seed) = the same expansion of ~seed, stream_base = 0.
  *
- *   crc_encrypt_sym_seeded[_key]   host only, any context (device = -1 included), spread over the host threads like crc_encrypt_sym
+ *   crc_encrypt_sym_seeded[_key]   on the host, any context (device = -1 included), spread over the host threads like crc_encrypt_sym
  *   crc_seeded_expand              the host twin of the kernel (any context): it pins the device's bits
  *   crc_seeded_expand_dev          d_c0 packed [count][k][n] -> d_ct [count][2][k][n]; asynchronous on `stream`, no work buffer (the CRC_COEFF result is the
  *                                  in-place inverse transform of the CRC_NTT one).  count == 0 is CRC_OK and writes nothing; the two ranges must not overlap and
  *                                  must be 16-byte aligned
+ *   crc_encrypt_sym_seeded_dev[_key]   the encryptor on the device (a client-side GPU): d_sk_ntt [k][n], d_plain [count][n] dense plaintexts -> d_c0 packed
+ *                                  [count][k][n], NTT form, bit for bit what crc_encrypt_sym_seeded[_key] computes for the same (secret key, plaintexts, private
+ *                                  key, public seed, stream_base).  Three steps on `stream`, the rows formed in place: a sampling kernel writes e + Delta m into
+ *                                  the packed rows, the forward row transform runs over them, a mask kernel regenerates A pair by pair in registers and
+ *                                  subtracts A . s.  No c1 row is ever written and there is no work buffer.  The uint64-seed variant derives what
+ *                                  crc_encrypt_sym_seeded derives (private key = the expansion of seed, public seed = crc_seeded_public_seed(seed), stream_base
+ *                                  0); the _key variant refuses a public seed byte-equal to the private key.  NULL arguments, a source or key that overlaps
+ *                                  d_c0 and device pointers that are not 16-byte aligned are refused (CRC_ERR_INVALID_ARGUMENT) and nothing is written;
+ *                                  count == 0 is CRC_OK and writes nothing.  Asynchronous on `stream`
+ *   crc_encrypt_f32_seeded_dev[_key]   pixels in, packed rows out: d_values [count] floats on the device -> FractionalEncoder::encode (the device encoder that
+ *                                  crc_encode_dev_f32 runs, written in the compact 96-word form: the words of crc_encode_f32_compact) -> the encryptor above
+ *                                  reading the compact plaintexts: 4 bytes per pixel go up instead of 8 n.  d_work: crc_encrypt_f32_seeded_dev_work_bytes(count)
+ *                                  (the compact plaintexts), which must not overlap d_values either.  Refuses a ring with n <= CRC_PLAIN_COMPACT_WORDS (count == 0 is CRC_OK there too); otherwise as above
  *   crc_seeded_ct_bytes / _save / _load   the container: 96 header bytes -- magic "CRCSEED\0", uint32 version 1, uint32 0, crc_params_hash (32), uint64 count,
  *                                  uint64 stream_base, the seed (32) -- then the c0 rows, count * k * n uint64, all little-endian.  _load refuses a wrong magic /
  *                                  version / hash, a short buffer and a count that does not match the byte length, and then writes nothing; with h_c0 = NULL it
@@ -528,6 +541,14 @@ int crc_seeded_expand(const crc_ctx *ctx, const uint64_t *h_c0, size_t count, co
                       uint64_t *h_ct /*[count][2][k][n]*/);
 int crc_seeded_expand_dev(crc_ctx *ctx, const uint64_t *d_c0, size_t count, const uint8_t *h_seed, uint64_t stream_base, int out_form, uint64_t *d_ct,
                           void *stream);
+int crc_encrypt_sym_seeded_dev_key(crc_ctx *ctx, const uint64_t *d_sk_ntt, const uint64_t *d_plain /*[count][n]*/, size_t count, const uint8_t *h_key /*PRIVATE*/,
+                                   const uint8_t *h_seed /*PUBLIC*/, uint64_t stream_base, uint64_t *d_c0 /*[count][k][n], NTT form*/, void *stream);
+int crc_encrypt_sym_seeded_dev(crc_ctx *ctx, const uint64_t *d_sk_ntt, const uint64_t *d_plain, size_t count, uint64_t seed, uint64_t *d_c0, void *stream);
+size_t crc_encrypt_f32_seeded_dev_work_bytes(const crc_ctx *ctx, size_t count);
+int crc_encrypt_f32_seeded_dev_key(crc_ctx *ctx, const uint64_t *d_sk_ntt, const float *d_values /*[count]*/, size_t count, const uint8_t *h_key /*PRIVATE*/,
+                                   const uint8_t *h_seed /*PUBLIC*/, uint64_t stream_base, uint64_t *d_c0, void *d_work, void *stream);
+int crc_encrypt_f32_seeded_dev(crc_ctx *ctx, const uint64_t *d_sk_ntt, const float *d_values, size_t count, uint64_t seed, uint64_t *d_c0, void *d_work,
+                               void *stream);
 size_t crc_seeded_ct_bytes(const crc_ctx *ctx, size_t count);
 int crc_seeded_ct_save(const crc_ctx *ctx, const uint64_t *h_c0, size_t count, const uint8_t *h_seed, uint64_t stream_base, void *buf, size_t cap, size_t *written);
 int crc_seeded_ct_load(const crc_ctx *ctx, const void *buf, size_t bytes, uint64_t *h_c0, size_t max_count, size_t *count, uint8_t *h_seed,
