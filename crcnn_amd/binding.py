@@ -108,6 +108,7 @@ def load():
     L.crc_dense.argtypes = [VP, VP, VP, VP, CI, CI, CI, CI, CI, VP, VP, VP]
     L.crc_pool.argtypes = [VP, VP] + [CI] * 8 + [VP, CI, VP, VP]
     L.crc_batchnorm.argtypes = [VP, VP, CI, CI, CI, CI, VP, VP, CI, VP]
+    L.crc_pad.argtypes = [VP, VP] + [CI] * 9 + [VP, VP]
     L.crc_square_relin_work_bytes.restype = SZ; L.crc_square_relin_work_bytes.argtypes = [VP, SZ, CI]
     L.crc_square_relin.argtypes = [VP, VP, SZ, VP, CI, VP, VP, VP]
     L.crc_square_relin_forms.argtypes = [VP, VP, CI, SZ, VP, CI, VP, CI, VP, VP]
@@ -236,6 +237,13 @@ def h5_read(path, name):
     out = np.zeros(cnt.value, dtype=np.float32)
     _chk(L.crc_h5_read_f32(path.encode(), name.encode(), out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), cnt.value, None), "crc_h5_read_f32")
     return out
+
+
+def h5_count(path, name):
+    """number of elements of a dataset"""
+    cnt = SZ(0)
+    _chk(load().crc_h5_dataset_count(path.encode(), name.encode(), ctypes.byref(cnt)), f"crc_h5_dataset_count({name})")
+    return int(cnt.value)
 
 
 def h5_list(path):
@@ -574,6 +582,10 @@ class Engine:
 
     def pool(self, d_x, B, zd, xd, yd, xs, ys, xf, yf, d_div, form, d_y):
         _chk(self.L.crc_pool(self.c, self.p(d_x), B, zd, xd, yd, xs, ys, xf, yf, self.p(d_div), form, self.p(d_y), self.stream), "crc_pool")
+
+    def pad(self, d_x, B, zd, xd, yd, px0, px1, py0, py1, form, d_y):
+        """zero padding of the two spatial dimensions (crc_pad): [B][zd][xd][yd] -> [B][zd][px0 + xd + px1][py0 + yd + py1], the form (COEFF / NTT) kept"""
+        _chk(self.L.crc_pad(self.c, self.p(d_x), B, zd, xd, yd, px0, px1, py0, py1, form, self.p(d_y), self.stream), "crc_pad")
 
     def batchnorm(self, d_x, B, zd, xd, yd, d_mean, d_invstd, form):
         _chk(self.L.crc_batchnorm(self.c, self.p(d_x), B, zd, xd, yd, self.p(d_mean), self.p(d_invstd), form, self.stream), "crc_batchnorm")

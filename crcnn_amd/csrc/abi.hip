@@ -338,6 +338,25 @@ extern "C" int crc_pool(crc_ctx *c, const uint64_t *d_x, int B, int zd, int xd, 
     return k_ntt_ct(c, true, d_y, d_y, cnt, 2, false, st, nullptr, 0, 0);
 }
 
+// zero padding (PaddingLayer): all-zero ciphertexts around every channel plane, the form kept.  Only canonical rows: in the packed and limb operand forms a
+// tensor is laid out for the layer that reads it, and no such hand-over spans a pad
+extern "C" int crc_pad(crc_ctx *c, const uint64_t *d_x, int B, int zd, int xd, int yd, int px0, int px1, int py0, int py1, int form, uint64_t *d_y,
+                       void *stream)
+{
+    CHECK_CTX(c);
+    if (!d_x || !d_y || B < 0 || zd < 1 || xd < 1 || yd < 1 || px0 < 0 || px1 < 0 || py0 < 0 || py1 < 0 || !form_ok(form)) return CRC_ERR_INVALID_ARGUMENT;
+    if (((uintptr_t)d_x | (uintptr_t)d_y) & 15) return CRC_ERR_INVALID_ARGUMENT;           // 16-byte loads and stores
+    const long long xo = (long long)xd + px0 + px1, yo = (long long)yd + py0 + py1;
+    if (xo > 0x7fffffffLL || yo > 0x7fffffffLL) return CRC_ERR_INVALID_ARGUMENT;
+    const size_t ctb = crc_ct_words(c, 2) * 8;
+    const size_t in_bytes = (size_t)B * zd * xd * yd * ctb, out_bytes = (size_t)B * zd * (size_t)xo * (size_t)yo * ctb;
+    // not in place: an output row would overwrite input rows that are still to be read
+    const uintptr_t x0 = (uintptr_t)d_x, y0 = (uintptr_t)d_y;
+    if (x0 < y0 + out_bytes && y0 < x0 + in_bytes) return CRC_ERR_INVALID_ARGUMENT;
+    if (B == 0) return CRC_OK;
+    return k_pad(c, d_x, d_y, B, zd, xd, yd, px0, px1, py0, py1, S(stream));
+}
+
 extern "C" int crc_batchnorm(crc_ctx *c, uint64_t *d_x, int B, int zd, int xd, int yd, const uint64_t *d_mean, const uint64_t *d_invstd,
                              int form, void *stream)
 {

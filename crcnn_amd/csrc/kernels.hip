@@ -912,6 +912,45 @@ int k_pool(crc_ctx *c, const u64 *x, u64 *y, int B, int zd, int xd, int yd, int 
     return CRC_OK;
 }
 
+// zero padding of the two spatial dimensions: y[b][z][ox][oy] = x[b][z][ox - px0][oy - py0] inside the image, the all-zero ciphertext outside it.
+// (0, 0) is the additive identity of BFV in coefficient and in NTT form alike (the transform of the zero polynomial is zero), so the kernel is form-blind.
+// One block per output row as in pool_kernel; whether the row is copied or zeroed depends on the block index alone, so no wave diverges.  Streaming: every
+// byte is read at most once and written once, 16 B per lane, four loads in flight per lane before the first store
+__global__ void __launch_bounds__(256) pad_kernel(const u64 *x, u64 *y, int n, int k, int xd, int yd, int px0, int py0, int xo, int yo)
+{
+    // row = (((b*zd + z)*xo + ox)*yo + oy)*2k + r,  r = p*k + i
+    const size_t row = blockIdx.x;
+    const int r = (int)(row % (2 * (size_t)k));
+    size_t ct = row / (2 * (size_t)k);
+    const int oy = (int)(ct % yo); ct /= yo; const int ox = (int)(ct % xo); ct /= xo;       // ct = b*zd + z
+    const int ix = ox - px0, iy = oy - py0;
+    ulonglong2 *dst = reinterpret_cast<ulonglong2 *>(y + row * (size_t)n);
+    const int n2 = n / 2;
+    if (ix < 0 || ix >= xd || iy < 0 || iy >= yd) {          // border row (block-uniform)
+        const ulonglong2 z = make_ulonglong2(0, 0);
+        for (int s = threadIdx.x; s < n2; s += blockDim.x) dst[s] = z;
+        return;
+    }
+    const ulonglong2 *src = reinterpret_cast<const ulonglong2 *>(x + (((ct * xd + ix) * yd + iy) * (2 * (size_t)k) + r) * (size_t)n);
+    int s = threadIdx.x;
+    for (; s + 3 * (int)blockDim.x < n2; s += 4 * blockDim.x) {
+        const ulonglong2 a = src[s], b = src[s + blockDim.x], c = src[s + 2 * blockDim.x], d = src[s + 3 * blockDim.x];
+        dst[s] = a; dst[s + blockDim.x] = b; dst[s + 2 * blockDim.x] = c; dst[s + 3 * blockDim.x] = d;
+    }
+    for (; s < n2; s += blockDim.x) dst[s] = src[s];
+}
+
+int k_pad(crc_ctx *c, const u64 *x, u64 *y, int B, int zd, int xd, int yd, int px0, int px1, int py0, int py1, hipStream_t st)
+{
+    const int xo = xd + px0 + px1, yo = yd + py0 + py1;
+    const size_t rows = (size_t)B * zd * xo * yo * 2 * c->k;
+    if (rows == 0) return CRC_OK;
+    if (rows > 0x7fffffffULL) return CRC_ERR_UNSUPPORTED;                 // one block per row: the grid's x dimension
+    hipLaunchKernelGGL(pad_kernel, dim3((unsigned)rows), dim3(256), 0, st, x, y, c->n, c->k, xd, yd, px0, py0, xo, yo);
+    HIPCHK(hipGetLastError());
+    return CRC_OK;
+}
+
 // batch-norm on an NTT-resident tensor: x = (x - mean_delta_ntt[z]) * invstd_ntt[z]   (poly 0 gets the subtraction)
 __global__ void __launch_bounds__(256) bn_ntt_kernel(u64 *x, const u64 *mean, const u64 *invstd, const ModParams *mods, int n, int k,
                                                      int zd, int hw)

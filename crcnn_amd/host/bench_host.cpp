@@ -3,7 +3,7 @@
 // mainparams.cpp:81); this is the same loop over chunks of encrypted images: CnnBuilder builds the network from the HDF5 model, Network::fuse() folds it,
 // Network::forward runs it.
 //
-//   bench_host model=<name> h5=<model.h5> n=<n> k=<k> t=<t> [q=<p0>,<p1>,..] inputs=<file> distinct=<D> batch=<B> chunk=<C> group=<G> steps=<K> warmup=<W>
+//   bench_host model=<name | description file> h5=<model.h5> n=<n> k=<k> t=<t> [q=<p0>,<p1>,..] inputs=<file> distinct=<D> batch=<B> chunk=<C> group=<G> steps=<K> warmup=<W>
 //              outputs=<file> [fuse=1] [matrix_cores=1] [reenc=<layer>] [reenc_sym=1]
 //
 // inputs        D encrypted images ([D][784][2][k][n] u64, coefficient form: bench.py's client side writes them), tiled to one launch of C * G images that
@@ -187,14 +187,17 @@ int main(int argc, char **argv)
         if (group > 1) net.head_chunk = head;
         net.time_with_events = true;
         // one launch's images: the D distinct ones tiled
-        const size_t ctw = (size_t)2 * k * n, imgw = 784 * ctw;
+        // (model=<name> or the path of a description file: the input shape is the description's)
+        const int iz = net.input_zd, ix = net.input_xd, iy = net.input_yd;
+        const size_t ipx = (size_t)iz * ix * iy;
+        const size_t ctw = (size_t)2 * k * n, imgw = ipx * ctw;
         ciphertext3D x;
         vector<uint64_t> h((size_t)distinct * imgw);
         {
             ifstream f(inputs, ios::binary); if (!f) throw runtime_error("cannot open " + inputs);
             f.read((char *)h.data(), (streamsize)(h.size() * 8)); if (!f) throw runtime_error("short read: " + inputs);
             vector<ciphertext3D> one, tiled;
-            for (int d = 0; d < distinct; d++) one.push_back(ciphertext3D::fromHost(h.data() + (size_t)d * imgw, 1, 1, 28, 28));
+            for (int d = 0; d < distinct; d++) one.push_back(ciphertext3D::fromHost(h.data() + (size_t)d * imgw, 1, iz, ix, iy));
             for (int b = 0; b < launch; b++) tiled.push_back(one[b % distinct]);
             x = stackImages(tiled);
         }
@@ -271,7 +274,7 @@ int main(int argc, char **argv)
         for (const string &mode : modes) {
             double st_dt = 0.0, st_images = 0.0, st_bytes = 0.0; bool same = true;
             const bool pt = mode == "plaintext", sd = mode == "seeded";
-            const size_t unit = pt ? (size_t)784 * n : sd ? (size_t)784 * k * n : imgw;      // words uploaded per image
+            const size_t unit = pt ? ipx * n : sd ? ipx * k * n : imgw;      // words uploaded per image
             uint8_t sd_seed[CRC_KEY_BYTES] = {0};
             bool dec_same = true;
             uint64_t *pinned = nullptr;
@@ -283,12 +286,12 @@ int main(int argc, char **argv)
             } else if (sd) {
                 // the client side of this mode, before the timed region: the distinct images' pixel plaintexts under the secret key of the seeded client keys,
                 // straight into the page-locked rows (stream ids 0 .. distinct * 784 - 1 under one public seed)
-                vector<uint64_t> pl((size_t)distinct * 784 * n);
+                vector<uint64_t> pl((size_t)distinct * ipx * n);
                 ifstream f(need("plain_inputs"), ios::binary); if (!f) throw runtime_error("cannot open plain_inputs");
                 f.read((char *)pl.data(), (streamsize)(pl.size() * 8)); if (!f) throw runtime_error("short read: plain_inputs");
                 const uint64_t client_seed = 0x5eeded00 + (uint64_t)geti("key_seed", 2024);
                 if (crc_seeded_public_seed(client_seed, sd_seed) ||
-                    crc_encrypt_sym_seeded(context, secret_key.data(), pl.data(), (size_t)distinct * 784, client_seed, pinned))
+                    crc_encrypt_sym_seeded(context, secret_key.data(), pl.data(), (size_t)distinct * ipx, client_seed, pinned))
                     throw runtime_error("crc_encrypt_sym_seeded");
             } else {
                 memcpy(pinned, h.data(), (size_t)distinct * unit * 8);
@@ -298,13 +301,13 @@ int main(int argc, char **argv)
             // and the first layer skips the transform it runs on a coefficient-form image)
             // (seeded mode: the NTT form is the definition of a secret-key ciphertext; the expansion leaves it as it is)
             const int xform = pt || sd ? CRC_NTT : CRC_COEFF;
-            ciphertext3D xin[2] = {ciphertext3D(launch, 1, 28, 28, xform), ciphertext3D(launch, 1, 28, 28, xform)};
+            ciphertext3D xin[2] = {ciphertext3D(launch, iz, ix, iy, xform), ciphertext3D(launch, iz, ix, iy, xform)};
             shared_ptr<DeviceBuffer> up[2], d_pk, d_encwork;
             if (sd) for (auto &u : up) u = make_shared<DeviceBuffer>((size_t)launch * unit * 8);
             if (pt) {
                 for (auto &u : up) u = make_shared<DeviceBuffer>((size_t)launch * unit * 8);
                 d_pk = make_shared<DeviceBuffer>(public_key.size() * 8);
-                d_encwork = make_shared<DeviceBuffer>(crc_encrypt_dev_work_bytes(context, (size_t)launch * 784));
+                d_encwork = make_shared<DeviceBuffer>(crc_encrypt_dev_work_bytes(context, (size_t)launch * ipx));
                 if (crc_memcpy_h2d(context, d_pk->ptr, public_key.data(), public_key.size() * 8, compute) || crc_stream_sync(context,
                     compute)) throw runtime_error("public key upload");
             }
@@ -322,14 +325,14 @@ int main(int argc, char **argv)
             };
             auto run = [&](int slot) {
                 if (crc_stream_wait_event(context, compute, copied[slot])) throw runtime_error("crc_stream_wait_event");
-                if (pt && crc_encrypt_dev_forms(context, (const uint64_t *)d_pk->ptr, (const uint64_t *)up[slot]->ptr, (size_t)launch * 784, enc_seed++,
+                if (pt && crc_encrypt_dev_forms(context, (const uint64_t *)d_pk->ptr, (const uint64_t *)up[slot]->ptr, (size_t)launch * ipx, enc_seed++,
                     CRC_NTT,
                                                 xin[slot].data(), d_encwork->ptr, compute)) throw runtime_error("crc_encrypt_dev_forms");
                 // one expansion per run of `distinct` images: the launch tiles them, and the stream ids of a call are contiguous
                 if (sd) for (int b0 = 0; b0 < launch; b0 += distinct) {
                     const int nb = min(distinct, launch - b0);
                     ciphertext3D view = xin[slot].images(b0, nb);
-                    expandSeeded((const uint64_t *)up[slot]->ptr + (size_t)b0 * unit, nb, 1, 28, 28, sd_seed, 0, view);
+                    expandSeeded((const uint64_t *)up[slot]->ptr + (size_t)b0 * unit, nb, iz, ix, iy, sd_seed, 0, view);
                 }
                 ciphertext3D y = net.forward(xin[slot]);
                 if (crc_event_record(context, consumed[slot], compute)) throw runtime_error("crc_event_record");

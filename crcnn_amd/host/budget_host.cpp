@@ -1,7 +1,8 @@
 // budget_host.cpp -- the noise-budget profile of a real batch: one profiled Network::forward on seeded synthetic images, written as a small JSON file.
 //
-// usage: budget_host <model.h5> <n> <k> <t> <batch> <seed> <outdir>
-//   <model.h5>  the model file; its base name is the topology (PlainModelTiny | ApproxPlainModel | PlainModelWoPad)
+// usage: budget_host <model.h5> <n> <k> <t> <batch> <seed> <outdir> [description]
+//   <model.h5>  the model file; its base name is the topology (PlainModelTiny | ApproxPlainModel | PlainModelWoPad) unless the path of a description file
+//               follows as the last argument (28 x 28 one-channel inputs: the images are the synthetic digits)
 //   <n> <k>     ring size and the first k primes of coeff_modulus_128(n); <t> the plain modulus
 //   <batch>     seeded MNIST-like images (the generator of crcnn_amd/synth.py), encrypted under the deterministic seed <seed>
 // Writes <outdir>/budget_<model>_n<n>_k<k>_b<batch>.json:
@@ -56,12 +57,14 @@ static string list(const vector<int> &v)
 
 int main(int argc, char **argv)
 {
-    if (argc != 8) { fprintf(stderr, "usage: %s <model.h5> <n> <k> <t> <batch> <seed> <outdir>\n", argv[0]); return 1; }
+    if (argc != 8 && argc != 9) { fprintf(stderr, "usage: %s <model.h5> <n> <k> <t> <batch> <seed> <outdir> [description]\n", argv[0]); return 1; }
     const string h5 = argv[1], outdir = argv[7];
     const int n = atoi(argv[2]), k = atoi(argv[3]), batch = atoi(argv[5]);
     const uint64_t t = strtoull(argv[4], 0, 0), seed = strtoull(argv[6], 0, 0);
     string model = h5.substr(h5.find_last_of('/') + 1);
     if (model.size() > 3 && model.substr(model.size() - 3) == ".h5") model.resize(model.size() - 3);
+    const string label = model;                               // names the output file
+    if (argc == 9) model = argv[8];
     try {
         if (n < 1 || k < 1 || batch < 1) throw invalid_argument("bad sizes");
         uint64_t q[16];
@@ -72,6 +75,7 @@ int main(int argc, char **argv)
         ostringstream f;
         {                                                     // (every tensor and the network go before the search below sets the parameters again)
         Network net = build.buildNetworkByName(model);
+        if (net.input_zd != 1 || net.input_xd != 28 || net.input_yd != 28) throw invalid_argument("the synthetic images are 1 x 28 x 28");
         vector<ciphertext3D> imgs;
         for (int b = 0; b < batch; b++) imgs.push_back(encryptImage(synthImage(b), 1, 28, 28));
         const ciphertext3D x = stackImages(imgs);
@@ -123,7 +127,7 @@ int main(int argc, char **argv)
             try { noiseBudgets(p); rejected = false; } catch (const invalid_argument &) {}
             try { minNoiseBudget(p); rejected = false; } catch (const invalid_argument &) {}
         }
-        f << "{\"model\": \"" << model << "\", \"n\": " << n << ", \"k\": " << k << ", \"t\": " << t << ", \"batch\": " << batch << ", \"seed\": " << seed << ",\n";
+        f << "{\"model\": \"" << label << "\", \"n\": " << n << ", \"k\": " << k << ", \"t\": " << t << ", \"batch\": " << batch << ", \"seed\": " << seed << ",\n";
         f << " \"layers\": [";
         for (int i = 0; i < L; i++) f << (i ? ", " : "") << "\"" << net.layers[i]->getName() << "\"";
         f << "],\n";
@@ -149,7 +153,7 @@ int main(int argc, char **argv)
             const int whole = (int)s.testPlainModulus(build, t, (int)s.test_set.size());
             f << " \"search_status\": {\"first_ciphertext\": " << first << ", \"whole_batch\": " << whole << "}}\n";
         }
-        const string path = outdir + "/budget_" + model + "_n" + to_string(n) + "_k" + to_string(k) + "_b" + to_string(batch) + ".json";
+        const string path = outdir + "/budget_" + label + "_n" + to_string(n) + "_k" + to_string(k) + "_b" + to_string(batch) + ".json";
         ofstream o(path);
         o << f.str();
         o.close();

@@ -11,6 +11,7 @@
 #include <iostream>
 #include <list>
 #include <mutex>
+#include <sstream>
 
 using namespace std;
 
@@ -1108,6 +1109,32 @@ AvgPoolingLayer::AvgPoolingLayer(string name, int xd, int yd, int zd, int xs, in
     d_div = uploadPlain({&div_factor}, 0);
 }
 
+// ---- Padding ----------------------------------------------------------------------------------------------------------
+PaddingLayer::PaddingLayer(string name, int xd, int yd, int zd, int px, int py)
+    : Layer(name), xd(xd), yd(yd), zd(zd), px(px), py(py), xo(xd + 2 * px), yo(yd + 2 * py), zo(zd)
+{
+    if (xd < 1 || yd < 1 || zd < 1 || px < 0 || py < 0) throw invalid_argument("PaddingLayer: dimensions must be positive and pads non-negative");
+}
+ciphertext3D PaddingLayer::forward(ciphertext3D input)
+{
+    checkInput(input, zd, xd, yd, "PaddingLayer");
+    if (input.form != CRC_COEFF && input.form != CRC_NTT) throw invalid_argument("PaddingLayer: input must be in CRC_COEFF or CRC_NTT form");
+    ciphertext3D out(input.B, zo, xo, yo, input.form);
+    chk(crc_pad(ctx(), input.data(), input.B, zd, xd, yd, px, px, py, py, input.form, out.data(), stream()), "crc_pad");
+    if (out_form != out.form) {      // padding is form-preserving; convert only if the network asked for the other form
+        if (out_form == CRC_NTT) chk(crc_ntt_fwd(ctx(), out.data(), out.count(), 2, stream()), "crc_ntt_fwd");
+            else if (out_form == CRC_COEFF) chk(crc_ntt_inv(ctx(), out.data(), out.count(), 2, stream()), "crc_ntt_inv");
+            else throw invalid_argument("PaddingLayer: out_form must be CRC_NTT or CRC_COEFF");
+        out.form = out_form;
+    }
+    return out;
+}
+void PaddingLayer::printLayerStructure()
+{
+    cerr << "Padding " << name << " : input (" << zd << "," << xd << "," << yd << "); pad(" << px << "," << py << "); output(" << zo << "," << xo << "," << yo
+         << ")" << endl;
+}
+
 // ---- Square -----------------------------------------------------------------------------------------------------------
 ciphertext3D SquareLayer::forward(ciphertext3D input)
 {
@@ -1567,7 +1594,181 @@ int Network::fuse()
         eraseLayer(i);
     }
     chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+    if (removed) fused_ = true;
     return removed;
+}
+
+// ---- network descriptions ---------------------------------------------------------------------------------------------
+namespace {
+const struct { const char *name, *text; } kBuiltinModels[] = {
+#include "builtin_models.inc"
+};
+[[noreturn]] void descError(int line, const string &what) { throw invalid_argument("line " + to_string(line) + ": " + what); }
+int descInt(int line, const string &tok, const char *what)
+{
+    if (tok.empty() || tok.size() > 9 || tok.find_first_not_of("0123456789") != string::npos)
+        descError(line, string(what) + ": expected a non-negative integer, got '" + tok + "'");
+    return atoi(tok.c_str());
+}
+// the shapes crc_conv2d / crc_pool take (abi.hip, conv_shape_ok): the window fits and the stride leaves no trailing outputs the reference would leave as
+// empty ciphertexts
+bool windowOk(int xd, int yd, int xs, int ys, int xf, int yf)
+{
+    if (xd < 1 || yd < 1 || xs < 1 || ys < 1 || xf < 1 || yf < 1 || xf > xd || yf > yd) return false;
+    const int xl = xd - max(xf, xs) + 1, yl = yd - max(yf, ys) + 1;
+    if (xl < 1 || yl < 1) return false;
+    return (xl + xs - 1) / xs == (xd - xf) / xs + 1 && (yl + ys - 1) / ys == (yd - yf) / ys + 1;
+}
+}   // namespace
+const char *builtinDescription(const string &model)
+{
+    for (auto &m : kBuiltinModels) if (model == m.name) return m.text;
+    return nullptr;
+}
+NetworkDescription NetworkDescription::parse(const string &text, const string &h5_path)
+{
+    NetworkDescription d;
+    bool have_input = false, flat = false;
+    int pending_refresh = 0, refresh_line = 0, zd = 0, xd = 0, yd = 0, ln = 0;
+    auto check = [&](int line, const string &name, long long count) {
+        if (h5_path.empty()) return;
+        size_t have = 0;
+        if (crc_h5_dataset_count(h5_path.c_str(), name.c_str(), &have)) descError(line, "the model " + h5_path + " has no dataset " + name);
+        if ((long long)have != count) descError(line, "dataset " + name + " holds " + to_string(have) + " values, the layer needs " + to_string(count));
+    };
+    istringstream in(text);
+    string raw;
+    while (getline(in, raw)) {
+        ln++;
+        raw = raw.substr(0, raw.find('#'));
+        vector<string> tok;
+        { istringstream ls(raw); string t; while (ls >> t) tok.push_back(t); }
+        if (tok.empty()) continue;
+        const string &kind = tok[0];
+        if (!have_input) {
+            if (kind != "input" || tok.size() != 4) descError(ln, "the first line must be `input zd xd yd`");
+            d.zd = zd = descInt(ln, tok[1], "input"); d.xd = xd = descInt(ln, tok[2], "input"); d.yd = yd = descInt(ln, tok[3], "input");
+            if (zd < 1 || xd < 1 || yd < 1) descError(ln, "input: dimensions must be positive");
+            have_input = true;
+            continue;
+        }
+        if (kind == "refresh") {
+            if (tok.size() != 1) descError(ln, "unknown token '" + tok[1] + "' after refresh");
+            if (refresh_line) descError(ln, "a second refresh (line " + to_string(refresh_line) + " has the first)");
+            pending_refresh = refresh_line = ln;
+            continue;
+        }
+        const bool windowed = kind == "conv" || kind == "pool" || kind == "avgpool";
+        if (!windowed && kind != "bn" && kind != "square" && kind != "fc" && kind != "pad") descError(ln, "unknown layer kind '" + kind + "'");
+        if (tok.size() < 2) descError(ln, kind + ": the layer name is missing");
+        LayerSpec L;
+        L.kind = kind; L.name = tok[1]; L.line = ln; L.zd = zd; L.xd = xd; L.yd = yd;
+        vector<string> rest(tok.begin() + 2, tok.end());
+        if (rest.size() >= 2 && rest[rest.size() - 2] == "threads") {
+            if (kind != "conv" && kind != "fc" && kind != "square") descError(ln, "unknown token 'threads' for a " + kind + " layer");
+            L.threads = descInt(ln, rest.back(), "threads");
+            rest.resize(rest.size() - 2);
+        }
+        if (flat && (windowed || kind == "pad"))
+            descError(ln, "a " + kind + " layer cannot follow a fully connected layer: the tensor is flat (" + to_string(xd) + " values)");
+        if (windowed) {
+            size_t pos = 0;
+            auto values = [&](const char *key, int *a, int *b) {
+                if (pos >= rest.size() || rest[pos] != key) descError(ln, kind + ": expected `" + key + "`, got '" + (pos < rest.size() ? rest[pos] : "end of line") + "'");
+                const size_t cnt = b ? 2 : 1;
+                if (pos + cnt >= rest.size()) descError(ln, kind + ": `" + key + "` takes " + to_string(cnt) + " value(s)");
+                *a = descInt(ln, rest[pos + 1], key); if (b) *b = descInt(ln, rest[pos + 2], key);
+                pos += 1 + cnt;
+            };
+            values("stride", &L.xs, &L.ys);
+            values(kind == "conv" ? "filter" : "window", &L.xf, &L.yf);
+            if (kind == "conv") values("filters", &L.nf, nullptr);
+            if (pos != rest.size()) descError(ln, "unknown token '" + rest[pos] + "'");
+            if (L.xs < 1 || L.ys < 1 || L.xf < 1 || L.yf < 1) descError(ln, kind + ": strides and window sizes must be positive");
+            if (L.xf > xd || L.yf > yd)
+                descError(ln, kind + ": the " + to_string(L.xf) + " x " + to_string(L.yf) + " window is larger than its " + to_string(xd) + " x " + to_string(yd) + " input");
+            if (!windowOk(xd, yd, L.xs, L.ys, L.xf, L.yf))
+                descError(ln, kind + ": stride " + to_string(L.xs) + " x " + to_string(L.ys) + " over a " + to_string(L.xf) + " x " + to_string(L.yf) +
+                    " window leaves a remainder of the " + to_string(xd) + " x " + to_string(yd) + " input without outputs");
+            L.zo = zd; L.xo = (xd - L.xf) / L.xs + 1; L.yo = (yd - L.yf) / L.ys + 1;
+            if (kind == "conv") {
+                if (L.nf < 1) descError(ln, "conv: filters must be positive");
+                L.zo = L.nf;
+                check(ln, L.name + ".weight", (long long)L.nf * zd * L.xf * L.yf); check(ln, L.name + ".bias", L.nf);
+            }
+        } else if (kind == "fc") {
+            if (rest.size() != 1) descError(ln, rest.size() > 1 ? "unknown token '" + rest[1] + "'" : string("fc: out_dim is missing"));
+            L.out_dim = descInt(ln, rest[0], "out_dim");
+            if (L.out_dim < 1) descError(ln, "fc: out_dim must be positive");
+            if ((long long)zd * xd * yd > 0x7fffffffLL) descError(ln, "fc: the input is too large");
+            check(ln, L.name + ".weight", (long long)zd * xd * yd * L.out_dim); check(ln, L.name + ".bias", L.out_dim);
+            L.zo = 1; L.xo = L.out_dim; L.yo = 1;
+        } else if (kind == "pad") {
+            if (rest.size() != 2) descError(ln, rest.size() > 2 ? "unknown token '" + rest[2] + "'" : string("pad: takes px py"));
+            L.px = descInt(ln, rest[0], "pad"); L.py = descInt(ln, rest[1], "pad");
+            L.zo = zd; L.xo = xd + 2 * L.px; L.yo = yd + 2 * L.py;
+        } else {
+            if (!rest.empty()) descError(ln, "unknown token '" + rest[0] + "'");
+            if (kind == "bn") { check(ln, L.name + ".running_mean", zd); check(ln, L.name + ".running_var", zd); }
+            L.zo = zd; L.xo = xd; L.yo = yd;
+        }
+        if (pending_refresh) { d.layer_before_reenc = (int)d.layers.size(); pending_refresh = 0; }
+        d.layers.push_back(L);
+        zd = L.zo; xd = L.xo; yd = L.yo;
+        flat = flat || kind == "fc";
+    }
+    if (!have_input) descError(1, "the first line must be `input zd xd yd`");
+    if (pending_refresh) descError(pending_refresh, "refresh must be followed by a layer");
+    if (d.layers.empty()) descError(ln, "the description has no layers");
+    return d;
+}
+NetworkDescription NetworkDescription::load(const string &what, const string &h5_path)
+{
+    if (what.find('\n') != string::npos) return parse(what, h5_path);
+    if (const char *text = builtinDescription(what)) return parse(text, h5_path);
+    ifstream f(what);
+    if (!f) throw invalid_argument("unknown model " + what + ": neither a built-in model nor a readable description file");
+    stringstream ss; ss << f.rdbuf();
+    return parse(ss.str(), h5_path);
+}
+string NetworkDescription::str() const
+{
+    ostringstream o;
+    o << "input " << zd << " " << xd << " " << yd << "\n";
+    for (size_t i = 0; i < layers.size(); i++) {
+        const LayerSpec &L = layers[i];
+        if ((int)i == layer_before_reenc) o << "refresh\n";
+        o << L.kind << " " << L.name;
+        if (L.kind == "conv") o << " stride " << L.xs << " " << L.ys << " filter " << L.xf << " " << L.yf << " filters " << L.nf;
+        else if (L.kind == "pool" || L.kind == "avgpool") o << " stride " << L.xs << " " << L.ys << " window " << L.xf << " " << L.yf;
+        else if (L.kind == "fc") o << " " << L.out_dim;
+        else if (L.kind == "pad") o << " " << L.px << " " << L.py;
+        if (L.threads >= 0 && L.threads != 1) o << " threads " << L.threads;          // (1 is what a layer without the token is built with)
+        o << "\n";
+    }
+    return o.str();
+}
+string Network::describe() const
+{
+    if (fused_) throw logic_error("Network::describe: fuse() has folded layers; describe the network before it is fused");
+    NetworkDescription d;
+    d.zd = input_zd; d.xd = input_xd; d.yd = input_yd; d.layer_before_reenc = layer_before_reenc;
+    for (auto &l : layers) {
+        LayerSpec L; L.name = l->name;
+        if (L.name.empty() || L.name.find_first_of(" \t\n#") != string::npos) throw logic_error("Network::describe: layer name '" + L.name + "' cannot be written");
+        if (auto c = dynamic_pointer_cast<ConvolutionalLayer>(l)) { L.kind = "conv"; L.xs = c->xs; L.ys = c->ys; L.xf = c->xf; L.yf = c->yf; L.nf = c->nf;
+            L.threads = c->th_count; }
+        else if (auto f = dynamic_pointer_cast<FullyConnectedLayer>(l)) { L.kind = "fc"; L.out_dim = f->out_dim; L.threads = f->th_count; }
+        else if (auto p = dynamic_pointer_cast<PoolingLayer>(l)) { L.kind = dynamic_pointer_cast<AvgPoolingLayer>(l) ? "avgpool" : "pool"; L.xs = p->xs; L.ys = p->ys;
+            L.xf = p->xf; L.yf = p->yf; }
+        else if (auto pd = dynamic_pointer_cast<PaddingLayer>(l)) { L.kind = "pad"; L.px = pd->px; L.py = pd->py; }
+        else if (auto sq = dynamic_pointer_cast<SquareLayer>(l)) { L.kind = "square"; L.threads = sq->th_count; }
+        else if (dynamic_pointer_cast<BatchNormLayer>(l)) L.kind = "bn";
+        else throw logic_error("Network::describe: layer " + l->name + " has no description");
+        d.layers.push_back(L);
+    }
+    // (parsing the text back infers every shape again and so checks that the layers fit each other)
+    return NetworkDescription::parse(d.str()).str();
 }
 
 // ---- CnnBuilder -------------------------------------------------------------------------------------------------------
@@ -1638,33 +1839,30 @@ BatchNormLayer *CnnBuilder::buildBatchNormLayer(string name, int num_channels, i
     return new BatchNormLayer(name, num_channels, em, ev);
 }
 Network CnnBuilder::buildNetwork(string file_name) { return buildNetworkByName("PlainModelTiny", file_name); }
-Network CnnBuilder::buildNetworkByName(const string &model, string file_name)
+PaddingLayer *CnnBuilder::buildPaddingLayer(string name, int xd, int yd, int zd, int px, int py) { return new PaddingLayer(name, xd, yd, zd, px, py); }
+// the three networks of cnnBuilder.cpp:115-169 come from their descriptions (crcnn_amd/models/*.net, compiled in): same build*Layer calls, same arguments
+Network CnnBuilder::buildNetworkByName(const string &model, string file_name) { return buildNetworkFromDescription(model, file_name); }
+Network CnnBuilder::buildNetworkFromDescription(const string &path_or_text, string file_name)
 {
-    int th_count = 40, th_count2 = 50, th_tiny = 32, th_tiny2 = 42;
+    // (an encoded-model file brings its own parameters: the HDF5 datasets are not consulted then, as in build*Layer)
+    const NetworkDescription d = NetworkDescription::load(path_or_text, file_name == "" ? plain_model_path : string());
     Network net;
     unique_ptr<ifstream> infile;
     if (file_name != "") { infile.reset(new ifstream(file_name, ifstream::binary)); if (!*infile) throw runtime_error("cannot open " + file_name); }
     istream *in = infile.get();
     auto add = [&](Layer *l) { net.getLayers().push_back(shared_ptr<Layer>(l)); };
-    if (model == "PlainModelTiny") {                         // cnnBuilder.cpp:157-169
-        add(buildConvolutionalLayer("pool1_features.conv1", 28, 28, 1, 1, 1, 5, 5, 32, th_tiny, in));
-        add(buildAvgPoolingLayer("pool1", 24, 24, 32, 2, 2, 2, 2));
-        add(buildConvolutionalLayer("pool2_features.conv2", 12, 12, 32, 1, 1, 5, 5, 64, th_tiny * 2, in));
-        add(buildAvgPoolingLayer("pool2", 8, 8, 64, 2, 2, 2, 2));
-        add(buildFullyConnectedLayer("classifier.fc3", 4 * 4 * 64, 512, th_tiny2, in));
-        add(buildFullyConnectedLayer("classifier.fc4", 512, 10, th_tiny2, in));
-    } else if (model == "ApproxPlainModel" || model == "PlainModelWoPad") {   // cnnBuilder.cpp:115-134 / :136-155
-        const bool avg = model == "ApproxPlainModel";
-        add(buildConvolutionalLayer("pool1_features.conv1", 28, 28, 1, 2, 2, 5, 5, 20, th_count, in));
-        add(avg ? (Layer *)buildAvgPoolingLayer("pool1", 12, 12, 20, 1, 1, 2, 2) : (Layer *)buildPoolingLayer("pool1", 12, 12, 20, 1, 1, 2, 2));
-        add(buildBatchNormLayer("pool1_features.norm1", 20, in));
-        add(buildConvolutionalLayer("pool2_features.conv2", 11, 11, 20, 2, 2, 3, 3, 50, avg ? th_count2 : th_count, in));
-        add(buildSquareLayer("act1", avg ? th_count2 : th_count));
-        add(avg ? (Layer *)buildAvgPoolingLayer("pool2", 5, 5, 50, 1, 1, 2, 2) : (Layer *)buildPoolingLayer("pool2", 5, 5, 50, 1, 1, 2, 2));
-        add(buildBatchNormLayer("pool2_features.norm2", 50, in));
-        add(buildFullyConnectedLayer("classifier.fc3", 4 * 4 * 50, 500, th_count, in));
-        add(buildFullyConnectedLayer("classifier.fc4", 500, 10, avg ? th_count2 : th_count, in));
-    } else throw invalid_argument("unknown model " + model);
+    for (const LayerSpec &L : d.layers) {
+        const int th = L.threads >= 0 ? L.threads : 1;
+        if (L.kind == "conv") add(buildConvolutionalLayer(L.name, L.xd, L.yd, L.zd, L.xs, L.ys, L.xf, L.yf, L.nf, th, in));
+        else if (L.kind == "pool") add(buildPoolingLayer(L.name, L.xd, L.yd, L.zd, L.xs, L.ys, L.xf, L.yf));
+        else if (L.kind == "avgpool") add(buildAvgPoolingLayer(L.name, L.xd, L.yd, L.zd, L.xs, L.ys, L.xf, L.yf));
+        else if (L.kind == "bn") add(buildBatchNormLayer(L.name, L.zd, in));
+        else if (L.kind == "square") add(buildSquareLayer(L.name, th));
+        else if (L.kind == "fc") add(buildFullyConnectedLayer(L.name, L.zd * L.xd * L.yd, L.out_dim, th, in));
+        else add(buildPaddingLayer(L.name, L.xd, L.yd, L.zd, L.px, L.py));
+    }
+    net.input_zd = d.zd; net.input_xd = d.xd; net.input_yd = d.yd;
+    net.layer_before_reenc = d.layer_before_reenc;
     return net;
 }
 Network CnnBuilder::buildAndSaveNetwork(string file_name)

@@ -267,6 +267,20 @@ public:
     AvgPoolingLayer(std::string name, int xd, int yd, int zd, int xs, int ys, int xf, int yf);
 };
 
+// Zero padding of the two spatial dimensions (no layer of the reference, whose convolution is valid-only): px all-zero ciphertexts on both sides of the
+// first dimension, py on both sides of the second (crc_pad).  The all-zero ciphertext is BFV's additive identity in either form, so the layer keeps its
+// input's form, like PoolingLayer, and takes canonical CRC_COEFF or CRC_NTT rows only: Network::forward plans the layer in front of it as it plans the layer
+// in front of a pooling layer, and no packed or limb hand-over spans it.  Nothing to save or load
+class PaddingLayer : public Layer {
+public:
+    int xd, yd, zd, px, py, xo, yo, zo;
+    PaddingLayer(std::string name, int xd, int yd, int zd, int px, int py);
+    ciphertext3D forward(ciphertext3D input) override;
+    void savePlaintextParameters(std::ostream *) override {}
+    void loadPlaintextParameters(std::istream *) override {}
+    void printLayerStructure() override;
+};
+
 class SquareLayer : public Layer {                          // squareLayer.h:12
 public:
     int th_count;
@@ -331,6 +345,11 @@ public:
 class Network {
 public:
     std::vector<std::shared_ptr<Layer>> layers;
+    // shape of one input image, [zd][xd][yd]: what the description the network was built from says (CrCNN's three models: 1 x 28 x 28)
+    int input_zd = 1, input_xd = 28, input_yd = 28;
+    // the layer list as a description (NetworkDescription, INTEGRATION.md "Network descriptions") that CnnBuilder::buildNetworkFromDescription builds back
+    // into this network, refresh point included.  It describes the layers as built: std::logic_error once fuse() has folded some
+    std::string describe() const;
     // network.cpp:23 hard-codes a client-side decrypt/re-encrypt "refresh" before layer 6; it needs the secret key and is off
     // the accelerated path, so it is a setting here: 6 reproduces the committed reference, -1 (default) never refreshes.
     int layer_before_reenc = -1;
@@ -397,6 +416,9 @@ public:
     // b' = b - sum_taps w' (*) mean[channel]).  The network's output ciphertexts stay bit-identical; only the folded layers'
     // intermediate tensors disappear (their plaintext parameters can no longer be saved).  Returns the number of layers removed.
     int fuse();
+private:
+    bool fused_ = false;
+public:
     // Multi-GPU start-up (no analogue in the reference): one process (or host thread) per GPU, images sharded across them
     // with no data-path collective.  Rank `root` holds the encoded model -- this call lifts + NTTs its plaintext parameters if that has
     // not happened yet -- and every other rank receives the NTT-form weights / bias / batch-norm rows and the evaluation keys over RCCL
@@ -407,6 +429,37 @@ public:
     // model file it read (the 2 MB of floats instead of 35-200 GB of residues on the wire; the same placement agreement and the same checksum comparison).
     size_t broadcastParameters(crc_comm *comm, int root = 0, bool encode_locally = false);
 };
+
+// ---- network descriptions ------------------------------------------------------------------------------------------------
+// A layer list as text (INTEGRATION.md "Network descriptions"; crcnn_amd/netrun.py parses the same format with the same checks): `#` comments, first
+//   input zd xd yd
+// then one layer per line, the input shape of each inferred from the line above:
+//   conv NAME stride xs ys filter xf yf filters nf      pool | avgpool NAME stride xs ys window xf yf      bn NAME      square NAME
+//   fc NAME out_dim      pad NAME px py      refresh (sets layer_before_reenc to the next layer; at most one)
+// conv, fc and square lines may end in `threads N` (the th_count the reference's constructors take).  NAME is the HDF5 dataset prefix.
+// Every error is a std::invalid_argument whose message starts with "line N:".
+struct LayerSpec {
+    std::string kind, name;
+    int line = 0;
+    int zd = 0, xd = 0, yd = 0;                             // the layer's input shape
+    int xs = 0, ys = 0, xf = 0, yf = 0, nf = 0;             // conv / pool / avgpool
+    int out_dim = 0;                                        // fc (in_dim = zd xd yd, the reference's reshapeInput order)
+    int px = 0, py = 0;                                     // pad
+    int threads = -1;                                       // -1: no `threads` token (the layer is built with th_count 1)
+    int zo = 0, xo = 0, yo = 0;                             // output shape
+};
+struct NetworkDescription {
+    int zd = 1, xd = 28, yd = 28;
+    int layer_before_reenc = -1;
+    std::vector<LayerSpec> layers;
+    // h5_path != "": the weight, bias and batch-norm datasets of the model file are checked against the inferred shapes
+    static NetworkDescription parse(const std::string &text, const std::string &h5_path = "");
+    // text (anything with a line break), the name of a built-in model, or the path of a description file
+    static NetworkDescription load(const std::string &text_name_or_path, const std::string &h5_path = "");
+    std::string str() const;                                // canonical form: parse(str()) gives the same description
+};
+// the description of "PlainModelTiny" | "ApproxPlainModel" | "PlainModelWoPad" (crcnn_amd/models/<name>.net, compiled in); nullptr for any other name
+const char *builtinDescription(const std::string &model);
 
 // ---- model loader + builder (CrCNN/src/cnnBuilder.h:16-44) ----------------------------------------------------------
 class CnnBuilder {
@@ -421,9 +474,14 @@ public:
     PoolingLayer *buildPoolingLayer(std::string name, int xd, int yd, int zd, int xs, int ys, int xf, int yf);
     AvgPoolingLayer *buildAvgPoolingLayer(std::string name, int xd, int yd, int zd, int xs, int ys, int xf, int yf);
     SquareLayer *buildSquareLayer(std::string name, int th_count);
+    PaddingLayer *buildPaddingLayer(std::string name, int xd, int yd, int zd, int px, int py);
     BatchNormLayer *buildBatchNormLayer(std::string name, int num_channels, std::istream *infile);
-    // cnnBuilder.cpp:108-179 hard-codes one topology per source edit (Tiny is the committed one); all three are available here
+    // cnnBuilder.cpp:108-179 hard-codes one topology per source edit (Tiny is the committed one); all three are available here, and any other as a description
     Network buildNetwork(std::string file_name = "");                  // PlainModelTiny, as committed (cnnBuilder.cpp:157-169)
-    Network buildNetworkByName(const std::string &model, std::string file_name = "");   // "PlainModelTiny" | "ApproxPlainModel" | "PlainModelWoPad"
+    // "PlainModelTiny" | "ApproxPlainModel" | "PlainModelWoPad" (built from their compiled-in descriptions), or the path of a description file
+    Network buildNetworkByName(const std::string &model, std::string file_name = "");
+    // any layer list: description text, a built-in name or the path of a description file (NetworkDescription::load).  The model file's datasets are checked
+    // against the inferred shapes before anything is encoded (not when the parameters come from the encoded-model file `file_name`)
+    Network buildNetworkFromDescription(const std::string &path_or_text, std::string file_name = "");
     Network buildAndSaveNetwork(std::string file_name);
 };

@@ -23,9 +23,12 @@ int main(int argc, char **argv)
     try {
         ifstream f(images, ios::binary);
         if (!f) throw runtime_error("cannot open " + images);
-        f.seekg(0, ios::end); const size_t cnt = (size_t)f.tellg() / (784 * 4); f.seekg(0);
-        vector<vector<float>> test_set(cnt, vector<float>(784));
-        for (auto &im : test_set) f.read((char *)im.data(), 784 * 4);
+        // <model>: a built-in name or the path of a description file; the images have the description's input shape (784 floats for CrCNN's models)
+        const NetworkDescription desc = NetworkDescription::load(model);
+        const size_t px = (size_t)desc.zd * desc.xd * desc.yd;
+        f.seekg(0, ios::end); const size_t cnt = (size_t)f.tellg() / (px * 4); f.seekg(0);
+        vector<vector<float>> test_set(cnt, vector<float>(px));
+        for (auto &im : test_set) f.read((char *)im.data(), px * 4);
 
         setParameters(poly_modulus, plain_modulus);
         CnnBuilder build(h5);
@@ -43,7 +46,7 @@ int main(int argc, char **argv)
             const vector<float> logits_plain = plainModelForward(build, model, test_set[i]);
             const int expected = (int)(max_element(logits_plain.begin(), logits_plain.end()) - logits_plain.begin());
             cout << "OUTPUT: " << i << ",";
-            ciphertext3D encrypted_image = encryptImage(test_set[i], 1, 28, 28);
+            ciphertext3D encrypted_image = encryptImage(test_set[i], desc.zd, desc.xd, desc.yd);
             exit_status_forward ret_value = SUCCESS;
             int predicted = -1;
             try {

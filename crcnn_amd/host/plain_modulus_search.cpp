@@ -100,32 +100,30 @@ Cube fcF(Cube &in, const vector<float> &w, const vector<float> &b, int out_dim)
     for (int r = 0; r < out_dim; r++) { double acc = b[r]; for (size_t c = 0; c < in_dim; c++) acc += (double)w[(size_t)r * in_dim + c] * in.v[c]; o.v[r] = (float)acc; }
     return o;
 }
+Cube padF(Cube &in, int px, int py)
+{
+    Cube o{in.z, in.x + 2 * px, in.y + 2 * py, {}}; o.v.assign((size_t)o.z * o.x * o.y, 0.f);
+    for (int c = 0; c < in.z; c++) for (int i = 0; i < in.x; i++) for (int j = 0; j < in.y; j++) o.at(c, i + px, j + py) = in.at(c, i, j);
+    return o;
+}
 }   // namespace
 
 vector<float> plainModelForward(CnnBuilder &build, const string &model, const vector<float> &image)
-{   // the layer lists of cnnBuilder.cpp:115-169, in float
-    if (image.size() != 28 * 28) throw invalid_argument("plainModelForward expects a 28x28 image");
-    auto P = [&](const char *name) { return build.getPretrained(name); };
-    Cube t{1, 28, 28, image};
-    if (model == "PlainModelTiny") {
-        t = convF(t, P("pool1_features.conv1.weight"), P("pool1_features.conv1.bias"), 1, 1, 5, 5, 32);
-        t = poolF(t, 2, 2, 2, 2, true);
-        t = convF(t, P("pool2_features.conv2.weight"), P("pool2_features.conv2.bias"), 1, 1, 5, 5, 64);
-        t = poolF(t, 2, 2, 2, 2, true);
-        t = fcF(t, P("classifier.fc3.weight"), P("classifier.fc3.bias"), 512);
-        t = fcF(t, P("classifier.fc4.weight"), P("classifier.fc4.bias"), 10);
-    } else if (model == "ApproxPlainModel" || model == "PlainModelWoPad") {
-        const bool avg = model == "ApproxPlainModel";
-        t = convF(t, P("pool1_features.conv1.weight"), P("pool1_features.conv1.bias"), 2, 2, 5, 5, 20);
-        t = poolF(t, 1, 1, 2, 2, avg);
-        bnF(t, P("pool1_features.norm1.running_mean"), P("pool1_features.norm1.running_var"));
-        t = convF(t, P("pool2_features.conv2.weight"), P("pool2_features.conv2.bias"), 2, 2, 3, 3, 50);
-        for (float &v : t.v) v = v * v;
-        t = poolF(t, 1, 1, 2, 2, avg);
-        bnF(t, P("pool2_features.norm2.running_mean"), P("pool2_features.norm2.running_var"));
-        t = fcF(t, P("classifier.fc3.weight"), P("classifier.fc3.bias"), 500);
-        t = fcF(t, P("classifier.fc4.weight"), P("classifier.fc4.bias"), 10);
-    } else throw invalid_argument("unknown model " + model);
+{   // the layer list of the model's description (the built-in ones: cnnBuilder.cpp:115-169), in float
+    const NetworkDescription d = NetworkDescription::load(model);
+    if (image.size() != (size_t)d.zd * d.xd * d.yd)
+        throw invalid_argument("plainModelForward expects a " + to_string(d.zd) + "x" + to_string(d.xd) + "x" + to_string(d.yd) + " image");
+    auto P = [&](const string &name) { return build.getPretrained(name); };
+    Cube t{d.zd, d.xd, d.yd, image};
+    for (const LayerSpec &L : d.layers) {
+        if (L.kind == "conv") t = convF(t, P(L.name + ".weight"), P(L.name + ".bias"), L.xs, L.ys, L.xf, L.yf, L.nf);
+        else if (L.kind == "pool" || L.kind == "avgpool") t = poolF(t, L.xs, L.ys, L.xf, L.yf, L.kind == "avgpool");
+        else if (L.kind == "bn") bnF(t, P(L.name + ".running_mean"), P(L.name + ".running_var"));
+        else if (L.kind == "square") { for (float &v : t.v) v = v * v; }
+        else if (L.kind == "fc") t = fcF(t, P(L.name + ".weight"), P(L.name + ".bias"), L.out_dim);
+        else if (L.kind == "pad") t = padF(t, L.px, L.py);
+        else throw invalid_argument("plainModelForward: unknown layer kind " + L.kind);
+    }
     return t.v;
 }
 
@@ -208,7 +206,7 @@ exit_status_forward PlainModulusSearch::testPlainModulus(CnnBuilder &build, uint
     for (int i = 0; i < num_images_to_test; i++) {
         const int img_test = min(distribution(generator), (int)test_set.size() - 1);
         picks.push_back(img_test);
-        enc.push_back(encryptImage(test_set[img_test], 1, 28, 28));
+        enc.push_back(encryptImage(test_set[img_test], net.input_zd, net.input_xd, net.input_yd));
     }
     try {
         // all picked images go through the network as one batch; the reference runs them one after the other and stops at the

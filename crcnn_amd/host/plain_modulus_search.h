@@ -37,7 +37,8 @@ uint64_t minSmallModulusinCoeffModulus(int max_poly_modulus);                   
 
 struct PlainModulusSearch {
     // what the reference keeps in file-level globals (:16-19) and hard-codes inside the functions (:32, :41)
-    std::string model = "ApproxPlainModel";                  // topology behind path_to_model (cnnBuilder.cpp:108-179 selects it by source edit)
+    // topology behind path_to_model (cnnBuilder.cpp:108-179 selects it by source edit): a built-in name, or the path of a description file
+    std::string model = "ApproxPlainModel";
     int max_poly_modulus = 4096;
     std::vector<uint64_t> coeff_modulus;                     // empty: coeff_modulus_128(max_poly_modulus)
     std::vector<std::vector<float>> test_set;                // normalised images

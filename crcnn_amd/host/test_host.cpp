@@ -1,6 +1,11 @@
 // test_host.cpp -- driver for the C++ host classes, run by tests/test_gpu_host_cpp.py on the GPU box.
 //   test_host net <model> <h5> <dir> <resident 0|1> <batch> [fuse 0|1]      (fuse: Network::fuse() before the resident forward)
 //     <dir>/params.u64 (n,k,t,q...), evk.u64, net_in.u64 ([1][1][28][28][2][k][n]) -> writes layer_<i>.u64 (layerwise mode) and out.u64
+//     <model>: a built-in name or the path of a description file, here and in net3 / netr / netseeded / search (netr: a <layer_before_reenc> of -1 keeps the
+//     description's refresh point)
+//   test_host describe <name | description file> [h5]     parse and validate a description (with h5: dataset sizes too); prints its canonical form.  No GPU work
+//   test_host labels <model> <h5> <images.f32>     argmax of plainModelForward per image ("label <i> <class>").  No GPU work
+//   test_host build <description> <h5> <dir> <batch>     see do_build
 //   test_host api <h5> <dir>     exercises save/load of the encoded model, client-side encrypt/decrypt, and error behaviour
 //   test_host files <dir>        CrCNN's own files: loads the encoded-model stream and the cipher_image file the REFERENCE wrote (<dir>/ref_encoded_layers.bin,
 //     ref_cipher_image.bin; cnnBuilder.cpp:181-196, globals.cpp:174-205), runs conv -> bn -> dense on them (out_from_ref_files.u64), then writes the same two
@@ -57,7 +62,7 @@ static int do_net(int argc, char **argv)
     if (argc > 9) net.matrix_cores = atoi(argv[9]) != 0;
     auto x = rd(dir + "/net_in.u64");
     vector<ciphertext3D> imgs;
-    for (int b = 0; b < batch; b++) imgs.push_back(ciphertext3D::fromHost(x.data(), 1, 1, 28, 28));
+    for (int b = 0; b < batch; b++) imgs.push_back(ciphertext3D::fromHost(x.data(), 1, net.input_zd, net.input_xd, net.input_yd));
     ciphertext3D in = stackImages(imgs);
     if (!resident) {      // layer by layer, coefficient form at every boundary: dump each output for the per-layer digests
         ciphertext3D t = in;
@@ -95,7 +100,7 @@ static int do_net3(int argc, char **argv)
     Network net = builder.buildNetworkByName(model);
     net.ntt_resident = true;
     auto x = rd(dir + "/net_in.u64");
-    const ciphertext3D one = ciphertext3D::fromHost(x.data(), 1, 1, 28, 28);
+    const ciphertext3D one = ciphertext3D::fromHost(x.data(), 1, net.input_zd, net.input_xd, net.input_yd);
     // (the unfused run leaves the weights in the matrix-core forms; Network::fuse() rebuilds the canonical ones from the plaintexts before it folds)
     { ciphertext3D out = net.forward(one); wr(dir + "/out_unfused.u64", out.toHost()); }
     const int removed = net.fuse();
@@ -115,7 +120,7 @@ static int do_net3(int argc, char **argv)
 static int do_netr(int argc, char **argv)
 {
     if (argc < 9) return 1;
-    string model = argv[2], h5 = argv[3], dir = argv[4]; const int batch = atoi(argv[5]), reenc = atoi(argv[6]); const bool fuse = atoi(argv[7]) != 0;
+    string model = argv[2], h5 = argv[3], dir = argv[4]; const int batch = atoi(argv[5]); int reenc = atoi(argv[6]); const bool fuse = atoi(argv[7]) != 0;
     const int head_chunk = atoi(argv[8]);
     setDeterministicSeed(4242);
     setup(dir);
@@ -125,8 +130,9 @@ static int do_netr(int argc, char **argv)
       crc_memcpy_h2d(context, ev_keys16->ptr, evk.data(), evk.size() * 8, nullptr); crc_stream_sync(context, nullptr); }
     CnnBuilder builder(h5);
     Network net = builder.buildNetworkByName(model);
+    if (reenc < 0) reenc = net.layer_before_reenc;          // the description's own refresh point
     auto x = rd(dir + "/net_in.u64");
-    const ciphertext3D one = ciphertext3D::fromHost(x.data(), 1, 1, 28, 28);
+    const ciphertext3D one = ciphertext3D::fromHost(x.data(), 1, net.input_zd, net.input_xd, net.input_yd);
     if (!fuse) {
         ciphertext3D t = one;
         for (int i = 0; i < reenc; i++) { net.getLayer(i)->out_form = CRC_COEFF; t = net.getLayer(i)->forward(t); wr(dir + "/pre_" + to_string(i) + ".u64", t.toHost()); }
@@ -420,15 +426,100 @@ static int do_search(int argc, char **argv)
     const int num_images = atoi(argv[8]); s.seed = (unsigned)strtoul(argv[9], 0, 0);
     for (int i = 10; i < argc; i++) s.coeff_modulus.push_back(strtoull(argv[i], 0, 0));
     ifstream f(images, ios::binary); if (!f) { fprintf(stderr, "missing %s\n", images.c_str()); return 2; }
-    f.seekg(0, ios::end); const size_t cnt = (size_t)f.tellg() / (784 * 4); f.seekg(0);
-    s.test_set.assign(cnt, vector<float>(784));
-    for (auto &im : s.test_set) f.read((char *)im.data(), 784 * 4);
+    const NetworkDescription desc = NetworkDescription::load(s.model);
+    const size_t px = (size_t)desc.zd * desc.xd * desc.yd;
+    f.seekg(0, ios::end); const size_t cnt = (size_t)f.tellg() / (px * 4); f.seekg(0);
+    s.test_set.assign(cnt, vector<float>(px));
+    for (auto &im : s.test_set) f.read((char *)im.data(), px * 4);
     s.predictWithPlainModel(h5);
     for (size_t i = 0; i < cnt; i++) printf("label %zu %d\n", i, (int)s.predicted_labels[i]);
     const u64 found = s.run(num_images, lo, hi, h5);
     printf("found %llu\n", (unsigned long long)found);
     for (size_t i = 0; i < s.tried.size(); i++) printf("tried %llu %s %.2f\n", (unsigned long long)s.tried[i].first, status_name(s.tried[i].second),
         s.test_seconds[i]);
+    return 0;
+}
+
+// describe <name | description file> [h5]: the canonical form of a description on stdout; an invalid one ends in "exception: line N: ..." and status 10
+static int do_describe(int argc, char **argv)
+{
+    if (argc < 3) return 1;
+    fputs(NetworkDescription::load(argv[2], argc > 3 ? argv[3] : "").str().c_str(), stdout);
+    return 0;
+}
+
+// labels <model> <h5> <images.f32>: the float forward of the model's description on every image: "label <i> <argmax>" and "logits <i> <v0> <v1> ..."
+static int do_labels(int argc, char **argv)
+{
+    if (argc < 5) return 1;
+    const string model = argv[2];
+    const NetworkDescription desc = NetworkDescription::load(model);
+    const size_t px = (size_t)desc.zd * desc.xd * desc.yd;
+    ifstream f(argv[4], ios::binary); if (!f) { fprintf(stderr, "missing %s\n", argv[4]); return 2; }
+    f.seekg(0, ios::end); const size_t cnt = (size_t)f.tellg() / (px * 4); f.seekg(0);
+    CnnBuilder build(argv[3]);
+    PlainModulusSearch s;
+    s.model = model;
+    s.test_set.assign(cnt, vector<float>(px));
+    for (auto &im : s.test_set) f.read((char *)im.data(), px * 4);
+    s.predictWithPlainModel(argv[3]);
+    for (size_t i = 0; i < cnt; i++) {
+        printf("label %zu %d\n", i, (int)s.predicted_labels[i]);
+        printf("logits %zu", i);
+        for (float v : plainModelForward(build, model, s.test_set[i])) printf(" %.9g", v);
+        printf("\n");
+    }
+    return 0;
+}
+
+// build <description> <h5> <dir> <batch>: one network built from a description (<dir> as for `net`: params.u64, evk.u64, net_in.u64 = one encrypted image of
+// the description's input shape), run four ways:
+//   layer by layer in coefficient form      -> layer_<i>.u64, and one line "layer <i> <kind> <name> <zd> <xd> <yd> <fnv-1a 64 of the tensor>" per layer
+//   Network::forward, NTT-resident           -> out_unfused.u64
+//   after Network::fuse()                    -> out_fused.u64, and on <batch> images out_fused_batch.u64
+// Prints "describe-ok" when Network::describe() is the description's canonical form and builds back to the same text, and the layer names after fuse()
+// ("fused <name> <name> ...")
+static int do_build(int argc, char **argv)
+{
+    if (argc < 6) return 1;
+    string desc = argv[2], h5 = argv[3], dir = argv[4]; const int batch = atoi(argv[5]);
+    setup(dir);
+    { auto evk = rd(dir + "/evk.u64");
+      ev_keys16 = make_shared<DeviceBuffer>(evk.size() * 8);
+      crc_memcpy_h2d(context, ev_keys16->ptr, evk.data(), evk.size() * 8, nullptr); crc_stream_sync(context, nullptr); }
+    CnnBuilder builder(h5);
+    Network net = builder.buildNetworkFromDescription(desc);
+    const string canon = NetworkDescription::load(desc).str();
+    if (net.describe() != canon) { fprintf(stderr, "describe() differs from the canonical form:\n%s", net.describe().c_str()); return 4; }
+    if (builder.buildNetworkFromDescription(net.describe()).describe() != canon) { fprintf(stderr, "describe() does not build back\n"); return 4; }
+    printf("describe-ok\n");
+    auto x = rd(dir + "/net_in.u64");
+    const ciphertext3D one = ciphertext3D::fromHost(x.data(), 1, net.input_zd, net.input_xd, net.input_yd);
+    {
+        ciphertext3D t = one;
+        for (int i = 0; i < net.getNumLayers(); i++) {
+            net.getLayer(i)->out_form = CRC_COEFF;
+            t = net.getLayer(i)->forward(t);
+            const vector<u64> h = t.toHost();
+            u64 fnv = 1469598103934665603ULL;
+            for (size_t j = 0; j < h.size() * 8; j++) fnv = (fnv ^ ((const unsigned char *)h.data())[j]) * 1099511628211ULL;
+            wr(dir + "/layer_" + to_string(i) + ".u64", h);
+            const string kind = NetworkDescription::load(desc).layers[i].kind;
+            printf("layer %d %s %s %d %d %d %016llx\n", i, kind.c_str(), net.getLayer(i)->getName().c_str(), t.zd, t.xd, t.yd, (unsigned long long)fnv);
+        }
+    }
+    net.ntt_resident = true;
+    { ciphertext3D out = net.forward(one); wr(dir + "/out_unfused.u64", out.toHost()); }
+    const int removed = net.fuse();
+    fprintf(stderr, "fused: %d layers removed, %d left\n", removed, net.getNumLayers());
+    printf("fused");
+    for (int i = 0; i < net.getNumLayers(); i++) printf(" %s", net.getLayer(i)->getName().c_str());
+    printf("\n");
+    { ciphertext3D out = net.forward(one); wr(dir + "/out_fused.u64", out.toHost()); }
+    vector<ciphertext3D> imgs(batch, one);
+    { ciphertext3D out = net.forward(stackImages(imgs)); wr(dir + "/out_fused_batch.u64", out.toHost()); }
+    delParameters();
+    printf("build ok\n");
     return 0;
 }
 
@@ -634,6 +725,9 @@ int main(int argc, char **argv)
         if (!strcmp(argv[1], "files")) return do_files(argc, argv);
         if (!strcmp(argv[1], "searchlogic")) return do_searchlogic(argc, argv);
         if (!strcmp(argv[1], "search")) return do_search(argc, argv);
+        if (!strcmp(argv[1], "describe")) return do_describe(argc, argv);
+        if (!strcmp(argv[1], "labels")) return do_labels(argc, argv);
+        if (!strcmp(argv[1], "build")) return do_build(argc, argv);
     } catch (const exception &e) { fprintf(stderr, "exception: %s\n", e.what()); return 10; }
     return 1;
 }

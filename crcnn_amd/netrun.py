@@ -1,7 +1,7 @@
 """Python driver for whole CrCNN networks on the engine (used by bench.py and the tests).
 
-Mirrors CnnBuilder::buildNetwork (CrCNN/src/cnnBuilder.cpp:108-179): the three hard-coded topologies, weights read from
-the HDF5 model by dataset name, every float encoded with the fractional encoder, then `Network::forward`
+Mirrors CnnBuilder::buildNetwork (CrCNN/src/cnnBuilder.cpp:108-179): the three topologies the reference hard-codes, or any layer list a description file
+gives (parse_description; zero padding included), weights read from the HDF5 model by dataset name, every float encoded with the fractional encoder, then `Network::forward`
 (network.cpp:22-47) layer by layer over a batch of encrypted images.  All arithmetic happens in libcrcnn_hip.so; this
 file only sequences C-ABI calls and owns device buffers.  The C++ twin of this logic is crcnn_amd/host/.
 """
@@ -40,7 +40,197 @@ TOPOLOGIES = {
 TOPOLOGIES["PlainModelWoPad"] = [(("pool" if k == "avgpool" else k), n, a) for (k, n, a) in TOPOLOGIES["ApproxPlainModel"]]
 
 
+MODELS_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "models")      # the built-in descriptions: <name>.net, one per entry of TOPOLOGIES
+
+
+# ---- layer description files ("Network descriptions"): plain text, one layer per line, shapes inferred from the line above.
+# CnnBuilder::buildNetworkFromDescription (crcnn_amd/host) reads the same format, applies the same checks and prints the same canonical form
+class Description(list):
+    """the (kind, name, args) list TOPOLOGIES holds, with what else a description says: the input shape (zd, xd, yd), the layer the client-side refresh sits in
+    front of (-1: none), the `threads` token of every layer (None where there is none) and the source line of every layer"""
+    input_shape = (1, 28, 28)
+    layer_before_reenc = -1
+
+    def __init__(self, layers=(), input_shape=(1, 28, 28), layer_before_reenc=-1, threads=None, lines=None):
+        super().__init__(layers)
+        self.input_shape, self.layer_before_reenc = tuple(input_shape), layer_before_reenc
+        self.threads = list(threads) if threads is not None else [None] * len(self)
+        self.lines = list(lines) if lines is not None else [0] * len(self)
+
+
+def window_ok(xd, yd, xs, ys, xf, yf):
+    """shapes crc_conv2d / crc_pool take: the window fits, and the stride leaves no trailing outputs the reference would leave as empty ciphertexts
+    (Layer::computeBoundaries stops at xd - max(xf, xs) + 1 but the result is sized (xd - xf) / xs + 1)"""
+    if min(xd, yd, xs, ys, xf, yf) < 1 or xf > xd or yf > yd:
+        return False
+    xl, yl = xd - max(xf, xs) + 1, yd - max(yf, ys) + 1
+    if xl < 1 or yl < 1:
+        return False
+    return (xl + xs - 1) // xs == (xd - xf) // xs + 1 and (yl + ys - 1) // ys == (yd - yf) // ys + 1
+
+
+_KEYS = {"conv": (("stride", 2), ("filter", 2), ("filters", 1)), "pool": (("stride", 2), ("window", 2)), "avgpool": (("stride", 2), ("window", 2))}
+_THREADED = ("conv", "fc", "square")
+
+
+def parse_description(text, dataset_count=None):
+    """description text -> Description.  Every error is a ValueError that starts with "line N:".  dataset_count(name) -> number of elements of an HDF5
+    dataset (None: absent): given, the weight, bias and batch-norm datasets are checked against the inferred shapes"""
+    layers, threads, lines = [], [], []
+    shape, refresh, pending_refresh, flat = None, -1, 0, False
+
+    def ints(ln, toks, what):
+        try:
+            v = [int(t) for t in toks]
+        except ValueError:
+            raise ValueError(f"line {ln}: {what}: expected integers, got {' '.join(toks)!r}") from None
+        if any(x < 0 for x in v):
+            raise ValueError(f"line {ln}: {what}: negative value")
+        return v
+
+    def check(ln, name, count):
+        if dataset_count is None:
+            return
+        have = dataset_count(name)
+        if have is None:
+            raise ValueError(f"line {ln}: the model has no dataset {name}")
+        if have != count:
+            raise ValueError(f"line {ln}: dataset {name} holds {have} values, the layer needs {count}")
+
+    for ln, raw in enumerate(text.splitlines(), 1):
+        tok = raw.split("#", 1)[0].split()
+        if not tok:
+            continue
+        kind = tok[0]
+        if shape is None:
+            if kind != "input" or len(tok) != 4:
+                raise ValueError(f"line {ln}: the first line must be `input zd xd yd`")
+            shape = tuple(ints(ln, tok[1:], "input"))
+            if min(shape) < 1:
+                raise ValueError(f"line {ln}: input: dimensions must be positive")
+            in_shape = shape
+            continue
+        if kind == "refresh":
+            if len(tok) != 1:
+                raise ValueError(f"line {ln}: unknown token {tok[1]!r} after refresh")
+            if refresh >= 0 or pending_refresh:
+                raise ValueError(f"line {ln}: a second refresh (line {pending_refresh or lines[refresh]} has the first)")
+            pending_refresh = ln
+            continue
+        if kind not in ("conv", "pool", "avgpool", "bn", "square", "fc", "pad"):
+            raise ValueError(f"line {ln}: unknown layer kind {kind!r}")
+        if len(tok) < 2:
+            raise ValueError(f"line {ln}: {kind}: the layer name is missing")
+        name, rest = tok[1], tok[2:]
+        th = None
+        if len(rest) >= 2 and rest[-2] == "threads":
+            if kind not in _THREADED:
+                raise ValueError(f"line {ln}: unknown token 'threads' for a {kind} layer")
+            th = ints(ln, rest[-1:], "threads")[0]
+            rest = rest[:-2]
+        zd, xd, yd = shape
+        if flat and kind in ("conv", "pool", "avgpool", "pad"):
+            raise ValueError(f"line {ln}: a {kind} layer cannot follow a fully connected layer: the tensor is flat ({xd} values)")
+        if kind in _KEYS:
+            vals, pos = {}, 0
+            for key, cnt in _KEYS[kind]:
+                if pos >= len(rest) or rest[pos] != key:
+                    raise ValueError(f"line {ln}: {kind}: expected `{key}`, got {(rest[pos] if pos < len(rest) else 'end of line')!r}")
+                vals[key] = ints(ln, rest[pos + 1:pos + 1 + cnt], key)
+                if len(vals[key]) != cnt:
+                    raise ValueError(f"line {ln}: {kind}: `{key}` takes {cnt} value(s)")
+                pos += 1 + cnt
+            if pos != len(rest):
+                raise ValueError(f"line {ln}: unknown token {rest[pos]!r}")
+            (xs, ys), (xf, yf) = vals["stride"], vals["filter" if kind == "conv" else "window"]
+            if min(xs, ys, xf, yf) < 1:
+                raise ValueError(f"line {ln}: {kind}: strides and window sizes must be positive")
+            if xf > xd or yf > yd:
+                raise ValueError(f"line {ln}: {kind}: the {xf} x {yf} window is larger than its {xd} x {yd} input")
+            if not window_ok(xd, yd, xs, ys, xf, yf):
+                raise ValueError(f"line {ln}: {kind}: stride {xs} x {ys} over a {xf} x {yf} window leaves a remainder of the {xd} x {yd} input without outputs")
+            a = dict(xd=xd, yd=yd, zd=zd, xs=xs, ys=ys, xf=xf, yf=yf)
+            if kind == "conv":
+                a["nf"] = vals["filters"][0]
+                if a["nf"] < 1:
+                    raise ValueError(f"line {ln}: conv: filters must be positive")
+                check(ln, name + ".weight", a["nf"] * zd * xf * yf); check(ln, name + ".bias", a["nf"])
+        elif kind == "fc":
+            if len(rest) != 1:
+                raise ValueError(f"line {ln}: " + (f"unknown token {rest[1]!r}" if len(rest) > 1 else "fc: out_dim is missing"))
+            a = dict(in_dim=zd * xd * yd, out_dim=ints(ln, rest, "out_dim")[0])
+            if a["out_dim"] < 1:
+                raise ValueError(f"line {ln}: fc: out_dim must be positive")
+            check(ln, name + ".weight", a["in_dim"] * a["out_dim"]); check(ln, name + ".bias", a["out_dim"])
+        elif kind == "pad":
+            if len(rest) != 2:
+                raise ValueError(f"line {ln}: " + (f"unknown token {rest[2]!r}" if len(rest) > 2 else "pad: takes px py"))
+            px, py = ints(ln, rest, "pad")
+            a = dict(zd=zd, xd=xd, yd=yd, px=px, py=py)
+        else:
+            if rest:
+                raise ValueError(f"line {ln}: unknown token {rest[0]!r}")
+            a = dict(ch=zd) if kind == "bn" else dict()
+            if kind == "bn":
+                check(ln, name + ".running_mean", zd); check(ln, name + ".running_var", zd)
+        if pending_refresh:
+            refresh, pending_refresh = len(layers), 0
+        layers.append((kind, name, a)); threads.append(th); lines.append(ln)
+        shape = out_shape(kind, a, shape)
+        flat = flat or kind == "fc"
+    if shape is None:
+        raise ValueError("line 1: the first line must be `input zd xd yd`")
+    if pending_refresh:
+        raise ValueError(f"line {pending_refresh}: refresh must be followed by a layer")
+    if not layers:
+        raise ValueError(f"line {ln}: the description has no layers")
+    return Description(layers, in_shape, refresh, threads, lines)
+
+
+def format_description(desc):
+    """the canonical text of a Description (what `test_host describe` prints and Network::describe() writes): parse_description(format_description(d)) == d"""
+    d = desc if isinstance(desc, Description) else Description(desc)
+    out = ["input %d %d %d" % d.input_shape]
+    for i, (kind, name, a) in enumerate(d):
+        if i == d.layer_before_reenc:
+            out.append("refresh")
+        if kind == "conv":
+            ln = f"conv {name} stride {a['xs']} {a['ys']} filter {a['xf']} {a['yf']} filters {a['nf']}"
+        elif kind in ("pool", "avgpool"):
+            ln = f"{kind} {name} stride {a['xs']} {a['ys']} window {a['xf']} {a['yf']}"
+        elif kind == "fc":
+            ln = f"fc {name} {a['out_dim']}"
+        elif kind == "pad":
+            ln = f"pad {name} {a['px']} {a['py']}"
+        else:
+            ln = f"{kind} {name}"
+        if d.threads[i] not in (None, 1):         # (1 is what a layer without the token is built with)
+            ln += f" threads {d.threads[i]}"
+        out.append(ln)
+    return "\n".join(out) + "\n"
+
+
+def load_description(model, h5_path=None):
+    """a built-in name, the path of a description file, description text (anything with a line break) or a (kind, name, args) list -> Description"""
+    if isinstance(model, Description):
+        return model
+    if not isinstance(model, str):
+        return Description(model)
+    count = None
+    if h5_path is not None:
+        names = set(binding.h5_list(h5_path))
+        count = lambda nm: binding.h5_count(h5_path, nm) if nm in names else None
+    if "\n" in model:
+        return parse_description(model, count)
+    path = os.path.join(MODELS_DIR, model + ".net") if model in TOPOLOGIES else model
+    if not os.path.exists(path):
+        raise ValueError(f"{model!r} is neither a built-in model ({', '.join(TOPOLOGIES)}) nor a description file")
+    return parse_description(open(path).read(), count)
+
+
 def out_shape(kind, a, in_shape):
+    if kind == "pad":
+        return (a["zd"], a["xd"] + 2 * a["px"], a["yd"] + 2 * a["py"])
     if kind == "conv":
         return (a["nf"], (a["xd"] - a["xf"]) // a["xs"] + 1, (a["yd"] - a["yf"]) // a["ys"] + 1)
     if kind in ("pool", "avgpool"):
@@ -68,7 +258,10 @@ class Network:
     """Encoded network resident in HBM.  `alloc(nbytes)` must return an object Engine.p() understands."""
 
     def __init__(self, eng, model, h5_path=None, weights=None, alloc=None, resident=True, encode_chunk=2048, dbc=16, d_evk=None, materialize=True, fuse_pool=None, limb=None):
-        self.E, self.model, self.topo = eng, model, TOPOLOGIES[model]
+        # `model`: a built-in name, the path of a description file, description text or a (kind, name, args) list
+        self.E, self.model, self.topo = eng, model, load_description(model, h5_path)
+        if self.topo.layer_before_reenc >= 0:
+            raise ValueError("this driver has no client side: a description with a refresh point runs through the C++ Network (crcnn_amd/host)")
         # conv / dense layers with long reductions run on the matrix cores (operand form CRC_NTTL, kernels_mfma.hip) unless CRC_MFMA=0
         self.limb = (os.environ.get("CRC_MFMA", "1") != "0") if limb is None else limb
         self._limbed = False
@@ -89,7 +282,7 @@ class Network:
         get = (lambda nm: np.asarray(weights[nm], dtype=np.float32)) if weights is not None else (lambda nm: binding.h5_read(h5_path, nm))
         self._keep = []
         mid_form = NTT if resident else COEFF
-        shape = (1, 28, 28)
+        shape = self.in_shape = self.topo.input_shape
         form = COEFF
         self.plan = []
         for li, (kind, name, a) in enumerate(self.topo):
@@ -123,6 +316,9 @@ class Network:
                 mean = get(name + ".running_mean"); var = get(name + ".running_var")
                 invstd = np.float32(1.0 / np.sqrt(var.astype(np.float64) + 0.00001))       # cnnBuilder.cpp:100-102
                 p["mean"] = self._delta(mean, form); p["invstd"] = self._encode_ntt(invstd, encode_chunk); p["form"] = form
+            elif kind == "pad":
+                # canonical rows in, the same form out (crc_pad): conv / dense layers around it are planned as around a pooling layer, without its packed hand-over
+                p["form"] = form
             elif kind == "square":
                 # crc_square_relin_forms takes and leaves NTT-resident tensors (one INTT inside feeds the BEHZ base extension)
                 p["in_form"] = form
@@ -650,7 +846,7 @@ class Network:
                         self.xltile, self._xltile_bytes = self.alloc(xl), xl
                 p["stream_kernel"] = "mfma_mac2w_kernel on 64-filter limb tiles" if g["limb"] else "mac3_kernel"
 
-    # ---- forward over one chunk of B images; d_x: [B][1][28][28] cts in coefficient form.  Returns device ptr of the
+    # ---- forward over one chunk of B images; d_x: [B] + in_shape cts in coefficient form ([B][1][28][28] for the built-in models).  Returns device ptr of the
     # [B][10] output cts (coefficient form).  `timer(i, name)` (optional) is called around every layer.
     def forward(self, d_x, B, timer=None):
         assert self.G == 1, "prepared for two-level chunking: use forward_group"
@@ -695,6 +891,9 @@ class Network:
                 cur = out
             elif kind in ("pool", "avgpool"):
                 E.pool(cur, B, a["zd"], a["xd"], a["yd"], a["xs"], a["ys"], a["xf"], a["yf"], p["div"], p["form"], out)
+                cur = out
+            elif kind == "pad":
+                E.pad(cur, B, a["zd"], a["xd"], a["yd"], a["px"], a["px"], a["py"], a["py"], p["form"], out)
                 cur = out
             elif kind == "bn":
                 if E.p(cur) != E.p(out):     # first layer: never modify the caller's input in place

@@ -290,6 +290,11 @@ int crc_pool(crc_ctx *ctx, const uint64_t *d_x, int B, int zd, int xd, int yd, i
              const uint64_t *d_div_ntt /* NULL = sum pool */, int form, uint64_t *d_y, void *stream);
 int crc_batchnorm(crc_ctx *ctx, uint64_t *d_x, int B, int zd, int xd, int yd, const uint64_t *d_mean_delta,
                   const uint64_t *d_invstd_ntt, int form, void *stream);
+/* Zero padding (no layer of the reference: its convolution is valid-only).  d_x [B][zd][xd][yd] ciphertexts -> d_y [B][zd][px0 + xd + px1][py0 + yd + py1]:
+ * the input in the interior, bit for bit, and all-zero ciphertexts -- the additive identity of BFV in either form -- on the border.  form: CRC_COEFF or
+ * CRC_NTT, kept (the packed and limb operand forms are refused).  CRC_ERR_INVALID_ARGUMENT for a negative pad, a null or not 16-byte aligned pointer and a
+ * d_y that overlaps d_x; a zero pad is a plain copy. */
+int crc_pad(crc_ctx *ctx, const uint64_t *d_x, int B, int zd, int xd, int yd, int px0, int px1, int py0, int py1, int form, uint64_t *d_y, void *stream);
 size_t crc_square_relin_work_bytes(const crc_ctx *ctx, size_t count, int dbc);
 int crc_square_relin(crc_ctx *ctx, const uint64_t *d_x, size_t count, const uint64_t *d_evk, int dbc,
                      uint64_t *d_y, void *d_work, void *stream);
