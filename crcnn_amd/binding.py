@@ -115,6 +115,11 @@ def load():
     L.crc_square_pool_relin_supported.argtypes = [VP, CI, CI, CI]
     L.crc_square_pool_relin_work_bytes.restype = SZ; L.crc_square_pool_relin_work_bytes.argtypes = [VP] + [CI] * 9
     L.crc_square_pool_relin_forms.argtypes = [VP, VP, CI] + [CI] * 8 + [VP, CI, VP, VP, CI, VP, VP]
+    L.crc_poly2_relin_work_bytes.restype = SZ; L.crc_poly2_relin_work_bytes.argtypes = [VP, SZ, CI]
+    L.crc_poly2_relin_forms.argtypes = [VP, VP, CI, SZ, VP, CI, VP, VP, VP, VP, CI, VP, VP]
+    L.crc_poly2_pool_relin_supported.argtypes = [VP, CI, CI, CI]
+    L.crc_poly2_pool_relin_work_bytes.restype = SZ; L.crc_poly2_pool_relin_work_bytes.argtypes = [VP] + [CI] * 9
+    L.crc_poly2_pool_relin_forms.argtypes = [VP, VP, CI] + [CI] * 8 + [VP, CI, VP, VP, VP, VP, CI, VP, VP]
     L.crc_conv2d_forms.argtypes = [VP, VP, VP, CI, VP] + [CI] * 9 + [CI, CI, VP, VP, VP]
     L.crc_dense_forms.argtypes = [VP, VP, VP, CI, VP, CI, CI, CI, CI, CI, VP, VP, VP]
     L.crc_pack28.argtypes = [VP, VP, SZ, CI, VP]
@@ -649,6 +654,69 @@ class Engine:
 
     def decode_dev(self, d_plain, count, d_out):
         _chk(self.L.crc_decode_dev(self.c, self.p(d_plain), count, self.p(d_out), self.stream), "crc_decode_dev")
+
+    # ---- degree-2 polynomial activation c2 x^2 + c1 x + c0 (crc_poly2_relin_forms / crc_poly2_pool_relin_forms)
+    def poly2_rows(self, c2, c1, c0, window=1, d_div=None):
+        """the three NTT-form plaintext rows [k][n] the poly2 calls take, None where a term is absent (c2 == 1, c1 == 0, c0 == 0): encode(c2) and encode(c1) as
+        crc_plain_to_ntt leaves them, encode(c0) in delta form.  For the pooled call the window count `window` (xf * yf) is folded into the constant term and an average
+        pooling's divisor `d_div` (NTT-form row) into all three -- exact ring arithmetic, done once"""
+        c2, c1, c0 = (float(np.float32(v)) for v in (c2, c1, c0))
+        if not all(np.isfinite(v) for v in (c2, c1, c0)) or c2 == 0.0:
+            raise ValueError("poly2_rows: c2 must be non-zero and every coefficient finite")
+        rowb = self.k * self.n * 8
+
+        def row(value, delta):
+            plain, _ = self.encode(np.array([value], dtype=np.float32))
+            d_plain = self.upload(plain); d_row = self.alloc(rowb)
+            if delta:
+                self.plain_to_delta(d_plain, 1, NTT, d_row)
+            else:
+                self.plain_to_ntt(d_plain, 1, d_row)
+            if d_div is not None:
+                self.multiply_plain_ntt(d_row, d_div, 1, 1, size=1)
+            self.sync()
+            return d_row
+        if c2 != 1.0:
+            d_p2 = row(c2, False)
+        elif d_div is not None:
+            d_p2 = self.alloc(rowb); self.copy_d2d(d_p2, d_div, rowb)
+        else:
+            d_p2 = None
+        d_p1 = row(c1, False) if c1 != 0.0 else None
+        d_p0 = None
+        if c0 != 0.0:
+            plain, _ = self.encode(np.array([c0], dtype=np.float32))
+            d_one = self.alloc(rowb); self.plain_to_delta(self.upload(plain), 1, NTT, d_one)
+            d_p0 = self.alloc(rowb); self.copy_d2d(d_p0, d_one, rowb)
+            for _ in range(int(window) - 1):
+                self.add(d_p0, d_one, 1, size=1)
+            if d_div is not None:
+                self.multiply_plain_ntt(d_p0, d_div, 1, 1, size=1)
+            self.sync()
+        return d_p2, d_p1, d_p0
+
+    def copy_d2d(self, d_dst, d_src, nbytes):
+        _chk(self.L.crc_memcpy_d2d(self.c, self.p(d_dst), self.p(d_src), nbytes, self.stream), "crc_memcpy_d2d")
+
+    def poly2_relin_work_bytes(self, count, dbc=16):
+        return self.L.crc_poly2_relin_work_bytes(self.c, count, dbc)
+
+    def poly2_relin(self, d_x, count, d_evk, d_p2, d_p1, d_p0, d_y, d_work, dbc=16, in_form=COEFF, out_form=COEFF):
+        """c2 x^2 + c1 x + c0 on `count` ciphertexts with one key switch each; d_p2 / d_p1 / d_p0: poly2_rows (None = 1 / 0 / 0)"""
+        _chk(self.L.crc_poly2_relin_forms(self.c, self.p(d_x), in_form, count, self.p(d_evk), dbc, self.p(d_p2), self.p(d_p1), self.p(d_p0), self.p(d_y), out_form,
+                                          self.p(d_work), self.stream), "crc_poly2_relin_forms")
+
+    def poly2_pool_relin_supported(self, xf, yf, dbc=16):
+        return bool(self.L.crc_poly2_pool_relin_supported(self.c, dbc, xf, yf))
+
+    def poly2_pool_relin_work_bytes(self, B, zd, xd, yd, xs, ys, xf, yf, dbc=16):
+        return self.L.crc_poly2_pool_relin_work_bytes(self.c, B, zd, xd, yd, xs, ys, xf, yf, dbc)
+
+    def poly2_pool_relin(self, d_x, B, zd, xd, yd, xs, ys, xf, yf, d_evk, d_p2, d_p1, d_p0, d_y, d_work, dbc=16, in_form=COEFF, out_form=COEFF):
+        """the polynomial activation followed by a sum / average pooling, one key switch per pooled ciphertext; the rows carry the window count and the divisor
+        (poly2_rows(..., window=xf * yf, d_div=...))"""
+        _chk(self.L.crc_poly2_pool_relin_forms(self.c, self.p(d_x), in_form, B, zd, xd, yd, xs, ys, xf, yf, self.p(d_evk), dbc, self.p(d_p2), self.p(d_p1), self.p(d_p0),
+                                               self.p(d_y), out_form, self.p(d_work), self.stream), "crc_poly2_pool_relin_forms")
 
     def encode_dev(self, d_values, count, d_plain, f64=False):
         f = self.L.crc_encode_dev_f64 if f64 else self.L.crc_encode_dev_f32

@@ -744,6 +744,98 @@ extern "C" int crc_square_pool_relin_forms(crc_ctx *c, const uint64_t *d_x, int 
     }
     return CRC_OK;
 }
+// ---- degree-2 polynomial activation: c2 x^2 + c1 x + c0 in one key switch ----
+// The square and the key switch are crc_square_relin_forms' / crc_square_pool_relin_forms'; the ring-linear terms P2 (*) . + P1 (*) Sum_w xh_w + P0 join the NTT-form
+// result in the key switch's last kernel (tune.poly_tail = 0, where the key switch runs over the fp64 primes) or in poly2_tail_kernel.  A coefficient-form input is
+// transformed pass by pass into work space ([xh of one pass] in front of the square's work space) when P1 needs it, a coefficient-form output is transformed
+// back at the end.
+static bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes)
+{
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + bbytes && b0 < a0 + abytes;
+}
+extern "C" size_t crc_poly2_relin_work_bytes(const crc_ctx *c, size_t count, int dbc)
+{
+    if (!c || !dbc_ok(dbc)) return 0;
+    const size_t chunk = square_chunk(c), ch = count < chunk ? count : chunk;
+    return crc_square_relin_work_bytes(c, count, dbc) + 8 * ch * crc_ct_words(c, 2) + 256;
+}
+extern "C" int crc_poly2_relin_forms(crc_ctx *c, const uint64_t *d_x, int in_form, size_t count, const uint64_t *d_evk, int dbc, const uint64_t *d_p2_ntt,
+                                     const uint64_t *d_p1_ntt, const uint64_t *d_p0_ntt, uint64_t *d_y, int out_form, void *d_work, void *stream)
+{
+    CHECK_CTX(c); if (!d_x || !d_y || !d_evk || !d_work || !form_ok(in_form) || !form_ok(out_form) || !dbc_ok(dbc)) return CRC_ERR_INVALID_ARGUMENT;
+    if (!d_p2_ntt && !d_p1_ntt && !d_p0_ntt) return crc_square_relin_forms(c, d_x, in_form, count, d_evk, dbc, d_y, out_form, d_work, stream);
+    const size_t ctw = crc_ct_words(c, 2);
+    // the P1 term reads the NTT-form input after the result's rows are written: the two tensors must not share memory then
+    if (d_p1_ntt && in_form == CRC_NTT && ranges_overlap(d_x, 8 * count * ctw, d_y, 8 * count * ctw)) return CRC_ERR_INVALID_ARGUMENT;
+    u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
+    const size_t kSquareChunk = square_chunk(c);
+    const size_t ch0 = count < kSquareChunk ? count : kSquareChunk;
+    const bool own_xh = d_p1_ntt && in_form == CRC_COEFF;
+    u64 *xh_w = w; if (own_xh) w += (ch0 * ctw + 31) & ~(size_t)31;
+    for (size_t o = 0; o < count; o += kSquareChunk) {
+        const size_t ch = count - o < kSquareChunk ? count - o : kSquareChunk;
+        u64 *kp = w, *y3 = kp + k_relin_keys_words(c, dbc), *rest = y3 + ch0 * crc_ct_words(c, 3);
+        const u64 *xin = d_x + o * ctw;
+        if (own_xh) {
+            HIPCHK(hipMemcpyAsync(xh_w, xin, 8 * ch * ctw, hipMemcpyDeviceToDevice, S(stream)));
+            RUN(crc_ntt_fwd(c, xh_w, ch, 2, stream));
+            xin = xh_w;
+        }
+        u64 *yo = d_y + o * ctw;
+        RUN(k_square(c, xin, ch, y3, rest, S(stream), own_xh || in_form == CRC_NTT, true));
+        const PolyTail pt{xin, d_p1_ntt, d_p0_ntt};
+        bool fused = false;
+        RUN(k_relinearize(c, y3, ch, d_evk, dbc, yo, rest, kp, S(stream), true, true, o != 0, d_p2_ntt, &pt, &fused));
+        if (!fused) RUN(k_poly2_tail(c, yo, xin, ch, 1, 1, 1, 1, 1, 1, d_p2_ntt, d_p1_ntt, d_p0_ntt, S(stream)));
+    }
+    if (out_form == CRC_COEFF) RUN(crc_ntt_inv(c, d_y, count, 2, stream));
+    return CRC_OK;
+}
+extern "C" int crc_poly2_pool_relin_supported(const crc_ctx *c, int dbc, int xf, int yf) { return crc_square_pool_relin_supported(c, dbc, xf, yf); }
+extern "C" size_t crc_poly2_pool_relin_work_bytes(const crc_ctx *c, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int dbc)
+{
+    const size_t sq = crc_square_pool_relin_work_bytes(c, B, zd, xd, yd, xs, ys, xf, yf, dbc);
+    if (!sq) return 0;
+    const size_t planes = (size_t)B * zd, pp = planes < sqpool_planes(c, xd, yd) ? planes : sqpool_planes(c, xd, yd);
+    return sq + 8 * pp * xd * yd * crc_ct_words(c, 2) + 256;
+}
+extern "C" int crc_poly2_pool_relin_forms(crc_ctx *c, const uint64_t *d_x, int in_form, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf,
+                                          const uint64_t *d_evk, int dbc, const uint64_t *d_p2_ntt, const uint64_t *d_p1_ntt, const uint64_t *d_p0_ntt,
+                                          uint64_t *d_y, int out_form, void *d_work, void *stream)
+{
+    CHECK_CTX(c); if (!d_x || !d_y || !d_evk || !d_work || !form_ok(in_form) || !form_ok(out_form) || !dbc_ok(dbc)) return CRC_ERR_INVALID_ARGUMENT;
+    if (B < 0 || zd < 1 || xd < xf || yd < yf || xs < 1 || ys < 1 || xf < 1 || yf < 1) return CRC_ERR_INVALID_ARGUMENT;
+    if (!crc_poly2_pool_relin_supported(c, dbc, xf, yf)) return CRC_ERR_UNSUPPORTED;
+    if (!d_p2_ntt && !d_p1_ntt && !d_p0_ntt)
+        return crc_square_pool_relin_forms(c, d_x, in_form, B, zd, xd, yd, xs, ys, xf, yf, d_evk, dbc, nullptr, d_y, out_form, d_work, stream);
+    const PoolGeom pg{xd, yd, xs, ys, xf, yf, (xd - xf) / xs + 1, (yd - yf) / ys + 1};
+    const size_t planes = (size_t)B * zd, step = sqpool_planes(c, xd, yd), pp0 = planes < step ? planes : step;
+    const size_t pin = (size_t)xd * yd, pout = (size_t)pg.xo * pg.yo, ctw = crc_ct_words(c, 2);
+    if (d_p1_ntt && in_form == CRC_NTT && ranges_overlap(d_x, 8 * planes * pin * ctw, d_y, 8 * planes * pout * ctw)) return CRC_ERR_INVALID_ARGUMENT;
+    u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
+    const bool own_xh = d_p1_ntt && in_form == CRC_COEFF;
+    u64 *xh_w = w; if (own_xh) w += (pp0 * pin * ctw + 31) & ~(size_t)31;
+    u64 *kp = w, *y3 = kp + k_relin_keys_words(c, dbc), *rest = y3 + pp0 * pin * crc_ct_words(c, 3);
+    const bool fused = k_relin64_poly_fused(c);
+    for (size_t o = 0; o < planes; o += step) {
+        const size_t pp = planes - o < step ? planes - o : step, cin = pp * pin, cout = pp * pout;
+        const u64 *xin = d_x + o * pin * ctw;
+        if (own_xh) {
+            HIPCHK(hipMemcpyAsync(xh_w, xin, 8 * cin * ctw, hipMemcpyDeviceToDevice, S(stream)));
+            RUN(crc_ntt_fwd(c, xh_w, cin, 2, stream));
+            xin = xh_w;
+        }
+        u64 *yo = d_y + o * pout * ctw;
+        RUN(k_square(c, xin, cin, y3, rest, S(stream), own_xh || in_form == CRC_NTT, true));
+        if (o == 0) RUN(k_relin64_prepare_keys(c, d_evk, dbc, kp, rest, S(stream)));
+        const PolyTail pt{xin, d_p1_ntt, d_p0_ntt};
+        RUN(k_relinearize64(c, y3, 3, 2, y3, 3, cout, dbc, yo, rest, kp, S(stream), true, &pg, fused ? d_p2_ntt : nullptr, fused ? &pt : nullptr));
+        if (!fused) RUN(k_poly2_tail(c, yo, xin, pp, xd, yd, xs, ys, xf, yf, d_p2_ntt, d_p1_ntt, d_p0_ntt, S(stream)));
+    }
+    if (out_form == CRC_COEFF) RUN(crc_ntt_inv(c, d_y, planes * pout, 2, stream));
+    return CRC_OK;
+}
 extern "C" int crc_square_relin(crc_ctx *c, const uint64_t *d_x, size_t count, const uint64_t *d_evk, int dbc, uint64_t *d_y, void *d_work, void *stream)
 {
     return crc_square_relin_forms(c, d_x, CRC_COEFF, count, d_evk, dbc, d_y, CRC_COEFF, d_work, stream);

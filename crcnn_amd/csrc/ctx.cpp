@@ -187,6 +187,7 @@ static void read_tuning(CrcTuning &t)
     t.mfma_min_steps = (int)geti("CRC_MFMA_MIN_STEPS", 0);
     t.relin_mac_ct = (int)geti("CRC_RELIN_MAC_CT", 0);
     t.ntt_split = (int)geti("CRC_NTT_SPLIT", 1);
+    t.poly_tail = (int)geti("CRC_POLY_TAIL", 0);
 }
 extern "C" int crc_ctx_set_tuning(crc_ctx *c, const char *name, long long value)
 {
@@ -215,6 +216,7 @@ extern "C" int crc_ctx_set_tuning(crc_ctx *c, const char *name, long long value)
     else if (s == "mfma_min_steps") t.mfma_min_steps = (int)value;
     else if (s == "relin_mac_ct") t.relin_mac_ct = (int)value;
     else if (s == "ntt_split") t.ntt_split = (int)value;
+    else if (s == "poly_tail") t.poly_tail = value ? 1 : 0;
     else return CRC_ERR_NOT_FOUND;             // (no_fold is baked into the tables at creation)
     return CRC_OK;
 }

@@ -130,6 +130,7 @@ struct CrcTuning {
                                   // (profiles/r05_square_pool_wave_local_*.txt): 7; 0: round-4 kernels
     // CRC_SQ_PATH=0: by parameters, 1: the square's auxiliary base is SEAL's 61-bit one (round-2 kernels), 2: the engine's fp64 primes
     int sq_path = 0;
+    int poly_tail = 0;            // CRC_POLY_TAIL=1: a polynomial activation's ring-linear terms always in poly2_tail_kernel (0: in the key switch's last kernel where it can)
     int relin_path = 0;           // CRC_RELIN_PATH=0: by parameters, 1: key switching over the coefficient moduli (round-2 path), 2: over the two fp64 primes
 };
 

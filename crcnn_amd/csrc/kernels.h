@@ -40,14 +40,21 @@ int k_relin64_prepare_keys(crc_ctx *c, const u64 *evk, int dbc, u64 *kp, u64 *sc
 // they are transformed and ONE key switch serves the pooled ciphertext (kernels_relin64.hip)
 struct PoolGeom { int xd, yd, xs, ys, xf, yf, xo, yo; };
 bool k_relin64_pool_supported(const crc_ctx *c, int dbc, int window);
+// the ring-linear terms of a degree-2 polynomial activation, joined to an NTT-form result while it leaves the key switch's last kernel:
+// y = mul (*) y + p1 (*) Sum_w xh_w (+ p0 on poly 0); xh: the activation's NTT-form input (size-2 ciphertexts where x3 holds the size-3 squares)
+struct PolyTail { const u64 *xh, *p1, *p0; };
+bool k_relin64_poly_fused(const crc_ctx *c);           // tune.poly_tail = 0 and a transform radix whose last kernel has room for the tail
 int k_relinearize64(crc_ctx *c, const u64 *src, int src_size, int src_poly, const u64 *x3, int add_size, size_t cnt, int dbc, u64 *y, u64 *work, const u64 *kp,
-                    hipStream_t st, bool out_ntt, const PoolGeom *pool = nullptr, const u64 *mul = nullptr);
+                    hipStream_t st, bool out_ntt, const PoolGeom *pool = nullptr, const u64 *mul = nullptr, const PolyTail *poly = nullptr);
+// the same terms in a kernel of their own (kernels.hip: poly2_tail_kernel), in place on y [planes][xo][yo]
+int k_poly2_tail(crc_ctx *c, u64 *y, const u64 *xh, size_t planes, int xd, int yd, int xs, int ys, int xf, int yf, const u64 *p2, const u64 *p1, const u64 *p0,
+                 hipStream_t st);
 int k_square(crc_ctx *c, const u64 *x, size_t cnt, u64 *y3, u64 *work, hipStream_t st, bool in_ntt = false, bool premul_c2 = false);
 // kernels_square64.hip: the square's auxiliary base over the engine's fp64 primes
 bool k_square64_supported(const crc_ctx *c);
 int k_square64(crc_ctx *c, const u64 *x, size_t cnt, u64 *y3, u64 *work, hipStream_t st, bool in_ntt, bool premul_c2);
 int k_relinearize(crc_ctx *c, const u64 *x3, size_t cnt, const u64 *evk, int dbc, u64 *y, u64 *work, u64 *kp, hipStream_t st, bool out_ntt = false,
-                  bool c2_premul = false, bool keys_ready = false);
+                  bool c2_premul = false, bool keys_ready = false, const u64 *p2 = nullptr, const struct PolyTail *poly = nullptr, bool *poly_fused = nullptr);
 int k_mac2(crc_ctx *c, const u64 *x, const u64 *w, u64 *y, const int *d_xoff, const int *d_toff, int B, int P, int F, int T, int in_cts,
            const u64 *bias_ntt, int gxd, int gyd, int gxf, int gyf, const unsigned *d_toffw, hipStream_t st, int xp = 0, int wp = 0, int yp = 0);
 int k_fold_pool(crc_ctx *c, const u64 *w, const u64 *bias, const u64 *div, u64 *wout, u64 *bout, int nf, int zd, int xf, int yf, int cxs, int cys,

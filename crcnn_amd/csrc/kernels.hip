@@ -980,6 +980,53 @@ int k_bn_ntt(crc_ctx *c, u64 *x, int B, int zd, int hw, const u64 *mean, const u
     return CRC_OK;
 }
 
+// the ring-linear tail of a degree-2 polynomial activation on an NTT-resident tensor (crc_poly2_relin_forms / crc_poly2_pool_relin_forms):
+//     y = p2 (*) y + p1 (*) Sum_w xh_w (+ p0 on poly 0)
+// y [planes][xo][yo] holds the (pooled) relinearised squares, xh [planes][xd][yd] the activation's NTT-form input whose window rows are gathered as in
+// pool_kernel (an unpooled activation is the 1 x 1 window over a 1 x 1 plane); p2 / p1 / p0 are NTT-form plaintext rows [k][n], NULL = 1 / 0 / 0.
+// One block per output row, 16 bytes per lane and access; a block reads and rewrites only its own row of y.
+__global__ void __launch_bounds__(256) poly2_tail_kernel(u64 *y, const u64 *xh, const u64 *p2, const u64 *p1, const u64 *p0, const ModParams *mods, int n, int k,
+                                                         int xd, int yd, int xs, int ys, int xf, int yf, int xo, int yo)
+{
+    // row = ((plane*xo + ox)*yo + oy)*2k + p*k + i
+    const size_t row = blockIdx.x;
+    const int i = (int)(row % k); const int p = (int)((row / k) % 2);
+    size_t ct = row / (2 * (size_t)k);
+    const int oy = (int)(ct % yo); ct /= yo; const int ox = (int)(ct % xo); ct /= xo;       // ct = plane
+    const ModParams m = mods[i];
+    const size_t cw = 2 * (size_t)k * n;
+    const u64 *base = xh + ((ct * xd + (size_t)ox * xs) * yd + (size_t)oy * ys) * cw + ((size_t)p * k + i) * n;
+    u64 *d = y + row * (size_t)n;
+    const u64 *w2 = p2 ? p2 + (size_t)i * n : nullptr, *w1 = p1 ? p1 + (size_t)i * n : nullptr, *w0 = p0 && p == 0 ? p0 + (size_t)i * n : nullptr;
+    for (int s = threadIdx.x * 2; s < n; s += blockDim.x * 2) {
+        ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(d + s);
+        if (w2) { const ulonglong2 wv = *reinterpret_cast<const ulonglong2 *>(w2 + s); v.x = mulmod(v.x, wv.x, m); v.y = mulmod(v.y, wv.y, m); }
+        if (w1) {
+            ulonglong2 acc = make_ulonglong2(0, 0);
+            for (int kx = 0; kx < xf; kx++) for (int ky = 0; ky < yf; ky++) {
+                const ulonglong2 xv = *reinterpret_cast<const ulonglong2 *>(base + ((size_t)kx * yd + ky) * cw + s);
+                acc.x = addmod(acc.x, xv.x, m.q); acc.y = addmod(acc.y, xv.y, m.q);
+            }
+            const ulonglong2 wv = *reinterpret_cast<const ulonglong2 *>(w1 + s);
+            v.x = addmod(v.x, mulmod(acc.x, wv.x, m), m.q); v.y = addmod(v.y, mulmod(acc.y, wv.y, m), m.q);
+        }
+        if (w0) { const ulonglong2 wv = *reinterpret_cast<const ulonglong2 *>(w0 + s); v.x = addmod(v.x, wv.x, m.q); v.y = addmod(v.y, wv.y, m.q); }
+        *reinterpret_cast<ulonglong2 *>(d + s) = v;
+    }
+}
+
+int k_poly2_tail(crc_ctx *c, u64 *y, const u64 *xh, size_t planes, int xd, int yd, int xs, int ys, int xf, int yf, const u64 *p2, const u64 *p1, const u64 *p0,
+                 hipStream_t st)
+{
+    const int xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys + 1;
+    const size_t rows = planes * xo * yo * 2 * c->k;
+    if (rows == 0 || (!p2 && !p1 && !p0)) return CRC_OK;
+    if (rows > 0x7fffffffULL) return CRC_ERR_UNSUPPORTED;                 // one block per row: the grid's x dimension
+    hipLaunchKernelGGL(poly2_tail_kernel, dim3((unsigned)rows), dim3(256), 0, st, y, xh, p2, p1, p0, c->d_mods, c->n, c->k, xd, yd, xs, ys, xf, yf, xo, yo);
+    HIPCHK(hipGetLastError());
+    return CRC_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // ct x pt multiply-accumulate in the NTT domain (the hot loop of convolution3d / FullyConnectedLayer::forward):
 //   y[b][f][p][poly][i][s] = sum_T  x[b][xoff[p] + toff[T]][poly][i][s] * w[f][T][i][s]   (mod q_i)

@@ -292,13 +292,41 @@ __global__ void __launch_bounds__(256, CT * PJ <= 36 ? 4 : 1) relin_mac_f64_kern
 // 512-thread workgroups per CU, four waves per SIMD and 128 registers -- with 1024 threads and 8 points the 64-register line of the second workgroup left no
 // room for the held row (18 spilled registers, 16.6 instead of 12.2 MB of traffic per ciphertext and 5.55 instead of 5.19 us at (8192, 3):
 // profiles/r04_square_relin_ab_step1.txt)
-template <int RB, int NPT, bool OUT_NTT, bool LAZY>
+// POLY (OUT_NTT only): the ring-linear terms of a degree-2 polynomial activation join the result while it leaves (crc_poly2_*_relin_forms):
+//     y = mul (*) y + pt.p1 (*) Sum_w xh_w (+ pt.p0 on poly 0),   xh = the activation's NTT-form input (size-2 ciphertexts, laid out as x3's),
+// NULL rows = 1 / 0 / 0.  A compile-time variant of relin_inv_crt_kernel: the kernel takes the PolyTail as a trailing parameter PACK (TAIL = PolyTail or
+// nothing), so the instantiations without it keep their parameter list, their kernel-argument offsets and with them every instruction they had
+template <typename T> __device__ __forceinline__ const T &first_of(const T &t) { return t; }
+__device__ __forceinline__ void poly_tail_pair(ulonglong2 &v, int s, const u64 *mul, const PolyTail &pt, size_t actw, int poly, int j, int n, int k, const PoolGeom &pg,
+                                               const ModParams &mq)
+{
+    const size_t row = (size_t)j * n + s;
+    if (mul) { const ulonglong2 w = *reinterpret_cast<const ulonglong2 *>(mul + row); v.x = mulmod(v.x, w.x, mq); v.y = mulmod(v.y, w.y, mq); }
+    if (pt.p1) {
+        const size_t cw = 2 * (size_t)k * n;
+        const u64 *xrow = pt.xh + actw * cw + (size_t)poly * k * n + row;
+        const int xf = pg.xf > 0 ? pg.xf : 1, yf = pg.xf > 0 ? pg.yf : 1;
+        ulonglong2 acc = make_ulonglong2(0, 0);
+        for (int kx = 0; kx < xf; kx++, xrow += (size_t)pg.yd * cw)
+            for (int ky = 0; ky < yf; ky++) {
+                const ulonglong2 xv = *reinterpret_cast<const ulonglong2 *>(xrow + (size_t)ky * cw);
+                acc.x = addmod(acc.x, xv.x, mq.q); acc.y = addmod(acc.y, xv.y, mq.q);
+            }
+        const ulonglong2 w1 = *reinterpret_cast<const ulonglong2 *>(pt.p1 + row);
+        v.x = addmod(v.x, mulmod(acc.x, w1.x, mq), mq.q); v.y = addmod(v.y, mulmod(acc.y, w1.y, mq), mq.q);
+    }
+    if (pt.p0 && poly == 0) { const ulonglong2 w0 = *reinterpret_cast<const ulonglong2 *>(pt.p0 + row); v.x = addmod(v.x, w0.x, mq.q); v.y = addmod(v.y, w0.y, mq.q); }
+}
+template <int RB, int NPT, bool OUT_NTT, bool LAZY, typename... TAIL>
 __global__ void __launch_bounds__(RB == 5 ? 512 : 1024, 4) relin_inv_crt_kernel(const double *A, const u64 *x3, int add_size, u64 *y, const ModParams *mods,
     const double *Wi,
                                                                                                                      const ulonglong2 *Wq, F64Params fp,
                                                                                                                          int n, int logn, int k,
-                                                                                                                         const u64 *mul, PoolGeom pg)
+                                                                                                                         const u64 *mul, PoolGeom pg,
+                                                                                                                         TAIL... tail)
 {
+    constexpr bool POLY = sizeof...(TAIL) != 0;
+    static_assert(!POLY || OUT_NTT, "the polynomial tail multiplies slot-wise");
     extern __shared__ double smd[];
     const size_t ct = blockIdx.x / (2 * k); const int pj = blockIdx.x % (2 * k), poly = pj / k, j = pj % k;
     const int tid = threadIdx.x, nt = blockDim.x;
@@ -380,7 +408,9 @@ __global__ void __launch_bounds__(RB == 5 ? 512 : 1024, 4) relin_inv_crt_kernel(
         if (LAZY) { v.x = reduce_small(v.x, q, mq.two_q, rq); v.y = reduce_small(v.y, q, mq.two_q, rq); }
         else { v.x = v.x >= mq.two_q ? v.x - mq.two_q : v.x; v.x = v.x >= q ? v.x - q : v.x; v.y = v.y >= mq.two_q ? v.y - mq.two_q : v.y;
             v.y = v.y >= q ? v.y - q : v.y; }
-        if (mul) {          // the divisor of an average pooling behind the Square layer (an NTT-form plaintext [k][n]): slot-wise, while the result leaves
+        if constexpr (POLY)
+            poly_tail_pair(v, s, mul, first_of(tail...), actw, poly, j, n, k, pg, mq);
+        else if (mul) {     // the divisor of an average pooling behind the Square layer (an NTT-form plaintext [k][n]): slot-wise, while the result leaves
             const ulonglong2 w = *reinterpret_cast<const ulonglong2 *>(mul + (size_t)j * n + s);
             v.x = mulmod(v.x, w.x, mq); v.y = mulmod(v.y, w.y, mq);
         }
@@ -628,14 +658,20 @@ static bool f64_wave_path(const crc_ctx *c, int RB, int bit)
     return (sel >> bit) & 1;
 }
 
+// whether K3 can carry a polynomial activation's tail (tune.poly_tail = 0): at the default radix.  The radix-16 / -32 variants of the tuning switch "f64_radix"
+// would spill with it, so those take poly2_tail_kernel
+bool k_relin64_poly_fused(const crc_ctx *c) { return c->tune.poly_tail == 0 && f64_radix(c) == 3; }
+
 template <int RB, int NPT>
 static int relin64_tail(crc_ctx *c, const double *A, const u64 *x3, int add_size, u64 *y, size_t cnt, bool out_ntt, hipStream_t st, const u64 *mul,
-    const PoolGeom *pool)
+    const PoolGeom *pool, const PolyTail *poly)
 {
     bool lazy = true;
     for (int i = 0; i < c->k; i++) if (c->tabs[i].m.bits > 57 || c->tabs[i].m.bits < 45) lazy = false;
     const size_t lds = (size_t)c->n * 8;
-    if (f64_wave_path(c, RB, 2)) {
+    // (a polynomial tail goes through relin_inv_crt_kernel at every ring: with it the wave-local kernels spill 4 / 14 / 24 registers per lane at n = 4096 / 8192 /
+    // 16384, and what they gain over this kernel is 0.3 to 1.5 % of the sequence)
+    if (!poly && f64_wave_path(c, RB, 2)) {
         const int cs = c->logn - 10;
         const bool u64w = f64_wave_path(c, RB, 4);           // (bit 4: the 64-bit forward transform behind the CRT wave-local as well)
 #define K3W(A, B, C) (cs == 2 ? relin_inv_crt_wave_kernel<2, A, B, C> : cs == 3 ? relin_inv_crt_wave_kernel<3, A, B, C> : relin_inv_crt_wave_kernel<4, A, B, C>)
@@ -649,6 +685,15 @@ static int relin64_tail(crc_ctx *c, const double *A, const u64 *x3, int add_size
     }
     auto kern = !out_ntt ? relin_inv_crt_kernel<RB, NPT, false, false> : lazy ? relin_inv_crt_kernel<RB, NPT, true, true> : relin_inv_crt_kernel<RB, NPT,
         true, false>;
+    if constexpr (RB != 3) { if (poly) return CRC_ERR_UNSUPPORTED; }       // (k_relin64_poly_fused: the wider passes have no registers left for the tail)
+    else if (poly) {
+        auto kp = lazy ? relin_inv_crt_kernel<RB, NPT, true, true, PolyTail> : relin_inv_crt_kernel<RB, NPT, true, false, PolyTail>;
+        { const int rc = crc_ctx_ensure_lds(c, (const void *)kp, lds); if (rc) return rc; }
+        hipLaunchKernelGGL(kp, dim3((unsigned)(cnt * 2 * c->k)), dim3(f64_hold_threads(c, RB)), lds, st, A, x3, add_size, y, c->d_mods, c->d_f64_irp,
+                           reinterpret_cast<const ulonglong2 *>(c->d_rp), c->f64, c->n, c->logn, c->k, mul, pool ? *pool : PoolGeom{0, 0, 0, 0, 0, 0, 0, 0}, *poly);
+        HIPCHK(hipGetLastError());
+        return CRC_OK;
+    }
     { const int rc = crc_ctx_ensure_lds(c, (const void *)kern, lds); if (rc) return rc; }
     hipLaunchKernelGGL(kern, dim3((unsigned)(cnt * 2 * c->k)), dim3(f64_hold_threads(c, RB)), lds, st, A, x3, add_size, y, c->d_mods, c->d_f64_irp,
                        reinterpret_cast<const ulonglong2 *>(c->d_rp), c->f64, c->n, c->logn, c->k, mul, pool ? *pool : PoolGeom{0, 0, 0, 0, 0, 0, 0, 0});
@@ -659,7 +704,7 @@ static int relin64_tail(crc_ctx *c, const double *A, const u64 *x3, int add_size
 // src / src_size / src_poly: where c2 (q/q_i)^-1 lives; x3 / add_size: the ciphertexts whose (c0, c1) are added; kp: the keys as k_relin64_prepare_keys left
 // them; work: cnt n (2 D + 4 k) words
 int k_relinearize64(crc_ctx *c, const u64 *src, int src_size, int src_poly, const u64 *x3, int add_size, size_t cnt, int dbc, u64 *y, u64 *work, const u64 *kp,
-                    hipStream_t st, bool out_ntt, const PoolGeom *pool, const u64 *mul)
+                    hipStream_t st, bool out_ntt, const PoolGeom *pool, const u64 *mul, const PolyTail *poly)
 {
     if (cnt == 0) return CRC_OK;
     if (!k_relin64_supported(c, dbc)) return CRC_ERR_UNSUPPORTED;
@@ -717,9 +762,9 @@ int k_relinearize64(crc_ctx *c, const u64 *src, int src_size, int src_poly, cons
     default: return CRC_ERR_UNSUPPORTED;
     }
     if (rc) return rc;
-    if (mul && !out_ntt) return CRC_ERR_INVALID_ARGUMENT;
+    if ((mul || poly) && !out_ntt) return CRC_ERR_INVALID_ARGUMENT;
     // (pooled: x3 / add_size are the UNPOOLED ciphertexts whose (c0, c1) K3 adds up window by window)
-    return RB == 3 ? relin64_tail<3, 16>(c, A, x3, add_size, y, cnt, out_ntt, st, mul, pool)
-         : RB == 4 ? relin64_tail<4, 16>(c, A, x3, add_size, y, cnt, out_ntt, st, mul, pool) : relin64_tail<5, 32>(c, A, x3, add_size, y, cnt, out_ntt, st,
-             mul, pool);
+    return RB == 3 ? relin64_tail<3, 16>(c, A, x3, add_size, y, cnt, out_ntt, st, mul, pool, poly)
+         : RB == 4 ? relin64_tail<4, 16>(c, A, x3, add_size, y, cnt, out_ntt, st, mul, pool, poly) : relin64_tail<5, 32>(c, A, x3, add_size, y, cnt, out_ntt, st,
+             mul, pool, poly);
 }

@@ -256,9 +256,12 @@ int k_square(crc_ctx *c, const u64 *x, size_t cnt, u64 *y3, u64 *work, hipStream
 }
 
 // c2_premul: the third polynomial of x3 already holds c2 (q/q_i)^-1 (k_square with premul_c2).  kp: crc_evk_words of space for the packed keys;
-// keys_ready: a previous call with the same evk has filled it
-int k_relinearize(crc_ctx *c, const u64 *x3, size_t cnt, const u64 *evk, int dbc, u64 *y, u64 *work, u64 *kp, hipStream_t st, bool out_ntt, bool c2_premul, bool keys_ready)
+// keys_ready: a previous call with the same evk has filled it.  poly (with its multiplier p2): a polynomial activation's ring-linear terms, joined to the
+// result where the key switch runs over the fp64 primes -- *poly_fused says whether that happened (the caller runs k_poly2_tail otherwise)
+int k_relinearize(crc_ctx *c, const u64 *x3, size_t cnt, const u64 *evk, int dbc, u64 *y, u64 *work, u64 *kp, hipStream_t st, bool out_ntt, bool c2_premul, bool keys_ready,
+                  const u64 *p2, const PolyTail *poly, bool *poly_fused)
 {
+    if (poly_fused) *poly_fused = false;
     if (cnt == 0) return CRC_OK;
     if (!dbc_ok(dbc)) return CRC_ERR_INVALID_ARGUMENT;
     const size_t n = c->n, k = c->k;
@@ -272,6 +275,10 @@ int k_relinearize(crc_ctx *c, const u64 *x3, size_t cnt, const u64 *evk, int dbc
             hipLaunchKernelGGL(relin_premul_kernel, dim3((unsigned)(cnt * k)), dim3(256), 0, st, x3, work, c->d_mods, c->d_behz, c->n, c->k);
             HIPCHK(hipGetLastError());
             src = work; src_size = 1; src_poly = 0;
+        }
+        if (poly && out_ntt && poly_fused && k_relin64_poly_fused(c)) {
+            *poly_fused = true;
+            return k_relinearize64(c, src, src_size, src_poly, x3, 3, cnt, dbc, y, c2_premul ? work : work + cnt * k * n, kp, st, out_ntt, nullptr, p2, poly);
         }
         return k_relinearize64(c, src, src_size, src_poly, x3, 3, cnt, dbc, y, c2_premul ? work : work + cnt * k * n, kp, st, out_ntt);
     }

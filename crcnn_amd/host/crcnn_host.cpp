@@ -1176,6 +1176,87 @@ void SquarePoolLayer::printLayerStructure()
          << yo << "); one key switch per pooled ciphertext" << endl;
 }
 
+// ---- polynomial activation ------------------------------------------------------------------------------------------------
+// the three NTT-form rows crc_poly2_*_relin_forms take (empty = 1, 0, 0), with the window count and the divisor of a pooling behind the activation folded in
+static void polyRows(float c2, float c1, float c0, int window, const shared_ptr<DeviceBuffer> &d_div, shared_ptr<DeviceBuffer> out[3])
+{
+    const size_t rowb = (size_t)K() * N() * 8;
+    auto copyOf = [&](const shared_ptr<DeviceBuffer> &src) {
+        auto r = make_shared<DeviceBuffer>(rowb);
+        chk(crc_memcpy_d2d(ctx(), r->ptr, src->ptr, rowb, stream()), "crc_memcpy_d2d");
+        return r;
+    };
+    auto timesDiv = [&](const shared_ptr<DeviceBuffer> &r) {
+        if (d_div) chk(crc_multiply_plain_ntt(ctx(), (uint64_t *)r->ptr, (const uint64_t *)d_div->ptr, 1, 1, 1, stream()), "crc_multiply_plain_ntt");
+    };
+    out[0].reset(); out[1].reset(); out[2].reset();
+    if (c2 != 1.0f) { const Plaintext p = fraencode((double)c2); out[0] = uploadPlain({&p}, 0); timesDiv(out[0]); }
+    else if (d_div) out[0] = copyOf(d_div);
+    if (c1 != 0.0f) { const Plaintext p = fraencode((double)c1); out[1] = uploadPlain({&p}, 0); timesDiv(out[1]); }
+    if (c0 != 0.0f) {
+        const Plaintext p = fraencode((double)c0);
+        const shared_ptr<DeviceBuffer> one = uploadPlain({&p}, 2);
+        out[2] = copyOf(one);
+        for (int w = 1; w < window; w++) chk(crc_add(ctx(), (uint64_t *)out[2]->ptr, (const uint64_t *)one->ptr, 1, 1, stream()), "crc_add");
+        timesDiv(out[2]);
+    }
+    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+}
+static void polyCheck(const string &what, float c2, float c1, float c0)
+{
+    if (!isfinite(c2) || !isfinite(c1) || !isfinite(c0)) throw invalid_argument(what + ": the coefficients must be finite");
+    if (c2 == 0.0f) throw invalid_argument(what + ": c2 must not be zero (a polynomial without its square term is a batch norm, not an activation)");
+}
+static const uint64_t *rowPtr(const shared_ptr<DeviceBuffer> &b) { return b ? (const uint64_t *)b->ptr : nullptr; }
+PolyLayer::PolyLayer(string name, float c2, float c1, float c0, int th_count) : Layer(name), c2(c2), c1(c1), c0(c0), th_count(th_count)
+{
+    polyCheck("PolyLayer", c2, c1, c0);
+}
+size_t PolyLayer::deviceBytes() const { size_t b = 0; for (auto &r : d_p) if (r) b += r->bytes; return b; }
+ciphertext3D PolyLayer::forward(ciphertext3D input)
+{
+    if (!input.buf) throw invalid_argument("PolyLayer: empty input");
+    if (!ev_keys16) throw invalid_argument("not enough evaluation keys");
+    if (out_form != CRC_NTT && out_form != CRC_COEFF) throw invalid_argument("PolyLayer: out_form must be CRC_NTT or CRC_COEFF");
+    if (!uploaded) { polyRows(c2, c1, c0, 1, nullptr, d_p); uploaded = true; }
+    ciphertext3D out(input.B, input.zd, input.xd, input.yd, out_form);
+    ensure(g_scratch, crc_poly2_relin_work_bytes(ctx(), input.count(), 16));
+    chk(crc_poly2_relin_forms(ctx(), input.data(), input.form, input.count(), (const uint64_t *)ev_keys16->ptr, 16, rowPtr(d_p[0]), rowPtr(d_p[1]), rowPtr(d_p[2]),
+                              out.data(), out_form, g_scratch->ptr, stream()), "crc_poly2_relin_forms");
+    return out;
+}
+void PolyLayer::printLayerStructure()
+{
+    cerr << "Poly " << name << " : " << c2 << " x^2 + " << c1 << " x + " << c0 << " run with " << th_count << " threads" << endl;
+}
+
+// ---- polynomial activation + pooling (Network::fuse) ------------------------------------------------------------------------
+PolyPoolLayer::PolyPoolLayer(string name, int xd, int yd, int zd, int xs, int ys, int xf, int yf, int th_count, float c2, float c1, float c0,
+    shared_ptr<DeviceBuffer> d_div)
+    : Layer(name), xd(xd), yd(yd), zd(zd), xs(xs), ys(ys), xf(xf), yf(yf), xo((xd - xf) / xs + 1), yo((yd - yf) / ys + 1), zo(zd), th_count(th_count),
+        c2(c2), c1(c1), c0(c0), d_div(d_div)
+{
+    polyCheck("PolyPoolLayer", c2, c1, c0);
+}
+size_t PolyPoolLayer::deviceBytes() const { size_t b = d_div ? d_div->bytes : 0; for (auto &r : d_p) if (r) b += r->bytes; return b; }
+ciphertext3D PolyPoolLayer::forward(ciphertext3D input)
+{
+    checkInput(input, zd, xd, yd, "PolyPoolLayer");
+    if (!ev_keys16) throw invalid_argument("not enough evaluation keys");
+    if (out_form != CRC_NTT && out_form != CRC_COEFF) throw invalid_argument("PolyPoolLayer: out_form must be CRC_NTT or CRC_COEFF");
+    if (!uploaded) { polyRows(c2, c1, c0, xf * yf, d_div, d_p); uploaded = true; }
+    ciphertext3D out(input.B, zo, xo, yo, out_form);
+    ensure(g_scratch, crc_poly2_pool_relin_work_bytes(ctx(), input.B, zd, xd, yd, xs, ys, xf, yf, 16));
+    chk(crc_poly2_pool_relin_forms(ctx(), input.data(), input.form, input.B, zd, xd, yd, xs, ys, xf, yf, (const uint64_t *)ev_keys16->ptr, 16, rowPtr(d_p[0]),
+                                   rowPtr(d_p[1]), rowPtr(d_p[2]), out.data(), out_form, g_scratch->ptr, stream()), "crc_poly2_pool_relin_forms");
+    return out;
+}
+void PolyPoolLayer::printLayerStructure()
+{
+    cerr << "Poly + Pooling " << name << " : " << c2 << " x^2 + " << c1 << " x + " << c0 << "; input (" << zd << "," << xd << "," << yd << "); kernel(" << xf << ","
+         << yf << "); stride(" << xs << "," << ys << "); output(" << zo << "," << xo << "," << yo << "); one key switch per pooled ciphertext" << endl;
+}
+
 // ---- BatchNorm --------------------------------------------------------------------------------------------------------
 BatchNormLayer::BatchNormLayer(string name, int num_channels, vector<Plaintext> &mean, vector<Plaintext> &var) : Layer(name), num_channels(num_channels),
     mean(mean), var(var) {}
@@ -1542,6 +1623,16 @@ int Network::fuse()
                                                  pool->d_div);
         eraseLayer(i + 1);
     }
+    // 1c. polynomial activation + pooling, the same way (PolyPoolLayer; a batch norm behind it is left to the fold below)
+    for (size_t i = 0; i + 1 < layers.size(); i++) {
+        auto po = dynamic_pointer_cast<PolyLayer>(layers[i]);
+        auto pool = dynamic_pointer_cast<PoolingLayer>(layers[i + 1]);
+        if (!po || !pool || refreshBetween(i)) continue;
+        if (!crc_poly2_pool_relin_supported(ctx(), 16, pool->xf, pool->yf)) continue;
+        layers[i] = make_shared<PolyPoolLayer>(po->name + "+" + pool->name, pool->xd, pool->yd, pool->zd, pool->xs, pool->ys, pool->xf, pool->yf, po->th_count,
+                                               po->c2, po->c1, po->c0, pool->d_div);
+        eraseLayer(i + 1);
+    }
     // 2. batch-norm + conv / dense
     for (size_t i = 0; i + 1 < layers.size(); i++) {
         auto bn = dynamic_pointer_cast<BatchNormLayer>(layers[i]);
@@ -1604,6 +1695,19 @@ const struct { const char *name, *text; } kBuiltinModels[] = {
 #include "builtin_models.inc"
 };
 [[noreturn]] void descError(int line, const string &what) { throw invalid_argument("line " + to_string(line) + ": " + what); }
+// a coefficient of a `poly` line: a decimal number read as double and rounded to float32 (what netrun.py's float() -> numpy.float32 gives)
+float descFloat(int line, const string &tok, const char *what)
+{
+    // (decimal notation, `inf` and `nan` only: the characters both hosts' number parsers agree on)
+    char *end = nullptr;
+    const bool plain = !tok.empty() && tok.find_first_not_of("0123456789+-.eEinfatyINFATY") == string::npos;
+    const double v = plain ? strtod(tok.c_str(), &end) : 0.0;
+    if (!plain || end == tok.c_str() || *end) descError(line, string(what) + ": expected a number, got '" + tok + "'");
+    const float f = (float)v;
+    if (!isfinite(f)) descError(line, string(what) + ": the coefficient must be finite, got '" + tok + "'");
+    return f;
+}
+string descFloatStr(float v) { char b[32]; snprintf(b, sizeof b, "%.9g", (double)v); return b; }
 int descInt(int line, const string &tok, const char *what)
 {
     if (tok.empty() || tok.size() > 9 || tok.find_first_not_of("0123456789") != string::npos)
@@ -1659,17 +1763,17 @@ NetworkDescription NetworkDescription::parse(const string &text, const string &h
             continue;
         }
         const bool windowed = kind == "conv" || kind == "pool" || kind == "avgpool";
-        if (!windowed && kind != "bn" && kind != "square" && kind != "fc" && kind != "pad") descError(ln, "unknown layer kind '" + kind + "'");
+        if (!windowed && kind != "bn" && kind != "square" && kind != "fc" && kind != "pad" && kind != "poly") descError(ln, "unknown layer kind '" + kind + "'");
         if (tok.size() < 2) descError(ln, kind + ": the layer name is missing");
         LayerSpec L;
         L.kind = kind; L.name = tok[1]; L.line = ln; L.zd = zd; L.xd = xd; L.yd = yd;
         vector<string> rest(tok.begin() + 2, tok.end());
         if (rest.size() >= 2 && rest[rest.size() - 2] == "threads") {
-            if (kind != "conv" && kind != "fc" && kind != "square") descError(ln, "unknown token 'threads' for a " + kind + " layer");
+            if (kind != "conv" && kind != "fc" && kind != "square" && kind != "poly") descError(ln, "unknown token 'threads' for a " + kind + " layer");
             L.threads = descInt(ln, rest.back(), "threads");
             rest.resize(rest.size() - 2);
         }
-        if (flat && (windowed || kind == "pad"))
+        if (flat && (windowed || kind == "pad" || kind == "poly"))
             descError(ln, "a " + kind + " layer cannot follow a fully connected layer: the tensor is flat (" + to_string(xd) + " values)");
         if (windowed) {
             size_t pos = 0;
@@ -1707,6 +1811,11 @@ NetworkDescription NetworkDescription::parse(const string &text, const string &h
             if (rest.size() != 2) descError(ln, rest.size() > 2 ? "unknown token '" + rest[2] + "'" : string("pad: takes px py"));
             L.px = descInt(ln, rest[0], "pad"); L.py = descInt(ln, rest[1], "pad");
             L.zo = zd; L.xo = xd + 2 * L.px; L.yo = yd + 2 * L.py;
+        } else if (kind == "poly") {
+            if (rest.size() != 3) descError(ln, rest.size() > 3 ? "unknown token '" + rest[3] + "'" : string("poly: takes c2 c1 c0"));
+            L.c2 = descFloat(ln, rest[0], "c2"); L.c1 = descFloat(ln, rest[1], "c1"); L.c0 = descFloat(ln, rest[2], "c0");
+            if (L.c2 == 0.0f) descError(ln, "poly: c2 must not be zero (without its square term the layer is a batch norm, not an activation)");
+            L.zo = zd; L.xo = xd; L.yo = yd;
         } else {
             if (!rest.empty()) descError(ln, "unknown token '" + rest[0] + "'");
             if (kind == "bn") { check(ln, L.name + ".running_mean", zd); check(ln, L.name + ".running_var", zd); }
@@ -1743,6 +1852,7 @@ string NetworkDescription::str() const
         else if (L.kind == "pool" || L.kind == "avgpool") o << " stride " << L.xs << " " << L.ys << " window " << L.xf << " " << L.yf;
         else if (L.kind == "fc") o << " " << L.out_dim;
         else if (L.kind == "pad") o << " " << L.px << " " << L.py;
+        else if (L.kind == "poly") o << " " << descFloatStr(L.c2) << " " << descFloatStr(L.c1) << " " << descFloatStr(L.c0);
         if (L.threads >= 0 && L.threads != 1) o << " threads " << L.threads;          // (1 is what a layer without the token is built with)
         o << "\n";
     }
@@ -1763,6 +1873,7 @@ string Network::describe() const
             L.xf = p->xf; L.yf = p->yf; }
         else if (auto pd = dynamic_pointer_cast<PaddingLayer>(l)) { L.kind = "pad"; L.px = pd->px; L.py = pd->py; }
         else if (auto sq = dynamic_pointer_cast<SquareLayer>(l)) { L.kind = "square"; L.threads = sq->th_count; }
+        else if (auto po = dynamic_pointer_cast<PolyLayer>(l)) { L.kind = "poly"; L.c2 = po->c2; L.c1 = po->c1; L.c0 = po->c0; L.threads = po->th_count; }
         else if (dynamic_pointer_cast<BatchNormLayer>(l)) L.kind = "bn";
         else throw logic_error("Network::describe: layer " + l->name + " has no description");
         d.layers.push_back(L);
@@ -1828,6 +1939,7 @@ PoolingLayer *CnnBuilder::buildPoolingLayer(string name, int xd, int yd, int zd,
 AvgPoolingLayer *CnnBuilder::buildAvgPoolingLayer(string name, int xd, int yd, int zd, int xs, int ys, int xf, int yf) { return new AvgPoolingLayer(name, xd,
     yd, zd, xs, ys, xf, yf); }
 SquareLayer *CnnBuilder::buildSquareLayer(string name, int th_count) { return new SquareLayer(name, th_count); }
+PolyLayer *CnnBuilder::buildPolyLayer(string name, float c2, float c1, float c0, int th_count) { return new PolyLayer(name, c2, c1, c0, th_count); }
 BatchNormLayer *CnnBuilder::buildBatchNormLayer(string name, int num_channels, istream *infile)
 {   // cnnBuilder.cpp:89-105
     if (infile != NULL) return new BatchNormLayer(name, num_channels, infile);
@@ -1858,6 +1970,7 @@ Network CnnBuilder::buildNetworkFromDescription(const string &path_or_text, stri
         else if (L.kind == "avgpool") add(buildAvgPoolingLayer(L.name, L.xd, L.yd, L.zd, L.xs, L.ys, L.xf, L.yf));
         else if (L.kind == "bn") add(buildBatchNormLayer(L.name, L.zd, in));
         else if (L.kind == "square") add(buildSquareLayer(L.name, th));
+        else if (L.kind == "poly") add(buildPolyLayer(L.name, L.c2, L.c1, L.c0, th));
         else if (L.kind == "fc") add(buildFullyConnectedLayer(L.name, L.zd * L.xd * L.yd, L.out_dim, th, in));
         else add(buildPaddingLayer(L.name, L.xd, L.yd, L.zd, L.px, L.py));
     }

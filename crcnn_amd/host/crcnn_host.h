@@ -308,6 +308,46 @@ private:
     std::shared_ptr<DeviceBuffer> d_div;                    // NTT-form divisor of an average pooling (applied to the pooled ciphertexts)
 };
 
+// Degree-2 polynomial activation c2 x^2 + c1 x + c0 (no layer of the reference, whose one non-linearity is SquareLayer): per ciphertext the Evaluator sequence
+//     s = relinearize(square(x), ev_keys16); s = multiply_plain(s, encode(c2)); s = add(s, multiply_plain(x, encode(c1))); s = add_plain(s, encode(c0))
+// (a step is left out for c2 == 1, c1 == 0, c0 == 0), computed with one key switch per ciphertext (crc_poly2_relin_forms).  The coefficients are float32
+// and encoded as the weights are; c2 == 0 (a batch norm, not an activation) and non-finite values are std::invalid_argument.  PolyLayer(name, 1, 0, 0, ...)
+// produces SquareLayer's ciphertexts bit for bit
+class PolyLayer : public Layer {
+public:
+    float c2, c1, c0;
+    int th_count;
+    PolyLayer(std::string name, float c2, float c1, float c0, int th_count);
+    ciphertext3D forward(ciphertext3D input) override;
+    void savePlaintextParameters(std::ostream *) override {}
+    void loadPlaintextParameters(std::istream *) override {}
+    void printLayerStructure() override;
+    size_t deviceBytes() const override;
+private:
+    bool uploaded = false;
+    std::shared_ptr<DeviceBuffer> d_p[3];                   // NTT-form rows of encode(c2), encode(c1) and Delta encode(c0); empty = 1, 0, 0
+};
+
+// Network::fuse(): a PolyLayer with a (sum or average) PoolingLayer behind it, as SquarePoolLayer pairs a SquareLayer:
+//     Sum_w (c2 x_w^2 + c1 x_w + c0) = c2 Sum_w relin(x_w^2) + c1 Sum_w x_w + W c0
+// keeps ONE key switch per pooled ciphertext (crc_poly2_pool_relin_forms); the window count and an average pooling's divisor are folded into the three
+// rows once (exact ring arithmetic).  Same ciphertexts as the two layers one after the other
+class PolyPoolLayer : public Layer {
+public:
+    int xd, yd, zd, xs, ys, xf, yf, xo, yo, zo, th_count;
+    float c2, c1, c0;
+    PolyPoolLayer(std::string name, int xd, int yd, int zd, int xs, int ys, int xf, int yf, int th_count, float c2, float c1, float c0,
+        std::shared_ptr<DeviceBuffer> d_div);
+    ciphertext3D forward(ciphertext3D input) override;
+    void savePlaintextParameters(std::ostream *) override {}
+    void loadPlaintextParameters(std::istream *) override {}
+    void printLayerStructure() override;
+    size_t deviceBytes() const override;
+private:
+    bool uploaded = false;
+    std::shared_ptr<DeviceBuffer> d_div, d_p[3];            // the pooling's divisor; the rows with the window count and the divisor folded in
+};
+
 class BatchNormLayer : public Layer {                       // batchNormLayer.h:18-20
 public:
     friend class Network;
@@ -436,7 +476,8 @@ public:
 // then one layer per line, the input shape of each inferred from the line above:
 //   conv NAME stride xs ys filter xf yf filters nf      pool | avgpool NAME stride xs ys window xf yf      bn NAME      square NAME
 //   fc NAME out_dim      pad NAME px py      refresh (sets layer_before_reenc to the next layer; at most one)
-// conv, fc and square lines may end in `threads N` (the th_count the reference's constructors take).  NAME is the HDF5 dataset prefix.
+//   poly NAME c2 c1 c0   (c2 x^2 + c1 x + c0: decimal numbers, read as double and rounded to float32; c2 != 0, all finite; written back as %.9g)
+// conv, fc, square and poly lines may end in `threads N` (the th_count the reference's constructors take).  NAME is the HDF5 dataset prefix.
 // Every error is a std::invalid_argument whose message starts with "line N:".
 struct LayerSpec {
     std::string kind, name;
@@ -445,6 +486,7 @@ struct LayerSpec {
     int xs = 0, ys = 0, xf = 0, yf = 0, nf = 0;             // conv / pool / avgpool
     int out_dim = 0;                                        // fc (in_dim = zd xd yd, the reference's reshapeInput order)
     int px = 0, py = 0;                                     // pad
+    float c2 = 1.0f, c1 = 0.0f, c0 = 0.0f;                  // poly
     int threads = -1;                                       // -1: no `threads` token (the layer is built with th_count 1)
     int zo = 0, xo = 0, yo = 0;                             // output shape
 };
@@ -474,6 +516,7 @@ public:
     PoolingLayer *buildPoolingLayer(std::string name, int xd, int yd, int zd, int xs, int ys, int xf, int yf);
     AvgPoolingLayer *buildAvgPoolingLayer(std::string name, int xd, int yd, int zd, int xs, int ys, int xf, int yf);
     SquareLayer *buildSquareLayer(std::string name, int th_count);
+    PolyLayer *buildPolyLayer(std::string name, float c2, float c1, float c0, int th_count);
     PaddingLayer *buildPaddingLayer(std::string name, int xd, int yd, int zd, int px, int py);
     BatchNormLayer *buildBatchNormLayer(std::string name, int num_channels, std::istream *infile);
     // cnnBuilder.cpp:108-179 hard-codes one topology per source edit (Tiny is the committed one); all three are available here, and any other as a description

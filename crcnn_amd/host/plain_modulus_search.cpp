@@ -120,6 +120,7 @@ vector<float> plainModelForward(CnnBuilder &build, const string &model, const ve
         else if (L.kind == "pool" || L.kind == "avgpool") t = poolF(t, L.xs, L.ys, L.xf, L.yf, L.kind == "avgpool");
         else if (L.kind == "bn") bnF(t, P(L.name + ".running_mean"), P(L.name + ".running_var"));
         else if (L.kind == "square") { for (float &v : t.v) v = v * v; }
+        else if (L.kind == "poly") { for (float &v : t.v) v = (L.c2 * v + L.c1) * v + L.c0; }
         else if (L.kind == "fc") t = fcF(t, P(L.name + ".weight"), P(L.name + ".bias"), L.out_dim);
         else if (L.kind == "pad") t = padF(t, L.px, L.py);
         else throw invalid_argument("plainModelForward: unknown layer kind " + L.kind);

@@ -5,6 +5,7 @@ gives (parse_description; zero padding included), weights read from the HDF5 mod
 (network.cpp:22-47) layer by layer over a batch of encrypted images.  All arithmetic happens in libcrcnn_hip.so; this
 file only sequences C-ABI calls and owns device buffers.  The C++ twin of this logic is crcnn_amd/host/.
 """
+import math
 import os
 
 import numpy as np
@@ -70,7 +71,7 @@ def window_ok(xd, yd, xs, ys, xf, yf):
 
 
 _KEYS = {"conv": (("stride", 2), ("filter", 2), ("filters", 1)), "pool": (("stride", 2), ("window", 2)), "avgpool": (("stride", 2), ("window", 2))}
-_THREADED = ("conv", "fc", "square")
+_THREADED = ("conv", "fc", "square", "poly")
 
 
 def parse_description(text, dataset_count=None):
@@ -87,6 +88,23 @@ def parse_description(text, dataset_count=None):
         if any(x < 0 for x in v):
             raise ValueError(f"line {ln}: {what}: negative value")
         return v
+
+    def coef(ln, t, what):
+        # a coefficient of a `poly` line: a decimal number read as double and rounded to float32, as the C++ host reads it (decimal notation, `inf` and `nan` only:
+        # the characters both hosts' number parsers agree on)
+        v = None
+        if t and all(ch in "0123456789+-.eEinfatyINFATY" for ch in t):
+            try:
+                v = float(t)
+            except ValueError:
+                pass
+        if v is None:
+            raise ValueError(f"line {ln}: {what}: expected a number, got '{t}'")
+        with np.errstate(over="ignore"):
+            f = float(np.float32(v))
+        if not math.isfinite(f):
+            raise ValueError(f"line {ln}: {what}: the coefficient must be finite, got '{t}'")
+        return f
 
     def check(ln, name, count):
         if dataset_count is None:
@@ -117,7 +135,7 @@ def parse_description(text, dataset_count=None):
                 raise ValueError(f"line {ln}: a second refresh (line {pending_refresh or lines[refresh]} has the first)")
             pending_refresh = ln
             continue
-        if kind not in ("conv", "pool", "avgpool", "bn", "square", "fc", "pad"):
+        if kind not in ("conv", "pool", "avgpool", "bn", "square", "fc", "pad", "poly"):
             raise ValueError(f"line {ln}: unknown layer kind {kind!r}")
         if len(tok) < 2:
             raise ValueError(f"line {ln}: {kind}: the layer name is missing")
@@ -129,7 +147,7 @@ def parse_description(text, dataset_count=None):
             th = ints(ln, rest[-1:], "threads")[0]
             rest = rest[:-2]
         zd, xd, yd = shape
-        if flat and kind in ("conv", "pool", "avgpool", "pad"):
+        if flat and kind in ("conv", "pool", "avgpool", "pad", "poly"):
             raise ValueError(f"line {ln}: a {kind} layer cannot follow a fully connected layer: the tensor is flat ({xd} values)")
         if kind in _KEYS:
             vals, pos = {}, 0
@@ -167,6 +185,12 @@ def parse_description(text, dataset_count=None):
                 raise ValueError(f"line {ln}: " + (f"unknown token {rest[2]!r}" if len(rest) > 2 else "pad: takes px py"))
             px, py = ints(ln, rest, "pad")
             a = dict(zd=zd, xd=xd, yd=yd, px=px, py=py)
+        elif kind == "poly":
+            if len(rest) != 3:
+                raise ValueError(f"line {ln}: " + (f"unknown token {rest[3]!r}" if len(rest) > 3 else "poly: takes c2 c1 c0"))
+            a = dict(c2=coef(ln, rest[0], "c2"), c1=coef(ln, rest[1], "c1"), c0=coef(ln, rest[2], "c0"))
+            if a["c2"] == 0.0:
+                raise ValueError(f"line {ln}: poly: c2 must not be zero (without its square term the layer is a batch norm, not an activation)")
         else:
             if rest:
                 raise ValueError(f"line {ln}: unknown token {rest[0]!r}")
@@ -202,6 +226,8 @@ def format_description(desc):
             ln = f"fc {name} {a['out_dim']}"
         elif kind == "pad":
             ln = f"pad {name} {a['px']} {a['py']}"
+        elif kind == "poly":
+            ln = "poly %s %.9g %.9g %.9g" % (name, a["c2"], a["c1"], a["c0"])      # (%.9g of a float32 reads back as the same float32)
         else:
             ln = f"{kind} {name}"
         if d.threads[i] not in (None, 1):         # (1 is what a layer without the token is built with)
@@ -324,6 +350,14 @@ class Network:
                 p["in_form"] = form
                 p["out_form"] = COEFF if (last or not resident) else NTT
                 form = p["out_form"]
+            elif kind == "poly":
+                # c2 x^2 + c1 x + c0 with one key switch per ciphertext (crc_poly2_relin_forms): the forms of a Square layer, and the three plaintext rows
+                p["in_form"] = form
+                p["out_form"] = COEFF if (last or not resident) else NTT
+                form = p["out_form"]
+                if eng.device >= 0:
+                    p["rows"] = eng.poly2_rows(a["c2"], a["c1"], a["c0"])
+                    self._keep_rows(p["rows"])
             nshape = out_shape(kind, a, shape)
             self.plan.append((kind, name, a, p, shape, nshape))
             shape = nshape
@@ -546,6 +580,13 @@ class Network:
         self._pair_square_pool()
         self._fold_batchnorm()
 
+    def _keep_rows(self, rows):
+        rowb = self.E.k * self.E.n * 8
+        for r in rows:
+            if r is not None:
+                self.weight_bytes += rowb
+                self.param_bufs.append((r, rowb))
+
     def _pair_square_pool(self):
         """a Square layer with a (sum or average) pooling behind it: relinearisation is linear in the digit polynomials of c2, so the digits of a pooling window are
         added and ONE key switch serves the pooled ciphertext (crc_square_pool_relin_forms) -- the same ciphertexts, xo yo / (xd yd) of the key-switching work"""
@@ -557,6 +598,20 @@ class Network:
             if (kind == "square" and nxt and nxt[0] in ("pool", "avgpool") and p["out_form"] == NTT and nxt[3]["form"] == NTT
                     and E.square_pool_relin_supported(nxt[2]["xf"], nxt[2]["yf"], self.dbc)):
                 plan.append(("squarepool", name + "+" + nxt[1], dict(nxt[2]), dict(in_form=p["in_form"], out_form=NTT, div=nxt[3]["div"]), ishape, nxt[5]))
+                i += 2
+                continue
+            # a polynomial activation pairs the same way: Sum_w (c2 x_w^2 + c1 x_w + c0) = c2 Sum_w relin(x_w^2) + c1 Sum_w x_w + W c0, the window count and the
+            # divisor folded into the three rows once (crc_poly2_pool_relin_forms)
+            if (kind == "poly" and nxt and nxt[0] in ("pool", "avgpool") and p["out_form"] == NTT and nxt[3]["form"] == NTT
+                    and E.poly2_pool_relin_supported(nxt[2]["xf"], nxt[2]["yf"], self.dbc)):
+                rows = (None, None, None)
+                if E.device >= 0:
+                    old = [r for r in p.get("rows", ()) if r is not None]              # the unpaired layer's rows are dropped
+                    self.param_bufs = [(b_, n_) for (b_, n_) in self.param_bufs if not any(b_ is r for r in old)]
+                    self.weight_bytes -= len(old) * E.k * E.n * 8
+                    rows = E.poly2_rows(a["c2"], a["c1"], a["c0"], window=nxt[2]["xf"] * nxt[2]["yf"], d_div=nxt[3]["div"])
+                    self._keep_rows(rows)
+                plan.append(("polypool", name + "+" + nxt[1], dict(nxt[2]), dict(in_form=p["in_form"], out_form=NTT, rows=rows), ishape, nxt[5]))
                 i += 2
                 continue
             plan.append(self.plan[i]); i += 1
@@ -704,6 +759,10 @@ class Network:
                 work = max(work, E.square_relin_work_bytes(B * int(np.prod(ishape)), self.dbc))
             elif kind == "squarepool":
                 work = max(work, E.square_pool_relin_work_bytes(B, a["zd"], a["xd"], a["yd"], a["xs"], a["ys"], a["xf"], a["yf"], self.dbc))
+            elif kind == "poly":
+                work = max(work, E.poly2_relin_work_bytes(B * int(np.prod(ishape)), self.dbc))
+            elif kind == "polypool":
+                work = max(work, E.poly2_pool_relin_work_bytes(B, a["zd"], a["xd"], a["yd"], a["xs"], a["ys"], a["xf"], a["yf"], self.dbc))
         return need_act, work
 
     def _stream_geometry(self, kind, a, B=None):
@@ -906,6 +965,13 @@ class Network:
             elif kind == "squarepool":
                 E.square_pool_relin(cur, B, a["zd"], a["xd"], a["yd"], a["xs"], a["ys"], a["xf"], a["yf"], self.d_evk, out, self.work, self.dbc, p["in_form"], p["out_form"],
                                     d_div=p["div"])          # (an average pooling's divisor multiplies the pooled tensor as it leaves the key switch)
+                cur = out
+            elif kind == "poly":
+                E.poly2_relin(cur, B * int(np.prod(ishape)), self.d_evk, *p["rows"], out, self.work, self.dbc, p["in_form"], p["out_form"])
+                cur = out
+            elif kind == "polypool":
+                E.poly2_pool_relin(cur, B, a["zd"], a["xd"], a["yd"], a["xs"], a["ys"], a["xf"], a["yf"], self.d_evk, *p["rows"], out, self.work, self.dbc,
+                                   p["in_form"], p["out_form"])
                 cur = out
             if timer:
                 timer(i, name, kind, 1)

@@ -108,7 +108,7 @@ int  crc_ctx_table(const crc_ctx *ctx, const char *name, uint64_t *h_out, int ca
  * exactly
  * once, inside crc_ctx_create; this call changes one switch of a context nobody is launching on: "mfma_variant", "mfma_order", "mfma_ring", "conv1_waves",
  * "conv1_narrow" (0: a one-channel convolution with 17-20 filters runs its second filter group like a full one), "conv1_pass_bytes", "limb_pack_group", "mac2_cfg", "mac_order", "mac_regstage", "ntt_inv61_loose", "ntt_split", "mfma_min_steps", "f64_radix",
- * "relin_mac_ct",
+ * "relin_mac_ct", "poly_tail" (crc_poly2_relin_forms),
  * "relin_path" (1: key switching over the coefficient moduli, as the reference does it, instead of over two fp64 primes), "sq_path" (1: the square's auxiliary
  * base is SEAL's 61-bit
  * one instead of the engine's fp64 primes; 2: force the latter), "sq_chunk" (ciphertexts per internal pass of square + relinearise; changes
@@ -319,6 +319,28 @@ size_t crc_square_pool_relin_work_bytes(const crc_ctx *ctx, int B, int zd, int x
 int    crc_square_pool_relin_forms(crc_ctx *ctx, const uint64_t *d_x, int in_form, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf,
                                    const uint64_t *d_evk, int dbc, const uint64_t *d_div_ntt /* NULL = sum pool */, uint64_t *d_y, int out_form, void *d_work,
                                    void *stream);
+/* Degree-2 polynomial activation c2 x^2 + c1 x + c0 (no layer of the reference, whose one non-linearity is x^2), defined per ciphertext x as the Evaluator sequence
+ *     s = relinearize(square(x), evk);  s = multiply_plain(s, encode(c2));  s = add(s, multiply_plain(x, encode(c1)));  s = add_plain(s, encode(c0))
+ * in coefficient form (a step is left out for c2 == 1, c1 == 0, c0 == 0).  c1 x and c0 are ring-linear in the ciphertext, so they join the key switch's result
+ * while it leaves the last kernel, and the pooled form keeps ONE key switch per pooled ciphertext:
+ *     Sum_w (c2 x_w^2 + c1 x_w + c0) = c2 Sum_w relin(x_w^2) + c1 Sum_w x_w + W c0.
+ * d_p2_ntt / d_p1_ntt: NTT-form plaintext rows [k][n] (crc_plain_to_ntt of encode(c2) / encode(c1)); d_p0_ntt: the delta-form row of encode(c0) in NTT form
+ * (crc_plain_to_delta, form = CRC_NTT), added to c0 only.  Any of them may be NULL: 1, 0 and 0 (all three NULL is crc_square_relin_forms /
+ * crc_square_pool_relin_forms, bit for bit).  For the pooled call the HOST folds the window count and an average pooling's divisor into the rows (exact ring
+ * arithmetic, done once): p2' = div (*) p2, p1' = div (*) p1, p0' = W div (*) p0 -- the call computes
+ *     y = p2 (*) (Sum_w relin(x_w^2)) + p1 (*) (Sum_w NTT(x_w)) + [poly 0] p0.
+ * Either form in and out: a coefficient-form side is transformed at the boundary inside the call, the result is the sequence's ciphertext in the requested
+ * form.  With d_p1_ntt and in_form = CRC_NTT, d_y must not overlap d_x (CRC_ERR_INVALID_ARGUMENT).  crc_ctx_set_tuning "poly_tail": 0 the terms are added in the
+ * key switch's last kernel wherever that runs over the fp64 primes, 1 always in a slot-wise kernel of their own (poly2_tail_kernel, which also serves
+ * "sq_path" / "relin_path" = 1 and the moduli the fp64 key switch refuses).  crc_poly2_pool_relin_supported: the conditions of crc_square_pool_relin_supported. */
+size_t crc_poly2_relin_work_bytes(const crc_ctx *ctx, size_t count, int dbc);
+int    crc_poly2_relin_forms(crc_ctx *ctx, const uint64_t *d_x, int in_form, size_t count, const uint64_t *d_evk, int dbc, const uint64_t *d_p2_ntt,
+                             const uint64_t *d_p1_ntt, const uint64_t *d_p0_ntt, uint64_t *d_y, int out_form, void *d_work, void *stream);
+int    crc_poly2_pool_relin_supported(const crc_ctx *ctx, int dbc, int xf, int yf);
+size_t crc_poly2_pool_relin_work_bytes(const crc_ctx *ctx, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int dbc);
+int    crc_poly2_pool_relin_forms(crc_ctx *ctx, const uint64_t *d_x, int in_form, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf,
+                                  const uint64_t *d_evk, int dbc, const uint64_t *d_p2_ntt, const uint64_t *d_p1_ntt, const uint64_t *d_p0_ntt, uint64_t *d_y,
+                                  int out_form, void *d_work, void *stream);
 /* the two halves separately (unit tests): square -> size-3 ciphertexts; relinearize -> size 2 */
 int crc_square(crc_ctx *ctx, const uint64_t *d_x, size_t count, uint64_t *d_y3, void *d_work, void *stream);
 int crc_relinearize(crc_ctx *ctx, const uint64_t *d_x3, size_t count, const uint64_t *d_evk, int dbc, uint64_t *d_y,
