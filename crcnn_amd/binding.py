@@ -135,6 +135,8 @@ def load():
     L.crc_limb_conv1_supported.argtypes = [VP] + [CI] * 8
     L.crc_limb_conv1_weights_bytes.restype = SZ; L.crc_limb_conv1_weights_bytes.argtypes = [VP]
     L.crc_limb_conv1_pack_weights.argtypes = [VP, VP, CI, CI, CI, VP, VP]
+    L.crc_limb_conv1_weights_bytes_for.restype = SZ; L.crc_limb_conv1_weights_bytes_for.argtypes = [VP, CI, CI, CI]
+    L.crc_limb_conv1_form.argtypes = [VP] + [CI] * 8
     L.crc_conv2d_forms_work_bytes.restype = SZ; L.crc_conv2d_forms_work_bytes.argtypes = [VP] + [CI] * 12
     L.crc_square.argtypes = [VP, VP, SZ, VP, VP, VP]
     L.crc_relinearize.argtypes = [VP, VP, SZ, VP, CI, VP, VP, VP]
@@ -560,6 +562,13 @@ class Engine:
 
     def limb_conv1_weights_bytes(self):
         return self.L.crc_limb_conv1_weights_bytes(self.c)
+
+    def limb_conv1_weights_bytes_for(self, nf, xf, yf):
+        return self.L.crc_limb_conv1_weights_bytes_for(self.c, nf, xf, yf)
+
+    def limb_conv1_form(self, zd, xd, yd, xs, ys, xf, yf, nf):
+        """0: not a one-channel matrix-core shape, 1: plane-major image, 2: pixel-major image (tuning key conv1_form)"""
+        return self.L.crc_limb_conv1_form(self.c, zd, xd, yd, xs, ys, xf, yf, nf)
 
     def limb_conv1_pack_weights(self, d_w_ntt, nf, xf, yf, d_wl):
         _chk(self.L.crc_limb_conv1_pack_weights(self.c, self.p(d_w_ntt), nf, xf, yf, self.p(d_wl), self.stream), "crc_limb_conv1_pack_weights")

@@ -141,6 +141,15 @@ extern "C" int crc_limb_conv1_supported(const crc_ctx *c, int zd, int xd, int yd
     return k_limb_conv1_shape(c, zd, xd, yd, xs, ys, xf, yf, nf) ? 1 : 0;
 }
 extern "C" size_t crc_limb_conv1_weights_bytes(const crc_ctx *c) { return c ? k_limb_conv1_weights_bytes(c) : 0; }
+extern "C" size_t crc_limb_conv1_weights_bytes_for(const crc_ctx *c, int nf, int xf, int yf)
+{
+    return c && nf >= 1 && xf >= 1 && yf >= 1 ? k_limb_conv1_weights_bytes_for(c, nf, xf, yf) : 0;
+}
+// which form of the kernel a shape runs under the present tuning: 0 not a one-channel matrix-core shape, 1 plane-major, 2 pixel-major
+extern "C" int crc_limb_conv1_form(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf)
+{
+    return crc_limb_conv1_supported(c, zd, xd, yd, xs, ys, xf, yf, nf) ? k_limb_conv1_form(c, xf, yf, nf) : 0;
+}
 extern "C" int crc_limb_conv1_pack_weights(crc_ctx *c, const uint64_t *d_w_ntt, int nf, int xf, int yf, void *d_wl, void *stream)
 {
     CHECK_CTX(c); if (!d_w_ntt || !d_wl || nf < 1 || nf > 32 || xf < 1 || yf < 1 || xf > 8 || yf > 8) return CRC_ERR_INVALID_ARGUMENT;
@@ -149,10 +158,10 @@ extern "C" int crc_limb_conv1_pack_weights(crc_ctx *c, const uint64_t *d_w_ntt, 
 }
 // images per internal pass: the y-expanded limb images and the slot-major result of a pass stay below ~16 GiB of work space (a dense consumer's flattened
 // limb tensor is converted from the whole batch's result at once: no sub-batching there)
-static int conv1_sub_batch(const crc_ctx *c, int B, int xd, int yo, int nf, int P, int out_form)
+static int conv1_sub_batch(const crc_ctx *c, int B, int xd, int yd, int xf, int yf, int nf, int P, int out_form)
 {
     if (out_form == CRC_NTTL || B <= 1) return B;
-    const size_t per = k_limb_conv1_image_bytes(c, 1, xd) + (out_form == CRC_NTTLC ? 0 : 8 * k_limb_result_words(c, 1, nf, P));
+    const size_t per = k_limb_conv1_image_bytes(c, 1, xd, yd, xf, yf, nf) + (out_form == CRC_NTTLC ? 0 : 8 * k_limb_result_words(c, 1, nf, P));
     const long long ev = c->tune.conv1_pass_bytes;                   // (the tests shrink it to cover the multi-pass path at small sizes: crc_ctx_set_tuning)
     const size_t cap = ev > 0 ? (size_t)ev : (size_t)16 << 30;
     const size_t fit = cap / (per ? per : 1);
@@ -165,10 +174,10 @@ static int conv2d_limb1(crc_ctx *c, const uint64_t *d_x, const void *d_wl, const
     const int xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys + 1, P = xo * yo, in_cts = xd * yd;
     // a 1 x 1 result is a dense layer's input: the K-blocked form (kernels_mfma.hip), made from the slot-major result
     if (out_form == CRC_NTTLC && P == 1) out_form = CRC_NTTL;
-    const int Bs = conv1_sub_batch(c, B, xd, yo, nf, P, out_form);
+    const int Bs = conv1_sub_batch(c, B, xd, yd, xf, yf, nf, P, out_form);
     const size_t ctw = crc_ct_words(c, 2);
     char *w = (char *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
-    signed char *Xr = (signed char *)w; w += align256(k_limb_conv1_image_bytes(c, Bs, xd));
+    signed char *Xr = (signed char *)w; w += align256(k_limb_conv1_image_bytes(c, Bs, xd, yd, xf, yf, nf));
     u64 *Ys = nullptr;
     if (out_form != CRC_NTTLC) { Ys = (u64 *)w; w += align256(8 * k_limb_result_words(c, Bs, nf, P)); }
     u64 *buf = (u64 *)w;                                           // NTT copy of a coefficient-form sub-batch
@@ -193,8 +202,8 @@ extern "C" size_t crc_conv2d_forms_work_bytes(const crc_ctx *c, int B, int zd, i
         if (!c || !conv_shape_ok(xd, yd, xs, ys, xf, yf)) return 0;
         const int xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys + 1;
         if (out_form == CRC_NTTLC && xo * yo == 1) out_form = CRC_NTTL;
-        const int Bs = conv1_sub_batch(c, B, xd, yo, nf, xo * yo, out_form);
-        size_t b = align256(k_limb_conv1_image_bytes(c, Bs, xd));
+        const int Bs = conv1_sub_batch(c, B, xd, yd, xf, yf, nf, xo * yo, out_form);
+        size_t b = align256(k_limb_conv1_image_bytes(c, Bs, xd, yd, xf, yf, nf));
         if (out_form != CRC_NTTLC) b += align256(8 * k_limb_result_words(c, Bs, nf, xo * yo));
         if (in_form == CRC_COEFF) b += align256((size_t)Bs * xd * yd * crc_ct_words(c, 2) * 8);
         return b + 256;

@@ -103,8 +103,10 @@ int k_limb_mac(crc_ctx *c, const signed char *xl, const signed char *wl, u64 *ys
                hipStream_t st);
 // kernels_mfma1.hip: one-channel convolutions (conv1 [+ pool1]) on the matrix cores (weight form CRC_NTTL1)
 bool   k_limb_conv1_shape(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys_, int xf, int yf, int nf);
-size_t k_limb_conv1_weights_bytes(const crc_ctx *c);
-size_t k_limb_conv1_image_bytes(const crc_ctx *c, int B, int xd);
+int    k_limb_conv1_form(const crc_ctx *c, int xf, int yf, int nf);          // 1 plane-major, 2 pixel-major image and limb-folded weights
+size_t k_limb_conv1_weights_bytes(const crc_ctx *c);                         // enough for either form
+size_t k_limb_conv1_weights_bytes_for(const crc_ctx *c, int nf, int xf, int yf);
+size_t k_limb_conv1_image_bytes(const crc_ctx *c, int B, int xd, int yd, int xf, int yf, int nf);
 int k_limb_conv1_pack_weights(crc_ctx *c, const u64 *w, signed char *wl, int nf, int xf, int yf, hipStream_t st);
 int k_limb_conv1(crc_ctx *c, const u64 *x, bool packed, signed char *xr, const signed char *wl, u64 *ys, signed char *xl_out, int Bout, int b0, const u64 *bias_ntt, int B, int xd, int yd,
                  int xs, int ys_, int xf, int yf, int nf, hipStream_t st);

@@ -24,6 +24,9 @@
 //   output      either the limb tensor of a following convolution, staged in LDS and written out as one contiguous [plane][pixel][poly][32 channels] block
 //               (no limb_pack_tensor pass in front of conv2), or slot-major u64 for the generic conversions. Exact integer arithmetic throughout: the same
 //               element of Z_q, hence the same bits, as mac3_kernel and the reference (convolutionalLayer.cpp:56-93).
+// Two forms of the kernel share the epilogue's end (conv1_store4, conv1_copy_out): the plane-major one described above (mfma_conv1_kernel: any window up to
+// 8 x 8, the packed second filter group of 17-20 filters) and, for windows of at most 40 taps, the pixel-major one further down (mfma_conv1_kernel_px: 35 MFMAs
+// and 7 diagonals per tile, no window cutting, one fold).  k_limb_conv1_form picks per layer; the tuning key conv1_form forces one.
 #include "kernels.h"
 #include "limbred.h"
 #include <cstdlib>
@@ -48,6 +51,11 @@ struct Conv1Args {
                                                        // (mfma_conv1_kernel)
     int acc0[MAXK][13];                                // initial value of the 13 diagonal accumulators, per modulus (conv1_tables)
     u32 qbits[MAXK], qfold[MAXK];                      // q = 2^qbits - qfold (limbred.h conv1_fold_ok)
+    // pixel-major form (mfma_conv1_kernel_px): image [poly][row][column] of 8-byte pixels, rows px_rs bytes apart (poly_bytes between the polys); taps = xf * yf,
+    // tap = kx * yf + ky; px_pair: taps 2G and 2G + 1 are always neighbouring pixels at an even column (one 16-byte read per K group)
+    unsigned px_rs;
+    int px_taps, px_yf, px_pair;
+    int acc7[MAXK][7];                                 // biases of the seven weight-digit diagonals (limbred.h conv1_bias7_table)
 };
 
 // canonical residue -> 7 balanced base-256 digits of its centred representative
@@ -56,6 +64,58 @@ __device__ __forceinline__ void limb_digits1(u64 r, u64 q, int (&d)[NPL])
     long long v = r > (q >> 1) ? (long long)r - (long long)q : (long long)r;
 #pragma unroll
     for (int l = 0; l < NPL; l++) { d[l] = (int)(signed char)(v & 0xff); v = (v - d[l]) >> 8; }
+}
+
+// the end of a tile's epilogue, shared by both forms of the kernel: four consecutive filters f0 .. f0 + 3 of output row mm (pixel mm >> 1, poly mm & 1) of image b,
+// given as centred representatives
+__device__ __forceinline__ void conv1_store4(const Conv1Args &a, i8 *stage, const long long (&cv)[4], int mm, int f0, int chan_bytes, u64 q, int slot, int b)
+{
+    if (mm >= 2 * a.P) return;
+    // limb tensor of the next convolution, staged in LDS as it leaves: [row][plane][32 channels], or the flat form [plane][poly][pixel][zdc]
+    if (a.xl_out) {
+        if (f0 >= chan_bytes) return;                                      // (flat form: channel padding is a multiple of 4, this group is past it)
+        u32 lo[4], hi[4];
+#pragma unroll
+        for (int reg = 0; reg < 4; reg++) { const u64 dg = f0 + reg < a.F ? centred_digit_bytes(cv[reg]) : 0; lo[reg] = (u32)dg;
+            hi[reg] = (u32)(dg >> 32); }
+        // 4 x 7 byte transpose: dword l = digit l of the four filters (v_perm_b32: result byte = selector byte picks from {second operand: 0-3, first:
+        // 4-7})
+        const u32 t0 = __builtin_amdgcn_perm(lo[1], lo[0], 0x05010400u), t1 = __builtin_amdgcn_perm(lo[1], lo[0], 0x07030602u);
+        const u32 u0 = __builtin_amdgcn_perm(lo[3], lo[2], 0x05010400u), u1 = __builtin_amdgcn_perm(lo[3], lo[2], 0x07030602u);
+        const u32 t2 = __builtin_amdgcn_perm(hi[1], hi[0], 0x05010400u), t3 = __builtin_amdgcn_perm(hi[1], hi[0], 0x07030602u);
+        const u32 u2 = __builtin_amdgcn_perm(hi[3], hi[2], 0x05010400u), u3 = __builtin_amdgcn_perm(hi[3], hi[2], 0x07030602u);
+        u32 pl[NPL];
+        pl[0] = __builtin_amdgcn_perm(u0, t0, 0x05040100u); pl[1] = __builtin_amdgcn_perm(u0, t0, 0x07060302u);
+        pl[2] = __builtin_amdgcn_perm(u1, t1, 0x05040100u); pl[3] = __builtin_amdgcn_perm(u1, t1, 0x07060302u);
+        pl[4] = __builtin_amdgcn_perm(u2, t2, 0x05040100u); pl[5] = __builtin_amdgcn_perm(u2, t2, 0x07060302u);
+        pl[6] = __builtin_amdgcn_perm(u3, t3, 0x05040100u);
+        i8 *sp; unsigned pstride;
+        if (a.out_zdc) { sp = stage + ((mm & 1) * a.P + (mm >> 1)) * a.out_zdc + f0; pstride = 2 * a.P * a.out_zdc; }
+        else { sp = stage + mm * (NPL * 32) + f0; pstride = 32; }
+#pragma unroll
+        for (int l = 0; l < NPL; l++) *reinterpret_cast<u32 *>(sp + l * pstride) = pl[l];
+    } else {
+#pragma unroll
+        for (int reg = 0; reg < 4; reg++)
+            // canonical
+            if (f0 + reg < a.F) a.ys[(((size_t)slot * a.B + b) * a.F + f0 + reg) * (2 * a.P) + mm] = (u64)(cv[reg] + ((cv[reg] >> 63) & (long long)q));
+    }
+}
+// the staged limb result of image b leaves as one contiguous block (after a workgroup barrier)
+__device__ __forceinline__ void conv1_copy_out(const Conv1Args &a, const i8 *stage, int slot, int b)
+{
+    i8 *dst = a.xl_out + ((size_t)slot * a.Bout + a.b0 + b) * a.out_img_bytes;
+    if (a.out_zdc) {              // the staging area IS the image's byte layout
+        for (unsigned o = threadIdx.x; o < a.out_img_bytes / 16; o += blockDim.x)
+            *reinterpret_cast<uint4 *>(dst + (size_t)o * 16) = *reinterpret_cast<const uint4 *>(stage + (size_t)o * 16);
+    } else {
+        const unsigned per_plane = a.out_img_bytes / (NPL * 16);      // 16-byte pieces of one plane: (row, half)
+        for (unsigned o = threadIdx.x; o < NPL * per_plane; o += blockDim.x) {
+            const unsigned l = o / per_plane, rem = o - l * per_plane;
+            *reinterpret_cast<uint4 *>(dst + (size_t)o * 16) = *reinterpret_cast<const uint4 *>(stage + (rem >> 1) * (NPL * 32) + l * 32 +
+                (rem & 1) * 16);
+        }
+    }
 }
 
 __global__ void __launch_bounds__(768) mfma_conv1_kernel(Conv1Args a)
@@ -211,51 +271,120 @@ __global__ void __launch_bounds__(768) mfma_conv1_kernel(Conv1Args a)
                 // one pass from the diagonals to the centred representative, bias included
                 cv[reg] = diag_fold_short_centred(D, q, qbits, qfold, bvc[reg], PB);
             }
-            if (mm >= 2 * a.P) continue;
-            // limb tensor of the next convolution, staged in LDS as it leaves: [row][plane][32 channels], or the flat form [plane][poly][pixel][zdc]
-            if (a.xl_out) {
-                if (f0 >= chan_bytes) continue;                                      // (flat form: channel padding is a multiple of 4, this group is past it)
-                u32 lo[4], hi[4];
-#pragma unroll
-                for (int reg = 0; reg < 4; reg++) { const u64 dg = f0 + reg < a.F ? centred_digit_bytes(cv[reg]) : 0; lo[reg] = (u32)dg;
-                    hi[reg] = (u32)(dg >> 32); }
-                // 4 x 7 byte transpose: dword l = digit l of the four filters (v_perm_b32: result byte = selector byte picks from {second operand: 0-3, first:
-                // 4-7})
-                const u32 t0 = __builtin_amdgcn_perm(lo[1], lo[0], 0x05010400u), t1 = __builtin_amdgcn_perm(lo[1], lo[0], 0x07030602u);
-                const u32 u0 = __builtin_amdgcn_perm(lo[3], lo[2], 0x05010400u), u1 = __builtin_amdgcn_perm(lo[3], lo[2], 0x07030602u);
-                const u32 t2 = __builtin_amdgcn_perm(hi[1], hi[0], 0x05010400u), t3 = __builtin_amdgcn_perm(hi[1], hi[0], 0x07030602u);
-                const u32 u2 = __builtin_amdgcn_perm(hi[3], hi[2], 0x05010400u), u3 = __builtin_amdgcn_perm(hi[3], hi[2], 0x07030602u);
-                u32 pl[NPL];
-                pl[0] = __builtin_amdgcn_perm(u0, t0, 0x05040100u); pl[1] = __builtin_amdgcn_perm(u0, t0, 0x07060302u);
-                pl[2] = __builtin_amdgcn_perm(u1, t1, 0x05040100u); pl[3] = __builtin_amdgcn_perm(u1, t1, 0x07060302u);
-                pl[4] = __builtin_amdgcn_perm(u2, t2, 0x05040100u); pl[5] = __builtin_amdgcn_perm(u2, t2, 0x07060302u);
-                pl[6] = __builtin_amdgcn_perm(u3, t3, 0x05040100u);
-                i8 *sp; unsigned pstride;
-                if (a.out_zdc) { sp = stage + ((mm & 1) * a.P + (mm >> 1)) * a.out_zdc + f0; pstride = 2 * a.P * a.out_zdc; }
-                else { sp = stage + mm * (NPL * 32) + f0; pstride = 32; }
-#pragma unroll
-                for (int l = 0; l < NPL; l++) *reinterpret_cast<u32 *>(sp + l * pstride) = pl[l];
-            } else {
-#pragma unroll
-                for (int reg = 0; reg < 4; reg++)
-                    // canonical
-                    if (f0 + reg < a.F) a.ys[(((size_t)slot * a.B + b) * a.F + f0 + reg) * (2 * a.P) + mm] = (u64)(cv[reg] + ((cv[reg] >> 63) & (long long)q));
-            }
+            conv1_store4(a, stage, cv, mm, f0, chan_bytes, q, slot, b);
         }
         if (a.xl_out) {
             __syncthreads();
-            i8 *dst = a.xl_out + ((size_t)slot * a.Bout + a.b0 + b) * a.out_img_bytes;
-            if (a.out_zdc) {              // the staging area IS the image's byte layout
-                for (unsigned o = threadIdx.x; o < a.out_img_bytes / 16; o += blockDim.x)
-                    *reinterpret_cast<uint4 *>(dst + (size_t)o * 16) = *reinterpret_cast<const uint4 *>(stage + (size_t)o * 16);
+            conv1_copy_out(a, stage, slot, b);
+        }
+    }
+}
+
+// ---- pixel-major form: windows of at most 40 taps --------------------------------------------------------------------------------------------------------
+// The same layer with the image limb index inside the reduction.  Write a centred image residue as x = sum_l a_l 256^l and let W'_l = centred(w 256^l mod q)
+// with balanced digits W'_{l,m}: x w = sum_m 256^m E_m (mod q), E_m = sum over (tap, l) of a_l[tap] W'_{l,m}[tap].  K = (tap, l): a pixel is ONE 8-byte value
+// (balanced_digit_bytes: seven digits and a zero byte), the image is [poly][row][column] of pixels, and K group G of an MFMA -- 16 bytes -- is taps 2G and
+// 2G + 1 (tap = kx yf + ky): every tap is an aligned 8-byte LDS read, two neighbouring taps at an even column one 16-byte read (always so for an even window
+// width at an even column stride: the 6 x 6 stride-2 window of PlainModelTiny), no byte alignment and no per-plane loop.  40 taps = 20 groups = NJ = 5 MFMAs
+// per weight-digit plane: 35 per tile instead of 49, 7 accumulators instead of 13, and the value they make is below 2^72: one fold (limbred.h
+// diag7_fold_centred) instead of three.  The A operand is 35 resident fragments (140 registers) per wave: 8 waves per workgroup, two per SIMD.
+// Weights Wp [slot][7 planes m][NJ][32 filters][4 K groups][2 taps][8: l] (limb_pack_w1_kernel_px).  Wave roles, C layout, staging and copy-out as above.
+#define NJ 5
+__global__ void __launch_bounds__(512) mfma_conv1_kernel_px(Conv1Args a)
+{
+    extern __shared__ __attribute__((aligned(16))) i8 lds[];                  // [2 image buffers][output staging]
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nwaves = blockDim.x >> 6;
+    const int slot = blockIdx.x, i = slot / a.n, s = slot % a.n;
+    const u64 q = a.mods[i].q;
+    const u32 qbits = a.qbits[i], qfold = a.qfold[i];
+    const int g = lane >> 4, r16 = lane & 15, nt = wave & 1, tile0 = wave >> 1, tile_step = nwaves >> 1;
+    // operand A = the weights: this lane's filter nt * 16 + r16, K group g of each of the NJ steps, every digit plane m: resident for the whole workgroup
+    v4i wv[NPL][NJ];
+    {
+        const i8 *ws = a.wl + (size_t)slot * (NPL * NJ * 32 * 64) + (nt * 16 + r16) * 64 + g * 16;
+#pragma unroll
+        for (int m = 0; m < NPL; m++)
+#pragma unroll
+            for (int j = 0; j < NJ; j++) wv[m][j] = *reinterpret_cast<const v4i *>(ws + (m * NJ + j) * (32 * 64));
+    }
+    u32 PB[4];
+#pragma unroll
+    for (int j = 0; j < 3; j++) PB[j] = (u32)a.acc7[i][2 * j] + ((u32)a.acc7[i][2 * j + 1] << 8);
+    PB[3] = (u32)a.acc7[i][6];
+    // this lane's taps of step j, as byte offsets from the window's first pixel: low half tap 2G, high half tap 2G + 1, G = 4j + g (taps past the window meet
+    // zero weights: they re-read its last tap, or its last pair)
+    u32 toff[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; j++) {
+        const int last = a.px_pair ? a.px_taps - 2 : a.px_taps - 1;
+        const int t0 = min(2 * (4 * j + g), last), t1 = min(2 * (4 * j + g) + 1, a.px_taps - 1);
+        const u32 o0 = (u32)(t0 / a.px_yf) * a.px_rs + (u32)(t0 % a.px_yf) * 8, o1 = (u32)(t1 / a.px_yf) * a.px_rs + (u32)(t1 % a.px_yf) * 8;
+        toff[j] = o0 | (o1 << 16);
+    }
+    const u32 rcp_yo = (65536u + (u32)a.yo - 1) / (u32)a.yo;
+    const int f0 = nt * 16 + 4 * g;
+    long long bvc[4];
+#pragma unroll
+    for (int reg = 0; reg < 4; reg++) {
+        const int f = f0 + reg;
+        const u64 bv = (a.bias && f < a.F && !(lane & 1)) ? a.bias[((size_t)f * a.k + i) * a.n + s] : 0;
+        bvc[reg] = bv > (q >> 1) ? (long long)(bv - q) : (long long)bv;
+    }
+    i8 *stage = lds + 2 * (size_t)a.img_stride;
+    const i8 *ximg = a.xr + (size_t)slot * a.B * a.img_stride;
+    const int pieces = a.img_stride / 1024;
+    auto issue_img = [&](int b) {
+        i8 *dst = lds + (b & 1) * (size_t)a.img_stride;
+        const i8 *src = ximg + (size_t)b * a.img_stride + lane * 16;
+        for (int pc = wave; pc < pieces; pc += nwaves)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + pc * 1024),
+                (__attribute__((address_space(3))) void *)(dst + pc * 1024), 16, 0, 0);
+    };
+    if (a.xl_out && a.out_zdc && threadIdx.x < 16) { const unsigned e = a.out_img_bytes - 16 + threadIdx.x;
+        if (e >= (unsigned)(NPL * 2 * a.P * a.out_zdc)) stage[e] = 0; }
+    issue_img(0);
+    const int chan_bytes = a.out_zdc ? a.out_zdc : 32;
+    for (int b = 0; b < a.B; b++) {
+        __builtin_amdgcn_s_waitcnt(0 | (7 << 4) | (15 << 8));
+        __syncthreads();
+        if (b + 1 < a.B) issue_img(b + 1);
+        const i8 *img = lds + (b & 1) * (size_t)a.img_stride;
+        for (int mt = tile0; mt < a.mtiles; mt += tile_step) {
+            // operand B = this lane's output row: pixel p, poly c (rows past 2P re-read the last one and are never stored)
+            const int mm = mt * 16 + r16, mrow = min(mm, 2 * a.P - 1), p = mrow >> 1, c = mrow & 1, ox = (int)(((u32)p * rcp_yo) >> 16), oy = p - ox * a.yo;
+            const i8 *win = img + c * a.poly_bytes + (u32)(ox * a.xs) * a.px_rs + (u32)(oy * a.ystr) * 8;
+            v4i bv[NJ];
+            if (a.px_pair) {
+#pragma unroll
+                for (int j = 0; j < NJ; j++) bv[j] = *reinterpret_cast<const v4i *>(win + (toff[j] & 0xffffu));
             } else {
-                const unsigned per_plane = a.out_img_bytes / (NPL * 16);      // 16-byte pieces of one plane: (row, half)
-                for (unsigned o = threadIdx.x; o < NPL * per_plane; o += blockDim.x) {
-                    const unsigned l = o / per_plane, rem = o - l * per_plane;
-                    *reinterpret_cast<uint4 *>(dst + (size_t)o * 16) = *reinterpret_cast<const uint4 *>(stage + (rem >> 1) * (NPL * 32) + l * 32 +
-                        (rem & 1) * 16);
+#pragma unroll
+                for (int j = 0; j < NJ; j++) {
+                    const uint2 t0 = *reinterpret_cast<const uint2 *>(win + (toff[j] & 0xffffu)), t1 = *reinterpret_cast<const uint2 *>(win + (toff[j] >> 16));
+                    bv[j] = v4i{(int)t0.x, (int)t0.y, (int)t1.x, (int)t1.y};
                 }
             }
+            v4i acc[NPL];
+#pragma unroll
+            for (int m = 0; m < NPL; m++) acc[m] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wv[m][0], bv[0], v4i{0, 0, 0, 0}, 0, 0, 0);
+#pragma unroll
+            for (int j = 1; j < NJ; j++)
+#pragma unroll
+                for (int m = 0; m < NPL; m++) acc[m] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wv[m][j], bv[j], acc[m], 0, 0, 0);
+            // epilogue: four consecutive filters of output row mm
+            long long cv[4];
+#pragma unroll
+            for (int reg = 0; reg < 4; reg++) {
+                int E[NPL];
+#pragma unroll
+                for (int m = 0; m < NPL; m++) E[m] = acc[m][reg];
+                cv[reg] = diag7_fold_centred(E, q, qbits, qfold, bvc[reg], PB);
+            }
+            conv1_store4(a, stage, cv, mm, f0, chan_bytes, q, slot, b);
+        }
+        if (a.xl_out) {
+            __syncthreads();
+            conv1_copy_out(a, stage, slot, b);
         }
     }
 }
@@ -316,6 +445,47 @@ __global__ void __launch_bounds__(256) limb_pack_rows1_kernel(const u64 *x, i8 *
         *reinterpret_cast<uint4 *>(dst) = *reinterpret_cast<const uint4 *>(st + (size_t)run * (RG * 32) + part * 16);
     }
 }
+// The pixel-major image: Xp [slot][B][poly][row][column], one balanced_digit_bytes value per pixel, rows rs bytes and polys poly_bytes apart.  The same workgroup
+// and the same 32-slot transpose through LDS; a thread stages its 16 pixels as they are (no per-byte scatter into planes), and the RG rows a slot owns are one
+// contiguous run of RG * rs bytes in Xp.  Staging: [slot][RG rows][rs bytes] + 16 bytes per slot (neighbouring slots on different banks).
+__global__ void __launch_bounds__(256) limb_pack_rows1_kernel_px(const u64 *x, i8 *xr, const ModParams *mods, int n, int k, int B, int xd, int yd, int packed,
+                                                                 unsigned img_stride, unsigned poly_bytes, unsigned rs)
+{
+    extern __shared__ __attribute__((aligned(16))) i8 stp[];
+    const unsigned sstride = RG * rs + 16;
+    const int sblocks = n / RSL;
+    const int sb = blockIdx.x % (sblocks * k), i = sb / sblocks, s0 = (sb % sblocks) * RSL;
+    const int rgs = (xd + RG - 1) / RG;
+    size_t r = blockIdx.x / (sblocks * k);                       // (b*2 + c)*rgs + row group
+    const int rg = (int)(r % rgs); r /= rgs; const int c = (int)(r % 2); const int b = (int)(r / 2);
+    const u64 q = mods[i].q;
+    const int lane = threadIdx.x & (RSL - 1), qrow = (threadIdx.x >> 5) & (RG - 1), h = threadIdx.x >> 7, row = rg * RG + qrow;
+    if (row < xd) {
+        const u64 *src = x + ((((size_t)b * xd * yd + (size_t)row * yd + h * 16) * 2 + c) * k + i) * (size_t)n + s0 + lane;
+        u64 *sp = reinterpret_cast<u64 *>(stp + (size_t)lane * sstride + qrow * rs) + h * 16;
+#pragma unroll
+        for (int colx = 0; colx < 16; colx++) {
+            const int col = h * 16 + colx;
+            if ((unsigned)col * 8 >= rs) continue;
+            u64 dg = 0;                                              // (a column past yd: the padding of an odd width)
+            if (col < yd) {
+                u64 v = src[(size_t)colx * 2 * k * n];
+                if (packed) v = (v & 0xffffffffULL) | ((v >> 32) << 28);
+                dg = balanced_digit_bytes(v, q);
+            }
+            sp[colx] = dg;
+        }
+    }
+    __syncthreads();
+    // RSL runs of RG * rs bytes, 16 bytes per lane (rows past xd of a ragged last group are not stored)
+    const int per_run = RG * rs / 16, valid = min(RG, xd - rg * RG) * (int)rs / 16;
+    for (int o = threadIdx.x; o < RSL * per_run; o += 256) {
+        const int sl = o / per_run, part = o - sl * per_run;
+        if (part >= valid) continue;
+        i8 *dst = xr + (((size_t)i * n + s0 + sl) * B + b) * img_stride + (size_t)c * poly_bytes + (size_t)(rg * RG) * rs + part * 16;
+        *reinterpret_cast<uint4 *>(dst) = *reinterpret_cast<const uint4 *>(stp + (size_t)sl * sstride + part * 16);
+    }
+}
 // NTT-form weights w [F][1][xf][yf][k][n] -> Wl1 [slot][7 planes][32 filters][64 taps], tap = kx*8 + ky (pre-zeroed).  (No 2^64 factor since round 4: the
 // kernel's reduction folds, it no longer divides by 2^64.)
 __global__ void __launch_bounds__(64) limb_pack_w1_kernel(const u64 *w, i8 *wl, const ModParams *mods, int n, int k, int F, int xf, int yf)
@@ -331,12 +501,57 @@ __global__ void __launch_bounds__(64) limb_pack_w1_kernel(const u64 *w, i8 *wl, 
     for (int l = 0; l < NPL; l++) dst[(size_t)l * (32 * 64)] = (i8)d[l];
 }
 
+// The pixel-major form's weights: Wp [slot][7 digit planes m][NJ steps][32 filters][4 K groups][2 taps][8: image limb l] (pre-zeroed), tap = kx*yf + ky = 8 step +
+// 2 group + half: byte l of a tap is digit m of W'_l = centred(w 256^l mod q) -- one mulmod by 256 per image limb, then the digits.
+__global__ void __launch_bounds__(64) limb_pack_w1_kernel_px(const u64 *w, i8 *wl, const ModParams *mods, int n, int k, int F, int xf, int yf)
+{
+    const int sblocks = n / 64;
+    const int sb = blockIdx.x % (sblocks * k), i = sb / sblocks, s = (sb % sblocks) * 64 + threadIdx.x;
+    size_t r = blockIdx.x / (sblocks * k);                       // (f*xf + kx)*yf + ky
+    const int ky = (int)(r % yf); r /= yf; const int kx = (int)(r % xf); const int f = (int)(r / xf);
+    const ModParams m = mods[i];
+    u64 v = w[((((size_t)f * xf + kx) * yf + ky) * k + i) * (size_t)n + s];
+    const int tap = kx * yf + ky, G = tap >> 1;
+    i8 *dst = wl + ((size_t)i * n + s) * (NPL * NJ * 32 * 64) + ((G >> 2) * 32 + f) * 64 + (G & 3) * 16 + (tap & 1) * 8;
+    for (int l = 0; l < NPL; l++) {
+        int d[NPL]; limb_digits1(v, m.q, d);
+#pragma unroll
+        for (int dm = 0; dm < NPL; dm++) dst[(size_t)dm * (NJ * 32 * 64) + l] = (i8)d[dm];
+        v = mulmod(v, 256, m);
+    }
+}
+
 // ---- launchers ---------------------------------------------------------------------------------------------------------------------------
 // per (slot, image): 7 planes x 2 polys x (xd rows + 1) x 32 bytes: the extra row puts the two polys' blocks 8 LDS banks apart (xd = 28: 896-byte blocks would
 // be 224 dwords = 0 banks apart, and the window reads of a pixel's two polys -- neighbouring lanes -- a two-way conflict each); it also takes the last window's
 // read-ahead
 static inline unsigned conv1_poly_bytes(int xd) { return ((unsigned)xd + 1) * 32; }
 static inline unsigned conv1_img_stride(int xd) { const unsigned b = NPL * 2 * conv1_poly_bytes(xd); return (b + 1023) / 1024 * 1024; }
+// pixel-major form: rows of yd 8-byte pixels rounded up to 16 bytes; the second poly's block starts 128 bytes (mod 256) past the first one's, so that the eight
+// pixels x two polys that one LDS cycle of a 16-byte window read serves cover the 64 banks once (28 x 28: 224-byte rows, 6272-byte blocks, no padding at all)
+static inline unsigned conv1_px_rs(int yd) { return ((unsigned)yd * 8 + 15) / 16 * 16; }
+static inline unsigned conv1_px_poly_bytes(int xd, int yd) { const unsigned b = (unsigned)xd * conv1_px_rs(yd); return b + (128 + 256 - b % 256) % 256; }
+static inline unsigned conv1_px_img_stride(int xd, int yd) { return (2 * conv1_px_poly_bytes(xd, yd) + 1023) / 1024 * 1024; }
+static bool conv1_fits(unsigned img_stride, int xd, int yd, int xs, int ys_, int xf, int yf)
+{
+    const int xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys_ + 1;
+    // two image buffers + the staging area of a limb result (at most 32 channel bytes per position) must fit the 160 KiB of LDS
+    return 2 * (size_t)img_stride + (size_t)NPL * xo * yo * 2 * 32 <= 160 * 1024;
+}
+// Which form a layer runs: 1 plane-major (mfma_conv1_kernel), 2 pixel-major (mfma_conv1_kernel_px).  Decided by the tuning switch, the window and the filter
+// count ALONE, so that the weights (packed without knowing the image) and every later launch agree; conv1_narrow does not enter (the tests flip it between
+// launches on one set of weights).  Pixel-major takes windows of at most 8 NJ = 40 taps and moduli within conv1_fold7_ok; a forced form the layer cannot take
+// falls back to the other one.  Auto: pixel-major wherever it applies except for 17-20 filters, whose second filter group has the packed plane-major form
+// (DESIGN.md section 4.2 has the measurements).
+int k_limb_conv1_form(const crc_ctx *c, int xf, int yf, int nf)
+{
+    bool px = xf * yf <= 8 * NJ;
+    for (int i = 0; i < c->k && px; i++) px = conv1_fold7_ok(c->tabs[i].m.q, c->tabs[i].m.bits, fold_constant(c->tabs[i].m.q, c->tabs[i].m.bits));
+    const int forced = c->tune.conv1_form;
+    if (forced == 1 || !px) return 1;
+    if (forced == 2) return 2;
+    return nf > 16 && nf <= 20 ? 1 : 2;
+}
 bool k_limb_conv1_shape(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys_, int xf, int yf, int nf)
 {
     if (zd != 1 || xf > 8 || yf > 8 || nf > 32 || yd > 32 || c->n < 64 || c->k > MAXK) return false;
@@ -345,23 +560,30 @@ bool k_limb_conv1_shape(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys
     for (int i = 0; i < c->k; i++) if (!conv1_fold_ok(c->tabs[i].m.q, c->tabs[i].m.bits, fold_constant(c->tabs[i].m.q, c->tabs[i].m.bits))) return false;
     const int xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys_ + 1;
     if (xo * yo > 1024) return false;                          // (the kernel's reciprocal division of a pixel index by yo <= 32 is exact below 2048)
-    // two image buffers + the staging area of a limb result (at most 32 channel bytes per position) must fit the 160 KiB of LDS
-    return 2 * (size_t)conv1_img_stride(xd) + (size_t)NPL * xo * yo * 2 * 32 <= 160 * 1024;
+    // (the pixel-major image is the smaller one up to 28 columns; wider than that it can be up to 14 % larger)
+    return conv1_fits(k_limb_conv1_form(c, xf, yf, nf) == 2 ? conv1_px_img_stride(xd, yd) : conv1_img_stride(xd), xd, yd, xs, ys_, xf, yf);
 }
-size_t k_limb_conv1_weights_bytes(const crc_ctx *c) { return (size_t)c->n * c->k * NPL * 32 * 64; }
-size_t k_limb_conv1_image_bytes(const crc_ctx *c, int B, int xd) { return (size_t)c->n * c->k * B * conv1_img_stride(xd); }
+static size_t conv1_form_weights_bytes(const crc_ctx *c, int form) { return (size_t)c->n * c->k * NPL * 32 * 64 * (form == 2 ? NJ : 1); }
+size_t k_limb_conv1_weights_bytes(const crc_ctx *c) { return conv1_form_weights_bytes(c, 2); }            // enough for either form
+size_t k_limb_conv1_weights_bytes_for(const crc_ctx *c, int nf, int xf, int yf) { return conv1_form_weights_bytes(c, k_limb_conv1_form(c, xf, yf, nf)); }
+size_t k_limb_conv1_image_bytes(const crc_ctx *c, int B, int xd, int yd, int xf, int yf, int nf)
+{
+    return (size_t)c->n * c->k * B * (k_limb_conv1_form(c, xf, yf, nf) == 2 ? conv1_px_img_stride(xd, yd) : conv1_img_stride(xd));
+}
 
 static void conv1_tables(const crc_ctx *c, Conv1Args &a)      // limbred.h: accumulator biases and q^-1 mod 2^64 per modulus
 {
-    for (int i = 0; i < c->k; i++) { conv1_bias_table(c->tabs[i].m.q, a.acc0[i]); a.qbits[i] = c->tabs[i].m.bits;
+    for (int i = 0; i < c->k; i++) { conv1_bias_table(c->tabs[i].m.q, a.acc0[i]); conv1_bias7_table(c->tabs[i].m.q, a.acc7[i]); a.qbits[i] = c->tabs[i].m.bits;
         a.qfold[i] = fold_constant(c->tabs[i].m.q, c->tabs[i].m.bits); }
 }
 
 int k_limb_conv1_pack_weights(crc_ctx *c, const u64 *w, i8 *wl, int nf, int xf, int yf, hipStream_t st)
 {
-    HIPCHK(hipMemsetAsync(wl, 0, k_limb_conv1_weights_bytes(c), st));
+    const int form = k_limb_conv1_form(c, xf, yf, nf);
+    HIPCHK(hipMemsetAsync(wl, 0, conv1_form_weights_bytes(c, form), st));
     const size_t blocks = (size_t)(c->n / 64) * c->k * nf * xf * yf;
-    hipLaunchKernelGGL(limb_pack_w1_kernel, dim3((unsigned)blocks), dim3(64), 0, st, w, wl, c->d_mods, c->n, c->k, nf, xf, yf);
+    if (form == 2) hipLaunchKernelGGL(limb_pack_w1_kernel_px, dim3((unsigned)blocks), dim3(64), 0, st, w, wl, c->d_mods, c->n, c->k, nf, xf, yf);
+    else hipLaunchKernelGGL(limb_pack_w1_kernel, dim3((unsigned)blocks), dim3(64), 0, st, w, wl, c->d_mods, c->n, c->k, nf, xf, yf);
     HIPCHK(hipGetLastError());
     return CRC_OK;
 }
@@ -374,20 +596,35 @@ int k_limb_conv1(crc_ctx *c, const u64 *x, bool packed, i8 *xr, const i8 *wl, u6
     if (B == 0) return CRC_OK;
     if (!k_limb_conv1_shape(c, 1, xd, yd, xs, ys_, xf, yf, nf)) return CRC_ERR_UNSUPPORTED;
     const int xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys_ + 1;
+    const int form = k_limb_conv1_form(c, xf, yf, nf);
     Conv1Args a{};
     a.xr = xr; a.wl = wl; a.ys = ys; a.xl_out = xl_out; a.mods = c->d_mods; a.bias = bias_ntt;
     a.n = c->n; a.k = c->k; a.B = B; a.Bout = Bout; a.b0 = b0; a.xd = xd; a.yo = yo; a.xs = xs; a.ystr = ys_; a.P = xo * yo; a.F = nf;
         a.mtiles = (2 * a.P + 15) / 16;
-    a.poly_bytes = conv1_poly_bytes(xd); a.plane_bytes = 2 * a.poly_bytes; a.img_stride = conv1_img_stride(xd);
     // (the limb tensor of the convolution behind: its layout follows ITS channel count = this layer's filters)
     a.out_zdc = a.P > 1 ? k_limb_flat_zdc(nf) : 0;
     a.out_img_bytes = a.out_zdc ? (unsigned)((NPL * 2 * a.P * a.out_zdc + 15) / 16 * 16) : (unsigned)(NPL * a.P * 2 * 32);
-    a.narrow = c->tune.conv1_narrow != 0 && nf > 16 && nf <= 20 ? 1 : 0;
     conv1_tables(c, a);
+    const size_t pack_blocks = (size_t)(c->n / RSL) * c->k * B * 2 * ((xd + RG - 1) / RG);
+    if (pack_blocks > 0x7fffffffULL) return CRC_ERR_INVALID_ARGUMENT;
+    if (form == 2) {
+        a.px_rs = conv1_px_rs(yd); a.poly_bytes = conv1_px_poly_bytes(xd, yd); a.img_stride = conv1_px_img_stride(xd, yd);
+        a.px_taps = xf * yf; a.px_yf = yf;
+        a.px_pair = yf % 2 == 0 && ys_ % 2 == 0 ? 1 : 0;
+        hipLaunchKernelGGL(limb_pack_rows1_kernel_px, dim3((unsigned)pack_blocks), dim3(256), RSL * (RG * a.px_rs + 16), st, x, xr, c->d_mods, c->n, c->k, B, xd,
+            yd, packed ? 1 : 0, a.img_stride, a.poly_bytes, a.px_rs);
+        HIPCHK(hipGetLastError());
+        // (140 registers of resident weights: two waves per SIMD, whatever conv1_waves asks for)
+        const size_t lds = 2 * (size_t)a.img_stride + (xl_out ? a.out_img_bytes : 0);
+        { const int rc = crc_ctx_ensure_lds(c, (const void *)mfma_conv1_kernel_px, lds); if (rc) return rc; }
+        hipLaunchKernelGGL(mfma_conv1_kernel_px, dim3((unsigned)(c->n * c->k)), dim3(64 * 8), lds, st, a);
+        HIPCHK(hipGetLastError());
+        return CRC_OK;
+    }
+    a.poly_bytes = conv1_poly_bytes(xd); a.plane_bytes = 2 * a.poly_bytes; a.img_stride = conv1_img_stride(xd);
+    a.narrow = c->tune.conv1_narrow != 0 && nf > 16 && nf <= 20 ? 1 : 0;
     {
-        const size_t blocks = (size_t)(c->n / RSL) * c->k * B * 2 * ((xd + RG - 1) / RG);
-        if (blocks > 0x7fffffffULL) return CRC_ERR_INVALID_ARGUMENT;
-        hipLaunchKernelGGL(limb_pack_rows1_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, xr, c->d_mods, c->n, c->k, B, xd, yd, packed ? 1 : 0,
+        hipLaunchKernelGGL(limb_pack_rows1_kernel, dim3((unsigned)pack_blocks), dim3(256), 0, st, x, xr, c->d_mods, c->n, c->k, B, xd, yd, packed ? 1 : 0,
             a.img_stride, a.plane_bytes,
                            a.poly_bytes);
         HIPCHK(hipGetLastError());

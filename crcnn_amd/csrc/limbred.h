@@ -156,6 +156,44 @@ CRC_HD long long diag_fold_short_centred(const int (&D)[13], u64 q, u32 bits, u3
     diag_pack_words(D, PB, u);
     return fold_words_centred(u[0], u[1], u[2], u[3], q, bits, fold, bias_centred);
 }
+// ---- seven diagonals, one fold (kernels_mfma1.hip, pixel-major form) ------------------------------------------------------------------------------------------
+// With the image limb index inside the reduction (x w = sum_m 256^m E_m, E_m = sum over (tap, l) of a_l[tap] W'_{l,m}[tap], W'_l = centred(w 256^l mod q)) only the
+// seven weight-digit planes carry accumulators.  At most 64 taps: |E_m| <= 64 * 7 * 2^14 = 0.875 2^23, so with biases B_m = 2^23 (+ the balanced digits of the distance
+// of K0 = sum B_m 2^(8m) to the nearest multiple of q, at most 128 each) every E'_m = B_m + E_m lies in (0, 0.94 2^24), a pair E'_2j + E'_2j+1 2^8 fits a word, and
+// 0 < U = sum E'_m 2^(8m) < 2^72.01 is V = x w plus a multiple of q.  U >> b < 2^19.1 for b >= 53: ONE fold U = Uh 2^b + Ul -> Ul + Uh f leaves a value below
+// 2^b + 2^45.1 < 2q (conv1_fold7_ok), one v_mad_u64_u32 instead of the three folds and four multiplies of fold_words_centred.
+// PB: the biases pair by pair, PB_j = B_2j + B_2j+1 2^8 (j < 3), PB_3 = B_6 -- null when the diagonals arrive biased already.
+CRC_HD void diag7_pack_words(const int (&E)[7], const u32 *PB, u32 (&u)[3])
+{
+    u32 P[4];
+    for (int j = 0; j < 3; j++) P[j] = (u32)E[2 * j] + ((u32)E[2 * j + 1] << 8);
+    P[3] = (u32)E[6];
+    if (PB) for (int j = 0; j < 4; j++) P[j] += PB[j];
+    // U = (P2 : P0) + ((P3 : P1) << 16): three words, u2 < 2^9
+    const u32 o0 = P[1] << 16, o1 = crc_alignbit(P[3], P[1], 16), o2 = P[3] >> 16;
+    const u64 ev = ((u64)P[2] << 32) | P[0];
+    const u64 lo64 = ev + (((u64)o1 << 32) | o0);
+    u[0] = (u32)lo64; u[1] = (u32)(lo64 >> 32); u[2] = o2 + (lo64 < ev);
+}
+// the centred representative of (U + bias) mod q, bias centred: in [-(q-1)/2, (q-1)/2]
+CRC_HD long long fold7_words_centred(u32 u0, u32 u1, u32 u2, u64 q, u32 bits, u32 fold, long long bias_centred)
+{
+    const u32 sb = bits - 32, m1 = (1u << sb) - 1;
+    const u32 uh = crc_alignbit(u2, u1, sb);                                    // U >> b < 2^20
+    const u64 r = (u64)uh * fold + (((u64)(u1 & m1) << 32) | u0);                // < 2^b + 2^46 < 2 q
+    // r - q + bias lies in [-1.5 q, 1.5 q): one conditional + q, then one conditional - q
+    long long t = (long long)(r - q) + bias_centred;
+    const long long h = (long long)(q >> 1);
+    t += t < -h ? (long long)q : 0;
+    t -= t > h ? (long long)q : 0;
+    return t;
+}
+CRC_HD long long diag7_fold_centred(const int (&E)[7], u64 q, u32 bits, u32 fold, long long bias_centred, const u32 *PB = nullptr)
+{
+    u32 u[3];
+    diag7_pack_words(E, PB, u);
+    return fold7_words_centred(u[0], u[1], u[2], q, bits, fold, bias_centred);
+}
 CRC_HD u64 centred_digit_bytes(long long cv) { return ((u64)cv + 0x0080808080808080ULL) ^ 0x0080808080808080ULL; }
 
 // the 7 balanced base-256 digits of a canonical residue's centred representative, one per byte: the bytes of (centred value + 0x80...80) with their top bits flipped
@@ -200,4 +238,32 @@ inline void conv1_bias_table(u64 q, int (&out)[13])
     for (int d = 0; d < 13; d++) B[d] = d <= 10 ? 1 << 23 : d == 11 ? 1 << 21 : 1 << 19;
     bias_to_multiple(q, B);
     for (int d = 0; d < 13; d++) out[d] = (int)B[d];
+}
+
+// seven-diagonal form: B_m = 2^23, moved to a multiple of q by the (at most seven, |q/2| < 2^54) balanced digits of the distance
+inline void conv1_bias7_table(u64 q, int (&out)[7])
+{
+    typedef unsigned __int128 u128;
+    long long B[7];
+    u128 K0 = 0;
+    for (int m = 0; m < 7; m++) { B[m] = 1 << 23; K0 += (u128)(u64)B[m] << (8 * m); }
+    const u64 rem = (u64)(K0 % q);
+    long long delta = rem > q / 2 ? (long long)(q - rem) : -(long long)rem;
+    for (int m = 0; m < 7; m++) { const long long dg = (long long)(signed char)(delta & 0xff); B[m] += dg; delta = (delta - dg) >> 8; }
+    for (int m = 0; m < 7; m++) out[m] = delta == 0 ? (int)B[m] : 0;                   // (delta != 0: q >= 2^55, which conv1_fold7_ok refuses)
+}
+// precondition of diag7_fold_centred for reductions of at most 64 taps (checked on the host): q = 2^b - f with 53 <= b <= 55 and f < 2^26, the biases of
+// conv1_bias7_table reach a multiple of q, and the fold of the largest biased U stays below 2q
+inline bool conv1_fold7_ok(u64 q, u32 bits, u32 fold)
+{
+    typedef unsigned __int128 u128;
+    if (bits < 53 || bits > 55 || fold == 0 || fold >= (1u << 26) || (((u64)1 << bits) - fold) != q) return false;
+    int B[7]; conv1_bias7_table(q, B);
+    u128 umax = 0, k0 = 0;
+    for (int m = 0; m < 7; m++) {
+        if (B[m] <= 64 * 7 * 16384) return false;                                         // a bias must exceed the largest |E_m|
+        umax += (u128)(u64)(B[m] + 64 * 7 * 16384) << (8 * m); k0 += (u128)(u64)B[m] << (8 * m);
+    }
+    if (k0 % q != 0) return false;
+    return (umax >> bits) * fold + ((u128)1 << bits) < (u128)2 * q;
 }

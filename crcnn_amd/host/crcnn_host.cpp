@@ -848,7 +848,7 @@ bool ConvolutionalLayer::limbWeights(int B)
     if (planned != CRC_NTTL1 && !(planned == CRC_NTTL && limbFits(nf, zd, xf, yf))) return false;
     if (w_form == CRC_NTTP) packWeights(true);
     if (planned == CRC_NTTL1) {          // one-channel convolutions have their own matrix-core kernel (kernels_mfma1.hip)
-        auto wl = make_shared<DeviceBuffer>(crc_limb_conv1_weights_bytes(ctx()));
+        auto wl = make_shared<DeviceBuffer>(crc_limb_conv1_weights_bytes_for(ctx(), nf, xf, yf));
         chk(crc_limb_conv1_pack_weights(ctx(), (const uint64_t *)d_w->ptr, nf, xf, yf, wl->ptr, stream()), "crc_limb_conv1_pack_weights");
         chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
         // (the canonical copy of a one-channel layer is small: kept, so that the weights can go back on the wire)

@@ -464,7 +464,7 @@ class Network:
         self._build_tilewise()
         for idx, (kind, name, a, p, ishape, oshape) in enumerate(self.plan):
             if self.conv1_eligible(kind, a) and not p.get("streamed"):
-                nbytes = E.limb_conv1_weights_bytes()
+                nbytes = E.limb_conv1_weights_bytes_for(a["nf"], a["xf"], a["yf"])
                 wl = self.alloc(nbytes)
                 E.limb_conv1_pack_weights(p["w"], a["nf"], a["xf"], a["yf"], wl)
                 E.sync()

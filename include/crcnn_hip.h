@@ -278,6 +278,12 @@ int    crc_limb_pack_tensor_at(crc_ctx *ctx, const uint64_t *d_x, int in_form, i
 /* one-channel convolutions on the matrix cores (w_form = CRC_NTTL1): eligibility of a shape, size of the weights, conversion from CRC_NTT weights */
 int    crc_limb_conv1_supported(const crc_ctx *ctx, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf);
 size_t crc_limb_conv1_weights_bytes(const crc_ctx *ctx);
+/* the kernel has two forms (tuning key conv1_form / CRC_CONV1_FORM: 0 by shape, 1 plane-major image, 2 pixel-major image with limb-folded weights, windows of at
+ * most 40 taps; a forced form the shape cannot take falls back to the other).  The weights are packed for the form in force when crc_limb_conv1_pack_weights runs:
+ * set the key before that and leave it alone afterwards.  crc_limb_conv1_weights_bytes is enough for either form, ..._for what the layer's own form needs;
+ * crc_limb_conv1_form reports the form a shape runs (0: not a one-channel matrix-core shape) */
+size_t crc_limb_conv1_weights_bytes_for(const crc_ctx *ctx, int nf, int xf, int yf);
+int    crc_limb_conv1_form(const crc_ctx *ctx, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf);
 int    crc_limb_conv1_pack_weights(crc_ctx *ctx, const uint64_t *d_w_ntt, int nf, int xf, int yf, void *d_wl, void *stream);
 size_t crc_conv2d_forms_work_bytes(const crc_ctx *ctx, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int in_form, int w_form,
 int out_form);
