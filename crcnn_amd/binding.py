@@ -117,6 +117,11 @@ def load():
     L.crc_square_pool_relin_forms.argtypes = [VP, VP, CI] + [CI] * 8 + [VP, CI, VP, VP, CI, VP, VP]
     L.crc_poly2_relin_work_bytes.restype = SZ; L.crc_poly2_relin_work_bytes.argtypes = [VP, SZ, CI]
     L.crc_poly2_relin_forms.argtypes = [VP, VP, CI, SZ, VP, CI, VP, VP, VP, VP, CI, VP, VP]
+    L.crc_multiply_relin_work_bytes.restype = SZ; L.crc_multiply_relin_work_bytes.argtypes = [VP, SZ, CI]
+    L.crc_multiply.argtypes = [VP, VP, VP, SZ, VP, VP, VP]
+    L.crc_multiply_relin_forms.argtypes = [VP, VP, VP, CI, SZ, VP, CI, VP, CI, VP, VP]
+    L.crc_poly3_relin_work_bytes.restype = SZ; L.crc_poly3_relin_work_bytes.argtypes = [VP, SZ, CI]
+    L.crc_poly3_relin_forms.argtypes = [VP, VP, CI, SZ, VP, CI, VP, VP, VP, VP, VP, CI, VP, VP]
     L.crc_poly2_pool_relin_supported.argtypes = [VP, CI, CI, CI]
     L.crc_poly2_pool_relin_work_bytes.restype = SZ; L.crc_poly2_pool_relin_work_bytes.argtypes = [VP] + [CI] * 9
     L.crc_poly2_pool_relin_forms.argtypes = [VP, VP, CI] + [CI] * 8 + [VP, CI, VP, VP, VP, VP, CI, VP, VP]
@@ -714,6 +719,48 @@ class Engine:
         """c2 x^2 + c1 x + c0 on `count` ciphertexts with one key switch each; d_p2 / d_p1 / d_p0: poly2_rows (None = 1 / 0 / 0)"""
         _chk(self.L.crc_poly2_relin_forms(self.c, self.p(d_x), in_form, count, self.p(d_evk), dbc, self.p(d_p2), self.p(d_p1), self.p(d_p0), self.p(d_y), out_form,
                                           self.p(d_work), self.stream), "crc_poly2_relin_forms")
+
+    # ---- ciphertext x ciphertext multiply and the degree-3 activation c3 x^3 + c2 x^2 + c1 x + c0 (crc_multiply* / crc_poly3_relin_forms)
+    def multiply_relin_work_bytes(self, count, dbc=16):
+        return self.L.crc_multiply_relin_work_bytes(self.c, count, dbc)
+
+    def multiply(self, d_x, d_y, count, d_out3, d_work):
+        """Evaluator::multiply of `count` pairs of size-2 coefficient-form ciphertexts -> size-3 ciphertexts; d_work: multiply_relin_work_bytes"""
+        _chk(self.L.crc_multiply(self.c, self.p(d_x), self.p(d_y), count, self.p(d_out3), self.p(d_work), self.stream), "crc_multiply")
+
+    def multiply_relin(self, d_x, d_y, count, d_evk, d_out, d_work, dbc=16, in_form=COEFF, out_form=COEFF):
+        """relinearize(multiply(x, y)); both inputs in in_form; the result must not overlap an input"""
+        _chk(self.L.crc_multiply_relin_forms(self.c, self.p(d_x), self.p(d_y), in_form, count, self.p(d_evk), dbc, self.p(d_out), out_form, self.p(d_work),
+                                             self.stream), "crc_multiply_relin_forms")
+
+    def poly3_rows(self, c3, c2, c1, c0):
+        """the four NTT-form plaintext rows [k][n] of poly3_relin, None where a term is absent (c3 == 1, c2 == 0, c1 == 0, c0 == 0); c3 == 0 is refused: that
+        activation is poly2's"""
+        with np.errstate(over="ignore"):                 # (a value beyond float32 becomes inf and is refused below)
+            c3, c2, c1, c0 = [float(np.float32(v)) for v in (c3, c2, c1, c0)]
+        if not all(np.isfinite(v) for v in (c3, c2, c1, c0)) or c3 == 0.0:
+            raise ValueError("poly3_rows: c3 must be non-zero and every coefficient finite")
+        rowb = self.k * self.n * 8
+
+        def row(value, delta):
+            plain, _ = self.encode(np.array([value], dtype=np.float32))
+            d_plain = self.upload(plain); d_row = self.alloc(rowb)
+            if delta:
+                self.plain_to_delta(d_plain, 1, NTT, d_row)
+            else:
+                self.plain_to_ntt(d_plain, 1, d_row)
+            self.sync()
+            return d_row
+        return (row(c3, False) if c3 != 1.0 else None, row(c2, False) if c2 != 0.0 else None, row(c1, False) if c1 != 0.0 else None,
+                row(c0, True) if c0 != 0.0 else None)
+
+    def poly3_relin_work_bytes(self, count, dbc=16):
+        return self.L.crc_poly3_relin_work_bytes(self.c, count, dbc)
+
+    def poly3_relin(self, d_x, count, d_evk, d_p3, d_p2, d_p1, d_p0, d_out, d_work, dbc=16, in_form=COEFF, out_form=COEFF):
+        """c3 x^3 + c2 x^2 + c1 x + c0 on `count` ciphertexts, two key switches each; rows: poly3_rows (None = 1 / 0 / 0 / 0)"""
+        _chk(self.L.crc_poly3_relin_forms(self.c, self.p(d_x), in_form, count, self.p(d_evk), dbc, self.p(d_p3), self.p(d_p2), self.p(d_p1), self.p(d_p0),
+                                          self.p(d_out), out_form, self.p(d_work), self.stream), "crc_poly3_relin_forms")
 
     def poly2_pool_relin_supported(self, xf, yf, dbc=16):
         return bool(self.L.crc_poly2_pool_relin_supported(self.c, dbc, xf, yf))

@@ -845,6 +845,85 @@ extern "C" int crc_poly2_pool_relin_forms(crc_ctx *c, const uint64_t *d_x, int i
     if (out_form == CRC_COEFF) RUN(crc_ntt_inv(c, d_y, planes * pout, 2, stream));
     return CRC_OK;
 }
+// ---- ciphertext x ciphertext multiply, and the degree-3 polynomial activation built on it ----
+// Evaluator::multiply for size-2 inputs (k_multiply: the square's chain with the tensor product (ac, ad + bc, bd)); passes, key packing and work layout are
+// crc_square_relin_forms'.  The result may not share memory with an input: a pass writes its results while later passes have not read their inputs, and the
+// size-3 result of crc_multiply has another stride than its inputs -- every overlap is refused rather than some allowed.  d_x == d_y is the square.
+extern "C" size_t crc_multiply_relin_work_bytes(const crc_ctx *c, size_t count, int dbc)
+{
+    if (!c || !dbc_ok(dbc)) return 0;
+    const size_t chunk = square_chunk(c), ch = count < chunk ? count : chunk;
+    const size_t mu = k_multiply_work_words(c, ch), rl = k_relin_work_words(c, ch, dbc);
+    return 8 * (k_relin_keys_words(c, dbc) + (mu > rl ? mu : rl) + ch * crc_ct_words(c, 3)) + 256;
+}
+extern "C" int crc_multiply(crc_ctx *c, const uint64_t *d_x, const uint64_t *d_y, size_t count, uint64_t *d_out3, void *d_work, void *stream)
+{
+    CHECK_CTX(c); if (!d_x || !d_y || !d_out3 || !d_work) return CRC_ERR_INVALID_ARGUMENT;
+    const size_t ctw = crc_ct_words(c, 2), ctw3 = crc_ct_words(c, 3);
+    if (ranges_overlap(d_x, 8 * count * ctw, d_out3, 8 * count * ctw3) || ranges_overlap(d_y, 8 * count * ctw, d_out3, 8 * count * ctw3)) return CRC_ERR_INVALID_ARGUMENT;
+    u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
+    const size_t chunk = square_chunk(c);
+    for (size_t o = 0; o < count; o += chunk) {
+        const size_t ch = count - o < chunk ? count - o : chunk;
+        RUN(k_multiply(c, d_x + o * ctw, d_y + o * ctw, ch, d_out3 + o * ctw3, w, S(stream)));
+    }
+    return CRC_OK;
+}
+extern "C" int crc_multiply_relin_forms(crc_ctx *c, const uint64_t *d_x, const uint64_t *d_y, int in_form, size_t count, const uint64_t *d_evk, int dbc,
+                                        uint64_t *d_out, int out_form, void *d_work, void *stream)
+{
+    CHECK_CTX(c); if (!d_x || !d_y || !d_out || !d_evk || !d_work || !form_ok(in_form) || !form_ok(out_form) || !dbc_ok(dbc)) return CRC_ERR_INVALID_ARGUMENT;
+    const size_t ctw = crc_ct_words(c, 2);
+    if (ranges_overlap(d_x, 8 * count * ctw, d_out, 8 * count * ctw) || ranges_overlap(d_y, 8 * count * ctw, d_out, 8 * count * ctw)) return CRC_ERR_INVALID_ARGUMENT;
+    u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
+    const size_t chunk = square_chunk(c), ch0 = count < chunk ? count : chunk;
+    for (size_t o = 0; o < count; o += chunk) {
+        const size_t ch = count - o < chunk ? count - o : chunk;
+        // [packed keys (filled by pass 0)][size-3 intermediates][scratch]
+        u64 *kp = w, *y3 = kp + k_relin_keys_words(c, dbc), *rest = y3 + ch0 * crc_ct_words(c, 3);
+        RUN(k_multiply(c, d_x + o * ctw, d_y + o * ctw, ch, y3, rest, S(stream), in_form == CRC_NTT, true));
+        RUN(k_relinearize(c, y3, ch, d_evk, dbc, d_out + o * ctw, rest, kp, S(stream), out_form == CRC_NTT, true, o != 0));
+    }
+    return CRC_OK;
+}
+// c3 x^3 + c2 x^2 + c1 x + c0:  s = relin(x^2), u = relin(s x), result = P3 (*) u + P2 (*) s + P1 (*) x + P0 slot-wise in NTT form (two key switches, depth 2).
+// Work: [x in NTT form, one pass (coefficient-form callers)][s, one pass][crc_multiply_relin_forms' work]; the ring-linear terms join in poly2_tail_kernel
+extern "C" size_t crc_poly3_relin_work_bytes(const crc_ctx *c, size_t count, int dbc)
+{
+    if (!c || !dbc_ok(dbc)) return 0;
+    const size_t chunk = square_chunk(c), ch = count < chunk ? count : chunk;
+    return crc_multiply_relin_work_bytes(c, count, dbc) + 8 * 2 * (ch * crc_ct_words(c, 2) + 32) + 256;
+}
+extern "C" int crc_poly3_relin_forms(crc_ctx *c, const uint64_t *d_x, int in_form, size_t count, const uint64_t *d_evk, int dbc, const uint64_t *d_p3_ntt,
+                                     const uint64_t *d_p2_ntt, const uint64_t *d_p1_ntt, const uint64_t *d_p0_ntt, uint64_t *d_out, int out_form, void *d_work,
+                                     void *stream)
+{
+    CHECK_CTX(c); if (!d_x || !d_out || !d_evk || !d_work || !form_ok(in_form) || !form_ok(out_form) || !dbc_ok(dbc)) return CRC_ERR_INVALID_ARGUMENT;
+    const size_t ctw = crc_ct_words(c, 2);
+    if (ranges_overlap(d_x, 8 * count * ctw, d_out, 8 * count * ctw)) return CRC_ERR_INVALID_ARGUMENT;
+    u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
+    const size_t chunk = square_chunk(c), ch0 = count < chunk ? count : chunk, slab = (ch0 * ctw + 31) & ~(size_t)31;
+    u64 *xh_w = w, *s_w = w + slab; w += 2 * slab;
+    for (size_t o = 0; o < count; o += chunk) {
+        const size_t ch = count - o < chunk ? count - o : chunk;
+        u64 *kp = w, *y3 = kp + k_relin_keys_words(c, dbc), *rest = y3 + ch0 * crc_ct_words(c, 3);
+        const u64 *xin = d_x + o * ctw;
+        if (in_form == CRC_COEFF) {
+            HIPCHK(hipMemcpyAsync(xh_w, xin, 8 * ch * ctw, hipMemcpyDeviceToDevice, S(stream)));
+            RUN(crc_ntt_fwd(c, xh_w, ch, 2, stream));
+            xin = xh_w;
+        }
+        u64 *yo = d_out + o * ctw;
+        RUN(k_square(c, xin, ch, y3, rest, S(stream), true, true));
+        RUN(k_relinearize(c, y3, ch, d_evk, dbc, s_w, rest, kp, S(stream), true, true, o != 0));
+        RUN(k_multiply(c, s_w, xin, ch, y3, rest, S(stream), true, true));
+        RUN(k_relinearize(c, y3, ch, d_evk, dbc, yo, rest, kp, S(stream), true, true, true));
+        RUN(k_poly2_tail(c, yo, s_w, ch, 1, 1, 1, 1, 1, 1, d_p3_ntt, d_p2_ntt, nullptr, S(stream)));
+        RUN(k_poly2_tail(c, yo, xin, ch, 1, 1, 1, 1, 1, 1, nullptr, d_p1_ntt, d_p0_ntt, S(stream)));
+    }
+    if (out_form == CRC_COEFF) RUN(crc_ntt_inv(c, d_out, count, 2, stream));
+    return CRC_OK;
+}
 extern "C" int crc_square_relin(crc_ctx *c, const uint64_t *d_x, size_t count, const uint64_t *d_evk, int dbc, uint64_t *d_y, void *d_work, void *stream)
 {
     return crc_square_relin_forms(c, d_x, CRC_COEFF, count, d_evk, dbc, d_y, CRC_COEFF, d_work, stream);

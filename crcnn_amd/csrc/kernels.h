@@ -17,6 +17,7 @@ int k_spread_ntt(crc_ctx *c, const u64 *src, size_t items, u64 *dst, hipStream_t
 int k_digit_ntt(crc_ctx *c, const u64 *src, int src_size, int src_poly, size_t count, int D, const unsigned char *dig_i, const unsigned char *dig_shift, int dbc,
                 u64 *dst, hipStream_t st, int pack_out = 0);
 int k_square_intt(crc_ctx *c, const u64 *src, u64 *dst, size_t count, bool bsk, hipStream_t st, const u64 *opt_mul = nullptr, bool *applied = nullptr);
+int k_multiply_intt(crc_ctx *c, const u64 *x, const u64 *y, u64 *dst, size_t count, bool bsk, hipStream_t st, const u64 *opt_mul = nullptr, bool *applied = nullptr);
 int k_ntt_ct_inv_scaled(crc_ctx *c, const u64 *src, u64 *dst, size_t count, int size, const u64 *mul, const u64 *mul_s, hipStream_t st);
 int k_plain_ntt(crc_ctx *c, const u64 *d_plain, size_t count, int mode, bool do_ntt, u64 *d_out, hipStream_t st);
 int k_plain_expand(crc_ctx *c, const u64 *d_compact, size_t count, u64 *d_plain, hipStream_t st);
@@ -29,6 +30,7 @@ int k_mac(crc_ctx *c, const u64 *x, const u64 *w, u64 *y, const int *d_xoff, con
 int k_pack28(crc_ctx *c, u64 *rows, size_t nrows, bool unpack, hipStream_t st);
 int k_conv_offsets(crc_ctx *c, int *xoff, int *toff, unsigned *toffw, int P, int T, int in_cts, int xd, int yd, int xs, int ys, int xf, int yf, int yo, hipStream_t st);
 size_t k_square_work_words(const crc_ctx *c, size_t cnt);
+size_t k_multiply_work_words(const crc_ctx *c, size_t cnt);          // the product of two ciphertexts: four input polynomials per pair
 size_t k_relin_work_words(const crc_ctx *c, size_t cnt, int dbc);
 size_t k_relin_keys_words(const crc_ctx *c, int dbc);
 // kernels_relin64.hip: key switching over the two fp64 primes
@@ -53,6 +55,9 @@ int k_square(crc_ctx *c, const u64 *x, size_t cnt, u64 *y3, u64 *work, hipStream
 // kernels_square64.hip: the square's auxiliary base over the engine's fp64 primes
 bool k_square64_supported(const crc_ctx *c);
 int k_square64(crc_ctx *c, const u64 *x, size_t cnt, u64 *y3, u64 *work, hipStream_t st, bool in_ntt, bool premul_c2);
+// Evaluator::multiply of size-2 ciphertexts x[i] . y[i] -> size-3 y3[i] (x == y allowed: the square); forms and premul_c2 as k_square
+int k_multiply(crc_ctx *c, const u64 *x, const u64 *y, size_t cnt, u64 *y3, u64 *work, hipStream_t st, bool in_ntt = false, bool premul_c2 = false);
+int k_multiply64(crc_ctx *c, const u64 *x, const u64 *y, size_t cnt, u64 *y3, u64 *work, hipStream_t st, bool in_ntt, bool premul_c2);
 int k_relinearize(crc_ctx *c, const u64 *x3, size_t cnt, const u64 *evk, int dbc, u64 *y, u64 *work, u64 *kp, hipStream_t st, bool out_ntt = false,
                   bool c2_premul = false, bool keys_ready = false, const u64 *p2 = nullptr, const struct PolyTail *poly = nullptr, bool *poly_fused = nullptr);
 int k_mac2(crc_ctx *c, const u64 *x, const u64 *w, u64 *y, const int *d_xoff, const int *d_toff, int B, int P, int F, int T, int in_cts,

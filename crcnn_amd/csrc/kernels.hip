@@ -26,7 +26,7 @@ struct NttArgs {
     int pack_out;                                              // forward only: store the result as 28-bit limb pairs (operand form of the MAC kernels)
     // both > 0: dst row r = (ct, j < dst_ct_rows) reads src row ct*src_ct_rows + j (leading polys of wider cts)
     int src_ct_rows, dst_ct_rows;
-    // 0 none, 1 plain lift, 2 delta scale, 3 relinearisation digit, 4 square products, 5 (inverse) scaled result
+    // 0 none, 1 plain lift, 2 delta scale, 3 relinearisation digit, 4 square products, 5 (inverse) scaled result, 6 products of two ciphertexts
     int prologue;
     // prologue 3 (forward): row = ((ct*D + g)*k + j); the source row is the premultiplied third polynomial c2 (q/q_i)^-1 mod q_i of ciphertext ct under
     //   modulus i = dig_i[g] (src = size-`src_size` ciphertexts, poly `src_poly`); the value fed to the transform is its digit (v >> dig_shift[g]) & dig_mask
@@ -34,6 +34,9 @@ struct NttArgs {
     // prologue 4 (inverse): row = ((ct*3 + p)*mod_count + j); sources are the NTT-form rows a, b of polys 0 and 1 of ciphertext ct in `src`
     //   ([ct][2][mod_count][n]); the value fed to the transform is a^2, 2ab or b^2 (Evaluator::square's dyadic products, evaluator.cpp:798-852).
     //   The three products of one (ciphertext, modulus) pair run on ONE XCD, blockIdx -> row through xcd_group; `pairs` = ciphertexts x mod_count
+    // prologue 6 (inverse): prologue 4 for two DIFFERENT ciphertexts x = (a, b) in `src` and y = (c, d) in `fma_k` (an inverse transform has no other use for that
+    //   pointer; both [ct][2][mod_count][n]): the value fed to the transform is ac, ad + bc or bd (Evaluator::multiply's tensor product, evaluator.cpp:398-700;
+    //   the reference forms the middle term as (a + b)(c + d) - ac - bd, the same residue).  Rows, XCD grouping, opt_mul as at prologue 4
     // prologue 5 (inverse): the result leaves multiplied by the per-modulus constant post_mul (Shoup companion post_mul_s) -- the square's lift wants
     //   x m~ (q/q_i)^-1 mod q_i (baseconverter.cpp:686-696), and the Shoup multiplication takes the lazy value in place of the final reduction
     int D, src_size, src_poly; unsigned long long dig_mask;
@@ -71,7 +74,8 @@ __device__ __forceinline__ u64 plain_lift(u64 c, const PlainParams &pp, int i, c
 #include "ntt_f64.h"     // the wave-local scheme: block ownership, cross layout, u64_local_passes_*
 __device__ __forceinline__ u64 split28v(u64 v) { return (v & 0x0fffffffULL) | ((v >> 28) << 32); }      // = split28 further down
 
-// PRO: load prologue compiled into this instance -- 0: a.prologue in {0 none, 1 plain lift, 2 delta scale}; 3: relinearisation digit; 4: square products
+// PRO: load prologue compiled into this instance -- 0: a.prologue in {0 none, 1 plain lift, 2 delta scale}; 3: relinearisation digit; 4: square products;
+// 6: the products of two ciphertexts
 // (separate instances keep every variant at <= 64 VGPRs = two resident 1024-thread workgroups per CU at n = 8192)
 template <bool INV, bool LAZY, int PRO>
 __device__ __forceinline__ void ntt_rows_body(const NttArgs &a)
@@ -79,7 +83,7 @@ __device__ __forceinline__ void ntt_rows_body(const NttArgs &a)
     extern __shared__ u64 sm[];
     const int n = a.n, logn = a.logn, tid = threadIdx.x, nt = blockDim.x;
     size_t row = blockIdx.x;
-    if (INV && PRO == 4) {
+    if (INV && (PRO == 4 || PRO == 6)) {
         size_t pair; unsigned p;
         if (!xcd_group(blockIdx.x, 3, a.pairs, pair, p)) return;
         row = ((pair / a.mod_count) * 3 + p) * a.mod_count + pair % a.mod_count;
@@ -105,6 +109,21 @@ __device__ __forceinline__ void ntt_rows_body(const NttArgs &a)
             const ulonglong2 av = ld2(pa + s), bv = ld2(pb + s);
             u64 v0 = mulmod(av.x, bv.x, m), v1 = mulmod(av.y, bv.y, m);
             if (p == 1) { v0 = addmod(v0, v0, q); v1 = addmod(v1, v1, q); }
+            put(s, v0, v1);
+        }
+    } else if (INV && PRO == 6) {
+        const size_t ct = row / (3 * (size_t)a.mod_count); const int p = (int)((row / a.mod_count) % 3);
+        const size_t pn = (size_t)a.mod_count * n, o = (ct * 2 * a.mod_count + mloc) * (size_t)n;
+        // p = 0: a c, p = 2: b d, p = 1: a d + b c
+        const u64 *pa = a.src + o + (p == 2 ? pn : 0), *pb = a.fma_k + o + (p == 0 ? 0 : pn);
+        const u64 *pc = a.src + o + pn, *pd = a.fma_k + o;
+        for (int s = 2 * tid; s < n; s += 2 * nt) {
+            const ulonglong2 av = ld2(pa + s), bv = ld2(pb + s);
+            u64 v0 = mulmod(av.x, bv.x, m), v1 = mulmod(av.y, bv.y, m);
+            if (p == 1) {
+                const ulonglong2 cv = ld2(pc + s), dv = ld2(pd + s);
+                v0 = addmod(v0, mulmod(cv.x, dv.x, m), q); v1 = addmod(v1, mulmod(cv.y, dv.y, m), q);
+            }
             put(s, v0, v1);
         }
     } else if (!INV && PRO == 3) {
@@ -188,7 +207,7 @@ __global__ void __launch_bounds__(CS == 1 ? 128 : CS == 2 ? 256 : CS == 3 ? 512 
     extern __shared__ u64 sm[];
     const int n = a.n, tid = threadIdx.x;
     size_t row = blockIdx.x;
-    if (INV && PRO == 4) {
+    if (INV && (PRO == 4 || PRO == 6)) {
         size_t pair; unsigned p;
         if (!xcd_group(blockIdx.x, 3, a.pairs, pair, p)) return;
         row = ((pair / a.mod_count) * 3 + p) * a.mod_count + pair % a.mod_count;
@@ -273,6 +292,28 @@ __global__ void __launch_bounds__(CS == 1 ? 128 : CS == 2 ? 256 : CS == 3 ? 512 
                 if (UNS) inv_pair_stage_unscaled(v, W1[s >> 1], q, q2 + q2); else inv_pair_stage<true>(v, W1[s >> 1], q, q2);
                 sm_store_pair64(sm, s, v.x, v.y);
             }
+        } else if (PRO == 6) {
+            const size_t ct = row / (3 * (size_t)a.mod_count); const int p = (int)((row / a.mod_count) % 3);
+            const size_t pn = (size_t)a.mod_count * n, o = (ct * 2 * a.mod_count + mloc) * (size_t)n;
+            const u64 *pa = a.src + o + (p == 2 ? pn : 0), *pb = a.fma_k + o + (p == 0 ? 0 : pn);
+            const u64 *pc = a.src + o + pn, *pd = a.fma_k + o;
+            const bool lazy_prod = m.fold != 0 && m.bits >= 53;
+#pragma unroll 4
+            for (int u = 0; u < 8; u++) {
+                const int s = f64_local_pair(u);
+                const ulonglong2 av = ld2(pa + s), bv = ld2(pb + s);
+                ulonglong2 v;
+                // below 2q each, 4q for the sum of two (the doubled product of the square): what the unscaled butterflies take
+                if (UNS && lazy_prod) {
+                    v = ulonglong2{mulmod_fold2_lazy(av.x, bv.x, m), mulmod_fold2_lazy(av.y, bv.y, m)};
+                    if (p == 1) { const ulonglong2 cv = ld2(pc + s), dv = ld2(pd + s); v.x += mulmod_fold2_lazy(cv.x, dv.x, m); v.y += mulmod_fold2_lazy(cv.y, dv.y, m); }
+                } else {
+                    v = ulonglong2{mulmod(av.x, bv.x, m), mulmod(av.y, bv.y, m)};
+                    if (p == 1) { const ulonglong2 cv = ld2(pc + s), dv = ld2(pd + s); v.x = addmod(v.x, mulmod(cv.x, dv.x, m), q); v.y = addmod(v.y, mulmod(cv.y, dv.y, m), q); }
+                }
+                if (UNS) inv_pair_stage_unscaled(v, W1[s >> 1], q, q2 + q2); else inv_pair_stage<true>(v, W1[s >> 1], q, q2);
+                sm_store_pair64(sm, s, v.x, v.y);
+            }
         } else {
             const size_t srow = a.dst_ct_rows ? (row / a.dst_ct_rows) * a.src_ct_rows + row % a.dst_ct_rows : (a.src_rows_per_item ? (row / a.mod_count) : row);
             const u64 *src = a.src + srow * (size_t)n;
@@ -327,7 +368,7 @@ __device__ __forceinline__ void ntt_rows_split_body(const NttArgs &a)
     extern __shared__ u64 sm[];
     const int n = a.n, n2 = n >> 1, logn2 = a.logn - 1, tid = threadIdx.x, nt = blockDim.x;
     size_t row = blockIdx.x;
-    if (INV && PRO == 4) {
+    if (INV && (PRO == 4 || PRO == 6)) {
         size_t pair; unsigned p;
         if (!xcd_group(blockIdx.x, 3, a.pairs, pair, p)) return;
         row = ((pair / a.mod_count) * 3 + p) * a.mod_count + pair % a.mod_count;
@@ -340,8 +381,12 @@ __device__ __forceinline__ void ntt_rows_split_body(const NttArgs &a)
     const ulonglong2 *W = a.w + (size_t)mi * n;
     u64 *dst = a.dst + row * (size_t)n;
     // ---- the value the transform reads at index s (the load prologues of ntt_rows_body)
-    const u64 *pa = nullptr, *pb = nullptr, *src = nullptr; int prod = 0, sh = 0;
-    if (INV && PRO == 4) {
+    const u64 *pa = nullptr, *pb = nullptr, *pc = nullptr, *pd = nullptr, *src = nullptr; int prod = 0, sh = 0;
+    if (INV && PRO == 6) {
+        const size_t ct = row / (3 * (size_t)a.mod_count); prod = (int)((row / a.mod_count) % 3);
+        const size_t pn = (size_t)a.mod_count * n, o = (ct * 2 * a.mod_count + mloc) * (size_t)n;
+        pa = a.src + o + (prod == 2 ? pn : 0); pb = a.fma_k + o + (prod == 0 ? 0 : pn); pc = a.src + o + pn; pd = a.fma_k + o;
+    } else if (INV && PRO == 4) {
         const size_t ct = row / (3 * (size_t)a.mod_count); prod = (int)((row / a.mod_count) % 3);
         pa = a.src + ((ct * 2 + (prod == 2 ? 1 : 0)) * a.mod_count + mloc) * (size_t)n;
         pb = a.src + ((ct * 2 + (prod == 0 ? 0 : 1)) * a.mod_count + mloc) * (size_t)n;
@@ -366,6 +411,12 @@ __device__ __forceinline__ void ntt_rows_split_body(const NttArgs &a)
             const ulonglong2 av = ld2(pa + s), bv = ld2(pb + s);
             ulonglong2 v{mulmod(av.x, bv.x, m), mulmod(av.y, bv.y, m)};
             if (prod == 1) { v.x = addmod(v.x, v.x, q); v.y = addmod(v.y, v.y, q); }
+            return v;
+        }
+        if (INV && PRO == 6) {
+            const ulonglong2 av = ld2(pa + s), bv = ld2(pb + s);
+            ulonglong2 v{mulmod(av.x, bv.x, m), mulmod(av.y, bv.y, m)};
+            if (prod == 1) { const ulonglong2 cv = ld2(pc + s), dv = ld2(pd + s); v.x = addmod(v.x, mulmod(cv.x, dv.x, m), q); v.y = addmod(v.y, mulmod(cv.y, dv.y, m), q); }
             return v;
         }
         const ulonglong2 v = ld2(src + s);
@@ -557,8 +608,9 @@ static int ntt_launch(crc_ctx *c, bool inv, NttArgs &a, size_t rows, hipStream_t
     bool lazy = true;
     for (int i = a.mod_base; i < a.mod_base + a.mod_count; i++) if (c->tabs[i].m.bits > 57 || c->tabs[i].m.bits < 45) lazy = false;
     const int cus = c->cus;
-    if ((a.prologue == 3 && inv) || ((a.prologue == 4 || a.prologue == 5) && !inv)) return CRC_ERR_INVALID_ARGUMENT;
-    if (a.prologue == 4) rows = xcd_grid(a.pairs, 3);                  // (the three products of a pair on one XCD: ntt_rows_body)
+    if ((a.prologue == 3 && inv) || ((a.prologue == 4 || a.prologue == 5 || a.prologue == 6) && !inv)) return CRC_ERR_INVALID_ARGUMENT;
+    const bool two_src = a.prologue == 6;                               // (fma_k is the second ciphertext there, not an epilogue)
+    if (a.prologue == 4 || two_src) rows = xcd_grid(a.pairs, 3);                  // (the three products of a pair on one XCD: ntt_rows_body)
     // wave-local passes (ntt_rows_wave_kernel): CRC_NTT_WAVE bit 0 n = 8192, bit 1 n = 4096, bit 2 n = 16384 (plain transforms), bit 3 n = 16384 with the
     // Square prologues (slower than the split kernel with the halving butterflies, 11.9 against 11.7 us per squared ciphertext, faster with the ones that do
     // not halve: 11.27 against 11.6 -- profiles/r05_ntt_u64_wave_local_ab.txt, r05_ntt_inverse_unscaled_ab.txt), bit 4: keep the halving butterflies; -1: bits
@@ -567,7 +619,7 @@ static int ntt_launch(crc_ctx *c, bool inv, NttArgs &a, size_t rows, hipStream_t
         // (bit 5, round 6: n = 2048 -- one cross stage, two waves per workgroup)
         const int sel = c->tune.ntt_wave < 0 ? 47 : c->tune.ntt_wave;
         const int bit = c->n == 8192 ? 0 : c->n == 4096 ? 1 : c->n == 16384 ? (a.prologue ? 3 : 2) : c->n == 2048 ? 5 : -1;
-        if (bit >= 0 && ((sel >> bit) & 1) && lazy && !a.addend && (a.prologue == 0 || a.prologue == 4 || a.prologue == 5)) {
+        if (bit >= 0 && ((sel >> bit) & 1) && lazy && !a.addend && (a.prologue == 0 || a.prologue == 4 || a.prologue == 5 || two_src)) {
             lds = (size_t)c->n * 8;
             // inverse transforms over moduli below 2^55 take the butterflies that do not halve (inv_stages_unscaled; CRC_NTT_WAVE bit 4 switches them off): the
             // table of plain inverse powers, and n^-1 in the constant of the closing multiplication
@@ -583,13 +635,13 @@ static int ntt_launch(crc_ctx *c, bool inv, NttArgs &a, size_t rows, hipStream_t
                 if (a.opt_mul) a.opt_mul = 2;
             }
             const int cs = c->logn - 10;
-#define WAVEK(CSV, U) (a.prologue == 4 ? ntt_rows_wave_kernel<true, 4, CSV, U> : a.prologue == 5 ? ntt_rows_wave_kernel<true, 5, CSV, U> \
+#define WAVEK(CSV, U) (two_src ? ntt_rows_wave_kernel<true, 6, CSV, U> : a.prologue == 4 ? ntt_rows_wave_kernel<true, 4, CSV, U> : a.prologue == 5 ? ntt_rows_wave_kernel<true, 5, CSV, U> \
                        : inv ? ntt_rows_wave_kernel<true, 0, CSV, U> : ntt_rows_wave_kernel<false, 0, CSV, false>)
 #define WAVECS(U) (cs == 1 ? WAVEK(1, U) : cs == 2 ? WAVEK(2, U) : cs == 3 ? WAVEK(3, U) : WAVEK(4, U))
 #define WAVEF(FV) (cs == 1 ? ntt_rows_wave_kernel<false, 0, 1, false, FV> : cs == 2 ? ntt_rows_wave_kernel<false, 0, 2, false, FV> \
                    : cs == 3 ? ntt_rows_wave_kernel<false, 0, 3, false, FV> : ntt_rows_wave_kernel<false, 0, 4, false, FV>)
             auto kw = uns ? WAVECS(true) : WAVECS(false);
-            if (a.fma_u || a.fma_k) {
+            if (!two_src && (a.fma_u || a.fma_k)) {
                 if (inv || a.prologue || a.pack_out) return CRC_ERR_INVALID_ARGUMENT;
                 if (a.fma_neg && (a.fma_u || a.src != a.dst || a.dst_ct_rows != a.mod_count || a.src_ct_rows != 2 * a.mod_count)) return CRC_ERR_INVALID_ARGUMENT;
                 kw = a.fma_neg ? WAVEF(3) : a.fma_u ? WAVEF(1) : WAVEF(2);
@@ -604,10 +656,11 @@ static int ntt_launch(crc_ctx *c, bool inv, NttArgs &a, size_t rows, hipStream_t
         }
     }
     // n = 16384: the row as two halves through a 64-KiB image -- two workgroups per CU (ntt_rows_split_body)
-    if (a.fma_u || a.fma_k) return CRC_ERR_UNSUPPORTED;   // (only the wave-local kernel above has those epilogues; the caller runs the product as a pass of its own)
+    if (!two_src && (a.fma_u || a.fma_k)) return CRC_ERR_UNSUPPORTED;   // (only the wave-local kernel above has those epilogues; the caller runs the product as a pass of its own)
     if (c->n == 16384 && nt == 1024 && c->tune.ntt_split != 0) {
         lds /= 2;
-        auto ks = a.prologue == 4 ? (lazy ? ntt_rows_split_kernel<true, true, 4> : ntt_rows_split_kernel<true, false, 4>)
+        auto ks = two_src ? (lazy ? ntt_rows_split_kernel<true, true, 6> : ntt_rows_split_kernel<true, false, 6>)
+                : a.prologue == 4 ? (lazy ? ntt_rows_split_kernel<true, true, 4> : ntt_rows_split_kernel<true, false, 4>)
                 : a.prologue == 5 ? (lazy ? ntt_rows_split_kernel<true, true, 5> : ntt_rows_split_kernel<true, false, 5>)
                 : a.prologue == 3 ? (lazy ? ntt_rows_split_kernel<false, true, 3> : ntt_rows_split_kernel<false, false, 3>)
                 : inv ? (lazy ? ntt_rows_split_kernel<true, true, 0> : ntt_rows_split_kernel<true, false, 0>) : (lazy ? ntt_rows_split_kernel<false, true,
@@ -627,7 +680,8 @@ static int ntt_launch(crc_ctx *c, bool inv, NttArgs &a, size_t rows, hipStream_t
     }
     if ((a.prologue == 3 && inv) || (a.prologue == 4 && !inv)) return CRC_ERR_INVALID_ARGUMENT;
     const bool strict61 = !c->tune.ntt_inv61_loose;
-    auto kern = a.prologue == 4 ? (lazy ? ntt_rows_kernel<true, true, 4> : strict61 ? ntt_rows_inv61_kernel<4> : ntt_rows_kernel<true, false, 4>)
+    auto kern = two_src ? (lazy ? ntt_rows_kernel<true, true, 6> : strict61 ? ntt_rows_inv61_kernel<6> : ntt_rows_kernel<true, false, 6>)
+              : a.prologue == 4 ? (lazy ? ntt_rows_kernel<true, true, 4> : strict61 ? ntt_rows_inv61_kernel<4> : ntt_rows_kernel<true, false, 4>)
               : a.prologue == 5 ? (lazy ? ntt_rows_kernel<true, true, 5> : ntt_rows_kernel<true, false, 5>)
               : a.prologue == 3 ? (lazy ? ntt_rows_kernel<false, true, 3> : ntt_rows_kernel<false, false, 3>)
               : inv ? (lazy ? ntt_rows_kernel<true, true, 0> : strict61 ? ntt_rows_inv61_kernel<0> : ntt_rows_kernel<true, false, 0>) : (lazy ?
@@ -742,6 +796,18 @@ int k_square_intt(crc_ctx *c, const u64 *src, u64 *dst, size_t count, bool bsk, 
 {
     NttArgs a{};
     a.src = src; a.dst = dst; a.mod_base = bsk ? c->k : 0; a.mod_count = bsk ? c->kb : c->k; a.prologue = 4;
+    a.rows_per_ct = 3 * a.mod_count; a.add_group = 1; a.pairs = count * a.mod_count;
+    if (opt_mul) { a.opt_mul = 1; for (int i = 0; i < a.mod_count; i++) a.post_mul[i] = opt_mul[i]; }
+    const int rc = ntt_launch(c, true, a, count * 3 * a.mod_count, st);
+    if (applied) *applied = a.opt_mul == 2;
+    return rc;
+}
+
+// the same for the tensor product (ac, ad + bc, bd) of two size-2 NTT-form ciphertext arrays x = (a, b), y = (c, d) (NttArgs prologue 6)
+int k_multiply_intt(crc_ctx *c, const u64 *x, const u64 *y, u64 *dst, size_t count, bool bsk, hipStream_t st, const u64 *opt_mul, bool *applied)
+{
+    NttArgs a{};
+    a.src = x; a.fma_k = y; a.dst = dst; a.mod_base = bsk ? c->k : 0; a.mod_count = bsk ? c->kb : c->k; a.prologue = 6;
     a.rows_per_ct = 3 * a.mod_count; a.add_group = 1; a.pairs = count * a.mod_count;
     if (opt_mul) { a.opt_mul = 1; for (int i = 0; i < a.mod_count; i++) a.post_mul[i] = opt_mul[i]; }
     const int rc = ntt_launch(c, true, a, count * 3 * a.mod_count, st);

@@ -206,6 +206,12 @@ size_t k_square_work_words(const crc_ctx *c, size_t cnt)
     // QN[2k] BS[2kb] DQ[3k] DB[3kb]   (kb: whichever auxiliary base has more rows -- SEAL's 61-bit one or the engine's fp64 primes, kernels_square64.hip)
     return cnt * n * (2 * k + 2 * kb + 3 * k + 3 * kb);
 }
+size_t k_multiply_work_words(const crc_ctx *c, size_t cnt)
+{
+    const size_t n = c->n, k = c->k, kb = k_square64_supported(c) && (size_t)c->sq64.kf > (size_t)c->kb ? c->sq64.kf : c->kb;
+    // QN[2][2k] BS[2][2kb] DQ[3k] DB[3kb]: both inputs are lifted and transformed, the products are the square's three
+    return cnt * n * (4 * k + 4 * kb + 3 * k + 3 * kb);
+}
 size_t k_relin_work_words(const crc_ctx *c, size_t cnt, int dbc)
 {
     const size_t n = c->n, k = c->k;
@@ -243,6 +249,45 @@ int k_square(crc_ctx *c, const u64 *x, size_t cnt, u64 *y3, u64 *work, hipStream
     // a^2, 2ab, b^2 are formed while the inverse transforms load their rows (no product tensors in memory)
     if ((rc = k_square_intt(c, xn, DQ, cnt, false, st))) return rc;
     if ((rc = k_square_intt(c, BS, DB, cnt, true, st))) return rc;
+    {
+        const dim3 grid((unsigned)(cnt * 3 * sblocks)), blk(threads);
+        bool launched = false;
+#define FLOOR(KV, KAV) if (c->k == KV && c->ka == KAV) { hipLaunchKernelGGL((sq_floor_kernel<KV, KAV>), grid, blk, 0, st, DQ, DB, y3, c->d_mods, c->d_behz, c->n, premul_c2 ? 1 : 0); launched = true; }
+        CRC_FOR_ALL_K_KA(FLOOR)
+#undef FLOOR
+        if (!launched) return CRC_ERR_UNSUPPORTED;
+        HIPCHK(hipGetLastError());
+    }
+    return CRC_OK;
+}
+
+// Evaluator::multiply (evaluator.cpp:356-700) for size-2 inputs: k_square's chain with both inputs lifted and transformed and the tensor product
+// (ac, ad + bc, bd) formed where the square forms (a^2, 2ab, b^2) -- NttArgs prologue 6 over q and over Bsk
+int k_multiply(crc_ctx *c, const u64 *x, const u64 *y, size_t cnt, u64 *y3, u64 *work, hipStream_t st, bool in_ntt, bool premul_c2)
+{
+    if (cnt == 0) return CRC_OK;
+    if (c->tune.sq_path != 1 && k_square64_supported(c)) return k_multiply64(c, x, y, cnt, y3, work, st, in_ntt, premul_c2);
+    const size_t n = c->n, k = c->k, kb = c->kb;
+    u64 *QN = work, *BS = QN + cnt * 4 * k * n, *DQ = BS + cnt * 4 * kb * n, *DB = DQ + cnt * 3 * k * n;
+    const int threads = c->n < 256 ? c->n : 256, sblocks = c->n / threads;
+    int rc;
+    const u64 *in[2] = {x, y}, *nt[2] = {nullptr, nullptr};
+    for (int h = 0; h < 2; h++) {
+        u64 *qn = QN + (size_t)h * cnt * 2 * k * n, *bs = BS + (size_t)h * cnt * 2 * kb * n;
+        const u64 *xc = in[h]; nt[h] = qn;
+        if (in_ntt) { if ((rc = k_ntt_ct(c, true, in[h], qn, cnt, 2, false, st, nullptr, 0, 0, 0))) return rc; xc = qn; nt[h] = in[h]; }
+        const dim3 grid((unsigned)(cnt * 2 * sblocks)), blk(threads);
+        bool launched = false;
+#define LIFT(KV, KAV) if (c->k == KV && c->ka == KAV) { hipLaunchKernelGGL((sq_lift_kernel<KV, KAV + 1>), grid, blk, 0, st, xc, bs, c->d_mods, c->d_behz, c->n); launched = true; }
+        CRC_FOR_ALL_K_KA(LIFT)
+#undef LIFT
+        if (!launched) return CRC_ERR_UNSUPPORTED;
+        HIPCHK(hipGetLastError());
+        if (!in_ntt && (rc = k_ntt_ct(c, false, in[h], qn, cnt, 2, false, st, nullptr, 0, 0, 0))) return rc;
+    }
+    if ((rc = k_ntt_ct(c, false, BS, BS, 2 * cnt, 2, true, st, nullptr, 0, 0, 0))) return rc;
+    if ((rc = k_multiply_intt(c, nt[0], nt[1], DQ, cnt, false, st))) return rc;
+    if ((rc = k_multiply_intt(c, BS, BS + cnt * 2 * kb * n, DB, cnt, true, st))) return rc;
     {
         const dim3 grid((unsigned)(cnt * 3 * sblocks)), blk(threads);
         bool launched = false;

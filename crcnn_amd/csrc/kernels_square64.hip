@@ -271,6 +271,118 @@ __global__ void __launch_bounds__(CS == 2 ? 256 : CS == 3 ? 512 : 1024, 4) sq64_
     finish(2);
 }
 
+// ---- the product of two DIFFERENT ciphertexts x = (a, b), y = (c, d) (Evaluator::multiply, evaluator.cpp:398-700): inx / iny [count][2][kf][n] transformed rows
+// -> out [count][3][kf][n]: n (ac, ad + bc, bd) in coefficient form, reduced.  The counterparts of sq64_inv_kernel / sq64_inv_wave_kernel: one workgroup per
+// (pair, prime).  ONE row waits in registers, as in the square -- a from the first product to the middle term, then d to the last product -- and b and c are
+// read a second time: six row reads for four rows.  (Holding two rows, a and c then b and d, reads every row once but does not fit 128 registers: 24 to 1028
+// bytes of scratch per thread over the six instantiations)  The middle term is the sum of two reduced products, below 1.75 p like the square's
+// doubled one
+template <int RB, int NPT>
+__global__ void __launch_bounds__(RB == 5 ? 512 : 1024, 4) mul64_inv_kernel(const double *inx, const double *iny, double *out, const double *Wi,
+    const Sq64Params *sp, int n, int logn, int kf)
+{
+    extern __shared__ double smd[];
+    const size_t ct = blockIdx.x / kf; const int j = blockIdx.x % kf;
+    const F64Mod md = sp->m[j];
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const size_t ra = ((ct * 2 + 0) * kf + j) * (size_t)n, rb = ((ct * 2 + 1) * kf + j) * (size_t)n;
+    const double *a = inx + ra, *b = inx + rb, *cc = iny + ra, *d = iny + rb;
+    const double *W = Wi + (size_t)j * n;
+    auto put = [&](int s, double x, double y) { const d2 v = f64_stage_in<true, RB>(d2{x, y}, W, n, logn, s, md); sm_store_pair<RB>(smd, s, v.x, v.y); };
+    double r[NPT];
+    auto transform_store = [&](int o) {
+        __syncthreads();
+        ntt_row_passes_f64<true, RB>(smd, W, n, logn, md, false);
+        double *dst = out + ((ct * 3 + o) * kf + j) * (size_t)n;
+        f64_drain<true, RB, NPT / 2>(smd, W, n, logn, md, [&](int s, d2 v) { *reinterpret_cast<d2 *>(dst + s) = d2{f64_reduce(v.x, md), f64_reduce(v.y,
+            md)}; });
+        __syncthreads();
+    };
+    // a c; a stays in r
+#pragma unroll
+    for (int u = 0; u < NPT / 2; u++) {
+        const int s = 2 * (tid + u * nt);
+        if (s < n) {
+            const d2 va = *reinterpret_cast<const d2 *>(a + s), vc = *reinterpret_cast<const d2 *>(cc + s);
+            r[2 * u] = va.x; r[2 * u + 1] = va.y;
+            put(s, f64_mulmod(va.x, vc.x, md), f64_mulmod(va.y, vc.y, md));
+        }
+    }
+    transform_store(0);
+    // a d + b c; d replaces a in r
+#pragma unroll
+    for (int u = 0; u < NPT / 2; u++) {
+        const int s = 2 * (tid + u * nt);
+        if (s < n) {
+            const d2 vb = *reinterpret_cast<const d2 *>(b + s), vc = *reinterpret_cast<const d2 *>(cc + s), vd = *reinterpret_cast<const d2 *>(d + s);
+            put(s, f64_mulmod(r[2 * u], vd.x, md) + f64_mulmod(vb.x, vc.x, md), f64_mulmod(r[2 * u + 1], vd.y, md) + f64_mulmod(vb.y, vc.y, md));
+            r[2 * u] = vd.x; r[2 * u + 1] = vd.y;
+        }
+    }
+    transform_store(1);
+    // b d
+#pragma unroll
+    for (int u = 0; u < NPT / 2; u++) {
+        const int s = 2 * (tid + u * nt);
+        if (s < n) { const d2 vb = *reinterpret_cast<const d2 *>(b + s); put(s, f64_mulmod(vb.x, r[2 * u], md), f64_mulmod(vb.y, r[2 * u + 1], md)); }
+    }
+    transform_store(2);
+}
+// a workgroup-uniform pointer as a fresh value the compiler keeps in scalar registers: the row kernels below read the same rows in several fills, and addresses
+// carried from one fill to the next (64-bit, per thread and pair) were what took them past 128 registers
+__device__ __forceinline__ const double *f64_row_ptr(const double *p)
+{
+    const u64 v = (u64)p;
+    return reinterpret_cast<const double *>(((u64)(u32)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)v));
+}
+// the one-barrier form (n = 4096 / 8192 / 16384), after sq64_inv_wave_kernel: a waits in r from the first product to the middle term, d from there to the last
+template <int CS>
+__global__ void __launch_bounds__(CS == 2 ? 256 : CS == 3 ? 512 : 1024, 4) mul64_inv_wave_kernel(const double *inx, const double *iny, double *out,
+    const double *Wi, const Sq64Params *sp, int n, int kf)
+{
+    extern __shared__ double smd[];
+    const size_t ct = blockIdx.x / kf; const int j = blockIdx.x % kf;
+    const F64Mod md = sp->m[j];
+    const size_t ra = ((ct * 2 + 0) * kf + j) * (size_t)n, rb = ((ct * 2 + 1) * kf + j) * (size_t)n;
+    const double *W = Wi + (size_t)j * n;
+    double r[16], res[16];
+    auto finish = [&](int o) {
+        f64_wave_inverse<CS, 3>(smd, W, n, md, [&](int q, double x) { res[q] = f64_reduce(x, md); });
+        f64_cross_store<CS>(out + ((ct * 3 + o) * kf + j) * (size_t)n, res);
+        __syncthreads();                                      // the image is filled again
+    };
+    // a c; a stays in r
+    {
+        const double *a = f64_row_ptr(inx + ra), *c = f64_row_ptr(iny + ra);
+        f64_local_fill<3>(smd, f64_row_ptr(W), n, md, [&](int u, int s) {
+            const d2 va = *reinterpret_cast<const d2 *>(a + s), vc = *reinterpret_cast<const d2 *>(c + s);
+            r[2 * u] = va.x; r[2 * u + 1] = va.y;
+            return d2{f64_mulmod(va.x, vc.x, md), f64_mulmod(va.y, vc.y, md)};
+        });
+    }
+    finish(0);
+    // a d + b c; d replaces a in r
+    {
+        const double *b = f64_row_ptr(inx + rb), *c = f64_row_ptr(iny + ra), *d = f64_row_ptr(iny + rb);
+        f64_local_fill<3>(smd, f64_row_ptr(W), n, md, [&](int u, int s) {
+            const d2 vb = *reinterpret_cast<const d2 *>(b + s), vc = *reinterpret_cast<const d2 *>(c + s), vd = *reinterpret_cast<const d2 *>(d + s);
+            const d2 pr{f64_mulmod(r[2 * u], vd.x, md) + f64_mulmod(vb.x, vc.x, md), f64_mulmod(r[2 * u + 1], vd.y, md) + f64_mulmod(vb.y, vc.y, md)};
+            r[2 * u] = vd.x; r[2 * u + 1] = vd.y;
+            return pr;
+        });
+    }
+    finish(1);
+    // b d
+    {
+        const double *b = f64_row_ptr(inx + rb);
+        f64_local_fill<3>(smd, f64_row_ptr(W), n, md, [&](int u, int s) {
+            const d2 vb = *reinterpret_cast<const d2 *>(b + s);
+            return d2{f64_mulmod(vb.x, r[2 * u], md), f64_mulmod(vb.y, r[2 * u + 1], md)};
+        });
+    }
+    finish(2);
+}
+
 // dq: [count][3][K][n] u64 (coefficient form over q, scaled), db: [count][3][KF][n] doubles (n times the coefficient, reduced) -> y3: [count][3][K][n]. (One
 // coefficient per thread: two, as in the lift kernel, cost more in occupancy than the 16-byte accesses returned -- 0.77 against 0.64 us per ciphertext at
 // (8192, 3))
@@ -377,19 +489,16 @@ bool k_square64_supported(const crc_ctx *c)
 static int sq64_hold_threads(const crc_ctx *c, int RB) { int nt = c->n >> (RB == 5 ? 5 : 4); if (nt < 64) nt = 64;
     if (nt > (RB == 5 ? 512 : 1024)) nt = RB == 5 ? 512 : 1024; return nt; }
 
-// work: QN [2k] | LB [2 kf] | DQ [3k] | DB [3 kf]   (k_square_work_words sizes the rows by max(kb, kf))
-int k_square64(crc_ctx *c, const u64 *x, size_t cnt, u64 *y3, u64 *work, hipStream_t st, bool in_ntt, bool premul_c2)
+// the lift and the forward transforms of cnt size-2 ciphertexts x: LB [cnt][2][kf][n] transformed rows under the fp64 primes; *xn_out: x in NTT form over q (x
+// itself for an NTT-resident caller, QN [cnt][2][k][n] otherwise)
+static int sq64_lift_forward(crc_ctx *c, const u64 *x, size_t cnt, u64 *QN, double *LB, hipStream_t st, bool in_ntt, const u64 **xn_out)
 {
-    if (cnt == 0) return CRC_OK;
-    if (!k_square64_supported(c)) return CRC_ERR_UNSUPPORTED;
-    const size_t n = c->n, k = c->k, kf = c->sq64.kf;
-    u64 *QN = work, *LBw = QN + cnt * 2 * k * n, *DQ = LBw + cnt * 2 * kf * n, *DBw = DQ + cnt * 3 * k * n;
-    double *LB = reinterpret_cast<double *>(LBw), *DB = reinterpret_cast<double *>(DBw);
+    const size_t n = c->n, kf = c->sq64.kf;
     const int lthreads = c->n < 512 ? c->n / 2 : 256, lblocks = c->n / (2 * lthreads);         // (the lift kernel: two coefficients per thread)
     int rc;
     const size_t lds = n * 8;
     const int RB = sq64_radix(c), nt = sq64_threads(c, RB);
-    const double *Wf = c->d_f64_rp, *Wi = c->d_f64_irp;
+    const double *Wf = c->d_f64_rp;
     const u64 *xn = QN;
     // (fused up to k = 4: every one of the kf workgroups of a polynomial reads its k source rows, and at k = 8, kf = 11 that costs more than the lift kernel's
     // round trip -- 35.7 against 34.3 us per ciphertext at (16384, 8), 14.6 against 14.75 at (16384, 4), 5.55 against 5.69 at (8192, 3):
@@ -435,6 +544,37 @@ int k_square64(crc_ctx *c, const u64 *x, size_t cnt, u64 *y3, u64 *work, hipStre
         hipLaunchKernelGGL(kern, dim3((unsigned)(cnt * 2 * kf)), dim3(nt), lds, st, LB, Wf, c->d_sq64, c->n, c->logn, (int)kf);
         HIPCHK(hipGetLastError());
     }
+    *xn_out = xn;
+    return CRC_OK;
+}
+// fast_floor and fastbconv_sk of cnt size-3 products: DQ (over q), DB (over the fp64 primes) -> y3
+static int sq64_floor(crc_ctx *c, const u64 *DQ, const double *DB, u64 *y3, size_t cnt, hipStream_t st, bool premul_c2, bool dq_scaled)
+{
+    const int threads = c->n < 256 ? c->n : 256;
+    const dim3 grid((unsigned)(cnt * 3 * (c->n / threads))), blk(threads);
+    bool launched = false;
+#define FLOOR(KV, KFV) if (c->k == KV && c->sq64.kf == KFV) { hipLaunchKernelGGL((sq64_floor_kernel<KV, KFV>), grid, blk, 0, st, DQ, DB, y3, c->d_mods, c->d_behz, c->d_sq64, c->n, premul_c2 ? 1 : 0, dq_scaled ? 1 : 0); launched = true; }
+    CRC_FOR_ALL_K_KF(FLOOR)
+#undef FLOOR
+    if (!launched) return CRC_ERR_UNSUPPORTED;
+    HIPCHK(hipGetLastError());
+    return CRC_OK;
+}
+
+// work: QN [2k] | LB [2 kf] | DQ [3k] | DB [3 kf]   (k_square_work_words sizes the rows by max(kb, kf))
+int k_square64(crc_ctx *c, const u64 *x, size_t cnt, u64 *y3, u64 *work, hipStream_t st, bool in_ntt, bool premul_c2)
+{
+    if (cnt == 0) return CRC_OK;
+    if (!k_square64_supported(c)) return CRC_ERR_UNSUPPORTED;
+    const size_t n = c->n, k = c->k, kf = c->sq64.kf;
+    u64 *QN = work, *LBw = QN + cnt * 2 * k * n, *DQ = LBw + cnt * 2 * kf * n, *DBw = DQ + cnt * 3 * k * n;
+    double *LB = reinterpret_cast<double *>(LBw), *DB = reinterpret_cast<double *>(DBw);
+    int rc;
+    const size_t lds = n * 8;
+    const int RB = sq64_radix(c);
+    const double *Wi = c->d_f64_irp;
+    const u64 *xn = nullptr;
+    if ((rc = sq64_lift_forward(c, x, cnt, QN, LB, st, in_ntt, &xn))) return rc;
     // a^2, 2ab, b^2 over q are formed while the inverse transforms load their rows (kernels.hip); over the fp64 primes in sq64_inv_kernel
     // (x t (q/q_i)^-1, the first thing the floor kernel does to these rows, goes into the transform's closing multiplication where it has one)
     bool dq_scaled = false;
@@ -450,15 +590,38 @@ int k_square64(crc_ctx *c, const u64 *x, size_t cnt, u64 *y3, u64 *work, hipStre
         hipLaunchKernelGGL(kern, dim3((unsigned)(cnt * kf)), dim3(sq64_hold_threads(c, RB)), lds, st, LB, DB, Wi, c->d_sq64, c->n, c->logn, (int)kf);
         HIPCHK(hipGetLastError());
     }
-    {
-        const int threads = c->n < 256 ? c->n : 256;
-        const dim3 grid((unsigned)(cnt * 3 * (c->n / threads))), blk(threads);
-        bool launched = false;
-#define FLOOR(KV, KFV) if (c->k == KV && c->sq64.kf == KFV) { hipLaunchKernelGGL((sq64_floor_kernel<KV, KFV>), grid, blk, 0, st, DQ, DB, y3, c->d_mods, c->d_behz, c->d_sq64, c->n, premul_c2 ? 1 : 0, dq_scaled ? 1 : 0); launched = true; }
-        CRC_FOR_ALL_K_KF(FLOOR)
-#undef FLOOR
-        if (!launched) return CRC_ERR_UNSUPPORTED;
+    return sq64_floor(c, DQ, DB, y3, cnt, st, premul_c2, dq_scaled);
+}
+
+// the product of two ciphertext arrays: the square's chain with the lift and the forward transforms run for both inputs and the tensor product (ac, ad + bc, bd)
+// in place of (a^2, 2ab, b^2); floor, premultiplication of the third polynomial and result form are the square's.
+// work: QN [2][2k] | LB [2][2 kf] | DQ [3k] | DB [3 kf]   (k_multiply_work_words)
+int k_multiply64(crc_ctx *c, const u64 *x, const u64 *y, size_t cnt, u64 *y3, u64 *work, hipStream_t st, bool in_ntt, bool premul_c2)
+{
+    if (cnt == 0) return CRC_OK;
+    if (!k_square64_supported(c)) return CRC_ERR_UNSUPPORTED;
+    const size_t n = c->n, k = c->k, kf = c->sq64.kf;
+    u64 *QN = work, *LBw = QN + cnt * 4 * k * n, *DQ = LBw + cnt * 4 * kf * n, *DBw = DQ + cnt * 3 * k * n;
+    double *LBx = reinterpret_cast<double *>(LBw), *LBy = LBx + cnt * 2 * kf * n, *DB = reinterpret_cast<double *>(DBw);
+    int rc;
+    const size_t lds = n * 8;
+    const int RB = sq64_radix(c);
+    const double *Wi = c->d_f64_irp;
+    const u64 *xn = nullptr, *yn = nullptr;
+    if ((rc = sq64_lift_forward(c, x, cnt, QN, LBx, st, in_ntt, &xn))) return rc;
+    if ((rc = sq64_lift_forward(c, y, cnt, QN + cnt * 2 * k * n, LBy, st, in_ntt, &yn))) return rc;
+    bool dq_scaled = false;
+    if ((rc = k_multiply_intt(c, xn, yn, DQ, cnt, false, st, c->behz.t_inv_qhat, &dq_scaled))) return rc;
+    if (sq64_wave_path(c, RB, 0)) {
+        auto kern = c->logn == 12 ? mul64_inv_wave_kernel<2> : c->logn == 13 ? mul64_inv_wave_kernel<3> : mul64_inv_wave_kernel<4>;
+        if ((rc = crc_ctx_ensure_lds(c, (const void *)kern, lds))) return rc;
+        hipLaunchKernelGGL(kern, dim3((unsigned)(cnt * kf)), dim3(c->n / 16), lds, st, LBx, LBy, DB, Wi, c->d_sq64, c->n, (int)kf);
+        HIPCHK(hipGetLastError());
+    } else {
+        auto kern = RB == 3 ? mul64_inv_kernel<3, 16> : RB == 4 ? mul64_inv_kernel<4, 16> : mul64_inv_kernel<5, 32>;
+        if ((rc = crc_ctx_ensure_lds(c, (const void *)kern, lds))) return rc;
+        hipLaunchKernelGGL(kern, dim3((unsigned)(cnt * kf)), dim3(sq64_hold_threads(c, RB)), lds, st, LBx, LBy, DB, Wi, c->d_sq64, c->n, c->logn, (int)kf);
         HIPCHK(hipGetLastError());
     }
-    return CRC_OK;
+    return sq64_floor(c, DQ, DB, y3, cnt, st, premul_c2, dq_scaled);
 }

@@ -1230,6 +1230,51 @@ void PolyLayer::printLayerStructure()
     cerr << "Poly " << name << " : " << c2 << " x^2 + " << c1 << " x + " << c0 << " run with " << th_count << " threads" << endl;
 }
 
+// ---- ciphertext x ciphertext multiply, degree-3 activation ------------------------------------------------------------------
+ciphertext3D multiplyRelin(const ciphertext3D &a, const ciphertext3D &b, int out_form)
+{
+    if (!a.buf || !b.buf) throw invalid_argument("multiplyRelin: empty input");
+    if (a.B != b.B || a.zd != b.zd || a.xd != b.xd || a.yd != b.yd) throw invalid_argument("multiplyRelin: the tensors differ in shape");
+    if (a.form != b.form || (a.form != CRC_NTT && a.form != CRC_COEFF)) throw invalid_argument("multiplyRelin: both tensors must be in CRC_NTT or both in CRC_COEFF form");
+    if (out_form != CRC_NTT && out_form != CRC_COEFF) throw invalid_argument("multiplyRelin: out_form must be CRC_NTT or CRC_COEFF");
+    if (!ev_keys16) throw invalid_argument("not enough evaluation keys");
+    ciphertext3D out(a.B, a.zd, a.xd, a.yd, out_form);
+    ensure(g_scratch, crc_multiply_relin_work_bytes(ctx(), a.count(), 16));
+    chk(crc_multiply_relin_forms(ctx(), a.data(), b.data(), a.form, a.count(), (const uint64_t *)ev_keys16->ptr, 16, out.data(), out_form, g_scratch->ptr,
+                                 stream()), "crc_multiply_relin_forms");
+    return out;
+}
+Poly3Layer::Poly3Layer(string name, float c3, float c2, float c1, float c0, int th_count) : Layer(name), c3(c3), c2(c2), c1(c1), c0(c0), th_count(th_count)
+{
+    if (!isfinite(c3) || !isfinite(c2) || !isfinite(c1) || !isfinite(c0)) throw invalid_argument("Poly3Layer: the coefficients must be finite");
+    if (c3 == 0.0f) throw invalid_argument("Poly3Layer: c3 must not be zero (a polynomial without its cubic term is a PolyLayer)");
+}
+size_t Poly3Layer::deviceBytes() const { size_t b = 0; for (auto &r : d_p) if (r) b += r->bytes; return b; }
+ciphertext3D Poly3Layer::forward(ciphertext3D input)
+{
+    if (!input.buf) throw invalid_argument("Poly3Layer: empty input");
+    if (!ev_keys16) throw invalid_argument("not enough evaluation keys");
+    if (out_form != CRC_NTT && out_form != CRC_COEFF) throw invalid_argument("Poly3Layer: out_form must be CRC_NTT or CRC_COEFF");
+    if (!uploaded) {
+        for (auto &r : d_p) r.reset();
+        if (c3 != 1.0f) { const Plaintext p = fraencode((double)c3); d_p[0] = uploadPlain({&p}, 0); }
+        if (c2 != 0.0f) { const Plaintext p = fraencode((double)c2); d_p[1] = uploadPlain({&p}, 0); }
+        if (c1 != 0.0f) { const Plaintext p = fraencode((double)c1); d_p[2] = uploadPlain({&p}, 0); }
+        if (c0 != 0.0f) { const Plaintext p = fraencode((double)c0); d_p[3] = uploadPlain({&p}, 2); }
+        chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+        uploaded = true;
+    }
+    ciphertext3D out(input.B, input.zd, input.xd, input.yd, out_form);
+    ensure(g_scratch, crc_poly3_relin_work_bytes(ctx(), input.count(), 16));
+    chk(crc_poly3_relin_forms(ctx(), input.data(), input.form, input.count(), (const uint64_t *)ev_keys16->ptr, 16, rowPtr(d_p[0]), rowPtr(d_p[1]), rowPtr(d_p[2]),
+                              rowPtr(d_p[3]), out.data(), out_form, g_scratch->ptr, stream()), "crc_poly3_relin_forms");
+    return out;
+}
+void Poly3Layer::printLayerStructure()
+{
+    cerr << "Poly3 " << name << " : " << c3 << " x^3 + " << c2 << " x^2 + " << c1 << " x + " << c0 << " run with " << th_count << " threads" << endl;
+}
+
 // ---- polynomial activation + pooling (Network::fuse) ------------------------------------------------------------------------
 PolyPoolLayer::PolyPoolLayer(string name, int xd, int yd, int zd, int xs, int ys, int xf, int yf, int th_count, float c2, float c1, float c0,
     shared_ptr<DeviceBuffer> d_div)
@@ -1623,7 +1668,8 @@ int Network::fuse()
                                                  pool->d_div);
         eraseLayer(i + 1);
     }
-    // 1c. polynomial activation + pooling, the same way (PolyPoolLayer; a batch norm behind it is left to the fold below)
+    // 1c. polynomial activation + pooling, the same way (PolyPoolLayer; a batch norm behind it is left to the fold below).  A Poly3Layer stays a layer of its
+    // own, like a SquareLayer whose pooling cannot be paired: its two key switches are not linear in one set of digits
     for (size_t i = 0; i + 1 < layers.size(); i++) {
         auto po = dynamic_pointer_cast<PolyLayer>(layers[i]);
         auto pool = dynamic_pointer_cast<PoolingLayer>(layers[i + 1]);
@@ -1763,17 +1809,17 @@ NetworkDescription NetworkDescription::parse(const string &text, const string &h
             continue;
         }
         const bool windowed = kind == "conv" || kind == "pool" || kind == "avgpool";
-        if (!windowed && kind != "bn" && kind != "square" && kind != "fc" && kind != "pad" && kind != "poly") descError(ln, "unknown layer kind '" + kind + "'");
+        if (!windowed && kind != "bn" && kind != "square" && kind != "fc" && kind != "pad" && kind != "poly" && kind != "poly3") descError(ln, "unknown layer kind '" + kind + "'");
         if (tok.size() < 2) descError(ln, kind + ": the layer name is missing");
         LayerSpec L;
         L.kind = kind; L.name = tok[1]; L.line = ln; L.zd = zd; L.xd = xd; L.yd = yd;
         vector<string> rest(tok.begin() + 2, tok.end());
         if (rest.size() >= 2 && rest[rest.size() - 2] == "threads") {
-            if (kind != "conv" && kind != "fc" && kind != "square" && kind != "poly") descError(ln, "unknown token 'threads' for a " + kind + " layer");
+            if (kind != "conv" && kind != "fc" && kind != "square" && kind != "poly" && kind != "poly3") descError(ln, "unknown token 'threads' for a " + kind + " layer");
             L.threads = descInt(ln, rest.back(), "threads");
             rest.resize(rest.size() - 2);
         }
-        if (flat && (windowed || kind == "pad" || kind == "poly"))
+        if (flat && (windowed || kind == "pad" || kind == "poly" || kind == "poly3"))
             descError(ln, "a " + kind + " layer cannot follow a fully connected layer: the tensor is flat (" + to_string(xd) + " values)");
         if (windowed) {
             size_t pos = 0;
@@ -1816,6 +1862,11 @@ NetworkDescription NetworkDescription::parse(const string &text, const string &h
             L.c2 = descFloat(ln, rest[0], "c2"); L.c1 = descFloat(ln, rest[1], "c1"); L.c0 = descFloat(ln, rest[2], "c0");
             if (L.c2 == 0.0f) descError(ln, "poly: c2 must not be zero (without its square term the layer is a batch norm, not an activation)");
             L.zo = zd; L.xo = xd; L.yo = yd;
+        } else if (kind == "poly3") {
+            if (rest.size() != 4) descError(ln, rest.size() > 4 ? "unknown token '" + rest[4] + "'" : string("poly3: takes c3 c2 c1 c0"));
+            L.c3 = descFloat(ln, rest[0], "c3"); L.c2 = descFloat(ln, rest[1], "c2"); L.c1 = descFloat(ln, rest[2], "c1"); L.c0 = descFloat(ln, rest[3], "c0");
+            if (L.c3 == 0.0f) descError(ln, "poly3: c3 must not be zero (without its cubic term the layer is a poly layer)");
+            L.zo = zd; L.xo = xd; L.yo = yd;
         } else {
             if (!rest.empty()) descError(ln, "unknown token '" + rest[0] + "'");
             if (kind == "bn") { check(ln, L.name + ".running_mean", zd); check(ln, L.name + ".running_var", zd); }
@@ -1853,6 +1904,7 @@ string NetworkDescription::str() const
         else if (L.kind == "fc") o << " " << L.out_dim;
         else if (L.kind == "pad") o << " " << L.px << " " << L.py;
         else if (L.kind == "poly") o << " " << descFloatStr(L.c2) << " " << descFloatStr(L.c1) << " " << descFloatStr(L.c0);
+        else if (L.kind == "poly3") o << " " << descFloatStr(L.c3) << " " << descFloatStr(L.c2) << " " << descFloatStr(L.c1) << " " << descFloatStr(L.c0);
         if (L.threads >= 0 && L.threads != 1) o << " threads " << L.threads;          // (1 is what a layer without the token is built with)
         o << "\n";
     }
@@ -1874,6 +1926,8 @@ string Network::describe() const
         else if (auto pd = dynamic_pointer_cast<PaddingLayer>(l)) { L.kind = "pad"; L.px = pd->px; L.py = pd->py; }
         else if (auto sq = dynamic_pointer_cast<SquareLayer>(l)) { L.kind = "square"; L.threads = sq->th_count; }
         else if (auto po = dynamic_pointer_cast<PolyLayer>(l)) { L.kind = "poly"; L.c2 = po->c2; L.c1 = po->c1; L.c0 = po->c0; L.threads = po->th_count; }
+        else if (auto p3 = dynamic_pointer_cast<Poly3Layer>(l)) { L.kind = "poly3"; L.c3 = p3->c3; L.c2 = p3->c2; L.c1 = p3->c1; L.c0 = p3->c0;
+            L.threads = p3->th_count; }
         else if (dynamic_pointer_cast<BatchNormLayer>(l)) L.kind = "bn";
         else throw logic_error("Network::describe: layer " + l->name + " has no description");
         d.layers.push_back(L);
@@ -1940,6 +1994,7 @@ AvgPoolingLayer *CnnBuilder::buildAvgPoolingLayer(string name, int xd, int yd, i
     yd, zd, xs, ys, xf, yf); }
 SquareLayer *CnnBuilder::buildSquareLayer(string name, int th_count) { return new SquareLayer(name, th_count); }
 PolyLayer *CnnBuilder::buildPolyLayer(string name, float c2, float c1, float c0, int th_count) { return new PolyLayer(name, c2, c1, c0, th_count); }
+Poly3Layer *CnnBuilder::buildPoly3Layer(string name, float c3, float c2, float c1, float c0, int th_count) { return new Poly3Layer(name, c3, c2, c1, c0, th_count); }
 BatchNormLayer *CnnBuilder::buildBatchNormLayer(string name, int num_channels, istream *infile)
 {   // cnnBuilder.cpp:89-105
     if (infile != NULL) return new BatchNormLayer(name, num_channels, infile);
@@ -1971,6 +2026,7 @@ Network CnnBuilder::buildNetworkFromDescription(const string &path_or_text, stri
         else if (L.kind == "bn") add(buildBatchNormLayer(L.name, L.zd, in));
         else if (L.kind == "square") add(buildSquareLayer(L.name, th));
         else if (L.kind == "poly") add(buildPolyLayer(L.name, L.c2, L.c1, L.c0, th));
+        else if (L.kind == "poly3") add(buildPoly3Layer(L.name, L.c3, L.c2, L.c1, L.c0, th));
         else if (L.kind == "fc") add(buildFullyConnectedLayer(L.name, L.zd * L.xd * L.yd, L.out_dim, th, in));
         else add(buildPaddingLayer(L.name, L.xd, L.yd, L.zd, L.px, L.py));
     }

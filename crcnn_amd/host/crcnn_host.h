@@ -328,6 +328,30 @@ private:
     std::shared_ptr<DeviceBuffer> d_p[3];                   // NTT-form rows of encode(c2), encode(c1) and Delta encode(c0); empty = 1, 0, 0
 };
 
+// Degree-3 polynomial activation c3 x^3 + c2 x^2 + c1 x + c0: per ciphertext the Evaluator sequence
+//     s = relinearize(square(x), ev_keys16); u = relinearize(multiply(s, x), ev_keys16); r = multiply_plain(u, encode(c3));
+//     r = add(r, multiply_plain(s, encode(c2))); r = add(r, multiply_plain(x, encode(c1))); r = add_plain(r, encode(c0))
+// (a step is left out for c3 == 1, c2 == 0, c1 == 0, c0 == 0), computed by crc_poly3_relin_forms: TWO key switches and a multiplicative depth of 2 -- the
+// parameters must leave noise budget for a second multiplication (CrCNN's published (4096, two moduli, t = 2^29) leave none).  c3 == 0 (a PolyLayer) and
+// non-finite values are std::invalid_argument.  Network::fuse() treats the layer as an unfused SquareLayer: nothing is paired with a pooling behind it
+class Poly3Layer : public Layer {
+public:
+    float c3, c2, c1, c0;
+    int th_count;
+    Poly3Layer(std::string name, float c3, float c2, float c1, float c0, int th_count);
+    ciphertext3D forward(ciphertext3D input) override;
+    void savePlaintextParameters(std::ostream *) override {}
+    void loadPlaintextParameters(std::istream *) override {}
+    void printLayerStructure() override;
+    size_t deviceBytes() const override;
+private:
+    bool uploaded = false;
+    std::shared_ptr<DeviceBuffer> d_p[4];                   // NTT-form rows of encode(c3), encode(c2), encode(c1) and Delta encode(c0); empty = 1, 0, 0, 0
+};
+// relinearize(multiply(a, b), ev_keys16) elementwise on two tensors of equal shape and form (CRC_COEFF or CRC_NTT), the result in out_form
+// (crc_multiply_relin_forms: Evaluator::multiply of SEAL 2.3.1, bit for bit); std::invalid_argument otherwise
+ciphertext3D multiplyRelin(const ciphertext3D &a, const ciphertext3D &b, int out_form = CRC_COEFF);
+
 // Network::fuse(): a PolyLayer with a (sum or average) PoolingLayer behind it, as SquarePoolLayer pairs a SquareLayer:
 //     Sum_w (c2 x_w^2 + c1 x_w + c0) = c2 Sum_w relin(x_w^2) + c1 Sum_w x_w + W c0
 // keeps ONE key switch per pooled ciphertext (crc_poly2_pool_relin_forms); the window count and an average pooling's divisor are folded into the three
@@ -477,7 +501,8 @@ public:
 //   conv NAME stride xs ys filter xf yf filters nf      pool | avgpool NAME stride xs ys window xf yf      bn NAME      square NAME
 //   fc NAME out_dim      pad NAME px py      refresh (sets layer_before_reenc to the next layer; at most one)
 //   poly NAME c2 c1 c0   (c2 x^2 + c1 x + c0: decimal numbers, read as double and rounded to float32; c2 != 0, all finite; written back as %.9g)
-// conv, fc, square and poly lines may end in `threads N` (the th_count the reference's constructors take).  NAME is the HDF5 dataset prefix.
+//   poly3 NAME c3 c2 c1 c0   (c3 x^3 + c2 x^2 + c1 x + c0, two key switches and depth 2; the same number rules, c3 != 0)
+// conv, fc, square, poly and poly3 lines may end in `threads N` (the th_count the reference's constructors take).  NAME is the HDF5 dataset prefix.
 // Every error is a std::invalid_argument whose message starts with "line N:".
 struct LayerSpec {
     std::string kind, name;
@@ -487,6 +512,7 @@ struct LayerSpec {
     int out_dim = 0;                                        // fc (in_dim = zd xd yd, the reference's reshapeInput order)
     int px = 0, py = 0;                                     // pad
     float c2 = 1.0f, c1 = 0.0f, c0 = 0.0f;                  // poly
+    float c3 = 1.0f;                                        // poly3 (with c2 c1 c0)
     int threads = -1;                                       // -1: no `threads` token (the layer is built with th_count 1)
     int zo = 0, xo = 0, yo = 0;                             // output shape
 };
@@ -517,6 +543,7 @@ public:
     AvgPoolingLayer *buildAvgPoolingLayer(std::string name, int xd, int yd, int zd, int xs, int ys, int xf, int yf);
     SquareLayer *buildSquareLayer(std::string name, int th_count);
     PolyLayer *buildPolyLayer(std::string name, float c2, float c1, float c0, int th_count);
+    Poly3Layer *buildPoly3Layer(std::string name, float c3, float c2, float c1, float c0, int th_count);
     PaddingLayer *buildPaddingLayer(std::string name, int xd, int yd, int zd, int px, int py);
     BatchNormLayer *buildBatchNormLayer(std::string name, int num_channels, std::istream *infile);
     // cnnBuilder.cpp:108-179 hard-codes one topology per source edit (Tiny is the committed one); all three are available here, and any other as a description

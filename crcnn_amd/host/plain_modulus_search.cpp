@@ -121,6 +121,7 @@ vector<float> plainModelForward(CnnBuilder &build, const string &model, const ve
         else if (L.kind == "bn") bnF(t, P(L.name + ".running_mean"), P(L.name + ".running_var"));
         else if (L.kind == "square") { for (float &v : t.v) v = v * v; }
         else if (L.kind == "poly") { for (float &v : t.v) v = (L.c2 * v + L.c1) * v + L.c0; }
+        else if (L.kind == "poly3") { for (float &v : t.v) v = ((L.c3 * v + L.c2) * v + L.c1) * v + L.c0; }
         else if (L.kind == "fc") t = fcF(t, P(L.name + ".weight"), P(L.name + ".bias"), L.out_dim);
         else if (L.kind == "pad") t = padF(t, L.px, L.py);
         else throw invalid_argument("plainModelForward: unknown layer kind " + L.kind);

@@ -6,6 +6,8 @@
 //   test_host describe <name | description file> [h5]     parse and validate a description (with h5: dataset sizes too); prints its canonical form.  No GPU work
 //   test_host labels <model> <h5> <images.f32>     argmax of plainModelForward per image ("label <i> <class>").  No GPU work
 //   test_host build <description> <h5> <dir> <batch>     see do_build
+//   test_host multiply <dir> <count>     multiplyRelin on <dir>/mul_x.u64, mul_y.u64 ([count] ciphertexts each, coefficient form; params.u64, evk.u64):
+//     writes mul_cc.u64 (coefficient form in and out) and mul_nn.u64 (both tensors NTT-resident, result NTT-resident, transformed back by the caller)
 //   test_host api <h5> <dir>     exercises save/load of the encoded model, client-side encrypt/decrypt, and error behaviour
 //   test_host files <dir>        CrCNN's own files: loads the encoded-model stream and the cipher_image file the REFERENCE wrote (<dir>/ref_encoded_layers.bin,
 //     ref_cipher_image.bin; cnnBuilder.cpp:181-196, globals.cpp:174-205), runs conv -> bn -> dense on them (out_from_ref_files.u64), then writes the same two
@@ -479,6 +481,35 @@ static int do_labels(int argc, char **argv)
 //   after Network::fuse()                    -> out_fused.u64, and on <batch> images out_fused_batch.u64
 // Prints "describe-ok" when Network::describe() is the description's canonical form and builds back to the same text, and the layer names after fuse()
 // ("fused <name> <name> ...")
+// multiplyRelin elementwise on two tensors; unequal shapes and forms must throw std::invalid_argument
+static int do_multiply(int argc, char **argv)
+{
+    if (argc < 4) return 1;
+    const string dir = argv[2]; const int count = atoi(argv[3]);
+    setup(dir);
+    { auto evk = rd(dir + "/evk.u64");
+      ev_keys16 = make_shared<DeviceBuffer>(evk.size() * 8);
+      crc_memcpy_h2d(context, ev_keys16->ptr, evk.data(), evk.size() * 8, nullptr); crc_stream_sync(context, nullptr); }
+    auto hx = rd(dir + "/mul_x.u64"), hy = rd(dir + "/mul_y.u64");
+    const ciphertext3D x = ciphertext3D::fromHost(hx.data(), 1, 1, 1, count), y = ciphertext3D::fromHost(hy.data(), 1, 1, 1, count);
+    wr(dir + "/mul_cc.u64", multiplyRelin(x, y, CRC_COEFF).toHost());
+    ciphertext3D xn = ciphertext3D::fromHost(hx.data(), 1, 1, 1, count), yn = ciphertext3D::fromHost(hy.data(), 1, 1, 1, count);
+    crc_ntt_fwd(context, xn.data(), count, 2, nullptr); xn.form = CRC_NTT;
+    crc_ntt_fwd(context, yn.data(), count, 2, nullptr); yn.form = CRC_NTT;
+    crc_stream_sync(context, nullptr);
+    ciphertext3D out = multiplyRelin(xn, yn, CRC_NTT);
+    if (out.form != CRC_NTT) return 4;
+    wr(dir + "/mul_nn.u64", out.toHost());
+    int refused = 0;
+    try { multiplyRelin(x, yn); } catch (const invalid_argument &) { refused++; }                                       // forms differ
+    try { multiplyRelin(x, ciphertext3D::fromHost(hy.data(), 1, 1, count, 1)); } catch (const invalid_argument &) { refused++; }      // shapes differ
+    try { multiplyRelin(x, y, CRC_NTTP); } catch (const invalid_argument &) { refused++; }                              // no packed result
+    try { multiplyRelin(ciphertext3D(), y); } catch (const invalid_argument &) { refused++; }                          // empty
+    delParameters();
+    printf("multiply ok refused %d\n", refused);
+    return refused == 4 ? 0 : 4;
+}
+
 static int do_build(int argc, char **argv)
 {
     if (argc < 6) return 1;
@@ -728,6 +759,7 @@ int main(int argc, char **argv)
         if (!strcmp(argv[1], "describe")) return do_describe(argc, argv);
         if (!strcmp(argv[1], "labels")) return do_labels(argc, argv);
         if (!strcmp(argv[1], "build")) return do_build(argc, argv);
+        if (!strcmp(argv[1], "multiply")) return do_multiply(argc, argv);
     } catch (const exception &e) { fprintf(stderr, "exception: %s\n", e.what()); return 10; }
     return 1;
 }

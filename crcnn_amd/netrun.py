@@ -71,7 +71,7 @@ def window_ok(xd, yd, xs, ys, xf, yf):
 
 
 _KEYS = {"conv": (("stride", 2), ("filter", 2), ("filters", 1)), "pool": (("stride", 2), ("window", 2)), "avgpool": (("stride", 2), ("window", 2))}
-_THREADED = ("conv", "fc", "square", "poly")
+_THREADED = ("conv", "fc", "square", "poly", "poly3")
 
 
 def parse_description(text, dataset_count=None):
@@ -135,7 +135,7 @@ def parse_description(text, dataset_count=None):
                 raise ValueError(f"line {ln}: a second refresh (line {pending_refresh or lines[refresh]} has the first)")
             pending_refresh = ln
             continue
-        if kind not in ("conv", "pool", "avgpool", "bn", "square", "fc", "pad", "poly"):
+        if kind not in ("conv", "pool", "avgpool", "bn", "square", "fc", "pad", "poly", "poly3"):
             raise ValueError(f"line {ln}: unknown layer kind {kind!r}")
         if len(tok) < 2:
             raise ValueError(f"line {ln}: {kind}: the layer name is missing")
@@ -147,7 +147,7 @@ def parse_description(text, dataset_count=None):
             th = ints(ln, rest[-1:], "threads")[0]
             rest = rest[:-2]
         zd, xd, yd = shape
-        if flat and kind in ("conv", "pool", "avgpool", "pad", "poly"):
+        if flat and kind in ("conv", "pool", "avgpool", "pad", "poly", "poly3"):
             raise ValueError(f"line {ln}: a {kind} layer cannot follow a fully connected layer: the tensor is flat ({xd} values)")
         if kind in _KEYS:
             vals, pos = {}, 0
@@ -191,6 +191,12 @@ def parse_description(text, dataset_count=None):
             a = dict(c2=coef(ln, rest[0], "c2"), c1=coef(ln, rest[1], "c1"), c0=coef(ln, rest[2], "c0"))
             if a["c2"] == 0.0:
                 raise ValueError(f"line {ln}: poly: c2 must not be zero (without its square term the layer is a batch norm, not an activation)")
+        elif kind == "poly3":
+            if len(rest) != 4:
+                raise ValueError(f"line {ln}: " + (f"unknown token {rest[4]!r}" if len(rest) > 4 else "poly3: takes c3 c2 c1 c0"))
+            a = dict(c3=coef(ln, rest[0], "c3"), c2=coef(ln, rest[1], "c2"), c1=coef(ln, rest[2], "c1"), c0=coef(ln, rest[3], "c0"))
+            if a["c3"] == 0.0:
+                raise ValueError(f"line {ln}: poly3: c3 must not be zero (without its cubic term the layer is a poly layer)")
         else:
             if rest:
                 raise ValueError(f"line {ln}: unknown token {rest[0]!r}")
@@ -228,6 +234,8 @@ def format_description(desc):
             ln = f"pad {name} {a['px']} {a['py']}"
         elif kind == "poly":
             ln = "poly %s %.9g %.9g %.9g" % (name, a["c2"], a["c1"], a["c0"])      # (%.9g of a float32 reads back as the same float32)
+        elif kind == "poly3":
+            ln = "poly3 %s %.9g %.9g %.9g %.9g" % (name, a["c3"], a["c2"], a["c1"], a["c0"])
         else:
             ln = f"{kind} {name}"
         if d.threads[i] not in (None, 1):         # (1 is what a layer without the token is built with)
@@ -357,6 +365,15 @@ class Network:
                 form = p["out_form"]
                 if eng.device >= 0:
                     p["rows"] = eng.poly2_rows(a["c2"], a["c1"], a["c0"])
+                    self._keep_rows(p["rows"])
+            elif kind == "poly3":
+                # c3 x^3 + c2 x^2 + c1 x + c0 with two key switches per ciphertext (crc_poly3_relin_forms): the forms of a Square layer, four plaintext rows.
+                # fuse() leaves the layer alone: nothing pairs it with a pooling layer behind it
+                p["in_form"] = form
+                p["out_form"] = COEFF if (last or not resident) else NTT
+                form = p["out_form"]
+                if eng.device >= 0:
+                    p["rows"] = eng.poly3_rows(a["c3"], a["c2"], a["c1"], a["c0"])
                     self._keep_rows(p["rows"])
             nshape = out_shape(kind, a, shape)
             self.plan.append((kind, name, a, p, shape, nshape))
@@ -761,6 +778,8 @@ class Network:
                 work = max(work, E.square_pool_relin_work_bytes(B, a["zd"], a["xd"], a["yd"], a["xs"], a["ys"], a["xf"], a["yf"], self.dbc))
             elif kind == "poly":
                 work = max(work, E.poly2_relin_work_bytes(B * int(np.prod(ishape)), self.dbc))
+            elif kind == "poly3":
+                work = max(work, E.poly3_relin_work_bytes(B * int(np.prod(ishape)), self.dbc))
             elif kind == "polypool":
                 work = max(work, E.poly2_pool_relin_work_bytes(B, a["zd"], a["xd"], a["yd"], a["xs"], a["ys"], a["xf"], a["yf"], self.dbc))
         return need_act, work
@@ -968,6 +987,9 @@ class Network:
                 cur = out
             elif kind == "poly":
                 E.poly2_relin(cur, B * int(np.prod(ishape)), self.d_evk, *p["rows"], out, self.work, self.dbc, p["in_form"], p["out_form"])
+                cur = out
+            elif kind == "poly3":
+                E.poly3_relin(cur, B * int(np.prod(ishape)), self.d_evk, *p["rows"], out, self.work, self.dbc, p["in_form"], p["out_form"])
                 cur = out
             elif kind == "polypool":
                 E.poly2_pool_relin(cur, B, a["zd"], a["xd"], a["yd"], a["xs"], a["ys"], a["xf"], a["yf"], self.d_evk, *p["rows"], out, self.work, self.dbc,

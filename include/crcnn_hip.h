@@ -347,6 +347,29 @@ size_t crc_poly2_pool_relin_work_bytes(const crc_ctx *ctx, int B, int zd, int xd
 int    crc_poly2_pool_relin_forms(crc_ctx *ctx, const uint64_t *d_x, int in_form, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf,
                                   const uint64_t *d_evk, int dbc, const uint64_t *d_p2_ntt, const uint64_t *d_p1_ntt, const uint64_t *d_p0_ntt, uint64_t *d_y,
                                   int out_form, void *d_work, void *stream);
+/* Ciphertext x ciphertext multiply: Evaluator::multiply of SEAL 2.3.1 (evaluator.cpp:356-700) for size-2 inputs x = (a, b), y = (c, d) -- BEHZ steps 0-4 with the
+ * tensor product (ac, ad + bc, bd); the reference forms the middle term by Karatsuba, the same residue -- bit for bit on every kernel selection ("sq_path",
+ * "f64_wave", ...), as the square.  d_x, d_y: [count] size-2 ciphertexts, multiplied pairwise; d_x == d_y is allowed and is the square (crc_square /
+ * crc_square_relin_forms, to the bit); swapped arguments give equal bytes.
+ *   crc_multiply              coefficient form in, size-3 ciphertexts out (unit tests; d_work: crc_multiply_relin_work_bytes with any valid dbc)
+ *   crc_multiply_relin_forms  relinearize(multiply(x, y), evk); both inputs share in_form; forms as crc_square_relin_forms (CRC_COEFF or CRC_NTT only)
+ * The result must not overlap either input: CRC_ERR_INVALID_ARGUMENT, like null pointers, a bad dbc and the packed or limb forms -- nothing is written then.
+ * Cost: the lift and the forward transforms run for both inputs, floor and key switch once -- see profiles/ct_multiply.md. */
+size_t crc_multiply_relin_work_bytes(const crc_ctx *ctx, size_t count, int dbc);
+int    crc_multiply(crc_ctx *ctx, const uint64_t *d_x, const uint64_t *d_y, size_t count, uint64_t *d_out3, void *d_work, void *stream);
+int    crc_multiply_relin_forms(crc_ctx *ctx, const uint64_t *d_x, const uint64_t *d_y, int in_form, size_t count, const uint64_t *d_evk, int dbc,
+                                uint64_t *d_out, int out_form, void *d_work, void *stream);
+/* Degree-3 polynomial activation c3 x^3 + c2 x^2 + c1 x + c0, per ciphertext x the Evaluator sequence (coefficient form)
+ *     s = relinearize(square(x), evk);  u = relinearize(multiply(s, x), evk);  r = multiply_plain(u, encode(c3));
+ *     r = add(r, multiply_plain(s, encode(c2)));  r = add(r, multiply_plain(x, encode(c1)));  r = add_plain(r, encode(c0))
+ * (a step is left out for c3 == 1, c2 == 0, c1 == 0, c0 == 0).  TWO key switches and a multiplicative depth of 2: the parameters must leave noise budget for
+ * a second multiplication -- CrCNN's published (4096, two moduli, t = 2^29) leave none.  The rows are NTT-form plaintext rows [k][n] as crc_poly2_relin_forms
+ * takes them (d_p0_ntt in delta form); NULL means 1, 0, 0, 0.  The lower terms are added slot-wise in NTT form, the same ring elements as the sequence.  d_out
+ * must not overlap d_x (CRC_ERR_INVALID_ARGUMENT). */
+size_t crc_poly3_relin_work_bytes(const crc_ctx *ctx, size_t count, int dbc);
+int    crc_poly3_relin_forms(crc_ctx *ctx, const uint64_t *d_x, int in_form, size_t count, const uint64_t *d_evk, int dbc, const uint64_t *d_p3_ntt,
+                             const uint64_t *d_p2_ntt, const uint64_t *d_p1_ntt, const uint64_t *d_p0_ntt, uint64_t *d_out, int out_form, void *d_work,
+                             void *stream);
 /* the two halves separately (unit tests): square -> size-3 ciphertexts; relinearize -> size 2 */
 int crc_square(crc_ctx *ctx, const uint64_t *d_x, size_t count, uint64_t *d_y3, void *d_work, void *stream);
 int crc_relinearize(crc_ctx *ctx, const uint64_t *d_x3, size_t count, const uint64_t *d_evk, int dbc, uint64_t *d_y,
