@@ -678,14 +678,230 @@ static bool tooLargeForHbm(size_t weights)
     const double share = e ? atof(e) : 0.75;
     return (double)weights * K() * N() * 8 > share * (double)total_b;
 }
+static size_t bytesOf(const shared_ptr<DeviceBuffer> &b) { return b ? b->bytes : 0; }
+static shared_ptr<DeviceBuffer> inttCopy(const shared_ptr<DeviceBuffer> &ntt_rows, size_t rows)       // coefficient-form twin of NTT-form delta rows
+{
+    const size_t rowb = (size_t)K() * N() * 8;
+    auto out = make_shared<DeviceBuffer>(rows * rowb);
+    chk(crc_memcpy_d2d(ctx(), out->ptr, ntt_rows->ptr, rows * rowb, stream()), "crc_memcpy_d2d");
+    chk(crc_ntt_inv(ctx(), (uint64_t *)out->ptr, rows, 1, stream()), "crc_ntt_inv");
+    return out;
+}
+
+// A batch-norm layer folded into the conv / dense layer behind it (Network::fuse), on canonical NTT-form weight rows [f][T] -- the whole layer, or one tile
+// of output rows while a tile-wise layer's limb weights are built: w'[f][z][tap] = w (*) s[z], b'[f] = b[f] - sum_t w'[f][t] (*) M[z(t)]
+struct BnFold {
+    BatchNormLayer &bn;
+    const int T, per_ch;                                    // weights per output row, and per batch-norm channel
+    DeviceBuffer fake, outc, wk;
+    vector<uint64_t> corr, q;
+    // (the correction is the dense kernel on one pseudo-image whose ciphertexts are (M[z(t)], 0), built here once for calls on up to max_rows output rows)
+    BnFold(BatchNormLayer &bn, int T, int per_ch, int max_rows) : bn(bn), T(T), per_ch(per_ch), fake((size_t)T * 2 * K() * N() * 8),
+        outc((size_t)max_rows * 2 * K() * N() * 8), wk(max<size_t>(crc_dense_work_bytes(ctx(), 1, T, max_rows, CRC_NTT), 256)),
+        corr((size_t)max_rows * 2 * K() * N()), q(K())
+    {
+        const size_t rowb = (size_t)K() * N() * 8;
+        chk(crc_memset(ctx(), fake.ptr, 0, fake.bytes, stream()), "crc_memset");
+        for (int z = 0; z < T / per_ch; z++) for (int t = 0; t < per_ch; t++)
+            chk(crc_memcpy_d2d(ctx(), (char *)fake.ptr + ((size_t)z * per_ch + t) * 2 * rowb, (char *)bn.d_mean[1]->ptr + (size_t)z * rowb, rowb, stream()),
+                "crc_memcpy_d2d");
+        chk(crc_ctx_table(ctx(), "q", q.data(), K()) < 0 ? CRC_ERR_INVALID_ARGUMENT : CRC_OK, "crc_ctx_table");
+    }
+    // d_w: fn output rows, scaled in place; bias: their NTT-form rows [fn][k][n] on the host, corrected in place.  Waits for the stream
+    void apply(uint64_t *d_w, int fn, uint64_t *bias)
+    {
+        const int n = N(), k = K();
+        for (int f = 0; f < fn; f++)
+            chk(crc_multiply_plain_ntt(ctx(), d_w + (size_t)f * T * k * n, (const uint64_t *)bn.d_invstd->ptr, T, per_ch, 1, stream()),
+                "crc_multiply_plain_ntt");
+        chk(crc_dense(ctx(), (const uint64_t *)fake.ptr, d_w, nullptr, 1, T, fn, CRC_NTT, CRC_NTT, (uint64_t *)outc.ptr, wk.ptr, stream()), "crc_dense");
+        chk(crc_memcpy_d2h(ctx(), corr.data(), outc.ptr, (size_t)fn * 2 * k * n * 8, stream()), "crc_memcpy_d2h");
+        chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+        for (int f = 0; f < fn; f++) for (int m = 0; m < k; m++) for (int s2 = 0; s2 < n; s2++) {
+            uint64_t &b = bias[((size_t)f * k + m) * n + s2]; const uint64_t c = corr[(((size_t)f * 2) * k + m) * n + s2];
+            b = b >= c ? b - c : b + q[m] - c;
+        }
+    }
+};
+
+// ---- MacLayer: what ConvolutionalLayer and FullyConnectedLayer share ------------------------------------------------------------------
+static bool g_matrix_cores = true;                  // Network::matrix_cores of the forward in progress (layers called directly plan with the default)
+// (the one statement of the policy, shared with netrun.py)
+int MacLayer::plannedForm(int B) const
+{
+    int wf = CRC_NTT;
+    chk(crc_plan_mac(ctx(), zd, xd, yd, xs, ys, xf, yf, nf, B, g_matrix_cores ? 1 : 0, &wf), "crc_plan_mac");
+    return wf;
+}
+// room for the limb copy (CRC_NTTL) beside the canonical weights it is made from
+bool MacLayer::limbFits() const
+{
+    size_t free_b = 0, total_b = 0;
+    chk(crc_mem_info(ctx(), &free_b, &total_b), "crc_mem_info");
+    return free_b >= crc_limb_weights_bytes(ctx(), nf, zd, xf, yf) + ((size_t)24 << 30);
+}
+void MacLayer::upload()
+{
+    if (alreadyNtt()) return;
+    vector<const Plaintext *> w, b;
+    plaintexts(0, nf, w, &b);
+    streamed = forced_placement >= 0 ? forced_placement == 1 : tooLargeForHbm(w.size());
+    // Tile-wise limb weights are a dense layer's only: the root's placement 2, or decided here.
+    if (forced_placement >= 0) tilewise = forcedTilewise();
+    // (g_expected_batch: a deployment that evaluates one image at a time -- setExpectedBatch(1) -- never takes the limb GEMM for a dense layer, so its canonical
+    // weights stay resident and the layer runs as a weight stream (mac_stream_kernel) instead of being built tile-wise in limb form)
+    else if (dense && !streamed && plannedForm(g_expected_batch) == CRC_NTTL) {
+        // canonical + limb copy beyond what HBM has left, the limb copy alone within it: build the limb weights tile by tile at the first forward
+        // (buildTilewise)
+        size_t free_b = 0, total_b = 0;
+        chk(crc_mem_info(ctx(), &free_b, &total_b), "crc_mem_info");
+        const size_t canon = w.size() * (size_t)K() * N() * 8, limb = crc_limb_weights_bytes(ctx(), nf, zd, xf, yf), reserve = (size_t)24 << 30;
+        // (the tests force it on small rings)
+        tilewise = (canon + limb + reserve > free_b && limb + reserve + ((size_t)8 << 30) <= free_b) || getenv("CRC_FORCE_TILEWISE") != nullptr;
+    }
+    if (streamed) d_plain = uploadPlain(w, 3); else if (!tilewise) d_w = uploadPlain(w, 0);
+    d_b[0] = uploadPlain(b, 1); d_b[1] = uploadPlain(b, 2);
+    alreadyNtt() = true;                   // transform_kernel_to_ntt, convolutionalLayer.cpp:151-156 (done once)
+}
+vector<uint64_t> MacLayer::hostBias()
+{
+    vector<uint64_t> bias((size_t)nf * K() * N());
+    chk(crc_memcpy_d2h(ctx(), bias.data(), d_b[1]->ptr, bias.size() * 8, stream()), "crc_memcpy_d2h");
+    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+    return bias;
+}
+void MacLayer::setBias(const vector<uint64_t> &ntt_rows)
+{
+    d_b[1] = make_shared<DeviceBuffer>(ntt_rows.size() * 8);
+    chk(crc_memcpy_h2d(ctx(), d_b[1]->ptr, ntt_rows.data(), ntt_rows.size() * 8, stream()), "crc_memcpy_h2d");
+    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+    d_b[0] = inttCopy(d_b[1], nf);
+}
+void MacLayer::buildTilewise()
+{
+    if (tile_built) return;
+    const size_t rowb = (size_t)K() * N() * 8, T = taps();
+    d_w = make_shared<DeviceBuffer>(crc_limb_weights_bytes(ctx(), nf, zd, xf, yf));
+    const int ft = (int)max<size_t>(1, min<size_t>((size_t)nf, ((size_t)4 << 30) / (T * rowb)));
+    unique_ptr<BnFold> fold;
+    vector<uint64_t> bias;
+    if (fold_bn) { fold.reset(new BnFold(*fold_bn, (int)T, (int)T / fold_bn->num_channels, ft)); bias = hostBias(); }
+    for (int f0 = 0; f0 < nf; f0 += ft) {
+        const int fn = min(ft, nf - f0);
+        vector<const Plaintext *> w;
+        plaintexts(f0, fn, w, nullptr);
+        shared_ptr<DeviceBuffer> wt = uploadPlain(w, 0);                                   // lift + NTT of the tile's plaintexts (canonical, scratch)
+        if (fold) fold->apply((uint64_t *)wt->ptr, fn, bias.data() + (size_t)f0 * K() * N());
+        chk(crc_limb_pack_weights_tile(ctx(), (const uint64_t *)wt->ptr, nf, f0, fn, zd, xf, yf, d_w->ptr, stream()), "crc_limb_pack_weights_tile");
+        chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+    }
+    if (fold) { setBias(bias); chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync"); }
+    w_form = CRC_NTTL; tile_built = true;
+}
+size_t MacLayer::deviceBytes() const { return bytesOf(d_w) + bytesOf(d_b[0]) + bytesOf(d_b[1]) + bytesOf(d_plain) + bytesOf(d_wtile) + bytesOf(d_ytile) +
+    bytesOf(d_w_canon); }
+string MacLayer::kernelName() const
+{
+    // one image through a resident dense layer runs as a weight stream
+    if (dense && last_B == 1 && !streamed && (w_form == CRC_NTTP || w_form == CRC_NTT)) return w_form == CRC_NTTP ?
+        "mac_stream_kernel (weight stream: one image, two rows per weight; v_mad_u64_u32, CRC_NTTP)" :
+        "mac_stream_kernel (weight stream: one image; canonical residues)";
+    const int wf = streamed ? stream_form : w_form;
+    const string k = wf == CRC_NTTL ? "mfma_mac2w_kernel (int8 limb GEMM, CRC_NTTL)" : wf == CRC_NTTL1 ?
+        "mfma_conv1_kernel (one-channel convolution on the matrix cores, CRC_NTTL1)"
+                   : wf == CRC_NTTP ? "mac3_kernel (v_mad_u64_u32, CRC_NTTP)" : "mac3_kernel (v_mad_u64_u32, canonical residues)";
+    return k + (!streamed ? "" : wf == CRC_NTTL ? ", streamed weights (64-filter limb tiles built inside the forward)" : ", streamed weights") +
+        (tilewise ? ", limb weights built tile by tile" : "");
+}
+int MacLayer::placement() { upload(); return streamed ? 1 : tilewise ? 2 : 0; }
+bool MacLayer::streamsOnMatrixCores(int B) { upload(); return streamed && plannedForm(B) == CRC_NTTL; }
+void MacLayer::restoreCanonical()
+{
+    if (w_form == CRC_NTTP || (w_form == CRC_NTTL1 && d_w_canon)) { packWeights(true); return; }
+    if (w_form != CRC_NTTL && w_form != CRC_NTTL1) return;
+    if (!hasPlaintexts()) throw logic_error(dense ? "FullyConnectedLayer " + name + ": weights are in limb form and there are no plaintexts to rebuild them from" :
+        "ConvolutionalLayer " + name + ": a folded layer's weights are in limb form and it has no plaintexts to rebuild them from");
+    // (a tile-wise layer goes back to "not built": the next forward builds its limb tensor again, with whatever batch-norm layer fuse() folds into it)
+    d_w.reset(); w_form = CRC_NTT; alreadyNtt() = false; tile_built = false;
+    upload();
+}
+void MacLayer::deviceParameters(vector<shared_ptr<DeviceBuffer>> &out, bool allocate_only)
+{
+    if (allocate_only && !alreadyNtt() && forcedTilewise()) {
+        // a tile-wise layer is never on the wire (its only device copy is the limb tensor -- 182 GiB for PlainModelWoPad's fc3 at n = 16384, k = 4 -- which
+        // every rank builds from its own plaintexts, deterministically): a receiving rank needs the model's plaintexts like the root
+        if (!hasPlaintexts()) throw logic_error("FullyConnectedLayer " + name +
+            ": tile-wise weights are built on every rank -- a receiving rank must load the model too");
+    } else if (allocate_only && !alreadyNtt()) {            // a receiving rank sizes the buffers without encoding anything
+        const size_t rowb = (size_t)K() * N() * 8;
+        streamed = forced_placement >= 0 ? forced_placement == 1 : tooLargeForHbm(nf * taps());
+        if (!streamed) d_w = make_shared<DeviceBuffer>(nf * taps() * rowb);
+        d_b[0] = make_shared<DeviceBuffer>(nf * rowb); d_b[1] = make_shared<DeviceBuffer>(nf * rowb);
+        alreadyNtt() = true;
+    }
+    upload();
+    if (tilewise) { buildTilewise(); return; }              // nothing to send or receive (see above)
+    packWeights(true);                                      // canonical residues on the wire
+    if (streamed && !d_plain) d_plain = make_shared<DeviceBuffer>(nf * taps() * N() * 8);
+    out.push_back(streamed ? d_plain : d_w); out.push_back(d_b[0]); out.push_back(d_b[1]);
+}
+bool MacLayer::limbWeights(int B)
+{
+    upload();
+    if (streamed) return false;
+    if (tilewise) { buildTilewise(); return true; }
+    if (w_form == CRC_NTTL || w_form == CRC_NTTL1) return true;
+    const int planned = plannedForm(B);
+    // The one-channel matrix-core kernel (kernels_mfma1.hip) is a convolution's only: crc_plan_mac answers CRC_NTTL1 for a dense layer with in_dim == 1 as
+    // well, which stays on the vector-ALU kernel
+    const bool conv1 = !dense && planned == CRC_NTTL1;
+    // (decided BEFORE the weights are touched: a layer that stays on the vector-ALU kernel keeps its 28-bit packed weights -- unpacking and re-packing them on
+    // every forward() is a read-modify-write of the whole layer.  Nothing is allocated between this look at the free memory and the limb copy below)
+    if (!conv1 && !(planned == CRC_NTTL && limbFits())) return false;
+    if (w_form == CRC_NTTP) packWeights(true);
+    auto wl = make_shared<DeviceBuffer>(conv1 ? crc_limb_conv1_weights_bytes_for(ctx(), nf, xf, yf) : crc_limb_weights_bytes(ctx(), nf, zd, xf, yf));
+    if (conv1) chk(crc_limb_conv1_pack_weights(ctx(), (const uint64_t *)d_w->ptr, nf, xf, yf, wl->ptr, stream()), "crc_limb_conv1_pack_weights");
+    else chk(crc_limb_pack_weights(ctx(), (const uint64_t *)d_w->ptr, nf, zd, xf, yf, wl->ptr, stream()), "crc_limb_pack_weights");
+    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+    // (the canonical copy of a one-channel layer is small: kept, so that the weights can go back on the wire; the limb GEMM's is dropped)
+    if (conv1) d_w_canon = d_w;
+    d_w = wl; w_form = conv1 ? CRC_NTTL1 : CRC_NTTL;
+    return true;
+}
+void MacLayer::packWeights(bool unpack)
+{
+    upload();
+    if (streamed || (tilewise && !tile_built)) return;
+    if (w_form == CRC_NTTL1 && unpack) { d_w = d_w_canon; d_w_canon.reset(); w_form = CRC_NTT; return; }
+    if (w_form == CRC_NTTL || w_form == CRC_NTTL1) { if (unpack) throw logic_error(kind() + (" " + name) +
+        ": weights are in limb form (fuse() / broadcastParameters() must precede the first forward())"); return; }
+    if ((w_form == CRC_NTTP) == !unpack) return;
+    chk(crc_pack28(ctx(), (uint64_t *)d_w->ptr, nf * taps() * K(), unpack ? 1 : 0, stream()), "crc_pack28");
+    w_form = unpack ? CRC_NTT : CRC_NTTP;
+}
+ciphertext3D MacLayer::run(const ciphertext3D &input, int zo, int xo, int yo)
+{
+    upload();
+    // a tile-wise layer has no canonical weights: whoever reaches it first -- Network::forward through limbWeights, a direct call, a network with matrix_cores
+    // off -- builds the limb tensor, the only form its weights exist in (the layer then runs on the limb GEMM whatever the plan would have been)
+    if (tilewise) buildTilewise();
+    last_B = input.B;
+    ciphertext3D out(input.B, zo, xo, yo, out_form);
+    if (streamed) { stream_form = forwardStreamed(input, out); return out; }
+    size_t wb = crc_conv2d_forms_work_bytes(ctx(), input.B, zd, xd, yd, xs, ys, xf, yf, nf, input.form, w_form, out_form);
+    if (!wb) throw invalid_argument(kind() + string(": unsupported geometry"));      // (a convolution's: a 1x1 geometry always has work bytes)
+    ensure(g_scratch, wb);
+    // (crc_dense_forms IS this call on the 1x1 geometry; a dense layer's failure keeps the name it has always been reported under)
+    chk(crc_conv2d_forms(ctx(), input.data(), (const uint64_t *)d_w->ptr, w_form, (const uint64_t *)d_b[out_form != CRC_COEFF]->ptr, input.B, zd, xd, yd, xs,
+        ys, xf, yf, nf, input.form, out_form, out.data(), g_scratch->ptr, stream()), dense ? "crc_dense_forms" : "crc_conv2d_forms");
+    if (out_form == CRC_NTTLC) out.form = CRC_NTTL;         // what the convolution behind reads as its limb-form input
+    return out;
+}
 // a streamed layer: lift + NTT a tile of filters, run the layer on the tile, scatter the tile's output channels into the [B][F][P] tensor
-static int plannedForm(int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int B);
-static int forwardStreamed(const ciphertext3D &input, ciphertext3D &out, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int out_form,
-                            shared_ptr<DeviceBuffer> &d_plain, shared_ptr<DeviceBuffer> *d_b, shared_ptr<DeviceBuffer> &d_wtile,
-                                shared_ptr<DeviceBuffer> &d_ytile, shared_ptr<DeviceBuffer> &d_work)
+int MacLayer::forwardStreamed(const ciphertext3D &input, ciphertext3D &out)
 {
     const size_t n = N(), k = K(), rowb = k * n * 8, ctb = ctBytes();
-    const size_t T = (size_t)zd * xf * yf, P = (size_t)((xd - xf) / xs + 1) * ((yd - yf) / ys + 1);
+    const size_t T = taps(), P = (size_t)((xd - xf) / xs + 1) * ((yd - yf) / ys + 1);
     auto scatter = [&](int f0, int ft) {
         for (int b = 0; b < input.B; b++)
             chk(crc_memcpy_d2d(ctx(), (char *)out.buf->ptr + ((size_t)b * nf + f0) * P * ctb, (const char *)d_ytile->ptr + (size_t)b * ft * P * ctb,
@@ -695,21 +911,21 @@ static int forwardStreamed(const ciphertext3D &input, ciphertext3D &out, int zd,
     // canonical sub-tiles of 8 filters (crc_limb_pack_weights_tile), the layer's input converted to limb form once per launch -- PlainModelWoPad's fc3 with all
     // eight primes of n = 16384 (netrun.py does the same: 25 against 58 ms per image on the vector-ALU tiles)
     const bool ntt_in = input.form == CRC_NTT || input.form == CRC_NTTP || input.form == CRC_NTTL;
-    if (ntt_in && plannedForm(zd, xd, yd, xs, ys, xf, yf, nf, input.B) == CRC_NTTL) {
+    if (ntt_in && plannedForm(input.B) == CRC_NTTL) {
         const int ft_max = min(64, nf), sub = min(8, ft_max);
         const size_t wt = (size_t)sub * T * rowb, wl = crc_limb_weights_bytes(ctx(), ft_max, zd, xf, yf), yt = (size_t)input.B * ft_max * P * ctb;
-        if (!d_wtile || d_wtile->bytes < wt) d_wtile = make_shared<DeviceBuffer>(wt);
-        if (!d_ytile || d_ytile->bytes < yt) d_ytile = make_shared<DeviceBuffer>(yt);
-        if (!g_wltile || g_wltile->bytes < wl) g_wltile = make_shared<DeviceBuffer>(wl);
+        ensure(d_wtile, wt);
+        ensure(d_ytile, yt);
+        ensure(g_wltile, wl);
         const void *xl = input.data();
         if (input.form != CRC_NTTL) {
             const size_t xb = crc_limb_tensor_bytes(ctx(), input.B, zd, xd, yd);
-            if (!g_xltile || g_xltile->bytes < xb) g_xltile = make_shared<DeviceBuffer>(xb);
+            ensure(g_xltile, xb);
             chk(crc_limb_pack_tensor(ctx(), input.data(), input.form, input.B, zd, xd, yd, g_xltile->ptr, stream()), "crc_limb_pack_tensor");
             xl = g_xltile->ptr;
         }
         const size_t wb = crc_conv2d_forms_work_bytes(ctx(), input.B, zd, xd, yd, xs, ys, xf, yf, ft_max, CRC_NTTL, CRC_NTTL, out_form);
-        if (!d_work || d_work->bytes < wb) d_work = make_shared<DeviceBuffer>(wb);
+        ensure(g_scratch, wb);
         for (int f0 = 0; f0 < nf; f0 += ft_max) {
             const int ft = min(ft_max, nf - f0);
             for (int s0 = 0; s0 < ft; s0 += sub) {
@@ -721,7 +937,7 @@ static int forwardStreamed(const ciphertext3D &input, ciphertext3D &out, int zd,
             }
             chk(crc_conv2d_forms(ctx(), (const uint64_t *)xl, (const uint64_t *)g_wltile->ptr, CRC_NTTL,
                 (const uint64_t *)((const char *)d_b[out_form != CRC_COEFF]->ptr + (size_t)f0 * rowb),
-                                 input.B, zd, xd, yd, xs, ys, xf, yf, ft, CRC_NTTL, out_form, (uint64_t *)d_ytile->ptr, d_work->ptr, stream()),
+                                 input.B, zd, xd, yd, xs, ys, xf, yf, ft, CRC_NTTL, out_form, (uint64_t *)d_ytile->ptr, g_scratch->ptr, stream()),
                                      "crc_conv2d_forms");
             scatter(f0, ft);
         }
@@ -734,155 +950,44 @@ static int forwardStreamed(const ciphertext3D &input, ciphertext3D &out, int zd,
         free_b / 8));
     size_t ftv = tile_bytes / (T * rowb); if (ftv >= 8) ftv = ftv / 8 * 8;
     const int ft_max = (int)max<size_t>(1, min<size_t>(nf, ftv));
-    if (!d_wtile || d_wtile->bytes < ft_max * T * rowb) d_wtile = make_shared<DeviceBuffer>(ft_max * T * rowb);
-    if (!d_ytile || d_ytile->bytes < (size_t)input.B * ft_max * P * ctb) d_ytile = make_shared<DeviceBuffer>((size_t)input.B * ft_max * P * ctb);
+    ensure(d_wtile, ft_max * T * rowb);
+    ensure(d_ytile, (size_t)input.B * ft_max * P * ctb);
     size_t wb = crc_conv2d_forms_work_bytes(ctx(), input.B, zd, xd, yd, xs, ys, xf, yf, ft_max, input.form, CRC_NTT, out_form);
-    if (!d_work || d_work->bytes < wb) d_work = make_shared<DeviceBuffer>(wb);
+    ensure(g_scratch, wb);
     for (int f0 = 0; f0 < nf; f0 += ft_max) {
         const int ft = min(ft_max, nf - f0);
         chk(crc_plain_to_ntt(ctx(), (const uint64_t *)d_plain->ptr + (size_t)f0 * T * n, (size_t)ft * T, (uint64_t *)d_wtile->ptr, stream()),
             "crc_plain_to_ntt");
         chk(crc_conv2d_forms(ctx(), input.data(), (const uint64_t *)d_wtile->ptr, CRC_NTT, (const uint64_t *)((const char *)d_b[out_form != CRC_COEFF]->ptr +
             (size_t)f0 * rowb), input.B,
-                             zd, xd, yd, xs, ys, xf, yf, ft, input.form, out_form, (uint64_t *)d_ytile->ptr, d_work->ptr, stream()), "crc_conv2d_forms");
+                             zd, xd, yd, xs, ys, xf, yf, ft, input.form, out_form, (uint64_t *)d_ytile->ptr, g_scratch->ptr, stream()), "crc_conv2d_forms");
         scatter(f0, ft);
     }
     return CRC_NTT;
 }
 
-// the kernel crc_plan_mac picks for a conv / dense layer launched on B images (the one statement of the policy, shared with netrun.py)
-static bool g_matrix_cores = true;                  // Network::matrix_cores of the forward in progress (layers called directly plan with the default)
-static int plannedForm(int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int B)
-{
-    int wf = CRC_NTT;
-    chk(crc_plan_mac(ctx(), zd, xd, yd, xs, ys, xf, yf, nf, B, g_matrix_cores ? 1 : 0, &wf), "crc_plan_mac");
-    return wf;
-}
-// canonical NTT-form weights -> limb form (CRC_NTTL) when crc_plan_mac says the limb GEMM pays for this shape and launch size and the second copy fits beside
-// the first; the canonical copy is dropped
-static bool limbFits(int nf, int zd, int xf, int yf)
-{
-    size_t free_b = 0, total_b = 0;
-    chk(crc_mem_info(ctx(), &free_b, &total_b), "crc_mem_info");
-    return free_b >= crc_limb_weights_bytes(ctx(), nf, zd, xf, yf) + ((size_t)24 << 30);
-}
-static bool toLimb(shared_ptr<DeviceBuffer> &d_w, int &w_form, int nf, int zd, int xf, int yf, bool planned)
-{
-    if (w_form == CRC_NTTL) return true;
-    if (!planned || !limbFits(nf, zd, xf, yf)) return false;
-    const size_t nbytes = crc_limb_weights_bytes(ctx(), nf, zd, xf, yf);
-    auto wl = make_shared<DeviceBuffer>(nbytes);
-    chk(crc_limb_pack_weights(ctx(), (const uint64_t *)d_w->ptr, nf, zd, xf, yf, wl->ptr, stream()), "crc_limb_pack_weights");
-    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
-    d_w = wl; w_form = CRC_NTTL;
-    return true;
-}
-
 // ---- ConvolutionalLayer -----------------------------------------------------------------------------------------------
 ConvolutionalLayer::ConvolutionalLayer(string name, int xd, int yd, int zd, int xs, int ys, int xf, int yf, int nf, int th_count, plaintext4D &filters,
     vector<Plaintext> &biases)
-    : Layer(name), xd(xd), yd(yd), zd(zd), xs(xs), ys(ys), xf(xf), yf(yf), nf(nf), th_count(th_count),
-      xo((xd - xf) / xs + 1), yo((yd - yf) / ys + 1), zo(nf), filters(filters), biases(biases) {}
+    : MacLayer(name, false, zd, xd, yd, xs, ys, xf, yf, nf), th_count(th_count), xo((xd - xf) / xs + 1), yo((yd - yf) / ys + 1), zo(nf), filters(filters),
+      biases(biases) {}
 ConvolutionalLayer::ConvolutionalLayer(string name, int xd, int yd, int zd, int xs, int ys, int xf, int yf, int nf, int th_count, istream *infile)
-    : Layer(name), xd(xd), yd(yd), zd(zd), xs(xs), ys(ys), xf(xf), yf(yf), nf(nf), th_count(th_count),
-      xo((xd - xf) / xs + 1), yo((yd - yf) / ys + 1), zo(nf) { loadPlaintextParameters(infile); }
-void ConvolutionalLayer::upload()
+    : MacLayer(name, false, zd, xd, yd, xs, ys, xf, yf, nf), th_count(th_count), xo((xd - xf) / xs + 1), yo((yd - yf) / ys + 1), zo(nf)
+    { loadPlaintextParameters(infile); }
+void ConvolutionalLayer::plaintexts(int f0, int fn, vector<const Plaintext *> &w, vector<const Plaintext *> *b) const
 {
-    if (filters_already_ntt) return;
     if ((int)filters.size() != nf || (int)biases.size() != nf) throw invalid_argument("conv: filter/bias count mismatch");
-    vector<const Plaintext *> w, b;
-    for (int f = 0; f < nf; f++) {
+    for (int f = f0; f < f0 + fn; f++) {
         if ((int)filters[f].size() != zd || (int)filters[f][0].size() != xf ||
             (int)filters[f][0][0].size() != yf) throw invalid_argument("conv: kernel shape mismatch");
         for (int z = 0; z < zd; z++) for (int i = 0; i < xf; i++) for (int j = 0; j < yf; j++) w.push_back(&filters[f][z][i][j]);
-        b.push_back(&biases[f]);
+        if (b) b->push_back(&biases[f]);
     }
-    streamed = forced_placement >= 0 ? forced_placement == 1 : tooLargeForHbm(w.size());
-    if (streamed) d_plain = uploadPlain(w, 3); else d_w = uploadPlain(w, 0);
-    d_b[0] = uploadPlain(b, 1); d_b[1] = uploadPlain(b, 2);
-    filters_already_ntt = true;            // transform_kernel_to_ntt, convolutionalLayer.cpp:151-156 (done once)
-}
-static size_t bytesOf(const shared_ptr<DeviceBuffer> &b) { return b ? b->bytes : 0; }
-static string macKernelName(int w_form, bool streamed)
-{
-    const string k = w_form == CRC_NTTL ? "mfma_mac2w_kernel (int8 limb GEMM, CRC_NTTL)" : w_form == CRC_NTTL1 ?
-        "mfma_conv1_kernel (one-channel convolution on the matrix cores, CRC_NTTL1)"
-                   : w_form == CRC_NTTP ? "mac3_kernel (v_mad_u64_u32, CRC_NTTP)" : "mac3_kernel (v_mad_u64_u32, canonical residues)";
-    return streamed ? k + (w_form == CRC_NTTL ? ", streamed weights (64-filter limb tiles built inside the forward)" : ", streamed weights") : k;
-}
-size_t ConvolutionalLayer::deviceBytes() const { return bytesOf(d_w) + bytesOf(d_b[0]) + bytesOf(d_b[1]) + bytesOf(d_plain) + bytesOf(d_wtile) +
-    bytesOf(d_ytile) + bytesOf(d_w_canon); }
-string ConvolutionalLayer::kernelName() const { return macKernelName(streamed ? stream_form : w_form, streamed); }
-int ConvolutionalLayer::placement() { upload(); return streamed ? 1 : 0; }
-void ConvolutionalLayer::restoreCanonical()
-{
-    if (w_form == CRC_NTTP) { packWeights(true); return; }
-    if (w_form == CRC_NTTL1 && d_w_canon) { d_w = d_w_canon; d_w_canon.reset(); w_form = CRC_NTT; return; }
-    if (w_form != CRC_NTTL && w_form != CRC_NTTL1) return;
-    if ((int)filters.size() != nf) throw logic_error("ConvolutionalLayer " + name +
-        ": a folded layer's weights are in limb form and it has no plaintexts to rebuild them from");
-    d_w.reset(); w_form = CRC_NTT; filters_already_ntt = false;
-    upload();
-}
-void ConvolutionalLayer::deviceParameters(vector<shared_ptr<DeviceBuffer>> &out, bool allocate_only)
-{
-    if (allocate_only && !filters_already_ntt) {
-        const size_t rowb = (size_t)K() * N() * 8;
-        streamed = forced_placement >= 0 ? forced_placement == 1 : tooLargeForHbm((size_t)nf * zd * xf * yf);
-        if (!streamed) d_w = make_shared<DeviceBuffer>((size_t)nf * zd * xf * yf * rowb);
-        d_b[0] = make_shared<DeviceBuffer>(nf * rowb); d_b[1] = make_shared<DeviceBuffer>(nf * rowb);
-        filters_already_ntt = true;
-    }
-    packWeights(true);                                      // canonical residues on the wire (uploads first if needed)
-    if (streamed && !d_plain) d_plain = make_shared<DeviceBuffer>((size_t)nf * zd * xf * yf * N() * 8);
-    out.push_back(streamed ? d_plain : d_w); out.push_back(d_b[0]); out.push_back(d_b[1]);
-}
-bool ConvolutionalLayer::limbWeights(int B)
-{
-    upload();
-    if (streamed) return false;
-    if (w_form == CRC_NTTL || w_form == CRC_NTTL1) return true;
-    const int planned = plannedForm(zd, xd, yd, xs, ys, xf, yf, nf, B);
-    // (decided BEFORE the weights are touched: a layer that stays on the vector-ALU kernel keeps its 28-bit packed weights -- unpacking and re-packing them on
-    // every forward() is a read-modify-write of the whole layer)
-    if (planned != CRC_NTTL1 && !(planned == CRC_NTTL && limbFits(nf, zd, xf, yf))) return false;
-    if (w_form == CRC_NTTP) packWeights(true);
-    if (planned == CRC_NTTL1) {          // one-channel convolutions have their own matrix-core kernel (kernels_mfma1.hip)
-        auto wl = make_shared<DeviceBuffer>(crc_limb_conv1_weights_bytes_for(ctx(), nf, xf, yf));
-        chk(crc_limb_conv1_pack_weights(ctx(), (const uint64_t *)d_w->ptr, nf, xf, yf, wl->ptr, stream()), "crc_limb_conv1_pack_weights");
-        chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
-        // (the canonical copy of a one-channel layer is small: kept, so that the weights can go back on the wire)
-        d_w_canon = d_w; d_w = wl; w_form = CRC_NTTL1;
-        return true;
-    }
-    return toLimb(d_w, w_form, nf, zd, xf, yf, planned == CRC_NTTL);
-}
-void ConvolutionalLayer::packWeights(bool unpack)
-{
-    upload();
-    if (streamed) return;
-    if (w_form == CRC_NTTL1 && unpack) { d_w = d_w_canon; d_w_canon.reset(); w_form = CRC_NTT; return; }
-    if (w_form == CRC_NTTL || w_form == CRC_NTTL1) { if (unpack) throw logic_error("ConvolutionalLayer " + name +
-        ": weights are in limb form (fuse() / broadcastParameters() must precede the first forward())"); return; }
-    if ((w_form == CRC_NTTP) == !unpack) return;
-    chk(crc_pack28(ctx(), (uint64_t *)d_w->ptr, (size_t)nf * zd * xf * yf * K(), unpack ? 1 : 0, stream()), "crc_pack28");
-    w_form = unpack ? CRC_NTT : CRC_NTTP;
 }
 ciphertext3D ConvolutionalLayer::forward(ciphertext3D input)
 {
     checkInput(input, zd, xd, yd, "ConvolutionalLayer");
-    upload();
-    ciphertext3D out(input.B, zo, xo, yo, out_form);
-    if (streamed) { stream_form = forwardStreamed(input, out, zd, xd, yd, xs, ys, xf, yf, nf, out_form, d_plain, d_b, d_wtile, d_ytile, g_scratch);
-        return out; }
-    size_t wb = crc_conv2d_forms_work_bytes(ctx(), input.B, zd, xd, yd, xs, ys, xf, yf, nf, input.form, w_form, out_form);
-    if (!wb) throw invalid_argument("ConvolutionalLayer: unsupported geometry");
-    ensure(g_scratch, wb);
-    chk(crc_conv2d_forms(ctx(), input.data(), (const uint64_t *)d_w->ptr, w_form, (const uint64_t *)d_b[out_form != CRC_COEFF]->ptr, input.B, zd, xd, yd, xs,
-        ys, xf, yf, nf,
-                         input.form, out_form, out.data(), g_scratch->ptr, stream()), "crc_conv2d_forms");
-    if (out_form == CRC_NTTLC) out.form = CRC_NTTL;         // what the convolution behind reads as its limb-form input
-    return out;
+    return run(input, zo, xo, yo);
 }
 void ConvolutionalLayer::savePlaintextParameters(ostream *outfile)
 {   // order of convolutionalLayer.cpp:213-229
@@ -907,167 +1012,23 @@ void ConvolutionalLayer::printLayerStructure()
 
 // ---- FullyConnectedLayer ----------------------------------------------------------------------------------------------
 FullyConnectedLayer::FullyConnectedLayer(string name, int in_dim, int out_dim, int th_count, plaintext2D &weights, vector<Plaintext> &biases)
-    : Layer(name), in_dim(in_dim), out_dim(out_dim), th_count(th_count), weights(weights), biases(biases) {}
+    : MacLayer(name, true, in_dim, 1, 1, 1, 1, 1, 1, out_dim), in_dim(in_dim), out_dim(out_dim), th_count(th_count), weights(weights), biases(biases) {}
 FullyConnectedLayer::FullyConnectedLayer(string name, int in_dim, int out_dim, int th_count, istream *infile)
-    : Layer(name), in_dim(in_dim), out_dim(out_dim), th_count(th_count) { loadPlaintextParameters(infile); }
-void FullyConnectedLayer::upload()
+    : MacLayer(name, true, in_dim, 1, 1, 1, 1, 1, 1, out_dim), in_dim(in_dim), out_dim(out_dim), th_count(th_count) { loadPlaintextParameters(infile); }
+void FullyConnectedLayer::plaintexts(int f0, int fn, vector<const Plaintext *> &w, vector<const Plaintext *> *b) const
 {
-    if (weights_already_ntt) return;
     if ((int)weights.size() != out_dim || (int)biases.size() != out_dim) throw invalid_argument("fc: weight/bias count mismatch");
-    vector<const Plaintext *> w, b;
-    for (int i = 0; i < out_dim; i++) {
+    for (int i = f0; i < f0 + fn; i++) {
         if ((int)weights[i].size() != in_dim) throw invalid_argument("fc: row length mismatch");
         for (int j = 0; j < in_dim; j++) w.push_back(&weights[i][j]);
-        b.push_back(&biases[i]);
+        if (b) b->push_back(&biases[i]);
     }
-    streamed = forced_placement >= 0 ? forced_placement == 1 : tooLargeForHbm(w.size());
-    if (forced_placement >= 0) tilewise = forced_placement == 2;
-    // (g_expected_batch: a deployment that evaluates one image at a time -- setExpectedBatch(1) -- never takes the limb GEMM for a dense layer, so its canonical
-    // weights stay resident and the layer runs as a weight stream (mac_stream_kernel) instead of being built tile-wise in limb form)
-    else if (!streamed && plannedForm(in_dim, 1, 1, 1, 1, 1, 1, out_dim, g_expected_batch) == CRC_NTTL) {
-        // canonical + limb copy beyond what HBM has left, the limb copy alone within it: build the limb weights tile by tile at the first forward
-        // (buildTilewise)
-        size_t free_b = 0, total_b = 0;
-        chk(crc_mem_info(ctx(), &free_b, &total_b), "crc_mem_info");
-        const size_t canon = w.size() * (size_t)K() * N() * 8, limb = crc_limb_weights_bytes(ctx(), out_dim, in_dim, 1, 1), reserve = (size_t)24 << 30;
-        // (the tests force it on small rings)
-        tilewise = (canon + limb + reserve > free_b && limb + reserve + ((size_t)8 << 30) <= free_b) || getenv("CRC_FORCE_TILEWISE") != nullptr;
-    }
-    if (streamed) d_plain = uploadPlain(w, 3); else if (!tilewise) d_w = uploadPlain(w, 0);
-    d_b[0] = uploadPlain(b, 1); d_b[1] = uploadPlain(b, 2);
-    weights_already_ntt = true;
-}
-void FullyConnectedLayer::buildTilewise()
-{
-    if (tile_built) return;
-    const int n = N(), k = K();
-    const size_t rowb = (size_t)k * n * 8, T = (size_t)in_dim;
-    d_w = make_shared<DeviceBuffer>(crc_limb_weights_bytes(ctx(), out_dim, in_dim, 1, 1));
-    const int ft = (int)max<size_t>(1, min<size_t>((size_t)out_dim, ((size_t)4 << 30) / (T * rowb)));
-    shared_ptr<DeviceBuffer> fake, outc, wk;
-    vector<uint64_t> bias, corr, q(k);
-    int ch = 0, per_ch = 0;
-    if (fold_bn) {
-        ch = fold_bn->num_channels; per_ch = in_dim / ch;
-        fake = make_shared<DeviceBuffer>(T * 2 * rowb); outc = make_shared<DeviceBuffer>((size_t)ft * 2 * rowb);
-        wk = make_shared<DeviceBuffer>(max<size_t>(crc_dense_work_bytes(ctx(), 1, in_dim, ft, CRC_NTT), 256));
-        chk(crc_memset(ctx(), fake->ptr, 0, T * 2 * rowb, stream()), "crc_memset");
-        for (int z = 0; z < ch; z++) for (int t = 0; t < per_ch; t++)
-            chk(crc_memcpy_d2d(ctx(), (char *)fake->ptr + ((size_t)z * per_ch + t) * 2 * rowb, (char *)fold_bn->d_mean[1]->ptr + (size_t)z * rowb, rowb,
-                stream()), "crc_memcpy_d2d");
-        bias.resize((size_t)out_dim * k * n); corr.resize((size_t)ft * 2 * k * n);
-        chk(crc_memcpy_d2h(ctx(), bias.data(), d_b[1]->ptr, bias.size() * 8, stream()), "crc_memcpy_d2h");
-        chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
-        chk(crc_ctx_table(ctx(), "q", q.data(), k) < 0 ? CRC_ERR_INVALID_ARGUMENT : CRC_OK, "crc_ctx_table");
-    }
-    for (int f0 = 0; f0 < out_dim; f0 += ft) {
-        const int fn = min(ft, out_dim - f0);
-        vector<const Plaintext *> w;
-        for (int i = f0; i < f0 + fn; i++) for (int j = 0; j < in_dim; j++) w.push_back(&weights[i][j]);
-        shared_ptr<DeviceBuffer> wt = uploadPlain(w, 0);                                   // lift + NTT of the tile's plaintexts (canonical, scratch)
-        if (fold_bn) {
-            for (int f = 0; f < fn; f++)                                                   // w'[f][z][tap] = w (*) s[z]
-                chk(crc_multiply_plain_ntt(ctx(), (uint64_t *)wt->ptr + (size_t)f * T * k * n, (const uint64_t *)fold_bn->d_invstd->ptr, T, per_ch, 1,
-                    stream()), "crc_multiply_plain_ntt");
-            chk(crc_dense(ctx(), (const uint64_t *)fake->ptr, (const uint64_t *)wt->ptr, nullptr, 1, in_dim, fn, CRC_NTT, CRC_NTT, (uint64_t *)outc->ptr,
-                wk->ptr, stream()), "crc_dense");
-            chk(crc_memcpy_d2h(ctx(), corr.data(), outc->ptr, (size_t)fn * 2 * rowb, stream()), "crc_memcpy_d2h");
-            chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
-            for (int f = 0; f < fn; f++) for (int m = 0; m < k; m++) for (int s2 = 0; s2 < n; s2++) {
-                uint64_t &b = bias[((size_t)(f0 + f) * k + m) * n + s2]; const uint64_t c = corr[(((size_t)f * 2) * k + m) * n + s2];
-                b = b >= c ? b - c : b + q[m] - c;
-            }
-        }
-        chk(crc_limb_pack_weights_tile(ctx(), (const uint64_t *)wt->ptr, out_dim, f0, fn, in_dim, 1, 1, d_w->ptr, stream()), "crc_limb_pack_weights_tile");
-        chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
-    }
-    if (fold_bn) {
-        d_b[1] = make_shared<DeviceBuffer>(bias.size() * 8);
-        chk(crc_memcpy_h2d(ctx(), d_b[1]->ptr, bias.data(), bias.size() * 8, stream()), "crc_memcpy_h2d");
-        chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
-        d_b[0] = make_shared<DeviceBuffer>(bias.size() * 8);
-        chk(crc_memcpy_d2d(ctx(), d_b[0]->ptr, d_b[1]->ptr, bias.size() * 8, stream()), "crc_memcpy_d2d");
-        chk(crc_ntt_inv(ctx(), (uint64_t *)d_b[0]->ptr, (size_t)out_dim, 1, stream()), "crc_ntt_inv");
-        chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
-    }
-    w_form = CRC_NTTL; tile_built = true;
-}
-size_t FullyConnectedLayer::deviceBytes() const { return bytesOf(d_w) + bytesOf(d_b[0]) + bytesOf(d_b[1]) + bytesOf(d_plain) + bytesOf(d_wtile) +
-    bytesOf(d_ytile); }
-string FullyConnectedLayer::kernelName() const { if (last_B == 1 && !streamed && (w_form == CRC_NTTP || w_form == CRC_NTT)) return w_form == CRC_NTTP ?
-    "mac_stream_kernel (weight stream: one image, two rows per weight; v_mad_u64_u32, CRC_NTTP)" : "mac_stream_kernel (weight stream: one image; canonical residues)";
-    return macKernelName(streamed ? stream_form : w_form, streamed) + (tilewise ?
-    ", limb weights built tile by tile" : ""); }
-int FullyConnectedLayer::placement() { upload(); return streamed ? 1 : tilewise ? 2 : 0; }
-bool FullyConnectedLayer::streamsOnMatrixCores(int B) { upload(); return streamed && plannedForm(in_dim, 1, 1, 1, 1, 1, 1, out_dim, B) == CRC_NTTL; }
-void FullyConnectedLayer::restoreCanonical()
-{
-    if (w_form == CRC_NTTP) { packWeights(true); return; }
-    if (w_form != CRC_NTTL) return;
-    if ((int)weights.size() != out_dim) throw logic_error("FullyConnectedLayer " + name +
-        ": weights are in limb form and there are no plaintexts to rebuild them from");
-    // (a tile-wise layer goes back to "not built": the next forward builds its limb tensor again, with whatever batch-norm layer fuse() folds into it)
-    d_w.reset(); w_form = CRC_NTT; weights_already_ntt = false; tile_built = false;
-    upload();
-}
-void FullyConnectedLayer::deviceParameters(vector<shared_ptr<DeviceBuffer>> &out, bool allocate_only)
-{
-    if (allocate_only && !weights_already_ntt && forced_placement == 2) {
-        // a tile-wise layer is never on the wire (its only device copy is the limb tensor -- 182 GiB for PlainModelWoPad's fc3 at n = 16384, k = 4 -- which
-        // every rank builds from its own plaintexts, deterministically): a receiving rank needs the model's plaintexts like the root
-        if ((int)weights.size() != out_dim) throw logic_error("FullyConnectedLayer " + name +
-            ": tile-wise weights are built on every rank -- a receiving rank must load the model too");
-    } else if (allocate_only && !weights_already_ntt) {
-        const size_t rowb = (size_t)K() * N() * 8;
-        streamed = forced_placement >= 0 ? forced_placement == 1 : tooLargeForHbm((size_t)in_dim * out_dim);
-        if (!streamed) d_w = make_shared<DeviceBuffer>((size_t)in_dim * out_dim * rowb);
-        d_b[0] = make_shared<DeviceBuffer>(out_dim * rowb); d_b[1] = make_shared<DeviceBuffer>(out_dim * rowb);
-        weights_already_ntt = true;
-    }
-    upload();
-    if (tilewise) { buildTilewise(); return; }              // nothing to send or receive (see above)
-    packWeights(true);
-    if (streamed && !d_plain) d_plain = make_shared<DeviceBuffer>((size_t)in_dim * out_dim * N() * 8);
-    out.push_back(streamed ? d_plain : d_w); out.push_back(d_b[0]); out.push_back(d_b[1]);
-}
-bool FullyConnectedLayer::limbWeights(int B)
-{
-    upload();
-    if (streamed) return false;
-    if (tilewise) { buildTilewise(); return true; }
-    if (w_form == CRC_NTTL) return true;
-    // (before the packed weights are touched)
-    if (plannedForm(in_dim, 1, 1, 1, 1, 1, 1, out_dim, B) != CRC_NTTL || !limbFits(out_dim, in_dim, 1, 1)) return false;
-    if (w_form == CRC_NTTP) packWeights(true);
-    return toLimb(d_w, w_form, out_dim, in_dim, 1, 1, true);
-}
-void FullyConnectedLayer::packWeights(bool unpack)
-{
-    upload();
-    if (streamed || (tilewise && !tile_built)) return;
-    if (w_form == CRC_NTTL) { if (unpack) throw logic_error("FullyConnectedLayer " + name +
-        ": weights are in limb form (fuse() / broadcastParameters() must precede the first forward())"); return; }
-    if ((w_form == CRC_NTTP) == !unpack) return;
-    chk(crc_pack28(ctx(), (uint64_t *)d_w->ptr, (size_t)in_dim * out_dim * K(), unpack ? 1 : 0, stream()), "crc_pack28");
-    w_form = unpack ? CRC_NTT : CRC_NTTP;
 }
 ciphertext3D FullyConnectedLayer::forward(ciphertext3D input)
 {
     // reshapeInput, :38-56
     if (!input.buf || input.zd * input.xd * input.yd != in_dim) throw invalid_argument("FullyConnectedLayer: input size does not match in_dim");
-    upload();
-    // a tile-wise layer has no canonical weights: whoever reaches it first -- Network::forward through limbWeights, a direct call, a network with matrix_cores
-    // off -- builds the limb tensor, the only form its weights exist in (the layer then runs on the limb GEMM whatever the plan would have been)
-    if (tilewise && !tile_built) buildTilewise();
-    last_B = input.B;
-    ciphertext3D out(input.B, 1, out_dim, 1, out_form);
-    if (streamed) { stream_form = forwardStreamed(input, out, in_dim, 1, 1, 1, 1, 1, 1, out_dim, out_form, d_plain, d_b, d_wtile, d_ytile, g_scratch);
-        return out; }
-    ensure(g_scratch, crc_conv2d_forms_work_bytes(ctx(), input.B, in_dim, 1, 1, 1, 1, 1, 1, out_dim, input.form, w_form, out_form));
-    chk(crc_dense_forms(ctx(), input.data(), (const uint64_t *)d_w->ptr, w_form, (const uint64_t *)d_b[out_form != CRC_COEFF]->ptr, input.B, in_dim, out_dim,
-        input.form, out_form,
-                        out.data(), g_scratch->ptr, stream()), "crc_dense_forms");
-    return out;
+    return run(input, 1, out_dim, 1);
 }
 void FullyConnectedLayer::savePlaintextParameters(ostream *outfile)
 {
@@ -1364,26 +1325,22 @@ ciphertext3D Network::forward(ciphertext3D input)
     // conv / dense weights go into the MAC kernels' operand form (28-bit limb pairs) once; moduli above 55 bits cannot be packed
     bool packable = true;
     { vector<uint64_t> q(K()); crc_ctx_table(ctx(), "q", q.data(), K()); for (uint64_t v : q) if (v >> 55) packable = false; }
-    auto isMac = [&](int i) { return i >= 0 && i < L && (dynamic_pointer_cast<ConvolutionalLayer>(layers[i]) ||
-        dynamic_pointer_cast<FullyConnectedLayer>(layers[i])); };
+    vector<shared_ptr<MacLayer>> mac(L + 1);                // the conv / dense layers (mac[L]: none behind the last layer)
+    for (int i = 0; i < L; i++) mac[i] = dynamic_pointer_cast<MacLayer>(layers[i]);
     vector<char> limb(L, 0), streams(L, 0);
     // two-level chunking: the layers in front of the first dense layer on sub-batches of head_chunk images, the dense layers on the whole batch
     int split = L;
     if (head_chunk > 0 && input.B > head_chunk && ntt_resident && max_num_of_reencryptions < 0)
-        for (int i = 1; i < L; i++) if (dynamic_pointer_cast<FullyConnectedLayer>(layers[i])) { split = i; break; }
+        for (int i = 1; i < L; i++) if (mac[i] && mac[i]->dense) { split = i; break; }
     const bool chunked = split < L;
     if (packable)
-        for (int i = 0; i < L; i++) {
+        for (int i = 0; i < L; i++) if (auto m = mac[i]) {
             const int Bi = chunked && i < split ? head_chunk : input.B;
-            if (auto c = dynamic_pointer_cast<ConvolutionalLayer>(layers[i])) { limb[i] = matrix_cores && c->limbWeights(Bi);
-                if (!limb[i]) c->packWeights(false); }
-            else if (auto f = dynamic_pointer_cast<FullyConnectedLayer>(layers[i])) {
-                limb[i] = matrix_cores && f->limbWeights(Bi);
-                if (!limb[i]) f->packWeights(false);
-                // a STREAMED dense layer that will run on the matrix cores (64-filter limb tiles built inside the forward) reads a limb tensor like a resident
-                // one: the chunks of a group are packed straight into it, and no second copy of the group's input is made inside the layer
-                if (matrix_cores && f->streamsOnMatrixCores(Bi)) { limb[i] = 1; streams[i] = 1; }
-            }
+            limb[i] = matrix_cores && m->limbWeights(Bi);
+            if (!limb[i]) m->packWeights(false);
+            // a STREAMED dense layer that will run on the matrix cores (64-filter limb tiles built inside the forward) reads a limb tensor like a resident
+            // one: the chunks of a group are packed straight into it, and no second copy of the group's input is made inside the layer
+            if (matrix_cores && m->dense && m->streamsOnMatrixCores(Bi)) { limb[i] = 1; streams[i] = 1; }
         }
     for (int i = 0; i < L; i++) {
         // the tensor in front of the refresh is decrypted as it stands (crc_refresh_dev takes either ciphertext form): an NTT-resident network stays resident
@@ -1392,14 +1349,11 @@ ciphertext3D Network::forward(ciphertext3D input)
         bool coeff = !ntt_resident || i == L - 1;
         // a conv / dense layer feeding another one hands its tensor over packed as well ... and a limb layer feeding a DENSE limb layer hands it over in limb
         // form (not across the chunk boundary: a dense layer's limb tensor is laid out for its whole batch, the chunks are assembled into it below)
-        const bool to_dense_limb = i + 1 < L && limb[i] && !streams[i] && limb[i + 1] && dynamic_pointer_cast<FullyConnectedLayer>(layers[i + 1]) &&
-            !(chunked && i + 1 == split);
+        const bool to_dense_limb = i + 1 < L && limb[i] && !streams[i] && limb[i + 1] && mac[i + 1]->dense && !(chunked && i + 1 == split);
         // ... and a one-channel convolution writes the limb tensor of a matrix-core CONVOLUTION behind it itself
-        auto ci = dynamic_pointer_cast<ConvolutionalLayer>(layers[i]);
-        auto cn = i + 1 < L ? dynamic_pointer_cast<ConvolutionalLayer>(layers[i + 1]) : nullptr;
-        const bool to_conv_limb = ci && cn && ci->w_form == CRC_NTTL1 && cn->w_form == CRC_NTTL;
+        const bool to_conv_limb = mac[i] && mac[i + 1] && !mac[i]->dense && !mac[i + 1]->dense && mac[i]->w_form == CRC_NTTL1 && mac[i + 1]->w_form == CRC_NTTL;
         layers[i]->out_form = coeff ? CRC_COEFF : before_refresh ? CRC_NTT : to_dense_limb && max_num_of_reencryptions < 0 ? CRC_NTTL : to_conv_limb &&
-            max_num_of_reencryptions < 0 ? CRC_NTTLC : (packable && max_num_of_reencryptions < 0 && isMac(i) && isMac(i + 1) ? CRC_NTTP : CRC_NTT);
+            max_num_of_reencryptions < 0 ? CRC_NTTLC : (packable && max_num_of_reencryptions < 0 && mac[i] && mac[i + 1] ? CRC_NTTP : CRC_NTT);
     }
     last_layer_ms.assign(L, 0.0);
     last_layer_launches.assign(L, 0);
@@ -1599,8 +1553,7 @@ size_t Network::broadcastParameters(crc_comm *comm, int root, bool encode_locall
 
 int Network::fuse()
 {
-    const int n = N(), k = K();
-    const size_t rowb = (size_t)k * n * 8;
+    const size_t rowb = (size_t)K() * N() * 8;
     int removed = 0;
     // The client-side refresh sits in front of layers[layer_before_reenc] (network.cpp:30-34).  No fold may span it, and the index follows the layers it
     // counts: erasing a layer below it moves the refresh point down with the layers behind it, so the refresh still runs in front of the same layer.
@@ -1610,18 +1563,10 @@ int Network::fuse()
         if (layer_before_reenc >= 0 && (int)idx < layer_before_reenc) layer_before_reenc--;
         removed++;
     };
-    for (auto &l : layers) {                                // the folding kernels work on canonical residues
-        // (a network that has already run holds its weights in the MAC kernels' operand forms: packed residues are unpacked, matrix-core forms -- which drop
-        // the canonical copy -- are rebuilt from the layer's plaintexts, so fuse() may follow a forward())
-        if (auto c = dynamic_pointer_cast<ConvolutionalLayer>(l)) c->restoreCanonical();
-        else if (auto f = dynamic_pointer_cast<FullyConnectedLayer>(l)) f->restoreCanonical();
-    }
-    auto inttCopy = [&](const shared_ptr<DeviceBuffer> &ntt_rows, size_t rows) {       // coefficient-form twin of NTT-form delta rows
-        auto out = make_shared<DeviceBuffer>(rows * rowb);
-        chk(crc_memcpy_d2d(ctx(), out->ptr, ntt_rows->ptr, rows * rowb, stream()), "crc_memcpy_d2d");
-        chk(crc_ntt_inv(ctx(), (uint64_t *)out->ptr, rows, 1, stream()), "crc_ntt_inv");
-        return out;
-    };
+    // the folding kernels work on canonical residues
+    // (a network that has already run holds its weights in the MAC kernels' operand forms: packed residues are unpacked, matrix-core forms -- which drop
+    // the canonical copy -- are rebuilt from the layer's plaintexts, so fuse() may follow a forward())
+    for (auto &l : layers) if (auto m = dynamic_pointer_cast<MacLayer>(l)) m->restoreCanonical();
     // 1. conv + pool
     for (size_t i = 0; i + 1 < layers.size(); i++) {
         auto conv = dynamic_pointer_cast<ConvolutionalLayer>(layers[i]);
@@ -1683,51 +1628,29 @@ int Network::fuse()
     for (size_t i = 0; i + 1 < layers.size(); i++) {
         auto bn = dynamic_pointer_cast<BatchNormLayer>(layers[i]);
         if (!bn || refreshBetween(i)) continue;
-        auto conv = dynamic_pointer_cast<ConvolutionalLayer>(layers[i + 1]);
-        auto fc = dynamic_pointer_cast<FullyConnectedLayer>(layers[i + 1]);
-        if (!conv && !fc) continue;
-        const int ch = bn->num_channels;
-        int F, per_ch, T;
-        if (conv) { if (conv->zd != ch) continue; F = conv->nf; per_ch = conv->xf * conv->yf; T = conv->zd * per_ch; conv->upload();
-            if (conv->streamed) continue; }
-        else { if (fc->in_dim % ch) continue; F = fc->out_dim; per_ch = fc->in_dim / ch; T = fc->in_dim; fc->upload(); if (fc->streamed) continue; }
+        auto m = dynamic_pointer_cast<MacLayer>(layers[i + 1]);
+        if (!m) continue;
+        // weights per output row and per batch-norm channel: a convolution has one channel per batch-norm channel, a dense layer reads the flattened
+        // [ch][x][y] tensor
+        const int ch = bn->num_channels, T = (int)m->taps();
+        if (m->dense ? T % ch != 0 : m->zd != ch) continue;
+        const int per_ch = T / ch;
+        m->upload();
+        if (m->streamed) continue;
         bn->upload();
         // no canonical weights to fold into: the fold is applied tile by tile when the limb weights are built
-        if (fc && fc->tilewise) {
-            if (fc->tile_built) continue;
-            fc->fold_bn = bn;
-            layers[i + 1]->name = bn->name + "+" + layers[i + 1]->name;
+        if (m->tilewise) {
+            if (m->tile_built) continue;
+            m->fold_bn = bn;
+            m->name = bn->name + "+" + m->name;
             eraseLayer(i);
             continue;
         }
-        shared_ptr<DeviceBuffer> &dw = conv ? conv->d_w : fc->d_w;
-        shared_ptr<DeviceBuffer> *db = conv ? conv->d_b : fc->d_b;
-        // w'[f][z][tap] = w (*) s[z]
-        for (int f = 0; f < F; f++)
-            chk(crc_multiply_plain_ntt(ctx(), (uint64_t *)dw->ptr + (size_t)f * T * k * n, (const uint64_t *)bn->d_invstd->ptr, T, per_ch, 1, stream()),
-                "crc_multiply_plain_ntt");
-        // correction[f] = sum_t w'[f][t] (*) M[z(t)]: the dense kernel on one pseudo-image whose ciphertexts are (M[z(t)], 0)
-        DeviceBuffer fake((size_t)T * 2 * rowb), outc((size_t)F * 2 * rowb), wk(max<size_t>(crc_dense_work_bytes(ctx(), 1, T, F, CRC_NTT), 256));
-        chk(crc_memset(ctx(), fake.ptr, 0, (size_t)T * 2 * rowb, stream()), "crc_memset");
-        for (int z = 0; z < ch; z++) for (int t = 0; t < per_ch; t++)
-            chk(crc_memcpy_d2d(ctx(), (char *)fake.ptr + ((size_t)z * per_ch + t) * 2 * rowb, (char *)bn->d_mean[1]->ptr + (size_t)z * rowb, rowb, stream()),
-                "crc_memcpy_d2d");
-        chk(crc_dense(ctx(), (const uint64_t *)fake.ptr, (const uint64_t *)dw->ptr, nullptr, 1, T, F, CRC_NTT, CRC_NTT, (uint64_t *)outc.ptr, wk.ptr,
-            stream()), "crc_dense");
-        vector<uint64_t> corr((size_t)F * 2 * k * n), bias((size_t)F * k * n), q(k);
-        chk(crc_memcpy_d2h(ctx(), corr.data(), outc.ptr, corr.size() * 8, stream()), "crc_memcpy_d2h");
-        chk(crc_memcpy_d2h(ctx(), bias.data(), db[1]->ptr, bias.size() * 8, stream()), "crc_memcpy_d2h");
-        chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
-        chk(crc_ctx_table(ctx(), "q", q.data(), k) < 0 ? CRC_ERR_INVALID_ARGUMENT : CRC_OK, "crc_ctx_table");
-        for (int f = 0; f < F; f++) for (int m = 0; m < k; m++) for (int s2 = 0; s2 < n; s2++) {
-            uint64_t &b = bias[((size_t)f * k + m) * n + s2]; const uint64_t c = corr[(((size_t)f * 2) * k + m) * n + s2];
-            b = b >= c ? b - c : b + q[m] - c;
-        }
-        db[1] = make_shared<DeviceBuffer>(bias.size() * 8);
-        chk(crc_memcpy_h2d(ctx(), db[1]->ptr, bias.data(), bias.size() * 8, stream()), "crc_memcpy_h2d");
-        chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
-        db[0] = inttCopy(db[1], F);
-        layers[i + 1]->name = bn->name + "+" + layers[i + 1]->name;
+        BnFold fold(*bn, T, per_ch, m->nf);
+        vector<uint64_t> bias = m->hostBias();
+        fold.apply((uint64_t *)m->d_w->ptr, m->nf, bias.data());
+        m->setBias(bias);
+        m->name = bn->name + "+" + m->name;
         eraseLayer(i);
     }
     chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");

@@ -162,10 +162,72 @@ public:
 };
 
 class BatchNormLayer;
-class ConvolutionalLayer : public Layer {                   // convolutionalLayer.h:33-34
+struct BnFold;
+// What a convolutional and a fully connected layer share: the multiply-accumulate layer y[f] = sum_t x[t] (*) w[f][t] + Delta b[f] over a geometry
+// (zd, xd, yd, xs, ys, xf, yf, nf) -- a dense layer is the 1x1 convolution (in_dim, 1, 1, 1, 1, 1, 1, out_dim), as everywhere below the host -- with ONE copy
+// of the weights' device state, of their placement and operand forms, and of the forward call.  The two classes add the reference's constructors, fields and
+// plaintext containers.  The geometry is fixed at construction
+class MacLayer : public Layer {
 public:
     friend class Network;
-    int xd, yd, zd, xs, ys, xf, yf, nf, th_count;
+    const int zd, xd, yd, xs, ys, xf, yf, nf;
+    void deviceParameters(std::vector<std::shared_ptr<DeviceBuffer>> &out, bool allocate_only) override;
+    int placement() override;
+    void adoptPlacement(int p) override { forced_placement = p; }
+    // weights back to canonical NTT form (unpacked; rebuilt from the plaintexts when the matrix-core form replaced them)
+    void restoreCanonical();
+    size_t deviceBytes() const override;
+    std::string kernelName() const override;
+protected:
+    MacLayer(std::string name, bool dense, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf)
+        : Layer(name), zd(zd), xd(xd), yd(yd), xs(xs), ys(ys), xf(xf), yf(yf), nf(nf), dense(dense) {}
+    // the layer on an input the caller has checked; the output tensor is [B][zo][xo][yo]
+    ciphertext3D run(const ciphertext3D &input, int zo, int xo, int yo);
+private:
+    // what the shared code asks of the class's plaintext containers: the reference's "weights are on the device" flag, whether the containers are filled (a
+    // layer Network::fuse() made has none), and the plaintexts of output rows [f0, f0 + fn) in the order the kernels read them, [f][zd][xf][yf], with the
+    // biases of those rows when b is given (std::invalid_argument when the containers do not have the layer's shape)
+    virtual bool &alreadyNtt() = 0;
+    virtual bool hasPlaintexts() const = 0;
+    virtual void plaintexts(int f0, int fn, std::vector<const Plaintext *> &w, std::vector<const Plaintext *> *b) const = 0;
+    const bool dense;                                       // decides the two one-sided features below, and the class name in error texts
+    const char *kind() const { return dense ? "FullyConnectedLayer" : "ConvolutionalLayer"; }
+    size_t taps() const { return (size_t)zd * xf * yf; }    // weights per output row
+    std::shared_ptr<DeviceBuffer> d_w, d_b[2];              // NTT-form weights, bias delta in coefficient / NTT form
+    // weights whose NTT form (k rows each) would take more than 75 % of HBM stay coefficient-form plaintexts (ONE row each) and are lifted + transformed a
+    // ~2-GiB filter tile at a time inside every forward (SURVEY section 7's fall-back; PlainModelWoPad's fc3 with all eight primes of n = 16384 is 419 GB)
+    bool streamed = false;
+    int stream_form = CRC_NTT;                              // operand form of the last streamed forward (CRC_NTTL: 64-filter limb tiles on the matrix cores)
+    std::shared_ptr<DeviceBuffer> d_plain, d_wtile, d_ytile;
+    // CRC_NTTP / CRC_NTTL / CRC_NTTL1 once Network::forward has put the weights into their MAC kernel's operand form
+    int w_form = CRC_NTT;
+    // CONVOLUTIONS ONLY: the one-channel matrix-core form CRC_NTTL1 (limbWeights), and with it the canonical NTT-form weights it keeps beside the limb copy
+    std::shared_ptr<DeviceBuffer> d_w_canon;
+    // DENSE LAYERS ONLY (upload): a layer whose canonical NTT-form weights and their limb copy do not fit in HBM together (PlainModelWoPad's fc3 at n = 16384,
+    // k = 4: 202 + 182 GiB) never gets a canonical copy: its limb weights are built a tile of output rows at a time straight from the plaintexts (lift + NTT ->
+    // batch-norm fold of the tile -> pack), a batch-norm layer that Network::fuse() folds into it being applied to every tile (same ciphertexts; netrun.py
+    // does the same)
+    bool tilewise = false, tile_built = false;
+    std::shared_ptr<BatchNormLayer> fold_bn;
+    int last_B = 0;                                         // images of the last forward (kernelName: one image through a dense layer runs as a weight stream)
+    int forced_placement = -1;
+    bool forcedTilewise() const { return dense && forced_placement == 2; }
+    int plannedForm(int B) const;                           // the kernel crc_plan_mac picks for a launch on B images
+    bool limbFits() const;
+    void upload();
+    void buildTilewise();
+    void packWeights(bool unpack);
+    // -> CRC_NTTL / CRC_NTTL1 (matrix-core kernels) when the layer qualifies (for batches of B) and HBM has room for the second copy
+    bool limbWeights(int B);
+    bool streamsOnMatrixCores(int B);                       // streamed, and a launch on B images takes the limb GEMM (forwardStreamed's 64-filter limb tiles)
+    int forwardStreamed(const ciphertext3D &input, ciphertext3D &out);
+    std::vector<uint64_t> hostBias();                       // the NTT-form bias rows [nf][k][n]
+    void setBias(const std::vector<uint64_t> &ntt_rows);    // ... replaced, with their coefficient-form twin
+};
+
+class ConvolutionalLayer : public MacLayer {                // convolutionalLayer.h:33-34
+public:
+    int th_count;
     int xo, yo, zo;
     plaintext4D filters;                                    // nf,zd,xf,yf
     std::vector<Plaintext> biases;
@@ -180,33 +242,13 @@ public:
     void loadPlaintextParameters(std::istream *infile) override;
     void printLayerStructure() override;
 private:
-    std::shared_ptr<DeviceBuffer> d_w, d_b[2];              // NTT-form weights, bias delta in coefficient / NTT form
-    // weights whose NTT form (k rows each) would take more than 75 % of HBM stay coefficient-form plaintexts (ONE row each) and are lifted + transformed a
-    // ~2-GiB filter tile at a time inside every forward (SURVEY section 7's fall-back; PlainModelWoPad's fc3 with all eight primes of n = 16384 is 419 GB)
-    bool streamed = false;
-    int stream_form = CRC_NTT;                              // operand form of the last streamed forward (CRC_NTTL: 64-filter limb tiles on the matrix cores)
-    std::shared_ptr<DeviceBuffer> d_plain, d_wtile, d_ytile;
-    // CRC_NTTP / CRC_NTTL / CRC_NTTL1 once Network::forward has put the weights into their MAC kernel's operand form
-    int w_form = CRC_NTT;
-    std::shared_ptr<DeviceBuffer> d_w_canon;                // CRC_NTTL1 only: the canonical NTT-form weights
-    int forced_placement = -1;
-    void upload();
-    void packWeights(bool unpack);
-    // -> CRC_NTTL (matrix-core kernel) when the layer qualifies (for batches of B) and HBM has room for the second copy
-    bool limbWeights(int B);
-public:
-    void deviceParameters(std::vector<std::shared_ptr<DeviceBuffer>> &out, bool allocate_only) override;
-    int placement() override;
-    void adoptPlacement(int p) override { forced_placement = p; }
-    // weights back to canonical NTT form (unpacked; rebuilt from the plaintexts when the matrix-core form replaced them)
-    void restoreCanonical();
-    size_t deviceBytes() const override;
-    std::string kernelName() const override;
+    bool &alreadyNtt() override { return filters_already_ntt; }
+    bool hasPlaintexts() const override { return (int)filters.size() == nf; }
+    void plaintexts(int f0, int fn, std::vector<const Plaintext *> &w, std::vector<const Plaintext *> *b) const override;
 };
 
-class FullyConnectedLayer : public Layer {                  // fullyConnectedLayer.h:22-24
+class FullyConnectedLayer : public MacLayer {               // fullyConnectedLayer.h:22-24
 public:
-    friend class Network;
     int in_dim, out_dim, th_count;
     plaintext2D weights;
     std::vector<Plaintext> biases;
@@ -220,30 +262,9 @@ public:
     void loadPlaintextParameters(std::istream *infile) override;
     void printLayerStructure() override;
 private:
-    std::shared_ptr<DeviceBuffer> d_w, d_b[2];
-    bool streamed = false;                                  // see ConvolutionalLayer
-    int stream_form = CRC_NTT;
-    std::shared_ptr<DeviceBuffer> d_plain, d_wtile, d_ytile;
-    int w_form = CRC_NTT;
-    // A layer whose canonical NTT-form weights and their limb copy do not fit in HBM together (PlainModelWoPad's fc3 at n = 16384, k = 4: 202 + 182 GiB) never
-    // gets a canonical copy: its limb weights are built a tile of output rows at a time straight from the plaintexts (lift + NTT -> batch-norm fold of the tile
-    // -> pack), a batch-norm layer that Network::fuse() folds into it being applied to every tile (same ciphertexts; netrun.py does the same)
-    bool tilewise = false, tile_built = false;
-    int last_B = 0;                                         // images of the last forward (kernelName: one image runs as a weight stream)
-    int forced_placement = -1;
-    std::shared_ptr<BatchNormLayer> fold_bn;
-    void buildTilewise();
-    void upload();
-    void packWeights(bool unpack);
-    bool limbWeights(int B);
-    bool streamsOnMatrixCores(int B);                      // streamed, and a launch on B images takes the limb GEMM (forwardStreamed's 64-filter limb tiles)
-public:
-    void deviceParameters(std::vector<std::shared_ptr<DeviceBuffer>> &out, bool allocate_only) override;
-    int placement() override;
-    void adoptPlacement(int p) override { forced_placement = p; }
-    void restoreCanonical();
-    size_t deviceBytes() const override;
-    std::string kernelName() const override;
+    bool &alreadyNtt() override { return weights_already_ntt; }
+    bool hasPlaintexts() const override { return (int)weights.size() == out_dim; }
+    void plaintexts(int f0, int fn, std::vector<const Plaintext *> &w, std::vector<const Plaintext *> *b) const override;
 };
 
 class PoolingLayer : public Layer {                         // poolingLayer.h:15
@@ -375,7 +396,7 @@ private:
 class BatchNormLayer : public Layer {                       // batchNormLayer.h:18-20
 public:
     friend class Network;
-    friend class FullyConnectedLayer;
+    friend struct BnFold;
     int num_channels;
     std::vector<Plaintext> mean, var;                       // var already holds encode(1/sqrt(var+1e-5)) (cnnBuilder.cpp:100-102)
     BatchNormLayer(std::string name, int num_channels, std::vector<Plaintext> &mean, std::vector<Plaintext> &var);

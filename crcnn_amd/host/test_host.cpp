@@ -664,6 +664,23 @@ static int do_api(int argc, char **argv)
         EXPECT_THROW(net.broadcastParameters(comm, 1), invalid_argument);
         crc_comm_destroy(comm);
     }
+    // a dense layer with ONE input: crc_plan_mac may answer the one-channel matrix-core form for its (1, 1, 1, ...) geometry, which is a convolution's only --
+    // the layer runs on the vector-ALU kernel with matrix_cores on as with it off, and gives the same words
+    {
+        plaintext2D ow(4, vector<Plaintext>(1)); vector<Plaintext> ob(4);
+        for (int i = 0; i < 4; i++) { ow[i][0] = enc(0.25f * (float)(i - 2)); ob[i] = enc(0.125f * (float)i); }
+        ciphertext3D one = encryptImage(vector<float>{0.75f}, 1, 1, 1);
+        vector<u64> got[2];
+        for (int on = 1; on >= 0; on--) {
+            Network nn;
+            nn.getLayers().push_back(shared_ptr<Layer>(new FullyConnectedLayer("one", 1, 4, 1, ow, ob)));
+            nn.matrix_cores = on != 0;
+            got[on] = nn.forward(one).toHost();
+            const string kn = nn.getLayer(0)->kernelName();
+            if (kn.find("mfma_conv1_kernel") != string::npos) { fprintf(stderr, "in_dim = 1 dense layer runs on %s\n", kn.c_str()); return 15; }
+        }
+        if (got[0].empty() || got[0] != got[1]) { fprintf(stderr, "in_dim = 1 dense layer: matrix_cores on and off differ\n"); return 15; }
+    }
     // error behaviour mirrors the reference (std::invalid_argument on bad shapes / truncated streams)
     EXPECT_THROW(net.getLayer(0)->forward(ciphertext3D(1, 1, 10, 10)), invalid_argument);
     { istringstream empty(""); EXPECT_THROW(FullyConnectedLayer("f", 4, 2, 1, &empty), invalid_argument); }
