@@ -3,6 +3,7 @@
 #include <cstring>
 #include "kernels.h"
 #include "chacha.h"
+#include "work_arena.h"
 
 // every device entry point makes its context's GPU current for the calling thread (a no-op in the one-process-per-GPU flow; in a one-process, many-GPU
 // application the launch must not land on whatever device the thread used last)
@@ -13,6 +14,9 @@ static inline hipStream_t S(void *s) { return (hipStream_t)s; }
 static inline bool form_ok(int f) { return f == CRC_COEFF || f == CRC_NTT; }
 static inline bool nform_ok(int f) { return f == CRC_COEFF || f == CRC_NTT || f == CRC_NTTP; }
 static inline bool lform_ok(int f) { return nform_ok(f) || f == CRC_NTTL; }
+// entry points whose work space is one region: its start in d_work, and the size of `words` of it
+static inline u64 *work_base(void *d_work) { return WorkArena(d_work).take<u64>(0); }
+static inline size_t work_bytes(size_t words) { WorkArena a; a.take<u64>(words); return a.bytes(); }
 
 extern "C" int crc_plain_to_ntt(crc_ctx *c, const uint64_t *d_plain, size_t count, uint64_t *d_out, void *stream)
 {
@@ -89,16 +93,15 @@ static bool conv_shape_ok(int xd, int yd, int xs, int ys, int xf, int yf)
     if (xl < 1 || yl < 1) return false;
     return (xl + xs - 1) / xs == (xd - xf) / xs + 1 && (yl + ys - 1) / ys == (yd - yf) / ys + 1;
 }
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-extern "C" size_t crc_conv2d_work_bytes(const crc_ctx *c, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int in_form)
+// Work of a layer on the vector-ALU kernels: [offsets of the P outputs][offsets of the T (+ 8) taps, in ciphertexts and in words][NTT copy of a coefficient-form input]
+struct ConvWork { int *xoff, *toff; unsigned *toffw; u64 *buf; };
+static ConvWork conv_layout(const crc_ctx *c, int B, int zd, int xd, int yd, int xf, int yf, int P, int in_form, WorkArena &a)
 {
-    (void)nf;
-    if (!c || !conv_shape_ok(xd, yd, xs, ys, xf, yf)) return 0;
-    const int xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys + 1;
-    size_t b = align256(sizeof(int) * (size_t)xo * yo) + 2 * align256(sizeof(int) * ((size_t)zd * xf * yf + 8));
-    if (in_form == CRC_COEFF) b += (size_t)B * zd * xd * yd * crc_ct_words(c, 2) * 8;
-    return b + 256;
+    const size_t T = (size_t)zd * xf * yf;
+    ConvWork L{};
+    L.xoff = a.take<int>(P); L.toff = a.take<int>(T + 8); L.toffw = a.take<unsigned>(T + 8);
+    if (in_form == CRC_COEFF) L.buf = a.take<u64>((size_t)B * zd * xd * yd * crc_ct_words(c, 2));
+    return L;
 }
 
 // ---- limb form (CRC_NTTL): the layer on the matrix cores (kernels_mfma.hip) ------------------------------------------------------------
@@ -167,55 +170,67 @@ static int conv1_sub_batch(const crc_ctx *c, int B, int xd, int yd, int xf, int 
     const size_t fit = cap / (per ? per : 1);
     return (int)(fit < 1 ? 1 : fit > (size_t)B ? (size_t)B : fit);
 }
+// Work of a one-channel layer, for a pass of Bs images: [y-expanded limb images][slot-major result (not where the kernel writes the limb tensor itself)][NTT copy
+// of a coefficient-form sub-batch].  out_form: the form the passes produce
+struct Limb1Work { signed char *Xr; u64 *Ys, *buf; int Bs, out_form; };
+static Limb1Work limb1_layout(const crc_ctx *c, int B, int xd, int yd, int xf, int yf, int nf, int P, int in_form, int out_form, WorkArena &a)
+{
+    Limb1Work L{};
+    // a 1 x 1 result is a dense layer's input: the K-blocked form (kernels_mfma.hip), made from the slot-major result
+    L.out_form = out_form == CRC_NTTLC && P == 1 ? CRC_NTTL : out_form;
+    L.Bs = conv1_sub_batch(c, B, xd, yd, xf, yf, nf, P, L.out_form);
+    L.Xr = a.take<signed char>(k_limb_conv1_image_bytes(c, L.Bs, xd, yd, xf, yf, nf));
+    if (L.out_form != CRC_NTTLC) L.Ys = a.take<u64>(k_limb_result_words(c, L.Bs, nf, P));
+    if (in_form == CRC_COEFF) L.buf = a.take<u64>((size_t)L.Bs * xd * yd * crc_ct_words(c, 2));
+    return L;
+}
 static int conv2d_limb1(crc_ctx *c, const uint64_t *d_x, const void *d_wl, const uint64_t *d_bias, int B, int xd, int yd, int xs, int ys, int xf, int yf,
     int nf,
                         int in_form, int out_form, uint64_t *d_y, void *d_work, hipStream_t st)
 {
     const int xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys + 1, P = xo * yo, in_cts = xd * yd;
-    // a 1 x 1 result is a dense layer's input: the K-blocked form (kernels_mfma.hip), made from the slot-major result
-    if (out_form == CRC_NTTLC && P == 1) out_form = CRC_NTTL;
-    const int Bs = conv1_sub_batch(c, B, xd, yd, xf, yf, nf, P, out_form);
+    WorkArena a(d_work);
+    const Limb1Work L = limb1_layout(c, B, xd, yd, xf, yf, nf, P, in_form, out_form, a);
+    out_form = L.out_form;
     const size_t ctw = crc_ct_words(c, 2);
-    char *w = (char *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
-    signed char *Xr = (signed char *)w; w += align256(k_limb_conv1_image_bytes(c, Bs, xd, yd, xf, yf, nf));
-    u64 *Ys = nullptr;
-    if (out_form != CRC_NTTLC) { Ys = (u64 *)w; w += align256(8 * k_limb_result_words(c, Bs, nf, P)); }
-    u64 *buf = (u64 *)w;                                           // NTT copy of a coefficient-form sub-batch
-    for (int b0 = 0; b0 < B; b0 += Bs) {
-        const int Bn = B - b0 < Bs ? B - b0 : Bs;
+    for (int b0 = 0; b0 < B; b0 += L.Bs) {
+        const int Bn = B - b0 < L.Bs ? B - b0 : L.Bs;
         const u64 *xn = d_x + (size_t)b0 * in_cts * ctw; bool packed = in_form == CRC_NTTP;
-        if (in_form == CRC_COEFF) { RUN(k_ntt_ct(c, false, xn, buf, (size_t)Bn * in_cts, 2, false, st, nullptr, 0, 0, 0, 0)); xn = buf; packed = false; }
-        RUN(k_limb_conv1(c, xn, packed, Xr, (const signed char *)d_wl, Ys, out_form == CRC_NTTLC ? (signed char *)d_y : nullptr, B, b0,
+        if (in_form == CRC_COEFF) { RUN(k_ntt_ct(c, false, xn, L.buf, (size_t)Bn * in_cts, 2, false, st, nullptr, 0, 0, 0, 0)); xn = L.buf; packed = false; }
+        RUN(k_limb_conv1(c, xn, packed, L.Xr, (const signed char *)d_wl, L.Ys, out_form == CRC_NTTLC ? (signed char *)d_y : nullptr, B, b0,
             out_form != CRC_COEFF ? d_bias : nullptr,
                          Bn, xd, yd, xs, ys, xf, yf, nf, st));
         if (out_form == CRC_NTTLC) continue;
-        if (out_form == CRC_NTTL) return k_limb_result_to_limb(c, Ys, (signed char *)d_y, B, nf * P, st);     // (Bs == B)
-        RUN(k_limb_result_to_rows(c, Ys, d_y + (size_t)b0 * nf * P * ctw, (size_t)Bn * nf * P * 2, out_form == CRC_NTTP, st));
+        if (out_form == CRC_NTTL) return k_limb_result_to_limb(c, L.Ys, (signed char *)d_y, B, nf * P, st);     // (Bs == B)
+        RUN(k_limb_result_to_rows(c, L.Ys, d_y + (size_t)b0 * nf * P * ctw, (size_t)Bn * nf * P * 2, out_form == CRC_NTTP, st));
     }
     if (out_form == CRC_COEFF) RUN(k_ntt_ct(c, true, d_y, d_y, (size_t)B * nf * P, 2, false, st, d_bias, 1, (size_t)P, nf));
     return CRC_OK;
 }
+// Work of a layer on the limb GEMM: [slot-major result][limb form of a canonical or packed input][NTT copy of a coefficient-form input]
+struct LimbWork { u64 *Ys; signed char *Xl; u64 *buf; };
+static LimbWork limb_layout(const crc_ctx *c, int B, int zd, int xd, int yd, int nf, int P, int in_form, WorkArena &a)
+{
+    LimbWork L{};
+    L.Ys = a.take<u64>(k_limb_result_words(c, B, nf, P));
+    if (in_form != CRC_NTTL) L.Xl = a.take<signed char>(k_limb_tensor_bytes(c, B, zd, xd * yd));
+    if (in_form == CRC_COEFF) L.buf = a.take<u64>((size_t)B * zd * xd * yd * crc_ct_words(c, 2));
+    return L;
+}
 extern "C" size_t crc_conv2d_forms_work_bytes(const crc_ctx *c, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int in_form,
     int w_form, int out_form)
 {
-    if (w_form == CRC_NTTL1) {
-        if (!c || !conv_shape_ok(xd, yd, xs, ys, xf, yf)) return 0;
-        const int xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys + 1;
-        if (out_form == CRC_NTTLC && xo * yo == 1) out_form = CRC_NTTL;
-        const int Bs = conv1_sub_batch(c, B, xd, yd, xf, yf, nf, xo * yo, out_form);
-        size_t b = align256(k_limb_conv1_image_bytes(c, Bs, xd, yd, xf, yf, nf));
-        if (out_form != CRC_NTTLC) b += align256(8 * k_limb_result_words(c, Bs, nf, xo * yo));
-        if (in_form == CRC_COEFF) b += align256((size_t)Bs * xd * yd * crc_ct_words(c, 2) * 8);
-        return b + 256;
-    }
-    if (w_form != CRC_NTTL) return crc_conv2d_work_bytes(c, B, zd, xd, yd, xs, ys, xf, yf, nf, in_form);
     if (!c || !conv_shape_ok(xd, yd, xs, ys, xf, yf)) return 0;
-    (void)out_form;
-    const int xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys + 1;
-    size_t b = align256(8 * k_limb_result_words(c, B, nf, xo * yo));                                   // Ys
-    if (in_form != CRC_NTTL) b += align256(k_limb_tensor_bytes(c, B, zd, xd * yd));                      // Xl
-    if (in_form == CRC_COEFF) b += align256((size_t)B * zd * xd * yd * crc_ct_words(c, 2) * 8);          // NTT copy of the input
-    return b + 256;
+    const int P = ((xd - xf) / xs + 1) * ((yd - yf) / ys + 1);
+    WorkArena a;
+    if (w_form == CRC_NTTL1) limb1_layout(c, B, xd, yd, xf, yf, nf, P, in_form, out_form, a);
+    else if (w_form == CRC_NTTL) limb_layout(c, B, zd, xd, yd, nf, P, in_form, a);
+    else conv_layout(c, B, zd, xd, yd, xf, yf, P, in_form, a);
+    return a.bytes();
+}
+extern "C" size_t crc_conv2d_work_bytes(const crc_ctx *c, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int in_form)
+{
+    return crc_conv2d_forms_work_bytes(c, B, zd, xd, yd, xs, ys, xf, yf, nf, in_form, CRC_NTT, CRC_COEFF);
 }
 static int conv2d_limb(crc_ctx *c, const uint64_t *d_x, const void *d_wl, const uint64_t *d_bias, int B, int zd, int xd, int yd, int xs, int ys, int xf,
     int yf, int nf,
@@ -223,23 +238,21 @@ static int conv2d_limb(crc_ctx *c, const uint64_t *d_x, const void *d_wl, const 
 {
     if (!crc_limb_supported(c, zd, xf, yf)) return CRC_ERR_UNSUPPORTED;
     const int xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys + 1, P = xo * yo, in_cts = zd * xd * yd;
-    char *w = (char *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
-    u64 *Ys = (u64 *)w; w += align256(8 * k_limb_result_words(c, B, nf, P));
+    WorkArena a(d_work);
+    const LimbWork L = limb_layout(c, B, zd, xd, yd, nf, P, in_form, a);
     const signed char *xl = (const signed char *)d_x;
     if (in_form != CRC_NTTL) {
-        signed char *Xl = (signed char *)w; w += align256(k_limb_tensor_bytes(c, B, zd, xd * yd));
         const u64 *xn = d_x; bool packed = in_form == CRC_NTTP;
-        if (in_form == CRC_COEFF) { u64 *buf = (u64 *)w; RUN(k_ntt_ct(c, false, d_x, buf, (size_t)B * in_cts, 2, false, st, nullptr, 0, 0, 0, 0)); xn = buf;
-            packed = false; }
-        RUN(k_limb_pack_tensor(c, xn, Xl, B, zd, xd * yd, packed, st));
-        xl = Xl;
+        if (in_form == CRC_COEFF) { RUN(k_ntt_ct(c, false, d_x, L.buf, (size_t)B * in_cts, 2, false, st, nullptr, 0, 0, 0, 0)); xn = L.buf; packed = false; }
+        RUN(k_limb_pack_tensor(c, xn, L.Xl, B, zd, xd * yd, packed, st));
+        xl = L.Xl;
     }
     // bias joins in the NTT domain unless the result goes back to coefficient form (then add_plain(bias) rides on the inverse transform's store)
     if (out_form == CRC_NTTL && k_limb_direct_dense(P))         // hand-over to a dense layer (channels = (f, px, py) flattened), written by the kernel itself
-        return k_limb_mac(c, xl, (const signed char *)d_wl, Ys, (signed char *)d_y, d_bias, B, zd, xd, yd, xs, ys, xf, yf, nf, st);
-    RUN(k_limb_mac(c, xl, (const signed char *)d_wl, Ys, nullptr, out_form != CRC_COEFF ? d_bias : nullptr, B, zd, xd, yd, xs, ys, xf, yf, nf, st));
-    if (out_form == CRC_NTTL) return k_limb_result_to_limb(c, Ys, (signed char *)d_y, B, nf * P, st);     // ... or re-limbed from the slot-major result
-    RUN(k_limb_result_to_rows(c, Ys, d_y, (size_t)B * nf * P * 2, out_form == CRC_NTTP, st));
+        return k_limb_mac(c, xl, (const signed char *)d_wl, L.Ys, (signed char *)d_y, d_bias, B, zd, xd, yd, xs, ys, xf, yf, nf, st);
+    RUN(k_limb_mac(c, xl, (const signed char *)d_wl, L.Ys, nullptr, out_form != CRC_COEFF ? d_bias : nullptr, B, zd, xd, yd, xs, ys, xf, yf, nf, st));
+    if (out_form == CRC_NTTL) return k_limb_result_to_limb(c, L.Ys, (signed char *)d_y, B, nf * P, st);     // ... or re-limbed from the slot-major result
+    RUN(k_limb_result_to_rows(c, L.Ys, d_y, (size_t)B * nf * P * 2, out_form == CRC_NTTP, st));
     if (out_form == CRC_COEFF) RUN(k_ntt_ct(c, true, d_y, d_y, (size_t)B * nf * P, 2, false, st, d_bias, 1, (size_t)P, nf));
     return CRC_OK;
 }
@@ -268,22 +281,19 @@ extern "C" int crc_conv2d_forms(crc_ctx *c, const uint64_t *d_x, const uint64_t 
     if (B == 0) return CRC_OK;
     const int xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys + 1, P = xo * yo, T = zd * xf * yf, in_cts = zd * xd * yd;
     hipStream_t st = S(stream);
-    char *w = (char *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
-    int *xoff = (int *)w; w += align256(sizeof(int) * (size_t)P);
-    int *toff = (int *)w; w += align256(sizeof(int) * ((size_t)T + 8));
-    unsigned *toffw = (unsigned *)w; w += align256(sizeof(int) * ((size_t)T + 8));
-    RUN(k_conv_offsets(c, xoff, toff, toffw, P, T, in_cts, xd, yd, xs, ys, xf, yf, yo, st));
+    WorkArena a(d_work);
+    const ConvWork L = conv_layout(c, B, zd, xd, yd, xf, yf, P, in_form, a);
+    RUN(k_conv_offsets(c, L.xoff, L.toff, L.toffw, P, T, in_cts, xd, yd, xs, ys, xf, yf, yo, st));
     const u64 *xn = d_x;
     int xp = in_form == CRC_NTTP;
     if (in_form == CRC_COEFF) {                   // transform_input_to_ntt, convolutionalLayer.cpp:95-148 (out of place: x is const)
-        u64 *buf = (u64 *)w;
         int maxbits = 0; for (int i = 0; i < c->k; i++) if ((int)c->tabs[i].m.bits > maxbits) maxbits = c->tabs[i].m.bits;
         xp = maxbits <= 55;                       // the private copy goes straight into the MAC kernels' operand form
-        RUN(k_ntt_ct(c, false, d_x, buf, (size_t)B * in_cts, 2, false, st, nullptr, 0, 0, 0, xp));
-        xn = buf;
+        RUN(k_ntt_ct(c, false, d_x, L.buf, (size_t)B * in_cts, 2, false, st, nullptr, 0, 0, 0, xp));
+        xn = L.buf;
     }
     // sum of products in the NTT domain; bias joins here when the output stays NTT-resident
-    RUN(k_mac2(c, xn, d_w, d_y, xoff, toff, B, P, nf, T, in_cts, out_form != CRC_COEFF ? d_bias : nullptr, xd, yd, xf, yf, toffw, st, xp, w_form == CRC_NTTP,
+    RUN(k_mac2(c, xn, d_w, d_y, L.xoff, L.toff, B, P, nf, T, in_cts, out_form != CRC_COEFF ? d_bias : nullptr, xd, yd, xf, yf, L.toffw, st, xp, w_form == CRC_NTTP,
         out_form == CRC_NTTP));
     if (out_form == CRC_COEFF)                    // one inverse NTT per output ciphertext, add_plain(bias) fused into its store
         RUN(k_ntt_ct(c, true, d_y, d_y, (size_t)B * nf * P, 2, false, st, d_bias, 1, (size_t)P, nf));
@@ -441,42 +451,60 @@ static size_t square_chunk(const crc_ctx *c)
     return nk <= 32768 ? 1024 : nk <= 65536 ? 512 : nk <= 131072 ? 256 : 128;
 }
 
-extern "C" size_t crc_square_relin_work_bytes(const crc_ctx *c, size_t count, int dbc)
+// Work of the activation family (the square or the multiply, then the key switch; flat or pooled; with or without ring-linear terms), sized for one internal pass:
+// [xh: NTT copy of a coefficient-form input][s: relin(x^2) of the degree-3 activation][packed keys (filled by pass 0)][size-3 products][scratch of the product, then
+// of the key switch].  A pass takes `step` whole channel planes of pin ciphertexts in, pout out (a pooling window never leaves its plane); flat calls have 1 x 1 planes
+struct ActWork { u64 *xh, *s, *kp, *y3, *rest; size_t step; };
+enum { ACT_XH = 1, ACT_S = 2, ACT_MULTIPLY = 4 };      // which of xh and s a call has, and whether its product is the multiply's (k_multiply_work_words)
+static ActWork act_layout(const crc_ctx *c, size_t planes, size_t pin, size_t pout, int dbc, int regions, WorkArena &a)
 {
-    if (!c || !dbc_ok(dbc)) return 0;
-    const size_t kSquareChunk = square_chunk(c); const size_t ch = count < kSquareChunk ? count : kSquareChunk;
-    const size_t sq = k_square_work_words(c, ch), rl = k_relin_work_words(c, ch, dbc);
-    // [packed keys][size-3 intermediates of one pass][scratch of the square, then of the relinearisation]
-    return 8 * (k_relin_keys_words(c, dbc) + (sq > rl ? sq : rl) + ch * crc_ct_words(c, 3)) + 256;
+    ActWork L{};
+    L.step = square_chunk(c) / pin ? square_chunk(c) / pin : 1;
+    const size_t pp = planes < L.step ? planes : L.step, cin = pp * pin, cout = pp * pout;
+    const size_t pr = regions & ACT_MULTIPLY ? k_multiply_work_words(c, cin) : k_square_work_words(c, cin), rl = k_relin_work_words(c, cout, dbc);
+    if (regions & ACT_XH) L.xh = a.take<u64>(cin * crc_ct_words(c, 2));
+    if (regions & ACT_S) L.s = a.take<u64>(cin * crc_ct_words(c, 2));
+    L.kp = a.take<u64>(k_relin_keys_words(c, dbc));
+    L.y3 = a.take<u64>(cin * crc_ct_words(c, 3));
+    L.rest = a.take<u64>(pr > rl ? pr : rl);
+    return L;
 }
-extern "C" size_t crc_encrypt_dev_work_bytes(const crc_ctx *c, size_t count) { return c ? 8 * k_encrypt_work_words(c, count) + 256 : 0; }
+static size_t act_bytes(const crc_ctx *c, size_t planes, size_t pin, size_t pout, int dbc, int regions)
+{
+    WorkArena a;
+    act_layout(c, planes, pin, pout, dbc, regions, a);
+    return a.bytes();
+}
+static inline size_t pass_len(size_t count, size_t o, size_t step) { return count - o < step ? count - o : step; }      // of the internal pass that starts at o
+// a coefficient-form pass of ch ciphertexts, copied into work space and transformed
+static int ntt_copy(crc_ctx *c, const u64 *x, size_t ch, u64 *xh, void *stream)
+{
+    HIPCHK(hipMemcpyAsync(xh, x, 8 * ch * crc_ct_words(c, 2), hipMemcpyDeviceToDevice, S(stream)));
+    return crc_ntt_fwd(c, xh, ch, 2, stream);
+}
+extern "C" size_t crc_square_relin_work_bytes(const crc_ctx *c, size_t count, int dbc) { return c && dbc_ok(dbc) ? act_bytes(c, count, 1, 1, dbc, 0) : 0; }
+extern "C" size_t crc_encrypt_dev_work_bytes(const crc_ctx *c, size_t count) { return c ? work_bytes(k_encrypt_work_words(c, count)) : 0; }
 extern "C" int crc_encrypt_dev_key(crc_ctx *c, const uint64_t *d_pk, const uint64_t *d_plain, size_t count, const uint8_t *key, uint64_t stream_base,
                                    uint64_t *d_ct, void *d_work, void *stream)
 {
-    CHECK_CTX(c); if (!d_pk || !d_plain || !d_ct || !d_work || !key) return CRC_ERR_INVALID_ARGUMENT;
-    u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
-    return k_encrypt(c, d_pk, d_plain, count, chacha_load_key(key), stream_base, d_ct, w, S(stream));
+    return crc_encrypt_dev_key_forms(c, d_pk, d_plain, count, key, stream_base, CRC_COEFF, d_ct, d_work, stream);
 }
 extern "C" int crc_encrypt_dev(crc_ctx *c, const uint64_t *d_pk, const uint64_t *d_plain, size_t count, uint64_t seed, uint64_t *d_ct, void *d_work,
     void *stream)
 {
-    CHECK_CTX(c); if (!d_pk || !d_plain || !d_ct || !d_work) return CRC_ERR_INVALID_ARGUMENT;
-    u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
-    return k_encrypt(c, d_pk, d_plain, count, chacha_seed_key(seed), 0, d_ct, w, S(stream));
+    return crc_encrypt_dev_forms(c, d_pk, d_plain, count, seed, CRC_COEFF, d_ct, d_work, stream);
 }
 extern "C" int crc_encrypt_dev_key_forms(crc_ctx *c, const uint64_t *d_pk, const uint64_t *d_plain, size_t count, const uint8_t *key, uint64_t stream_base,
                                          int out_form, uint64_t *d_ct, void *d_work, void *stream)
 {
     CHECK_CTX(c); if (!d_pk || !d_plain || !d_ct || !d_work || !key || (out_form != CRC_COEFF && out_form != CRC_NTT)) return CRC_ERR_INVALID_ARGUMENT;
-    u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
-    return k_encrypt(c, d_pk, d_plain, count, chacha_load_key(key), stream_base, d_ct, w, S(stream), out_form == CRC_NTT);
+    return k_encrypt(c, d_pk, d_plain, count, chacha_load_key(key), stream_base, d_ct, work_base(d_work), S(stream), out_form == CRC_NTT);
 }
 extern "C" int crc_encrypt_dev_forms(crc_ctx *c, const uint64_t *d_pk, const uint64_t *d_plain, size_t count, uint64_t seed, int out_form, uint64_t *d_ct,
                                      void *d_work, void *stream)
 {
     CHECK_CTX(c); if (!d_pk || !d_plain || !d_ct || !d_work || (out_form != CRC_COEFF && out_form != CRC_NTT)) return CRC_ERR_INVALID_ARGUMENT;
-    u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
-    return k_encrypt(c, d_pk, d_plain, count, chacha_seed_key(seed), 0, d_ct, w, S(stream), out_form == CRC_NTT);
+    return k_encrypt(c, d_pk, d_plain, count, chacha_seed_key(seed), 0, d_ct, work_base(d_work), S(stream), out_form == CRC_NTT);
 }
 extern "C" void crc_encrypt_dev_noise_thresholds(uint64_t *h_out19) { if (h_out19) k_encrypt_cdt(h_out19); }
 
@@ -484,27 +512,25 @@ extern "C" void crc_encrypt_dev_noise_thresholds(uint64_t *h_out19) { if (h_out1
 static bool ct_form_ok(int f) { return f == CRC_COEFF || f == CRC_NTT; }
 extern "C" size_t crc_decrypt_dev_work_bytes(const crc_ctx *c, size_t count, int size, int in_form)
 {
-    return c && ct_form_ok(in_form) ? 8 * k_decrypt_work_words(c, count, size, in_form == CRC_NTT) + 256 : 0;
+    return c && ct_form_ok(in_form) ? work_bytes(k_decrypt_work_words(c, count, size, in_form == CRC_NTT)) : 0;
 }
 extern "C" int crc_decrypt_dev(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_ct, size_t count, int size, int in_form, uint64_t *d_plain, void *d_work,
                                void *stream)
 {
     CHECK_CTX(c); if (!d_sk || !d_ct || !d_plain || !d_work || !ct_form_ok(in_form)) return CRC_ERR_INVALID_ARGUMENT;
-    u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
-    return k_decrypt(c, d_sk, d_ct, count, size, in_form == CRC_NTT, d_plain, w, S(stream));
+    return k_decrypt(c, d_sk, d_ct, count, size, in_form == CRC_NTT, d_plain, work_base(d_work), S(stream));
 }
 // Decryptor::invariant_noise_budget of every ciphertext of a tensor (kernels_budget.hip)
 extern "C" size_t crc_noise_budget_dev_work_bytes(const crc_ctx *c, size_t count, int size, int in_form)
 {
-    return c && ct_form_ok(in_form) && (size == 2 || size == 3) ? 8 * k_decrypt_work_words(c, count, size, in_form == CRC_NTT) + 256 : 0;
+    return c && ct_form_ok(in_form) && (size == 2 || size == 3) ? work_bytes(k_decrypt_work_words(c, count, size, in_form == CRC_NTT)) : 0;
 }
 extern "C" int crc_noise_budget_dev(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_ct, size_t count, int size, int in_form, int32_t *d_bits, int32_t *d_min,
                                     void *d_work, void *stream)
 {
     if (!d_sk || !d_ct || !d_bits || !d_work || !ct_form_ok(in_form) || size < 2 || size > 3) return CRC_ERR_INVALID_ARGUMENT;
     CHECK_CTX(c);
-    u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
-    return k_noise_budget(c, d_sk, d_ct, count, size, in_form == CRC_NTT, d_bits, d_min, w, S(stream));
+    return k_noise_budget(c, d_sk, d_ct, count, size, in_form == CRC_NTT, d_bits, d_min, work_base(d_work), S(stream));
 }
 extern "C" int crc_budget_bits_host(const crc_ctx *c, const uint64_t *h_v, size_t count, int32_t *h_bits)
 {
@@ -526,24 +552,39 @@ extern "C" int crc_encode_dev_f64(crc_ctx *c, const double *d_values, size_t cou
     CHECK_CTX(c); if (!d_values || !d_plain) return CRC_ERR_INVALID_ARGUMENT;
     return k_fra_encode(c, d_values, 1, count, d_plain, nullptr, S(stream));
 }
-// work of a refresh: [compact plaintexts [count][96]][dense plaintexts [count][n]: coefficient-form results only][the decryptor's rows, then the encryptor's samples]
-extern "C" size_t crc_refresh_dev_work_bytes(const crc_ctx *c, size_t count, int in_form)
+// Work of a refresh: [compact plaintexts [count][96]][dense plaintexts [count][n]: the public-key refresh's coefficient-form results only][the decryptor's
+// rows, then the encryptor's (sym: the secret-key encryptor's) samples]
+struct RefreshWork { u64 *compact, *dense, *w; };
+static RefreshWork refresh_layout(const crc_ctx *c, size_t count, int in_form, bool sym, WorkArena &a)
+{
+    const size_t dec = k_decrypt_work_words(c, count, 2, in_form == CRC_NTT), enc = sym ? k_encrypt_sym_work_words(c, count) : k_encrypt_work_words(c, count);
+    RefreshWork L{};
+    L.compact = a.take<u64>(count * (size_t)CRC_PLAIN_COMPACT_WORDS);
+    if (!sym) L.dense = a.take<u64>(count * (size_t)c->n);
+    L.w = a.take<u64>(dec > enc ? dec : enc);
+    return L;
+}
+static size_t refresh_bytes(const crc_ctx *c, size_t count, int in_form, bool sym)
 {
     if (!c || !ct_form_ok(in_form)) return 0;
-    const size_t dec = k_decrypt_work_words(c, count, 2, in_form == CRC_NTT), enc = k_encrypt_work_words(c, count);
-    return 8 * (count * ((size_t)c->n + CRC_PLAIN_COMPACT_WORDS) + (dec > enc ? dec : enc)) + 256;
+    WorkArena a;
+    refresh_layout(c, count, in_form, sym, a);
+    return a.bytes();
 }
+extern "C" size_t crc_refresh_dev_work_bytes(const crc_ctx *c, size_t count, int in_form) { return refresh_bytes(c, count, in_form, false); }
 static int refresh_impl(crc_ctx *c, const u64 *d_sk, const u64 *d_pk, const u64 *d_in, size_t count, int in_form, const ChaChaKey &key, u64 stream_base,
                         int out_form, u64 *d_out, float *d_vals, void *d_work, hipStream_t st)
 {
-    u64 *compact = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255), *dense = compact + count * (size_t)CRC_PLAIN_COMPACT_WORDS;
-    u64 *w = dense + count * (size_t)c->n;
+    WorkArena a(d_work);
+    const RefreshWork L = refresh_layout(c, count, in_form, !d_pk, a);
     // decrypt -> decode -> float -> encode leaves the 96-word compact plaintexts (only the 96 coefficients the decoder reads are ever scaled) ...
-    RUN(k_decrypt_recode(c, d_sk, d_in, count, in_form == CRC_NTT, compact, d_vals, w, st));
-    // ... which the NTT-form encryptor reads as they are; the coefficient-form one adds Delta m from dense rows
-    if (out_form == CRC_NTT) return k_encrypt(c, d_pk, compact, count, key, stream_base, d_out, w, st, true, true);
-    RUN(k_plain_expand(c, compact, count, dense, st));
-    return k_encrypt(c, d_pk, dense, count, key, stream_base, d_out, w, st, false);
+    RUN(k_decrypt_recode(c, d_sk, d_in, count, in_form == CRC_NTT, L.compact, d_vals, L.w, st));
+    // ... which the secret-key encryptor (d_pk null) reads for either result form (the NTT form is its definition) ...
+    if (!d_pk) return k_encrypt_sym(c, d_sk, L.compact, count, key, stream_base, d_out, L.w, st, out_form == CRC_NTT, true);
+    // ... and the NTT-form public-key encryptor reads as they are; the coefficient-form one adds Delta m from dense rows
+    if (out_form == CRC_NTT) return k_encrypt(c, d_pk, L.compact, count, key, stream_base, d_out, L.w, st, true, true);
+    RUN(k_plain_expand(c, L.compact, count, L.dense, st));
+    return k_encrypt(c, d_pk, L.dense, count, key, stream_base, d_out, L.w, st, false);
 }
 extern "C" int crc_refresh_dev(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_pk, const uint64_t *d_ct_in, size_t count, int in_form, uint64_t seed,
                                int out_form, uint64_t *d_ct_out, float *d_values_out, void *d_work, void *stream)
@@ -559,51 +600,35 @@ extern "C" int crc_refresh_dev_key(crc_ctx *c, const uint64_t *d_sk, const uint6
     return refresh_impl(c, d_sk, d_pk, d_ct_in, count, in_form, chacha_load_key(key), stream_base, out_form, d_ct_out, d_values_out, d_work, S(stream));
 }
 // ---- encryption under the secret key and the refresh that uses it (kernels_client.hip: k_encrypt_sym) ----
-extern "C" size_t crc_encrypt_sym_dev_work_bytes(const crc_ctx *c, size_t count) { return c ? 8 * k_encrypt_sym_work_words(c, count) + 256 : 0; }
+extern "C" size_t crc_encrypt_sym_dev_work_bytes(const crc_ctx *c, size_t count) { return c ? work_bytes(k_encrypt_sym_work_words(c, count)) : 0; }
 extern "C" int crc_encrypt_sym_dev_key_forms(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_plain, size_t count, const uint8_t *key, uint64_t stream_base,
                                              int out_form, uint64_t *d_ct, void *d_work, void *stream)
 {
     if (!d_sk || !d_plain || !d_ct || !d_work || !key || !ct_form_ok(out_form)) return CRC_ERR_INVALID_ARGUMENT;
     CHECK_CTX(c);
-    u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
-    return k_encrypt_sym(c, d_sk, d_plain, count, chacha_load_key(key), stream_base, d_ct, w, S(stream), out_form == CRC_NTT, false);
+    return k_encrypt_sym(c, d_sk, d_plain, count, chacha_load_key(key), stream_base, d_ct, work_base(d_work), S(stream), out_form == CRC_NTT, false);
 }
 extern "C" int crc_encrypt_sym_dev_forms(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_plain, size_t count, uint64_t seed, int out_form, uint64_t *d_ct,
                                          void *d_work, void *stream)
 {
     if (!d_sk || !d_plain || !d_ct || !d_work || !ct_form_ok(out_form)) return CRC_ERR_INVALID_ARGUMENT;
     CHECK_CTX(c);
-    u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
-    return k_encrypt_sym(c, d_sk, d_plain, count, chacha_seed_key(seed), 0, d_ct, w, S(stream), out_form == CRC_NTT, false);
+    return k_encrypt_sym(c, d_sk, d_plain, count, chacha_seed_key(seed), 0, d_ct, work_base(d_work), S(stream), out_form == CRC_NTT, false);
 }
-// work of a secret-key refresh: [compact plaintexts [count][96]][the decryptor's rows, then the encryptor's]
-extern "C" size_t crc_refresh_sym_dev_work_bytes(const crc_ctx *c, size_t count, int in_form)
-{
-    if (!c || !ct_form_ok(in_form)) return 0;
-    const size_t dec = k_decrypt_work_words(c, count, 2, in_form == CRC_NTT), enc = k_encrypt_sym_work_words(c, count);
-    return 8 * (count * (size_t)CRC_PLAIN_COMPACT_WORDS + (dec > enc ? dec : enc)) + 256;
-}
-static int refresh_sym_impl(crc_ctx *c, const u64 *d_sk, const u64 *d_in, size_t count, int in_form, const ChaChaKey &key, u64 stream_base, int out_form,
-                            u64 *d_out, float *d_vals, void *d_work, hipStream_t st)
-{
-    u64 *compact = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255), *w = compact + count * (size_t)CRC_PLAIN_COMPACT_WORDS;
-    // the front end of crc_refresh_dev; the encryptor reads the compact plaintexts for either result form (the NTT form is its definition)
-    RUN(k_decrypt_recode(c, d_sk, d_in, count, in_form == CRC_NTT, compact, d_vals, w, st));
-    return k_encrypt_sym(c, d_sk, compact, count, key, stream_base, d_out, w, st, out_form == CRC_NTT, true);
-}
+extern "C" size_t crc_refresh_sym_dev_work_bytes(const crc_ctx *c, size_t count, int in_form) { return refresh_bytes(c, count, in_form, true); }
 extern "C" int crc_refresh_sym_dev(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_ct_in, size_t count, int in_form, uint64_t seed, int out_form,
                                    uint64_t *d_ct_out, float *d_values_out, void *d_work, void *stream)
 {
     if (!d_sk || !d_ct_in || !d_ct_out || !d_work || !ct_form_ok(in_form) || !ct_form_ok(out_form)) return CRC_ERR_INVALID_ARGUMENT;
     CHECK_CTX(c);
-    return refresh_sym_impl(c, d_sk, d_ct_in, count, in_form, chacha_seed_key(seed), 0, out_form, d_ct_out, d_values_out, d_work, S(stream));
+    return refresh_impl(c, d_sk, nullptr, d_ct_in, count, in_form, chacha_seed_key(seed), 0, out_form, d_ct_out, d_values_out, d_work, S(stream));
 }
 extern "C" int crc_refresh_sym_dev_key(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_ct_in, size_t count, int in_form, const uint8_t *key,
                                        uint64_t stream_base, int out_form, uint64_t *d_ct_out, float *d_values_out, void *d_work, void *stream)
 {
     if (!d_sk || !d_ct_in || !d_ct_out || !d_work || !key || !ct_form_ok(in_form) || !ct_form_ok(out_form)) return CRC_ERR_INVALID_ARGUMENT;
     CHECK_CTX(c);
-    return refresh_sym_impl(c, d_sk, d_ct_in, count, in_form, chacha_load_key(key), stream_base, out_form, d_ct_out, d_values_out, d_work, S(stream));
+    return refresh_impl(c, d_sk, nullptr, d_ct_in, count, in_form, chacha_load_key(key), stream_base, out_form, d_ct_out, d_values_out, d_work, S(stream));
 }
 // ---- seeded secret-key ciphertexts: the packed c0 rows and a public seed -> ordinary ciphertexts (kernels_client.hip: k_seeded_expand) ----
 extern "C" int crc_seeded_expand_dev(crc_ctx *c, const uint64_t *d_c0, size_t count, const uint8_t *seed, uint64_t stream_base, int out_form, uint64_t *d_ct,
@@ -648,14 +673,14 @@ extern "C" int crc_encrypt_sym_seeded_dev(crc_ctx *c, const uint64_t *d_sk, cons
     return k_encrypt_sym_seeded(c, d_sk, d_plain, count, chacha_seed_key(seed), chacha_seed_key(~seed), 0, d_c0, S(stream), false);
 }
 // pixels in, packed rows out: work = [compact plaintexts [count][96]]
-extern "C" size_t crc_encrypt_f32_seeded_dev_work_bytes(const crc_ctx *c, size_t count) { return c ? 8 * count * (size_t)CRC_PLAIN_COMPACT_WORDS + 256 : 0; }
+extern "C" size_t crc_encrypt_f32_seeded_dev_work_bytes(const crc_ctx *c, size_t count) { return c ? work_bytes(count * (size_t)CRC_PLAIN_COMPACT_WORDS) : 0; }
 static int encrypt_f32_seeded_impl(crc_ctx *c, const u64 *d_sk, const float *d_values, size_t count, const ChaChaKey &key, const ChaChaKey &seed, u64 stream_base,
                                    u64 *d_c0, void *d_work, hipStream_t st)
 {
     if (count == 0) return CRC_OK;
     if (c->n <= CRC_PLAIN_COMPACT_WORDS) return CRC_ERR_INVALID_ARGUMENT;
     if (count > (size_t)-1 / (16 * (size_t)CRC_PLAIN_COMPACT_WORDS)) return CRC_ERR_INVALID_ARGUMENT;
-    u64 *compact = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
+    u64 *compact = work_base(d_work);
     // the encoder writes the compact plaintexts while other workgroups still read floats: the two must not overlap either
     { const uintptr_t v0 = (uintptr_t)d_values, v1 = v0 + 4 * count, w0 = (uintptr_t)compact, w1 = w0 + 8 * count * (size_t)CRC_PLAIN_COMPACT_WORDS;
       if (v0 < w1 && w0 < v1) return CRC_ERR_INVALID_ARGUMENT; }
@@ -681,10 +706,9 @@ extern "C" int crc_encrypt_f32_seeded_dev(crc_ctx *c, const uint64_t *d_sk, cons
 extern "C" int crc_square(crc_ctx *c, const uint64_t *d_x, size_t count, uint64_t *d_y3, void *d_work, void *stream)
 {
     CHECK_CTX(c); if (!d_x || !d_y3 || !d_work) return CRC_ERR_INVALID_ARGUMENT;
-    u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
-    const size_t kSquareChunk = square_chunk(c);
-    for (size_t o = 0; o < count; o += kSquareChunk) {
-        const size_t ch = count - o < kSquareChunk ? count - o : kSquareChunk;
+    u64 *w = work_base(d_work);
+    for (size_t o = 0, step = square_chunk(c); o < count; o += step) {
+        const size_t ch = pass_len(count, o, step);
         RUN(k_square(c, d_x + o * crc_ct_words(c, 2), ch, d_y3 + o * crc_ct_words(c, 3), w, S(stream)));
     }
     return CRC_OK;
@@ -692,10 +716,9 @@ extern "C" int crc_square(crc_ctx *c, const uint64_t *d_x, size_t count, uint64_
 extern "C" int crc_relinearize(crc_ctx *c, const uint64_t *d_x3, size_t count, const uint64_t *d_evk, int dbc, uint64_t *d_y, void *d_work, void *stream)
 {
     CHECK_CTX(c); if (!d_x3 || !d_y || !d_evk || !d_work || !dbc_ok(dbc)) return CRC_ERR_INVALID_ARGUMENT;
-    u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
-    const size_t kSquareChunk = square_chunk(c);
-    for (size_t o = 0; o < count; o += kSquareChunk) {
-        const size_t ch = count - o < kSquareChunk ? count - o : kSquareChunk;
+    u64 *w = work_base(d_work);
+    for (size_t o = 0, step = square_chunk(c); o < count; o += step) {
+        const size_t ch = pass_len(count, o, step);
         RUN(k_relinearize(c, d_x3 + o * crc_ct_words(c, 3), ch, d_evk, dbc, d_y + o * crc_ct_words(c, 2), w + k_relin_keys_words(c, dbc), w, S(stream), false,
             false, o != 0));
     }
@@ -705,32 +728,29 @@ extern "C" int crc_square_relin_forms(crc_ctx *c, const uint64_t *d_x, int in_fo
                                       void *d_work, void *stream)
 {
     CHECK_CTX(c); if (!d_x || !d_y || !d_evk || !d_work || !form_ok(in_form) || !form_ok(out_form) || !dbc_ok(dbc)) return CRC_ERR_INVALID_ARGUMENT;
-    u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
-    const size_t kSquareChunk = square_chunk(c);
-    const size_t ch0 = count < kSquareChunk ? count : kSquareChunk;
-    for (size_t o = 0; o < count; o += kSquareChunk) {
-        const size_t ch = count - o < kSquareChunk ? count - o : kSquareChunk;
-        // [packed keys (filled by pass 0)][size-3 intermediates][scratch]
-        u64 *kp = w, *y3 = kp + k_relin_keys_words(c, dbc), *rest = y3 + ch0 * crc_ct_words(c, 3);
-        RUN(k_square(c, d_x + o * crc_ct_words(c, 2), ch, y3, rest, S(stream), in_form == CRC_NTT, true));
-        RUN(k_relinearize(c, y3, ch, d_evk, dbc, d_y + o * crc_ct_words(c, 2), rest, kp, S(stream), out_form == CRC_NTT, true, o != 0));
+    WorkArena a(d_work);
+    const ActWork L = act_layout(c, count, 1, 1, dbc, 0, a);
+    for (size_t o = 0; o < count; o += L.step) {
+        const size_t ch = pass_len(count, o, L.step);
+        RUN(k_square(c, d_x + o * crc_ct_words(c, 2), ch, L.y3, L.rest, S(stream), in_form == CRC_NTT, true));
+        RUN(k_relinearize(c, L.y3, ch, d_evk, dbc, d_y + o * crc_ct_words(c, 2), L.rest, L.kp, S(stream), out_form == CRC_NTT, true, o != 0));
     }
     return CRC_OK;
 }
 // Square + relinearise + sum pooling as ONE key switch per pooled ciphertext (kernels_relin64.hip: relin_digits_pool_f64_kernel).  Internal passes take whole
-// channel planes (a window never leaves its plane): [packed keys][size-3 squares of a pass][scratch]
-static size_t sqpool_planes(const crc_ctx *c, int xd, int yd) { const size_t per = (size_t)xd * yd, ch = square_chunk(c); return ch / per ? ch / per : 1; }
+// channel planes (act_layout)
 extern "C" int crc_square_pool_relin_supported(const crc_ctx *c, int dbc, int xf, int yf)
 {
     return c && dbc_ok(dbc) && c->tune.sq_path != 1 && c->tune.relin_path != 1 && k_relin64_pool_supported(c, dbc, xf * yf) ? 1 : 0;
 }
-extern "C" size_t crc_square_pool_relin_work_bytes(const crc_ctx *c, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int dbc)
+static size_t pool_act_bytes(const crc_ctx *c, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int dbc, int regions)
 {
     if (!c || xd < xf || yd < yf || xs < 1 || ys < 1 || !dbc_ok(dbc)) return 0;
-    const size_t planes = (size_t)B * zd, pp = planes < sqpool_planes(c, xd, yd) ? planes : sqpool_planes(c, xd, yd);
-    const size_t xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys + 1, cin = pp * xd * yd, cout = pp * xo * yo;
-    const size_t sq = k_square_work_words(c, cin), rl = k_relin_work_words(c, cout, dbc);
-    return 8 * (k_relin_keys_words(c, dbc) + cin * crc_ct_words(c, 3) + (sq > rl ? sq : rl)) + 256;
+    return act_bytes(c, (size_t)B * zd, (size_t)xd * yd, (size_t)((xd - xf) / xs + 1) * ((yd - yf) / ys + 1), dbc, regions);
+}
+extern "C" size_t crc_square_pool_relin_work_bytes(const crc_ctx *c, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int dbc)
+{
+    return pool_act_bytes(c, B, zd, xd, yd, xs, ys, xf, yf, dbc, 0);
 }
 extern "C" int crc_square_pool_relin_forms(crc_ctx *c, const uint64_t *d_x, int in_form, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf,
                                            const uint64_t *d_evk, int dbc, const uint64_t *d_div_ntt, uint64_t *d_y, int out_form, void *d_work, void *stream)
@@ -739,17 +759,16 @@ extern "C" int crc_square_pool_relin_forms(crc_ctx *c, const uint64_t *d_x, int 
     if (d_div_ntt && out_form != CRC_NTT) return CRC_ERR_INVALID_ARGUMENT;           // the divisor multiplies slot-wise
     if (B < 0 || zd < 1 || xd < xf || yd < yf || xs < 1 || ys < 1 || xf < 1 || yf < 1) return CRC_ERR_INVALID_ARGUMENT;
     if (!crc_square_pool_relin_supported(c, dbc, xf, yf)) return CRC_ERR_UNSUPPORTED;
-    u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
     const PoolGeom pg{xd, yd, xs, ys, xf, yf, (xd - xf) / xs + 1, (yd - yf) / ys + 1};
-    const size_t planes = (size_t)B * zd, step = sqpool_planes(c, xd, yd), pp0 = planes < step ? planes : step;
-    const size_t pin = (size_t)xd * yd, pout = (size_t)pg.xo * pg.yo;
-    u64 *kp = w, *y3 = kp + k_relin_keys_words(c, dbc), *rest = y3 + pp0 * pin * crc_ct_words(c, 3);
-    for (size_t o = 0; o < planes; o += step) {
-        const size_t pp = planes - o < step ? planes - o : step, cin = pp * pin, cout = pp * pout;
-        RUN(k_square(c, d_x + o * pin * crc_ct_words(c, 2), cin, y3, rest, S(stream), in_form == CRC_NTT, true));
-        if (o == 0) RUN(k_relin64_prepare_keys(c, d_evk, dbc, kp, rest, S(stream)));
+    const size_t planes = (size_t)B * zd, pin = (size_t)xd * yd, pout = (size_t)pg.xo * pg.yo;
+    WorkArena a(d_work);
+    const ActWork L = act_layout(c, planes, pin, pout, dbc, 0, a);
+    for (size_t o = 0; o < planes; o += L.step) {
+        const size_t pp = pass_len(planes, o, L.step), cin = pp * pin, cout = pp * pout;
+        RUN(k_square(c, d_x + o * pin * crc_ct_words(c, 2), cin, L.y3, L.rest, S(stream), in_form == CRC_NTT, true));
+        if (o == 0) RUN(k_relin64_prepare_keys(c, d_evk, dbc, L.kp, L.rest, S(stream)));
         // (the (c0, c1) of a window are added up where the key switch's result meets them: relin_inv_crt_kernel)
-        RUN(k_relinearize64(c, y3, 3, 2, y3, 3, cout, dbc, d_y + o * pout * crc_ct_words(c, 2), rest, kp, S(stream), out_form == CRC_NTT, &pg, d_div_ntt));
+        RUN(k_relinearize64(c, L.y3, 3, 2, L.y3, 3, cout, dbc, d_y + o * pout * crc_ct_words(c, 2), L.rest, L.kp, S(stream), out_form == CRC_NTT, &pg, d_div_ntt));
     }
     return CRC_OK;
 }
@@ -763,12 +782,7 @@ static bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t b
     const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
     return a0 < b0 + bbytes && b0 < a0 + abytes;
 }
-extern "C" size_t crc_poly2_relin_work_bytes(const crc_ctx *c, size_t count, int dbc)
-{
-    if (!c || !dbc_ok(dbc)) return 0;
-    const size_t chunk = square_chunk(c), ch = count < chunk ? count : chunk;
-    return crc_square_relin_work_bytes(c, count, dbc) + 8 * ch * crc_ct_words(c, 2) + 256;
-}
+extern "C" size_t crc_poly2_relin_work_bytes(const crc_ctx *c, size_t count, int dbc) { return c && dbc_ok(dbc) ? act_bytes(c, count, 1, 1, dbc, ACT_XH) : 0; }
 extern "C" int crc_poly2_relin_forms(crc_ctx *c, const uint64_t *d_x, int in_form, size_t count, const uint64_t *d_evk, int dbc, const uint64_t *d_p2_ntt,
                                      const uint64_t *d_p1_ntt, const uint64_t *d_p0_ntt, uint64_t *d_y, int out_form, void *d_work, void *stream)
 {
@@ -777,25 +791,18 @@ extern "C" int crc_poly2_relin_forms(crc_ctx *c, const uint64_t *d_x, int in_for
     const size_t ctw = crc_ct_words(c, 2);
     // the P1 term reads the NTT-form input after the result's rows are written: the two tensors must not share memory then
     if (d_p1_ntt && in_form == CRC_NTT && ranges_overlap(d_x, 8 * count * ctw, d_y, 8 * count * ctw)) return CRC_ERR_INVALID_ARGUMENT;
-    u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
-    const size_t kSquareChunk = square_chunk(c);
-    const size_t ch0 = count < kSquareChunk ? count : kSquareChunk;
     const bool own_xh = d_p1_ntt && in_form == CRC_COEFF;
-    u64 *xh_w = w; if (own_xh) w += (ch0 * ctw + 31) & ~(size_t)31;
-    for (size_t o = 0; o < count; o += kSquareChunk) {
-        const size_t ch = count - o < kSquareChunk ? count - o : kSquareChunk;
-        u64 *kp = w, *y3 = kp + k_relin_keys_words(c, dbc), *rest = y3 + ch0 * crc_ct_words(c, 3);
+    WorkArena a(d_work);
+    const ActWork L = act_layout(c, count, 1, 1, dbc, own_xh ? ACT_XH : 0, a);
+    for (size_t o = 0; o < count; o += L.step) {
+        const size_t ch = pass_len(count, o, L.step);
         const u64 *xin = d_x + o * ctw;
-        if (own_xh) {
-            HIPCHK(hipMemcpyAsync(xh_w, xin, 8 * ch * ctw, hipMemcpyDeviceToDevice, S(stream)));
-            RUN(crc_ntt_fwd(c, xh_w, ch, 2, stream));
-            xin = xh_w;
-        }
+        if (own_xh) { RUN(ntt_copy(c, xin, ch, L.xh, stream)); xin = L.xh; }
         u64 *yo = d_y + o * ctw;
-        RUN(k_square(c, xin, ch, y3, rest, S(stream), own_xh || in_form == CRC_NTT, true));
+        RUN(k_square(c, xin, ch, L.y3, L.rest, S(stream), own_xh || in_form == CRC_NTT, true));
         const PolyTail pt{xin, d_p1_ntt, d_p0_ntt};
         bool fused = false;
-        RUN(k_relinearize(c, y3, ch, d_evk, dbc, yo, rest, kp, S(stream), true, true, o != 0, d_p2_ntt, &pt, &fused));
+        RUN(k_relinearize(c, L.y3, ch, d_evk, dbc, yo, L.rest, L.kp, S(stream), true, true, o != 0, d_p2_ntt, &pt, &fused));
         if (!fused) RUN(k_poly2_tail(c, yo, xin, ch, 1, 1, 1, 1, 1, 1, d_p2_ntt, d_p1_ntt, d_p0_ntt, S(stream)));
     }
     if (out_form == CRC_COEFF) RUN(crc_ntt_inv(c, d_y, count, 2, stream));
@@ -804,10 +811,7 @@ extern "C" int crc_poly2_relin_forms(crc_ctx *c, const uint64_t *d_x, int in_for
 extern "C" int crc_poly2_pool_relin_supported(const crc_ctx *c, int dbc, int xf, int yf) { return crc_square_pool_relin_supported(c, dbc, xf, yf); }
 extern "C" size_t crc_poly2_pool_relin_work_bytes(const crc_ctx *c, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int dbc)
 {
-    const size_t sq = crc_square_pool_relin_work_bytes(c, B, zd, xd, yd, xs, ys, xf, yf, dbc);
-    if (!sq) return 0;
-    const size_t planes = (size_t)B * zd, pp = planes < sqpool_planes(c, xd, yd) ? planes : sqpool_planes(c, xd, yd);
-    return sq + 8 * pp * xd * yd * crc_ct_words(c, 2) + 256;
+    return pool_act_bytes(c, B, zd, xd, yd, xs, ys, xf, yf, dbc, ACT_XH);
 }
 extern "C" int crc_poly2_pool_relin_forms(crc_ctx *c, const uint64_t *d_x, int in_form, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf,
                                           const uint64_t *d_evk, int dbc, const uint64_t *d_p2_ntt, const uint64_t *d_p1_ntt, const uint64_t *d_p0_ntt,
@@ -819,27 +823,21 @@ extern "C" int crc_poly2_pool_relin_forms(crc_ctx *c, const uint64_t *d_x, int i
     if (!d_p2_ntt && !d_p1_ntt && !d_p0_ntt)
         return crc_square_pool_relin_forms(c, d_x, in_form, B, zd, xd, yd, xs, ys, xf, yf, d_evk, dbc, nullptr, d_y, out_form, d_work, stream);
     const PoolGeom pg{xd, yd, xs, ys, xf, yf, (xd - xf) / xs + 1, (yd - yf) / ys + 1};
-    const size_t planes = (size_t)B * zd, step = sqpool_planes(c, xd, yd), pp0 = planes < step ? planes : step;
-    const size_t pin = (size_t)xd * yd, pout = (size_t)pg.xo * pg.yo, ctw = crc_ct_words(c, 2);
+    const size_t planes = (size_t)B * zd, pin = (size_t)xd * yd, pout = (size_t)pg.xo * pg.yo, ctw = crc_ct_words(c, 2);
     if (d_p1_ntt && in_form == CRC_NTT && ranges_overlap(d_x, 8 * planes * pin * ctw, d_y, 8 * planes * pout * ctw)) return CRC_ERR_INVALID_ARGUMENT;
-    u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
     const bool own_xh = d_p1_ntt && in_form == CRC_COEFF;
-    u64 *xh_w = w; if (own_xh) w += (pp0 * pin * ctw + 31) & ~(size_t)31;
-    u64 *kp = w, *y3 = kp + k_relin_keys_words(c, dbc), *rest = y3 + pp0 * pin * crc_ct_words(c, 3);
+    WorkArena a(d_work);
+    const ActWork L = act_layout(c, planes, pin, pout, dbc, own_xh ? ACT_XH : 0, a);
     const bool fused = k_relin64_poly_fused(c);
-    for (size_t o = 0; o < planes; o += step) {
-        const size_t pp = planes - o < step ? planes - o : step, cin = pp * pin, cout = pp * pout;
+    for (size_t o = 0; o < planes; o += L.step) {
+        const size_t pp = pass_len(planes, o, L.step), cin = pp * pin, cout = pp * pout;
         const u64 *xin = d_x + o * pin * ctw;
-        if (own_xh) {
-            HIPCHK(hipMemcpyAsync(xh_w, xin, 8 * cin * ctw, hipMemcpyDeviceToDevice, S(stream)));
-            RUN(crc_ntt_fwd(c, xh_w, cin, 2, stream));
-            xin = xh_w;
-        }
+        if (own_xh) { RUN(ntt_copy(c, xin, cin, L.xh, stream)); xin = L.xh; }
         u64 *yo = d_y + o * pout * ctw;
-        RUN(k_square(c, xin, cin, y3, rest, S(stream), own_xh || in_form == CRC_NTT, true));
-        if (o == 0) RUN(k_relin64_prepare_keys(c, d_evk, dbc, kp, rest, S(stream)));
+        RUN(k_square(c, xin, cin, L.y3, L.rest, S(stream), own_xh || in_form == CRC_NTT, true));
+        if (o == 0) RUN(k_relin64_prepare_keys(c, d_evk, dbc, L.kp, L.rest, S(stream)));
         const PolyTail pt{xin, d_p1_ntt, d_p0_ntt};
-        RUN(k_relinearize64(c, y3, 3, 2, y3, 3, cout, dbc, yo, rest, kp, S(stream), true, &pg, fused ? d_p2_ntt : nullptr, fused ? &pt : nullptr));
+        RUN(k_relinearize64(c, L.y3, 3, 2, L.y3, 3, cout, dbc, yo, L.rest, L.kp, S(stream), true, &pg, fused ? d_p2_ntt : nullptr, fused ? &pt : nullptr));
         if (!fused) RUN(k_poly2_tail(c, yo, xin, pp, xd, yd, xs, ys, xf, yf, d_p2_ntt, d_p1_ntt, d_p0_ntt, S(stream)));
     }
     if (out_form == CRC_COEFF) RUN(crc_ntt_inv(c, d_y, planes * pout, 2, stream));
@@ -849,22 +847,15 @@ extern "C" int crc_poly2_pool_relin_forms(crc_ctx *c, const uint64_t *d_x, int i
 // Evaluator::multiply for size-2 inputs (k_multiply: the square's chain with the tensor product (ac, ad + bc, bd)); passes, key packing and work layout are
 // crc_square_relin_forms'.  The result may not share memory with an input: a pass writes its results while later passes have not read their inputs, and the
 // size-3 result of crc_multiply has another stride than its inputs -- every overlap is refused rather than some allowed.  d_x == d_y is the square.
-extern "C" size_t crc_multiply_relin_work_bytes(const crc_ctx *c, size_t count, int dbc)
-{
-    if (!c || !dbc_ok(dbc)) return 0;
-    const size_t chunk = square_chunk(c), ch = count < chunk ? count : chunk;
-    const size_t mu = k_multiply_work_words(c, ch), rl = k_relin_work_words(c, ch, dbc);
-    return 8 * (k_relin_keys_words(c, dbc) + (mu > rl ? mu : rl) + ch * crc_ct_words(c, 3)) + 256;
-}
+extern "C" size_t crc_multiply_relin_work_bytes(const crc_ctx *c, size_t count, int dbc) { return c && dbc_ok(dbc) ? act_bytes(c, count, 1, 1, dbc, ACT_MULTIPLY) : 0; }
 extern "C" int crc_multiply(crc_ctx *c, const uint64_t *d_x, const uint64_t *d_y, size_t count, uint64_t *d_out3, void *d_work, void *stream)
 {
     CHECK_CTX(c); if (!d_x || !d_y || !d_out3 || !d_work) return CRC_ERR_INVALID_ARGUMENT;
     const size_t ctw = crc_ct_words(c, 2), ctw3 = crc_ct_words(c, 3);
     if (ranges_overlap(d_x, 8 * count * ctw, d_out3, 8 * count * ctw3) || ranges_overlap(d_y, 8 * count * ctw, d_out3, 8 * count * ctw3)) return CRC_ERR_INVALID_ARGUMENT;
-    u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
-    const size_t chunk = square_chunk(c);
-    for (size_t o = 0; o < count; o += chunk) {
-        const size_t ch = count - o < chunk ? count - o : chunk;
+    u64 *w = work_base(d_work);
+    for (size_t o = 0, step = square_chunk(c); o < count; o += step) {
+        const size_t ch = pass_len(count, o, step);
         RUN(k_multiply(c, d_x + o * ctw, d_y + o * ctw, ch, d_out3 + o * ctw3, w, S(stream)));
     }
     return CRC_OK;
@@ -875,25 +866,18 @@ extern "C" int crc_multiply_relin_forms(crc_ctx *c, const uint64_t *d_x, const u
     CHECK_CTX(c); if (!d_x || !d_y || !d_out || !d_evk || !d_work || !form_ok(in_form) || !form_ok(out_form) || !dbc_ok(dbc)) return CRC_ERR_INVALID_ARGUMENT;
     const size_t ctw = crc_ct_words(c, 2);
     if (ranges_overlap(d_x, 8 * count * ctw, d_out, 8 * count * ctw) || ranges_overlap(d_y, 8 * count * ctw, d_out, 8 * count * ctw)) return CRC_ERR_INVALID_ARGUMENT;
-    u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
-    const size_t chunk = square_chunk(c), ch0 = count < chunk ? count : chunk;
-    for (size_t o = 0; o < count; o += chunk) {
-        const size_t ch = count - o < chunk ? count - o : chunk;
-        // [packed keys (filled by pass 0)][size-3 intermediates][scratch]
-        u64 *kp = w, *y3 = kp + k_relin_keys_words(c, dbc), *rest = y3 + ch0 * crc_ct_words(c, 3);
-        RUN(k_multiply(c, d_x + o * ctw, d_y + o * ctw, ch, y3, rest, S(stream), in_form == CRC_NTT, true));
-        RUN(k_relinearize(c, y3, ch, d_evk, dbc, d_out + o * ctw, rest, kp, S(stream), out_form == CRC_NTT, true, o != 0));
+    WorkArena a(d_work);
+    const ActWork L = act_layout(c, count, 1, 1, dbc, ACT_MULTIPLY, a);
+    for (size_t o = 0; o < count; o += L.step) {
+        const size_t ch = pass_len(count, o, L.step);
+        RUN(k_multiply(c, d_x + o * ctw, d_y + o * ctw, ch, L.y3, L.rest, S(stream), in_form == CRC_NTT, true));
+        RUN(k_relinearize(c, L.y3, ch, d_evk, dbc, d_out + o * ctw, L.rest, L.kp, S(stream), out_form == CRC_NTT, true, o != 0));
     }
     return CRC_OK;
 }
 // c3 x^3 + c2 x^2 + c1 x + c0:  s = relin(x^2), u = relin(s x), result = P3 (*) u + P2 (*) s + P1 (*) x + P0 slot-wise in NTT form (two key switches, depth 2).
-// Work: [x in NTT form, one pass (coefficient-form callers)][s, one pass][crc_multiply_relin_forms' work]; the ring-linear terms join in poly2_tail_kernel
-extern "C" size_t crc_poly3_relin_work_bytes(const crc_ctx *c, size_t count, int dbc)
-{
-    if (!c || !dbc_ok(dbc)) return 0;
-    const size_t chunk = square_chunk(c), ch = count < chunk ? count : chunk;
-    return crc_multiply_relin_work_bytes(c, count, dbc) + 8 * 2 * (ch * crc_ct_words(c, 2) + 32) + 256;
-}
+// The ring-linear terms join in poly2_tail_kernel; the work space holds x in NTT form and s for one pass in front of crc_multiply_relin_forms' (act_layout)
+extern "C" size_t crc_poly3_relin_work_bytes(const crc_ctx *c, size_t count, int dbc) { return c && dbc_ok(dbc) ? act_bytes(c, count, 1, 1, dbc, ACT_XH | ACT_S | ACT_MULTIPLY) : 0; }
 extern "C" int crc_poly3_relin_forms(crc_ctx *c, const uint64_t *d_x, int in_form, size_t count, const uint64_t *d_evk, int dbc, const uint64_t *d_p3_ntt,
                                      const uint64_t *d_p2_ntt, const uint64_t *d_p1_ntt, const uint64_t *d_p0_ntt, uint64_t *d_out, int out_form, void *d_work,
                                      void *stream)
@@ -901,24 +885,18 @@ extern "C" int crc_poly3_relin_forms(crc_ctx *c, const uint64_t *d_x, int in_for
     CHECK_CTX(c); if (!d_x || !d_out || !d_evk || !d_work || !form_ok(in_form) || !form_ok(out_form) || !dbc_ok(dbc)) return CRC_ERR_INVALID_ARGUMENT;
     const size_t ctw = crc_ct_words(c, 2);
     if (ranges_overlap(d_x, 8 * count * ctw, d_out, 8 * count * ctw)) return CRC_ERR_INVALID_ARGUMENT;
-    u64 *w = (u64 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
-    const size_t chunk = square_chunk(c), ch0 = count < chunk ? count : chunk, slab = (ch0 * ctw + 31) & ~(size_t)31;
-    u64 *xh_w = w, *s_w = w + slab; w += 2 * slab;
-    for (size_t o = 0; o < count; o += chunk) {
-        const size_t ch = count - o < chunk ? count - o : chunk;
-        u64 *kp = w, *y3 = kp + k_relin_keys_words(c, dbc), *rest = y3 + ch0 * crc_ct_words(c, 3);
+    WorkArena a(d_work);
+    const ActWork L = act_layout(c, count, 1, 1, dbc, ACT_XH | ACT_S | ACT_MULTIPLY, a);
+    for (size_t o = 0; o < count; o += L.step) {
+        const size_t ch = pass_len(count, o, L.step);
         const u64 *xin = d_x + o * ctw;
-        if (in_form == CRC_COEFF) {
-            HIPCHK(hipMemcpyAsync(xh_w, xin, 8 * ch * ctw, hipMemcpyDeviceToDevice, S(stream)));
-            RUN(crc_ntt_fwd(c, xh_w, ch, 2, stream));
-            xin = xh_w;
-        }
+        if (in_form == CRC_COEFF) { RUN(ntt_copy(c, xin, ch, L.xh, stream)); xin = L.xh; }
         u64 *yo = d_out + o * ctw;
-        RUN(k_square(c, xin, ch, y3, rest, S(stream), true, true));
-        RUN(k_relinearize(c, y3, ch, d_evk, dbc, s_w, rest, kp, S(stream), true, true, o != 0));
-        RUN(k_multiply(c, s_w, xin, ch, y3, rest, S(stream), true, true));
-        RUN(k_relinearize(c, y3, ch, d_evk, dbc, yo, rest, kp, S(stream), true, true, true));
-        RUN(k_poly2_tail(c, yo, s_w, ch, 1, 1, 1, 1, 1, 1, d_p3_ntt, d_p2_ntt, nullptr, S(stream)));
+        RUN(k_square(c, xin, ch, L.y3, L.rest, S(stream), true, true));
+        RUN(k_relinearize(c, L.y3, ch, d_evk, dbc, L.s, L.rest, L.kp, S(stream), true, true, o != 0));
+        RUN(k_multiply(c, L.s, xin, ch, L.y3, L.rest, S(stream), true, true));
+        RUN(k_relinearize(c, L.y3, ch, d_evk, dbc, yo, L.rest, L.kp, S(stream), true, true, true));
+        RUN(k_poly2_tail(c, yo, L.s, ch, 1, 1, 1, 1, 1, 1, d_p3_ntt, d_p2_ntt, nullptr, S(stream)));
         RUN(k_poly2_tail(c, yo, xin, ch, 1, 1, 1, 1, 1, 1, nullptr, d_p1_ntt, d_p0_ntt, S(stream)));
     }
     if (out_form == CRC_COEFF) RUN(crc_ntt_inv(c, d_out, count, 2, stream));
