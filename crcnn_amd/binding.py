@@ -104,6 +104,7 @@ def load():
     L.crc_conv2d_work_bytes.restype = SZ; L.crc_conv2d_work_bytes.argtypes = [VP] + [CI] * 10
     L.crc_conv2d.argtypes = [VP, VP, VP, VP] + [CI] * 11 + [VP, VP, VP]
     L.crc_conv2d_fold_pool.argtypes = [VP, VP, VP, VP] + [CI] * 8 + [VP, VP, VP]
+    L.crc_conv2d_hoist_pool.argtypes = [VP, VP, VP, VP] + [CI] * 6 + [VP, VP, VP]
     L.crc_dense_work_bytes.restype = SZ; L.crc_dense_work_bytes.argtypes = [VP, CI, CI, CI, CI]
     L.crc_dense.argtypes = [VP, VP, VP, VP, CI, CI, CI, CI, CI, VP, VP, VP]
     L.crc_pool.argtypes = [VP, VP] + [CI] * 8 + [VP, CI, VP, VP]
@@ -136,6 +137,7 @@ def load():
     L.crc_limb_pack_tensor_at.argtypes = [VP, VP, CI, CI, CI, CI, CI, VP, CI, CI, VP]
     L.crc_plan_mac.argtypes = [VP] + [CI] * 10 + [ctypes.POINTER(CI)]
     L.crc_plan_fold_pool.argtypes = [VP] + [CI] * 12 + [ctypes.POINTER(CI)]
+    L.crc_plan_hoist_pool.argtypes = [VP] + [CI] * 22 + [ctypes.POINTER(CI)]
     L.crc_limb_pack_tensor.argtypes = [VP, VP, CI, CI, CI, CI, CI, VP, VP]
     L.crc_limb_conv1_supported.argtypes = [VP] + [CI] * 8
     L.crc_limb_conv1_weights_bytes.restype = SZ; L.crc_limb_conv1_weights_bytes.argtypes = [VP]
@@ -552,6 +554,14 @@ class Engine:
         _chk(self.L.crc_plan_fold_pool(self.c, zd, xd, yd, xs, ys, xf, yf, nf, pxs, pys, pxf, pyf, ctypes.byref(f)), "crc_plan_fold_pool")
         return bool(f.value)
 
+    def plan_hoist_pool(self, up, conv, pool, B, matrix_cores=True):
+        """crc_plan_hoist_pool: is the pool behind a stride-1 convolution hoisted in front of it?  up: (zd, xd, yd, xs, ys, xf, yf, nf) of the layer in front as it
+        runs (already folded), or None where no resident convolution feeds this one; conv: the same eight; pool: (xs, ys, xf, yf)"""
+        h = CI(0)
+        _chk(self.L.crc_plan_hoist_pool(self.c, *(tuple(up) if up else (0,) * 8), *conv, *pool, int(B or 0), 1 if matrix_cores else 0, ctypes.byref(h)),
+             "crc_plan_hoist_pool")
+        return bool(h.value)
+
     def limb_pack_weights_tile(self, d_w_tile, nf, f0, ft, zd, xf, yf, d_wl):
         _chk(self.L.crc_limb_pack_weights_tile(self.c, self.p(d_w_tile), nf, f0, ft, zd, xf, yf, self.p(d_wl), self.stream), "crc_limb_pack_weights_tile")
 
@@ -587,6 +597,10 @@ class Engine:
     def conv2d_fold_pool(self, d_w, d_bias_ntt, d_div_ntt, nf, zd, xf, yf, cxs, cys, pxf, pyf, d_w_out, d_bias_out):
         _chk(self.L.crc_conv2d_fold_pool(self.c, self.p(d_w), self.p(d_bias_ntt), self.p(d_div_ntt), nf, zd, xf, yf, cxs, cys, pxf, pyf,
                                          self.p(d_w_out), self.p(d_bias_out), self.stream), "crc_conv2d_fold_pool")
+
+    def conv2d_hoist_pool(self, d_w, d_bias_ntt, d_div_ntt, nf, zd, xf, yf, pxf, pyf, d_w_out, d_bias_out):
+        _chk(self.L.crc_conv2d_hoist_pool(self.c, self.p(d_w), self.p(d_bias_ntt), self.p(d_div_ntt), nf, zd, xf, yf, pxf, pyf,
+                                          self.p(d_w_out), self.p(d_bias_out), self.stream), "crc_conv2d_hoist_pool")
 
     def dense_work_bytes(self, B, in_dim, out_dim, in_form):
         return self.L.crc_dense_work_bytes(self.c, B, in_dim, out_dim, in_form)

@@ -336,6 +336,14 @@ extern "C" int crc_conv2d_fold_pool(crc_ctx *c, const uint64_t *d_w, const uint6
         pyf < 1) return CRC_ERR_INVALID_ARGUMENT;
     return k_fold_pool(c, d_w, d_bias_ntt, d_div_ntt, d_w_out, d_bias_out, nf, zd, xf, yf, cxs, cys, pxf, pyf, S(stream));
 }
+// the downstream half of the hoisted pair (crc_plan_hoist_pool): w' = div * w in the convolution's own window, b' = div * pxf*pyf * b
+extern "C" int crc_conv2d_hoist_pool(crc_ctx *c, const uint64_t *d_w, const uint64_t *d_bias_ntt, const uint64_t *d_div_ntt, int nf, int zd, int xf, int yf,
+                                     int pxf, int pyf, uint64_t *d_w_out, uint64_t *d_bias_out, void *stream)
+{
+    CHECK_CTX(c);
+    if (!d_w || !d_bias_ntt || !d_w_out || !d_bias_out || nf < 1 || zd < 1 || xf < 1 || yf < 1 || pxf < 1 || pyf < 1) return CRC_ERR_INVALID_ARGUMENT;
+    return k_fold_pool(c, d_w, d_bias_ntt, d_div_ntt, d_w_out, d_bias_out, nf, zd, xf, yf, 1, 1, pxf, pyf, S(stream), true);
+}
 
 // ---- pooling / batch-norm -----------------------------------------------------------------------------------------
 extern "C" int crc_pool(crc_ctx *c, const uint64_t *d_x, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf,
@@ -437,6 +445,58 @@ extern "C" int crc_plan_fold_pool(const crc_ctx *c, int zd, int xd, int yd, int 
     const long long cost_sep = fpad * xo * yo * (T1 + 24) + (long long)nf * xo2 * yo2 * 10 * (pxf * pyf + 1);
     const long long cost_fused = fpad * xo2 * yo2 * (T2 + 24);
     *fold = cost_fused < cost_sep ? 1 : 0;
+    return CRC_OK;
+}
+
+// Cost of a conv / dense layer on the kernel crc_plan_mac gives it, in crc_plan_fold_pool's units (one multiply-accumulate term per output ciphertext, ~24 terms
+// of prologue / epilogue per output).  The limb GEMM pads the channels of every tap to 32 and takes filters in tiles of 32.  The one-channel matrix-core kernel
+// pays for its whole K whatever the window -- 64 taps in the plane-major form, 40 in the pixel-major one -- for 32 filters and whole 16-row tiles (8 positions x 2
+// polys), and a term there costs 25/16 of the limb GEMM's (PlainModelTiny at n = 4096, 128 images per launch, kernel + image pack: pixel-major 35.6 ms for 18
+// tiles, plane-major 48.4 ms, against 92.8 ms for the limb GEMM's 64 x 16 outputs of 1152 + 24 terms -- 1.57 and 1.55; profiles/conv1_pixel_major_ab.txt)
+static long long plan_mac_cost(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int B, int matrix_cores)
+{
+    int wf = CRC_NTT;
+    if (crc_plan_mac(c, zd, xd, yd, xs, ys, xf, yf, nf, B, matrix_cores, &wf) != CRC_OK) return -1;
+    const long long P = (long long)((xd - xf) / xs + 1) * ((yd - yf) / ys + 1);
+    if (wf == CRC_NTTL1) return 32 * ((2 * P + 15) / 16 * 8) * ((k_limb_conv1_form(c, xf, yf, nf) == 2 ? 40 : 64) + 24) * 25 / 16;
+    if (wf == CRC_NTTL) return (long long)(nf + 31) / 32 * 32 * P * ((long long)k_limb_steps(zd, xf, yf) * 32 + 24);
+    return (long long)(nf + 7) / 8 * 8 * P * ((long long)zd * xf * yf + 24);
+}
+// Should the pooling layer behind a stride-1 convolution be HOISTED instead of folded into that convolution's weights?  pool(conv_w(x) + b) = conv_{div w}(S) +
+// div pxf pyf b with S the stride-1 pxf x pyf window sum of x: the convolution keeps its window (xf x yf taps per channel instead of the folded (xf + pxf - 1) x
+// (yf + pyf - 1)) and takes the pool's stride, and S is made by the layer in FRONT -- u..., a convolution, as already folded -- with that sum pool folded into its
+// weights (crc_conv2d_fold_pool, no divisor): no pass of its own.  Exact over Z_q.  The answer is no unless: the convolution has stride 1; the pool decimates (a
+// stride-1 pool removes no multiply-accumulates) and crc_plan_fold_pool folds it; the layer in front is a convolution whose output is this one's input (the
+// caller passes uzd = 0 where there is none, or where it is not resident: streamed or tile-wise weights); its enlarged window fits its image and, where the layer
+// runs on the matrix cores, keeps a matrix-core kernel (one-channel kernel: windows up to 8 x 8); and the two layers cost less hoisted than folded (plan_mac_cost
+// on B images per launch).  The tuning key hoist_pool = 0 (CRC_HOIST_POOL=0) answers no throughout.
+extern "C" int crc_plan_hoist_pool(const crc_ctx *c, int uzd, int uxd, int uyd, int uxs, int uys, int uxf, int uyf, int unf, int zd, int xd, int yd, int xs,
+                                   int ys, int xf, int yf, int nf, int pxs, int pys, int pxf, int pyf, int B, int matrix_cores, int *hoist)
+{
+    if (!c || !hoist || zd < 1 || nf < 1 || !conv_shape_ok(xd, yd, xs, ys, xf, yf) || pxs < 1 || pys < 1 || pxf < 1 || pyf < 1) return CRC_ERR_INVALID_ARGUMENT;
+    *hoist = 0;
+    if (!c->tune.hoist_pool || xs != 1 || ys != 1 || pxs * pys == 1) return CRC_OK;
+    int fold = 0;
+    { const int rc = crc_plan_fold_pool(c, zd, xd, yd, xs, ys, xf, yf, nf, pxs, pys, pxf, pyf, &fold); if (rc != CRC_OK) return rc; }
+    if (!fold) return CRC_OK;
+    if (uzd < 1 || unf != zd || !conv_shape_ok(uxd, uyd, uxs, uys, uxf, uyf) || (uxd - uxf) / uxs + 1 != xd || (uyd - uyf) / uys + 1 != yd) return CRC_OK;
+    // the layer in front with the sum pool folded in: S = [zd][xd - pxf + 1][yd - pyf + 1]
+    const int uxf2 = (pxf - 1) * uxs + uxf, uyf2 = (pyf - 1) * uys + uyf, sxd = xd - pxf + 1, syd = yd - pyf + 1;
+    if (uxf2 > uxd || uyf2 > uyd || !conv_shape_ok(uxd, uyd, uxs, uys, uxf2, uyf2)) return CRC_OK;
+    if ((uxd - uxf2) / uxs + 1 != sxd || (uyd - uyf2) / uys + 1 != syd) return CRC_OK;
+    // the convolution over S must produce exactly the pooled tensor
+    const int xo = xd - xf + 1, yo = yd - yf + 1;
+    if (!conv_shape_ok(sxd, syd, pxs, pys, xf, yf) || (sxd - xf) / pxs + 1 != (xo - pxf) / pxs + 1 || (syd - yf) / pys + 1 != (yo - pyf) / pys + 1) return CRC_OK;
+    int uf = CRC_NTT, uf2 = CRC_NTT;
+    if (crc_plan_mac(c, uzd, uxd, uyd, uxs, uys, uxf, uyf, unf, B, matrix_cores, &uf) != CRC_OK) return CRC_OK;
+    if (crc_plan_mac(c, uzd, uxd, uyd, uxs, uys, uxf2, uyf2, unf, B, matrix_cores, &uf2) != CRC_OK) return CRC_OK;
+    if ((uf == CRC_NTTL1 || uf == CRC_NTTL) && uf2 != uf) return CRC_OK;
+    const int xf2 = xf + pxf - 1, yf2 = yf + pyf - 1;
+    const long long folded = plan_mac_cost(c, uzd, uxd, uyd, uxs, uys, uxf, uyf, unf, B, matrix_cores) +
+                             plan_mac_cost(c, zd, xd, yd, pxs, pys, xf2, yf2, nf, B, matrix_cores);
+    const long long hoisted = plan_mac_cost(c, uzd, uxd, uyd, uxs, uys, uxf2, uyf2, unf, B, matrix_cores) +
+                              plan_mac_cost(c, zd, sxd, syd, pxs, pys, xf, yf, nf, B, matrix_cores);
+    *hoist = hoisted < folded ? 1 : 0;
     return CRC_OK;
 }
 

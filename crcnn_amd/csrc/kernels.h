@@ -63,7 +63,7 @@ int k_relinearize(crc_ctx *c, const u64 *x3, size_t cnt, const u64 *evk, int dbc
 int k_mac2(crc_ctx *c, const u64 *x, const u64 *w, u64 *y, const int *d_xoff, const int *d_toff, int B, int P, int F, int T, int in_cts,
            const u64 *bias_ntt, int gxd, int gyd, int gxf, int gyf, const unsigned *d_toffw, hipStream_t st, int xp = 0, int wp = 0, int yp = 0);
 int k_fold_pool(crc_ctx *c, const u64 *w, const u64 *bias, const u64 *div, u64 *wout, u64 *bout, int nf, int zd, int xf, int yf, int cxs, int cys,
-                int pxf, int pyf, hipStream_t st);
+                int pxf, int pyf, hipStream_t st, bool hoisted = false);
 size_t k_encrypt_work_words(const crc_ctx *c, size_t cnt);
 struct ChaChaKey;
 int k_encrypt(crc_ctx *c, const u64 *pk, const u64 *plain, size_t cnt, const ChaChaKey &key, u64 stream_base, u64 *ct, u64 *work, hipStream_t st, bool out_ntt = false,

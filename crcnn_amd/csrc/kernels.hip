@@ -1810,10 +1810,14 @@ int k_mac2(crc_ctx *c, const u64 *x, const u64 *w, u64 *y, const int *d_xoff, co
 // b' = div * (pxf*pyf) * b, window xf' = (pxf-1)*cxs + xf, stride cxs*pxs.  For a decimating pool (stride = window) the
 // fused layer has (xf'*yf')/(xf*yf) more terms but pxs*pys fewer outputs: 2.8x fewer MACs for CrCNN's 5x5 conv + 2x2/2 pool.
 // All inputs/outputs in NTT form.
+// The HOISTED form of the same pair (bias_cnt > 0; stride-1 convolutions): the pool's window SUM moves in front of the convolution -- it is folded into the layer
+// that produces the convolution's input, as a stride-1 sum pool -- and what stays here is  w' = div * w  (the launcher passes a 1 x 1 window), stride pxs, and the
+// bias of all bias_cnt = pxf*pyf window positions:  pool(conv_w(x) + b) == conv_w'(S) + b',  S = the stride-1 window sum of x.
 // ---------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) fold_pool_kernel(const u64 *w, const u64 *bias, const u64 *div, u64 *wout, u64 *bout, const ModParams *mods, int n,
     int k,
-                                                        int nf, int zd, int xf, int yf, int cxs, int cys, int pxf, int pyf, int xf2, int yf2)
+                                                        int nf, int zd, int xf, int yf, int cxs, int cys, int pxf, int pyf, int xf2, int yf2,
+                                                        int bias_cnt)
 {
     // rows: first nf*zd*xf2*yf2*k weight rows, then nf*k bias rows
     const size_t row = blockIdx.x;
@@ -1835,7 +1839,7 @@ __global__ void __launch_bounds__(256) fold_pool_kernel(const u64 *w, const u64 
     } else {
         const size_t br = row - wrows;                   // f*k + i
         const u64 *src = bias + br * (size_t)n; u64 *dst = bout + br * (size_t)n;
-        const u64 cnt = (u64)(pxf * pyf) % m.q;
+        const u64 cnt = (u64)(bias_cnt > 0 ? bias_cnt : pxf * pyf) % m.q;
         for (int s = threadIdx.x; s < n; s += blockDim.x) {
             u64 x = mulmod(src[s], cnt, m);
             dst[s] = dv ? mulmod(x, dv[s], m) : x;
@@ -1844,12 +1848,14 @@ __global__ void __launch_bounds__(256) fold_pool_kernel(const u64 *w, const u64 
 }
 
 int k_fold_pool(crc_ctx *c, const u64 *w, const u64 *bias, const u64 *div, u64 *wout, u64 *bout, int nf, int zd, int xf, int yf, int cxs, int cys,
-                int pxf, int pyf, hipStream_t st)
+                int pxf, int pyf, hipStream_t st, bool hoisted)
 {
+    const int bias_cnt = hoisted ? pxf * pyf : 0;
+    if (hoisted) pxf = pyf = 1;                   // the window sum is the layer in front's: the weights keep their window
     const int xf2 = (pxf - 1) * cxs + xf, yf2 = (pyf - 1) * cys + yf;
     const size_t rows = ((size_t)nf * zd * xf2 * yf2 + nf) * c->k;
     hipLaunchKernelGGL(fold_pool_kernel, dim3((unsigned)rows), dim3(256), 0, st, w, bias, div, wout, bout, c->d_mods, c->n, c->k, nf, zd, xf, yf, cxs, cys,
-        pxf, pyf, xf2, yf2);
+        pxf, pyf, xf2, yf2, bias_cnt);
     HIPCHK(hipGetLastError());
     return CRC_OK;
 }

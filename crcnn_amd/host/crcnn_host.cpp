@@ -1567,6 +1567,20 @@ int Network::fuse()
     // (a network that has already run holds its weights in the MAC kernels' operand forms: packed residues are unpacked, matrix-core forms -- which drop
     // the canonical copy -- are rebuilt from the layer's plaintexts, so fuse() may follow a forward())
     for (auto &l : layers) if (auto m = dynamic_pointer_cast<MacLayer>(l)) m->restoreCanonical();
+    // pool(conv(x)) as ONE convolution with the pooled kernel (crc_conv2d_fold_pool; div: an average pool's NTT-form divisor rows, or null)
+    auto foldPool = [&](const ConvolutionalLayer &conv, const string &name, int pxs, int pys, int pxf, int pyf, const shared_ptr<DeviceBuffer> &div) {
+        const int xf2 = (pxf - 1) * conv.xs + conv.xf, yf2 = (pyf - 1) * conv.ys + conv.yf;
+        vector<Plaintext> nob; plaintext4D nof;
+        auto fused = make_shared<ConvolutionalLayer>(name, conv.xd, conv.yd, conv.zd, conv.xs * pxs, conv.ys * pys, xf2, yf2, conv.nf, conv.th_count, nof, nob);
+        fused->d_w = make_shared<DeviceBuffer>((size_t)conv.nf * conv.zd * xf2 * yf2 * rowb);
+        fused->d_b[1] = make_shared<DeviceBuffer>((size_t)conv.nf * rowb);
+        chk(crc_conv2d_fold_pool(ctx(), (const uint64_t *)conv.d_w->ptr, (const uint64_t *)conv.d_b[1]->ptr, div ? (const uint64_t *)div->ptr : nullptr,
+                                 conv.nf, conv.zd, conv.xf, conv.yf, conv.xs, conv.ys, pxf, pyf, (uint64_t *)fused->d_w->ptr, (uint64_t *)fused->d_b[1]->ptr,
+                                 stream()), "crc_conv2d_fold_pool");
+        fused->d_b[0] = inttCopy(fused->d_b[1], conv.nf);
+        fused->filters_already_ntt = true;
+        return fused;
+    };
     // 1. conv + pool
     for (size_t i = 0; i + 1 < layers.size(); i++) {
         auto conv = dynamic_pointer_cast<ConvolutionalLayer>(layers[i]);
@@ -1581,25 +1595,38 @@ int Network::fuse()
         const int xo2 = (conv->xd - xf2) / xs2 + 1, yo2 = (conv->yd - yf2) / ys2 + 1;
         if (xo2 != pool->xo || yo2 != pool->yo) continue;
         // the cost model lives behind the C ABI (crc_plan_fold_pool), shared with netrun.py
-        const long long T2 = (long long)conv->zd * xf2 * yf2;
         int fold = 0;
         chk(crc_plan_fold_pool(ctx(), conv->zd, conv->xd, conv->yd, conv->xs, conv->ys, conv->xf, conv->yf, conv->nf, pool->xs, pool->ys, pool->xf, pool->yf,
             &fold), "crc_plan_fold_pool");
         if (!fold) continue;
-        conv->upload();
-        vector<Plaintext> nob; plaintext4D nof;
-        auto fused = make_shared<ConvolutionalLayer>(conv->name + "+" + pool->name, conv->xd, conv->yd, conv->zd, xs2, ys2, xf2, yf2, conv->nf,
-            conv->th_count, nof, nob);
-        fused->d_w = make_shared<DeviceBuffer>((size_t)conv->nf * T2 * rowb);
-        fused->d_b[1] = make_shared<DeviceBuffer>((size_t)conv->nf * rowb);
-        chk(crc_conv2d_fold_pool(ctx(), (const uint64_t *)conv->d_w->ptr, (const uint64_t *)conv->d_b[1]->ptr, pool->d_div ?
-            (const uint64_t *)pool->d_div->ptr : nullptr,
-                                 conv->nf, conv->zd, conv->xf, conv->yf, conv->xs, conv->ys, pool->xf, pool->yf, (uint64_t *)fused->d_w->ptr,
-                                     (uint64_t *)fused->d_b[1]->ptr, stream()),
-            "crc_conv2d_fold_pool");
-        fused->d_b[0] = inttCopy(fused->d_b[1], conv->nf);
-        fused->filters_already_ntt = true;
-        layers[i] = fused;
+        // 1a. ... or the pool's window sum hoisted in front of the convolution (crc_plan_hoist_pool): the layer in front -- a resident convolution, as fused
+        // so far, with no refresh in between -- takes the stride-1 sum pool into its weights and so hands over S, the window sums of this layer's input; this
+        // layer keeps its window, takes the pool's stride, the divisor into its weights and the bias of every window position (crc_conv2d_hoist_pool).  Both
+        // layers keep the names the weight-folded pair has
+        auto up = i > 0 && !refreshBetween(i - 1) ? dynamic_pointer_cast<ConvolutionalLayer>(layers[i - 1]) : nullptr;
+        if (up) { up->upload(); if (up->streamed || up->tilewise) up = nullptr; }
+        int hoist = 0;
+        chk(crc_plan_hoist_pool(ctx(), up ? up->zd : 0, up ? up->xd : 0, up ? up->yd : 0, up ? up->xs : 0, up ? up->ys : 0, up ? up->xf : 0, up ? up->yf : 0,
+            up ? up->nf : 0, conv->zd, conv->xd, conv->yd, conv->xs, conv->ys, conv->xf, conv->yf, conv->nf, pool->xs, pool->ys, pool->xf, pool->yf,
+            g_expected_batch, matrix_cores ? 1 : 0, &hoist), "crc_plan_hoist_pool");
+        if (hoist) {
+            auto sums = foldPool(*up, up->name, 1, 1, pool->xf, pool->yf, nullptr);
+            vector<Plaintext> nob; plaintext4D nof;
+            auto down = make_shared<ConvolutionalLayer>(conv->name + "+" + pool->name, sums->xo, sums->yo, conv->zd, pool->xs, pool->ys, conv->xf, conv->yf,
+                conv->nf, conv->th_count, nof, nob);
+            down->d_w = make_shared<DeviceBuffer>((size_t)conv->nf * conv->zd * conv->xf * conv->yf * rowb);
+            down->d_b[1] = make_shared<DeviceBuffer>((size_t)conv->nf * rowb);
+            chk(crc_conv2d_hoist_pool(ctx(), (const uint64_t *)conv->d_w->ptr, (const uint64_t *)conv->d_b[1]->ptr, pool->d_div ?
+                (const uint64_t *)pool->d_div->ptr : nullptr, conv->nf, conv->zd, conv->xf, conv->yf, pool->xf, pool->yf, (uint64_t *)down->d_w->ptr,
+                (uint64_t *)down->d_b[1]->ptr, stream()), "crc_conv2d_hoist_pool");
+            down->d_b[0] = inttCopy(down->d_b[1], conv->nf);
+            down->filters_already_ntt = true;
+            layers[i - 1] = sums;
+            layers[i] = down;
+            eraseLayer(i + 1);
+            continue;
+        }
+        layers[i] = foldPool(*conv, conv->name + "+" + pool->name, pool->xs, pool->ys, pool->xf, pool->yf, pool->d_div);
         eraseLayer(i + 1);
     }
     // 1b. Square + pooling: one key switch per pooled ciphertext (SquarePoolLayer)

@@ -3,6 +3,8 @@
 //     <dir>/params.u64 (n,k,t,q...), evk.u64, net_in.u64 ([1][1][28][28][2][k][n]) -> writes layer_<i>.u64 (layerwise mode) and out.u64
 //     <model>: a built-in name or the path of a description file, here and in net3 / netr / netseeded / search (netr: a <layer_before_reenc> of -1 keeps the
 //     description's refresh point)
+//   test_host netgeom <model> <h5> <dir> <batch> <head_chunk>     `net` with Network::fuse(), NTT-resident, on <batch> copies of the image (out.u64); prints one line
+//     "geom <i> <name> <zd> <xd> <yd> <xs> <ys> <xf> <yf> <nf>" per conv / dense layer the fused network runs
 //   test_host describe <name | description file> [h5]     parse and validate a description (with h5: dataset sizes too); prints its canonical form.  No GPU work
 //   test_host labels <model> <h5> <images.f32>     argmax of plainModelForward per image ("label <i> <class>").  No GPU work
 //   test_host build <description> <h5> <dir> <batch>     see do_build
@@ -80,6 +82,30 @@ static int do_net(int argc, char **argv)
         for (double ms : net.last_layer_ms) fprintf(stderr, "%.3f,", ms);
         fprintf(stderr, "\n");
     }
+    delParameters();
+    return 0;
+}
+
+static int do_netgeom(int argc, char **argv)
+{
+    if (argc < 7) return 1;
+    string model = argv[2], h5 = argv[3], dir = argv[4]; const int batch = atoi(argv[5]);
+    setup(dir);
+    { auto evk = rd(dir + "/evk.u64");
+      ev_keys16 = make_shared<DeviceBuffer>(evk.size() * 8);
+      crc_memcpy_h2d(context, ev_keys16->ptr, evk.data(), evk.size() * 8, nullptr); crc_stream_sync(context, nullptr); }
+    CnnBuilder builder(h5);
+    Network net = builder.buildNetworkByName(model);
+    net.ntt_resident = true;
+    net.head_chunk = atoi(argv[6]);
+    net.fuse();
+    for (int i = 0; i < net.getNumLayers(); i++)
+        if (auto m = dynamic_pointer_cast<MacLayer>(net.getLayer(i)))
+            printf("geom %d %s %d %d %d %d %d %d %d %d\n", i, m->getName().c_str(), m->zd, m->xd, m->yd, m->xs, m->ys, m->xf, m->yf, m->nf);
+    auto x = rd(dir + "/net_in.u64");
+    vector<ciphertext3D> imgs;
+    for (int b = 0; b < batch; b++) imgs.push_back(ciphertext3D::fromHost(x.data(), 1, net.input_zd, net.input_xd, net.input_yd));
+    wr(dir + "/out.u64", net.forward(stackImages(imgs)).toHost());
     delParameters();
     return 0;
 }
@@ -763,6 +789,7 @@ int main(int argc, char **argv)
     try {
         if (!strcmp(argv[1], "bcast")) return do_bcast(argc, argv);
         if (!strcmp(argv[1], "net")) return do_net(argc, argv);
+        if (!strcmp(argv[1], "netgeom")) return do_netgeom(argc, argv);
         if (!strcmp(argv[1], "net3")) return do_net3(argc, argv);
         if (!strcmp(argv[1], "netr")) return do_netr(argc, argv);
         if (!strcmp(argv[1], "encsym")) return do_encsym(argc, argv);

@@ -577,6 +577,25 @@ class Network:
                 # (crc_plan_fold_pool: the cost model behind the C ABI, shared with the C++ host classes -- folding wins whenever it removes MACs and narrowly for
                 # CrCNN's stride-1 pools)
                 if same_shape and E.plan_fold_pool(a["zd"], a["xd"], a["yd"], a["xs"], a["ys"], a["xf"], a["yf"], a["nf"], pa["xs"], pa["ys"], pa["xf"], pa["yf"]):
+                    # ... or the pool's window sum hoisted in front of the convolution (crc_plan_hoist_pool, Network::fuse() step 1a): the layer in front -- a
+                    # resident convolution, as fused so far -- takes the stride-1 sum pool into its weights, this one keeps its window and takes the pool's stride
+                    up = plan[-1] if plan and plan[-1][0] == "conv" and not plan[-1][3].get("streamed") and not plan[-1][3].get("tilewise") and plan[-1][3]["out_form"] == NTT else None
+                    if E.plan_hoist_pool(self._geom("conv", up[2]) if up else None, self._geom("conv", a), (pa["xs"], pa["ys"], pa["xf"], pa["yf"]), 0, matrix_cores=self.limb):
+                        plan[-1] = self._fold_sum_pool(up, pa["xf"], pa["yf"])
+                        sshape = plan[-1][5]
+                        cnt = a["nf"] * a["zd"] * a["xf"] * a["yf"]
+                        w2 = self.alloc(cnt * E.k * E.n * 8); b2 = self.alloc(a["nf"] * E.k * E.n * 8)
+                        if self.materialize:
+                            E.conv2d_hoist_pool(p["w"], p["b"], nxt[3]["div"], a["nf"], a["zd"], a["xf"], a["yf"], pa["xf"], pa["yf"], w2, b2)
+                            E.sync()
+                        self.param_bufs = [(b_, n_) for (b_, n_) in self.param_bufs if b_ is not p["w"] and b_ is not p["b"]]
+                        self.param_bufs += [(w2, cnt * E.k * E.n * 8), (b2, a["nf"] * E.k * E.n * 8)]
+                        a2 = dict(a, xd=sshape[1], yd=sshape[2], xs=pa["xs"], ys=pa["ys"])
+                        p2 = dict(p, w=w2, b=b2, fused=(name, nxt[1]), macs_separate=macs_sep, macs=layer_macs("conv", a2))
+                        p["w"] = p["b"] = None
+                        plan.append(("conv", name + "+" + nxt[1], a2, p2, sshape, nxt[5]))
+                        i += 2
+                        continue
                     cnt = a["nf"] * a["zd"] * xf2 * yf2
                     w2 = self.alloc(cnt * E.k * E.n * 8); b2 = self.alloc(a["nf"] * E.k * E.n * 8)
                     if self.materialize:
@@ -596,6 +615,23 @@ class Network:
         self.plan = plan
         self._pair_square_pool()
         self._fold_batchnorm()
+
+    def _fold_sum_pool(self, entry, pxf, pyf):
+        """a plan entry of a resident convolution with a (pxf x pyf, stride 1) sum pool folded into its weights: the window sums of its output, under its own name"""
+        E = self.E
+        kind, name, a, p, ishape, oshape = entry
+        xf2, yf2 = (pxf - 1) * a["xs"] + a["xf"], (pyf - 1) * a["ys"] + a["yf"]
+        cnt = a["nf"] * a["zd"] * xf2 * yf2
+        w2 = self.alloc(cnt * E.k * E.n * 8); b2 = self.alloc(a["nf"] * E.k * E.n * 8)
+        if self.materialize:
+            E.conv2d_fold_pool(p["w"], p["b"], None, a["nf"], a["zd"], a["xf"], a["yf"], a["xs"], a["ys"], pxf, pyf, w2, b2)
+            E.sync()
+        self.param_bufs = [(b_, n_) for (b_, n_) in self.param_bufs if b_ is not p["w"] and b_ is not p["b"]]
+        self.param_bufs += [(w2, cnt * E.k * E.n * 8), (b2, a["nf"] * E.k * E.n * 8)]
+        self.weight_bytes += (cnt - a["nf"] * a["zd"] * a["xf"] * a["yf"]) * E.k * E.n * 8
+        a2 = dict(a, xf=xf2, yf=yf2)
+        p2 = dict(p, w=w2, b=b2, macs=layer_macs("conv", a2))
+        return (kind, name, a2, p2, ishape, (oshape[0], oshape[1] - pxf + 1, oshape[2] - pyf + 1))
 
     def _keep_rows(self, rows):
         rowb = self.E.k * self.E.n * 8

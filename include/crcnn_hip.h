@@ -240,6 +240,12 @@ int crc_conv2d(crc_ctx *ctx, const uint64_t *d_x, const uint64_t *d_w_ntt, const
  * (unobservable in NTT-resident mode) intermediate tensor disappears.  d_div_ntt = NULL for sum pooling. */
 int crc_conv2d_fold_pool(crc_ctx *ctx, const uint64_t *d_w_ntt, const uint64_t *d_bias_delta_ntt, const uint64_t *d_div_ntt, int nf, int zd, int xf, int yf,
                          int cxs, int cys, int pxf, int pyf, uint64_t *d_w_out, uint64_t *d_bias_out, void *stream);
+/* The other way round for a stride-1 convolution whose input comes from another convolution (crc_plan_hoist_pool): the pool's window sum is HOISTED in front of
+ * the convolution, pool(conv_w(x) + b) = conv_w'(S) + b' with S[u][v] = sum_{a<pxf, b<pyf} x[u+a][v+b], w' = div * w (the window stays xf x yf), b' = div*pxf*pyf*b.
+ * S is the layer in front with a (pxf x pyf, stride 1) sum pool folded into ITS weights (crc_conv2d_fold_pool, d_div_ntt = NULL); this entry produces w' [nf][zd][xf][yf][k][n]
+ * and b' [nf][k][n]; run them with crc_conv2d(..., xd - pxf + 1, yd - pyf + 1, xs = pxs, ys = pys, xf, yf).  Exact mod q: the same ciphertexts as the folded pair. */
+int crc_conv2d_hoist_pool(crc_ctx *ctx, const uint64_t *d_w_ntt, const uint64_t *d_bias_delta_ntt, const uint64_t *d_div_ntt, int nf, int zd, int xf, int yf,
+                          int pxf, int pyf, uint64_t *d_w_out, uint64_t *d_bias_out, void *stream);
 /* the same two layers with the packed operand form: in_form / out_form may also be CRC_NTTP, w_form says how d_w_ntt is stored
  * (CRC_NTT canonical, CRC_NTTP packed by crc_pack28).  Same ciphertexts; nothing is re-split inside the kernels. */
 int crc_conv2d_forms(crc_ctx *ctx, const uint64_t *d_x, const uint64_t *d_w_ntt, int w_form, const uint64_t *d_bias_delta,
@@ -265,9 +271,16 @@ int    crc_limb_pack_weights_tile(crc_ctx *ctx, const uint64_t *d_w_tile_ntt, in
  *                       2 polys x output pixels per launch), CRC_NTTP the vector-ALU kernel on 28-bit limb pairs, CRC_NTT canonical (moduli above 55 bits).
  *                       A dense layer is the 1 x 1 convolution zd = in_dim, nf = out_dim.  matrix_cores = 0 keeps everything on the vector ALU.
  *   crc_plan_fold_pool  whether folding a pooling layer into the convolution in front of it (crc_conv2d_fold_pool) pays, by the cost model of DESIGN.md section
- *   4 */
+ *   4
+ *   crc_plan_hoist_pool whether the pool behind a stride-1 convolution is hoisted in front of it instead (crc_conv2d_hoist_pool): u... is the geometry of the layer in
+ *                       front AS IT RUNS (already folded), a resident convolution -- uzd = 0 where there is no such layer (nothing in front, another kind of layer, a
+ *                       refresh in between, streamed or tile-wise weights).  No unless the convolution has stride 1, the pool decimates and crc_plan_fold_pool folds
+ *                       it, the layer in front takes the enlarged window on the kernel family it runs on, and the pair costs less that way on B images per launch
+ *                       (same units; the one-channel kernel's two forms are priced at the K they pay for).  Tuning key hoist_pool = 0 / CRC_HOIST_POOL=0: always no */
 int    crc_plan_mac(const crc_ctx *ctx, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int B, int matrix_cores, int *w_form);
 int    crc_plan_fold_pool(const crc_ctx *ctx, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int pxs, int pys, int pxf, int pyf, int *fold);
+int    crc_plan_hoist_pool(const crc_ctx *ctx, int uzd, int uxd, int uyd, int uxs, int uys, int uxf, int uyf, int unf, int zd, int xd, int yd, int xs, int ys,
+                           int xf, int yf, int nf, int pxs, int pys, int pxf, int pyf, int B, int matrix_cores, int *hoist);
 /* an NTT-form tensor (CRC_NTT canonical or CRC_NTTP) -> limb form; crc_conv2d_forms does this itself for such inputs, the separate entry point lets a
  * caller convert once and reuse (d_xl: crc_limb_tensor_bytes) */
 int    crc_limb_pack_tensor(crc_ctx *ctx, const uint64_t *d_x, int in_form, int B, int zd, int xd, int yd, void *d_xl, void *stream);

@@ -41,6 +41,16 @@ def fused_plan(E, model, names=None):
         if kind == "conv" and nxt and nxt[0] in ("pool", "avgpool"):
             pa = nxt[2]
             if E.plan_fold_pool(a["zd"], a["xd"], a["yd"], a["xs"], a["ys"], a["xf"], a["yf"], a["nf"], pa["xs"], pa["ys"], pa["xf"], pa["yf"]):
+                # ... or hoisted (crc_plan_hoist_pool, Network::fuse() step 1a): the layer in front takes the pool's stride-1 window sum into its weights, this one keeps
+                # its window and takes the pool's stride; both keep their names
+                up = folded[-1] if folded and folded[-1][0] == "conv" else None
+                geo = lambda g: (g["zd"], g["xd"], g["yd"], g["xs"], g["ys"], g["xf"], g["yf"], g["nf"])
+                if E.plan_hoist_pool(geo(up[2]) if up else None, geo(a), (pa["xs"], pa["ys"], pa["xf"], pa["yf"]), 0):
+                    u = up[2]
+                    sums = (up[4][0], up[4][1] - pa["xf"] + 1, up[4][2] - pa["yf"] + 1)
+                    folded[-1] = ["conv", up[1], dict(u, xf=(pa["xf"] - 1) * u["xs"] + u["xf"], yf=(pa["yf"] - 1) * u["ys"] + u["yf"]), up[3], sums]
+                    folded.append(["conv", name + "+" + nxt[1], dict(a, xd=sums[1], yd=sums[2], xs=pa["xs"], ys=pa["ys"]), sums, nxt[4]]); i += 2
+                    continue
                 a2 = dict(a, xf=(pa["xf"] - 1) * a["xs"] + a["xf"], yf=(pa["yf"] - 1) * a["ys"] + a["yf"], xs=a["xs"] * pa["xs"], ys=a["ys"] * pa["ys"])
                 folded.append(["conv", name + "+" + nxt[1], a2, ish, nxt[4]]); i += 2
                 continue
