@@ -185,6 +185,13 @@ def load():
     L.crc_noise_budget_dev.argtypes = [VP, VP, VP, SZ, CI, CI, VP, VP, VP, VP]
     L.crc_budget_bits_host.argtypes = [VP, PU, SZ, ctypes.POINTER(ctypes.c_int32)]
     L.crc_decode_dev.argtypes = [VP, VP, SZ, VP, VP]
+    L.crc_slots_supported.argtypes = [VP]
+    L.crc_slots_prime.argtypes = [CI, CI, PU]
+    PI64 = ctypes.POINTER(ctypes.c_int64)
+    L.crc_slots_compose.argtypes = [VP, PI64, SZ, CI, SZ, SZ, PU]
+    L.crc_slots_decompose.argtypes = [VP, PU, SZ, CI, PI64, SZ, SZ]
+    L.crc_slots_compose_dev.argtypes = [VP, VP, SZ, CI, SZ, SZ, VP, VP]
+    L.crc_slots_decompose_dev.argtypes = [VP, VP, SZ, CI, VP, SZ, SZ, VP]
     L.crc_encode_dev_f32.argtypes = [VP, VP, SZ, VP, VP]
     L.crc_encode_dev_f64.argtypes = [VP, VP, SZ, VP, VP]
     L.crc_refresh_dev_work_bytes.restype = SZ; L.crc_refresh_dev_work_bytes.argtypes = [VP, SZ, CI]
@@ -374,6 +381,44 @@ class Engine:
 
     def decode(self, plain):
         return self.L.crc_decode(self.c, _pu(np.ascontiguousarray(plain)))
+
+    # ---- slot batching: n numbers of Z_t per plaintext (prime t = 1 mod 2n); (item c, slot i) at values[c * item_stride + i * slot_stride]
+    @property
+    def slots_supported(self):
+        return bool(self.L.crc_slots_supported(self.c))
+
+    @staticmethod
+    def slots_prime(n, bits):
+        """the largest prime below 2**bits that is 1 mod 2n"""
+        t = u64(0)
+        _chk(load().crc_slots_prime(int(n), int(bits), ctypes.byref(t)), "crc_slots_prime")
+        return int(t.value)
+
+    def slots_compose(self, values, count, slots, item_stride, slot_stride):
+        """host twin: int64 values (flat, strided) -> plaintexts [count][n]"""
+        values = np.ascontiguousarray(values, dtype=np.int64).reshape(-1)
+        assert values.size > (count - 1) * item_stride + (slots - 1) * slot_stride
+        out = np.zeros((count, self.n), dtype=np.uint64)
+        _chk(self.L.crc_slots_compose(self.c, values.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), count, slots, item_stride, slot_stride, _pu(out)),
+             "crc_slots_compose")
+        return out
+
+    def slots_decompose(self, plains, slots, item_stride, slot_stride, size=None):
+        """host twin: plaintexts [count][n] -> flat int64 array of `size` words (default: just what the strides reach), untouched words 0"""
+        plains = np.ascontiguousarray(plains, dtype=np.uint64).reshape(-1, self.n); count = plains.shape[0]
+        need = (count - 1) * item_stride + (slots - 1) * slot_stride + 1
+        out = np.zeros(need if size is None else size, dtype=np.int64)
+        assert out.size >= need
+        _chk(self.L.crc_slots_decompose(self.c, _pu(plains), count, slots, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), item_stride, slot_stride),
+             "crc_slots_decompose")
+        return out
+
+    def slots_compose_dev(self, d_values, count, slots, item_stride, slot_stride, d_plain):
+        _chk(self.L.crc_slots_compose_dev(self.c, self.p(d_values), count, slots, item_stride, slot_stride, self.p(d_plain), self.stream), "crc_slots_compose_dev")
+
+    def slots_decompose_dev(self, d_plain, count, slots, d_values, item_stride, slot_stride):
+        _chk(self.L.crc_slots_decompose_dev(self.c, self.p(d_plain), count, slots, self.p(d_values), item_stride, slot_stride, self.stream),
+             "crc_slots_decompose_dev")
 
     def keygen(self, seed):
         sk = np.zeros((self.k, self.n), dtype=np.uint64); pk = np.zeros((2, self.k, self.n), dtype=np.uint64)

@@ -597,6 +597,41 @@ extern "C" int crc_budget_bits_host(const crc_ctx *c, const uint64_t *h_v, size_
     if (!c || !h_v || !h_bits) return CRC_ERR_INVALID_ARGUMENT;
     return k_budget_bits_host(c, h_v, count, h_bits);
 }
+// Slot batching (kernels_slots.hip).  The parameter check comes first: a context without slots answers CRC_ERR_PARAMETERS whatever else is wrong
+static int slots_args_ok(const crc_ctx *c, const void *values, const void *plain, int slots, size_t item_stride, size_t slot_stride)
+{
+    if (!crc_slots_supported(c)) return CRC_ERR_PARAMETERS;
+    if (!values || !plain || slots < 1 || slots > c->n || !item_stride || !slot_stride) return CRC_ERR_INVALID_ARGUMENT;
+    return CRC_OK;
+}
+extern "C" int crc_slots_compose(crc_ctx *c, const int64_t *h_values, size_t count, int slots, size_t item_stride, size_t slot_stride, uint64_t *h_plain)
+{
+    if (!c) return CRC_ERR_INVALID_ARGUMENT;
+    RUN(slots_args_ok(c, h_values, h_plain, slots, item_stride, slot_stride));
+    return k_slots_compose_host(c, (const long long *)h_values, count, slots, item_stride, slot_stride, h_plain);
+}
+extern "C" int crc_slots_decompose(crc_ctx *c, const uint64_t *h_plain, size_t count, int slots, int64_t *h_values, size_t item_stride, size_t slot_stride)
+{
+    if (!c) return CRC_ERR_INVALID_ARGUMENT;
+    RUN(slots_args_ok(c, h_values, h_plain, slots, item_stride, slot_stride));
+    return k_slots_decompose_host(c, h_plain, count, slots, (long long *)h_values, item_stride, slot_stride);
+}
+extern "C" int crc_slots_compose_dev(crc_ctx *c, const int64_t *d_values, size_t count, int slots, size_t item_stride, size_t slot_stride, uint64_t *d_plain,
+                                     void *stream)
+{
+    CHECK_CTX(c);
+    RUN(slots_args_ok(c, d_values, d_plain, slots, item_stride, slot_stride));
+    if (((uintptr_t)d_plain & 15) || ((uintptr_t)d_values & 7)) return CRC_ERR_INVALID_ARGUMENT;
+    return k_slots_compose(c, (const long long *)d_values, count, slots, item_stride, slot_stride, d_plain, S(stream));
+}
+extern "C" int crc_slots_decompose_dev(crc_ctx *c, const uint64_t *d_plain, size_t count, int slots, int64_t *d_values, size_t item_stride, size_t slot_stride,
+                                       void *stream)
+{
+    CHECK_CTX(c);
+    RUN(slots_args_ok(c, d_values, d_plain, slots, item_stride, slot_stride));
+    if (((uintptr_t)d_plain & 15) || ((uintptr_t)d_values & 7)) return CRC_ERR_INVALID_ARGUMENT;
+    return k_slots_decompose(c, d_plain, count, slots, (long long *)d_values, item_stride, slot_stride, S(stream));
+}
 extern "C" int crc_decode_dev(crc_ctx *c, const uint64_t *d_plain, size_t count, double *d_out, void *stream)
 {
     CHECK_CTX(c); if (!d_plain || !d_out) return CRC_ERR_INVALID_ARGUMENT;

@@ -475,7 +475,9 @@ extern "C" void crc_ctx_destroy(crc_ctx *c)
     if (c->device >= 0) {
         (void)hipFree(c->d_mods); (void)hipFree(c->d_rp); (void)hipFree(c->d_irp2); (void)hipFree(c->d_irp); (void)hipFree(c->d_behz); (void)hipFree(c->d_zero);
         (void)hipFree(c->d_f64_rp); (void)hipFree(c->d_f64_irp); (void)hipFree(c->d_sq64);
+        if (c->slots) { (void)hipFree(c->slots->d_fwd); (void)hipFree(c->slots->d_inv); (void)hipFree(c->slots->d_idx); }
     }
+    delete c->slots;
     delete c;
 }
 
@@ -488,6 +490,65 @@ int crc_ctx_ensure_lds(crc_ctx *c, const void *kernel, size_t lds_bytes)
     if (it != c->lds_attr.end() && it->second >= lds_bytes) return CRC_OK;
     HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     c->lds_attr[kernel] = lds_bytes;
+    return CRC_OK;
+}
+
+// ---- slot batching: which contexts have slots, the prime search, the tables -----------------------------------
+extern "C" int crc_slots_supported(const crc_ctx *c)
+{
+    if (!c) return 0;
+    const u64 t = c->t;
+    if (!is_prime(t) || (t - 1) % (2 * (u64)c->n)) return 0;
+    // t must not be one of the moduli the context computes with: base conversions between equal moduli have no inverse
+    for (int i = 0; i < c->k; i++) if (t == c->q[i]) return 0;
+    for (int j = 0; j < c->kb; j++) if (t == c->tabs[c->k + j].m.q) return 0;
+    if (t == kGamma) return 0;
+    for (int m = 0; m < c->nf64; m++) if (t == c->f64_primes[m]) return 0;
+    return 1;
+}
+extern "C" int crc_slots_prime(int n, int bits, uint64_t *t)
+{
+    if (!t || n < 2 || (n & (n - 1)) || bits < 2 || bits > 60) return CRC_ERR_INVALID_ARGUMENT;
+    const u64 m = 2 * (u64)n, top = (u64)1 << bits;
+    if (top <= m) return CRC_ERR_NOT_FOUND;
+    for (u64 cand = (top - 2) / m * m + 1; cand > m; cand -= m) if (is_prime(cand)) { *t = cand; return CRC_OK; }
+    return CRC_ERR_NOT_FOUND;
+}
+int crc_slots_tables(crc_ctx *c, const SlotTables **out)
+{
+    if (!crc_slots_supported(c)) return CRC_ERR_PARAMETERS;
+    std::lock_guard<std::mutex> g(c->slots_mu);
+    if (!c->slots) {
+        SlotTables *s = new SlotTables();
+        const int n = c->n, logn = c->logn;
+        if (!build_ntt(s->T, logn, c->t, true)) { delete s; return CRC_ERR_PARAMETERS; }
+        s->one_s = (u64)(((u128)1 << 64) / c->t);
+        s->lazy = s->T.m.bits <= 57;
+        // polycrt.cpp:82-106: slot i sits where the transform leaves p(psi^(3^i)), slot n/2 + i where it leaves p(psi^(-3^i))
+        s->idx.assign(n, 0);
+        const u64 m = 2 * (u64)n;
+        u64 pos = 1;
+        for (int i = 0; i < n / 2; i++) {
+            s->idx[i] = bitrev((u32)((pos - 1) >> 1), logn);
+            s->idx[n / 2 + i] = bitrev((u32)((m - pos - 1) >> 1), logn);
+            pos = pos * 3 % m;
+        }
+        if (c->device >= 0) {
+            std::vector<u64> fw((size_t)n * 2), iv((size_t)n * 2);
+            for (int i = 0; i < n; i++) { fw[2 * i] = s->T.rp[i]; fw[2 * i + 1] = s->T.srp[i]; iv[2 * i] = s->T.irp2[i]; iv[2 * i + 1] = s->T.sirp2[i]; }
+            hipError_t e;
+            if ((e = hipSetDevice(c->device)) != hipSuccess || (e = hipMalloc(&s->d_fwd, (size_t)n * 16)) != hipSuccess ||
+                (e = hipMalloc(&s->d_inv, (size_t)n * 16)) != hipSuccess || (e = hipMalloc(&s->d_idx, (size_t)n * 4)) != hipSuccess ||
+                (e = hipMemcpy(s->d_fwd, fw.data(), (size_t)n * 16, hipMemcpyHostToDevice)) != hipSuccess ||
+                (e = hipMemcpy(s->d_inv, iv.data(), (size_t)n * 16, hipMemcpyHostToDevice)) != hipSuccess ||
+                (e = hipMemcpy(s->d_idx, s->idx.data(), (size_t)n * 4, hipMemcpyHostToDevice)) != hipSuccess) {
+                (void)hipFree(s->d_fwd); (void)hipFree(s->d_inv); (void)hipFree(s->d_idx); delete s;
+                return crc_set_hip_error(e);
+            }
+        }
+        c->slots = s;
+    }
+    *out = c->slots;
     return CRC_OK;
 }
 
@@ -520,6 +581,11 @@ extern "C" int crc_ctx_table(const crc_ctx *c, const char *name, uint64_t *out, 
     else if (s.rfind("root_powers:", 0) == 0) { int mi = atoi(name + 12); if (mi < 0 || mi >= k + kb) return CRC_ERR_INVALID_ARGUMENT; v = c->tabs[mi].rp; }
     else if (s.rfind("inv_root_powers_div_two:", 0) == 0) { int mi = atoi(name + 24); if (mi < 0 || mi >= k + kb) return CRC_ERR_INVALID_ARGUMENT;
         v = c->tabs[mi].irp2; }
+    else if (s == "slots_root" || s == "slots_index_map") {
+        const SlotTables *st; const int rc = crc_slots_tables(const_cast<crc_ctx *>(c), &st);      // (built on first use, under the context's lock)
+        if (rc) return rc;
+        if (s == "slots_root") v.push_back(st->T.root); else v.assign(st->idx.begin(), st->idx.end());
+    }
     else return CRC_ERR_NOT_FOUND;
     for (size_t i = 0; i < v.size() && (int)i < cap; i++) out[i] = v[i];
     return (int)v.size();

@@ -136,6 +136,17 @@ struct CrcTuning {
     int relin_path = 0;           // CRC_RELIN_PATH=0: by parameters, 1: key switching over the coefficient moduli (round-2 path), 2: over the two fp64 primes
 };
 
+// Slot (batching) tables of a prime plain modulus t = 1 mod 2n (SEAL's PolyCRTBuilder, polycrt.cpp:82-147): the transform tables of t, as build_ntt makes them
+// for any other modulus, and the slot -> position map.  Built on first use (crc_slots_tables), never by crc_ctx_create
+struct SlotTables {
+    HostNtt T;
+    std::vector<u32> idx;                    // idx[i]: position of slot i in the (bit-reversed) transform of the plaintext
+    u64 one_s = 0;                           // floor(2^64 / t): Shoup companion of 1 -- mulmod_shoup(v, 1, one_s, t) is v mod t for any 64-bit v
+    bool lazy = false;                       // t < 2^57: the lazy butterflies of ntt_device.h
+    ulonglong2 *d_fwd = nullptr, *d_inv = nullptr;   // [n] {root power, Shoup companion}: forward / inverse-div-2 (device contexts only)
+    u32 *d_idx = nullptr;
+};
+
 struct crc_ctx {
     int n, logn, k, ka, kb, device;
     CrcTuning tune;
@@ -167,7 +178,11 @@ struct crc_ctx {
     // kernels whose dynamic-LDS limit has been raised on this context's device (hipFuncSetAttribute is a driver call: once, not per launch)
     std::mutex attr_mu;
     std::unordered_map<const void *, size_t> lds_attr;
+    std::mutex slots_mu;
+    SlotTables *slots = nullptr;             // null until the first slot call on a context that supports slots
 };
+// CRC_ERR_PARAMETERS where crc_slots_supported is 0; builds (and, on a device context, uploads) the tables on the first call
+int crc_slots_tables(crc_ctx *c, const SlotTables **out);
 int crc_ctx_ensure_lds(crc_ctx *c, const void *kernel, size_t lds_bytes);
 
 int  crc_set_hip_error(hipError_t e);

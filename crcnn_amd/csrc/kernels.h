@@ -92,6 +92,12 @@ int k_decrypt_rows(crc_ctx *c, const u64 *sk, const u64 *ct, size_t cnt, int siz
 int k_noise_budget(crc_ctx *c, const u64 *sk, const u64 *ct, size_t cnt, int size, bool in_ntt, int32_t *bits, int32_t *min_out, u64 *work, hipStream_t st);
 int k_budget_bits_host(const crc_ctx *c, const u64 *h_v, size_t cnt, int32_t *h_bits);
 
+// kernels_slots.hip: slot batching -- values (item c, slot i) at values[c item_stride + i slot_stride] <-> plaintexts [count][n]; *_host: the host twins
+int k_slots_compose(crc_ctx *c, const long long *d_values, size_t count, int slots, size_t item_stride, size_t slot_stride, u64 *d_plain, hipStream_t st);
+int k_slots_decompose(crc_ctx *c, const u64 *d_plain, size_t count, int slots, long long *d_values, size_t item_stride, size_t slot_stride, hipStream_t st);
+int k_slots_compose_host(crc_ctx *c, const long long *values, size_t count, int slots, size_t item_stride, size_t slot_stride, u64 *plain);
+int k_slots_decompose_host(crc_ctx *c, const u64 *plain, size_t count, int slots, long long *values, size_t item_stride, size_t slot_stride);
+
 // kernels_mfma.hip: conv / dense multiply-accumulate as an int8 limb GEMM on the matrix cores (operand form CRC_NTTL)
 bool   k_limb_supported(const crc_ctx *c, int T);
 size_t k_limb_tensor_bytes(const crc_ctx *c, int B, int zd, int npos);

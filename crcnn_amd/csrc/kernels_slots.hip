@@ -1,0 +1,90 @@
+// kernels_slots.hip -- slot batching (SEAL's PolyCRTBuilder, polycrt.cpp:82-147, 327-370) for whole tensors of plaintexts on gfx950, and its host twins.
+//
+// For a prime plain modulus t = 1 mod 2n a plaintext polynomial p is n independent numbers of Z_t: slot i is p(psi^(3^i)), slot n/2 + i is p(psi^(-3^i)), psi
+// the minimal primitive 2n-th root of unity mod t.  compose: values -> the row positions idx[i] -> inverse negacyclic transform mod t -> coefficients;
+// decompose: coefficients -> forward transform -> positions idx[i] -> centred values.  One workgroup per row, the row in LDS, ntt_device.h's passes with t's
+// tables; the permutation, the reduction of the int64 inputs mod t, the zero fill and the centring sit in the loops that fill / drain the image, so a row costs
+// one read and one write of 8 n bytes and nothing else touches memory.
+//
+// A device kernel cannot throw: where SEAL refuses a value outside the plain modulus, every int64 is accepted here and taken as its residue mod t.
+#include "kernels.h"
+#include "host_parallel.h"
+#include "slots_device.h"      // SlotArgs, the block -> item order, the two kernel bodies
+
+template <bool LAZY>
+__global__ void __launch_bounds__(1024) slots_compose_kernel(SlotArgs a)
+{
+    extern __shared__ u64 sm[];
+    slots_compose_body<LAZY>(a, sm);
+}
+template <bool LAZY>
+__global__ void __launch_bounds__(1024) slots_decompose_kernel(SlotArgs a)
+{
+    extern __shared__ u64 sm[];
+    slots_decompose_body<LAZY>(a, sm);
+}
+
+static int slots_launch(crc_ctx *c, bool compose, SlotArgs &a, hipStream_t st)
+{
+    const SlotTables *T;
+    { const int rc = crc_slots_tables(c, &T); if (rc) return rc; }
+    if (a.count == 0) return CRC_OK;
+    const size_t lds = (size_t)c->n * 8;
+    if (lds > 128 * 1024) return CRC_ERR_UNSUPPORTED;                 // (n = 32768: the row does not fit the LDS; the host twins serve it)
+    const size_t groups = (a.count + CRC_SLOT_GROUP - 1) / CRC_SLOT_GROUP;
+    if ((groups + 7) / 8 * 8 * CRC_SLOT_GROUP > 0x7fffffffULL) return CRC_ERR_INVALID_ARGUMENT;
+    a.W = compose ? T->d_inv : T->d_fwd; a.idx = T->d_idx;
+    a.n = c->n; a.logn = c->logn; a.t = c->t; a.one_s = T->one_s;
+    int nt = c->n / 8; if (nt < 64) nt = 64; if (nt > 1024) nt = 1024;
+    auto kern = compose ? (T->lazy ? slots_compose_kernel<true> : slots_compose_kernel<false>)
+                        : (T->lazy ? slots_decompose_kernel<true> : slots_decompose_kernel<false>);
+    { const int rc = crc_ctx_ensure_lds(c, (const void *)kern, lds); if (rc) return rc; }
+    hipLaunchKernelGGL(kern, dim3(xcd_grid(groups, CRC_SLOT_GROUP)), dim3(nt), lds, st, a);
+    HIPCHK(hipGetLastError());
+    return CRC_OK;
+}
+
+int k_slots_compose(crc_ctx *c, const long long *d_values, size_t count, int slots, size_t item_stride, size_t slot_stride, u64 *d_plain, hipStream_t st)
+{
+    SlotArgs a{};
+    a.vals_in = d_values; a.plain_out = d_plain; a.count = count; a.slots = slots; a.item_stride = item_stride; a.slot_stride = slot_stride;
+    return slots_launch(c, true, a, st);
+}
+int k_slots_decompose(crc_ctx *c, const u64 *d_plain, size_t count, int slots, long long *d_values, size_t item_stride, size_t slot_stride, hipStream_t st)
+{
+    SlotArgs a{};
+    a.plain_in = d_plain; a.vals_out = d_values; a.count = count; a.slots = slots; a.item_stride = item_stride; a.slot_stride = slot_stride;
+    return slots_launch(c, false, a, st);
+}
+
+// ---- host twins (any context, device = -1 included): the reference transforms of ctx.cpp on the same tables ----------------------------------------------
+int k_slots_compose_host(crc_ctx *c, const long long *values, size_t count, int slots, size_t item_stride, size_t slot_stride, u64 *plain)
+{
+    const SlotTables *T;
+    { const int rc = crc_slots_tables(c, &T); if (rc) return rc; }
+    const int n = c->n; const long long t = (long long)c->t;
+    crc_host::parallel_for(count, 4, [&](size_t b, size_t e) {
+        for (size_t m = b; m < e; m++) {
+            u64 *row = plain + m * (size_t)n;
+            for (int i = 0; i < n; i++) row[i] = 0;
+            for (int i = 0; i < slots; i++) { long long r = values[m * item_stride + (size_t)i * slot_stride] % t; if (r < 0) r += t; row[T->idx[i]] = (u64)r; }
+            h_ntt_inv(T->T, row, n);
+        }
+    });
+    return CRC_OK;
+}
+int k_slots_decompose_host(crc_ctx *c, const u64 *plain, size_t count, int slots, long long *values, size_t item_stride, size_t slot_stride)
+{
+    const SlotTables *T;
+    { const int rc = crc_slots_tables(c, &T); if (rc) return rc; }
+    const int n = c->n; const u64 t = c->t, half = (t - 1) >> 1;
+    crc_host::parallel_for(count, 4, [&](size_t b, size_t e) {
+        std::vector<u64> row((size_t)n);
+        for (size_t m = b; m < e; m++) {
+            for (int i = 0; i < n; i++) row[i] = plain[m * (size_t)n + i] % t;
+            h_ntt_fwd(T->T, row.data(), n);
+            for (int i = 0; i < slots; i++) { const u64 r = row[T->idx[i]]; values[m * item_stride + (size_t)i * slot_stride] = r > half ? (long long)r - (long long)t : (long long)r; }
+        }
+    });
+    return CRC_OK;
+}

@@ -30,6 +30,11 @@ static bool g_det = false;                                  // setDeterministicS
 static uint64_t g_det_seed = 0;
 static uint8_t g_master_key[CRC_KEY_BYTES];                 // fresh from the OS on every setParameters()
 static uint64_t g_enc_counter = 0;                          // ciphertexts encrypted under g_master_key so far (= next keystream id)
+// slot encoding (setSlotEncoding): scalar plaintexts instead of the fractional encoder
+static bool g_slot_on = false;
+static int g_slot_in_bits = 0, g_slot_w_bits = 0;
+static uint64_t g_plain_modulus = 0;                        // t of the current context
+static double g_enc_scale[2] = {0, 0};                      // slot encoding: scales of the first / second dataset of the layer CnnBuilder builds next
 void setDeterministicSeed(uint64_t seed) { g_det = true; g_det_seed = seed; }
 void clearDeterministicSeed() { g_det = false; }
 
@@ -132,6 +137,27 @@ static Plaintext fromDense(const uint64_t *co, int n, int cc)
     for (int i = 0; i < n; i++) if (co[i]) p.nz.emplace_back(i, co[i]);
     return p;
 }
+// slot encoding: the constant polynomial nearbyint(value * scale) mod t -- the same number in every slot
+static Plaintext scalarPlain(double value, double scale)
+{
+    const double r = nearbyint(value * scale);
+    if (!(fabs(r) < 9.2e18)) throw invalid_argument("slot encoding: value * scale does not fit an int64");
+    long long v = (long long)r % (long long)g_plain_modulus;
+    if (v < 0) v += (long long)g_plain_modulus;
+    Plaintext p; p.coeff_count_ = 1;
+    if (v) p.nz.emplace_back(0, (uint64_t)v);
+    return p;
+}
+// the one switch between the two encodings: scale 0 = the fractional encoder
+static Plaintext encodeScaled(double value, double scale) { return scale != 0 ? scalarPlain(value, scale) : fraencode(value); }
+void setSlotEncoding(int input_bits, int weight_bits)
+{
+    if (!crc_slots_supported(ctx())) throw invalid_argument("setSlotEncoding: the plain modulus must be a prime that is 1 mod 2n and none of the engine's moduli");
+    if (input_bits < 0 || input_bits > 30 || weight_bits < 0 || weight_bits > 30) throw invalid_argument("setSlotEncoding: bit counts must be in 0..30");
+    g_slot_on = true; g_slot_in_bits = input_bits; g_slot_w_bits = weight_bits;
+}
+void clearSlotEncoding() { g_slot_on = false; g_enc_scale[0] = g_enc_scale[1] = 0; }
+bool slotEncoding() { return g_slot_on; }
 Plaintext fraencode(double value)
 {
     vector<uint64_t> co((size_t)N()); int32_t cc = 0;
@@ -270,6 +296,7 @@ void setParameters(int poly_modulus, const vector<uint64_t> &coeff_modulus, uint
     delParameters();
     chk(crc_ctx_create(poly_modulus, coeff_modulus.data(), (int)coeff_modulus.size(), plain_modulus, device, &context),
         "encryption parameters are not set correctly");
+    g_plain_modulus = plain_modulus;
     const int n = N(), k = K();
     secret_key.assign((size_t)k * n, 0); public_key.assign((size_t)2 * k * n, 0);
     ev_keys16_host.assign(crc_evk_words(context, 16), 0);                  // keygen->generate_evaluation_keys(16, *ev_keys16), globals.cpp:54
@@ -315,6 +342,7 @@ void delParameters()
     g_d_sk.reset(); g_d_pk.reset();
     g_scratch.reset(); g_wltile.reset(); g_xltile.reset();
     g_pool.flush();
+    clearSlotEncoding();
     if (context) { crc_ctx_destroy(context); context = nullptr; }
 }
 static void writeFile(const string &path, const vector<uint8_t> &b) { ofstream f(path, ofstream::binary); if (!f) throw runtime_error("cannot write " + path);
@@ -531,6 +559,74 @@ ciphertext3D expandSeeded(const SeededImages &im, int out_form)
     ciphertext3D out(im.B, im.zd, im.xd, im.yd, out_form);
     expandSeeded((const uint64_t *)d_c0.ptr, im.B, im.zd, im.xd, im.yd, im.seed, im.stream_base, out);
     chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");     // the packed rows and the host vector are released here
+    return out;
+}
+// ---- slot-batched client side ------------------------------------------------------------------------------------------------
+ciphertext3D encryptImageSlots(const vector<vector<int64_t>> &images, int zd, int xd, int yd, int out_form)
+{
+    if (!g_slot_on) throw logic_error("encryptImageSlots: setSlotEncoding() must be called first");
+    const size_t per = (size_t)zd * xd * yd, S = images.size();
+    if (zd < 1 || xd < 1 || yd < 1 || S < 1 || S > (size_t)N()) throw invalid_argument("encryptImageSlots: 1 to n images of [zd][xd][yd] pixels");
+    if (out_form != CRC_COEFF && out_form != CRC_NTT) throw invalid_argument("encryptImageSlots: ciphertext forms only (CRC_COEFF / CRC_NTT)");
+    vector<int64_t> h(S * per);
+    for (size_t j = 0; j < S; j++) {
+        if (images[j].size() != per) throw invalid_argument("encryptImageSlots: every image must have zd xd yd pixels");
+        memcpy(h.data() + j * per, images[j].data(), per * 8);
+    }
+    DeviceBuffer d_v(h.size() * 8), d_pl(per * (size_t)N() * 8), d_work(crc_encrypt_dev_work_bytes(ctx(), per));
+    const uint64_t *d_pk = deviceKey(g_d_pk, g_d_pk_fp, public_key, "public key");
+    chk(crc_memcpy_h2d(ctx(), d_v.ptr, h.data(), h.size() * 8, stream()), "crc_memcpy_h2d");
+    // image-major: pixel c of image j at h[j per + c]
+    chk(crc_slots_compose_dev(ctx(), (const int64_t *)d_v.ptr, per, (int)S, 1, per, (uint64_t *)d_pl.ptr, stream()), "crc_slots_compose_dev");
+    ciphertext3D out(1, zd, xd, yd, out_form);
+    if (g_det)
+        chk(crc_encrypt_dev_forms(ctx(), d_pk, (const uint64_t *)d_pl.ptr, per, g_det_seed + 1000003 * (g_enc_counter + 1), out_form, (uint64_t *)out.data(),
+                                  d_work.ptr, stream()), "crc_encrypt_dev_forms");
+    else
+        chk(crc_encrypt_dev_key_forms(ctx(), d_pk, (const uint64_t *)d_pl.ptr, per, g_master_key, g_enc_counter, out_form, (uint64_t *)out.data(), d_work.ptr,
+                                      stream()), "crc_encrypt_dev_key_forms");
+    g_enc_counter += per;
+    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+    return out;
+}
+ciphertext3D encryptImageSlots(const vector<vector<float>> &images, int zd, int xd, int yd, int out_form)
+{
+    if (!g_slot_on) throw logic_error("encryptImageSlots: setSlotEncoding() must be called first");
+    const double scale = ldexp(1.0, g_slot_in_bits);
+    vector<vector<int64_t>> q(images.size());
+    for (size_t j = 0; j < images.size(); j++) {
+        q[j].resize(images[j].size());
+        for (size_t i = 0; i < images[j].size(); i++) {
+            const double r = nearbyint((double)images[j][i] * scale);
+            if (!(fabs(r) < 9.2e18)) throw invalid_argument("encryptImageSlots: a pixel does not fit an int64 at this scale");
+            q[j][i] = (int64_t)r;
+        }
+    }
+    return encryptImageSlots(q, zd, xd, yd, out_form);
+}
+vector<vector<int64_t>> decryptSlots(const ciphertext3D &t, int S)
+{
+    if (!t.buf || t.count() == 0) throw invalid_argument("decryptSlots: empty tensor");
+    if (t.form != CRC_COEFF && t.form != CRC_NTT) throw invalid_argument("decryptSlots: ciphertext forms only (CRC_COEFF / CRC_NTT)");
+    if (S < 1 || S > N()) throw invalid_argument("decryptSlots: 1 to n slots");
+    const size_t cnt = t.count();
+    const uint64_t *d_sk = deviceKey(g_d_sk, g_d_sk_fp, secret_key, "secret key");
+    DeviceBuffer d_pl(cnt * (size_t)N() * 8), d_v(cnt * (size_t)S * 8), d_work(crc_decrypt_dev_work_bytes(ctx(), cnt, 2, t.form));
+    chk(crc_decrypt_dev(ctx(), d_sk, t.data(), cnt, 2, t.form, (uint64_t *)d_pl.ptr, d_work.ptr, stream()), "crc_decrypt_dev");
+    chk(crc_slots_decompose_dev(ctx(), (const uint64_t *)d_pl.ptr, cnt, S, (int64_t *)d_v.ptr, 1, cnt, stream()), "crc_slots_decompose_dev");
+    vector<int64_t> h(cnt * (size_t)S);
+    chk(crc_memcpy_d2h(ctx(), h.data(), d_v.ptr, h.size() * 8, stream()), "crc_memcpy_d2h");
+    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+    vector<vector<int64_t>> out(S);
+    for (int j = 0; j < S; j++) out[j].assign(h.begin() + (size_t)j * cnt, h.begin() + (size_t)(j + 1) * cnt);
+    return out;
+}
+vector<vector<double>> decryptImageSlots(const ciphertext3D &t, int S, double scale)
+{
+    if (!(scale > 0)) throw invalid_argument("decryptImageSlots: the scale must be positive (Network::slot_scale())");
+    const vector<vector<int64_t>> v = decryptSlots(t, S);
+    vector<vector<double>> out(v.size());
+    for (size_t j = 0; j < v.size(); j++) { out[j].resize(v[j].size()); for (size_t i = 0; i < v[j].size(); i++) out[j][i] = (double)v[j][i] / scale; }
     return out;
 }
 vector<floatCube> decryptImages(const ciphertext3D &t)
@@ -1066,6 +1162,8 @@ void PoolingLayer::printLayerStructure()
 }
 AvgPoolingLayer::AvgPoolingLayer(string name, int xd, int yd, int zd, int xs, int ys, int xf, int yf) : PoolingLayer(name, xd, yd, zd, xs, ys, xf, yf)
 {
+    // slot encoding has no 1 / (xf yf): the layer is the sum pool (no divisor row) and the scale ledger carries the factor xf yf
+    if (g_slot_on) { div_factor = scalarPlain(1.0, 1.0); return; }
     div_factor = fraencode(1. / (xf * yf));                 // avgPoolingLayer.cpp:12
     d_div = uploadPlain({&div_factor}, 0);
 }
@@ -1139,7 +1237,7 @@ void SquarePoolLayer::printLayerStructure()
 
 // ---- polynomial activation ------------------------------------------------------------------------------------------------
 // the three NTT-form rows crc_poly2_*_relin_forms take (empty = 1, 0, 0), with the window count and the divisor of a pooling behind the activation folded in
-static void polyRows(float c2, float c1, float c0, int window, const shared_ptr<DeviceBuffer> &d_div, shared_ptr<DeviceBuffer> out[3])
+static void polyRows(float c2, float c1, float c0, int window, const shared_ptr<DeviceBuffer> &d_div, shared_ptr<DeviceBuffer> out[3], const double *sc)
 {
     const size_t rowb = (size_t)K() * N() * 8;
     auto copyOf = [&](const shared_ptr<DeviceBuffer> &src) {
@@ -1151,11 +1249,11 @@ static void polyRows(float c2, float c1, float c0, int window, const shared_ptr<
         if (d_div) chk(crc_multiply_plain_ntt(ctx(), (uint64_t *)r->ptr, (const uint64_t *)d_div->ptr, 1, 1, 1, stream()), "crc_multiply_plain_ntt");
     };
     out[0].reset(); out[1].reset(); out[2].reset();
-    if (c2 != 1.0f) { const Plaintext p = fraencode((double)c2); out[0] = uploadPlain({&p}, 0); timesDiv(out[0]); }
+    if (c2 != 1.0f || sc[0] != 0) { const Plaintext p = encodeScaled((double)c2, sc[0]); out[0] = uploadPlain({&p}, 0); timesDiv(out[0]); }    // (a scaled 1 is not 1)
     else if (d_div) out[0] = copyOf(d_div);
-    if (c1 != 0.0f) { const Plaintext p = fraencode((double)c1); out[1] = uploadPlain({&p}, 0); timesDiv(out[1]); }
+    if (c1 != 0.0f) { const Plaintext p = encodeScaled((double)c1, sc[1]); out[1] = uploadPlain({&p}, 0); timesDiv(out[1]); }
     if (c0 != 0.0f) {
-        const Plaintext p = fraencode((double)c0);
+        const Plaintext p = encodeScaled((double)c0, sc[2]);
         const shared_ptr<DeviceBuffer> one = uploadPlain({&p}, 2);
         out[2] = copyOf(one);
         for (int w = 1; w < window; w++) chk(crc_add(ctx(), (uint64_t *)out[2]->ptr, (const uint64_t *)one->ptr, 1, 1, stream()), "crc_add");
@@ -1179,7 +1277,7 @@ ciphertext3D PolyLayer::forward(ciphertext3D input)
     if (!input.buf) throw invalid_argument("PolyLayer: empty input");
     if (!ev_keys16) throw invalid_argument("not enough evaluation keys");
     if (out_form != CRC_NTT && out_form != CRC_COEFF) throw invalid_argument("PolyLayer: out_form must be CRC_NTT or CRC_COEFF");
-    if (!uploaded) { polyRows(c2, c1, c0, 1, nullptr, d_p); uploaded = true; }
+    if (!uploaded) { polyRows(c2, c1, c0, 1, nullptr, d_p, slot_scale); uploaded = true; }
     ciphertext3D out(input.B, input.zd, input.xd, input.yd, out_form);
     ensure(g_scratch, crc_poly2_relin_work_bytes(ctx(), input.count(), 16));
     chk(crc_poly2_relin_forms(ctx(), input.data(), input.form, input.count(), (const uint64_t *)ev_keys16->ptr, 16, rowPtr(d_p[0]), rowPtr(d_p[1]), rowPtr(d_p[2]),
@@ -1218,10 +1316,10 @@ ciphertext3D Poly3Layer::forward(ciphertext3D input)
     if (out_form != CRC_NTT && out_form != CRC_COEFF) throw invalid_argument("Poly3Layer: out_form must be CRC_NTT or CRC_COEFF");
     if (!uploaded) {
         for (auto &r : d_p) r.reset();
-        if (c3 != 1.0f) { const Plaintext p = fraencode((double)c3); d_p[0] = uploadPlain({&p}, 0); }
-        if (c2 != 0.0f) { const Plaintext p = fraencode((double)c2); d_p[1] = uploadPlain({&p}, 0); }
-        if (c1 != 0.0f) { const Plaintext p = fraencode((double)c1); d_p[2] = uploadPlain({&p}, 0); }
-        if (c0 != 0.0f) { const Plaintext p = fraencode((double)c0); d_p[3] = uploadPlain({&p}, 2); }
+        if (c3 != 1.0f || slot_scale[0] != 0) { const Plaintext p = encodeScaled((double)c3, slot_scale[0]); d_p[0] = uploadPlain({&p}, 0); }
+        if (c2 != 0.0f) { const Plaintext p = encodeScaled((double)c2, slot_scale[1]); d_p[1] = uploadPlain({&p}, 0); }
+        if (c1 != 0.0f) { const Plaintext p = encodeScaled((double)c1, slot_scale[2]); d_p[2] = uploadPlain({&p}, 0); }
+        if (c0 != 0.0f) { const Plaintext p = encodeScaled((double)c0, slot_scale[3]); d_p[3] = uploadPlain({&p}, 2); }
         chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
         uploaded = true;
     }
@@ -1250,7 +1348,7 @@ ciphertext3D PolyPoolLayer::forward(ciphertext3D input)
     checkInput(input, zd, xd, yd, "PolyPoolLayer");
     if (!ev_keys16) throw invalid_argument("not enough evaluation keys");
     if (out_form != CRC_NTT && out_form != CRC_COEFF) throw invalid_argument("PolyPoolLayer: out_form must be CRC_NTT or CRC_COEFF");
-    if (!uploaded) { polyRows(c2, c1, c0, xf * yf, d_div, d_p); uploaded = true; }
+    if (!uploaded) { polyRows(c2, c1, c0, xf * yf, d_div, d_p, slot_scale); uploaded = true; }
     ciphertext3D out(input.B, zo, xo, yo, out_form);
     ensure(g_scratch, crc_poly2_pool_relin_work_bytes(ctx(), input.B, zd, xd, yd, xs, ys, xf, yf, 16));
     chk(crc_poly2_pool_relin_forms(ctx(), input.data(), input.form, input.B, zd, xd, yd, xs, ys, xf, yf, (const uint64_t *)ev_keys16->ptr, 16, rowPtr(d_p[0]),
@@ -1647,8 +1745,10 @@ int Network::fuse()
         auto pool = dynamic_pointer_cast<PoolingLayer>(layers[i + 1]);
         if (!po || !pool || refreshBetween(i)) continue;
         if (!crc_poly2_pool_relin_supported(ctx(), 16, pool->xf, pool->yf)) continue;
-        layers[i] = make_shared<PolyPoolLayer>(po->name + "+" + pool->name, pool->xd, pool->yd, pool->zd, pool->xs, pool->ys, pool->xf, pool->yf, po->th_count,
-                                               po->c2, po->c1, po->c0, pool->d_div);
+        auto pp = make_shared<PolyPoolLayer>(po->name + "+" + pool->name, pool->xd, pool->yd, pool->zd, pool->xs, pool->ys, pool->xf, pool->yf, po->th_count,
+                                             po->c2, po->c1, po->c0, pool->d_div);
+        for (int j = 0; j < 3; j++) pp->slot_scale[j] = po->slot_scale[j];
+        layers[i] = pp;
         eraseLayer(i + 1);
     }
     // 2. batch-norm + conv / dense
@@ -1829,6 +1929,7 @@ NetworkDescription NetworkDescription::parse(const string &text, const string &h
     }
     if (!have_input) descError(1, "the first line must be `input zd xd yd`");
     if (pending_refresh) descError(pending_refresh, "refresh must be followed by a layer");
+    d.refresh_line = refresh_line;
     if (d.layers.empty()) descError(ln, "the description has no layers");
     return d;
 }
@@ -1896,8 +1997,16 @@ vector<float> CnnBuilder::getPretrained(string var_name)
     chk(crc_h5_read_f32(plain_model_path.c_str(), var_name.c_str(), v.data(), cnt, nullptr), "crc_h5_read_f32");
     return v;
 }
-static vector<Plaintext> encodeAll(const vector<float> &v)
+// `which`: 0 the layer's first dataset (weights, mean), 1 its second (biases, invstd) -- slot encoding takes the scale the ledger set for it
+static vector<Plaintext> encodeAll(const vector<float> &v, int which)
 {
+    if (g_slot_on) {
+        const double scale = g_enc_scale[which];
+        if (scale == 0) throw logic_error("slot encoding: layers with parameters are built from a description (CnnBuilder::buildNetworkFromDescription)");
+        vector<Plaintext> out(v.size());
+        crc_host::parallel_for(v.size(), 1024, [&](size_t b, size_t e) { for (size_t i = b; i < e; i++) out[i] = scalarPlain((double)v[i], scale); });
+        return out;
+    }
     // compact form (crc_encode_f32_compact: the 96 coefficients the encoder can set), encoded and turned into Plaintexts on the host threads
     // (csrc/host_parallel.h)
     const int n = N();
@@ -1921,7 +2030,7 @@ ConvolutionalLayer *CnnBuilder::buildConvolutionalLayer(string name, int xd, int
     if (infile != NULL) return new ConvolutionalLayer(name, xd, yd, zd, xs, ys, xf, yf, nf, th_count, infile);
     vector<float> weights = getPretrained(name + ".weight"), biases = getPretrained(name + ".bias");
     if ((int)weights.size() != nf * zd * xf * yf || (int)biases.size() != nf) throw invalid_argument("conv: dataset size does not match the layer");
-    vector<Plaintext> ew = encodeAll(weights), eb = encodeAll(biases);
+    vector<Plaintext> ew = encodeAll(weights, 0), eb = encodeAll(biases, 1);
     plaintext4D encoded_weights(nf, plaintext3D(zd, plaintext2D(xf, vector<Plaintext>(yf))));
     size_t w = 0;
     for (int n = 0; n < nf; n++) for (int z = 0; z < zd; z++) for (int i = 0; i < xf; i++) for (int j = 0; j < yf; j++) encoded_weights[n][z][i][j] = ew[w++];
@@ -1932,7 +2041,7 @@ FullyConnectedLayer *CnnBuilder::buildFullyConnectedLayer(string name, int in_di
     if (infile != NULL) return new FullyConnectedLayer(name, in_dim, out_dim, th_count, infile);
     vector<float> weights = getPretrained(name + ".weight"), biases = getPretrained(name + ".bias");
     if ((int)weights.size() != in_dim * out_dim || (int)biases.size() != out_dim) throw invalid_argument("fc: dataset size does not match the layer");
-    vector<Plaintext> ew = encodeAll(weights), eb = encodeAll(biases);
+    vector<Plaintext> ew = encodeAll(weights, 0), eb = encodeAll(biases, 1);
     plaintext2D encoded_weights(out_dim, vector<Plaintext>(in_dim));
     size_t w = 0;
     for (int i = 0; i < out_dim; i++) for (int j = 0; j < in_dim; j++) encoded_weights[i][j] = ew[w++];
@@ -1952,13 +2061,40 @@ BatchNormLayer *CnnBuilder::buildBatchNormLayer(string name, int num_channels, i
     if ((int)mean.size() != num_channels || (int)var.size() != num_channels) throw invalid_argument("bn: dataset size does not match the layer");
     vector<float> invstd(var.size());
     chk(crc_bn_invstd_f32(var.data(), var.size(), invstd.data()), "crc_bn_invstd_f32");
-    vector<Plaintext> em = encodeAll(mean), ev = encodeAll(invstd);
+    vector<Plaintext> em = encodeAll(mean, 0), ev = encodeAll(invstd, 1);
     return new BatchNormLayer(name, num_channels, em, ev);
 }
 Network CnnBuilder::buildNetwork(string file_name) { return buildNetworkByName("PlainModelTiny", file_name); }
 PaddingLayer *CnnBuilder::buildPaddingLayer(string name, int xd, int yd, int zd, int px, int py) { return new PaddingLayer(name, xd, yd, zd, px, py); }
 // the three networks of cnnBuilder.cpp:115-169 come from their descriptions (crcnn_amd/models/*.net, compiled in): same build*Layer calls, same arguments
 Network CnnBuilder::buildNetworkByName(const string &model, string file_name) { return buildNetworkFromDescription(model, file_name); }
+// ---- the scale ledger of slot encoding ---------------------------------------------------------------------------------------
+// a * b for integer-valued doubles below 2^62, exact or std::invalid_argument
+static double scaleTimes(int line, double a, double b)
+{
+    const unsigned __int128 z = (unsigned __int128)(uint64_t)a * (uint64_t)b;
+    const double r = (double)(uint64_t)z;
+    if ((z >> 62) || (unsigned __int128)(uint64_t)r != z) descError(line, "slot encoding: the scale leaves the integers below 2^62 that a double holds exactly");
+    return r;
+}
+vector<double> slotScales(const NetworkDescription &d, int input_bits, int weight_bits)
+{
+    if (input_bits < 0 || input_bits > 30 || weight_bits < 0 || weight_bits > 30) throw invalid_argument("slotScales: bit counts must be in 0..30");
+    if (d.layer_before_reenc >= 0) descError(d.refresh_line, "refresh is not available with slot encoding (it would need a slot-wise re-encoding)");
+    const double W = ldexp(1.0, weight_bits);
+    double s = ldexp(1.0, input_bits);
+    vector<double> out;
+    for (const LayerSpec &L : d.layers) {
+        out.push_back(s);
+        if (L.kind == "conv" || L.kind == "fc" || L.kind == "bn") s = scaleTimes(L.line, s, W);
+        else if (L.kind == "avgpool") s = scaleTimes(L.line, s, (double)(L.xf * L.yf));
+        else if (L.kind == "square") s = scaleTimes(L.line, s, s);
+        else if (L.kind == "poly") s = scaleTimes(L.line, scaleTimes(L.line, s, s), W);
+        else if (L.kind == "poly3") s = scaleTimes(L.line, scaleTimes(L.line, scaleTimes(L.line, s, s), s), W);
+    }
+    out.push_back(s);
+    return out;
+}
 Network CnnBuilder::buildNetworkFromDescription(const string &path_or_text, string file_name)
 {
     // (an encoded-model file brings its own parameters: the HDF5 datasets are not consulted then, as in build*Layer)
@@ -1968,20 +2104,39 @@ Network CnnBuilder::buildNetworkFromDescription(const string &path_or_text, stri
     if (file_name != "") { infile.reset(new ifstream(file_name, ifstream::binary)); if (!*infile) throw runtime_error("cannot open " + file_name); }
     istream *in = infile.get();
     auto add = [&](Layer *l) { net.getLayers().push_back(shared_ptr<Layer>(l)); };
+    // slot encoding: the ledger says at which scale every plaintext of the layer is an integer (slotScales)
+    const vector<double> sigma = g_slot_on ? slotScales(d, g_slot_in_bits, g_slot_w_bits) : vector<double>();
+    const double W = ldexp(1.0, g_slot_w_bits);
+    struct ScaleScope { ~ScaleScope() { g_enc_scale[0] = g_enc_scale[1] = 0; } } scale_scope;
+    size_t li = 0;
     for (const LayerSpec &L : d.layers) {
         const int th = L.threads >= 0 ? L.threads : 1;
+        const double s = g_slot_on ? sigma[li] : 0;
+        li++;
+        if (g_slot_on) {
+            if (L.kind == "bn") { g_enc_scale[0] = s; g_enc_scale[1] = W; }
+            else { g_enc_scale[0] = W; g_enc_scale[1] = s * W; }
+        }
         if (L.kind == "conv") add(buildConvolutionalLayer(L.name, L.xd, L.yd, L.zd, L.xs, L.ys, L.xf, L.yf, L.nf, th, in));
         else if (L.kind == "pool") add(buildPoolingLayer(L.name, L.xd, L.yd, L.zd, L.xs, L.ys, L.xf, L.yf));
         else if (L.kind == "avgpool") add(buildAvgPoolingLayer(L.name, L.xd, L.yd, L.zd, L.xs, L.ys, L.xf, L.yf));
         else if (L.kind == "bn") add(buildBatchNormLayer(L.name, L.zd, in));
         else if (L.kind == "square") add(buildSquareLayer(L.name, th));
-        else if (L.kind == "poly") add(buildPolyLayer(L.name, L.c2, L.c1, L.c0, th));
-        else if (L.kind == "poly3") add(buildPoly3Layer(L.name, L.c3, L.c2, L.c1, L.c0, th));
+        else if (L.kind == "poly") {
+            PolyLayer *p = buildPolyLayer(L.name, L.c2, L.c1, L.c0, th);
+            if (g_slot_on) { p->slot_scale[0] = W; p->slot_scale[1] = W * s; p->slot_scale[2] = W * s * s; }
+            add(p);
+        } else if (L.kind == "poly3") {
+            Poly3Layer *p = buildPoly3Layer(L.name, L.c3, L.c2, L.c1, L.c0, th);
+            if (g_slot_on) { p->slot_scale[0] = W; p->slot_scale[1] = W * s; p->slot_scale[2] = W * s * s; p->slot_scale[3] = W * s * s * s; }
+            add(p);
+        }
         else if (L.kind == "fc") add(buildFullyConnectedLayer(L.name, L.zd * L.xd * L.yd, L.out_dim, th, in));
         else add(buildPaddingLayer(L.name, L.xd, L.yd, L.zd, L.px, L.py));
     }
     net.input_zd = d.zd; net.input_xd = d.xd; net.input_yd = d.yd;
     net.layer_before_reenc = d.layer_before_reenc;
+    net.slot_scale_ = g_slot_on ? sigma.back() : 0;
     return net;
 }
 Network CnnBuilder::buildAndSaveNetwork(string file_name)

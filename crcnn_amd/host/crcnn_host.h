@@ -78,6 +78,15 @@ void clearDeterministicSeed();                              // back to OS entrop
 void setParameters(int poly_modulus = 4096, uint64_t plain_modulus = 1 << 20);          // coeff_modulus_128(poly_modulus)
 void setParameters(int poly_modulus, const std::vector<uint64_t> &coeff_modulus, uint64_t plain_modulus, int device = 0);
 void delParameters();
+// Slot-batched inference (include/crcnn_hip.h, "Slot batching"): with a prime plain modulus t = 1 (mod 2n) one ciphertext tensor carries up to n images, image j
+// in slot j of every ciphertext, through the same layers.  setSlotEncoding switches the encoding of everything these classes turn into plaintexts from the
+// fractional encoder to SCALARS: the constant polynomial of nearbyint(value * scale) mod t (round half even on doubles), the same number in every slot.  Pixels
+// are scaled by 2^input_bits, weights by 2^weight_bits, and every other plaintext by what CnnBuilder::buildNetworkFromDescription's scale ledger says (below,
+// slotScales).  Both throw std::invalid_argument when crc_slots_supported(context) is 0 or a bit count is outside 0..30.  Off by default and after every
+// setParameters(); with it off every path is what it is without these calls.
+void setSlotEncoding(int input_bits, int weight_bits);
+void clearSlotEncoding();
+bool slotEncoding();
 // key / ciphertext files in SEAL's wire formats, interchangeable with CrCNN's (globals.cpp:58-111, 174-205)
 void setAndSaveParameters(std::string public_key_path, std::string secret_key_path, std::string evaluation_key_path, int poly_modulus, uint64_t plain_modulus);
 void initFromKeys(std::string public_key_path, std::string secret_key_path, std::string evaluation_key_path, int poly_modulus, uint64_t plain_modulus);
@@ -132,6 +141,16 @@ ciphertext3D expandSeeded(const SeededImages &images, int out_form = CRC_NTT);
 // the same for rows that are already on the device (a host that uploads on a copy stream of its own): d_c0 packed [B zd xd yd][k][n], `dst` a tensor of that
 // shape whose form says what to produce; asynchronous on the installed stream
 void expandSeeded(const uint64_t *d_c0, int B, int zd, int xd, int yd, const uint8_t *seed, uint64_t stream_base, ciphertext3D &dst);
+
+// S images ([S][zd xd yd] pixels each, S <= n) -> ONE tensor [1][zd][xd][yd] whose ciphertext (z, x, y) holds pixel (z, x, y) of image j in slot j: the pixels
+// are quantised as nearbyint(double(p) 2^input_bits) (the int64 overload takes them as they are), composed on the device (crc_slots_compose_dev, image-major) and
+// encrypted there (crc_encrypt_dev_forms); keystream discipline as encryptImage.  std::logic_error unless setSlotEncoding is on
+ciphertext3D encryptImageSlots(const std::vector<std::vector<float>> &images, int zd, int xd, int yd, int out_form = CRC_COEFF);
+ciphertext3D encryptImageSlots(const std::vector<std::vector<int64_t>> &images, int zd, int xd, int yd, int out_form = CRC_COEFF);
+// the first S slots of every ciphertext of a tensor (CRC_COEFF or CRC_NTT), as centred integers [S][count]: crc_decrypt_dev, then crc_slots_decompose_dev
+std::vector<std::vector<int64_t>> decryptSlots(const ciphertext3D &t, int S);
+// ... divided by `scale` (Network::slot_scale() of the network that produced the tensor)
+std::vector<std::vector<double>> decryptImageSlots(const ciphertext3D &t, int S, double scale);
 
 // ---- layers (CrCNN/src/layer.h:10-31) ------------------------------------------------------------------------------
 class Layer {
@@ -337,6 +356,8 @@ private:
 class PolyLayer : public Layer {
 public:
     float c2, c1, c0;
+    // slot encoding: the scales of c2, c1, c0 (the rows are the constants nearbyint(c * scale) mod t); 0 = the fractional encoder.  Set before the first forward
+    double slot_scale[3] = {0, 0, 0};
     int th_count;
     PolyLayer(std::string name, float c2, float c1, float c0, int th_count);
     ciphertext3D forward(ciphertext3D input) override;
@@ -358,6 +379,7 @@ private:
 class Poly3Layer : public Layer {
 public:
     float c3, c2, c1, c0;
+    double slot_scale[4] = {0, 0, 0, 0};                    // of c3, c2, c1, c0, as PolyLayer's
     int th_count;
     Poly3Layer(std::string name, float c3, float c2, float c1, float c0, int th_count);
     ciphertext3D forward(ciphertext3D input) override;
@@ -381,6 +403,7 @@ class PolyPoolLayer : public Layer {
 public:
     int xd, yd, zd, xs, ys, xf, yf, xo, yo, zo, th_count;
     float c2, c1, c0;
+    double slot_scale[3] = {0, 0, 0};                       // as PolyLayer's (Network::fuse() copies them)
     PolyPoolLayer(std::string name, int xd, int yd, int zd, int xs, int ys, int xf, int yf, int th_count, float c2, float c1, float c0,
         std::shared_ptr<DeviceBuffer> d_div);
     ciphertext3D forward(ciphertext3D input) override;
@@ -501,8 +524,13 @@ public:
     // b' = b - sum_taps w' (*) mean[channel]).  The network's output ciphertexts stay bit-identical; only the folded layers'
     // intermediate tensors disappear (their plaintext parameters can no longer be saved).  Returns the number of layers removed.
     int fuse();
+    // slot encoding: the scale of the network's outputs (decryptSlots' integers are slot_scale() times the numbers the float network computes); 0 for a
+    // network built without setSlotEncoding
+    double slot_scale() const { return slot_scale_; }
 private:
     bool fused_ = false;
+    double slot_scale_ = 0;
+    friend class CnnBuilder;
 public:
     // Multi-GPU start-up (no analogue in the reference): one process (or host thread) per GPU, images sharded across them
     // with no data-path collective.  Rank `root` holds the encoded model -- this call lifts + NTTs its plaintext parameters if that has
@@ -540,6 +568,7 @@ struct LayerSpec {
 struct NetworkDescription {
     int zd = 1, xd = 28, yd = 28;
     int layer_before_reenc = -1;
+    int refresh_line = 0;                                   // line of the `refresh` token (0: none)
     std::vector<LayerSpec> layers;
     // h5_path != "": the weight, bias and batch-norm datasets of the model file are checked against the inferred shapes
     static NetworkDescription parse(const std::string &text, const std::string &h5_path = "");
@@ -547,6 +576,19 @@ struct NetworkDescription {
     static NetworkDescription load(const std::string &text_name_or_path, const std::string &h5_path = "");
     std::string str() const;                                // canonical form: parse(str()) gives the same description
 };
+// The scale ledger of slot encoding: the scale sigma IN FRONT of every layer of the description, and behind the last one (layers.size() + 1 entries).  sigma
+// starts at 2^input_bits; with W = 2^weight_bits
+//   conv / fc   weights at scale W, biases at sigma W                               -> sigma W
+//   bn          mean at sigma, invstd at W                                          -> sigma W
+//   pool, pad   no plaintexts                                                       -> sigma
+//   avgpool     none: the layer is built as the sum pool                            -> sigma xf yf
+//   square                                                                          -> sigma^2
+//   poly        c2 at W, c1 at W sigma, c0 at W sigma^2                             -> sigma^2 W
+//   poly3       c3 at W, c2 at W sigma, c1 at W sigma^2, c0 at W sigma^3            -> sigma^3 W
+// Every scale must be an integer below 2^62 that a double holds exactly; std::invalid_argument ("line N: ...") otherwise, and for a `refresh` (the slot-wise
+// re-encoding a refresh would need is not implemented).  Needs no context
+std::vector<double> slotScales(const NetworkDescription &d, int input_bits, int weight_bits);
+
 // the description of "PlainModelTiny" | "ApproxPlainModel" | "PlainModelWoPad" (crcnn_amd/models/<name>.net, compiled in); nullptr for any other name
 const char *builtinDescription(const std::string &model);
 

@@ -15,6 +15,9 @@
 //     ref_cipher_image.bin; cnnBuilder.cpp:181-196, globals.cpp:174-205), runs conv -> bn -> dense on them (out_from_ref_files.u64), then writes the same two
 //     files itself (our_encoded_layers.bin, our_cipher_image.bin) and runs those (out_from_our_files.u64)
 //   test_host seeded <n> <t> / netseeded <model> <h5> <dir>     seeded secret-key images through the host classes (see do_seeded / do_netseeded)
+//   test_host slots_describe <description> <input_bits> <weight_bits>     the scale ledger of slot encoding: "scale <i> <kind> <name> <sigma>" in front of every
+//     layer, then "slot_scale <sigma>".  No GPU work
+//   test_host slots_build <description> <h5> <dir> <S> <input_bits> <weight_bits> [reps]     see do_slots_build
 //   test_host searchlogic <min> <max> <first_good> <last_good> <min_q>
 //     the plain-modulus search on a synthetic predicate (t < first_good: MISPREDICTED, t > last_good: OUT_OF_BUDGET); no GPU work.
 //     prints "found <t>" and one "tried <t> <status>" line per test
@@ -22,6 +25,7 @@
 //     the real search: images.f32 = N x 784 normalised float32 pixels, labels from the float model; prints found / tried lines
 #include "crcnn_host.h"
 #include "plain_modulus_search.h"
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <sstream>
@@ -580,6 +584,66 @@ static int do_build(int argc, char **argv)
     return 0;
 }
 
+static int do_slots_describe(int argc, char **argv)
+{
+    if (argc < 5) return 1;
+    const NetworkDescription d = NetworkDescription::load(argv[2]);
+    const vector<double> s = slotScales(d, atoi(argv[3]), atoi(argv[4]));
+    for (size_t i = 0; i < d.layers.size(); i++) printf("scale %zu %s %s %.17g\n", i, d.layers[i].kind.c_str(), d.layers[i].name.c_str(), s[i]);
+    printf("slot_scale %.17g\n", s.back());
+    return 0;
+}
+
+// slots_build <description> <h5> <dir> <S> <input_bits> <weight_bits>: slot-batched inference through the host classes.  <dir>/params.u64 (n, k, t, q...: t a
+// slot prime), <dir>/images.f32 = [S][zd xd yd] float32 pixels.  Keys from a deterministic seed; the S images are encrypted into one tensor (encryptImageSlots),
+// run through Network::forward unfused and after Network::fuse(), decrypted and decomposed: slots_unfused.i64 / slots_fused.i64 = [S][outputs] int64.
+// Prints "slot_scale <sigma>", "budget unfused <bits> fused <bits>" (minNoiseBudget of the output tensors) and "describe-ok" when Network::describe() is the
+// description's canonical form (slot encoding does not change it).  With <reps> > 0 the fused forward runs <reps> times more between two stream synchronisations:
+// "forward_ms <milliseconds per tensor evaluation>" (tools/measure_slots.py)
+static int do_slots_build(int argc, char **argv)
+{
+    if (argc < 8) return 1;
+    const string desc = argv[2], h5 = argv[3], dir = argv[4]; const int S = atoi(argv[5]), in_bits = atoi(argv[6]), w_bits = atoi(argv[7]);
+    setDeterministicSeed(20240611);
+    setup(dir);
+    setSlotEncoding(in_bits, w_bits);
+    CnnBuilder builder(h5);
+    Network net = builder.buildNetworkFromDescription(desc);
+    if (net.describe() != NetworkDescription::load(desc).str()) { fprintf(stderr, "describe() differs from the canonical form\n"); return 4; }
+    printf("describe-ok\n");
+    const size_t px = (size_t)net.input_zd * net.input_xd * net.input_yd;
+    vector<vector<float>> images(S, vector<float>(px));
+    { ifstream f(dir + "/images.f32", ios::binary); if (!f) { fprintf(stderr, "missing images.f32\n"); return 2; }
+      for (auto &im : images) f.read((char *)im.data(), px * 4);
+      if (!f) { fprintf(stderr, "images.f32 is too short\n"); return 2; } }
+    const ciphertext3D in = encryptImageSlots(images, net.input_zd, net.input_xd, net.input_yd);
+    auto dump = [&](const string &name, const ciphertext3D &out) {
+        const vector<vector<int64_t>> v = decryptSlots(out, S);
+        ofstream f(dir + "/" + name, ios::binary);
+        for (auto &row : v) f.write((const char *)row.data(), row.size() * 8);
+        return minNoiseBudget(out);
+    };
+    net.ntt_resident = true;
+    const int b0 = dump("slots_unfused.i64", net.forward(in));
+    const int removed = net.fuse();
+    fprintf(stderr, "fused: %d layers removed, %d left\n", removed, net.getNumLayers());
+    const int b1 = dump("slots_fused.i64", net.forward(in));
+    printf("slot_scale %.17g\n", net.slot_scale());
+    printf("budget unfused %d fused %d\n", b0, b1);
+    const int reps = argc > 8 ? atoi(argv[8]) : 0;
+    if (reps > 0) {
+        crc_stream_sync(context, getStream());
+        const auto t0 = chrono::steady_clock::now();
+        for (int r = 0; r < reps; r++) net.forward(in);
+        crc_stream_sync(context, getStream());
+        printf("forward_ms %.6f\n", chrono::duration<double, milli>(chrono::steady_clock::now() - t0).count() / reps);
+    }
+    delParameters();
+    clearDeterministicSeed();
+    printf("slots_build ok\n");
+    return 0;
+}
+
 #define EXPECT_THROW(stmt, type) do { bool ok_ = false; try { stmt; } catch (const type &) { ok_ = true; } catch (...) {} if (!ok_) { fprintf(stderr, "expected " #type " from: " #stmt "\n"); return 3; } } while (0)
 
 static int do_api(int argc, char **argv)
@@ -804,6 +868,8 @@ int main(int argc, char **argv)
         if (!strcmp(argv[1], "labels")) return do_labels(argc, argv);
         if (!strcmp(argv[1], "build")) return do_build(argc, argv);
         if (!strcmp(argv[1], "multiply")) return do_multiply(argc, argv);
+        if (!strcmp(argv[1], "slots_describe")) return do_slots_describe(argc, argv);
+        if (!strcmp(argv[1], "slots_build")) return do_slots_build(argc, argv);
     } catch (const exception &e) { fprintf(stderr, "exception: %s\n", e.what()); return 10; }
     return 1;
 }

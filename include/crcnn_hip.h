@@ -101,7 +101,7 @@ size_t crc_ct_words(const crc_ctx *ctx, int size);     /* size*k*n */
 size_t crc_evk_words(const crc_ctx *ctx, int dbc);     /* words of an evaluation-key blob: sum_l 2*L_l*k*n (0 for a dbc outside 1..60: every call that
                                                           takes a dbc refuses those with CRC_ERR_INVALID_ARGUMENT, every size query gives 0) */
 /* named host-side table read-out (tests): "root","const_ratio","delta","upper_half_increment","bsk","bsk_root",
- * "root_powers:<i>","inv_root_powers_div_two:<i>", "f64_primes" (the two fp64 primes of relinearisation's key switching), "sq64_primes" (the fp64 primes that
+ * "root_powers:<i>","inv_root_powers_div_two:<i>", "slots_root", "slots_index_map" (slot batching, below), "f64_primes" (the two fp64 primes of relinearisation's key switching), "sq64_primes" (the fp64 primes that
  * carry the square's auxiliary base: B' = all but the last, m_sk' = the last; empty when the parameters do not fit twelve of them); returns word count */
 int  crc_ctx_table(const crc_ctx *ctx, const char *name, uint64_t *h_out, int cap);
 /* Tuning switches of tools/ and the tests (none is needed for normal use).  The engine reads its environment (CRC_MFMA_VARIANT, CRC_CONV1_PASS_BYTES, ...)
@@ -494,6 +494,34 @@ size_t crc_noise_budget_dev_work_bytes(const crc_ctx *ctx, size_t count, int siz
 int crc_noise_budget_dev(crc_ctx *ctx, const uint64_t *d_sk_ntt, const uint64_t *d_ct, size_t count, int size, int in_form, int32_t *d_bits /*[count]*/,
                          int32_t *d_min /*[2]: min, index; may be NULL*/, void *d_work, void *stream);
 int crc_budget_bits_host(const crc_ctx *ctx, const uint64_t *h_v /*[count][k][n], coefficient form*/, size_t count, int32_t *h_bits /*[count]*/);
+/* -------------------------------------------------------------------------------------------------------------
+ * Slot batching (SEAL's PolyCRTBuilder, polycrt.cpp:82-147, 327-370): with a PRIME plain modulus t = 1 (mod 2n) a plaintext is n independent numbers of Z_t,
+ * and ciphertext addition, multiplication by a plaintext, square and multiply act on every slot separately -- image j of a batch in slot j makes one
+ * ciphertext tensor carry up to n images through the same kernels.  psi = the minimal primitive 2n-th root of unity mod t ("slots_root" of crc_ctx_table),
+ * m = 2n, pos_i = 3^i mod m, idx[i] = bitrev((pos_i - 1)/2, log n), idx[n/2 + i] = bitrev((m - pos_i - 1)/2, log n) for i < n/2 ("slots_index_map"):
+ *   compose    v[0..slots) -> v[i] mod t at position idx[i] of a row, zeros at idx[i] for i >= slots, inverse negacyclic transform mod t = the coefficients
+ *   decompose  forward transform mod t; slot i = position idx[i], returned as the centred representative in [-(t-1)/2, (t-1)/2]
+ * i.e. slot i of p is p(psi^(3^i)) and slot n/2 + i is p(psi^(-3^i)).  A constant polynomial w is the number w in every slot.
+ * Values are int64; (item c, slot i) sits at values[c item_stride + i slot_stride]: image-major data [slots][count] is (1, count), item-major (slots, 1).
+ * ANY int64 is accepted and taken as its residue mod t: SEAL throws for a value outside the plain modulus, a device kernel cannot.  Plaintext words read by
+ * decompose are reduced mod t the same way.
+ *   crc_slots_supported   1 only if t is prime, t = 1 (mod 2n) and t differs from every modulus the context computes with (the q_i, the Bsk base, gamma, the
+ *                         fp64 primes of the square and the key switch)
+ *   crc_slots_prime       the largest prime below 2^bits that is 1 (mod 2n), 2 <= bits <= 60 (CRC_ERR_NOT_FOUND if there is none)
+ *   crc_slots_compose / crc_slots_decompose            host memory, any context (device = -1 included)
+ *   crc_slots_compose_dev / crc_slots_decompose_dev    device memory, asynchronous on `stream`, no work buffer: one kernel, one workgroup per row
+ *                         (kernels_slots.hip); d_plain 16-byte aligned; n <= 16384 (CRC_ERR_UNSUPPORTED above)
+ * The tables of t are built by the first of these calls (or by crc_ctx_table), not by crc_ctx_create; on a device context that first call uploads them and
+ * synchronises once.  Every entry point returns CRC_ERR_PARAMETERS on a context where crc_slots_supported is 0, CRC_ERR_INVALID_ARGUMENT for slots outside
+ * [1, n], null pointers or a zero stride.  The caller guarantees that the values buffer covers (count - 1) item_stride + (slots - 1) slot_stride.
+ * ------------------------------------------------------------------------------------------------------------- */
+int crc_slots_supported(const crc_ctx *ctx);
+int crc_slots_prime(int n, int bits, uint64_t *t);
+int crc_slots_compose(crc_ctx *ctx, const int64_t *h_values, size_t count, int slots, size_t item_stride, size_t slot_stride, uint64_t *h_plain /*[count][n]*/);
+int crc_slots_decompose(crc_ctx *ctx, const uint64_t *h_plain /*[count][n]*/, size_t count, int slots, int64_t *h_values, size_t item_stride, size_t slot_stride);
+int crc_slots_compose_dev(crc_ctx *ctx, const int64_t *d_values, size_t count, int slots, size_t item_stride, size_t slot_stride, uint64_t *d_plain, void *stream);
+int crc_slots_decompose_dev(crc_ctx *ctx, const uint64_t *d_plain, size_t count, int slots, int64_t *d_values, size_t item_stride, size_t slot_stride,
+                            void *stream);
 /* FractionalEncoder::decode / encode (encoder.cpp:1226-1270, 1013-1076; 64 integer + 32 fractional coefficients, base 3: CrCNN/src/globals.cpp:52) on the
  * device: the doubles crc_decode returns for d_plain [count][n], and the dense plaintexts [count][n] crc_encode_f32 / _f64 make of the values -- the same IEEE
  * operations in the same order as the host encoder, contraction off. */
