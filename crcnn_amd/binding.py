@@ -20,7 +20,7 @@ VP = ctypes.c_void_p
 CI = ctypes.c_int
 SZ = ctypes.c_size_t
 
-COEFF, NTT, NTTP, NTTL, NTTL1, NTTLC = 0, 1, 2, 3, 4, 5
+COEFF, NTT, NTTP, NTTL, NTTL1, NTTLC, NTTLS = 0, 1, 2, 3, 4, 5, 6
 
 
 class CrcError(RuntimeError):
@@ -136,6 +136,10 @@ def load():
     L.crc_limb_pack_weights_tile.argtypes = [VP, VP, CI, CI, CI, CI, CI, CI, VP, VP]
     L.crc_limb_pack_tensor_at.argtypes = [VP, VP, CI, CI, CI, CI, CI, VP, CI, CI, VP]
     L.crc_plan_mac.argtypes = [VP] + [CI] * 10 + [ctypes.POINTER(CI)]
+    L.crc_plan_mac_scalar.argtypes = [VP] + [CI] * 9 + [ctypes.POINTER(CI)]
+    L.crc_scalar_weights_bytes.restype = SZ; L.crc_scalar_weights_bytes.argtypes = [VP, CI, CI, CI, CI]
+    L.crc_scalar_supported.argtypes = [VP] + [CI] * 9
+    L.crc_scalar_pack_weights.argtypes = [VP, VP, CI, CI, CI, CI, CI, VP, ctypes.POINTER(CI), VP]
     L.crc_plan_fold_pool.argtypes = [VP] + [CI] * 12 + [ctypes.POINTER(CI)]
     L.crc_plan_hoist_pool.argtypes = [VP] + [CI] * 22 + [ctypes.POINTER(CI)]
     L.crc_limb_pack_tensor.argtypes = [VP, VP, CI, CI, CI, CI, CI, VP, VP]
@@ -606,6 +610,29 @@ class Engine:
         _chk(self.L.crc_plan_hoist_pool(self.c, *(tuple(up) if up else (0,) * 8), *conv, *pool, int(B or 0), 1 if matrix_cores else 0, ctypes.byref(h)),
              "crc_plan_hoist_pool")
         return bool(h.value)
+
+    # ---- scalar form (CRC_NTTLS): the layers of a slot-batched network, whose weights are constant polynomials
+    def scalar_weights_bytes(self, nf, zd, xf=1, yf=1):
+        return self.L.crc_scalar_weights_bytes(self.c, nf, zd, xf, yf)
+
+    def scalar_supported(self, B, zd, xd, yd, xs, ys, xf, yf, nf):
+        return bool(self.L.crc_scalar_supported(self.c, B, zd, xd, yd, xs, ys, xf, yf, nf))
+
+    def scalar_pack_weights(self, d_w, w_stride, nf, zd, xf, yf, d_ws):
+        """d_w: NTT-form weight rows (w_stride = n) or one residue per modulus [nf][zd][xf][yf][k] (w_stride = 1).  Returns False, with d_ws untouched, where a
+        row is not a constant polynomial (crc_scalar_pack_weights' *constant = 0); any other failure raises"""
+        const = CI(1)
+        rc = self.L.crc_scalar_pack_weights(self.c, self.p(d_w), w_stride, nf, zd, xf, yf, self.p(d_ws), ctypes.byref(const), self.stream)
+        if rc == -1 and const.value == 0:
+            return False
+        _chk(rc, "crc_scalar_pack_weights")
+        return True
+
+    def plan_mac_scalar(self, zd, xd, yd, xs, ys, xf, yf, nf, B):
+        """crc_plan_mac for a layer of a slot-batched network: NTTLS where the scalar form runs (tuning key scalar_mac), else what plan_mac says"""
+        wf = CI(0)
+        _chk(self.L.crc_plan_mac_scalar(self.c, zd, xd, yd, xs, ys, xf, yf, nf, int(B or 0), ctypes.byref(wf)), "crc_plan_mac_scalar")
+        return wf.value
 
     def limb_pack_weights_tile(self, d_w_tile, nf, f0, ft, zd, xf, yf, d_wl):
         _chk(self.L.crc_limb_pack_weights_tile(self.c, self.p(d_w_tile), nf, f0, ft, zd, xf, yf, self.p(d_wl), self.stream), "crc_limb_pack_weights_tile")

@@ -14,6 +14,7 @@ static inline hipStream_t S(void *s) { return (hipStream_t)s; }
 static inline bool form_ok(int f) { return f == CRC_COEFF || f == CRC_NTT; }
 static inline bool nform_ok(int f) { return f == CRC_COEFF || f == CRC_NTT || f == CRC_NTTP; }
 static inline bool lform_ok(int f) { return nform_ok(f) || f == CRC_NTTL; }
+static inline bool limb_in(int f) { return f == CRC_NTTL || f == CRC_NTTLS; }          // the input already is the kernel's operand
 // entry points whose work space is one region: its start in d_work, and the size of `words` of it
 static inline u64 *work_base(void *d_work) { return WorkArena(d_work).take<u64>(0); }
 static inline size_t work_bytes(size_t words) { WorkArena a; a.take<u64>(words); return a.bytes(); }
@@ -213,7 +214,7 @@ static LimbWork limb_layout(const crc_ctx *c, int B, int zd, int xd, int yd, int
 {
     LimbWork L{};
     L.Ys = a.take<u64>(k_limb_result_words(c, B, nf, P));
-    if (in_form != CRC_NTTL) L.Xl = a.take<signed char>(k_limb_tensor_bytes(c, B, zd, xd * yd));
+    if (!limb_in(in_form)) L.Xl = a.take<signed char>(k_limb_tensor_bytes(c, B, zd, xd * yd));
     if (in_form == CRC_COEFF) L.buf = a.take<u64>((size_t)B * zd * xd * yd * crc_ct_words(c, 2));
     return L;
 }
@@ -224,7 +225,7 @@ extern "C" size_t crc_conv2d_forms_work_bytes(const crc_ctx *c, int B, int zd, i
     const int P = ((xd - xf) / xs + 1) * ((yd - yf) / ys + 1);
     WorkArena a;
     if (w_form == CRC_NTTL1) limb1_layout(c, B, xd, yd, xf, yf, nf, P, in_form, out_form, a);
-    else if (w_form == CRC_NTTL) limb_layout(c, B, zd, xd, yd, nf, P, in_form, a);
+    else if (w_form == CRC_NTTL || w_form == CRC_NTTLS) limb_layout(c, B, zd, xd, yd, nf, P, in_form, a);
     else conv_layout(c, B, zd, xd, yd, xf, yf, P, in_form, a);
     return a.bytes();
 }
@@ -234,24 +235,27 @@ extern "C" size_t crc_conv2d_work_bytes(const crc_ctx *c, int B, int zd, int xd,
 }
 static int conv2d_limb(crc_ctx *c, const uint64_t *d_x, const void *d_wl, const uint64_t *d_bias, int B, int zd, int xd, int yd, int xs, int ys, int xf,
     int yf, int nf,
-                       int in_form, int out_form, uint64_t *d_y, void *d_work, hipStream_t st)
+                       int in_form, int out_form, uint64_t *d_y, void *d_work, hipStream_t st, bool scalar = false)
 {
-    if (!crc_limb_supported(c, zd, xf, yf)) return CRC_ERR_UNSUPPORTED;
+    // scalar (w_form = CRC_NTTLS): the same steps on the merged GEMM of a modulus.  A convolution's tensor is the same bytes in either form; a dense layer's
+    // (in_form / out_form = CRC_NTTLS) has its rows in image order e = s B + b.  Ys is the same bytes too, so every other out_form goes the way it always went
+    if (!(scalar ? k_scalar_supported(c, B, zd, xd, yd, xs, ys, xf, yf, nf) : crc_limb_supported(c, zd, xf, yf) != 0)) return CRC_ERR_UNSUPPORTED;
     const int xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys + 1, P = xo * yo, in_cts = zd * xd * yd;
     WorkArena a(d_work);
     const LimbWork L = limb_layout(c, B, zd, xd, yd, nf, P, in_form, a);
     const signed char *xl = (const signed char *)d_x;
-    if (in_form != CRC_NTTL) {
+    if (!limb_in(in_form)) {
         const u64 *xn = d_x; bool packed = in_form == CRC_NTTP;
         if (in_form == CRC_COEFF) { RUN(k_ntt_ct(c, false, d_x, L.buf, (size_t)B * in_cts, 2, false, st, nullptr, 0, 0, 0, 0)); xn = L.buf; packed = false; }
-        RUN(k_limb_pack_tensor(c, xn, L.Xl, B, zd, xd * yd, packed, st));
+        RUN(k_limb_pack_tensor(c, xn, L.Xl, B, zd, xd * yd, packed, st, 0, 0, scalar));
         xl = L.Xl;
     }
     // bias joins in the NTT domain unless the result goes back to coefficient form (then add_plain(bias) rides on the inverse transform's store)
-    if (out_form == CRC_NTTL && k_limb_direct_dense(P))         // hand-over to a dense layer (channels = (f, px, py) flattened), written by the kernel itself
-        return k_limb_mac(c, xl, (const signed char *)d_wl, L.Ys, (signed char *)d_y, d_bias, B, zd, xd, yd, xs, ys, xf, yf, nf, st);
-    RUN(k_limb_mac(c, xl, (const signed char *)d_wl, L.Ys, nullptr, out_form != CRC_COEFF ? d_bias : nullptr, B, zd, xd, yd, xs, ys, xf, yf, nf, st));
-    if (out_form == CRC_NTTL) return k_limb_result_to_limb(c, L.Ys, (signed char *)d_y, B, nf * P, st);     // ... or re-limbed from the slot-major result
+    // hand-over to a dense layer (channels = (f, px, py) flattened), written by the kernel itself -- in its own row order: the scalar kernel writes CRC_NTTLS
+    if (out_form == (scalar ? CRC_NTTLS : CRC_NTTL) && k_limb_direct_dense(P))
+        return k_limb_mac(c, xl, (const signed char *)d_wl, L.Ys, (signed char *)d_y, d_bias, B, zd, xd, yd, xs, ys, xf, yf, nf, st, scalar);
+    RUN(k_limb_mac(c, xl, (const signed char *)d_wl, L.Ys, nullptr, out_form != CRC_COEFF ? d_bias : nullptr, B, zd, xd, yd, xs, ys, xf, yf, nf, st, scalar));
+    if (limb_in(out_form)) return k_limb_result_to_limb(c, L.Ys, (signed char *)d_y, B, nf * P, st, out_form == CRC_NTTLS);     // ... or re-limbed from the slot-major result
     RUN(k_limb_result_to_rows(c, L.Ys, d_y, (size_t)B * nf * P * 2, out_form == CRC_NTTP, st));
     if (out_form == CRC_COEFF) RUN(k_ntt_ct(c, true, d_y, d_y, (size_t)B * nf * P, 2, false, st, d_bias, 1, (size_t)P, nf));
     return CRC_OK;
@@ -274,6 +278,14 @@ extern "C" int crc_conv2d_forms(crc_ctx *c, const uint64_t *d_x, const uint64_t 
             yf)) return CRC_ERR_INVALID_ARGUMENT;
         if (B == 0) return CRC_OK;
         return conv2d_limb(c, d_x, d_w, d_bias, B, zd, xd, yd, xs, ys, xf, yf, nf, in_form, out_form, d_y, d_work, S(stream));
+    }
+    if (w_form == CRC_NTTLS) {
+        // in_form: a convolution's tensor as CRC_NTTL, a dense layer's (one position) as CRC_NTTLS -- the two dense layouts differ -- or rows in any form
+        const bool in_ok = nform_ok(in_form) || (xd * yd == 1 ? in_form == CRC_NTTLS : in_form == CRC_NTTL);
+        if (!d_x || !d_w || !d_y || !d_work || B < 0 || zd < 1 || nf < 1 || !(lform_ok(out_form) || out_form == CRC_NTTLS) || !conv_shape_ok(xd, yd, xs, ys, xf,
+            yf) || !in_ok) return CRC_ERR_INVALID_ARGUMENT;
+        if (B == 0) return CRC_OK;
+        return conv2d_limb(c, d_x, d_w, d_bias, B, zd, xd, yd, xs, ys, xf, yf, nf, in_form, out_form, d_y, d_work, S(stream), true);
     }
     if (!d_x || !d_w || !d_y || !d_work || B < 0 || zd < 1 || nf < 1 || !nform_ok(in_form) || !nform_ok(out_form) || (w_form != CRC_NTT && w_form != CRC_NTTP))
         return CRC_ERR_INVALID_ARGUMENT;
@@ -425,6 +437,32 @@ extern "C" int crc_plan_mac(const crc_ctx *c, int zd, int xd, int yd, int xs, in
     const bool few_filters_ok = nf >= 24 || (long long)c->n * c->k <= 32768;
     if (zd >= 16 && few_filters_ok && (long long)((zd + 31) / 32) * xf * yf >= min_steps && crc_limb_supported(c, zd, xf, yf) && (B <= 0 ||
         rows >= min_rows)) *w_form = CRC_NTTL;
+    return CRC_OK;
+}
+// ---- scalar form (CRC_NTTLS): slot-batched networks, whose weights are constant polynomials -----------------------------------------------------
+extern "C" size_t crc_scalar_weights_bytes(const crc_ctx *c, int nf, int zd, int xf, int yf)
+{
+    return c && nf >= 1 && zd >= 1 && xf >= 1 && yf >= 1 ? k_scalar_weights_bytes(c, nf, zd, xf, yf) : 0;
+}
+extern "C" int crc_scalar_supported(const crc_ctx *c, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf)
+{
+    if (!c || B < 1 || zd < 1 || nf < 1 || !conv_shape_ok(xd, yd, xs, ys, xf, yf)) return 0;
+    return k_scalar_supported(c, B, zd, xd, yd, xs, ys, xf, yf, nf) ? 1 : 0;
+}
+extern "C" int crc_scalar_pack_weights(crc_ctx *c, const uint64_t *d_w, int w_stride, int nf, int zd, int xf, int yf, void *d_ws, int *constant, void *stream)
+{
+    if (constant) *constant = 1;                                  // 0 only where a row was found not to be constant
+    CHECK_CTX(c);
+    if (!d_w || !d_ws || !constant || nf < 1 || zd < 1 || xf < 1 || yf < 1 || (w_stride != 1 && w_stride != c->n)) return CRC_ERR_INVALID_ARGUMENT;
+    if (c->k > 8 || !k_limb_supported(c, k_limb_steps(zd, xf, yf) * 32)) return CRC_ERR_UNSUPPORTED;
+    return k_scalar_pack_weights(c, d_w, (size_t)w_stride, (signed char *)d_ws, nf, zd, xf, yf, constant, S(stream));
+}
+// crc_plan_mac for a layer of a slot-batched network: the scalar form wherever it runs and the layer has a reduction worth a GEMM (zd >= 2); one-channel
+// convolutions keep their own kernel, moduli above 55 bits theirs.  The rows guard of crc_plan_mac does not apply: the merged GEMM has n B 2P rows.
+extern "C" int crc_plan_mac_scalar(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int B, int *w_form)
+{
+    RUN(crc_plan_mac(c, zd, xd, yd, xs, ys, xf, yf, nf, B, 1, w_form));
+    if (c->tune.scalar_mac && zd >= 2 && k_scalar_supported(c, B < 1 ? 1 : B, zd, xd, yd, xs, ys, xf, yf, nf)) *w_form = CRC_NTTLS;
     return CRC_OK;
 }
 // should a (sum / average) pooling layer be folded into the convolution in front of it (crc_conv2d_fold_pool: exact)?  Cost in units of one multiply-accumulate

@@ -118,6 +118,7 @@ struct CrcTuning {
     int mac2_dbg = 0;             // CRC_MAC2_DBG (only in -DCRC_TUNING builds)
     int ntt_split = 1;            // CRC_NTT_SPLIT=0: rows of n = 16384 as one 128-KiB LDS image (one workgroup per CU) instead of two 64-KiB halves
     int relin_mac_ct = 0;         // CRC_RELIN_MAC_CT=8: eight ciphertexts per thread in relin_mac_f64_kernel for k >= 4 (default 4)
+    int scalar_mac = 1;           // CRC_SCALAR_MAC=0: crc_plan_mac_scalar answers what crc_plan_mac says instead of the scalar form CRC_NTTLS (profiles/scalar_mac.md: it won on every layer)
     int mfma_min_steps = 0;       // CRC_MFMA_MIN_STEPS: reduction steps of 32 channels from which a conv / dense layer goes to the limb GEMM (0: 8)
     int f64_radix = 0;            // CRC_F64_RADIX=3|4|5: butterfly stages per LDS pass of the fp64 transforms (0: default)
     int sq_chunk = 0;             // CRC_SQ_CHUNK: ciphertexts per internal pass of square + relinearise (0: by ring size)

@@ -105,13 +105,17 @@ size_t k_limb_weights_bytes(const crc_ctx *c, int nf, int zd, int xf, int yf);
 int    k_limb_flat_zdc(int zd);                        // channel bytes per position of the flat form (layers of fewer than 32 channels), 0: blocked form
 int    k_limb_steps(int zd, int xf, int yf);           // 32-term reduction steps of a layer
 size_t k_limb_result_words(const crc_ctx *c, int B, int nf, int P);
-int k_limb_pack_tensor(crc_ctx *c, const u64 *x, signed char *xl, int B, int zd, int npos, bool packed, hipStream_t st, int Btot = 0, int b0 = 0);
+int k_limb_pack_tensor(crc_ctx *c, const u64 *x, signed char *xl, int B, int zd, int npos, bool packed, hipStream_t st, int Btot = 0, int b0 = 0, bool scalar = false);
 int k_limb_pack_weights(crc_ctx *c, const u64 *w, signed char *wl, int nf, int zd, int xf, int yf, hipStream_t st, int f0 = 0, int ft = -1);
 int k_limb_result_to_rows(crc_ctx *c, const u64 *ys, u64 *y, size_t rows, bool pack_out, hipStream_t st);
-int k_limb_result_to_limb(crc_ctx *c, const u64 *ys, signed char *xl, int B, int zd, hipStream_t st);
+int k_limb_result_to_limb(crc_ctx *c, const u64 *ys, signed char *xl, int B, int zd, hipStream_t st, bool scalar = false);
 bool k_limb_direct_dense(int P);
 int k_limb_mac(crc_ctx *c, const signed char *xl, const signed char *wl, u64 *ys, signed char *xl_out, const u64 *bias_ntt, int B, int zd, int xd, int yd, int xs, int ys_, int xf, int yf, int nf,
-               hipStream_t st);
+               hipStream_t st, bool scalar = false);
+// scalar form (CRC_NTTLS): the weights of a slot-batched network are constant polynomials, one residue per modulus; the n GEMMs of a modulus run as one
+size_t k_scalar_weights_bytes(const crc_ctx *c, int nf, int zd, int xf, int yf);
+bool   k_scalar_supported(const crc_ctx *c, int B, int zd, int xd, int yd, int xs, int ys_, int xf, int yf, int nf);
+int k_scalar_pack_weights(crc_ctx *c, const u64 *w, size_t wstride, signed char *wl, int nf, int zd, int xf, int yf, int *constant, hipStream_t st);
 // kernels_mfma1.hip: one-channel convolutions (conv1 [+ pool1]) on the matrix cores (weight form CRC_NTTL1)
 bool   k_limb_conv1_shape(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys_, int xf, int yf, int nf);
 int    k_limb_conv1_form(const crc_ctx *c, int xf, int yf, int nf);          // 1 plane-major, 2 pixel-major image and limb-folded weights

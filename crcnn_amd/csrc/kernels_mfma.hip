@@ -31,6 +31,7 @@
 // patch matrix exists -- and as much of W (contiguous) into a 5-slot LDS ring (140 KiB), three steps ahead of use; an MFMA spans two steps: 196 per wave and barrier.
 #include "kernels.h"
 #include "limbred.h"
+#include <algorithm>
 #include <cstdlib>
 
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -48,6 +49,7 @@ struct MfmaArgs {
     int n, k, B, zdp, npos, yd, xs, ys_, yf, yo, P, F, Fp, zblks, ksteps, M, mtiles, ntiles;      // ksteps: rounded up to even (the weights carry a zero step)
     unsigned img_bytes; unsigned long long wslot_bytes; int ksteps_real;
     int flat, S, zdc; unsigned fplane;                 // flat form: S steps per window row, zdc channel bytes per position, fplane = 2 npos zdc bytes per plane
+    int sc_B;                                          // scalar form (mfma_mac2w_kernel<.., SC>): B is n * sc_B, image e = s * sc_B + b, the bias of a row is read at slot e / sc_B
     int acc0[8][13];                                   // initial value of the 13 diagonal accumulators, per modulus (limb_tables)
     u64 qinv[8];                                       // q^-1 mod 2^64
 };
@@ -214,7 +216,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 // workgroup, <= 256 registers per wave, so TWO workgroups share a CU and one's stalls are the other's issue slots.
 #define TILE_A (NPL * 64 * 32)
 // MODE: the tensor's addressing -- 0 a dense layer's K-blocked tensor (one position), 1 the flat form of a convolution with fewer than 32 channels, 2 32-channel blocks
-template <int NST, int MODE>
+// SC: the scalar form (CRC_NTTLS).  Under slot batching every weight is a constant polynomial: the same residue at all n slots of a modulus, so the n GEMMs of a
+// modulus share W and are ONE GEMM whose rows run over the n B images e = s B + b.  The tensors of CRC_NTTL already are that GEMM's operands -- [slot][B] images is
+// [modulus][n B] images, byte for byte -- so the tile engine runs as it is with a.B = n B and "slot" = the modulus; what differs is the grid (z = modulus, x = row
+// tile: consecutive workgroups, dealt to the eight XCDs in turn, share one weight tile, which every XCD's L2 holds), the weight base (per modulus) and the bias, an
+// ordinary NTT row read at the row's own slot e / sc_B.  Offsets stay 32-bit: the launcher refuses a modulus whose tensor or result passes 4 GiB (k_scalar_supported).
+template <int NST, int MODE, bool SC = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) mfma_mac2w_kernel(MfmaArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) i8 lds[];
@@ -223,10 +230,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
     // turn and gridDim.x is a multiple of 8 -- y = the slow tile index, z = the slot within the XCD's share.  The workgroups of an XCD walk the tiles of one slot, then
     // of the next: its L2 holds that slot's operands meanwhile.  (Rings whose slot count is not a multiple of 8 -- none of CrCNN's -- put the slot in z as it is.)
     const int slots = a.n * a.k;
-    const int fast = a.xcdmap ? (int)(blockIdx.x >> 3) : (int)blockIdx.x, slow = (int)blockIdx.y;
-    const int slot = a.xcdmap ? (int)(blockIdx.x & 7) * (slots >> 3) + (int)blockIdx.z : (int)blockIdx.z;
-    const int mt = a.mfast ? fast : slow, nt = a.mfast ? slow : fast;
-    const int lgn = __builtin_ctz(a.n), i = slot >> lgn, s = slot & (a.n - 1);          // (n is a power of two)
+    const int fast = !SC && a.xcdmap ? (int)(blockIdx.x >> 3) : (int)blockIdx.x, slow = (int)blockIdx.y;
+    const int slot = !SC && a.xcdmap ? (int)(blockIdx.x & 7) * (slots >> 3) + (int)blockIdx.z : (int)blockIdx.z;
+    const int mt = SC || a.mfast ? fast : slow, nt = SC || a.mfast ? slow : fast;
+    const int lgn = __builtin_ctz(a.n), i = SC ? slot : slot >> lgn, s = SC ? 0 : slot & (a.n - 1);          // (n is a power of two)
     const int m0 = mt * 64, f0 = nt * 32;
     if (f0 >= a.F) return;                                        // a 32-filter tile that is all padding (filters are padded to 64): nothing to compute or store
     const ModParams m = a.mods[i];
@@ -334,7 +341,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
     const u32 RL = 32 * a.P;                                      // bytes of one run of a direct limb result (this tile's 32 filters)
     if (a.xl_out) __syncthreads();
     const int fl = wn * 16 + r16, f = f0 + fl;
-    const u64 bv = (a.bias && f < a.F) ? a.bias[((size_t)f * a.k + i) * a.n + s] : 0;
+    const u64 bv = (!SC && a.bias && f < a.F) ? a.bias[((size_t)f * a.k + i) * a.n + s] : 0;
     const u32 img_jump = (u32)(a.F - 1) * P2;                     // Ys [image][filter][2P]: rows run on inside an image's filter block, the next image's is F - 1 blocks further
 #pragma unroll
     for (int rs = 0; rs < 2; rs++) {
@@ -346,7 +353,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
 #pragma unroll
             for (int d = 0; d < 13; d++) D[d] = acc[rs][d][reg];
             u64 v = diag_reduce_w(D, m, qinv);
-            if ((reg & 1) == 0) v = addmod(v, bv, m.q);
+            if (SC) {                                                 // the row's image e = s B + b: its bias sits at slot s (rows past M belong to no image)
+                if ((reg & 1) == 0 && a.bias && f < a.F && mbase + reg < (u32)a.M) {
+                    const u32 r = rem + reg, e = bb + (r >= P2) + (r >= 2 * P2);
+                    v = addmod(v, a.bias[((size_t)f * a.k + i) * a.n + e / (u32)a.sc_B], m.q);
+                }
+            } else if ((reg & 1) == 0) v = addmod(v, bv, m.q);
             if (a.xl_out) {
                 const u32 rt = wm * 32 + rs * 16 + 4 * kg + reg, bl = rt >> a.lp2, qq = rt & (P2 - 1);
                 const u64 dg = f < a.F ? balanced_digit_bytes(v, m.q) : 0;
@@ -437,9 +449,11 @@ __global__ void __launch_bounds__(64) limb_pack_tensor_kernel(const u64 *x, i8 *
 // The same conversion for ONE position (a dense layer's K-blocked tensor [plane][channel block][row = image * 2 + poly][32]) as an LDS-staged transpose, the structure of
 // limb_pack_weights_kernel below: a workgroup = 32 slots x 4 neighbouring rows of one channel block; thread (slot, row, 16-channel half) reads its channel values (lanes
 // over slots: coalesced row segments), stages the seven planes' bytes, and the workgroup writes every (slot, plane)'s 4 x 32 = 128 contiguous bytes as one line.
+// `scalar`: the CRC_NTTLS dense input [modulus][plane][channel block][row = (e, poly)][32], e = s B + b (a whole-launch tensor: Btot = B, b0 = 0) -- the same
+// 128-byte runs, at the row of image s B + b of the modulus' n B images instead of in a block of the slot's own
 #define TRG 4
 #define TSL 32
-__global__ void __launch_bounds__(256) limb_pack_dense_kernel(const u64 *x, i8 *xl, const ModParams *mods, int n, int k, int B, int zd, int zdp, int packed, int Btot, int b0)
+__global__ void __launch_bounds__(256) limb_pack_dense_kernel(const u64 *x, i8 *xl, const ModParams *mods, int n, int k, int B, int zd, int zdp, int packed, int Btot, int b0, int scalar)
 {
     __shared__ __attribute__((aligned(16))) i8 st[TSL * NPL * TRG * 32];         // [slot][plane][row of the group][32 channels]
     const int sblocks = n / TSL, zblks = zdp / 32, rgs = (2 * B + TRG - 1) / TRG;
@@ -477,7 +491,8 @@ __global__ void __launch_bounds__(256) limb_pack_dense_kernel(const u64 *x, i8 *
     for (int o = threadIdx.x; o < TSL * NPL * pieces_per_run; o += 256) {
         const int run = o / pieces_per_run, part = o - run * pieces_per_run, sl = run / NPL, l = run - sl * NPL;
         if ((part >> 1) >= rows_here) continue;
-        i8 *dst = xl + ((size_t)i * n + s0 + sl) * slot_stride + (size_t)l * plane_stride + ((size_t)zb * (2 * Btot) + (size_t)b0 * 2 + rg * TRG) * 32 + part * 16;
+        i8 *dst = scalar ? xl + ((size_t)i * NPL + l) * (plane_stride * n) + (((size_t)zb * n + s0 + sl) * (2 * B) + rg * TRG) * 32 + part * 16
+                         : xl + ((size_t)i * n + s0 + sl) * slot_stride + (size_t)l * plane_stride + ((size_t)zb * (2 * Btot) + (size_t)b0 * 2 + rg * TRG) * 32 + part * 16;
         *reinterpret_cast<uint4 *>(dst) = *reinterpret_cast<const uint4 *>(st + (size_t)run * (TRG * 32) + part * 16);
     }
 }
@@ -566,7 +581,8 @@ __global__ void __launch_bounds__(256) slotmajor_to_rows_kernel(const u64 *ys, u
     }
 }
 // Ys [slot][B][zd'*2] (zd' = F*P flattened channels, poly innermost) -> Xl' [slot][7][zdp'/32][B*2][32] for a dense consumer.  One thread per 16 channels.
-__global__ void __launch_bounds__(256) slotmajor_to_limb_kernel(const u64 *ys, i8 *xl, const ModParams *mods, int n, int B, int zd, int zdp, size_t total)
+// (`scalar`: the CRC_NTTLS dense input, rows = (e = s B + b, poly) of the modulus' n B images)
+__global__ void __launch_bounds__(256) slotmajor_to_limb_kernel(const u64 *ys, i8 *xl, const ModParams *mods, int n, int B, int zd, int zdp, size_t total, int scalar)
 {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;              // ((slot*B + b)*2 + c)*(zdp/16) + zg
     if (t >= total) return;
@@ -588,9 +604,55 @@ __global__ void __launch_bounds__(256) slotmajor_to_limb_kernel(const u64 *ys, i
             for (int l = 0; l < NPL; l++) pl[l][z >> 2] |= (u32)(d[l] & 0xff) << (8 * (z & 3));
         }
     }
-    i8 *dst = xl + slot * ((size_t)NPL * 2 * B * zdp) + ((size_t)(zg >> 1) * (2 * B) + b * 2 + c) * 32 + (zg & 1) * 16;      // K-blocked dense input (header)
+    const size_t rows = scalar ? (size_t)n * 2 * B : (size_t)2 * B, row = (scalar ? (slot % n) * (size_t)(2 * B) : 0) + b * 2 + c, blk = scalar ? slot / n : slot;
+    i8 *dst = xl + blk * ((size_t)NPL * rows * zdp) + ((size_t)(zg >> 1) * rows + row) * 32 + (zg & 1) * 16;      // K-blocked dense input (header)
 #pragma unroll
-    for (int l = 0; l < NPL; l++) *reinterpret_cast<uint4 *>(dst + (size_t)l * (zdp / 32) * (2 * B) * 32) = make_uint4(pl[l][0], pl[l][1], pl[l][2], pl[l][3]);
+    for (int l = 0; l < NPL; l++) *reinterpret_cast<uint4 *>(dst + (size_t)l * (zdp / 32) * rows * 32) = make_uint4(pl[l][0], pl[l][1], pl[l][2], pl[l][3]);
+}
+// ---- scalar form (CRC_NTTLS): the weights of a slot-batched network ---------------------------------------------------------------------------
+// Weights as one residue per modulus -> Wls [modulus][step][7][Fp][32]: CRC_NTTL's container (flat and blocked step order, zero filter / channel padding, a zero step
+// behind an odd count, every weight times 2^64 mod q) for a one-slot ring.  The source is canonical NTT rows [F][zd][taps][k][n] read at word 0 (wstride = n; that the
+// other n - 1 words say the same is scalar_rows_constant_kernel's business) or k-word scalars [F][zd][taps][k] (wstride = 1).  One thread per (modulus, step, filter
+// of Fp, 16-term half): it writes its 16 bytes of all seven planes, padding included, so nothing is cleared beforehand.  A start-up path: kilobytes to megabytes.
+__global__ void __launch_bounds__(256) scalar_pack_weights_kernel(const u64 *w, size_t wstride, i8 *wl, const ModParams *mods, int k, int F, int Fp, int zd, int zblks, int xf, int yf,
+                                                                  int flat_zdc, int S, int steps, int steps_even)
+{
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;              // ((i * steps_even + step) * Fp + f) * 2 + h
+    if (t >= (size_t)k * steps_even * Fp * 2) return;
+    const int h = (int)(t & 1), f = (int)((t >> 1) % Fp);
+    const int step = (int)((t >> 1) / Fp % steps_even), i = (int)((t >> 1) / Fp / steps_even), taps = xf * yf;
+    const ModParams m = mods[i];
+    const u64 R = barrett128(0, 1, m);                           // 2^64 mod q
+    u32 pl[NPL][4];
+#pragma unroll
+    for (int l = 0; l < NPL; l++)
+#pragma unroll
+        for (int wv = 0; wv < 4; wv++) pl[l][wv] = 0;
+    if (f < F && step < steps) {
+        int tap, ch, ky = 0, kx = 0;                              // term -> (tap, channel): limb_pack_weights_kernel's rule
+        if (flat_zdc) { kx = step / S; const int j0 = (step - kx * S) * 32 + h * 16; ky = j0 / flat_zdc; ch = j0 - ky * flat_zdc; tap = kx * yf + ky; }
+        else { tap = step / zblks; ch = (step - tap * zblks) * 32 + h * 16; }
+#pragma unroll
+        for (int z = 0; z < 16; z++) {
+            if (ch < zd && (!flat_zdc || ky < yf)) {
+                const u64 v = mulmod(w[((((size_t)f * zd + ch) * taps + tap) * k + i) * wstride], R, m);
+                int d[NPL]; limb_digits(v, m.q, d);
+#pragma unroll
+                for (int l = 0; l < NPL; l++) pl[l][z >> 2] |= (u32)(d[l] & 0xff) << (8 * (z & 3));
+            }
+            ch++;
+            if (flat_zdc && ch == flat_zdc) { ch = 0; ky++; tap++; }
+        }
+    }
+    i8 *dst = wl + ((size_t)i * steps_even + step) * ((size_t)NPL * Fp * 32) + (size_t)f * 32 + h * 16;
+#pragma unroll
+    for (int l = 0; l < NPL; l++) *reinterpret_cast<uint4 *>(dst + (size_t)l * Fp * 32) = make_uint4(pl[l][0], pl[l][1], pl[l][2], pl[l][3]);
+}
+// are all n words of every row equal (a constant polynomial's NTT form)?  *flag (pre-zeroed) is set otherwise: every thread that finds a difference stores the same 1
+__global__ void __launch_bounds__(256) scalar_rows_constant_kernel(const u64 *w, size_t words, int n, int *flag)
+{
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < words; t += (size_t)gridDim.x * blockDim.x)       // (a layer's rows can pass 2^32 words)
+        if (w[t] != w[t - (t & (size_t)(n - 1))]) *flag = 1;
 }
 
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
@@ -621,20 +683,23 @@ size_t k_limb_tensor_bytes(const crc_ctx *c, int B, int zd, int npos)
 size_t k_limb_weights_bytes(const crc_ctx *c, int nf, int zd, int xf, int yf) { return (size_t)c->n * c->k * round_up(k_limb_steps(zd, xf, yf), 2) * NPL * round_up(nf, 64) * 32; }      // (an odd number of reduction steps gets a zero step)
 size_t k_limb_result_words(const crc_ctx *c, int B, int nf, int P) { return (size_t)c->n * c->k * B * nf * P * 2; }
 
-int k_limb_pack_tensor(crc_ctx *c, const u64 *x, i8 *xl, int B, int zd, int npos, bool packed, hipStream_t st, int Btot, int b0)
+// scalar: a dense layer's tensor in the CRC_NTTLS row order (a convolution's tensor is the same bytes in either form: the flag changes nothing there)
+int k_limb_pack_tensor(crc_ctx *c, const u64 *x, i8 *xl, int B, int zd, int npos, bool packed, hipStream_t st, int Btot, int b0, bool scalar)
 {
     if (Btot <= 0) { Btot = B; b0 = 0; }
     if (b0 < 0 || b0 + B > Btot) return CRC_ERR_INVALID_ARGUMENT;
+    if (npos > 1) scalar = false;
+    if (scalar && (Btot != B || b0 != 0)) return CRC_ERR_INVALID_ARGUMENT;          // a whole-launch tensor only
     const int zdp = round_up(zd, 32);
     // pieces per thread: a dense layer's K-blocked tensor (one position) takes 4 neighbouring rows of a channel block -- 4 x 32 B = one whole line per plane, written back to
     // back; for the convolution layout 4 and 8 adjacent pieces per thread measured 3-7 % slower
     const int group = c->tune.limb_pack_group > 1 ? c->tune.limb_pack_group : (npos == 1 && (B * 2) % 4 == 0 ? 4 : 1);
     const size_t items = (size_t)B * npos * 2 * (zdp / 32);
-    if (npos == 1 && c->tune.limb_pack_group <= 1) {       // a dense layer's tensor: the LDS-staged transpose (whole-line stores)
+    if (npos == 1 && (scalar || c->tune.limb_pack_group <= 1)) {       // a dense layer's tensor: the LDS-staged transpose (whole-line stores)
         const size_t blocks = (size_t)(c->n / TSL) * c->k * (zdp / 32) * ((2 * (size_t)B + TRG - 1) / TRG);
         if (blocks == 0) return CRC_OK;
         if (blocks > 0x7fffffffULL) return CRC_ERR_INVALID_ARGUMENT;
-        hipLaunchKernelGGL(limb_pack_dense_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, xl, c->d_mods, c->n, c->k, B, zd, zdp, packed ? 1 : 0, Btot, b0);
+        hipLaunchKernelGGL(limb_pack_dense_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, xl, c->d_mods, c->n, c->k, B, zd, zdp, packed ? 1 : 0, Btot, b0, scalar ? 1 : 0);
         HIPCHK(hipGetLastError());
         return CRC_OK;
     }
@@ -673,21 +738,64 @@ int k_limb_result_to_rows(crc_ctx *c, const u64 *ys, u64 *y, size_t rows, bool p
     HIPCHK(hipGetLastError());
     return CRC_OK;
 }
-int k_limb_result_to_limb(crc_ctx *c, const u64 *ys, i8 *xl, int B, int zd, hipStream_t st)
+int k_limb_result_to_limb(crc_ctx *c, const u64 *ys, i8 *xl, int B, int zd, hipStream_t st, bool scalar)
 {
     const int zdp = round_up(zd, 32);
     const size_t total = (size_t)c->n * c->k * B * 2 * (zdp / 16);
     if (total == 0) return CRC_OK;
-    hipLaunchKernelGGL(slotmajor_to_limb_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, ys, xl, c->d_mods, c->n, B, zd, zdp, total);
+    hipLaunchKernelGGL(slotmajor_to_limb_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, ys, xl, c->d_mods, c->n, B, zd, zdp, total, scalar ? 1 : 0);
     HIPCHK(hipGetLastError());
     return CRC_OK;
 }
 // the layer: Xl (B images of zd x xd x yd) * Wl -> Ys [slot][B][nf][P][2], + NTT-form bias on poly 0
 // can the layer write a dense consumer's limb tensor itself?  (the output tile must be whole images: 2P a power of two dividing 64)
 bool k_limb_direct_dense(int P) { const int p2 = 2 * P; return p2 <= 64 && (p2 & (p2 - 1)) == 0; }
-int k_limb_mac(crc_ctx *c, const i8 *xl, const i8 *wl, u64 *ys, i8 *xl_out, const u64 *bias_ntt, int B, int zd, int xd, int yd, int xs, int ys_, int xf, int yf, int nf, hipStream_t st)
+// ---- scalar form: sizes, the admission query, the weight pack ----
+size_t k_scalar_weights_bytes(const crc_ctx *c, int nf, int zd, int xf, int yf) { return (size_t)c->k * round_up(k_limb_steps(zd, xf, yf), 2) * NPL * round_up(nf, 64) * 32; }
+// Can the layer run in scalar form on B images per slot?  The limb form's own limits (moduli of at most 55 bits, reductions of at most 18 000 terms, k <= 8) and the
+// 32-bit offsets of the tile engine: with n B images behind one base pointer a modulus' tensor and its slot-major result must each stay below 4 GiB.  (REFUSED here
+// rather than widened to a 64-bit tile base in the kernel: no model at the parameters of the records comes within two orders of magnitude of the limit.)
+bool k_scalar_supported(const crc_ctx *c, int B, int zd, int xd, int yd, int xs, int ys_, int xf, int yf, int nf)
+{
+    if (B < 1 || c->k > 8 || !k_limb_supported(c, k_limb_steps(zd, xf, yf) * 32)) return false;
+    const unsigned long long Be = (unsigned long long)c->n * B, npos = (unsigned long long)xd * yd, P = (unsigned long long)((xd - xf) / xs + 1) * ((yd - yf) / ys_ + 1);
+    const unsigned long long img = npos == 1 ? (unsigned long long)NPL * 2 * round_up(zd, 32) : limb_img_bytes(zd, (int)npos);
+    if (Be * img + 64 > 0xffffffffULL) return false;                                  // src_off, delta (+ 64: the flat form's last piece)
+    if (Be * 2 * P * round_up(nf, 64) > 0xffffffffULL) return false;                  // idx0 + jump: words of the modulus' result, rows rounded up by the filter padding
+    if ((Be * 2 * P + 63) / 64 > 0x7fffffffULL) return false;                         // row tiles: grid x
+    return true;
+}
+int k_scalar_pack_weights(crc_ctx *c, const u64 *w, size_t wstride, i8 *wl, int nf, int zd, int xf, int yf, int *constant, hipStream_t st)
+{
+    *constant = 1;
+    const int zblks = round_up(zd, 32) / 32, Fp = round_up(nf, 64), zdc = k_limb_flat_zdc(zd), S = zdc ? (yf * zdc + 31) / 32 : 0, steps = k_limb_steps(zd, xf, yf), se = round_up(steps, 2);
+    if (wstride != 1) {                                           // rows: every one must be a constant polynomial
+        const size_t words = (size_t)nf * zd * xf * yf * c->k * c->n;
+        const size_t cblocks = std::min<size_t>((words + 255) / 256, (size_t)1 << 20);
+        int *d_flag = nullptr, flag = 0;
+        HIPCHK(hipMalloc(&d_flag, sizeof(int)));
+        hipError_t e = hipMemsetAsync(d_flag, 0, sizeof(int), st);
+        if (e == hipSuccess) { hipLaunchKernelGGL(scalar_rows_constant_kernel, dim3((unsigned)cblocks), dim3(256), 0, st, w, words, c->n, d_flag); e = hipGetLastError(); }
+        if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        (void)hipFree(d_flag);
+        HIPCHK(e);
+        if (flag) { *constant = 0; return CRC_ERR_INVALID_ARGUMENT; }
+    }
+    const size_t threads = (size_t)c->k * se * Fp * 2;
+    if ((threads + 255) / 256 > 0x7fffffffULL) return CRC_ERR_INVALID_ARGUMENT;
+    hipLaunchKernelGGL(scalar_pack_weights_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, w, wstride, wl, c->d_mods, c->k, nf, Fp, zd, zblks, xf, yf, zdc, S, steps, se);
+    HIPCHK(hipGetLastError());
+    if (wstride == 1) HIPCHK(hipStreamSynchronize(st));           // (one synchronisation either way: a start-up path)
+    return CRC_OK;
+}
+// scalar: xl / ys / xl_out hold n B images per modulus (CRC_NTTLS), wl is k_scalar_pack_weights' result; always on mfma_mac2w_kernel
+int k_limb_mac(crc_ctx *c, const i8 *xl, const i8 *wl, u64 *ys, i8 *xl_out, const u64 *bias_ntt, int B, int zd, int xd, int yd, int xs, int ys_, int xf, int yf, int nf, hipStream_t st,
+               bool scalar)
 {
     if (B == 0) return CRC_OK;
+    const int Bslot = B;
+    if (scalar) { if (!k_scalar_supported(c, B, zd, xd, yd, xs, ys_, xf, yf, nf)) return CRC_ERR_UNSUPPORTED; B *= c->n; }
     const int xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys_ + 1;
     MfmaArgs a{};
     a.xl = xl; a.wl = wl; a.ys = ys; a.mods = c->d_mods; a.bias = bias_ntt;
@@ -704,8 +812,9 @@ int k_limb_mac(crc_ctx *c, const i8 *xl, const i8 *wl, u64 *ys, i8 *xl_out, cons
         for (a.lp2 = 0; (1 << a.lp2) < 2 * a.P; a.lp2++) {}
     }
     a.img_bytes = (unsigned)img; a.wslot_bytes = (unsigned long long)round_up(a.ksteps_real, 2) * NPL * a.Fp * 32;
+    a.sc_B = Bslot;
     const size_t grid = (size_t)c->n * c->k * a.mtiles * a.ntiles;
-    if (grid > 0x7fffffffULL) return CRC_ERR_INVALID_ARGUMENT;
+    if (!scalar && grid > 0x7fffffffULL) return CRC_ERR_INVALID_ARGUMENT;
     if (c->k > 8) return CRC_ERR_UNSUPPORTED;
     limb_tables(c, a.ksteps_real * 32, a.acc0, a.qinv);
     const int ring = c->tune.mfma_ring;     // tuning (tools/)
@@ -713,6 +822,15 @@ int k_limb_mac(crc_ctx *c, const i8 *xl, const i8 *wl, u64 *ys, i8 *xl_out, cons
     // layers with few row tiles and many filter tiles (dense layers) stream their weights: walk the row tiles of one filter tile back to back, so that the weight tile is
     // fetched from HBM once and the (small) tensor stays in L2; convolutions keep filter tiles fastest (the big tensor tile is shared, the weights sit in L2)
     a.mfast = c->tune.mfma_order >= 0 ? c->tune.mfma_order : (a.mtiles < a.Fp / 32 ? 1 : 0);
+    if (scalar) {                                                // grid: x = row tile, y = 32-filter tile, z = modulus
+        const size_t lds = (size_t)5 * TILE_A;
+        auto kern2 = a.npos == 1 ? mfma_mac2w_kernel<5, 0, true> : a.flat ? mfma_mac2w_kernel<5, 1, true> : mfma_mac2w_kernel<5, 2, true>;
+        if (a.Fp / 32 > 65535) return CRC_ERR_INVALID_ARGUMENT;
+        { const int rc = crc_ctx_ensure_lds(c, (const void *)kern2, lds); if (rc) return rc; }
+        hipLaunchKernelGGL(kern2, dim3((unsigned)a.mtiles, (unsigned)(a.Fp / 32), (unsigned)c->k), dim3(256), lds, st, a);
+        HIPCHK(hipGetLastError());
+        return CRC_OK;
+    }
     const int variant = c->tune.mfma_variant;                    // 2 (default): two workgroups per CU (mfma_mac2w_kernel); 1: mfma_mac_kernel (the tests run both: crc_ctx_set_tuning)
     if (variant == 2) {
         const int slots = c->n * c->k, ntiles2 = a.Fp / 32;

@@ -229,7 +229,7 @@ ciphertext3D::ciphertext3D(int B, int zd, int xd, int yd, int form) : B(B), zd(z
     if (form == CRC_NTTLC) { const size_t lb = crc_limb_tensor_bytes(ctx(), B, zd, xd, yd); if (lb > bytes) bytes = lb; }      // channels padded to 32
     // a dense consumer's limb tensor: every output a channel of ONE position, rounded up to 32 (7 bytes per residue: larger than the ciphertexts below 217
     // channels)
-    if (form == CRC_NTTL) { const size_t lb = crc_limb_tensor_bytes(ctx(), B, zd * xd * yd, 1, 1); if (lb > bytes) bytes = lb; }
+    if (form == CRC_NTTL || form == CRC_NTTLS) { const size_t lb = crc_limb_tensor_bytes(ctx(), B, zd * xd * yd, 1, 1); if (lb > bytes) bytes = lb; }
     if (g_out_hint) {
         shared_ptr<DeviceBuffer> *slot = g_out_hint; g_out_hint = nullptr;
         if (!*slot || (*slot)->bytes < bytes) { slot->reset(); *slot = make_shared<DeviceBuffer>(bytes); }
@@ -241,7 +241,7 @@ ciphertext3D::ciphertext3D(int B, int zd, int xd, int yd, int form) : B(B), zd(z
 ciphertext3D ciphertext3D::images(int b0, int count) const
 {
     if (!buf || b0 < 0 || count < 1 || b0 + count > B) throw invalid_argument("ciphertext3D::images: range outside the batch");
-    if (form == CRC_NTTL || form == CRC_NTTLC) throw invalid_argument("ciphertext3D::images: a limb tensor is laid out for its whole batch");
+    if (form == CRC_NTTL || form == CRC_NTTLC || form == CRC_NTTLS) throw invalid_argument("ciphertext3D::images: a limb tensor is laid out for its whole batch");
     ciphertext3D v; v.B = count; v.zd = zd; v.xd = xd; v.yd = yd; v.form = form; v.buf = buf;
     v.offset = offset + (size_t)b0 * zd * xd * yd * ctBytes();
     return v;
@@ -826,7 +826,8 @@ static bool g_matrix_cores = true;                  // Network::matrix_cores of 
 int MacLayer::plannedForm(int B) const
 {
     int wf = CRC_NTT;
-    chk(crc_plan_mac(ctx(), zd, xd, yd, xs, ys, xf, yf, nf, B, g_matrix_cores ? 1 : 0, &wf), "crc_plan_mac");
+    if (slot_weights && g_matrix_cores) chk(crc_plan_mac_scalar(ctx(), zd, xd, yd, xs, ys, xf, yf, nf, B, &wf), "crc_plan_mac_scalar");
+    else chk(crc_plan_mac(ctx(), zd, xd, yd, xs, ys, xf, yf, nf, B, g_matrix_cores ? 1 : 0, &wf), "crc_plan_mac");
     return wf;
 }
 // room for the limb copy (CRC_NTTL) beside the canonical weights it is made from
@@ -903,7 +904,8 @@ string MacLayer::kernelName() const
         "mac_stream_kernel (weight stream: one image, two rows per weight; v_mad_u64_u32, CRC_NTTP)" :
         "mac_stream_kernel (weight stream: one image; canonical residues)";
     const int wf = streamed ? stream_form : w_form;
-    const string k = wf == CRC_NTTL ? "mfma_mac2w_kernel (int8 limb GEMM, CRC_NTTL)" : wf == CRC_NTTL1 ?
+    const string k = wf == CRC_NTTLS ? "mfma_mac2w_kernel (int8 limb GEMM over all slots, scalar weights, CRC_NTTLS)" :
+                     wf == CRC_NTTL ? "mfma_mac2w_kernel (int8 limb GEMM, CRC_NTTL)" : wf == CRC_NTTL1 ?
         "mfma_conv1_kernel (one-channel convolution on the matrix cores, CRC_NTTL1)"
                    : wf == CRC_NTTP ? "mac3_kernel (v_mad_u64_u32, CRC_NTTP)" : "mac3_kernel (v_mad_u64_u32, canonical residues)";
     return k + (!streamed ? "" : wf == CRC_NTTL ? ", streamed weights (64-filter limb tiles built inside the forward)" : ", streamed weights") +
@@ -914,7 +916,7 @@ bool MacLayer::streamsOnMatrixCores(int B) { upload(); return streamed && planne
 void MacLayer::restoreCanonical()
 {
     if (w_form == CRC_NTTP || (w_form == CRC_NTTL1 && d_w_canon)) { packWeights(true); return; }
-    if (w_form != CRC_NTTL && w_form != CRC_NTTL1) return;
+    if (w_form != CRC_NTTL && w_form != CRC_NTTL1 && w_form != CRC_NTTLS) return;
     if (!hasPlaintexts()) throw logic_error(dense ? "FullyConnectedLayer " + name + ": weights are in limb form and there are no plaintexts to rebuild them from" :
         "ConvolutionalLayer " + name + ": a folded layer's weights are in limb form and it has no plaintexts to rebuild them from");
     // (a tile-wise layer goes back to "not built": the next forward builds its limb tensor again, with whatever batch-norm layer fuse() folds into it)
@@ -946,8 +948,20 @@ bool MacLayer::limbWeights(int B)
     upload();
     if (streamed) return false;
     if (tilewise) { buildTilewise(); return true; }
-    if (w_form == CRC_NTTL || w_form == CRC_NTTL1) return true;
-    const int planned = plannedForm(B);
+    if (w_form == CRC_NTTL || w_form == CRC_NTTL1 || w_form == CRC_NTTLS) return true;
+    int planned = plannedForm(B);
+    if (planned == CRC_NTTLS) {
+        // the scalar form of a slot-batched layer: packed from the (possibly fused) canonical rows, which are dropped like the limb GEMM's.  Kilobytes to a few
+        // megabytes: no look at the free memory.  A row that is not a constant polynomial (the pack says so) keeps the layer on the row path, silently
+        if (w_form == CRC_NTTP) packWeights(true);
+        auto ws = make_shared<DeviceBuffer>(crc_scalar_weights_bytes(ctx(), nf, zd, xf, yf));
+        int constant = 1;
+        const int rc = crc_scalar_pack_weights(ctx(), (const uint64_t *)d_w->ptr, N(), nf, zd, xf, yf, ws->ptr, &constant, stream());
+        if (rc == CRC_OK) { d_w = ws; w_form = CRC_NTTLS; return true; }
+        if (constant) chk(rc, "crc_scalar_pack_weights");
+        slot_weights = false;
+        planned = plannedForm(B);
+    }
     // The one-channel matrix-core kernel (kernels_mfma1.hip) is a convolution's only: crc_plan_mac answers CRC_NTTL1 for a dense layer with in_dim == 1 as
     // well, which stays on the vector-ALU kernel
     const bool conv1 = !dense && planned == CRC_NTTL1;
@@ -969,7 +983,7 @@ void MacLayer::packWeights(bool unpack)
     upload();
     if (streamed || (tilewise && !tile_built)) return;
     if (w_form == CRC_NTTL1 && unpack) { d_w = d_w_canon; d_w_canon.reset(); w_form = CRC_NTT; return; }
-    if (w_form == CRC_NTTL || w_form == CRC_NTTL1) { if (unpack) throw logic_error(kind() + (" " + name) +
+    if (w_form == CRC_NTTL || w_form == CRC_NTTL1 || w_form == CRC_NTTLS) { if (unpack) throw logic_error(kind() + (" " + name) +
         ": weights are in limb form (fuse() / broadcastParameters() must precede the first forward())"); return; }
     if ((w_form == CRC_NTTP) == !unpack) return;
     chk(crc_pack28(ctx(), (uint64_t *)d_w->ptr, nf * taps() * K(), unpack ? 1 : 0, stream()), "crc_pack28");
@@ -1440,6 +1454,8 @@ ciphertext3D Network::forward(ciphertext3D input)
             // one: the chunks of a group are packed straight into it, and no second copy of the group's input is made inside the layer
             if (matrix_cores && m->dense && m->streamsOnMatrixCores(Bi)) { limb[i] = 1; streams[i] = 1; }
         }
+    // a dense layer in scalar form (CRC_NTTLS) has no weight stream to amortise over a group of chunks: the whole network runs chunk by chunk instead
+    const bool per_chunk = chunked && mac[split]->w_form == CRC_NTTLS;
     for (int i = 0; i < L; i++) {
         // the tensor in front of the refresh is decrypted as it stands (crc_refresh_dev takes either ciphertext form): an NTT-resident network stays resident
         // across it, but no packed / limb hand-over spans it
@@ -1447,10 +1463,15 @@ ciphertext3D Network::forward(ciphertext3D input)
         bool coeff = !ntt_resident || i == L - 1;
         // a conv / dense layer feeding another one hands its tensor over packed as well ... and a limb layer feeding a DENSE limb layer hands it over in limb
         // form (not across the chunk boundary: a dense layer's limb tensor is laid out for its whole batch, the chunks are assembled into it below)
-        const bool to_dense_limb = i + 1 < L && limb[i] && !streams[i] && limb[i + 1] && mac[i + 1]->dense && !(chunked && i + 1 == split);
-        // ... and a one-channel convolution writes the limb tensor of a matrix-core CONVOLUTION behind it itself
-        const bool to_conv_limb = mac[i] && mac[i + 1] && !mac[i]->dense && !mac[i + 1]->dense && mac[i]->w_form == CRC_NTTL1 && mac[i + 1]->w_form == CRC_NTTL;
-        layers[i]->out_form = coeff ? CRC_COEFF : before_refresh ? CRC_NTT : to_dense_limb && max_num_of_reencryptions < 0 ? CRC_NTTL : to_conv_limb &&
+        // A producer writes the form its consumer's plan names: a scalar dense layer reads CRC_NTTLS, which only a scalar layer writes (any other producer hands
+        // over packed rows and the consumer converts them); the per-slot limb GEMM reads CRC_NTTL, which every limb layer writes
+        const bool to_scalar = i + 1 < L && mac[i + 1] && mac[i + 1]->w_form == CRC_NTTLS;
+        const bool to_dense_limb = i + 1 < L && limb[i] && !streams[i] && limb[i + 1] && mac[i + 1]->dense && !(chunked && !per_chunk && i + 1 == split) &&
+            (!to_scalar || mac[i]->w_form == CRC_NTTLS);
+        // ... and a one-channel convolution writes the limb tensor of a matrix-core CONVOLUTION behind it itself (the same bytes for CRC_NTTL and CRC_NTTLS)
+        const bool to_conv_limb = mac[i] && mac[i + 1] && !mac[i]->dense && !mac[i + 1]->dense && mac[i]->w_form == CRC_NTTL1 &&
+            (mac[i + 1]->w_form == CRC_NTTL || mac[i + 1]->w_form == CRC_NTTLS);
+        layers[i]->out_form = coeff ? CRC_COEFF : before_refresh ? CRC_NTT : to_dense_limb && max_num_of_reencryptions < 0 ? (to_scalar ? CRC_NTTLS : CRC_NTTL) : to_conv_limb &&
             max_num_of_reencryptions < 0 ? CRC_NTTLC : (packable && max_num_of_reencryptions < 0 && mac[i] && mac[i + 1] ? CRC_NTTP : CRC_NTT);
     }
     last_layer_ms.assign(L, 0.0);
@@ -1544,6 +1565,25 @@ ciphertext3D Network::forward(ciphertext3D input)
         return input;
     }
     int first = 0;
+    if (per_chunk) {
+        const int B = input.B;
+        ciphertext3D result;
+        for (int b0 = 0; b0 < B; b0 += head_chunk) {
+            const int Bc = min(head_chunk, B - b0);
+            ciphertext3D t = input.images(b0, Bc);
+            later_chunk = b0 > 0;
+            for (int i = 0; i < L; i++) {
+                if (i == layer_before_reenc) t = run_refresh(t);
+                OutHint hint(&act_slot[t.buf == act_slot[0] ? 1 : 0]); t = run_layer(i, t);
+            }
+            const size_t out_cts = (size_t)t.zd * t.xd * t.yd;
+            if (!result.buf) result = ciphertext3D(B, t.zd, t.xd, t.yd, t.form);
+            chk(crc_memcpy_d2d(ctx(), (char *)result.data() + (size_t)b0 * out_cts * ctBytes(), t.data(), (size_t)Bc * out_cts * ctBytes(), stream()), "crc_memcpy_d2d");
+        }
+        later_chunk = false;
+        if (time_with_events) { chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync"); read_events(); }
+        return result;
+    }
     if (chunked) {
         const int B = input.B;
         ciphertext3D tail_in;

@@ -199,7 +199,7 @@ public:
     std::string kernelName() const override;
 protected:
     MacLayer(std::string name, bool dense, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf)
-        : Layer(name), zd(zd), xd(xd), yd(yd), xs(xs), ys(ys), xf(xf), yf(yf), nf(nf), dense(dense) {}
+        : Layer(name), zd(zd), xd(xd), yd(yd), xs(xs), ys(ys), xf(xf), yf(yf), nf(nf), dense(dense), slot_weights(slotEncoding()) {}
     // the layer on an input the caller has checked; the output tensor is [B][zo][xo][yo]
     ciphertext3D run(const ciphertext3D &input, int zo, int xo, int yo);
 private:
@@ -218,8 +218,11 @@ private:
     bool streamed = false;
     int stream_form = CRC_NTT;                              // operand form of the last streamed forward (CRC_NTTL: 64-filter limb tiles on the matrix cores)
     std::shared_ptr<DeviceBuffer> d_plain, d_wtile, d_ytile;
-    // CRC_NTTP / CRC_NTTL / CRC_NTTL1 once Network::forward has put the weights into their MAC kernel's operand form
+    // CRC_NTTP / CRC_NTTL / CRC_NTTL1 / CRC_NTTLS once Network::forward has put the weights into their MAC kernel's operand form
     int w_form = CRC_NTT;
+    // built under setSlotEncoding: the weights are constant polynomials and the layer asks crc_plan_mac_scalar (the scalar form CRC_NTTLS, one GEMM per modulus
+    // over all slots).  Cleared for good when crc_scalar_pack_weights finds a row that is not constant: the layer then keeps the row path
+    bool slot_weights;
     // CONVOLUTIONS ONLY: the one-channel matrix-core form CRC_NTTL1 (limbWeights), and with it the canonical NTT-form weights it keeps beside the limb copy
     std::shared_ptr<DeviceBuffer> d_w_canon;
     // DENSE LAYERS ONLY (upload): a layer whose canonical NTT-form weights and their limb copy do not fit in HBM together (PlainModelWoPad's fc3 at n = 16384,

@@ -77,7 +77,15 @@ enum { CRC_COEFF = 0, CRC_NTT = 1,
        CRC_NTTL1 = 4,
        /* out_form only, with w_form = CRC_NTTL1: the result as the limb tensor a CONVOLUTION reads with in_form = CRC_NTTL
         * ([k][n][B][7][xo*yo][2][32 channels]; CRC_NTTL as out_form flattens for a dense consumer instead) */
-       CRC_NTTLC = 5 };
+       CRC_NTTLC = 5,
+       /* "scalar limb form": CRC_NTTL for a slot-batched network (crc_slots_*: n images per ciphertext), whose weights are constant polynomials -- one residue
+        * per modulus, the same at all n slots.  The n per-slot GEMMs of a modulus share their weights and run as ONE GEMM over the n B images e = s B + b.
+        *   weights (w_form)       [k][step][7][Fp][32] int8, CRC_NTTL's container for a one-slot ring: crc_scalar_pack_weights, crc_limb_weights_bytes / n bytes
+        *   convolution tensors    byte-identical to CRC_NTTL ([slot][B] images ARE [modulus][n B] images): pass in_form = CRC_NTTL
+        *   dense input / output   [k][7][zdp / 32][(e, poly)][32]: in_form / out_form = CRC_NTTLS (differs from CRC_NTTL's per-slot K-blocking)
+        * crc_conv2d_forms / crc_dense_forms take w_form = CRC_NTTLS with any in_form / out_form of CRC_NTTL besides; biases stay ordinary NTT rows.
+        * crc_scalar_supported answers for a context and shape. */
+       CRC_NTTLS = 6 };
 
 const char *crc_strerror(int status);
 int         crc_last_hip_error(void);
@@ -107,7 +115,7 @@ int  crc_ctx_table(const crc_ctx *ctx, const char *name, uint64_t *h_out, int ca
 /* Tuning switches of tools/ and the tests (none is needed for normal use).  The engine reads its environment (CRC_MFMA_VARIANT, CRC_CONV1_PASS_BYTES, ...)
  * exactly
  * once, inside crc_ctx_create; this call changes one switch of a context nobody is launching on: "mfma_variant", "mfma_order", "mfma_ring", "conv1_waves",
- * "conv1_narrow" (0: a one-channel convolution with 17-20 filters runs its second filter group like a full one), "conv1_pass_bytes", "limb_pack_group", "mac2_cfg", "mac_order", "mac_regstage", "ntt_inv61_loose", "ntt_split", "mfma_min_steps", "f64_radix",
+ * "conv1_narrow" (0: a one-channel convolution with 17-20 filters runs its second filter group like a full one), "conv1_pass_bytes", "limb_pack_group", "mac2_cfg", "mac_order", "mac_regstage", "ntt_inv61_loose", "ntt_split", "mfma_min_steps", "scalar_mac" (crc_plan_mac_scalar), "f64_radix",
  * "relin_mac_ct", "poly_tail" (crc_poly2_relin_forms),
  * "relin_path" (1: key switching over the coefficient moduli, as the reference does it, instead of over two fp64 primes), "sq_path" (1: the square's auxiliary
  * base is SEAL's 61-bit
@@ -278,6 +286,22 @@ int    crc_limb_pack_weights_tile(crc_ctx *ctx, const uint64_t *d_w_tile_ntt, in
  *                       it, the layer in front takes the enlarged window on the kernel family it runs on, and the pair costs less that way on B images per launch
  *                       (same units; the one-channel kernel's two forms are priced at the K they pay for).  Tuning key hoist_pool = 0 / CRC_HOIST_POOL=0: always no */
 int    crc_plan_mac(const crc_ctx *ctx, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int B, int matrix_cores, int *w_form);
+/* Scalar form (CRC_NTTLS), for networks under slot batching:
+ *   crc_scalar_weights_bytes   size of the packed weights (crc_limb_weights_bytes / n)
+ *   crc_scalar_supported       pure host query, 0 / 1: can crc_conv2d_forms run the layer with w_form = CRC_NTTLS on B images per slot?  The limb form's limits (moduli
+ *                              of at most 55 bits, at most 18 000 terms, at most 8 moduli) and the kernel's 32-bit offsets: a modulus' limb tensor and its result of n B
+ *                              images each below 4 GiB.  Where it says 0 the forms call returns CRC_ERR_UNSUPPORTED and launches nothing
+ *   crc_scalar_pack_weights    d_w: canonical NTT-form weight rows [nf][zd][xf][yf][k][n] (w_stride = n) or one residue per modulus [nf][zd][xf][yf][k] (w_stride = 1)
+ *                              -> d_ws.  Synchronises once (a start-up path).  A row whose n words are not all equal is no constant polynomial: *constant = 0 and
+ *                              CRC_ERR_INVALID_ARGUMENT, d_ws is not written; *constant = 1 in every other case, refusals of the arguments included
+ *   crc_plan_mac_scalar        crc_plan_mac for a layer of a slot-batched network: CRC_NTTLS where crc_scalar_supported and zd >= 2, else crc_plan_mac's answer
+ *                              with the matrix cores on (one-channel convolutions keep CRC_NTTL1, moduli above 55 bits their kernels).  Tuning key scalar_mac /
+ *                              CRC_SCALAR_MAC (default 1: the form beat the row path on every layer measured, profiles/scalar_mac.md): 0 gives crc_plan_mac's
+ *                              answer everywhere */
+size_t crc_scalar_weights_bytes(const crc_ctx *ctx, int nf, int zd, int xf, int yf);
+int    crc_scalar_supported(const crc_ctx *ctx, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf);
+int    crc_scalar_pack_weights(crc_ctx *ctx, const uint64_t *d_w, int w_stride, int nf, int zd, int xf, int yf, void *d_ws, int *constant, void *stream);
+int    crc_plan_mac_scalar(const crc_ctx *ctx, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int B, int *w_form);
 int    crc_plan_fold_pool(const crc_ctx *ctx, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int pxs, int pys, int pxf, int pyf, int *fold);
 int    crc_plan_hoist_pool(const crc_ctx *ctx, int uzd, int uxd, int uyd, int uxs, int uys, int uxf, int uyf, int unf, int zd, int xd, int yd, int xs, int ys,
                            int xf, int yf, int nf, int pxs, int pys, int pxf, int pyf, int B, int matrix_cores, int *hoist);
