@@ -196,6 +196,14 @@ def load():
     L.crc_slots_decompose.argtypes = [VP, PU, SZ, CI, PI64, SZ, SZ]
     L.crc_slots_compose_dev.argtypes = [VP, VP, SZ, CI, SZ, SZ, VP, VP]
     L.crc_slots_decompose_dev.argtypes = [VP, VP, SZ, CI, VP, SZ, SZ, VP]
+    L.crc_slots_rescale.argtypes = [VP, PU, SZ, u64, PU]
+    L.crc_slots_rescale_dev.argtypes = [VP, VP, SZ, u64, VP, VP]
+    L.crc_slots_refresh_dev_work_bytes.restype = SZ; L.crc_slots_refresh_dev_work_bytes.argtypes = [VP, SZ, CI]
+    L.crc_slots_refresh_dev.argtypes = [VP, VP, VP, VP, SZ, CI, u64, u64, CI, VP, VP, VP]
+    L.crc_slots_refresh_dev_key.argtypes = [VP, VP, VP, VP, SZ, CI, u64, PB, u64, CI, VP, VP, VP]
+    L.crc_slots_refresh_sym_dev_work_bytes.restype = SZ; L.crc_slots_refresh_sym_dev_work_bytes.argtypes = [VP, SZ, CI]
+    L.crc_slots_refresh_sym_dev.argtypes = [VP, VP, VP, SZ, CI, u64, u64, CI, VP, VP, VP]
+    L.crc_slots_refresh_sym_dev_key.argtypes = [VP, VP, VP, SZ, CI, u64, PB, u64, CI, VP, VP, VP]
     L.crc_encode_dev_f32.argtypes = [VP, VP, SZ, VP, VP]
     L.crc_encode_dev_f64.argtypes = [VP, VP, SZ, VP, VP]
     L.crc_refresh_dev_work_bytes.restype = SZ; L.crc_refresh_dev_work_bytes.argtypes = [VP, SZ, CI]
@@ -423,6 +431,40 @@ class Engine:
     def slots_decompose_dev(self, d_plain, count, slots, d_values, item_stride, slot_stride):
         _chk(self.L.crc_slots_decompose_dev(self.c, self.p(d_plain), count, slots, self.p(d_values), item_stride, slot_stride, self.stream),
              "crc_slots_decompose_dev")
+
+    def slots_rescale(self, plains, divisor):
+        """host twin: every slot of plaintexts [count][n] -> floor(slot / divisor + 1/2), recomposed"""
+        plains = np.ascontiguousarray(plains, dtype=np.uint64).reshape(-1, self.n)
+        out = np.zeros_like(plains)
+        _chk(self.L.crc_slots_rescale(self.c, _pu(plains), plains.shape[0], int(divisor), _pu(out)), "crc_slots_rescale")
+        return out
+
+    def slots_rescale_dev(self, d_plain_in, count, divisor, d_plain_out):
+        _chk(self.L.crc_slots_rescale_dev(self.c, self.p(d_plain_in), count, int(divisor), self.p(d_plain_out), self.stream), "crc_slots_rescale_dev")
+
+    def slots_refresh_dev_work_bytes(self, count, in_form=COEFF):
+        return self.L.crc_slots_refresh_dev_work_bytes(self.c, count, in_form)
+
+    def slots_refresh_dev(self, d_sk, d_pk, d_ct_in, count, divisor, seed, d_ct_out, d_work, in_form=COEFF, out_form=COEFF, key=None, stream_base=0):
+        """decrypt -> rescale every slot by `divisor` -> encrypt under the public key: crc_decrypt_dev, crc_slots_rescale_dev, crc_encrypt_dev[_key]_forms as one call"""
+        if key is None:
+            _chk(self.L.crc_slots_refresh_dev(self.c, self.p(d_sk), self.p(d_pk), self.p(d_ct_in), count, in_form, int(divisor), seed, out_form, self.p(d_ct_out),
+                                              self.p(d_work), self.stream), "crc_slots_refresh_dev")
+        else:
+            _chk(self.L.crc_slots_refresh_dev_key(self.c, self.p(d_sk), self.p(d_pk), self.p(d_ct_in), count, in_form, int(divisor), self._key(key), stream_base,
+                                                  out_form, self.p(d_ct_out), self.p(d_work), self.stream), "crc_slots_refresh_dev_key")
+
+    def slots_refresh_sym_dev_work_bytes(self, count, in_form=COEFF):
+        return self.L.crc_slots_refresh_sym_dev_work_bytes(self.c, count, in_form)
+
+    def slots_refresh_sym_dev(self, d_sk, d_ct_in, count, divisor, seed, d_ct_out, d_work, in_form=COEFF, out_form=COEFF, key=None, stream_base=0):
+        """the same under the secret key (crc_encrypt_sym_dev[_key]_forms)"""
+        if key is None:
+            _chk(self.L.crc_slots_refresh_sym_dev(self.c, self.p(d_sk), self.p(d_ct_in), count, in_form, int(divisor), seed, out_form, self.p(d_ct_out),
+                                                  self.p(d_work), self.stream), "crc_slots_refresh_sym_dev")
+        else:
+            _chk(self.L.crc_slots_refresh_sym_dev_key(self.c, self.p(d_sk), self.p(d_ct_in), count, in_form, int(divisor), self._key(key), stream_base, out_form,
+                                                      self.p(d_ct_out), self.p(d_work), self.stream), "crc_slots_refresh_sym_dev_key")
 
     def keygen(self, seed):
         sk = np.zeros((self.k, self.n), dtype=np.uint64); pk = np.zeros((2, self.k, self.n), dtype=np.uint64)

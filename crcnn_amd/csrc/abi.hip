@@ -670,6 +670,25 @@ extern "C" int crc_slots_decompose_dev(crc_ctx *c, const uint64_t *d_plain, size
     if (((uintptr_t)d_plain & 15) || ((uintptr_t)d_values & 7)) return CRC_ERR_INVALID_ARGUMENT;
     return k_slots_decompose(c, d_plain, count, slots, (long long *)d_values, item_stride, slot_stride, S(stream));
 }
+static int slots_rescale_args_ok(const crc_ctx *c, const void *in, const void *out, uint64_t divisor)
+{
+    if (!crc_slots_supported(c)) return CRC_ERR_PARAMETERS;
+    if (!in || !out || divisor < 1 || divisor > ((uint64_t)1 << 62)) return CRC_ERR_INVALID_ARGUMENT;
+    return CRC_OK;
+}
+extern "C" int crc_slots_rescale(crc_ctx *c, const uint64_t *h_plain_in, size_t count, uint64_t divisor, uint64_t *h_plain_out)
+{
+    if (!c) return CRC_ERR_INVALID_ARGUMENT;
+    RUN(slots_rescale_args_ok(c, h_plain_in, h_plain_out, divisor));
+    return k_slots_rescale_host(c, h_plain_in, count, divisor, h_plain_out);
+}
+extern "C" int crc_slots_rescale_dev(crc_ctx *c, const uint64_t *d_plain_in, size_t count, uint64_t divisor, uint64_t *d_plain_out, void *stream)
+{
+    CHECK_CTX(c);
+    RUN(slots_rescale_args_ok(c, d_plain_in, d_plain_out, divisor));
+    if (((uintptr_t)d_plain_in & 15) || ((uintptr_t)d_plain_out & 15)) return CRC_ERR_INVALID_ARGUMENT;
+    return k_slots_rescale(c, d_plain_in, count, divisor, d_plain_out, S(stream));
+}
 extern "C" int crc_decode_dev(crc_ctx *c, const uint64_t *d_plain, size_t count, double *d_out, void *stream)
 {
     CHECK_CTX(c); if (!d_plain || !d_out) return CRC_ERR_INVALID_ARGUMENT;
@@ -762,6 +781,63 @@ extern "C" int crc_refresh_sym_dev_key(crc_ctx *c, const uint64_t *d_sk, const u
     if (!d_sk || !d_ct_in || !d_ct_out || !d_work || !key || !ct_form_ok(in_form) || !ct_form_ok(out_form)) return CRC_ERR_INVALID_ARGUMENT;
     CHECK_CTX(c);
     return refresh_impl(c, d_sk, nullptr, d_ct_in, count, in_form, chacha_load_key(key), stream_base, out_form, d_ct_out, d_values_out, d_work, S(stream));
+}
+// ---- the refresh of a slot-batched tensor: crc_decrypt_dev, the rescale kernel in place on the plaintexts, the matching encryptor ----
+// Work: [plaintexts [count][n]][the decryptor's rows, then the encryptor's (sym: the secret-key encryptor's) samples]
+struct SlotsRefreshWork { u64 *plain, *w; };
+static SlotsRefreshWork slots_refresh_layout(const crc_ctx *c, size_t count, int in_form, bool sym, WorkArena &a)
+{
+    const size_t dec = k_decrypt_work_words(c, count, 2, in_form == CRC_NTT), enc = sym ? k_encrypt_sym_work_words(c, count) : k_encrypt_work_words(c, count);
+    SlotsRefreshWork L{};
+    L.plain = a.take<u64>(count * (size_t)c->n);
+    L.w = a.take<u64>(dec > enc ? dec : enc);
+    return L;
+}
+static size_t slots_refresh_bytes(const crc_ctx *c, size_t count, int in_form, bool sym)
+{
+    if (!c || !ct_form_ok(in_form)) return 0;
+    WorkArena a;
+    slots_refresh_layout(c, count, in_form, sym, a);
+    return a.bytes();
+}
+// sym: encrypt under the secret key (d_pk unused)
+static int slots_refresh_impl(crc_ctx *c, bool sym, const u64 *d_sk, const u64 *d_pk, const u64 *d_in, size_t count, int in_form, u64 divisor, const ChaChaKey &key,
+                              u64 stream_base, int out_form, u64 *d_out, void *d_work, hipStream_t st)
+{
+    RUN(slots_rescale_args_ok(c, d_in, d_out, divisor));
+    if (!d_sk || (!sym && !d_pk) || !d_work || !ct_form_ok(in_form) || !ct_form_ok(out_form)) return CRC_ERR_INVALID_ARGUMENT;
+    WorkArena a(d_work);
+    const SlotsRefreshWork L = slots_refresh_layout(c, count, in_form, sym, a);
+    RUN(k_decrypt(c, d_sk, d_in, count, 2, in_form == CRC_NTT, L.plain, L.w, st));
+    RUN(k_slots_rescale(c, L.plain, count, divisor, L.plain, st));
+    if (sym) return k_encrypt_sym(c, d_sk, L.plain, count, key, stream_base, d_out, L.w, st, out_form == CRC_NTT, false);
+    return k_encrypt(c, d_pk, L.plain, count, key, stream_base, d_out, L.w, st, out_form == CRC_NTT);
+}
+extern "C" size_t crc_slots_refresh_dev_work_bytes(const crc_ctx *c, size_t count, int in_form) { return slots_refresh_bytes(c, count, in_form, false); }
+extern "C" size_t crc_slots_refresh_sym_dev_work_bytes(const crc_ctx *c, size_t count, int in_form) { return slots_refresh_bytes(c, count, in_form, true); }
+extern "C" int crc_slots_refresh_dev(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_pk, const uint64_t *d_ct_in, size_t count, int in_form, uint64_t divisor,
+                                     uint64_t seed, int out_form, uint64_t *d_ct_out, void *d_work, void *stream)
+{
+    CHECK_CTX(c);
+    return slots_refresh_impl(c, false, d_sk, d_pk, d_ct_in, count, in_form, divisor, chacha_seed_key(seed), 0, out_form, d_ct_out, d_work, S(stream));
+}
+extern "C" int crc_slots_refresh_dev_key(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_pk, const uint64_t *d_ct_in, size_t count, int in_form,
+                                         uint64_t divisor, const uint8_t *key, uint64_t stream_base, int out_form, uint64_t *d_ct_out, void *d_work, void *stream)
+{
+    CHECK_CTX(c); if (!key) return crc_slots_supported(c) ? CRC_ERR_INVALID_ARGUMENT : CRC_ERR_PARAMETERS;
+    return slots_refresh_impl(c, false, d_sk, d_pk, d_ct_in, count, in_form, divisor, chacha_load_key(key), stream_base, out_form, d_ct_out, d_work, S(stream));
+}
+extern "C" int crc_slots_refresh_sym_dev(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_ct_in, size_t count, int in_form, uint64_t divisor, uint64_t seed,
+                                         int out_form, uint64_t *d_ct_out, void *d_work, void *stream)
+{
+    CHECK_CTX(c);
+    return slots_refresh_impl(c, true, d_sk, nullptr, d_ct_in, count, in_form, divisor, chacha_seed_key(seed), 0, out_form, d_ct_out, d_work, S(stream));
+}
+extern "C" int crc_slots_refresh_sym_dev_key(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_ct_in, size_t count, int in_form, uint64_t divisor,
+                                             const uint8_t *key, uint64_t stream_base, int out_form, uint64_t *d_ct_out, void *d_work, void *stream)
+{
+    CHECK_CTX(c); if (!key) return crc_slots_supported(c) ? CRC_ERR_INVALID_ARGUMENT : CRC_ERR_PARAMETERS;
+    return slots_refresh_impl(c, true, d_sk, nullptr, d_ct_in, count, in_form, divisor, chacha_load_key(key), stream_base, out_form, d_ct_out, d_work, S(stream));
 }
 // ---- seeded secret-key ciphertexts: the packed c0 rows and a public seed -> ordinary ciphertexts (kernels_client.hip: k_seeded_expand) ----
 extern "C" int crc_seeded_expand_dev(crc_ctx *c, const uint64_t *d_c0, size_t count, const uint8_t *seed, uint64_t stream_base, int out_form, uint64_t *d_ct,

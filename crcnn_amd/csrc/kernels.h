@@ -97,6 +97,9 @@ int k_slots_compose(crc_ctx *c, const long long *d_values, size_t count, int slo
 int k_slots_decompose(crc_ctx *c, const u64 *d_plain, size_t count, int slots, long long *d_values, size_t item_stride, size_t slot_stride, hipStream_t st);
 int k_slots_compose_host(crc_ctx *c, const long long *values, size_t count, int slots, size_t item_stride, size_t slot_stride, u64 *plain);
 int k_slots_decompose_host(crc_ctx *c, const u64 *plain, size_t count, int slots, long long *values, size_t item_stride, size_t slot_stride);
+// every slot of a plaintext -> floor(slot / divisor + 1/2), 1 <= divisor <= 2^62 (the caller checks); in == out allowed
+int k_slots_rescale(crc_ctx *c, const u64 *d_in, size_t count, u64 divisor, u64 *d_out, hipStream_t st);
+int k_slots_rescale_host(crc_ctx *c, const u64 *plain_in, size_t count, u64 divisor, u64 *plain_out);
 
 // kernels_mfma.hip: conv / dense multiply-accumulate as an int8 limb GEMM on the matrix cores (operand form CRC_NTTL)
 bool   k_limb_supported(const crc_ctx *c, int T);

@@ -23,8 +23,17 @@ __global__ void __launch_bounds__(1024) slots_decompose_kernel(SlotArgs a)
     extern __shared__ u64 sm[];
     slots_decompose_body<LAZY>(a, sm);
 }
+template <bool LAZY>
+__global__ void __launch_bounds__(1024) slots_rescale_kernel(SlotRescaleArgs a)
+{
+    extern __shared__ u64 sm[];
+    slots_rescale_body<LAZY>(a, sm);
+}
 
-static int slots_launch(crc_ctx *c, bool compose, SlotArgs &a, hipStream_t st)
+// The launch rules of the three slot kernels in one place: t's tables, one workgroup of max(64, n / 8) threads per row with the row as its LDS image, the rows in
+// XCD groups.  `tables` puts the table pointers the kernel reads into the argument block; the ring's fields and the kernel's variant are chosen here.
+template <class Args, class Tables>
+static int slots_launch(crc_ctx *c, void (*lazy)(Args), void (*strict)(Args), Args &a, Tables tables, hipStream_t st)
 {
     const SlotTables *T;
     { const int rc = crc_slots_tables(c, &T); if (rc) return rc; }
@@ -33,11 +42,10 @@ static int slots_launch(crc_ctx *c, bool compose, SlotArgs &a, hipStream_t st)
     if (lds > 128 * 1024) return CRC_ERR_UNSUPPORTED;                 // (n = 32768: the row does not fit the LDS; the host twins serve it)
     const size_t groups = (a.count + CRC_SLOT_GROUP - 1) / CRC_SLOT_GROUP;
     if ((groups + 7) / 8 * 8 * CRC_SLOT_GROUP > 0x7fffffffULL) return CRC_ERR_INVALID_ARGUMENT;
-    a.W = compose ? T->d_inv : T->d_fwd; a.idx = T->d_idx;
+    tables(a, *T);
     a.n = c->n; a.logn = c->logn; a.t = c->t; a.one_s = T->one_s;
     int nt = c->n / 8; if (nt < 64) nt = 64; if (nt > 1024) nt = 1024;
-    auto kern = compose ? (T->lazy ? slots_compose_kernel<true> : slots_compose_kernel<false>)
-                        : (T->lazy ? slots_decompose_kernel<true> : slots_decompose_kernel<false>);
+    auto kern = T->lazy ? lazy : strict;
     { const int rc = crc_ctx_ensure_lds(c, (const void *)kern, lds); if (rc) return rc; }
     hipLaunchKernelGGL(kern, dim3(xcd_grid(groups, CRC_SLOT_GROUP)), dim3(nt), lds, st, a);
     HIPCHK(hipGetLastError());
@@ -48,13 +56,23 @@ int k_slots_compose(crc_ctx *c, const long long *d_values, size_t count, int slo
 {
     SlotArgs a{};
     a.vals_in = d_values; a.plain_out = d_plain; a.count = count; a.slots = slots; a.item_stride = item_stride; a.slot_stride = slot_stride;
-    return slots_launch(c, true, a, st);
+    return slots_launch(c, slots_compose_kernel<true>, slots_compose_kernel<false>, a, [](SlotArgs &a, const SlotTables &T) { a.W = T.d_inv; a.idx = T.d_idx; }, st);
 }
 int k_slots_decompose(crc_ctx *c, const u64 *d_plain, size_t count, int slots, long long *d_values, size_t item_stride, size_t slot_stride, hipStream_t st)
 {
     SlotArgs a{};
     a.plain_in = d_plain; a.vals_out = d_values; a.count = count; a.slots = slots; a.item_stride = item_stride; a.slot_stride = slot_stride;
-    return slots_launch(c, false, a, st);
+    return slots_launch(c, slots_decompose_kernel<true>, slots_decompose_kernel<false>, a, [](SlotArgs &a, const SlotTables &T) { a.W = T.d_fwd; a.idx = T.d_idx; }, st);
+}
+
+// every slot of count plaintexts divided by `divisor`, rounded to nearest (slots_device.h); d_in == d_out allowed
+int k_slots_rescale(crc_ctx *c, const u64 *d_in, size_t count, u64 divisor, u64 *d_out, hipStream_t st)
+{
+    SlotRescaleArgs a{};
+    a.plain_in = d_in; a.plain_out = d_out; a.count = count;
+    a.D = divisor; a.recip = divisor == 1 ? ~(u64)0 : (u64)(((unsigned __int128)1 << 64) / divisor);
+    a.hpos = divisor >> 1; a.hneg = (divisor - 1) >> 1;
+    return slots_launch(c, slots_rescale_kernel<true>, slots_rescale_kernel<false>, a, [](SlotRescaleArgs &a, const SlotTables &T) { a.Wf = T.d_fwd; a.Wi = T.d_inv; }, st);
 }
 
 // ---- host twins (any context, device = -1 included): the reference transforms of ctx.cpp on the same tables ----------------------------------------------
@@ -84,6 +102,28 @@ int k_slots_decompose_host(crc_ctx *c, const u64 *plain, size_t count, int slots
             for (int i = 0; i < n; i++) row[i] = plain[m * (size_t)n + i] % t;
             h_ntt_fwd(T->T, row.data(), n);
             for (int i = 0; i < slots; i++) { const u64 r = row[T->idx[i]]; values[m * item_stride + (size_t)i * slot_stride] = r > half ? (long long)r - (long long)t : (long long)r; }
+        }
+    });
+    return CRC_OK;
+}
+int k_slots_rescale_host(crc_ctx *c, const u64 *plain_in, size_t count, u64 divisor, u64 *plain_out)
+{
+    const SlotTables *T;
+    { const int rc = crc_slots_tables(c, &T); if (rc) return rc; }
+    const int n = c->n; const u64 t = c->t, half = (t - 1) >> 1;
+    const __int128 D = (__int128)divisor, h = (__int128)(divisor >> 1);
+    crc_host::parallel_for(count, 4, [&](size_t b, size_t e) {
+        std::vector<u64> row((size_t)n);
+        for (size_t m = b; m < e; m++) {
+            for (int i = 0; i < n; i++) row[i] = plain_in[m * (size_t)n + i] % t;
+            h_ntt_fwd(T->T, row.data(), n);
+            for (int i = 0; i < n; i++) {
+                const __int128 num = (row[i] > half ? (__int128)row[i] - (__int128)t : (__int128)row[i]) + h;
+                __int128 q = num / D; if (num % D < 0) q--;                    // floor division
+                row[i] = (u64)(q < 0 ? q + (__int128)t : q);                   // |q| <= (t - 1) / 2
+            }
+            h_ntt_inv(T->T, row.data(), n);
+            for (int i = 0; i < n; i++) plain_out[m * (size_t)n + i] = row[i];
         }
     });
     return CRC_OK;

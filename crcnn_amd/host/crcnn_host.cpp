@@ -716,6 +716,50 @@ ciphertext3D refreshImages(const ciphertext3D &t, int out_form, vector<float> *v
     return out;
 }
 
+// The refresh of a slot-batched tensor (crc_slots_refresh_dev: decrypt, every slot divided by `divisor` and rounded, encrypt), on the launch stream, in passes
+// of bounded size on the layers' scratch area; seed / key and counter exactly as refreshImages draws them
+ciphertext3D rescaleSlots(const ciphertext3D &t, uint64_t divisor, int out_form, bool symmetric)
+{
+    if (!t.buf) throw invalid_argument("rescaleSlots: empty tensor");
+    if ((t.form != CRC_COEFF && t.form != CRC_NTT) || (out_form != CRC_COEFF && out_form != CRC_NTT))
+        throw invalid_argument("rescaleSlots: ciphertext forms only (CRC_COEFF / CRC_NTT)");
+    if (divisor < 1 || divisor > ((uint64_t)1 << 62)) throw invalid_argument("rescaleSlots: the divisor must be in 1..2^62");
+    if (!crc_slots_supported(ctx())) throw invalid_argument("rescaleSlots: the plain modulus must be a prime that is 1 mod 2n and none of the engine's moduli");
+    const uint64_t *d_sk = deviceKey(g_d_sk, g_d_sk_fp, secret_key, "secret key");
+    const uint64_t *d_pk = symmetric ? nullptr : deviceKey(g_d_pk, g_d_pk_fp, public_key, "public key");
+    auto work_bytes = [&](size_t c) { return symmetric ? crc_slots_refresh_sym_dev_work_bytes(ctx(), c, t.form) : crc_slots_refresh_dev_work_bytes(ctx(), c, t.form); };
+    ciphertext3D out(t.B, t.zd, t.xd, t.yd, out_form);
+    const size_t cnt = t.count(), one = work_bytes(1);
+    size_t pass = ((size_t)4 << 30) / (one ? one : 1);
+    if (pass < 1024) pass = 1024;
+    if (pass > cnt) pass = cnt;
+    ensure(g_scratch, work_bytes(pass));
+    for (size_t o = 0; o < cnt; o += pass) {
+        const size_t c = min(pass, cnt - o);
+        const uint64_t *in = (const uint64_t *)((const char *)t.data() + o * ctBytes());
+        uint64_t *dst = (uint64_t *)((char *)out.data() + o * ctBytes());
+        const uint64_t seed = g_det_seed + 1000003 * (g_enc_counter + 1);
+        if (symmetric && g_det)
+            chk(crc_slots_refresh_sym_dev(ctx(), d_sk, in, c, t.form, divisor, seed, out_form, dst, g_scratch->ptr, stream()), "crc_slots_refresh_sym_dev");
+        else if (symmetric)
+            chk(crc_slots_refresh_sym_dev_key(ctx(), d_sk, in, c, t.form, divisor, g_master_key, g_enc_counter, out_form, dst, g_scratch->ptr, stream()),
+                "crc_slots_refresh_sym_dev_key");
+        else if (g_det)
+            chk(crc_slots_refresh_dev(ctx(), d_sk, d_pk, in, c, t.form, divisor, seed, out_form, dst, g_scratch->ptr, stream()), "crc_slots_refresh_dev");
+        else
+            chk(crc_slots_refresh_dev_key(ctx(), d_sk, d_pk, in, c, t.form, divisor, g_master_key, g_enc_counter, out_form, dst, g_scratch->ptr, stream()),
+                "crc_slots_refresh_dev_key");
+        g_enc_counter += c;
+    }
+    return out;
+}
+ciphertext3D SlotRescaleLayer::forward(ciphertext3D input)
+{
+    if (out_form != CRC_COEFF && out_form != CRC_NTT) throw invalid_argument("SlotRescaleLayer: ciphertext forms only (CRC_COEFF / CRC_NTT)");
+    return rescaleSlots(input, divisor, out_form, symmetric);
+}
+void SlotRescaleLayer::printLayerStructure() { cerr << "SlotRescaleLayer " << name << " :bits " << bits << " divisor " << divisor << endl; }
+
 // Decryptor::invariant_noise_budget of a whole tensor on the launch stream (crc_noise_budget_dev), in passes of bounded work that share the layers' scratch
 // area.  The result buffer: one {min, first index} pair per pass, then the budgets -- so the pairs and the first ciphertext's budget are one small copy
 struct DeviceBudgets { shared_ptr<DeviceBuffer> buf; size_t passes = 0, pass = 0, count = 0;
@@ -1899,7 +1943,7 @@ NetworkDescription NetworkDescription::parse(const string &text, const string &h
             continue;
         }
         const bool windowed = kind == "conv" || kind == "pool" || kind == "avgpool";
-        if (!windowed && kind != "bn" && kind != "square" && kind != "fc" && kind != "pad" && kind != "poly" && kind != "poly3") descError(ln, "unknown layer kind '" + kind + "'");
+        if (!windowed && kind != "bn" && kind != "square" && kind != "fc" && kind != "pad" && kind != "poly" && kind != "poly3" && kind != "rescale") descError(ln, "unknown layer kind '" + kind + "'");
         if (tok.size() < 2) descError(ln, kind + ": the layer name is missing");
         LayerSpec L;
         L.kind = kind; L.name = tok[1]; L.line = ln; L.zd = zd; L.xd = xd; L.yd = yd;
@@ -1947,6 +1991,11 @@ NetworkDescription NetworkDescription::parse(const string &text, const string &h
             if (rest.size() != 2) descError(ln, rest.size() > 2 ? "unknown token '" + rest[2] + "'" : string("pad: takes px py"));
             L.px = descInt(ln, rest[0], "pad"); L.py = descInt(ln, rest[1], "pad");
             L.zo = zd; L.xo = xd + 2 * L.px; L.yo = yd + 2 * L.py;
+        } else if (kind == "rescale") {
+            if (rest.size() != 1) descError(ln, rest.size() > 1 ? "unknown token '" + rest[1] + "'" : string("rescale: takes the scale's bit count"));
+            L.bits = descInt(ln, rest[0], "rescale");
+            if (L.bits > 30) descError(ln, "rescale: the bit count must be in 0..30");
+            L.zo = zd; L.xo = xd; L.yo = yd;
         } else if (kind == "poly") {
             if (rest.size() != 3) descError(ln, rest.size() > 3 ? "unknown token '" + rest[3] + "'" : string("poly: takes c2 c1 c0"));
             L.c2 = descFloat(ln, rest[0], "c2"); L.c1 = descFloat(ln, rest[1], "c1"); L.c0 = descFloat(ln, rest[2], "c0");
@@ -1994,6 +2043,7 @@ string NetworkDescription::str() const
         else if (L.kind == "pool" || L.kind == "avgpool") o << " stride " << L.xs << " " << L.ys << " window " << L.xf << " " << L.yf;
         else if (L.kind == "fc") o << " " << L.out_dim;
         else if (L.kind == "pad") o << " " << L.px << " " << L.py;
+        else if (L.kind == "rescale") o << " " << L.bits;
         else if (L.kind == "poly") o << " " << descFloatStr(L.c2) << " " << descFloatStr(L.c1) << " " << descFloatStr(L.c0);
         else if (L.kind == "poly3") o << " " << descFloatStr(L.c3) << " " << descFloatStr(L.c2) << " " << descFloatStr(L.c1) << " " << descFloatStr(L.c0);
         if (L.threads >= 0 && L.threads != 1) o << " threads " << L.threads;          // (1 is what a layer without the token is built with)
@@ -2020,6 +2070,7 @@ string Network::describe() const
         else if (auto p3 = dynamic_pointer_cast<Poly3Layer>(l)) { L.kind = "poly3"; L.c3 = p3->c3; L.c2 = p3->c2; L.c1 = p3->c1; L.c0 = p3->c0;
             L.threads = p3->th_count; }
         else if (dynamic_pointer_cast<BatchNormLayer>(l)) L.kind = "bn";
+        else if (auto rs = dynamic_pointer_cast<SlotRescaleLayer>(l)) { L.kind = "rescale"; L.bits = rs->bits; }
         else throw logic_error("Network::describe: layer " + l->name + " has no description");
         d.layers.push_back(L);
     }
@@ -2131,6 +2182,11 @@ vector<double> slotScales(const NetworkDescription &d, int input_bits, int weigh
         else if (L.kind == "square") s = scaleTimes(L.line, s, s);
         else if (L.kind == "poly") s = scaleTimes(L.line, scaleTimes(L.line, s, s), W);
         else if (L.kind == "poly3") s = scaleTimes(L.line, scaleTimes(L.line, scaleTimes(L.line, s, s), s), W);
+        else if (L.kind == "rescale") {                     // the client divides every slot by sigma / 2^bits: an integer >= 1, or the line is refused
+            const double target = ldexp(1.0, L.bits);
+            if (s < target || fmod(s, target) != 0) descError(L.line, "rescale: the scale 2^" + to_string(L.bits) + " does not divide the scale in front of it");
+            s = target;
+        }
     }
     out.push_back(s);
     return out;
@@ -2157,7 +2213,13 @@ Network CnnBuilder::buildNetworkFromDescription(const string &path_or_text, stri
             if (L.kind == "bn") { g_enc_scale[0] = s; g_enc_scale[1] = W; }
             else { g_enc_scale[0] = W; g_enc_scale[1] = s * W; }
         }
-        if (L.kind == "conv") add(buildConvolutionalLayer(L.name, L.xd, L.yd, L.zd, L.xs, L.ys, L.xf, L.yf, L.nf, th, in));
+        if (L.kind == "rescale") {
+            if (!g_slot_on) descError(L.line, "rescale needs slot encoding (setSlotEncoding)");
+            SlotRescaleLayer *r = new SlotRescaleLayer(L.name, L.bits);
+            r->divisor = (uint64_t)(s / ldexp(1.0, L.bits));
+            add(r);
+        }
+        else if (L.kind == "conv") add(buildConvolutionalLayer(L.name, L.xd, L.yd, L.zd, L.xs, L.ys, L.xf, L.yf, L.nf, th, in));
         else if (L.kind == "pool") add(buildPoolingLayer(L.name, L.xd, L.yd, L.zd, L.xs, L.ys, L.xf, L.yf));
         else if (L.kind == "avgpool") add(buildAvgPoolingLayer(L.name, L.xd, L.yd, L.zd, L.xs, L.ys, L.xf, L.yf));
         else if (L.kind == "bn") add(buildBatchNormLayer(L.name, L.zd, in));

@@ -112,6 +112,10 @@ int minNoiseBudget(const ciphertext3D &t, size_t *where = nullptr);
 // (crc_refresh_sym_dev: c1 uniform in the NTT domain, one forward transform per modulus instead of three, fresh noise e alone) -- another ciphertext
 // distribution, the same plaintexts and floats; only the cached device copy of the secret key is needed
 ciphertext3D refreshImages(const ciphertext3D &encrypted, int out_form = CRC_COEFF, std::vector<float> *values = nullptr, bool symmetric = false);
+// the refresh of a SLOT-BATCHED tensor: decrypt, every slot of every plaintext divided by `divisor` (1..2^62) and rounded to nearest, ties towards +infinity
+// (crc_slots_rescale_dev), encrypt under fresh randomness -- crc_slots_refresh[_sym]_dev in bounded passes on the shared scratch, seed / key and counter as
+// refreshImages.  CRC_COEFF / CRC_NTT in and out; std::invalid_argument for other forms, a divisor out of range or a context without slots
+ciphertext3D rescaleSlots(const ciphertext3D &encrypted, uint64_t divisor, int out_form, bool symmetric = false);
 // encryptImage's sibling for a client that holds the secret key: the pixels of one image ([zd][xd][yd]) or of a batch ([B][zd][xd][yd] floats, B = size /
 // (zd xd yd)) encrypted under the secret key on the device (crc_encrypt_sym_dev); same keystream discipline as encryptImage
 ciphertext3D encryptImageSymmetric(const std::vector<float> &pixels, int zd, int xd, int yd, int out_form = CRC_COEFF);
@@ -318,6 +322,21 @@ class PaddingLayer : public Layer {
 public:
     int xd, yd, zd, px, py, xo, yo, zo;
     PaddingLayer(std::string name, int xd, int yd, int zd, int px, int py);
+    ciphertext3D forward(ciphertext3D input) override;
+    void savePlaintextParameters(std::ostream *) override {}
+    void loadPlaintextParameters(std::istream *) override {}
+    void printLayerStructure() override;
+};
+
+// `rescale NAME BITS` of a slot-batched network: in front of the next layer the client re-encodes every slot to the scale 2^BITS -- decrypt, every slot divided
+// by `divisor` = sigma / 2^BITS and rounded to nearest, encrypt (rescaleSlots).  Takes CRC_COEFF / CRC_NTT and writes out_form CRC_COEFF / CRC_NTT
+// (std::invalid_argument otherwise); no plaintext parameters.  The divisor is set by CnnBuilder::buildNetworkFromDescription from the scale ledger
+class SlotRescaleLayer : public Layer {
+public:
+    int bits;
+    uint64_t divisor = 1;
+    bool symmetric = false;                                 // re-encrypt under the secret key (crc_slots_refresh_sym_dev)
+    SlotRescaleLayer(std::string name, int bits) : Layer(name), bits(bits) {}
     ciphertext3D forward(ciphertext3D input) override;
     void savePlaintextParameters(std::ostream *) override {}
     void loadPlaintextParameters(std::istream *) override {}
@@ -554,6 +573,7 @@ public:
 //   fc NAME out_dim      pad NAME px py      refresh (sets layer_before_reenc to the next layer; at most one)
 //   poly NAME c2 c1 c0   (c2 x^2 + c1 x + c0: decimal numbers, read as double and rounded to float32; c2 != 0, all finite; written back as %.9g)
 //   poly3 NAME c3 c2 c1 c0   (c3 x^3 + c2 x^2 + c1 x + c0, two key switches and depth 2; the same number rules, c3 != 0)
+//   rescale NAME BITS   (slot encoding only: the client re-encodes every slot to the scale 2^BITS in front of the next layer, BITS in 0..30; SlotRescaleLayer)
 // conv, fc, square, poly and poly3 lines may end in `threads N` (the th_count the reference's constructors take).  NAME is the HDF5 dataset prefix.
 // Every error is a std::invalid_argument whose message starts with "line N:".
 struct LayerSpec {
@@ -565,6 +585,7 @@ struct LayerSpec {
     int px = 0, py = 0;                                     // pad
     float c2 = 1.0f, c1 = 0.0f, c0 = 0.0f;                  // poly
     float c3 = 1.0f;                                        // poly3 (with c2 c1 c0)
+    int bits = 0;                                           // rescale: the scale behind the layer is 2^bits
     int threads = -1;                                       // -1: no `threads` token (the layer is built with th_count 1)
     int zo = 0, xo = 0, yo = 0;                             // output shape
 };
@@ -588,8 +609,9 @@ struct NetworkDescription {
 //   square                                                                          -> sigma^2
 //   poly        c2 at W, c1 at W sigma, c0 at W sigma^2                             -> sigma^2 W
 //   poly3       c3 at W, c2 at W sigma, c1 at W sigma^2, c0 at W sigma^3            -> sigma^3 W
-// Every scale must be an integer below 2^62 that a double holds exactly; std::invalid_argument ("line N: ...") otherwise, and for a `refresh` (the slot-wise
-// re-encoding a refresh would need is not implemented).  Needs no context
+//   rescale     none: every slot divided by sigma / 2^BITS, an integer >= 1         -> 2^BITS
+// Every scale must be an integer below 2^62 that a double holds exactly; std::invalid_argument ("line N: ...") otherwise, for a `rescale` whose 2^BITS does not
+// divide sigma, and for a `refresh` (the fractional re-encoding of a refresh is not a slot-wise one: `rescale` is).  Needs no context
 std::vector<double> slotScales(const NetworkDescription &d, int input_bits, int weight_bits);
 
 // the description of "PlainModelTiny" | "ApproxPlainModel" | "PlainModelWoPad" (crcnn_amd/models/<name>.net, compiled in); nullptr for any other name

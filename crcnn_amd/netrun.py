@@ -135,7 +135,7 @@ def parse_description(text, dataset_count=None):
                 raise ValueError(f"line {ln}: a second refresh (line {pending_refresh or lines[refresh]} has the first)")
             pending_refresh = ln
             continue
-        if kind not in ("conv", "pool", "avgpool", "bn", "square", "fc", "pad", "poly", "poly3"):
+        if kind not in ("conv", "pool", "avgpool", "bn", "square", "fc", "pad", "poly", "poly3", "rescale"):
             raise ValueError(f"line {ln}: unknown layer kind {kind!r}")
         if len(tok) < 2:
             raise ValueError(f"line {ln}: {kind}: the layer name is missing")
@@ -185,6 +185,13 @@ def parse_description(text, dataset_count=None):
                 raise ValueError(f"line {ln}: " + (f"unknown token {rest[2]!r}" if len(rest) > 2 else "pad: takes px py"))
             px, py = ints(ln, rest, "pad")
             a = dict(zd=zd, xd=xd, yd=yd, px=px, py=py)
+        elif kind == "rescale":
+            # slot encoding only (the C++ Network): the client re-encodes every slot to the scale 2^bits in front of the next layer; the shape passes through
+            if len(rest) != 1:
+                raise ValueError(f"line {ln}: " + (f"unknown token {rest[1]!r}" if len(rest) > 1 else "rescale: takes the scale's bit count"))
+            a = dict(bits=ints(ln, rest, "rescale")[0])
+            if a["bits"] > 30:
+                raise ValueError(f"line {ln}: rescale: the bit count must be in 0..30")
         elif kind == "poly":
             if len(rest) != 3:
                 raise ValueError(f"line {ln}: " + (f"unknown token {rest[3]!r}" if len(rest) > 3 else "poly: takes c2 c1 c0"))
@@ -232,6 +239,8 @@ def format_description(desc):
             ln = f"fc {name} {a['out_dim']}"
         elif kind == "pad":
             ln = f"pad {name} {a['px']} {a['py']}"
+        elif kind == "rescale":
+            ln = f"rescale {name} {a['bits']}"
         elif kind == "poly":
             ln = "poly %s %.9g %.9g %.9g" % (name, a["c2"], a["c1"], a["c0"])      # (%.9g of a float32 reads back as the same float32)
         elif kind == "poly3":
@@ -296,6 +305,8 @@ class Network:
         self.E, self.model, self.topo = eng, model, load_description(model, h5_path)
         if self.topo.layer_before_reenc >= 0:
             raise ValueError("this driver has no client side: a description with a refresh point runs through the C++ Network (crcnn_amd/host)")
+        if any(kind == "rescale" for kind, _, _ in self.topo):
+            raise ValueError("this driver has no slot mode: a description with a rescale layer runs through the C++ Network (crcnn_amd/host) under slot encoding")
         # conv / dense layers with long reductions run on the matrix cores (operand form CRC_NTTL, kernels_mfma.hip) unless CRC_MFMA=0
         self.limb = (os.environ.get("CRC_MFMA", "1") != "0") if limb is None else limb
         self._limbed = False

@@ -546,6 +546,29 @@ int crc_slots_decompose(crc_ctx *ctx, const uint64_t *h_plain /*[count][n]*/, si
 int crc_slots_compose_dev(crc_ctx *ctx, const int64_t *d_values, size_t count, int slots, size_t item_stride, size_t slot_stride, uint64_t *d_plain, void *stream);
 int crc_slots_decompose_dev(crc_ctx *ctx, const uint64_t *d_plain, size_t count, int slots, int64_t *d_values, size_t item_stride, size_t slot_stride,
                             void *stream);
+/* rescale: every slot of a plaintext divided by an integer -- the re-encoding a slot-batched network needs where its scale has to come down.  For a row p (n
+ * words, each taken mod t) and 1 <= divisor D <= 2^62: v_i = the centred value of slot i (all n slots), v'_i = floor(v_i / D + 1/2) (floor division: ties go
+ * towards +infinity), result = the canonical coefficients of compose(v').  D = 1 returns p reduced mod t; zero slots stay zero; no slot count is needed, the
+ * operation is the same in every slot.  crc_slots_rescale: host memory, any context.  crc_slots_rescale_dev: device memory, asynchronous on `stream`, one kernel,
+ * one workgroup per row, no work buffer; both pointers 16-byte aligned, d_plain_out may be d_plain_in; n <= 16384 (CRC_ERR_UNSUPPORTED above); count = 0 is
+ * CRC_OK.  CRC_ERR_PARAMETERS on a context without slots comes first, then CRC_ERR_INVALID_ARGUMENT for D = 0, D > 2^62 or a null pointer.
+ *
+ * crc_slots_refresh_*: the client-side refresh of a slot-batched tensor -- crc_decrypt_dev (size 2), crc_slots_rescale_dev in place on the plaintexts,
+ * crc_encrypt_dev[_key]_forms (public key) / crc_encrypt_sym_dev[_key]_forms (secret key) -- as one call on `stream`; the result is by definition bit for bit
+ * what those three calls give with the same seed or key + stream_base.  in_form / out_form: CRC_COEFF or CRC_NTT; d_ct_out may be d_ct_in; d_work of
+ * crc_slots_refresh[_sym]_dev_work_bytes(ctx, count, in_form) bytes. */
+int crc_slots_rescale(crc_ctx *ctx, const uint64_t *h_plain_in /*[count][n]*/, size_t count, uint64_t divisor, uint64_t *h_plain_out /*[count][n]*/);
+int crc_slots_rescale_dev(crc_ctx *ctx, const uint64_t *d_plain_in, size_t count, uint64_t divisor, uint64_t *d_plain_out, void *stream);
+size_t crc_slots_refresh_dev_work_bytes(const crc_ctx *ctx, size_t count, int in_form);
+int crc_slots_refresh_dev(crc_ctx *ctx, const uint64_t *d_sk_ntt, const uint64_t *d_pk, const uint64_t *d_ct_in, size_t count, int in_form, uint64_t divisor,
+                          uint64_t seed, int out_form, uint64_t *d_ct_out, void *d_work, void *stream);
+int crc_slots_refresh_dev_key(crc_ctx *ctx, const uint64_t *d_sk_ntt, const uint64_t *d_pk, const uint64_t *d_ct_in, size_t count, int in_form, uint64_t divisor,
+                              const uint8_t *h_key /*[32]*/, uint64_t stream_base, int out_form, uint64_t *d_ct_out, void *d_work, void *stream);
+size_t crc_slots_refresh_sym_dev_work_bytes(const crc_ctx *ctx, size_t count, int in_form);
+int crc_slots_refresh_sym_dev(crc_ctx *ctx, const uint64_t *d_sk_ntt, const uint64_t *d_ct_in, size_t count, int in_form, uint64_t divisor, uint64_t seed,
+                              int out_form, uint64_t *d_ct_out, void *d_work, void *stream);
+int crc_slots_refresh_sym_dev_key(crc_ctx *ctx, const uint64_t *d_sk_ntt, const uint64_t *d_ct_in, size_t count, int in_form, uint64_t divisor,
+                                  const uint8_t *h_key /*[32]*/, uint64_t stream_base, int out_form, uint64_t *d_ct_out, void *d_work, void *stream);
 /* FractionalEncoder::decode / encode (encoder.cpp:1226-1270, 1013-1076; 64 integer + 32 fractional coefficients, base 3: CrCNN/src/globals.cpp:52) on the
  * device: the doubles crc_decode returns for d_plain [count][n], and the dense plaintexts [count][n] crc_encode_f32 / _f64 make of the values -- the same IEEE
  * operations in the same order as the host encoder, contraction off. */
