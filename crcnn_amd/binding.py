@@ -144,6 +144,10 @@ def load():
     L.crc_plan_hoist_pool.argtypes = [VP] + [CI] * 22 + [ctypes.POINTER(CI)]
     L.crc_limb_pack_tensor.argtypes = [VP, VP, CI, CI, CI, CI, CI, VP, VP]
     L.crc_limb_conv1_supported.argtypes = [VP] + [CI] * 8
+    L.crc_limb_conv1_box_supported.argtypes = [VP] + [CI] * 10
+    L.crc_conv2d_box_forms_work_bytes.restype = SZ; L.crc_conv2d_box_forms_work_bytes.argtypes = [VP] + [CI] * 14
+    L.crc_conv2d_box_forms.argtypes = [VP, VP, VP, CI, VP] + [CI] * 11 + [CI, CI, VP, VP, VP]
+    L.crc_plan_conv1_box.argtypes = [VP] + [CI] * 12 + [ctypes.POINTER(CI)]
     L.crc_limb_conv1_weights_bytes.restype = SZ; L.crc_limb_conv1_weights_bytes.argtypes = [VP]
     L.crc_limb_conv1_pack_weights.argtypes = [VP, VP, CI, CI, CI, VP, VP]
     L.crc_limb_conv1_weights_bytes_for.restype = SZ; L.crc_limb_conv1_weights_bytes_for.argtypes = [VP, CI, CI, CI]
@@ -652,6 +656,24 @@ class Engine:
         _chk(self.L.crc_plan_hoist_pool(self.c, *(tuple(up) if up else (0,) * 8), *conv, *pool, int(B or 0), 1 if matrix_cores else 0, ctypes.byref(h)),
              "crc_plan_hoist_pool")
         return bool(h.value)
+
+    # ---- the box of a one-channel convolution: the layer reads the bxf x byf window sums of its input (crc_conv2d_box_forms); (xf, yf) is the BASE window
+    def limb_conv1_box_supported(self, zd, xd, yd, xs, ys, xf, yf, nf, bxf, byf):
+        return bool(self.L.crc_limb_conv1_box_supported(self.c, zd, xd, yd, xs, ys, xf, yf, nf, bxf, byf))
+
+    def conv2d_box_forms_work_bytes(self, B, zd, xd, yd, xs, ys, xf, yf, nf, bxf, byf, in_form, w_form, out_form):
+        return self.L.crc_conv2d_box_forms_work_bytes(self.c, B, zd, xd, yd, xs, ys, xf, yf, nf, bxf, byf, in_form, w_form, out_form)
+
+    def conv2d_box(self, d_x, d_w, d_bias, B, zd, xd, yd, xs, ys, xf, yf, nf, bxf, byf, in_form, out_form, d_y, d_work, w_form=NTTL1):
+        _chk(self.L.crc_conv2d_box_forms(self.c, self.p(d_x), self.p(d_w), w_form, self.p(d_bias), B, zd, xd, yd, xs, ys, xf, yf, nf, bxf, byf, in_form, out_form,
+                                         self.p(d_y), self.p(d_work), self.stream), "crc_conv2d_box_forms")
+
+    def plan_conv1_box(self, zd, xd, yd, xs, ys, xf, yf, nf, bxf, byf, B=0, matrix_cores=True):
+        """crc_plan_conv1_box: does a one-channel layer with base window (xf, yf) sum its input (the box) instead of running the enlarged window?"""
+        b = CI(0)
+        _chk(self.L.crc_plan_conv1_box(self.c, zd, xd, yd, xs, ys, xf, yf, nf, bxf, byf, int(B or 0), 1 if matrix_cores else 0, ctypes.byref(b)),
+             "crc_plan_conv1_box")
+        return bool(b.value)
 
     # ---- scalar form (CRC_NTTLS): the layers of a slot-batched network, whose weights are constant polynomials
     def scalar_weights_bytes(self, nf, zd, xf=1, yf=1):

@@ -172,26 +172,28 @@ static int conv1_sub_batch(const crc_ctx *c, int B, int xd, int yd, int xf, int 
     return (int)(fit < 1 ? 1 : fit > (size_t)B ? (size_t)B : fit);
 }
 // Work of a one-channel layer, for a pass of Bs images: [y-expanded limb images][slot-major result (not where the kernel writes the limb tensor itself)][NTT copy
-// of a coefficient-form sub-batch].  out_form: the form the passes produce
+// of a coefficient-form sub-batch].  out_form: the form the passes produce.  xd x yd: the input image; xdi x ydi: the image the kernel reads (the box sums of a
+// boxed layer, crc_conv2d_box_forms; the input itself otherwise)
 struct Limb1Work { signed char *Xr; u64 *Ys, *buf; int Bs, out_form; };
-static Limb1Work limb1_layout(const crc_ctx *c, int B, int xd, int yd, int xf, int yf, int nf, int P, int in_form, int out_form, WorkArena &a)
+static Limb1Work limb1_layout(const crc_ctx *c, int B, int xd, int yd, int xdi, int ydi, int xf, int yf, int nf, int P, int in_form, int out_form, WorkArena &a)
 {
     Limb1Work L{};
     // a 1 x 1 result is a dense layer's input: the K-blocked form (kernels_mfma.hip), made from the slot-major result
     L.out_form = out_form == CRC_NTTLC && P == 1 ? CRC_NTTL : out_form;
-    L.Bs = conv1_sub_batch(c, B, xd, yd, xf, yf, nf, P, L.out_form);
-    L.Xr = a.take<signed char>(k_limb_conv1_image_bytes(c, L.Bs, xd, yd, xf, yf, nf));
+    L.Bs = conv1_sub_batch(c, B, xdi, ydi, xf, yf, nf, P, L.out_form);
+    L.Xr = a.take<signed char>(k_limb_conv1_image_bytes(c, L.Bs, xdi, ydi, xf, yf, nf));
     if (L.out_form != CRC_NTTLC) L.Ys = a.take<u64>(k_limb_result_words(c, L.Bs, nf, P));
     if (in_form == CRC_COEFF) L.buf = a.take<u64>((size_t)L.Bs * xd * yd * crc_ct_words(c, 2));
     return L;
 }
 static int conv2d_limb1(crc_ctx *c, const uint64_t *d_x, const void *d_wl, const uint64_t *d_bias, int B, int xd, int yd, int xs, int ys, int xf, int yf,
     int nf,
-                        int in_form, int out_form, uint64_t *d_y, void *d_work, hipStream_t st)
+                        int in_form, int out_form, uint64_t *d_y, void *d_work, hipStream_t st, int bxf = 1, int byf = 1)
 {
-    const int xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys + 1, P = xo * yo, in_cts = xd * yd;
+    const int xdi = xd - (bxf - 1) * xs, ydi = yd - (byf - 1) * ys;
+    const int xo = (xdi - xf) / xs + 1, yo = (ydi - yf) / ys + 1, P = xo * yo, in_cts = xd * yd;
     WorkArena a(d_work);
-    const Limb1Work L = limb1_layout(c, B, xd, yd, xf, yf, nf, P, in_form, out_form, a);
+    const Limb1Work L = limb1_layout(c, B, xd, yd, xdi, ydi, xf, yf, nf, P, in_form, out_form, a);
     out_form = L.out_form;
     const size_t ctw = crc_ct_words(c, 2);
     for (int b0 = 0; b0 < B; b0 += L.Bs) {
@@ -200,7 +202,7 @@ static int conv2d_limb1(crc_ctx *c, const uint64_t *d_x, const void *d_wl, const
         if (in_form == CRC_COEFF) { RUN(k_ntt_ct(c, false, xn, L.buf, (size_t)Bn * in_cts, 2, false, st, nullptr, 0, 0, 0, 0)); xn = L.buf; packed = false; }
         RUN(k_limb_conv1(c, xn, packed, L.Xr, (const signed char *)d_wl, L.Ys, out_form == CRC_NTTLC ? (signed char *)d_y : nullptr, B, b0,
             out_form != CRC_COEFF ? d_bias : nullptr,
-                         Bn, xd, yd, xs, ys, xf, yf, nf, st));
+                         Bn, xd, yd, xs, ys, xf, yf, nf, st, bxf, byf));
         if (out_form == CRC_NTTLC) continue;
         if (out_form == CRC_NTTL) return k_limb_result_to_limb(c, L.Ys, (signed char *)d_y, B, nf * P, st);     // (Bs == B)
         RUN(k_limb_result_to_rows(c, L.Ys, d_y + (size_t)b0 * nf * P * ctw, (size_t)Bn * nf * P * 2, out_form == CRC_NTTP, st));
@@ -224,7 +226,7 @@ extern "C" size_t crc_conv2d_forms_work_bytes(const crc_ctx *c, int B, int zd, i
     if (!c || !conv_shape_ok(xd, yd, xs, ys, xf, yf)) return 0;
     const int P = ((xd - xf) / xs + 1) * ((yd - yf) / ys + 1);
     WorkArena a;
-    if (w_form == CRC_NTTL1) limb1_layout(c, B, xd, yd, xf, yf, nf, P, in_form, out_form, a);
+    if (w_form == CRC_NTTL1) limb1_layout(c, B, xd, yd, xd, yd, xf, yf, nf, P, in_form, out_form, a);
     else if (w_form == CRC_NTTL || w_form == CRC_NTTLS) limb_layout(c, B, zd, xd, yd, nf, P, in_form, a);
     else conv_layout(c, B, zd, xd, yd, xf, yf, P, in_form, a);
     return a.bytes();
@@ -310,6 +312,37 @@ extern "C" int crc_conv2d_forms(crc_ctx *c, const uint64_t *d_x, const uint64_t 
     if (out_form == CRC_COEFF)                    // one inverse NTT per output ciphertext, add_plain(bias) fused into its store
         RUN(k_ntt_ct(c, true, d_y, d_y, (size_t)B * nf * P, 2, false, st, d_bias, 1, (size_t)P, nf));
     return CRC_OK;
+}
+// The one-channel layer on the bxf x byf window sums of its input (the box: kernels_mfma1.hip limb_pack_rows1_kernel_px).  (xd, yd): the full image, (xf, yf):
+// the BASE window; a 1 x 1 box is crc_conv2d_forms
+extern "C" int crc_limb_conv1_box_supported(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int bxf, int byf)
+{
+    if (!c || nf < 1 || bxf < 1 || byf < 1 || xs < 1 || ys < 1) return 0;
+    const int xdi = xd - (bxf - 1) * xs, ydi = yd - (byf - 1) * ys;
+    if (!conv_shape_ok(xd, yd, xs, ys, xf, yf) || !conv_shape_ok(xdi, ydi, xs, ys, xf, yf)) return 0;
+    return k_limb_conv1_box_shape(c, zd, xd, yd, xs, ys, xf, yf, nf, bxf, byf) ? 1 : 0;
+}
+extern "C" size_t crc_conv2d_box_forms_work_bytes(const crc_ctx *c, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int bxf, int byf,
+    int in_form, int w_form, int out_form)
+{
+    if (c && bxf == 1 && byf == 1) return crc_conv2d_forms_work_bytes(c, B, zd, xd, yd, xs, ys, xf, yf, nf, in_form, w_form, out_form);
+    if (w_form != CRC_NTTL1 || !crc_limb_conv1_box_supported(c, zd, xd, yd, xs, ys, xf, yf, nf, bxf, byf)) return 0;
+    const int xdi = xd - (bxf - 1) * xs, ydi = yd - (byf - 1) * ys, P = ((xdi - xf) / xs + 1) * ((ydi - yf) / ys + 1);
+    WorkArena a;
+    limb1_layout(c, B, xd, yd, xdi, ydi, xf, yf, nf, P, in_form, out_form, a);
+    return a.bytes();
+}
+extern "C" int crc_conv2d_box_forms(crc_ctx *c, const uint64_t *d_x, const uint64_t *d_w, int w_form, const uint64_t *d_bias, int B, int zd, int xd, int yd,
+                                    int xs, int ys, int xf, int yf, int nf, int bxf, int byf, int in_form, int out_form, uint64_t *d_y, void *d_work,
+                                    void *stream)
+{
+    if (bxf == 1 && byf == 1) return crc_conv2d_forms(c, d_x, d_w, w_form, d_bias, B, zd, xd, yd, xs, ys, xf, yf, nf, in_form, out_form, d_y, d_work, stream);
+    CHECK_CTX(c);
+    if (!d_x || !d_w || !d_y || !d_work || B < 0 || nf < 1 || bxf < 1 || byf < 1 || !nform_ok(in_form) || !(lform_ok(out_form) || out_form == CRC_NTTLC) ||
+        !conv_shape_ok(xd, yd, xs, ys, xf, yf)) return CRC_ERR_INVALID_ARGUMENT;
+    if (w_form != CRC_NTTL1 || !crc_limb_conv1_box_supported(c, zd, xd, yd, xs, ys, xf, yf, nf, bxf, byf)) return CRC_ERR_UNSUPPORTED;
+    if (B == 0) return CRC_OK;
+    return conv2d_limb1(c, d_x, d_w, d_bias, B, xd, yd, xs, ys, xf, yf, nf, in_form, out_form, d_y, d_work, S(stream), bxf, byf);
 }
 extern "C" int crc_conv2d(crc_ctx *c, const uint64_t *d_x, const uint64_t *d_w, const uint64_t *d_bias, int B, int zd, int xd, int yd,
                           int xs, int ys, int xf, int yf, int nf, int in_form, int out_form, uint64_t *d_y, void *d_work, void *stream)
@@ -489,14 +522,15 @@ extern "C" int crc_plan_fold_pool(const crc_ctx *c, int zd, int xd, int yd, int 
 // Cost of a conv / dense layer on the kernel crc_plan_mac gives it, in crc_plan_fold_pool's units (one multiply-accumulate term per output ciphertext, ~24 terms
 // of prologue / epilogue per output).  The limb GEMM pads the channels of every tap to 32 and takes filters in tiles of 32.  The one-channel matrix-core kernel
 // pays for its whole K whatever the window -- 64 taps in the plane-major form, 40 in the pixel-major one -- for 32 filters and whole 16-row tiles (8 positions x 2
-// polys), and a term there costs 25/16 of the limb GEMM's (PlainModelTiny at n = 4096, 128 images per launch, kernel + image pack: pixel-major 35.6 ms for 18
-// tiles, plane-major 48.4 ms, against 92.8 ms for the limb GEMM's 64 x 16 outputs of 1152 + 24 terms -- 1.57 and 1.55; profiles/conv1_pixel_major_ab.txt)
+// polys), and a term there costs 8/5 of the limb GEMM's (PlainModelTiny at n = 4096, 128 images per launch, kernel + image pack: pixel-major 6 x 6 35.9 ms for 18
+// tiles, plane-major 8 x 8 44.5 ms for 16, against 92.6 ms for the limb GEMM's 64 x 16 outputs of 1152 + 24 terms -- 1.59 and 1.60; profiles/conv1_box_ab.txt.
+// 25/16 before those measurements)
 static long long plan_mac_cost(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int B, int matrix_cores)
 {
     int wf = CRC_NTT;
     if (crc_plan_mac(c, zd, xd, yd, xs, ys, xf, yf, nf, B, matrix_cores, &wf) != CRC_OK) return -1;
     const long long P = (long long)((xd - xf) / xs + 1) * ((yd - yf) / ys + 1);
-    if (wf == CRC_NTTL1) return 32 * ((2 * P + 15) / 16 * 8) * ((k_limb_conv1_form(c, xf, yf, nf) == 2 ? 40 : 64) + 24) * 25 / 16;
+    if (wf == CRC_NTTL1) return 32 * ((2 * P + 15) / 16 * 8) * ((k_limb_conv1_form(c, xf, yf, nf) == 2 ? 40 : 64) + 24) * 8 / 5;
     if (wf == CRC_NTTL) return (long long)(nf + 31) / 32 * 32 * P * ((long long)k_limb_steps(zd, xf, yf) * 32 + 24);
     return (long long)(nf + 7) / 8 * 8 * P * ((long long)zd * xf * yf + 24);
 }
@@ -535,6 +569,32 @@ extern "C" int crc_plan_hoist_pool(const crc_ctx *c, int uzd, int uxd, int uyd, 
     const long long hoisted = plan_mac_cost(c, uzd, uxd, uyd, uxs, uys, uxf2, uyf2, unf, B, matrix_cores) +
                               plan_mac_cost(c, zd, sxd, syd, pxs, pys, xf, yf, nf, B, matrix_cores);
     *hoist = hoisted < folded ? 1 : 0;
+    return CRC_OK;
+}
+
+// Should a one-channel convolution whose weights are its base window W (xf x yf) convolved with a bxf x byf sum at its own stride -- the upstream layer of a hoisted
+// pair (crc_plan_hoist_pool) -- sum its INPUT instead (crc_conv2d_box_forms) and keep W?  conv_{W * box}(x) = conv_W(box x): exact over Z_q.  Yes when the base
+// window runs on the pixel-major one-channel kernel, the summed image fits it, and the box execution costs less than the enlarged window in plan_mac_cost's units.
+// The box's own cost is the image pack's extra reads: bxf byf - 1 further loads per pixel and poly of the summed image, PLAN_BOX_READ units each -- measured, not
+// derived: PlainModelTiny at n = 4096, 128 images per launch, the pack 12.0 ms with the 2 x 2 box against 6.4 ms x 26^2 / 28^2 = 5.5 ms without one, 6.5 ms for
+// 26 x 26 x 2 x 3 reads, at the limb GEMM's 77 ns per unit (profiles/conv1_box_ab.txt): the re-reads miss L1 and are served by L2 / the memory-side cache, they are
+// not free.  The tuning key conv1_box = 0 (CRC_CONV1_BOX=0) answers no throughout.
+#define PLAN_BOX_READ 21
+extern "C" int crc_plan_conv1_box(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int bxf, int byf, int B, int matrix_cores,
+                                  int *box)
+{
+    if (!c || !box || zd < 1 || nf < 1 || bxf < 1 || byf < 1 || !conv_shape_ok(xd, yd, xs, ys, xf, yf)) return CRC_ERR_INVALID_ARGUMENT;
+    *box = 0;
+    if (!c->tune.conv1_box || !matrix_cores || bxf * byf == 1) return CRC_OK;
+    if (!crc_limb_conv1_box_supported(c, zd, xd, yd, xs, ys, xf, yf, nf, bxf, byf)) return CRC_OK;
+    const int xf2 = (bxf - 1) * xs + xf, yf2 = (byf - 1) * ys + yf, xdi = xd - (bxf - 1) * xs, ydi = yd - (byf - 1) * ys;
+    if (!conv_shape_ok(xd, yd, xs, ys, xf2, yf2)) return CRC_OK;
+    int wf = CRC_NTT;
+    if (crc_plan_mac(c, zd, xdi, ydi, xs, ys, xf, yf, nf, B, matrix_cores, &wf) != CRC_OK || wf != CRC_NTTL1) return CRC_OK;
+    const long long enlarged = plan_mac_cost(c, zd, xd, yd, xs, ys, xf2, yf2, nf, B, matrix_cores);
+    const long long boxed = plan_mac_cost(c, zd, xdi, ydi, xs, ys, xf, yf, nf, B, matrix_cores) +
+                            (long long)xdi * ydi * 2 * (bxf * byf - 1) * PLAN_BOX_READ;
+    *box = enlarged >= 0 && boxed < enlarged ? 1 : 0;
     return CRC_OK;
 }
 

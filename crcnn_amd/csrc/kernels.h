@@ -127,4 +127,6 @@ size_t k_limb_conv1_weights_bytes_for(const crc_ctx *c, int nf, int xf, int yf);
 size_t k_limb_conv1_image_bytes(const crc_ctx *c, int B, int xd, int yd, int xf, int yf, int nf);
 int k_limb_conv1_pack_weights(crc_ctx *c, const u64 *w, signed char *wl, int nf, int xf, int yf, hipStream_t st);
 int k_limb_conv1(crc_ctx *c, const u64 *x, bool packed, signed char *xr, const signed char *wl, u64 *ys, signed char *xl_out, int Bout, int b0, const u64 *bias_ntt, int B, int xd, int yd,
-                 int xs, int ys_, int xf, int yf, int nf, hipStream_t st);
+                 int xs, int ys_, int xf, int yf, int nf, hipStream_t st, int bxf = 1, int byf = 1);
+// a bxf x byf box (window sum of the xd x yd input at the layer's stride, made by the image pack) in front of the layer with base window xf x yf
+bool   k_limb_conv1_box_shape(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys_, int xf, int yf, int nf, int bxf, int byf);

@@ -448,37 +448,77 @@ __global__ void __launch_bounds__(256) limb_pack_rows1_kernel(const u64 *x, i8 *
 // The pixel-major image: Xp [slot][B][poly][row][column], one balanced_digit_bytes value per pixel, rows rs bytes and polys poly_bytes apart.  The same workgroup
 // and the same 32-slot transpose through LDS; a thread stages its 16 pixels as they are (no per-byte scatter into planes), and the RG rows a slot owns are one
 // contiguous run of RG * rs bytes in Xp.  Staging: [slot][RG rows][rs bytes] + 16 bytes per slot (neighbouring slots on different banks).
+// Box (bxf x byf, default 1 x 1): the packed image is the WINDOW SUM of the input at the layer's stride, pixel (r, c) = sum over a < bxf, b < byf of
+// x(r + a xs, c + b ys) mod q, xdo x ydo = (xd - (bxf-1) xs) x (yd - (byf-1) ys) pixels -- a sum pool behind the convolution, moved in front of it (the layer is
+// shift-equivariant: DESIGN.md section 4.5).  The sum is taken on canonical residues (after the 28-bit unpack) and reduced once (limbred.h sum_reduce16: bxf byf <=
+// 9 terms below 2^55).  Halo: a thread reads every term of its 16 pixels itself -- bxf byf loads per pixel, the same coalesced 256-byte segment per (row, column) and
+// 32 slots as without a box -- and nothing more is staged in LDS, so the staging area stays at 27 KiB = five workgroups per CU and there is one barrier.  The terms
+// of one pixel are other pixels' terms too (the same thread two columns on, the thread two rows on, the next row group's workgroup on the same XCD), and the choice
+// counted on those re-reads being L1 / L2 hits.  MEASURED (profiles/conv1_box_ab.txt, PlainModelTiny at n = 4096, 128 images): they are not L1 hits -- five
+// workgroups per CU each walk 6 rows x 28 columns x 256 bytes, more than the 32 KiB L1 -- and the pass takes 12.0 ms with the 2 x 2 box against 5.5 ms for the
+// same output without one: the three further reads per pixel cost 6.5 ms, served by L2 and the memory-side cache.  The layer still gains (kernel + pack 44.5 ->
+// 38.4 ms), so the simple form stays; the form that reads every input once per workgroup -- row sums of RG + (bxf-1) xs rows staged in LDS as 8-byte residues, 41
+// KiB: three workgroups per CU, a second barrier -- is the open step.
+// (BOX = false: no box -- the body every unboxed layer ran before the pass could take one)
+template <bool BOX>
 __global__ void __launch_bounds__(256) limb_pack_rows1_kernel_px(const u64 *x, i8 *xr, const ModParams *mods, int n, int k, int B, int xd, int yd, int packed,
-                                                                 unsigned img_stride, unsigned poly_bytes, unsigned rs)
+                                                                 unsigned img_stride, unsigned poly_bytes, unsigned rs, int xdo, int ydo, int bxf, int byf, int xs,
+                                                                 int ys)
 {
     extern __shared__ __attribute__((aligned(16))) i8 stp[];
     const unsigned sstride = RG * rs + 16;
     const int sblocks = n / RSL;
     const int sb = blockIdx.x % (sblocks * k), i = sb / sblocks, s0 = (sb % sblocks) * RSL;
-    const int rgs = (xd + RG - 1) / RG;
+    const int rgs = (xdo + RG - 1) / RG;
     size_t r = blockIdx.x / (sblocks * k);                       // (b*2 + c)*rgs + row group
     const int rg = (int)(r % rgs); r /= rgs; const int c = (int)(r % 2); const int b = (int)(r / 2);
     const u64 q = mods[i].q;
     const int lane = threadIdx.x & (RSL - 1), qrow = (threadIdx.x >> 5) & (RG - 1), h = threadIdx.x >> 7, row = rg * RG + qrow;
-    if (row < xd) {
+    if (row < xdo) {
+        const size_t cs = (size_t)2 * k * n;                         // words between neighbouring columns
         const u64 *src = x + ((((size_t)b * xd * yd + (size_t)row * yd + h * 16) * 2 + c) * k + i) * (size_t)n + s0 + lane;
         u64 *sp = reinterpret_cast<u64 *>(stp + (size_t)lane * sstride + qrow * rs) + h * 16;
+        if constexpr (!BOX) {
+            // no box (xdo = xd, ydo = yd): a pixel is loaded, cut into digits and staged in one go, as the pass did before it could take a box
 #pragma unroll
-        for (int colx = 0; colx < 16; colx++) {
-            const int col = h * 16 + colx;
-            if ((unsigned)col * 8 >= rs) continue;
-            u64 dg = 0;                                              // (a column past yd: the padding of an odd width)
-            if (col < yd) {
-                u64 v = src[(size_t)colx * 2 * k * n];
-                if (packed) v = (v & 0xffffffffULL) | ((v >> 32) << 28);
-                dg = balanced_digit_bytes(v, q);
+            for (int colx = 0; colx < 16; colx++) {
+                const int col = h * 16 + colx;
+                if ((unsigned)col * 8 >= rs) continue;
+                u64 dg = 0;                                              // (a column past yd: the padding of an odd width)
+                if (col < yd) {
+                    u64 v = src[(size_t)colx * cs];
+                    if (packed) v = (v & 0xffffffffULL) | ((v >> 32) << 28);
+                    dg = balanced_digit_bytes(v, q);
+                }
+                sp[colx] = dg;
             }
-            sp[colx] = dg;
+        } else {
+            u64 sum[16];
+#pragma unroll
+            for (int colx = 0; colx < 16; colx++) sum[colx] = 0;
+            for (int a = 0; a < bxf; a++)
+                for (int bb = 0; bb < byf; bb++) {
+                    const u64 *tp = src + ((size_t)a * xs * yd + (size_t)bb * ys) * cs;  // (row + a xs <= xd - 1, column + bb ys <= yd - 1 for column < ydo)
+#pragma unroll
+                    for (int colx = 0; colx < 16; colx++)
+                        if (h * 16 + colx < ydo) {
+                            u64 v = tp[(size_t)colx * cs];
+                            if (packed) v = (v & 0xffffffffULL) | ((v >> 32) << 28);
+                            sum[colx] += v;
+                        }
+                }
+#pragma unroll
+            for (int colx = 0; colx < 16; colx++) {
+                const int col = h * 16 + colx;
+                if ((unsigned)col * 8 >= rs) continue;
+                // (a column past ydo: the padding of an odd width)
+                sp[colx] = col < ydo ? balanced_digit_bytes(sum_reduce16(sum[colx], q), q) : 0;
+            }
         }
     }
     __syncthreads();
-    // RSL runs of RG * rs bytes, 16 bytes per lane (rows past xd of a ragged last group are not stored)
-    const int per_run = RG * rs / 16, valid = min(RG, xd - rg * RG) * (int)rs / 16;
+    // RSL runs of RG * rs bytes, 16 bytes per lane (rows past xdo of a ragged last group are not stored)
+    const int per_run = RG * rs / 16, valid = min(RG, xdo - rg * RG) * (int)rs / 16;
     for (int o = threadIdx.x; o < RSL * per_run; o += 256) {
         const int sl = o / per_run, part = o - sl * per_run;
         if (part >= valid) continue;
@@ -563,6 +603,15 @@ bool k_limb_conv1_shape(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys
     // (the pixel-major image is the smaller one up to 28 columns; wider than that it can be up to 14 % larger)
     return conv1_fits(k_limb_conv1_form(c, xf, yf, nf) == 2 ? conv1_px_img_stride(xd, yd) : conv1_img_stride(xd), xd, yd, xs, ys_, xf, yf);
 }
+// A box (input-side window sum, limb_pack_rows1_kernel_px) in front of a layer with base window xf x yf: the pixel-major form only, at most 9 terms (sum_reduce16's
+// bound with room to spare), and the SUMMED image must be a shape the kernel takes
+bool k_limb_conv1_box_shape(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys_, int xf, int yf, int nf, int bxf, int byf)
+{
+    if (bxf < 1 || byf < 1 || bxf * byf > 9) return false;
+    const int xdo = xd - (bxf - 1) * xs, ydo = yd - (byf - 1) * ys_;
+    if (xdo < xf || ydo < yf || !k_limb_conv1_shape(c, zd, xdo, ydo, xs, ys_, xf, yf, nf)) return false;
+    return bxf * byf == 1 || k_limb_conv1_form(c, xf, yf, nf) == 2;
+}
 static size_t conv1_form_weights_bytes(const crc_ctx *c, int form) { return (size_t)c->n * c->k * NPL * 32 * 64 * (form == 2 ? NJ : 1); }
 size_t k_limb_conv1_weights_bytes(const crc_ctx *c) { return conv1_form_weights_bytes(c, 2); }            // enough for either form
 size_t k_limb_conv1_weights_bytes_for(const crc_ctx *c, int nf, int xf, int yf) { return conv1_form_weights_bytes(c, k_limb_conv1_form(c, xf, yf, nf)); }
@@ -587,14 +636,16 @@ int k_limb_conv1_pack_weights(crc_ctx *c, const u64 *w, i8 *wl, int nf, int xf, 
     HIPCHK(hipGetLastError());
     return CRC_OK;
 }
-// x: B NTT-form one-channel images; xr: k_limb_conv1_image_bytes of scratch; result either images b0 .. b0 + B of a limb tensor of Bout images (xl_out,
+// x: B NTT-form one-channel images of xd_in x yd_in pixels; the convolution reads their bxf x byf window sums at its own stride (xd x yd pixels below; no box: the
+// images themselves); xr: k_limb_conv1_image_bytes of scratch for that xd x yd image; result either images b0 .. b0 + B of a limb tensor of Bout images (xl_out,
 // [slot][Bout][7][P][2][32]) or slot-major u64 (ys, [slot][B][F][P][2])
-int k_limb_conv1(crc_ctx *c, const u64 *x, bool packed, i8 *xr, const i8 *wl, u64 *ys, i8 *xl_out, int Bout, int b0, const u64 *bias_ntt, int B, int xd,
-    int yd, int xs, int ys_,
-                 int xf, int yf, int nf, hipStream_t st)
+int k_limb_conv1(crc_ctx *c, const u64 *x, bool packed, i8 *xr, const i8 *wl, u64 *ys, i8 *xl_out, int Bout, int b0, const u64 *bias_ntt, int B, int xd_in,
+    int yd_in, int xs, int ys_,
+                 int xf, int yf, int nf, hipStream_t st, int bxf, int byf)
 {
     if (B == 0) return CRC_OK;
-    if (!k_limb_conv1_shape(c, 1, xd, yd, xs, ys_, xf, yf, nf)) return CRC_ERR_UNSUPPORTED;
+    if (!k_limb_conv1_box_shape(c, 1, xd_in, yd_in, xs, ys_, xf, yf, nf, bxf, byf)) return CRC_ERR_UNSUPPORTED;
+    const int xd = xd_in - (bxf - 1) * xs, yd = yd_in - (byf - 1) * ys_;
     const int xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys_ + 1;
     const int form = k_limb_conv1_form(c, xf, yf, nf);
     Conv1Args a{};
@@ -611,8 +662,12 @@ int k_limb_conv1(crc_ctx *c, const u64 *x, bool packed, i8 *xr, const i8 *wl, u6
         a.px_rs = conv1_px_rs(yd); a.poly_bytes = conv1_px_poly_bytes(xd, yd); a.img_stride = conv1_px_img_stride(xd, yd);
         a.px_taps = xf * yf; a.px_yf = yf;
         a.px_pair = yf % 2 == 0 && ys_ % 2 == 0 ? 1 : 0;
-        hipLaunchKernelGGL(limb_pack_rows1_kernel_px, dim3((unsigned)pack_blocks), dim3(256), RSL * (RG * a.px_rs + 16), st, x, xr, c->d_mods, c->n, c->k, B, xd,
-            yd, packed ? 1 : 0, a.img_stride, a.poly_bytes, a.px_rs);
+        if (bxf * byf > 1)
+            hipLaunchKernelGGL(limb_pack_rows1_kernel_px<true>, dim3((unsigned)pack_blocks), dim3(256), RSL * (RG * a.px_rs + 16), st, x, xr, c->d_mods, c->n, c->k,
+                B, xd_in, yd_in, packed ? 1 : 0, a.img_stride, a.poly_bytes, a.px_rs, xd, yd, bxf, byf, xs, ys_);
+        else
+            hipLaunchKernelGGL(limb_pack_rows1_kernel_px<false>, dim3((unsigned)pack_blocks), dim3(256), RSL * (RG * a.px_rs + 16), st, x, xr, c->d_mods, c->n, c->k,
+                B, xd_in, yd_in, packed ? 1 : 0, a.img_stride, a.poly_bytes, a.px_rs, xd, yd, 1, 1, xs, ys_);
         HIPCHK(hipGetLastError());
         // (140 registers of resident weights: two waves per SIMD, whatever conv1_waves asks for)
         const size_t lds = 2 * (size_t)a.img_stride + (xl_out ? a.out_img_bytes : 0);

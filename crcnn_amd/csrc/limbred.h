@@ -203,6 +203,17 @@ CRC_HD u64 balanced_digit_bytes(u64 r, u64 q)
     return ((u64)cv + 0x0080808080808080ULL) ^ 0x0080808080808080ULL;
 }
 
+// the canonical residue of a sum of at most 15 canonical residues, s < 16 q, for q < 2^60 (8 q fits a word): four conditional subtractions.  The one-channel
+// kernel's box (kernels_mfma1.hip limb_pack_rows1_kernel_px) sums at most 9 residues below 2^55: s < 2^59
+CRC_HD u64 sum_reduce16(u64 s, u64 q)
+{
+    s -= s >= (q << 3) ? q << 3 : 0;
+    s -= s >= (q << 2) ? q << 2 : 0;
+    s -= s >= (q << 1) ? q << 1 : 0;
+    s -= s >= q ? q : 0;
+    return s;
+}
+
 // ---- tables (host) ------------------------------------------------------------------------------------------------------------------------------------------
 inline u64 inverse_mod_2_64(u64 q) { u64 inv = q; for (int it = 0; it < 6; it++) inv *= 2 - q * inv; return inv; }      // Newton: q odd, q q = 1 (mod 8)
 

@@ -870,9 +870,24 @@ static bool g_matrix_cores = true;                  // Network::matrix_cores of 
 int MacLayer::plannedForm(int B) const
 {
     int wf = CRC_NTT;
-    if (slot_weights && g_matrix_cores) chk(crc_plan_mac_scalar(ctx(), zd, xd, yd, xs, ys, xf, yf, nf, B, &wf), "crc_plan_mac_scalar");
-    else chk(crc_plan_mac(ctx(), zd, xd, yd, xs, ys, xf, yf, nf, B, g_matrix_cores ? 1 : 0, &wf), "crc_plan_mac");
+    // (a boxed layer is planned as what it runs: the base window over the summed image)
+    const int xdi = xd - (bxf - 1) * xs, ydi = yd - (byf - 1) * ys;
+    if (slot_weights && g_matrix_cores) chk(crc_plan_mac_scalar(ctx(), zd, xdi, ydi, xs, ys, wxf(), wyf(), nf, B, &wf), "crc_plan_mac_scalar");
+    else chk(crc_plan_mac(ctx(), zd, xdi, ydi, xs, ys, wxf(), wyf(), nf, B, g_matrix_cores ? 1 : 0, &wf), "crc_plan_mac");
     return wf;
+}
+// a boxed layer's weights back to the enlarged window W * box (crc_conv2d_fold_pool makes exactly that; its bias output -- the box's multiple of a bias that already
+// is one -- is dropped)
+void MacLayer::unbox()
+{
+    if (!boxed()) return;
+    packWeights(true);
+    const size_t rowb = (size_t)K() * N() * 8;
+    auto w2 = make_shared<DeviceBuffer>((size_t)nf * zd * xf * yf * rowb), b2 = make_shared<DeviceBuffer>((size_t)nf * rowb);
+    chk(crc_conv2d_fold_pool(ctx(), (const uint64_t *)d_w->ptr, (const uint64_t *)d_b[1]->ptr, nullptr, nf, zd, wxf(), wyf(), xs, ys, bxf, byf,
+        (uint64_t *)w2->ptr, (uint64_t *)b2->ptr, stream()), "crc_conv2d_fold_pool");
+    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+    d_w = w2; bxf = byf = 1;
 }
 // room for the limb copy (CRC_NTTL) beside the canonical weights it is made from
 bool MacLayer::limbFits() const
@@ -1009,12 +1024,14 @@ bool MacLayer::limbWeights(int B)
     // The one-channel matrix-core kernel (kernels_mfma1.hip) is a convolution's only: crc_plan_mac answers CRC_NTTL1 for a dense layer with in_dim == 1 as
     // well, which stays on the vector-ALU kernel
     const bool conv1 = !dense && planned == CRC_NTTL1;
+    // (a boxed layer that does not get the one-channel kernel -- matrix cores off, a forced form -- takes its enlarged window back and is planned again)
+    if (boxed() && !(conv1 && crc_limb_conv1_box_supported(ctx(), zd, xd, yd, xs, ys, wxf(), wyf(), nf, bxf, byf))) { unbox(); return limbWeights(B); }
     // (decided BEFORE the weights are touched: a layer that stays on the vector-ALU kernel keeps its 28-bit packed weights -- unpacking and re-packing them on
     // every forward() is a read-modify-write of the whole layer.  Nothing is allocated between this look at the free memory and the limb copy below)
     if (!conv1 && !(planned == CRC_NTTL && limbFits())) return false;
     if (w_form == CRC_NTTP) packWeights(true);
-    auto wl = make_shared<DeviceBuffer>(conv1 ? crc_limb_conv1_weights_bytes_for(ctx(), nf, xf, yf) : crc_limb_weights_bytes(ctx(), nf, zd, xf, yf));
-    if (conv1) chk(crc_limb_conv1_pack_weights(ctx(), (const uint64_t *)d_w->ptr, nf, xf, yf, wl->ptr, stream()), "crc_limb_conv1_pack_weights");
+    auto wl = make_shared<DeviceBuffer>(conv1 ? crc_limb_conv1_weights_bytes_for(ctx(), nf, wxf(), wyf()) : crc_limb_weights_bytes(ctx(), nf, zd, xf, yf));
+    if (conv1) chk(crc_limb_conv1_pack_weights(ctx(), (const uint64_t *)d_w->ptr, nf, wxf(), wyf(), wl->ptr, stream()), "crc_limb_conv1_pack_weights");
     else chk(crc_limb_pack_weights(ctx(), (const uint64_t *)d_w->ptr, nf, zd, xf, yf, wl->ptr, stream()), "crc_limb_pack_weights");
     chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
     // (the canonical copy of a one-channel layer is small: kept, so that the weights can go back on the wire; the limb GEMM's is dropped)
@@ -1042,6 +1059,18 @@ ciphertext3D MacLayer::run(const ciphertext3D &input, int zo, int xo, int yo)
     last_B = input.B;
     ciphertext3D out(input.B, zo, xo, yo, out_form);
     if (streamed) { stream_form = forwardStreamed(input, out); return out; }
+    // a boxed layer runs on the one-channel matrix-core kernel alone: a layer that reaches this point in another form (called directly, matrix cores off) takes
+    // its enlarged window back
+    if (boxed() && w_form != CRC_NTTL1) unbox();
+    if (boxed()) {
+        const size_t bw = crc_conv2d_box_forms_work_bytes(ctx(), input.B, zd, xd, yd, xs, ys, wxf(), wyf(), nf, bxf, byf, input.form, w_form, out_form);
+        if (!bw) throw invalid_argument(kind() + string(": unsupported geometry"));
+        ensure(g_scratch, bw);
+        chk(crc_conv2d_box_forms(ctx(), input.data(), (const uint64_t *)d_w->ptr, w_form, (const uint64_t *)d_b[out_form != CRC_COEFF]->ptr, input.B, zd, xd, yd,
+            xs, ys, wxf(), wyf(), nf, bxf, byf, input.form, out_form, out.data(), g_scratch->ptr, stream()), "crc_conv2d_box_forms");
+        if (out_form == CRC_NTTLC) out.form = CRC_NTTL;
+        return out;
+    }
     size_t wb = crc_conv2d_forms_work_bytes(ctx(), input.B, zd, xd, yd, xs, ys, xf, yf, nf, input.form, w_form, out_form);
     if (!wb) throw invalid_argument(kind() + string(": unsupported geometry"));      // (a convolution's: a 1x1 geometry always has work bytes)
     ensure(g_scratch, wb);
@@ -1793,6 +1822,15 @@ int Network::fuse()
             g_expected_batch, matrix_cores ? 1 : 0, &hoist), "crc_plan_hoist_pool");
         if (hoist) {
             auto sums = foldPool(*up, up->name, 1, 1, pool->xf, pool->yf, nullptr);
+            // ... and a one-channel layer in front sums its INPUT instead of enlarging its window (crc_plan_conv1_box): it keeps its base weights and carries the
+            // box; name, geometry and the bias of the fold (pxf pyf b) are the enlarged layer's.  Not behind a batch-norm layer, which step 2 folds into the
+            // enlarged window's weights
+            int box = 0;
+            const bool bn_in_front = i >= 2 && !refreshBetween(i - 2) && dynamic_pointer_cast<BatchNormLayer>(layers[i - 2]);
+            if (!up->boxed() && !bn_in_front)
+                chk(crc_plan_conv1_box(ctx(), up->zd, up->xd, up->yd, up->xs, up->ys, up->xf, up->yf, up->nf, pool->xf, pool->yf, g_expected_batch,
+                    matrix_cores ? 1 : 0, &box), "crc_plan_conv1_box");
+            if (box) { sums->d_w = up->d_w; sums->bxf = pool->xf; sums->byf = pool->yf; }
             vector<Plaintext> nob; plaintext4D nof;
             auto down = make_shared<ConvolutionalLayer>(conv->name + "+" + pool->name, sums->xo, sums->yo, conv->zd, pool->xs, pool->ys, conv->xf, conv->yf,
                 conv->nf, conv->th_count, nof, nob);
@@ -1841,6 +1879,9 @@ int Network::fuse()
         if (!bn || refreshBetween(i)) continue;
         auto m = dynamic_pointer_cast<MacLayer>(layers[i + 1]);
         if (!m) continue;
+        // (the fold is written for the window the layer reports: a boxed layer takes its enlarged weights back first -- step 1a does not box behind a batch norm,
+        // so this serves a second fuse() only)
+        if (m->boxed()) { m->upload(); m->unbox(); }
         // weights per output row and per batch-norm channel: a convolution has one channel per batch-norm channel, a dense layer reads the flattened
         // [ch][x][y] tensor
         const int ch = bn->num_channels, T = (int)m->taps();

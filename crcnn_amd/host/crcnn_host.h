@@ -201,6 +201,8 @@ public:
     void restoreCanonical();
     size_t deviceBytes() const override;
     std::string kernelName() const override;
+    // the box the layer carries at this moment (1 x 1: none -- never taken, or given back by unbox())
+    void boxSize(int &bx, int &by) const { bx = bxf; by = byf; }
 protected:
     MacLayer(std::string name, bool dense, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf)
         : Layer(name), zd(zd), xd(xd), yd(yd), xs(xs), ys(ys), xf(xf), yf(yf), nf(nf), dense(dense), slot_weights(slotEncoding()) {}
@@ -215,7 +217,15 @@ private:
     virtual void plaintexts(int f0, int fn, std::vector<const Plaintext *> &w, std::vector<const Plaintext *> *b) const = 0;
     const bool dense;                                       // decides the two one-sided features below, and the class name in error texts
     const char *kind() const { return dense ? "FullyConnectedLayer" : "ConvolutionalLayer"; }
-    size_t taps() const { return (size_t)zd * xf * yf; }    // weights per output row
+    // CONVOLUTIONS ONLY (Network::fuse() step 1a, crc_plan_conv1_box): a one-channel layer whose xf x yf window is a base window convolved with a bxf x byf sum at
+    // the layer's stride keeps the BASE window's weights and has the image pack sum its input instead (crc_conv2d_box_forms).  The layer still reports the
+    // geometry of the map it computes; unbox() goes back to the enlarged window's weights where the layer cannot run on the one-channel matrix-core kernel
+    int bxf = 1, byf = 1;
+    bool boxed() const { return bxf * byf > 1; }
+    int wxf() const { return xf - (bxf - 1) * xs; }         // the window the weights are stored for
+    int wyf() const { return yf - (byf - 1) * ys; }
+    void unbox();
+    size_t taps() const { return (size_t)zd * wxf() * wyf(); }    // weights per output row
     std::shared_ptr<DeviceBuffer> d_w, d_b[2];              // NTT-form weights, bias delta in coefficient / NTT form
     // weights whose NTT form (k rows each) would take more than 75 % of HBM stay coefficient-form plaintexts (ONE row each) and are lifted + transformed a
     // ~2-GiB filter tile at a time inside every forward (SURVEY section 7's fall-back; PlainModelWoPad's fc3 with all eight primes of n = 16384 is 419 GB)

@@ -111,6 +111,9 @@ static int do_netgeom(int argc, char **argv)
     vector<ciphertext3D> imgs;
     for (int b = 0; b < batch; b++) imgs.push_back(ciphertext3D::fromHost(x.data(), 1, net.input_zd, net.input_xd, net.input_yd));
     wr(dir + "/out.u64", net.forward(stackImages(imgs)).toHost());
+    // (after the forward: a boxed layer that fell back to its enlarged window says 1 1 here)
+    for (int i = 0; i < net.getNumLayers(); i++)
+        if (auto m = dynamic_pointer_cast<MacLayer>(net.getLayer(i))) { int bx, by; m->boxSize(bx, by); printf("box %d %s %d %d\n", i, m->getName().c_str(), bx, by); }
     delParameters();
     return 0;
 }

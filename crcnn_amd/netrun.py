@@ -402,6 +402,13 @@ class Network:
         """(zd, xd, yd, xs, ys, xf, yf, nf) of a conv / dense layer (a dense layer is the 1 x 1 convolution zd = in_dim, nf = out_dim)"""
         return (a["zd"], a["xd"], a["yd"], a["xs"], a["ys"], a["xf"], a["yf"], a["nf"]) if kind == "conv" else (a["in_dim"], 1, 1, 1, 1, 1, 1, a["out_dim"])
 
+    @staticmethod
+    def _run_geom(a, p):
+        """the geometry a conv layer's WEIGHTS are stored for and its kernel runs on: a boxed layer (p["box"], fuse()) reports the enlarged window it computes and
+        runs its base window over the box sums of its input"""
+        bxf, byf = p.get("box") or (1, 1)
+        return dict(a, xd=a["xd"] - (bxf - 1) * a["xs"], yd=a["yd"] - (byf - 1) * a["ys"], xf=a["xf"] - (bxf - 1) * a["xs"], yf=a["yf"] - (byf - 1) * a["ys"])
+
     def planned_form(self, kind, a, B=0):
         """the kernel (weight form) crc_plan_mac picks for the layer launched on B images (0: by shape alone) -- the policy lives behind the C ABI, shared with the C++ host
         classes: reductions of at least 8 steps of 32 channels with at least 32 rows per launch -> limb GEMM (CRC_NTTL), one-channel convolutions -> their own matrix-core
@@ -491,12 +498,13 @@ class Network:
         assert not self._packed
         self._build_tilewise()
         for idx, (kind, name, a, p, ishape, oshape) in enumerate(self.plan):
-            if self.conv1_eligible(kind, a) and not p.get("streamed"):
-                nbytes = E.limb_conv1_weights_bytes_for(a["nf"], a["xf"], a["yf"])
+            ar = self._run_geom(a, p) if kind == "conv" else a
+            if self.conv1_eligible(kind, ar) and not p.get("streamed"):
+                nbytes = E.limb_conv1_weights_bytes_for(a["nf"], ar["xf"], ar["yf"])
                 wl = self.alloc(nbytes)
-                E.limb_conv1_pack_weights(p["w"], a["nf"], a["xf"], a["yf"], wl)
+                E.limb_conv1_pack_weights(p["w"], a["nf"], ar["xf"], ar["yf"], wl)
                 E.sync()
-                self.weight_bytes += nbytes - a["nf"] * a["xf"] * a["yf"] * E.k * E.n * 8
+                self.weight_bytes += nbytes - a["nf"] * ar["xf"] * ar["yf"] * E.k * E.n * 8
                 self._free(p["w"])
                 p["w"], p["w_form"] = wl, binding.NTTL1
                 continue
@@ -555,7 +563,8 @@ class Network:
             if kind not in ("conv", "fc"):
                 continue
             if p.get("w_form") not in (binding.NTTL, binding.NTTL1) and not p.get("streamed"):
-                rows = (a["nf"] * a["zd"] * a["xf"] * a["yf"] if kind == "conv" else a["in_dim"] * a["out_dim"]) * E.k
+                ar = self._run_geom(a, p) if kind == "conv" else a
+                rows = (a["nf"] * a["zd"] * ar["xf"] * ar["yf"] if kind == "conv" else a["in_dim"] * a["out_dim"]) * E.k
                 E.pack28(p["w"], rows, unpack=unpack)
                 p["w_form"] = NTT if unpack else binding.NTTP
             nxt = self.plan[idx + 1] if idx + 1 < len(self.plan) else None
@@ -592,7 +601,12 @@ class Network:
                     # resident convolution, as fused so far -- takes the stride-1 sum pool into its weights, this one keeps its window and takes the pool's stride
                     up = plan[-1] if plan and plan[-1][0] == "conv" and not plan[-1][3].get("streamed") and not plan[-1][3].get("tilewise") and plan[-1][3]["out_form"] == NTT else None
                     if E.plan_hoist_pool(self._geom("conv", up[2]) if up else None, self._geom("conv", a), (pa["xs"], pa["ys"], pa["xf"], pa["yf"]), 0, matrix_cores=self.limb):
-                        plan[-1] = self._fold_sum_pool(up, pa["xf"], pa["yf"])
+                        # ... and a one-channel layer in front sums its INPUT instead of enlarging its window (crc_plan_conv1_box): base weights, the fold's bias.  Not
+                        # behind a batch-norm layer (folded into the enlarged window's weights)
+                        ua = up[2]
+                        box = (not up[3].get("box") and not (len(plan) >= 2 and plan[-2][0] == "bn") and os.environ.get("CRC_MFMA_CONV1", "1") != "0"
+                               and E.plan_conv1_box(ua["zd"], ua["xd"], ua["yd"], ua["xs"], ua["ys"], ua["xf"], ua["yf"], ua["nf"], pa["xf"], pa["yf"], 0, matrix_cores=self.limb))
+                        plan[-1] = self._fold_sum_pool(up, pa["xf"], pa["yf"], box=box)
                         sshape = plan[-1][5]
                         cnt = a["nf"] * a["zd"] * a["xf"] * a["yf"]
                         w2 = self.alloc(cnt * E.k * E.n * 8); b2 = self.alloc(a["nf"] * E.k * E.n * 8)
@@ -627,8 +641,9 @@ class Network:
         self._pair_square_pool()
         self._fold_batchnorm()
 
-    def _fold_sum_pool(self, entry, pxf, pyf):
-        """a plan entry of a resident convolution with a (pxf x pyf, stride 1) sum pool folded into its weights: the window sums of its output, under its own name"""
+    def _fold_sum_pool(self, entry, pxf, pyf, box=False):
+        """a plan entry of a resident convolution with a (pxf x pyf, stride 1) sum pool folded into its weights: the window sums of its output, under its own name.
+        box: the layer keeps its base weights and carries the pool as a box on its input (p["box"]); only the bias is the fold's"""
         E = self.E
         kind, name, a, p, ishape, oshape = entry
         xf2, yf2 = (pxf - 1) * a["xs"] + a["xf"], (pyf - 1) * a["ys"] + a["yf"]
@@ -637,10 +652,15 @@ class Network:
         if self.materialize:
             E.conv2d_fold_pool(p["w"], p["b"], None, a["nf"], a["zd"], a["xf"], a["yf"], a["xs"], a["ys"], pxf, pyf, w2, b2)
             E.sync()
+        a2 = dict(a, xf=xf2, yf=yf2)
+        if box:
+            self.param_bufs = [(b_, n_) for (b_, n_) in self.param_bufs if b_ is not p["b"]] + [(b2, a["nf"] * E.k * E.n * 8)]
+            self._free(w2)                           # (the enlarged weights were made for the bias that comes with them)
+            p2 = dict(p, b=b2, box=(pxf, pyf), macs=layer_macs("conv", a2))
+            return (kind, name, a2, p2, ishape, (oshape[0], oshape[1] - pxf + 1, oshape[2] - pyf + 1))
         self.param_bufs = [(b_, n_) for (b_, n_) in self.param_bufs if b_ is not p["w"] and b_ is not p["b"]]
         self.param_bufs += [(w2, cnt * E.k * E.n * 8), (b2, a["nf"] * E.k * E.n * 8)]
         self.weight_bytes += (cnt - a["nf"] * a["zd"] * a["xf"] * a["yf"]) * E.k * E.n * 8
-        a2 = dict(a, xf=xf2, yf=yf2)
         p2 = dict(p, w=w2, b=b2, macs=layer_macs("conv", a2))
         return (kind, name, a2, p2, ishape, (oshape[0], oshape[1] - pxf + 1, oshape[2] - pyf + 1))
 
@@ -690,7 +710,8 @@ class Network:
         while i < len(self.plan):
             kind, name, a, p, ishape, oshape = self.plan[i]
             nxt = self.plan[i + 1] if i + 1 < len(self.plan) else None
-            if kind == "bn" and nxt and nxt[0] in ("conv", "fc") and p["form"] == NTT and nxt[3]["out_form"] == NTT and "fused" not in nxt[3] and not nxt[3].get("streamed"):
+            if (kind == "bn" and nxt and nxt[0] in ("conv", "fc") and p["form"] == NTT and nxt[3]["out_form"] == NTT and "fused" not in nxt[3] and not nxt[3].get("streamed")
+                    and not nxt[3].get("box")):
                 nk, nname, na, np_, nish, nosh = nxt
                 ch = ishape[0]
                 if nk == "conv":
@@ -815,7 +836,11 @@ class Network:
                 else:
                     work = max(work, E.conv2d_forms_work_bytes(B, g["zd"], g["xd"], g["yd"], g["xs"], g["ys"], g["xf"], g["yf"], g["ft"], p["in_form"], NTT, p["out_form"]))
                 continue
-            if kind == "conv":
+            if kind == "conv" and p.get("box"):
+                ar = self._run_geom(a, p)
+                work = max(work, E.conv2d_box_forms_work_bytes(B, a["zd"], a["xd"], a["yd"], a["xs"], a["ys"], ar["xf"], ar["yf"], a["nf"], *p["box"], p["in_form"],
+                                                               p.get("w_form", NTT), p["out_form"]))
+            elif kind == "conv":
                 work = max(work, E.conv2d_forms_work_bytes(B, a["zd"], a["xd"], a["yd"], a["xs"], a["ys"], a["xf"], a["yf"], a["nf"], p["in_form"], p.get("w_form", NTT), p["out_form"]))
             elif kind == "fc":
                 work = max(work, E.conv2d_forms_work_bytes(B, a["in_dim"], 1, 1, 1, 1, 1, 1, a["out_dim"], p["in_form"], p.get("w_form", NTT), p["out_form"]))
@@ -1006,6 +1031,11 @@ class Network:
                 timer(i, name, kind, 0)
             if p.get("streamed"):
                 self._forward_streamed(kind, a, p, cur, B, out)
+                cur = out
+            elif kind == "conv" and p.get("box"):
+                ar = self._run_geom(a, p)
+                E.conv2d_box(cur, p["w"], p["b"], B, a["zd"], a["xd"], a["yd"], a["xs"], a["ys"], ar["xf"], ar["yf"], a["nf"], *p["box"], p["in_form"], p["out_form"], out,
+                             self.work, w_form=p.get("w_form", NTT))
                 cur = out
             elif kind == "conv":
                 E.conv2d(cur, p["w"], p["b"], B, a["zd"], a["xd"], a["yd"], a["xs"], a["ys"], a["xf"], a["yf"], a["nf"], p["in_form"], p["out_form"], out, self.work,

@@ -115,7 +115,7 @@ int  crc_ctx_table(const crc_ctx *ctx, const char *name, uint64_t *h_out, int ca
 /* Tuning switches of tools/ and the tests (none is needed for normal use).  The engine reads its environment (CRC_MFMA_VARIANT, CRC_CONV1_PASS_BYTES, ...)
  * exactly
  * once, inside crc_ctx_create; this call changes one switch of a context nobody is launching on: "mfma_variant", "mfma_order", "mfma_ring", "conv1_waves",
- * "conv1_narrow" (0: a one-channel convolution with 17-20 filters runs its second filter group like a full one), "conv1_pass_bytes", "limb_pack_group", "mac2_cfg", "mac_order", "mac_regstage", "ntt_inv61_loose", "ntt_split", "mfma_min_steps", "scalar_mac" (crc_plan_mac_scalar), "f64_radix",
+ * "conv1_narrow" (0: a one-channel convolution with 17-20 filters runs its second filter group like a full one), "conv1_pass_bytes", "conv1_box" (crc_plan_conv1_box), "hoist_pool" (crc_plan_hoist_pool), "limb_pack_group", "mac2_cfg", "mac_order", "mac_regstage", "ntt_inv61_loose", "ntt_split", "mfma_min_steps", "scalar_mac" (crc_plan_mac_scalar), "f64_radix",
  * "relin_mac_ct", "poly_tail" (crc_poly2_relin_forms),
  * "relin_path" (1: key switching over the coefficient moduli, as the reference does it, instead of over two fp64 primes), "sq_path" (1: the square's auxiliary
  * base is SEAL's 61-bit
@@ -305,6 +305,22 @@ int    crc_plan_mac_scalar(const crc_ctx *ctx, int zd, int xd, int yd, int xs, i
 int    crc_plan_fold_pool(const crc_ctx *ctx, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int pxs, int pys, int pxf, int pyf, int *fold);
 int    crc_plan_hoist_pool(const crc_ctx *ctx, int uzd, int uxd, int uyd, int uxs, int uys, int uxf, int uyf, int unf, int zd, int xd, int yd, int xs, int ys,
                            int xf, int yf, int nf, int pxs, int pys, int pxf, int pyf, int B, int matrix_cores, int *hoist);
+/* The box of a one-channel convolution (CRC_NTTL1): the layer reads the bxf x byf WINDOW SUMS of its input, taken at its own stride (xs, ys) by the image pack --
+ * conv_W(box x) = conv_{W * box}(x) over Z_q, so the upstream layer of a hoisted pair keeps its base window W instead of the enlarged one.  (xd, yd) is the full
+ * image, (xf, yf) the BASE window; the result has ((xd - (bxf-1) xs - xf) / xs + 1) x ((yd - (byf-1) ys - yf) / ys + 1) positions; the bias is the caller's (a
+ * folded sum pool's is bxf byf b).
+ *   crc_limb_conv1_box_supported    pure host query, 0 / 1: the base window takes the pixel-major form of the kernel (at most 40 taps, not 17-20 filters), bxf byf
+ *                                   <= 9, and the summed image is a shape crc_limb_conv1_supported accepts
+ *   crc_conv2d_box_forms[_work_bytes]  crc_conv2d_forms' arguments plus the box; w_form must be CRC_NTTL1 (weights: crc_limb_conv1_pack_weights of the base
+ *                                   window) unless the box is 1 x 1, which IS crc_conv2d_forms.  CRC_ERR_UNSUPPORTED (work bytes: 0) where the query says 0
+ *   crc_plan_conv1_box              does the box execution cost less than the enlarged window (crc_plan_hoist_pool's units, plus the pack's extra reads)?  No where
+ *                                   the query says 0, with matrix_cores = 0, and under the tuning key conv1_box = 0 / CRC_CONV1_BOX=0 */
+int    crc_limb_conv1_box_supported(const crc_ctx *ctx, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int bxf, int byf);
+size_t crc_conv2d_box_forms_work_bytes(const crc_ctx *ctx, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int bxf, int byf, int in_form,
+                                       int w_form, int out_form);
+int    crc_conv2d_box_forms(crc_ctx *ctx, const uint64_t *d_x, const uint64_t *d_w, int w_form, const uint64_t *d_bias_delta, int B, int zd, int xd, int yd,
+                            int xs, int ys, int xf, int yf, int nf, int bxf, int byf, int in_form, int out_form, uint64_t *d_y, void *d_work, void *stream);
+int    crc_plan_conv1_box(const crc_ctx *ctx, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int bxf, int byf, int B, int matrix_cores, int *box);
 /* an NTT-form tensor (CRC_NTT canonical or CRC_NTTP) -> limb form; crc_conv2d_forms does this itself for such inputs, the separate entry point lets a
  * caller convert once and reuse (d_xl: crc_limb_tensor_bytes) */
 int    crc_limb_pack_tensor(crc_ctx *ctx, const uint64_t *d_x, int in_form, int B, int zd, int xd, int yd, void *d_xl, void *stream);
