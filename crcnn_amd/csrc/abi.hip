@@ -575,11 +575,13 @@ extern "C" int crc_plan_hoist_pool(const crc_ctx *c, int uzd, int uxd, int uyd, 
 // Should a one-channel convolution whose weights are its base window W (xf x yf) convolved with a bxf x byf sum at its own stride -- the upstream layer of a hoisted
 // pair (crc_plan_hoist_pool) -- sum its INPUT instead (crc_conv2d_box_forms) and keep W?  conv_{W * box}(x) = conv_W(box x): exact over Z_q.  Yes when the base
 // window runs on the pixel-major one-channel kernel, the summed image fits it, and the box execution costs less than the enlarged window in plan_mac_cost's units.
-// The box's own cost is the image pack's extra reads: bxf byf - 1 further loads per pixel and poly of the summed image, PLAN_BOX_READ units each -- measured, not
-// derived: PlainModelTiny at n = 4096, 128 images per launch, the pack 12.0 ms with the 2 x 2 box against 6.4 ms x 26^2 / 28^2 = 5.5 ms without one, 6.5 ms for
-// 26 x 26 x 2 x 3 reads, at the limb GEMM's 77 ns per unit (profiles/conv1_box_ab.txt): the re-reads miss L1 and are served by L2 / the memory-side cache, they are
-// not free.  The tuning key conv1_box = 0 (CRC_CONV1_BOX=0) answers no throughout.
-#define PLAN_BOX_READ 21
+// The box's own cost is what the image pack takes on top of packing the summed image alone, written as PLAN_BOX_READ units per further term (bxf byf - 1 per
+// pixel and poly of the summed image) -- measured, not derived: PlainModelTiny at n = 4096, 128 images per launch, the staged pack (kernels_mfma1.hip
+// limb_pack_box_kernel_px: every input loaded once into a ring in LDS) 8.67 ms with the 2 x 2 box against 5.67 ms x 26^2 / 28^2 = 4.89 ms without one, 3.78 ms for
+// 26 x 26 x 2 x 3 terms, at the limb GEMM's 75.2 ns per unit (90.56 ms / 1 204 224 units in the same job: profiles/conv1_box_staged_ab.txt) = 12.4.  (The direct
+// form, which re-read every term from L2, was 21.)  What is left is no longer re-reading: the pass reads 28 x 28 inputs to write 26 x 26 pixels, holds 68.5 KiB of
+// LDS (two workgroups per CU) and has two barriers per row group.  The tuning key conv1_box = 0 (CRC_CONV1_BOX=0) answers no throughout.
+#define PLAN_BOX_READ 12
 extern "C" int crc_plan_conv1_box(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int bxf, int byf, int B, int matrix_cores,
                                   int *box)
 {

@@ -29,6 +29,7 @@
 // and 7 diagonals per tile, no window cutting, one fold).  k_limb_conv1_form picks per layer; the tuning key conv1_form forces one.
 #include "kernels.h"
 #include "limbred.h"
+#include "boxstage.h"
 #include <cstdlib>
 
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -451,14 +452,11 @@ __global__ void __launch_bounds__(256) limb_pack_rows1_kernel(const u64 *x, i8 *
 // Box (bxf x byf, default 1 x 1): the packed image is the WINDOW SUM of the input at the layer's stride, pixel (r, c) = sum over a < bxf, b < byf of
 // x(r + a xs, c + b ys) mod q, xdo x ydo = (xd - (bxf-1) xs) x (yd - (byf-1) ys) pixels -- a sum pool behind the convolution, moved in front of it (the layer is
 // shift-equivariant: DESIGN.md section 4.5).  The sum is taken on canonical residues (after the 28-bit unpack) and reduced once (limbred.h sum_reduce16: bxf byf <=
-// 9 terms below 2^55).  Halo: a thread reads every term of its 16 pixels itself -- bxf byf loads per pixel, the same coalesced 256-byte segment per (row, column) and
-// 32 slots as without a box -- and nothing more is staged in LDS, so the staging area stays at 27 KiB = five workgroups per CU and there is one barrier.  The terms
-// of one pixel are other pixels' terms too (the same thread two columns on, the thread two rows on, the next row group's workgroup on the same XCD), and the choice
-// counted on those re-reads being L1 / L2 hits.  MEASURED (profiles/conv1_box_ab.txt, PlainModelTiny at n = 4096, 128 images): they are not L1 hits -- five
-// workgroups per CU each walk 6 rows x 28 columns x 256 bytes, more than the 32 KiB L1 -- and the pass takes 12.0 ms with the 2 x 2 box against 5.5 ms for the
-// same output without one: the three further reads per pixel cost 6.5 ms, served by L2 and the memory-side cache.  The layer still gains (kernel + pack 44.5 ->
-// 38.4 ms), so the simple form stays; the form that reads every input once per workgroup -- row sums of RG + (bxf-1) xs rows staged in LDS as 8-byte residues, 41
-// KiB: three workgroups per CU, a second barrier -- is the open step.
+// 9 terms below 2^55).  BOX = true is the DIRECT form: a thread reads every term of its 16 pixels itself -- bxf byf loads per pixel, the same coalesced 256-byte
+// segment per (row, column) and 32 slots as without a box, nothing more staged in LDS.  The re-reads are not L1 hits (five workgroups per CU each walk 6 rows x 28
+// columns x 256 bytes, more than the 32 KiB L1): 11.9 ms for PlainModelTiny's 2 x 2 box at n = 4096, 128 images, against 5.7-6.0 ms for the 28 x 28 image without
+// one.  The launcher takes this form only for a box whose ring does not fit the LDS (boxstage.h box_staged: tall boxes at stride 2-3 on wide images); every
+// other box runs limb_pack_box_kernel_px below, which loads every input once (8.7 ms: profiles/conv1_box_staged_ab.txt).
 // (BOX = false: no box -- the body every unboxed layer ran before the pass could take one)
 template <bool BOX>
 __global__ void __launch_bounds__(256) limb_pack_rows1_kernel_px(const u64 *x, i8 *xr, const ModParams *mods, int n, int k, int B, int xd, int yd, int packed,
@@ -524,6 +522,83 @@ __global__ void __launch_bounds__(256) limb_pack_rows1_kernel_px(const u64 *x, i
         if (part >= valid) continue;
         i8 *dst = xr + (((size_t)i * n + s0 + sl) * B + b) * img_stride + (size_t)c * poly_bytes + (size_t)(rg * RG) * rs + part * 16;
         *reinterpret_cast<uint4 *>(dst) = *reinterpret_cast<const uint4 *>(stp + (size_t)sl * sstride + part * 16);
+    }
+}
+// The staged box (boxstage.h has the index arithmetic, tests/cpp/box_stage_check.cpp walks it on the CPU): the same image, byte for byte, with every input
+// residue loaded from global memory ONCE per walk.  A workgroup = 32 slots x (modulus, image, poly) x a walk of row groups (gridDim.x decides: one group per
+// workgroup, or the whole image).  Per group: (1) the 256 threads = 8 segment rows of 32 slots load the input pixels that are new -- BOX_LD independent loads
+// per thread in flight, each the coalesced 256-byte segment of (row, column, 32 slots) -- unpack them and put the canonical residues into the ring
+// [pixel mod ring_px][slot]; barrier; (2) thread (slot, row of the group, 16-column half) sums the bxf byf terms of its 16 pixels from the ring, reduces once,
+// cuts digits and stages them as the unboxed pass does; barrier; (3) the 32-slot transpose and the 16-byte stores of the unboxed pass.  The next group's loads
+// overwrite only rows this group's sums (before the second barrier) were the last to need, and its staging follows its own first barrier, after these stores.
+#define BOX_LD 16
+static_assert(BOX_RG == RG && BOX_RSL == RSL, "boxstage.h describes this pack's workgroup");
+__global__ void __launch_bounds__(256) limb_pack_box_kernel_px(const u64 *x, i8 *xr, const ModParams *mods, int n, int k, int B, int xd, int yd, int packed,
+                                                               unsigned img_stride, unsigned poly_bytes, unsigned rs, int xdo, int ydo, int bxf, int byf, int xs,
+                                                               int ys)
+{
+    extern __shared__ __attribute__((aligned(16))) i8 stp[];
+    u64 *ring = reinterpret_cast<u64 *>(stp);
+    i8 *dig = stp + box_ring_bytes(yd, bxf, xs);
+    const unsigned sstride = RG * rs + 16;
+    const int sblocks = n / RSL;
+    const int sb = blockIdx.x % (sblocks * k), i = sb / sblocks, s0 = (sb % sblocks) * RSL;
+    const int wpi = (int)(gridDim.x / (unsigned)(sblocks * k * 2 * B));                // workgroups per (image, poly)
+    size_t r = blockIdx.x / (sblocks * k);                       // (b*2 + c)*wpi + walk
+    const int w = (int)(r % wpi); r /= wpi; const int c = (int)(r % 2); const int b = (int)(r / 2);
+    const u64 q = mods[i].q;
+    const int lane = threadIdx.x & (RSL - 1), seg = threadIdx.x >> 5, qrow = seg & (RG - 1), h = threadIdx.x >> 7;
+    const u32 ring_px = box_ring_px(yd, bxf, xs);
+    const size_t cs = (size_t)2 * k * n;                             // words between neighbouring pixels of a row, and between a row's last and the next row's first
+    const u64 *src = x + (((size_t)b * xd * yd * 2 + c) * k + i) * (size_t)n + s0 + lane;
+    const int g0 = box_walk_first(w, xdo, wpi), g1 = box_walk_end(w, xdo, wpi);
+    for (int g = g0; g < g1; g++) {
+        const int p1 = box_load_end(g, xd, yd, bxf, xs);
+        for (int pb = box_load_first(g, g == g0, xd, yd, bxf, xs) + seg; pb < p1; pb += 8 * BOX_LD) {
+            u64 v[BOX_LD];
+#pragma unroll
+            for (int u = 0; u < BOX_LD; u++) v[u] = pb + 8 * u < p1 ? src[(size_t)(pb + 8 * u) * cs] : 0;
+#pragma unroll
+            for (int u = 0; u < BOX_LD; u++)
+                if (pb + 8 * u < p1) {
+                    u64 t = v[u];
+                    if (packed) t = (t & 0xffffffffULL) | ((t >> 32) << 28);
+                    ring[box_cell((u32)(pb + 8 * u), ring_px, lane)] = t;
+                }
+        }
+        __syncthreads();
+        const int row = g * RG + qrow;
+        if (row < xdo) {
+            u64 sum[16];
+#pragma unroll
+            for (int colx = 0; colx < 16; colx++) sum[colx] = 0;
+            for (int a = 0; a < bxf; a++)
+                for (int bb = 0; bb < byf; bb++) {
+                    u32 pos = box_ring_pos(box_term_px(row, box_col(h, 0), a, bb, xs, ys, yd), ring_px);
+#pragma unroll
+                    for (int colx = 0; colx < 16; colx++) {
+                        if (box_col(h, colx) < ydo) sum[colx] += ring[box_pos_cell(pos, lane)];
+                        pos = box_ring_step(pos, 1, ring_px);
+                    }
+                }
+            u64 *sp = reinterpret_cast<u64 *>(dig + (size_t)lane * sstride + qrow * rs) + h * 16;
+#pragma unroll
+            for (int colx = 0; colx < 16; colx++) {
+                const int col = box_col(h, colx);
+                if ((unsigned)col * 8 >= rs) continue;
+                // (a column past ydo: the padding of an odd width)
+                sp[colx] = col < ydo ? balanced_digit_bytes(sum_reduce16(sum[colx], q), q) : 0;
+            }
+        }
+        __syncthreads();
+        // RSL runs of RG * rs bytes, 16 bytes per lane (rows past xdo of a ragged last group are not stored)
+        const int per_run = RG * rs / 16, valid = box_rows_here(g, xdo) * (int)rs / 16;
+        for (int o = threadIdx.x; o < RSL * per_run; o += 256) {
+            const int sl = o / per_run, part = o - sl * per_run;
+            if (part >= valid) continue;
+            i8 *dst = xr + (((size_t)i * n + s0 + sl) * B + b) * img_stride + (size_t)c * poly_bytes + (size_t)(g * RG) * rs + part * 16;
+            *reinterpret_cast<uint4 *>(dst) = *reinterpret_cast<const uint4 *>(dig + (size_t)sl * sstride + part * 16);
+        }
     }
 }
 // NTT-form weights w [F][1][xf][yf][k][n] -> Wl1 [slot][7 planes][32 filters][64 taps], tap = kx*8 + ky (pre-zeroed).  (No 2^64 factor since round 4: the
@@ -662,7 +737,14 @@ int k_limb_conv1(crc_ctx *c, const u64 *x, bool packed, i8 *xr, const i8 *wl, u6
         a.px_rs = conv1_px_rs(yd); a.poly_bytes = conv1_px_poly_bytes(xd, yd); a.img_stride = conv1_px_img_stride(xd, yd);
         a.px_taps = xf * yf; a.px_yf = yf;
         a.px_pair = yf % 2 == 0 && ys_ % 2 == 0 ? 1 : 0;
-        if (bxf * byf > 1)
+        if (bxf * byf > 1 && box_staged(yd_in, bxf, xs, a.px_rs)) {
+            // the staged box, one workgroup per (32 slots, modulus, image, poly) walking the whole image: every input residue is loaded once
+            const size_t lds = box_lds_bytes(yd_in, bxf, xs, a.px_rs);
+            const int wpi = 1;                                          // (box_row_groups(xd): one row group per workgroup, the halo read 1.5 x: 10.2 ms against 8.7)
+            { const int rc = crc_ctx_ensure_lds(c, (const void *)limb_pack_box_kernel_px, lds); if (rc) return rc; }
+            hipLaunchKernelGGL(limb_pack_box_kernel_px, dim3((unsigned)((size_t)(c->n / RSL) * c->k * B * 2 * wpi)), dim3(256), lds, st, x, xr, c->d_mods, c->n,
+                c->k, B, xd_in, yd_in, packed ? 1 : 0, a.img_stride, a.poly_bytes, a.px_rs, xd, yd, bxf, byf, xs, ys_);
+        } else if (bxf * byf > 1)                                   // a ring past the LDS of a CU (a 9 x 1 box at stride 3 on a wide image): every term read directly
             hipLaunchKernelGGL(limb_pack_rows1_kernel_px<true>, dim3((unsigned)pack_blocks), dim3(256), RSL * (RG * a.px_rs + 16), st, x, xr, c->d_mods, c->n, c->k,
                 B, xd_in, yd_in, packed ? 1 : 0, a.img_stride, a.poly_bytes, a.px_rs, xd, yd, bxf, byf, xs, ys_);
         else

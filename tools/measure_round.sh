@@ -13,7 +13,7 @@ if [ $P = all ] || [ $P = prof ]; then
 K=/tmp/crc_keep; rm -rf $K; mkdir -p $K
 CRC_BENCH_KEEP=$K timeout -k 10 400 python bench.py --also approx8192 --cpu-seconds 0 --batch 256 --also-batch 96 --also-steps 1 --full > $O/prof_prepare.json 2> $O/prof_prepare.err
 for cfg in tiny4096 approx8192; do
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$cfg -o $cfg -- $(cat $K/$cfg/cmd.txt) > $O/prof_$cfg.log 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$cfg -o $cfg -- $(cat $K/$cfg/cmd_$cfg.txt) > $O/prof_$cfg.log 2>&1
 done
 rm -rf $K
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_sq -o sq -- python3 tools/bench_square.py 8192 3 1250 > $O/prof_sq.log 2>&1
