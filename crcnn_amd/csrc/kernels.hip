@@ -603,6 +603,7 @@ static int ntt_launch(crc_ctx *c, bool inv, NttArgs &a, size_t rows, hipStream_t
     a.w = reinterpret_cast<const ulonglong2 *>(inv ? c->d_irp2 : c->d_rp);
     int nt = c->n / 8; if (nt < 64) nt = 64; if (nt > 1024) nt = 1024;
     size_t lds = (size_t)c->n * 8;
+    if (lds > 128 * 1024) return CRC_ERR_UNSUPPORTED;                   // (n = 32768: the row does not fit one workgroup's LDS image, in halves or whole)
     // lazy butterflies need (1 + 4 log2 n) q < 2^64 (and the float quotient estimate a q of 45+ bits): every coefficient modulus of the
     // reference's parameter sets qualifies (54..55 bits), the 61-bit auxiliary base of Square does not
     bool lazy = true;
