@@ -669,6 +669,15 @@ static shared_ptr<DeviceBuffer> &ensure(shared_ptr<DeviceBuffer> &b, size_t byte
     if (!b || b->bytes < bytes) b = make_shared<DeviceBuffer>(bytes);
     return b;
 }
+// a form-preserving layer's output converted to the form the network asked for: CRC_COEFF <-> CRC_NTT, nothing when the tensor is in it already
+static void toForm(ciphertext3D &t, int form, const char *who)
+{
+    if (t.form == form) return;
+    if (t.form == CRC_COEFF && form == CRC_NTT) chk(crc_ntt_fwd(ctx(), t.data(), t.count(), 2, stream()), "crc_ntt_fwd");
+    else if (t.form == CRC_NTT && form == CRC_COEFF) chk(crc_ntt_inv(ctx(), t.data(), t.count(), 2, stream()), "crc_ntt_inv");
+    else throw invalid_argument(string(who) + ": cannot convert form " + to_string(t.form) + " to out_form " + to_string(form) + " (CRC_COEFF and CRC_NTT only)");
+    t.form = form;
+}
 
 // The client-side refresh of network.cpp:30-34 -- `floatCube image = decryptImage(input); input = encryptImage(image);` -- for a whole batch on the launch
 // stream (crc_refresh_dev: decrypt, decode, round to float, encode, encrypt; nothing crosses PCIe and the host does not wait).  Passes of bounded size share the
@@ -1235,11 +1244,7 @@ ciphertext3D PoolingLayer::forward(ciphertext3D input)
     ciphertext3D out(input.B, zo, xo, yo, input.form);
     chk(crc_pool(ctx(), input.data(), input.B, zd, xd, yd, xs, ys, xf, yf, d_div ? (const uint64_t *)d_div->ptr : nullptr, input.form, out.data(), stream()),
         "crc_pool");
-    if (out_form != out.form) {      // pooling is form-preserving; convert only if the network asked for the other form
-        if (out_form == CRC_NTT) chk(crc_ntt_fwd(ctx(), out.data(), out.count(), 2, stream()), "crc_ntt_fwd");
-            else chk(crc_ntt_inv(ctx(), out.data(), out.count(), 2, stream()), "crc_ntt_inv");
-        out.form = out_form;
-    }
+    toForm(out, out_form, "PoolingLayer");          // pooling is form-preserving
     return out;
 }
 void PoolingLayer::printLayerStructure()
@@ -1267,12 +1272,7 @@ ciphertext3D PaddingLayer::forward(ciphertext3D input)
     if (input.form != CRC_COEFF && input.form != CRC_NTT) throw invalid_argument("PaddingLayer: input must be in CRC_COEFF or CRC_NTT form");
     ciphertext3D out(input.B, zo, xo, yo, input.form);
     chk(crc_pad(ctx(), input.data(), input.B, zd, xd, yd, px, px, py, py, input.form, out.data(), stream()), "crc_pad");
-    if (out_form != out.form) {      // padding is form-preserving; convert only if the network asked for the other form
-        if (out_form == CRC_NTT) chk(crc_ntt_fwd(ctx(), out.data(), out.count(), 2, stream()), "crc_ntt_fwd");
-            else if (out_form == CRC_COEFF) chk(crc_ntt_inv(ctx(), out.data(), out.count(), 2, stream()), "crc_ntt_inv");
-            else throw invalid_argument("PaddingLayer: out_form must be CRC_NTT or CRC_COEFF");
-        out.form = out_form;
-    }
+    toForm(out, out_form, "PaddingLayer");          // padding is form-preserving
     return out;
 }
 void PaddingLayer::printLayerStructure()
@@ -1281,50 +1281,28 @@ void PaddingLayer::printLayerStructure()
          << ")" << endl;
 }
 
-// ---- Square -----------------------------------------------------------------------------------------------------------
-ciphertext3D SquareLayer::forward(ciphertext3D input)
-{
-    if (!input.buf) throw invalid_argument("SquareLayer: empty input");
-    if (!ev_keys16) throw invalid_argument("not enough evaluation keys");
-    // either form in, the requested form out: crc_square_relin_forms keeps an NTT-resident network resident
-    ciphertext3D out(input.B, input.zd, input.xd, input.yd, out_form);
-    ensure(g_scratch, crc_square_relin_work_bytes(ctx(), input.count(), 16));
-    chk(crc_square_relin_forms(ctx(), input.data(), input.form, input.count(), (const uint64_t *)ev_keys16->ptr, 16, out.data(), out_form, g_scratch->ptr,
-        stream()),
-        "crc_square_relin_forms");
-    return out;
-}
-void SquareLayer::printLayerStructure() { cerr << "Square run with " << th_count << " threads" << endl; }
-
-// ---- Square + pooling (Network::fuse) ---------------------------------------------------------------------------------
-SquarePoolLayer::SquarePoolLayer(string name, int xd, int yd, int zd, int xs, int ys, int xf, int yf, int th_count, shared_ptr<DeviceBuffer> d_div)
-    : Layer(name), xd(xd), yd(yd), zd(zd), xs(xs), ys(ys), xf(xf), yf(yf), xo((xd - xf) / xs + 1), yo((yd - yf) / ys + 1), zo(zd), th_count(th_count),
+// ---- ActivationLayer: what the five activation layers share -----------------------------------------------------------------------------------
+ActivationLayer::ActivationLayer(string name, const char *kind, int th_count, int xd, int yd, int zd, int xs, int ys, int xf, int yf, shared_ptr<DeviceBuffer> d_div)
+    : Layer(name), xd(xd), yd(yd), zd(zd), xs(xs), ys(ys), xf(xf), yf(yf), xo((xd - xf) / xs + 1), yo((yd - yf) / ys + 1), zo(zd), th_count(th_count), kind(kind),
         d_div(d_div) {}
-ciphertext3D SquarePoolLayer::forward(ciphertext3D input)
+size_t ActivationLayer::deviceBytes() const { size_t b = bytesOf(d_div); for (auto &r : d_p) b += bytesOf(r); return b; }
+ciphertext3D ActivationLayer::begin(const ciphertext3D &input, int form)
 {
-    checkInput(input, zd, xd, yd, "SquarePoolLayer");
-    if (!ev_keys16) throw invalid_argument("not enough evaluation keys");
-    // an average pooling's divisor multiplies slot-wise: the pooled tensor is made NTT-resident for it, and brought back to coefficients when the network asked
-    // for those.  The packed / limb operand forms are not produced here (Network::forward never asks this layer for them)
-    if (out_form != CRC_NTT && out_form != CRC_COEFF) throw invalid_argument("SquarePoolLayer: out_form must be CRC_NTT or CRC_COEFF");
-    const int of = d_div ? CRC_NTT : out_form;
-    ciphertext3D out(input.B, zo, xo, yo, of);
-    ensure(g_scratch, crc_square_pool_relin_work_bytes(ctx(), input.B, zd, xd, yd, xs, ys, xf, yf, 16));
-    chk(crc_square_pool_relin_forms(ctx(), input.data(), input.form, input.B, zd, xd, yd, xs, ys, xf, yf, (const uint64_t *)ev_keys16->ptr, 16,
-                                    d_div ? (const uint64_t *)d_div->ptr : nullptr, out.data(), of, g_scratch->ptr, stream()), "crc_square_pool_relin_forms");
-    if (of != out_form) { chk(crc_ntt_inv(ctx(), out.data(), out.count(), 2, stream()), "crc_ntt_inv"); out.form = out_form; }
-    return out;
+    if (!input.buf || (pooled() && (input.zd != zd || input.xd != xd || input.yd != yd)))
+        throw invalid_argument(string(kind) + ": the input tensor is empty or its shape does not match the layer");
+    if (!ev_keys16) throw invalid_argument(string(kind) + ": not enough evaluation keys");
+    // the packed / limb operand forms are not produced here (Network::forward never asks an activation layer for them)
+    if (out_form != CRC_NTT && out_form != CRC_COEFF) throw invalid_argument(string(kind) + ": out_form must be CRC_NTT or CRC_COEFF");
+    if (!uploaded) { rows(); uploaded = true; }
+    return pooled() ? ciphertext3D(input.B, zo, xo, yo, form) : ciphertext3D(input.B, input.zd, input.xd, input.yd, form);
 }
-void SquarePoolLayer::printLayerStructure()
-{
-    cerr << "Square + Pooling " << name << " : input (" << zd << "," << xd << "," << yd << "); kernel(" << xf << "," << yf << "); stride(" << xs << "," <<
-        ys << "); output(" << zo << "," << xo << ","
-         << yo << "); one key switch per pooled ciphertext" << endl;
-}
-
-// ---- polynomial activation ------------------------------------------------------------------------------------------------
-// the three NTT-form rows crc_poly2_*_relin_forms take (empty = 1, 0, 0), with the window count and the divisor of a pooling behind the activation folded in
-static void polyRows(float c2, float c1, float c0, int window, const shared_ptr<DeviceBuffer> &d_div, shared_ptr<DeviceBuffer> out[3], const double *sc)
+void *ActivationLayer::scratch(size_t bytes) const { return ensure(g_scratch, bytes)->ptr; }
+static const uint64_t *evk16() { return (const uint64_t *)ev_keys16->ptr; }
+static const uint64_t *rowPtr(const shared_ptr<DeviceBuffer> &b) { return b ? (const uint64_t *)b->ptr : nullptr; }
+// one coefficient encoded (at `scale` under slot encoding) and uploaded as its NTT-form row: mode 0 the plaintext itself (a factor), mode 2 Delta times it (a summand)
+static shared_ptr<DeviceBuffer> coeffRow(float c, double scale, int mode) { const Plaintext p = encodeScaled((double)c, scale); return uploadPlain({&p}, mode); }
+// the three rows crc_poly2_*_relin_forms take (empty = 1, 0, 0), with the window count and the divisor of a pooling behind the activation folded in
+void ActivationLayer::poly2Rows(float c2, float c1, float c0, const double *sc)
 {
     const size_t rowb = (size_t)K() * N() * 8;
     auto copyOf = [&](const shared_ptr<DeviceBuffer> &src) {
@@ -1335,16 +1313,14 @@ static void polyRows(float c2, float c1, float c0, int window, const shared_ptr<
     auto timesDiv = [&](const shared_ptr<DeviceBuffer> &r) {
         if (d_div) chk(crc_multiply_plain_ntt(ctx(), (uint64_t *)r->ptr, (const uint64_t *)d_div->ptr, 1, 1, 1, stream()), "crc_multiply_plain_ntt");
     };
-    out[0].reset(); out[1].reset(); out[2].reset();
-    if (c2 != 1.0f || sc[0] != 0) { const Plaintext p = encodeScaled((double)c2, sc[0]); out[0] = uploadPlain({&p}, 0); timesDiv(out[0]); }    // (a scaled 1 is not 1)
-    else if (d_div) out[0] = copyOf(d_div);
-    if (c1 != 0.0f) { const Plaintext p = encodeScaled((double)c1, sc[1]); out[1] = uploadPlain({&p}, 0); timesDiv(out[1]); }
+    if (c2 != 1.0f || sc[0] != 0) { d_p[0] = coeffRow(c2, sc[0], 0); timesDiv(d_p[0]); }                    // (a scaled 1 is not 1)
+    else if (d_div) d_p[0] = copyOf(d_div);
+    if (c1 != 0.0f) { d_p[1] = coeffRow(c1, sc[1], 0); timesDiv(d_p[1]); }
     if (c0 != 0.0f) {
-        const Plaintext p = encodeScaled((double)c0, sc[2]);
-        const shared_ptr<DeviceBuffer> one = uploadPlain({&p}, 2);
-        out[2] = copyOf(one);
-        for (int w = 1; w < window; w++) chk(crc_add(ctx(), (uint64_t *)out[2]->ptr, (const uint64_t *)one->ptr, 1, 1, stream()), "crc_add");
-        timesDiv(out[2]);
+        const shared_ptr<DeviceBuffer> one = coeffRow(c0, sc[2], 2);
+        d_p[2] = copyOf(one);
+        for (int w = 1; w < (pooled() ? xf * yf : 1); w++) chk(crc_add(ctx(), (uint64_t *)d_p[2]->ptr, (const uint64_t *)one->ptr, 1, 1, stream()), "crc_add");
+        timesDiv(d_p[2]);
     }
     chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
 }
@@ -1353,22 +1329,44 @@ static void polyCheck(const string &what, float c2, float c1, float c0)
     if (!isfinite(c2) || !isfinite(c1) || !isfinite(c0)) throw invalid_argument(what + ": the coefficients must be finite");
     if (c2 == 0.0f) throw invalid_argument(what + ": c2 must not be zero (a polynomial without its square term is a batch norm, not an activation)");
 }
-static const uint64_t *rowPtr(const shared_ptr<DeviceBuffer> &b) { return b ? (const uint64_t *)b->ptr : nullptr; }
-PolyLayer::PolyLayer(string name, float c2, float c1, float c0, int th_count) : Layer(name), c2(c2), c1(c1), c0(c0), th_count(th_count)
+
+// ---- Square -----------------------------------------------------------------------------------------------------------
+ciphertext3D SquareLayer::forward(ciphertext3D input)
 {
-    polyCheck("PolyLayer", c2, c1, c0);
+    // either form in, the requested form out: crc_square_relin_forms keeps an NTT-resident network resident
+    ciphertext3D out = begin(input, out_form);
+    chk(crc_square_relin_forms(ctx(), input.data(), input.form, input.count(), evk16(), 16, out.data(), out_form,
+                               scratch(crc_square_relin_work_bytes(ctx(), input.count(), 16)), stream()), "crc_square_relin_forms");
+    return out;
 }
-size_t PolyLayer::deviceBytes() const { size_t b = 0; for (auto &r : d_p) if (r) b += r->bytes; return b; }
+void SquareLayer::printLayerStructure() { cerr << "Square run with " << th_count << " threads" << endl; }
+
+// ---- Square + pooling (Network::fuse) ---------------------------------------------------------------------------------
+ciphertext3D SquarePoolLayer::forward(ciphertext3D input)
+{
+    // an average pooling's divisor multiplies slot-wise: the pooled tensor is made NTT-resident for it, and brought back to coefficients when the network asked
+    // for those
+    const int of = d_div ? CRC_NTT : out_form;
+    ciphertext3D out = begin(input, of);
+    chk(crc_square_pool_relin_forms(ctx(), input.data(), input.form, input.B, zd, xd, yd, xs, ys, xf, yf, evk16(), 16, rowPtr(d_div), out.data(), of,
+                                    scratch(crc_square_pool_relin_work_bytes(ctx(), input.B, zd, xd, yd, xs, ys, xf, yf, 16)), stream()), "crc_square_pool_relin_forms");
+    toForm(out, out_form, kind);
+    return out;
+}
+void SquarePoolLayer::printLayerStructure()
+{
+    cerr << "Square + Pooling " << name << " : input (" << zd << "," << xd << "," << yd << "); kernel(" << xf << "," << yf << "); stride(" << xs << "," <<
+        ys << "); output(" << zo << "," << xo << "," << yo << "); one key switch per pooled ciphertext" << endl;
+}
+
+// ---- polynomial activation ------------------------------------------------------------------------------------------------
+PolyLayer::PolyLayer(string name, float c2, float c1, float c0, int th_count) : ActivationLayer(name, "PolyLayer", th_count), c2(c2), c1(c1), c0(c0)
+    { polyCheck(kind, c2, c1, c0); }
 ciphertext3D PolyLayer::forward(ciphertext3D input)
 {
-    if (!input.buf) throw invalid_argument("PolyLayer: empty input");
-    if (!ev_keys16) throw invalid_argument("not enough evaluation keys");
-    if (out_form != CRC_NTT && out_form != CRC_COEFF) throw invalid_argument("PolyLayer: out_form must be CRC_NTT or CRC_COEFF");
-    if (!uploaded) { polyRows(c2, c1, c0, 1, nullptr, d_p, slot_scale); uploaded = true; }
-    ciphertext3D out(input.B, input.zd, input.xd, input.yd, out_form);
-    ensure(g_scratch, crc_poly2_relin_work_bytes(ctx(), input.count(), 16));
-    chk(crc_poly2_relin_forms(ctx(), input.data(), input.form, input.count(), (const uint64_t *)ev_keys16->ptr, 16, rowPtr(d_p[0]), rowPtr(d_p[1]), rowPtr(d_p[2]),
-                              out.data(), out_form, g_scratch->ptr, stream()), "crc_poly2_relin_forms");
+    ciphertext3D out = begin(input, out_form);
+    chk(crc_poly2_relin_forms(ctx(), input.data(), input.form, input.count(), evk16(), 16, rowPtr(d_p[0]), rowPtr(d_p[1]), rowPtr(d_p[2]), out.data(), out_form,
+                              scratch(crc_poly2_relin_work_bytes(ctx(), input.count(), 16)), stream()), "crc_poly2_relin_forms");
     return out;
 }
 void PolyLayer::printLayerStructure()
@@ -1390,30 +1388,25 @@ ciphertext3D multiplyRelin(const ciphertext3D &a, const ciphertext3D &b, int out
                                  stream()), "crc_multiply_relin_forms");
     return out;
 }
-Poly3Layer::Poly3Layer(string name, float c3, float c2, float c1, float c0, int th_count) : Layer(name), c3(c3), c2(c2), c1(c1), c0(c0), th_count(th_count)
+Poly3Layer::Poly3Layer(string name, float c3, float c2, float c1, float c0, int th_count) : ActivationLayer(name, "Poly3Layer", th_count), c3(c3), c2(c2), c1(c1),
+    c0(c0)
 {
     if (!isfinite(c3) || !isfinite(c2) || !isfinite(c1) || !isfinite(c0)) throw invalid_argument("Poly3Layer: the coefficients must be finite");
     if (c3 == 0.0f) throw invalid_argument("Poly3Layer: c3 must not be zero (a polynomial without its cubic term is a PolyLayer)");
 }
-size_t Poly3Layer::deviceBytes() const { size_t b = 0; for (auto &r : d_p) if (r) b += r->bytes; return b; }
+void Poly3Layer::rows()
+{
+    if (c3 != 1.0f || slot_scale[0] != 0) d_p[0] = coeffRow(c3, slot_scale[0], 0);
+    if (c2 != 0.0f) d_p[1] = coeffRow(c2, slot_scale[1], 0);
+    if (c1 != 0.0f) d_p[2] = coeffRow(c1, slot_scale[2], 0);
+    if (c0 != 0.0f) d_p[3] = coeffRow(c0, slot_scale[3], 2);
+    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+}
 ciphertext3D Poly3Layer::forward(ciphertext3D input)
 {
-    if (!input.buf) throw invalid_argument("Poly3Layer: empty input");
-    if (!ev_keys16) throw invalid_argument("not enough evaluation keys");
-    if (out_form != CRC_NTT && out_form != CRC_COEFF) throw invalid_argument("Poly3Layer: out_form must be CRC_NTT or CRC_COEFF");
-    if (!uploaded) {
-        for (auto &r : d_p) r.reset();
-        if (c3 != 1.0f || slot_scale[0] != 0) { const Plaintext p = encodeScaled((double)c3, slot_scale[0]); d_p[0] = uploadPlain({&p}, 0); }
-        if (c2 != 0.0f) { const Plaintext p = encodeScaled((double)c2, slot_scale[1]); d_p[1] = uploadPlain({&p}, 0); }
-        if (c1 != 0.0f) { const Plaintext p = encodeScaled((double)c1, slot_scale[2]); d_p[2] = uploadPlain({&p}, 0); }
-        if (c0 != 0.0f) { const Plaintext p = encodeScaled((double)c0, slot_scale[3]); d_p[3] = uploadPlain({&p}, 2); }
-        chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
-        uploaded = true;
-    }
-    ciphertext3D out(input.B, input.zd, input.xd, input.yd, out_form);
-    ensure(g_scratch, crc_poly3_relin_work_bytes(ctx(), input.count(), 16));
-    chk(crc_poly3_relin_forms(ctx(), input.data(), input.form, input.count(), (const uint64_t *)ev_keys16->ptr, 16, rowPtr(d_p[0]), rowPtr(d_p[1]), rowPtr(d_p[2]),
-                              rowPtr(d_p[3]), out.data(), out_form, g_scratch->ptr, stream()), "crc_poly3_relin_forms");
+    ciphertext3D out = begin(input, out_form);
+    chk(crc_poly3_relin_forms(ctx(), input.data(), input.form, input.count(), evk16(), 16, rowPtr(d_p[0]), rowPtr(d_p[1]), rowPtr(d_p[2]), rowPtr(d_p[3]), out.data(),
+                              out_form, scratch(crc_poly3_relin_work_bytes(ctx(), input.count(), 16)), stream()), "crc_poly3_relin_forms");
     return out;
 }
 void Poly3Layer::printLayerStructure()
@@ -1423,23 +1416,14 @@ void Poly3Layer::printLayerStructure()
 
 // ---- polynomial activation + pooling (Network::fuse) ------------------------------------------------------------------------
 PolyPoolLayer::PolyPoolLayer(string name, int xd, int yd, int zd, int xs, int ys, int xf, int yf, int th_count, float c2, float c1, float c0,
-    shared_ptr<DeviceBuffer> d_div)
-    : Layer(name), xd(xd), yd(yd), zd(zd), xs(xs), ys(ys), xf(xf), yf(yf), xo((xd - xf) / xs + 1), yo((yd - yf) / ys + 1), zo(zd), th_count(th_count),
-        c2(c2), c1(c1), c0(c0), d_div(d_div)
-{
-    polyCheck("PolyPoolLayer", c2, c1, c0);
-}
-size_t PolyPoolLayer::deviceBytes() const { size_t b = d_div ? d_div->bytes : 0; for (auto &r : d_p) if (r) b += r->bytes; return b; }
+    shared_ptr<DeviceBuffer> d_div) : ActivationLayer(name, "PolyPoolLayer", th_count, xd, yd, zd, xs, ys, xf, yf, d_div), c2(c2), c1(c1), c0(c0)
+    { polyCheck(kind, c2, c1, c0); }
 ciphertext3D PolyPoolLayer::forward(ciphertext3D input)
 {
-    checkInput(input, zd, xd, yd, "PolyPoolLayer");
-    if (!ev_keys16) throw invalid_argument("not enough evaluation keys");
-    if (out_form != CRC_NTT && out_form != CRC_COEFF) throw invalid_argument("PolyPoolLayer: out_form must be CRC_NTT or CRC_COEFF");
-    if (!uploaded) { polyRows(c2, c1, c0, xf * yf, d_div, d_p, slot_scale); uploaded = true; }
-    ciphertext3D out(input.B, zo, xo, yo, out_form);
-    ensure(g_scratch, crc_poly2_pool_relin_work_bytes(ctx(), input.B, zd, xd, yd, xs, ys, xf, yf, 16));
-    chk(crc_poly2_pool_relin_forms(ctx(), input.data(), input.form, input.B, zd, xd, yd, xs, ys, xf, yf, (const uint64_t *)ev_keys16->ptr, 16, rowPtr(d_p[0]),
-                                   rowPtr(d_p[1]), rowPtr(d_p[2]), out.data(), out_form, g_scratch->ptr, stream()), "crc_poly2_pool_relin_forms");
+    ciphertext3D out = begin(input, out_form);
+    chk(crc_poly2_pool_relin_forms(ctx(), input.data(), input.form, input.B, zd, xd, yd, xs, ys, xf, yf, evk16(), 16, rowPtr(d_p[0]), rowPtr(d_p[1]), rowPtr(d_p[2]),
+                                   out.data(), out_form, scratch(crc_poly2_pool_relin_work_bytes(ctx(), input.B, zd, xd, yd, xs, ys, xf, yf, 16)), stream()),
+        "crc_poly2_pool_relin_forms");
     return out;
 }
 void PolyPoolLayer::printLayerStructure()
@@ -1477,11 +1461,7 @@ ciphertext3D BatchNormLayer::forward(ciphertext3D input)
     ciphertext3D out = deepCopyImage(input);                // the reference works on its by-value copy (batchNormLayer.cpp:29)
     chk(crc_batchnorm(ctx(), out.data(), out.B, out.zd, out.xd, out.yd, (const uint64_t *)d_mean[out.form == CRC_NTT]->ptr, (const uint64_t *)d_invstd->ptr,
         out.form, stream()), "crc_batchnorm");
-    if (out_form != out.form) {
-        if (out_form == CRC_NTT) chk(crc_ntt_fwd(ctx(), out.data(), out.count(), 2, stream()), "crc_ntt_fwd");
-            else chk(crc_ntt_inv(ctx(), out.data(), out.count(), 2, stream()), "crc_ntt_inv");
-        out.form = out_form;
-    }
+    toForm(out, out_form, "BatchNormLayer");
     return out;
 }
 void BatchNormLayer::savePlaintextParameters(ostream *outfile) { for (int i = 0; i < num_channels; i++) { mean[i].save(*outfile); var[i].save(*outfile);
@@ -1499,6 +1479,181 @@ void Network::printNetworkStructure()
 {
     for (size_t i = 0; i < layers.size(); i++) { cerr << "(" << i << ") : "; layers[i]->printLayerStructure(); cout << endl; }
 }
+// ---- Network::forward: plan, timing, range runner, chunk loop (crcnn_amd/netrun.py: _plan / _run / forward_group) ----------------------------------------
+struct Network::ForwardRun {
+    bool packable = true;                                   // no modulus above 55 bits: the MAC kernels' 28-bit limb pairs exist
+    vector<shared_ptr<MacLayer>> mac;                       // the conv / dense layers (mac[L]: none behind the last layer)
+    vector<char> limb, streams;                             // layer i reads a limb tensor / ... as a streamed dense layer (limb tiles built inside the forward)
+    int split = 0;                                          // chunked: the first dense layer ([0, split) runs on sub-batches of head_chunk images)
+    // two-level chunking / the dense layers chunk by chunk as well (no tail) / the refresh in front of `split` runs chunk by chunk, before the assembly
+    bool chunked = false, per_chunk = false, chunk_refresh = false;
+    struct Timed { int layer; void *start, *stop; };
+    vector<Timed> events;                                   // time_with_events: read after the last layer; ev_used of event_pool's are taken
+    size_t ev_used = 0;
+    bool later_chunk = false;                               // two-level chunking: not the first chunk (profile_budget only lowers a layer's minimum)
+};
+// The hand-over form behind layer i: NTT between linear layers when resident, coefficient form into Square and out of the net; a producer writes the form its
+// consumer's plan names
+int Network::boundaryForm(const ForwardRun &f, int i) const
+{
+    const bool checking = max_num_of_reencryptions >= 0;
+    const shared_ptr<MacLayer> &m = f.mac[i], &next = f.mac[i + 1];
+    if (!ntt_resident || i + 1 == (int)layers.size()) return CRC_COEFF;
+    // the budget-checking forward's scope 0 reads ciphertext 0 on the host: coefficient form at every boundary
+    if (checking && budget_scope == 0) return CRC_COEFF;
+    // the tensor in front of the refresh is decrypted as it stands (crc_refresh_dev takes either ciphertext form): an NTT-resident network stays resident
+    // across it, but no packed / limb hand-over spans it
+    if (i + 1 == layer_before_reenc) return CRC_NTT;
+    // scope 1 measures the tensor on the device, in CRC_COEFF or CRC_NTT: the packed and limb hand-overs are off under max_num_of_reencryptions >= 0
+    if (checking) return CRC_NTT;
+    // a limb layer feeding a DENSE limb layer hands its tensor over in limb form (not across the chunk boundary: a dense layer's limb tensor is laid out for its
+    // whole batch, runChunks assembles the chunks into it).  The per-slot limb GEMM reads CRC_NTTL, which every limb layer writes; a scalar dense layer reads
+    // CRC_NTTLS, which only a scalar layer writes (any other producer hands over packed rows and the consumer converts them)
+    const bool across_chunks = f.chunked && !f.per_chunk && i + 1 == f.split;
+    if (f.limb[i] && !f.streams[i] && f.limb[i + 1] && next->dense && !across_chunks) {
+        if (next->w_form != CRC_NTTLS) return CRC_NTTL;
+        if (m->w_form == CRC_NTTLS) return CRC_NTTLS;
+    }
+    // a one-channel convolution writes the limb tensor of a matrix-core CONVOLUTION behind it itself (the same bytes for CRC_NTTL and CRC_NTTLS)
+    if (m && next && !m->dense && !next->dense && m->w_form == CRC_NTTL1 && (next->w_form == CRC_NTTL || next->w_form == CRC_NTTLS)) return CRC_NTTLC;
+    // a conv / dense layer feeding another one hands its tensor over packed (28-bit limb pairs)
+    if (f.packable && m && next) return CRC_NTTP;
+    return CRC_NTT;
+}
+Network::ForwardRun Network::plan(int B)
+{
+    const int L = (int)layers.size();
+    ForwardRun f;
+    // conv / dense weights go into the MAC kernels' operand form (28-bit limb pairs) once; moduli above 55 bits cannot be packed
+    { vector<uint64_t> q(K()); crc_ctx_table(ctx(), "q", q.data(), K()); for (uint64_t v : q) if (v >> 55) f.packable = false; }
+    f.mac.resize(L + 1);
+    for (int i = 0; i < L; i++) f.mac[i] = dynamic_pointer_cast<MacLayer>(layers[i]);
+    f.limb.assign(L + 1, 0); f.streams.assign(L + 1, 0);
+    // two-level chunking: the layers in front of the first dense layer on sub-batches of head_chunk images, the dense layers on the whole batch
+    f.split = L;
+    if (head_chunk > 0 && B > head_chunk && ntt_resident && max_num_of_reencryptions < 0)
+        for (int i = 1; i < L; i++) if (f.mac[i] && f.mac[i]->dense) { f.split = i; break; }
+    f.chunked = f.split < L;
+    if (f.packable)
+        for (int i = 0; i < L; i++) if (auto m = f.mac[i]) {
+            const int Bi = f.chunked && i < f.split ? head_chunk : B;
+            f.limb[i] = matrix_cores && m->limbWeights(Bi);
+            if (!f.limb[i]) m->packWeights(false);
+            // a STREAMED dense layer that will run on the matrix cores (64-filter limb tiles built inside the forward) reads a limb tensor like a resident
+            // one: the chunks of a group are packed straight into it, and no second copy of the group's input is made inside the layer
+            if (matrix_cores && m->dense && m->streamsOnMatrixCores(Bi)) { f.limb[i] = 1; f.streams[i] = 1; }
+        }
+    // a dense layer in scalar form (CRC_NTTLS) has no weight stream to amortise over a group of chunks: the whole network runs chunk by chunk instead
+    f.per_chunk = f.chunked && f.mac[f.split]->w_form == CRC_NTTLS;
+    // the refresh in front of the first dense layer runs chunk by chunk, before the chunks are assembled (the tail range then starts behind it)
+    f.chunk_refresh = f.chunked && !f.per_chunk && f.split == layer_before_reenc;
+    for (int i = 0; i < L; i++) layers[i]->out_form = boundaryForm(f, i);
+    return f;
+}
+// events on the launch stream (read after the last layer), or wall clock + stream synchronisation
+ciphertext3D Network::timed(ForwardRun &f, int i, const function<ciphertext3D()> &call)
+{
+    if (i >= 0) last_layer_launches[i]++;
+    ciphertext3D out;
+    if (time_with_events) {
+        auto next_event = [&]() { auto &ev = event_pool->ev; if (f.ev_used == ev.size()) { void *e = nullptr; chk(crc_event_create(ctx(), &e), "crc_event_create");
+            ev.push_back(e); } return ev[f.ev_used++]; };
+        void *e0 = next_event(), *e1 = next_event();
+        chk(crc_event_record(ctx(), e0, stream()), "crc_event_record");
+        out = call();
+        chk(crc_event_record(ctx(), e1, stream()), "crc_event_record");
+        f.events.push_back({i, e0, e1});
+    } else {
+        auto t0 = chrono::high_resolution_clock::now();
+        out = call();
+        chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+        (i < 0 ? last_reenc_ms : last_layer_ms[i]) += chrono::duration<double, milli>(chrono::high_resolution_clock::now() - t0).count();
+    }
+    // profile_budget: the layer's output tensor measured on the device, outside the timed region.  A later chunk of the same layer (two-level chunking) only
+    // lowers the minimum; a layer that is repeated after a refresh is measured afresh
+    if (i < 0 || !profile_budget || (out.form != CRC_COEFF && out.form != CRC_NTT)) return out;
+    int first = -1;
+    const int mn = minAndFirstBudget(out, "Network::forward", nullptr, &first);
+    if (f.later_chunk && last_layer_budget_min[i] >= 0) { last_layer_budget_min[i] = min(last_layer_budget_min[i], mn); return out; }
+    last_layer_budget_min[i] = mn; last_layer_budget_first[i] = first;
+    return out;
+}
+ciphertext3D Network::runLayer(ForwardRun &f, int i, const ciphertext3D &in) { return timed(f, i, [&] { return layers[i]->forward(in); }); }
+// the client-side refresh (needs the secret key; network.cpp:30-34), timed like a layer: T_REENC of mainparams.cpp:81
+ciphertext3D Network::runRefresh(ForwardRun &f, const ciphertext3D &in)
+{
+    const int of = ntt_resident && max_num_of_reencryptions < 0 ? CRC_NTT : CRC_COEFF;
+    OutHint hint(&act_slot[in.buf == act_slot[0] ? 1 : 0]);
+    return timed(f, -1, [&] {
+        vector<float> v;
+        ciphertext3D out = refreshImages(in, of, keep_reenc_values ? &v : nullptr, reenc_symmetric);
+        last_reenc_values.insert(last_reenc_values.end(), v.begin(), v.end());
+        return out;
+    });
+}
+ciphertext3D Network::runRange(ForwardRun &f, int lo, int hi, ciphertext3D t, bool to_caller, bool refresh_at_lo)
+{
+    for (int i = lo; i < hi; i++) {
+        if (i == layer_before_reenc && (i > lo || refresh_at_lo)) t = runRefresh(f, t);
+        // every layer writes into one of the network's two activation slots (the one its input does not live in); but the last layer's output -- ten
+        // ciphertexts per image -- is the caller's own tensor, as in the reference
+        OutHint hint(to_caller && i + 1 == hi ? nullptr : &act_slot[t.buf == act_slot[0] ? 1 : 0]);
+        t = runLayer(f, i, t);
+    }
+    // a last layer that hands its input back (none of CrCNN's does) must not give the caller a tensor that lives in a slot the next forward overwrites
+    if (to_caller && t.buf && (t.buf == act_slot[0] || t.buf == act_slot[1] || t.buf == tail_slot)) {
+        ciphertext3D own(t.B, t.zd, t.xd, t.yd, t.form);
+        chk(crc_memcpy_d2d(ctx(), own.data(), t.data(), t.count() * ctBytes(), stream()), "crc_memcpy_d2d");
+        t = own;
+    }
+    return t;
+}
+// Two-level chunking: layers [0, split) -- all of them when per_chunk -- on sub-batches of head_chunk images, every chunk's result put into one whole-batch tensor
+ciphertext3D Network::runChunks(ForwardRun &f, const ciphertext3D &input)
+{
+    const int B = input.B, hi = f.per_chunk ? (int)layers.size() : f.split;
+    const bool limb = !f.per_chunk && f.limb[f.split];
+    ciphertext3D whole;
+    for (int b0 = 0; b0 < B; b0 += head_chunk) {
+        const int Bc = min(head_chunk, B - b0);
+        f.later_chunk = b0 > 0;
+        ciphertext3D t = runRange(f, 0, hi, input.images(b0, Bc), false, true);
+        if (f.chunk_refresh) t = runRefresh(f, t);
+        const size_t out_cts = (size_t)t.zd * t.xd * t.yd;
+        if (!whole.buf) {
+            // the dense layers' input is kept across calls like the activation slots (next to 182 GiB of weights the pool has no room to hold it); the result of
+            // a network run chunk by chunk is the caller's own tensor
+            OutHint hint(f.per_chunk ? nullptr : &tail_slot);
+            whole = ciphertext3D(B, t.zd, t.xd, t.yd, limb ? CRC_NTTL : t.form);
+        }
+        if (limb)                 // every chunk's tensor goes straight into the dense layer's K-blocked limb tensor
+            chk(crc_limb_pack_tensor_at(ctx(), t.data(), t.form, Bc, (int)out_cts, 1, 1, whole.data(), B, b0, stream()), "crc_limb_pack_tensor_at");
+        else
+            chk(crc_memcpy_d2d(ctx(), (char *)whole.data() + (size_t)b0 * out_cts * ctBytes(), t.data(), (size_t)Bc * out_cts * ctBytes(), stream()), "crc_memcpy_d2d");
+    }
+    f.later_chunk = false;
+    if (!f.per_chunk) chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+    return whole;
+}
+// network.cpp:52-96: after every layer the budget of its output; at <= 5 bits the layer's input is refreshed and the layer repeated (every output a fresh tensor)
+ciphertext3D Network::runChecked(ForwardRun &f, ciphertext3D input)
+{
+    int refreshes_left = max_num_of_reencryptions;
+    for (int i = 0; i < (int)layers.size(); i++) {
+        ciphertext3D output = runLayer(f, i, input);
+        // scope 0: ciphertext 0, on the host; scope 1: the whole tensor on the device, in the form boundaryForm chose (a profiled forward has just measured it)
+        const int budget = budget_scope == 0 ? noiseBudget(output) : profile_budget ? last_layer_budget_min[i] : minNoiseBudget(output);
+        if (budget <= 5) {
+            if (refreshes_left <= 0) throw OutOfBudgetException(i - 1);
+            input = runRefresh(f, input);
+            refreshes_left--;
+            i--;
+            continue;
+        }
+        input = output;
+    }
+    return input;
+}
 ciphertext3D Network::forward(ciphertext3D input)
 {   // network.cpp:22-47
     const int L = (int)layers.size();
@@ -1506,205 +1661,25 @@ ciphertext3D Network::forward(ciphertext3D input)
     // the planning flag is this forward's only: layers called directly afterwards plan with the default again
     struct Restore { bool &ref; bool old; ~Restore() { ref = old; } } restore_matrix_cores{g_matrix_cores, g_matrix_cores};
     g_matrix_cores = matrix_cores;
-    // choose the form of every boundary: NTT between linear layers when resident, coefficient form into Square and out of the net
-    // conv / dense weights go into the MAC kernels' operand form (28-bit limb pairs) once; moduli above 55 bits cannot be packed
-    bool packable = true;
-    { vector<uint64_t> q(K()); crc_ctx_table(ctx(), "q", q.data(), K()); for (uint64_t v : q) if (v >> 55) packable = false; }
-    vector<shared_ptr<MacLayer>> mac(L + 1);                // the conv / dense layers (mac[L]: none behind the last layer)
-    for (int i = 0; i < L; i++) mac[i] = dynamic_pointer_cast<MacLayer>(layers[i]);
-    vector<char> limb(L, 0), streams(L, 0);
-    // two-level chunking: the layers in front of the first dense layer on sub-batches of head_chunk images, the dense layers on the whole batch
-    int split = L;
-    if (head_chunk > 0 && input.B > head_chunk && ntt_resident && max_num_of_reencryptions < 0)
-        for (int i = 1; i < L; i++) if (mac[i] && mac[i]->dense) { split = i; break; }
-    const bool chunked = split < L;
-    if (packable)
-        for (int i = 0; i < L; i++) if (auto m = mac[i]) {
-            const int Bi = chunked && i < split ? head_chunk : input.B;
-            limb[i] = matrix_cores && m->limbWeights(Bi);
-            if (!limb[i]) m->packWeights(false);
-            // a STREAMED dense layer that will run on the matrix cores (64-filter limb tiles built inside the forward) reads a limb tensor like a resident
-            // one: the chunks of a group are packed straight into it, and no second copy of the group's input is made inside the layer
-            if (matrix_cores && m->dense && m->streamsOnMatrixCores(Bi)) { limb[i] = 1; streams[i] = 1; }
-        }
-    // a dense layer in scalar form (CRC_NTTLS) has no weight stream to amortise over a group of chunks: the whole network runs chunk by chunk instead
-    const bool per_chunk = chunked && mac[split]->w_form == CRC_NTTLS;
-    for (int i = 0; i < L; i++) {
-        // the tensor in front of the refresh is decrypted as it stands (crc_refresh_dev takes either ciphertext form): an NTT-resident network stays resident
-        // across it, but no packed / limb hand-over spans it
-        const bool before_refresh = i + 1 == layer_before_reenc;
-        bool coeff = !ntt_resident || i == L - 1;
-        // a conv / dense layer feeding another one hands its tensor over packed as well ... and a limb layer feeding a DENSE limb layer hands it over in limb
-        // form (not across the chunk boundary: a dense layer's limb tensor is laid out for its whole batch, the chunks are assembled into it below)
-        // A producer writes the form its consumer's plan names: a scalar dense layer reads CRC_NTTLS, which only a scalar layer writes (any other producer hands
-        // over packed rows and the consumer converts them); the per-slot limb GEMM reads CRC_NTTL, which every limb layer writes
-        const bool to_scalar = i + 1 < L && mac[i + 1] && mac[i + 1]->w_form == CRC_NTTLS;
-        const bool to_dense_limb = i + 1 < L && limb[i] && !streams[i] && limb[i + 1] && mac[i + 1]->dense && !(chunked && !per_chunk && i + 1 == split) &&
-            (!to_scalar || mac[i]->w_form == CRC_NTTLS);
-        // ... and a one-channel convolution writes the limb tensor of a matrix-core CONVOLUTION behind it itself (the same bytes for CRC_NTTL and CRC_NTTLS)
-        const bool to_conv_limb = mac[i] && mac[i + 1] && !mac[i]->dense && !mac[i + 1]->dense && mac[i]->w_form == CRC_NTTL1 &&
-            (mac[i + 1]->w_form == CRC_NTTL || mac[i + 1]->w_form == CRC_NTTLS);
-        layers[i]->out_form = coeff ? CRC_COEFF : before_refresh ? CRC_NTT : to_dense_limb && max_num_of_reencryptions < 0 ? (to_scalar ? CRC_NTTLS : CRC_NTTL) : to_conv_limb &&
-            max_num_of_reencryptions < 0 ? CRC_NTTLC : (packable && max_num_of_reencryptions < 0 && mac[i] && mac[i + 1] ? CRC_NTTP : CRC_NTT);
-    }
+    ForwardRun f = plan(input.B);
     last_layer_ms.assign(L, 0.0);
     last_layer_launches.assign(L, 0);
     last_reenc_ms = 0.0;
-    // one timed Layer::forward call: events on the launch stream (read after the last layer), or wall clock + stream synchronisation
-    vector<pair<int, pair<void *, void *>>> timed;
-    size_t ev_used = 0;
-    if (time_with_events && !event_pool) event_pool = make_shared<EventPool>();
-    auto next_event = [&]() { auto &ev = event_pool->ev; if (ev_used == ev.size()) { void *e = nullptr; chk(crc_event_create(ctx(), &e), "crc_event_create");
-        ev.push_back(e); } return ev[ev_used++]; };
-    // profile_budget: the layer's output tensor measured on the device, outside the timed region.  A later chunk of the same layer (two-level chunking) only
-    // lowers the minimum; a layer that is repeated after a refresh is measured afresh
+    last_reenc_values.clear();
     last_layer_budget_min.assign(profile_budget ? L : 0, -1);
     last_layer_budget_first.assign(profile_budget ? L : 0, -1);
-    bool later_chunk = false;
-    auto profile = [&](int i, const ciphertext3D &out) {
-        if (!profile_budget || (out.form != CRC_COEFF && out.form != CRC_NTT)) return;
-        int first = -1;
-        const int mn = minAndFirstBudget(out, "Network::forward", nullptr, &first);
-        if (later_chunk && last_layer_budget_min[i] >= 0) { last_layer_budget_min[i] = min(last_layer_budget_min[i], mn); return; }
-        last_layer_budget_min[i] = mn; last_layer_budget_first[i] = first;
-    };
-    auto run_layer = [&](int i, const ciphertext3D &in) {
-        last_layer_launches[i]++;
-        if (time_with_events) {
-            void *e0 = next_event(), *e1 = next_event();
-            chk(crc_event_record(ctx(), e0, stream()), "crc_event_record");
-            ciphertext3D out = layers[i]->forward(in);
-            chk(crc_event_record(ctx(), e1, stream()), "crc_event_record");
-            timed.push_back({i, {e0, e1}});
-            profile(i, out);
-            return out;
-        }
-        auto t0 = chrono::high_resolution_clock::now();
-        ciphertext3D out = layers[i]->forward(in);
+    if (time_with_events && !event_pool) event_pool = make_shared<EventPool>();
+    if (max_num_of_reencryptions >= 0) input = runChecked(f, input);
+    else {
+        if (f.chunked) input = runChunks(f, input);
+        // (a network run chunk by chunk has no tail; under two-level chunking the tail starts behind a refresh that ran chunk by chunk)
+        if (!f.per_chunk) input = runRange(f, f.chunked ? f.split : 0, L, input, true, !f.chunk_refresh);
+    }
+    if (time_with_events) {
         chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
-        last_layer_ms[i] += chrono::duration<double, milli>(chrono::high_resolution_clock::now() - t0).count();
-        profile(i, out);
-        return out;
-    };
-    auto read_events = [&]() {
-        for (auto &t : timed) { float ms = 0; chk(crc_event_elapsed_ms(ctx(), t.second.first, t.second.second, &ms), "crc_event_elapsed_ms");
-            (t.first < 0 ? last_reenc_ms : last_layer_ms[t.first]) += ms; }
-        timed.clear();
-    };
-    // the refresh (network.cpp:30-34), timed like a layer: T_REENC of mainparams.cpp:81
-    last_reenc_values.clear();
-    auto refresh_into = [&](const ciphertext3D &in, int of) {
-        if (!keep_reenc_values) return refreshImages(in, of, nullptr, reenc_symmetric);
-        vector<float> v; ciphertext3D out = refreshImages(in, of, &v, reenc_symmetric);
-        last_reenc_values.insert(last_reenc_values.end(), v.begin(), v.end());
-        return out;
-    };
-    auto run_refresh = [&](const ciphertext3D &in) {
-        const int of = ntt_resident && max_num_of_reencryptions < 0 ? CRC_NTT : CRC_COEFF;
-        OutHint hint(&act_slot[in.buf == act_slot[0] ? 1 : 0]);
-        if (time_with_events) {
-            void *e0 = next_event(), *e1 = next_event();
-            chk(crc_event_record(ctx(), e0, stream()), "crc_event_record");
-            ciphertext3D out = refresh_into(in, of);
-            chk(crc_event_record(ctx(), e1, stream()), "crc_event_record");
-            timed.push_back({-1, {e0, e1}});
-            return out;
-        }
-        auto r0 = chrono::high_resolution_clock::now();
-        ciphertext3D out = refresh_into(in, of);
-        chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
-        last_reenc_ms += chrono::duration<double, milli>(chrono::high_resolution_clock::now() - r0).count();
-        return out;
-    };
-    if (max_num_of_reencryptions >= 0) {                    // network.cpp:52-96
-        int refreshes_left = max_num_of_reencryptions;
-        for (int i = 0; i < L; i++) {
-            // scope 0 reads ciphertext 0 on the host: coefficient form at every boundary.  Scope 1 measures the tensor on the device in the form chosen above
-            // (CRC_COEFF or CRC_NTT: the packed and limb hand-overs are off under max_num_of_reencryptions >= 0)
-            if (budget_scope == 0) layers[i]->out_form = CRC_COEFF;
-            ciphertext3D output = run_layer(i, input);
-            // (a profiled forward has just measured this tensor: its minimum is reused)
-            const int budget = budget_scope == 0 ? noiseBudget(output) : profile_budget ? last_layer_budget_min[i] : minNoiseBudget(output);
-            if (budget <= 5) {
-                if (refreshes_left <= 0) throw OutOfBudgetException(i - 1);
-                input = run_refresh(input);
-                refreshes_left--;
-                i--;
-                continue;
-            }
-            input = output;
-        }
-        read_events();
-        return input;
+        for (auto &t : f.events) { float ms = 0; chk(crc_event_elapsed_ms(ctx(), t.start, t.stop, &ms), "crc_event_elapsed_ms");
+            (t.layer < 0 ? last_reenc_ms : last_layer_ms[t.layer]) += ms; }
     }
-    int first = 0;
-    if (per_chunk) {
-        const int B = input.B;
-        ciphertext3D result;
-        for (int b0 = 0; b0 < B; b0 += head_chunk) {
-            const int Bc = min(head_chunk, B - b0);
-            ciphertext3D t = input.images(b0, Bc);
-            later_chunk = b0 > 0;
-            for (int i = 0; i < L; i++) {
-                if (i == layer_before_reenc) t = run_refresh(t);
-                OutHint hint(&act_slot[t.buf == act_slot[0] ? 1 : 0]); t = run_layer(i, t);
-            }
-            const size_t out_cts = (size_t)t.zd * t.xd * t.yd;
-            if (!result.buf) result = ciphertext3D(B, t.zd, t.xd, t.yd, t.form);
-            chk(crc_memcpy_d2d(ctx(), (char *)result.data() + (size_t)b0 * out_cts * ctBytes(), t.data(), (size_t)Bc * out_cts * ctBytes(), stream()), "crc_memcpy_d2d");
-        }
-        later_chunk = false;
-        if (time_with_events) { chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync"); read_events(); }
-        return result;
-    }
-    if (chunked) {
-        const int B = input.B;
-        ciphertext3D tail_in;
-        for (int b0 = 0; b0 < B; b0 += head_chunk) {
-            const int Bc = min(head_chunk, B - b0);
-            ciphertext3D t = input.images(b0, Bc);
-            later_chunk = b0 > 0;
-            for (int i = 0; i < split; i++) {
-                if (i == layer_before_reenc) t = run_refresh(t);
-                OutHint hint(&act_slot[t.buf == act_slot[0] ? 1 : 0]); t = run_layer(i, t);
-            }
-            if (split == layer_before_reenc) t = run_refresh(t);        // in front of the first dense layer: chunk by chunk, before the chunks are assembled
-            const size_t out_cts = (size_t)t.zd * t.xd * t.yd;
-            if (!tail_in.buf) {         // kept across calls like the activation slots: next to 182 GiB of weights the pool has no room to hold it
-                OutHint hint(&tail_slot);
-                tail_in = ciphertext3D(B, t.zd, t.xd, t.yd, limb[split] ? CRC_NTTL : t.form);
-            }
-            if (limb[split])      // every chunk's tensor goes straight into the dense layer's K-blocked limb tensor
-                chk(crc_limb_pack_tensor_at(ctx(), t.data(), t.form, Bc, (int)out_cts, 1, 1, tail_in.data(), B, b0, stream()), "crc_limb_pack_tensor_at");
-            else
-                chk(crc_memcpy_d2d(ctx(), (char *)tail_in.data() + (size_t)b0 * out_cts * ctBytes(), t.data(), (size_t)Bc * out_cts * ctBytes(), stream()),
-                    "crc_memcpy_d2d");
-        }
-        chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
-        later_chunk = false;
-        input = tail_in;
-        first = split;
-    }
-    for (int i = first; i < L; i++) {
-        // client-side refresh (needs the secret key), network.cpp:30-34; timed as T_REENC (:29-37).  Under two-level chunking a refresh at or in front of the
-        // first dense layer has already run, chunk by chunk
-        if (i == layer_before_reenc && !(chunked && layer_before_reenc <= split)) input = run_refresh(input);
-        // every layer but the last writes into one of the network's two activation slots (the one its input does not live in); the last layer's output -- ten
-        // ciphertexts per image -- is the caller's own tensor, as in the reference
-        if (i + 1 < L) { OutHint hint(&act_slot[input.buf == act_slot[0] ? 1 : 0]); input = run_layer(i, input); }
-        else {
-            ciphertext3D output = run_layer(i, input);
-            // a last layer that hands its input back (none of CrCNN's does) must not give the caller a tensor that lives in an activation slot the next forward
-            // overwrites
-            if (output.buf && (output.buf == act_slot[0] || output.buf == act_slot[1] || output.buf == tail_slot)) {
-                ciphertext3D own(output.B, output.zd, output.xd, output.yd, output.form);
-                chk(crc_memcpy_d2d(ctx(), own.data(), output.data(), output.count() * ctBytes(), stream()), "crc_memcpy_d2d");
-                output = own;
-            }
-            input = output;
-        }
-    }
-    if (time_with_events) { chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync"); read_events(); }
     return input;
 }
 Network::HbmPlan Network::hbmPlan() const

@@ -10,6 +10,7 @@
 //   * th_count arguments are accepted and ignored (parallelism is the GPU's).
 #pragma once
 #include <cstdint>
+#include <functional>
 #include <istream>
 #include <memory>
 #include <ostream>
@@ -353,53 +354,65 @@ public:
     void printLayerStructure() override;
 };
 
-class SquareLayer : public Layer {                          // squareLayer.h:12
+// What the five activation layers share, as MacLayer does for conv / dense: the pooling window Network::fuse() may put behind the activation (a flat layer has
+// none: the fields are 0, any input shape goes in and comes out) with the pooling's divisor, the NTT-form coefficient rows with their upload at the first forward,
+// and what every forward starts with.  The classes add their constructor, their one C-ABI call and printLayerStructure.  Nothing to save or load
+class ActivationLayer : public Layer {
 public:
-    int th_count;
-    SquareLayer(std::string name, int th_count) : Layer(name), th_count(th_count) {}
-    ciphertext3D forward(ciphertext3D input) override;
+    int xd = 0, yd = 0, zd = 0, xs = 0, ys = 0, xf = 0, yf = 0, xo = 0, yo = 0, zo = 0, th_count;
     void savePlaintextParameters(std::ostream *) override {}
     void loadPlaintextParameters(std::istream *) override {}
-    void printLayerStructure() override;
+    size_t deviceBytes() const override;
+protected:
+    ActivationLayer(std::string name, const char *kind, int th_count) : Layer(name), th_count(th_count), kind(kind) {}
+    ActivationLayer(std::string name, const char *kind, int th_count, int xd, int yd, int zd, int xs, int ys, int xf, int yf, std::shared_ptr<DeviceBuffer> d_div);
+    bool pooled() const { return xf > 0; }
+    // Every forward's start: std::invalid_argument for an empty input (a pooled layer: any shape but its own), without evaluation keys and for an out_form other
+    // than CRC_COEFF / CRC_NTT; the rows uploaded at the first call.  Returns the output tensor, in `form`.  scratch: the shared work area, `bytes` at least
+    ciphertext3D begin(const ciphertext3D &input, int form);
+    void *scratch(size_t bytes) const;
+    void poly2Rows(float c2, float c1, float c0, const double *scales);
+    const char *const kind;                                 // the class's name, for error texts
+    std::shared_ptr<DeviceBuffer> d_div;                    // NTT-form divisor of an average pooling
+    std::shared_ptr<DeviceBuffer> d_p[4];                   // the rows, highest power first; empty = 1 for the first, 0 for the others
 private:
+    virtual void rows() {}                                  // fills d_p (once)
+    bool uploaded = false;
+};
+
+class SquareLayer : public ActivationLayer {                // squareLayer.h:12
+public:
+    SquareLayer(std::string name, int th_count) : ActivationLayer(name, "SquareLayer", th_count) {}
+    ciphertext3D forward(ciphertext3D input) override;
+    void printLayerStructure() override;
 };
 
 // Network::fuse(): a SquareLayer with a (sum or average) PoolingLayer behind it.  Relinearisation is linear in the digit polynomials of c2, so the digits of a
 // pooling window are added and ONE key switch serves the pooled ciphertext (crc_square_pool_relin_forms): the ciphertexts squareLayer.cpp:21-39 followed by
-// poolingLayer.cpp:22-44 produce, bit for bit, with xo yo / (xd yd) of the key-switching work
-class SquarePoolLayer : public Layer {
+// poolingLayer.cpp:22-44 produce, bit for bit, with xo yo / (xd yd) of the key-switching work.  The divisor is applied to the pooled ciphertexts
+class SquarePoolLayer : public ActivationLayer {
 public:
-    int xd, yd, zd, xs, ys, xf, yf, xo, yo, zo, th_count;
-    SquarePoolLayer(std::string name, int xd, int yd, int zd, int xs, int ys, int xf, int yf, int th_count, std::shared_ptr<DeviceBuffer> d_div);
+    SquarePoolLayer(std::string name, int xd, int yd, int zd, int xs, int ys, int xf, int yf, int th_count, std::shared_ptr<DeviceBuffer> d_div)
+        : ActivationLayer(name, "SquarePoolLayer", th_count, xd, yd, zd, xs, ys, xf, yf, d_div) {}
     ciphertext3D forward(ciphertext3D input) override;
-    void savePlaintextParameters(std::ostream *) override {}
-    void loadPlaintextParameters(std::istream *) override {}
     void printLayerStructure() override;
-    size_t deviceBytes() const override { return d_div ? d_div->bytes : 0; }
-private:
-    std::shared_ptr<DeviceBuffer> d_div;                    // NTT-form divisor of an average pooling (applied to the pooled ciphertexts)
 };
 
 // Degree-2 polynomial activation c2 x^2 + c1 x + c0 (no layer of the reference, whose one non-linearity is SquareLayer): per ciphertext the Evaluator sequence
 //     s = relinearize(square(x), ev_keys16); s = multiply_plain(s, encode(c2)); s = add(s, multiply_plain(x, encode(c1))); s = add_plain(s, encode(c0))
 // (a step is left out for c2 == 1, c1 == 0, c0 == 0), computed with one key switch per ciphertext (crc_poly2_relin_forms).  The coefficients are float32
 // and encoded as the weights are; c2 == 0 (a batch norm, not an activation) and non-finite values are std::invalid_argument.  PolyLayer(name, 1, 0, 0, ...)
-// produces SquareLayer's ciphertexts bit for bit
-class PolyLayer : public Layer {
+// produces SquareLayer's ciphertexts bit for bit.  Rows: encode(c2), encode(c1), Delta encode(c0)
+class PolyLayer : public ActivationLayer {
 public:
     float c2, c1, c0;
     // slot encoding: the scales of c2, c1, c0 (the rows are the constants nearbyint(c * scale) mod t); 0 = the fractional encoder.  Set before the first forward
     double slot_scale[3] = {0, 0, 0};
-    int th_count;
     PolyLayer(std::string name, float c2, float c1, float c0, int th_count);
     ciphertext3D forward(ciphertext3D input) override;
-    void savePlaintextParameters(std::ostream *) override {}
-    void loadPlaintextParameters(std::istream *) override {}
     void printLayerStructure() override;
-    size_t deviceBytes() const override;
 private:
-    bool uploaded = false;
-    std::shared_ptr<DeviceBuffer> d_p[3];                   // NTT-form rows of encode(c2), encode(c1) and Delta encode(c0); empty = 1, 0, 0
+    void rows() override { poly2Rows(c2, c1, c0, slot_scale); }
 };
 
 // Degree-3 polynomial activation c3 x^3 + c2 x^2 + c1 x + c0: per ciphertext the Evaluator sequence
@@ -407,21 +420,17 @@ private:
 //     r = add(r, multiply_plain(s, encode(c2))); r = add(r, multiply_plain(x, encode(c1))); r = add_plain(r, encode(c0))
 // (a step is left out for c3 == 1, c2 == 0, c1 == 0, c0 == 0), computed by crc_poly3_relin_forms: TWO key switches and a multiplicative depth of 2 -- the
 // parameters must leave noise budget for a second multiplication (CrCNN's published (4096, two moduli, t = 2^29) leave none).  c3 == 0 (a PolyLayer) and
-// non-finite values are std::invalid_argument.  Network::fuse() treats the layer as an unfused SquareLayer: nothing is paired with a pooling behind it
-class Poly3Layer : public Layer {
+// non-finite values are std::invalid_argument.  Network::fuse() treats the layer as an unfused SquareLayer: nothing is paired with a pooling behind it.
+// Rows: encode(c3), encode(c2), encode(c1), Delta encode(c0)
+class Poly3Layer : public ActivationLayer {
 public:
     float c3, c2, c1, c0;
     double slot_scale[4] = {0, 0, 0, 0};                    // of c3, c2, c1, c0, as PolyLayer's
-    int th_count;
     Poly3Layer(std::string name, float c3, float c2, float c1, float c0, int th_count);
     ciphertext3D forward(ciphertext3D input) override;
-    void savePlaintextParameters(std::ostream *) override {}
-    void loadPlaintextParameters(std::istream *) override {}
     void printLayerStructure() override;
-    size_t deviceBytes() const override;
 private:
-    bool uploaded = false;
-    std::shared_ptr<DeviceBuffer> d_p[4];                   // NTT-form rows of encode(c3), encode(c2), encode(c1) and Delta encode(c0); empty = 1, 0, 0, 0
+    void rows() override;
 };
 // relinearize(multiply(a, b), ev_keys16) elementwise on two tensors of equal shape and form (CRC_COEFF or CRC_NTT), the result in out_form
 // (crc_multiply_relin_forms: Evaluator::multiply of SEAL 2.3.1, bit for bit); std::invalid_argument otherwise
@@ -431,21 +440,16 @@ ciphertext3D multiplyRelin(const ciphertext3D &a, const ciphertext3D &b, int out
 //     Sum_w (c2 x_w^2 + c1 x_w + c0) = c2 Sum_w relin(x_w^2) + c1 Sum_w x_w + W c0
 // keeps ONE key switch per pooled ciphertext (crc_poly2_pool_relin_forms); the window count and an average pooling's divisor are folded into the three
 // rows once (exact ring arithmetic).  Same ciphertexts as the two layers one after the other
-class PolyPoolLayer : public Layer {
+class PolyPoolLayer : public ActivationLayer {
 public:
-    int xd, yd, zd, xs, ys, xf, yf, xo, yo, zo, th_count;
     float c2, c1, c0;
     double slot_scale[3] = {0, 0, 0};                       // as PolyLayer's (Network::fuse() copies them)
     PolyPoolLayer(std::string name, int xd, int yd, int zd, int xs, int ys, int xf, int yf, int th_count, float c2, float c1, float c0,
         std::shared_ptr<DeviceBuffer> d_div);
     ciphertext3D forward(ciphertext3D input) override;
-    void savePlaintextParameters(std::ostream *) override {}
-    void loadPlaintextParameters(std::istream *) override {}
     void printLayerStructure() override;
-    size_t deviceBytes() const override;
 private:
-    bool uploaded = false;
-    std::shared_ptr<DeviceBuffer> d_div, d_p[3];            // the pooling's divisor; the rows with the window count and the divisor folded in
+    void rows() override { poly2Rows(c2, c1, c0, slot_scale); }
 };
 
 class BatchNormLayer : public Layer {                       // batchNormLayer.h:18-20
@@ -539,6 +543,20 @@ public:
 private:
     struct EventPool { std::vector<void *> ev; ~EventPool(); };
     std::shared_ptr<EventPool> event_pool;                  // HIP events of time_with_events, reused from forward to forward (copies of a Network share them)
+    // forward() in pieces, as crcnn_amd/netrun.py reads.  ForwardRun (crcnn_host.cpp): the plan of one forward and what it keeps between its layer calls.  plan(B)
+    // puts the conv / dense weights into their operand forms, decides the chunking and sets every layer's out_form: boundaryForm, the form behind layer i
+    struct ForwardRun;
+    ForwardRun plan(int B);
+    int boundaryForm(const ForwardRun &f, int i) const;
+    // one timed call, booked under layer i (-1: the refresh); a layer's launch is counted and its output budget-profiled behind the timed region
+    ciphertext3D timed(ForwardRun &f, int i, const std::function<ciphertext3D()> &call);
+    ciphertext3D runLayer(ForwardRun &f, int i, const ciphertext3D &in);
+    ciphertext3D runRefresh(ForwardRun &f, const ciphertext3D &in);
+    // layers [lo, hi) on t, with the refresh in front of layer_before_reenc (in front of lo: only if refresh_at_lo) and the ping-pong between the activation
+    // slots; to_caller: layer hi - 1 is the network's last, its output the caller's own tensor
+    ciphertext3D runRange(ForwardRun &f, int lo, int hi, ciphertext3D t, bool to_caller, bool refresh_at_lo);
+    ciphertext3D runChunks(ForwardRun &f, const ciphertext3D &input);              // two-level chunking: the sub-batches, assembled
+    ciphertext3D runChecked(ForwardRun &f, ciphertext3D input);                    // the budget-checking forward (max_num_of_reencryptions >= 0)
 public:
     std::shared_ptr<DeviceBuffer> tail_slot;                // ... and the dense layers' whole-batch input under two-level chunking
     // the two ping-pong activation buffers forward() keeps across calls (sized by the largest layer output so far)

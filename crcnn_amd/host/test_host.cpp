@@ -19,6 +19,7 @@
 //     layer, then "slot_scale <sigma>".  No GPU work
 //   test_host slots_build <description> <h5> <dir> <S> <input_bits> <weight_bits> [reps]     see do_slots_build
 //   test_host slots_rescale_plan <description> <h5> <dir> <S> <input_bits> <weight_bits>     see do_slots_rescale_plan
+//   test_host plan <model> <h5> <dir> <batch> <fuse 0|1> <head_chunk> <matrix_cores 0|1> <layer_before_reenc>     see do_plan
 //   test_host searchlogic <min> <max> <first_good> <last_good> <min_q>
 //     the plain-modulus search on a synthetic predicate (t < first_good: MISPREDICTED, t > last_good: OUT_OF_BUDGET); no GPU work.
 //     prints "found <t>" and one "tried <t> <status>" line per test
@@ -194,6 +195,37 @@ static int do_netr(int argc, char **argv)
     if (pl2 != pl) { fprintf(stderr, "second forward decrypts differently\n"); return 5; }
     delParameters();
     printf("netr ok\n");
+    return 0;
+}
+
+// plan <model> <h5> <dir> <batch> <fuse 0|1> <head_chunk> <matrix_cores 0|1> <layer_before_reenc>: what ONE Network::forward planned -- the network built as `net` /
+// `netr` build it (NTT-resident; <layer_before_reenc> >= 0 places the refresh and needs sk.u64 / pk.u64 in <dir>, -1: none), run once on <batch> copies of the image.
+// Prints "refresh <layer>" (where Network::fuse() left the refresh point) and per layer "plan <i> <name> <out_form> <kernelName(), - for none> <launches>": identical
+// output ciphertexts do not show that a boundary kept its limb hand-over or a layer its kernel, this table does (tests/test_gpu_host_plan.py)
+static int do_plan(int argc, char **argv)
+{
+    if (argc < 10) return 1;
+    string model = argv[2], h5 = argv[3], dir = argv[4]; const int batch = atoi(argv[5]); const bool fuse = atoi(argv[6]) != 0; const int reenc = atoi(argv[9]);
+    setDeterministicSeed(4242);
+    setup(dir);
+    if (reenc >= 0) { secret_key = rd(dir + "/sk.u64"); public_key = rd(dir + "/pk.u64"); }
+    { auto evk = rd(dir + "/evk.u64");
+      ev_keys16 = make_shared<DeviceBuffer>(evk.size() * 8);
+      crc_memcpy_h2d(context, ev_keys16->ptr, evk.data(), evk.size() * 8, nullptr); crc_stream_sync(context, nullptr); }
+    CnnBuilder builder(h5);
+    Network net = builder.buildNetworkByName(model);
+    net.ntt_resident = true; net.layer_before_reenc = reenc; net.head_chunk = atoi(argv[7]); net.matrix_cores = atoi(argv[8]) != 0;
+    if (fuse) net.fuse();
+    auto x = rd(dir + "/net_in.u64");
+    vector<ciphertext3D> imgs(batch, ciphertext3D::fromHost(x.data(), 1, net.input_zd, net.input_xd, net.input_yd));
+    const ciphertext3D out = net.forward(stackImages(imgs));
+    if (out.B != batch) { fprintf(stderr, "plan: %d images out of a batch of %d\n", out.B, batch); return 4; }
+    printf("refresh %d\n", net.layer_before_reenc);
+    for (int i = 0; i < net.getNumLayers(); i++) {
+        const string kernel = net.getLayer(i)->kernelName();
+        printf("plan %d %s %d %s %d\n", i, net.getLayer(i)->getName().c_str(), net.getLayer(i)->out_form, kernel.empty() ? "-" : kernel.c_str(), net.last_layer_launches[i]);
+    }
+    delParameters();
     return 0;
 }
 
@@ -932,6 +964,7 @@ int main(int argc, char **argv)
         if (!strcmp(argv[1], "netgeom")) return do_netgeom(argc, argv);
         if (!strcmp(argv[1], "net3")) return do_net3(argc, argv);
         if (!strcmp(argv[1], "netr")) return do_netr(argc, argv);
+        if (!strcmp(argv[1], "plan")) return do_plan(argc, argv);
         if (!strcmp(argv[1], "encsym")) return do_encsym(argc, argv);
         if (!strcmp(argv[1], "budgetsym")) return do_budgetsym(argc, argv);
         if (!strcmp(argv[1], "seeded")) return do_seeded(argc, argv);
