@@ -244,6 +244,21 @@ def load():
     L.crc_comm_allgather_u64.argtypes = [VP, PU, SZ, PU, VP]
     L.crc_checksum64.argtypes = [VP, VP, SZ, PU, VP]
     L.crc_decrypt.argtypes = [VP, PU, PU, SZ, CI, PU]
+    PI = ctypes.POINTER(CI)
+    L.crc_galois_elt_valid.argtypes = [VP, u64]
+    L.crc_galois_elt_rows.restype = u64; L.crc_galois_elt_rows.argtypes = [VP, CI]
+    L.crc_galois_elt_columns.restype = u64; L.crc_galois_elt_columns.argtypes = [VP]
+    L.crc_galois_default_elts.argtypes = [VP, PU, CI]
+    L.crc_gen_galois_keys.argtypes = [VP, u64, PU, CI, PU, CI, PU]
+    L.crc_gen_galois_keys_key.argtypes = [VP, PB, PU, CI, PU, CI, PU]
+    L.crc_galois_plan.argtypes = [VP, u64, PU, CI, PI, CI]
+    L.crc_galois_permute_dev.argtypes = [VP, VP, SZ, u64, CI, VP, VP]
+    L.crc_apply_galois_work_bytes.restype = SZ; L.crc_apply_galois_work_bytes.argtypes = [VP, SZ, CI]
+    L.crc_apply_galois_forms.argtypes = [VP, VP, CI, SZ, u64, VP, PU, CI, CI, VP, CI, VP, VP]
+    L.crc_rotate_rows_forms.argtypes = [VP, VP, CI, SZ, CI, VP, PU, CI, CI, VP, CI, VP, VP]
+    L.crc_rotate_columns_forms.argtypes = [VP, VP, CI, SZ, VP, PU, CI, CI, VP, CI, VP, VP]
+    L.crc_sum_slots_work_bytes.restype = SZ; L.crc_sum_slots_work_bytes.argtypes = [VP, SZ, CI]
+    L.crc_sum_slots_forms.argtypes = [VP, VP, CI, SZ, VP, PU, CI, CI, VP, CI, VP, VP]
     L.crc_noise_budget.argtypes = [VP, PU, PU, CI]
     _lib = L
     return L
@@ -869,6 +884,75 @@ class Engine:
         """c2 x^2 + c1 x + c0 on `count` ciphertexts with one key switch each; d_p2 / d_p1 / d_p0: poly2_rows (None = 1 / 0 / 0)"""
         _chk(self.L.crc_poly2_relin_forms(self.c, self.p(d_x), in_form, count, self.p(d_evk), dbc, self.p(d_p2), self.p(d_p1), self.p(d_p0), self.p(d_y), out_form,
                                           self.p(d_work), self.stream), "crc_poly2_relin_forms")
+
+    # ---- Galois automorphisms: rotations between the slots of a batched ciphertext (crc_galois_* / crc_apply_galois_forms / crc_rotate_* / crc_sum_slots_forms).
+    # A key set is (elts, blobs): the host list of elements and one key blob [crc_evk_words] per element in the same order, on the host or on the device
+    def galois_elt_valid(self, g):
+        return bool(self.L.crc_galois_elt_valid(self.c, int(g)))
+
+    def galois_elt_rows(self, steps):
+        """the element of rotate_rows(steps); 0 for |steps| >= n/2"""
+        return int(self.L.crc_galois_elt_rows(self.c, int(steps)))
+
+    def galois_elt_columns(self):
+        return int(self.L.crc_galois_elt_columns(self.c))
+
+    def galois_default_elts(self):
+        """the elements of KeyGenerator::generate_galois_keys(dbc): 2n - 1, then 3^(2^i), 3^(-2^i) mod 2n"""
+        out = np.zeros(_chk(self.L.crc_galois_default_elts(self.c, None, 0), "crc_galois_default_elts"), dtype=np.uint64)
+        _chk(self.L.crc_galois_default_elts(self.c, _pu(out), out.size), "crc_galois_default_elts")
+        return out
+
+    @staticmethod
+    def _elts(elts):
+        return np.ascontiguousarray(np.asarray(elts, dtype=np.uint64).reshape(-1))
+
+    def gen_galois_keys(self, seed, sk, dbc=16, elts=None, key=None):
+        """-> (elts, blobs [n_elts][crc_evk_words]); elts None: the default set.  With `key`: crc_gen_galois_keys_key"""
+        elts = self.galois_default_elts() if elts is None else self._elts(elts)
+        gk = np.zeros((elts.size, self.L.crc_evk_words(self.c, dbc)), dtype=np.uint64)
+        if key is None:
+            _chk(self.L.crc_gen_galois_keys(self.c, seed, _pu(sk), dbc, _pu(elts), elts.size, _pu(gk)), "crc_gen_galois_keys")
+        else:
+            _chk(self.L.crc_gen_galois_keys_key(self.c, self._key(key), _pu(sk), dbc, _pu(elts), elts.size, _pu(gk)), "crc_gen_galois_keys_key")
+        return elts, gk
+
+    def galois_plan(self, g, elts):
+        """the indices into elts that apply_galois(g) applies, in order (CrcError where a key is missing)"""
+        elts = self._elts(elts); out = (CI * 64)()
+        cnt = _chk(self.L.crc_galois_plan(self.c, int(g), _pu(elts), elts.size, out, 64), "crc_galois_plan")
+        return [int(out[i]) for i in range(cnt)]
+
+    def galois_permute_dev(self, d_x, count, g, d_x3, accumulate=False):
+        _chk(self.L.crc_galois_permute_dev(self.c, self.p(d_x), count, int(g), 1 if accumulate else 0, self.p(d_x3), self.stream), "crc_galois_permute_dev")
+
+    def apply_galois_work_bytes(self, count, dbc=16):
+        return self.L.crc_apply_galois_work_bytes(self.c, count, dbc)
+
+    def apply_galois(self, d_x, count, g, d_gk, elts, d_y, d_work, dbc=16, in_form=COEFF, out_form=COEFF):
+        elts = self._elts(elts)
+        _chk(self.L.crc_apply_galois_forms(self.c, self.p(d_x), in_form, count, int(g), self.p(d_gk), _pu(elts), elts.size, dbc, self.p(d_y), out_form,
+                                           self.p(d_work), self.stream), "crc_apply_galois_forms")
+
+    def rotate_rows(self, d_x, count, steps, d_gk, elts, d_y, d_work, dbc=16, in_form=COEFF, out_form=COEFF):
+        """new slot i of each half = old slot (i + steps) mod n/2; d_work: apply_galois_work_bytes (rotate_columns too)"""
+        elts = self._elts(elts)
+        _chk(self.L.crc_rotate_rows_forms(self.c, self.p(d_x), in_form, count, int(steps), self.p(d_gk), _pu(elts), elts.size, dbc, self.p(d_y), out_form,
+                                          self.p(d_work), self.stream), "crc_rotate_rows_forms")
+
+    def rotate_columns(self, d_x, count, d_gk, elts, d_y, d_work, dbc=16, in_form=COEFF, out_form=COEFF):
+        elts = self._elts(elts)
+        _chk(self.L.crc_rotate_columns_forms(self.c, self.p(d_x), in_form, count, self.p(d_gk), _pu(elts), elts.size, dbc, self.p(d_y), out_form, self.p(d_work),
+                                             self.stream), "crc_rotate_columns_forms")
+
+    def sum_slots_work_bytes(self, count, dbc=16):
+        return self.L.crc_sum_slots_work_bytes(self.c, count, dbc)
+
+    def sum_slots(self, d_x, count, d_gk, elts, d_y, d_work, dbc=16, in_form=COEFF, out_form=COEFF):
+        """every slot of the result = the sum of all n slots mod t (log2 n key switches)"""
+        elts = self._elts(elts)
+        _chk(self.L.crc_sum_slots_forms(self.c, self.p(d_x), in_form, count, self.p(d_gk), _pu(elts), elts.size, dbc, self.p(d_y), out_form, self.p(d_work),
+                                        self.stream), "crc_sum_slots_forms")
 
     # ---- ciphertext x ciphertext multiply and the degree-3 activation c3 x^3 + c2 x^2 + c1 x + c0 (crc_multiply* / crc_poly3_relin_forms)
     def multiply_relin_work_bytes(self, count, dbc=16):

@@ -1173,6 +1173,126 @@ extern "C" int crc_poly3_relin_forms(crc_ctx *c, const uint64_t *d_x, int in_for
     if (out_form == CRC_COEFF) RUN(crc_ntt_inv(c, d_out, count, 2, stream));
     return CRC_OK;
 }
+// ---- Galois automorphisms: Evaluator::apply_galois, rotate_rows, rotate_columns, and the sum over all slots ----
+// A step is galois_permute_kernel (kernels_galois.hip) into the size-3 rows (sigma(c0), 0, sigma(c1) (q/q_i)^-1), then relinearisation's key switch with the
+// element's key: its tail adds the first two polynomials, which is SEAL's + (temp0, 0).  Steps run one after the other over the whole tensor, each in internal
+// passes of whole ciphertexts; the result of a step lives in d_y (a pass is read into work space before its rows are written), so the work space is one pass':
+// [coefficient copy of an NTT-form pass][prepared keys of the step's element, made by its pass 0][size-3 rows][scratch of the key switch]
+struct GalWork { u64 *xc, *kp, *x3, *rest; size_t step; };
+static GalWork gal_layout(const crc_ctx *c, size_t count, int dbc, WorkArena &a)
+{
+    GalWork L{};
+    L.step = square_chunk(c);
+    const size_t ch = count < L.step ? count : L.step;
+    L.xc = a.take<u64>(ch * crc_ct_words(c, 2));
+    L.kp = a.take<u64>(k_relin_keys_words(c, dbc));
+    L.x3 = a.take<u64>(ch * crc_ct_words(c, 3));
+    L.rest = a.take<u64>(k_relin_work_words(c, ch, dbc));
+    return L;
+}
+static size_t gal_bytes(const crc_ctx *c, size_t count, int dbc)
+{
+    if (!c || !dbc_ok(dbc)) return 0;
+    WorkArena a;
+    gal_layout(c, count, dbc, a);
+    return a.bytes();
+}
+static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+// one step over the whole tensor: src (src_form) -> d_y (coefficient form, or NTT form where out_ntt); src may be d_y itself
+static int gal_step(crc_ctx *c, const GalWork &L, const u64 *src, int src_form, size_t count, u64 g, bool accumulate, const u64 *d_key, int dbc, u64 *d_y, bool out_ntt,
+                    void *stream)
+{
+    const size_t ctw = crc_ct_words(c, 2);
+    for (size_t o = 0; o < count; o += L.step) {
+        const size_t ch = pass_len(count, o, L.step);
+        const u64 *xin = src + o * ctw;
+        if (src_form == CRC_NTT) { RUN(k_ntt_ct(c, true, xin, L.xc, ch, 2, false, S(stream), nullptr, 0, 0, 0)); xin = L.xc; }
+        RUN(k_galois_permute(c, xin, ch, g, accumulate, L.x3, S(stream)));
+        RUN(k_relinearize(c, L.x3, ch, d_key, dbc, d_y + o * ctw, L.rest, L.kp, S(stream), out_ntt, true, o != 0));
+    }
+    return CRC_OK;
+}
+static int gal_args_ok(const crc_ctx *c, const uint64_t *d_x, int in_form, size_t count, const uint64_t *d_gk, const uint64_t *elts, int n_elts, int dbc,
+                       const uint64_t *d_y, int out_form, const void *d_work)
+{
+    if (!d_x || !d_y || !d_work || !form_ok(in_form) || !form_ok(out_form) || !dbc_ok(dbc) || n_elts < 0 || (n_elts && (!elts || !d_gk))) return 0;
+    if (!aligned16(d_x) || !aligned16(d_y) || !aligned16(d_gk)) return 0;
+    const size_t ctw = crc_ct_words(c, 2), wb = gal_bytes(c, count, dbc);
+    if (ranges_overlap(d_work, wb, d_x, 8 * count * ctw) || ranges_overlap(d_work, wb, d_y, 8 * count * ctw)) return 0;     // (every pass is staged there)
+    return ranges_overlap(d_x, 8 * count * ctw, d_y, 8 * count * ctw) ? 0 : 1;
+}
+extern "C" int crc_galois_permute_dev(crc_ctx *c, const uint64_t *d_x, size_t count, uint64_t g, int accumulate, uint64_t *d_x3, void *stream)
+{
+    CHECK_CTX(c);
+    if (!d_x || !d_x3 || !aligned16(d_x) || !aligned16(d_x3) || !crc_galois_elt_valid(c, g)) return CRC_ERR_INVALID_ARGUMENT;
+    if (ranges_overlap(d_x, 8 * count * crc_ct_words(c, 2), d_x3, 8 * count * crc_ct_words(c, 3))) return CRC_ERR_INVALID_ARGUMENT;
+    return k_galois_permute(c, d_x, count, g, accumulate != 0, d_x3, S(stream));
+}
+extern "C" size_t crc_apply_galois_work_bytes(const crc_ctx *c, size_t count, int dbc) { return gal_bytes(c, count, dbc); }
+extern "C" int crc_apply_galois_forms(crc_ctx *c, const uint64_t *d_x, int in_form, size_t count, uint64_t g, const uint64_t *d_gk, const uint64_t *elts, int n_elts,
+                                      int dbc, uint64_t *d_y, int out_form, void *d_work, void *stream)
+{
+    CHECK_CTX(c);
+    if (!gal_args_ok(c, d_x, in_form, count, d_gk, elts, n_elts, dbc, d_y, out_form, d_work) || !crc_galois_elt_valid(c, g)) return CRC_ERR_INVALID_ARGUMENT;
+    int plan[64];
+    const int ns = crc_galois_plan(c, g, elts, n_elts, plan, 64);      // (at most log2 n steps: fewer than 64)
+    if (ns < 0) return ns;
+    if (count == 0) return CRC_OK;
+    const size_t ctw = crc_ct_words(c, 2), kw = crc_evk_words(c, dbc);
+    if (ns == 0) {                                                     // g = 1: the same ciphertext in the requested form
+        HIPCHK(hipMemcpyAsync(d_y, d_x, 8 * count * ctw, hipMemcpyDeviceToDevice, S(stream)));
+        if (in_form == out_form) return CRC_OK;
+        return out_form == CRC_NTT ? crc_ntt_fwd(c, d_y, count, 2, stream) : crc_ntt_inv(c, d_y, count, 2, stream);
+    }
+    WorkArena a(d_work);
+    const GalWork L = gal_layout(c, count, dbc, a);
+    for (int s = 0; s < ns; s++)
+        RUN(gal_step(c, L, s ? d_y : d_x, s ? CRC_COEFF : in_form, count, elts[plan[s]], false, d_gk + (size_t)plan[s] * kw, dbc, d_y,
+                     s == ns - 1 && out_form == CRC_NTT, stream));
+    return CRC_OK;
+}
+extern "C" int crc_rotate_rows_forms(crc_ctx *c, const uint64_t *d_x, int in_form, size_t count, int steps, const uint64_t *d_gk, const uint64_t *elts, int n_elts,
+                                     int dbc, uint64_t *d_y, int out_form, void *d_work, void *stream)
+{
+    CHECK_CTX(c);
+    if (!crc_slots_supported(c)) return CRC_ERR_PARAMETERS;            // "encryption parameters do not support batching", evaluator.cpp:1790
+    const u64 g = crc_galois_elt_rows(c, steps);
+    if (!g) return CRC_ERR_INVALID_ARGUMENT;
+    return crc_apply_galois_forms(c, d_x, in_form, count, g, d_gk, elts, n_elts, dbc, d_y, out_form, d_work, stream);
+}
+extern "C" int crc_rotate_columns_forms(crc_ctx *c, const uint64_t *d_x, int in_form, size_t count, const uint64_t *d_gk, const uint64_t *elts, int n_elts, int dbc,
+                                        uint64_t *d_y, int out_form, void *d_work, void *stream)
+{
+    CHECK_CTX(c);
+    if (!crc_slots_supported(c)) return CRC_ERR_PARAMETERS;
+    return crc_apply_galois_forms(c, d_x, in_form, count, crc_galois_elt_columns(c), d_gk, elts, n_elts, dbc, d_y, out_form, d_work, stream);
+}
+// y = x; y += rotate_rows(y, 2^j) for j < log2(n/2); y += rotate_columns(y): every slot holds the sum of all n.  A step is the permute's accumulate form --
+// (sigma(c0) + c0, c1, sigma(c1) ...) -- so the key switch's tail forms y + rotate(y) and no add kernel runs.  Every element must have its own key in the set
+extern "C" size_t crc_sum_slots_work_bytes(const crc_ctx *c, size_t count, int dbc) { return gal_bytes(c, count, dbc); }
+extern "C" int crc_sum_slots_forms(crc_ctx *c, const uint64_t *d_x, int in_form, size_t count, const uint64_t *d_gk, const uint64_t *elts, int n_elts, int dbc,
+                                   uint64_t *d_y, int out_form, void *d_work, void *stream)
+{
+    CHECK_CTX(c);
+    if (!crc_slots_supported(c)) return CRC_ERR_PARAMETERS;
+    if (!gal_args_ok(c, d_x, in_form, count, d_gk, elts, n_elts, dbc, d_y, out_form, d_work)) return CRC_ERR_INVALID_ARGUMENT;
+    int idx[64], ns = 0;
+    for (int j = 0; j < c->logn; j++) {
+        const u64 g = j < c->logn - 1 ? crc_galois_elt_rows(c, 1 << j) : crc_galois_elt_columns(c);
+        int at = -1;
+        for (int i = 0; i < n_elts; i++) if (elts[i] == g) { at = i; break; }
+        if (at < 0) return CRC_ERR_INVALID_ARGUMENT;
+        idx[ns++] = at;
+    }
+    if (count == 0) return CRC_OK;
+    const size_t kw = crc_evk_words(c, dbc);
+    WorkArena a(d_work);
+    const GalWork L = gal_layout(c, count, dbc, a);
+    for (int s = 0; s < ns; s++)
+        RUN(gal_step(c, L, s ? d_y : d_x, s ? CRC_COEFF : in_form, count, elts[idx[s]], true, d_gk + (size_t)idx[s] * kw, dbc, d_y,
+                     s == ns - 1 && out_form == CRC_NTT, stream));
+    return CRC_OK;
+}
 extern "C" int crc_square_relin(crc_ctx *c, const uint64_t *d_x, size_t count, const uint64_t *d_evk, int dbc, uint64_t *d_y, void *d_work, void *stream)
 {
     return crc_square_relin_forms(c, d_x, CRC_COEFF, count, d_evk, dbc, d_y, CRC_COEFF, d_work, stream);

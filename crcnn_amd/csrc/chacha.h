@@ -72,7 +72,7 @@ inline ChaChaKey chacha_load_key(const uint8_t *key)
 
 // stream domains (nonce word 2 carries the domain in its top byte)
 enum { CHACHA_DOM_KEYGEN = 1, CHACHA_DOM_EVK = 2, CHACHA_DOM_ENC_HOST = 3, CHACHA_DOM_ENC_DEV = 4, CHACHA_DOM_ENC_SYM = 5, CHACHA_DOM_SEEDED_A = 6,
-       CHACHA_DOM_SEEDED_E = 7 };
+       CHACHA_DOM_SEEDED_E = 7, CHACHA_DOM_GALOIS = 8 };
 
 // Streams of the secret-key encryptor (crc_encrypt_sym* on the host, enc_sym_sample_kernel on the device: the same bits).  One stream per (ciphertext,
 // coefficient pair), nonce = (stream id low, stream id high, CHACHA_DOM_ENC_SYM << 24 | even coefficient index s); its 32-bit words w[0], w[1], ... run

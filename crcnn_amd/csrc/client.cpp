@@ -119,14 +119,13 @@ extern "C" int crc_keygen(const crc_ctx *c, uint64_t seed, uint64_t *sk, uint64_
     return keygen_impl(c, seed_key(seed), sk, pk);
 }
 
-static int gen_evk_impl(const crc_ctx *c, const ChaChaKey &ckey, const uint64_t *sk, int dbc, uint64_t *evk)
+// A key-switching key towards the secret key s for the target polynomial w (NTT form): for l < k and d < L_l the pair first = -(a s + e) + [j == l] (q/q_l) 2^(dbc d) w,
+// second = a, NTT form, [2 L_l][k][n] per l -- the evaluation keys with w = s^2 (keygenerator.cpp:652-698), a Galois key with w = sigma_g(s) (:325-405)
+static void switch_key_impl(const crc_ctx *c, Rng &r, const uint64_t *sk, const u64 *target, int dbc, uint64_t *out)
 {
-    if (!dbc_ok(dbc)) return CRC_ERR_INVALID_ARGUMENT;
     const int n = c->n, k = c->k;
-    Rng r(ckey, 0, 0, (u32)CHACHA_DOM_EVK << 24);
-    std::vector<u64> s2((size_t)k * n), e((size_t)k * n);
-    for (int j = 0; j < k; j++) for (int s = 0; s < n; s++) { const size_t o = (size_t)j * n + s; s2[o] = h_mulmod(sk[o], sk[o], c->q[j]); }
-    u64 *key = evk;
+    std::vector<u64> e((size_t)k * n);
+    u64 *key = out;
     for (int l = 0; l < k; l++) {
         u64 factor = 1;                            // (q/q_l) mod q_l, then times 2^(dbc*d)   keygenerator.cpp:652-698
         for (int j = 0; j < k; j++) if (j != l) factor = h_mulmod(factor, c->q[j] % c->q[l], c->q[l]);
@@ -140,7 +139,7 @@ static int gen_evk_impl(const crc_ctx *c, const ChaChaKey &ckey, const uint64_t 
                 for (int s = 0; s < n; s++) {
                     const size_t o = (size_t)j * n + s;
                     u64 v = negmod(addmod(h_mulmod(second[o], sk[o], q), e[o], q), q);
-                    if (j == l) v = addmod(v, h_mulmod(s2[o], factor, q), q);
+                    if (j == l) v = addmod(v, h_mulmod(target[o], factor, q), q);
                     first[o] = v;
                 }
             }
@@ -148,6 +147,15 @@ static int gen_evk_impl(const crc_ctx *c, const ChaChaKey &ckey, const uint64_t 
         }
         key += (size_t)2 * L * k * n;
     }
+}
+static int gen_evk_impl(const crc_ctx *c, const ChaChaKey &ckey, const uint64_t *sk, int dbc, uint64_t *evk)
+{
+    if (!dbc_ok(dbc)) return CRC_ERR_INVALID_ARGUMENT;
+    const int n = c->n, k = c->k;
+    Rng r(ckey, 0, 0, (u32)CHACHA_DOM_EVK << 24);
+    std::vector<u64> s2((size_t)k * n);
+    for (int j = 0; j < k; j++) for (int s = 0; s < n; s++) { const size_t o = (size_t)j * n + s; s2[o] = h_mulmod(sk[o], sk[o], c->q[j]); }
+    switch_key_impl(c, r, sk, s2.data(), dbc, evk);
     return CRC_OK;
 }
 extern "C" int crc_gen_evk_key(const crc_ctx *c, const uint8_t *key, const uint64_t *sk, int dbc, uint64_t *evk)
@@ -159,6 +167,99 @@ extern "C" int crc_gen_evk(const crc_ctx *c, uint64_t seed, const uint64_t *sk, 
 {
     if (!c || !sk || !evk) return CRC_ERR_INVALID_ARGUMENT;
     return gen_evk_impl(c, seed_key(seed), sk, dbc, evk);
+}
+
+// ---- Galois elements, keys and the rotation planner (Evaluator::apply_galois / rotate_rows / rotate_columns, KeyGenerator::generate_galois_keys) ----
+extern "C" int crc_galois_elt_valid(const crc_ctx *c, uint64_t g) { return c && (g & 1) && g < 2 * (u64)c->n ? 1 : 0; }      // evaluator.cpp:1595
+extern "C" uint64_t crc_galois_elt_rows(const crc_ctx *c, int steps)
+{
+    if (!c || c->n < 2) return 0;
+    const long long half = c->n / 2, a = steps < 0 ? -(long long)steps : steps;
+    if (a >= half) return 0;                       // "step count too large", evaluator.cpp:1808
+    const long long e = steps < 0 ? half - a : a;  // a right rotation by a is a left rotation by n/2 - a
+    u64 g = 1;
+    for (long long i = 0; i < e; i++) g = g * 3 & (2 * (u64)c->n - 1);
+    return g;
+}
+extern "C" uint64_t crc_galois_elt_columns(const crc_ctx *c) { return c ? 2 * (u64)c->n - 1 : 0; }
+extern "C" int crc_galois_default_elts(const crc_ctx *c, uint64_t *out, int cap)
+{
+    if (!c) return CRC_ERR_INVALID_ARGUMENT;
+    const u64 mask = 2 * (u64)c->n - 1;
+    u64 p = 3, m = 1, list[2 * 64];               // keygenerator.cpp:436-453: m - 1, then 3^(2^i) and 3^(-2^i) for i < log2 n - 1
+    for (u64 x = 3, e = (u64)c->n - 1; e; e >>= 1, x = x * x & mask) if (e & 1) m = m * x & mask;      // 3^-1 = 3^(n - 1) mod 2n
+    int cnt = 0;
+    // (SEAL keeps the keys in a map: 3^(n/4) is its own inverse and appears once)
+    auto put = [&](u64 e) { for (int i = 0; i < cnt; i++) if (list[i] == e) return; list[cnt++] = e; };
+    put(mask);
+    for (int i = 0; i < c->logn - 1; i++) { put(p); p = p * p & mask; put(m); m = m * m & mask; }
+    if (!out) return cnt;
+    if (cap < cnt) return CRC_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < cnt; i++) out[i] = list[i];
+    return cnt;
+}
+// The steps of apply_galois(g) with the keys of elts[]: the indices into elts to apply, in order (evaluator.cpp:1623-1661).  Returns their count: 0 for g = 1, one
+// where the key of g is in the set, else the bits of the discrete logarithm over 3 or 3^-1, whichever has fewer, then 2n - 1 for the sign
+extern "C" int crc_galois_plan(const crc_ctx *c, uint64_t g, const uint64_t *elts, int n_elts, int *steps_out, int cap)
+{
+    if (!c || !crc_galois_elt_valid(c, g) || n_elts < 0 || (n_elts && !elts) || cap < 0 || (cap && !steps_out)) return CRC_ERR_INVALID_ARGUMENT;
+    if (g == 1) return 0;
+    auto find = [&](u64 e) { for (int i = 0; i < n_elts; i++) if (elts[i] == e) return i; return -1; };
+    int cnt = 0;
+    auto put = [&](u64 e) { const int i = find(e); if (i < 0 || cnt >= cap) return false; steps_out[cnt++] = i; return true; };
+    if (find(g) >= 0) return put(g) ? 1 : CRC_ERR_INVALID_ARGUMENT;
+    const u64 mask = 2 * (u64)c->n - 1, half = (u64)c->n / 2;
+    u64 o1 = 0, o2 = 0, p = 1;                     // g = 3^o1 (-1)^o2
+    for (; o1 < half; o1++, p = p * 3 & mask) { if (p == g) break; if (((mask + 1) - p) == g) { o2 = 1; break; } }
+    if (o1 >= half) return CRC_ERR_INVALID_ARGUMENT;               // (n = 2: every odd residue is +-1)
+    u64 gen = 3;
+    if (__builtin_popcountll(half - o1) < __builtin_popcountll(o1)) {
+        o1 = half - o1; gen = 1;
+        for (u64 x = 3, e = (u64)c->n - 1; e; e >>= 1, x = x * x & mask) if (e & 1) gen = gen * x & mask;
+    }
+    for (; o1; o1 >>= 1, gen = gen * gen & mask) if ((o1 & 1) && !put(gen)) return CRC_ERR_INVALID_ARGUMENT;
+    if (o2 && !put(mask)) return CRC_ERR_INVALID_ARGUMENT;
+    return cnt;
+}
+// sigma_g of a coefficient row mod q (util::apply_galois, util/polyarithsmallmod.h:313-360): the host twin of galois_permute_kernel's gather
+static void galois_row(const u64 *in, u64 *out, int n, u64 g, u64 q)
+{
+    for (u64 i = 0; i < (u64)n; i++) {
+        const u64 r = i * g;
+        out[r & ((u64)n - 1)] = r & (u64)n ? negmod(in[i], q) : in[i];
+    }
+}
+// One key blob (crc_evk_words) per element: the evaluation-key construction with s^2 replaced by NTT(sigma_g(INTT(s))).  A stream of its own per element
+// (CHACHA_DOM_GALOIS, the element in the nonce): keys of different elements never share randomness, and a set's keys do not depend on its order
+static int gen_galois_impl(const crc_ctx *c, const ChaChaKey &ckey, const uint64_t *sk, int dbc, const uint64_t *elts, int n_elts, uint64_t *gk)
+{
+    if (!dbc_ok(dbc) || n_elts < 0) return CRC_ERR_INVALID_ARGUMENT;
+    for (int e = 0; e < n_elts; e++) if (!crc_galois_elt_valid(c, elts[e])) return CRC_ERR_INVALID_ARGUMENT;
+    const int n = c->n, k = c->k;
+    const size_t words = crc_evk_words(c, dbc);
+    std::vector<u64> sc((size_t)k * n);            // s in coefficient form
+    std::memcpy(sc.data(), sk, 8 * (size_t)k * n);
+    for (int j = 0; j < k; j++) h_ntt_inv(c->tabs[j], sc.data() + (size_t)j * n, n);
+    crc_host::parallel_for((size_t)n_elts, 1, [&](size_t e0, size_t e1) {
+    std::vector<u64> w((size_t)k * n);
+    for (size_t e = e0; e < e1; e++) {
+        const u64 g = elts[e];
+        for (int j = 0; j < k; j++) { galois_row(sc.data() + (size_t)j * n, w.data() + (size_t)j * n, n, g, c->q[j]); h_ntt_fwd(c->tabs[j], w.data() + (size_t)j * n, n); }
+        Rng r(ckey, (u32)g, (u32)(g >> 32), (u32)CHACHA_DOM_GALOIS << 24);
+        switch_key_impl(c, r, sk, w.data(), dbc, gk + e * words);
+    }
+    });
+    return CRC_OK;
+}
+extern "C" int crc_gen_galois_keys_key(const crc_ctx *c, const uint8_t *key, const uint64_t *sk, int dbc, const uint64_t *elts, int n_elts, uint64_t *gk)
+{
+    if (!c || !key || !sk || (n_elts > 0 && (!elts || !gk))) return CRC_ERR_INVALID_ARGUMENT;
+    return gen_galois_impl(c, load_key(key), sk, dbc, elts, n_elts, gk);
+}
+extern "C" int crc_gen_galois_keys(const crc_ctx *c, uint64_t seed, const uint64_t *sk, int dbc, const uint64_t *elts, int n_elts, uint64_t *gk)
+{
+    if (!c || !sk || (n_elts > 0 && (!elts || !gk))) return CRC_ERR_INVALID_ARGUMENT;
+    return gen_galois_impl(c, seed_key(seed), sk, dbc, elts, n_elts, gk);
 }
 
 static int encrypt_impl(const crc_ctx *c, const uint64_t *pk, const uint64_t *plain, size_t count, const ChaChaKey &key, uint64_t stream_base, uint64_t *ct)

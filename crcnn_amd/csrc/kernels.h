@@ -60,6 +60,9 @@ int k_multiply(crc_ctx *c, const u64 *x, const u64 *y, size_t cnt, u64 *y3, u64 
 int k_multiply64(crc_ctx *c, const u64 *x, const u64 *y, size_t cnt, u64 *y3, u64 *work, hipStream_t st, bool in_ntt, bool premul_c2);
 int k_relinearize(crc_ctx *c, const u64 *x3, size_t cnt, const u64 *evk, int dbc, u64 *y, u64 *work, u64 *kp, hipStream_t st, bool out_ntt = false,
                   bool c2_premul = false, bool keys_ready = false, const u64 *p2 = nullptr, const struct PolyTail *poly = nullptr, bool *poly_fused = nullptr);
+// kernels_galois.hip: sigma_g of size-2 coefficient-form ciphertexts as the size-3 rows k_relinearize(..., c2_premul = true) takes: (sigma(c0) [+ c0], 0 [c1],
+// sigma(c1) (q/q_i)^-1); g a valid Galois element, x and x3 disjoint and 16-byte aligned
+int k_galois_permute(crc_ctx *c, const u64 *x, size_t cnt, u64 g, bool accumulate, u64 *x3, hipStream_t st);
 int k_mac2(crc_ctx *c, const u64 *x, const u64 *w, u64 *y, const int *d_xoff, const int *d_toff, int B, int P, int F, int T, int in_cts,
            const u64 *bias_ntt, int gxd, int gyd, int gxf, int gyf, const unsigned *d_toffw, hipStream_t st, int xp = 0, int wp = 0, int yp = 0);
 int k_fold_pool(crc_ctx *c, const u64 *w, const u64 *bias, const u64 *div, u64 *wout, u64 *bout, int nf, int zd, int xf, int yf, int cxs, int cys,

@@ -26,6 +26,9 @@ void *getStream() { return g_stream; }
 static inline void *stream() { return g_stream; }
 vector<uint64_t> secret_key, public_key, ev_keys16_host;
 shared_ptr<DeviceBuffer> ev_keys16;
+vector<uint64_t> galois_elts, galois_keys_host;
+static shared_ptr<DeviceBuffer> g_galois_keys;              // the key blobs of galois_elts, dbc g_galois_dbc, resident in HBM
+static int g_galois_dbc = 0;
 static bool g_det = false;                                  // setDeterministicSeed(): tests / bench only
 static uint64_t g_det_seed = 0;
 static uint8_t g_master_key[CRC_KEY_BYTES];                 // fresh from the OS on every setParameters()
@@ -339,6 +342,7 @@ static const uint64_t *deviceKey(shared_ptr<DeviceBuffer> &d, uint64_t &fp, cons
 void delParameters()
 {
     ev_keys16.reset();
+    g_galois_keys.reset(); galois_elts.clear(); galois_keys_host.clear(); g_galois_dbc = 0;
     g_d_sk.reset(); g_d_pk.reset();
     g_scratch.reset(); g_wltile.reset(); g_xltile.reset();
     g_pool.flush();
@@ -629,6 +633,57 @@ vector<vector<double>> decryptImageSlots(const ciphertext3D &t, int S, double sc
     for (size_t j = 0; j < v.size(); j++) { out[j].resize(v[j].size()); for (size_t i = 0; i < v[j].size(); i++) out[j][i] = (double)v[j][i] / scale; }
     return out;
 }
+// ---- Galois keys, rotations, slot sums ------------------------------------------------------------------------------------
+static shared_ptr<DeviceBuffer> &ensure(shared_ptr<DeviceBuffer> &b, size_t bytes);
+void generateGaloisKeys(int dbc, vector<uint64_t> elts)
+{
+    if (secret_key.empty()) throw logic_error("cannot generate galois keys for unspecified secret key");
+    if (dbc < 1 || dbc > 60) throw invalid_argument("decomposition_bit_count is not in the valid range");
+    for (uint64_t g : elts) if (!crc_galois_elt_valid(ctx(), g)) throw invalid_argument("galois element is not valid");
+    vector<uint64_t> keys(elts.size() * crc_evk_words(ctx(), dbc));
+    // a domain of its own in the key generator's streams (the element in the nonce): the master key, or the deterministic seed next to the evaluation keys'
+    if (g_det) chk(crc_gen_galois_keys(ctx(), g_det_seed + 2, secret_key.data(), dbc, elts.data(), (int)elts.size(), keys.data()), "crc_gen_galois_keys");
+    else chk(crc_gen_galois_keys_key(ctx(), g_master_key, secret_key.data(), dbc, elts.data(), (int)elts.size(), keys.data()), "crc_gen_galois_keys_key");
+    g_galois_keys = make_shared<DeviceBuffer>(keys.size() * 8 + 8);
+    chk(crc_memcpy_h2d(ctx(), g_galois_keys->ptr, keys.data(), keys.size() * 8, stream()), "crc_memcpy_h2d");
+    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+    galois_elts = std::move(elts); galois_keys_host = std::move(keys); g_galois_dbc = dbc;
+}
+void generateGaloisKeys(int dbc)
+{
+    vector<uint64_t> elts(crc_galois_default_elts(ctx(), nullptr, 0));
+    chk(crc_galois_default_elts(ctx(), elts.data(), (int)elts.size()), "crc_galois_default_elts");
+    generateGaloisKeys(dbc, elts);
+}
+// what the three operations share: the checks in the reference's order, the result tensor, the scratch.  mode 0 rotate_rows(steps), 1 rotate_columns, 2 the slot sum
+static ciphertext3D galoisOp(const char *what, const ciphertext3D &t, int mode, int steps, int out_form)
+{
+    if (!crc_slots_supported(ctx())) throw logic_error("encryption parameters do not support batching");
+    if (!t.buf) throw invalid_argument(string(what) + ": empty tensor");
+    if ((t.form != CRC_COEFF && t.form != CRC_NTT) || (out_form != CRC_COEFF && out_form != CRC_NTT))
+        throw invalid_argument(string(what) + ": ciphertext forms only (CRC_COEFF / CRC_NTT)");
+    if (mode == 0 && !crc_galois_elt_rows(ctx(), steps)) throw invalid_argument("step count too large");
+    const uint64_t *d_gk = g_galois_keys ? (const uint64_t *)g_galois_keys->ptr : nullptr;
+    const int dbc = g_galois_dbc ? g_galois_dbc : 16, ne = (int)galois_elts.size();
+    if (mode == 0 || mode == 1) {                           // (the planner on the host: a missing key is the reference's exception, not a status)
+        int plan[64];
+        const uint64_t g = mode == 0 ? crc_galois_elt_rows(ctx(), steps) : crc_galois_elt_columns(ctx());
+        if (crc_galois_plan(ctx(), g, galois_elts.data(), ne, plan, 64) < 0) throw invalid_argument("galois key not present");
+    }
+    ciphertext3D out(t.B, t.zd, t.xd, t.yd, out_form);
+    const size_t cnt = t.count();
+    ensure(g_scratch, mode == 2 ? crc_sum_slots_work_bytes(ctx(), cnt, dbc) : crc_apply_galois_work_bytes(ctx(), cnt, dbc));
+    int rc;
+    if (mode == 0) rc = crc_rotate_rows_forms(ctx(), t.data(), t.form, cnt, steps, d_gk, galois_elts.data(), ne, dbc, out.data(), out_form, g_scratch->ptr, stream());
+    else if (mode == 1) rc = crc_rotate_columns_forms(ctx(), t.data(), t.form, cnt, d_gk, galois_elts.data(), ne, dbc, out.data(), out_form, g_scratch->ptr, stream());
+    else rc = crc_sum_slots_forms(ctx(), t.data(), t.form, cnt, d_gk, galois_elts.data(), ne, dbc, out.data(), out_form, g_scratch->ptr, stream());
+    if (mode == 2 && rc == CRC_ERR_INVALID_ARGUMENT) throw invalid_argument("galois key not present");      // (every other argument was checked above)
+    chk(rc, what);
+    return out;
+}
+ciphertext3D rotateRows(const ciphertext3D &t, int steps, int out_form) { return galoisOp("rotateRows", t, 0, steps, out_form); }
+ciphertext3D rotateColumns(const ciphertext3D &t, int out_form) { return galoisOp("rotateColumns", t, 1, 0, out_form); }
+ciphertext3D sumSlots(const ciphertext3D &t, int out_form) { return galoisOp("sumSlots", t, 2, 0, out_form); }
 vector<floatCube> decryptImages(const ciphertext3D &t)
 {
     const int n = N();

@@ -156,6 +156,20 @@ ciphertext3D encryptImageSlots(const std::vector<std::vector<int64_t>> &images, 
 std::vector<std::vector<int64_t>> decryptSlots(const ciphertext3D &t, int S);
 // ... divided by `scale` (Network::slot_scale() of the network that produced the tensor)
 std::vector<std::vector<double>> decryptImageSlots(const ciphertext3D &t, int S, double scale);
+// Galois keys and the operations that move data between slots (include/crcnn_hip.h, "Galois automorphisms": Evaluator::rotate_rows / rotate_columns of SEAL
+// 2.3.1, KeyGenerator::generate_galois_keys).  generateGaloisKeys builds the keys of the default set (2n - 1 and 3^(+-2^i): every rotation in at most log2 n key
+// switches) or of the given elements from the global secret_key, keeps them beside the evaluation keys and uploads them once; setParameters() / delParameters()
+// drop them.  std::invalid_argument for a dbc outside 1..60 or an invalid element
+void generateGaloisKeys(int dbc = 16);
+void generateGaloisKeys(int dbc, std::vector<uint64_t> elts);
+extern std::vector<uint64_t> galois_elts, galois_keys_host;             // the elements, and their key blobs [elts][crc_evk_words(dbc)]
+// Every ciphertext of the tensor rotated (CRC_COEFF / CRC_NTT in, out_form CRC_COEFF / CRC_NTT out; a new tensor of the same shape).  The n slots are a
+// 2 x n/2 matrix: rotateRows puts old slot (i + steps) mod n/2 of each row at slot i (to the left for positive steps), rotateColumns swaps the rows, sumSlots
+// leaves the sum of all n slots in every slot.  As in the reference: std::logic_error when the parameters do not support batching, std::invalid_argument for
+// |steps| >= n/2 ("step count too large"), a key that is not in the set ("galois key not present") and the other operand forms
+ciphertext3D rotateRows(const ciphertext3D &t, int steps, int out_form = CRC_COEFF);
+ciphertext3D rotateColumns(const ciphertext3D &t, int out_form = CRC_COEFF);
+ciphertext3D sumSlots(const ciphertext3D &t, int out_form = CRC_COEFF);
 
 // ---- layers (CrCNN/src/layer.h:10-31) ------------------------------------------------------------------------------
 class Layer {

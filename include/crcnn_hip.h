@@ -585,6 +585,67 @@ int crc_slots_refresh_sym_dev(crc_ctx *ctx, const uint64_t *d_sk_ntt, const uint
                               int out_form, uint64_t *d_ct_out, void *d_work, void *stream);
 int crc_slots_refresh_sym_dev_key(crc_ctx *ctx, const uint64_t *d_sk_ntt, const uint64_t *d_ct_in, size_t count, int in_form, uint64_t divisor,
                                   const uint8_t *h_key /*[32]*/, uint64_t stream_base, int out_form, uint64_t *d_ct_out, void *d_work, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Galois automorphisms: Evaluator::apply_galois / rotate_rows / rotate_columns (evaluator.cpp:1587-1834) and KeyGenerator::generate_galois_keys
+ * (keygenerator.cpp:325-455) -- the operations that move data between the slots of a batched ciphertext.
+ *
+ * A Galois element g is valid iff it is odd and 1 <= g < 2n.  sigma_g maps a coefficient row mod q as util::apply_galois does: out[(i g) mod n] = in[i] where bit
+ * log2 n of i g is clear, (q - in[i]) mod q where it is set.  apply_galois(ct, g) = (sigma(c0), 0) + KeySwitch_g(sigma(c1)): relinearisation's key switch (the
+ * same (q/q_i)^-1 premultiply, dbc-bit digits, lazy inner products, inverse transform) with the key of g.  The result is canonical: the reference's ciphertext
+ * bit for bit under the same key blob.  g = 1 is a copy and needs no key.
+ *
+ * Keys: one blob of crc_evk_words(ctx, dbc) words per element, laid out exactly as an evaluation-key blob with s^2 replaced by sigma_g(s).  A key SET is the
+ * host list elts[n_elts] and the blobs [n_elts][crc_evk_words] in the same order (d_gk: the blobs in device memory, 16-byte aligned).  Randomness: a ChaCha20
+ * stream per element (a domain of its own, the element in the nonce), so a key does not depend on which other elements the set holds.
+ *   crc_galois_elt_valid      1 / 0
+ *   crc_galois_elt_rows       the element of rotate_rows(steps): 3^steps mod 2n, a negative step count taken as n/2 - |steps|; 1 for steps = 0; 0 for
+ *                             |steps| >= n/2 ("step count too large")
+ *   crc_galois_elt_columns    2n - 1
+ *   crc_galois_default_elts   the set of generate_galois_keys(dbc): 2n - 1, then 3^(2^i), 3^(-2^i) mod 2n for i < log2 n - 1, in that order, each once (3^(n/4) is its own
+ *                             inverse: 2 log2 n - 2 elements).  Returns the count (out = NULL: only that); CRC_ERR_INVALID_ARGUMENT if cap is smaller
+ *   crc_gen_galois_keys[_key] host memory, any context; seed / key as crc_gen_evk[_key].  CRC_ERR_INVALID_ARGUMENT for an invalid element or dbc
+ *   crc_galois_plan           the steps apply_galois(g) takes with the keys of elts: indices into elts, in order, their count returned.  0 for g = 1; 1 where g
+ *                             is in the set; otherwise g = 3^o1 (-1)^o2, o1 replaced by n/2 - o1 over 3^-1 where that has the smaller Hamming weight, one step
+ *                             gen^(2^b) per set bit b of o1 from the low end, then 2n - 1 if o2 is set (evaluator.cpp:1623-1661).  CRC_ERR_INVALID_ARGUMENT
+ *                             if a step's key is absent ("galois key not present"), g is invalid or cap is too small (log2 n always suffices)
+ * Device entry points (asynchronous on `stream`; a host-only context gets CRC_ERR_INVALID_ARGUMENT as from every device entry point):
+ *   crc_galois_permute_dev    unit-test access to the kernel (kernels_galois.hip): coefficient-form d_x [count][2][k][n] -> d_x3 [count][3][k][n] =
+ *                             (sigma(c0), 0, sigma(c1) (q/q_i)^-1 mod q_i), with accumulate != 0 (sigma(c0) + c0, c1, the same) -- what crc_relinearize's
+ *                             key switch takes after its own premultiply
+ *   crc_apply_galois_forms    runs the plan's steps in order.  in_form / out_form: CRC_COEFF or CRC_NTT (an NTT-form side is transformed inside the call: the
+ *                             same ciphertext transformed).  d_work: crc_apply_galois_work_bytes(ctx, count, dbc) bytes, bounded in count (internal passes of
+ *                             whole ciphertexts as crc_relinearize; a step's prepared keys are made once per step, not per pass)
+ *   crc_rotate_rows_forms     crc_apply_galois_forms with crc_galois_elt_rows(steps): with the slot order of crc_slots_compose the n slots are a 2 x n/2 matrix
+ *                             and new slot i of each row = old slot (i + steps) mod n/2 -- a rotation to the left for positive steps
+ *   crc_rotate_columns_forms  crc_apply_galois_forms with 2n - 1: the two rows swap
+ *   crc_sum_slots_forms       y = x; y += rotate_rows(y, 2^j) for j < log2(n/2); y += rotate_columns(y): every slot of y holds the sum of all n slots of x mod
+ *                             t, in log2 n key switches.  Each y + rotate(y) is formed inside the step (no add pass) and equals crc_add(y, rotate(y)) bit for
+ *                             bit.  Every element (all in the default set) must have its own key in elts
+ * CRC_ERR_INVALID_ARGUMENT for a null or not 16-byte aligned d_x / d_y / d_gk, a d_y that overlaps d_x, a d_work that overlaps either, an invalid element or step count, a missing key, a
+ * form other than CRC_COEFF / CRC_NTT and a dbc outside 1..60 (work bytes: 0) -- nothing is launched then; the rotations and the slot sum give
+ * CRC_ERR_PARAMETERS first where crc_slots_supported is 0.  count = 0 is CRC_OK.
+ * ------------------------------------------------------------------------------------------------------------- */
+int crc_galois_elt_valid(const crc_ctx *ctx, uint64_t g);
+uint64_t crc_galois_elt_rows(const crc_ctx *ctx, int steps);
+uint64_t crc_galois_elt_columns(const crc_ctx *ctx);
+int crc_galois_default_elts(const crc_ctx *ctx, uint64_t *out, int cap);
+int crc_gen_galois_keys_key(const crc_ctx *ctx, const uint8_t *h_key, const uint64_t *h_sk_ntt, int dbc, const uint64_t *elts, int n_elts,
+                            uint64_t *h_gk /*[n_elts][crc_evk_words]*/);
+int crc_gen_galois_keys(const crc_ctx *ctx, uint64_t seed, const uint64_t *h_sk_ntt, int dbc, const uint64_t *elts, int n_elts,
+                        uint64_t *h_gk /*[n_elts][crc_evk_words]*/);
+int crc_galois_plan(const crc_ctx *ctx, uint64_t g, const uint64_t *elts, int n_elts, int *steps_out, int cap);
+int crc_galois_permute_dev(crc_ctx *ctx, const uint64_t *d_x, size_t count, uint64_t g, int accumulate, uint64_t *d_x3, void *stream);
+size_t crc_apply_galois_work_bytes(const crc_ctx *ctx, size_t count, int dbc);
+int crc_apply_galois_forms(crc_ctx *ctx, const uint64_t *d_x, int in_form, size_t count, uint64_t g, const uint64_t *d_gk, const uint64_t *elts, int n_elts,
+                           int dbc, uint64_t *d_y, int out_form, void *d_work, void *stream);
+int crc_rotate_rows_forms(crc_ctx *ctx, const uint64_t *d_x, int in_form, size_t count, int steps, const uint64_t *d_gk, const uint64_t *elts, int n_elts,
+                          int dbc, uint64_t *d_y, int out_form, void *d_work, void *stream);
+int crc_rotate_columns_forms(crc_ctx *ctx, const uint64_t *d_x, int in_form, size_t count, const uint64_t *d_gk, const uint64_t *elts, int n_elts, int dbc,
+                             uint64_t *d_y, int out_form, void *d_work, void *stream);
+size_t crc_sum_slots_work_bytes(const crc_ctx *ctx, size_t count, int dbc);
+int crc_sum_slots_forms(crc_ctx *ctx, const uint64_t *d_x, int in_form, size_t count, const uint64_t *d_gk, const uint64_t *elts, int n_elts, int dbc,
+                        uint64_t *d_y, int out_form, void *d_work, void *stream);
 /* FractionalEncoder::decode / encode (encoder.cpp:1226-1270, 1013-1076; 64 integer + 32 fractional coefficients, base 3: CrCNN/src/globals.cpp:52) on the
  * device: the doubles crc_decode returns for d_plain [count][n], and the dense plaintexts [count][n] crc_encode_f32 / _f64 make of the values -- the same IEEE
  * operations in the same order as the host encoder, contraction off. */
