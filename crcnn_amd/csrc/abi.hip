@@ -84,24 +84,15 @@ extern "C" int crc_multiply_plain(crc_ctx *c, uint64_t *d_ct, const uint64_t *d_
 }
 
 // ---- convolution / dense ------------------------------------------------------------------------------------------
-static bool conv_shape_ok(int xd, int yd, int xs, int ys, int xf, int yf)
-{
-    if (xd < 1 || yd < 1 || xs < 1 || ys < 1 || xf < 1 || yf < 1 || xf > xd || yf > yd) return false;
-    // the reference iterates i in [0, xd - max(xf,xs) + 1) step xs (Layer::computeBoundaries, layer.cpp:12-26) but sizes
-    // its result (xd-xf)/xs+1: when the stride exceeds the window the two disagree and trailing outputs stay empty
-    // Ciphertexts -- reject those shapes instead of inventing values.
-    const int xl = xd - (xf > xs ? xf : xs) + 1, yl = yd - (yf > ys ? yf : ys) + 1;
-    if (xl < 1 || yl < 1) return false;
-    return (xl + xs - 1) / xs == (xd - xf) / xs + 1 && (yl + ys - 1) / ys == (yd - yf) / ys + 1;
-}
+// (window geometry: window.h.  Every entry point builds its Window / LayerShape once from its integer parameters and checks it before anything divides by a stride)
 // Work of a layer on the vector-ALU kernels: [offsets of the P outputs][offsets of the T (+ 8) taps, in ciphertexts and in words][NTT copy of a coefficient-form input]
 struct ConvWork { int *xoff, *toff; unsigned *toffw; u64 *buf; };
-static ConvWork conv_layout(const crc_ctx *c, int B, int zd, int xd, int yd, int xf, int yf, int P, int in_form, WorkArena &a)
+static ConvWork conv_layout(const crc_ctx *c, int B, const LayerShape &s, int in_form, WorkArena &a)
 {
-    const size_t T = (size_t)zd * xf * yf;
+    const size_t T = (size_t)s.zd * s.w.xf * s.w.yf;
     ConvWork L{};
-    L.xoff = a.take<int>(P); L.toff = a.take<int>(T + 8); L.toffw = a.take<unsigned>(T + 8);
-    if (in_form == CRC_COEFF) L.buf = a.take<u64>((size_t)B * zd * xd * yd * crc_ct_words(c, 2));
+    L.xoff = a.take<int>(s.w.P()); L.toff = a.take<int>(T + 8); L.toffw = a.take<unsigned>(T + 8);
+    if (in_form == CRC_COEFF) L.buf = a.take<u64>((size_t)B * s.zd * s.w.xd * s.w.yd * crc_ct_words(c, 2));
     return L;
 }
 
@@ -141,8 +132,9 @@ extern "C" int crc_limb_pack_tensor_at(crc_ctx *c, const uint64_t *d_x, int in_f
 // one-channel convolutions (CRC_NTTL1, kernels_mfma1.hip)
 extern "C" int crc_limb_conv1_supported(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf)
 {
-    if (!c || nf < 1 || !conv_shape_ok(xd, yd, xs, ys, xf, yf)) return 0;
-    return k_limb_conv1_shape(c, zd, xd, yd, xs, ys, xf, yf, nf) ? 1 : 0;
+    const LayerShape s{{xd, yd, xs, ys, xf, yf}, zd, nf};
+    if (!c || nf < 1 || !s.w.ok()) return 0;
+    return k_limb_conv1_shape(c, s) ? 1 : 0;
 }
 extern "C" size_t crc_limb_conv1_weights_bytes(const crc_ctx *c) { return c ? k_limb_conv1_weights_bytes(c) : 0; }
 extern "C" size_t crc_limb_conv1_weights_bytes_for(const crc_ctx *c, int nf, int xf, int yf)
@@ -162,38 +154,38 @@ extern "C" int crc_limb_conv1_pack_weights(crc_ctx *c, const uint64_t *d_w_ntt, 
 }
 // images per internal pass: the y-expanded limb images and the slot-major result of a pass stay below ~16 GiB of work space (a dense consumer's flattened
 // limb tensor is converted from the whole batch's result at once: no sub-batching there)
-static int conv1_sub_batch(const crc_ctx *c, int B, int xd, int yd, int xf, int yf, int nf, int P, int out_form)
+static int conv1_sub_batch(const crc_ctx *c, int B, const Window &w, int nf, int out_form)
 {
     if (out_form == CRC_NTTL || B <= 1) return B;
-    const size_t per = k_limb_conv1_image_bytes(c, 1, xd, yd, xf, yf, nf) + (out_form == CRC_NTTLC ? 0 : 8 * k_limb_result_words(c, 1, nf, P));
+    const size_t per = k_limb_conv1_image_bytes(c, 1, w, nf) + (out_form == CRC_NTTLC ? 0 : 8 * k_limb_result_words(c, 1, nf, w.P()));
     const long long ev = c->tune.conv1_pass_bytes;                   // (the tests shrink it to cover the multi-pass path at small sizes: crc_ctx_set_tuning)
     const size_t cap = ev > 0 ? (size_t)ev : (size_t)16 << 30;
     const size_t fit = cap / (per ? per : 1);
     return (int)(fit < 1 ? 1 : fit > (size_t)B ? (size_t)B : fit);
 }
 // Work of a one-channel layer, for a pass of Bs images: [y-expanded limb images][slot-major result (not where the kernel writes the limb tensor itself)][NTT copy
-// of a coefficient-form sub-batch].  out_form: the form the passes produce.  xd x yd: the input image; xdi x ydi: the image the kernel reads (the box sums of a
+// of a coefficient-form sub-batch].  out_form: the form the passes produce.  in: the window on the input image; the kernel reads in.boxed(bxf, byf) (the box sums of a
 // boxed layer, crc_conv2d_box_forms; the input itself otherwise)
 struct Limb1Work { signed char *Xr; u64 *Ys, *buf; int Bs, out_form; };
-static Limb1Work limb1_layout(const crc_ctx *c, int B, int xd, int yd, int xdi, int ydi, int xf, int yf, int nf, int P, int in_form, int out_form, WorkArena &a)
+static Limb1Work limb1_layout(const crc_ctx *c, int B, const Window &in, int bxf, int byf, int nf, int in_form, int out_form, WorkArena &a)
 {
+    const Window w = in.boxed(bxf, byf);
+    const int P = w.P();
     Limb1Work L{};
     // a 1 x 1 result is a dense layer's input: the K-blocked form (kernels_mfma.hip), made from the slot-major result
     L.out_form = out_form == CRC_NTTLC && P == 1 ? CRC_NTTL : out_form;
-    L.Bs = conv1_sub_batch(c, B, xdi, ydi, xf, yf, nf, P, L.out_form);
-    L.Xr = a.take<signed char>(k_limb_conv1_image_bytes(c, L.Bs, xdi, ydi, xf, yf, nf));
+    L.Bs = conv1_sub_batch(c, B, w, nf, L.out_form);
+    L.Xr = a.take<signed char>(k_limb_conv1_image_bytes(c, L.Bs, w, nf));
     if (L.out_form != CRC_NTTLC) L.Ys = a.take<u64>(k_limb_result_words(c, L.Bs, nf, P));
-    if (in_form == CRC_COEFF) L.buf = a.take<u64>((size_t)L.Bs * xd * yd * crc_ct_words(c, 2));
+    if (in_form == CRC_COEFF) L.buf = a.take<u64>((size_t)L.Bs * in.xd * in.yd * crc_ct_words(c, 2));
     return L;
 }
-static int conv2d_limb1(crc_ctx *c, const uint64_t *d_x, const void *d_wl, const uint64_t *d_bias, int B, int xd, int yd, int xs, int ys, int xf, int yf,
-    int nf,
-                        int in_form, int out_form, uint64_t *d_y, void *d_work, hipStream_t st, int bxf = 1, int byf = 1)
+static int conv2d_limb1(crc_ctx *c, const uint64_t *d_x, const void *d_wl, const uint64_t *d_bias, int B, const Window &in, int nf, int in_form, int out_form,
+                        uint64_t *d_y, void *d_work, hipStream_t st, int bxf = 1, int byf = 1)
 {
-    const int xdi = xd - (bxf - 1) * xs, ydi = yd - (byf - 1) * ys;
-    const int xo = (xdi - xf) / xs + 1, yo = (ydi - yf) / ys + 1, P = xo * yo, in_cts = xd * yd;
+    const int P = in.boxed(bxf, byf).P(), in_cts = in.xd * in.yd;
     WorkArena a(d_work);
-    const Limb1Work L = limb1_layout(c, B, xd, yd, xdi, ydi, xf, yf, nf, P, in_form, out_form, a);
+    const Limb1Work L = limb1_layout(c, B, in, bxf, byf, nf, in_form, out_form, a);
     out_form = L.out_form;
     const size_t ctw = crc_ct_words(c, 2);
     for (int b0 = 0; b0 < B; b0 += L.Bs) {
@@ -201,8 +193,7 @@ static int conv2d_limb1(crc_ctx *c, const uint64_t *d_x, const void *d_wl, const
         const u64 *xn = d_x + (size_t)b0 * in_cts * ctw; bool packed = in_form == CRC_NTTP;
         if (in_form == CRC_COEFF) { RUN(k_ntt_ct(c, false, xn, L.buf, (size_t)Bn * in_cts, 2, false, st, nullptr, 0, 0, 0, 0)); xn = L.buf; packed = false; }
         RUN(k_limb_conv1(c, xn, packed, L.Xr, (const signed char *)d_wl, L.Ys, out_form == CRC_NTTLC ? (signed char *)d_y : nullptr, B, b0,
-            out_form != CRC_COEFF ? d_bias : nullptr,
-                         Bn, xd, yd, xs, ys, xf, yf, nf, st, bxf, byf));
+            out_form != CRC_COEFF ? d_bias : nullptr, Bn, in, nf, st, bxf, byf));
         if (out_form == CRC_NTTLC) continue;
         if (out_form == CRC_NTTL) return k_limb_result_to_limb(c, L.Ys, (signed char *)d_y, B, nf * P, st);     // (Bs == B)
         RUN(k_limb_result_to_rows(c, L.Ys, d_y + (size_t)b0 * nf * P * ctw, (size_t)Bn * nf * P * 2, out_form == CRC_NTTP, st));
@@ -212,51 +203,51 @@ static int conv2d_limb1(crc_ctx *c, const uint64_t *d_x, const void *d_wl, const
 }
 // Work of a layer on the limb GEMM: [slot-major result][limb form of a canonical or packed input][NTT copy of a coefficient-form input]
 struct LimbWork { u64 *Ys; signed char *Xl; u64 *buf; };
-static LimbWork limb_layout(const crc_ctx *c, int B, int zd, int xd, int yd, int nf, int P, int in_form, WorkArena &a)
+static LimbWork limb_layout(const crc_ctx *c, int B, const LayerShape &s, int in_form, WorkArena &a)
 {
     LimbWork L{};
-    L.Ys = a.take<u64>(k_limb_result_words(c, B, nf, P));
-    if (!limb_in(in_form)) L.Xl = a.take<signed char>(k_limb_tensor_bytes(c, B, zd, xd * yd));
-    if (in_form == CRC_COEFF) L.buf = a.take<u64>((size_t)B * zd * xd * yd * crc_ct_words(c, 2));
+    L.Ys = a.take<u64>(k_limb_result_words(c, B, s.nf, s.w.P()));
+    if (!limb_in(in_form)) L.Xl = a.take<signed char>(k_limb_tensor_bytes(c, B, s.zd, s.w.xd * s.w.yd));
+    if (in_form == CRC_COEFF) L.buf = a.take<u64>((size_t)B * s.zd * s.w.xd * s.w.yd * crc_ct_words(c, 2));
     return L;
 }
 extern "C" size_t crc_conv2d_forms_work_bytes(const crc_ctx *c, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int in_form,
     int w_form, int out_form)
 {
-    if (!c || !conv_shape_ok(xd, yd, xs, ys, xf, yf)) return 0;
-    const int P = ((xd - xf) / xs + 1) * ((yd - yf) / ys + 1);
+    const LayerShape s{{xd, yd, xs, ys, xf, yf}, zd, nf};
+    if (!c || !s.w.ok()) return 0;
     WorkArena a;
-    if (w_form == CRC_NTTL1) limb1_layout(c, B, xd, yd, xd, yd, xf, yf, nf, P, in_form, out_form, a);
-    else if (w_form == CRC_NTTL || w_form == CRC_NTTLS) limb_layout(c, B, zd, xd, yd, nf, P, in_form, a);
-    else conv_layout(c, B, zd, xd, yd, xf, yf, P, in_form, a);
+    if (w_form == CRC_NTTL1) limb1_layout(c, B, s.w, 1, 1, nf, in_form, out_form, a);
+    else if (w_form == CRC_NTTL || w_form == CRC_NTTLS) limb_layout(c, B, s, in_form, a);
+    else conv_layout(c, B, s, in_form, a);
     return a.bytes();
 }
 extern "C" size_t crc_conv2d_work_bytes(const crc_ctx *c, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int in_form)
 {
     return crc_conv2d_forms_work_bytes(c, B, zd, xd, yd, xs, ys, xf, yf, nf, in_form, CRC_NTT, CRC_COEFF);
 }
-static int conv2d_limb(crc_ctx *c, const uint64_t *d_x, const void *d_wl, const uint64_t *d_bias, int B, int zd, int xd, int yd, int xs, int ys, int xf,
-    int yf, int nf,
-                       int in_form, int out_form, uint64_t *d_y, void *d_work, hipStream_t st, bool scalar = false)
+static int conv2d_limb(crc_ctx *c, const uint64_t *d_x, const void *d_wl, const uint64_t *d_bias, int B, const LayerShape &s, int in_form, int out_form,
+                       uint64_t *d_y, void *d_work, hipStream_t st, bool scalar = false)
 {
+    const int zd = s.zd, nf = s.nf, npos = s.w.xd * s.w.yd;
     // scalar (w_form = CRC_NTTLS): the same steps on the merged GEMM of a modulus.  A convolution's tensor is the same bytes in either form; a dense layer's
     // (in_form / out_form = CRC_NTTLS) has its rows in image order e = s B + b.  Ys is the same bytes too, so every other out_form goes the way it always went
-    if (!(scalar ? k_scalar_supported(c, B, zd, xd, yd, xs, ys, xf, yf, nf) : crc_limb_supported(c, zd, xf, yf) != 0)) return CRC_ERR_UNSUPPORTED;
-    const int xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys + 1, P = xo * yo, in_cts = zd * xd * yd;
+    if (!(scalar ? k_scalar_supported(c, B, s) : crc_limb_supported(c, zd, s.w.xf, s.w.yf) != 0)) return CRC_ERR_UNSUPPORTED;
+    const int P = s.w.P(), in_cts = s.in_cts();
     WorkArena a(d_work);
-    const LimbWork L = limb_layout(c, B, zd, xd, yd, nf, P, in_form, a);
+    const LimbWork L = limb_layout(c, B, s, in_form, a);
     const signed char *xl = (const signed char *)d_x;
     if (!limb_in(in_form)) {
         const u64 *xn = d_x; bool packed = in_form == CRC_NTTP;
         if (in_form == CRC_COEFF) { RUN(k_ntt_ct(c, false, d_x, L.buf, (size_t)B * in_cts, 2, false, st, nullptr, 0, 0, 0, 0)); xn = L.buf; packed = false; }
-        RUN(k_limb_pack_tensor(c, xn, L.Xl, B, zd, xd * yd, packed, st, 0, 0, scalar));
+        RUN(k_limb_pack_tensor(c, xn, L.Xl, B, zd, npos, packed, st, 0, 0, scalar));
         xl = L.Xl;
     }
     // bias joins in the NTT domain unless the result goes back to coefficient form (then add_plain(bias) rides on the inverse transform's store)
     // hand-over to a dense layer (channels = (f, px, py) flattened), written by the kernel itself -- in its own row order: the scalar kernel writes CRC_NTTLS
     if (out_form == (scalar ? CRC_NTTLS : CRC_NTTL) && k_limb_direct_dense(P))
-        return k_limb_mac(c, xl, (const signed char *)d_wl, L.Ys, (signed char *)d_y, d_bias, B, zd, xd, yd, xs, ys, xf, yf, nf, st, scalar);
-    RUN(k_limb_mac(c, xl, (const signed char *)d_wl, L.Ys, nullptr, out_form != CRC_COEFF ? d_bias : nullptr, B, zd, xd, yd, xs, ys, xf, yf, nf, st, scalar));
+        return k_limb_mac(c, xl, (const signed char *)d_wl, L.Ys, (signed char *)d_y, d_bias, B, s, st, scalar);
+    RUN(k_limb_mac(c, xl, (const signed char *)d_wl, L.Ys, nullptr, out_form != CRC_COEFF ? d_bias : nullptr, B, s, st, scalar));
     if (limb_in(out_form)) return k_limb_result_to_limb(c, L.Ys, (signed char *)d_y, B, nf * P, st, out_form == CRC_NTTLS);     // ... or re-limbed from the slot-major result
     RUN(k_limb_result_to_rows(c, L.Ys, d_y, (size_t)B * nf * P * 2, out_form == CRC_NTTP, st));
     if (out_form == CRC_COEFF) RUN(k_ntt_ct(c, true, d_y, d_y, (size_t)B * nf * P, 2, false, st, d_bias, 1, (size_t)P, nf));
@@ -267,37 +258,36 @@ extern "C" int crc_conv2d_forms(crc_ctx *c, const uint64_t *d_x, const uint64_t 
                                 int xs, int ys, int xf, int yf, int nf, int in_form, int out_form, uint64_t *d_y, void *d_work, void *stream)
 {
     CHECK_CTX(c);
+    const LayerShape s{{xd, yd, xs, ys, xf, yf}, zd, nf};
     if (w_form == CRC_NTTL1) {
-        if (!d_x || !d_w || !d_y || !d_work || B < 0 || nf < 1 || !nform_ok(in_form) || !(lform_ok(out_form) || out_form == CRC_NTTLC) || !conv_shape_ok(xd,
-            yd, xs, ys, xf, yf))
+        if (!d_x || !d_w || !d_y || !d_work || B < 0 || nf < 1 || !nform_ok(in_form) || !(lform_ok(out_form) || out_form == CRC_NTTLC) || !s.w.ok())
             return CRC_ERR_INVALID_ARGUMENT;
-        if (!k_limb_conv1_shape(c, zd, xd, yd, xs, ys, xf, yf, nf)) return CRC_ERR_UNSUPPORTED;
+        if (!k_limb_conv1_shape(c, s)) return CRC_ERR_UNSUPPORTED;
         if (B == 0) return CRC_OK;
-        return conv2d_limb1(c, d_x, d_w, d_bias, B, xd, yd, xs, ys, xf, yf, nf, in_form, out_form, d_y, d_work, S(stream));
+        return conv2d_limb1(c, d_x, d_w, d_bias, B, s.w, nf, in_form, out_form, d_y, d_work, S(stream));
     }
     if (w_form == CRC_NTTL) {
-        if (!d_x || !d_w || !d_y || !d_work || B < 0 || zd < 1 || nf < 1 || !lform_ok(in_form) || !lform_ok(out_form) || !conv_shape_ok(xd, yd, xs, ys, xf,
-            yf)) return CRC_ERR_INVALID_ARGUMENT;
+        if (!d_x || !d_w || !d_y || !d_work || B < 0 || zd < 1 || nf < 1 || !lform_ok(in_form) || !lform_ok(out_form) || !s.w.ok())
+            return CRC_ERR_INVALID_ARGUMENT;
         if (B == 0) return CRC_OK;
-        return conv2d_limb(c, d_x, d_w, d_bias, B, zd, xd, yd, xs, ys, xf, yf, nf, in_form, out_form, d_y, d_work, S(stream));
+        return conv2d_limb(c, d_x, d_w, d_bias, B, s, in_form, out_form, d_y, d_work, S(stream));
     }
     if (w_form == CRC_NTTLS) {
         // in_form: a convolution's tensor as CRC_NTTL, a dense layer's (one position) as CRC_NTTLS -- the two dense layouts differ -- or rows in any form
         const bool in_ok = nform_ok(in_form) || (xd * yd == 1 ? in_form == CRC_NTTLS : in_form == CRC_NTTL);
-        if (!d_x || !d_w || !d_y || !d_work || B < 0 || zd < 1 || nf < 1 || !(lform_ok(out_form) || out_form == CRC_NTTLS) || !conv_shape_ok(xd, yd, xs, ys, xf,
-            yf) || !in_ok) return CRC_ERR_INVALID_ARGUMENT;
+        if (!d_x || !d_w || !d_y || !d_work || B < 0 || zd < 1 || nf < 1 || !(lform_ok(out_form) || out_form == CRC_NTTLS) || !s.w.ok() ||
+            !in_ok) return CRC_ERR_INVALID_ARGUMENT;
         if (B == 0) return CRC_OK;
-        return conv2d_limb(c, d_x, d_w, d_bias, B, zd, xd, yd, xs, ys, xf, yf, nf, in_form, out_form, d_y, d_work, S(stream), true);
+        return conv2d_limb(c, d_x, d_w, d_bias, B, s, in_form, out_form, d_y, d_work, S(stream), true);
     }
-    if (!d_x || !d_w || !d_y || !d_work || B < 0 || zd < 1 || nf < 1 || !nform_ok(in_form) || !nform_ok(out_form) || (w_form != CRC_NTT && w_form != CRC_NTTP))
-        return CRC_ERR_INVALID_ARGUMENT;
-    if (!conv_shape_ok(xd, yd, xs, ys, xf, yf)) return CRC_ERR_INVALID_ARGUMENT;
+    if (!d_x || !d_w || !d_y || !d_work || B < 0 || zd < 1 || nf < 1 || !nform_ok(in_form) || !nform_ok(out_form) || (w_form != CRC_NTT && w_form != CRC_NTTP) ||
+        !s.w.ok()) return CRC_ERR_INVALID_ARGUMENT;
     if (B == 0) return CRC_OK;
-    const int xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys + 1, P = xo * yo, T = zd * xf * yf, in_cts = zd * xd * yd;
+    const int P = s.w.P(), in_cts = s.in_cts();
     hipStream_t st = S(stream);
     WorkArena a(d_work);
-    const ConvWork L = conv_layout(c, B, zd, xd, yd, xf, yf, P, in_form, a);
-    RUN(k_conv_offsets(c, L.xoff, L.toff, L.toffw, P, T, in_cts, xd, yd, xs, ys, xf, yf, yo, st));
+    const ConvWork L = conv_layout(c, B, s, in_form, a);
+    RUN(k_conv_offsets(c, L.xoff, L.toff, L.toffw, s, st));
     const u64 *xn = d_x;
     int xp = in_form == CRC_NTTP;
     if (in_form == CRC_COEFF) {                   // transform_input_to_ntt, convolutionalLayer.cpp:95-148 (out of place: x is const)
@@ -307,8 +297,7 @@ extern "C" int crc_conv2d_forms(crc_ctx *c, const uint64_t *d_x, const uint64_t 
         xn = L.buf;
     }
     // sum of products in the NTT domain; bias joins here when the output stays NTT-resident
-    RUN(k_mac2(c, xn, d_w, d_y, L.xoff, L.toff, B, P, nf, T, in_cts, out_form != CRC_COEFF ? d_bias : nullptr, xd, yd, xf, yf, L.toffw, st, xp, w_form == CRC_NTTP,
-        out_form == CRC_NTTP));
+    RUN(k_mac2(c, xn, d_w, d_y, L.xoff, L.toff, B, s, out_form != CRC_COEFF ? d_bias : nullptr, L.toffw, st, xp, w_form == CRC_NTTP, out_form == CRC_NTTP));
     if (out_form == CRC_COEFF)                    // one inverse NTT per output ciphertext, add_plain(bias) fused into its store
         RUN(k_ntt_ct(c, true, d_y, d_y, (size_t)B * nf * P, 2, false, st, d_bias, 1, (size_t)P, nf));
     return CRC_OK;
@@ -318,18 +307,17 @@ extern "C" int crc_conv2d_forms(crc_ctx *c, const uint64_t *d_x, const uint64_t 
 extern "C" int crc_limb_conv1_box_supported(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int bxf, int byf)
 {
     if (!c || nf < 1 || bxf < 1 || byf < 1 || xs < 1 || ys < 1) return 0;
-    const int xdi = xd - (bxf - 1) * xs, ydi = yd - (byf - 1) * ys;
-    if (!conv_shape_ok(xd, yd, xs, ys, xf, yf) || !conv_shape_ok(xdi, ydi, xs, ys, xf, yf)) return 0;
-    return k_limb_conv1_box_shape(c, zd, xd, yd, xs, ys, xf, yf, nf, bxf, byf) ? 1 : 0;
+    const LayerShape s{{xd, yd, xs, ys, xf, yf}, zd, nf};
+    if (!s.w.ok() || !s.w.boxed(bxf, byf).ok()) return 0;
+    return k_limb_conv1_box_shape(c, s, bxf, byf) ? 1 : 0;
 }
 extern "C" size_t crc_conv2d_box_forms_work_bytes(const crc_ctx *c, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int bxf, int byf,
     int in_form, int w_form, int out_form)
 {
     if (c && bxf == 1 && byf == 1) return crc_conv2d_forms_work_bytes(c, B, zd, xd, yd, xs, ys, xf, yf, nf, in_form, w_form, out_form);
     if (w_form != CRC_NTTL1 || !crc_limb_conv1_box_supported(c, zd, xd, yd, xs, ys, xf, yf, nf, bxf, byf)) return 0;
-    const int xdi = xd - (bxf - 1) * xs, ydi = yd - (byf - 1) * ys, P = ((xdi - xf) / xs + 1) * ((ydi - yf) / ys + 1);
     WorkArena a;
-    limb1_layout(c, B, xd, yd, xdi, ydi, xf, yf, nf, P, in_form, out_form, a);
+    limb1_layout(c, B, {xd, yd, xs, ys, xf, yf}, bxf, byf, nf, in_form, out_form, a);
     return a.bytes();
 }
 extern "C" int crc_conv2d_box_forms(crc_ctx *c, const uint64_t *d_x, const uint64_t *d_w, int w_form, const uint64_t *d_bias, int B, int zd, int xd, int yd,
@@ -338,11 +326,12 @@ extern "C" int crc_conv2d_box_forms(crc_ctx *c, const uint64_t *d_x, const uint6
 {
     if (bxf == 1 && byf == 1) return crc_conv2d_forms(c, d_x, d_w, w_form, d_bias, B, zd, xd, yd, xs, ys, xf, yf, nf, in_form, out_form, d_y, d_work, stream);
     CHECK_CTX(c);
+    const Window in{xd, yd, xs, ys, xf, yf};
     if (!d_x || !d_w || !d_y || !d_work || B < 0 || nf < 1 || bxf < 1 || byf < 1 || !nform_ok(in_form) || !(lform_ok(out_form) || out_form == CRC_NTTLC) ||
-        !conv_shape_ok(xd, yd, xs, ys, xf, yf)) return CRC_ERR_INVALID_ARGUMENT;
+        !in.ok()) return CRC_ERR_INVALID_ARGUMENT;
     if (w_form != CRC_NTTL1 || !crc_limb_conv1_box_supported(c, zd, xd, yd, xs, ys, xf, yf, nf, bxf, byf)) return CRC_ERR_UNSUPPORTED;
     if (B == 0) return CRC_OK;
-    return conv2d_limb1(c, d_x, d_w, d_bias, B, xd, yd, xs, ys, xf, yf, nf, in_form, out_form, d_y, d_work, S(stream), bxf, byf);
+    return conv2d_limb1(c, d_x, d_w, d_bias, B, in, nf, in_form, out_form, d_y, d_work, S(stream), bxf, byf);
 }
 extern "C" int crc_conv2d(crc_ctx *c, const uint64_t *d_x, const uint64_t *d_w, const uint64_t *d_bias, int B, int zd, int xd, int yd,
                           int xs, int ys, int xf, int yf, int nf, int in_form, int out_form, uint64_t *d_y, void *d_work, void *stream)
@@ -396,15 +385,15 @@ extern "C" int crc_pool(crc_ctx *c, const uint64_t *d_x, int B, int zd, int xd, 
 {
     // form = CRC_NTTP: NTT-form input, result written in the MAC kernels' operand form (the layer behind is a conv / dense layer)
     CHECK_CTX(c);
-    if (!d_x || !d_y || B < 0 || zd < 1 || !nform_ok(form) || !conv_shape_ok(xd, yd, xs, ys, xf, yf)) return CRC_ERR_INVALID_ARGUMENT;
+    const Window w{xd, yd, xs, ys, xf, yf};
+    if (!d_x || !d_y || B < 0 || zd < 1 || !nform_ok(form) || !w.ok()) return CRC_ERR_INVALID_ARGUMENT;
     if (B == 0) return CRC_OK;
     hipStream_t st = S(stream);
-    const int xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys + 1;
-    if (form == CRC_NTTP) return k_pool(c, d_x, d_y, B, zd, xd, yd, xs, ys, xf, yf, d_div, st, 1);
-    if (form == CRC_NTT || !d_div) return k_pool(c, d_x, d_y, B, zd, xd, yd, xs, ys, xf, yf, form == CRC_NTT ? d_div : nullptr, st);
+    if (form == CRC_NTTP) return k_pool(c, d_x, d_y, B, zd, w, d_div, st, 1);
+    if (form == CRC_NTT || !d_div) return k_pool(c, d_x, d_y, B, zd, w, form == CRC_NTT ? d_div : nullptr, st);
     // coefficient form average pooling: add_many then multiply_plain(div_factor) (avgPoolingLayer.cpp:37-38)
-    RUN(k_pool(c, d_x, d_y, B, zd, xd, yd, xs, ys, xf, yf, nullptr, st));
-    const size_t cnt = (size_t)B * zd * xo * yo;
+    RUN(k_pool(c, d_x, d_y, B, zd, w, nullptr, st));
+    const size_t cnt = (size_t)B * zd * w.xo() * w.yo();
     RUN(k_ntt_ct(c, false, d_y, d_y, cnt, 2, false, st, nullptr, 0, 0));
     RUN(k_rowwise(c, d_y, d_div, cnt, 2, 2, 1, cnt, 0, st));
     return k_ntt_ct(c, true, d_y, d_y, cnt, 2, false, st, nullptr, 0, 0);
@@ -447,20 +436,21 @@ extern "C" int crc_batchnorm(crc_ctx *c, uint64_t *d_x, int B, int zd, int xd, i
 
 // ---- kernel selection: ONE statement of the policy for every host (netrun.py, crcnn_amd/host) ------------------------------------------------------
 // which multiply-accumulate kernel a conv / dense layer (dense: xd = yd = xf = yf = xs = ys = 1, zd = in_dim, nf = out_dim) runs on when launched on B images
-extern "C" int crc_plan_mac(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int B, int matrix_cores, int *w_form)
+static int plan_mac(const crc_ctx *c, const LayerShape &s, int B, int matrix_cores, int *w_form)
 {
-    if (!c || !w_form || zd < 1 || nf < 1 || !conv_shape_ok(xd, yd, xs, ys, xf, yf)) return CRC_ERR_INVALID_ARGUMENT;
+    const int zd = s.zd, nf = s.nf, xf = s.w.xf, yf = s.w.yf;
+    if (!c || !w_form || zd < 1 || nf < 1 || !s.w.ok()) return CRC_ERR_INVALID_ARGUMENT;
     bool packable = true;
     for (int i = 0; i < c->k; i++) if (c->tabs[i].m.bits > 55) packable = false;
     *w_form = packable ? CRC_NTTP : CRC_NTT;                      // mac3_kernel / mac2_kernel on 28-bit limb pairs (canonical residues above 55 bits)
     if (!matrix_cores || !packable) return CRC_OK;
     // one-channel convolutions (conv1, alone or with its pooling layer folded in) have their own matrix-core kernel
-    if (zd == 1) { if (k_limb_conv1_shape(c, zd, xd, yd, xs, ys, xf, yf, nf)) *w_form = CRC_NTTL1; return CRC_OK; }
+    if (zd == 1) { if (k_limb_conv1_shape(c, s)) *w_form = CRC_NTTL1; return CRC_OK; }
     // the limb GEMM pays from 8 reduction steps of 32 channels on (below that its fixed costs per output tile and the channel padding eat the gain), and only
     // with at least half a 64-row tile of rows = (image, pixel, poly) per launch: with fewer, most of every MFMA is padding and every slot's weights are
     // streamed for a handful of rows (PlainModelWoPad at 6 images per launch: fc4 0.23 ms per image on mac3_kernel against 1.59)
     const int min_steps = c->tune.mfma_min_steps > 0 ? c->tune.mfma_min_steps : 8;
-    const long long P = (long long)((xd - xf) / xs + 1) * ((yd - yf) / ys + 1);
+    const long long P = s.w.P64();
     // ... a full tile of rows for layers of fewer than 24 filters: the limb form pads the filters to 64, so a 10-filter layer -- CrCNN's fc4 -- spends 6x its
     // canonical bytes and 5/6 of its MFMAs on zeros (PlainModelWoPad's fc4 at 24 images: 14 GiB of weights, 0.16 against 0.11 ms per image on the vector-ALU
     // kernel; with 64 rows and more -- PlainModelTiny at 128 images, ApproxPlainModel at 32 -- it still wins, not least because the layer in front hands its
@@ -472,6 +462,10 @@ extern "C" int crc_plan_mac(const crc_ctx *c, int zd, int xd, int yd, int xs, in
         rows >= min_rows)) *w_form = CRC_NTTL;
     return CRC_OK;
 }
+extern "C" int crc_plan_mac(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int B, int matrix_cores, int *w_form)
+{
+    return plan_mac(c, {{xd, yd, xs, ys, xf, yf}, zd, nf}, B, matrix_cores, w_form);
+}
 // ---- scalar form (CRC_NTTLS): slot-batched networks, whose weights are constant polynomials -----------------------------------------------------
 extern "C" size_t crc_scalar_weights_bytes(const crc_ctx *c, int nf, int zd, int xf, int yf)
 {
@@ -479,8 +473,9 @@ extern "C" size_t crc_scalar_weights_bytes(const crc_ctx *c, int nf, int zd, int
 }
 extern "C" int crc_scalar_supported(const crc_ctx *c, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf)
 {
-    if (!c || B < 1 || zd < 1 || nf < 1 || !conv_shape_ok(xd, yd, xs, ys, xf, yf)) return 0;
-    return k_scalar_supported(c, B, zd, xd, yd, xs, ys, xf, yf, nf) ? 1 : 0;
+    const LayerShape s{{xd, yd, xs, ys, xf, yf}, zd, nf};
+    if (!c || B < 1 || zd < 1 || nf < 1 || !s.w.ok()) return 0;
+    return k_scalar_supported(c, B, s) ? 1 : 0;
 }
 extern "C" int crc_scalar_pack_weights(crc_ctx *c, const uint64_t *d_w, int w_stride, int nf, int zd, int xf, int yf, void *d_ws, int *constant, void *stream)
 {
@@ -494,8 +489,9 @@ extern "C" int crc_scalar_pack_weights(crc_ctx *c, const uint64_t *d_w, int w_st
 // convolutions keep their own kernel, moduli above 55 bits theirs.  The rows guard of crc_plan_mac does not apply: the merged GEMM has n B 2P rows.
 extern "C" int crc_plan_mac_scalar(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int B, int *w_form)
 {
-    RUN(crc_plan_mac(c, zd, xd, yd, xs, ys, xf, yf, nf, B, 1, w_form));
-    if (c->tune.scalar_mac && zd >= 2 && k_scalar_supported(c, B < 1 ? 1 : B, zd, xd, yd, xs, ys, xf, yf, nf)) *w_form = CRC_NTTLS;
+    const LayerShape s{{xd, yd, xs, ys, xf, yf}, zd, nf};
+    RUN(plan_mac(c, s, B, 1, w_form));
+    if (c->tune.scalar_mac && zd >= 2 && k_scalar_supported(c, B < 1 ? 1 : B, s)) *w_form = CRC_NTTLS;
     return CRC_OK;
 }
 // should a (sum / average) pooling layer be folded into the convolution in front of it (crc_conv2d_fold_pool: exact)?  Cost in units of one multiply-accumulate
@@ -505,14 +501,15 @@ extern "C" int crc_plan_mac_scalar(const crc_ctx *c, int zd, int xd, int yd, int
 extern "C" int crc_plan_fold_pool(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int pxs, int pys, int pxf, int pyf,
     int *fold)
 {
-    if (!c || !fold || zd < 1 || nf < 1 || !conv_shape_ok(xd, yd, xs, ys, xf, yf) || pxs < 1 || pys < 1 || pxf < 1 || pyf < 1) return CRC_ERR_INVALID_ARGUMENT;
+    const Window w{xd, yd, xs, ys, xf, yf};
+    if (!c || !fold || zd < 1 || nf < 1 || !w.ok() || pxs < 1 || pys < 1 || pxf < 1 || pyf < 1) return CRC_ERR_INVALID_ARGUMENT;
     *fold = 0;
-    const int xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys + 1;
-    const int xf2 = (pxf - 1) * xs + xf, yf2 = (pyf - 1) * ys + yf, xs2 = xs * pxs, ys2 = ys * pys;
-    if (xf2 > xd || yf2 > yd || pxf > xo || pyf > yo) return CRC_OK;
-    const int xo2 = (xd - xf2) / xs2 + 1, yo2 = (yd - yf2) / ys2 + 1;
-    if (xo2 != (xo - pxf) / pxs + 1 || yo2 != (yo - pyf) / pys + 1) return CRC_OK;           // the folded convolution must produce exactly the pooled tensor
-    const long long fpad = (nf + 7) / 8 * 8, T1 = (long long)zd * xf * yf, T2 = (long long)zd * xf2 * yf2;
+    const int xo = w.xo(), yo = w.yo();
+    const Window w2 = w.fold(pxs, pys, pxf, pyf), pool{xo, yo, pxs, pys, pxf, pyf};
+    if (w2.xf > w.xd || w2.yf > w.yd || pxf > xo || pyf > yo) return CRC_OK;
+    const int xo2 = w2.xo(), yo2 = w2.yo();
+    if (xo2 != pool.xo() || yo2 != pool.yo()) return CRC_OK;           // the folded convolution must produce exactly the pooled tensor
+    const long long fpad = (nf + 7) / 8 * 8, T1 = (long long)zd * w.xf * w.yf, T2 = (long long)zd * w2.xf * w2.yf;
     const long long cost_sep = fpad * xo * yo * (T1 + 24) + (long long)nf * xo2 * yo2 * 10 * (pxf * pyf + 1);
     const long long cost_fused = fpad * xo2 * yo2 * (T2 + 24);
     *fold = cost_fused < cost_sep ? 1 : 0;
@@ -525,11 +522,12 @@ extern "C" int crc_plan_fold_pool(const crc_ctx *c, int zd, int xd, int yd, int 
 // polys), and a term there costs 8/5 of the limb GEMM's (PlainModelTiny at n = 4096, 128 images per launch, kernel + image pack: pixel-major 6 x 6 35.9 ms for 18
 // tiles, plane-major 8 x 8 44.5 ms for 16, against 92.6 ms for the limb GEMM's 64 x 16 outputs of 1152 + 24 terms -- 1.59 and 1.60; profiles/conv1_box_ab.txt.
 // 25/16 before those measurements)
-static long long plan_mac_cost(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int B, int matrix_cores)
+static long long plan_mac_cost(const crc_ctx *c, const LayerShape &s, int B, int matrix_cores)
 {
+    const int zd = s.zd, nf = s.nf, xf = s.w.xf, yf = s.w.yf;
     int wf = CRC_NTT;
-    if (crc_plan_mac(c, zd, xd, yd, xs, ys, xf, yf, nf, B, matrix_cores, &wf) != CRC_OK) return -1;
-    const long long P = (long long)((xd - xf) / xs + 1) * ((yd - yf) / ys + 1);
+    if (plan_mac(c, s, B, matrix_cores, &wf) != CRC_OK) return -1;
+    const long long P = s.w.P64();
     if (wf == CRC_NTTL1) return 32 * ((2 * P + 15) / 16 * 8) * ((k_limb_conv1_form(c, xf, yf, nf) == 2 ? 40 : 64) + 24) * 8 / 5;
     if (wf == CRC_NTTL) return (long long)(nf + 31) / 32 * 32 * P * ((long long)k_limb_steps(zd, xf, yf) * 32 + 24);
     return (long long)(nf + 7) / 8 * 8 * P * ((long long)zd * xf * yf + 24);
@@ -545,30 +543,31 @@ static long long plan_mac_cost(const crc_ctx *c, int zd, int xd, int yd, int xs,
 extern "C" int crc_plan_hoist_pool(const crc_ctx *c, int uzd, int uxd, int uyd, int uxs, int uys, int uxf, int uyf, int unf, int zd, int xd, int yd, int xs,
                                    int ys, int xf, int yf, int nf, int pxs, int pys, int pxf, int pyf, int B, int matrix_cores, int *hoist)
 {
-    if (!c || !hoist || zd < 1 || nf < 1 || !conv_shape_ok(xd, yd, xs, ys, xf, yf) || pxs < 1 || pys < 1 || pxf < 1 || pyf < 1) return CRC_ERR_INVALID_ARGUMENT;
+    const LayerShape up{{uxd, uyd, uxs, uys, uxf, uyf}, uzd, unf}, conv{{xd, yd, xs, ys, xf, yf}, zd, nf};
+    const Window &w = conv.w;
+    if (!c || !hoist || zd < 1 || nf < 1 || !w.ok() || pxs < 1 || pys < 1 || pxf < 1 || pyf < 1) return CRC_ERR_INVALID_ARGUMENT;
     *hoist = 0;
     if (!c->tune.hoist_pool || xs != 1 || ys != 1 || pxs * pys == 1) return CRC_OK;
     int fold = 0;
     { const int rc = crc_plan_fold_pool(c, zd, xd, yd, xs, ys, xf, yf, nf, pxs, pys, pxf, pyf, &fold); if (rc != CRC_OK) return rc; }
     if (!fold) return CRC_OK;
-    if (uzd < 1 || unf != zd || !conv_shape_ok(uxd, uyd, uxs, uys, uxf, uyf) || (uxd - uxf) / uxs + 1 != xd || (uyd - uyf) / uys + 1 != yd) return CRC_OK;
-    // the layer in front with the sum pool folded in: S = [zd][xd - pxf + 1][yd - pyf + 1]
-    const int uxf2 = (pxf - 1) * uxs + uxf, uyf2 = (pyf - 1) * uys + uyf, sxd = xd - pxf + 1, syd = yd - pyf + 1;
-    if (uxf2 > uxd || uyf2 > uyd || !conv_shape_ok(uxd, uyd, uxs, uys, uxf2, uyf2)) return CRC_OK;
-    if ((uxd - uxf2) / uxs + 1 != sxd || (uyd - uyf2) / uys + 1 != syd) return CRC_OK;
-    // the convolution over S must produce exactly the pooled tensor
-    const int xo = xd - xf + 1, yo = yd - yf + 1;
-    if (!conv_shape_ok(sxd, syd, pxs, pys, xf, yf) || (sxd - xf) / pxs + 1 != (xo - pxf) / pxs + 1 || (syd - yf) / pys + 1 != (yo - pyf) / pys + 1) return CRC_OK;
+    if (uzd < 1 || unf != zd || !up.w.ok() || up.w.xo() != xd || up.w.yo() != yd) return CRC_OK;
+    // the layer in front with the sum pool folded in: S = [zd][xd - pxf + 1][yd - pyf + 1], the stride-1 box sums of the convolution's image, which the
+    // convolution's own window then reads at the pool's stride
+    const LayerShape up_folded{up.w.fold(1, 1, pxf, pyf), uzd, unf}, folded{w.fold(pxs, pys, pxf, pyf), zd, nf};
+    LayerShape hoisted{w.boxed(pxf, pyf), zd, nf};
+    hoisted.w.xs = pxs; hoisted.w.ys = pys;
+    if (up_folded.w.xf > uxd || up_folded.w.yf > uyd || !up_folded.w.ok()) return CRC_OK;
+    if (up_folded.w.xo() != hoisted.w.xd || up_folded.w.yo() != hoisted.w.yd) return CRC_OK;
+    // the convolution over S must produce exactly the pooled tensor (pool: on the convolution's own output, xd - xf + 1 at its stride of 1)
+    const Window pool{xd - xf + 1, yd - yf + 1, pxs, pys, pxf, pyf};
+    if (!hoisted.w.ok() || hoisted.w.xo() != pool.xo() || hoisted.w.yo() != pool.yo()) return CRC_OK;
     int uf = CRC_NTT, uf2 = CRC_NTT;
-    if (crc_plan_mac(c, uzd, uxd, uyd, uxs, uys, uxf, uyf, unf, B, matrix_cores, &uf) != CRC_OK) return CRC_OK;
-    if (crc_plan_mac(c, uzd, uxd, uyd, uxs, uys, uxf2, uyf2, unf, B, matrix_cores, &uf2) != CRC_OK) return CRC_OK;
+    if (plan_mac(c, up, B, matrix_cores, &uf) != CRC_OK || plan_mac(c, up_folded, B, matrix_cores, &uf2) != CRC_OK) return CRC_OK;
     if ((uf == CRC_NTTL1 || uf == CRC_NTTL) && uf2 != uf) return CRC_OK;
-    const int xf2 = xf + pxf - 1, yf2 = yf + pyf - 1;
-    const long long folded = plan_mac_cost(c, uzd, uxd, uyd, uxs, uys, uxf, uyf, unf, B, matrix_cores) +
-                             plan_mac_cost(c, zd, xd, yd, pxs, pys, xf2, yf2, nf, B, matrix_cores);
-    const long long hoisted = plan_mac_cost(c, uzd, uxd, uyd, uxs, uys, uxf2, uyf2, unf, B, matrix_cores) +
-                              plan_mac_cost(c, zd, sxd, syd, pxs, pys, xf, yf, nf, B, matrix_cores);
-    *hoist = hoisted < folded ? 1 : 0;
+    const long long cost_folded = plan_mac_cost(c, up, B, matrix_cores) + plan_mac_cost(c, folded, B, matrix_cores);
+    const long long cost_hoisted = plan_mac_cost(c, up_folded, B, matrix_cores) + plan_mac_cost(c, hoisted, B, matrix_cores);
+    *hoist = cost_hoisted < cost_folded ? 1 : 0;
     return CRC_OK;
 }
 
@@ -585,18 +584,18 @@ extern "C" int crc_plan_hoist_pool(const crc_ctx *c, int uzd, int uxd, int uyd, 
 extern "C" int crc_plan_conv1_box(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int bxf, int byf, int B, int matrix_cores,
                                   int *box)
 {
-    if (!c || !box || zd < 1 || nf < 1 || bxf < 1 || byf < 1 || !conv_shape_ok(xd, yd, xs, ys, xf, yf)) return CRC_ERR_INVALID_ARGUMENT;
+    const Window w{xd, yd, xs, ys, xf, yf};
+    if (!c || !box || zd < 1 || nf < 1 || bxf < 1 || byf < 1 || !w.ok()) return CRC_ERR_INVALID_ARGUMENT;
     *box = 0;
     if (!c->tune.conv1_box || !matrix_cores || bxf * byf == 1) return CRC_OK;
     if (!crc_limb_conv1_box_supported(c, zd, xd, yd, xs, ys, xf, yf, nf, bxf, byf)) return CRC_OK;
-    const int xf2 = (bxf - 1) * xs + xf, yf2 = (byf - 1) * ys + yf, xdi = xd - (bxf - 1) * xs, ydi = yd - (byf - 1) * ys;
-    if (!conv_shape_ok(xd, yd, xs, ys, xf2, yf2)) return CRC_OK;
+    const LayerShape enlarged{w.fold(1, 1, bxf, byf), zd, nf}, boxed{w.boxed(bxf, byf), zd, nf};
+    if (!enlarged.w.ok()) return CRC_OK;
     int wf = CRC_NTT;
-    if (crc_plan_mac(c, zd, xdi, ydi, xs, ys, xf, yf, nf, B, matrix_cores, &wf) != CRC_OK || wf != CRC_NTTL1) return CRC_OK;
-    const long long enlarged = plan_mac_cost(c, zd, xd, yd, xs, ys, xf2, yf2, nf, B, matrix_cores);
-    const long long boxed = plan_mac_cost(c, zd, xdi, ydi, xs, ys, xf, yf, nf, B, matrix_cores) +
-                            (long long)xdi * ydi * 2 * (bxf * byf - 1) * PLAN_BOX_READ;
-    *box = enlarged >= 0 && boxed < enlarged ? 1 : 0;
+    if (plan_mac(c, boxed, B, matrix_cores, &wf) != CRC_OK || wf != CRC_NTTL1) return CRC_OK;
+    const long long cost_enlarged = plan_mac_cost(c, enlarged, B, matrix_cores);
+    const long long cost_boxed = plan_mac_cost(c, boxed, B, matrix_cores) + (long long)boxed.w.xd * boxed.w.yd * 2 * (bxf * byf - 1) * PLAN_BOX_READ;
+    *box = cost_enlarged >= 0 && cost_boxed < cost_enlarged ? 1 : 0;
     return CRC_OK;
 }
 
@@ -1014,14 +1013,14 @@ extern "C" int crc_square_pool_relin_supported(const crc_ctx *c, int dbc, int xf
 {
     return c && dbc_ok(dbc) && c->tune.sq_path != 1 && c->tune.relin_path != 1 && k_relin64_pool_supported(c, dbc, xf * yf) ? 1 : 0;
 }
-static size_t pool_act_bytes(const crc_ctx *c, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int dbc, int regions)
+static size_t pool_act_bytes(const crc_ctx *c, int B, int zd, const Window &w, int dbc, int regions)
 {
-    if (!c || xd < xf || yd < yf || xs < 1 || ys < 1 || !dbc_ok(dbc)) return 0;
-    return act_bytes(c, (size_t)B * zd, (size_t)xd * yd, (size_t)((xd - xf) / xs + 1) * ((yd - yf) / ys + 1), dbc, regions);
+    if (!c || w.xd < w.xf || w.yd < w.yf || w.xs < 1 || w.ys < 1 || !dbc_ok(dbc)) return 0;
+    return act_bytes(c, (size_t)B * zd, (size_t)w.xd * w.yd, (size_t)w.P64(), dbc, regions);
 }
 extern "C" size_t crc_square_pool_relin_work_bytes(const crc_ctx *c, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int dbc)
 {
-    return pool_act_bytes(c, B, zd, xd, yd, xs, ys, xf, yf, dbc, 0);
+    return pool_act_bytes(c, B, zd, {xd, yd, xs, ys, xf, yf}, dbc, 0);
 }
 extern "C" int crc_square_pool_relin_forms(crc_ctx *c, const uint64_t *d_x, int in_form, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf,
                                            const uint64_t *d_evk, int dbc, const uint64_t *d_div_ntt, uint64_t *d_y, int out_form, void *d_work, void *stream)
@@ -1030,7 +1029,7 @@ extern "C" int crc_square_pool_relin_forms(crc_ctx *c, const uint64_t *d_x, int 
     if (d_div_ntt && out_form != CRC_NTT) return CRC_ERR_INVALID_ARGUMENT;           // the divisor multiplies slot-wise
     if (B < 0 || zd < 1 || xd < xf || yd < yf || xs < 1 || ys < 1 || xf < 1 || yf < 1) return CRC_ERR_INVALID_ARGUMENT;
     if (!crc_square_pool_relin_supported(c, dbc, xf, yf)) return CRC_ERR_UNSUPPORTED;
-    const PoolGeom pg{xd, yd, xs, ys, xf, yf, (xd - xf) / xs + 1, (yd - yf) / ys + 1};
+    const PoolGeom pg = pool_geom({xd, yd, xs, ys, xf, yf});
     const size_t planes = (size_t)B * zd, pin = (size_t)xd * yd, pout = (size_t)pg.xo * pg.yo;
     WorkArena a(d_work);
     const ActWork L = act_layout(c, planes, pin, pout, dbc, 0, a);
@@ -1074,7 +1073,7 @@ extern "C" int crc_poly2_relin_forms(crc_ctx *c, const uint64_t *d_x, int in_for
         const PolyTail pt{xin, d_p1_ntt, d_p0_ntt};
         bool fused = false;
         RUN(k_relinearize(c, L.y3, ch, d_evk, dbc, yo, L.rest, L.kp, S(stream), true, true, o != 0, d_p2_ntt, &pt, &fused));
-        if (!fused) RUN(k_poly2_tail(c, yo, xin, ch, 1, 1, 1, 1, 1, 1, d_p2_ntt, d_p1_ntt, d_p0_ntt, S(stream)));
+        if (!fused) RUN(k_poly2_tail(c, yo, xin, ch, {1, 1, 1, 1, 1, 1}, d_p2_ntt, d_p1_ntt, d_p0_ntt, S(stream)));
     }
     if (out_form == CRC_COEFF) RUN(crc_ntt_inv(c, d_y, count, 2, stream));
     return CRC_OK;
@@ -1082,7 +1081,7 @@ extern "C" int crc_poly2_relin_forms(crc_ctx *c, const uint64_t *d_x, int in_for
 extern "C" int crc_poly2_pool_relin_supported(const crc_ctx *c, int dbc, int xf, int yf) { return crc_square_pool_relin_supported(c, dbc, xf, yf); }
 extern "C" size_t crc_poly2_pool_relin_work_bytes(const crc_ctx *c, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int dbc)
 {
-    return pool_act_bytes(c, B, zd, xd, yd, xs, ys, xf, yf, dbc, ACT_XH);
+    return pool_act_bytes(c, B, zd, {xd, yd, xs, ys, xf, yf}, dbc, ACT_XH);
 }
 extern "C" int crc_poly2_pool_relin_forms(crc_ctx *c, const uint64_t *d_x, int in_form, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf,
                                           const uint64_t *d_evk, int dbc, const uint64_t *d_p2_ntt, const uint64_t *d_p1_ntt, const uint64_t *d_p0_ntt,
@@ -1093,7 +1092,7 @@ extern "C" int crc_poly2_pool_relin_forms(crc_ctx *c, const uint64_t *d_x, int i
     if (!crc_poly2_pool_relin_supported(c, dbc, xf, yf)) return CRC_ERR_UNSUPPORTED;
     if (!d_p2_ntt && !d_p1_ntt && !d_p0_ntt)
         return crc_square_pool_relin_forms(c, d_x, in_form, B, zd, xd, yd, xs, ys, xf, yf, d_evk, dbc, nullptr, d_y, out_form, d_work, stream);
-    const PoolGeom pg{xd, yd, xs, ys, xf, yf, (xd - xf) / xs + 1, (yd - yf) / ys + 1};
+    const PoolGeom pg = pool_geom({xd, yd, xs, ys, xf, yf});
     const size_t planes = (size_t)B * zd, pin = (size_t)xd * yd, pout = (size_t)pg.xo * pg.yo, ctw = crc_ct_words(c, 2);
     if (d_p1_ntt && in_form == CRC_NTT && ranges_overlap(d_x, 8 * planes * pin * ctw, d_y, 8 * planes * pout * ctw)) return CRC_ERR_INVALID_ARGUMENT;
     const bool own_xh = d_p1_ntt && in_form == CRC_COEFF;
@@ -1109,7 +1108,7 @@ extern "C" int crc_poly2_pool_relin_forms(crc_ctx *c, const uint64_t *d_x, int i
         if (o == 0) RUN(k_relin64_prepare_keys(c, d_evk, dbc, L.kp, L.rest, S(stream)));
         const PolyTail pt{xin, d_p1_ntt, d_p0_ntt};
         RUN(k_relinearize64(c, L.y3, 3, 2, L.y3, 3, cout, dbc, yo, L.rest, L.kp, S(stream), true, &pg, fused ? d_p2_ntt : nullptr, fused ? &pt : nullptr));
-        if (!fused) RUN(k_poly2_tail(c, yo, xin, pp, xd, yd, xs, ys, xf, yf, d_p2_ntt, d_p1_ntt, d_p0_ntt, S(stream)));
+        if (!fused) RUN(k_poly2_tail(c, yo, xin, pp, {xd, yd, xs, ys, xf, yf}, d_p2_ntt, d_p1_ntt, d_p0_ntt, S(stream)));
     }
     if (out_form == CRC_COEFF) RUN(crc_ntt_inv(c, d_y, planes * pout, 2, stream));
     return CRC_OK;
@@ -1167,8 +1166,8 @@ extern "C" int crc_poly3_relin_forms(crc_ctx *c, const uint64_t *d_x, int in_for
         RUN(k_relinearize(c, L.y3, ch, d_evk, dbc, L.s, L.rest, L.kp, S(stream), true, true, o != 0));
         RUN(k_multiply(c, L.s, xin, ch, L.y3, L.rest, S(stream), true, true));
         RUN(k_relinearize(c, L.y3, ch, d_evk, dbc, yo, L.rest, L.kp, S(stream), true, true, true));
-        RUN(k_poly2_tail(c, yo, L.s, ch, 1, 1, 1, 1, 1, 1, d_p3_ntt, d_p2_ntt, nullptr, S(stream)));
-        RUN(k_poly2_tail(c, yo, xin, ch, 1, 1, 1, 1, 1, 1, nullptr, d_p1_ntt, d_p0_ntt, S(stream)));
+        RUN(k_poly2_tail(c, yo, L.s, ch, {1, 1, 1, 1, 1, 1}, d_p3_ntt, d_p2_ntt, nullptr, S(stream)));
+        RUN(k_poly2_tail(c, yo, xin, ch, {1, 1, 1, 1, 1, 1}, nullptr, d_p1_ntt, d_p0_ntt, S(stream)));
     }
     if (out_form == CRC_COEFF) RUN(crc_ntt_inv(c, d_out, count, 2, stream));
     return CRC_OK;

@@ -1,6 +1,7 @@
 // kernels.h -- launchers implemented in kernels.hip / kernels_square.hip (internal; the public surface is crcnn_hip.h)
 #pragma once
 #include "ctx.h"
+#include "window.h"
 
 // grid of a launch whose workgroups are mapped by xcd_group (ntt_device.h): `groups` groups of G workgroups, each group on one XCD
 static inline unsigned xcd_grid(size_t groups, unsigned G) { return (unsigned)((groups + 7) / 8 * 8 * G); }
@@ -22,13 +23,13 @@ int k_ntt_ct_inv_scaled(crc_ctx *c, const u64 *src, u64 *dst, size_t count, int 
 int k_plain_ntt(crc_ctx *c, const u64 *d_plain, size_t count, int mode, bool do_ntt, u64 *d_out, hipStream_t st);
 int k_plain_expand(crc_ctx *c, const u64 *d_compact, size_t count, u64 *d_plain, hipStream_t st);
 int k_rowwise(crc_ctx *c, u64 *acc, const u64 *b, size_t count, int size, int op, int sign, size_t group, size_t gmod, hipStream_t st);
-int k_pool(crc_ctx *c, const u64 *x, u64 *y, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf, const u64 *mul, hipStream_t st, int pack_out = 0);
+int k_pool(crc_ctx *c, const u64 *x, u64 *y, int B, int zd, const Window &w, const u64 *mul, hipStream_t st, int pack_out = 0);
 int k_pad(crc_ctx *c, const u64 *x, u64 *y, int B, int zd, int xd, int yd, int px0, int px1, int py0, int py1, hipStream_t st);
 int k_bn_ntt(crc_ctx *c, u64 *x, int B, int zd, int hw, const u64 *mean, const u64 *invstd, hipStream_t st);
 int k_mac(crc_ctx *c, const u64 *x, const u64 *w, u64 *y, const int *d_xoff, const int *d_toff, int B, int P, int F, int T, int in_cts,
           const u64 *bias_ntt, hipStream_t st, int xp = 0, int wp = 0, int yp = 0);
 int k_pack28(crc_ctx *c, u64 *rows, size_t nrows, bool unpack, hipStream_t st);
-int k_conv_offsets(crc_ctx *c, int *xoff, int *toff, unsigned *toffw, int P, int T, int in_cts, int xd, int yd, int xs, int ys, int xf, int yf, int yo, hipStream_t st);
+int k_conv_offsets(crc_ctx *c, int *xoff, int *toff, unsigned *toffw, const LayerShape &s, hipStream_t st);
 size_t k_square_work_words(const crc_ctx *c, size_t cnt);
 size_t k_multiply_work_words(const crc_ctx *c, size_t cnt);          // the product of two ciphertexts: four input polynomials per pair
 size_t k_relin_work_words(const crc_ctx *c, size_t cnt, int dbc);
@@ -39,8 +40,7 @@ size_t k_relin64_keys_words(const crc_ctx *c, int dbc);
 size_t k_relin64_work_words(const crc_ctx *c, size_t cnt, int dbc);
 int k_relin64_prepare_keys(crc_ctx *c, const u64 *evk, int dbc, u64 *kp, u64 *scratch, hipStream_t st);
 // a window of the sum pooling that follows a Square layer: the key switch is linear in the digit polynomials, so the digits of a window's c2's are summed before
-// they are transformed and ONE key switch serves the pooled ciphertext (kernels_relin64.hip)
-struct PoolGeom { int xd, yd, xs, ys, xf, yf, xo, yo; };
+// they are transformed and ONE key switch serves the pooled ciphertext (kernels_relin64.hip; PoolGeom: window.h)
 bool k_relin64_pool_supported(const crc_ctx *c, int dbc, int window);
 // the ring-linear terms of a degree-2 polynomial activation, joined to an NTT-form result while it leaves the key switch's last kernel:
 // y = mul (*) y + p1 (*) Sum_w xh_w (+ p0 on poly 0); xh: the activation's NTT-form input (size-2 ciphertexts where x3 holds the size-3 squares)
@@ -49,8 +49,7 @@ bool k_relin64_poly_fused(const crc_ctx *c);           // tune.poly_tail = 0 and
 int k_relinearize64(crc_ctx *c, const u64 *src, int src_size, int src_poly, const u64 *x3, int add_size, size_t cnt, int dbc, u64 *y, u64 *work, const u64 *kp,
                     hipStream_t st, bool out_ntt, const PoolGeom *pool = nullptr, const u64 *mul = nullptr, const PolyTail *poly = nullptr);
 // the same terms in a kernel of their own (kernels.hip: poly2_tail_kernel), in place on y [planes][xo][yo]
-int k_poly2_tail(crc_ctx *c, u64 *y, const u64 *xh, size_t planes, int xd, int yd, int xs, int ys, int xf, int yf, const u64 *p2, const u64 *p1, const u64 *p0,
-                 hipStream_t st);
+int k_poly2_tail(crc_ctx *c, u64 *y, const u64 *xh, size_t planes, const Window &w, const u64 *p2, const u64 *p1, const u64 *p0, hipStream_t st);
 int k_square(crc_ctx *c, const u64 *x, size_t cnt, u64 *y3, u64 *work, hipStream_t st, bool in_ntt = false, bool premul_c2 = false);
 // kernels_square64.hip: the square's auxiliary base over the engine's fp64 primes
 bool k_square64_supported(const crc_ctx *c);
@@ -63,8 +62,8 @@ int k_relinearize(crc_ctx *c, const u64 *x3, size_t cnt, const u64 *evk, int dbc
 // kernels_galois.hip: sigma_g of size-2 coefficient-form ciphertexts as the size-3 rows k_relinearize(..., c2_premul = true) takes: (sigma(c0) [+ c0], 0 [c1],
 // sigma(c1) (q/q_i)^-1); g a valid Galois element, x and x3 disjoint and 16-byte aligned
 int k_galois_permute(crc_ctx *c, const u64 *x, size_t cnt, u64 g, bool accumulate, u64 *x3, hipStream_t st);
-int k_mac2(crc_ctx *c, const u64 *x, const u64 *w, u64 *y, const int *d_xoff, const int *d_toff, int B, int P, int F, int T, int in_cts,
-           const u64 *bias_ntt, int gxd, int gyd, int gxf, int gyf, const unsigned *d_toffw, hipStream_t st, int xp = 0, int wp = 0, int yp = 0);
+int k_mac2(crc_ctx *c, const u64 *x, const u64 *w, u64 *y, const int *d_xoff, const int *d_toff, int B, const LayerShape &s, const u64 *bias_ntt,
+           const unsigned *d_toffw, hipStream_t st, int xp = 0, int wp = 0, int yp = 0);
 int k_fold_pool(crc_ctx *c, const u64 *w, const u64 *bias, const u64 *div, u64 *wout, u64 *bout, int nf, int zd, int xf, int yf, int cxs, int cys,
                 int pxf, int pyf, hipStream_t st, bool hoisted = false);
 size_t k_encrypt_work_words(const crc_ctx *c, size_t cnt);
@@ -116,20 +115,21 @@ int k_limb_pack_weights(crc_ctx *c, const u64 *w, signed char *wl, int nf, int z
 int k_limb_result_to_rows(crc_ctx *c, const u64 *ys, u64 *y, size_t rows, bool pack_out, hipStream_t st);
 int k_limb_result_to_limb(crc_ctx *c, const u64 *ys, signed char *xl, int B, int zd, hipStream_t st, bool scalar = false);
 bool k_limb_direct_dense(int P);
-int k_limb_mac(crc_ctx *c, const signed char *xl, const signed char *wl, u64 *ys, signed char *xl_out, const u64 *bias_ntt, int B, int zd, int xd, int yd, int xs, int ys_, int xf, int yf, int nf,
-               hipStream_t st, bool scalar = false);
+int k_limb_mac(crc_ctx *c, const signed char *xl, const signed char *wl, u64 *ys, signed char *xl_out, const u64 *bias_ntt, int B, const LayerShape &s, hipStream_t st,
+               bool scalar = false);
 // scalar form (CRC_NTTLS): the weights of a slot-batched network are constant polynomials, one residue per modulus; the n GEMMs of a modulus run as one
 size_t k_scalar_weights_bytes(const crc_ctx *c, int nf, int zd, int xf, int yf);
-bool   k_scalar_supported(const crc_ctx *c, int B, int zd, int xd, int yd, int xs, int ys_, int xf, int yf, int nf);
+bool   k_scalar_supported(const crc_ctx *c, int B, const LayerShape &s);
 int k_scalar_pack_weights(crc_ctx *c, const u64 *w, size_t wstride, signed char *wl, int nf, int zd, int xf, int yf, int *constant, hipStream_t st);
 // kernels_mfma1.hip: one-channel convolutions (conv1 [+ pool1]) on the matrix cores (weight form CRC_NTTL1)
-bool   k_limb_conv1_shape(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys_, int xf, int yf, int nf);
+bool   k_limb_conv1_shape(const crc_ctx *c, const LayerShape &s);
 int    k_limb_conv1_form(const crc_ctx *c, int xf, int yf, int nf);          // 1 plane-major, 2 pixel-major image and limb-folded weights
 size_t k_limb_conv1_weights_bytes(const crc_ctx *c);                         // enough for either form
 size_t k_limb_conv1_weights_bytes_for(const crc_ctx *c, int nf, int xf, int yf);
-size_t k_limb_conv1_image_bytes(const crc_ctx *c, int B, int xd, int yd, int xf, int yf, int nf);
+size_t k_limb_conv1_image_bytes(const crc_ctx *c, int B, const Window &w, int nf);
 int k_limb_conv1_pack_weights(crc_ctx *c, const u64 *w, signed char *wl, int nf, int xf, int yf, hipStream_t st);
-int k_limb_conv1(crc_ctx *c, const u64 *x, bool packed, signed char *xr, const signed char *wl, u64 *ys, signed char *xl_out, int Bout, int b0, const u64 *bias_ntt, int B, int xd, int yd,
-                 int xs, int ys_, int xf, int yf, int nf, hipStream_t st, int bxf = 1, int byf = 1);
-// a bxf x byf box (window sum of the xd x yd input at the layer's stride, made by the image pack) in front of the layer with base window xf x yf
-bool   k_limb_conv1_box_shape(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys_, int xf, int yf, int nf, int bxf, int byf);
+// a bxf x byf box (window sum of the input at the layer's stride, made by the image pack) in front of the layer with base window xf x yf; in: the window on the
+// INPUT image -- the kernel reads in.boxed(bxf, byf)
+int k_limb_conv1(crc_ctx *c, const u64 *x, bool packed, signed char *xr, const signed char *wl, u64 *ys, signed char *xl_out, int Bout, int b0, const u64 *bias_ntt, int B,
+                 const Window &in, int nf, hipStream_t st, int bxf = 1, int byf = 1);
+bool   k_limb_conv1_box_shape(const crc_ctx *c, const LayerShape &s, int bxf, int byf);

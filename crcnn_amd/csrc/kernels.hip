@@ -969,12 +969,12 @@ __global__ void __launch_bounds__(256) pool_kernel(const u64 *x, u64 *y, const M
     }
 }
 
-int k_pool(crc_ctx *c, const u64 *x, u64 *y, int B, int zd, int xd, int yd, int xs, int ys, int xf, int yf, const u64 *mul, hipStream_t st, int pack_out)
+int k_pool(crc_ctx *c, const u64 *x, u64 *y, int B, int zd, const Window &w, const u64 *mul, hipStream_t st, int pack_out)
 {
-    int xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys + 1;
+    int xo = w.xo(), yo = w.yo();
     size_t rows = (size_t)B * zd * xo * yo * 2 * c->k;
     if (rows == 0) return CRC_OK;
-    hipLaunchKernelGGL(pool_kernel, dim3((unsigned)rows), dim3(256), 0, st, x, y, c->d_mods, c->n, c->k, zd, xd, yd, xs, ys, xf, yf, xo, yo, mul, pack_out);
+    hipLaunchKernelGGL(pool_kernel, dim3((unsigned)rows), dim3(256), 0, st, x, y, c->d_mods, c->n, c->k, zd, w.xd, w.yd, w.xs, w.ys, w.xf, w.yf, xo, yo, mul, pack_out);
     HIPCHK(hipGetLastError());
     return CRC_OK;
 }
@@ -1082,14 +1082,13 @@ __global__ void __launch_bounds__(256) poly2_tail_kernel(u64 *y, const u64 *xh, 
     }
 }
 
-int k_poly2_tail(crc_ctx *c, u64 *y, const u64 *xh, size_t planes, int xd, int yd, int xs, int ys, int xf, int yf, const u64 *p2, const u64 *p1, const u64 *p0,
-                 hipStream_t st)
+int k_poly2_tail(crc_ctx *c, u64 *y, const u64 *xh, size_t planes, const Window &w, const u64 *p2, const u64 *p1, const u64 *p0, hipStream_t st)
 {
-    const int xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys + 1;
+    const int xo = w.xo(), yo = w.yo();
     const size_t rows = planes * xo * yo * 2 * c->k;
     if (rows == 0 || (!p2 && !p1 && !p0)) return CRC_OK;
     if (rows > 0x7fffffffULL) return CRC_ERR_UNSUPPORTED;                 // one block per row: the grid's x dimension
-    hipLaunchKernelGGL(poly2_tail_kernel, dim3((unsigned)rows), dim3(256), 0, st, y, xh, p2, p1, p0, c->d_mods, c->n, c->k, xd, yd, xs, ys, xf, yf, xo, yo);
+    hipLaunchKernelGGL(poly2_tail_kernel, dim3((unsigned)rows), dim3(256), 0, st, y, xh, p2, p1, p0, c->d_mods, c->n, c->k, w.xd, w.yd, w.xs, w.ys, w.xf, w.yf, xo, yo);
     HIPCHK(hipGetLastError());
     return CRC_OK;
 }
@@ -1113,13 +1112,13 @@ __global__ void conv_offsets_kernel(int *xoff, int *toff, unsigned *toffw, unsig
         toff[idx] = o; toffw[idx] = (unsigned)o * ctw;
     }
 }
-int k_conv_offsets(crc_ctx *c, int *xoff, int *toff, unsigned *toffw, int P, int T, int in_cts, int xd, int yd, int xs, int ys, int xf, int yf, int yo,
-    hipStream_t st)
+int k_conv_offsets(crc_ctx *c, int *xoff, int *toff, unsigned *toffw, const LayerShape &s, hipStream_t st)
 {
-    const int m = P > T + 8 ? P : T + 8;
+    const Window &w = s.w;
+    const int P = w.P(), T = s.T(), m = P > T + 8 ? P : T + 8;
     const size_t ctw = 2 * (size_t)c->k * c->n;
-    if ((size_t)in_cts * ctw > 0xffffffffULL) return CRC_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(conv_offsets_kernel, dim3((m + 255) / 256), dim3(256), 0, st, xoff, toff, toffw, (unsigned)ctw, P, T, xd, yd, xs, ys, xf, yf, yo);
+    if ((size_t)s.in_cts() * ctw > 0xffffffffULL) return CRC_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(conv_offsets_kernel, dim3((m + 255) / 256), dim3(256), 0, st, xoff, toff, toffw, (unsigned)ctw, P, T, w.xd, w.yd, w.xs, w.ys, w.xf, w.yf, w.yo());
     HIPCHK(hipGetLastError());
     return CRC_OK;
 }
@@ -1740,9 +1739,10 @@ static int mac2_launch(crc_ctx *c, MacArgs &a, hipStream_t st)
     return CRC_OK;
 }
 
-int k_mac2(crc_ctx *c, const u64 *x, const u64 *w, u64 *y, const int *d_xoff, const int *d_toff, int B, int P, int F, int T, int in_cts,
-           const u64 *bias_ntt, int gxd, int gyd, int gxf, int gyf, const unsigned *d_toffw, hipStream_t st, int xp, int wp, int yp)
+int k_mac2(crc_ctx *c, const u64 *x, const u64 *w, u64 *y, const int *d_xoff, const int *d_toff, int B, const LayerShape &s, const u64 *bias_ntt,
+           const unsigned *d_toffw, hipStream_t st, int xp, int wp, int yp)
 {
+    const int P = s.w.P(), F = s.nf, T = s.T(), in_cts = s.in_cts();
     if (B == 0 || P == 0 || F == 0) return CRC_OK;
     int maxbits = 0; for (int i = 0; i < c->k; i++) if ((int)c->tabs[i].m.bits > maxbits) maxbits = c->tabs[i].m.bits;
     // operands are addressed as wave-uniform base + 32-bit ELEMENT offset (term offset + half-wave pair offset + slot), widened to bytes per lane
@@ -1752,7 +1752,7 @@ int k_mac2(crc_ctx *c, const u64 *x, const u64 *w, u64 *y, const int *d_xoff, co
     MacArgs a{};
     a.x = x; a.w = w; a.y = y; a.mods = c->d_mods; a.xoff = d_xoff; a.toff = d_toff; a.toffw = d_toffw;
     a.n = c->n; a.k = c->k; a.B = B; a.P = P; a.F = F; a.T = T; a.in_cts = in_cts; a.bias = bias_ntt; a.bias_sign = 1;
-    a.gxd = gxd; a.gyd = gyd; a.gxf = gxf; a.gyf = gyf; a.xp = xp; a.wp = wp; a.yp = yp;
+    a.gxd = s.w.xd; a.gyd = s.w.yd; a.gxf = s.w.xf; a.gyf = s.w.yf; a.xp = xp; a.wp = wp; a.yp = yp;
 #ifdef CRC_TUNING
     a.dbg = c->tune.mac2_dbg;
 #endif

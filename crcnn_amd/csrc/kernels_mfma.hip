@@ -46,7 +46,7 @@ struct MfmaArgs {
     int xcdmap;                                        // grid x carries the XCD in its low three bits (the slot count is a multiple of 8)
     int mfast;                                         // tile order inside a slot: row tiles fastest (neighbouring workgroups share the weight tile) instead of filter tiles fastest
     i8 *xl_out; int lp2; unsigned zdp_out;             // direct limb result for a dense consumer (2P = 2^lp2 divides 64): [slot][B][7][2][zdp_out], channel = f P + p
-    int n, k, B, zdp, npos, yd, xs, ys_, yf, yo, P, F, Fp, zblks, ksteps, M, mtiles, ntiles;      // ksteps: rounded up to even (the weights carry a zero step)
+    int n, k, B, zdp, npos, yd, xs, ystr, yf, yo, P, F, Fp, zblks, ksteps, M, mtiles, ntiles;      // ksteps: rounded up to even (the weights carry a zero step)
     unsigned img_bytes; unsigned long long wslot_bytes; int ksteps_real;
     int flat, S, zdc; unsigned fplane;                 // flat form: S steps per window row, zdc channel bytes per position, fplane = 2 npos zdc bytes per plane
     int sc_B;                                          // scalar form (mfma_mac2w_kernel<.., SC>): B is n * sc_B, image e = s * sc_B + b, the bias of a row is read at slot e / sc_B
@@ -93,8 +93,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
             const int b = mm / (2 * a.P), p = (mm >> 1) % a.P, c = mm & 1;
             const int ox = p / a.yo, oy = p % a.yo;
             src_off[j] = a.npos == 1 ? (u32)(plane * a.zblks * (2 * a.B) + mm) * 32 + half * 16        // dense input: K-blocked rows (mm = image * 2 + poly)
-                       : a.flat ? (u32)b * a.img_bytes + (u32)(plane * a.fplane + (c * a.npos + (ox * a.xs) * a.yd + oy * a.ys_) * a.zdc + half * 16)
-                                : (u32)b * a.img_bytes + (u32)(plane * (a.npos * 2 * a.zdp) + (((ox * a.xs) * a.yd + oy * a.ys_) * 2 + c) * a.zdp + half * 16);
+                       : a.flat ? (u32)b * a.img_bytes + (u32)(plane * a.fplane + (c * a.npos + (ox * a.xs) * a.yd + oy * a.ystr) * a.zdc + half * 16)
+                                : (u32)b * a.img_bytes + (u32)(plane * (a.npos * 2 * a.zdp) + (((ox * a.xs) * a.yd + oy * a.ystr) * 2 + c) * a.zdp + half * 16);
         } else src_off[j] = (u32)(((pc - 14) >> 1) * (a.Fp * 32) + ((pc - 14) & 1) * 1024 + lane * 16);
     }
     const int kreal = a.ksteps_real;
@@ -254,8 +254,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
         const int b = mm / (2 * a.P), rem = mm - b * (2 * a.P), p = rem >> 1, c = rem & 1;
         const int ox = p / a.yo, oy = p - ox * a.yo;
         const u32 rowpart = MODE == 0 ? (u32)mm * 32 + half * 16
-                          : MODE == 1 ? (u32)b * a.img_bytes + (u32)((c * a.npos + (ox * a.xs) * a.yd + oy * a.ys_) * a.zdc + half * 16)
-                                   : (u32)b * a.img_bytes + (u32)((((ox * a.xs) * a.yd + oy * a.ys_) * 2 + c) * a.zdp + half * 16);
+                          : MODE == 1 ? (u32)b * a.img_bytes + (u32)((c * a.npos + (ox * a.xs) * a.yd + oy * a.ystr) * a.zdc + half * 16)
+                                   : (u32)b * a.img_bytes + (u32)((((ox * a.xs) * a.yd + oy * a.ystr) * 2 + c) * a.zdp + half * 16);
         const u32 pstride = MODE == 0 ? (u32)(a.zblks * (2 * a.B)) * 32 : MODE == 1 ? a.fplane : (u32)(a.npos * 2 * a.zdp);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
@@ -755,10 +755,11 @@ size_t k_scalar_weights_bytes(const crc_ctx *c, int nf, int zd, int xf, int yf) 
 // Can the layer run in scalar form on B images per slot?  The limb form's own limits (moduli of at most 55 bits, reductions of at most 18 000 terms, k <= 8) and the
 // 32-bit offsets of the tile engine: with n B images behind one base pointer a modulus' tensor and its slot-major result must each stay below 4 GiB.  (REFUSED here
 // rather than widened to a 64-bit tile base in the kernel: no model at the parameters of the records comes within two orders of magnitude of the limit.)
-bool k_scalar_supported(const crc_ctx *c, int B, int zd, int xd, int yd, int xs, int ys_, int xf, int yf, int nf)
+bool k_scalar_supported(const crc_ctx *c, int B, const LayerShape &s)
 {
-    if (B < 1 || c->k > 8 || !k_limb_supported(c, k_limb_steps(zd, xf, yf) * 32)) return false;
-    const unsigned long long Be = (unsigned long long)c->n * B, npos = (unsigned long long)xd * yd, P = (unsigned long long)((xd - xf) / xs + 1) * ((yd - yf) / ys_ + 1);
+    const int zd = s.zd, nf = s.nf;
+    if (B < 1 || c->k > 8 || !k_limb_supported(c, k_limb_steps(zd, s.w.xf, s.w.yf) * 32)) return false;
+    const unsigned long long Be = (unsigned long long)c->n * B, npos = (unsigned long long)s.w.xd * s.w.yd, P = (unsigned long long)s.w.P64();
     const unsigned long long img = npos == 1 ? (unsigned long long)NPL * 2 * round_up(zd, 32) : limb_img_bytes(zd, (int)npos);
     if (Be * img + 64 > 0xffffffffULL) return false;                                  // src_off, delta (+ 64: the flat form's last piece)
     if (Be * 2 * P * round_up(nf, 64) > 0xffffffffULL) return false;                  // idx0 + jump: words of the modulus' result, rows rounded up by the filter padding
@@ -790,17 +791,15 @@ int k_scalar_pack_weights(crc_ctx *c, const u64 *w, size_t wstride, i8 *wl, int 
     return CRC_OK;
 }
 // scalar: xl / ys / xl_out hold n B images per modulus (CRC_NTTLS), wl is k_scalar_pack_weights' result; always on mfma_mac2w_kernel
-int k_limb_mac(crc_ctx *c, const i8 *xl, const i8 *wl, u64 *ys, i8 *xl_out, const u64 *bias_ntt, int B, int zd, int xd, int yd, int xs, int ys_, int xf, int yf, int nf, hipStream_t st,
-               bool scalar)
+int k_limb_mac(crc_ctx *c, const i8 *xl, const i8 *wl, u64 *ys, i8 *xl_out, const u64 *bias_ntt, int B, const LayerShape &s, hipStream_t st, bool scalar)
 {
     if (B == 0) return CRC_OK;
-    const int Bslot = B;
-    if (scalar) { if (!k_scalar_supported(c, B, zd, xd, yd, xs, ys_, xf, yf, nf)) return CRC_ERR_UNSUPPORTED; B *= c->n; }
-    const int xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys_ + 1;
+    const int Bslot = B, zd = s.zd, nf = s.nf, xd = s.w.xd, yd = s.w.yd, xf = s.w.xf, yf = s.w.yf;
+    if (scalar) { if (!k_scalar_supported(c, B, s)) return CRC_ERR_UNSUPPORTED; B *= c->n; }
     MfmaArgs a{};
     a.xl = xl; a.wl = wl; a.ys = ys; a.mods = c->d_mods; a.bias = bias_ntt;
     a.xl_out = nullptr; a.lp2 = -1; a.zdp_out = 0; a.mfast = 0;
-    a.n = c->n; a.k = c->k; a.B = B; a.zdp = round_up(zd, 32); a.npos = xd * yd; a.yd = yd; a.xs = xs; a.ys_ = ys_; a.yf = yf; a.yo = yo; a.P = xo * yo;
+    a.n = c->n; a.k = c->k; a.B = B; a.zdp = round_up(zd, 32); a.npos = xd * yd; a.yd = yd; a.xs = s.w.xs; a.ystr = s.w.ys; a.yf = yf; a.yo = s.w.yo(); a.P = s.w.P();
     a.F = nf; a.Fp = round_up(nf, 64); a.zblks = a.zdp / 32; a.ksteps_real = k_limb_steps(zd, xf, yf); a.M = B * a.P * 2;
     a.mtiles = (a.M + 63) / 64; a.ntiles = a.Fp / 64;
     a.zdc = a.npos > 1 ? k_limb_flat_zdc(zd) : 0; a.flat = a.zdc ? 1 : 0; a.S = a.zdc ? (yf * a.zdc + 31) / 32 : 1; a.fplane = (unsigned)(2 * a.npos * a.zdc);

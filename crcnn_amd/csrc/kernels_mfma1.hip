@@ -647,11 +647,10 @@ static inline unsigned conv1_img_stride(int xd) { const unsigned b = NPL * 2 * c
 static inline unsigned conv1_px_rs(int yd) { return ((unsigned)yd * 8 + 15) / 16 * 16; }
 static inline unsigned conv1_px_poly_bytes(int xd, int yd) { const unsigned b = (unsigned)xd * conv1_px_rs(yd); return b + (128 + 256 - b % 256) % 256; }
 static inline unsigned conv1_px_img_stride(int xd, int yd) { return (2 * conv1_px_poly_bytes(xd, yd) + 1023) / 1024 * 1024; }
-static bool conv1_fits(unsigned img_stride, int xd, int yd, int xs, int ys_, int xf, int yf)
+static bool conv1_fits(unsigned img_stride, const Window &w)
 {
-    const int xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys_ + 1;
     // two image buffers + the staging area of a limb result (at most 32 channel bytes per position) must fit the 160 KiB of LDS
-    return 2 * (size_t)img_stride + (size_t)NPL * xo * yo * 2 * 32 <= 160 * 1024;
+    return 2 * (size_t)img_stride + (size_t)NPL * w.xo() * w.yo() * 2 * 32 <= 160 * 1024;
 }
 // Which form a layer runs: 1 plane-major (mfma_conv1_kernel), 2 pixel-major (mfma_conv1_kernel_px).  Decided by the tuning switch, the window and the filter
 // count ALONE, so that the weights (packed without knowing the image) and every later launch agree; conv1_narrow does not enter (the tests flip it between
@@ -667,32 +666,32 @@ int k_limb_conv1_form(const crc_ctx *c, int xf, int yf, int nf)
     if (forced == 2) return 2;
     return nf > 16 && nf <= 20 ? 1 : 2;
 }
-bool k_limb_conv1_shape(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys_, int xf, int yf, int nf)
+bool k_limb_conv1_shape(const crc_ctx *c, const LayerShape &s)
 {
-    if (zd != 1 || xf > 8 || yf > 8 || nf > 32 || yd > 32 || c->n < 64 || c->k > MAXK) return false;
+    const int xd = s.w.xd, yd = s.w.yd, xf = s.w.xf, yf = s.w.yf, nf = s.nf;
+    if (s.zd != 1 || xf > 8 || yf > 8 || nf > 32 || yd > 32 || c->n < 64 || c->k > MAXK) return false;
     // the epilogue's bounds: the folding reduction wants q = 2^b - f with 53 <= b <= 55 and a small f (limbred.h conv1_fold_ok); 7 balanced digits with |top
     // digit| <= 64 need q < 2^55
     for (int i = 0; i < c->k; i++) if (!conv1_fold_ok(c->tabs[i].m.q, c->tabs[i].m.bits, fold_constant(c->tabs[i].m.q, c->tabs[i].m.bits))) return false;
-    const int xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys_ + 1;
-    if (xo * yo > 1024) return false;                          // (the kernel's reciprocal division of a pixel index by yo <= 32 is exact below 2048)
+    if (s.w.P() > 1024) return false;                              // (the kernel's reciprocal division of a pixel index by yo <= 32 is exact below 2048)
     // (the pixel-major image is the smaller one up to 28 columns; wider than that it can be up to 14 % larger)
-    return conv1_fits(k_limb_conv1_form(c, xf, yf, nf) == 2 ? conv1_px_img_stride(xd, yd) : conv1_img_stride(xd), xd, yd, xs, ys_, xf, yf);
+    return conv1_fits(k_limb_conv1_form(c, xf, yf, nf) == 2 ? conv1_px_img_stride(xd, yd) : conv1_img_stride(xd), s.w);
 }
 // A box (input-side window sum, limb_pack_rows1_kernel_px) in front of a layer with base window xf x yf: the pixel-major form only, at most 9 terms (sum_reduce16's
 // bound with room to spare), and the SUMMED image must be a shape the kernel takes
-bool k_limb_conv1_box_shape(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys_, int xf, int yf, int nf, int bxf, int byf)
+bool k_limb_conv1_box_shape(const crc_ctx *c, const LayerShape &s, int bxf, int byf)
 {
     if (bxf < 1 || byf < 1 || bxf * byf > 9) return false;
-    const int xdo = xd - (bxf - 1) * xs, ydo = yd - (byf - 1) * ys_;
-    if (xdo < xf || ydo < yf || !k_limb_conv1_shape(c, zd, xdo, ydo, xs, ys_, xf, yf, nf)) return false;
-    return bxf * byf == 1 || k_limb_conv1_form(c, xf, yf, nf) == 2;
+    const LayerShape sum{s.w.boxed(bxf, byf), s.zd, s.nf};
+    if (sum.w.xd < sum.w.xf || sum.w.yd < sum.w.yf || !k_limb_conv1_shape(c, sum)) return false;
+    return bxf * byf == 1 || k_limb_conv1_form(c, s.w.xf, s.w.yf, s.nf) == 2;
 }
 static size_t conv1_form_weights_bytes(const crc_ctx *c, int form) { return (size_t)c->n * c->k * NPL * 32 * 64 * (form == 2 ? NJ : 1); }
 size_t k_limb_conv1_weights_bytes(const crc_ctx *c) { return conv1_form_weights_bytes(c, 2); }            // enough for either form
 size_t k_limb_conv1_weights_bytes_for(const crc_ctx *c, int nf, int xf, int yf) { return conv1_form_weights_bytes(c, k_limb_conv1_form(c, xf, yf, nf)); }
-size_t k_limb_conv1_image_bytes(const crc_ctx *c, int B, int xd, int yd, int xf, int yf, int nf)
+size_t k_limb_conv1_image_bytes(const crc_ctx *c, int B, const Window &w, int nf)
 {
-    return (size_t)c->n * c->k * B * (k_limb_conv1_form(c, xf, yf, nf) == 2 ? conv1_px_img_stride(xd, yd) : conv1_img_stride(xd));
+    return (size_t)c->n * c->k * B * (k_limb_conv1_form(c, w.xf, w.yf, nf) == 2 ? conv1_px_img_stride(w.xd, w.yd) : conv1_img_stride(w.xd));
 }
 
 static void conv1_tables(const crc_ctx *c, Conv1Args &a)      // limbred.h: accumulator biases and q^-1 mod 2^64 per modulus
@@ -711,21 +710,20 @@ int k_limb_conv1_pack_weights(crc_ctx *c, const u64 *w, i8 *wl, int nf, int xf, 
     HIPCHK(hipGetLastError());
     return CRC_OK;
 }
-// x: B NTT-form one-channel images of xd_in x yd_in pixels; the convolution reads their bxf x byf window sums at its own stride (xd x yd pixels below; no box: the
+// x: B NTT-form one-channel images of in.xd x in.yd pixels; the convolution reads their bxf x byf window sums at its own stride (xd x yd pixels below; no box: the
 // images themselves); xr: k_limb_conv1_image_bytes of scratch for that xd x yd image; result either images b0 .. b0 + B of a limb tensor of Bout images (xl_out,
 // [slot][Bout][7][P][2][32]) or slot-major u64 (ys, [slot][B][F][P][2])
-int k_limb_conv1(crc_ctx *c, const u64 *x, bool packed, i8 *xr, const i8 *wl, u64 *ys, i8 *xl_out, int Bout, int b0, const u64 *bias_ntt, int B, int xd_in,
-    int yd_in, int xs, int ys_,
-                 int xf, int yf, int nf, hipStream_t st, int bxf, int byf)
+int k_limb_conv1(crc_ctx *c, const u64 *x, bool packed, i8 *xr, const i8 *wl, u64 *ys, i8 *xl_out, int Bout, int b0, const u64 *bias_ntt, int B, const Window &in,
+                 int nf, hipStream_t st, int bxf, int byf)
 {
     if (B == 0) return CRC_OK;
-    if (!k_limb_conv1_box_shape(c, 1, xd_in, yd_in, xs, ys_, xf, yf, nf, bxf, byf)) return CRC_ERR_UNSUPPORTED;
-    const int xd = xd_in - (bxf - 1) * xs, yd = yd_in - (byf - 1) * ys_;
-    const int xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys_ + 1;
+    if (!k_limb_conv1_box_shape(c, {in, 1, nf}, bxf, byf)) return CRC_ERR_UNSUPPORTED;
+    const Window w = in.boxed(bxf, byf);
+    const int xd = w.xd, yd = w.yd, xs = w.xs, xf = w.xf, yf = w.yf, xd_in = in.xd, yd_in = in.yd;
     const int form = k_limb_conv1_form(c, xf, yf, nf);
     Conv1Args a{};
     a.xr = xr; a.wl = wl; a.ys = ys; a.xl_out = xl_out; a.mods = c->d_mods; a.bias = bias_ntt;
-    a.n = c->n; a.k = c->k; a.B = B; a.Bout = Bout; a.b0 = b0; a.xd = xd; a.yo = yo; a.xs = xs; a.ystr = ys_; a.P = xo * yo; a.F = nf;
+    a.n = c->n; a.k = c->k; a.B = B; a.Bout = Bout; a.b0 = b0; a.xd = xd; a.yo = w.yo(); a.xs = xs; a.ystr = w.ys; a.P = w.P(); a.F = nf;
         a.mtiles = (2 * a.P + 15) / 16;
     // (the limb tensor of the convolution behind: its layout follows ITS channel count = this layer's filters)
     a.out_zdc = a.P > 1 ? k_limb_flat_zdc(nf) : 0;
@@ -736,20 +734,20 @@ int k_limb_conv1(crc_ctx *c, const u64 *x, bool packed, i8 *xr, const i8 *wl, u6
     if (form == 2) {
         a.px_rs = conv1_px_rs(yd); a.poly_bytes = conv1_px_poly_bytes(xd, yd); a.img_stride = conv1_px_img_stride(xd, yd);
         a.px_taps = xf * yf; a.px_yf = yf;
-        a.px_pair = yf % 2 == 0 && ys_ % 2 == 0 ? 1 : 0;
+        a.px_pair = yf % 2 == 0 && w.ys % 2 == 0 ? 1 : 0;
         if (bxf * byf > 1 && box_staged(yd_in, bxf, xs, a.px_rs)) {
             // the staged box, one workgroup per (32 slots, modulus, image, poly) walking the whole image: every input residue is loaded once
             const size_t lds = box_lds_bytes(yd_in, bxf, xs, a.px_rs);
             const int wpi = 1;                                          // (box_row_groups(xd): one row group per workgroup, the halo read 1.5 x: 10.2 ms against 8.7)
             { const int rc = crc_ctx_ensure_lds(c, (const void *)limb_pack_box_kernel_px, lds); if (rc) return rc; }
             hipLaunchKernelGGL(limb_pack_box_kernel_px, dim3((unsigned)((size_t)(c->n / RSL) * c->k * B * 2 * wpi)), dim3(256), lds, st, x, xr, c->d_mods, c->n,
-                c->k, B, xd_in, yd_in, packed ? 1 : 0, a.img_stride, a.poly_bytes, a.px_rs, xd, yd, bxf, byf, xs, ys_);
+                c->k, B, xd_in, yd_in, packed ? 1 : 0, a.img_stride, a.poly_bytes, a.px_rs, xd, yd, bxf, byf, xs, w.ys);
         } else if (bxf * byf > 1)                                   // a ring past the LDS of a CU (a 9 x 1 box at stride 3 on a wide image): every term read directly
             hipLaunchKernelGGL(limb_pack_rows1_kernel_px<true>, dim3((unsigned)pack_blocks), dim3(256), RSL * (RG * a.px_rs + 16), st, x, xr, c->d_mods, c->n, c->k,
-                B, xd_in, yd_in, packed ? 1 : 0, a.img_stride, a.poly_bytes, a.px_rs, xd, yd, bxf, byf, xs, ys_);
+                B, xd_in, yd_in, packed ? 1 : 0, a.img_stride, a.poly_bytes, a.px_rs, xd, yd, bxf, byf, xs, w.ys);
         else
             hipLaunchKernelGGL(limb_pack_rows1_kernel_px<false>, dim3((unsigned)pack_blocks), dim3(256), RSL * (RG * a.px_rs + 16), st, x, xr, c->d_mods, c->n, c->k,
-                B, xd_in, yd_in, packed ? 1 : 0, a.img_stride, a.poly_bytes, a.px_rs, xd, yd, 1, 1, xs, ys_);
+                B, xd_in, yd_in, packed ? 1 : 0, a.img_stride, a.poly_bytes, a.px_rs, xd, yd, 1, 1, xs, w.ys);
         HIPCHK(hipGetLastError());
         // (140 registers of resident weights: two waves per SIMD, whatever conv1_waves asks for)
         const size_t lds = 2 * (size_t)a.img_stride + (xl_out ? a.out_img_bytes : 0);
@@ -762,8 +760,7 @@ int k_limb_conv1(crc_ctx *c, const u64 *x, bool packed, i8 *xr, const i8 *wl, u6
     a.narrow = c->tune.conv1_narrow != 0 && nf > 16 && nf <= 20 ? 1 : 0;
     {
         hipLaunchKernelGGL(limb_pack_rows1_kernel, dim3((unsigned)pack_blocks), dim3(256), 0, st, x, xr, c->d_mods, c->n, c->k, B, xd, yd, packed ? 1 : 0,
-            a.img_stride, a.plane_bytes,
-                           a.poly_bytes);
+            a.img_stride, a.plane_bytes, a.poly_bytes);
         HIPCHK(hipGetLastError());
     }
     // waves per workgroup (8 or 12; wave w runs on SIMD w % 4 and takes row tiles w/2, w/2 + waves/2, ...): the count that loads the busiest SIMD least, 12 on
