@@ -259,6 +259,14 @@ def load():
     L.crc_rotate_columns_forms.argtypes = [VP, VP, CI, SZ, VP, PU, CI, CI, VP, CI, VP, VP]
     L.crc_sum_slots_work_bytes.restype = SZ; L.crc_sum_slots_work_bytes.argtypes = [VP, SZ, CI]
     L.crc_sum_slots_forms.argtypes = [VP, VP, CI, SZ, VP, PU, CI, CI, VP, CI, VP, VP]
+    L.crc_galois_ntt_table.argtypes = [VP, u64, ctypes.POINTER(ctypes.c_uint32)]
+    L.crc_galois_conjugate_keys.argtypes = [VP, PU, CI, CI, PU, PU]
+    L.crc_galois_conjugate_keys_dev.argtypes = [VP, PU, CI, CI, VP, VP, VP]
+    L.crc_galois_permute_ntt_dev.argtypes = [VP, VP, SZ, u64, VP, VP]
+    L.crc_rotate_hoisted_work_bytes.restype = SZ; L.crc_rotate_hoisted_work_bytes.argtypes = [VP, SZ, CI, CI]
+    L.crc_rotate_hoisted_forms.argtypes = [VP, VP, CI, SZ, PU, CI, VP, PU, CI, CI, VP, CI, VP, VP]
+    L.crc_diag_mac_work_bytes.restype = SZ; L.crc_diag_mac_work_bytes.argtypes = [VP, SZ, CI, CI]
+    L.crc_diag_mac_forms.argtypes = [VP, VP, CI, SZ, PU, CI, VP, VP, PU, CI, CI, VP, CI, VP, VP]
     L.crc_noise_budget.argtypes = [VP, PU, PU, CI]
     _lib = L
     return L
@@ -280,6 +288,26 @@ def default_coeff_modulus_128(n):
     buf = (u64 * 16)()
     cnt = _chk(L.crc_default_coeff_modulus_128(n, buf, 16), "crc_default_coeff_modulus_128")
     return [int(buf[i]) for i in range(cnt)]
+
+
+def diag_matvec_plan(W, M, n):
+    """The diagonal method for y = W x mod t over the slots of one ciphertext.  W: integers (out x in, already reduced mod t, out and in <= M), zero-padded here to
+    M x M; M a power of two <= n/2.  Returns (steps, rows): the steps d of the non-zero diagonals and their slot rows [len(steps)][n] (int64),
+    rows[r][i] = W[i mod M][(i mod M + d) mod M] -- period M over both rows of n/2 slots.  With x tiled with period M as well, a row rotation by d is a rotation
+    mod M, and  y = Sum_r rows[r] (.) rotate_rows(x, steps[r])  holds W x in slots 0..out-1 of every period."""
+    W = np.asarray(W)
+    if W.ndim != 2 or M < 1 or M & (M - 1) or M > n // 2 or W.shape[0] > M or W.shape[1] > M:
+        raise ValueError("diag_matvec_plan: W must be out x in with out, in <= M, M a power of two <= n/2")
+    P = np.zeros((M, M), dtype=np.int64)
+    P[:W.shape[0], :W.shape[1]] = W
+    i = np.arange(M)
+    steps, rows = [], []
+    for d in range(M):
+        diag = P[i, (i + d) % M]
+        if diag.any():
+            steps.append(d)
+            rows.append(np.tile(diag, n // M))
+    return steps, np.array(rows, dtype=np.int64).reshape(len(steps), n)
 
 
 def h5_read(path, name):
@@ -953,6 +981,52 @@ class Engine:
         elts = self._elts(elts)
         _chk(self.L.crc_sum_slots_forms(self.c, self.p(d_x), in_form, count, self.p(d_gk), _pu(elts), elts.size, dbc, self.p(d_y), out_form, self.p(d_work),
                                         self.stream), "crc_sum_slots_forms")
+
+    # ---- hoisted rotations and the diagonal product over slots (crc_galois_conjugate_keys* / crc_rotate_hoisted_forms / crc_diag_mac_forms).  Their key set is
+    # (elts, CONJUGATED blobs): galois_conjugate_keys of an ordinary set.  An ordinary set passed by mistake cannot be detected and gives garbage
+    def galois_ntt_table(self, g):
+        """table with NTT(sigma_g(p))[i] = NTT(p)[table[i]] for every modulus"""
+        out = np.zeros(self.n, dtype=np.uint32)
+        _chk(self.L.crc_galois_ntt_table(self.c, int(g), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))), "crc_galois_ntt_table")
+        return out
+
+    def galois_conjugate_keys(self, elts, gk, dbc=16):
+        """host blobs [n_elts][crc_evk_words] -> the conjugated blobs K'_g = sigma_g^-1(K_g), same shape"""
+        elts = self._elts(elts)
+        gk = np.ascontiguousarray(gk, dtype=np.uint64).reshape(elts.size, self.L.crc_evk_words(self.c, dbc))
+        out = np.zeros_like(gk)
+        _chk(self.L.crc_galois_conjugate_keys(self.c, _pu(elts), elts.size, dbc, _pu(gk), _pu(out)), "crc_galois_conjugate_keys")
+        return out
+
+    def galois_conjugate_keys_dev(self, elts, d_gk, d_out, dbc=16):
+        elts = self._elts(elts)
+        _chk(self.L.crc_galois_conjugate_keys_dev(self.c, _pu(elts), elts.size, dbc, self.p(d_gk), self.p(d_out), self.stream), "crc_galois_conjugate_keys_dev")
+
+    def galois_permute_ntt_dev(self, d_in, rows, g, d_out):
+        """NTT-form rows [rows][k][n] -> NTT(sigma_g(INTT(rows)))"""
+        _chk(self.L.crc_galois_permute_ntt_dev(self.c, self.p(d_in), rows, int(g), self.p(d_out), self.stream), "crc_galois_permute_ntt_dev")
+
+    def rotate_hoisted_work_bytes(self, count, R, dbc=16):
+        return self.L.crc_rotate_hoisted_work_bytes(self.c, count, R, dbc)
+
+    def rotate_hoisted(self, d_x, count, gs, d_cgk, elts, d_y, d_work, dbc=16, in_form=COEFF, out_form=COEFF):
+        """d_y [R][count] = H_g(d_x) for every g of gs (g = 1: a copy), all from one digit decomposition; d_cgk: the CONJUGATED keys of elts"""
+        elts = self._elts(elts); gs = self._elts(gs)
+        _chk(self.L.crc_rotate_hoisted_forms(self.c, self.p(d_x), in_form, count, _pu(gs), gs.size, self.p(d_cgk), _pu(elts), elts.size, dbc, self.p(d_y), out_form,
+                                             self.p(d_work), self.stream), "crc_rotate_hoisted_forms")
+
+    def diag_mac_work_bytes(self, count, R, dbc=16):
+        return self.L.crc_diag_mac_work_bytes(self.c, count, R, dbc)
+
+    def diag_mac(self, d_x, count, gs, d_p_ntt, d_cgk, elts, d_y, d_work, dbc=16, in_form=COEFF, out_form=COEFF):
+        """d_y [count] = Sum_r P_r (*) H_{gs[r]}(d_x); d_p_ntt [R][k][n]: NTT-form plaintext rows (plain_to_ntt)"""
+        elts = self._elts(elts); gs = self._elts(gs)
+        _chk(self.L.crc_diag_mac_forms(self.c, self.p(d_x), in_form, count, _pu(gs), gs.size, self.p(d_p_ntt), self.p(d_cgk), _pu(elts), elts.size, dbc, self.p(d_y),
+                                       out_form, self.p(d_work), self.stream), "crc_diag_mac_forms")
+
+    def diag_matvec_plan(self, W, M):
+        """binding.diag_matvec_plan at this ring: (steps, slot rows [len(steps)][n]) of the non-zero diagonals of W padded to M x M"""
+        return diag_matvec_plan(W, M, self.n)
 
     # ---- ciphertext x ciphertext multiply and the degree-3 activation c3 x^3 + c2 x^2 + c1 x + c0 (crc_multiply* / crc_poly3_relin_forms)
     def multiply_relin_work_bytes(self, count, dbc=16):

@@ -1,6 +1,7 @@
 // abi.hip -- extern "C" entry points of include/crcnn_hip.h that drive the kernels (layers and Evaluator ops).
 #include <cstdlib>
 #include <cstring>
+#include <vector>
 #include "kernels.h"
 #include "chacha.h"
 #include "work_arena.h"
@@ -1290,6 +1291,195 @@ extern "C" int crc_sum_slots_forms(crc_ctx *c, const uint64_t *d_x, int in_form,
     for (int s = 0; s < ns; s++)
         RUN(gal_step(c, L, s ? d_y : d_x, s ? CRC_COEFF : in_form, count, elts[idx[s]], true, d_gk + (size_t)idx[s] * kw, dbc, d_y,
                      s == ns - 1 && out_form == CRC_NTT, stream));
+    return CRC_OK;
+}
+// ---- hoisted rotations: many automorphisms of one ciphertext from one digit decomposition, and the diagonal product that consumes them ----
+// With the conjugated key K'_g = sigma_g^-1(K_g) (crc_galois_conjugate_keys),  H_g(ct) := sigma_g((c0, 0) + KeySwitch(c1; K'_g))  decrypts to sigma_g(m).  The key
+// switch reads c1 itself, so the digits and their transforms (K1) are made once per pass and serve every element; per element run K2 + K3 into NTT form and the
+// NTT-domain gather.  Where the fp64 key switch does not apply, k_relinearize runs per element with the conjugated key: the same exact function on Z_q.
+// Work: [coefficient copy of an NTT-form pass][size-3 rows (c0, 0, c1 (q/q_i)^-1)][zc key-switch results of a pass][nk prepared keys, made by pass 0][scratch of
+// the key switch].  A pass is square_chunk ciphertexts, fewer once more than 8 results are kept at once: it shrinks with R.
+struct HoistWork { u64 *xc, *x3, *z, *kp, *rest; size_t step, kpw; };
+enum { HOIST_Z_PASSES = 8 };
+static HoistWork hoist_layout(const crc_ctx *c, size_t count, int nk, int zc, int dbc, WorkArena &a)
+{
+    HoistWork L{};
+    // (the zc results kept at once may take the room of HOIST_Z_PASSES passes' ciphertexts: up to 8 of them leave the pass whole, 32 make it a quarter)
+    L.step = square_chunk(c) * HOIST_Z_PASSES / (size_t)zc;
+    if (L.step > square_chunk(c)) L.step = square_chunk(c);
+    if (L.step < 1) L.step = 1;
+    const size_t ch = count < L.step ? count : L.step;
+    L.kpw = (k_relin_keys_words(c, dbc) + 31) & ~(size_t)31;
+    L.xc = a.take<u64>(ch * crc_ct_words(c, 2));
+    L.x3 = a.take<u64>(ch * crc_ct_words(c, 3));
+    L.z = a.take<u64>((size_t)zc * ch * crc_ct_words(c, 2));
+    L.kp = a.take<u64>((size_t)nk * L.kpw);
+    const size_t one = k_relin_work_words(c, ch, dbc), two = k_relin64_supported(c, dbc) ? k_relin64_work_words_multi(c, ch, dbc, 2) : 0;
+    L.rest = a.take<u64>(one > two ? one : two);                        // (either setting of hoist_rt: a tuning switch does not change the size)
+    return L;
+}
+// keys per digit load in K2: HOIST_RT_DEFAULT unless the tuning key "hoist_rt" says otherwise (profiles/galois_hoisted.md has both measured)
+enum { HOIST_RT_DEFAULT = 2 };
+static int hoist_rt(const crc_ctx *c) { return c->tune.hoist_rt ? c->tune.hoist_rt : (int)HOIST_RT_DEFAULT; }
+static int diag_zc(int R) { return R < GALOIS_DIAG_MAX ? R : (int)GALOIS_DIAG_MAX; }
+static size_t hoist_bytes(const crc_ctx *c, size_t count, int R, int zc, int dbc)
+{
+    if (!c || !dbc_ok(dbc) || R < 1) return 0;
+    WorkArena a;
+    hoist_layout(c, count, R, zc, dbc, a);
+    return a.bytes();
+}
+// the key of every element of gs in the set (-1 for g = 1); false where one is invalid or missing
+static bool hoist_keys(const crc_ctx *c, const uint64_t *gs, int R, const uint64_t *elts, int n_elts, int *at)
+{
+    for (int r = 0; r < R; r++) {
+        if (!crc_galois_elt_valid(c, gs[r])) return false;
+        at[r] = -1;
+        if (gs[r] == 1) continue;
+        for (int i = 0; i < n_elts; i++) if (elts[i] == gs[r]) { at[r] = i; break; }
+        if (at[r] < 0) return false;
+    }
+    return true;
+}
+static int hoist_args_ok(const crc_ctx *c, const uint64_t *d_x, int in_form, size_t count, const uint64_t *gs, int R, const uint64_t *d_cgk, const uint64_t *elts,
+                         int n_elts, int dbc, const uint64_t *d_y, size_t y_cts, int out_form, const void *d_work, size_t wb)
+{
+    if (!d_x || !d_y || !d_work || !gs || R < 1 || !form_ok(in_form) || !form_ok(out_form) || !dbc_ok(dbc) || n_elts < 0 || (n_elts && (!elts || !d_cgk))) return 0;
+    if (!aligned16(d_x) || !aligned16(d_y) || !aligned16(d_cgk)) return 0;
+    const size_t ctw = crc_ct_words(c, 2);
+    if (ranges_overlap(d_work, wb, d_x, 8 * count * ctw) || ranges_overlap(d_work, wb, d_y, 8 * y_cts * ctw)) return 0;
+    return ranges_overlap(d_x, 8 * count * ctw, d_y, 8 * y_cts * ctw) ? 0 : 1;
+}
+// one pass' operand and digits: xin (in_form) -> L.x3 = (c0, 0, c1 (q/q_i)^-1) and, on the fp64 path, E in L.rest.  first: the pass that prepares the keys
+static int hoist_pass_head(crc_ctx *c, const HoistWork &L, const u64 *xin, int in_form, size_t ch, const int *at, int R, const u64 *d_cgk, int dbc, bool f64, bool first,
+                           void *stream)
+{
+    const size_t kw = crc_evk_words(c, dbc);
+    if (in_form == CRC_NTT) { RUN(k_ntt_ct(c, true, xin, L.xc, ch, 2, false, S(stream), nullptr, 0, 0, 0)); xin = L.xc; }
+    RUN(k_galois_permute(c, xin, ch, 1, false, L.x3, S(stream)));
+    if (!f64) return CRC_OK;
+    if (first)                                                          // (the preparation borrows the scratch: before E is put there)
+        for (int r = 0; r < R; r++) if (at[r] >= 0) RUN(k_relin64_prepare_keys(c, d_cgk + (size_t)at[r] * kw, dbc, L.kp + (size_t)r * L.kpw, L.rest, S(stream)));
+    return k_relin64_digits(c, L.x3, 3, 2, ch, dbc, L.rest, S(stream));
+}
+// (c0, 0) + KeySwitch(c1; K'_g) of the pass in NTT form -> z
+static int hoist_switch(crc_ctx *c, const HoistWork &L, size_t ch, int r, int key_at, const u64 *d_cgk, int dbc, bool f64, bool first, u64 *z, void *stream)
+{
+    if (f64) return k_relin64_from_digits(c, L.x3, 3, ch, dbc, z, L.rest, L.kp + (size_t)r * L.kpw, S(stream), true);
+    return k_relinearize(c, L.x3, ch, d_cgk + (size_t)key_at * crc_evk_words(c, dbc), dbc, z, L.rest, L.kp + (size_t)r * L.kpw, S(stream), true, true, !first);
+}
+// the same for the two elements ra, rb with one read of the digit values (fp64 path only)
+static int hoist_switch2(crc_ctx *c, const HoistWork &L, size_t ch, int ra, int rb, int dbc, u64 *za, u64 *zb, void *stream)
+{
+    return k_relin64_from_digits2(c, L.x3, 3, ch, dbc, za, zb, L.rest, L.kp + (size_t)ra * L.kpw, L.kp + (size_t)rb * L.kpw, S(stream), true);
+}
+extern "C" int crc_galois_permute_ntt_dev(crc_ctx *c, const uint64_t *d_in, size_t rows, uint64_t g, uint64_t *d_out, void *stream)
+{
+    CHECK_CTX(c);
+    if (!d_in || !d_out || !aligned16(d_in) || !aligned16(d_out) || !crc_galois_elt_valid(c, g)) return CRC_ERR_INVALID_ARGUMENT;
+    const size_t bytes = 8 * rows * (size_t)c->k * c->n;
+    if (ranges_overlap(d_in, bytes, d_out, bytes)) return CRC_ERR_INVALID_ARGUMENT;
+    return k_galois_permute_ntt(c, d_in, rows * (size_t)c->k, g, d_out, S(stream));
+}
+extern "C" int crc_galois_conjugate_keys_dev(crc_ctx *c, const uint64_t *elts, int n_elts, int dbc, const uint64_t *d_gk, uint64_t *d_out, void *stream)
+{
+    CHECK_CTX(c);
+    if (!dbc_ok(dbc) || n_elts < 0 || (n_elts && (!elts || !d_gk || !d_out)) || !aligned16(d_gk) || !aligned16(d_out)) return CRC_ERR_INVALID_ARGUMENT;
+    for (int e = 0; e < n_elts; e++) if (!crc_galois_elt_valid(c, elts[e]) || elts[e] == 1) return CRC_ERR_INVALID_ARGUMENT;
+    const size_t kw = crc_evk_words(c, dbc);
+    if (ranges_overlap(d_gk, 8 * kw * n_elts, d_out, 8 * kw * n_elts)) return CRC_ERR_INVALID_ARGUMENT;
+    const u64 mask = 2 * (u64)c->n - 1;
+    for (int e = 0; e < n_elts; e++) {
+        u64 h = 1;                                                      // g^-1 = g^(n - 1) mod 2n
+        for (u64 x = elts[e] & mask, p = (u64)c->n - 1; p; p >>= 1, x = x * x & mask) if (p & 1) h = h * x & mask;
+        RUN(k_galois_permute_ntt(c, d_gk + (size_t)e * kw, kw / c->n, h, d_out + (size_t)e * kw, S(stream)));
+    }
+    return CRC_OK;
+}
+extern "C" size_t crc_rotate_hoisted_work_bytes(const crc_ctx *c, size_t count, int R, int dbc) { return hoist_bytes(c, count, R, 2, dbc); }
+extern "C" int crc_rotate_hoisted_forms(crc_ctx *c, const uint64_t *d_x, int in_form, size_t count, const uint64_t *gs, int R, const uint64_t *d_cgk,
+                                        const uint64_t *elts, int n_elts, int dbc, uint64_t *d_y, int out_form, void *d_work, void *stream)
+{
+    CHECK_CTX(c);
+    if (R < 1 || R > (1 << 20)) return CRC_ERR_INVALID_ARGUMENT;
+    if (!hoist_args_ok(c, d_x, in_form, count, gs, R, d_cgk, elts, n_elts, dbc, d_y, (size_t)R * count, out_form, d_work, hoist_bytes(c, count, R, 2, dbc)))
+        return CRC_ERR_INVALID_ARGUMENT;
+    std::vector<int> at((size_t)R);
+    if (!hoist_keys(c, gs, R, elts, n_elts, at.data())) return CRC_ERR_INVALID_ARGUMENT;
+    if (count == 0) return CRC_OK;
+    const size_t ctw = crc_ct_words(c, 2);
+    WorkArena a(d_work);
+    const HoistWork L = hoist_layout(c, count, R, 2, dbc, a);
+    const bool f64 = c->tune.relin_path != 1 && k_relin64_supported(c, dbc), pair = f64 && hoist_rt(c) == 2;
+    bool any = false;
+    for (int r = 0; r < R; r++) {
+        if (at[r] >= 0) { any = true; continue; }
+        u64 *yr = d_y + (size_t)r * count * ctw;                       // g = 1: the same ciphertext in the requested form
+        HIPCHK(hipMemcpyAsync(yr, d_x, 8 * count * ctw, hipMemcpyDeviceToDevice, S(stream)));
+        if (in_form != out_form) RUN(out_form == CRC_NTT ? crc_ntt_fwd(c, yr, count, 2, stream) : crc_ntt_inv(c, yr, count, 2, stream));
+    }
+    if (!any) return CRC_OK;
+    for (size_t o = 0; o < count; o += L.step) {
+        const size_t ch = pass_len(count, o, L.step);
+        RUN(hoist_pass_head(c, L, d_x + o * ctw, in_form, ch, at.data(), R, d_cgk, dbc, f64, o == 0, stream));
+        for (int r = 0; r < R; r++) {
+            if (at[r] < 0) continue;
+            int r2 = -1;                                                // the next keyed element shares this one's K2 where two keys go per digit load
+            if (pair) for (int i = r + 1; i < R && r2 < 0; i++) if (at[i] >= 0) r2 = i;
+            if (r2 >= 0) RUN(hoist_switch2(c, L, ch, r, r2, dbc, L.z, L.z + ch * ctw, stream));
+            else RUN(hoist_switch(c, L, ch, r, at[r], d_cgk, dbc, f64, o == 0, L.z, stream));
+            const int rs[2] = {r, r2};
+            for (int i = 0; i < 2 && rs[i] >= 0; i++) {
+                u64 *yr = d_y + ((size_t)rs[i] * count + o) * ctw;
+                RUN(k_galois_permute_ntt(c, L.z + (size_t)i * ch * ctw, ch * 2 * c->k, gs[rs[i]], yr, S(stream)));
+                if (out_form == CRC_COEFF) RUN(crc_ntt_inv(c, yr, ch, 2, stream));
+            }
+            if (r2 >= 0) r = r2;                                        // (the elements between them are copies: g = 1)
+        }
+    }
+    return CRC_OK;
+}
+// y = Sum_r P_r (*) H_{g_r}(x): the hoisted rotations above with galois_diag_mac_kernel in the place of the gather, GALOIS_DIAG_MAX elements at a time.  Canonical
+// residues throughout: bit for bit crc_rotate_hoisted_forms, then crc_multiply_plain_ntt, then crc_add
+extern "C" size_t crc_diag_mac_work_bytes(const crc_ctx *c, size_t count, int R, int dbc) { return hoist_bytes(c, count, R, diag_zc(R), dbc); }
+extern "C" int crc_diag_mac_forms(crc_ctx *c, const uint64_t *d_x, int in_form, size_t count, const uint64_t *gs, int R, const uint64_t *d_p_ntt, const uint64_t *d_cgk,
+                                  const uint64_t *elts, int n_elts, int dbc, uint64_t *d_y, int out_form, void *d_work, void *stream)
+{
+    CHECK_CTX(c);
+    if (R < 1 || R > (1 << 20) || !d_p_ntt || !aligned16(d_p_ntt)) return CRC_ERR_INVALID_ARGUMENT;
+    if (!hoist_args_ok(c, d_x, in_form, count, gs, R, d_cgk, elts, n_elts, dbc, d_y, count, out_form, d_work, hoist_bytes(c, count, R, diag_zc(R), dbc)))
+        return CRC_ERR_INVALID_ARGUMENT;
+    std::vector<int> at((size_t)R);
+    if (!hoist_keys(c, gs, R, elts, n_elts, at.data())) return CRC_ERR_INVALID_ARGUMENT;
+    if (count == 0) return CRC_OK;
+    const size_t ctw = crc_ct_words(c, 2), rowp = (size_t)c->k * c->n;
+    const int zc = diag_zc(R);
+    WorkArena a(d_work);
+    const HoistWork L = hoist_layout(c, count, R, zc, dbc, a);
+    const bool f64 = c->tune.relin_path != 1 && k_relin64_supported(c, dbc), pair = f64 && hoist_rt(c) == 2;
+    for (size_t o = 0; o < count; o += L.step) {
+        const size_t ch = pass_len(count, o, L.step);
+        const u64 *xin = d_x + o * ctw;
+        RUN(hoist_pass_head(c, L, xin, in_form, ch, at.data(), R, d_cgk, dbc, f64, o == 0, stream));
+        for (int r0 = 0; r0 < R; r0 += zc) {
+            const int rn = R - r0 < zc ? R - r0 : zc;
+            const u64 *z[GALOIS_DIAG_MAX], *p[GALOIS_DIAG_MAX];
+            int held = -1;                                              // a keyed element that waits for a partner (two keys per digit load)
+            for (int i = 0; i < rn; i++) {
+                const int r = r0 + i;
+                u64 *zi = L.z + (size_t)i * ch * ctw;
+                z[i] = zi; p[i] = d_p_ntt + (size_t)r * rowp;
+                if (at[r] >= 0 && pair && held < 0) held = i;
+                else if (at[r] >= 0 && pair) { RUN(hoist_switch2(c, L, ch, r0 + held, r, dbc, L.z + (size_t)held * ch * ctw, zi, stream)); held = -1; }
+                else if (at[r] >= 0) RUN(hoist_switch(c, L, ch, r, at[r], d_cgk, dbc, f64, o == 0, zi, stream));
+                else if (in_form == CRC_NTT) z[i] = xin;               // g = 1: x itself, in NTT form
+                else RUN(ntt_copy(c, xin, ch, zi, stream));
+            }
+            if (held >= 0) RUN(hoist_switch(c, L, ch, r0 + held, at[r0 + held], d_cgk, dbc, f64, o == 0, L.z + (size_t)held * ch * ctw, stream));
+            RUN(k_galois_diag_mac(c, z, p, gs + r0, rn, ch, r0 != 0, d_y + o * ctw, S(stream)));
+        }
+    }
+    if (out_form == CRC_COEFF) RUN(crc_ntt_inv(c, d_y, count, 2, stream));
     return CRC_OK;
 }
 extern "C" int crc_square_relin(crc_ctx *c, const uint64_t *d_x, size_t count, const uint64_t *d_evk, int dbc, uint64_t *d_y, void *d_work, void *stream)

@@ -262,6 +262,44 @@ extern "C" int crc_gen_galois_keys(const crc_ctx *c, uint64_t seed, const uint64
     return gen_galois_impl(c, seed_key(seed), sk, dbc, elts, n_elts, gk);
 }
 
+// ---- conjugated Galois keys (the hoisted rotations, abi.hip) ----
+// sigma_g on an NTT-form row is a gather by index alone: X[i] = p(psi^(2 brev(i) + 1)), so NTT(sigma_g(p))[i] = X[pi_g(i)] with 2 brev(pi_g(i)) + 1 =
+// g (2 brev(i) + 1) mod 2n -- the table galois_permute_ntt_kernel computes on the fly
+extern "C" int crc_galois_ntt_table(const crc_ctx *c, uint64_t g, uint32_t *table)
+{
+    if (!c || !table || !crc_galois_elt_valid(c, g)) return CRC_ERR_INVALID_ARGUMENT;
+    const u64 n = (u64)c->n, m2 = 2 * n - 1;
+    auto brev = [&](u64 v) { u64 r = 0; for (int b = 0; b < c->logn; b++) r |= ((v >> b) & 1) << (c->logn - 1 - b); return r; };
+    for (u64 i = 0; i < n; i++) table[i] = (uint32_t)brev(((g * (2 * brev(i) + 1)) & m2) >> 1);
+    return CRC_OK;
+}
+static u64 galois_inverse(const crc_ctx *c, u64 g)
+{
+    const u64 mask = 2 * (u64)c->n - 1;
+    u64 h = 1;                                     // g^-1 = g^(n - 1) mod 2n (the odd residues have exponent n / 2)
+    for (u64 x = g & mask, e = (u64)c->n - 1; e; e >>= 1, x = x * x & mask) if (e & 1) h = h * x & mask;
+    return h;
+}
+// K'_g = sigma_g^-1(K_g): sigma_{g^-1} of every polynomial of the blob of g, the same layout.  K_g switches sigma_g(s) -> s; the gadget constants are integers,
+// which sigma fixes, so K'_g switches s -> sigma_g^-1(s), and sigma_g of that key switch's result is a ciphertext under s again.  g = 1 has no key
+extern "C" int crc_galois_conjugate_keys(const crc_ctx *c, const uint64_t *elts, int n_elts, int dbc, const uint64_t *gk, uint64_t *out)
+{
+    if (!c || !dbc_ok(dbc) || n_elts < 0 || (n_elts > 0 && (!elts || !gk || !out || gk == out))) return CRC_ERR_INVALID_ARGUMENT;
+    for (int e = 0; e < n_elts; e++) if (!crc_galois_elt_valid(c, elts[e]) || elts[e] == 1) return CRC_ERR_INVALID_ARGUMENT;
+    const size_t n = (size_t)c->n, words = crc_evk_words(c, dbc), rows = words / n;
+    crc_host::parallel_for((size_t)n_elts, 1, [&](size_t e0, size_t e1) {
+    std::vector<uint32_t> tab(n);
+    for (size_t e = e0; e < e1; e++) {
+        crc_galois_ntt_table(c, galois_inverse(c, elts[e]), tab.data());
+        for (size_t r = 0; r < rows; r++) {
+            const u64 *src = gk + e * words + r * n; u64 *dst = out + e * words + r * n;
+            for (size_t i = 0; i < n; i++) dst[i] = src[tab[i]];
+        }
+    }
+    });
+    return CRC_OK;
+}
+
 static int encrypt_impl(const crc_ctx *c, const uint64_t *pk, const uint64_t *plain, size_t count, const ChaChaKey &key, uint64_t stream_base, uint64_t *ct)
 {
     const int n = c->n, k = c->k;

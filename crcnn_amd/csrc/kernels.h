@@ -48,6 +48,14 @@ struct PolyTail { const u64 *xh, *p1, *p0; };
 bool k_relin64_poly_fused(const crc_ctx *c);           // tune.poly_tail = 0 and a transform radix whose last kernel has room for the tail
 int k_relinearize64(crc_ctx *c, const u64 *src, int src_size, int src_poly, const u64 *x3, int add_size, size_t cnt, int dbc, u64 *y, u64 *work, const u64 *kp,
                     hipStream_t st, bool out_ntt, const PoolGeom *pool = nullptr, const u64 *mul = nullptr, const PolyTail *poly = nullptr);
+// its two halves: the digit transforms into E at the front of `work` (K1), then inner products, lift and tail from an E that is there (K2 + K3)
+int k_relin64_digits(crc_ctx *c, const u64 *src, int src_size, int src_poly, size_t cnt, int dbc, u64 *work, hipStream_t st, const PoolGeom *pool = nullptr);
+int k_relin64_from_digits(crc_ctx *c, const u64 *x3, int add_size, size_t cnt, int dbc, u64 *y, u64 *work, const u64 *kp, hipStream_t st, bool out_ntt,
+                          const PoolGeom *pool = nullptr, const u64 *mul = nullptr, const PolyTail *poly = nullptr);
+// K2 + K3 of two prepared keys on one E, the digit values read once for both (work: k_relin64_work_words_multi(.., 2)): the bits of two k_relin64_from_digits
+size_t k_relin64_work_words_multi(const crc_ctx *c, size_t cnt, int dbc, int keys);
+int k_relin64_from_digits2(crc_ctx *c, const u64 *x3, int add_size, size_t cnt, int dbc, u64 *y0, u64 *y1, u64 *work, const u64 *kp0, const u64 *kp1,
+                           hipStream_t st, bool out_ntt);
 // the same terms in a kernel of their own (kernels.hip: poly2_tail_kernel), in place on y [planes][xo][yo]
 int k_poly2_tail(crc_ctx *c, u64 *y, const u64 *xh, size_t planes, const Window &w, const u64 *p2, const u64 *p1, const u64 *p0, hipStream_t st);
 int k_square(crc_ctx *c, const u64 *x, size_t cnt, u64 *y3, u64 *work, hipStream_t st, bool in_ntt = false, bool premul_c2 = false);
@@ -62,6 +70,11 @@ int k_relinearize(crc_ctx *c, const u64 *x3, size_t cnt, const u64 *evk, int dbc
 // kernels_galois.hip: sigma_g of size-2 coefficient-form ciphertexts as the size-3 rows k_relinearize(..., c2_premul = true) takes: (sigma(c0) [+ c0], 0 [c1],
 // sigma(c1) (q/q_i)^-1); g a valid Galois element, x and x3 disjoint and 16-byte aligned
 int k_galois_permute(crc_ctx *c, const u64 *x, size_t cnt, u64 g, bool accumulate, u64 *x3, hipStream_t st);
+// sigma_g on NTT-form rows [rows][n] (any modulus: a gather by index alone), out = NTT(sigma_g(INTT(in))); in and out disjoint and 16-byte aligned
+int k_galois_permute_ntt(crc_ctx *c, const u64 *in, size_t rows, u64 g, u64 *out, hipStream_t st);
+// y [cnt][2][k][n] (+)= Sum_r p[r] (*) sigma_{g[r]}(z[r]) on NTT-form ciphertexts z[r] [cnt][2][k][n] and plaintext rows p[r] [k][n]; R <= GALOIS_DIAG_MAX
+enum { GALOIS_DIAG_MAX = 32 };
+int k_galois_diag_mac(crc_ctx *c, const u64 *const *z, const u64 *const *p, const u64 *g, int R, size_t cnt, bool accumulate, u64 *y, hipStream_t st);
 int k_mac2(crc_ctx *c, const u64 *x, const u64 *w, u64 *y, const int *d_xoff, const int *d_toff, int B, const LayerShape &s, const u64 *bias_ntt,
            const unsigned *d_toffw, hipStream_t st, int xp = 0, int wp = 0, int yp = 0);
 int k_fold_pool(crc_ctx *c, const u64 *w, const u64 *bias, const u64 *div, u64 *wout, u64 *bout, int nf, int zd, int xf, int yf, int cxs, int cys,

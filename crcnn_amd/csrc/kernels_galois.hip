@@ -8,6 +8,9 @@
 // Written as a gather: with h = g^-1 mod 2n and r = (j h) mod 2n, out[j] = in[r] for r < n and -in[r - n] otherwise (i = r or r - n is the one index with
 // i g = j or j + n mod 2n).  A thread owns the coefficients j, j + 1: its stores are 16 bytes wide and coalesced, only the 8-byte reads are strided (by the
 // odd h, so the 64 lanes of a wave touch 64 different 128-byte lines of a row that sits in L2: 16-128 KiB).  j h < n 2n <= 2^29: 32-bit index arithmetic.
+//
+// Below it: the same automorphism on NTT-FORM rows, where it is an index gather alone (galois_permute_ntt_kernel), and that gather folded into a sum of
+// plaintext products (galois_diag_mac_kernel) -- the hoisted rotations and the diagonal product of abi.hip.
 #include "kernels.h"
 #include "ntt_device.h"
 
@@ -56,5 +59,91 @@ int k_galois_permute(crc_ctx *c, const u64 *x, size_t cnt, u64 g, bool accumulat
     if (blocks > 0x7fffffffull) return CRC_ERR_INVALID_ARGUMENT;
     hipLaunchKernelGGL(galois_permute_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, x3, c->d_mods, c->d_behz, c->n, c->k, bpr, (u32)h, accumulate ? 1 : 0);
     HIPCHK(hipGetLastError());
+    return CRC_OK;
+}
+
+// ---- the automorphism on NTT-form rows ----
+// A row in NTT form holds X[i] = p(psi^(2 brev(i) + 1)) (brev: the bit reversal over log2 n bits; psi the modulus' primitive 2n-th root), so
+// NTT(sigma_g(p))[i] = p(psi^(g (2 brev(i) + 1))) = X[pi_g(i)] with 2 brev(pi_g(i)) + 1 = g (2 brev(i) + 1) mod 2n: an index gather that knows nothing of the modulus, with
+// no negation and no transform.  32-bit index arithmetic: the product is taken mod 2n, a power of two, so a wrap at 2^32 changes nothing.  pi_g(i) < n for every i < n,
+// because an odd residue below 2n minus one, halved, is below n and the reversal keeps log2 n bits.
+__device__ __forceinline__ u32 galois_ntt_src(u32 i, u32 g, u32 m2, int sh)
+{
+    const u32 e = (g * (2u * (__brev(i) >> sh) + 1u)) & m2;         // odd, < 2n
+    return __brev(e >> 1) >> sh;
+}
+// in, out [rows][n]; grid: rows max(1, n / 512) workgroups of 256 threads, a thread owns the outputs i, i + 1 (one 16-byte store; the 8-byte reads are scattered
+// over a row that sits in L2)
+__global__ void __launch_bounds__(256) galois_permute_ntt_kernel(const u64 *in, u64 *out, int n, int logn, int blocks_per_row, u32 g)
+{
+    const size_t row = blockIdx.x / (u32)blocks_per_row; const u32 part = blockIdx.x - (u32)row * (u32)blocks_per_row;
+    const u32 i = (part * 256u + threadIdx.x) * 2u;
+    if (i >= (u32)n) return;                                   // n < 512: the tail of the one workgroup of a row
+    const u32 m2 = 2u * (u32)n - 1u; const int sh = 32 - logn;
+    const u64 *src = in + row * (size_t)n;
+    st2(out + row * (size_t)n + i, src[galois_ntt_src(i, g, m2, sh)], src[galois_ntt_src(i + 1u, g, m2, sh)]);
+}
+int k_galois_permute_ntt(crc_ctx *c, const u64 *in, size_t rows, u64 g, u64 *out, hipStream_t st)
+{
+    if (rows == 0) return CRC_OK;
+    const int bpr = c->n > 512 ? c->n / 512 : 1;
+    const size_t blocks = rows * bpr;
+    if (blocks > 0x7fffffffull) return CRC_ERR_INVALID_ARGUMENT;
+    hipLaunchKernelGGL(galois_permute_ntt_kernel, dim3((unsigned)blocks), dim3(256), 0, st, in, out, c->n, c->logn, bpr, (u32)g);
+    HIPCHK(hipGetLastError());
+    return CRC_OK;
+}
+
+// ---- the diagonal product: y = Sum_r P_r (*) sigma_{g_r}(Z_r), the gather of the kernel above folded into the product ----
+// Z_r [cnt][2][k][n]: NTT-form ciphertexts (the key switch's results before their automorphism), P_r [k][n]: NTT-form plaintext rows, y [cnt][2][k][n].
+// y[s] = Sum_r P_r[s] Z_r[pi_r(s)] mod q_j, so the R permuted ciphertexts are never written.  The products are summed as 128-bit integers and reduced once: with
+// canonical operands a product is below q^2, the launcher keeps R q^2 + q below 2^128 (R <= 32 for moduli of up to 61 bits), and barrett128 is exact for every
+// 128-bit value -- the canonical residue of the sum, which is what R canonical products added mod q give.
+struct GaloisDiagArgs { const u64 *z[GALOIS_DIAG_MAX]; const u64 *p[GALOIS_DIAG_MAX]; u32 g[GALOIS_DIAG_MAX]; };
+__global__ void __launch_bounds__(256) galois_diag_mac_kernel(GaloisDiagArgs a, int R, u64 *y, const ModParams *mods, int n, int logn, int k, int blocks_per_row,
+                                                              int accumulate)
+{
+    const size_t row = blockIdx.x / (u32)blocks_per_row; const u32 part = blockIdx.x - (u32)row * (u32)blocks_per_row;      // row = (ct 2 + poly) k + j
+    const u32 s = (part * 256u + threadIdx.x) * 2u;
+    if (s >= (u32)n) return;
+    const int j = (int)(row % (size_t)k);
+    const ModParams m = mods[j];
+    const u32 m2 = 2u * (u32)n - 1u; const int sh = 32 - logn;
+    unsigned __int128 acc0 = 0, acc1 = 0;
+    u64 *yo = y + row * (size_t)n + s;
+    if (accumulate) { const ulonglong2 v = ld2(yo); acc0 = v.x; acc1 = v.y; }
+    for (int r = 0; r < R; r++) {
+        const u64 *zr = a.z[r] + row * (size_t)n;
+        const ulonglong2 w = ld2(a.p[r] + (size_t)j * n + s);
+        const u32 g = a.g[r];
+        u64 lo, hi;
+        mul64wide(w.x, zr[galois_ntt_src(s, g, m2, sh)], lo, hi); acc0 += ((unsigned __int128)hi << 64) | lo;
+        mul64wide(w.y, zr[galois_ntt_src(s + 1u, g, m2, sh)], lo, hi); acc1 += ((unsigned __int128)hi << 64) | lo;
+    }
+    st2(yo, barrett128((u64)acc0, (u64)(acc0 >> 64), m), barrett128((u64)acc1, (u64)(acc1 >> 64), m));
+}
+// the elements one launch may sum: R q_max^2 + q_max < 2^128
+static int diag_group(const crc_ctx *c)
+{
+    int bits = 0;
+    for (int i = 0; i < c->k; i++) if ((int)c->tabs[i].m.bits > bits) bits = c->tabs[i].m.bits;
+    const int room = 127 - 2 * bits;
+    return room >= 5 ? GALOIS_DIAG_MAX : room > 0 ? 1 << room : 1;
+}
+int k_galois_diag_mac(crc_ctx *c, const u64 *const *z, const u64 *const *p, const u64 *g, int R, size_t cnt, bool accumulate, u64 *y, hipStream_t st)
+{
+    if (cnt == 0 || R < 1) return CRC_OK;
+    if (R > GALOIS_DIAG_MAX) return CRC_ERR_INVALID_ARGUMENT;
+    const int bpr = c->n > 512 ? c->n / 512 : 1;
+    const size_t blocks = cnt * 2 * (size_t)c->k * bpr;
+    if (blocks > 0x7fffffffull) return CRC_ERR_INVALID_ARGUMENT;
+    for (int r0 = 0, per = diag_group(c); r0 < R; r0 += per) {
+        GaloisDiagArgs a{};
+        const int rn = R - r0 < per ? R - r0 : per;
+        for (int r = 0; r < rn; r++) { a.z[r] = z[r0 + r]; a.p[r] = p[r0 + r]; a.g[r] = (u32)g[r0 + r]; }
+        hipLaunchKernelGGL(galois_diag_mac_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, rn, y, c->d_mods, c->n, c->logn, c->k, bpr,
+                           accumulate || r0 ? 1 : 0);
+        HIPCHK(hipGetLastError());
+    }
     return CRC_OK;
 }

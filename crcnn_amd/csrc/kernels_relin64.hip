@@ -285,6 +285,65 @@ __global__ void __launch_bounds__(256, CT * PJ <= 36 ? 4 : 1) relin_mac_f64_kern
             for (int pj = 0; pj < PJ; pj++) A[(((ct0 + c) * 2 * K + pj0 + pj) * CRC_NF64 + m) * nn + s] = acc[c][pj];
 }
 
+// K2 for RT keys at once (the hoisted rotations: several keys are applied to the digits of ONE ciphertext): the products of RT key tiles per digit value
+// loaded, so a call over R keys streams E from HBM R / RT times instead of R times.  The tile is CT x PJ x RT sums, kept within the 36 doubles the look-ahead
+// path of the kernel above affords (CT shrinks as RT grows: the key tiles, RT of them now, still come from L2).  Every sum adds the same reduced products in
+// the same order as the kernel above: the same doubles.  A of key r: A + r a_stride
+struct RelinMultiKeys { const double *kf[2]; };
+template <int K, int CT, int PJ, int RT>
+__global__ void __launch_bounds__(256, 4) relin_mac_multi_f64_kernel(const double *E, RelinMultiKeys keys, double *A, size_t a_stride, F64Params fp, int n, int D,
+    size_t cnt)
+{
+    static_assert(CT * PJ * RT <= 36 && RT <= 2, "the tile must fit the look-ahead path's register budget");
+    constexpr int PJS = 2 * K / PJ;
+    const int sblocks = n / blockDim.x;
+    const unsigned groups = (unsigned)((cnt + CT - 1) / CT);            // ciphertext group fastest, as above: resident workgroups share their key tiles
+    unsigned b = blockIdx.x;
+    const size_t ct0 = (size_t)(b % groups) * CT; b /= groups;
+    const int s = (b % sblocks) * blockDim.x + threadIdx.x; b /= sblocks;
+    const int pj0 = (b % PJS) * PJ; b /= PJS;
+    const int m = b % CRC_NF64;
+    const F64Mod md = fp.m[m];
+    double acc[RT][CT][PJ];
+#pragma unroll
+    for (int r = 0; r < RT; r++)
+#pragma unroll
+        for (int c = 0; c < CT; c++)
+#pragma unroll
+            for (int pj = 0; pj < PJ; pj++) acc[r][c][pj] = 0.0;
+    const size_t nn = (size_t)n;
+    double e[CT];
+    auto fetch = [&](int g, double (&ev)[CT]) {
+#pragma unroll
+        for (int c = 0; c < CT; c++) ev[c] = ct0 + c < cnt ? E[(((ct0 + c) * D + g) * CRC_NF64 + m) * nn + s] : 0.0;
+    };
+    fetch(0, e);
+    for (int g = 0; g < D; g++) {
+        double en[CT];
+        if (g + 1 < D) fetch(g + 1, en);
+        const size_t ko = (((size_t)g * 2 * K + pj0) * CRC_NF64 + m) * nn + s;
+#pragma unroll
+        for (int r = 0; r < RT; r++)
+#pragma unroll
+            for (int pj = 0; pj < PJ; pj++) {
+                const double kv = keys.kf[r][ko + (size_t)pj * CRC_NF64 * nn];
+#pragma unroll
+                for (int c = 0; c < CT; c++) acc[r][c][pj] += f64_mulmod(kv, e[c], md);
+            }
+        if (g + 1 < D) {
+#pragma unroll
+            for (int c = 0; c < CT; c++) e[c] = en[c];
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < RT; r++)
+#pragma unroll
+        for (int c = 0; c < CT; c++)
+            if (ct0 + c < cnt)
+#pragma unroll
+                for (int pj = 0; pj < PJ; pj++) A[r * a_stride + (((ct0 + c) * 2 * K + pj0 + pj) * CRC_NF64 + m) * nn + s] = acc[r][c][pj];
+}
+
 // ---- K3: inverse transforms, CRT lift, mod q_j, + (c0, c1) --------------------------------------------------------------------------------------------------
 // A [ct][poly k + j][m][n]; x3: size-`add_size` ciphertexts whose polys 0, 1 are added (coefficient form); y [ct][2][k][n].  The first prime's result waits in
 // registers (NPT points per thread, reduced) while the image serves the second transform -- round 3 parked it in its own row of A (6 rows written and read back
@@ -648,6 +707,19 @@ static int relin64_mac(crc_ctx *c, const double *E, const double *Kf, double *A,
     return CRC_OK;
 }
 
+template <int K>
+static int relin64_mac2(crc_ctx *c, const double *E, const double *Kf0, const double *Kf1, double *A, size_t a_stride, int D, size_t cnt, hipStream_t st)
+{
+    constexpr int PJ = 2 * K <= 8 ? 2 * K : (2 * K) % 8 == 0 ? 8 : (2 * K) % 6 == 0 ? 6 : (2 * K) % 5 == 0 ? 5 : 7, CT = 18 / PJ > 6 ? 6 : 18 / PJ, PJS = 2 * K / PJ;       // (k = 1: 8 x 2 x 2 sums and the 16 look-ahead values spill)
+    static_assert(PJ * PJS == 2 * K && CT >= 1, "key columns must split evenly");
+    const int threads = c->n < 256 ? c->n : 256, sblocks = c->n / threads;
+    const size_t groups = (cnt + CT - 1) / CT;
+    hipLaunchKernelGGL((relin_mac_multi_f64_kernel<K, CT, PJ, 2>), dim3((unsigned)(groups * CRC_NF64 * PJS * sblocks)), dim3(threads), 0, st, E,
+        RelinMultiKeys{{Kf0, Kf1}}, A, a_stride, c->f64, c->n, D, cnt);
+    HIPCHK(hipGetLastError());
+    return CRC_OK;
+}
+
 // the wave-local transforms (one workgroup barrier per transform) serve the two rings the bench configurations use; CRC_F64_WAVE=0 keeps the round-4 kernels
 // (bit 1: the digit kernel, bit 2: K3.  Measured, same box: K1 -17 % at n = 8192, -16 % at 16384; K3 +3 % / +14 % in its first form, which parked the first
 // prime's result in scratch, -0.3 % / -1.5 % of the whole sequence now -- its 64-bit forward transform is untouched: profiles/r05_square_pool_wave_local_*.txt)
@@ -701,10 +773,12 @@ static int relin64_tail(crc_ctx *c, const double *A, const u64 *x3, int add_size
     return CRC_OK;
 }
 
+// The key switch in two halves.  K1 (k_relin64_digits): the digit polynomials of c2 (q/q_i)^-1, transformed over the fp64 primes, into E at the front of `work`.
+// K2 + K3 (k_relin64_from_digits): the inner products of an E that is already there with one prepared key, the CRT lift, and the sum with (c0, c1).  E depends
+// on the ciphertext alone, so several keys can be applied to one K1 (the hoisted rotations); k_relinearize64 is the two in a row.
 // src / src_size / src_poly: where c2 (q/q_i)^-1 lives; x3 / add_size: the ciphertexts whose (c0, c1) are added; kp: the keys as k_relin64_prepare_keys left
 // them; work: cnt n (2 D + 4 k) words
-int k_relinearize64(crc_ctx *c, const u64 *src, int src_size, int src_poly, const u64 *x3, int add_size, size_t cnt, int dbc, u64 *y, u64 *work, const u64 *kp,
-                    hipStream_t st, bool out_ntt, const PoolGeom *pool, const u64 *mul, const PolyTail *poly)
+int k_relin64_digits(crc_ctx *c, const u64 *src, int src_size, int src_poly, size_t cnt, int dbc, u64 *work, hipStream_t st, const PoolGeom *pool)
 {
     if (cnt == 0) return CRC_OK;
     if (!k_relin64_supported(c, dbc)) return CRC_ERR_UNSUPPORTED;
@@ -714,9 +788,7 @@ int k_relinearize64(crc_ctx *c, const u64 *src, int src_size, int src_poly, cons
     Relin64Tab tab{};
     int D = 0;
     for (int i = 0; i < c->k; i++) { tab.L[i] = (unsigned char)evk_digits(c->q[i], dbc); tab.g0[i] = (unsigned char)D; D += tab.L[i]; }
-    const double *Kf = reinterpret_cast<const double *>(kp);
-    int rc;
-    double *E = reinterpret_cast<double *>(work), *A = E + cnt * D * CRC_NF64 * n;
+    double *E = reinterpret_cast<double *>(work);
     const size_t lds = n * 8;
     const int RB = f64_radix(c);
     if (pool) {
@@ -755,6 +827,21 @@ int k_relinearize64(crc_ctx *c, const u64 *src, int src_size, int src_poly, cons
             c->logn, c->k, D, dbc, tab);
         HIPCHK(hipGetLastError());
     }
+    return CRC_OK;
+}
+int k_relin64_from_digits(crc_ctx *c, const u64 *x3, int add_size, size_t cnt, int dbc, u64 *y, u64 *work, const u64 *kp, hipStream_t st, bool out_ntt,
+                          const PoolGeom *pool, const u64 *mul, const PolyTail *poly)
+{
+    if (cnt == 0) return CRC_OK;
+    if (!k_relin64_supported(c, dbc)) return CRC_ERR_UNSUPPORTED;
+    if (pool && !k_relin64_pool_supported(c, dbc, pool->xf * pool->yf)) return CRC_ERR_UNSUPPORTED;
+    const size_t n = c->n;
+    int D = 0;
+    for (int i = 0; i < c->k; i++) D += evk_digits(c->q[i], dbc);
+    const double *Kf = reinterpret_cast<const double *>(kp);
+    int rc;
+    double *E = reinterpret_cast<double *>(work), *A = E + cnt * D * CRC_NF64 * n;
+    const int RB = f64_radix(c);
     switch (c->k) {
 #define MACK(KV) case KV: rc = c->tune.relin_mac_ct == 8 ? relin64_mac<KV, 8>(c, E, Kf, A, D, cnt, st) : relin64_mac<KV, 4>(c, E, Kf, A, D, cnt, st); break;
     MACK(1) MACK(2) MACK(3) MACK(4) MACK(5) MACK(6) MACK(7) MACK(8)
@@ -767,4 +854,48 @@ int k_relinearize64(crc_ctx *c, const u64 *src, int src_size, int src_poly, cons
     return RB == 3 ? relin64_tail<3, 16>(c, A, x3, add_size, y, cnt, out_ntt, st, mul, pool, poly)
          : RB == 4 ? relin64_tail<4, 16>(c, A, x3, add_size, y, cnt, out_ntt, st, mul, pool, poly) : relin64_tail<5, 32>(c, A, x3, add_size, y, cnt, out_ntt, st,
              mul, pool, poly);
+}
+int k_relinearize64(crc_ctx *c, const u64 *src, int src_size, int src_poly, const u64 *x3, int add_size, size_t cnt, int dbc, u64 *y, u64 *work, const u64 *kp,
+                    hipStream_t st, bool out_ntt, const PoolGeom *pool, const u64 *mul, const PolyTail *poly)
+{
+    const int rc = k_relin64_digits(c, src, src_size, src_poly, cnt, dbc, work, st, pool);
+    return rc ? rc : k_relin64_from_digits(c, x3, add_size, cnt, dbc, y, work, kp, st, out_ntt, pool, mul, poly);
+}
+
+// scratch of K2 + K3 for `keys` keys at once: one more A per further key behind k_relin64_work_words
+size_t k_relin64_work_words_multi(const crc_ctx *c, size_t cnt, int dbc, int keys)
+{
+    return k_relin64_work_words(c, cnt, dbc) + (size_t)(keys > 1 ? keys - 1 : 0) * cnt * c->n * CRC_NF64 * 2 * c->k;
+}
+// K2 + K3 of TWO prepared keys on the E that is there (relin_mac_multi_f64_kernel): y0 / y1 what k_relin64_from_digits gives with kp0 / kp1, bit for bit.
+// work: k_relin64_work_words_multi(.., 2)
+int k_relin64_from_digits2(crc_ctx *c, const u64 *x3, int add_size, size_t cnt, int dbc, u64 *y0, u64 *y1, u64 *work, const u64 *kp0, const u64 *kp1,
+                           hipStream_t st, bool out_ntt)
+{
+    if (cnt == 0) return CRC_OK;
+    if (!k_relin64_supported(c, dbc)) return CRC_ERR_UNSUPPORTED;
+    const size_t n = c->n;
+    int D = 0;
+    for (int i = 0; i < c->k; i++) D += evk_digits(c->q[i], dbc);
+    double *E = reinterpret_cast<double *>(work), *A = E + cnt * D * CRC_NF64 * n;
+    const size_t a_stride = cnt * 2 * c->k * CRC_NF64 * n;
+    const double *K0 = reinterpret_cast<const double *>(kp0), *K1 = reinterpret_cast<const double *>(kp1);
+    int rc;
+    switch (c->k) {
+#define MACK(KV) case KV: rc = relin64_mac2<KV>(c, E, K0, K1, A, a_stride, D, cnt, st); break;
+    MACK(1) MACK(2) MACK(3) MACK(4) MACK(5) MACK(6) MACK(7) MACK(8)
+#undef MACK
+    default: return CRC_ERR_UNSUPPORTED;
+    }
+    if (rc) return rc;
+    const int RB = f64_radix(c);
+    u64 *ys[2] = {y0, y1};
+    for (int r = 0; r < 2; r++) {
+        const double *Ar = A + r * a_stride;
+        rc = RB == 3 ? relin64_tail<3, 16>(c, Ar, x3, add_size, ys[r], cnt, out_ntt, st, nullptr, nullptr, nullptr)
+           : RB == 4 ? relin64_tail<4, 16>(c, Ar, x3, add_size, ys[r], cnt, out_ntt, st, nullptr, nullptr, nullptr)
+                     : relin64_tail<5, 32>(c, Ar, x3, add_size, ys[r], cnt, out_ntt, st, nullptr, nullptr, nullptr);
+        if (rc) return rc;
+    }
+    return CRC_OK;
 }

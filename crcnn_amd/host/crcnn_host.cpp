@@ -1,5 +1,6 @@
 // crcnn_host.cpp -- implementation of the CrCNN-compatible C++ host classes on top of the C ABI (include/crcnn_hip.h).
 #include "crcnn_host.h"
+#include "diag_plan.h"
 #include "../csrc/host_parallel.h"          // std::thread ranges (header only; no other csrc internals are used here: the engine is reached through the C ABI)
 #include <algorithm>
 #include <atomic>
@@ -28,6 +29,7 @@ vector<uint64_t> secret_key, public_key, ev_keys16_host;
 shared_ptr<DeviceBuffer> ev_keys16;
 vector<uint64_t> galois_elts, galois_keys_host;
 static shared_ptr<DeviceBuffer> g_galois_keys;              // the key blobs of galois_elts, dbc g_galois_dbc, resident in HBM
+static shared_ptr<DeviceBuffer> g_galois_ckeys;             // their conjugated blobs (crc_galois_conjugate_keys_dev): the keys of the hoisted rotations
 static int g_galois_dbc = 0;
 static bool g_det = false;                                  // setDeterministicSeed(): tests / bench only
 static uint64_t g_det_seed = 0;
@@ -342,7 +344,7 @@ static const uint64_t *deviceKey(shared_ptr<DeviceBuffer> &d, uint64_t &fp, cons
 void delParameters()
 {
     ev_keys16.reset();
-    g_galois_keys.reset(); galois_elts.clear(); galois_keys_host.clear(); g_galois_dbc = 0;
+    g_galois_keys.reset(); g_galois_ckeys.reset(); galois_elts.clear(); galois_keys_host.clear(); g_galois_dbc = 0;
     g_d_sk.reset(); g_d_pk.reset();
     g_scratch.reset(); g_wltile.reset(); g_xltile.reset();
     g_pool.flush();
@@ -646,6 +648,12 @@ void generateGaloisKeys(int dbc, vector<uint64_t> elts)
     else chk(crc_gen_galois_keys_key(ctx(), g_master_key, secret_key.data(), dbc, elts.data(), (int)elts.size(), keys.data()), "crc_gen_galois_keys_key");
     g_galois_keys = make_shared<DeviceBuffer>(keys.size() * 8 + 8);
     chk(crc_memcpy_h2d(ctx(), g_galois_keys->ptr, keys.data(), keys.size() * 8, stream()), "crc_memcpy_h2d");
+    // the conjugated blobs beside them, made on the device element by element (g = 1 has no key to conjugate: its blob is never read)
+    g_galois_ckeys = make_shared<DeviceBuffer>(keys.size() * 8 + 8);
+    const size_t kw = crc_evk_words(ctx(), dbc);
+    for (size_t e = 0; e < elts.size(); e++)
+        if (elts[e] != 1) chk(crc_galois_conjugate_keys_dev(ctx(), &elts[e], 1, dbc, (const uint64_t *)g_galois_keys->ptr + e * kw,
+                                                            (uint64_t *)g_galois_ckeys->ptr + e * kw, stream()), "crc_galois_conjugate_keys_dev");
     chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
     galois_elts = std::move(elts); galois_keys_host = std::move(keys); g_galois_dbc = dbc;
 }
@@ -684,6 +692,67 @@ static ciphertext3D galoisOp(const char *what, const ciphertext3D &t, int mode, 
 ciphertext3D rotateRows(const ciphertext3D &t, int steps, int out_form) { return galoisOp("rotateRows", t, 0, steps, out_form); }
 ciphertext3D rotateColumns(const ciphertext3D &t, int out_form) { return galoisOp("rotateColumns", t, 1, 0, out_form); }
 ciphertext3D sumSlots(const ciphertext3D &t, int out_form) { return galoisOp("sumSlots", t, 2, 0, out_form); }
+// ---- hoisted rotations and the matrix-vector product over slots ------------------------------------------------------------
+// what the two share: the reference's checks in rotateRows' order, then every step's element with its own conjugated key in the set
+static vector<uint64_t> hoistedElements(const char *what, const ciphertext3D &t, const vector<int> &steps, int out_form)
+{
+    if (!crc_slots_supported(ctx())) throw logic_error("encryption parameters do not support batching");
+    if (!t.buf) throw invalid_argument(string(what) + ": empty tensor");
+    if ((t.form != CRC_COEFF && t.form != CRC_NTT) || (out_form != CRC_COEFF && out_form != CRC_NTT))
+        throw invalid_argument(string(what) + ": ciphertext forms only (CRC_COEFF / CRC_NTT)");
+    vector<uint64_t> gs;
+    for (int s : steps) {
+        const uint64_t g = crc_galois_elt_rows(ctx(), s);
+        if (!g) throw invalid_argument("step count too large");
+        if (g != 1 && find(galois_elts.begin(), galois_elts.end(), g) == galois_elts.end()) throw invalid_argument("galois key not present");
+        gs.push_back(g);
+    }
+    return gs;
+}
+vector<ciphertext3D> rotateRowsMany(const ciphertext3D &t, const vector<int> &steps, int out_form)
+{
+    const vector<uint64_t> gs = hoistedElements("rotateRowsMany", t, steps, out_form);
+    if (gs.empty()) return {};
+    const int R = (int)gs.size(), dbc = g_galois_dbc ? g_galois_dbc : 16;
+    if ((long long)R * t.B > 0x7fffffffLL) throw invalid_argument("rotateRowsMany: too many results");
+    ciphertext3D all(R * t.B, t.zd, t.xd, t.yd, out_form);              // [R][count]: one buffer, handed out as R views
+    const size_t cnt = t.count();
+    ensure(g_scratch, crc_rotate_hoisted_work_bytes(ctx(), cnt, R, dbc));
+    chk(crc_rotate_hoisted_forms(ctx(), t.data(), t.form, cnt, gs.data(), R, g_galois_ckeys ? (const uint64_t *)g_galois_ckeys->ptr : nullptr, galois_elts.data(),
+                                 (int)galois_elts.size(), dbc, all.data(), out_form, g_scratch->ptr, stream()), "rotateRowsMany");
+    vector<ciphertext3D> out;
+    for (int r = 0; r < R; r++) out.push_back(all.images(r * t.B, t.B));
+    return out;
+}
+void diagMatvecPlan(const vector<vector<int64_t>> &W, int M, int n, vector<int> &steps, vector<int64_t> &rows)
+{
+    if (!crc_diag_plan(W, M, n, steps, rows)) throw invalid_argument("matvecSlots: M must be a power of two <= n/2 and W at most M x M");
+}
+ciphertext3D matvecSlots(const ciphertext3D &t, const vector<vector<int64_t>> &W, int M, int out_form)
+{
+    if (!crc_slots_supported(ctx())) throw logic_error("encryption parameters do not support batching");
+    const int n = N(), k = crc_ctx_k(ctx());
+    vector<int> steps; vector<int64_t> rows;
+    diagMatvecPlan(W, M, n, steps, rows);
+    const vector<uint64_t> gs = hoistedElements("matvecSlots", t, steps, out_form);
+    ciphertext3D out(t.B, t.zd, t.xd, t.yd, out_form);
+    const size_t cnt = t.count(), ctb = crc_ct_words(ctx(), 2) * 8;
+    if (gs.empty()) {                                                   // W = 0: the transparent zero ciphertext, as the sum of no terms
+        chk(crc_memset(ctx(), out.data(), 0, cnt * ctb, stream()), "crc_memset");
+        return out;
+    }
+    const int R = (int)gs.size(), dbc = g_galois_dbc ? g_galois_dbc : 16;
+    vector<uint64_t> plain((size_t)R * n);
+    chk(crc_slots_compose(ctx(), rows.data(), R, n, n, 1, plain.data()), "crc_slots_compose");
+    DeviceBuffer d_plain(plain.size() * 8), d_p((size_t)R * k * n * 8);
+    chk(crc_memcpy_h2d(ctx(), d_plain.ptr, plain.data(), plain.size() * 8, stream()), "crc_memcpy_h2d");
+    chk(crc_plain_to_ntt(ctx(), (const uint64_t *)d_plain.ptr, R, (uint64_t *)d_p.ptr, stream()), "crc_plain_to_ntt");
+    ensure(g_scratch, crc_diag_mac_work_bytes(ctx(), cnt, R, dbc));
+    chk(crc_diag_mac_forms(ctx(), t.data(), t.form, cnt, gs.data(), R, (const uint64_t *)d_p.ptr, g_galois_ckeys ? (const uint64_t *)g_galois_ckeys->ptr : nullptr,
+                           galois_elts.data(), (int)galois_elts.size(), dbc, out.data(), out_form, g_scratch->ptr, stream()), "matvecSlots");
+    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");           // (the diagonals' buffers go out of scope here)
+    return out;
+}
 vector<floatCube> decryptImages(const ciphertext3D &t)
 {
     const int n = N();

@@ -170,6 +170,22 @@ extern std::vector<uint64_t> galois_elts, galois_keys_host;             // the e
 ciphertext3D rotateRows(const ciphertext3D &t, int steps, int out_form = CRC_COEFF);
 ciphertext3D rotateColumns(const ciphertext3D &t, int out_form = CRC_COEFF);
 ciphertext3D sumSlots(const ciphertext3D &t, int out_form = CRC_COEFF);
+// Hoisted rotations (include/crcnn_hip.h, "Hoisted rotations"): generateGaloisKeys also keeps every key's CONJUGATED blob on the device, and rotateRowsMany
+// rotates every ciphertext of the tensor by each of `steps` from ONE digit decomposition -- result r is what rotateRows(t, steps[r]) decrypts to, in a ciphertext
+// of its own definition (not rotateRows' bits), as a view of one shared buffer.  Every step's element 3^steps needs ITS OWN key in the set: no chain of steps is
+// planned ("galois key not present" otherwise; step 0 needs none).  Exceptions as rotateRows
+std::vector<ciphertext3D> rotateRowsMany(const ciphertext3D &t, const std::vector<int> &steps, int out_form = CRC_COEFF);
+// y = W x over the slots of ONE image per ciphertext, by the diagonal method: y = Sum_d diag_d (.) rotateRows(x, d) over the non-zero diagonals of W, each
+// rotation hoisted and the products fused with it (crc_diag_mac_forms).  W: out x in integers mod t (any int64 is taken mod t), out, in <= M, zero-padded to
+// M x M; M a power of two <= n/2.
+// INPUT CONTRACT: the vector x (in <= M entries, zero-padded to M) must be TILED WITH PERIOD M over all n slots of every ciphertext -- slot i holds x[i mod M]
+// in both rows of n/2 slots -- so that a row rotation is a rotation mod M.  The result is tiled the same way: slot i holds (W x)[i mod M], zero beyond `out`.
+// The keys of 3^d for every non-zero diagonal d >= 1 must be in the set (generateGaloisKeys(dbc, elements)).  A host function, not a layer kind: a slot-batched
+// network keeps one IMAGE per slot, this keeps one VECTOR ENTRY per slot -- the low-latency counterpart for a single image.
+// std::logic_error when the parameters do not support batching, std::invalid_argument for a bad M or shape, other forms, a missing key
+ciphertext3D matvecSlots(const ciphertext3D &t, const std::vector<std::vector<int64_t>> &W, int M, int out_form = CRC_COEFF);
+// the plan matvecSlots follows: the steps of W's non-zero diagonals and their slot rows [steps][n], rows[r][i] = W[i mod M][(i mod M + steps[r]) mod M]
+void diagMatvecPlan(const std::vector<std::vector<int64_t>> &W, int M, int n, std::vector<int> &steps, std::vector<int64_t> &rows);
 
 // ---- layers (CrCNN/src/layer.h:10-31) ------------------------------------------------------------------------------
 class Layer {

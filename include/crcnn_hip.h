@@ -646,6 +646,43 @@ int crc_rotate_columns_forms(crc_ctx *ctx, const uint64_t *d_x, int in_form, siz
 size_t crc_sum_slots_work_bytes(const crc_ctx *ctx, size_t count, int dbc);
 int crc_sum_slots_forms(crc_ctx *ctx, const uint64_t *d_x, int in_form, size_t count, const uint64_t *d_gk, const uint64_t *elts, int n_elts, int dbc,
                         uint64_t *d_y, int out_form, void *d_work, void *stream);
+/* ---------------------------------------------------------------------------------------------------------------
+ * Hoisted rotations: many automorphisms of ONE ciphertext from one digit decomposition, and the diagonal product over slots that consumes them.
+ *
+ * For an element g with key K_g (crc_gen_galois_keys: a key from sigma_g(s) to s) the CONJUGATED key is K'_g = sigma_g^-1(K_g): sigma_{g^-1 mod 2n} of every
+ * polynomial of the blob, the same layout and size.  The gadget constants are integers, which sigma fixes, so K'_g switches from s to sigma_g^-1(s), and
+ *     H_g(ct) := sigma_g( (c0, 0) + KeySwitch(c1; K'_g) )
+ * decrypts to sigma_g(m) with the noise law of apply_galois.  KeySwitch is relinearisation's: the (q/q_i)^-1 premultiply, unsigned dbc-bit digits of the canonical
+ * residue, the inner product mod q_j.  The digits are those of c1 itself -- independent of g, so they and their transforms are made once for all elements of a
+ * call.  H_g is NOT apply_galois(ct, g) bit for bit (the digits of sigma(c1) are not sigma of the digits of c1 wherever sigma negates): it is an operation of its
+ * own, and the text above fixes its bits on either key-switch path, every step being an exact function on Z_q.
+ *   crc_galois_ntt_table        the automorphism on an NTT-form row is an index gather, the same for every modulus: NTT(sigma_g(p))[i] = NTT(p)[table[i]]
+ *   crc_galois_conjugate_keys   host memory, any context: h_out[e] = K'_{elts[e]} from h_gk[e] = K_{elts[e]}.  CRC_ERR_INVALID_ARGUMENT for an invalid element,
+ *                               for g = 1 (it has no key) and for a bad dbc, as crc_gen_galois_keys
+ *   crc_galois_conjugate_keys_dev   the same on device blobs (16-byte aligned, disjoint)
+ *   crc_galois_permute_ntt_dev  unit-test access to galois_permute_ntt_kernel: NTT-form d_in [rows][k][n] -> d_out = NTT(sigma_g(INTT(d_in))); disjoint, aligned
+ *   crc_rotate_hoisted_forms    d_y [R][count] size-2 ciphertexts: d_y[r] = H_{gs[r]}(d_x), or d_x itself in out_form where gs[r] = 1.  Every gs[r] != 1 must have
+ *                               its own CONJUGATED key in the set (d_cgk, elts): there is no chain of steps for an absent key.  A set of un-conjugated keys
+ *                               passed by mistake cannot be told apart and gives ciphertexts that do not decrypt.  d_work: crc_rotate_hoisted_work_bytes(ctx,
+ *                               count, R, dbc) -- bounded in count by internal passes, R prepared keys (each made once per call, not per pass)
+ *   crc_diag_mac_forms          d_y [count] = Sum_r P_r (*) H_{gs[r]}(d_x) with NTT-form plaintext rows d_p_ntt [R][k][n] (crc_plain_to_ntt): bit for bit
+ *                               crc_rotate_hoisted_forms, then crc_multiply_plain_ntt per element, then crc_add -- but the rotated ciphertexts are never
+ *                               written (the gather is folded into the product).  With the slots of one image tiled with period M over both rows and the
+ *                               diagonals of an M x M matrix as P_r, gs[r] = crc_galois_elt_rows(d_r), this is the matrix-vector product over slots.
+ *                               d_work: crc_diag_mac_work_bytes(ctx, count, R, dbc)
+ * Refusals as in the paragraph above (null / misaligned / overlapping operands, forms, dbc, an invalid element), plus R < 1 and a missing conjugated key:
+ * CRC_ERR_INVALID_ARGUMENT, nothing launched.  count = 0 is CRC_OK.
+ * ------------------------------------------------------------------------------------------------------------- */
+int crc_galois_ntt_table(const crc_ctx *ctx, uint64_t g, uint32_t *table /*[n]*/);
+int crc_galois_conjugate_keys(const crc_ctx *ctx, const uint64_t *elts, int n_elts, int dbc, const uint64_t *h_gk, uint64_t *h_out);
+int crc_galois_conjugate_keys_dev(crc_ctx *ctx, const uint64_t *elts, int n_elts, int dbc, const uint64_t *d_gk, uint64_t *d_out, void *stream);
+int crc_galois_permute_ntt_dev(crc_ctx *ctx, const uint64_t *d_in, size_t rows, uint64_t g, uint64_t *d_out, void *stream);
+size_t crc_rotate_hoisted_work_bytes(const crc_ctx *ctx, size_t count, int R, int dbc);
+int crc_rotate_hoisted_forms(crc_ctx *ctx, const uint64_t *d_x, int in_form, size_t count, const uint64_t *gs /*[R], host*/, int R, const uint64_t *d_cgk,
+                             const uint64_t *elts, int n_elts, int dbc, uint64_t *d_y /*[R][count]*/, int out_form, void *d_work, void *stream);
+size_t crc_diag_mac_work_bytes(const crc_ctx *ctx, size_t count, int R, int dbc);
+int crc_diag_mac_forms(crc_ctx *ctx, const uint64_t *d_x, int in_form, size_t count, const uint64_t *gs /*[R], host*/, int R, const uint64_t *d_p_ntt /*[R][k][n]*/,
+                       const uint64_t *d_cgk, const uint64_t *elts, int n_elts, int dbc, uint64_t *d_y /*[count]*/, int out_form, void *d_work, void *stream);
 /* FractionalEncoder::decode / encode (encoder.cpp:1226-1270, 1013-1076; 64 integer + 32 fractional coefficients, base 3: CrCNN/src/globals.cpp:52) on the
  * device: the doubles crc_decode returns for d_plain [count][n], and the dense plaintexts [count][n] crc_encode_f32 / _f64 make of the values -- the same IEEE
  * operations in the same order as the host encoder, contraction off. */
