@@ -267,6 +267,8 @@ def load():
     L.crc_rotate_hoisted_forms.argtypes = [VP, VP, CI, SZ, PU, CI, VP, PU, CI, CI, VP, CI, VP, VP]
     L.crc_diag_mac_work_bytes.restype = SZ; L.crc_diag_mac_work_bytes.argtypes = [VP, SZ, CI, CI]
     L.crc_diag_mac_forms.argtypes = [VP, VP, CI, SZ, PU, CI, VP, VP, PU, CI, CI, VP, CI, VP, VP]
+    L.crc_diag_mac_bsgs_work_bytes.restype = SZ; L.crc_diag_mac_bsgs_work_bytes.argtypes = [VP, SZ, CI, CI, CI]
+    L.crc_diag_mac_bsgs_forms.argtypes = [VP, VP, CI, SZ, PU, CI, PU, CI, VP, VP, PU, CI, CI, VP, CI, VP, VP]
     L.crc_noise_budget.argtypes = [VP, PU, PU, CI]
     _lib = L
     return L
@@ -308,6 +310,40 @@ def diag_matvec_plan(W, M, n):
             steps.append(d)
             rows.append(np.tile(diag, n // M))
     return steps, np.array(rows, dtype=np.int64).reshape(len(steps), n)
+
+
+def _bsgs_args(M, n, B, what):
+    if M < 1 or M & (M - 1) or M > n // 2 or B < 1 or B & (B - 1) or B > M:
+        raise ValueError(what + ": M a power of two <= n/2, B a power of two with 1 <= B <= M")
+
+
+def bsgs_matvec_plan(W, M, n, B):
+    """The baby-step / giant-step form of diag_matvec_plan: the diagonal d = B j + b is reached as a giant rotation by B j of a product with a baby rotation by b,
+        y = Sum_j rotate_rows( Sum_b rows[j][b] (.) rotate_rows(x, b), B j ),   rows[j][b][i] = W[(i - B j) mod M][(i + b) mod M]
+    (period M over both rows of n/2 slots).  B: a power of two, 1 <= B <= M.  Returns (baby_steps, giant_steps, rows [giant][baby][n] int64): the giant steps B j
+    whose group has a non-zero entry, the baby steps b with a non-zero entry in a kept group, zero rows where a pair is empty.  B = M is diag_matvec_plan."""
+    W = np.asarray(W)
+    _bsgs_args(M, n, B, "bsgs_matvec_plan")
+    if W.ndim != 2 or W.shape[0] > M or W.shape[1] > M:
+        raise ValueError("bsgs_matvec_plan: W must be out x in with out, in <= M")
+    P = np.zeros((M, M), dtype=np.int64)
+    P[:W.shape[0], :W.shape[1]] = W
+    i = np.arange(M)
+    used = np.array([P[i, (i + d) % M].any() for d in range(M)]).reshape(M // B, B)
+    giant = [B * j for j in range(M // B) if used[j].any()]
+    baby = [b for b in range(B) if used[:, b].any()]
+    rows = np.zeros((len(giant), len(baby), n), dtype=np.int64)
+    for a, gs in enumerate(giant):
+        for c, b in enumerate(baby):
+            rows[a, c] = np.tile(P[(i - gs) % M, (i + b) % M], n // M)
+    return baby, giant, rows
+
+
+def bsgs_elements(M, B, n):
+    """the Galois elements (3^s mod 2n) a dense M x M product split at B needs: the baby steps 1 .. B - 1, then the giant steps B, 2 B, .. M - B -- what to hand
+    to gen_galois_keys"""
+    _bsgs_args(M, n, B, "bsgs_elements")
+    return [pow(3, s, 2 * n) for s in range(1, M) if s < B or s % B == 0]
 
 
 def h5_read(path, name):
@@ -1027,6 +1063,19 @@ class Engine:
     def diag_matvec_plan(self, W, M):
         """binding.diag_matvec_plan at this ring: (steps, slot rows [len(steps)][n]) of the non-zero diagonals of W padded to M x M"""
         return diag_matvec_plan(W, M, self.n)
+
+    def bsgs_matvec_plan(self, W, M, B):
+        """binding.bsgs_matvec_plan at this ring: (baby_steps, giant_steps, slot rows [giant][baby][n])"""
+        return bsgs_matvec_plan(W, M, self.n, B)
+
+    def diag_mac_bsgs_work_bytes(self, count, B, G, dbc=16):
+        return self.L.crc_diag_mac_bsgs_work_bytes(self.c, count, B, G, dbc)
+
+    def diag_mac_bsgs(self, d_x, count, gb, gg, d_p_ntt, d_cgk, elts, d_y, d_work, dbc=16, in_form=COEFF, out_form=COEFF):
+        """d_y [count] = Sum_j H_{gg[j]}( Sum_b P[j][b] (*) H_{gb[b]}(d_x) ); d_p_ntt [G][B][k][n]: NTT-form plaintext rows (plain_to_ntt); B + G key switches"""
+        elts = self._elts(elts); gb = self._elts(gb); gg = self._elts(gg)
+        _chk(self.L.crc_diag_mac_bsgs_forms(self.c, self.p(d_x), in_form, count, _pu(gb), gb.size, _pu(gg), gg.size, self.p(d_p_ntt), self.p(d_cgk), _pu(elts),
+                                            elts.size, dbc, self.p(d_y), out_form, self.p(d_work), self.stream), "crc_diag_mac_bsgs_forms")
 
     # ---- ciphertext x ciphertext multiply and the degree-3 activation c3 x^3 + c2 x^2 + c1 x + c0 (crc_multiply* / crc_poly3_relin_forms)
     def multiply_relin_work_bytes(self, count, dbc=16):

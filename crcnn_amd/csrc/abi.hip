@@ -1299,13 +1299,14 @@ extern "C" int crc_sum_slots_forms(crc_ctx *c, const uint64_t *d_x, int in_form,
 // NTT-domain gather.  Where the fp64 key switch does not apply, k_relinearize runs per element with the conjugated key: the same exact function on Z_q.
 // Work: [coefficient copy of an NTT-form pass][size-3 rows (c0, 0, c1 (q/q_i)^-1)][zc key-switch results of a pass][nk prepared keys, made by pass 0][scratch of
 // the key switch].  A pass is square_chunk ciphertexts, fewer once more than 8 results are kept at once: it shrinks with R.
-struct HoistWork { u64 *xc, *x3, *z, *kp, *rest; size_t step, kpw; };
+struct HoistWork { u64 *xc, *x3, *z, *kp, *rest, *u; size_t step, kpw; };
 enum { HOIST_Z_PASSES = 8 };
-static HoistWork hoist_layout(const crc_ctx *c, size_t count, int nk, int zc, int dbc, WorkArena &a)
+// uc: further ciphertexts a pass keeps besides the zc results (the inner sums of crc_diag_mac_bsgs_forms; none elsewhere), in L.u behind every other region
+static HoistWork hoist_layout(const crc_ctx *c, size_t count, int nk, int zc, int dbc, WorkArena &a, int uc = 0)
 {
     HoistWork L{};
     // (the zc results kept at once may take the room of HOIST_Z_PASSES passes' ciphertexts: up to 8 of them leave the pass whole, 32 make it a quarter)
-    L.step = square_chunk(c) * HOIST_Z_PASSES / (size_t)zc;
+    L.step = square_chunk(c) * HOIST_Z_PASSES / ((size_t)zc + (size_t)uc);
     if (L.step > square_chunk(c)) L.step = square_chunk(c);
     if (L.step < 1) L.step = 1;
     const size_t ch = count < L.step ? count : L.step;
@@ -1316,6 +1317,7 @@ static HoistWork hoist_layout(const crc_ctx *c, size_t count, int nk, int zc, in
     L.kp = a.take<u64>((size_t)nk * L.kpw);
     const size_t one = k_relin_work_words(c, ch, dbc), two = k_relin64_supported(c, dbc) ? k_relin64_work_words_multi(c, ch, dbc, 2) : 0;
     L.rest = a.take<u64>(one > two ? one : two);                        // (either setting of hoist_rt: a tuning switch does not change the size)
+    if (uc) L.u = a.take<u64>((size_t)uc * ch * crc_ct_words(c, 2));
     return L;
 }
 // keys per digit load in K2: HOIST_RT_DEFAULT unless the tuning key "hoist_rt" says otherwise (profiles/galois_hoisted.md has both measured)
@@ -1478,6 +1480,87 @@ extern "C" int crc_diag_mac_forms(crc_ctx *c, const uint64_t *d_x, int in_form, 
             if (held >= 0) RUN(hoist_switch(c, L, ch, r0 + held, at[r0 + held], d_cgk, dbc, f64, o == 0, L.z + (size_t)held * ch * ctw, stream));
             RUN(k_galois_diag_mac(c, z, p, gs + r0, rn, ch, r0 != 0, d_y + o * ctw, S(stream)));
         }
+    }
+    if (out_form == CRC_COEFF) RUN(crc_ntt_inv(c, d_y, count, 2, stream));
+    return CRC_OK;
+}
+// ---- baby-step / giant-step: y = Sum_j H_{gg[j]}( Sum_b P[j][b] (*) H_{gb[b]}(x) ) ----
+// The baby stage is crc_diag_mac_forms' with G plaintext rows per element: one digit decomposition of x, the B key-switch results Z_b kept (GALOIS_DIAG_MAX at a time),
+// galois_diag_mac_multi_kernel into the G inner sums u_j.  The giant stage takes each u_j with gg[j] != 1 through the hoisted key switch on its own digits -- inverse
+// transform, (c0, 0, c1 (q/q_i)^-1), K1, K2 + K3 under K'_{gg[j]} -- and writes the result over u_j, which nothing reads any more; galois_sum_permuted_kernel then
+// gathers and sums all G (gg[j] = 1: u_j itself).  Every step is an exact function on Z_q with canonical residues, so the bits are those of crc_diag_mac_forms per j,
+// crc_rotate_hoisted_forms per j, crc_add.  Work: hoist_layout with B + G prepared keys, min(B, GALOIS_DIAG_MAX) results and the G inner sums kept per pass.
+// the inner sums: BSGS_JT_DEFAULT unless the tuning key "bsgs_jt" says otherwise (profiles/matvec_bsgs.md has both measured).  The same exact function either way
+enum { BSGS_JT_DEFAULT = 2 };
+static int bsgs_jt(const crc_ctx *c) { return c->tune.bsgs_jt ? c->tune.bsgs_jt : (int)BSGS_JT_DEFAULT; }
+static bool bsgs_counts_ok(int B, int G) { return B >= 1 && G >= 1 && B <= GALOIS_BSGS_MAX && G <= GALOIS_BSGS_MAX; }
+static size_t bsgs_bytes(const crc_ctx *c, size_t count, int B, int G, int dbc)
+{
+    if (!c || !dbc_ok(dbc) || !bsgs_counts_ok(B, G)) return 0;
+    WorkArena a;
+    hoist_layout(c, count, B + G, diag_zc(B), dbc, a, G);
+    return a.bytes();
+}
+extern "C" size_t crc_diag_mac_bsgs_work_bytes(const crc_ctx *c, size_t count, int B, int G, int dbc) { return bsgs_bytes(c, count, B, G, dbc); }
+extern "C" int crc_diag_mac_bsgs_forms(crc_ctx *c, const uint64_t *d_x, int in_form, size_t count, const uint64_t *gb, int B, const uint64_t *gg, int G,
+                                       const uint64_t *d_p_ntt, const uint64_t *d_cgk, const uint64_t *elts, int n_elts, int dbc, uint64_t *d_y, int out_form,
+                                       void *d_work, void *stream)
+{
+    CHECK_CTX(c);
+    if (!bsgs_counts_ok(B, G) || !gg || !d_p_ntt || !aligned16(d_p_ntt)) return CRC_ERR_INVALID_ARGUMENT;
+    const size_t wb = bsgs_bytes(c, count, B, G, dbc), ctw = crc_ct_words(c, 2), rowp = (size_t)c->k * c->n, pb = 8 * (size_t)G * B * rowp;
+    if (!hoist_args_ok(c, d_x, in_form, count, gb, B, d_cgk, elts, n_elts, dbc, d_y, count, out_form, d_work, wb)) return CRC_ERR_INVALID_ARGUMENT;
+    if (ranges_overlap(d_p_ntt, pb, d_y, 8 * count * ctw) || ranges_overlap(d_p_ntt, pb, d_work, wb)) return CRC_ERR_INVALID_ARGUMENT;
+    std::vector<int> at((size_t)B + G);                                 // the key of every baby element, then of every giant element
+    if (!hoist_keys(c, gb, B, elts, n_elts, at.data()) || !hoist_keys(c, gg, G, elts, n_elts, at.data() + B)) return CRC_ERR_INVALID_ARGUMENT;
+    if (count == 0) return CRC_OK;
+    const size_t kw = crc_evk_words(c, dbc);
+    const int zc = diag_zc(B);
+    WorkArena a(d_work);
+    const HoistWork L = hoist_layout(c, count, B + G, zc, dbc, a, G);
+    const bool f64 = c->tune.relin_path != 1 && k_relin64_supported(c, dbc), pair = f64 && hoist_rt(c) == 2;
+    const bool flat = G == 1 && gg[0] == 1;                             // one inner sum that is the result: crc_diag_mac_forms
+    std::vector<const u64 *> zs((size_t)G);
+    bool baby_keyed = false;                                            // (no digits of x where every baby element is 1)
+    for (int b = 0; b < B; b++) baby_keyed = baby_keyed || at[b] >= 0;
+    for (size_t o = 0; o < count; o += L.step) {
+        const size_t ch = pass_len(count, o, L.step), uj = ch * ctw;
+        const u64 *xin = d_x + o * ctw;
+        u64 *u = flat ? d_y + o * ctw : L.u;
+        if (o == 0 && f64)                                              // (the giant keys, like the baby keys in hoist_pass_head: before E is put into the scratch)
+            for (int j = 0; j < G; j++)
+                if (at[B + j] >= 0) RUN(k_relin64_prepare_keys(c, d_cgk + (size_t)at[B + j] * kw, dbc, L.kp + (size_t)(B + j) * L.kpw, L.rest, S(stream)));
+        if (baby_keyed) RUN(hoist_pass_head(c, L, xin, in_form, ch, at.data(), B, d_cgk, dbc, f64, o == 0, stream));
+        for (int r0 = 0; r0 < B; r0 += zc) {
+            const int rn = B - r0 < zc ? B - r0 : zc;
+            const u64 *z[GALOIS_DIAG_MAX], *p[GALOIS_DIAG_MAX];
+            int held = -1;                                              // a keyed element that waits for a partner (two keys per digit load)
+            for (int i = 0; i < rn; i++) {
+                const int r = r0 + i;
+                u64 *zi = L.z + (size_t)i * uj;
+                z[i] = zi;
+                if (at[r] >= 0 && pair && held < 0) held = i;
+                else if (at[r] >= 0 && pair) { RUN(hoist_switch2(c, L, ch, r0 + held, r, dbc, L.z + (size_t)held * uj, zi, stream)); held = -1; }
+                else if (at[r] >= 0) RUN(hoist_switch(c, L, ch, r, at[r], d_cgk, dbc, f64, o == 0, zi, stream));
+                else if (in_form == CRC_NTT) z[i] = xin;               // g = 1: x itself, in NTT form
+                else RUN(ntt_copy(c, xin, ch, zi, stream));
+            }
+            if (held >= 0) RUN(hoist_switch(c, L, ch, r0 + held, at[r0 + held], d_cgk, dbc, f64, o == 0, L.z + (size_t)held * uj, stream));
+            if (bsgs_jt(c) == 2) { RUN(k_galois_diag_mac_multi(c, z, gb + r0, r0, rn, B, d_p_ntt, G, ch, r0 != 0, u, S(stream))); continue; }
+            for (int j = 0; j < G; j++) {
+                for (int i = 0; i < rn; i++) p[i] = d_p_ntt + ((size_t)j * B + r0 + i) * rowp;
+                RUN(k_galois_diag_mac(c, z, p, gb + r0, rn, ch, r0 != 0, u + (size_t)j * uj, S(stream)));
+            }
+        }
+        if (flat) continue;
+        for (int j = 0; j < G; j++) {
+            u64 *ug = L.u + (size_t)j * uj;
+            zs[j] = ug;
+            if (at[B + j] < 0) continue;
+            RUN(hoist_pass_head(c, L, ug, CRC_NTT, ch, nullptr, 0, d_cgk, dbc, f64, false, stream));
+            RUN(hoist_switch(c, L, ch, B + j, at[B + j], d_cgk, dbc, f64, o == 0, ug, stream));
+        }
+        RUN(k_galois_sum_permuted(c, zs.data(), gg, G, ch, false, d_y + o * ctw, S(stream)));
     }
     if (out_form == CRC_COEFF) RUN(crc_ntt_inv(c, d_y, count, 2, stream));
     return CRC_OK;

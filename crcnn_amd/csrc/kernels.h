@@ -75,6 +75,13 @@ int k_galois_permute_ntt(crc_ctx *c, const u64 *in, size_t rows, u64 g, u64 *out
 // y [cnt][2][k][n] (+)= Sum_r p[r] (*) sigma_{g[r]}(z[r]) on NTT-form ciphertexts z[r] [cnt][2][k][n] and plaintext rows p[r] [k][n]; R <= GALOIS_DIAG_MAX
 enum { GALOIS_DIAG_MAX = 32 };
 int k_galois_diag_mac(crc_ctx *c, const u64 *const *z, const u64 *const *p, const u64 *g, int R, size_t cnt, bool accumulate, u64 *y, hipStream_t st);
+// baby-step / giant-step: u [G][cnt][2][k][n] (+)= Sum_{r < R} P[j][b0 + r] (*) sigma_{g[r]}(z[r]) for every j < G, P [G][B][k][n]; GALOIS_MULTI_JT giant indices share one
+// gather of the z[r] (galois_diag_mac_multi_kernel); R <= GALOIS_DIAG_MAX, G <= GALOIS_BSGS_MAX
+enum { GALOIS_MULTI_JT = 4, GALOIS_BSGS_MAX = 1 << 16 };
+int k_galois_diag_mac_multi(crc_ctx *c, const u64 *const *z, const u64 *g, int b0, int R, int B, const u64 *p, int G, size_t cnt, bool accumulate, u64 *u,
+                            hipStream_t st);
+// y [cnt][2][k][n] (+)= Sum_r sigma_{g[r]}(z[r]) on NTT-form ciphertexts, any R (GALOIS_DIAG_MAX per launch); y disjoint from every z[r]
+int k_galois_sum_permuted(crc_ctx *c, const u64 *const *z, const u64 *g, int R, size_t cnt, bool accumulate, u64 *y, hipStream_t st);
 int k_mac2(crc_ctx *c, const u64 *x, const u64 *w, u64 *y, const int *d_xoff, const int *d_toff, int B, const LayerShape &s, const u64 *bias_ntt,
            const unsigned *d_toffw, hipStream_t st, int xp = 0, int wp = 0, int yp = 0);
 int k_fold_pool(crc_ctx *c, const u64 *w, const u64 *bias, const u64 *div, u64 *wout, u64 *bout, int nf, int zd, int xf, int yf, int cxs, int cys,

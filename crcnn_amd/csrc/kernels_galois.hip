@@ -147,3 +147,106 @@ int k_galois_diag_mac(crc_ctx *c, const u64 *const *z, const u64 *const *p, cons
     }
     return CRC_OK;
 }
+
+// ---- baby-step / giant-step: G inner sums over the same B rotated inputs, and the sum of the G rotated results ----
+// u_j[s] = Sum_b P[j][b][s] Z_b[pi_b(s)] mod q for GALOIS_MULTI_JT giant indices j per thread: Z_b[pi_b(s)] is gathered once and multiplied into JT pairs of 128-bit
+// accumulators, so the B rotated inputs are read ceil(G / JT) times instead of G times.  One barrett128 per output, the bound and the accumulate continuation of
+// galois_diag_mac_kernel.  p: &P[0][b0] of P [G][Bt][k][n] (pj = Bt k n words from one giant index to the next), u [G][cnt][2][k][n] (uj = cnt 2 k n words).
+// grid: (cnt 2 k max(1, n / 512), ceil(G / JT)); a last tile with fewer than JT outputs computes its missing ones on the last giant index and does not store them
+struct GaloisMultiArgs { const u64 *z[GALOIS_DIAG_MAX]; u32 g[GALOIS_DIAG_MAX]; };
+template <int JT>
+__global__ void __launch_bounds__(256, 8) galois_diag_mac_multi_kernel(GaloisMultiArgs a, int R, const u64 *p, size_t pj, int G, u64 *u, size_t uj, const ModParams *mods,
+                                                                    int n, int logn, int k, int blocks_per_row, int accumulate)
+{
+    const size_t row = blockIdx.x / (u32)blocks_per_row; const u32 part = blockIdx.x - (u32)row * (u32)blocks_per_row;      // row = (ct 2 + poly) k + i
+    const u32 s = (part * 256u + threadIdx.x) * 2u;
+    if (s >= (u32)n) return;
+    const int i = (int)(row % (size_t)k);
+    const ModParams m = mods[i];
+    const u32 m2 = 2u * (u32)n - 1u; const int sh = 32 - logn;
+    const int j0 = (int)blockIdx.y * JT;
+    unsigned __int128 acc0[JT], acc1[JT];
+    size_t po[JT];                                                         // (uniform: the tile's giant rows of P from the thread's own pointer)
+    u64 *uo = u + (size_t)j0 * uj + row * (size_t)n + s;
+#pragma unroll
+    for (int t = 0; t < JT; t++) {
+        po[t] = (size_t)(j0 + t < G ? t : G - 1 - j0) * pj;
+        acc0[t] = 0; acc1[t] = 0;
+        if (accumulate && j0 + t < G) { const ulonglong2 v = ld2(uo + (size_t)t * uj); acc0[t] = v.x; acc1[t] = v.y; }
+    }
+    const u64 *pr = p + (size_t)j0 * pj + (size_t)i * n + s;
+    for (int r = 0; r < R; r++, pr += (size_t)k * n) {                      // (k n words from one baby row of P to the next)
+        const u64 *zr = a.z[r] + row * (size_t)n;
+        const u32 g = a.g[r];
+        const u64 za = zr[galois_ntt_src(s, g, m2, sh)], zb = zr[galois_ntt_src(s + 1u, g, m2, sh)];
+#pragma unroll
+        for (int t = 0; t < JT; t++) {
+            const ulonglong2 w = ld2(pr + po[t]);
+            u64 lo, hi;
+            mul64wide(w.x, za, lo, hi); acc0[t] += ((unsigned __int128)hi << 64) | lo;
+            mul64wide(w.y, zb, lo, hi); acc1[t] += ((unsigned __int128)hi << 64) | lo;
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < JT; t++)
+        if (j0 + t < G) st2(uo + (size_t)t * uj, barrett128((u64)acc0[t], (u64)(acc0[t] >> 64), m), barrett128((u64)acc1[t], (u64)(acc1[t] >> 64), m));
+}
+// z: the B key-switch results of the pass, g their elements; p = P [G][B][k][n]; u [G][cnt] (+)= the G inner sums
+int k_galois_diag_mac_multi(crc_ctx *c, const u64 *const *z, const u64 *g, int b0, int R, int B, const u64 *p, int G, size_t cnt, bool accumulate, u64 *u,
+                            hipStream_t st)
+{
+    if (cnt == 0 || R < 1 || G < 1) return CRC_OK;
+    if (R > GALOIS_DIAG_MAX || G > GALOIS_BSGS_MAX) return CRC_ERR_INVALID_ARGUMENT;
+    const int bpr = c->n > 512 ? c->n / 512 : 1;
+    const size_t blocks = cnt * 2 * (size_t)c->k * bpr, rowp = (size_t)c->k * c->n;
+    if (blocks > 0x7fffffffull) return CRC_ERR_INVALID_ARGUMENT;
+    const dim3 grid((unsigned)blocks, (unsigned)((G + GALOIS_MULTI_JT - 1) / GALOIS_MULTI_JT));
+    for (int r0 = 0, per = diag_group(c); r0 < R; r0 += per) {
+        GaloisMultiArgs a{};
+        const int rn = R - r0 < per ? R - r0 : per;
+        for (int r = 0; r < rn; r++) { a.z[r] = z[r0 + r]; a.g[r] = (u32)g[r0 + r]; }
+        hipLaunchKernelGGL(galois_diag_mac_multi_kernel<GALOIS_MULTI_JT>, grid, dim3(256), 0, st, a, rn, p + (size_t)(b0 + r0) * rowp, (size_t)B * rowp, G, u,
+                           cnt * 2 * rowp, c->d_mods, c->n, c->logn, c->k, bpr, accumulate || r0 ? 1 : 0);
+        HIPCHK(hipGetLastError());
+    }
+    return CRC_OK;
+}
+
+// y[s] (+)= Sum_j Z_j[pi_{g_j}(s)] mod q: the gather of galois_permute_ntt_kernel summed over up to GALOIS_DIAG_MAX NTT-form ciphertexts (g_j = 1: Z_j itself), so the
+// rotated ciphertexts are never written.  Canonical operands, one conditional subtraction per term: the canonical residue of the sum
+struct GaloisSumArgs { const u64 *z[GALOIS_DIAG_MAX]; u32 g[GALOIS_DIAG_MAX]; };
+__global__ void __launch_bounds__(256) galois_sum_permuted_kernel(GaloisSumArgs a, int R, u64 *y, const ModParams *mods, int n, int logn, int k, int blocks_per_row,
+                                                                  int accumulate)
+{
+    const size_t row = blockIdx.x / (u32)blocks_per_row; const u32 part = blockIdx.x - (u32)row * (u32)blocks_per_row;
+    const u32 s = (part * 256u + threadIdx.x) * 2u;
+    if (s >= (u32)n) return;
+    const u64 q = mods[(int)(row % (size_t)k)].q;
+    const u32 m2 = 2u * (u32)n - 1u; const int sh = 32 - logn;
+    u64 *yo = y + row * (size_t)n + s;
+    ulonglong2 acc{0, 0};
+    if (accumulate) acc = ld2(yo);
+    for (int r = 0; r < R; r++) {
+        const u64 *zr = a.z[r] + row * (size_t)n;
+        const u32 g = a.g[r];
+        acc.x = addmod(acc.x, zr[galois_ntt_src(s, g, m2, sh)], q);
+        acc.y = addmod(acc.y, zr[galois_ntt_src(s + 1u, g, m2, sh)], q);
+    }
+    st2(yo, acc.x, acc.y);
+}
+int k_galois_sum_permuted(crc_ctx *c, const u64 *const *z, const u64 *g, int R, size_t cnt, bool accumulate, u64 *y, hipStream_t st)
+{
+    if (cnt == 0 || R < 1) return CRC_OK;
+    const int bpr = c->n > 512 ? c->n / 512 : 1;
+    const size_t blocks = cnt * 2 * (size_t)c->k * bpr;
+    if (blocks > 0x7fffffffull) return CRC_ERR_INVALID_ARGUMENT;
+    for (int r0 = 0; r0 < R; r0 += GALOIS_DIAG_MAX) {
+        GaloisSumArgs a{};
+        const int rn = R - r0 < GALOIS_DIAG_MAX ? R - r0 : (int)GALOIS_DIAG_MAX;
+        for (int r = 0; r < rn; r++) { a.z[r] = z[r0 + r]; a.g[r] = (u32)g[r0 + r]; }
+        hipLaunchKernelGGL(galois_sum_permuted_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, rn, y, c->d_mods, c->n, c->logn, c->k, bpr,
+                           accumulate || r0 ? 1 : 0);
+        HIPCHK(hipGetLastError());
+    }
+    return CRC_OK;
+}

@@ -753,6 +753,45 @@ ciphertext3D matvecSlots(const ciphertext3D &t, const vector<vector<int64_t>> &W
     chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");           // (the diagonals' buffers go out of scope here)
     return out;
 }
+// baby-step / giant-step: the same product with B + M/B rotations instead of M (crc_diag_mac_bsgs_forms).  The default split is the power of two B >= M/B nearest
+// the square root: the fewest keys, and the fastest of sqrt(M) / 2, sqrt(M), 2 sqrt(M) at every shape of profiles/matvec_bsgs.md
+void bsgsMatvecPlan(const vector<vector<int64_t>> &W, int M, int n, int B, vector<int> &baby_steps, vector<int> &giant_steps, vector<int64_t> &rows)
+{
+    if (!crc_bsgs_plan(W, M, n, B, baby_steps, giant_steps, rows))
+        throw invalid_argument("matvecSlotsBsgs: M must be a power of two <= n/2, B a power of two <= M and W at most M x M");
+}
+int bsgsDefaultSplit(int M)
+{
+    int B = 1;
+    while ((long long)B * B < M) B *= 2;
+    return B;
+}
+ciphertext3D matvecSlotsBsgs(const ciphertext3D &t, const vector<vector<int64_t>> &W, int M, int B, int out_form)
+{
+    if (!crc_slots_supported(ctx())) throw logic_error("encryption parameters do not support batching");
+    const int n = N(), k = crc_ctx_k(ctx());
+    vector<int> baby, giant; vector<int64_t> rows;
+    bsgsMatvecPlan(W, M, n, B ? B : bsgsDefaultSplit(M), baby, giant, rows);
+    const vector<uint64_t> gb = hoistedElements("matvecSlotsBsgs", t, baby, out_form), gg = hoistedElements("matvecSlotsBsgs", t, giant, out_form);
+    ciphertext3D out(t.B, t.zd, t.xd, t.yd, out_form);
+    const size_t cnt = t.count(), ctb = crc_ct_words(ctx(), 2) * 8;
+    if (gg.empty()) {                                                   // W = 0: the transparent zero ciphertext, as the sum of no terms
+        chk(crc_memset(ctx(), out.data(), 0, cnt * ctb, stream()), "crc_memset");
+        return out;
+    }
+    const int nb = (int)gb.size(), ng = (int)gg.size(), R = nb * ng, dbc = g_galois_dbc ? g_galois_dbc : 16;
+    vector<uint64_t> plain((size_t)R * n);
+    chk(crc_slots_compose(ctx(), rows.data(), R, n, n, 1, plain.data()), "crc_slots_compose");
+    DeviceBuffer d_plain(plain.size() * 8), d_p((size_t)R * k * n * 8);
+    chk(crc_memcpy_h2d(ctx(), d_plain.ptr, plain.data(), plain.size() * 8, stream()), "crc_memcpy_h2d");
+    chk(crc_plain_to_ntt(ctx(), (const uint64_t *)d_plain.ptr, R, (uint64_t *)d_p.ptr, stream()), "crc_plain_to_ntt");
+    ensure(g_scratch, crc_diag_mac_bsgs_work_bytes(ctx(), cnt, nb, ng, dbc));
+    chk(crc_diag_mac_bsgs_forms(ctx(), t.data(), t.form, cnt, gb.data(), nb, gg.data(), ng, (const uint64_t *)d_p.ptr,
+                                g_galois_ckeys ? (const uint64_t *)g_galois_ckeys->ptr : nullptr, galois_elts.data(), (int)galois_elts.size(), dbc, out.data(),
+                                out_form, g_scratch->ptr, stream()), "matvecSlotsBsgs");
+    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");           // (the rows' buffers go out of scope here)
+    return out;
+}
 vector<floatCube> decryptImages(const ciphertext3D &t)
 {
     const int n = N();

@@ -186,6 +186,16 @@ std::vector<ciphertext3D> rotateRowsMany(const ciphertext3D &t, const std::vecto
 ciphertext3D matvecSlots(const ciphertext3D &t, const std::vector<std::vector<int64_t>> &W, int M, int out_form = CRC_COEFF);
 // the plan matvecSlots follows: the steps of W's non-zero diagonals and their slot rows [steps][n], rows[r][i] = W[i mod M][(i mod M + steps[r]) mod M]
 void diagMatvecPlan(const std::vector<std::vector<int64_t>> &W, int M, int n, std::vector<int> &steps, std::vector<int64_t> &rows);
+// The same product by baby steps and giant steps (include/crcnn_hip.h: crc_diag_mac_bsgs_forms): the diagonal d = B j + b is a giant rotation by B j of a product
+// with a baby rotation by b, so a dense W takes B + M/B - 2 key switches and keys where matvecSlots takes M - 1 -- the keys of crc_bsgs_elements(M, B, n)
+// (crcnn_amd/host/diag_plan.h) are what generateGaloisKeys(dbc, elements) must hold.  B: a power of two, 1 <= B <= M; 0: bsgsDefaultSplit(M), the power of two
+// B >= M/B nearest the square root.  Input contract, result, forms and exceptions as matvecSlots (plus a bad B); a ciphertext of its own definition, not
+// matvecSlots' bits, with one more key switch and a sum of M/B terms in its noise.  B = M is matvecSlots' product
+ciphertext3D matvecSlotsBsgs(const ciphertext3D &t, const std::vector<std::vector<int64_t>> &W, int M, int B = 0, int out_form = CRC_COEFF);
+int bsgsDefaultSplit(int M);
+// the plan it follows (crc_bsgs_plan): rows [giant][baby][n], rows[j][b][i] = W[(i - giant_steps[j]) mod M][(i + baby_steps[b]) mod M]
+void bsgsMatvecPlan(const std::vector<std::vector<int64_t>> &W, int M, int n, int B, std::vector<int> &baby_steps, std::vector<int> &giant_steps,
+                    std::vector<int64_t> &rows);
 
 // ---- layers (CrCNN/src/layer.h:10-31) ------------------------------------------------------------------------------
 class Layer {

@@ -7,7 +7,16 @@
 // Writes <dir>/<name>.i64 = [n][P] (decrypted and decomposed) for name in many_0, many_1, many_5, many_7 (one rotateRowsMany call), many_5_ntt (NTT form in and
 // out), rows_1 and rows_5 (rotateRows, for the budget comparison), matvec_8x8, matvec_5x8, matvec_8x8_ntt, matvec_zero; prints "budget <name> <min bits>" per
 // result, "throws <case> <exception kind>" for the exceptions and "hoist_host ok" at the end.
+//
+//   hoist_host <dir> bsgs          (tests/test_gpu_bsgs_cpp.py)
+//
+// matvecSlotsBsgs at M = 16: values.i64 tiles a vector of 16 entries with period 16, <dir>/w16.i64 = [16][16] and <dir>/w11.i64 = [11][16].  Keys: those of
+// crc_bsgs_elements(16, 4, n) only.  Per case (bsgs_16x16 at B = 4, bsgs_11x16 at the default split, bsgs_16x16_ntt, bsgs_16x16_B16 = the flat product through
+// the same entry point, on the diagonals 0..3 and 4, 8, 12 that the keys reach) writes <dir>/<name>.i64, prints "budget <name> <min bits>" and
+// "product <name> equal|differs" (every slot against W x mod t computed here), then "keys bsgs <bytes> flat <bytes>" for a dense 16 x 16 product,
+// "throws <case> <kind>" and "hoist_host bsgs ok".
 #include "crcnn_host.h"
+#include "diag_plan.h"
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -42,16 +51,71 @@ static vector<vector<int64_t>> matrix(const string &p, int rows, int cols)
     for (int i = 0; i < rows; i++) for (int j = 0; j < cols; j++) W[i][j] = (int64_t)raw[(size_t)i * cols + j];
     return W;
 }
+// the decrypted slots of y against W x mod t (centred), x read back from the slots of the input: "product <name> equal|differs"
+static void product(const char *name, const ciphertext3D &y, const ciphertext3D &x, const vector<vector<int64_t>> &W, int M, int64_t t)
+{
+    put(name, y);
+    const vector<vector<int64_t>> got = decryptSlots(y, n), in = decryptSlots(x, n);
+    bool equal = true;
+    for (size_t c = 0; c < in[0].size(); c++)
+        for (int i = 0; i < n; i++) {
+            __int128 acc = 0;
+            const int r = i % M;
+            if (r < (int)W.size()) for (int j = 0; j < (int)W[r].size(); j++) acc += (__int128)(W[r][j] % t) * in[j][c];
+            int64_t w = (int64_t)(acc % t);
+            w = (w + t) % t;
+            if (w > (t - 1) / 2) w -= t;
+            equal = equal && got[i][c] == w;
+        }
+    printf("product %s %s\n", name, equal ? "equal" : "differs");
+}
+static int bsgs_case(const vector<uint64_t> &p, const vector<uint64_t> &q)
+{
+    const int M = 16, B = 4;
+    const int64_t t = (int64_t)p[2];
+    vector<vector<int64_t>> W16 = matrix(dir + "/w16.i64", 16, 16), W11 = matrix(dir + "/w11.i64", 11, 16);
+    setParameters(n, q, (uint64_t)1 << 20, 0);
+    { ciphertext3D none(1, 1, 1, 1); thrown("no_batching_bsgs", [&] { matvecSlotsBsgs(none, W16, M); }); }
+    setParameters(n, q, p[2], 0);
+    setSlotEncoding(0, 0);
+    const auto raw = rd(dir + "/values.i64");
+    const size_t P = raw.size() / n;
+    vector<vector<int64_t>> images(n, vector<int64_t>(P));
+    for (int j = 0; j < n; j++) for (size_t c = 0; c < P; c++) images[j][c] = (int64_t)raw[(size_t)j * P + c];
+    const ciphertext3D x = encryptImageSlots(images, 1, 1, (int)P);
+    thrown("no_keys_bsgs", [&] { matvecSlotsBsgs(x, W16, M); });
+    const vector<uint64_t> elts = crc_bsgs_elements(M, B, n);
+    generateGaloisKeys(16, elts);
+    product("bsgs_16x16", matvecSlotsBsgs(x, W16, M, B), x, W16, M, t);
+    product("bsgs_11x16", matvecSlotsBsgs(x, W11, M), x, W11, M, t);
+    { ciphertext3D xn = rotateRowsMany(x, {0}, CRC_NTT)[0]; product("bsgs_16x16_ntt", matvecSlotsBsgs(xn, W16, M, B, CRC_NTT), x, W16, M, t); }
+    vector<vector<int64_t>> Wd = W16;                                   // only the diagonals whose own keys are in the set
+    for (int i = 0; i < M; i++) for (int j = 0; j < M; j++) { const int d = (j - i + M) % M; if (d >= B && d % B) Wd[i][j] = 0; }
+    product("bsgs_16x16_B16", matvecSlotsBsgs(x, Wd, M, M), x, Wd, M, t);
+    product("bsgs_zero", matvecSlotsBsgs(x, vector<vector<int64_t>>(16, vector<int64_t>(16, 0)), M), x, {}, M, t);
+    const size_t kb = crc_evk_words(context, 16) * 8;
+    printf("keys bsgs %zu flat %zu\n", elts.size() * kb, (size_t)(M - 1) * kb);
+    thrown("bad_B", [&] { matvecSlotsBsgs(x, W16, M, 3); });
+    thrown("B_too_large", [&] { matvecSlotsBsgs(x, W16, M, 32); });
+    thrown("bad_M_bsgs", [&] { matvecSlotsBsgs(x, W16, 6); });
+    thrown("missing_key_bsgs", [&] { matvecSlotsBsgs(x, W16, M, 8); });             // B = 8: the baby steps 5, 6, 7 have no key
+    thrown("bad_form_bsgs", [&] { matvecSlotsBsgs(x, W16, M, B, CRC_NTTP); });
+    delParameters();
+    clearDeterministicSeed();
+    printf("hoist_host bsgs ok\n");
+    return 0;
+}
 
 int main(int argc, char **argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: hoist_host <dir>\n"); return 1; }
+    if (argc < 2) { fprintf(stderr, "usage: hoist_host <dir> [bsgs]\n"); return 1; }
     try {
         dir = argv[1];
         setDeterministicSeed(20241019);
         const auto p = rd(dir + "/params.u64");
         n = (int)p[0]; const int k = (int)p[1];
         const vector<uint64_t> q(p.begin() + 3, p.begin() + 3 + k);
+        if (argc > 2 && string(argv[2]) == "bsgs") return bsgs_case(p, q);
         const vector<vector<int64_t>> W8 = matrix(dir + "/w8.i64", 8, 8), W5 = matrix(dir + "/w5.i64", 5, 8);
         // a plain modulus without slots: the reference's logic_error, before any key is looked at
         setParameters(n, q, (uint64_t)1 << 20, 0);

@@ -670,8 +670,15 @@ int crc_sum_slots_forms(crc_ctx *ctx, const uint64_t *d_x, int in_form, size_t c
  *                               written (the gather is folded into the product).  With the slots of one image tiled with period M over both rows and the
  *                               diagonals of an M x M matrix as P_r, gs[r] = crc_galois_elt_rows(d_r), this is the matrix-vector product over slots.
  *                               d_work: crc_diag_mac_work_bytes(ctx, count, R, dbc)
- * Refusals as in the paragraph above (null / misaligned / overlapping operands, forms, dbc, an invalid element), plus R < 1 and a missing conjugated key:
- * CRC_ERR_INVALID_ARGUMENT, nothing launched.  count = 0 is CRC_OK.
+ *   crc_diag_mac_bsgs_forms     baby-step / giant-step: d_y [count] = Sum_j H_{gg[j]}( Sum_b P[j][b] (*) H_{gb[b]}(d_x) ) with NTT-form plaintext rows d_p_ntt
+ *                               [G][B][k][n].  Bit for bit: crc_diag_mac_forms(d_x, gb, B, P[j]) into NTT form for every j, crc_rotate_hoisted_forms of each result
+ *                               by {gg[j]} into NTT form, crc_add over j, one inverse transform for CRC_COEFF -- but neither a rotated input nor a rotated inner
+ *                               sum is ever written.  B + G key switches and conjugated keys (fewer where an element is 1) where the flat product of the same
+ *                               B G terms takes B G.  With gb[b] = crc_galois_elt_rows(b), gg[j] = crc_galois_elt_rows(B j) and the rows of crc_bsgs_plan
+ *                               (crcnn_amd/host/diag_plan.h) this is the M x M matrix-vector product over slots, M = B G.  G = 1 with gg = {1} is
+ *                               crc_diag_mac_forms.  d_work: crc_diag_mac_bsgs_work_bytes(ctx, count, B, G, dbc); B, G <= 65536
+ * Refusals as in the paragraph above (null / misaligned / overlapping operands, forms, dbc, an invalid element), plus R < 1 (B < 1, G < 1) and a missing
+ * conjugated key: CRC_ERR_INVALID_ARGUMENT, nothing launched.  count = 0 is CRC_OK.
  * ------------------------------------------------------------------------------------------------------------- */
 int crc_galois_ntt_table(const crc_ctx *ctx, uint64_t g, uint32_t *table /*[n]*/);
 int crc_galois_conjugate_keys(const crc_ctx *ctx, const uint64_t *elts, int n_elts, int dbc, const uint64_t *h_gk, uint64_t *h_out);
@@ -683,6 +690,10 @@ int crc_rotate_hoisted_forms(crc_ctx *ctx, const uint64_t *d_x, int in_form, siz
 size_t crc_diag_mac_work_bytes(const crc_ctx *ctx, size_t count, int R, int dbc);
 int crc_diag_mac_forms(crc_ctx *ctx, const uint64_t *d_x, int in_form, size_t count, const uint64_t *gs /*[R], host*/, int R, const uint64_t *d_p_ntt /*[R][k][n]*/,
                        const uint64_t *d_cgk, const uint64_t *elts, int n_elts, int dbc, uint64_t *d_y /*[count]*/, int out_form, void *d_work, void *stream);
+size_t crc_diag_mac_bsgs_work_bytes(const crc_ctx *ctx, size_t count, int B, int G, int dbc);
+int crc_diag_mac_bsgs_forms(crc_ctx *ctx, const uint64_t *d_x, int in_form, size_t count, const uint64_t *gb /*[B], host*/, int B, const uint64_t *gg /*[G], host*/,
+                            int G, const uint64_t *d_p_ntt /*[G][B][k][n]*/, const uint64_t *d_cgk, const uint64_t *elts, int n_elts, int dbc,
+                            uint64_t *d_y /*[count]*/, int out_form, void *d_work, void *stream);
 /* FractionalEncoder::decode / encode (encoder.cpp:1226-1270, 1013-1076; 64 integer + 32 fractional coefficients, base 3: CrCNN/src/globals.cpp:52) on the
  * device: the doubles crc_decode returns for d_plain [count][n], and the dense plaintexts [count][n] crc_encode_f32 / _f64 make of the values -- the same IEEE
  * operations in the same order as the host encoder, contraction off. */
