@@ -269,6 +269,9 @@ def load():
     L.crc_diag_mac_forms.argtypes = [VP, VP, CI, SZ, PU, CI, VP, VP, PU, CI, CI, VP, CI, VP, VP]
     L.crc_diag_mac_bsgs_work_bytes.restype = SZ; L.crc_diag_mac_bsgs_work_bytes.argtypes = [VP, SZ, CI, CI, CI]
     L.crc_diag_mac_bsgs_forms.argtypes = [VP, VP, CI, SZ, PU, CI, PU, CI, VP, VP, PU, CI, CI, VP, CI, VP, VP]
+    L.crc_conv_slots_pack_weights.argtypes = [VP, ctypes.POINTER(ctypes.c_int64), SZ, PU]
+    L.crc_conv_slots_work_bytes.restype = SZ; L.crc_conv_slots_work_bytes.argtypes = [VP, SZ, CI, CI, CI, CI]
+    L.crc_conv_slots_forms.argtypes = [VP, VP, CI, SZ, CI, PU, CI, VP, CI, VP, PU, CI, CI, VP, CI, VP, VP]
     L.crc_noise_budget.argtypes = [VP, PU, PU, CI]
     _lib = L
     return L
@@ -344,6 +347,51 @@ def bsgs_elements(M, B, n):
     to gen_galois_keys"""
     _bsgs_args(M, n, B, "bsgs_elements")
     return [pow(3, s, 2 * n) for s in range(1, M) if s < B or s % B == 0]
+
+
+class ConvSlotsPlan:
+    """What conv_slots_plan returns.  steps [T]: the row rotation of every tap of the (fh + pool - 1) x (fw + pool - 1) window, row-major; elements [T]:
+    3^step mod 2n (crc_galois_elt_rows; the tap (0, 0) is the element 1, which needs no key); out_h, out_w, out_dil: the geometry of the valid outputs, output
+    (y, x) at slot out_dil (y pitch + x) of every period M; valid: those slots of the first period, row-major.  fold(w, t): the weights the taps take"""
+    def __init__(self, n, M, pitch, fh, fw, pool, steps, out_h, out_w, out_dil):
+        self.n, self.M, self.pitch, self.fh, self.fw, self.pool = n, M, pitch, fh, fw, pool
+        self.steps = steps
+        self.elements = [pow(3, s, 2 * n) for s in steps]
+        self.out_h, self.out_w, self.out_dil = out_h, out_w, out_dil
+        self.valid = [out_dil * (y * pitch + x) for y in range(out_h) for x in range(out_w)]
+
+    def fold(self, w, t):
+        """[Cout][Cin][fh][fw] integers -> [Cout][Cin][T] in [0, t): w'[a][b] = Sum_{u, v < pool} w[a - u][b - v] mod t, the pool's window sum folded into the taps"""
+        w = np.asarray(w)
+        if w.ndim != 4 or w.shape[2:] != (self.fh, self.fw):
+            raise ValueError("ConvSlotsPlan.fold: weights must be [Cout][Cin][fh][fw]")
+        p, t = self.pool, int(t)
+        out = np.zeros(w.shape[:2] + (self.fh + p - 1, self.fw + p - 1), dtype=object)
+        wm = w.astype(object) % t
+        for u in range(p):
+            for v in range(p):
+                out[:, :, u:u + self.fh, v:v + self.fw] += wm
+        return (out % t).astype(np.int64).reshape(w.shape[0], w.shape[1], -1)
+
+
+def conv_slots_plan(n, M, pitch, H, W, fh, fw, dil=1, pool=1):
+    """A 'valid' convolution (stride 1 on the dilated grid, then a pool x pool sum pool of stride pool) of ONE image whose channel planes each fill a ciphertext:
+    pixel (y, x) of an H x W plane at slot dil (y pitch + x), tiled with period M over both rows of n/2 slots (matvecSlots' input contract; M a power of two
+    <= n/2 that the plane fits in).  Tap (a, b) is the row rotation by dil (a pitch + b), so output (y, x) lands where input (y, x) was -- with a pool, where input
+    (pool y, pool x) was: dilation dil pool, the same pitch.  Slots outside `valid` hold junk that the next layer never reads: no masks, no zero padding.
+    Raises ValueError for a plane that does not fit, a step >= n/2, M not a power of two, or a window larger than the plane"""
+    n, M, pitch, H, W, fh, fw, dil, pool = (int(v) for v in (n, M, pitch, H, W, fh, fw, dil, pool))
+    if n < 2 or n & (n - 1) or M < 1 or M & (M - 1) or M > n // 2:
+        raise ValueError("conv_slots_plan: M must be a power of two <= n/2")
+    if min(pitch, H, W, fh, fw, dil, pool) < 1 or W > pitch or fh > H or fw > W or dil * ((H - 1) * pitch + W - 1) >= M:
+        raise ValueError("conv_slots_plan: the plane does not fit (W <= pitch, dil ((H - 1) pitch + W - 1) < M, window <= plane)")
+    out_h, out_w = (H - fh + 1) // pool, (W - fw + 1) // pool
+    if out_h < 1 or out_w < 1:
+        raise ValueError("conv_slots_plan: the pool leaves no output")
+    steps = [dil * (a * pitch + b) for a in range(fh + pool - 1) for b in range(fw + pool - 1)]
+    if steps[-1] >= n // 2:
+        raise ValueError("conv_slots_plan: a tap's step reaches n/2")
+    return ConvSlotsPlan(n, M, pitch, fh, fw, pool, steps, out_h, out_w, dil * pool)
 
 
 def h5_read(path, name):
@@ -1076,6 +1124,27 @@ class Engine:
         elts = self._elts(elts); gb = self._elts(gb); gg = self._elts(gg)
         _chk(self.L.crc_diag_mac_bsgs_forms(self.c, self.p(d_x), in_form, count, _pu(gb), gb.size, _pu(gg), gg.size, self.p(d_p_ntt), self.p(d_cgk), _pu(elts),
                                             elts.size, dbc, self.p(d_y), out_form, self.p(d_work), self.stream), "crc_diag_mac_bsgs_forms")
+
+    # ---- the packed convolution over slots (crc_conv_slots_*): one channel plane per ciphertext, scalar weights, the conjugated key set of the taps' elements
+    def conv_slots_plan(self, M, pitch, H, W, fh, fw, dil=1, pool=1):
+        """binding.conv_slots_plan at this ring"""
+        return conv_slots_plan(self.n, M, pitch, H, W, fh, fw, dil, pool)
+
+    def conv_slots_pack_weights(self, w):
+        """integers of any shape (taken mod t) -> uint64 [k] + shape: the word every position of the constant plaintext's NTT-form row holds, per modulus"""
+        w = np.ascontiguousarray(w, dtype=np.int64)
+        out = np.zeros((self.k,) + w.shape, dtype=np.uint64)
+        _chk(self.L.crc_conv_slots_pack_weights(self.c, w.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), w.size, _pu(out)), "crc_conv_slots_pack_weights")
+        return out
+
+    def conv_slots_work_bytes(self, count, Cin, Cout, T, dbc=16):
+        return self.L.crc_conv_slots_work_bytes(self.c, count, Cin, Cout, T, dbc)
+
+    def conv_slots(self, d_x, count, Cin, gs, d_w, Cout, d_cgk, elts, d_y, d_work, dbc=16, in_form=COEFF, out_form=COEFF):
+        """d_y [Cout][count] = Sum_ci Sum_tau w[.][co][ci][tau] H_{gs[tau]}(d_x[ci]); d_x [Cin][count], d_w [k][Cout][Cin][T]: conv_slots_pack_weights"""
+        elts = self._elts(elts); gs = self._elts(gs)
+        _chk(self.L.crc_conv_slots_forms(self.c, self.p(d_x), in_form, count, Cin, _pu(gs), gs.size, self.p(d_w), Cout, self.p(d_cgk), _pu(elts), elts.size, dbc,
+                                         self.p(d_y), out_form, self.p(d_work), self.stream), "crc_conv_slots_forms")
 
     # ---- ciphertext x ciphertext multiply and the degree-3 activation c3 x^3 + c2 x^2 + c1 x + c0 (crc_multiply* / crc_poly3_relin_forms)
     def multiply_relin_work_bytes(self, count, dbc=16):

@@ -1565,6 +1565,83 @@ extern "C" int crc_diag_mac_bsgs_forms(crc_ctx *c, const uint64_t *d_x, int in_f
     if (out_form == CRC_COEFF) RUN(crc_ntt_inv(c, d_y, count, 2, stream));
     return CRC_OK;
 }
+// ---- the packed convolution over slots: y[co] = Sum_ci Sum_tau w[co][ci][tau] H_{gs[tau]}(x[ci]) with scalar weights ----
+// crc_diag_mac_forms' passes over the FLAT input x [Cin][count] -- a pass is L.step consecutive ciphertexts whatever their channel, so one image of 32 channels is one
+// pass, not 32 -- with galois_conv_mac_kernel in the place of the diagonal product: one digit decomposition per input ciphertext, one key switch per (input
+// ciphertext, tap), and every rotated input read once per tile of conv_jt output channels.  Where every element is 1 there are no digits at all.  Every step is an
+// exact function on Z_q with canonical residues, so the bits are those of crc_diag_mac_forms per (co, ci) with constant rows, crc_add over ci.
+// output channels per thread: CONV_JT_DEFAULT unless the tuning key "conv_jt" says otherwise.  The same exact function at every setting
+enum { CONV_JT_DEFAULT = 4, CONV_SLOTS_MAX_CH = 4096, CONV_SLOTS_MAX_T = 1024 };
+static int conv_jt(const crc_ctx *c) { return c->tune.conv_jt ? c->tune.conv_jt : (int)CONV_JT_DEFAULT; }
+static bool conv_counts_ok(size_t count, int Cin, int Cout, int T)
+{
+    return Cin >= 1 && Cout >= 1 && T >= 1 && Cin <= CONV_SLOTS_MAX_CH && Cout <= CONV_SLOTS_MAX_CH && T <= CONV_SLOTS_MAX_T && count <= ((size_t)1 << 40);
+}
+static size_t conv_bytes(const crc_ctx *c, size_t count, int Cin, int Cout, int T, int dbc)
+{
+    if (!c || !dbc_ok(dbc) || !conv_counts_ok(count, Cin, Cout, T)) return 0;
+    WorkArena a;
+    hoist_layout(c, (size_t)Cin * count, T, diag_zc(T), dbc, a);
+    return a.bytes();
+}
+extern "C" int crc_conv_slots_pack_weights(const crc_ctx *c, const int64_t *h_w, size_t count, uint64_t *h_out)
+{
+    if (!c || (count && (!h_w || !h_out))) return CRC_ERR_INVALID_ARGUMENT;
+    const int64_t t = (int64_t)c->t;
+    for (int i = 0; i < c->k; i++)
+        for (size_t j = 0; j < count; j++) {
+            const int64_t r = h_w[j] % t;                               // (any int64: the remainder lies in (-t, t))
+            const u64 v = (u64)(r < 0 ? r + t : r), qi = c->q[i];
+            const u64 low = c->plain.fast ? v : v % qi;                 // plain_lift (kernels.hip) of the constant's one coefficient: every position of its NTT-form row
+            h_out[(size_t)i * count + j] = v < c->plain.threshold ? low : c->plain.fast ? v + c->plain.inc[i] : (low + c->plain.inc[i]) % qi;
+        }
+    return CRC_OK;
+}
+extern "C" size_t crc_conv_slots_work_bytes(const crc_ctx *c, size_t count, int Cin, int Cout, int T, int dbc) { return conv_bytes(c, count, Cin, Cout, T, dbc); }
+extern "C" int crc_conv_slots_forms(crc_ctx *c, const uint64_t *d_x, int in_form, size_t count, int Cin, const uint64_t *gs, int T, const uint64_t *d_w, int Cout,
+                                    const uint64_t *d_cgk, const uint64_t *elts, int n_elts, int dbc, uint64_t *d_y, int out_form, void *d_work, void *stream)
+{
+    CHECK_CTX(c);
+    if (!conv_counts_ok(count, Cin, Cout, T) || !d_w || !aligned16(d_w)) return CRC_ERR_INVALID_ARGUMENT;
+    const size_t total = (size_t)Cin * count, outs = (size_t)Cout * count, wb = conv_bytes(c, count, Cin, Cout, T, dbc), ctw = crc_ct_words(c, 2);
+    const size_t wbytes = 8 * (size_t)c->k * Cout * Cin * T;
+    if (!hoist_args_ok(c, d_x, in_form, total, gs, T, d_cgk, elts, n_elts, dbc, d_y, outs, out_form, d_work, wb)) return CRC_ERR_INVALID_ARGUMENT;
+    if (ranges_overlap(d_w, wbytes, d_y, 8 * outs * ctw) || ranges_overlap(d_w, wbytes, d_work, wb)) return CRC_ERR_INVALID_ARGUMENT;
+    std::vector<int> at((size_t)T);
+    if (!hoist_keys(c, gs, T, elts, n_elts, at.data())) return CRC_ERR_INVALID_ARGUMENT;
+    if (count == 0) return CRC_OK;
+    const int zc = diag_zc(T);
+    WorkArena a(d_work);
+    const HoistWork L = hoist_layout(c, total, T, zc, dbc, a);
+    const bool f64 = c->tune.relin_path != 1 && k_relin64_supported(c, dbc), pair = f64 && hoist_rt(c) == 2;
+    bool keyed = false;                                                 // (no digits where every element is 1)
+    for (int r = 0; r < T; r++) keyed = keyed || at[r] >= 0;
+    for (size_t o = 0; o < total; o += L.step) {
+        const size_t ch = pass_len(total, o, L.step);
+        const u64 *xin = d_x + o * ctw;
+        if (keyed) RUN(hoist_pass_head(c, L, xin, in_form, ch, at.data(), T, d_cgk, dbc, f64, o == 0, stream));
+        for (int r0 = 0; r0 < T; r0 += zc) {
+            const int rn = T - r0 < zc ? T - r0 : zc;
+            const u64 *z[GALOIS_DIAG_MAX], *same = nullptr;             // same: the pass itself in NTT form, made once per group for its elements 1
+            int held = -1;                                              // a keyed element that waits for a partner (two keys per digit load)
+            for (int i = 0; i < rn; i++) {
+                const int r = r0 + i;
+                u64 *zi = L.z + (size_t)i * ch * ctw;
+                z[i] = zi;
+                if (at[r] >= 0 && pair && held < 0) held = i;
+                else if (at[r] >= 0 && pair) { RUN(hoist_switch2(c, L, ch, r0 + held, r, dbc, L.z + (size_t)held * ch * ctw, zi, stream)); held = -1; }
+                else if (at[r] >= 0) RUN(hoist_switch(c, L, ch, r, at[r], d_cgk, dbc, f64, o == 0, zi, stream));
+                else if (in_form == CRC_NTT) z[i] = xin;
+                else if (same) z[i] = same;
+                else { RUN(ntt_copy(c, xin, ch, zi, stream)); same = zi; }
+            }
+            if (held >= 0) RUN(hoist_switch(c, L, ch, r0 + held, at[r0 + held], d_cgk, dbc, f64, o == 0, L.z + (size_t)held * ch * ctw, stream));
+            RUN(k_galois_conv_mac(c, z, gs + r0, rn, d_w + r0, T, Cin, Cout, o, ch, count, r0 == 0, d_y, conv_jt(c), S(stream)));
+        }
+    }
+    if (out_form == CRC_COEFF) RUN(crc_ntt_inv(c, d_y, outs, 2, stream));
+    return CRC_OK;
+}
 extern "C" int crc_square_relin(crc_ctx *c, const uint64_t *d_x, size_t count, const uint64_t *d_evk, int dbc, uint64_t *d_y, void *d_work, void *stream)
 {
     return crc_square_relin_forms(c, d_x, CRC_COEFF, count, d_evk, dbc, d_y, CRC_COEFF, d_work, stream);

@@ -250,3 +250,106 @@ int k_galois_sum_permuted(crc_ctx *c, const u64 *const *z, const u64 *g, int R, 
     }
     return CRC_OK;
 }
+
+// ---- the packed convolution: y[co] = Sum_ci Sum_tau w[co][ci][tau] sigma_{g_tau}(Z_tau[ci]) with SCALAR weights ----
+// The multi kernel above with its P row loads replaced by one residue per (modulus, output channel, input channel, tap): a constant plaintext's NTT-form row holds
+// the same word at every position.  z[r]: the pass' key-switch results for tap r, ch NTT-form ciphertexts that are the flat ciphertexts o .. o + ch - 1 of
+// x [Cin][count] (flat index ci count + ct), so a pass may begin and end inside a channel.  A workgroup owns 512 positions of one output row (ct, poly, modulus i) and
+// JT output channels; it walks the pass' input channels that hold a ciphertext of ITS ct -- ci count + ct in [o, o + ch), cut to the launch's [cA, cB) -- and the R
+// taps, gathers Z_r[pi_r(s)] once and multiplies it into JT pairs of 128-bit accumulators.  The weights w [k][Cout][Cin][T] (w points at tap r0 of the launch) are
+// uniform over the workgroup: their addresses depend on blockIdx and loop counters alone, so they come over the scalar path and hold no VGPR.  One barrett128 per
+// output; the launcher keeps (cB - cA) R q_max^2 + q_max below 2^128.  A row is first written by the launch that holds its channel 0 and tap 0 (first = the launch
+// starts at tap 0) and accumulated into by every other; a workgroup with no channel of its ct in the launch leaves its row alone.  A last tile with fewer than JT
+// outputs computes its missing ones with the weights of channel Cout - 1 and does not store them.
+// grid: (count 2 k max(1, n / 512), ceil(Cout / JT))
+struct GaloisConvArgs { const u64 *z[GALOIS_DIAG_MAX]; u32 g[GALOIS_DIAG_MAX]; };
+template <int JT>
+__global__ void __launch_bounds__(256, JT <= 4 ? 8 : 4) galois_conv_mac_kernel(GaloisConvArgs a, int R, const u64 *__restrict__ w, int T, int Cin, int Cout, size_t o,
+                                                                             size_t ch, size_t count, int cA, int cB, int first, u64 *y, const ModParams *mods, int n,
+                                                                             int logn, int k, int blocks_per_row)
+{
+    const size_t row = blockIdx.x / (u32)blocks_per_row; const u32 part = blockIdx.x - (u32)row * (u32)blocks_per_row;      // row = (ct 2 + poly) k + i
+    const u32 s = (part * 256u + threadIdx.x) * 2u;
+    if (s >= (u32)n) return;
+    const size_t ct = row / (2u * (u32)k); const u32 pk = (u32)(row - ct * 2u * (u32)k);                                    // pk = poly k + i
+    const int i = (int)(pk >= (u32)k ? pk - (u32)k : pk);
+    const size_t end = o + ch;
+    int lo = o > ct ? (int)((o - ct + count - 1) / count) : 0, hi = end > ct ? (int)((end - ct + count - 1) / count) : 0;   // ci count + ct in [o, end)
+    if (lo < cA) lo = cA;
+    if (hi > cB) hi = cB;
+    if (lo >= hi) return;
+    const bool accumulate = !(first && lo == 0);
+    const ModParams m = mods[i];
+    const u32 m2 = 2u * (u32)n - 1u; const int sh = 32 - logn;
+    const int j0 = (int)blockIdx.y * JT;
+    unsigned __int128 acc0[JT], acc1[JT];
+    const u64 *wt[JT];                                                     // (uniform: w[i][co][0][r0 ..])
+    const size_t yj = count * 2 * (size_t)k * n;                           // words from one output channel to the next
+    u64 *yo = y + (size_t)j0 * yj + row * (size_t)n + s;
+#pragma unroll
+    for (int t = 0; t < JT; t++) {
+        wt[t] = w + ((size_t)i * Cout + (j0 + t < Cout ? j0 + t : Cout - 1)) * Cin * (size_t)T;
+        acc0[t] = 0; acc1[t] = 0;
+        if (accumulate && j0 + t < Cout) { const ulonglong2 v = ld2(yo + (size_t)t * yj); acc0[t] = v.x; acc1[t] = v.y; }
+    }
+    for (int ci = lo; ci < hi; ci++) {
+        const size_t zo = (((size_t)ci * count + ct - o) * 2 * (size_t)k + pk) * n, wo = (size_t)ci * T;
+        for (int r = 0; r < R; r++) {
+            const u64 *zr = a.z[r] + zo;
+            const u32 g = a.g[r];
+            const u64 za = zr[galois_ntt_src(s, g, m2, sh)], zb = zr[galois_ntt_src(s + 1u, g, m2, sh)];
+#pragma unroll
+            for (int t = 0; t < JT; t++) {
+                const u64 wv = wt[t][wo + r];
+                u64 l, h;
+                mul64wide(wv, za, l, h); acc0[t] += ((unsigned __int128)h << 64) | l;
+                mul64wide(wv, zb, l, h); acc1[t] += ((unsigned __int128)h << 64) | l;
+            }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < JT; t++)
+        if (j0 + t < Cout) st2(yo + (size_t)t * yj, barrett128((u64)acc0[t], (u64)(acc0[t] >> 64), m), barrett128((u64)acc1[t], (u64)(acc1[t] >> 64), m));
+}
+// the terms one reduction may sum: terms q_max^2 + q_max < 2^128 (diag_group's rule without its cap of one launch's pointers)
+static int conv_terms(const crc_ctx *c)
+{
+    int bits = 0;
+    for (int i = 0; i < c->k; i++) if ((int)c->tabs[i].m.bits > bits) bits = c->tabs[i].m.bits;
+    const int room = 127 - 2 * bits;
+    return room >= 20 ? 1 << 20 : room > 0 ? 1 << room : 1;
+}
+template <int JT>
+static void conv_launch(crc_ctx *c, const GaloisConvArgs &a, int rn, const u64 *w, int T, int Cin, int Cout, size_t o, size_t ch, size_t count, int cA, int cB,
+                        bool first, u64 *y, unsigned blocks, int bpr, hipStream_t st)
+{
+    hipLaunchKernelGGL(galois_conv_mac_kernel<JT>, dim3(blocks, (unsigned)((Cout + JT - 1) / JT)), dim3(256), 0, st, a, rn, w, T, Cin, Cout, o, ch, count, cA, cB,
+                       first ? 1 : 0, y, c->d_mods, c->n, c->logn, c->k, bpr);
+}
+// z: the R <= GALOIS_DIAG_MAX key-switch results of the pass [o, o + ch) of the flat input [Cin][count], g their elements; w: &d_w[0][0][0][r0] of [k][Cout][Cin][T];
+// first: r0 = 0; y [Cout][count]; jt: 2 | 4 | 8
+int k_galois_conv_mac(crc_ctx *c, const u64 *const *z, const u64 *g, int R, const u64 *w, int T, int Cin, int Cout, size_t o, size_t ch, size_t count, bool first,
+                      u64 *y, int jt, hipStream_t st)
+{
+    if (count == 0 || ch == 0 || R < 1) return CRC_OK;
+    if (R > GALOIS_DIAG_MAX || Cin < 1 || Cout < 1 || o + ch > (size_t)Cin * count || (jt != 2 && jt != 4 && jt != 8)) return CRC_ERR_INVALID_ARGUMENT;
+    const int bpr = c->n > 512 ? c->n / 512 : 1;
+    const size_t blocks = count * 2 * (size_t)c->k * bpr;
+    if (blocks > 0x7fffffffull || (size_t)(Cout + 1) / 2 > 65535) return CRC_ERR_INVALID_ARGUMENT;
+    const int terms = conv_terms(c), per = R < terms ? R : terms, cper = terms / per;      // taps per launch; channels per launch (>= 1)
+    const int c_lo = (int)(o / count), c_hi = (int)((o + ch - 1) / count) + 1;             // the pass' channels
+    for (int r0 = 0; r0 < R; r0 += per) {
+        GaloisConvArgs a{};
+        const int rn = R - r0 < per ? R - r0 : per;
+        for (int r = 0; r < rn; r++) { a.z[r] = z[r0 + r]; a.g[r] = (u32)g[r0 + r]; }
+        for (int cA = c_lo; cA < c_hi; cA += cper) {
+            const int cB = c_hi - cA < cper ? c_hi : cA + cper;
+            const bool f = first && r0 == 0;
+            if (jt == 2) conv_launch<2>(c, a, rn, w + r0, T, Cin, Cout, o, ch, count, cA, cB, f, y, (unsigned)blocks, bpr, st);
+            else if (jt == 4) conv_launch<4>(c, a, rn, w + r0, T, Cin, Cout, o, ch, count, cA, cB, f, y, (unsigned)blocks, bpr, st);
+            else conv_launch<8>(c, a, rn, w + r0, T, Cin, Cout, o, ch, count, cA, cB, f, y, (unsigned)blocks, bpr, st);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    return CRC_OK;
+}

@@ -792,6 +792,97 @@ ciphertext3D matvecSlotsBsgs(const ciphertext3D &t, const vector<vector<int64_t>
     chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");           // (the rows' buffers go out of scope here)
     return out;
 }
+// ---- the packed convolution: one channel plane per ciphertext ---------------------------------------------------------------
+static ConvSlotsPlan convSlotsPlan(const SlotPlanes &g)
+{
+    ConvSlotsPlan P;
+    if (!crc_conv_slots_plan(N(), g.M, g.pitch, g.H, g.W, g.fh, g.fw, g.dil, g.pool, P))
+        throw invalid_argument("convSlots: M must be a power of two <= n/2, the plane must fit it and the window must leave an output");
+    return P;
+}
+SlotPlanes planesOf(int xd, int yd, int M)
+{
+    SlotPlanes g;
+    g.M = M; g.pitch = yd; g.H = xd; g.W = yd;
+    return g;
+}
+ciphertext3D encryptImagePlanes(const vector<int64_t> &pixels, int zd, int xd, int yd, int M, int out_form)
+{
+    if (!g_slot_on) throw logic_error("encryptImagePlanes: setSlotEncoding() must be called first");
+    const int n = N();
+    if (zd < 1 || xd < 1 || yd < 1 || pixels.size() != (size_t)zd * xd * yd) throw invalid_argument("encryptImagePlanes: [zd][xd][yd] pixels");
+    if (M < 1 || (M & (M - 1)) || M > n / 2 || (long long)xd * yd > M) throw invalid_argument("encryptImagePlanes: M must be a power of two <= n/2 that holds a plane");
+    if (out_form != CRC_COEFF && out_form != CRC_NTT) throw invalid_argument("encryptImagePlanes: ciphertext forms only (CRC_COEFF / CRC_NTT)");
+    const size_t per = (size_t)xd * yd;
+    vector<int64_t> h((size_t)zd * n, 0);                               // plane-major: slot i of plane z at h[z n + i]
+    for (int z = 0; z < zd; z++)
+        for (int i = 0; i < n; i++) if ((size_t)(i % M) < per) h[(size_t)z * n + i] = pixels[(size_t)z * per + i % M];
+    DeviceBuffer d_v(h.size() * 8), d_pl(h.size() * 8), d_work(crc_encrypt_dev_work_bytes(ctx(), zd));
+    const uint64_t *d_pk = deviceKey(g_d_pk, g_d_pk_fp, public_key, "public key");
+    chk(crc_memcpy_h2d(ctx(), d_v.ptr, h.data(), h.size() * 8, stream()), "crc_memcpy_h2d");
+    chk(crc_slots_compose_dev(ctx(), (const int64_t *)d_v.ptr, zd, n, n, 1, (uint64_t *)d_pl.ptr, stream()), "crc_slots_compose_dev");
+    ciphertext3D out(1, zd, 1, 1, out_form);
+    if (g_det)
+        chk(crc_encrypt_dev_forms(ctx(), d_pk, (const uint64_t *)d_pl.ptr, zd, g_det_seed + 1000003 * (g_enc_counter + 1), out_form, (uint64_t *)out.data(),
+                                  d_work.ptr, stream()), "crc_encrypt_dev_forms");
+    else
+        chk(crc_encrypt_dev_key_forms(ctx(), d_pk, (const uint64_t *)d_pl.ptr, zd, g_master_key, g_enc_counter, out_form, (uint64_t *)out.data(), d_work.ptr,
+                                      stream()), "crc_encrypt_dev_key_forms");
+    g_enc_counter += zd;
+    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+    return out;
+}
+ciphertext3D encryptImagePlanes(const vector<float> &pixels, int zd, int xd, int yd, int M, int out_form)
+{
+    if (!g_slot_on) throw logic_error("encryptImagePlanes: setSlotEncoding() must be called first");
+    const double scale = ldexp(1.0, g_slot_in_bits);
+    vector<int64_t> q(pixels.size());
+    for (size_t i = 0; i < pixels.size(); i++) {
+        const double r = nearbyint((double)pixels[i] * scale);
+        if (!(fabs(r) < 9.2e18)) throw invalid_argument("encryptImagePlanes: a pixel does not fit an int64 at this scale");
+        q[i] = (int64_t)r;
+    }
+    return encryptImagePlanes(q, zd, xd, yd, M, out_form);
+}
+vector<vector<int64_t>> decryptPlanes(const ciphertext3D &t, const SlotPlanes &g)
+{
+    if (g.M < 1 || g.M > N() || g.pitch < 1 || g.H < 1 || g.W < 1 || g.dil < 1 || g.W > g.pitch || (long long)g.dil * ((long long)(g.H - 1) * g.pitch + g.W - 1) >= g.M)
+        throw invalid_argument("decryptPlanes: the plane does not fit its period");
+    const vector<vector<int64_t>> v = decryptSlots(t, g.M);            // [M][count]
+    vector<vector<int64_t>> out(t.count());
+    for (size_t z = 0; z < out.size(); z++)
+        for (int r = 0; r < g.H; r++) for (int c = 0; c < g.W; c++) out[z].push_back(v[(size_t)g.dil * (r * g.pitch + c)][z]);
+    return out;
+}
+vector<uint64_t> convSlotsElements(const SlotPlanes &g)
+{
+    const ConvSlotsPlan P = convSlotsPlan(g);
+    vector<uint64_t> out;
+    for (uint64_t e : P.elements) if (e != 1 && find(out.begin(), out.end(), e) == out.end()) out.push_back(e);
+    return out;
+}
+ciphertext3D convSlots(const ciphertext3D &t, const vector<int64_t> &weights, int Cout, const SlotPlanes &g, SlotPlanes *og, int out_form)
+{
+    if (!crc_slots_supported(ctx())) throw logic_error("encryption parameters do not support batching");
+    const ConvSlotsPlan P = convSlotsPlan(g);
+    const vector<uint64_t> gs = hoistedElements("convSlots", t, P.steps, out_form);
+    if (t.B != 1 || t.xd != 1 || t.yd != 1) throw invalid_argument("convSlots: a tensor [1][zd][1][1] of channel planes (encryptImagePlanes)");
+    const int Cin = (int)t.count(), T = (int)P.steps.size(), k = crc_ctx_k(ctx()), dbc = g_galois_dbc ? g_galois_dbc : 16;
+    vector<int64_t> folded;
+    if (Cout < 1 || !crc_conv_slots_fold(P, weights, Cout, Cin, (int64_t)g_plain_modulus, folded)) throw invalid_argument("convSlots: weights must be [Cout][Cin][fh][fw]");
+    vector<uint64_t> packed((size_t)k * folded.size());
+    chk(crc_conv_slots_pack_weights(ctx(), folded.data(), folded.size(), packed.data()), "crc_conv_slots_pack_weights");
+    if (!crc_conv_slots_work_bytes(ctx(), 1, Cin, Cout, T, dbc)) throw invalid_argument("convSlots: too many channels or taps");
+    DeviceBuffer d_w(packed.size() * 8);
+    chk(crc_memcpy_h2d(ctx(), d_w.ptr, packed.data(), packed.size() * 8, stream()), "crc_memcpy_h2d");
+    ciphertext3D out(1, Cout, 1, 1, out_form);
+    ensure(g_scratch, crc_conv_slots_work_bytes(ctx(), 1, Cin, Cout, T, dbc));
+    chk(crc_conv_slots_forms(ctx(), t.data(), t.form, 1, Cin, gs.data(), T, (const uint64_t *)d_w.ptr, Cout, g_galois_ckeys ? (const uint64_t *)g_galois_ckeys->ptr : nullptr,
+                             galois_elts.data(), (int)galois_elts.size(), dbc, out.data(), out_form, g_scratch->ptr, stream()), "convSlots");
+    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");           // (the weights' buffer goes out of scope here)
+    if (og) { *og = SlotPlanes(); og->M = g.M; og->pitch = g.pitch; og->H = P.out_h; og->W = P.out_w; og->dil = P.out_dil; }
+    return out;
+}
 vector<floatCube> decryptImages(const ciphertext3D &t)
 {
     const int n = N();

@@ -197,6 +197,28 @@ int bsgsDefaultSplit(int M);
 void bsgsMatvecPlan(const std::vector<std::vector<int64_t>> &W, int M, int n, int B, std::vector<int> &baby_steps, std::vector<int> &giant_steps,
                     std::vector<int64_t> &rows);
 
+// A convolution over the slots of ONE image, one channel plane per ciphertext (include/crcnn_hip.h: crc_conv_slots_forms; the plan: crc_conv_slots_plan in
+// crcnn_amd/host/diag_plan.h).  SlotPlanes says where a tensor [1][zd][1][1] keeps its planes: pixel (r, c) of an H x W plane at slot dil (r pitch + c), tiled with
+// period M over both rows of n/2 slots (matvecSlots' input contract); fh, fw, pool describe the layer applied to it -- a 'valid' fh x fw convolution of stride 1,
+// then a pool x pool sum pool of stride pool, folded into the taps.  Slots that hold no valid pixel hold junk: no masks, no zero padding.
+struct SlotPlanes { int M = 0, pitch = 0, H = 0, W = 0, dil = 1, fh = 1, fw = 1, pool = 1; };
+// pixels [zd][xd][yd] (integers as they are; floats quantised as encryptImageSlots quantises) -> a tensor [1][zd][1][1] of zd ciphertexts, plane z with its xd rows
+// of yd pixels at pitch yd, dilation 1, period M.  Keystream discipline as encryptImage.  std::logic_error unless setSlotEncoding is on; std::invalid_argument
+// for M not a power of two <= n/2 or a plane that does not fit it.  planesOf: the SlotPlanes of such a tensor
+ciphertext3D encryptImagePlanes(const std::vector<int64_t> &pixels, int zd, int xd, int yd, int M, int out_form = CRC_COEFF);
+ciphertext3D encryptImagePlanes(const std::vector<float> &pixels, int zd, int xd, int yd, int M, int out_form = CRC_COEFF);
+SlotPlanes planesOf(int xd, int yd, int M);
+// the H x W valid pixels of every plane of the tensor, from the first period, as centred integers [zd][H W]
+std::vector<std::vector<int64_t>> decryptPlanes(const ciphertext3D &t, const SlotPlanes &g);
+// y[co] = Sum_ci conv(x[ci], weights[co][ci]) (+ pool) over the global Galois keys: plans (crc_conv_slots_plan), folds and packs the weights
+// [Cout][Cin = t.zd][fh][fw] (any int64, taken mod t), calls crc_conv_slots_forms.  Returns the Cout ciphertexts [1][Cout][1][1] and sets *out to where their valid
+// pixels are (fh = fw = pool = 1: ready for the next layer's window).  The keys of convSlotsElements(g) must be in the set (generateGaloisKeys(dbc, elements)).
+// Exceptions as matvecSlots: std::logic_error without batching, std::invalid_argument for a geometry the planner refuses, a weight count that is not
+// Cout t.zd fh fw, other forms, a missing key
+ciphertext3D convSlots(const ciphertext3D &t, const std::vector<int64_t> &weights, int Cout, const SlotPlanes &g, SlotPlanes *out = nullptr, int out_form = CRC_COEFF);
+// the Galois elements of the layer's taps without the element 1, each once (at most (fh + pool - 1)(fw + pool - 1) - 1 keys); std::invalid_argument as convSlots
+std::vector<uint64_t> convSlotsElements(const SlotPlanes &g);
+
 // ---- layers (CrCNN/src/layer.h:10-31) ------------------------------------------------------------------------------
 class Layer {
 public:

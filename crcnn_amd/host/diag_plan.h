@@ -66,3 +66,61 @@ inline std::vector<uint64_t> crc_bsgs_elements(int M, int B, int n)
     }
     return out;
 }
+
+// ---- the packed convolution over slots (convSlots; crc_conv_slots_forms) ----
+// ONE image, one channel plane per ciphertext: pixel (y, x) of an H x W plane at slot dil (y pitch + x), tiled with period M over both rows of n/2 slots (matvecSlots'
+// input contract).  A 'valid' convolution with an fh x fw window, stride 1 on the dilated grid, then a pool x pool sum pool of stride pool folded in front of the
+// rotations: the window becomes (fh + pool - 1) x (fw + pool - 1), tap (a, b) is the row rotation by dil (a pitch + b) with the weight
+// w'[a][b] = Sum_{u, v < pool} w[a - u][b - v], and output (y, x) lands where input (pool y, pool x) was: at slot out_dil (y pitch + x), out_dil = dil pool.
+// Slots outside `valid` hold junk that the next layer's weights never read: no masks, no zero padding.
+struct ConvSlotsPlan {
+    int n = 0, M = 0, pitch = 0, fh = 0, fw = 0, pool = 0;
+    int out_h = 0, out_w = 0, out_dil = 0;
+    std::vector<int> steps;                  // [T] row-major over the enlarged window
+    std::vector<uint64_t> elements;          // [T] 3^step mod 2n (crc_galois_elt_rows); tap (0, 0): the element 1, which needs no key
+    std::vector<int> valid;                  // [out_h out_w] row-major: the slots of the first period that hold an output
+};
+// false (P untouched) for M not a power of two <= n/2, a plane that does not fit (W <= pitch, dil ((H - 1) pitch + W - 1) < M), a window larger than the plane,
+// a pool that leaves no output, a step >= n/2
+inline bool crc_conv_slots_plan(int n, int M, int pitch, int H, int W, int fh, int fw, int dil, int pool, ConvSlotsPlan &P)
+{
+    if (n < 2 || (n & (n - 1)) || M < 1 || (M & (M - 1)) || M > n / 2) return false;
+    if (pitch < 1 || H < 1 || W < 1 || fh < 1 || fw < 1 || dil < 1 || pool < 1 || W > pitch || fh > H || fw > W) return false;
+    if ((int64_t)dil * ((int64_t)(H - 1) * pitch + W - 1) >= M) return false;      // (every factor is below M from here on: no overflow)
+    const int oh = (H - fh + 1) / pool, ow = (W - fw + 1) / pool, eh = fh + pool - 1, ew = fw + pool - 1;
+    if (oh < 1 || ow < 1 || (int64_t)dil * ((int64_t)(eh - 1) * pitch + ew - 1) >= n / 2) return false;
+    ConvSlotsPlan Q;
+    Q.n = n; Q.M = M; Q.pitch = pitch; Q.fh = fh; Q.fw = fw; Q.pool = pool; Q.out_h = oh; Q.out_w = ow; Q.out_dil = dil * pool;
+    const uint64_t mask = 2 * (uint64_t)n - 1;
+    for (int a = 0; a < eh; a++)
+        for (int b = 0; b < ew; b++) {
+            const int s = dil * (a * pitch + b);
+            uint64_t g = 1;
+            for (uint64_t e = (uint64_t)s, x = 3; e; e >>= 1, x = x * x & mask) if (e & 1) g = g * x & mask;
+            Q.steps.push_back(s); Q.elements.push_back(g);
+        }
+    for (int y = 0; y < oh; y++) for (int x = 0; x < ow; x++) Q.valid.push_back(Q.out_dil * (y * pitch + x));
+    P = Q;
+    return true;
+}
+// w [Cout][Cin][fh][fw] (any int64) -> out [Cout][Cin][T] in [0, t): the pool's window sum folded into the taps, mod t.  false (out untouched) for a size that is
+// not Cout Cin fh fw, or t < 2
+inline bool crc_conv_slots_fold(const ConvSlotsPlan &P, const std::vector<int64_t> &w, int Cout, int Cin, int64_t t, std::vector<int64_t> &out)
+{
+    if (Cout < 1 || Cin < 1 || t < 2 || P.fh < 1 || P.fw < 1 || P.pool < 1 || w.size() != (size_t)Cout * Cin * P.fh * P.fw) return false;
+    const int eh = P.fh + P.pool - 1, ew = P.fw + P.pool - 1;
+    std::vector<int64_t> o((size_t)Cout * Cin * eh * ew, 0);
+    for (size_t c = 0; c < (size_t)Cout * Cin; c++)
+        for (int a = 0; a < P.fh; a++)
+            for (int b = 0; b < P.fw; b++) {
+                int64_t v = w[(c * P.fh + a) * P.fw + b] % t;
+                if (v < 0) v += t;
+                for (int u = 0; u < P.pool; u++)
+                    for (int x = 0; x < P.pool; x++) {
+                        int64_t &d = o[(c * eh + a + u) * ew + b + x];
+                        d = d >= t - v ? d - (t - v) : d + v;               // (d + v mod t without leaving [0, t))
+                    }
+            }
+    out = o;
+    return true;
+}

@@ -15,8 +15,17 @@
 // the same entry point, on the diagonals 0..3 and 4, 8, 12 that the keys reach) writes <dir>/<name>.i64, prints "budget <name> <min bits>" and
 // "product <name> equal|differs" (every slot against W x mod t computed here), then "keys bsgs <bytes> flat <bytes>" for a dense 16 x 16 product,
 // "throws <case> <kind>" and "hoist_host bsgs ok".
+//
+//   hoist_host <dir> conv          (tests/test_gpu_conv_slots_cpp.py)
+//
+// convSlots on one image of channel planes: <dir>/image.i64 = [12][12] pixels, <dir>/w1.i64 = [2][1][3][3], <dir>/w2.i64 = [3][2][3][3] int64 weights; M = 256.
+// Layer 1 is the 3 x 3 convolution with a 2 x 2 sum pool folded in (16 taps, 5 x 5 outputs at dilation 2), layer 2 a 3 x 3 convolution at that dilation (3 x 3
+// outputs).  Keys: convSlotsElements of both layers, each element once.  Per case (conv_fresh = the encrypted image read back, conv_1, conv_2, conv_2_ntt = both
+// layers NTT-resident) writes <dir>/<name>.i64 = [channels][H W] (decryptPlanes), prints "budget <name> <min bits>" and "conv <name> equal|differs" (every valid
+// pixel against the integer convolution computed here), then "keys conv <bytes> elements <count>", "throws <case> <kind>" and "hoist_host conv ok".
 #include "crcnn_host.h"
 #include "diag_plan.h"
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -106,9 +115,74 @@ static int bsgs_case(const vector<uint64_t> &p, const vector<uint64_t> &q)
     return 0;
 }
 
+// [Cin][H][W] -> [Cout][oh][ow]: the 'valid' stride-1 convolution with w [Cout][Cin][fh][fw], then a pool x pool sum pool of stride pool; exact integers
+static vector<vector<int64_t>> conv_int(const vector<vector<int64_t>> &x, int H, int W, const vector<int64_t> &w, int Cout, int fh, int fw, int pool)
+{
+    const int Cin = (int)x.size(), oh = (H - fh + 1) / pool, ow = (W - fw + 1) / pool;
+    vector<vector<int64_t>> y(Cout, vector<int64_t>((size_t)oh * ow, 0));
+    for (int co = 0; co < Cout; co++) for (int r = 0; r < oh; r++) for (int c = 0; c < ow; c++)
+        for (int u = 0; u < pool; u++) for (int v = 0; v < pool; v++)
+            for (int ci = 0; ci < Cin; ci++) for (int a = 0; a < fh; a++) for (int b = 0; b < fw; b++)
+                y[co][(size_t)r * ow + c] += w[(((size_t)co * Cin + ci) * fh + a) * fw + b] * x[ci][(size_t)(pool * r + u + a) * W + pool * c + v + b];
+    return y;
+}
+static void planes(const char *name, const ciphertext3D &y, const SlotPlanes &g, const vector<vector<int64_t>> &want)
+{
+    printf("budget %s %d\n", name, minNoiseBudget(y));
+    const vector<vector<int64_t>> got = decryptPlanes(y, g);
+    ofstream f(dir + "/" + name + ".i64", ios::binary);
+    for (auto &row : got) f.write((const char *)row.data(), row.size() * 8);
+    printf("conv %s %s\n", name, got == want ? "equal" : "differs");
+}
+static int conv_case(const vector<uint64_t> &p, const vector<uint64_t> &q)
+{
+    const int M = 256, H = 12, W = 12;
+    auto ints = [&](const char *file) { const auto raw = rd(dir + "/" + file); return vector<int64_t>(raw.begin(), raw.end()); };
+    const vector<int64_t> img = ints("image.i64"), w1 = ints("w1.i64"), w2 = ints("w2.i64");
+    SlotPlanes g1 = planesOf(H, W, M);
+    g1.fh = 3; g1.fw = 3; g1.pool = 2;
+    setParameters(n, q, (uint64_t)1 << 20, 0);
+    { ciphertext3D none(1, 1, 1, 1); thrown("no_batching_conv", [&] { convSlots(none, w1, 2, g1); }); }
+    thrown("no_slot_encoding", [&] { encryptImagePlanes(img, 1, H, W, M); });
+    setParameters(n, q, p[2], 0);
+    setSlotEncoding(0, 0);
+    const ciphertext3D x = encryptImagePlanes(img, 1, H, W, M);
+    thrown("no_keys_conv", [&] { convSlots(x, w1, 2, g1); });
+    SlotPlanes g2, g3;
+    {                                                                   // the second layer's geometry is the first one's output: known from the plan alone
+        ConvSlotsPlan P1;
+        if (!crc_conv_slots_plan(n, M, W, H, W, 3, 3, 1, 2, P1)) return 5;
+        g2 = planesOf(H, W, M); g2.H = P1.out_h; g2.W = P1.out_w; g2.dil = P1.out_dil; g2.fh = 3; g2.fw = 3;
+    }
+    vector<uint64_t> elts = convSlotsElements(g1);
+    for (uint64_t e : convSlotsElements(g2)) if (find(elts.begin(), elts.end(), e) == elts.end()) elts.push_back(e);
+    generateGaloisKeys(16, elts);
+    const vector<vector<int64_t>> x0{img}, y1 = conv_int(x0, H, W, w1, 2, 3, 3, 2), y2 = conv_int(y1, g2.H, g2.W, w2, 3, 3, 3, 1);
+    planes("conv_fresh", x, planesOf(H, W, M), x0);
+    SlotPlanes o1;
+    const ciphertext3D c1 = convSlots(x, w1, 2, g1, &o1);
+    if (o1.H != g2.H || o1.W != g2.W || o1.dil != g2.dil || o1.pitch != g2.pitch || o1.M != M) return 6;
+    planes("conv_1", c1, o1, y1);
+    const ciphertext3D c2 = convSlots(c1, w2, 3, g2, &g3);
+    planes("conv_2", c2, g3, y2);
+    { const ciphertext3D n1 = convSlots(x, w1, 2, g1, nullptr, CRC_NTT); planes("conv_2_ntt", convSlots(n1, w2, 3, g2, nullptr, CRC_NTT), g3, y2); }
+    printf("keys conv %zu elements %zu\n", elts.size() * crc_evk_words(context, 16) * 8, elts.size());
+    thrown("bad_weights", [&] { convSlots(x, w2, 2, g1); });
+    thrown("bad_M_conv", [&] { SlotPlanes b = g1; b.M = 96; convSlots(x, w1, 2, b); });
+    thrown("plane_does_not_fit", [&] { SlotPlanes b = g1; b.M = 128; convSlots(x, w1, 2, b); });
+    thrown("missing_key_conv", [&] { SlotPlanes b = g1; b.pool = 3; convSlots(x, vector<int64_t>(2 * 9, 1), 2, b); });       // a 5 x 5 window: taps without keys
+    thrown("bad_form_conv", [&] { convSlots(x, w1, 2, g1, nullptr, CRC_NTTP); });
+    thrown("not_planes", [&] { convSlots(ciphertext3D(1, 1, 2, 1), vector<int64_t>(2 * 9, 1), 2, g1); });
+    thrown("plane_too_large", [&] { encryptImagePlanes(vector<int64_t>(17 * 17, 1), 1, 17, 17, M); });
+    delParameters();
+    clearDeterministicSeed();
+    printf("hoist_host conv ok\n");
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: hoist_host <dir> [bsgs]\n"); return 1; }
+    if (argc < 2) { fprintf(stderr, "usage: hoist_host <dir> [bsgs | conv]\n"); return 1; }
     try {
         dir = argv[1];
         setDeterministicSeed(20241019);
@@ -116,6 +190,7 @@ int main(int argc, char **argv)
         n = (int)p[0]; const int k = (int)p[1];
         const vector<uint64_t> q(p.begin() + 3, p.begin() + 3 + k);
         if (argc > 2 && string(argv[2]) == "bsgs") return bsgs_case(p, q);
+        if (argc > 2 && string(argv[2]) == "conv") return conv_case(p, q);
         const vector<vector<int64_t>> W8 = matrix(dir + "/w8.i64", 8, 8), W5 = matrix(dir + "/w5.i64", 5, 8);
         // a plain modulus without slots: the reference's logic_error, before any key is looked at
         setParameters(n, q, (uint64_t)1 << 20, 0);

@@ -677,8 +677,20 @@ int crc_sum_slots_forms(crc_ctx *ctx, const uint64_t *d_x, int in_form, size_t c
  *                               B G terms takes B G.  With gb[b] = crc_galois_elt_rows(b), gg[j] = crc_galois_elt_rows(B j) and the rows of crc_bsgs_plan
  *                               (crcnn_amd/host/diag_plan.h) this is the M x M matrix-vector product over slots, M = B G.  G = 1 with gg = {1} is
  *                               crc_diag_mac_forms.  d_work: crc_diag_mac_bsgs_work_bytes(ctx, count, B, G, dbc); B, G <= 65536
+ *   crc_conv_slots_forms        the packed convolution: d_x [Cin][count] -> d_y [Cout][count],  y[co] = Sum_ci Sum_tau w[.][co][ci][tau] H_{gs[tau]}(x[ci])  with
+ *                               SCALAR weights d_w [k][Cout][Cin][T], one canonical residue per modulus (crc_conv_slots_pack_weights).  Bit for bit: for every
+ *                               (co, ci) crc_diag_mac_forms(x[ci], gs, T, P[co][ci]) into NTT form, where P[co][ci][tau] is crc_plain_to_ntt of the constant
+ *                               polynomial w mod t; crc_add over ci; one inverse transform for CRC_COEFF -- at every tuning setting and however the call groups
+ *                               taps, channels and ciphertexts into launches and passes.  One digit decomposition per input ciphertext and one key switch per
+ *                               (input ciphertext, tap with gs[tau] != 1) where the composition takes Cout of each; neither a rotated input nor a product is
+ *                               written.  With one channel plane per ciphertext and the taps of crc_conv_slots_plan (crcnn_amd/host/diag_plan.h) this is a
+ *                               'valid' convolution of a single packed image.  d_work: crc_conv_slots_work_bytes(ctx, count, Cin, Cout, T, dbc) (0 for bad
+ *                               arguments); Cin, Cout <= 4096, T <= 1024
+ *   crc_conv_slots_pack_weights host memory, any context: h_out [k][count] from count integers h_w (any int64, taken mod t): for c = w mod t in [0, t) the word
+ *                               c >= (t + 1) / 2 ? c + q_i - t : c  (mod q_i) -- every position of the NTT-form row of the constant plaintext c
  * Refusals as in the paragraph above (null / misaligned / overlapping operands, forms, dbc, an invalid element), plus R < 1 (B < 1, G < 1) and a missing
- * conjugated key: CRC_ERR_INVALID_ARGUMENT, nothing launched.  count = 0 is CRC_OK.
+ * conjugated key; crc_conv_slots_forms also for Cin, Cout or T below 1 or above its caps, and for d_w null, misaligned or overlapping d_y or d_work:
+ * CRC_ERR_INVALID_ARGUMENT, nothing launched, d_y untouched.  count = 0 is CRC_OK.
  * ------------------------------------------------------------------------------------------------------------- */
 int crc_galois_ntt_table(const crc_ctx *ctx, uint64_t g, uint32_t *table /*[n]*/);
 int crc_galois_conjugate_keys(const crc_ctx *ctx, const uint64_t *elts, int n_elts, int dbc, const uint64_t *h_gk, uint64_t *h_out);
@@ -694,6 +706,11 @@ size_t crc_diag_mac_bsgs_work_bytes(const crc_ctx *ctx, size_t count, int B, int
 int crc_diag_mac_bsgs_forms(crc_ctx *ctx, const uint64_t *d_x, int in_form, size_t count, const uint64_t *gb /*[B], host*/, int B, const uint64_t *gg /*[G], host*/,
                             int G, const uint64_t *d_p_ntt /*[G][B][k][n]*/, const uint64_t *d_cgk, const uint64_t *elts, int n_elts, int dbc,
                             uint64_t *d_y /*[count]*/, int out_form, void *d_work, void *stream);
+int crc_conv_slots_pack_weights(const crc_ctx *ctx, const int64_t *h_w, size_t count, uint64_t *h_out /*[k][count]*/);
+size_t crc_conv_slots_work_bytes(const crc_ctx *ctx, size_t count, int Cin, int Cout, int T, int dbc);
+int crc_conv_slots_forms(crc_ctx *ctx, const uint64_t *d_x /*[Cin][count]*/, int in_form, size_t count, int Cin, const uint64_t *gs /*[T], host*/, int T,
+                         const uint64_t *d_w /*[k][Cout][Cin][T]*/, int Cout, const uint64_t *d_cgk, const uint64_t *elts, int n_elts, int dbc,
+                         uint64_t *d_y /*[Cout][count]*/, int out_form, void *d_work, void *stream);
 /* FractionalEncoder::decode / encode (encoder.cpp:1226-1270, 1013-1076; 64 integer + 32 fractional coefficients, base 3: CrCNN/src/globals.cpp:52) on the
  * device: the doubles crc_decode returns for d_plain [count][n], and the dense plaintexts [count][n] crc_encode_f32 / _f64 make of the values -- the same IEEE
  * operations in the same order as the host encoder, contraction off. */
