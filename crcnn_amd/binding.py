@@ -272,6 +272,10 @@ def load():
     L.crc_conv_slots_pack_weights.argtypes = [VP, ctypes.POINTER(ctypes.c_int64), SZ, PU]
     L.crc_conv_slots_work_bytes.restype = SZ; L.crc_conv_slots_work_bytes.argtypes = [VP, SZ, CI, CI, CI, CI]
     L.crc_conv_slots_forms.argtypes = [VP, VP, CI, SZ, CI, PU, CI, VP, CI, VP, PU, CI, CI, VP, CI, VP, VP]
+    L.crc_galois_prepared_key_words.restype = SZ; L.crc_galois_prepared_key_words.argtypes = [VP, CI]
+    L.crc_galois_prepare_keys_dev.argtypes = [VP, VP, PU, CI, CI, VP, VP, VP]
+    L.crc_dense_planes_work_bytes.restype = SZ; L.crc_dense_planes_work_bytes.argtypes = [VP, SZ, CI, CI, CI, CI]
+    L.crc_dense_planes_forms.argtypes = [VP, VP, CI, SZ, CI, PU, CI, VP, VP, PU, CI, VP, CI, VP, CI, VP, VP]
     L.crc_noise_budget.argtypes = [VP, PU, PU, CI]
     _lib = L
     return L
@@ -392,6 +396,55 @@ def conv_slots_plan(n, M, pitch, H, W, fh, fw, dil=1, pool=1):
     if steps[-1] >= n // 2:
         raise ValueError("conv_slots_plan: a tap's step reaches n/2")
     return ConvSlotsPlan(n, M, pitch, fh, fw, pool, steps, out_h, out_w, dil * pool)
+
+
+class DensePlanesPlan:
+    """What dense_planes_plan returns.  steps [R]: the distinct values (in_slots[p] - out_slots[o]) mod M, ascending; elements [R]: 3^step mod 2n
+    (crc_galois_elt_rows; step 0 is the element 1, which needs no key).  fold(W, t): the plaintext rows the steps take"""
+    def __init__(self, n, M, in_slots, out_slots):
+        self.n, self.M, self.in_slots, self.out_slots = n, M, list(in_slots), list(out_slots)
+        self.steps = sorted({(p - o) % M for p in self.in_slots for o in self.out_slots})
+        self.elements = [pow(3, s, 2 * n) for s in self.steps]
+
+    def fold(self, W, t, j=None):
+        """W [O][Cin][P] integers (any int64, taken mod t) -> slot rows [R][Cin][n] in [0, t) -- or [Cin][n] of the one step j, for a layer whose R Cin n integers
+        should not exist at once: for i mod M = in_slots[p], rows[j][c][i] = W[o][c][p] where out_slots[o] = (in_slots[p] - steps[j]) mod M; 0 where no such o
+        exists and at every other slot"""
+        W = np.asarray(W)
+        O, P = len(self.out_slots), len(self.in_slots)
+        if W.ndim != 3 or W.shape[0] != O or W.shape[2] != P or W.shape[1] < 1 or int(t) < 2:
+            raise ValueError("DensePlanesPlan.fold: weights must be [O][Cin][P] and t >= 2")
+        Wm = (W.astype(object) % int(t)).astype(np.int64)
+        at = {o: i for i, o in enumerate(self.out_slots)}
+
+        def one(step):
+            base = np.zeros((W.shape[1], self.M), dtype=np.int64)
+            for p, sp in enumerate(self.in_slots):
+                o = at.get((sp - step) % self.M)
+                if o is not None:
+                    base[:, sp] = Wm[o, :, p]
+            return np.tile(base, (1, self.n // self.M))
+        if j is not None:
+            return one(self.steps[j])
+        return np.stack([one(s) for s in self.steps])
+
+
+def dense_planes_plan(n, M, in_slots, out_slots):
+    """A dense layer behind packed channel planes, rotating its OUTPUTS: Cin ciphertexts x_c whose valid entries sit at the slots in_slots [P] of every period M
+    (tiled over both rows of n/2 slots: matvecSlots' contract; every other slot may hold junk), O outputs that land at out_slots [O] (an int O means 0 .. O - 1):
+        y = Sum_j rotate_rows( Sum_c rows[j][c] (.) x_c, steps[j] )   holds   Sum_c Sum_p W[o][c][p] x_c[in_slots[p]]   at out_slots[o]
+    and exactly 0 at every other slot of the period (rotate_rows' convention: after a rotation by r, slot i holds old slot (i + r) mod n/2).  The choice of
+    out_slots decides the number of steps.  Raises ValueError for M not a power of two <= n/2, an empty or duplicated slot list, a slot outside [0, M)"""
+    n, M = int(n), int(M)
+    if isinstance(out_slots, (int, np.integer)):
+        out_slots = range(int(out_slots))
+    in_slots, out_slots = [int(v) for v in in_slots], [int(v) for v in out_slots]
+    if n < 2 or n & (n - 1) or M < 1 or M & (M - 1) or M > n // 2:
+        raise ValueError("dense_planes_plan: M must be a power of two <= n/2")
+    for name, sl in (("in_slots", in_slots), ("out_slots", out_slots)):
+        if not sl or len(set(sl)) != len(sl) or min(sl) < 0 or max(sl) >= M:
+            raise ValueError(f"dense_planes_plan: {name} must be a non-empty list of distinct slots of [0, M)")
+    return DensePlanesPlan(n, M, in_slots, out_slots)
 
 
 def h5_read(path, name):
@@ -1145,6 +1198,35 @@ class Engine:
         elts = self._elts(elts); gs = self._elts(gs)
         _chk(self.L.crc_conv_slots_forms(self.c, self.p(d_x), in_form, count, Cin, _pu(gs), gs.size, self.p(d_w), Cout, self.p(d_cgk), _pu(elts), elts.size, dbc,
                                          self.p(d_y), out_form, self.p(d_work), self.stream), "crc_conv_slots_forms")
+
+    # ---- the dense layer over channel planes (crc_dense_planes_*): the outputs are rotated, one batched key switch with one key per step
+    def dense_planes_plan(self, M, in_slots, out_slots):
+        """binding.dense_planes_plan at this ring"""
+        return dense_planes_plan(self.n, M, in_slots, out_slots)
+
+    def galois_prepared_key_words(self, dbc=16):
+        return self.L.crc_galois_prepared_key_words(self.c, dbc)
+
+    def galois_prepare_keys(self, d_cgk, elts, d_pk=None, dbc=16):
+        """the prepared form of the conjugated keys d_cgk of elts, made once: returns d_pk [n_elts][galois_prepared_key_words] (allocated here unless given)"""
+        elts = self._elts(elts)
+        if d_pk is None:
+            d_pk = self.alloc(max(1, elts.size) * self.galois_prepared_key_words(dbc) * 8)
+        d_scratch = self.alloc(self.L.crc_evk_words(self.c, dbc) * 8)
+        _chk(self.L.crc_galois_prepare_keys_dev(self.c, self.p(d_cgk), _pu(elts), elts.size, dbc, self.p(d_pk), self.p(d_scratch), self.stream),
+             "crc_galois_prepare_keys_dev")
+        self.sync()                                                    # (the scratch is freed on return)
+        return d_pk
+
+    def dense_planes_work_bytes(self, count, Cin, R, dbc=16, prepared=False):
+        return self.L.crc_dense_planes_work_bytes(self.c, count, Cin, R, dbc, 1 if prepared else 0)
+
+    def dense_planes(self, d_x, count, Cin, gs, d_p_ntt, d_cgk, elts, d_y, d_work, d_pk=None, dbc=16, in_form=COEFF, out_form=COEFF):
+        """d_y [count] = Sum_j H_{gs[j]}( Sum_c P[j][c] (*) d_x[c] ); d_x [Cin][count], d_p_ntt [R][Cin][k][n]: NTT-form plaintext rows (plain_to_ntt); d_pk:
+        galois_prepare_keys of (d_cgk, elts), or None -- size d_work with prepared = d_pk is not None"""
+        elts = self._elts(elts); gs = self._elts(gs)
+        _chk(self.L.crc_dense_planes_forms(self.c, self.p(d_x), in_form, count, Cin, _pu(gs), gs.size, self.p(d_p_ntt), self.p(d_cgk), _pu(elts), elts.size,
+                                           self.p(d_pk) if d_pk is not None else None, dbc, self.p(d_y), out_form, self.p(d_work), self.stream), "crc_dense_planes_forms")
 
     # ---- ciphertext x ciphertext multiply and the degree-3 activation c3 x^3 + c2 x^2 + c1 x + c0 (crc_multiply* / crc_poly3_relin_forms)
     def multiply_relin_work_bytes(self, count, dbc=16):

@@ -1642,6 +1642,152 @@ extern "C" int crc_conv_slots_forms(crc_ctx *c, const uint64_t *d_x, int in_form
     if (out_form == CRC_COEFF) RUN(crc_ntt_inv(c, d_y, outs, 2, stream));
     return CRC_OK;
 }
+// ---- prepared keys that outlive a call: what k_relin64_prepare_keys leaves, per conjugated key, in a buffer of the caller's ----
+// Every hoisted entry point above prepares the fp64 form of its keys in pass 0 of every call (three launches per key); a layer with hundreds of keys prepares them
+// once.  d_pk [n_elts][crc_galois_prepared_key_words], d_scratch: crc_evk_words words
+extern "C" size_t crc_galois_prepared_key_words(const crc_ctx *c, int dbc) { return c && dbc_ok(dbc) && k_relin64_supported(c, dbc) ? k_relin64_keys_words(c, dbc) : 0; }
+extern "C" int crc_galois_prepare_keys_dev(crc_ctx *c, const uint64_t *d_cgk, const uint64_t *elts, int n_elts, int dbc, uint64_t *d_pk, uint64_t *d_scratch,
+                                           void *stream)
+{
+    CHECK_CTX(c);
+    if (!dbc_ok(dbc) || n_elts < 0 || (n_elts && (!elts || !d_cgk || !d_pk || !d_scratch)) || !aligned16(d_cgk) || !aligned16(d_pk) || !aligned16(d_scratch))
+        return CRC_ERR_INVALID_ARGUMENT;
+    for (int e = 0; e < n_elts; e++) if (!crc_galois_elt_valid(c, elts[e]) || elts[e] == 1) return CRC_ERR_INVALID_ARGUMENT;
+    if (!k_relin64_supported(c, dbc)) return CRC_ERR_UNSUPPORTED;
+    const size_t kw = crc_evk_words(c, dbc), pkw = k_relin64_keys_words(c, dbc);
+    if (ranges_overlap(d_cgk, 8 * kw * n_elts, d_pk, 8 * pkw * n_elts) || ranges_overlap(d_cgk, 8 * kw * n_elts, d_scratch, 8 * kw) ||
+        ranges_overlap(d_pk, 8 * pkw * n_elts, d_scratch, 8 * kw)) return CRC_ERR_INVALID_ARGUMENT;
+    for (int e = 0; e < n_elts; e++) RUN(k_relin64_prepare_keys(c, d_cgk + (size_t)e * kw, dbc, d_pk + (size_t)e * pkw, d_scratch, S(stream)));
+    return CRC_OK;
+}
+// ---- the dense layer over channel planes: y = Sum_j H_{gs[j]}( Sum_c P[j][c] (*) x[c] ), x [Cin][count], P [R][Cin][k][n] ----
+// The OUTPUTS are rotated, not the inputs: R key switches whatever Cin is.  Per pass of ch ciphertexts per channel: one forward transform of a coefficient-form
+// pass; the R inner sums u_j through galois_diag_mac_multi_kernel with every element 1 (GALOIS_DIAG_MAX channels per launch, the accumulate continuation); the
+// outer stage -- crc_diag_mac_bsgs_forms' giant stage -- over the keyed steps; galois_sum_permuted_kernel over all R (gs[j] = 1: u_j itself).  The outer stage on
+// the fp64 path runs in sub-batches of rb consecutive keyed steps: ONE inverse transform, (c0, 0, c1 (q/q_i)^-1), K1 over rb ch ciphertexts, then K2 with one key
+// per step (relin_mac_keyed_f64_kernel) and K3, whose results go over the u_j.  Where the fp64 key switch does not apply, or at planes_batch = 1, it runs step by
+// step through hoist_pass_head / hoist_switch exactly as the giant stage does.  Every step is an exact function on Z_q with canonical residues: the bits are those
+// of crc_multiply_plain_ntt + crc_add over c, crc_rotate_hoisted_forms per j, crc_add over j, at every setting and pass structure.
+// Work: [key pointers of the R steps][NTT copy of a coefficient-form pass, Cin ch][the R ch inner sums][coefficient copy of a sub-batch][its size-3 rows][prepared
+// keys: R, made by pass 0 -- with d_pk one, for the path that cannot use d_pk][scratch of the key switch].  A pass keeps (Cin + R) ch ciphertexts, so ch shrinks
+// with them as hoist_layout's does; rb ch <= square_chunk, at least one step of one ciphertext
+enum { PLANES_BATCH_DEFAULT = 2, DENSE_PLANES_MAX_CH = 4096 };
+static int planes_batch(const crc_ctx *c) { return c->tune.planes_batch ? c->tune.planes_batch : (int)PLANES_BATCH_DEFAULT; }
+struct PlanesWork { const u64 **kt; u64 *xh, *u, *xc, *x3, *kp, *rest; size_t step, rb, kpw; };
+static bool planes_counts_ok(size_t count, int Cin, int R)
+{
+    return Cin >= 1 && Cin <= DENSE_PLANES_MAX_CH && R >= 1 && R <= GALOIS_BSGS_MAX && count <= ((size_t)1 << 40);
+}
+static PlanesWork planes_layout(const crc_ctx *c, size_t count, int Cin, int R, int dbc, bool prepared, WorkArena &a)
+{
+    PlanesWork L{};
+    const size_t sq = square_chunk(c);
+    L.step = sq * HOIST_Z_PASSES / ((size_t)Cin + (size_t)R);
+    if (L.step > sq) L.step = sq;
+    if (L.step < 1) L.step = 1;
+    const size_t ch = count < L.step ? count : L.step;
+    L.rb = ch ? sq / ch : sq;                                          // steps per sub-batch of the outer stage: rb ch <= square_chunk
+    if (L.rb < 1) L.rb = 1;
+    if (L.rb > (size_t)R) L.rb = (size_t)R;
+    L.kpw = (k_relin_keys_words(c, dbc) + 31) & ~(size_t)31;
+    L.kt = a.take<const u64 *>((size_t)R);
+    L.xh = a.take<u64>((size_t)Cin * ch * crc_ct_words(c, 2));
+    L.u = a.take<u64>((size_t)R * ch * crc_ct_words(c, 2));
+    L.xc = a.take<u64>(L.rb * ch * crc_ct_words(c, 2));
+    L.x3 = a.take<u64>(L.rb * ch * crc_ct_words(c, 3));
+    L.kp = a.take<u64>((prepared ? 1 : (size_t)R) * L.kpw);
+    const size_t one = k_relin_work_words(c, ch, dbc), all = k_relin64_supported(c, dbc) ? k_relin64_work_words(c, L.rb * ch, dbc) : 0;
+    L.rest = a.take<u64>(one > all ? one : all);                        // (either setting of planes_batch, either key-switch path: a tuning switch does not change the size)
+    return L;
+}
+static size_t planes_bytes(const crc_ctx *c, size_t count, int Cin, int R, int dbc, bool prepared)
+{
+    if (!c || !dbc_ok(dbc) || !planes_counts_ok(count, Cin, R)) return 0;
+    WorkArena a;
+    planes_layout(c, count, Cin, R, dbc, prepared, a);
+    return a.bytes();
+}
+extern "C" size_t crc_dense_planes_work_bytes(const crc_ctx *c, size_t count, int Cin, int R, int dbc, int prepared)
+{
+    return planes_bytes(c, count, Cin, R, dbc, prepared != 0);
+}
+extern "C" int crc_dense_planes_forms(crc_ctx *c, const uint64_t *d_x, int in_form, size_t count, int Cin, const uint64_t *gs, int R, const uint64_t *d_p_ntt,
+                                      const uint64_t *d_cgk, const uint64_t *elts, int n_elts, const uint64_t *d_pk, int dbc, uint64_t *d_y, int out_form,
+                                      void *d_work, void *stream)
+{
+    CHECK_CTX(c);
+    if (!planes_counts_ok(count, Cin, R) || !d_p_ntt || !aligned16(d_p_ntt) || !aligned16(d_pk)) return CRC_ERR_INVALID_ARGUMENT;
+    const bool prepared = d_pk != nullptr;
+    const size_t total = (size_t)Cin * count, wb = planes_bytes(c, count, Cin, R, dbc, prepared), ctw = crc_ct_words(c, 2), rowp = (size_t)c->k * c->n;
+    const size_t xb = 8 * total * ctw, yb = 8 * count * ctw, pb = 8 * (size_t)R * Cin * rowp;
+    if (!hoist_args_ok(c, d_x, in_form, total, gs, R, d_cgk, elts, n_elts, dbc, d_y, count, out_form, d_work, wb)) return CRC_ERR_INVALID_ARGUMENT;
+    if (ranges_overlap(d_p_ntt, pb, d_y, yb) || ranges_overlap(d_p_ntt, pb, d_work, wb) || ranges_overlap(d_p_ntt, pb, d_x, xb)) return CRC_ERR_INVALID_ARGUMENT;
+    std::vector<int> at((size_t)R);
+    if (!hoist_keys(c, gs, R, elts, n_elts, at.data())) return CRC_ERR_INVALID_ARGUMENT;
+    bool keyed = false;                                                 // (no digits at all where every element is 1)
+    for (int j = 0; j < R; j++) keyed = keyed || at[j] >= 0;
+    const size_t pkw = k_relin64_keys_words(c, dbc), pkb = 8 * pkw * (size_t)n_elts;
+    if (prepared) {
+        if (keyed && n_elts == 0) return CRC_ERR_INVALID_ARGUMENT;
+        if (ranges_overlap(d_pk, pkb, d_x, xb) || ranges_overlap(d_pk, pkb, d_y, yb) || ranges_overlap(d_pk, pkb, d_p_ntt, pb) || ranges_overlap(d_pk, pkb, d_work, wb))
+            return CRC_ERR_INVALID_ARGUMENT;
+    }
+    if (count == 0) return CRC_OK;
+    const size_t kw = crc_evk_words(c, dbc);
+    WorkArena a(d_work);
+    const PlanesWork L = planes_layout(c, count, Cin, R, dbc, prepared, a);
+    const bool f64 = c->tune.relin_path != 1 && k_relin64_supported(c, dbc), batched = f64 && planes_batch(c) == 2, use_pk = f64 && prepared;
+    // the view hoist_pass_head / hoist_switch take: the prepared key of step j at kp + slot(j) kpw
+    HoistWork H{};
+    H.xc = L.xc; H.x3 = L.x3; H.rest = L.rest; H.step = L.step;
+    H.kp = use_pk ? const_cast<u64 *>(d_pk) : L.kp;                    // (d_pk is only read: the fp64 path never prepares into it)
+    H.kpw = use_pk ? pkw : L.kpw;
+    auto slot = [&](int j) { return use_pk ? at[j] : f64 || !prepared ? j : 0; };      // (!f64 with d_pk: the one slot, prepared again by every step)
+    if (batched && keyed) {
+        std::vector<int> slots((size_t)R, -1);                          // the pointer table is written on the device: the slots go as kernel arguments
+        for (int j = 0; j < R; j++) if (at[j] >= 0) slots[j] = slot(j);
+        RUN(k_relin64_key_table(H.kp, H.kpw, slots.data(), (size_t)R, L.kt, S(stream)));
+    }
+    std::vector<const u64 *> zs((size_t)R), zin((size_t)Cin);
+    const std::vector<u64> ones(GALOIS_DIAG_MAX, 1);
+    for (size_t o = 0; o < count; o += L.step) {
+        const size_t ch = pass_len(count, o, L.step), uj = ch * ctw;
+        for (int ci = 0; ci < Cin; ci++) zin[ci] = d_x + ((size_t)ci * count + o) * ctw;
+        if (in_form == CRC_COEFF) {                                     // one shared forward transform where the pass is contiguous, one per channel otherwise
+            if (ch == count) RUN(k_ntt_ct(c, false, d_x, L.xh, total, 2, false, S(stream), nullptr, 0, 0, 0));
+            else for (int ci = 0; ci < Cin; ci++) RUN(k_ntt_ct(c, false, zin[ci], L.xh + (size_t)ci * uj, ch, 2, false, S(stream), nullptr, 0, 0, 0));
+            for (int ci = 0; ci < Cin; ci++) zin[ci] = L.xh + (size_t)ci * uj;
+        }
+        for (int c0 = 0; c0 < Cin; c0 += GALOIS_DIAG_MAX) {
+            const int cn = Cin - c0 < GALOIS_DIAG_MAX ? Cin - c0 : (int)GALOIS_DIAG_MAX;
+            RUN(k_galois_diag_mac_multi(c, zin.data() + c0, ones.data(), c0, cn, Cin, d_p_ntt, R, ch, c0 != 0, L.u, S(stream)));
+        }
+        if (keyed && f64 && !use_pk && o == 0)                          // (the preparation borrows the scratch: before E is put there)
+            for (int j = 0; j < R; j++)
+                if (at[j] >= 0) RUN(k_relin64_prepare_keys(c, d_cgk + (size_t)at[j] * kw, dbc, L.kp + (size_t)j * L.kpw, L.rest, S(stream)));
+        for (int j0 = 0; j0 < R;) {
+            if (at[j0] < 0) { j0++; continue; }
+            int j1 = j0 + 1;                                            // a run of consecutive keyed steps, at most rb of them where they go as one batch
+            while (batched && j1 < R && at[j1] >= 0 && (size_t)(j1 - j0) < L.rb) j1++;
+            u64 *ub = L.u + (size_t)j0 * uj;
+            if (batched) {
+                const size_t cnt = (size_t)(j1 - j0) * ch;
+                RUN(k_ntt_ct(c, true, ub, L.xc, cnt, 2, false, S(stream), nullptr, 0, 0, 0));
+                RUN(k_galois_permute(c, L.xc, cnt, 1, false, L.x3, S(stream)));
+                RUN(k_relin64_digits(c, L.x3, 3, 2, cnt, dbc, L.rest, S(stream)));
+                RUN(k_relin64_from_digits_keyed(c, L.x3, 3, cnt, ch, dbc, ub, L.rest, L.kt + j0, S(stream), true));
+            } else {
+                RUN(hoist_pass_head(c, H, ub, CRC_NTT, ch, nullptr, 0, d_cgk, dbc, f64, false, stream));
+                RUN(hoist_switch(c, H, ch, slot(j0), at[j0], d_cgk, dbc, f64, prepared || o == 0, ub, stream));
+            }
+            j0 = j1;
+        }
+        for (int j = 0; j < R; j++) zs[j] = L.u + (size_t)j * uj;
+        RUN(k_galois_sum_permuted(c, zs.data(), gs, R, ch, false, d_y + o * ctw, S(stream)));
+    }
+    if (out_form == CRC_COEFF) RUN(crc_ntt_inv(c, d_y, count, 2, stream));
+    return CRC_OK;
+}
 extern "C" int crc_square_relin(crc_ctx *c, const uint64_t *d_x, size_t count, const uint64_t *d_evk, int dbc, uint64_t *d_y, void *d_work, void *stream)
 {
     return crc_square_relin_forms(c, d_x, CRC_COEFF, count, d_evk, dbc, d_y, CRC_COEFF, d_work, stream);

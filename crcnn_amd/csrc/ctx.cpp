@@ -174,6 +174,7 @@ static void read_tuning(CrcTuning &t)
     t.hoist_pool = geti("CRC_HOIST_POOL", 1) ? 1 : 0;
     { const int v = (int)geti("CRC_HOIST_RT", 0); t.hoist_rt = v == 1 || v == 2 ? v : 0; }
     { const int v = (int)geti("CRC_BSGS_JT", 0); t.bsgs_jt = v == 1 || v == 2 ? v : 0; }
+    { const int v = (int)geti("CRC_PLANES_BATCH", 0); t.planes_batch = v == 1 || v == 2 ? v : 0; }
     { const int v = (int)geti("CRC_CONV_JT", 0); t.conv_jt = v == 2 || v == 4 || v == 8 ? v : 0; }
     t.conv1_box = geti("CRC_CONV1_BOX", 1) ? 1 : 0;
     { const long long v = geti("CRC_CONV1_PASS_BYTES", 0); t.conv1_pass_bytes = v > 0 ? v : 0; }
@@ -210,6 +211,7 @@ extern "C" int crc_ctx_set_tuning(crc_ctx *c, const char *name, long long value)
     else if (s == "hoist_pool") t.hoist_pool = value ? 1 : 0;
     else if (s == "hoist_rt") t.hoist_rt = value == 1 || value == 2 ? (int)value : 0;
     else if (s == "bsgs_jt") t.bsgs_jt = value == 1 || value == 2 ? (int)value : 0;
+    else if (s == "planes_batch") t.planes_batch = value == 1 || value == 2 ? (int)value : 0;
     else if (s == "conv_jt") t.conv_jt = value == 2 || value == 4 || value == 8 ? (int)value : 0;
     else if (s == "conv1_box") t.conv1_box = value ? 1 : 0;
     else if (s == "conv1_pass_bytes") t.conv1_pass_bytes = value > 0 ? value : 0;

@@ -110,6 +110,7 @@ struct CrcTuning {
     int conv1_box = 1;            // CRC_CONV1_BOX=0: crc_plan_conv1_box always answers no (the hoisted pair's one-channel layer keeps the enlarged window)
     int hoist_rt = 0;             // CRC_HOIST_RT: keys per digit load in the hoisted rotations' K2 -- 0: the default (abi.hip: hoist_rt), 1: one launch per key, 2: relin_mac_multi_f64_kernel
     int bsgs_jt = 0;              // CRC_BSGS_JT: the inner sums of crc_diag_mac_bsgs_forms -- 0: the default (abi.hip: bsgs_jt), 1: one galois_diag_mac_kernel launch per giant index, 2: galois_diag_mac_multi_kernel
+    int planes_batch = 0;         // CRC_PLANES_BATCH: the outer stage of crc_dense_planes_forms on the fp64 path -- 0: the default (abi.hip: planes_batch), 1: one key switch per step, 2: relin_mac_keyed_f64_kernel over sub-batches of steps
     int conv_jt = 0;              // CRC_CONV_JT: output channels per thread of galois_conv_mac_kernel (crc_conv_slots_forms) -- 0: the default (abi.hip: conv_jt), 2 | 4 | 8: that instantiation
     int hoist_pool = 1;           // CRC_HOIST_POOL=0: crc_plan_hoist_pool always answers no (A/B of the hoisted against the weight-folded conv + pool pair in one build)
     int conv1_form = 0;           // CRC_CONV1_FORM=1: plane-major image (mfma_conv1_kernel), 2: pixel-major (mfma_conv1_kernel_px), 0: by shape; set BEFORE the weights are packed

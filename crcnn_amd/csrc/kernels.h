@@ -56,6 +56,12 @@ int k_relin64_from_digits(crc_ctx *c, const u64 *x3, int add_size, size_t cnt, i
 size_t k_relin64_work_words_multi(const crc_ctx *c, size_t cnt, int dbc, int keys);
 int k_relin64_from_digits2(crc_ctx *c, const u64 *x3, int add_size, size_t cnt, int dbc, u64 *y0, u64 *y1, u64 *work, const u64 *kp0, const u64 *kp1,
                            hipStream_t st, bool out_ntt);
+// K2 + K3 with one prepared key per step of the batch (relin_mac_keyed_f64_kernel): cnt = steps x per_key ciphertexts, those of step j under kp_table[j] -- a DEVICE
+// array of pointers to prepared keys; E over all cnt is there; work: k_relin64_work_words(cnt).  The bits of k_relin64_from_digits per step
+int k_relin64_from_digits_keyed(crc_ctx *c, const u64 *x3, int add_size, size_t cnt, size_t per_key, int dbc, u64 *y, u64 *work, const u64 *const *kp_table,
+                                hipStream_t st, bool out_ntt);
+// its kp_table, written by a kernel: table[j] = base + slots[j] kpw (words), null where slots[j] < 0; `slots` is a host array, consumed before the call returns
+int k_relin64_key_table(const u64 *base, size_t kpw, const int *slots, size_t steps, const u64 **table, hipStream_t st);
 // the same terms in a kernel of their own (kernels.hip: poly2_tail_kernel), in place on y [planes][xo][yo]
 int k_poly2_tail(crc_ctx *c, u64 *y, const u64 *xh, size_t planes, const Window &w, const u64 *p2, const u64 *p1, const u64 *p0, hipStream_t st);
 int k_square(crc_ctx *c, const u64 *x, size_t cnt, u64 *y3, u64 *work, hipStream_t st, bool in_ntt = false, bool premul_c2 = false);

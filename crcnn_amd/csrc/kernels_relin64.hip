@@ -344,6 +344,88 @@ __global__ void __launch_bounds__(256, 4) relin_mac_multi_f64_kernel(const doubl
                 for (int pj = 0; pj < PJ; pj++) A[r * a_stride + (((ct0 + c) * 2 * K + pj0 + pj) * CRC_NF64 + m) * nn + s] = acc[r][c][pj];
 }
 
+// K2 with ONE KEY PER STEP of the batch (the dense layer over channel planes rotates its outputs: R inner sums, each switched under its own key, in one launch):
+// the batch is [steps][per] ciphertexts, ciphertext i = j per + ct takes the prepared key keys[j] -- a table of pointers in device memory, R runs into the hundreds.
+//     A[i][pj][m][s] = Sum_g Kf_{keys[j]}[g][pj][m][s] E[i][g][m][s],  g ascending, every product f64_mulmod: relin_mac_f64_kernel's sums, the same doubles.
+// CT ciphertexts OF ONE STEP share every key value a thread loads; a ciphertext index past the step's `per` loads nothing and stores nothing.  At per = 1 nothing
+// is shared at all and the kernel is a stream of key values from HBM, every one used once: CT = 1, and SV = 2 slots per thread (16-byte loads; n >= 512).  The digit
+// values of g + 1 are requested before the products of digit g are formed, as above.
+// Index order: the ciphertext groups of a step fastest, so that the workgroups resident together and working on one key read the SAME key tile (D x PJ values
+// for 256 SV slots) and each tile comes from HBM once; the step slowest, so that at most a few keys are being read at any time and no key is touched again once its
+// workgroups have gone -- every prepared key is streamed exactly once
+template <int SV> struct f64_vec { double v[SV]; };
+template <int SV> __device__ __forceinline__ f64_vec<SV> f64_vec_load(const double *p)
+{
+    f64_vec<SV> r;
+    if constexpr (SV == 2) { const d2 t = *reinterpret_cast<const d2 *>(p); r.v[0] = t.x; r.v[1] = t.y; }
+    else r.v[0] = *p;
+    return r;
+}
+template <int K, int CT, int PJ, int SV>
+__global__ void __launch_bounds__(256, 4) relin_mac_keyed_f64_kernel(const double *E, const double *const *keys, double *A, F64Params fp, int n, int D,
+    unsigned steps, unsigned per)
+{
+    static_assert(CT * PJ * SV <= 36 && (SV == 1 || SV == 2), "the tile must fit the look-ahead path's register budget");
+    constexpr int PJS = 2 * K / PJ;
+    const int sblocks = n / ((int)blockDim.x * SV);
+    const unsigned groups = (per + CT - 1) / CT;
+    unsigned b = blockIdx.x;
+    const unsigned ct0 = (b % groups) * CT; b /= groups;
+    const int s = ((b % sblocks) * blockDim.x + threadIdx.x) * SV; b /= sblocks;
+    const int pj0 = (b % PJS) * PJ; b /= PJS;
+    const int m = b % CRC_NF64; b /= CRC_NF64;
+    const unsigned j = b;                                                 // the step: uniform over the workgroup, so is its key pointer
+    if (j >= steps) return;
+    const double *Kf = keys[j];
+    const size_t i0 = (size_t)j * per + ct0;                              // first ciphertext of the tile in the batch
+    const F64Mod md = fp.m[m];
+    double acc[CT][PJ][SV];
+#pragma unroll
+    for (int c = 0; c < CT; c++)
+#pragma unroll
+        for (int pj = 0; pj < PJ; pj++)
+#pragma unroll
+            for (int v = 0; v < SV; v++) acc[c][pj][v] = 0.0;
+    const size_t nn = (size_t)n;
+    f64_vec<SV> e[CT];
+    auto fetch = [&](int g, f64_vec<SV> (&ev)[CT]) {
+#pragma unroll
+        for (int c = 0; c < CT; c++) {
+            if (ct0 + c < per) ev[c] = f64_vec_load<SV>(E + (((i0 + c) * D + g) * CRC_NF64 + m) * nn + s);
+            else
+#pragma unroll
+                for (int v = 0; v < SV; v++) ev[c].v[v] = 0.0;
+        }
+    };
+    fetch(0, e);
+    for (int g = 0; g < D; g++) {
+        f64_vec<SV> en[CT];
+        if (g + 1 < D) fetch(g + 1, en);
+        const double *kr = Kf + (((size_t)g * 2 * K + pj0) * CRC_NF64 + m) * nn + s;
+#pragma unroll
+        for (int pj = 0; pj < PJ; pj++) {
+            const f64_vec<SV> kv = f64_vec_load<SV>(kr + (size_t)pj * CRC_NF64 * nn);
+#pragma unroll
+            for (int c = 0; c < CT; c++)
+#pragma unroll
+                for (int v = 0; v < SV; v++) acc[c][pj][v] += f64_mulmod(kv.v[v], e[c].v[v], md);
+        }
+        if (g + 1 < D) {
+#pragma unroll
+            for (int c = 0; c < CT; c++) e[c] = en[c];
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < CT; c++)
+        if (ct0 + c < per)
+#pragma unroll
+            for (int pj = 0; pj < PJ; pj++) {
+                double *dst = A + (((i0 + c) * 2 * K + pj0 + pj) * CRC_NF64 + m) * nn + s;
+                if constexpr (SV == 2) *reinterpret_cast<d2 *>(dst) = d2{acc[c][pj][0], acc[c][pj][1]};
+                else *dst = acc[c][pj][0];
+            }
+}
+
 // ---- K3: inverse transforms, CRT lift, mod q_j, + (c0, c1) --------------------------------------------------------------------------------------------------
 // A [ct][poly k + j][m][n]; x3: size-`add_size` ciphertexts whose polys 0, 1 are added (coefficient form); y [ct][2][k][n].  The first prime's result waits in
 // registers (NPT points per thread, reduced) while the image serves the second transform -- round 3 parked it in its own row of A (6 rows written and read back
@@ -896,6 +978,75 @@ int k_relin64_from_digits2(crc_ctx *c, const u64 *x3, int add_size, size_t cnt, 
            : RB == 4 ? relin64_tail<4, 16>(c, Ar, x3, add_size, ys[r], cnt, out_ntt, st, nullptr, nullptr, nullptr)
                      : relin64_tail<5, 32>(c, Ar, x3, add_size, ys[r], cnt, out_ntt, st, nullptr, nullptr, nullptr);
         if (rc) return rc;
+    }
+    return CRC_OK;
+}
+
+// K2 + K3 with one prepared key per STEP of the batch (relin_mac_keyed_f64_kernel): the cnt ciphertexts are [cnt / per_key][per_key], the ciphertexts of step j take
+// the key kp_table[j] -- a DEVICE array of cnt / per_key pointers to prepared keys (k_relin64_prepare_keys).  E is there (k_relin64_digits over all cnt); y what
+// k_relin64_from_digits gives for every step with its key, bit for bit.  work: k_relin64_work_words(cnt), laid out as there
+template <int K>
+static int relin64_mac_keyed(crc_ctx *c, const double *E, const double *const *keys, double *A, int D, size_t steps, size_t per, hipStream_t st)
+{
+    constexpr int PJ = 2 * K <= 8 ? 2 * K : (2 * K) % 8 == 0 ? 8 : (2 * K) % 6 == 0 ? 6 : (2 * K) % 5 == 0 ? 5 : 7, PJS = 2 * K / PJ;
+    static_assert(PJ * PJS == 2 * K, "key columns must split evenly");
+    const int threads = c->n < 256 ? c->n : 256;
+    const int ct = per == 1 ? 1 : per == 2 ? 2 : 4, sv = ct == 1 && c->n >= 512 ? 2 : 1;
+    const size_t groups = (per + ct - 1) / ct, blocks = steps * groups * CRC_NF64 * PJS * (c->n / (threads * sv));
+    if (blocks > 0x7fffffffull || steps > 0xffffffffull || per > 0xffffffffull) return CRC_ERR_INVALID_ARGUMENT;
+#define KEYED(CT, SV) hipLaunchKernelGGL((relin_mac_keyed_f64_kernel<K, CT, PJ, SV>), dim3((unsigned)blocks), dim3(threads), 0, st, E, keys, A, c->f64, c->n, D, \
+        (unsigned)steps, (unsigned)per)
+    if (ct == 1 && sv == 2) KEYED(1, 2);
+    else if (ct == 1) KEYED(1, 1);
+    else if (ct == 2) KEYED(2, 1);
+    else KEYED(4, 1);
+#undef KEYED
+    HIPCHK(hipGetLastError());
+    return CRC_OK;
+}
+int k_relin64_from_digits_keyed(crc_ctx *c, const u64 *x3, int add_size, size_t cnt, size_t per_key, int dbc, u64 *y, u64 *work, const u64 *const *kp_table,
+                                hipStream_t st, bool out_ntt)
+{
+    if (cnt == 0) return CRC_OK;
+    if (!k_relin64_supported(c, dbc)) return CRC_ERR_UNSUPPORTED;
+    if (per_key < 1 || cnt % per_key || !kp_table) return CRC_ERR_INVALID_ARGUMENT;
+    const size_t n = c->n;
+    int D = 0;
+    for (int i = 0; i < c->k; i++) D += evk_digits(c->q[i], dbc);
+    double *E = reinterpret_cast<double *>(work), *A = E + cnt * D * CRC_NF64 * n;
+    const double *const *keys = reinterpret_cast<const double *const *>(kp_table);
+    int rc;
+    switch (c->k) {
+#define MACK(KV) case KV: rc = relin64_mac_keyed<KV>(c, E, keys, A, D, cnt / per_key, per_key, st); break;
+    MACK(1) MACK(2) MACK(3) MACK(4) MACK(5) MACK(6) MACK(7) MACK(8)
+#undef MACK
+    default: return CRC_ERR_UNSUPPORTED;
+    }
+    if (rc) return rc;
+    const int RB = f64_radix(c);
+    return RB == 3 ? relin64_tail<3, 16>(c, A, x3, add_size, y, cnt, out_ntt, st, nullptr, nullptr, nullptr)
+         : RB == 4 ? relin64_tail<4, 16>(c, A, x3, add_size, y, cnt, out_ntt, st, nullptr, nullptr, nullptr)
+                   : relin64_tail<5, 32>(c, A, x3, add_size, y, cnt, out_ntt, st, nullptr, nullptr, nullptr);
+}
+
+// kp_table for k_relin64_from_digits_keyed, built on the device: table[j] = base + slot[j] kpw words, null where slot[j] < 0 (a step without a key).  The slots
+// travel as kernel arguments, KEY_TABLE_MAX per launch, as the pointer tables of the galois kernels do: no host memory is read after the call returns
+enum { KEY_TABLE_MAX = 256 };
+struct KeyTableSlots { int slot[KEY_TABLE_MAX]; };
+__global__ void __launch_bounds__(KEY_TABLE_MAX) relin_key_table_kernel(const u64 *base, size_t kpw, KeyTableSlots s, int cnt, const u64 **table)
+{
+    const int i = threadIdx.x;
+    if (i < cnt) table[i] = s.slot[i] < 0 ? nullptr : base + (size_t)s.slot[i] * kpw;
+}
+int k_relin64_key_table(const u64 *base, size_t kpw, const int *slots, size_t steps, const u64 **table, hipStream_t st)
+{
+    if (steps && (!base || !slots || !table)) return CRC_ERR_INVALID_ARGUMENT;
+    for (size_t j0 = 0; j0 < steps; j0 += KEY_TABLE_MAX) {
+        KeyTableSlots s{};
+        const int cnt = steps - j0 < KEY_TABLE_MAX ? (int)(steps - j0) : (int)KEY_TABLE_MAX;
+        for (int i = 0; i < cnt; i++) s.slot[i] = slots[j0 + i];
+        hipLaunchKernelGGL(relin_key_table_kernel, dim3(1), dim3(KEY_TABLE_MAX), 0, st, base, kpw, s, cnt, table + j0);
+        HIPCHK(hipGetLastError());
     }
     return CRC_OK;
 }

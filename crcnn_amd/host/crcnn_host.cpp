@@ -30,6 +30,7 @@ shared_ptr<DeviceBuffer> ev_keys16;
 vector<uint64_t> galois_elts, galois_keys_host;
 static shared_ptr<DeviceBuffer> g_galois_keys;              // the key blobs of galois_elts, dbc g_galois_dbc, resident in HBM
 static shared_ptr<DeviceBuffer> g_galois_ckeys;             // their conjugated blobs (crc_galois_conjugate_keys_dev): the keys of the hoisted rotations
+static shared_ptr<DeviceBuffer> g_galois_pkeys;             // their prepared form (crc_galois_prepare_keys_dev), made by the first densePlanes that can use it
 static int g_galois_dbc = 0;
 static bool g_det = false;                                  // setDeterministicSeed(): tests / bench only
 static uint64_t g_det_seed = 0;
@@ -344,7 +345,7 @@ static const uint64_t *deviceKey(shared_ptr<DeviceBuffer> &d, uint64_t &fp, cons
 void delParameters()
 {
     ev_keys16.reset();
-    g_galois_keys.reset(); g_galois_ckeys.reset(); galois_elts.clear(); galois_keys_host.clear(); g_galois_dbc = 0;
+    g_galois_keys.reset(); g_galois_ckeys.reset(); g_galois_pkeys.reset(); galois_elts.clear(); galois_keys_host.clear(); g_galois_dbc = 0;
     g_d_sk.reset(); g_d_pk.reset();
     g_scratch.reset(); g_wltile.reset(); g_xltile.reset();
     g_pool.flush();
@@ -656,6 +657,7 @@ void generateGaloisKeys(int dbc, vector<uint64_t> elts)
                                                             (uint64_t *)g_galois_ckeys->ptr + e * kw, stream()), "crc_galois_conjugate_keys_dev");
     chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
     galois_elts = std::move(elts); galois_keys_host = std::move(keys); g_galois_dbc = dbc;
+    g_galois_pkeys.reset();
 }
 void generateGaloisKeys(int dbc)
 {
@@ -881,6 +883,99 @@ ciphertext3D convSlots(const ciphertext3D &t, const vector<int64_t> &weights, in
                              galois_elts.data(), (int)galois_elts.size(), dbc, out.data(), out_form, g_scratch->ptr, stream()), "convSlots");
     chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");           // (the weights' buffer goes out of scope here)
     if (og) { *og = SlotPlanes(); og->M = g.M; og->pitch = g.pitch; og->H = P.out_h; og->W = P.out_w; og->dil = P.out_dil; }
+    return out;
+}
+// ---- the dense layer over channel planes: the outputs are rotated, one batched key switch with one key per step ------------
+static DensePlanesPlan densePlanesPlan(int M, const vector<int> &in_slots, int O, const vector<int> &out_slots)
+{
+    vector<int> outs = out_slots;
+    if (outs.empty()) for (int o = 0; o < O; o++) outs.push_back(o);    // the default: output o at slot o
+    DensePlanesPlan P;
+    if (O < 1 || (int)outs.size() != O || !crc_dense_planes_plan(N(), M, in_slots, outs, P))
+        throw invalid_argument("densePlanes: M must be a power of two <= n/2, both slot lists distinct slots of [0, M), O of them for the outputs");
+    return P;
+}
+vector<int> densePlanesInSlots(const SlotPlanes &g)
+{
+    if (g.M < 1 || g.pitch < 1 || g.H < 1 || g.W < 1 || g.dil < 1 || g.W > g.pitch || (long long)g.dil * ((long long)(g.H - 1) * g.pitch + g.W - 1) >= g.M)
+        throw invalid_argument("densePlanes: the plane does not fit its period");
+    vector<int> out;
+    for (int r = 0; r < g.H; r++) for (int c = 0; c < g.W; c++) out.push_back(g.dil * (r * g.pitch + c));
+    return out;
+}
+vector<uint64_t> densePlanesElements(int M, const vector<int> &in_slots, int O, const vector<int> &out_slots)
+{
+    const DensePlanesPlan P = densePlanesPlan(M, in_slots, O, out_slots);
+    vector<uint64_t> out;
+    for (uint64_t e : P.elements) if (e != 1) out.push_back(e);         // (distinct steps below n/2: distinct elements)
+    return out;
+}
+vector<uint64_t> densePlanesElements(const SlotPlanes &g, int O, const vector<int> &out_slots) { return densePlanesElements(g.M, densePlanesInSlots(g), O, out_slots); }
+// the prepared form of the keys of the set, one slot per key of the set (crc_dense_planes_forms indexes d_pk as it does elts), kept until the keys change.  A slot
+// is filled when a layer first asks for its element `gs`: the keys of other layers (the convolution's) are never prepared.  Null where the fp64 key switch does not
+// take these parameters
+static const uint64_t *preparedGaloisKeys(int dbc, const vector<uint64_t> &gs)
+{
+    static vector<char> done;                                           // per key of the set: its slot is filled
+    const size_t pkw = crc_galois_prepared_key_words(ctx(), dbc), kw = crc_evk_words(ctx(), dbc);
+    if (!pkw || !g_galois_ckeys || galois_elts.empty()) return nullptr;
+    if (!g_galois_pkeys) {
+        g_galois_pkeys = make_shared<DeviceBuffer>(galois_elts.size() * pkw * 8 + 8);
+        done.assign(galois_elts.size(), 0);
+    }
+    shared_ptr<DeviceBuffer> scratch;
+    for (uint64_t g : gs) {
+        const size_t e = find(galois_elts.begin(), galois_elts.end(), g) - galois_elts.begin();
+        if (g == 1 || e == galois_elts.size() || done[e]) continue;      // (a missing key is the entry point's refusal)
+        if (!scratch) scratch = make_shared<DeviceBuffer>(kw * 8);
+        chk(crc_galois_prepare_keys_dev(ctx(), (const uint64_t *)g_galois_ckeys->ptr + e * kw, &galois_elts[e], 1, dbc, (uint64_t *)g_galois_pkeys->ptr + e * pkw,
+                                        (uint64_t *)scratch->ptr, stream()), "crc_galois_prepare_keys_dev");
+        done[e] = 1;
+    }
+    if (scratch) chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");     // (the scratch goes out of scope here)
+    return (const uint64_t *)g_galois_pkeys->ptr;
+}
+size_t preparedGaloisKeyBytes() { return g_galois_pkeys ? g_galois_pkeys->bytes : 0; }
+ciphertext3D densePlanes(const ciphertext3D &t, const vector<int64_t> &W, int O, int M, const vector<int> &in_slots, const vector<int> &out_slots, int out_form)
+{
+    if (!crc_slots_supported(ctx())) throw logic_error("encryption parameters do not support batching");
+    const DensePlanesPlan P = densePlanesPlan(M, in_slots, O, out_slots);
+    const vector<uint64_t> gs = hoistedElements("densePlanes", t, P.steps, out_form);
+    if (t.B != 1 || t.xd != 1 || t.yd != 1) throw invalid_argument("densePlanes: a tensor [1][zd][1][1] of channel planes (convSlots' result, or a vector)");
+    const int Cin = (int)t.count(), R = (int)P.steps.size(), n = N(), k = crc_ctx_k(ctx()), dbc = g_galois_dbc ? g_galois_dbc : 16;
+    if (W.size() != (size_t)O * Cin * in_slots.size()) throw invalid_argument("densePlanes: weights must be [O][Cin][P]");
+    const uint64_t *d_pk = preparedGaloisKeys(dbc, gs);
+    if (!crc_dense_planes_work_bytes(ctx(), 1, Cin, R, dbc, d_pk != nullptr)) throw invalid_argument("densePlanes: too many channels or steps");
+    // the rows a step at a time: fold, compose on the device, transform -- the R Cin n integers never exist at once on the host
+    const size_t rowp = (size_t)k * n;
+    DeviceBuffer d_v((size_t)Cin * n * 8), d_pl((size_t)Cin * n * 8), d_p((size_t)R * Cin * rowp * 8);
+    vector<int64_t> rows;
+    for (int j = 0; j < R; j++) {
+        if (!crc_dense_planes_fold_step(P, W, Cin, (int64_t)g_plain_modulus, j, rows)) throw invalid_argument("densePlanes: weights must be [O][Cin][P]");
+        chk(crc_memcpy_h2d(ctx(), d_v.ptr, rows.data(), rows.size() * 8, stream()), "crc_memcpy_h2d");
+        chk(crc_slots_compose_dev(ctx(), (const int64_t *)d_v.ptr, Cin, n, n, 1, (uint64_t *)d_pl.ptr, stream()), "crc_slots_compose_dev");
+        chk(crc_plain_to_ntt(ctx(), (const uint64_t *)d_pl.ptr, Cin, (uint64_t *)d_p.ptr + (size_t)j * Cin * rowp, stream()), "crc_plain_to_ntt");
+        chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");       // (the next step writes `rows` again)
+    }
+    ciphertext3D out(1, 1, 1, 1, out_form);
+    ensure(g_scratch, crc_dense_planes_work_bytes(ctx(), 1, Cin, R, dbc, d_pk != nullptr));
+    chk(crc_dense_planes_forms(ctx(), t.data(), t.form, 1, Cin, gs.data(), R, (const uint64_t *)d_p.ptr, g_galois_ckeys ? (const uint64_t *)g_galois_ckeys->ptr : nullptr,
+                               galois_elts.data(), (int)galois_elts.size(), d_pk, dbc, out.data(), out_form, g_scratch->ptr, stream()), "densePlanes");
+    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");           // (the rows' buffer goes out of scope here)
+    return out;
+}
+ciphertext3D densePlanes(const ciphertext3D &t, const vector<int64_t> &W, int O, const SlotPlanes &g, const vector<int> &out_slots, int out_form)
+{
+    return densePlanes(t, W, O, g.M, densePlanesInSlots(g), out_slots, out_form);
+}
+vector<vector<int64_t>> decryptVector(const ciphertext3D &t, const vector<int> &out_slots)
+{
+    int top = 0;
+    for (int s : out_slots) { if (s < 0 || s >= N()) throw invalid_argument("decryptVector: a slot outside the ring"); top = s > top ? s : top; }
+    if (out_slots.empty()) throw invalid_argument("decryptVector: no slots");
+    const vector<vector<int64_t>> v = decryptSlots(t, top + 1);        // [slots][count]
+    vector<vector<int64_t>> out(t.count());
+    for (size_t z = 0; z < out.size(); z++) for (int s : out_slots) out[z].push_back(v[(size_t)s][z]);
     return out;
 }
 vector<floatCube> decryptImages(const ciphertext3D &t)

@@ -218,6 +218,24 @@ std::vector<std::vector<int64_t>> decryptPlanes(const ciphertext3D &t, const Slo
 ciphertext3D convSlots(const ciphertext3D &t, const std::vector<int64_t> &weights, int Cout, const SlotPlanes &g, SlotPlanes *out = nullptr, int out_form = CRC_COEFF);
 // the Galois elements of the layer's taps without the element 1, each once (at most (fh + pool - 1)(fw + pool - 1) - 1 keys); std::invalid_argument as convSlots
 std::vector<uint64_t> convSlotsElements(const SlotPlanes &g);
+// The dense layer behind the last packed convolution (crc_dense_planes_forms): t [1][Cin][1][1] holds Cin planes whose valid entries sit at in_slots [P] of every
+// period M (the H x W pixels of a SlotPlanes: densePlanesInSlots; every other slot may hold junk), W [O][Cin][P] are integer weights (any int64, taken mod t).  The
+// result [1][1][1][1] holds Sum_c Sum_p W[o][c][p] x_c[in_slots[p]] at slot out_slots[o] of every period (default: o) and exactly 0 at every other slot -- a clean
+// vector, so the same call at Cin = 1 with in_slots = the previous out_slots is the next dense layer.  The OUTPUTS are rotated: one key switch per distinct value
+// of (in_slots[p] - out_slots[o]) mod M whatever Cin is, so the choice of out_slots decides the cost (crcnn_amd/host/diag_plan.h).  The keys of
+// densePlanesElements must be in the set (generateGaloisKeys(dbc, elements)); the prepared form of a key is made when a layer first uses it and kept until the keys
+// change -- the buffer has a slot for every key of the set (preparedGaloisKeyBytes), the keys of other layers are never prepared.  Exceptions as matvecSlots: std::logic_error without batching, std::invalid_argument for lists the planner refuses, a weight count that
+// is not O Cin P, a tensor that is not [1][zd][1][1], a missing key ("galois key not present") or a form other than CRC_COEFF / CRC_NTT.
+ciphertext3D densePlanes(const ciphertext3D &t, const std::vector<int64_t> &W, int O, const SlotPlanes &g, const std::vector<int> &out_slots = {}, int out_form = CRC_COEFF);
+ciphertext3D densePlanes(const ciphertext3D &t, const std::vector<int64_t> &W, int O, int M, const std::vector<int> &in_slots, const std::vector<int> &out_slots = {},
+                         int out_form = CRC_COEFF);
+std::vector<int> densePlanesInSlots(const SlotPlanes &g);
+// the Galois elements of the layer's steps without the element 1, each once; std::invalid_argument as densePlanes
+std::vector<uint64_t> densePlanesElements(const SlotPlanes &g, int O, const std::vector<int> &out_slots = {});
+std::vector<uint64_t> densePlanesElements(int M, const std::vector<int> &in_slots, int O, const std::vector<int> &out_slots = {});
+size_t preparedGaloisKeyBytes();
+// the integers at out_slots of every ciphertext of t: [count][out_slots.size()]
+std::vector<std::vector<int64_t>> decryptVector(const ciphertext3D &t, const std::vector<int> &out_slots);
 
 // ---- layers (CrCNN/src/layer.h:10-31) ------------------------------------------------------------------------------
 class Layer {

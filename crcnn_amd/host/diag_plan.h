@@ -124,3 +124,74 @@ inline bool crc_conv_slots_fold(const ConvSlotsPlan &P, const std::vector<int64_
     out = o;
     return true;
 }
+
+// ---- the dense layer over channel planes (densePlanes; crc_dense_planes_forms) ----
+// Cin ciphertexts x_c whose valid entries sit at the slots in_slots [P] of every period M (tiled over both rows of n/2 slots: matvecSlots' contract; every other
+// slot may hold junk), O outputs that land at the slots out_slots [O].  The OUTPUTS are rotated (rotate_rows' convention: after a rotation by r, slot i holds
+// old slot (i + r) mod n/2):
+//     y = Sum_j rotate_rows( Sum_c rows[j][c] (.) x_c, steps[j] ),   steps: the distinct values (in_slots[p] - out_slots[o]) mod M, ascending,
+//     rows[j][c][i] = W[o][c][p]  for i mod M = in_slots[p] where out_slots[o] = (in_slots[p] - steps[j]) mod M;  0 where no such o exists and at every other slot
+// so that y holds Sum_c Sum_p W[o][c][p] x_c[in_slots[p]] at out_slots[o] and exactly 0 at every other slot of the period: one key switch per step whatever Cin
+// is.  The caller chooses out_slots, and the choice decides the number of steps.
+struct DensePlanesPlan {
+    int n = 0, M = 0;
+    std::vector<int> in_slots, out_slots;
+    std::vector<int> steps;                  // [R] ascending; step 0 is the element 1, which needs no key
+    std::vector<uint64_t> elements;          // [R] 3^step mod 2n (crc_galois_elt_rows)
+    std::vector<int> out_at;                 // [M] the output whose slot this is, or -1
+};
+// false (P untouched) for M not a power of two <= n/2, an empty or duplicated slot list, a slot outside [0, M)
+inline bool crc_dense_planes_plan(int n, int M, const std::vector<int> &in_slots, const std::vector<int> &out_slots, DensePlanesPlan &P)
+{
+    if (n < 2 || (n & (n - 1)) || M < 1 || (M & (M - 1)) || M > n / 2 || in_slots.empty() || out_slots.empty()) return false;
+    DensePlanesPlan Q;
+    Q.n = n; Q.M = M; Q.in_slots = in_slots; Q.out_slots = out_slots;
+    Q.out_at.assign((size_t)M, -1);
+    std::vector<char> in_seen((size_t)M, 0), used((size_t)M, 0);
+    for (int s : in_slots) { if (s < 0 || s >= M || in_seen[s]) return false; in_seen[s] = 1; }
+    for (size_t o = 0; o < out_slots.size(); o++) {
+        const int s = out_slots[o];
+        if (s < 0 || s >= M || Q.out_at[s] >= 0) return false;
+        Q.out_at[s] = (int)o;
+    }
+    for (int p : in_slots) for (int o : out_slots) used[((p - o) % M + M) % M] = 1;
+    const uint64_t mask = 2 * (uint64_t)n - 1;
+    uint64_t g = 1;
+    for (int s = 0; s < M; s++, g = g * 3 & mask)
+        if (used[s]) { Q.steps.push_back(s); Q.elements.push_back(g); }
+    P = Q;
+    return true;
+}
+// the rows of ONE step: W [O][Cin][P] (any int64, taken mod t) -> rows [Cin][n] in [0, t).  false (rows untouched) for a weight count that is not O Cin P,
+// Cin < 1, t < 2 or a step index outside the plan
+inline bool crc_dense_planes_fold_step(const DensePlanesPlan &P, const std::vector<int64_t> &W, int Cin, int64_t t, int j, std::vector<int64_t> &rows)
+{
+    const size_t O = P.out_slots.size(), NP = P.in_slots.size();
+    if (Cin < 1 || t < 2 || j < 0 || j >= (int)P.steps.size() || P.M < 1 || W.size() != O * (size_t)Cin * NP) return false;
+    std::vector<int64_t> r((size_t)Cin * P.n, 0);
+    for (size_t p = 0; p < NP; p++) {
+        const int sp = P.in_slots[p], o = P.out_at[((sp - P.steps[j]) % P.M + P.M) % P.M];
+        if (o < 0) continue;
+        for (int c = 0; c < Cin; c++) {
+            int64_t v = W[((size_t)o * Cin + c) * NP + p] % t;
+            if (v < 0) v += t;
+            for (int i = sp; i < P.n; i += P.M) r[(size_t)c * P.n + i] = v;
+        }
+    }
+    rows = r;
+    return true;
+}
+// every step: rows [R][Cin][n]
+inline bool crc_dense_planes_fold(const DensePlanesPlan &P, const std::vector<int64_t> &W, int Cin, int64_t t, std::vector<int64_t> &rows)
+{
+    std::vector<int64_t> all, one;
+    for (int j = 0; j < (int)P.steps.size(); j++) {
+        if (!crc_dense_planes_fold_step(P, W, Cin, t, j, one)) return false;
+        all.insert(all.end(), one.begin(), one.end());
+    }
+    if (P.steps.empty()) return false;
+    rows = all;
+    return true;
+}
+// where a packed convolution leaves its outputs: the in_slots of the dense layer behind it
+inline std::vector<int> crc_dense_planes_in_slots(const ConvSlotsPlan &P) { return P.valid; }

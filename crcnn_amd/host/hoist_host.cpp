@@ -23,6 +23,16 @@
 // outputs).  Keys: convSlotsElements of both layers, each element once.  Per case (conv_fresh = the encrypted image read back, conv_1, conv_2, conv_2_ntt = both
 // layers NTT-resident) writes <dir>/<name>.i64 = [channels][H W] (decryptPlanes), prints "budget <name> <min bits>" and "conv <name> equal|differs" (every valid
 // pixel against the integer convolution computed here), then "keys conv <bytes> elements <count>", "throws <case> <kind>" and "hoist_host conv ok".
+//
+//   hoist_host <dir> planes        (tests/test_gpu_dense_planes_cpp.py)
+//
+// One packed image through convSlots -> densePlanes -> densePlanes: <dir>/image.i64 = [12][12] pixels, <dir>/w1.i64 = [2][1][3][3] (the conv case's first layer:
+// 5 x 5 outputs per plane at dilation 2), <dir>/w3.i64 = [6][2][25] (the dense layer over the two planes, outputs on the input lattice at slots 2 (12 a + b),
+// a < 2, b < 3), <dir>/w4.i64 = [3][1][6] (the dense layer on that vector, Cin = 1, outputs at slots 0, 2, 4); M = 256.  Keys: convSlotsElements and
+// densePlanesElements of the layers, each element once.  Per case (dense_1, dense_2, dense_2_ntt = all three layers NTT-resident) writes <dir>/<name>.i64 = [M]
+// (the first period's slots), prints "budget <name> <min bits>" and "planes <name> equal|differs" (every output slot of every period against the integer network
+// computed here, every other slot 0), then "steps conv <T> dense_1 <R> dense_2 <R>", "keys planes <bytes> prepared <bytes> elements <count>",
+// "throws <case> <kind>" and "hoist_host planes ok".
 #include "crcnn_host.h"
 #include "diag_plan.h"
 #include <algorithm>
@@ -180,9 +190,85 @@ static int conv_case(const vector<uint64_t> &p, const vector<uint64_t> &q)
     return 0;
 }
 
+// every slot of y against `want` at out_slots of every period M and 0 elsewhere: "planes <name> equal|differs"
+static void vector_slots(const char *name, const ciphertext3D &y, int M, const vector<int> &out_slots, const vector<int64_t> &want, int64_t t)
+{
+    printf("budget %s %d\n", name, minNoiseBudget(y));
+    const vector<vector<int64_t>> got = decryptSlots(y, n);
+    vector<int64_t> expect((size_t)M, 0);
+    for (size_t o = 0; o < out_slots.size(); o++) {
+        int64_t w = (want[o] % t + t) % t;
+        expect[out_slots[o]] = w > (t - 1) / 2 ? w - t : w;
+    }
+    bool equal = true;
+    for (int i = 0; i < n; i++) equal = equal && got[i][0] == expect[i % M];
+    const vector<vector<int64_t>> v = decryptVector(y, out_slots);
+    for (size_t o = 0; o < out_slots.size(); o++) equal = equal && v[0][o] == expect[out_slots[o]];
+    ofstream f(dir + "/" + name + ".i64", ios::binary);
+    for (int i = 0; i < M; i++) f.write((const char *)&got[i][0], 8);
+    printf("planes %s %s\n", name, equal ? "equal" : "differs");
+}
+static int planes_case(const vector<uint64_t> &p, const vector<uint64_t> &q)
+{
+    const int M = 256, H = 12, W = 12;
+    const int64_t t = (int64_t)p[2];
+    auto ints = [&](const char *file) { const auto raw = rd(dir + "/" + file); return vector<int64_t>(raw.begin(), raw.end()); };
+    const vector<int64_t> img = ints("image.i64"), w1 = ints("w1.i64"), w3 = ints("w3.i64"), w4 = ints("w4.i64");
+    SlotPlanes g1 = planesOf(H, W, M);
+    g1.fh = 3; g1.fw = 3; g1.pool = 2;
+    setParameters(n, q, (uint64_t)1 << 20, 0);
+    { ciphertext3D none(1, 1, 1, 1); thrown("no_batching_planes", [&] { densePlanes(none, w4, 3, M, {0, 1, 2, 3, 4, 5}); }); }
+    setParameters(n, q, p[2], 0);
+    setSlotEncoding(0, 0);
+    const ciphertext3D x = encryptImagePlanes(img, 1, H, W, M);
+    ConvSlotsPlan P1;
+    if (!crc_conv_slots_plan(n, M, W, H, W, 3, 3, 1, 2, P1)) return 5;
+    SlotPlanes o1 = planesOf(H, W, M);
+    o1.H = P1.out_h; o1.W = P1.out_w; o1.dil = P1.out_dil;
+    if (densePlanesInSlots(o1) != crc_dense_planes_in_slots(P1)) return 6;
+    vector<int> out1, out2{0, 2, 4};
+    for (int a = 0; a < 2; a++) for (int b = 0; b < 3; b++) out1.push_back(2 * (12 * a + b));
+    vector<uint64_t> elts = convSlotsElements(g1);
+    const vector<uint64_t> e1 = densePlanesElements(o1, 6, out1), e2 = densePlanesElements(M, out1, 3, out2);
+    for (uint64_t e : e1) if (find(elts.begin(), elts.end(), e) == elts.end()) elts.push_back(e);
+    for (uint64_t e : e2) if (find(elts.begin(), elts.end(), e) == elts.end()) elts.push_back(e);
+    const ciphertext3D c0 = [&] { generateGaloisKeys(16, convSlotsElements(g1)); return convSlots(x, w1, 2, g1); }();
+    thrown("missing_key_planes", [&] { densePlanes(c0, w3, 6, o1, out1); });             // the conv's keys alone
+    generateGaloisKeys(16, elts);
+    const vector<vector<int64_t>> y1 = conv_int({img}, H, W, w1, 2, 3, 3, 2);
+    vector<int64_t> v1(6, 0), v2(3, 0);
+    for (int o = 0; o < 6; o++) for (int c = 0; c < 2; c++) for (int i = 0; i < 25; i++) v1[o] += w3[((size_t)o * 2 + c) * 25 + i] * y1[c][i];
+    for (int o = 0; o < 3; o++) for (int i = 0; i < 6; i++) v2[o] += w4[(size_t)o * 6 + i] * v1[i];
+    const ciphertext3D c1 = convSlots(x, w1, 2, g1);
+    const ciphertext3D d1 = densePlanes(c1, w3, 6, o1, out1);
+    vector_slots("dense_1", d1, M, out1, v1, t);
+    const size_t prepared = preparedGaloisKeyBytes();
+    const ciphertext3D d2 = densePlanes(d1, w4, 3, M, out1, out2);
+    vector_slots("dense_2", d2, M, out2, v2, t);
+    if (preparedGaloisKeyBytes() != prepared) return 7;                                  // (made once, kept)
+    {
+        const ciphertext3D n1 = convSlots(x, w1, 2, g1, nullptr, CRC_NTT), n2 = densePlanes(n1, w3, 6, o1, out1, CRC_NTT);
+        vector_slots("dense_2_ntt", densePlanes(n2, w4, 3, M, out1, out2, CRC_NTT), M, out2, v2, t);
+    }
+    printf("steps conv %zu dense_1 %zu dense_2 %zu\n", P1.steps.size(), e1.size() + 1, e2.size() + 1);
+    printf("keys planes %zu prepared %zu elements %zu\n", elts.size() * crc_evk_words(context, 16) * 8, prepared, elts.size());
+    thrown("bad_weights_planes", [&] { densePlanes(c1, w4, 6, o1, out1); });
+    thrown("bad_M_planes", [&] { densePlanes(d1, w4, 3, 96, out1, out2); });
+    thrown("duplicate_slot", [&] { densePlanes(d1, w4, 3, M, out1, {0, 2, 2}); });
+    thrown("slot_outside_M", [&] { densePlanes(d1, w4, 3, M, out1, {0, 2, 256}); });
+    thrown("wrong_output_count", [&] { densePlanes(d1, w4, 3, M, out1, {0, 2}); });
+    thrown("bad_form_planes", [&] { densePlanes(d1, w4, 3, M, out1, out2, CRC_NTTP); });
+    thrown("not_planes_dense", [&] { densePlanes(ciphertext3D(1, 1, 2, 1), w4, 3, M, out1, out2); });
+    thrown("no_slots", [&] { decryptVector(d2, {}); });
+    delParameters();
+    clearDeterministicSeed();
+    printf("hoist_host planes ok\n");
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: hoist_host <dir> [bsgs | conv]\n"); return 1; }
+    if (argc < 2) { fprintf(stderr, "usage: hoist_host <dir> [bsgs | conv | planes]\n"); return 1; }
     try {
         dir = argv[1];
         setDeterministicSeed(20241019);
@@ -191,6 +277,7 @@ int main(int argc, char **argv)
         const vector<uint64_t> q(p.begin() + 3, p.begin() + 3 + k);
         if (argc > 2 && string(argv[2]) == "bsgs") return bsgs_case(p, q);
         if (argc > 2 && string(argv[2]) == "conv") return conv_case(p, q);
+        if (argc > 2 && string(argv[2]) == "planes") return planes_case(p, q);
         const vector<vector<int64_t>> W8 = matrix(dir + "/w8.i64", 8, 8), W5 = matrix(dir + "/w5.i64", 5, 8);
         // a plain modulus without slots: the reference's logic_error, before any key is looked at
         setParameters(n, q, (uint64_t)1 << 20, 0);

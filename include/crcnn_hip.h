@@ -688,9 +688,28 @@ int crc_sum_slots_forms(crc_ctx *ctx, const uint64_t *d_x, int in_form, size_t c
  *                               arguments); Cin, Cout <= 4096, T <= 1024
  *   crc_conv_slots_pack_weights host memory, any context: h_out [k][count] from count integers h_w (any int64, taken mod t): for c = w mod t in [0, t) the word
  *                               c >= (t + 1) / 2 ? c + q_i - t : c  (mod q_i) -- every position of the NTT-form row of the constant plaintext c
+ *   crc_galois_prepare_keys_dev prepared keys that outlive a call: d_pk [n_elts][crc_galois_prepared_key_words(ctx, dbc)] from the CONJUGATED keys d_cgk of elts --
+ *                               per key exactly what every entry point above makes of it in pass 0 of every call (the fp64 key switch's form).  d_scratch:
+ *                               crc_evk_words(ctx, dbc) words.  CRC_ERR_UNSUPPORTED (and 0 words) where the fp64 key switch does not take (parameters, dbc);
+ *                               CRC_ERR_INVALID_ARGUMENT for null, misaligned or overlapping operands, an invalid element or g = 1
+ *   crc_dense_planes_forms      the dense layer over channel planes: d_x [Cin][count] -> d_y [count],  y = Sum_j H_{gs[j]}( Sum_c P[j][c] (*) x[c] )  with NTT-form
+ *                               plaintext rows d_p_ntt [R][Cin][k][n].  The OUTPUTS are rotated: R key switches (fewer where gs[j] = 1) whatever Cin is, the
+ *                               keyed steps of a pass in one batched key switch with one key per step.  Bit for bit: per j crc_multiply_plain_ntt(x[c], P[j][c])
+ *                               summed over c with crc_add, crc_rotate_hoisted_forms of the sum by {gs[j]} into NTT form, crc_add over j, one inverse transform
+ *                               for CRC_COEFF -- at every tuning setting ("planes_batch": 0 default, 1 one key switch per step, 2 batched) and pass structure.
+ *                               d_pk: NULL, or the prepared keys of (d_cgk, elts) from crc_galois_prepare_keys_dev -- then no key is prepared in the call where
+ *                               the fp64 key switch runs.  With the rows of crc_dense_planes_fold (crcnn_amd/host/diag_plan.h) this is a dense layer on strided
+ *                               slots of Cin planes; Cin = 1 is a dense layer on a vector at arbitrary slots.  d_work: crc_dense_planes_work_bytes(ctx, count,
+ *                               Cin, R, dbc, prepared = d_pk != NULL) (0 for bad arguments); Cin <= 4096, R <= 65536.  The size for prepared = 1 is
+ *                               SMALLER (one key slot instead of R), and the call derives its layout from d_pk, not from the buffer: a d_work sized with
+ *                               prepared = 1 and then passed with d_pk = NULL is written past its end, undetected -- size it with the flag the call will
+ *                               see, or with the larger of the two.  Of d_pk only the slots of the call's own elements gs are read, so the others need not
+ *                               be prepared.  The key pointers of the batched path are written by a kernel from launch arguments: like its siblings the
+ *                               call reads no host memory after it returns
  * Refusals as in the paragraph above (null / misaligned / overlapping operands, forms, dbc, an invalid element), plus R < 1 (B < 1, G < 1) and a missing
  * conjugated key; crc_conv_slots_forms also for Cin, Cout or T below 1 or above its caps, and for d_w null, misaligned or overlapping d_y or d_work:
- * CRC_ERR_INVALID_ARGUMENT, nothing launched, d_y untouched.  count = 0 is CRC_OK.
+ * CRC_ERR_INVALID_ARGUMENT, nothing launched, d_y untouched.  count = 0 is CRC_OK.  crc_dense_planes_forms also for Cin or R outside their caps, d_p_ntt or d_pk
+ * misaligned or overlapping d_x, d_y or d_work, and d_pk given with n_elts = 0 while a step is keyed.
  * ------------------------------------------------------------------------------------------------------------- */
 int crc_galois_ntt_table(const crc_ctx *ctx, uint64_t g, uint32_t *table /*[n]*/);
 int crc_galois_conjugate_keys(const crc_ctx *ctx, const uint64_t *elts, int n_elts, int dbc, const uint64_t *h_gk, uint64_t *h_out);
@@ -711,6 +730,13 @@ size_t crc_conv_slots_work_bytes(const crc_ctx *ctx, size_t count, int Cin, int 
 int crc_conv_slots_forms(crc_ctx *ctx, const uint64_t *d_x /*[Cin][count]*/, int in_form, size_t count, int Cin, const uint64_t *gs /*[T], host*/, int T,
                          const uint64_t *d_w /*[k][Cout][Cin][T]*/, int Cout, const uint64_t *d_cgk, const uint64_t *elts, int n_elts, int dbc,
                          uint64_t *d_y /*[Cout][count]*/, int out_form, void *d_work, void *stream);
+size_t crc_galois_prepared_key_words(const crc_ctx *ctx, int dbc);
+int crc_galois_prepare_keys_dev(crc_ctx *ctx, const uint64_t *d_cgk, const uint64_t *elts, int n_elts, int dbc, uint64_t *d_pk /*[n_elts][prepared_key_words]*/,
+                                uint64_t *d_scratch /*[crc_evk_words]*/, void *stream);
+size_t crc_dense_planes_work_bytes(const crc_ctx *ctx, size_t count, int Cin, int R, int dbc, int prepared);
+int crc_dense_planes_forms(crc_ctx *ctx, const uint64_t *d_x /*[Cin][count]*/, int in_form, size_t count, int Cin, const uint64_t *gs /*[R], host*/, int R,
+                           const uint64_t *d_p_ntt /*[R][Cin][k][n]*/, const uint64_t *d_cgk, const uint64_t *elts, int n_elts, const uint64_t *d_pk /*or NULL*/,
+                           int dbc, uint64_t *d_y /*[count]*/, int out_form, void *d_work, void *stream);
 /* FractionalEncoder::decode / encode (encoder.cpp:1226-1270, 1013-1076; 64 integer + 32 fractional coefficients, base 3: CrCNN/src/globals.cpp:52) on the
  * device: the doubles crc_decode returns for d_plain [count][n], and the dense plaintexts [count][n] crc_encode_f32 / _f64 make of the values -- the same IEEE
  * operations in the same order as the host encoder, contraction off. */
