@@ -343,46 +343,107 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
     const int fl = wn * 16 + r16, f = f0 + fl;
     const u64 bv = (!SC && a.bias && f < a.F) ? a.bias[((size_t)f * a.k + i) * a.n + s] : 0;
     const u32 img_jump = (u32)(a.F - 1) * P2;                     // Ys [image][filter][2P]: rows run on inside an image's filter block, the next image's is F - 1 blocks further
+    // Direct limb result under a modulus with a fold constant (every layer hand-over of the networks): only the centred digits are stored, so the reduction returns the
+    // centred representative in one pass (diag_reduce_w_centred; the lane's bias is centred once) and the digit bytes of a lane's neighbouring outputs leave as byte PAIRS.
+    // A lane's four registers are tile rows rt0 .. rt0 + 3, rt0 a multiple of 4.  With 2P >= 4 they are pixels p, p + 1 of both polys of one image: registers 0 / 2 and
+    // 1 / 3 are adjacent bytes of the staging run [image][plane][poly][filter P + pixel] (p and P even: 2-byte aligned) -- one v_perm_b32 gathers two planes' pairs, 8
+    // permutes and 14 two-byte stores per four outputs instead of 28 shifts and 28 byte stores.  With P = 1 (dense -> dense) the four rows are two images: byte stores.
+    const bool centred = a.xl_out && m.fold;                      // (uniform; the Barrett moduli keep the canonical sequence below)
+    if (centred) {
+        const long long bc = centred_rep(bv, m.q);
+        const u32 img_stage = NPL * 2 * RL, col = (u32)fl * a.P;
 #pragma unroll
-    for (int rs = 0; rs < 2; rs++) {
-        const u32 mbase = m0 + wm * 32 + rs * 16 + 4 * kg, bb = mbase / P2, rem = mbase - bb * P2;
-        const u32 idx0 = bb * img_jump + (u32)f * P2 + mbase;
+        for (int rs = 0; rs < 2; rs++) {
+            const u32 rt0 = wm * 32 + rs * 16 + 4 * kg;
+            u32 lo[4], hi[4];
 #pragma unroll
-        for (int reg = 0; reg < 4; reg++) {
-            int D[13];
+            for (int reg = 0; reg < 4; reg++) {
+                int D[13];
 #pragma unroll
-            for (int d = 0; d < 13; d++) D[d] = acc[rs][d][reg];
-            u64 v = diag_reduce_w(D, m, qinv);
-            if (SC) {                                                 // the row's image e = s B + b: its bias sits at slot s (rows past M belong to no image)
-                if ((reg & 1) == 0 && a.bias && f < a.F && mbase + reg < (u32)a.M) {
-                    const u32 r = rem + reg, e = bb + (r >= P2) + (r >= 2 * P2);
-                    v = addmod(v, a.bias[((size_t)f * a.k + i) * a.n + e / (u32)a.sc_B], m.q);
+                for (int d = 0; d < 13; d++) D[d] = acc[rs][d][reg];
+                long long cv;
+                if (reg & 1) cv = diag_reduce_w_centred<false>(D, m, qinv, 0);
+                else {
+                    long long brow = bc;
+                    if (SC) {                                         // the row's image e = s B + b: its bias sits at slot s (rows past M belong to no image)
+                        brow = 0;
+                        if (a.bias && f < a.F && (u32)m0 + rt0 + reg < (u32)a.M) brow = centred_rep(a.bias[((size_t)f * a.k + i) * a.n + (((u32)m0 + rt0 + reg) >> a.lp2) / (u32)a.sc_B], m.q);
+                    }
+                    cv = diag_reduce_w_centred<true>(D, m, qinv, brow);
                 }
-            } else if ((reg & 1) == 0) v = addmod(v, bv, m.q);
-            if (a.xl_out) {
-                const u32 rt = wm * 32 + rs * 16 + 4 * kg + reg, bl = rt >> a.lp2, qq = rt & (P2 - 1);
-                const u64 dg = f < a.F ? balanced_digit_bytes(v, m.q) : 0;
-                i8 *sp = lds + (size_t)bl * (NPL * 2 * RL) + (qq & 1) * RL + fl * a.P + (qq >> 1);
+                const u64 dg = f < a.F ? centred_digit_bytes(cv) : 0;      // filters past F: zero padding of the consumer's channels
+                lo[reg] = (u32)dg; hi[reg] = (u32)(dg >> 32);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (a.lp2 >= 2) {
+                i8 *sp = lds + (rt0 >> a.lp2) * img_stage + col + ((rt0 & (P2 - 1)) >> 1);
 #pragma unroll
-                for (int l = 0; l < NPL; l++) sp[(size_t)l * (2 * RL)] = (i8)(dg >> (8 * l));
+                for (int c = 0; c < 2; c++, sp += RL) {
+                    // bytes (l, l + 1) of registers c and c + 2, interleaved: [c_l, (c+2)_l, c_l+1, (c+2)_l+1]
+                    const u32 p01 = __builtin_amdgcn_perm(lo[c + 2], lo[c], 0x05010400), p23 = __builtin_amdgcn_perm(lo[c + 2], lo[c], 0x07030602);
+                    const u32 p45 = __builtin_amdgcn_perm(hi[c + 2], hi[c], 0x05010400), p6 = __builtin_amdgcn_perm(hi[c + 2], hi[c], 0x0c0c0602);
+                    const u32 pr[4] = {p01, p23, p45, p6};
+#pragma unroll
+                    for (int l = 0; l < NPL; l++)
+                        *reinterpret_cast<unsigned short *>(sp + (size_t)l * (2 * RL)) = (unsigned short)(l & 1 ? pr[l >> 1] >> 16 : pr[l >> 1]);
+                }
             } else {
-                const u32 r = rem + reg, jump = (r >= P2 ? img_jump : 0u) + (r >= 2 * P2 ? img_jump : 0u);
-                if (mbase + reg < (u32)a.M && f < a.F) yslot[idx0 + reg + jump] = v;
+                i8 *sp = lds + (rt0 >> 1) * img_stage + col;        // P = 1: row = (image, poly), one byte per filter
+#pragma unroll
+                for (int reg = 0; reg < 4; reg++) {
+                    i8 *sr = sp + (reg >> 1) * img_stage + (reg & 1) * RL;
+#pragma unroll
+                    for (int l = 0; l < NPL; l++) sr[(size_t)l * (2 * RL)] = (i8)((l < 4 ? lo[reg] : hi[reg]) >> (8 * (l & 3)));
+                }
             }
             __builtin_amdgcn_sched_barrier(0);
+        }
+    } else {
+#pragma unroll
+        for (int rs = 0; rs < 2; rs++) {
+            const u32 mbase = m0 + wm * 32 + rs * 16 + 4 * kg, bb = mbase / P2, rem = mbase - bb * P2;
+            const u32 idx0 = bb * img_jump + (u32)f * P2 + mbase;
+#pragma unroll
+            for (int reg = 0; reg < 4; reg++) {
+                int D[13];
+#pragma unroll
+                for (int d = 0; d < 13; d++) D[d] = acc[rs][d][reg];
+                u64 v = diag_reduce_w(D, m, qinv);
+                if (SC) {                                                 // the row's image e = s B + b: its bias sits at slot s (rows past M belong to no image)
+                    if ((reg & 1) == 0 && a.bias && f < a.F && mbase + reg < (u32)a.M) {
+                        const u32 r = rem + reg, e = bb + (r >= P2) + (r >= 2 * P2);
+                        v = addmod(v, a.bias[((size_t)f * a.k + i) * a.n + e / (u32)a.sc_B], m.q);
+                    }
+                } else if ((reg & 1) == 0) v = addmod(v, bv, m.q);
+                if (a.xl_out) {
+                    const u32 rt = wm * 32 + rs * 16 + 4 * kg + reg, bl = rt >> a.lp2, qq = rt & (P2 - 1);
+                    const u64 dg = f < a.F ? balanced_digit_bytes(v, m.q) : 0;
+                    i8 *sp = lds + (size_t)bl * (NPL * 2 * RL) + (qq & 1) * RL + fl * a.P + (qq >> 1);
+#pragma unroll
+                    for (int l = 0; l < NPL; l++) sp[(size_t)l * (2 * RL)] = (i8)(dg >> (8 * l));
+                } else {
+                    const u32 r = rem + reg, jump = (r >= P2 ? img_jump : 0u) + (r >= 2 * P2 ? img_jump : 0u);
+                    if (mbase + reg < (u32)a.M && f < a.F) yslot[idx0 + reg + jump] = v;
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
         }
     }
     if (a.xl_out) {
         __syncthreads();
-        const u32 imgs = 64 >> a.lp2, b0 = (u32)m0 >> a.lp2, per_run = RL / 16, pieces = imgs * NPL * 2 * per_run;
-        const u32 ch0 = (u32)f0 * a.P;
-        for (u32 o = threadIdx.x; o < pieces; o += 256) {
-            const u32 run = o / per_run, off = (o - run * per_run) * 16, bl = run / (NPL * 2), lc = run - bl * (NPL * 2);
-            const u32 ch = ch0 + off;                                 // consumer layout: [plane][channel block][row = image * 2 + poly][32]
+        // copy-out: 64 >> lp2 images x 7 planes x 2 polys runs of RL = 16 (2P) bytes, 896 pieces of 16 bytes whatever the layer.  Piece o = run << lp2 | piece of the run,
+        // run = image * 14 + plane * 2 + poly: a thread's pieces are 256 >> lp2 runs apart, so (image, plane * 2 + poly) is divided out once and stepped.  (The index
+        // of a 32-byte row inside the slot's tensor is a 32-bit number: a slot's tensor would have to pass 128 GiB.)
+        const u32 b0 = (u32)m0 >> a.lp2, ch = (u32)f0 * a.P + ((threadIdx.x & (P2 - 1)) << 4), zb_out = a.zdp_out >> 5;
+        const u32 drun = 256u >> a.lp2, dbl = drun / (NPL * 2), dlc = drun - dbl * (NPL * 2);
+        u32 run = threadIdx.x >> a.lp2, bl = run / (NPL * 2), lc = run - bl * (NPL * 2);                           // lc = plane * 2 + poly
+        i8 *yo = a.xl_out + (size_t)slot * ((size_t)NPL * 2 * a.B * a.zdp_out) + (ch & 31);                       // consumer layout: [plane][channel block][row = image * 2 + poly][32]
+        const i8 *sp = lds + ((threadIdx.x & (P2 - 1)) << 4);
+        for (u32 o = threadIdx.x; o < 64u * NPL * 2; o += 256) {
             if (b0 + bl < (u32)a.B && ch < a.zdp_out)
-                *reinterpret_cast<uint4 *>(a.xl_out + (size_t)slot * ((size_t)NPL * 2 * a.B * a.zdp_out)
-                                           + ((size_t)((lc >> 1) * (a.zdp_out / 32) + (ch >> 5)) * (2 * a.B) + (b0 + bl) * 2 + (lc & 1)) * 32 + (ch & 31)) =
-                    *reinterpret_cast<const uint4 *>(lds + (size_t)run * RL + off);
+                *reinterpret_cast<uint4 *>(yo + (size_t)(((lc >> 1) * zb_out + (ch >> 5)) * (u32)(2 * a.B) + (b0 + bl) * 2 + (lc & 1)) * 32) = *reinterpret_cast<const uint4 *>(sp + run * RL);
+            run += drun; bl += dbl; lc += dlc;
+            if (lc >= NPL * 2) { lc -= NPL * 2; bl++; }
         }
     }
 }

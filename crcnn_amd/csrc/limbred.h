@@ -43,7 +43,8 @@ CRC_HD u64 diag_reduce(const int (&D)[13], const ModParams &m, u64 qinv)
 // The same value from pre-shifted 32-bit words (round 4).  The compiler lowers the 128-bit shifts of s1 << 8, s2 << 16, s3 << 24 above to chains of 64-bit shifts and
 // ors (a quarter of the epilogue's instructions); here every shifted word is one v_alignbit_b32, the four numbers add as two carry chains, and the fold after the
 // Montgomery step works on the upper word (bits >= 32 for every modulus with a fold constant).  Same contract, same result as diag_reduce.
-CRC_HD u64 diag_reduce_w(const int (&D)[13], const ModParams &m, u64 qinv)
+// (its two steps, shared with the centred form below: the words of U and the Montgomery step, t + q in (0, 2^63 + q); then the fold of that value for q = 2^b - f)
+CRC_HD u64 diag_mont_w(const int (&D)[13], u64 q, u64 qinv)
 {
     typedef unsigned __int128 u128;
     const u32 a0 = (u32)D[1] << 8,  a1 = crc_alignbit((u32)D[5], (u32)D[1], 24), a2 = crc_alignbit((u32)D[9], (u32)D[5], 24),  a3 = (u32)D[9] >> 24;
@@ -53,14 +54,39 @@ CRC_HD u64 diag_reduce_w(const int (&D)[13], const ModParams &m, u64 qinv)
     const u128 U = w128((u32)D[12], (u32)D[8], (u32)D[4], (u32)D[0]) + w128(a3, a2, a1, a0) + w128(b3, b2, b1, b0) + w128(c3, c2, c1, c0);
     const u64 ulo = (u64)U, uhi = (u64)(U >> 64);
     const u64 mq = ulo * qinv;
-    const u64 t = uhi - mulhi64(mq, m.q) + m.q;                  // in (0, 2^63 + q)
-    if (m.fold) {                                                 // 2^b = f (mod q), b >= 52: (t >> b) < 2^12 lives in the upper word
-        const u32 th = (u32)(t >> 32), sb = m.bits - 32;
-        const u64 r = (((u64)(th & ((1u << sb) - 1)) << 32) | (u32)t) + (u64)(th >> sb) * (u32)m.fold;
+    return uhi - mulhi64(mq, q) + q;                              // in (0, 2^63 + q)
+}
+CRC_HD u64 fold_upper_word(u64 t, const ModParams &m)            // 2^b = f (mod q), b >= 52: (t >> b) < 2^12 lives in the upper word; the result is below 2^b + 2^38 < 2q
+{
+    const u32 th = (u32)(t >> 32), sb = m.bits - 32;
+    return (((u64)(th & ((1u << sb) - 1)) << 32) | (u32)t) + (u64)(th >> sb) * (u32)m.fold;
+}
+CRC_HD u64 diag_reduce_w(const int (&D)[13], const ModParams &m, u64 qinv)
+{
+    const u64 t = diag_mont_w(D, m.q, qinv);
+    if (m.fold) {
+        const u64 r = fold_upper_word(t, m);
         return r >= m.q ? r - m.q : r;
     }
     return barrett128(t, 0, m);
 }
+// the same for q = 2^b - f (m.fold != 0 is the precondition), returning the CENTRED representative of (U 2^-64 + bias) mod q in [-(q-1)/2, (q-1)/2] -- what the limb
+// form of the next layer is made of -- in one pass.  t + q in (0, 2^63 + q) folds to r = (t mod 2^b) + (t >> b) f < 2^b + 2^38 < 2q (b >= 52, f < 2^26), which is NOT
+// canonicalised: r - q lies in [-q, 2^38 + f), with a centred bias in [-(q-1)/2, (q-1)/2] added in (-1.5 q, 0.5 q + 2^38 + f).  One conditional + q brings either into
+// [-(q-1)/2, ...]: without a bias the value then is at most max(2^38 + f, (q-1)/2) = (q-1)/2 and done; with one it may stand up to 2^38 + f above (q-1)/2, and one
+// conditional - q (which cannot pass below -(q-1)/2: the value was above (q-1)/2) finishes.  These replace the three 64-bit corrections of canonicalise / addmod / centre.
+template <bool HAS_BIAS>
+CRC_HD long long diag_reduce_w_centred(const int (&D)[13], const ModParams &m, u64 qinv, long long bias_centred)
+{
+    long long t = (long long)(fold_upper_word(diag_mont_w(D, m.q, qinv), m) - m.q);
+    const long long h = (long long)(m.q >> 1);
+    if (HAS_BIAS) t += bias_centred;
+    t += t < -h ? (long long)m.q : 0;
+    if (HAS_BIAS) t -= t > h ? (long long)m.q : 0;
+    return t;
+}
+// the centred representative of a canonical residue (a lane centres its bias once per tile)
+CRC_HD long long centred_rep(u64 r, u64 q) { return r > (q >> 1) ? (long long)(r - q) : (long long)r; }
 
 // short form (kernels_mfma1.hip: 64-term reductions, 2^52 < q < 2^55): all D'_d < 2^24 with D'_odd < 0.94 2^24, 0 < U < 2^115.6.  PAIRS of diagonals
 // P_j = D'_2j + D'_2j+1 2^8 < 2^32 sit at bit 16 j: even pairs are the words of one 128-bit number, odd pairs of another, 16 bits up.  t in (-q, 2^51.6]: one
