@@ -95,6 +95,7 @@ def load():
     L.crc_plain_to_delta.argtypes = [VP, VP, SZ, CI, VP, VP]
     L.crc_ntt_fwd.argtypes = [VP, VP, SZ, CI, VP]
     L.crc_ntt_inv.argtypes = [VP, VP, SZ, CI, VP]
+    L.crc_ntt_fwd_box.argtypes = [VP, VP, VP] + [CI] * 7 + [VP]
     L.crc_ntt_fwd_bsk.argtypes = [VP, VP, SZ, VP]
     L.crc_ntt_inv_bsk.argtypes = [VP, VP, SZ, VP]
     L.crc_add.argtypes = [VP, VP, VP, SZ, CI, VP]
@@ -778,6 +779,10 @@ class Engine:
 
     def ntt_fwd(self, d_ct, count, size=2):
         _chk(self.L.crc_ntt_fwd(self.c, self.p(d_ct), count, size, self.stream), "crc_ntt_fwd")
+
+    def ntt_fwd_box(self, d_src, d_dst, B, xd, yd, bxf, byf, xs, ys):
+        """crc_ntt_fwd_box: [B][xd][yd] coefficient-form ciphertexts in, the NTT of their bxf x byf window sums at dilation (xs, ys) out ([B][xdo][ydo])"""
+        _chk(self.L.crc_ntt_fwd_box(self.c, self.p(d_src), self.p(d_dst), B, xd, yd, bxf, byf, xs, ys, self.stream), "crc_ntt_fwd_box")
 
     def ntt_inv(self, d_ct, count, size=2):
         _chk(self.L.crc_ntt_inv(self.c, self.p(d_ct), count, size, self.stream), "crc_ntt_inv")

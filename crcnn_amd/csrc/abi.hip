@@ -41,6 +41,13 @@ extern "C" int crc_ntt_fwd(crc_ctx *c, uint64_t *d_ct, size_t count, int size, v
     CHECK_CTX(c); if (!d_ct || size < 1) return CRC_ERR_INVALID_ARGUMENT;
     return k_ntt_ct(c, false, d_ct, d_ct, count, size, false, S(stream), nullptr, 0, 0);
 }
+// forward NTT of the bxf x byf window sums (dilation (xs, ys)) of B images of xd x yd coefficient-form size-2 ciphertexts: [B][xdo][ydo] NTT-form ciphertexts,
+// out of place (kernels.hip k_ntt_ct_box)
+extern "C" int crc_ntt_fwd_box(crc_ctx *c, const uint64_t *d_src, uint64_t *d_dst, int B, int xd, int yd, int bxf, int byf, int xs, int ys, void *stream)
+{
+    CHECK_CTX(c); if (!d_src || !d_dst) return CRC_ERR_INVALID_ARGUMENT;
+    return k_ntt_ct_box(c, d_src, d_dst, B, xd, yd, bxf, byf, xs, ys, S(stream));
+}
 extern "C" int crc_ntt_inv(crc_ctx *c, uint64_t *d_ct, size_t count, int size, void *stream)
 {
     CHECK_CTX(c); if (!d_ct || size < 1) return CRC_ERR_INVALID_ARGUMENT;
@@ -178,6 +185,7 @@ static Limb1Work limb1_layout(const crc_ctx *c, int B, const Window &in, int bxf
     L.Bs = conv1_sub_batch(c, B, w, nf, L.out_form);
     L.Xr = a.take<signed char>(k_limb_conv1_image_bytes(c, L.Bs, w, nf));
     if (L.out_form != CRC_NTTLC) L.Ys = a.take<u64>(k_limb_result_words(c, L.Bs, nf, P));
+    // (the boxed transform of conv2d_limb1 fills only Bs xdo ydo ciphertexts of it: the size does not depend on which path the call takes)
     if (in_form == CRC_COEFF) L.buf = a.take<u64>((size_t)L.Bs * in.xd * in.yd * crc_ct_words(c, 2));
     return L;
 }
@@ -189,12 +197,19 @@ static int conv2d_limb1(crc_ctx *c, const uint64_t *d_x, const void *d_wl, const
     const Limb1Work L = limb1_layout(c, B, in, bxf, byf, nf, in_form, out_form, a);
     out_form = L.out_form;
     const size_t ctw = crc_ct_words(c, 2);
+    // a coefficient-form input under a box: the window sums are taken while the input transform loads (k_ntt_ct_box: NTT(sum) = sum NTT mod q, bit for bit), 14 %
+    // fewer rows transformed for PlainModelTiny's 2 x 2 box, and the pack runs its unboxed body on the summed image.  box_ntt = 0 or a ring without that kernel:
+    // transform every input, then the boxed pack, as NTT-form inputs do
+    const bool sum_first = in_form == CRC_COEFF && bxf * byf > 1 && c->tune.box_ntt != 0 && k_ntt_ct_box_supported(c, bxf, byf);
+    const Window wsum = in.boxed(bxf, byf);
     for (int b0 = 0; b0 < B; b0 += L.Bs) {
         const int Bn = B - b0 < L.Bs ? B - b0 : L.Bs;
         const u64 *xn = d_x + (size_t)b0 * in_cts * ctw; bool packed = in_form == CRC_NTTP;
-        if (in_form == CRC_COEFF) { RUN(k_ntt_ct(c, false, xn, L.buf, (size_t)Bn * in_cts, 2, false, st, nullptr, 0, 0, 0, 0)); xn = L.buf; packed = false; }
+        if (sum_first) RUN(k_ntt_ct_box(c, xn, L.buf, Bn, in.xd, in.yd, bxf, byf, in.xs, in.ys, st));
+        else if (in_form == CRC_COEFF) RUN(k_ntt_ct(c, false, xn, L.buf, (size_t)Bn * in_cts, 2, false, st, nullptr, 0, 0, 0, 0));
+        if (in_form == CRC_COEFF) { xn = L.buf; packed = false; }
         RUN(k_limb_conv1(c, xn, packed, L.Xr, (const signed char *)d_wl, L.Ys, out_form == CRC_NTTLC ? (signed char *)d_y : nullptr, B, b0,
-            out_form != CRC_COEFF ? d_bias : nullptr, Bn, in, nf, st, bxf, byf));
+            out_form != CRC_COEFF ? d_bias : nullptr, Bn, sum_first ? wsum : in, nf, st, sum_first ? 1 : bxf, sum_first ? 1 : byf));
         if (out_form == CRC_NTTLC) continue;
         if (out_form == CRC_NTTL) return k_limb_result_to_limb(c, L.Ys, (signed char *)d_y, B, nf * P, st);     // (Bs == B)
         RUN(k_limb_result_to_rows(c, L.Ys, d_y + (size_t)b0 * nf * P * ctw, (size_t)Bn * nf * P * 2, out_form == CRC_NTTP, st));
@@ -581,6 +596,9 @@ extern "C" int crc_plan_hoist_pool(const crc_ctx *c, int uzd, int uxd, int uyd, 
 // 26 x 26 x 2 x 3 terms, at the limb GEMM's 75.2 ns per unit (90.56 ms / 1 204 224 units in the same job: profiles/conv1_box_staged_ab.txt) = 12.4.  (The direct
 // form, which re-read every term from L2, was 21.)  What is left is no longer re-reading: the pass reads 28 x 28 inputs to write 26 x 26 pixels, holds 68.5 KiB of
 // LDS (two workgroups per CU) and has two barriers per row group.  The tuning key conv1_box = 0 (CRC_CONV1_BOX=0) answers no throughout.
+// A COEFFICIENT-form input no longer pays this: its window sums are taken in front of the input transform (conv2d_limb1: k_ntt_ct_box) and the pack runs unboxed on
+// the summed image.  The constant stays the staged pack's: an NTT-form input still pays it, the plan has no input-form argument, and the cheaper path only makes a
+// yes more right.
 #define PLAN_BOX_READ 12
 extern "C" int crc_plan_conv1_box(const crc_ctx *c, int zd, int xd, int yd, int xs, int ys, int xf, int yf, int nf, int bxf, int byf, int B, int matrix_cores,
                                   int *box)

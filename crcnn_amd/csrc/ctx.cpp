@@ -177,6 +177,7 @@ static void read_tuning(CrcTuning &t)
     { const int v = (int)geti("CRC_PLANES_BATCH", 0); t.planes_batch = v == 1 || v == 2 ? v : 0; }
     { const int v = (int)geti("CRC_CONV_JT", 0); t.conv_jt = v == 2 || v == 4 || v == 8 ? v : 0; }
     t.conv1_box = geti("CRC_CONV1_BOX", 1) ? 1 : 0;
+    { const int v = (int)geti("CRC_BOX_NTT", 1); t.box_ntt = v >= 0 && v <= 2 ? v : 1; }
     { const long long v = geti("CRC_CONV1_PASS_BYTES", 0); t.conv1_pass_bytes = v > 0 ? v : 0; }
     { const int v = (int)geti("CRC_LIMB_PACK_GROUP", 1); t.limb_pack_group = v > 0 ? v : 1; }
     t.mac2_cfg = (int)geti("CRC_MAC2_CFG", 0);
@@ -214,6 +215,7 @@ extern "C" int crc_ctx_set_tuning(crc_ctx *c, const char *name, long long value)
     else if (s == "planes_batch") t.planes_batch = value == 1 || value == 2 ? (int)value : 0;
     else if (s == "conv_jt") t.conv_jt = value == 2 || value == 4 || value == 8 ? (int)value : 0;
     else if (s == "conv1_box") t.conv1_box = value ? 1 : 0;
+    else if (s == "box_ntt") t.box_ntt = value >= 0 && value <= 2 ? (int)value : 1;
     else if (s == "conv1_pass_bytes") t.conv1_pass_bytes = value > 0 ? value : 0;
     else if (s == "limb_pack_group") t.limb_pack_group = value > 0 ? (int)value : 1;
     else if (s == "mac2_cfg") t.mac2_cfg = (int)value;

@@ -108,6 +108,7 @@ struct CrcTuning {
     int conv1_waves = 0;          // CRC_CONV1_WAVES=8|12
     int conv1_narrow = 1;         // CRC_CONV1_NARROW=0: 17-20 filters run the second filter group like a full one (round 4) instead of the packed form
     int conv1_box = 1;            // CRC_CONV1_BOX=0: crc_plan_conv1_box always answers no (the hoisted pair's one-channel layer keeps the enlarged window)
+    int box_ntt = 1;              // CRC_BOX_NTT: a boxed one-channel layer on coefficient-form input sums the window in front of the input transform (k_ntt_ct_box) -- 0: off (transform all, staged box), 1: the default block order, 2: the other order
     int hoist_rt = 0;             // CRC_HOIST_RT: keys per digit load in the hoisted rotations' K2 -- 0: the default (abi.hip: hoist_rt), 1: one launch per key, 2: relin_mac_multi_f64_kernel
     int bsgs_jt = 0;              // CRC_BSGS_JT: the inner sums of crc_diag_mac_bsgs_forms -- 0: the default (abi.hip: bsgs_jt), 1: one galois_diag_mac_kernel launch per giant index, 2: galois_diag_mac_multi_kernel
     int planes_batch = 0;         // CRC_PLANES_BATCH: the outer stage of crc_dense_planes_forms on the fp64 path -- 0: the default (abi.hip: planes_batch), 1: one key switch per step, 2: relin_mac_keyed_f64_kernel over sub-batches of steps

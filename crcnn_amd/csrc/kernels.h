@@ -8,6 +8,8 @@ static inline unsigned xcd_grid(size_t groups, unsigned G) { return (unsigned)((
 
 int k_ntt_ct(crc_ctx *c, bool inv, const u64 *src, u64 *dst, size_t count, int size, bool bsk, hipStream_t st,
              const u64 *addend, int add_sign, size_t add_group, int add_mod = 0, int pack_out = 0);
+bool k_ntt_ct_box_supported(const crc_ctx *c, int bxf, int byf);     // the boxed forward transform (nttbox.h): this ring, these moduli, this many terms
+int k_ntt_ct_box(crc_ctx *c, const u64 *src, u64 *dst, int B, int xd, int yd, int bxf, int byf, int xs, int ys, hipStream_t st);
 int k_ntt_ct_fwd_mul(crc_ctx *c, u64 *ct, size_t count, const u64 *w, size_t group, hipStream_t st);
 int k_ntt_ct_fwd_fma(crc_ctx *c, u64 *ct, size_t count, const u64 *u, const u64 *key, hipStream_t st);
 int k_ntt_ct_fwd_negmul(crc_ctx *c, u64 *ct, size_t count, const u64 *sk, hipStream_t st);

@@ -5,6 +5,7 @@
 // Integer modular arithmetic only -- no MFMA.  Lane <-> coefficient/slot, so every global access is a coalesced
 // 512 B (8 B/lane) or 1 KiB (16 B/lane) wave transaction.
 #include "kernels.h"
+#include "nttbox.h"
 #include <type_traits>
 #include <cstdlib>
 
@@ -58,6 +59,9 @@ struct NttArgs {
     // same ciphertext (the secret-key encryptor: NTT(e + Delta m) - A . s).  (Sits in what was padding in front of pp: no other member moves)
     int fma_neg;
     PlainParams pp;
+    // the boxed forward transform (ntt_rows_wave_kernel<.., BOX = true>, k_ntt_ct_box; nttbox.h has the index arithmetic): the row that is transformed is the
+    // sum of bxf byf source rows, the window of an xd x yd image at dilation (xs, ys); box_order: the block -> row map, box_images: images of the launch
+    NttBox box; int box_order; unsigned box_images;
 };
 
 // transform_to_ntt(Plaintext)'s lift of a plaintext coefficient c < t to its residue mod q_i (evaluator.cpp:1447-1486): c, or c + (q - t) for the "negative"
@@ -72,6 +76,7 @@ __device__ __forceinline__ u64 plain_lift(u64 c, const PlainParams &pp, int i, c
 
 #include "ntt_device.h"  // lpad, shoup_lazy4, reduce_small, fwd_stages / inv_stages, ntt_pass
 #include "ntt_f64.h"     // the wave-local scheme: block ownership, cross layout, u64_local_passes_*
+#include "limbred.h"     // sum_reduce16
 __device__ __forceinline__ u64 split28v(u64 v) { return (v & 0x0fffffffULL) | ((v >> 28) << 32); }      // = split28 further down
 
 // PRO: load prologue compiled into this instance -- 0: a.prologue in {0 none, 1 plain lift, 2 delta scale}; 3: relinearisation digit; 4: square products;
@@ -198,12 +203,19 @@ __global__ void __launch_bounds__(1024) ntt_rows_kernel(NttArgs a) { ntt_rows_bo
 // -> block-local drain through the gap-1 stage.  Inverse: block-local fill through the gap-1 stage (PRO 4: the square's products formed on the way) -> three
 // wave-local passes | barrier | the cross stages from the image to registers -> final reduction (PRO 5: the scaled result) -> 16-byte stores.  Same butterflies
 // on the same values as ntt_rows_body, hence the same results.  Prologues 0 / 4 / 5 without an addend; everything else stays with ntt_rows_kernel.
-template <bool INV, int PRO, int CS, bool UNS, int FMA = 0>
-__global__ void __launch_bounds__(CS == 1 ? 128 : CS == 2 ? 256 : CS == 3 ? 512 : 1024, 4) ntt_rows_wave_kernel(NttArgs a)
+// BOX (forward, prologue 0, no FMA: k_ntt_ct_box): the row fed to the transform is the sum of the bxf byf source rows of a window (a.box, nttbox.h), taken while
+// they are loaded: the terms are canonical residues below 2^55, at most 9 of them, summed in 64 bits (below 2^59) and reduced ONCE to [0, q) (sum_reduce16), so
+// the butterflies see what they see without a box and every operand bound holds as documented.  NTT(sum x_j) = sum NTT(x_j) mod q, both canonical: bit for
+// bit what transforming every term and summing afterwards gives.  The loads run in two halves of 8 points; within a half the next term's loads are issued before
+// the present term is added (two terms in flight, 16 + 16 registers of buffers next to the 32 of the sums: never all terms at once).
+template <bool INV, int PRO, int CS, bool UNS, int FMA = 0, bool BOX = false>
+__global__ void __launch_bounds__(CS == 1 ? 128 : CS == 2 ? 256 : CS == 3 ? 512 : 1024, BOX && CS <= 2 ? 5 : 4) ntt_rows_wave_kernel(NttArgs a)   // (BOX: the five
+// workgroups per CU the LDS image allows at n = 4096, as without a box -- 96 registers)
 {
     // CS = log2 n - 10 stages cross the 1024-point blocks (n = 2048 / 4096 / 8192 / 16384: 1 / 2 / 3 / 4; n = 2048 -- the ring of the reference's published
     // PlainModelTiny run -- since round 6); a thread owns E = 16 >> CS neighbouring points of every block
     constexpr int E = 16 >> CS, C = 1 << CS;
+    static_assert(!BOX || (!INV && PRO == 0 && FMA == 0), "the box belongs to the plain forward transform");
     extern __shared__ u64 sm[];
     const int n = a.n, tid = threadIdx.x;
     size_t row = blockIdx.x;
@@ -212,7 +224,12 @@ __global__ void __launch_bounds__(CS == 1 ? 128 : CS == 2 ? 256 : CS == 3 ? 512 
         if (!xcd_group(blockIdx.x, 3, a.pairs, pair, p)) return;
         row = ((pair / a.mod_count) * 3 + p) * a.mod_count + pair % a.mod_count;
     }
-    const int mloc = (int)(row % a.mod_count), mi = a.mod_base + mloc;
+    NttBoxRow br{};
+    if constexpr (BOX) {
+        if (!nttbox_block_row(a.box_order, blockIdx.x, a.box_images, a.box, a.mod_count, br)) return;
+        row = nttbox_row_of(br, a.box, a.mod_count);
+    }
+    const int mloc = BOX ? br.mod : (int)(row % a.mod_count), mi = a.mod_base + mloc;
     const ModParams m = a.mods[mi];
     const u64 q = m.q, q2 = m.two_q;
     const float rq = 1.0f / (float)((u32)(q >> 32) + 1);
@@ -223,6 +240,34 @@ __global__ void __launch_bounds__(CS == 1 ? 128 : CS == 2 ? 256 : CS == 3 ? 512 
         const size_t srow = a.dst_ct_rows ? (row / a.dst_ct_rows) * a.src_ct_rows + row % a.dst_ct_rows : (a.src_rows_per_item ? (row / a.mod_count) : row);
         const u64 *src = a.src + srow * (size_t)n;
         u64 x[16];
+        if constexpr (BOX) {
+            // points h 8 .. h 8 + 7 of x: blocks c = h C/2 .. of the cross layout (E = 8: half a block)
+            const int terms = a.box.bxf * a.box.byf;
+            auto load8 = [&](u64 (&v)[8], int h, int t) {
+                const int ta = t / a.box.byf, tb = t - ta * a.box.byf;
+                const u64 *tp = a.src + nttbox_src_row(br, a.box, a.mod_count, ta, tb) * (size_t)n;
+#pragma unroll
+                for (int i = 0; i < 8; i += (E == 1 ? 1 : 2)) {
+                    const int p = h * 8 + i, c = p / E, e = p % E;
+                    if constexpr (E == 1) v[i] = tp[pt(c, 0)];
+                    else { const ulonglong2 w = ld2(tp + pt(c, e)); v[i] = w.x; v[i + 1] = w.y; }
+                }
+            };
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                u64 cur[8], nxt[8], acc[8];
+#pragma unroll
+                for (int i = 0; i < 8; i++) acc[i] = 0;
+                load8(cur, h, 0);
+                for (int t = 1; t < terms; t++) {
+                    load8(nxt, h, t);
+#pragma unroll
+                    for (int i = 0; i < 8; i++) { acc[i] += cur[i]; cur[i] = nxt[i]; }
+                }
+#pragma unroll
+                for (int i = 0; i < 8; i++) x[h * 8 + i] = sum_reduce16(acc[i] + cur[i], q);
+            }
+        } else {
 #pragma unroll
         for (int c = 0; c < C; c++) {
             if constexpr (E == 1) x[c] = src[pt(c, 0)];
@@ -230,6 +275,7 @@ __global__ void __launch_bounds__(CS == 1 ? 128 : CS == 2 ? 256 : CS == 3 ? 512 
 #pragma unroll
                 for (int e = 0; e < E; e += 2) { const ulonglong2 v = ld2(src + pt(c, e)); x[c * E + e] = v.x; x[c * E + e + 1] = v.y; }
             }
+        }
         }
 #pragma unroll
         for (int e = 0; e < E; e++) {
@@ -596,6 +642,20 @@ __global__ void __launch_bounds__(1024) ntt_rows_prefetch_kernel(NttArgs a)
     }
 }
 
+// lazy butterflies need (1 + 4 log2 n) q < 2^64 (and the float quotient estimate a q of 45+ bits): every coefficient modulus of the
+// reference's parameter sets qualifies (54..55 bits), the 61-bit auxiliary base of Square does not
+static bool ntt_lazy_moduli(const crc_ctx *c, int mod_base, int mod_count)
+{
+    for (int i = mod_base; i < mod_base + mod_count; i++) if (c->tabs[i].m.bits > 57 || c->tabs[i].m.bits < 45) return false;
+    return true;
+}
+// the ring's bit of CRC_NTT_WAVE is on (ntt_launch below has the bits): the ring has a wave-local kernel and the tuning has not switched it off
+static bool ntt_wave_ring(const crc_ctx *c, bool with_prologue)
+{
+    const int sel = c->tune.ntt_wave < 0 ? 47 : c->tune.ntt_wave;
+    const int bit = c->n == 8192 ? 0 : c->n == 4096 ? 1 : c->n == 16384 ? (with_prologue ? 3 : 2) : c->n == 2048 ? 5 : -1;
+    return bit >= 0 && ((sel >> bit) & 1);
+}
 static int ntt_launch(crc_ctx *c, bool inv, NttArgs &a, size_t rows, hipStream_t st)
 {
     if (rows == 0) return CRC_OK;
@@ -604,10 +664,7 @@ static int ntt_launch(crc_ctx *c, bool inv, NttArgs &a, size_t rows, hipStream_t
     int nt = c->n / 8; if (nt < 64) nt = 64; if (nt > 1024) nt = 1024;
     size_t lds = (size_t)c->n * 8;
     if (lds > 128 * 1024) return CRC_ERR_UNSUPPORTED;                   // (n = 32768: the row does not fit one workgroup's LDS image, in halves or whole)
-    // lazy butterflies need (1 + 4 log2 n) q < 2^64 (and the float quotient estimate a q of 45+ bits): every coefficient modulus of the
-    // reference's parameter sets qualifies (54..55 bits), the 61-bit auxiliary base of Square does not
-    bool lazy = true;
-    for (int i = a.mod_base; i < a.mod_base + a.mod_count; i++) if (c->tabs[i].m.bits > 57 || c->tabs[i].m.bits < 45) lazy = false;
+    const bool lazy = ntt_lazy_moduli(c, a.mod_base, a.mod_count);
     const int cus = c->cus;
     if ((a.prologue == 3 && inv) || ((a.prologue == 4 || a.prologue == 5 || a.prologue == 6) && !inv)) return CRC_ERR_INVALID_ARGUMENT;
     const bool two_src = a.prologue == 6;                               // (fma_k is the second ciphertext there, not an epilogue)
@@ -619,8 +676,7 @@ static int ntt_launch(crc_ctx *c, bool inv, NttArgs &a, size_t rows, hipStream_t
     {
         // (bit 5, round 6: n = 2048 -- one cross stage, two waves per workgroup)
         const int sel = c->tune.ntt_wave < 0 ? 47 : c->tune.ntt_wave;
-        const int bit = c->n == 8192 ? 0 : c->n == 4096 ? 1 : c->n == 16384 ? (a.prologue ? 3 : 2) : c->n == 2048 ? 5 : -1;
-        if (bit >= 0 && ((sel >> bit) & 1) && lazy && !a.addend && (a.prologue == 0 || a.prologue == 4 || a.prologue == 5 || two_src)) {
+        if (ntt_wave_ring(c, a.prologue != 0) && lazy && !a.addend && (a.prologue == 0 || a.prologue == 4 || a.prologue == 5 || two_src)) {
             lds = (size_t)c->n * 8;
             // inverse transforms over moduli below 2^55 take the butterflies that do not halve (inv_stages_unscaled; CRC_NTT_WAVE bit 4 switches them off): the
             // table of plain inverse powers, and n^-1 in the constant of the closing multiplication
@@ -703,6 +759,38 @@ int k_ntt_ct(crc_ctx *c, bool inv, const u64 *src, u64 *dst, size_t count, int s
     a.addend = addend; a.add_sign = add_sign; a.rows_per_ct = size * a.mod_count; a.add_group = (long long)(add_group ? add_group : 1);
     a.add_mode = 1; a.add_mod = add_mod;
     return ntt_launch(c, inv, a, count * size * a.mod_count, st);
+}
+
+// The boxed forward transform: src = B images of xd x yd coefficient-form size-2 ciphertexts, dst = B images of xdo x ydo NTT-form ones, each the transform of
+// the bxf x byf window sum of the input at dilation (xs, ys) (nttbox.h; ntt_rows_wave_kernel<.., BOX = true>); src != dst.  Only the wave-local kernel has the
+// box: CRC_ERR_UNSUPPORTED exactly where ntt_launch would not take that kernel for a plain forward transform, and for more than 9 terms.
+// order: the block -> row map of nttbox.h (1: XCD-grouped, 0: plain).  NTT_BOX_ORDER is the one that measured faster (profiles/ntt_box.md); the tuning key
+// box_ntt = 2 runs the other
+#define NTT_BOX_ORDER 1
+bool k_ntt_ct_box_supported(const crc_ctx *c, int bxf, int byf)
+{
+    return bxf >= 1 && byf >= 1 && bxf * byf <= NTTBOX_MAX_TERMS && ntt_wave_ring(c, false) && ntt_lazy_moduli(c, 0, c->k);
+}
+int k_ntt_ct_box(crc_ctx *c, const u64 *src, u64 *dst, int B, int xd, int yd, int bxf, int byf, int xs, int ys, hipStream_t st)
+{
+    const NttBox g = nttbox_make(xd, yd, bxf, byf, xs, ys);
+    if (B < 0 || !nttbox_ok(g) || src == dst) return CRC_ERR_INVALID_ARGUMENT;
+    if (!k_ntt_ct_box_supported(c, bxf, byf)) return CRC_ERR_UNSUPPORTED;
+    if (B == 0) return CRC_OK;
+    NttArgs a{};
+    a.src = src; a.dst = dst; a.mods = c->d_mods; a.n = c->n; a.logn = c->logn; a.w = reinterpret_cast<const ulonglong2 *>(c->d_rp);
+    a.mod_base = 0; a.mod_count = c->k;
+    a.box = g; a.box_images = (unsigned)B; a.box_order = c->tune.box_ntt == 2 ? 1 - NTT_BOX_ORDER : NTT_BOX_ORDER;
+    const size_t grid = nttbox_grid(a.box_order, (size_t)B, g, c->k);
+    if (grid > 0x7fffffffULL) return CRC_ERR_INVALID_ARGUMENT;            // (blocks and rows fit 31 bits: nttbox_block_row)
+    const int cs = c->logn - 10;
+    auto kw = cs == 1 ? ntt_rows_wave_kernel<false, 0, 1, false, 0, true> : cs == 2 ? ntt_rows_wave_kernel<false, 0, 2, false, 0, true>
+            : cs == 3 ? ntt_rows_wave_kernel<false, 0, 3, false, 0, true> : ntt_rows_wave_kernel<false, 0, 4, false, 0, true>;
+    const size_t lds = (size_t)c->n * 8;
+    { const int rc = crc_ctx_ensure_lds(c, (const void *)kw, lds); if (rc) return rc; }
+    hipLaunchKernelGGL(kw, dim3((unsigned)grid), dim3(c->n / 16), lds, st, a);
+    HIPCHK(hipGetLastError());
+    return CRC_OK;
 }
 
 // forward NTT in place of size-2 ciphertexts that leave as NTT(row) + u[ct][i] . key[p][i] (u: [count][k][n], key: [2][k][n], both NTT form) -- the device

@@ -115,7 +115,7 @@ int  crc_ctx_table(const crc_ctx *ctx, const char *name, uint64_t *h_out, int ca
 /* Tuning switches of tools/ and the tests (none is needed for normal use).  The engine reads its environment (CRC_MFMA_VARIANT, CRC_CONV1_PASS_BYTES, ...)
  * exactly
  * once, inside crc_ctx_create; this call changes one switch of a context nobody is launching on: "mfma_variant", "mfma_order", "mfma_ring", "conv1_waves",
- * "conv1_narrow" (0: a one-channel convolution with 17-20 filters runs its second filter group like a full one), "conv1_pass_bytes", "conv1_box" (crc_plan_conv1_box), "hoist_pool" (crc_plan_hoist_pool), "limb_pack_group", "mac2_cfg", "mac_order", "mac_regstage", "ntt_inv61_loose", "ntt_split", "mfma_min_steps", "scalar_mac" (crc_plan_mac_scalar), "f64_radix",
+ * "conv1_narrow" (0: a one-channel convolution with 17-20 filters runs its second filter group like a full one), "conv1_pass_bytes", "conv1_box" (crc_plan_conv1_box), "box_ntt" (CRC_BOX_NTT; a boxed one-channel layer on coefficient-form input sums the window in front of its input transform, crc_ntt_fwd_box: 0 off, 1 the default block order, 2 the other order), "hoist_pool" (crc_plan_hoist_pool), "limb_pack_group", "mac2_cfg", "mac_order", "mac_regstage", "ntt_inv61_loose", "ntt_split", "mfma_min_steps", "scalar_mac" (crc_plan_mac_scalar), "f64_radix",
  * "relin_mac_ct", "poly_tail" (crc_poly2_relin_forms),
  * "relin_path" (1: key switching over the coefficient moduli, as the reference does it, instead of over two fp64 primes), "sq_path" (1: the square's auxiliary
  * base is SEAL's 61-bit
@@ -195,6 +195,11 @@ int crc_plain_to_delta(crc_ctx *ctx, const uint64_t *d_plain, size_t count, int 
  * ------------------------------------------------------------------------------------------------------------- */
 int crc_ntt_fwd(crc_ctx *ctx, uint64_t *d_ct, size_t count, int size, void *stream);
 int crc_ntt_inv(crc_ctx *ctx, uint64_t *d_ct, size_t count, int size, void *stream);
+/* The forward transform of window sums, out of place (d_src != d_dst): d_src = B images of xd x yd coefficient-form size-2 ciphertexts with canonical residues,
+ * d_dst = B images of xdo x ydo = (xd - (bxf-1) xs) x (yd - (byf-1) ys) NTT-form ones, pixel (r, c) = NTT(sum over a < bxf, b < byf of src(r + a xs, c + b ys)
+ * mod q) -- bit for bit the sum mod q of the terms' crc_ntt_fwd.  The sum is taken while the transform loads its row.  CRC_ERR_UNSUPPORTED for rings other than
+ * 2048 / 4096 / 8192 / 16384, moduli outside 45..57 bits, the ring's bit of "ntt_wave" off, and boxes of more than 9 terms. */
+int crc_ntt_fwd_box(crc_ctx *ctx, const uint64_t *d_src, uint64_t *d_dst, int B, int xd, int yd, int bxf, int byf, int xs, int ys, void *stream);
 /* same over the Bsk moduli (rows are [count][kbsk][n]); exposed for unit tests of the Square pipeline */
 int crc_ntt_fwd_bsk(crc_ctx *ctx, uint64_t *d_rows, size_t count, void *stream);
 int crc_ntt_inv_bsk(crc_ctx *ctx, uint64_t *d_rows, size_t count, void *stream);
