@@ -1315,8 +1315,12 @@ extern "C" int crc_sum_slots_forms(crc_ctx *c, const uint64_t *d_x, int in_form,
 // With the conjugated key K'_g = sigma_g^-1(K_g) (crc_galois_conjugate_keys),  H_g(ct) := sigma_g((c0, 0) + KeySwitch(c1; K'_g))  decrypts to sigma_g(m).  The key
 // switch reads c1 itself, so the digits and their transforms (K1) are made once per pass and serve every element; per element run K2 + K3 into NTT form and the
 // NTT-domain gather.  Where the fp64 key switch does not apply, k_relinearize runs per element with the conjugated key: the same exact function on Z_q.
-// Work: [coefficient copy of an NTT-form pass][size-3 rows (c0, 0, c1 (q/q_i)^-1)][zc key-switch results of a pass][nk prepared keys, made by pass 0][scratch of
-// the key switch].  A pass is square_chunk ciphertexts, fewer once more than 8 results are kept at once: it shrinks with R.
+// Every entry point of the family is the same driver around its own consumer kernel.  After the argument checks it carves the work space and builds one
+// HoistCall; hoist_prepare_keys makes the fp64 form of the call's keys; then, per pass of L.step ciphertexts, hoist_pass_head makes the digits of the pass and
+// hoist_group turns GALOIS_DIAG_MAX elements at a time into the operands z[] of the consumer.  A stage that rotates sums it has just formed (the giant stage, the
+// dense layer's outer stage) takes each through hoist_switch_own.
+// Work: [coefficient copy of an NTT-form pass][size-3 rows (c0, 0, c1 (q/q_i)^-1)][zc key-switch results of a pass][nk prepared keys][scratch of the key
+// switch].  A pass is square_chunk ciphertexts, fewer once more than 8 results are kept at once: it shrinks with R.
 struct HoistWork { u64 *xc, *x3, *z, *kp, *rest, *u; size_t step, kpw; };
 enum { HOIST_Z_PASSES = 8 };
 // uc: further ciphertexts a pass keeps besides the zc results (the inner sums of crc_diag_mac_bsgs_forms; none elsewhere), in L.u behind every other region
@@ -1370,28 +1374,85 @@ static int hoist_args_ok(const crc_ctx *c, const uint64_t *d_x, int in_form, siz
     if (ranges_overlap(d_work, wb, d_x, 8 * count * ctw) || ranges_overlap(d_work, wb, d_y, 8 * y_cts * ctw)) return 0;
     return ranges_overlap(d_x, 8 * count * ctw, d_y, 8 * y_cts * ctw) ? 0 : 1;
 }
-// one pass' operand and digits: xin (in_form) -> L.x3 = (c0, 0, c1 (q/q_i)^-1) and, on the fp64 path, E in L.rest.  first: the pass that prepares the keys
-static int hoist_pass_head(crc_ctx *c, const HoistWork &L, const u64 *xin, int in_form, size_t ch, const int *at, int R, const u64 *d_cgk, int dbc, bool f64, bool first,
-                           void *stream)
+// the read-only operand of a consumer (plaintext rows, packed weights): there, aligned, and apart from everything the call writes
+static int hoist_operand_ok(const crc_ctx *c, const uint64_t *d_op, size_t op_bytes, const uint64_t *d_y, size_t y_cts, const void *d_work, size_t wb)
 {
-    const size_t kw = crc_evk_words(c, dbc);
-    if (in_form == CRC_NTT) { RUN(k_ntt_ct(c, true, xin, L.xc, ch, 2, false, S(stream), nullptr, 0, 0, 0)); xin = L.xc; }
-    RUN(k_galois_permute(c, xin, ch, 1, false, L.x3, S(stream)));
-    if (!f64) return CRC_OK;
-    if (first)                                                          // (the preparation borrows the scratch: before E is put there)
-        for (int r = 0; r < R; r++) if (at[r] >= 0) RUN(k_relin64_prepare_keys(c, d_cgk + (size_t)at[r] * kw, dbc, L.kp + (size_t)r * L.kpw, L.rest, S(stream)));
-    return k_relin64_digits(c, L.x3, 3, 2, ch, dbc, L.rest, S(stream));
+    if (!d_op || !aligned16(d_op)) return 0;
+    return ranges_overlap(d_op, op_bytes, d_y, 8 * y_cts * crc_ct_words(c, 2)) || ranges_overlap(d_op, op_bytes, d_work, wb) ? 0 : 1;
 }
-// (c0, 0) + KeySwitch(c1; K'_g) of the pass in NTT form -> z
-static int hoist_switch(crc_ctx *c, const HoistWork &L, size_t ch, int r, int key_at, const u64 *d_cgk, int dbc, bool f64, bool first, u64 *z, void *stream)
+// One call of the family, built once after the argument checks.  at[r]: the key of element r in the set (hoist_keys), whose prepared form lives in slot r of L.kp
+// unless a caller says otherwise; elements [0, n) are the ones hoist_group serves (further ones: the giant elements).  f64: the fp64 key switch runs; pair: two
+// keys per digit load in its K2; keyed: one of the n elements has a key, so the digits of a pass are needed at all
+struct HoistCall { crc_ctx *c; HoistWork L; const u64 *d_cgk; int dbc; void *stream; std::vector<int> at; bool f64, pair, keyed; };
+static HoistCall hoist_call(crc_ctx *c, const HoistWork &L, const u64 *d_cgk, int dbc, void *stream, std::vector<int> at, int n)
 {
-    if (f64) return k_relin64_from_digits(c, L.x3, 3, ch, dbc, z, L.rest, L.kp + (size_t)r * L.kpw, S(stream), true);
-    return k_relinearize(c, L.x3, ch, d_cgk + (size_t)key_at * crc_evk_words(c, dbc), dbc, z, L.rest, L.kp + (size_t)r * L.kpw, S(stream), true, true, !first);
+    HoistCall H{c, L, d_cgk, dbc, stream, std::move(at), false, false, false};
+    H.f64 = c->tune.relin_path != 1 && k_relin64_supported(c, dbc);
+    H.pair = H.f64 && hoist_rt(c) == 2;
+    for (int r = 0; r < n; r++) H.keyed = H.keyed || H.at[r] >= 0;
+    return H;
+}
+// the fp64 form of the keys of elements [first, first + n) into their slots, once per call.  The preparation borrows the scratch, so it runs before the first
+// pass puts E there.  (The other path prepares a key inside the first k_relinearize that uses it: hoist_switch's `first`.)
+static int hoist_prepare_keys(const HoistCall &H, int first, int n)
+{
+    if (!H.f64) return CRC_OK;
+    const size_t kw = crc_evk_words(H.c, H.dbc);
+    for (int r = first; r < first + n; r++)
+        if (H.at[r] >= 0) RUN(k_relin64_prepare_keys(H.c, H.d_cgk + (size_t)H.at[r] * kw, H.dbc, H.L.kp + (size_t)r * H.L.kpw, H.L.rest, S(H.stream)));
+    return CRC_OK;
+}
+// one pass' operand and digits: xin (in_form) -> L.x3 = (c0, 0, c1 (q/q_i)^-1) and, on the fp64 path, E in L.rest
+static int hoist_pass_head(const HoistCall &H, const u64 *xin, int in_form, size_t ch)
+{
+    const HoistWork &L = H.L;
+    if (in_form == CRC_NTT) { RUN(k_ntt_ct(H.c, true, xin, L.xc, ch, 2, false, S(H.stream), nullptr, 0, 0, 0)); xin = L.xc; }
+    RUN(k_galois_permute(H.c, xin, ch, 1, false, L.x3, S(H.stream)));
+    return H.f64 ? k_relin64_digits(H.c, L.x3, 3, 2, ch, H.dbc, L.rest, S(H.stream)) : CRC_OK;
+}
+// (c0, 0) + KeySwitch(c1; K'_g) of the pass in NTT form -> z, for element r with its prepared key in `slot`.  first: nothing has prepared that slot yet
+static int hoist_switch(const HoistCall &H, size_t ch, int r, int slot, bool first, u64 *z)
+{
+    const HoistWork &L = H.L;
+    if (H.f64) return k_relin64_from_digits(H.c, L.x3, 3, ch, H.dbc, z, L.rest, L.kp + (size_t)slot * L.kpw, S(H.stream), true);
+    return k_relinearize(H.c, L.x3, ch, H.d_cgk + (size_t)H.at[r] * crc_evk_words(H.c, H.dbc), H.dbc, z, L.rest, L.kp + (size_t)slot * L.kpw, S(H.stream), true, true,
+                         !first);
 }
 // the same for the two elements ra, rb with one read of the digit values (fp64 path only)
-static int hoist_switch2(crc_ctx *c, const HoistWork &L, size_t ch, int ra, int rb, int dbc, u64 *za, u64 *zb, void *stream)
+static int hoist_switch2(const HoistCall &H, size_t ch, int ra, int rb, u64 *za, u64 *zb)
 {
-    return k_relin64_from_digits2(c, L.x3, 3, ch, dbc, za, zb, L.rest, L.kp + (size_t)ra * L.kpw, L.kp + (size_t)rb * L.kpw, S(stream), true);
+    const HoistWork &L = H.L;
+    return k_relin64_from_digits2(H.c, L.x3, 3, ch, H.dbc, za, zb, L.rest, L.kp + (size_t)ra * L.kpw, L.kp + (size_t)rb * L.kpw, S(H.stream), true);
+}
+// a key switch of an inner sum on its own digits: u (NTT form, ch ciphertexts) -> inverse transform, (c0, 0, c1 (q/q_i)^-1), K1, K2 + K3 under the key of
+// element r -> over u, which nothing reads any more
+static int hoist_switch_own(const HoistCall &H, u64 *u, size_t ch, int r, int slot, bool first)
+{
+    RUN(hoist_pass_head(H, u, CRC_NTT, ch));
+    return hoist_switch(H, ch, r, slot, first, u);
+}
+// The operands of elements [r0, r0 + rn) of one pass, rn <= the zc of the layout: z[i] is (c0, 0) + KeySwitch(c1; K'_g) in slot i of L.z for a keyed element
+// and the pass itself in NTT form for g = 1 -- xin on NTT input, otherwise ONE transformed copy per group that its elements 1 share.  Where two keys go per digit
+// load a keyed element waits for the next keyed one of the group and the two share a K2; the last runs alone.  first: as hoist_switch
+static int hoist_group(const HoistCall &H, const u64 *xin, int in_form, size_t ch, bool first, int r0, int rn, const u64 **z)
+{
+    const size_t uj = ch * crc_ct_words(H.c, 2);
+    const u64 *same = in_form == CRC_NTT ? xin : nullptr;
+    int held = -1;
+    for (int i = 0; i < rn; i++) {
+        const int r = r0 + i;
+        u64 *zi = H.L.z + (size_t)i * uj;
+        z[i] = zi;
+        if (H.at[r] < 0) {
+            if (!same) { RUN(ntt_copy(H.c, xin, ch, zi, H.stream)); same = zi; }
+            z[i] = same;
+        }
+        else if (!H.pair) RUN(hoist_switch(H, ch, r, r, first, zi));
+        else if (held < 0) held = i;
+        else { RUN(hoist_switch2(H, ch, r0 + held, r, H.L.z + (size_t)held * uj, zi)); held = -1; }
+    }
+    if (held >= 0) RUN(hoist_switch(H, ch, r0 + held, r0 + held, first, H.L.z + (size_t)held * uj));
+    return CRC_OK;
 }
 extern "C" int crc_galois_permute_ntt_dev(crc_ctx *c, const uint64_t *d_in, size_t rows, uint64_t g, uint64_t *d_out, void *stream)
 {
@@ -1428,33 +1489,32 @@ extern "C" int crc_rotate_hoisted_forms(crc_ctx *c, const uint64_t *d_x, int in_
     if (!hoist_keys(c, gs, R, elts, n_elts, at.data())) return CRC_ERR_INVALID_ARGUMENT;
     if (count == 0) return CRC_OK;
     const size_t ctw = crc_ct_words(c, 2);
-    WorkArena a(d_work);
-    const HoistWork L = hoist_layout(c, count, R, 2, dbc, a);
-    const bool f64 = c->tune.relin_path != 1 && k_relin64_supported(c, dbc), pair = f64 && hoist_rt(c) == 2;
-    bool any = false;
+    std::vector<int> idx, kat;                                          // the keyed elements alone: where each result goes, its key; element i has key slot i
+    std::vector<u64> kg;
     for (int r = 0; r < R; r++) {
-        if (at[r] >= 0) { any = true; continue; }
+        if (at[r] >= 0) { idx.push_back(r); kat.push_back(at[r]); kg.push_back(gs[r]); continue; }
         u64 *yr = d_y + (size_t)r * count * ctw;                       // g = 1: the same ciphertext in the requested form
         HIPCHK(hipMemcpyAsync(yr, d_x, 8 * count * ctw, hipMemcpyDeviceToDevice, S(stream)));
         if (in_form != out_form) RUN(out_form == CRC_NTT ? crc_ntt_fwd(c, yr, count, 2, stream) : crc_ntt_inv(c, yr, count, 2, stream));
     }
-    if (!any) return CRC_OK;
-    for (size_t o = 0; o < count; o += L.step) {
-        const size_t ch = pass_len(count, o, L.step);
-        RUN(hoist_pass_head(c, L, d_x + o * ctw, in_form, ch, at.data(), R, d_cgk, dbc, f64, o == 0, stream));
-        for (int r = 0; r < R; r++) {
-            if (at[r] < 0) continue;
-            int r2 = -1;                                                // the next keyed element shares this one's K2 where two keys go per digit load
-            if (pair) for (int i = r + 1; i < R && r2 < 0; i++) if (at[i] >= 0) r2 = i;
-            if (r2 >= 0) RUN(hoist_switch2(c, L, ch, r, r2, dbc, L.z, L.z + ch * ctw, stream));
-            else RUN(hoist_switch(c, L, ch, r, at[r], d_cgk, dbc, f64, o == 0, L.z, stream));
-            const int rs[2] = {r, r2};
-            for (int i = 0; i < 2 && rs[i] >= 0; i++) {
-                u64 *yr = d_y + ((size_t)rs[i] * count + o) * ctw;
-                RUN(k_galois_permute_ntt(c, L.z + (size_t)i * ch * ctw, ch * 2 * c->k, gs[rs[i]], yr, S(stream)));
+    const int nk = (int)idx.size();
+    if (!nk) return CRC_OK;
+    WorkArena a(d_work);
+    const HoistCall H = hoist_call(c, hoist_layout(c, count, R, 2, dbc, a), d_cgk, dbc, stream, kat, nk);
+    const int gw = H.pair ? 2 : 1;                                      // a group is what shares a K2: each keyed element with the next keyed one
+    RUN(hoist_prepare_keys(H, 0, nk));
+    for (size_t o = 0; o < count; o += H.L.step) {
+        const size_t ch = pass_len(count, o, H.L.step);
+        RUN(hoist_pass_head(H, d_x + o * ctw, in_form, ch));
+        for (int r0 = 0; r0 < nk; r0 += gw) {
+            const int rn = nk - r0 < gw ? nk - r0 : gw;
+            const u64 *z[2];
+            RUN(hoist_group(H, d_x + o * ctw, in_form, ch, o == 0, r0, rn, z));
+            for (int i = 0; i < rn; i++) {
+                u64 *yr = d_y + ((size_t)idx[r0 + i] * count + o) * ctw;
+                RUN(k_galois_permute_ntt(c, z[i], ch * 2 * c->k, kg[r0 + i], yr, S(stream)));
                 if (out_form == CRC_COEFF) RUN(crc_ntt_inv(c, yr, ch, 2, stream));
             }
-            if (r2 >= 0) r = r2;                                        // (the elements between them are copies: g = 1)
         }
     }
     return CRC_OK;
@@ -1466,36 +1526,26 @@ extern "C" int crc_diag_mac_forms(crc_ctx *c, const uint64_t *d_x, int in_form, 
                                   const uint64_t *elts, int n_elts, int dbc, uint64_t *d_y, int out_form, void *d_work, void *stream)
 {
     CHECK_CTX(c);
-    if (R < 1 || R > (1 << 20) || !d_p_ntt || !aligned16(d_p_ntt)) return CRC_ERR_INVALID_ARGUMENT;
-    if (!hoist_args_ok(c, d_x, in_form, count, gs, R, d_cgk, elts, n_elts, dbc, d_y, count, out_form, d_work, hoist_bytes(c, count, R, diag_zc(R), dbc)))
-        return CRC_ERR_INVALID_ARGUMENT;
+    if (R < 1 || R > (1 << 20)) return CRC_ERR_INVALID_ARGUMENT;
+    const size_t wb = hoist_bytes(c, count, R, diag_zc(R), dbc), ctw = crc_ct_words(c, 2), rowp = (size_t)c->k * c->n;
+    if (!hoist_args_ok(c, d_x, in_form, count, gs, R, d_cgk, elts, n_elts, dbc, d_y, count, out_form, d_work, wb) ||
+        !hoist_operand_ok(c, d_p_ntt, 8 * (size_t)R * rowp, d_y, count, d_work, wb)) return CRC_ERR_INVALID_ARGUMENT;
     std::vector<int> at((size_t)R);
     if (!hoist_keys(c, gs, R, elts, n_elts, at.data())) return CRC_ERR_INVALID_ARGUMENT;
     if (count == 0) return CRC_OK;
-    const size_t ctw = crc_ct_words(c, 2), rowp = (size_t)c->k * c->n;
     const int zc = diag_zc(R);
     WorkArena a(d_work);
-    const HoistWork L = hoist_layout(c, count, R, zc, dbc, a);
-    const bool f64 = c->tune.relin_path != 1 && k_relin64_supported(c, dbc), pair = f64 && hoist_rt(c) == 2;
-    for (size_t o = 0; o < count; o += L.step) {
-        const size_t ch = pass_len(count, o, L.step);
+    const HoistCall H = hoist_call(c, hoist_layout(c, count, R, zc, dbc, a), d_cgk, dbc, stream, at, R);
+    RUN(hoist_prepare_keys(H, 0, R));
+    for (size_t o = 0; o < count; o += H.L.step) {
+        const size_t ch = pass_len(count, o, H.L.step);
         const u64 *xin = d_x + o * ctw;
-        RUN(hoist_pass_head(c, L, xin, in_form, ch, at.data(), R, d_cgk, dbc, f64, o == 0, stream));
+        RUN(hoist_pass_head(H, xin, in_form, ch));
         for (int r0 = 0; r0 < R; r0 += zc) {
             const int rn = R - r0 < zc ? R - r0 : zc;
             const u64 *z[GALOIS_DIAG_MAX], *p[GALOIS_DIAG_MAX];
-            int held = -1;                                              // a keyed element that waits for a partner (two keys per digit load)
-            for (int i = 0; i < rn; i++) {
-                const int r = r0 + i;
-                u64 *zi = L.z + (size_t)i * ch * ctw;
-                z[i] = zi; p[i] = d_p_ntt + (size_t)r * rowp;
-                if (at[r] >= 0 && pair && held < 0) held = i;
-                else if (at[r] >= 0 && pair) { RUN(hoist_switch2(c, L, ch, r0 + held, r, dbc, L.z + (size_t)held * ch * ctw, zi, stream)); held = -1; }
-                else if (at[r] >= 0) RUN(hoist_switch(c, L, ch, r, at[r], d_cgk, dbc, f64, o == 0, zi, stream));
-                else if (in_form == CRC_NTT) z[i] = xin;               // g = 1: x itself, in NTT form
-                else RUN(ntt_copy(c, xin, ch, zi, stream));
-            }
-            if (held >= 0) RUN(hoist_switch(c, L, ch, r0 + held, at[r0 + held], d_cgk, dbc, f64, o == 0, L.z + (size_t)held * ch * ctw, stream));
+            RUN(hoist_group(H, xin, in_form, ch, o == 0, r0, rn, z));
+            for (int i = 0; i < rn; i++) p[i] = d_p_ntt + (size_t)(r0 + i) * rowp;
             RUN(k_galois_diag_mac(c, z, p, gs + r0, rn, ch, r0 != 0, d_y + o * ctw, S(stream)));
         }
     }
@@ -1525,45 +1575,29 @@ extern "C" int crc_diag_mac_bsgs_forms(crc_ctx *c, const uint64_t *d_x, int in_f
                                        void *d_work, void *stream)
 {
     CHECK_CTX(c);
-    if (!bsgs_counts_ok(B, G) || !gg || !d_p_ntt || !aligned16(d_p_ntt)) return CRC_ERR_INVALID_ARGUMENT;
-    const size_t wb = bsgs_bytes(c, count, B, G, dbc), ctw = crc_ct_words(c, 2), rowp = (size_t)c->k * c->n, pb = 8 * (size_t)G * B * rowp;
-    if (!hoist_args_ok(c, d_x, in_form, count, gb, B, d_cgk, elts, n_elts, dbc, d_y, count, out_form, d_work, wb)) return CRC_ERR_INVALID_ARGUMENT;
-    if (ranges_overlap(d_p_ntt, pb, d_y, 8 * count * ctw) || ranges_overlap(d_p_ntt, pb, d_work, wb)) return CRC_ERR_INVALID_ARGUMENT;
+    if (!bsgs_counts_ok(B, G) || !gg) return CRC_ERR_INVALID_ARGUMENT;
+    const size_t wb = bsgs_bytes(c, count, B, G, dbc), ctw = crc_ct_words(c, 2), rowp = (size_t)c->k * c->n;
+    if (!hoist_args_ok(c, d_x, in_form, count, gb, B, d_cgk, elts, n_elts, dbc, d_y, count, out_form, d_work, wb) ||
+        !hoist_operand_ok(c, d_p_ntt, 8 * (size_t)G * B * rowp, d_y, count, d_work, wb)) return CRC_ERR_INVALID_ARGUMENT;
     std::vector<int> at((size_t)B + G);                                 // the key of every baby element, then of every giant element
     if (!hoist_keys(c, gb, B, elts, n_elts, at.data()) || !hoist_keys(c, gg, G, elts, n_elts, at.data() + B)) return CRC_ERR_INVALID_ARGUMENT;
     if (count == 0) return CRC_OK;
-    const size_t kw = crc_evk_words(c, dbc);
     const int zc = diag_zc(B);
     WorkArena a(d_work);
-    const HoistWork L = hoist_layout(c, count, B + G, zc, dbc, a, G);
-    const bool f64 = c->tune.relin_path != 1 && k_relin64_supported(c, dbc), pair = f64 && hoist_rt(c) == 2;
+    const HoistCall H = hoist_call(c, hoist_layout(c, count, B + G, zc, dbc, a, G), d_cgk, dbc, stream, at, B);
+    const HoistWork &L = H.L;
     const bool flat = G == 1 && gg[0] == 1;                             // one inner sum that is the result: crc_diag_mac_forms
     std::vector<const u64 *> zs((size_t)G);
-    bool baby_keyed = false;                                            // (no digits of x where every baby element is 1)
-    for (int b = 0; b < B; b++) baby_keyed = baby_keyed || at[b] >= 0;
+    RUN(hoist_prepare_keys(H, 0, B + G));
     for (size_t o = 0; o < count; o += L.step) {
         const size_t ch = pass_len(count, o, L.step), uj = ch * ctw;
         const u64 *xin = d_x + o * ctw;
         u64 *u = flat ? d_y + o * ctw : L.u;
-        if (o == 0 && f64)                                              // (the giant keys, like the baby keys in hoist_pass_head: before E is put into the scratch)
-            for (int j = 0; j < G; j++)
-                if (at[B + j] >= 0) RUN(k_relin64_prepare_keys(c, d_cgk + (size_t)at[B + j] * kw, dbc, L.kp + (size_t)(B + j) * L.kpw, L.rest, S(stream)));
-        if (baby_keyed) RUN(hoist_pass_head(c, L, xin, in_form, ch, at.data(), B, d_cgk, dbc, f64, o == 0, stream));
+        if (H.keyed) RUN(hoist_pass_head(H, xin, in_form, ch));         // (no digits of x where every baby element is 1)
         for (int r0 = 0; r0 < B; r0 += zc) {
             const int rn = B - r0 < zc ? B - r0 : zc;
             const u64 *z[GALOIS_DIAG_MAX], *p[GALOIS_DIAG_MAX];
-            int held = -1;                                              // a keyed element that waits for a partner (two keys per digit load)
-            for (int i = 0; i < rn; i++) {
-                const int r = r0 + i;
-                u64 *zi = L.z + (size_t)i * uj;
-                z[i] = zi;
-                if (at[r] >= 0 && pair && held < 0) held = i;
-                else if (at[r] >= 0 && pair) { RUN(hoist_switch2(c, L, ch, r0 + held, r, dbc, L.z + (size_t)held * uj, zi, stream)); held = -1; }
-                else if (at[r] >= 0) RUN(hoist_switch(c, L, ch, r, at[r], d_cgk, dbc, f64, o == 0, zi, stream));
-                else if (in_form == CRC_NTT) z[i] = xin;               // g = 1: x itself, in NTT form
-                else RUN(ntt_copy(c, xin, ch, zi, stream));
-            }
-            if (held >= 0) RUN(hoist_switch(c, L, ch, r0 + held, at[r0 + held], d_cgk, dbc, f64, o == 0, L.z + (size_t)held * uj, stream));
+            RUN(hoist_group(H, xin, in_form, ch, o == 0, r0, rn, z));
             if (bsgs_jt(c) == 2) { RUN(k_galois_diag_mac_multi(c, z, gb + r0, r0, rn, B, d_p_ntt, G, ch, r0 != 0, u, S(stream))); continue; }
             for (int j = 0; j < G; j++) {
                 for (int i = 0; i < rn; i++) p[i] = d_p_ntt + ((size_t)j * B + r0 + i) * rowp;
@@ -1574,9 +1608,7 @@ extern "C" int crc_diag_mac_bsgs_forms(crc_ctx *c, const uint64_t *d_x, int in_f
         for (int j = 0; j < G; j++) {
             u64 *ug = L.u + (size_t)j * uj;
             zs[j] = ug;
-            if (at[B + j] < 0) continue;
-            RUN(hoist_pass_head(c, L, ug, CRC_NTT, ch, nullptr, 0, d_cgk, dbc, f64, false, stream));
-            RUN(hoist_switch(c, L, ch, B + j, at[B + j], d_cgk, dbc, f64, o == 0, ug, stream));
+            if (at[B + j] >= 0) RUN(hoist_switch_own(H, ug, ch, B + j, B + j, o == 0));
         }
         RUN(k_galois_sum_permuted(c, zs.data(), gg, G, ch, false, d_y + o * ctw, S(stream)));
     }
@@ -1620,40 +1652,25 @@ extern "C" int crc_conv_slots_forms(crc_ctx *c, const uint64_t *d_x, int in_form
                                     const uint64_t *d_cgk, const uint64_t *elts, int n_elts, int dbc, uint64_t *d_y, int out_form, void *d_work, void *stream)
 {
     CHECK_CTX(c);
-    if (!conv_counts_ok(count, Cin, Cout, T) || !d_w || !aligned16(d_w)) return CRC_ERR_INVALID_ARGUMENT;
+    if (!conv_counts_ok(count, Cin, Cout, T)) return CRC_ERR_INVALID_ARGUMENT;
     const size_t total = (size_t)Cin * count, outs = (size_t)Cout * count, wb = conv_bytes(c, count, Cin, Cout, T, dbc), ctw = crc_ct_words(c, 2);
-    const size_t wbytes = 8 * (size_t)c->k * Cout * Cin * T;
-    if (!hoist_args_ok(c, d_x, in_form, total, gs, T, d_cgk, elts, n_elts, dbc, d_y, outs, out_form, d_work, wb)) return CRC_ERR_INVALID_ARGUMENT;
-    if (ranges_overlap(d_w, wbytes, d_y, 8 * outs * ctw) || ranges_overlap(d_w, wbytes, d_work, wb)) return CRC_ERR_INVALID_ARGUMENT;
+    if (!hoist_args_ok(c, d_x, in_form, total, gs, T, d_cgk, elts, n_elts, dbc, d_y, outs, out_form, d_work, wb) ||
+        !hoist_operand_ok(c, d_w, 8 * (size_t)c->k * Cout * Cin * T, d_y, outs, d_work, wb)) return CRC_ERR_INVALID_ARGUMENT;
     std::vector<int> at((size_t)T);
     if (!hoist_keys(c, gs, T, elts, n_elts, at.data())) return CRC_ERR_INVALID_ARGUMENT;
     if (count == 0) return CRC_OK;
     const int zc = diag_zc(T);
     WorkArena a(d_work);
-    const HoistWork L = hoist_layout(c, total, T, zc, dbc, a);
-    const bool f64 = c->tune.relin_path != 1 && k_relin64_supported(c, dbc), pair = f64 && hoist_rt(c) == 2;
-    bool keyed = false;                                                 // (no digits where every element is 1)
-    for (int r = 0; r < T; r++) keyed = keyed || at[r] >= 0;
-    for (size_t o = 0; o < total; o += L.step) {
-        const size_t ch = pass_len(total, o, L.step);
+    const HoistCall H = hoist_call(c, hoist_layout(c, total, T, zc, dbc, a), d_cgk, dbc, stream, at, T);
+    RUN(hoist_prepare_keys(H, 0, T));
+    for (size_t o = 0; o < total; o += H.L.step) {
+        const size_t ch = pass_len(total, o, H.L.step);
         const u64 *xin = d_x + o * ctw;
-        if (keyed) RUN(hoist_pass_head(c, L, xin, in_form, ch, at.data(), T, d_cgk, dbc, f64, o == 0, stream));
+        if (H.keyed) RUN(hoist_pass_head(H, xin, in_form, ch));         // (no digits where every element is 1)
         for (int r0 = 0; r0 < T; r0 += zc) {
             const int rn = T - r0 < zc ? T - r0 : zc;
-            const u64 *z[GALOIS_DIAG_MAX], *same = nullptr;             // same: the pass itself in NTT form, made once per group for its elements 1
-            int held = -1;                                              // a keyed element that waits for a partner (two keys per digit load)
-            for (int i = 0; i < rn; i++) {
-                const int r = r0 + i;
-                u64 *zi = L.z + (size_t)i * ch * ctw;
-                z[i] = zi;
-                if (at[r] >= 0 && pair && held < 0) held = i;
-                else if (at[r] >= 0 && pair) { RUN(hoist_switch2(c, L, ch, r0 + held, r, dbc, L.z + (size_t)held * ch * ctw, zi, stream)); held = -1; }
-                else if (at[r] >= 0) RUN(hoist_switch(c, L, ch, r, at[r], d_cgk, dbc, f64, o == 0, zi, stream));
-                else if (in_form == CRC_NTT) z[i] = xin;
-                else if (same) z[i] = same;
-                else { RUN(ntt_copy(c, xin, ch, zi, stream)); same = zi; }
-            }
-            if (held >= 0) RUN(hoist_switch(c, L, ch, r0 + held, at[r0 + held], d_cgk, dbc, f64, o == 0, L.z + (size_t)held * ch * ctw, stream));
+            const u64 *z[GALOIS_DIAG_MAX];
+            RUN(hoist_group(H, xin, in_form, ch, o == 0, r0, rn, z));
             RUN(k_galois_conv_mac(c, z, gs + r0, rn, d_w + r0, T, Cin, Cout, o, ch, count, r0 == 0, d_y, conv_jt(c), S(stream)));
         }
     }
@@ -1661,7 +1678,7 @@ extern "C" int crc_conv_slots_forms(crc_ctx *c, const uint64_t *d_x, int in_form
     return CRC_OK;
 }
 // ---- prepared keys that outlive a call: what k_relin64_prepare_keys leaves, per conjugated key, in a buffer of the caller's ----
-// Every hoisted entry point above prepares the fp64 form of its keys in pass 0 of every call (three launches per key); a layer with hundreds of keys prepares them
+// Every hoisted entry point above prepares the fp64 form of its keys at the start of every call (three launches per key); a layer with hundreds of keys prepares them
 // once.  d_pk [n_elts][crc_galois_prepared_key_words], d_scratch: crc_evk_words words
 extern "C" size_t crc_galois_prepared_key_words(const crc_ctx *c, int dbc) { return c && dbc_ok(dbc) && k_relin64_supported(c, dbc) ? k_relin64_keys_words(c, dbc) : 0; }
 extern "C" int crc_galois_prepare_keys_dev(crc_ctx *c, const uint64_t *d_cgk, const uint64_t *elts, int n_elts, int dbc, uint64_t *d_pk, uint64_t *d_scratch,
@@ -1684,14 +1701,15 @@ extern "C" int crc_galois_prepare_keys_dev(crc_ctx *c, const uint64_t *d_cgk, co
 // outer stage -- crc_diag_mac_bsgs_forms' giant stage -- over the keyed steps; galois_sum_permuted_kernel over all R (gs[j] = 1: u_j itself).  The outer stage on
 // the fp64 path runs in sub-batches of rb consecutive keyed steps: ONE inverse transform, (c0, 0, c1 (q/q_i)^-1), K1 over rb ch ciphertexts, then K2 with one key
 // per step (relin_mac_keyed_f64_kernel) and K3, whose results go over the u_j.  Where the fp64 key switch does not apply, or at planes_batch = 1, it runs step by
-// step through hoist_pass_head / hoist_switch exactly as the giant stage does.  Every step is an exact function on Z_q with canonical residues: the bits are those
+// step through hoist_switch_own exactly as the giant stage does.  Every step is an exact function on Z_q with canonical residues: the bits are those
 // of crc_multiply_plain_ntt + crc_add over c, crc_rotate_hoisted_forms per j, crc_add over j, at every setting and pass structure.
 // Work: [key pointers of the R steps][NTT copy of a coefficient-form pass, Cin ch][the R ch inner sums][coefficient copy of a sub-batch][its size-3 rows][prepared
-// keys: R, made by pass 0 -- with d_pk one, for the path that cannot use d_pk][scratch of the key switch].  A pass keeps (Cin + R) ch ciphertexts, so ch shrinks
+// keys: R -- with d_pk one, for the path that cannot use d_pk][scratch of the key switch].  A pass keeps (Cin + R) ch ciphertexts, so ch shrinks
 // with them as hoist_layout's does; rb ch <= square_chunk, at least one step of one ciphertext
 enum { PLANES_BATCH_DEFAULT = 2, DENSE_PLANES_MAX_CH = 4096 };
 static int planes_batch(const crc_ctx *c) { return c->tune.planes_batch ? c->tune.planes_batch : (int)PLANES_BATCH_DEFAULT; }
-struct PlanesWork { const u64 **kt; u64 *xh, *u, *xc, *x3, *kp, *rest; size_t step, rb, kpw; };
+// the HoistWork of the outer stage (xc and x3 of a sub-batch, the R inner sums in u, no z) and around it: kt the key pointers, xh the NTT copy, rb steps per sub-batch
+struct PlanesWork : HoistWork { const u64 **kt; u64 *xh; size_t rb; };
 static bool planes_counts_ok(size_t count, int Cin, int R)
 {
     return Cin >= 1 && Cin <= DENSE_PLANES_MAX_CH && R >= 1 && R <= GALOIS_BSGS_MAX && count <= ((size_t)1 << 40);
@@ -1715,7 +1733,7 @@ static PlanesWork planes_layout(const crc_ctx *c, size_t count, int Cin, int R, 
     L.x3 = a.take<u64>(L.rb * ch * crc_ct_words(c, 3));
     L.kp = a.take<u64>((prepared ? 1 : (size_t)R) * L.kpw);
     const size_t one = k_relin_work_words(c, ch, dbc), all = k_relin64_supported(c, dbc) ? k_relin64_work_words(c, L.rb * ch, dbc) : 0;
-    L.rest = a.take<u64>(one > all ? one : all);                        // (either setting of planes_batch, either key-switch path: a tuning switch does not change the size)
+    L.rest = a.take<u64>(one > all ? one : all);                        // (either setting of planes_batch, either key-switch path: as hoist_layout's)
     return L;
 }
 static size_t planes_bytes(const crc_ctx *c, size_t count, int Cin, int R, int dbc, bool prepared)
@@ -1734,38 +1752,32 @@ extern "C" int crc_dense_planes_forms(crc_ctx *c, const uint64_t *d_x, int in_fo
                                       void *d_work, void *stream)
 {
     CHECK_CTX(c);
-    if (!planes_counts_ok(count, Cin, R) || !d_p_ntt || !aligned16(d_p_ntt) || !aligned16(d_pk)) return CRC_ERR_INVALID_ARGUMENT;
+    if (!planes_counts_ok(count, Cin, R) || !aligned16(d_pk)) return CRC_ERR_INVALID_ARGUMENT;
     const bool prepared = d_pk != nullptr;
     const size_t total = (size_t)Cin * count, wb = planes_bytes(c, count, Cin, R, dbc, prepared), ctw = crc_ct_words(c, 2), rowp = (size_t)c->k * c->n;
     const size_t xb = 8 * total * ctw, yb = 8 * count * ctw, pb = 8 * (size_t)R * Cin * rowp;
-    if (!hoist_args_ok(c, d_x, in_form, total, gs, R, d_cgk, elts, n_elts, dbc, d_y, count, out_form, d_work, wb)) return CRC_ERR_INVALID_ARGUMENT;
-    if (ranges_overlap(d_p_ntt, pb, d_y, yb) || ranges_overlap(d_p_ntt, pb, d_work, wb) || ranges_overlap(d_p_ntt, pb, d_x, xb)) return CRC_ERR_INVALID_ARGUMENT;
+    if (!hoist_args_ok(c, d_x, in_form, total, gs, R, d_cgk, elts, n_elts, dbc, d_y, count, out_form, d_work, wb) ||
+        !hoist_operand_ok(c, d_p_ntt, pb, d_y, count, d_work, wb)) return CRC_ERR_INVALID_ARGUMENT;
+    if (ranges_overlap(d_p_ntt, pb, d_x, xb)) return CRC_ERR_INVALID_ARGUMENT;      // (two buffers that are only read: refused because the header says so)
     std::vector<int> at((size_t)R);
-    if (!hoist_keys(c, gs, R, elts, n_elts, at.data())) return CRC_ERR_INVALID_ARGUMENT;
-    bool keyed = false;                                                 // (no digits at all where every element is 1)
-    for (int j = 0; j < R; j++) keyed = keyed || at[j] >= 0;
+    if (!hoist_keys(c, gs, R, elts, n_elts, at.data())) return CRC_ERR_INVALID_ARGUMENT;       // (a keyed step with n_elts = 0 ends here, d_pk or not)
     const size_t pkw = k_relin64_keys_words(c, dbc), pkb = 8 * pkw * (size_t)n_elts;
-    if (prepared) {
-        if (keyed && n_elts == 0) return CRC_ERR_INVALID_ARGUMENT;
-        if (ranges_overlap(d_pk, pkb, d_x, xb) || ranges_overlap(d_pk, pkb, d_y, yb) || ranges_overlap(d_pk, pkb, d_p_ntt, pb) || ranges_overlap(d_pk, pkb, d_work, wb))
-            return CRC_ERR_INVALID_ARGUMENT;
-    }
+    if (prepared && (ranges_overlap(d_pk, pkb, d_x, xb) || ranges_overlap(d_pk, pkb, d_y, yb) || ranges_overlap(d_pk, pkb, d_p_ntt, pb) ||
+                     ranges_overlap(d_pk, pkb, d_work, wb))) return CRC_ERR_INVALID_ARGUMENT;
     if (count == 0) return CRC_OK;
-    const size_t kw = crc_evk_words(c, dbc);
     WorkArena a(d_work);
     const PlanesWork L = planes_layout(c, count, Cin, R, dbc, prepared, a);
-    const bool f64 = c->tune.relin_path != 1 && k_relin64_supported(c, dbc), batched = f64 && planes_batch(c) == 2, use_pk = f64 && prepared;
-    // the view hoist_pass_head / hoist_switch take: the prepared key of step j at kp + slot(j) kpw
-    HoistWork H{};
-    H.xc = L.xc; H.x3 = L.x3; H.rest = L.rest; H.step = L.step;
-    H.kp = use_pk ? const_cast<u64 *>(d_pk) : L.kp;                    // (d_pk is only read: the fp64 path never prepares into it)
-    H.kpw = use_pk ? pkw : L.kpw;
-    auto slot = [&](int j) { return use_pk ? at[j] : f64 || !prepared ? j : 0; };      // (!f64 with d_pk: the one slot, prepared again by every step)
-    if (batched && keyed) {
+    HoistCall H = hoist_call(c, L, d_cgk, dbc, stream, at, R);
+    const bool batched = H.f64 && planes_batch(c) == 2, use_pk = H.f64 && prepared;
+    if (use_pk) { H.L.kp = const_cast<u64 *>(d_pk); H.L.kpw = pkw; }   // (d_pk is only read: the fp64 path never prepares into it)
+    // the prepared key of step j is at kp + slot(j) kpw
+    auto slot = [&](int j) { return use_pk ? at[j] : H.f64 || !prepared ? j : 0; };    // (!f64 with d_pk: the one slot, prepared again by every step)
+    if (batched && H.keyed) {
         std::vector<int> slots((size_t)R, -1);                          // the pointer table is written on the device: the slots go as kernel arguments
         for (int j = 0; j < R; j++) if (at[j] >= 0) slots[j] = slot(j);
-        RUN(k_relin64_key_table(H.kp, H.kpw, slots.data(), (size_t)R, L.kt, S(stream)));
+        RUN(k_relin64_key_table(H.L.kp, H.L.kpw, slots.data(), (size_t)R, L.kt, S(stream)));
     }
+    if (!use_pk) RUN(hoist_prepare_keys(H, 0, R));
     std::vector<const u64 *> zs((size_t)R), zin((size_t)Cin);
     const std::vector<u64> ones(GALOIS_DIAG_MAX, 1);
     for (size_t o = 0; o < count; o += L.step) {
@@ -1780,9 +1792,6 @@ extern "C" int crc_dense_planes_forms(crc_ctx *c, const uint64_t *d_x, int in_fo
             const int cn = Cin - c0 < GALOIS_DIAG_MAX ? Cin - c0 : (int)GALOIS_DIAG_MAX;
             RUN(k_galois_diag_mac_multi(c, zin.data() + c0, ones.data(), c0, cn, Cin, d_p_ntt, R, ch, c0 != 0, L.u, S(stream)));
         }
-        if (keyed && f64 && !use_pk && o == 0)                          // (the preparation borrows the scratch: before E is put there)
-            for (int j = 0; j < R; j++)
-                if (at[j] >= 0) RUN(k_relin64_prepare_keys(c, d_cgk + (size_t)at[j] * kw, dbc, L.kp + (size_t)j * L.kpw, L.rest, S(stream)));
         for (int j0 = 0; j0 < R;) {
             if (at[j0] < 0) { j0++; continue; }
             int j1 = j0 + 1;                                            // a run of consecutive keyed steps, at most rb of them where they go as one batch
@@ -1794,10 +1803,8 @@ extern "C" int crc_dense_planes_forms(crc_ctx *c, const uint64_t *d_x, int in_fo
                 RUN(k_galois_permute(c, L.xc, cnt, 1, false, L.x3, S(stream)));
                 RUN(k_relin64_digits(c, L.x3, 3, 2, cnt, dbc, L.rest, S(stream)));
                 RUN(k_relin64_from_digits_keyed(c, L.x3, 3, cnt, ch, dbc, ub, L.rest, L.kt + j0, S(stream), true));
-            } else {
-                RUN(hoist_pass_head(c, H, ub, CRC_NTT, ch, nullptr, 0, d_cgk, dbc, f64, false, stream));
-                RUN(hoist_switch(c, H, ch, slot(j0), at[j0], d_cgk, dbc, f64, prepared || o == 0, ub, stream));
             }
+            else RUN(hoist_switch_own(H, ub, ch, j0, slot(j0), prepared || o == 0));
             j0 = j1;
         }
         for (int j = 0; j < R; j++) zs[j] = L.u + (size_t)j * uj;

@@ -695,6 +695,9 @@ ciphertext3D rotateRows(const ciphertext3D &t, int steps, int out_form) { return
 ciphertext3D rotateColumns(const ciphertext3D &t, int out_form) { return galoisOp("rotateColumns", t, 1, 0, out_form); }
 ciphertext3D sumSlots(const ciphertext3D &t, int out_form) { return galoisOp("sumSlots", t, 2, 0, out_form); }
 // ---- hoisted rotations and the matrix-vector product over slots ------------------------------------------------------------
+// the conjugated keys of the set on the device (null before generateGaloisKeys), and the digit width they were made with
+static const uint64_t *galoisCkeys() { return g_galois_ckeys ? (const uint64_t *)g_galois_ckeys->ptr : nullptr; }
+static int galoisDbc() { return g_galois_dbc ? g_galois_dbc : 16; }
 // what the two share: the reference's checks in rotateRows' order, then every step's element with its own conjugated key in the set
 static vector<uint64_t> hoistedElements(const char *what, const ciphertext3D &t, const vector<int> &steps, int out_form)
 {
@@ -715,13 +718,13 @@ vector<ciphertext3D> rotateRowsMany(const ciphertext3D &t, const vector<int> &st
 {
     const vector<uint64_t> gs = hoistedElements("rotateRowsMany", t, steps, out_form);
     if (gs.empty()) return {};
-    const int R = (int)gs.size(), dbc = g_galois_dbc ? g_galois_dbc : 16;
+    const int R = (int)gs.size(), dbc = galoisDbc();
     if ((long long)R * t.B > 0x7fffffffLL) throw invalid_argument("rotateRowsMany: too many results");
     ciphertext3D all(R * t.B, t.zd, t.xd, t.yd, out_form);              // [R][count]: one buffer, handed out as R views
     const size_t cnt = t.count();
     ensure(g_scratch, crc_rotate_hoisted_work_bytes(ctx(), cnt, R, dbc));
-    chk(crc_rotate_hoisted_forms(ctx(), t.data(), t.form, cnt, gs.data(), R, g_galois_ckeys ? (const uint64_t *)g_galois_ckeys->ptr : nullptr, galois_elts.data(),
-                                 (int)galois_elts.size(), dbc, all.data(), out_form, g_scratch->ptr, stream()), "rotateRowsMany");
+    chk(crc_rotate_hoisted_forms(ctx(), t.data(), t.form, cnt, gs.data(), R, galoisCkeys(), galois_elts.data(), (int)galois_elts.size(), dbc,
+                                 all.data(), out_form, g_scratch->ptr, stream()), "rotateRowsMany");
     vector<ciphertext3D> out;
     for (int r = 0; r < R; r++) out.push_back(all.images(r * t.B, t.B));
     return out;
@@ -730,10 +733,23 @@ void diagMatvecPlan(const vector<vector<int64_t>> &W, int M, int n, vector<int> 
 {
     if (!crc_diag_plan(W, M, n, steps, rows)) throw invalid_argument("matvecSlots: M must be a power of two <= n/2 and W at most M x M");
 }
+// R rows of n slot values each -> their NTT-form plaintexts [R][k][n] on the device: compose, upload, transform
+static shared_ptr<DeviceBuffer> plainRowsNtt(const vector<int64_t> &rows, int R)
+{
+    const int n = N(), k = crc_ctx_k(ctx());
+    vector<uint64_t> plain((size_t)R * n);
+    chk(crc_slots_compose(ctx(), rows.data(), R, n, n, 1, plain.data()), "crc_slots_compose");
+    DeviceBuffer d_plain(plain.size() * 8);
+    auto d_p = make_shared<DeviceBuffer>((size_t)R * k * n * 8);
+    chk(crc_memcpy_h2d(ctx(), d_plain.ptr, plain.data(), plain.size() * 8, stream()), "crc_memcpy_h2d");
+    chk(crc_plain_to_ntt(ctx(), (const uint64_t *)d_plain.ptr, R, (uint64_t *)d_p->ptr, stream()), "crc_plain_to_ntt");
+    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");           // (the composed rows and their upload go out of scope here)
+    return d_p;
+}
 ciphertext3D matvecSlots(const ciphertext3D &t, const vector<vector<int64_t>> &W, int M, int out_form)
 {
     if (!crc_slots_supported(ctx())) throw logic_error("encryption parameters do not support batching");
-    const int n = N(), k = crc_ctx_k(ctx());
+    const int n = N();
     vector<int> steps; vector<int64_t> rows;
     diagMatvecPlan(W, M, n, steps, rows);
     const vector<uint64_t> gs = hoistedElements("matvecSlots", t, steps, out_form);
@@ -743,15 +759,11 @@ ciphertext3D matvecSlots(const ciphertext3D &t, const vector<vector<int64_t>> &W
         chk(crc_memset(ctx(), out.data(), 0, cnt * ctb, stream()), "crc_memset");
         return out;
     }
-    const int R = (int)gs.size(), dbc = g_galois_dbc ? g_galois_dbc : 16;
-    vector<uint64_t> plain((size_t)R * n);
-    chk(crc_slots_compose(ctx(), rows.data(), R, n, n, 1, plain.data()), "crc_slots_compose");
-    DeviceBuffer d_plain(plain.size() * 8), d_p((size_t)R * k * n * 8);
-    chk(crc_memcpy_h2d(ctx(), d_plain.ptr, plain.data(), plain.size() * 8, stream()), "crc_memcpy_h2d");
-    chk(crc_plain_to_ntt(ctx(), (const uint64_t *)d_plain.ptr, R, (uint64_t *)d_p.ptr, stream()), "crc_plain_to_ntt");
+    const int R = (int)gs.size(), dbc = galoisDbc();
+    const shared_ptr<DeviceBuffer> d_p = plainRowsNtt(rows, R);
     ensure(g_scratch, crc_diag_mac_work_bytes(ctx(), cnt, R, dbc));
-    chk(crc_diag_mac_forms(ctx(), t.data(), t.form, cnt, gs.data(), R, (const uint64_t *)d_p.ptr, g_galois_ckeys ? (const uint64_t *)g_galois_ckeys->ptr : nullptr,
-                           galois_elts.data(), (int)galois_elts.size(), dbc, out.data(), out_form, g_scratch->ptr, stream()), "matvecSlots");
+    chk(crc_diag_mac_forms(ctx(), t.data(), t.form, cnt, gs.data(), R, (const uint64_t *)d_p->ptr, galoisCkeys(), galois_elts.data(),
+                           (int)galois_elts.size(), dbc, out.data(), out_form, g_scratch->ptr, stream()), "matvecSlots");
     chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");           // (the diagonals' buffers go out of scope here)
     return out;
 }
@@ -771,7 +783,7 @@ int bsgsDefaultSplit(int M)
 ciphertext3D matvecSlotsBsgs(const ciphertext3D &t, const vector<vector<int64_t>> &W, int M, int B, int out_form)
 {
     if (!crc_slots_supported(ctx())) throw logic_error("encryption parameters do not support batching");
-    const int n = N(), k = crc_ctx_k(ctx());
+    const int n = N();
     vector<int> baby, giant; vector<int64_t> rows;
     bsgsMatvecPlan(W, M, n, B ? B : bsgsDefaultSplit(M), baby, giant, rows);
     const vector<uint64_t> gb = hoistedElements("matvecSlotsBsgs", t, baby, out_form), gg = hoistedElements("matvecSlotsBsgs", t, giant, out_form);
@@ -781,16 +793,11 @@ ciphertext3D matvecSlotsBsgs(const ciphertext3D &t, const vector<vector<int64_t>
         chk(crc_memset(ctx(), out.data(), 0, cnt * ctb, stream()), "crc_memset");
         return out;
     }
-    const int nb = (int)gb.size(), ng = (int)gg.size(), R = nb * ng, dbc = g_galois_dbc ? g_galois_dbc : 16;
-    vector<uint64_t> plain((size_t)R * n);
-    chk(crc_slots_compose(ctx(), rows.data(), R, n, n, 1, plain.data()), "crc_slots_compose");
-    DeviceBuffer d_plain(plain.size() * 8), d_p((size_t)R * k * n * 8);
-    chk(crc_memcpy_h2d(ctx(), d_plain.ptr, plain.data(), plain.size() * 8, stream()), "crc_memcpy_h2d");
-    chk(crc_plain_to_ntt(ctx(), (const uint64_t *)d_plain.ptr, R, (uint64_t *)d_p.ptr, stream()), "crc_plain_to_ntt");
+    const int nb = (int)gb.size(), ng = (int)gg.size(), dbc = galoisDbc();
+    const shared_ptr<DeviceBuffer> d_p = plainRowsNtt(rows, nb * ng);
     ensure(g_scratch, crc_diag_mac_bsgs_work_bytes(ctx(), cnt, nb, ng, dbc));
-    chk(crc_diag_mac_bsgs_forms(ctx(), t.data(), t.form, cnt, gb.data(), nb, gg.data(), ng, (const uint64_t *)d_p.ptr,
-                                g_galois_ckeys ? (const uint64_t *)g_galois_ckeys->ptr : nullptr, galois_elts.data(), (int)galois_elts.size(), dbc, out.data(),
-                                out_form, g_scratch->ptr, stream()), "matvecSlotsBsgs");
+    chk(crc_diag_mac_bsgs_forms(ctx(), t.data(), t.form, cnt, gb.data(), nb, gg.data(), ng, (const uint64_t *)d_p->ptr, galoisCkeys(),
+                                galois_elts.data(), (int)galois_elts.size(), dbc, out.data(), out_form, g_scratch->ptr, stream()), "matvecSlotsBsgs");
     chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");           // (the rows' buffers go out of scope here)
     return out;
 }
@@ -869,7 +876,7 @@ ciphertext3D convSlots(const ciphertext3D &t, const vector<int64_t> &weights, in
     const ConvSlotsPlan P = convSlotsPlan(g);
     const vector<uint64_t> gs = hoistedElements("convSlots", t, P.steps, out_form);
     if (t.B != 1 || t.xd != 1 || t.yd != 1) throw invalid_argument("convSlots: a tensor [1][zd][1][1] of channel planes (encryptImagePlanes)");
-    const int Cin = (int)t.count(), T = (int)P.steps.size(), k = crc_ctx_k(ctx()), dbc = g_galois_dbc ? g_galois_dbc : 16;
+    const int Cin = (int)t.count(), T = (int)P.steps.size(), k = crc_ctx_k(ctx()), dbc = galoisDbc();
     vector<int64_t> folded;
     if (Cout < 1 || !crc_conv_slots_fold(P, weights, Cout, Cin, (int64_t)g_plain_modulus, folded)) throw invalid_argument("convSlots: weights must be [Cout][Cin][fh][fw]");
     vector<uint64_t> packed((size_t)k * folded.size());
@@ -879,7 +886,7 @@ ciphertext3D convSlots(const ciphertext3D &t, const vector<int64_t> &weights, in
     chk(crc_memcpy_h2d(ctx(), d_w.ptr, packed.data(), packed.size() * 8, stream()), "crc_memcpy_h2d");
     ciphertext3D out(1, Cout, 1, 1, out_form);
     ensure(g_scratch, crc_conv_slots_work_bytes(ctx(), 1, Cin, Cout, T, dbc));
-    chk(crc_conv_slots_forms(ctx(), t.data(), t.form, 1, Cin, gs.data(), T, (const uint64_t *)d_w.ptr, Cout, g_galois_ckeys ? (const uint64_t *)g_galois_ckeys->ptr : nullptr,
+    chk(crc_conv_slots_forms(ctx(), t.data(), t.form, 1, Cin, gs.data(), T, (const uint64_t *)d_w.ptr, Cout, galoisCkeys(),
                              galois_elts.data(), (int)galois_elts.size(), dbc, out.data(), out_form, g_scratch->ptr, stream()), "convSlots");
     chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");           // (the weights' buffer goes out of scope here)
     if (og) { *og = SlotPlanes(); og->M = g.M; og->pitch = g.pitch; og->H = P.out_h; og->W = P.out_w; og->dil = P.out_dil; }
@@ -942,7 +949,7 @@ ciphertext3D densePlanes(const ciphertext3D &t, const vector<int64_t> &W, int O,
     const DensePlanesPlan P = densePlanesPlan(M, in_slots, O, out_slots);
     const vector<uint64_t> gs = hoistedElements("densePlanes", t, P.steps, out_form);
     if (t.B != 1 || t.xd != 1 || t.yd != 1) throw invalid_argument("densePlanes: a tensor [1][zd][1][1] of channel planes (convSlots' result, or a vector)");
-    const int Cin = (int)t.count(), R = (int)P.steps.size(), n = N(), k = crc_ctx_k(ctx()), dbc = g_galois_dbc ? g_galois_dbc : 16;
+    const int Cin = (int)t.count(), R = (int)P.steps.size(), n = N(), k = crc_ctx_k(ctx()), dbc = galoisDbc();
     if (W.size() != (size_t)O * Cin * in_slots.size()) throw invalid_argument("densePlanes: weights must be [O][Cin][P]");
     const uint64_t *d_pk = preparedGaloisKeys(dbc, gs);
     if (!crc_dense_planes_work_bytes(ctx(), 1, Cin, R, dbc, d_pk != nullptr)) throw invalid_argument("densePlanes: too many channels or steps");
@@ -959,7 +966,7 @@ ciphertext3D densePlanes(const ciphertext3D &t, const vector<int64_t> &W, int O,
     }
     ciphertext3D out(1, 1, 1, 1, out_form);
     ensure(g_scratch, crc_dense_planes_work_bytes(ctx(), 1, Cin, R, dbc, d_pk != nullptr));
-    chk(crc_dense_planes_forms(ctx(), t.data(), t.form, 1, Cin, gs.data(), R, (const uint64_t *)d_p.ptr, g_galois_ckeys ? (const uint64_t *)g_galois_ckeys->ptr : nullptr,
+    chk(crc_dense_planes_forms(ctx(), t.data(), t.form, 1, Cin, gs.data(), R, (const uint64_t *)d_p.ptr, galoisCkeys(),
                                galois_elts.data(), (int)galois_elts.size(), d_pk, dbc, out.data(), out_form, g_scratch->ptr, stream()), "densePlanes");
     chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");           // (the rows' buffer goes out of scope here)
     return out;

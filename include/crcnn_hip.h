@@ -674,7 +674,7 @@ int crc_sum_slots_forms(crc_ctx *ctx, const uint64_t *d_x, int in_form, size_t c
  *                               crc_rotate_hoisted_forms, then crc_multiply_plain_ntt per element, then crc_add -- but the rotated ciphertexts are never
  *                               written (the gather is folded into the product).  With the slots of one image tiled with period M over both rows and the
  *                               diagonals of an M x M matrix as P_r, gs[r] = crc_galois_elt_rows(d_r), this is the matrix-vector product over slots.
- *                               d_work: crc_diag_mac_work_bytes(ctx, count, R, dbc)
+ *                               d_work: crc_diag_mac_work_bytes(ctx, count, R, dbc).  d_p_ntt must not overlap d_y or d_work (CRC_ERR_INVALID_ARGUMENT)
  *   crc_diag_mac_bsgs_forms     baby-step / giant-step: d_y [count] = Sum_j H_{gg[j]}( Sum_b P[j][b] (*) H_{gb[b]}(d_x) ) with NTT-form plaintext rows d_p_ntt
  *                               [G][B][k][n].  Bit for bit: crc_diag_mac_forms(d_x, gb, B, P[j]) into NTT form for every j, crc_rotate_hoisted_forms of each result
  *                               by {gg[j]} into NTT form, crc_add over j, one inverse transform for CRC_COEFF -- but neither a rotated input nor a rotated inner
@@ -712,8 +712,8 @@ int crc_sum_slots_forms(crc_ctx *ctx, const uint64_t *d_x, int in_form, size_t c
  *                               be prepared.  The key pointers of the batched path are written by a kernel from launch arguments: like its siblings the
  *                               call reads no host memory after it returns
  * Refusals as in the paragraph above (null / misaligned / overlapping operands, forms, dbc, an invalid element), plus R < 1 (B < 1, G < 1) and a missing
- * conjugated key; crc_conv_slots_forms also for Cin, Cout or T below 1 or above its caps, and for d_w null, misaligned or overlapping d_y or d_work:
- * CRC_ERR_INVALID_ARGUMENT, nothing launched, d_y untouched.  count = 0 is CRC_OK.  crc_dense_planes_forms also for Cin or R outside their caps, d_p_ntt or d_pk
+ * conjugated key; every entry point with a read-only operand (d_p_ntt, d_w) also where that is null, misaligned or overlaps d_y or d_work -- crc_diag_mac_forms
+ * included; crc_conv_slots_forms also for Cin, Cout or T below 1 or above its caps: CRC_ERR_INVALID_ARGUMENT, nothing launched, d_y untouched.  count = 0 is CRC_OK.  crc_dense_planes_forms also for Cin or R outside their caps, d_p_ntt or d_pk
  * misaligned or overlapping d_x, d_y or d_work, and d_pk given with n_elts = 0 while a step is keyed.
  * ------------------------------------------------------------------------------------------------------------- */
 int crc_galois_ntt_table(const crc_ctx *ctx, uint64_t g, uint32_t *table /*[n]*/);

@@ -65,30 +65,38 @@ def model_case(si, dbc):
     H = ca.Engine(n, q, t, device=-1)
     M = gm.GaloisModel(orc.Oracle(n, q, t))
     sk, pk = H.keygen(51 + si)
-    gs = [3, 1, 2 * n - 1]
+    lists = [[3, 1, 2 * n - 1], [1, 3, 1, 2 * n - 1, 3]]              # the second: copies first and between, three keyed results, one key in two slots
     elts, gk = H.gen_galois_keys(52 + si, sk, dbc=dbc, elts=[2 * n - 1, 3])
     cg = H.galois_conjugate_keys(elts, gk, dbc=dbc)
     elts = [int(e) for e in elts]
     rng = np.random.RandomState(10 + si)
     x = H.encrypt(pk, (rng.randint(0, 1 << 30, size=(COUNT, n)).astype(np.uint64) % np.uint64(t)), 600)
-    want = []
-    for g in gs:
+    of = {}
+    for g in lists[0]:
         kc = hm.conjugate_key_coeff(M, M.key_coeff(gk[elts.index(g)], dbc), g) if g != 1 else None       # (the model conjugates by the definition)
-        want.append(np.stack([hm.hoisted(M, x[i], g, None, dbc, key_coeff=kc) for i in range(COUNT)]))
+        of[g] = np.stack([hm.hoisted(M, x[i], g, None, dbc, key_coeff=kc) for i in range(COUNT)])
     H.close()
-    _MODEL[(si, dbc)] = (n, q, t, elts, cg, x, gs, np.stack(want))
+    _MODEL[(si, dbc)] = (n, q, t, elts, cg, x, [(gs, np.stack([of[g] for g in gs])) for gs in lists])
     return _MODEL[(si, dbc)]
 
 
 @pytest.mark.parametrize("dbc", [16, 8])
 @pytest.mark.parametrize("si", [0, 1], ids=["n256_k2", "n2048_k1"])
 def test_rotate_hoisted_equals_the_model(si, dbc):
-    """R = 3 with g = 1 and 2n - 1 among them, count = 5 in passes of 2 (a tail pass; the keys prepared by pass 0 serve the others), every form pair, both
+    """R = 3 with g = 1 and 2n - 1 among them, and R = 5 with an odd number of keyed elements (a pair and a single one at hoist_rt = 2), copies in front of and
+    between them and one key in two slots; count = 5 in passes of 2 (a tail pass; the keys prepared by pass 0 serve the others), every form pair, both
     key-switch paths and both settings of the tuning key hoist_rt; then the same call in one pass"""
     import crcnn_amd as ca
-    n, q, t, elts, cg, x, gs, want = model_case(si, dbc)
+    n, q, t, elts, cg, x, cases = model_case(si, dbc)
     E = ca.Engine(n, q, t, device=0)
     d_cg = E.upload(cg)
+    for gs, want in cases:
+        rotate_hoisted_case(E, dbc, elts, d_cg, x, gs, want)
+    E.close()
+
+
+def rotate_hoisted_case(E, dbc, elts, d_cg, x, gs, want):
+    import crcnn_amd as ca
     d_y = E.alloc(want.nbytes)
     d_work = E.alloc(E.rotate_hoisted_work_bytes(COUNT, len(gs), dbc))
     try:
@@ -113,17 +121,16 @@ def test_rotate_hoisted_equals_the_model(si, dbc):
                         assert np.array_equal(E.download(d_in, x.shape), x)             # the input is only read
     finally:
         E.set_tuning("relin_path", 0); E.set_tuning("sq_chunk", 0); E.set_tuning("hoist_rt", 0)
-    E.close()
 
 
-def big_case(R, n=4096, k=2, count=2, t=65537, seed=0):
+def big_case(R, n=4096, k=2, count=2, t=65537, seed=0, steps=None):
     import crcnn_amd as ca
     q = moduli(n, k)
     H = ca.Engine(n, q, t, device=-1)
     sk, pk = H.keygen(61 + seed)
-    steps = list(range(R))                                            # step 0 is g = 1
+    steps = list(range(R)) if steps is None else list(steps)          # step 0 is g = 1
     gs = [gm.elt_rows(n, s) for s in steps]
-    elts, gk = H.gen_galois_keys(62 + seed, sk, elts=[g for g in gs if g != 1])
+    elts, gk = H.gen_galois_keys(62 + seed, sk, elts=list(dict.fromkeys(g for g in gs if g != 1)))        # (one key per distinct element)
     cg = H.galois_conjugate_keys(elts, gk)
     rng = np.random.RandomState(R + seed)
     v = rng.randint(-(t // 2), t // 2 + 1, size=(count, n)).astype(np.int64)
@@ -154,14 +161,16 @@ def test_wave_kernels_equal_the_reference_path_at_n4096():
     E.close(); H.close()
 
 
-@pytest.mark.parametrize("n,R,count,chunk", [(4096, 5, 2, 0), (256, 34, 3, 8)], ids=["n4096_R5", "n256_R34_two_groups_tail_pass"])
-def test_diag_mac_equals_rotate_multiply_add(n, R, count, chunk):
+@pytest.mark.parametrize("n,R,count,chunk,steps", [(4096, 5, 2, 0, None), (256, 34, 3, 8, None), (256, 4, 3, 2, [0, 1, 0, 2])],
+                         ids=["n4096_R5", "n256_R34_two_groups_tail_pass", "n256_identity_twice_in_a_group_tail_pass"])
+def test_diag_mac_equals_rotate_multiply_add(n, R, count, chunk, steps):
     """the fused product = crc_rotate_hoisted_forms, crc_multiply_plain_ntt per element, crc_add, bit for bit.  R = 34 needs two launches of the diagonal kernel
-    (32 elements each at most, the second accumulating) and, with the pass shortened to 8 . 8 / 32 = 2 ciphertexts, a tail pass"""
+    (32 elements each at most, the second accumulating) and, with the pass shortened to 8 . 8 / 32 = 2 ciphertexts, a tail pass.  Steps [0, 1, 0, 2] hold the
+    identity twice in one group (one transformed copy of a coefficient-form pass serves both), in passes of 2 with a tail"""
     import crcnn_amd as ca
     k = 2
     t = 65537 if n == 4096 else ca.Engine.slots_prime(n, 20)
-    q, H, sk, pk, steps, gs, elts, gk, cg, v, x = big_case(R, n=n, k=k, count=count, t=t)
+    q, H, sk, pk, steps, gs, elts, gk, cg, v, x = big_case(R, n=n, k=k, count=count, t=t, steps=steps)
     E = ca.Engine(n, q, t, device=0)
     rng = np.random.RandomState(n + R)
     rows = rng.randint(0, t, size=(R, n)).astype(np.int64)
@@ -289,6 +298,7 @@ def test_refusals_leave_the_output_untouched():
         assert f(c=H.c) == -1                                                       # a host-only context
     assert rh(x=d_y.ptr + ctb) == -1                                                # the input inside the SECOND element's output
     assert dm(p=None) == -1 and dm(p=d_p.ptr + 8) == -1
+    assert dm(p=d_y.ptr) == -1 and dm(p=d_y.ptr + ctb - 16) == -1 and dm(p=d_work.ptr) == -1     # the plaintext rows inside the output or the work space
     pn = lambda g, x=d_x.ptr, o=d_o.ptr, c=None: E.L.crc_galois_permute_ntt_dev(c or E.c, x, 3, g, o, None)
     assert pn(2) == -1 and pn(2 * n + 1) == -1 and pn(3, o=d_o.ptr + 8) == -1 and pn(3, o=None) == -1 and pn(3, x=d_o.ptr) == -1 and pn(3, c=H.c) == -1
     one = E._elts([1]); e3 = E._elts([3])
