@@ -273,6 +273,8 @@ def load():
     L.crc_conv_slots_pack_weights.argtypes = [VP, ctypes.POINTER(ctypes.c_int64), SZ, PU]
     L.crc_conv_slots_work_bytes.restype = SZ; L.crc_conv_slots_work_bytes.argtypes = [VP, SZ, CI, CI, CI, CI]
     L.crc_conv_slots_forms.argtypes = [VP, VP, CI, SZ, CI, PU, CI, VP, CI, VP, PU, CI, CI, VP, CI, VP, VP]
+    L.crc_conv_slots_pack_bias.argtypes = [VP, ctypes.POINTER(ctypes.c_int64), SZ, PU]
+    L.crc_conv_slots_bias_mask_forms.argtypes = [VP, VP, CI, SZ, CI, PU, CI, VP, CI, VP, VP, VP, PU, CI, CI, VP, CI, VP, VP]
     L.crc_galois_prepared_key_words.restype = SZ; L.crc_galois_prepared_key_words.argtypes = [VP, CI]
     L.crc_galois_prepare_keys_dev.argtypes = [VP, VP, PU, CI, CI, VP, VP, VP]
     L.crc_dense_planes_work_bytes.restype = SZ; L.crc_dense_planes_work_bytes.argtypes = [VP, SZ, CI, CI, CI, CI]
@@ -397,6 +399,81 @@ def conv_slots_plan(n, M, pitch, H, W, fh, fw, dil=1, pool=1):
     if steps[-1] >= n // 2:
         raise ValueError("conv_slots_plan: a tap's step reaches n/2")
     return ConvSlotsPlan(n, M, pitch, fh, fw, pool, steps, out_h, out_w, dil * pool)
+
+
+class ConvSlotsGeomPlan:
+    """What conv_slots_plan_geom returns.  steps [T]: the row rotation of every tap of the (fh + stride (pool - 1)) x (fw + stride (pool - 1)) window, row-major,
+    negative for a right rotation; elements [T]: crc_galois_elt_rows(step); out_h, out_w, out_dil: output (y, x) at slot origin + out_dil (y pitch + x) of every
+    period M; valid: those slots of the first period, row-major; needs_clean_input: pad > 0 -- every slot of a period that holds no pixel must hold exactly 0.
+    fold(w, t): the weights the taps take; mask_slots(): the 0/1 slot vector of the valid outputs"""
+    def __init__(self, n, M, pitch, origin, fh, fw, pad, stride, pool, pool_stride, steps, out_h, out_w, out_dil):
+        self.n, self.M, self.pitch, self.origin, self.fh, self.fw = n, M, pitch, origin, fh, fw
+        self.pad, self.stride, self.pool, self.pool_stride = pad, stride, pool, pool_stride
+        self.steps = steps
+        self.elements = [pow(3, s if s >= 0 else n // 2 + s, 2 * n) for s in steps]
+        self.out_h, self.out_w, self.out_dil = out_h, out_w, out_dil
+        self.needs_clean_input = pad > 0
+        self.valid = [origin + out_dil * (y * pitch + x) for y in range(out_h) for x in range(out_w)]
+
+    def fold(self, w, t):
+        """[Cout][Cin][fh][fw] integers -> [Cout][Cin][T] in [0, t): w'[a][b] = Sum_{u, v < pool} w[a - stride u][b - stride v] mod t"""
+        w = np.asarray(w)
+        if w.ndim != 4 or w.shape[2:] != (self.fh, self.fw):
+            raise ValueError("ConvSlotsGeomPlan.fold: weights must be [Cout][Cin][fh][fw]")
+        p, s, t = self.pool, self.stride, int(t)
+        out = np.zeros(w.shape[:2] + (self.fh + s * (p - 1), self.fw + s * (p - 1)), dtype=object)
+        wm = w.astype(object) % t
+        for u in range(p):
+            for v in range(p):
+                out[:, :, s * u:s * u + self.fh, s * v:s * v + self.fw] += wm
+        return (out % t).astype(np.int64).reshape(w.shape[0], w.shape[1], -1)
+
+    def mask_slots(self, n=None):
+        """int64 [n]: 1 exactly where (slot mod M) is in valid -- the plaintext slots of conv_slots_bias_mask's mask row"""
+        n = self.n if n is None else int(n)
+        if n % self.M:
+            raise ValueError("ConvSlotsGeomPlan.mask_slots: n must be a multiple of M")
+        row = np.zeros(self.M, dtype=np.int64)
+        row[self.valid] = 1
+        return np.tile(row, n // self.M)
+
+
+def conv_slots_plan_geom(n, M, pitch, origin, H, W, fh, fw, dil=1, pad=0, stride=1, pool=1, pool_stride=0):
+    """conv_slots_plan with an origin, `pad` zero pixels on every side, a conv stride and a pool x pool sum pool of stride pool_stride (0: pool) on the convolution's
+    outputs: pixel (y, x) at slot origin + dil (y pitch + x) of every period M; tap (a, b) is the row rotation by dil ((a - pad) pitch + (b - pad)); output (y, x)
+    lands at origin + dil stride pool_stride (y pitch + x).  pad = 0: non-pixel slots may hold anything.  pad > 0: they must hold exactly 0 (needs_clean_input).
+    Raises ValueError for what conv_slots_plan refuses, for outputs that leave the period or share a slot, and -- by enumeration over every tap of every valid
+    output -- for a tap beyond the plane's edge that lands on another pixel's slot modulo M (too little margin).  With pad = 0, stride = 1, pool_stride = pool and
+    origin = 0 it is conv_slots_plan"""
+    n, M, pitch, origin, H, W, fh, fw, dil, pad, stride, pool, ps = (int(v) for v in (n, M, pitch, origin, H, W, fh, fw, dil, pad, stride, pool, pool_stride))
+    if n < 2 or n & (n - 1) or M < 1 or M & (M - 1) or M > n // 2:
+        raise ValueError("conv_slots_plan_geom: M must be a power of two <= n/2")
+    ps = ps or pool
+    if min(pitch, H, W, fh, fw, dil, stride, pool, ps) < 1 or pad < 0 or origin < 0 or W > pitch or max(pitch, origin, H, W, fh, fw, dil, pad, stride, pool, ps) > M \
+            or origin + dil * ((H - 1) * pitch + W - 1) >= M or fh > H + 2 * pad or fw > W + 2 * pad:
+        raise ValueError("conv_slots_plan_geom: the plane does not fit (W <= pitch, origin + dil ((H - 1) pitch + W - 1) < M, window <= padded plane)")
+    ch, cw = (H + 2 * pad - fh) // stride + 1, (W + 2 * pad - fw) // stride + 1
+    if ch < pool or cw < pool:
+        raise ValueError("conv_slots_plan_geom: the pool leaves no output")
+    oh, ow = (ch - pool) // ps + 1, (cw - pool) // ps + 1
+    eh, ew, od = fh + stride * (pool - 1), fw + stride * (pool - 1), dil * stride * ps
+    if od > 0x7fffffff or origin + od * ((oh - 1) * pitch + ow - 1) >= M:
+        raise ValueError("conv_slots_plan_geom: an output lands beyond the period")
+    steps = [dil * ((a - pad) * pitch + (b - pad)) for a in range(eh) for b in range(ew)]
+    if max(abs(s) for s in steps) >= n // 2:
+        raise ValueError("conv_slots_plan_geom: a tap's step reaches n/2")
+    plan = ConvSlotsGeomPlan(n, M, pitch, origin, fh, fw, pad, stride, pool, ps, steps, oh, ow, od)
+    if len(set(plan.valid)) != len(plan.valid):
+        raise ValueError("conv_slots_plan_geom: two outputs share a slot")
+    pixel = {origin + dil * (y * pitch + x) for y in range(H) for x in range(W)}
+    for y in range(oh if pad else 0):
+        for x in range(ow):
+            for a in range(eh):
+                for b in range(ew):
+                    iy, ix = stride * ps * y + a - pad, stride * ps * x + b - pad
+                    if not (0 <= iy < H and 0 <= ix < W) and (plan.valid[y * ow + x] + steps[a * ew + b]) % M in pixel:
+                        raise ValueError("conv_slots_plan_geom: too little margin -- a tap beyond the plane's edge lands on a pixel's slot")
+    return plan
 
 
 class DensePlanesPlan:
@@ -1203,6 +1280,26 @@ class Engine:
         elts = self._elts(elts); gs = self._elts(gs)
         _chk(self.L.crc_conv_slots_forms(self.c, self.p(d_x), in_form, count, Cin, _pu(gs), gs.size, self.p(d_w), Cout, self.p(d_cgk), _pu(elts), elts.size, dbc,
                                          self.p(d_y), out_form, self.p(d_work), self.stream), "crc_conv_slots_forms")
+
+    def conv_slots_plan_geom(self, M, pitch, origin, H, W, fh, fw, dil=1, pad=0, stride=1, pool=1, pool_stride=0):
+        """binding.conv_slots_plan_geom at this ring"""
+        return conv_slots_plan_geom(self.n, M, pitch, origin, H, W, fh, fw, dil, pad, stride, pool, pool_stride)
+
+    def conv_slots_pack_bias(self, b):
+        """integers of any shape (taken mod t) -> uint64 [k] + shape: the word every position of the constant plaintext's NTT-form DELTA row holds
+        (plain_to_delta, form = NTT), per modulus"""
+        b = np.ascontiguousarray(b, dtype=np.int64)
+        out = np.zeros((self.k,) + b.shape, dtype=np.uint64)
+        _chk(self.L.crc_conv_slots_pack_bias(self.c, b.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), b.size, _pu(out)), "crc_conv_slots_pack_bias")
+        return out
+
+    def conv_slots_bias_mask(self, d_x, count, Cin, gs, d_w, Cout, d_bias, d_mask_ntt, d_cgk, elts, d_y, d_work, dbc=16, in_form=COEFF, out_form=COEFF):
+        """conv_slots, then + bias[co] on every slot (d_bias [k][Cout]: conv_slots_pack_bias, or None), then times the plaintext row d_mask_ntt [k][n]
+        (plain_to_ntt, or None) -- inside the channel mix's epilogue; bit for bit conv_slots into NTT form, add_plain, multiply_plain_ntt, one inverse transform"""
+        elts = self._elts(elts); gs = self._elts(gs)
+        _chk(self.L.crc_conv_slots_bias_mask_forms(self.c, self.p(d_x), in_form, count, Cin, _pu(gs), gs.size, self.p(d_w), Cout, self.p(d_bias), self.p(d_mask_ntt),
+                                                   self.p(d_cgk), _pu(elts), elts.size, dbc, self.p(d_y), out_form, self.p(d_work), self.stream),
+             "crc_conv_slots_bias_mask_forms")
 
     # ---- the dense layer over channel planes (crc_dense_planes_*): the outputs are rotated, one batched key switch with one key per step
     def dense_planes_plan(self, M, in_slots, out_slots):

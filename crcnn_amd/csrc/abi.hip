@@ -1648,14 +1648,37 @@ extern "C" int crc_conv_slots_pack_weights(const crc_ctx *c, const int64_t *h_w,
     return CRC_OK;
 }
 extern "C" size_t crc_conv_slots_work_bytes(const crc_ctx *c, size_t count, int Cin, int Cout, int T, int dbc) { return conv_bytes(c, count, Cin, Cout, T, dbc); }
-extern "C" int crc_conv_slots_forms(crc_ctx *c, const uint64_t *d_x, int in_form, size_t count, int Cin, const uint64_t *gs, int T, const uint64_t *d_w, int Cout,
-                                    const uint64_t *d_cgk, const uint64_t *elts, int n_elts, int dbc, uint64_t *d_y, int out_form, void *d_work, void *stream)
+// the constant plaintext b mod t in delta form: floor(q / t) c (+ q mod t for the upper half) mod q_i (plain_prep_kernel's mode 2) -- a constant polynomial's
+// NTT-form row holds that one word at every position
+extern "C" int crc_conv_slots_pack_bias(const crc_ctx *c, const int64_t *h_b, size_t count, uint64_t *h_out)
+{
+    if (!c || (count && (!h_b || !h_out))) return CRC_ERR_INVALID_ARGUMENT;
+    const int64_t t = (int64_t)c->t;
+    for (int i = 0; i < c->k; i++)
+        for (size_t j = 0; j < count; j++) {
+            const int64_t r = h_b[j] % t;
+            const u64 v = (u64)(r < 0 ? r + t : r);
+            unsigned __int128 z = (unsigned __int128)c->plain.delta[i] * v;
+            if (v >= c->plain.threshold) z += c->plain.uhi[i];
+            h_out[(size_t)i * count + j] = (u64)(z % c->q[i]);
+        }
+    return CRC_OK;
+}
+// crc_conv_slots_forms (d_bias = d_mask_ntt = NULL: galois_conv_mac_kernel<jt, false>, as it always ran) and crc_conv_slots_bias_mask_forms.  With a bias or a
+// mask every launch of the channel mix adds mask (.) (its own sum [+ bias on polynomial 0 where it writes the row first]): exact in Z_q, so the bits are those of
+// the unmasked call into NTT form, crc_add_plain of the constant's delta row per output channel, crc_multiply_plain_ntt by the mask row, one inverse transform
+static int conv_slots_run(crc_ctx *c, const uint64_t *d_x, int in_form, size_t count, int Cin, const uint64_t *gs, int T, const uint64_t *d_w, int Cout,
+                          const uint64_t *d_bias, const uint64_t *d_mask_ntt, const uint64_t *d_cgk, const uint64_t *elts, int n_elts, int dbc, uint64_t *d_y,
+                          int out_form, void *d_work, void *stream)
 {
     CHECK_CTX(c);
     if (!conv_counts_ok(count, Cin, Cout, T)) return CRC_ERR_INVALID_ARGUMENT;
     const size_t total = (size_t)Cin * count, outs = (size_t)Cout * count, wb = conv_bytes(c, count, Cin, Cout, T, dbc), ctw = crc_ct_words(c, 2);
     if (!hoist_args_ok(c, d_x, in_form, total, gs, T, d_cgk, elts, n_elts, dbc, d_y, outs, out_form, d_work, wb) ||
         !hoist_operand_ok(c, d_w, 8 * (size_t)c->k * Cout * Cin * T, d_y, outs, d_work, wb)) return CRC_ERR_INVALID_ARGUMENT;
+    const size_t bb = 8 * (size_t)c->k * Cout, mb = 8 * (size_t)c->k * c->n, xb = 8 * total * ctw;
+    if (d_bias && (!hoist_operand_ok(c, d_bias, bb, d_y, outs, d_work, wb) || ranges_overlap(d_bias, bb, d_x, xb))) return CRC_ERR_INVALID_ARGUMENT;
+    if (d_mask_ntt && (!hoist_operand_ok(c, d_mask_ntt, mb, d_y, outs, d_work, wb) || ranges_overlap(d_mask_ntt, mb, d_x, xb))) return CRC_ERR_INVALID_ARGUMENT;
     std::vector<int> at((size_t)T);
     if (!hoist_keys(c, gs, T, elts, n_elts, at.data())) return CRC_ERR_INVALID_ARGUMENT;
     if (count == 0) return CRC_OK;
@@ -1671,11 +1694,22 @@ extern "C" int crc_conv_slots_forms(crc_ctx *c, const uint64_t *d_x, int in_form
             const int rn = T - r0 < zc ? T - r0 : zc;
             const u64 *z[GALOIS_DIAG_MAX];
             RUN(hoist_group(H, xin, in_form, ch, o == 0, r0, rn, z));
-            RUN(k_galois_conv_mac(c, z, gs + r0, rn, d_w + r0, T, Cin, Cout, o, ch, count, r0 == 0, d_y, conv_jt(c), S(stream)));
+            RUN(k_galois_conv_mac(c, z, gs + r0, rn, d_w + r0, T, Cin, Cout, o, ch, count, r0 == 0, d_y, conv_jt(c), d_bias, d_mask_ntt, S(stream)));
         }
     }
     if (out_form == CRC_COEFF) RUN(crc_ntt_inv(c, d_y, outs, 2, stream));
     return CRC_OK;
+}
+extern "C" int crc_conv_slots_forms(crc_ctx *c, const uint64_t *d_x, int in_form, size_t count, int Cin, const uint64_t *gs, int T, const uint64_t *d_w, int Cout,
+                                    const uint64_t *d_cgk, const uint64_t *elts, int n_elts, int dbc, uint64_t *d_y, int out_form, void *d_work, void *stream)
+{
+    return conv_slots_run(c, d_x, in_form, count, Cin, gs, T, d_w, Cout, nullptr, nullptr, d_cgk, elts, n_elts, dbc, d_y, out_form, d_work, stream);
+}
+extern "C" int crc_conv_slots_bias_mask_forms(crc_ctx *c, const uint64_t *d_x, int in_form, size_t count, int Cin, const uint64_t *gs, int T, const uint64_t *d_w,
+                                              int Cout, const uint64_t *d_bias, const uint64_t *d_mask_ntt, const uint64_t *d_cgk, const uint64_t *elts, int n_elts,
+                                              int dbc, uint64_t *d_y, int out_form, void *d_work, void *stream)
+{
+    return conv_slots_run(c, d_x, in_form, count, Cin, gs, T, d_w, Cout, d_bias, d_mask_ntt, d_cgk, elts, n_elts, dbc, d_y, out_form, d_work, stream);
 }
 // ---- prepared keys that outlive a call: what k_relin64_prepare_keys leaves, per conjugated key, in a buffer of the caller's ----
 // Every hoisted entry point above prepares the fp64 form of its keys at the start of every call (three launches per key); a layer with hundreds of keys prepares them

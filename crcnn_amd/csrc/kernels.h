@@ -90,9 +90,10 @@ int k_galois_diag_mac_multi(crc_ctx *c, const u64 *const *z, const u64 *g, int b
                             hipStream_t st);
 // the packed convolution's channel mix (galois_conv_mac_kernel<jt>): y [Cout][count] (+)= Sum_ci Sum_{r < R} w[.][co][ci][r] sigma_{g[r]}(z[r][ci count + ct - o]) over the
 // flat ciphertexts [o, o + ch) of x [Cin][count] that the pass holds; w = &W[0][0][0][r0] of the scalar weights W [k][Cout][Cin][T], first: r0 = 0 (rows whose channel 0
-// lies in the pass are written, every other row accumulated into); R <= GALOIS_DIAG_MAX, jt in {2, 4, 8}
+// lies in the pass are written, every other row accumulated into); R <= GALOIS_DIAG_MAX, jt in {2, 4, 8}.  bias [k][Cout] / mask [k][n] (either may be null): each
+// launch adds mask (.) (its own sum [+ bias on polynomial 0 where it writes the row first]) -- galois_conv_mac_kernel<jt, true>; both null: <jt, false>
 int k_galois_conv_mac(crc_ctx *c, const u64 *const *z, const u64 *g, int R, const u64 *w, int T, int Cin, int Cout, size_t o, size_t ch, size_t count, bool first,
-                      u64 *y, int jt, hipStream_t st);
+                      u64 *y, int jt, const u64 *bias, const u64 *mask, hipStream_t st);
 // y [cnt][2][k][n] (+)= Sum_r sigma_{g[r]}(z[r]) on NTT-form ciphertexts, any R (GALOIS_DIAG_MAX per launch); y disjoint from every z[r]
 int k_galois_sum_permuted(crc_ctx *c, const u64 *const *z, const u64 *g, int R, size_t cnt, bool accumulate, u64 *y, hipStream_t st);
 int k_mac2(crc_ctx *c, const u64 *x, const u64 *w, u64 *y, const int *d_xoff, const int *d_toff, int B, const LayerShape &s, const u64 *bias_ntt,

@@ -262,11 +262,17 @@ int k_galois_sum_permuted(crc_ctx *c, const u64 *const *z, const u64 *g, int R, 
 // starts at tap 0) and accumulated into by every other; a workgroup with no channel of its ct in the launch leaves its row alone.  A last tile with fewer than JT
 // outputs computes its missing ones with the weights of channel Cout - 1 and does not store them.
 // grid: (count 2 k max(1, n / 512), ceil(Cout / JT))
+// EPI (crc_conv_slots_bias_mask_forms): an epilogue on the launch's own reduced sum, y = y_old + mask (.) (barrett128(Sum) [+ bias on polynomial 0, in the launch
+// that first writes the row]).  Exact arithmetic in Z_q on canonical residues, so mask (.) (A + B) = mask (.) A + mask (.) B over the launches of a row: y_old, which
+// earlier launches have masked already, stays outside the product, and the bias enters with the one launch that does not accumulate.  bias [k][Cout] (or null) is
+// uniform over the workgroup like the weights; mask [k][n] (or null) is one 16-byte load at the row's own position, issued after the tap loop, when the gather's
+// registers are dead, as is the read of y_old.  EPI = false is the kernel without any of this: bias and mask are not looked at
 struct GaloisConvArgs { const u64 *z[GALOIS_DIAG_MAX]; u32 g[GALOIS_DIAG_MAX]; };
-template <int JT>
+template <int JT, bool EPI>
 __global__ void __launch_bounds__(256, JT <= 4 ? 8 : 4) galois_conv_mac_kernel(GaloisConvArgs a, int R, const u64 *__restrict__ w, int T, int Cin, int Cout, size_t o,
                                                                              size_t ch, size_t count, int cA, int cB, int first, u64 *y, const ModParams *mods, int n,
-                                                                             int logn, int k, int blocks_per_row)
+                                                                             int logn, int k, int blocks_per_row, const u64 *__restrict__ bias,
+                                                                             const u64 *__restrict__ mask)
 {
     const size_t row = blockIdx.x / (u32)blocks_per_row; const u32 part = blockIdx.x - (u32)row * (u32)blocks_per_row;      // row = (ct 2 + poly) k + i
     const u32 s = (part * 256u + threadIdx.x) * 2u;
@@ -290,7 +296,7 @@ __global__ void __launch_bounds__(256, JT <= 4 ? 8 : 4) galois_conv_mac_kernel(G
     for (int t = 0; t < JT; t++) {
         wt[t] = w + ((size_t)i * Cout + (j0 + t < Cout ? j0 + t : Cout - 1)) * Cin * (size_t)T;
         acc0[t] = 0; acc1[t] = 0;
-        if (accumulate && j0 + t < Cout) { const ulonglong2 v = ld2(yo + (size_t)t * yj); acc0[t] = v.x; acc1[t] = v.y; }
+        if (!EPI && accumulate && j0 + t < Cout) { const ulonglong2 v = ld2(yo + (size_t)t * yj); acc0[t] = v.x; acc1[t] = v.y; }
     }
     for (int ci = lo; ci < hi; ci++) {
         const size_t zo = (((size_t)ci * count + ct - o) * 2 * (size_t)k + pk) * n, wo = (size_t)ci * T;
@@ -307,9 +313,24 @@ __global__ void __launch_bounds__(256, JT <= 4 ? 8 : 4) galois_conv_mac_kernel(G
             }
         }
     }
+    if (!EPI) {
 #pragma unroll
-    for (int t = 0; t < JT; t++)
-        if (j0 + t < Cout) st2(yo + (size_t)t * yj, barrett128((u64)acc0[t], (u64)(acc0[t] >> 64), m), barrett128((u64)acc1[t], (u64)(acc1[t] >> 64), m));
+        for (int t = 0; t < JT; t++)
+            if (j0 + t < Cout) st2(yo + (size_t)t * yj, barrett128((u64)acc0[t], (u64)(acc0[t] >> 64), m), barrett128((u64)acc1[t], (u64)(acc1[t] >> 64), m));
+        return;
+    }
+    const bool biased = bias && !accumulate && pk < (u32)k;                // polynomial 0 of a row that this launch writes first
+    ulonglong2 mk{1, 1};
+    if (mask) mk = ld2(mask + (size_t)i * n + s);
+#pragma unroll
+    for (int t = 0; t < JT; t++) {
+        if (j0 + t >= Cout) continue;
+        u64 r0 = barrett128((u64)acc0[t], (u64)(acc0[t] >> 64), m), r1 = barrett128((u64)acc1[t], (u64)(acc1[t] >> 64), m);
+        if (biased) { const u64 b = bias[(size_t)i * Cout + j0 + t]; r0 = addmod(r0, b, m.q); r1 = addmod(r1, b, m.q); }
+        if (mask) { r0 = mulmod(r0, mk.x, m); r1 = mulmod(r1, mk.y, m); }
+        if (accumulate) { const ulonglong2 v = ld2(yo + (size_t)t * yj); r0 = addmod(r0, v.x, m.q); r1 = addmod(r1, v.y, m.q); }
+        st2(yo + (size_t)t * yj, r0, r1);
+    }
 }
 // the terms one reduction may sum: terms q_max^2 + q_max < 2^128 (diag_group's rule without its cap of one launch's pointers)
 static int conv_terms(const crc_ctx *c)
@@ -321,15 +342,20 @@ static int conv_terms(const crc_ctx *c)
 }
 template <int JT>
 static void conv_launch(crc_ctx *c, const GaloisConvArgs &a, int rn, const u64 *w, int T, int Cin, int Cout, size_t o, size_t ch, size_t count, int cA, int cB,
-                        bool first, u64 *y, unsigned blocks, int bpr, hipStream_t st)
+                        bool first, u64 *y, unsigned blocks, int bpr, const u64 *bias, const u64 *mask, hipStream_t st)
 {
-    hipLaunchKernelGGL(galois_conv_mac_kernel<JT>, dim3(blocks, (unsigned)((Cout + JT - 1) / JT)), dim3(256), 0, st, a, rn, w, T, Cin, Cout, o, ch, count, cA, cB,
-                       first ? 1 : 0, y, c->d_mods, c->n, c->logn, c->k, bpr);
+    const dim3 grid(blocks, (unsigned)((Cout + JT - 1) / JT));
+    if (bias || mask)
+        hipLaunchKernelGGL((galois_conv_mac_kernel<JT, true>), grid, dim3(256), 0, st, a, rn, w, T, Cin, Cout, o, ch, count, cA, cB, first ? 1 : 0, y, c->d_mods, c->n,
+                           c->logn, c->k, bpr, bias, mask);
+    else
+        hipLaunchKernelGGL((galois_conv_mac_kernel<JT, false>), grid, dim3(256), 0, st, a, rn, w, T, Cin, Cout, o, ch, count, cA, cB, first ? 1 : 0, y, c->d_mods, c->n,
+                           c->logn, c->k, bpr, bias, mask);
 }
 // z: the R <= GALOIS_DIAG_MAX key-switch results of the pass [o, o + ch) of the flat input [Cin][count], g their elements; w: &d_w[0][0][0][r0] of [k][Cout][Cin][T];
-// first: r0 = 0; y [Cout][count]; jt: 2 | 4 | 8
+// first: r0 = 0; y [Cout][count]; jt: 2 | 4 | 8; bias [k][Cout] and mask [k][n], either may be null: the epilogue instantiation where one is given
 int k_galois_conv_mac(crc_ctx *c, const u64 *const *z, const u64 *g, int R, const u64 *w, int T, int Cin, int Cout, size_t o, size_t ch, size_t count, bool first,
-                      u64 *y, int jt, hipStream_t st)
+                      u64 *y, int jt, const u64 *bias, const u64 *mask, hipStream_t st)
 {
     if (count == 0 || ch == 0 || R < 1) return CRC_OK;
     if (R > GALOIS_DIAG_MAX || Cin < 1 || Cout < 1 || o + ch > (size_t)Cin * count || (jt != 2 && jt != 4 && jt != 8)) return CRC_ERR_INVALID_ARGUMENT;
@@ -345,9 +371,9 @@ int k_galois_conv_mac(crc_ctx *c, const u64 *const *z, const u64 *g, int R, cons
         for (int cA = c_lo; cA < c_hi; cA += cper) {
             const int cB = c_hi - cA < cper ? c_hi : cA + cper;
             const bool f = first && r0 == 0;
-            if (jt == 2) conv_launch<2>(c, a, rn, w + r0, T, Cin, Cout, o, ch, count, cA, cB, f, y, (unsigned)blocks, bpr, st);
-            else if (jt == 4) conv_launch<4>(c, a, rn, w + r0, T, Cin, Cout, o, ch, count, cA, cB, f, y, (unsigned)blocks, bpr, st);
-            else conv_launch<8>(c, a, rn, w + r0, T, Cin, Cout, o, ch, count, cA, cB, f, y, (unsigned)blocks, bpr, st);
+            if (jt == 2) conv_launch<2>(c, a, rn, w + r0, T, Cin, Cout, o, ch, count, cA, cB, f, y, (unsigned)blocks, bpr, bias, mask, st);
+            else if (jt == 4) conv_launch<4>(c, a, rn, w + r0, T, Cin, Cout, o, ch, count, cA, cB, f, y, (unsigned)blocks, bpr, bias, mask, st);
+            else conv_launch<8>(c, a, rn, w + r0, T, Cin, Cout, o, ch, count, cA, cB, f, y, (unsigned)blocks, bpr, bias, mask, st);
             HIPCHK(hipGetLastError());
         }
     }

@@ -802,30 +802,36 @@ ciphertext3D matvecSlotsBsgs(const ciphertext3D &t, const vector<vector<int64_t>
     return out;
 }
 // ---- the packed convolution: one channel plane per ciphertext ---------------------------------------------------------------
-static ConvSlotsPlan convSlotsPlan(const SlotPlanes &g)
+// (the general planner: at origin = 0, pad = 0, stride = 1, pool_stride = pool it is crc_conv_slots_plan field for field)
+static ConvSlotsGeomPlan convSlotsPlan(const SlotPlanes &g)
 {
-    ConvSlotsPlan P;
-    if (!crc_conv_slots_plan(N(), g.M, g.pitch, g.H, g.W, g.fh, g.fw, g.dil, g.pool, P))
-        throw invalid_argument("convSlots: M must be a power of two <= n/2, the plane must fit it and the window must leave an output");
+    ConvSlotsGeomPlan P;
+    if (!crc_conv_slots_plan_geom(N(), g.M, g.pitch, g.origin, g.H, g.W, g.fh, g.fw, g.dil, g.pad, g.stride, g.pool, g.pool_stride, P))
+        throw invalid_argument("convSlots: M must be a power of two <= n/2, the plane must fit it with the margin its pad needs and the window must leave an output");
     return P;
 }
-SlotPlanes planesOf(int xd, int yd, int M)
+SlotPlanes planesOf(int xd, int yd, int M, int margin)
 {
     SlotPlanes g;
-    g.M = M; g.pitch = yd; g.H = xd; g.W = yd;
+    g.M = M; g.pitch = yd + margin; g.H = xd; g.W = yd; g.origin = margin * (g.pitch + 1);
     return g;
 }
-ciphertext3D encryptImagePlanes(const vector<int64_t> &pixels, int zd, int xd, int yd, int M, int out_form)
+SlotPlanes planesOf(int xd, int yd, int M) { return planesOf(xd, yd, M, 0); }
+ciphertext3D encryptImagePlanes(const vector<int64_t> &pixels, int zd, int xd, int yd, int M, int margin, int out_form)
 {
     if (!g_slot_on) throw logic_error("encryptImagePlanes: setSlotEncoding() must be called first");
     const int n = N();
     if (zd < 1 || xd < 1 || yd < 1 || pixels.size() != (size_t)zd * xd * yd) throw invalid_argument("encryptImagePlanes: [zd][xd][yd] pixels");
-    if (M < 1 || (M & (M - 1)) || M > n / 2 || (long long)xd * yd > M) throw invalid_argument("encryptImagePlanes: M must be a power of two <= n/2 that holds a plane");
+    if (M < 1 || (M & (M - 1)) || M > n / 2 || margin < 0 || margin > M || ((long long)xd + margin) * ((long long)yd + margin) + margin > M)
+        throw invalid_argument("encryptImagePlanes: M must be a power of two <= n/2 that holds a plane and its margin");
     if (out_form != CRC_COEFF && out_form != CRC_NTT) throw invalid_argument("encryptImagePlanes: ciphertext forms only (CRC_COEFF / CRC_NTT)");
     const size_t per = (size_t)xd * yd;
+    const int pitch = yd + margin, origin = margin * (pitch + 1);       // (the last pixel at origin + (xd - 1) pitch + yd - 1 < (xd + margin)(yd + margin) + margin)
     vector<int64_t> h((size_t)zd * n, 0);                               // plane-major: slot i of plane z at h[z n + i]
     for (int z = 0; z < zd; z++)
-        for (int i = 0; i < n; i++) if ((size_t)(i % M) < per) h[(size_t)z * n + i] = pixels[(size_t)z * per + i % M];
+        for (int base = 0; base < n; base += M)
+            for (int r = 0; r < xd; r++)
+                for (int c = 0; c < yd; c++) h[(size_t)z * n + base + origin + r * pitch + c] = pixels[(size_t)z * per + (size_t)r * yd + c];
     DeviceBuffer d_v(h.size() * 8), d_pl(h.size() * 8), d_work(crc_encrypt_dev_work_bytes(ctx(), zd));
     const uint64_t *d_pk = deviceKey(g_d_pk, g_d_pk_fp, public_key, "public key");
     chk(crc_memcpy_h2d(ctx(), d_v.ptr, h.data(), h.size() * 8, stream()), "crc_memcpy_h2d");
@@ -841,7 +847,7 @@ ciphertext3D encryptImagePlanes(const vector<int64_t> &pixels, int zd, int xd, i
     chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
     return out;
 }
-ciphertext3D encryptImagePlanes(const vector<float> &pixels, int zd, int xd, int yd, int M, int out_form)
+ciphertext3D encryptImagePlanes(const vector<float> &pixels, int zd, int xd, int yd, int M, int margin, int out_form)
 {
     if (!g_slot_on) throw logic_error("encryptImagePlanes: setSlotEncoding() must be called first");
     const double scale = ldexp(1.0, g_slot_in_bits);
@@ -851,45 +857,64 @@ ciphertext3D encryptImagePlanes(const vector<float> &pixels, int zd, int xd, int
         if (!(fabs(r) < 9.2e18)) throw invalid_argument("encryptImagePlanes: a pixel does not fit an int64 at this scale");
         q[i] = (int64_t)r;
     }
-    return encryptImagePlanes(q, zd, xd, yd, M, out_form);
+    return encryptImagePlanes(q, zd, xd, yd, M, margin, out_form);
 }
+ciphertext3D encryptImagePlanes(const vector<int64_t> &pixels, int zd, int xd, int yd, int M, int out_form) { return encryptImagePlanes(pixels, zd, xd, yd, M, 0, out_form); }
+ciphertext3D encryptImagePlanes(const vector<float> &pixels, int zd, int xd, int yd, int M, int out_form) { return encryptImagePlanes(pixels, zd, xd, yd, M, 0, out_form); }
 vector<vector<int64_t>> decryptPlanes(const ciphertext3D &t, const SlotPlanes &g)
 {
-    if (g.M < 1 || g.M > N() || g.pitch < 1 || g.H < 1 || g.W < 1 || g.dil < 1 || g.W > g.pitch || (long long)g.dil * ((long long)(g.H - 1) * g.pitch + g.W - 1) >= g.M)
+    if (g.M < 1 || g.M > N() || g.pitch < 1 || g.H < 1 || g.W < 1 || g.dil < 1 || g.W > g.pitch || g.origin < 0 ||
+        g.origin + (long long)g.dil * ((long long)(g.H - 1) * g.pitch + g.W - 1) >= g.M)
         throw invalid_argument("decryptPlanes: the plane does not fit its period");
     const vector<vector<int64_t>> v = decryptSlots(t, g.M);            // [M][count]
     vector<vector<int64_t>> out(t.count());
     for (size_t z = 0; z < out.size(); z++)
-        for (int r = 0; r < g.H; r++) for (int c = 0; c < g.W; c++) out[z].push_back(v[(size_t)g.dil * (r * g.pitch + c)][z]);
+        for (int r = 0; r < g.H; r++) for (int c = 0; c < g.W; c++) out[z].push_back(v[(size_t)g.origin + (size_t)g.dil * (r * g.pitch + c)][z]);
     return out;
 }
 vector<uint64_t> convSlotsElements(const SlotPlanes &g)
 {
-    const ConvSlotsPlan P = convSlotsPlan(g);
+    const ConvSlotsGeomPlan P = convSlotsPlan(g);
     vector<uint64_t> out;
     for (uint64_t e : P.elements) if (e != 1 && find(out.begin(), out.end(), e) == out.end()) out.push_back(e);
     return out;
 }
 ciphertext3D convSlots(const ciphertext3D &t, const vector<int64_t> &weights, int Cout, const SlotPlanes &g, SlotPlanes *og, int out_form)
 {
+    return convSlots(t, weights, Cout, g, {}, false, og, out_form);
+}
+ciphertext3D convSlots(const ciphertext3D &t, const vector<int64_t> &weights, int Cout, const SlotPlanes &g, const vector<int64_t> &bias, bool mask, SlotPlanes *og,
+                       int out_form)
+{
     if (!crc_slots_supported(ctx())) throw logic_error("encryption parameters do not support batching");
-    const ConvSlotsPlan P = convSlotsPlan(g);
+    const ConvSlotsGeomPlan P = convSlotsPlan(g);
     const vector<uint64_t> gs = hoistedElements("convSlots", t, P.steps, out_form);
     if (t.B != 1 || t.xd != 1 || t.yd != 1) throw invalid_argument("convSlots: a tensor [1][zd][1][1] of channel planes (encryptImagePlanes)");
     const int Cin = (int)t.count(), T = (int)P.steps.size(), k = crc_ctx_k(ctx()), dbc = galoisDbc();
     vector<int64_t> folded;
-    if (Cout < 1 || !crc_conv_slots_fold(P, weights, Cout, Cin, (int64_t)g_plain_modulus, folded)) throw invalid_argument("convSlots: weights must be [Cout][Cin][fh][fw]");
+    if (Cout < 1 || !crc_conv_slots_fold_geom(P, weights, Cout, Cin, (int64_t)g_plain_modulus, folded)) throw invalid_argument("convSlots: weights must be [Cout][Cin][fh][fw]");
+    if (!bias.empty() && bias.size() != (size_t)Cout) throw invalid_argument("convSlots: the bias must be [Cout]");
     vector<uint64_t> packed((size_t)k * folded.size());
     chk(crc_conv_slots_pack_weights(ctx(), folded.data(), folded.size(), packed.data()), "crc_conv_slots_pack_weights");
     if (!crc_conv_slots_work_bytes(ctx(), 1, Cin, Cout, T, dbc)) throw invalid_argument("convSlots: too many channels or taps");
     DeviceBuffer d_w(packed.size() * 8);
     chk(crc_memcpy_h2d(ctx(), d_w.ptr, packed.data(), packed.size() * 8, stream()), "crc_memcpy_h2d");
+    shared_ptr<DeviceBuffer> d_b, d_m;                                  // the packed bias [k][Cout]; the mask's NTT-form row [k][n]
+    if (!bias.empty()) {
+        vector<uint64_t> pb((size_t)k * Cout);
+        chk(crc_conv_slots_pack_bias(ctx(), bias.data(), bias.size(), pb.data()), "crc_conv_slots_pack_bias");
+        d_b = make_shared<DeviceBuffer>(pb.size() * 8);
+        chk(crc_memcpy_h2d(ctx(), d_b->ptr, pb.data(), pb.size() * 8, stream()), "crc_memcpy_h2d");
+        chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");       // (pb goes out of scope here)
+    }
+    if (mask) d_m = plainRowsNtt(crc_conv_slots_mask_slots(P), 1);
     ciphertext3D out(1, Cout, 1, 1, out_form);
     ensure(g_scratch, crc_conv_slots_work_bytes(ctx(), 1, Cin, Cout, T, dbc));
-    chk(crc_conv_slots_forms(ctx(), t.data(), t.form, 1, Cin, gs.data(), T, (const uint64_t *)d_w.ptr, Cout, galoisCkeys(),
-                             galois_elts.data(), (int)galois_elts.size(), dbc, out.data(), out_form, g_scratch->ptr, stream()), "convSlots");
-    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");           // (the weights' buffer goes out of scope here)
-    if (og) { *og = SlotPlanes(); og->M = g.M; og->pitch = g.pitch; og->H = P.out_h; og->W = P.out_w; og->dil = P.out_dil; }
+    chk(crc_conv_slots_bias_mask_forms(ctx(), t.data(), t.form, 1, Cin, gs.data(), T, (const uint64_t *)d_w.ptr, Cout, d_b ? (const uint64_t *)d_b->ptr : nullptr,
+                                       d_m ? (const uint64_t *)d_m->ptr : nullptr, galoisCkeys(), galois_elts.data(), (int)galois_elts.size(), dbc, out.data(),
+                                       out_form, g_scratch->ptr, stream()), "convSlots");
+    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");           // (the weights', the bias' and the mask's buffers go out of scope here)
+    if (og) { *og = SlotPlanes(); og->M = g.M; og->pitch = g.pitch; og->origin = g.origin; og->H = P.out_h; og->W = P.out_w; og->dil = P.out_dil; }
     return out;
 }
 // ---- the dense layer over channel planes: the outputs are rotated, one batched key switch with one key per step ------------
@@ -904,10 +929,11 @@ static DensePlanesPlan densePlanesPlan(int M, const vector<int> &in_slots, int O
 }
 vector<int> densePlanesInSlots(const SlotPlanes &g)
 {
-    if (g.M < 1 || g.pitch < 1 || g.H < 1 || g.W < 1 || g.dil < 1 || g.W > g.pitch || (long long)g.dil * ((long long)(g.H - 1) * g.pitch + g.W - 1) >= g.M)
+    if (g.M < 1 || g.pitch < 1 || g.H < 1 || g.W < 1 || g.dil < 1 || g.W > g.pitch || g.origin < 0 ||
+        g.origin + (long long)g.dil * ((long long)(g.H - 1) * g.pitch + g.W - 1) >= g.M)
         throw invalid_argument("densePlanes: the plane does not fit its period");
     vector<int> out;
-    for (int r = 0; r < g.H; r++) for (int c = 0; c < g.W; c++) out.push_back(g.dil * (r * g.pitch + c));
+    for (int r = 0; r < g.H; r++) for (int c = 0; c < g.W; c++) out.push_back(g.origin + g.dil * (r * g.pitch + c));
     return out;
 }
 vector<uint64_t> densePlanesElements(int M, const vector<int> &in_slots, int O, const vector<int> &out_slots)

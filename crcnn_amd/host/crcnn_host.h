@@ -201,13 +201,21 @@ void bsgsMatvecPlan(const std::vector<std::vector<int64_t>> &W, int M, int n, in
 // crcnn_amd/host/diag_plan.h).  SlotPlanes says where a tensor [1][zd][1][1] keeps its planes: pixel (r, c) of an H x W plane at slot dil (r pitch + c), tiled with
 // period M over both rows of n/2 slots (matvecSlots' input contract); fh, fw, pool describe the layer applied to it -- a 'valid' fh x fw convolution of stride 1,
 // then a pool x pool sum pool of stride pool, folded into the taps.  Slots that hold no valid pixel hold junk: no masks, no zero padding.
-struct SlotPlanes { int M = 0, pitch = 0, H = 0, W = 0, dil = 1, fh = 1, fw = 1, pool = 1; };
+// The appended fields are the general layer (crc_conv_slots_plan_geom): the plane begins at slot `origin`, the window has `pad` zero pixels on every side and
+// moves with `stride`, the pool's windows with pool_stride (0: pool).  pad > 0 needs a CLEAN tensor -- every slot of a period that holds no pixel exactly 0 -- which
+// encryptImagePlanes with a margin, a masked convSlots and densePlanes give.
+struct SlotPlanes { int M = 0, pitch = 0, H = 0, W = 0, dil = 1, fh = 1, fw = 1, pool = 1, origin = 0, stride = 1, pad = 0, pool_stride = 0; };
 // pixels [zd][xd][yd] (integers as they are; floats quantised as encryptImageSlots quantises) -> a tensor [1][zd][1][1] of zd ciphertexts, plane z with its xd rows
 // of yd pixels at pitch yd, dilation 1, period M.  Keystream discipline as encryptImage.  std::logic_error unless setSlotEncoding is on; std::invalid_argument
 // for M not a power of two <= n/2 or a plane that does not fit it.  planesOf: the SlotPlanes of such a tensor
 ciphertext3D encryptImagePlanes(const std::vector<int64_t> &pixels, int zd, int xd, int yd, int M, int out_form = CRC_COEFF);
 ciphertext3D encryptImagePlanes(const std::vector<float> &pixels, int zd, int xd, int yd, int M, int out_form = CRC_COEFF);
 SlotPlanes planesOf(int xd, int yd, int M);
+// the same with `margin` empty slots around the plane: pitch yd + margin, origin margin (pitch + 1), zeros everywhere else -- a clean tensor whose first layer may
+// have a pad of up to `margin`.  std::invalid_argument also for a negative margin or a plane that no longer fits M
+ciphertext3D encryptImagePlanes(const std::vector<int64_t> &pixels, int zd, int xd, int yd, int M, int margin, int out_form);
+ciphertext3D encryptImagePlanes(const std::vector<float> &pixels, int zd, int xd, int yd, int M, int margin, int out_form);
+SlotPlanes planesOf(int xd, int yd, int M, int margin);
 // the H x W valid pixels of every plane of the tensor, from the first period, as centred integers [zd][H W]
 std::vector<std::vector<int64_t>> decryptPlanes(const ciphertext3D &t, const SlotPlanes &g);
 // y[co] = Sum_ci conv(x[ci], weights[co][ci]) (+ pool) over the global Galois keys: plans (crc_conv_slots_plan), folds and packs the weights
@@ -216,7 +224,13 @@ std::vector<std::vector<int64_t>> decryptPlanes(const ciphertext3D &t, const Slo
 // Exceptions as matvecSlots: std::logic_error without batching, std::invalid_argument for a geometry the planner refuses, a weight count that is not
 // Cout t.zd fh fw, other forms, a missing key
 ciphertext3D convSlots(const ciphertext3D &t, const std::vector<int64_t> &weights, int Cout, const SlotPlanes &g, SlotPlanes *out = nullptr, int out_form = CRC_COEFF);
-// the Galois elements of the layer's taps without the element 1, each once (at most (fh + pool - 1)(fw + pool - 1) - 1 keys); std::invalid_argument as convSlots
+// The same with a bias [Cout] (any int64, taken mod t; empty: none) added to every slot and, with mask = true, every slot that holds no output set to exactly 0:
+// crc_conv_slots_bias_mask_forms, both inside the channel mix's epilogue.  The mask row is composed and transformed once per call.  A masked result is clean: the
+// next layer may have a pad, as far as the margin around the plane reaches.  std::invalid_argument also for a bias whose size is neither 0 nor Cout
+ciphertext3D convSlots(const ciphertext3D &t, const std::vector<int64_t> &weights, int Cout, const SlotPlanes &g, const std::vector<int64_t> &bias, bool mask,
+                       SlotPlanes *out = nullptr, int out_form = CRC_COEFF);
+// the Galois elements of the layer's taps without the element 1, each once (at most T - 1 keys; a tap left of or above the anchor is a right rotation);
+// std::invalid_argument as convSlots
 std::vector<uint64_t> convSlotsElements(const SlotPlanes &g);
 // The dense layer behind the last packed convolution (crc_dense_planes_forms): t [1][Cin][1][1] holds Cin planes whose valid entries sit at in_slots [P] of every
 // period M (the H x W pixels of a SlotPlanes: densePlanesInSlots; every other slot may hold junk), W [O][Cin][P] are integer weights (any int64, taken mod t).  The

@@ -125,6 +125,110 @@ inline bool crc_conv_slots_fold(const ConvSlotsPlan &P, const std::vector<int64_
     return true;
 }
 
+// ---- the packed convolution with strides, zero padding and a general pool (convSlots with a bias and a mask; crc_conv_slots_bias_mask_forms) ----
+// Pixel (y, x) of an H x W plane at slot origin + dil (y pitch + x), tiled with period M over both rows of n/2 slots.  `pad` zero pixels on every side, conv
+// stride `stride`, then a pool x pool sum pool of stride pool_stride on the convolution's outputs (pool = 1: none; pool_stride = 0 means pool).  The window becomes
+// eh x ew = (fh + stride (pool - 1)) x (fw + stride (pool - 1)); tap (a, b) is the row rotation by dil ((a - pad) pitch + (b - pad)) -- a negative step is a right
+// rotation, crc_galois_elt_rows' rule: 3^(n/2 - |step|) -- with the weight w'[a][b] = Sum_{u, v < pool} w[a - stride u][b - stride v]; ch = (H + 2 pad - fh) / stride
+// + 1 convolution rows, out_h = (ch - pool) / pool_stride + 1 pooled ones, and output (y, x) lands at origin + out_dil (y pitch + x), out_dil = dil stride
+// pool_stride: the same origin and pitch.
+// pad = 0: slots that hold no pixel may hold anything (every tap of a valid output reads a pixel).  pad > 0: needs_clean_input -- every slot of a period that is no
+// pixel must hold exactly 0, because that is where the taps beyond the edge read.  A result multiplied by mask_slots is clean again, and so is what
+// encryptImagePlanes with a margin or densePlanes writes.
+struct ConvSlotsGeomPlan {
+    int n = 0, M = 0, pitch = 0, origin = 0, fh = 0, fw = 0, pad = 0, stride = 0, pool = 0, pool_stride = 0;
+    int out_h = 0, out_w = 0, out_dil = 0;
+    bool needs_clean_input = false;
+    std::vector<int> steps;                  // [T] row-major over the enlarged window; negative: a right rotation
+    std::vector<uint64_t> elements;          // [T] crc_galois_elt_rows(step); step 0: the element 1, which needs no key
+    std::vector<int> valid;                  // [out_h out_w] row-major: the slots of the first period that hold an output
+};
+// false (P untouched) for what crc_conv_slots_plan refuses (M not a power of two <= n/2, a plane that does not fit, a window larger than the padded plane, no
+// output, |step| >= n/2), for outputs that leave the period or share a slot, and -- by enumeration over every tap of every valid output -- for a tap beyond the
+// plane's edge that lands on another pixel's slot modulo M: too little margin (pitch < W + pad, or an origin too small).  With pad = 0, stride = 1,
+// pool_stride = pool and origin = 0 the steps, elements, output geometry and valid list are crc_conv_slots_plan's
+inline bool crc_conv_slots_plan_geom(int n, int M, int pitch, int origin, int H, int W, int fh, int fw, int dil, int pad, int stride, int pool, int pool_stride,
+                                     ConvSlotsGeomPlan &P)
+{
+    if (n < 2 || (n & (n - 1)) || M < 1 || (M & (M - 1)) || M > n / 2) return false;
+    if (pool_stride == 0) pool_stride = pool;
+    if (pitch < 1 || H < 1 || W < 1 || fh < 1 || fw < 1 || dil < 1 || stride < 1 || pool < 1 || pool_stride < 1 || pad < 0 || origin < 0 || W > pitch) return false;
+    for (int v : {pitch, origin, H, W, fh, fw, dil, pad, stride, pool, pool_stride}) if (v > M) return false;     // (every factor at most M <= 2^30 from here on)
+    const int64_t span = (int64_t)(H - 1) * pitch + W - 1;
+    if (origin >= M || (span > 0 && dil > ((int64_t)M - 1 - origin) / span)) return false;                      // origin + dil span >= M
+    if (fh > H + 2 * (int64_t)pad || fw > W + 2 * (int64_t)pad) return false;
+    const int64_t ch = (H + 2 * (int64_t)pad - fh) / stride + 1, cw = (W + 2 * (int64_t)pad - fw) / stride + 1;
+    if (ch < pool || cw < pool) return false;
+    const int64_t oh = (ch - pool) / pool_stride + 1, ow = (cw - pool) / pool_stride + 1;
+    const int64_t eh = fh + (int64_t)stride * (pool - 1), ew = fw + (int64_t)stride * (pool - 1);               // (<= H + 2 pad, W + 2 pad: ch, cw >= pool)
+    if ((int64_t)dil * stride > 0x7fffffff || (int64_t)dil * stride * pool_stride > 0x7fffffff) return false;  // (dil stride <= 2^60, then <= 2^31 times 2^30)
+    const int64_t od = (int64_t)dil * stride * pool_stride;
+    const int64_t last = (oh - 1) * pitch + ow - 1;
+    if (last > 0 && od > ((int64_t)M - 1 - origin) / last) return false;                                         // an output beyond the period
+    int64_t far = 0;                                                                                             // max |(a - pad) pitch + (b - pad)|: at a corner
+    for (int64_t a : {(int64_t)0, eh - 1})
+        for (int64_t b : {(int64_t)0, ew - 1}) {
+            const int64_t v = (a - pad) * pitch + (b - pad);
+            far = v < 0 ? (-v > far ? -v : far) : (v > far ? v : far);
+        }
+    if (far > 0 && dil > (n / 2 - 1) / far) return false;                                                        // |step| >= n/2
+    ConvSlotsGeomPlan Q;
+    Q.n = n; Q.M = M; Q.pitch = pitch; Q.origin = origin; Q.fh = fh; Q.fw = fw; Q.pad = pad; Q.stride = stride; Q.pool = pool; Q.pool_stride = pool_stride;
+    Q.out_h = (int)oh; Q.out_w = (int)ow; Q.out_dil = (int)od; Q.needs_clean_input = pad > 0;
+    const uint64_t mask = 2 * (uint64_t)n - 1;
+    for (int64_t a = 0; a < eh; a++)
+        for (int64_t b = 0; b < ew; b++) {
+            const int s = (int)(dil * ((a - pad) * pitch + (b - pad)));
+            uint64_t g = 1;
+            for (uint64_t e = (uint64_t)(s < 0 ? n / 2 + s : s), x = 3; e; e >>= 1, x = x * x & mask) if (e & 1) g = g * x & mask;
+            Q.steps.push_back(s); Q.elements.push_back(g);
+        }
+    std::vector<char> pixel((size_t)M, 0), out((size_t)M, 0);
+    for (int y = 0; y < H; y++) for (int x = 0; x < W; x++) pixel[(size_t)(origin + (int64_t)dil * ((int64_t)y * pitch + x))] = 1;
+    for (int64_t y = 0; y < oh; y++)
+        for (int64_t x = 0; x < ow; x++) {
+            const int64_t s = origin + od * (y * pitch + x);
+            if (out[(size_t)s]) return false;                                                                    // two outputs in one slot
+            out[(size_t)s] = 1; Q.valid.push_back((int)s);
+            for (int64_t a = 0; a < eh && pad > 0; a++)
+                for (int64_t b = 0; b < ew; b++) {
+                    const int64_t iy = (int64_t)stride * pool_stride * y + a - pad, ix = (int64_t)stride * pool_stride * x + b - pad;
+                    if (iy >= 0 && iy < H && ix >= 0 && ix < W) continue;
+                    if (pixel[(size_t)(((s + Q.steps[(size_t)(a * ew + b)]) % M + M) % M)]) return false;        // a zero of the padding that is a pixel
+                }
+        }
+    P = Q;
+    return true;
+}
+// w [Cout][Cin][fh][fw] (any int64) -> out [Cout][Cin][T] in [0, t): w'[a][b] = Sum_{u, v < pool} w[a - stride u][b - stride v] mod t.  false (out untouched)
+// for a size that is not Cout Cin fh fw, or t < 2
+inline bool crc_conv_slots_fold_geom(const ConvSlotsGeomPlan &P, const std::vector<int64_t> &w, int Cout, int Cin, int64_t t, std::vector<int64_t> &out)
+{
+    if (Cout < 1 || Cin < 1 || t < 2 || P.fh < 1 || P.fw < 1 || P.pool < 1 || P.stride < 1 || w.size() != (size_t)Cout * Cin * P.fh * P.fw) return false;
+    const size_t eh = (size_t)P.fh + (size_t)P.stride * (P.pool - 1), ew = (size_t)P.fw + (size_t)P.stride * (P.pool - 1);
+    std::vector<int64_t> o((size_t)Cout * Cin * eh * ew, 0);
+    for (size_t c = 0; c < (size_t)Cout * Cin; c++)
+        for (int a = 0; a < P.fh; a++)
+            for (int b = 0; b < P.fw; b++) {
+                int64_t v = w[(c * P.fh + a) * P.fw + b] % t;
+                if (v < 0) v += t;
+                for (int u = 0; u < P.pool; u++)
+                    for (int x = 0; x < P.pool; x++) {
+                        int64_t &d = o[(c * eh + a + (size_t)P.stride * u) * ew + b + (size_t)P.stride * x];
+                        d = d >= t - v ? d - (t - v) : d + v;               // (d + v mod t without leaving [0, t))
+                    }
+            }
+    out = o;
+    return true;
+}
+// the 0/1 slot vector [n] that is 1 exactly where (slot mod M) is a valid output: the plaintext whose NTT-form row is crc_conv_slots_bias_mask_forms' d_mask_ntt
+inline std::vector<int64_t> crc_conv_slots_mask_slots(const ConvSlotsGeomPlan &P)
+{
+    std::vector<int64_t> m((size_t)(P.n > 0 ? P.n : 0), 0);
+    for (int s : P.valid) for (int i = s; P.M > 0 && i < P.n; i += P.M) m[(size_t)i] = 1;
+    return m;
+}
+
 // ---- the dense layer over channel planes (densePlanes; crc_dense_planes_forms) ----
 // Cin ciphertexts x_c whose valid entries sit at the slots in_slots [P] of every period M (tiled over both rows of n/2 slots: matvecSlots' contract; every other
 // slot may hold junk), O outputs that land at the slots out_slots [O].  The OUTPUTS are rotated (rotate_rows' convention: after a rotation by r, slot i holds
@@ -195,3 +299,4 @@ inline bool crc_dense_planes_fold(const DensePlanesPlan &P, const std::vector<in
 }
 // where a packed convolution leaves its outputs: the in_slots of the dense layer behind it
 inline std::vector<int> crc_dense_planes_in_slots(const ConvSlotsPlan &P) { return P.valid; }
+inline std::vector<int> crc_dense_planes_in_slots(const ConvSlotsGeomPlan &P) { return P.valid; }

@@ -33,6 +33,16 @@
 // (the first period's slots), prints "budget <name> <min bits>" and "planes <name> equal|differs" (every output slot of every period against the integer network
 // computed here, every other slot 0), then "steps conv <T> dense_1 <R> dense_2 <R>", "keys planes <bytes> prepared <bytes> elements <count>",
 // "throws <case> <kind>" and "hoist_host planes ok".
+//
+//   hoist_host <dir> convpad       (tests/test_gpu_conv_slots_pad_cpp.py)
+//
+// A padded, strided chain through convSlots with a bias and a mask: <dir>/image.i64 = [12][12] pixels, <dir>/w1.i64 = [2][1][3][3], <dir>/b1.i64 = [2],
+// <dir>/w2.i64 = [3][2][3][3]; M = 256, the image encrypted with a margin of 1 (pitch 13, origin 14).  Layer 1 is 3 x 3 with pad 1, stride 1, the bias and the mask
+// (12 x 12 outputs, a clean tensor), layer 2 is 3 x 3 with pad 1 and stride 2 (6 x 6 outputs at dilation 2) and reads the margin the mask zeroed.  Keys:
+// convSlotsElements of both layers, each element once.  Per case (convpad_fresh, convpad_1, convpad_2, convpad_2_ntt = both layers NTT-resident) writes
+// <dir>/<name>.i64 = [channels][H W] (decryptPlanes), prints "budget <name> <min bits>" and "conv <name> equal|differs" (every valid pixel against the integer
+// convolution computed here), "clean convpad_1 yes|no" (every slot of layer 1's result that holds no output is 0, in every period), "budget convpad_1_unmasked
+// <min bits>", then "keys convpad <bytes> elements <count>", "throws <case> <kind>" and "hoist_host convpad ok".
 #include "crcnn_host.h"
 #include "diag_plan.h"
 #include <algorithm>
@@ -190,6 +200,76 @@ static int conv_case(const vector<uint64_t> &p, const vector<uint64_t> &q)
     return 0;
 }
 
+// [Cin][H][W] -> [Cout][oh][ow]: `pad` zero pixels on every side, stride `stride`, w [Cout][Cin][fh][fw], + bias[co] where one is given; exact integers
+static vector<vector<int64_t>> conv_pad_int(const vector<vector<int64_t>> &x, int H, int W, const vector<int64_t> &w, int Cout, int fh, int fw, int pad, int stride,
+                                            const vector<int64_t> &bias)
+{
+    const int Cin = (int)x.size(), oh = (H + 2 * pad - fh) / stride + 1, ow = (W + 2 * pad - fw) / stride + 1;
+    vector<vector<int64_t>> y(Cout, vector<int64_t>((size_t)oh * ow, 0));
+    for (int co = 0; co < Cout; co++) for (int r = 0; r < oh; r++) for (int c = 0; c < ow; c++) {
+        int64_t acc = bias.empty() ? 0 : bias[co];
+        for (int ci = 0; ci < Cin; ci++) for (int a = 0; a < fh; a++) for (int b = 0; b < fw; b++) {
+            const int iy = stride * r + a - pad, ix = stride * c + b - pad;
+            if (iy >= 0 && iy < H && ix >= 0 && ix < W) acc += w[(((size_t)co * Cin + ci) * fh + a) * fw + b] * x[ci][(size_t)iy * W + ix];
+        }
+        y[co][(size_t)r * ow + c] = acc;
+    }
+    return y;
+}
+static int convpad_case(const vector<uint64_t> &p, const vector<uint64_t> &q)
+{
+    const int M = 256, H = 12, W = 12, margin = 1;
+    auto ints = [&](const char *file) { const auto raw = rd(dir + "/" + file); return vector<int64_t>(raw.begin(), raw.end()); };
+    const vector<int64_t> img = ints("image.i64"), w1 = ints("w1.i64"), b1 = ints("b1.i64"), w2 = ints("w2.i64");
+    setParameters(n, q, p[2], 0);
+    setSlotEncoding(0, 0);
+    SlotPlanes g1 = planesOf(H, W, M, margin);
+    if (g1.pitch != 13 || g1.origin != 14 || g1.stride != 1 || g1.pad != 0 || g1.pool_stride != 0) return 5;
+    g1.fh = 3; g1.fw = 3; g1.pad = 1;
+    const ciphertext3D x = encryptImagePlanes(img, 1, H, W, M, margin, CRC_COEFF);
+    SlotPlanes g2 = planesOf(H, W, M, margin);                          // a 'same' layer: the second one sees the first one's geometry
+    g2.fh = 3; g2.fw = 3; g2.pad = 1; g2.stride = 2;
+    vector<uint64_t> elts = convSlotsElements(g1);
+    for (uint64_t e : convSlotsElements(g2)) if (find(elts.begin(), elts.end(), e) == elts.end()) elts.push_back(e);
+    generateGaloisKeys(16, elts);
+    const vector<vector<int64_t>> x0{img}, y1 = conv_pad_int(x0, H, W, w1, 2, 3, 3, 1, 1, b1), y2 = conv_pad_int(y1, H, W, w2, 3, 3, 3, 1, 2, {});
+    planes("convpad_fresh", x, planesOf(H, W, M, margin), x0);
+    {                                                                   // the fresh tensor is clean: zeros around the plane
+        const vector<vector<int64_t>> v = decryptSlots(x, n);
+        const vector<int> in = densePlanesInSlots(planesOf(H, W, M, margin));
+        bool clean = true;
+        for (int i = 0; i < n; i++) if (find(in.begin(), in.end(), i % M) == in.end()) clean = clean && v[i][0] == 0;
+        printf("clean convpad_fresh %s\n", clean ? "yes" : "no");
+    }
+    SlotPlanes o1, g3;
+    const ciphertext3D c1 = convSlots(x, w1, 2, g1, b1, true, &o1);
+    if (o1.H != H || o1.W != W || o1.dil != 1 || o1.pitch != g1.pitch || o1.origin != g1.origin || o1.M != M || o1.pad != 0) return 6;
+    planes("convpad_1", c1, o1, y1);
+    {
+        const vector<vector<int64_t>> v = decryptSlots(c1, n);          // [n][2]
+        const vector<int> in = densePlanesInSlots(o1);
+        bool clean = true;
+        for (int i = 0; i < n; i++) if (find(in.begin(), in.end(), i % M) == in.end()) clean = clean && v[i][0] == 0 && v[i][1] == 0;
+        printf("clean convpad_1 %s\n", clean ? "yes" : "no");
+    }
+    printf("budget convpad_1_unmasked %d\n", minNoiseBudget(convSlots(x, w1, 2, g1, b1, false)));
+    const ciphertext3D c2 = convSlots(c1, w2, 3, g2, &g3);
+    if (g3.H != 6 || g3.W != 6 || g3.dil != 2 || g3.origin != g1.origin) return 7;
+    planes("convpad_2", c2, g3, y2);
+    { const ciphertext3D n1 = convSlots(x, w1, 2, g1, b1, true, nullptr, CRC_NTT); planes("convpad_2_ntt", convSlots(n1, w2, 3, g2, nullptr, CRC_NTT), g3, y2); }
+    printf("keys convpad %zu elements %zu\n", elts.size() * crc_evk_words(context, 16) * 8, elts.size());
+    thrown("bad_bias", [&] { convSlots(x, w1, 2, g1, vector<int64_t>(3, 1), true); });
+    thrown("too_little_margin", [&] { SlotPlanes b = g1; b.pad = 2; convSlots(x, w1, 2, b, b1, true); });
+    thrown("pad_without_margin", [&] { SlotPlanes b = planesOf(16, 16, M); b.fh = 3; b.fw = 3; b.pad = 1; convSlotsElements(b); });
+    thrown("negative_margin", [&] { encryptImagePlanes(img, 1, H, W, M, -1, CRC_COEFF); });
+    thrown("margin_too_large", [&] { encryptImagePlanes(img, 1, H, W, M, 4, CRC_COEFF); });      // 16 . 16 + 4 slots
+    thrown("bad_stride", [&] { SlotPlanes b = g1; b.stride = 0; convSlots(x, w1, 2, b, b1, true); });
+    delParameters();
+    clearDeterministicSeed();
+    printf("hoist_host convpad ok\n");
+    return 0;
+}
+
 // every slot of y against `want` at out_slots of every period M and 0 elsewhere: "planes <name> equal|differs"
 static void vector_slots(const char *name, const ciphertext3D &y, int M, const vector<int> &out_slots, const vector<int64_t> &want, int64_t t)
 {
@@ -268,7 +348,7 @@ static int planes_case(const vector<uint64_t> &p, const vector<uint64_t> &q)
 
 int main(int argc, char **argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: hoist_host <dir> [bsgs | conv | planes]\n"); return 1; }
+    if (argc < 2) { fprintf(stderr, "usage: hoist_host <dir> [bsgs | conv | planes | convpad]\n"); return 1; }
     try {
         dir = argv[1];
         setDeterministicSeed(20241019);
@@ -278,6 +358,7 @@ int main(int argc, char **argv)
         if (argc > 2 && string(argv[2]) == "bsgs") return bsgs_case(p, q);
         if (argc > 2 && string(argv[2]) == "conv") return conv_case(p, q);
         if (argc > 2 && string(argv[2]) == "planes") return planes_case(p, q);
+        if (argc > 2 && string(argv[2]) == "convpad") return convpad_case(p, q);
         const vector<vector<int64_t>> W8 = matrix(dir + "/w8.i64", 8, 8), W5 = matrix(dir + "/w5.i64", 5, 8);
         // a plain modulus without slots: the reference's logic_error, before any key is looked at
         setParameters(n, q, (uint64_t)1 << 20, 0);

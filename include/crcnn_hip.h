@@ -693,6 +693,18 @@ int crc_sum_slots_forms(crc_ctx *ctx, const uint64_t *d_x, int in_form, size_t c
  *                               arguments); Cin, Cout <= 4096, T <= 1024
  *   crc_conv_slots_pack_weights host memory, any context: h_out [k][count] from count integers h_w (any int64, taken mod t): for c = w mod t in [0, t) the word
  *                               c >= (t + 1) / 2 ? c + q_i - t : c  (mod q_i) -- every position of the NTT-form row of the constant plaintext c
+ *   crc_conv_slots_bias_mask_forms  crc_conv_slots_forms with an epilogue in the channel mix: d_bias [k][Cout] (crc_conv_slots_pack_bias) or NULL, d_mask_ntt [k][n]
+ *                               (ONE NTT-form plaintext row, crc_plain_to_ntt -- of a 0/1 slot vector for zero padding, but any canonical residues) or NULL.
+ *                               Bit for bit, in this order: crc_conv_slots_forms into NTT form; with d_bias, per output channel crc_add_plain (sign +1, group =
+ *                               count) of the NTT-form delta row of the constant b[co]; with d_mask_ntt, crc_multiply_plain_ntt of all Cout count ciphertexts by
+ *                               the row (group = Cout count); one inverse transform for CRC_COEFF -- at every tuning setting and pass structure.  Both NULL is
+ *                               crc_conv_slots_forms itself.  The masked result never leaves the kernel unmasked: no read and write of the Cout count rows, no
+ *                               further launch.  A result masked by the 0/1 vector of its valid slots decrypts to exactly 0 elsewhere, which is what a layer
+ *                               with zero padding behind it needs (crc_conv_slots_plan_geom, crcnn_amd/host/diag_plan.h).  Work space and caps as
+ *                               crc_conv_slots_forms; refused also for d_bias or d_mask_ntt misaligned or overlapping d_y, d_work or d_x
+ *   crc_conv_slots_pack_bias    host memory, any context: h_out [k][count] from count integers h_b (any int64, taken mod t): for c = b mod t in [0, t) the word
+ *                               floor(q / t) c + (c >= (t + 1) / 2 ? q mod t : 0)  (mod q_i) -- every position of crc_plain_to_delta(form = CRC_NTT) of the
+ *                               constant plaintext c
  *   crc_galois_prepare_keys_dev prepared keys that outlive a call: d_pk [n_elts][crc_galois_prepared_key_words(ctx, dbc)] from the CONJUGATED keys d_cgk of elts --
  *                               per key exactly what every entry point above makes of it in pass 0 of every call (the fp64 key switch's form).  d_scratch:
  *                               crc_evk_words(ctx, dbc) words.  CRC_ERR_UNSUPPORTED (and 0 words) where the fp64 key switch does not take (parameters, dbc);
@@ -735,6 +747,11 @@ size_t crc_conv_slots_work_bytes(const crc_ctx *ctx, size_t count, int Cin, int 
 int crc_conv_slots_forms(crc_ctx *ctx, const uint64_t *d_x /*[Cin][count]*/, int in_form, size_t count, int Cin, const uint64_t *gs /*[T], host*/, int T,
                          const uint64_t *d_w /*[k][Cout][Cin][T]*/, int Cout, const uint64_t *d_cgk, const uint64_t *elts, int n_elts, int dbc,
                          uint64_t *d_y /*[Cout][count]*/, int out_form, void *d_work, void *stream);
+int crc_conv_slots_pack_bias(const crc_ctx *ctx, const int64_t *h_b, size_t count, uint64_t *h_out /*[k][count]*/);
+int crc_conv_slots_bias_mask_forms(crc_ctx *ctx, const uint64_t *d_x /*[Cin][count]*/, int in_form, size_t count, int Cin, const uint64_t *gs /*[T], host*/, int T,
+                                   const uint64_t *d_w /*[k][Cout][Cin][T]*/, int Cout, const uint64_t *d_bias /*[k][Cout] or NULL*/,
+                                   const uint64_t *d_mask_ntt /*[k][n] or NULL*/, const uint64_t *d_cgk, const uint64_t *elts, int n_elts, int dbc,
+                                   uint64_t *d_y /*[Cout][count]*/, int out_form, void *d_work, void *stream);
 size_t crc_galois_prepared_key_words(const crc_ctx *ctx, int dbc);
 int crc_galois_prepare_keys_dev(crc_ctx *ctx, const uint64_t *d_cgk, const uint64_t *elts, int n_elts, int dbc, uint64_t *d_pk /*[n_elts][prepared_key_words]*/,
                                 uint64_t *d_scratch /*[crc_evk_words]*/, void *stream);
