@@ -280,6 +280,10 @@ def load():
     L.crc_dense_planes_work_bytes.restype = SZ; L.crc_dense_planes_work_bytes.argtypes = [VP, SZ, CI, CI, CI, CI]
     L.crc_dense_planes_forms.argtypes = [VP, VP, CI, SZ, CI, PU, CI, VP, VP, PU, CI, VP, CI, VP, CI, VP, VP]
     L.crc_noise_budget.argtypes = [VP, PU, PU, CI]
+    L.crc_mod_switch_supported.argtypes = [VP, VP]
+    L.crc_mod_switch_work_bytes.restype = SZ; L.crc_mod_switch_work_bytes.argtypes = [VP, VP, SZ, CI, CI, CI]
+    L.crc_mod_switch_forms.argtypes = [VP, VP, VP, CI, SZ, CI, VP, CI, VP, VP]
+    L.crc_mod_switch.argtypes = [VP, VP, PU, CI, SZ, CI, PU, CI]
     _lib = L
     return L
 
@@ -628,6 +632,33 @@ class Engine:
         out = np.zeros(cap, dtype=np.uint64)
         cnt = _chk(self.L.crc_ctx_table(self.c, name.encode(), _pu(out), cap), f"crc_ctx_table({name})")
         return out[:cnt].copy()
+
+    # ---- modulus switching: continue over the first `kept` moduli (crc_mod_switch*)
+    def level(self, kept):
+        """a second Engine over the first `kept` moduli: same n, t and device.  Rows [0, kept) of this engine's NTT-form secret key, public key and plaintext rows
+        are valid there; evaluation and Galois keys are generated afresh on it (gen_evk / gen_galois_keys with the prefix secret-key rows)"""
+        kept = int(kept)
+        if not 1 <= kept < self.k:
+            raise ValueError(f"level({kept}): a level keeps 1 .. {self.k - 1} of the {self.k} moduli")
+        return Engine(self.n, [int(v) for v in self.q[:kept]], self.t, device=self.device)
+
+    def mod_switch_supported(self, to):
+        return bool(self.L.crc_mod_switch_supported(self.c, to.c))
+
+    def mod_switch_work_bytes(self, to, count, size=2, in_form=COEFF, out_form=COEFF):
+        return self.L.crc_mod_switch_work_bytes(self.c, to.c, count, size, in_form, out_form)
+
+    def mod_switch_dev(self, to, d_in, count, d_out, d_work, size=2, in_form=COEFF, out_form=COEFF):
+        """d_in [count][size][k][n] of this engine -> d_out [count][size][to.k][n] of `to`, on this engine's stream"""
+        _chk(self.L.crc_mod_switch_forms(self.c, to.c, self.p(d_in), in_form, count, size, self.p(d_out), out_form, self.p(d_work), self.stream),
+             "crc_mod_switch_forms")
+
+    def mod_switch(self, to, cts, size=2, in_form=COEFF, out_form=COEFF):
+        """host twin: ciphertexts [count][size][k][n] -> [count][size][to.k][n]"""
+        cts = np.ascontiguousarray(cts, dtype=np.uint64).reshape(-1, size, self.k, self.n)
+        out = np.zeros((cts.shape[0], size, to.k, self.n), dtype=np.uint64)
+        _chk(self.L.crc_mod_switch(self.c, to.c, _pu(cts), in_form, cts.shape[0], size, _pu(out), out_form), "crc_mod_switch")
+        return out
 
     # ---- host side: encode / client
     def encode(self, values, dtype=np.float32):

@@ -1851,3 +1851,31 @@ extern "C" int crc_square_relin(crc_ctx *c, const uint64_t *d_x, size_t count, c
 {
     return crc_square_relin_forms(c, d_x, CRC_COEFF, count, d_evk, dbc, d_y, CRC_COEFF, d_work, stream);
 }
+
+// ---- modulus switching: a ciphertext tensor of `from` continues over the first k' moduli (kernels_modswitch.hip) ----
+static bool mod_switch_args_ok(const crc_ctx *from, const crc_ctx *to, int size, int in_form, int out_form)
+{
+    return k_mod_switch_supported(from, to) && (size == 2 || size == 3) && form_ok(in_form) && form_ok(out_form);
+}
+extern "C" int crc_mod_switch_supported(const crc_ctx *from, const crc_ctx *to) { return k_mod_switch_supported(from, to) ? 1 : 0; }
+extern "C" size_t crc_mod_switch_work_bytes(const crc_ctx *from, const crc_ctx *to, size_t count, int size, int in_form, int out_form)
+{
+    return mod_switch_args_ok(from, to, size, in_form, out_form) ? k_mod_switch_work_bytes(from, to, count * size, in_form, out_form) : 0;
+}
+extern "C" int crc_mod_switch_forms(crc_ctx *from, const crc_ctx *to, const uint64_t *d_in, int in_form, size_t count, int size, uint64_t *d_out, int out_form,
+                                    void *d_work, void *stream)
+{
+    CHECK_CTX(from);
+    if (!d_in || !d_out || !d_work || !mod_switch_args_ok(from, to, size, in_form, out_form)) return CRC_ERR_INVALID_ARGUMENT;
+    if (((uintptr_t)d_in & 15) || ((uintptr_t)d_out & 15)) return CRC_ERR_INVALID_ARGUMENT;
+    const size_t in_b = 8 * count * crc_ct_words(from, size), out_b = 8 * count * crc_ct_words(to, size);
+    const size_t wb = k_mod_switch_work_bytes(from, to, count * size, in_form, out_form);
+    if (ranges_overlap(d_in, in_b, d_out, out_b) || ranges_overlap(d_work, wb, d_in, in_b) || ranges_overlap(d_work, wb, d_out, out_b)) return CRC_ERR_INVALID_ARGUMENT;
+    return k_mod_switch(from, to, d_in, in_form, count * size, d_out, out_form, d_work, S(stream));
+}
+extern "C" int crc_mod_switch(const crc_ctx *from, const crc_ctx *to, const uint64_t *h_in, int in_form, size_t count, int size, uint64_t *h_out, int out_form)
+{
+    if (!h_in || !h_out || !mod_switch_args_ok(from, to, size, in_form, out_form)) return CRC_ERR_INVALID_ARGUMENT;
+    if (ranges_overlap(h_in, 8 * count * crc_ct_words(from, size), h_out, 8 * count * crc_ct_words(to, size))) return CRC_ERR_INVALID_ARGUMENT;
+    return k_mod_switch_host(from, to, h_in, in_form, count * size, h_out, out_form);
+}

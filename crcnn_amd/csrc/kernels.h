@@ -137,6 +137,13 @@ int k_slots_decompose_host(crc_ctx *c, const u64 *plain, size_t count, int slots
 int k_slots_rescale(crc_ctx *c, const u64 *d_in, size_t count, u64 divisor, u64 *d_out, hipStream_t st);
 int k_slots_rescale_host(crc_ctx *c, const u64 *plain_in, size_t count, u64 divisor, u64 *plain_out);
 
+// kernels_modswitch.hip: modulus switching from `from` to a context over a proper prefix of its moduli -- tensors of `polys` polynomials [polys][k][n] -> [polys][k'][n],
+// either side CRC_COEFF or CRC_NTT (work: k_mod_switch_work_bytes); *_host: the host twin
+bool   k_mod_switch_supported(const crc_ctx *from, const crc_ctx *to);
+size_t k_mod_switch_work_bytes(const crc_ctx *from, const crc_ctx *to, size_t polys, int in_form, int out_form);
+int k_mod_switch(crc_ctx *from, const crc_ctx *to, const u64 *d_in, int in_form, size_t polys, u64 *d_out, int out_form, void *d_work, hipStream_t st);
+int k_mod_switch_host(const crc_ctx *from, const crc_ctx *to, const u64 *in, int in_form, size_t polys, u64 *out, int out_form);
+
 // kernels_mfma.hip: conv / dense multiply-accumulate as an int8 limb GEMM on the matrix cores (operand form CRC_NTTL)
 bool   k_limb_supported(const crc_ctx *c, int T);
 size_t k_limb_tensor_bytes(const crc_ctx *c, int B, int zd, int npos);

@@ -22,6 +22,7 @@ crc_ctx *context = nullptr;
 // stream would order itself against every other blocking stream of the process.  A global like the context, the keys and the work buffer
 // (CrCNN/src/globals.h:18-26).
 static void *g_stream = nullptr;
+static uint64_t g_generation = 0;                          // counts delParameters(): what a Level (below) was made under
 void setStream(void *s) { g_stream = s; }
 void *getStream() { return g_stream; }
 static inline void *stream() { return g_stream; }
@@ -344,6 +345,7 @@ static const uint64_t *deviceKey(shared_ptr<DeviceBuffer> &d, uint64_t &fp, cons
 
 void delParameters()
 {
+    g_generation++;                                         // levels made under these parameters are stale from here on
     ev_keys16.reset();
     g_galois_keys.reset(); g_galois_ckeys.reset(); g_galois_pkeys.reset(); galois_elts.clear(); galois_keys_host.clear(); g_galois_dbc = 0;
     g_d_sk.reset(); g_d_pk.reset();
@@ -1155,49 +1157,176 @@ void SlotRescaleLayer::printLayerStructure() { cerr << "SlotRescaleLayer " << na
 // area.  The result buffer: one {min, first index} pair per pass, then the budgets -- so the pairs and the first ciphertext's budget are one small copy
 struct DeviceBudgets { shared_ptr<DeviceBuffer> buf; size_t passes = 0, pass = 0, count = 0;
     int32_t *pairs() const { return (int32_t *)buf->ptr; } int32_t *bits() const { return pairs() + 2 * passes; } };
-static DeviceBudgets deviceBudgets(const ciphertext3D &t, const char *who)
+// what the measurement reads: a tensor of the global context under the global secret key, or a LevelTensor under its level's
+struct BudgetView { crc_ctx *c; const uint64_t *d_sk; const uint64_t *data; size_t count; int form; };
+static BudgetView budgetView(const ciphertext3D &t, const char *who)
 {
     if (!t.buf || t.count() == 0) throw invalid_argument(string(who) + ": empty tensor");
+    return BudgetView{ctx(), deviceKey(g_d_sk, g_d_sk_fp, secret_key, "secret key"), t.data(), t.count(), t.form};
+}
+static DeviceBudgets deviceBudgets(const BudgetView &t, const char *who)
+{
     if (t.form != CRC_COEFF && t.form != CRC_NTT) throw invalid_argument(string(who) + ": ciphertext forms only (CRC_COEFF / CRC_NTT)");
-    const uint64_t *d_sk = deviceKey(g_d_sk, g_d_sk_fp, secret_key, "secret key");
+    const size_t ctb = crc_ct_words(t.c, 2) * 8;
     DeviceBudgets r;
-    r.count = t.count();
-    const size_t one = crc_noise_budget_dev_work_bytes(ctx(), 1, 2, t.form);
+    r.count = t.count;
+    const size_t one = crc_noise_budget_dev_work_bytes(t.c, 1, 2, t.form);
     r.pass = ((size_t)4 << 30) / (one ? one : 1);
     if (r.pass < 1024) r.pass = 1024;
     if (r.pass > r.count) r.pass = r.count;
     r.passes = (r.count + r.pass - 1) / r.pass;
-    ensure(g_scratch, crc_noise_budget_dev_work_bytes(ctx(), r.pass, 2, t.form));
+    ensure(g_scratch, crc_noise_budget_dev_work_bytes(t.c, r.pass, 2, t.form));
     r.buf = make_shared<DeviceBuffer>((2 * r.passes + r.count) * sizeof(int32_t));
     for (size_t o = 0, pi = 0; o < r.count; o += r.pass, pi++) {
         const size_t c = min(r.pass, r.count - o);
-        chk(crc_noise_budget_dev(ctx(), d_sk, (const uint64_t *)((const char *)t.data() + o * ctBytes()), c, 2, t.form, r.bits() + o, r.pairs() + 2 * pi,
+        chk(crc_noise_budget_dev(t.c, t.d_sk, (const uint64_t *)((const char *)t.data + o * ctb), c, 2, t.form, r.bits() + o, r.pairs() + 2 * pi,
                                  g_scratch->ptr, stream()), "crc_noise_budget_dev");
     }
     return r;
 }
-vector<int> noiseBudgets(const ciphertext3D &t)
+static vector<int> allBudgets(const BudgetView &t, const char *who)
 {
-    const DeviceBudgets r = deviceBudgets(t, "noiseBudgets");
+    const DeviceBudgets r = deviceBudgets(t, who);
     vector<int32_t> h(r.count);
-    chk(crc_memcpy_d2h(ctx(), h.data(), r.bits(), r.count * sizeof(int32_t), stream()), "crc_memcpy_d2h");
-    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+    chk(crc_memcpy_d2h(t.c, h.data(), r.bits(), r.count * sizeof(int32_t), stream()), "crc_memcpy_d2h");
+    chk(crc_stream_sync(t.c, stream()), "crc_stream_sync");
     return vector<int>(h.begin(), h.end());
 }
+vector<int> noiseBudgets(const ciphertext3D &t) { return allBudgets(budgetView(t, "noiseBudgets"), "noiseBudgets"); }
 // {min, first index} of the tensor and the budget of its ciphertext 0
-static int minAndFirstBudget(const ciphertext3D &t, const char *who, size_t *where, int *first)
+static int minAndFirstBudget(const BudgetView &t, const char *who, size_t *where, int *first)
 {
     const DeviceBudgets r = deviceBudgets(t, who);
     vector<int32_t> h(2 * r.passes + 1);
-    chk(crc_memcpy_d2h(ctx(), h.data(), r.pairs(), h.size() * sizeof(int32_t), stream()), "crc_memcpy_d2h");
-    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+    chk(crc_memcpy_d2h(t.c, h.data(), r.pairs(), h.size() * sizeof(int32_t), stream()), "crc_memcpy_d2h");
+    chk(crc_stream_sync(t.c, stream()), "crc_stream_sync");
     int best = h[0]; size_t at = (size_t)h[1];
     for (size_t pi = 1; pi < r.passes; pi++) if (h[2 * pi] < best) { best = h[2 * pi]; at = pi * r.pass + (size_t)h[2 * pi + 1]; }
     if (where) *where = at;
     if (first) *first = h[2 * r.passes];
     return best;
 }
+static int minAndFirstBudget(const ciphertext3D &t, const char *who, size_t *where, int *first) { return minAndFirstBudget(budgetView(t, who), who, where, first); }
 int minNoiseBudget(const ciphertext3D &t, size_t *where) { return minAndFirstBudget(t, "minNoiseBudget", where, nullptr); }
+
+// ---- levels: a tensor continues over the first `kept` moduli (crc_mod_switch_forms) --------------------------------------
+// A Level belongs to the parameters it was made under: setParameters() / delParameters() start a new generation, and a level of an older one is refused.
+Level::~Level() { if (ctx) crc_ctx_destroy(ctx); }
+shared_ptr<Level> makeLevel(int kept)
+{
+    const int k = K(), n = N();
+    if (kept < 1 || kept >= k) throw invalid_argument("makeLevel: a level keeps 1 .. k - 1 of the " + to_string(k) + " coefficient moduli");
+    if (secret_key.size() != (size_t)k * n || public_key.size() != (size_t)2 * k * n) throw logic_error("makeLevel: the keys do not match the parameters");
+    vector<uint64_t> q(k);
+    chk(crc_ctx_table(ctx(), "q", q.data(), k), "crc_ctx_table");
+    auto L = make_shared<Level>();
+    chk(crc_ctx_create(n, q.data(), kept, g_plain_modulus, crc_ctx_device(ctx()), &L->ctx), "makeLevel: crc_ctx_create");
+    if (!crc_mod_switch_supported(ctx(), L->ctx)) throw logic_error("makeLevel: the prefix context is not a level of the parameters");
+    L->kept = kept; L->generation = g_generation;
+    L->secret_key.assign(secret_key.begin(), secret_key.begin() + (size_t)kept * n);
+    for (int p = 0; p < 2; p++) L->public_key.insert(L->public_key.end(), public_key.begin() + (size_t)p * k * n, public_key.begin() + ((size_t)p * k + kept) * n);
+    L->d_secret_key = make_shared<DeviceBuffer>(L->secret_key.size() * 8);
+    chk(crc_memcpy_h2d(L->ctx, L->d_secret_key->ptr, L->secret_key.data(), L->secret_key.size() * 8, stream()), "crc_memcpy_h2d");
+    chk(crc_stream_sync(L->ctx, stream()), "crc_stream_sync");
+    return L;
+}
+static const Level &levelOf(const shared_ptr<Level> &L, const char *who)
+{
+    if (!L || !L->ctx) throw invalid_argument(string(who) + ": no level");
+    if (!context || L->generation != g_generation) throw invalid_argument(string(who) + ": the level was made under other parameters");
+    return *L;
+}
+static const Level &levelOf(const LevelTensor &t, const char *who)
+{
+    const Level &L = levelOf(t.level, who);
+    if (!t.buf || t.count() == 0) throw invalid_argument(string(who) + ": empty tensor");
+    if (t.buf->bytes < t.count() * crc_ct_words(L.ctx, 2) * 8) throw invalid_argument(string(who) + ": the tensor does not have this level's ciphertext size");
+    return L;
+}
+vector<uint64_t> LevelTensor::toHost() const
+{
+    const Level &L = levelOf(*this, "LevelTensor::toHost");
+    vector<uint64_t> h(count() * crc_ct_words(L.ctx, 2));
+    chk(crc_memcpy_d2h(L.ctx, h.data(), data(), h.size() * 8, stream()), "crc_memcpy_d2h");
+    chk(crc_stream_sync(L.ctx, stream()), "crc_stream_sync");
+    return h;
+}
+void LevelTensor::save(const string &path) const
+{
+    const Level &L = levelOf(*this, "LevelTensor::save");
+    if (form != CRC_COEFF) throw invalid_argument("LevelTensor::save: tensor is in NTT form");
+    const vector<uint64_t> h = toHost();
+    const size_t one = crc_seal_ct_bytes(L.ctx, 2), ctw = crc_ct_words(L.ctx, 2);
+    vector<uint8_t> b(one * count()); size_t w = 0;
+    for (size_t i = 0; i < count(); i++) chk(crc_seal_ct_save(L.ctx, h.data() + i * ctw, 2, b.data() + i * one, one, &w), "crc_seal_ct_save");
+    writeFile(path, b);
+}
+LevelTensor LevelTensor::load(const shared_ptr<Level> &level, int B, int zd, int xd, int yd, const string &path)
+{
+    const Level &L = levelOf(level, "LevelTensor::load");
+    if (B < 1 || zd < 1 || xd < 1 || yd < 1) throw invalid_argument("LevelTensor::load: empty shape");
+    const vector<uint8_t> b = readFile(path);
+    LevelTensor t; t.B = B; t.zd = zd; t.xd = xd; t.yd = yd; t.form = CRC_COEFF; t.level = level;
+    const size_t cnt = t.count(), ctw = crc_ct_words(L.ctx, 2);
+    vector<uint64_t> h(cnt * ctw); size_t off = 0;
+    for (size_t i = 0; i < cnt; i++) { int size = 0; size_t used = 0;
+        chk(crc_seal_ct_load(L.ctx, b.data() + off, b.size() - off, h.data() + i * ctw, 2, &size, &used), "encrypted is not valid for the level's encryption parameters");
+        if (size != 2) throw invalid_argument("expected size-2 ciphertexts");
+        off += used; }
+    if (off != b.size()) throw invalid_argument("LevelTensor::load: the file holds more than the tensor");
+    t.buf = make_shared<DeviceBuffer>(h.size() * 8);
+    chk(crc_memcpy_h2d(L.ctx, t.buf->ptr, h.data(), h.size() * 8, stream()), "crc_memcpy_h2d");
+    chk(crc_stream_sync(L.ctx, stream()), "crc_stream_sync");
+    return t;
+}
+LevelTensor modSwitch(const ciphertext3D &t, const shared_ptr<Level> &to, int out_form)
+{
+    const Level &L = levelOf(to, "modSwitch");
+    if (!t.buf || t.count() == 0) throw invalid_argument("modSwitch: empty tensor");
+    if (t.form != CRC_COEFF && t.form != CRC_NTT) throw invalid_argument("modSwitch: ciphertext forms only (CRC_COEFF / CRC_NTT)");
+    if (out_form != CRC_COEFF && out_form != CRC_NTT) throw invalid_argument("modSwitch: out_form must be CRC_COEFF or CRC_NTT");
+    LevelTensor out; out.B = t.B; out.zd = t.zd; out.xd = t.xd; out.yd = t.yd; out.form = out_form; out.level = to;
+    out.buf = make_shared<DeviceBuffer>(t.count() * crc_ct_words(L.ctx, 2) * 8);
+    ensure(g_scratch, crc_mod_switch_work_bytes(ctx(), L.ctx, t.count(), 2, t.form, out_form));
+    chk(crc_mod_switch_forms(ctx(), L.ctx, t.data(), t.form, t.count(), 2, out.data(), out_form, g_scratch->ptr, stream()), "crc_mod_switch_forms");
+    return out;
+}
+vector<floatCube> decryptImages(const LevelTensor &t)
+{
+    const Level &L = levelOf(t, "decryptImages");
+    const int n = N();
+    if (t.form != CRC_COEFF) throw invalid_argument("tensor is in NTT form");
+    vector<uint64_t> h = t.toHost(), pl(t.count() * n);
+    chk(crc_decrypt(L.ctx, L.secret_key.data(), h.data(), t.count(), 2, pl.data()), "crc_decrypt");
+    vector<floatCube> out(t.B, floatCube(t.zd, vector<vector<float>>(t.xd, vector<float>(t.yd))));
+    size_t i = 0;
+    for (int b = 0; b < t.B; b++) for (int z = 0; z < t.zd; z++) for (int x = 0; x < t.xd; x++) for (int y = 0; y < t.yd; y++, i++)
+        out[b][z][x][y] = (float)crc_decode(L.ctx, pl.data() + i * n);
+    return out;
+}
+vector<vector<int64_t>> decryptSlots(const LevelTensor &t, int S)
+{
+    const Level &L = levelOf(t, "decryptSlots");
+    if (t.form != CRC_COEFF && t.form != CRC_NTT) throw invalid_argument("decryptSlots: ciphertext forms only (CRC_COEFF / CRC_NTT)");
+    if (S < 1 || S > N()) throw invalid_argument("decryptSlots: 1 to n slots");
+    const size_t cnt = t.count();
+    DeviceBuffer d_pl(cnt * (size_t)N() * 8), d_v(cnt * (size_t)S * 8), d_work(crc_decrypt_dev_work_bytes(L.ctx, cnt, 2, t.form));
+    chk(crc_decrypt_dev(L.ctx, (const uint64_t *)L.d_secret_key->ptr, t.data(), cnt, 2, t.form, (uint64_t *)d_pl.ptr, d_work.ptr, stream()), "crc_decrypt_dev");
+    chk(crc_slots_decompose_dev(L.ctx, (const uint64_t *)d_pl.ptr, cnt, S, (int64_t *)d_v.ptr, 1, cnt, stream()), "crc_slots_decompose_dev");
+    vector<int64_t> h(cnt * (size_t)S);
+    chk(crc_memcpy_d2h(L.ctx, h.data(), d_v.ptr, h.size() * 8, stream()), "crc_memcpy_d2h");
+    chk(crc_stream_sync(L.ctx, stream()), "crc_stream_sync");
+    vector<vector<int64_t>> out(S);
+    for (int j = 0; j < S; j++) out[j].assign(h.begin() + (size_t)j * cnt, h.begin() + (size_t)(j + 1) * cnt);
+    return out;
+}
+static BudgetView budgetView(const LevelTensor &t, const char *who)
+{
+    const Level &L = levelOf(t, who);
+    return BudgetView{L.ctx, (const uint64_t *)L.d_secret_key->ptr, t.data(), t.count(), t.form};
+}
+vector<int> noiseBudgets(const LevelTensor &t) { return allBudgets(budgetView(t, "noiseBudgets"), "noiseBudgets"); }
+int minNoiseBudget(const LevelTensor &t, size_t *where) { return minAndFirstBudget(budgetView(t, "minNoiseBudget"), "minNoiseBudget", where, nullptr); }
 
 static int g_expected_batch = 0;                            // images per Network::forward the caller announced (0: unknown)
 void setExpectedBatch(int images_per_forward) { g_expected_batch = images_per_forward > 0 ? images_per_forward : 0; }

@@ -106,6 +106,45 @@ int noiseBudget(const ciphertext3D &t, size_t index = 0);
 std::vector<int> noiseBudgets(const ciphertext3D &t);
 // the smallest budget of the tensor and (optionally) the index of the first ciphertext that has it: two integers come back over PCIe, not the tensor
 int minNoiseBudget(const ciphertext3D &t, size_t *where = nullptr);
+// ---- levels: modulus switching (include/crcnn_hip.h, "Modulus switching") ------------------------------------------------------------------------------------
+// A Level is the parameters of setParameters() over the first `kept` coefficient moduli: its own context, and the rows [0, kept) of the secret and the public
+// key, which are valid there as they stand (copies taken by makeLevel: a later assignment to the global keys does not reach a level).  Evaluation and Galois
+// keys do NOT carry over; nothing here generates them, the layers run at the full modulus.  A level belongs to the parameters it was made under: after the
+// next setParameters() / delParameters() every call that is handed it, or a LevelTensor of it, throws std::invalid_argument.
+struct Level {
+    crc_ctx *ctx = nullptr;                                 // owned
+    int kept = 0;
+    uint64_t generation = 0;
+    std::vector<uint64_t> secret_key, public_key;           // [kept][n] and [2][kept][n], NTT form
+    std::shared_ptr<DeviceBuffer> d_secret_key;
+    Level() {}
+    ~Level();
+    Level(const Level &) = delete; Level &operator=(const Level &) = delete;
+};
+// valid after setParameters() / initFromKeys(); std::invalid_argument for `kept` outside 1 .. k - 1
+std::shared_ptr<Level> makeLevel(int kept);
+// a device tensor of size-2 ciphertexts of a level, [B][zd][xd][yd][2][kept][n] -- what a server sends back at a fraction of the bytes
+struct LevelTensor {
+    int B = 0, zd = 0, xd = 0, yd = 0, form = CRC_COEFF;
+    std::shared_ptr<Level> level;
+    std::shared_ptr<DeviceBuffer> buf;
+    size_t count() const { return (size_t)B * zd * xd * yd; }
+    uint64_t *data() const { return buf ? (uint64_t *)buf->ptr : nullptr; }
+    std::vector<uint64_t> toHost() const;
+    // the ciphertexts back to back in SEAL's Ciphertext::save format under the LEVEL's parameter hash (crc_seal_ct_save on the level's context), count() times
+    // crc_seal_ct_bytes(level->ctx, 2) bytes; coefficient form only.  load: std::invalid_argument for a file of other parameters (another level among them), a
+    // truncated one or one that holds more than [B][zd][xd][yd]
+    void save(const std::string &path) const;
+    static LevelTensor load(const std::shared_ptr<Level> &level, int B, int zd, int xd, int yd, const std::string &path);
+};
+// crc_mod_switch_forms on the launch stream, work space from the layers' scratch area: a CRC_COEFF or CRC_NTT tensor of the global context -> the level `to`, in
+// out_form (CRC_COEFF / CRC_NTT).  Asynchronous.  The plaintexts are unchanged; the budget is at least floor(-log2(2^-b + t (n + 1) / q_to)) - 2 bits
+LevelTensor modSwitch(const ciphertext3D &t, const std::shared_ptr<Level> &to, int out_form = CRC_COEFF);
+// the client side at a level, under the level's secret-key rows: as their ciphertext3D namesakes
+std::vector<floatCube> decryptImages(const LevelTensor &t);
+std::vector<std::vector<int64_t>> decryptSlots(const LevelTensor &t, int S);
+std::vector<int> noiseBudgets(const LevelTensor &t);
+int minNoiseBudget(const LevelTensor &t, size_t *where = nullptr);
 // decryptImage -> encryptImage for every image of a batch (the refresh Network::forward runs in front of layer_before_reenc, network.cpp:30-34), on the
 // device and on the launch stream: the tensor may be in coefficient or NTT form, comes back in `out_form` (CRC_COEFF / CRC_NTT) under fresh randomness, and
 // `values` (optional) receives the floats the client saw, [B][zd][xd][yd] -- asking for them makes the call wait for the stream

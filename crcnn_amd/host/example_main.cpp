@@ -36,6 +36,8 @@ int main(int argc, char **argv)
         if (fuse) net.fuse();
         if (argc > 8) net.layer_before_reenc = atoi(argv[8]);
         if (argc > 9) net.max_num_of_reencryptions = atoi(argv[9]);
+        // the response goes back at ONE prime where the logits' budget allows it: 1 / k of the bytes (LevelTensor::save is what a server would send)
+        const shared_ptr<Level> response_level = crc_ctx_k(context) > 1 ? makeLevel(1) : nullptr;
         const int reenc_at = net.max_num_of_reencryptions >= 0 ? net.getNumLayers() : net.layer_before_reenc;      // column position of T_REENC (-1: no refresh, no column)
         cout << "INDEX_IMG";
         for (int i = 0; i < net.getNumLayers(); i++) { if (i == reenc_at) cout << ",T_REENC"; cout << ",T_LAYER_" << i; }
@@ -54,7 +56,12 @@ int main(int argc, char **argv)
                 for (int l = 0; l < (int)net.last_layer_ms.size(); l++) { if (l == reenc_at) cout << net.last_reenc_ms << ","; cout << net.last_layer_ms[l] << ","; }
                 if (reenc_at == (int)net.last_layer_ms.size()) cout << net.last_reenc_ms << ",";
                 if (noiseBudget(encrypted_image) <= 0) ret_value = OUT_OF_BUDGET;
-                floatCube image = decryptImage(encrypted_image);
+                floatCube image;
+                if (response_level && ret_value == SUCCESS) {
+                    const LevelTensor response = modSwitch(encrypted_image, response_level);
+                    if (minNoiseBudget(response) > 0) image = decryptImages(response)[0];
+                }
+                if (image.empty()) image = decryptImage(encrypted_image);
                 predicted = 0;
                 for (int j = 1; j < (int)image[0].size(); j++) if (image[0][j][0] > image[0][predicted][0]) predicted = j;
                 if (ret_value == SUCCESS && predicted != expected) ret_value = MISPREDICTED;

@@ -889,6 +889,42 @@ int crc_seeded_ct_load(const crc_ctx *ctx, const void *buf, size_t bytes, uint64
                        uint64_t *stream_base);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Modulus switching: a ciphertext tensor continues over fewer coefficient moduli (SEAL 2.3.1 has no such operation; later SEALs call it
+ * mod_switch_to_next).  `from` has the moduli q_0 .. q_{k-1}, `to` the first k' < k of them (d = k - k' are dropped), the same n and t.
+ *
+ * Definition.  For every coefficient c in [0, q_from) of every polynomial of a ciphertext (CRT-composed from its residues), in integers:
+ *      for p in (q_{k-1}, q_{k-2}, ..., q_{k'}):   h = p >> 1;   c = (c + h) / p   (rounded down)
+ *      result = c mod q_to
+ * In residues: r_1 = ((c_{k-1} + h) mod p_1) - h is the centred remainder of the last row, every row i below it becomes (c_i - r_1) p_1^-1 mod q_i, r_2 is
+ * taken from row k-2 the same way, and so on; a kept row takes c'_i = (c_i - R) (p_1 .. p_d)^-1 mod q_i with R = r_1 + p_1 r_2 + p_1 p_2 r_3 + ...
+ *
+ * Noise (size-2 ciphertexts, ternary secret key): c' = c / P + delta with |delta| < (1 + 1/p) / 2 per coefficient, so the invariant noise grows by at most
+ * t (n + 1) / q_to: a ciphertext with a budget of b bits under `from` has at least floor(-log2(2^-b + t (n + 1) / q_to)) bits under `to` (less up to 2 bits for
+ * the two bit-count floors of the budget measurement).  The plaintext does not change.
+ *
+ * What carries over to `to`: the per-modulus tables are those of `from` (same primes, same minimal roots), so the rows [0, k') of an NTT-form secret key
+ * ([k][n]), of each public-key polynomial ([2][k][n]) and of an NTT-form plaintext row are valid there as they stand.  Evaluation keys and Galois keys do NOT
+ * carry over (they hold (q / q_i) factors): generate them on `to` with crc_gen_evk* / crc_gen_galois_keys* from the prefix secret-key rows.
+ *
+ *   crc_mod_switch_supported   1 if `to` is a proper prefix of `from` (1 <= k' < k, the same moduli in the same order, the same n and t), else 0
+ *   crc_mod_switch_forms       d_in [count][size][k][n] of `from` in in_form -> d_out [count][size][k'][n] of `to` in out_form; size 2 or 3; forms CRC_COEFF or
+ *                              CRC_NTT on either side.  Asynchronous on `stream`, on `from`'s device.  COEFF -> COEFF is one elementwise kernel; NTT -> NTT
+ *                              inverse-transforms only the d dropped rows and forward-transforms R mod q_i per kept row (d + k' transforms per polynomial, the
+ *                              kept rows never leave NTT form); COEFF -> NTT costs k' forward, NTT -> COEFF k inverse transforms.  Every form pair gives the
+ *                              bits of the definition on coefficient form with crc_ntt_inv in front / crc_ntt_fwd (on `to`) behind.
+ *                              d_work: crc_mod_switch_work_bytes(from, to, count, size, in_form, out_form).  n <= 16384 where a side is CRC_NTT
+ *                              (CRC_ERR_UNSUPPORTED above).
+ *   crc_mod_switch             the host twin: host memory, any contexts (device = -1 included), bit for bit the device call
+ * CRC_ERR_INVALID_ARGUMENT, and nothing written, where crc_mod_switch_supported is 0, for a null or (device) not 16-byte aligned pointer, another form or
+ * size, and a d_out or d_work that overlaps d_in (or each other); the work-bytes query gives 0 for whatever the call would refuse.  count = 0 is CRC_OK.
+ * ------------------------------------------------------------------------------------------------------------- */
+int    crc_mod_switch_supported(const crc_ctx *from, const crc_ctx *to);
+size_t crc_mod_switch_work_bytes(const crc_ctx *from, const crc_ctx *to, size_t count, int size, int in_form, int out_form);
+int    crc_mod_switch_forms(crc_ctx *from, const crc_ctx *to, const uint64_t *d_in, int in_form, size_t count, int size, uint64_t *d_out, int out_form,
+                            void *d_work, void *stream);
+int    crc_mod_switch(const crc_ctx *from, const crc_ctx *to, const uint64_t *h_in, int in_form, size_t count, int size, uint64_t *h_out, int out_form);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * multi-GPU (SURVEY 8e / 8b `crc_broadcast_weights`).  The reference has no analogue: its only parallelism is the
  * std::thread fan-out inside a layer (convolutionalLayer.cpp:177-191).  Here a batch of encrypted images shards over the
  * GPUs of a node with NO data-path collective; the ONE collective is the start-up broadcast of the encoded (NTT-form)
