@@ -235,6 +235,16 @@ def load():
     L.crc_seeded_ct_bytes.restype = SZ; L.crc_seeded_ct_bytes.argtypes = [VP, SZ]
     L.crc_seeded_ct_save.argtypes = [VP, PU, SZ, PB, u64, VP, SZ, ctypes.POINTER(SZ)]
     L.crc_seeded_ct_load.argtypes = [VP, VP, SZ, PU, SZ, ctypes.POINTER(SZ), PB, ctypes.POINTER(u64)]
+    L.crc_seeded_key_words.restype = SZ; L.crc_seeded_key_words.argtypes = [VP, CI]
+    L.crc_gen_keys_seeded.argtypes = [VP, u64, PU, CI, PU, CI, PU]
+    L.crc_gen_keys_seeded_key.argtypes = [VP, PB, PB, PU, CI, PU, CI, PU]
+    L.crc_seeded_keys_expand.argtypes = [VP, PU, PU, CI, CI, PB, CI, PU]
+    L.crc_gen_keys_seeded_dev.argtypes = [VP, u64, VP, CI, PU, CI, VP, VP]
+    L.crc_gen_keys_seeded_dev_key.argtypes = [VP, PB, PB, VP, CI, PU, CI, VP, VP]
+    L.crc_seeded_keys_expand_dev.argtypes = [VP, VP, PU, CI, CI, PB, CI, VP, VP]
+    L.crc_seeded_keys_bytes.restype = SZ; L.crc_seeded_keys_bytes.argtypes = [VP, CI, CI]
+    L.crc_seeded_keys_save.argtypes = [VP, PU, PU, CI, CI, PB, VP, SZ, ctypes.POINTER(SZ)]
+    L.crc_seeded_keys_load.argtypes = [VP, VP, SZ, PU, PU, CI, ctypes.POINTER(CI), ctypes.POINTER(CI), PB]
     L.crc_comm_unique_id.argtypes = [PB]
     L.crc_comm_create.argtypes = [VP, CI, CI, PB, ctypes.POINTER(VP)]
     L.crc_comm_create_all.argtypes = [ctypes.POINTER(VP), CI, ctypes.POINTER(VP)]
@@ -1251,6 +1261,67 @@ class Engine:
     def galois_conjugate_keys_dev(self, elts, d_gk, d_out, dbc=16):
         elts = self._elts(elts)
         _chk(self.L.crc_galois_conjugate_keys_dev(self.c, _pu(elts), elts.size, dbc, self.p(d_gk), self.p(d_out), self.stream), "crc_galois_conjugate_keys_dev")
+
+    # ---- seeded key-switching keys (crc_gen_keys_seeded* / crc_seeded_keys_expand*): a key set is (ids, dbc, PUBLIC seed, first rows [n_ids][P][k][n]); id 0 is
+    # the evaluation key, every other id a Galois element.  Expanded, a key is an ordinary blob
+    def seeded_key_words(self, dbc=16):
+        return self.L.crc_seeded_key_words(self.c, dbc)
+
+    def gen_keys_seeded(self, seed, sk, ids, dbc=16, key=None, public_seed=None):
+        """-> (first rows [n_ids][crc_seeded_key_words], public seed).  With `key` (PRIVATE) and `public_seed`: crc_gen_keys_seeded_key"""
+        ids = self._elts(ids)
+        first = np.zeros((ids.size, self.seeded_key_words(dbc)), dtype=np.uint64)
+        if key is None:
+            _chk(self.L.crc_gen_keys_seeded(self.c, seed, _pu(sk), dbc, _pu(ids), ids.size, _pu(first)), "crc_gen_keys_seeded")
+            return first, self.seeded_public_seed(seed)
+        _chk(self.L.crc_gen_keys_seeded_key(self.c, self._key(key), self._key(public_seed), _pu(sk), dbc, _pu(ids), ids.size, _pu(first)), "crc_gen_keys_seeded_key")
+        return first, bytes(public_seed)
+
+    def seeded_keys_expand(self, first, ids, public_seed, dbc=16, conjugate=False):
+        """the host twin of seeded_keys_expand_dev: first rows -> blobs [n_ids][crc_evk_words] (conjugate: the blobs of galois_conjugate_keys)"""
+        ids = self._elts(ids)
+        first = np.ascontiguousarray(first, dtype=np.uint64).reshape(ids.size, self.seeded_key_words(dbc))
+        out = np.zeros((ids.size, self.L.crc_evk_words(self.c, dbc)), dtype=np.uint64)
+        _chk(self.L.crc_seeded_keys_expand(self.c, _pu(first), _pu(ids), ids.size, dbc, self._key(public_seed), 1 if conjugate else 0, _pu(out)),
+             "crc_seeded_keys_expand")
+        return out
+
+    def gen_keys_seeded_dev(self, seed, d_sk, ids, d_first, dbc=16, key=None, public_seed=None):
+        """secret key [k][n] on the device -> first rows on the device, the bits of gen_keys_seeded; asynchronous, no work buffer -> public seed"""
+        ids = self._elts(ids)
+        if key is None:
+            _chk(self.L.crc_gen_keys_seeded_dev(self.c, seed, self.p(d_sk), dbc, _pu(ids), ids.size, self.p(d_first), self.stream), "crc_gen_keys_seeded_dev")
+            return self.seeded_public_seed(seed)
+        _chk(self.L.crc_gen_keys_seeded_dev_key(self.c, self._key(key), self._key(public_seed), self.p(d_sk), dbc, _pu(ids), ids.size, self.p(d_first),
+                                                self.stream), "crc_gen_keys_seeded_dev_key")
+        return bytes(public_seed)
+
+    def seeded_keys_expand_dev(self, d_first, ids, public_seed, d_out, dbc=16, conjugate=False):
+        ids = self._elts(ids)
+        _chk(self.L.crc_seeded_keys_expand_dev(self.c, self.p(d_first), _pu(ids), ids.size, dbc, self._key(public_seed), 1 if conjugate else 0, self.p(d_out),
+                                               self.stream), "crc_seeded_keys_expand_dev")
+
+    def seeded_keys_bytes(self, n_ids, dbc=16):
+        return self.L.crc_seeded_keys_bytes(self.c, dbc, n_ids)
+
+    def seeded_keys_save(self, first, ids, public_seed, dbc=16):
+        ids = self._elts(ids)
+        first = np.ascontiguousarray(first, dtype=np.uint64).reshape(ids.size, self.seeded_key_words(dbc))
+        buf = np.zeros(self.seeded_keys_bytes(ids.size, dbc), dtype=np.uint8); w = SZ(0)
+        _chk(self.L.crc_seeded_keys_save(self.c, _pu(first), _pu(ids), ids.size, dbc, self._key(public_seed), buf.ctypes.data, buf.nbytes, ctypes.byref(w)),
+             "crc_seeded_keys_save")
+        return buf[:w.value].tobytes()
+
+    def seeded_keys_load(self, blob):
+        """-> (first rows [n_ids][crc_seeded_key_words], ids, dbc, public seed)"""
+        raw = np.frombuffer(bytes(blob), dtype=np.uint8)
+        cnt, dbc = CI(0), CI(0)
+        _chk(self.L.crc_seeded_keys_load(self.c, raw.ctypes.data, raw.nbytes, None, None, 0, ctypes.byref(cnt), ctypes.byref(dbc), None), "crc_seeded_keys_load")
+        first = np.zeros((cnt.value, self.seeded_key_words(dbc.value)), dtype=np.uint64); ids = np.zeros(cnt.value, dtype=np.uint64)
+        sd = (ctypes.c_uint8 * 32)()
+        _chk(self.L.crc_seeded_keys_load(self.c, raw.ctypes.data, raw.nbytes, _pu(first), _pu(ids), cnt.value, ctypes.byref(cnt), ctypes.byref(dbc), sd),
+             "crc_seeded_keys_load")
+        return first, ids, dbc.value, bytes(sd)
 
     def galois_permute_ntt_dev(self, d_in, rows, g, d_out):
         """NTT-form rows [rows][k][n] -> NTT(sigma_g(INTT(rows)))"""

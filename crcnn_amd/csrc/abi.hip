@@ -1477,6 +1477,51 @@ extern "C" int crc_galois_conjugate_keys_dev(crc_ctx *c, const uint64_t *elts, i
     }
     return CRC_OK;
 }
+// ---- seeded key-switching keys: first rows made on the device, and their expansion into ordinary blobs (kernels_seeded_keys.hip) ----
+// ids: 0 (the evaluation key) or valid Galois elements; conjugate: 0 and 1 have no conjugated key
+static bool seeded_key_ids_ok(const crc_ctx *c, const uint64_t *ids, int n_ids, bool conjugate)
+{
+    for (int e = 0; e < n_ids; e++) if ((ids[e] && !crc_galois_elt_valid(c, ids[e])) || (conjugate && ids[e] <= 1)) return false;
+    return true;
+}
+static int gen_keys_seeded_dev_impl(crc_ctx *c, const ChaChaKey &key, const ChaChaKey &seed, const u64 *d_sk, int dbc, const uint64_t *ids, int n_ids, u64 *d_first,
+                                    hipStream_t st)
+{
+    if (!dbc_ok(dbc) || n_ids < 0) return CRC_ERR_INVALID_ARGUMENT;
+    if (n_ids == 0) return CRC_OK;
+    if (!ids || !d_first || !aligned16(d_sk) || !aligned16(d_first) || !k_seeded_keys_grid_ok(c, dbc, n_ids) || !seeded_key_ids_ok(c, ids, n_ids, false))
+        return CRC_ERR_INVALID_ARGUMENT;
+    // the rows are formed in place while every lane reads the secret key: the two must not overlap
+    if (ranges_overlap(d_sk, 8 * (size_t)c->k * c->n, d_first, 4 * crc_evk_words(c, dbc) * n_ids)) return CRC_ERR_INVALID_ARGUMENT;
+    return k_gen_keys_seeded(c, d_sk, dbc, ids, n_ids, key, seed, d_first, st);
+}
+extern "C" int crc_gen_keys_seeded_dev_key(crc_ctx *c, const uint8_t *key, const uint8_t *seed, const uint64_t *d_sk, int dbc, const uint64_t *ids, int n_ids,
+                                           uint64_t *d_first, void *stream)
+{
+    if (!key || !seed || !d_sk || !std::memcmp(key, seed, CRC_KEY_BYTES)) return CRC_ERR_INVALID_ARGUMENT;
+    CHECK_CTX(c);
+    return gen_keys_seeded_dev_impl(c, chacha_load_key(key), chacha_load_key(seed), d_sk, dbc, ids, n_ids, d_first, S(stream));
+}
+extern "C" int crc_gen_keys_seeded_dev(crc_ctx *c, uint64_t seed, const uint64_t *d_sk, int dbc, const uint64_t *ids, int n_ids, uint64_t *d_first, void *stream)
+{
+    if (!d_sk) return CRC_ERR_INVALID_ARGUMENT;
+    CHECK_CTX(c);
+    // what crc_gen_keys_seeded derives: private key = the expansion of seed, public seed = crc_seeded_public_seed(seed)
+    return gen_keys_seeded_dev_impl(c, chacha_seed_key(seed), chacha_seed_key(~seed), d_sk, dbc, ids, n_ids, d_first, S(stream));
+}
+extern "C" int crc_seeded_keys_expand_dev(crc_ctx *c, const uint64_t *d_first, const uint64_t *ids, int n_ids, int dbc, const uint8_t *seed, int conjugate,
+                                          uint64_t *d_out, void *stream)
+{
+    if (!seed || (conjugate != 0 && conjugate != 1)) return CRC_ERR_INVALID_ARGUMENT;
+    CHECK_CTX(c);
+    if (!dbc_ok(dbc) || n_ids < 0) return CRC_ERR_INVALID_ARGUMENT;
+    if (n_ids == 0) return CRC_OK;
+    if (!d_first || !ids || !d_out || !aligned16(d_first) || !aligned16(d_out) || !k_seeded_keys_grid_ok(c, dbc, n_ids) ||
+        !seeded_key_ids_ok(c, ids, n_ids, conjugate != 0)) return CRC_ERR_INVALID_ARGUMENT;
+    const size_t kw = crc_evk_words(c, dbc);
+    if (ranges_overlap(d_first, 4 * kw * n_ids, d_out, 8 * kw * n_ids)) return CRC_ERR_INVALID_ARGUMENT;
+    return k_seeded_keys_expand(c, d_first, ids, n_ids, dbc, chacha_load_key(seed), conjugate != 0, d_out, S(stream));
+}
 extern "C" size_t crc_rotate_hoisted_work_bytes(const crc_ctx *c, size_t count, int R, int dbc) { return hoist_bytes(c, count, R, 2, dbc); }
 extern "C" int crc_rotate_hoisted_forms(crc_ctx *c, const uint64_t *d_x, int in_form, size_t count, const uint64_t *gs, int R, const uint64_t *d_cgk,
                                         const uint64_t *elts, int n_elts, int dbc, uint64_t *d_y, int out_form, void *d_work, void *stream)

@@ -72,7 +72,7 @@ inline ChaChaKey chacha_load_key(const uint8_t *key)
 
 // stream domains (nonce word 2 carries the domain in its top byte)
 enum { CHACHA_DOM_KEYGEN = 1, CHACHA_DOM_EVK = 2, CHACHA_DOM_ENC_HOST = 3, CHACHA_DOM_ENC_DEV = 4, CHACHA_DOM_ENC_SYM = 5, CHACHA_DOM_SEEDED_A = 6,
-       CHACHA_DOM_SEEDED_E = 7, CHACHA_DOM_GALOIS = 8 };
+       CHACHA_DOM_SEEDED_E = 7, CHACHA_DOM_GALOIS = 8, CHACHA_DOM_KSK_A = 9, CHACHA_DOM_KSK_E = 10, CHACHA_DOM_KSK_SEED = 11 };
 
 // Streams of the secret-key encryptor (crc_encrypt_sym* on the host, enc_sym_sample_kernel on the device: the same bits).  One stream per (ciphertext,
 // coefficient pair), nonce = (stream id low, stream id high, CHACHA_DOM_ENC_SYM << 24 | even coefficient index s); its 32-bit words w[0], w[1], ... run
@@ -97,3 +97,21 @@ enum { CHACHA_DOM_KEYGEN = 1, CHACHA_DOM_EVK = 2, CHACHA_DOM_ENC_HOST = 3, CHACH
 // The noise has a domain of its own, not CHACHA_DOM_ENC_SYM: one private key serving crc_encrypt_sym_key and the seeded encryptor at the same stream id would
 // give equal e under different, known A -- for equal plaintexts c0 - c0' = -(A - A') s, the secret key.
 #define CHACHA_SEEDED_BLOCKS(k) (((k) + 1) >> 1)
+
+// Streams of a SEEDED key-switching key (crc_gen_keys_seeded* / crc_seeded_keys_expand on the host, seeded_keys_device.h on the device).  A key-switching key is
+// a list of pairs (first, second) with second = A uniform, so, as for a seeded ciphertext, A is a function of a PUBLIC seed and only the first rows travel.
+// A key id is 0 for the evaluation key (target w = s^2) or a valid Galois element g (target w = sigma_g(s)); no valid element is even, so 0 is free.  The pairs of
+// a blob are numbered in the blob's own order, p = Sum_{l' < l} L_l' + d (modulus l, digit d), P = Sum_l L_l of them; the seeded form of one key is its P first
+// polynomials [P][k][n], NTT form: half the blob.  One stream per (id, pair, even slot s), nonce = (id, p | dbc << 16 | k << 24, domain << 24 | s):
+//   mask stream, PUBLIC seed, CHACHA_DOM_KSK_A: blocks and words exactly as CHACHA_DOM_SEEDED_A -- block j serves modulus 2j with its words 0..7 and modulus
+//                         2j + 1 with its words 8..15, the 128-bit z of words 4c .. 4c + 3 gives second[i][s + c] = z mod q_i
+//   noise stream, PRIVATE key, CHACHA_DOM_KSK_E: one block (counter 0), words 0..4 as block 0 of CHACHA_DOM_ENC_SYM (two magnitude words against the 19
+//                         thresholds, sign bits in w[4]); e is a coefficient-form polynomial, the same integer under every modulus
+// and, in NTT form and pointwise,  first[j] = -(A[j] s[j] + NTT_j(e)) + [j == l] factor_{l,d} w[j],  factor_{l,d} = (q / q_l) 2^(dbc d) mod q_l.
+// Two domains and two keys for the reason given above for SEEDED_A / SEEDED_E.  dbc and k are in the nonce because the streams are counter-based: without them one
+// private key serving the same id at two digit widths, or on a context and on a prefix of its moduli, would give equal A and equal e around DIFFERENT known
+// factors, and first - first' = (factor - factor') sigma_g(s) would reveal the secret key.
+// Nothing in these nonces is per call, so whoever holds a private key must pair it with ONE public seed for as long as it lives: the host classes take the seed
+// from the private (master) key itself -- bytes 0..31 of block 0 of the stream nonce = (0, 0, CHACHA_DOM_KSK_SEED << 24), a PRF output that can be published --
+// so that an element generated twice is the same key twice.
+#define CHACHA_KSK_NONCE1(p, dbc, k) ((uint32_t)(p) | ((uint32_t)(dbc) << 16) | ((uint32_t)(k) << 24))

@@ -533,3 +533,126 @@ extern "C" int crc_noise_budget(const crc_ctx *c, const uint64_t *sk, const uint
     const int b = c->total_bits - nb - 1;
     return b > 0 ? b : 0;
 }
+
+// ---- seeded key-switching keys: the first rows and a public seed (chacha.h: CHACHA_DOM_KSK_A / CHACHA_DOM_KSK_E) ----
+// A key id is 0 (the evaluation key, target s^2) or a valid Galois element g (target sigma_g(s)).  The host twin of seeded_keys_device.h, bit for bit.
+namespace {
+struct KskPair { int l; u64 factor; };                     // pair p of a blob: its modulus l and (q/q_l) 2^(dbc d) mod q_l, as switch_key_impl walks them
+std::vector<KskPair> ksk_pairs(const crc_ctx *c, int dbc)
+{
+    int L[CRC_MAXK]; u64 qhat[CRC_MAXK];
+    evk_gadget(c, dbc, L, qhat);
+    std::vector<KskPair> v;
+    for (int l = 0; l < c->k; l++) {
+        u64 factor = qhat[l];
+        for (int d = 0; d < L[l]; d++) { v.push_back({l, factor}); factor = h_mulmod(factor, (1ULL << dbc) % c->q[l], c->q[l]); }
+    }
+    return v;
+}
+bool ksk_id_ok(const crc_ctx *c, u64 id) { return id == 0 || crc_galois_elt_valid(c, id); }
+// A of one pair, NTT form: a [k][n]
+void ksk_mask(const crc_ctx *c, const ChaChaKey &seed, u64 id, u32 n1, u64 *a)
+{
+    const int n = c->n, k = c->k;
+    for (int s = 0; s < n; s += 2) {
+        const u32 n2 = ((u32)CHACHA_DOM_KSK_A << 24) | (u32)s;
+        u32 b[16];
+        for (int i = 0; i < k; i++) {
+            if (!(i & 1)) chacha20_block(seed, (u32)(i >> 1), (u32)id, n1, n2, b);
+            const u32 *w = b + 8 * (i & 1);
+            for (int x = 0; x < 2; x++) {
+                const u128 z = (u128)w[4 * x] | ((u128)w[4 * x + 1] << 32) | ((u128)w[4 * x + 2] << 64) | ((u128)w[4 * x + 3] << 96);
+                a[(size_t)i * n + s + x] = (u64)(z % c->q[i]);
+            }
+        }
+    }
+}
+int gen_keys_seeded_impl(const crc_ctx *c, const ChaChaKey &key, const ChaChaKey &seed, const uint64_t *sk, int dbc, const uint64_t *ids, int n_ids, uint64_t *first)
+{
+    if (!dbc_ok(dbc) || n_ids < 0) return CRC_ERR_INVALID_ARGUMENT;
+    for (int e = 0; e < n_ids; e++) if (!ksk_id_ok(c, ids[e])) return CRC_ERR_INVALID_ARGUMENT;
+    const int n = c->n, k = c->k;
+    const std::vector<KskPair> pairs = ksk_pairs(c, dbc);
+    const size_t P = pairs.size();
+    u64 T[19]; k_encrypt_cdt(T);
+    crc_host::parallel_for((size_t)n_ids, 1, [&](size_t e0, size_t e1) {
+    std::vector<u64> a((size_t)k * n), w((size_t)k * n);
+    std::vector<uint32_t> tab(n);
+    for (size_t e = e0; e < e1; e++) {
+        const u64 id = ids[e];
+        if (id) crc_galois_ntt_table(c, id, tab.data());
+        for (int j = 0; j < k; j++) for (int s = 0; s < n; s++) {
+            const size_t o = (size_t)j * n + s;
+            w[o] = id ? sk[(size_t)j * n + tab[s]] : h_mulmod(sk[o], sk[o], c->q[j]);
+        }
+        for (size_t p = 0; p < P; p++) {
+            u64 *o = first + (e * P + p) * (size_t)k * n;
+            const u32 n1 = CHACHA_KSK_NONCE1(p, dbc, k);
+            ksk_mask(c, seed, id, n1, a.data());
+            for (int s = 0; s < n; s += 2) {
+                u32 b[16];
+                chacha20_block(key, 0, (u32)id, n1, ((u32)CHACHA_DOM_KSK_E << 24) | (u32)s, b);
+                for (int x = 0; x < 2; x++) {
+                    const u64 m = (u64)b[2 * x] | ((u64)b[2 * x + 1] << 32);
+                    int mag = 0; for (int j = 0; j < 19; j++) mag += m >= T[j] ? 1 : 0;
+                    const int ev = (b[4] >> x) & 1u ? -mag : mag;
+                    for (int i = 0; i < k; i++) o[(size_t)i * n + s + x] = ev >= 0 ? (u64)ev : c->q[i] - (u64)(-ev);
+                }
+            }
+            for (int j = 0; j < k; j++) {
+                const u64 q = c->q[j];
+                h_ntt_fwd(c->tabs[j], o + (size_t)j * n, n);
+                for (int s = 0; s < n; s++) {
+                    const size_t x = (size_t)j * n + s;
+                    u64 v = negmod(addmod(h_mulmod(a[x], sk[x], q), o[x], q), q);
+                    if (j == pairs[p].l) v = addmod(v, h_mulmod(w[x], pairs[p].factor, q), q);
+                    o[x] = v;
+                }
+            }
+        }
+    }
+    });
+    return CRC_OK;
+}
+}  // namespace
+
+extern "C" size_t crc_seeded_key_words(const crc_ctx *c, int dbc) { return crc_evk_words(c, dbc) / 2; }
+extern "C" int crc_gen_keys_seeded_key(const crc_ctx *c, const uint8_t *key, const uint8_t *seed, const uint64_t *sk, int dbc, const uint64_t *ids, int n_ids,
+                                       uint64_t *first)
+{
+    if (!c || !key || !seed || !sk || (n_ids > 0 && (!ids || !first)) || !std::memcmp(key, seed, CRC_KEY_BYTES)) return CRC_ERR_INVALID_ARGUMENT;
+    return gen_keys_seeded_impl(c, load_key(key), load_key(seed), sk, dbc, ids, n_ids, first);
+}
+extern "C" int crc_gen_keys_seeded(const crc_ctx *c, uint64_t seed, const uint64_t *sk, int dbc, const uint64_t *ids, int n_ids, uint64_t *first)
+{
+    if (!c || !sk || (n_ids > 0 && (!ids || !first))) return CRC_ERR_INVALID_ARGUMENT;
+    return gen_keys_seeded_impl(c, seed_key(seed), seed_key(~seed), sk, dbc, ids, n_ids, first);
+}
+// first [n_ids][P][k][n] -> blobs [n_ids][crc_evk_words]: pair p of a blob is (first row p, A(seed, id, p)).  conjugate: K' = crc_galois_conjugate_keys of that
+extern "C" int crc_seeded_keys_expand(const crc_ctx *c, const uint64_t *first, const uint64_t *ids, int n_ids, int dbc, const uint8_t *seed, int conjugate,
+                                      uint64_t *out)
+{
+    if (!c || !seed || !dbc_ok(dbc) || n_ids < 0 || (conjugate != 0 && conjugate != 1) || (n_ids > 0 && (!first || !ids || !out || first == out)))
+        return CRC_ERR_INVALID_ARGUMENT;
+    for (int e = 0; e < n_ids; e++) if (!ksk_id_ok(c, ids[e]) || (conjugate && ids[e] <= 1)) return CRC_ERR_INVALID_ARGUMENT;
+    const size_t n = (size_t)c->n, kn = (size_t)c->k * n, words = crc_evk_words(c, dbc), P = words / (2 * kn);
+    const ChaChaKey sd = load_key(seed);
+    crc_host::parallel_for((size_t)n_ids, 1, [&](size_t e0, size_t e1) {
+    std::vector<u64> blob(conjugate ? words : 0);
+    std::vector<uint32_t> tab(conjugate ? n : 0);
+    for (size_t e = e0; e < e1; e++) {
+        u64 *dst = conjugate ? blob.data() : out + e * words;
+        for (size_t p = 0; p < P; p++) {
+            std::memcpy(dst + p * 2 * kn, first + (e * P + p) * kn, 8 * kn);
+            ksk_mask(c, sd, ids[e], CHACHA_KSK_NONCE1(p, dbc, c->k), dst + p * 2 * kn + kn);
+        }
+        if (!conjugate) continue;
+        crc_galois_ntt_table(c, galois_inverse(c, ids[e]), tab.data());
+        for (size_t r = 0; r < words / n; r++) {
+            const u64 *src = blob.data() + r * n; u64 *o = out + e * words + r * n;
+            for (size_t i = 0; i < n; i++) o[i] = src[tab[i]];
+        }
+    }
+    });
+    return CRC_OK;
+}

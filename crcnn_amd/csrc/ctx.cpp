@@ -56,6 +56,16 @@ ModParams make_mod(u64 q, bool no_fold)
 
 // (0 for a dbc outside 1..63: the loop would never end at dbc <= 0, and a shift by 64 or more is undefined -- x86 masks it to 0)
 int evk_digits(u64 q, int dbc) { if (dbc < 1 || dbc > 63) return 0; int L = 0; while (q) { L++; q >>= dbc; } return L; }
+int evk_gadget(const crc_ctx *c, int dbc, int L[CRC_MAXK], u64 qhat[CRC_MAXK])
+{
+    int P = 0;
+    for (int l = 0; l < c->k; l++) {
+        u64 f = 1;
+        for (int j = 0; j < c->k; j++) if (j != l) f = h_mulmod(f, c->q[j] % c->q[l], c->q[l]);
+        qhat[l] = f; L[l] = evk_digits(c->q[l], dbc); P += L[l];
+    }
+    return P;
+}
 
 static bool is_prime(u64 n)
 {

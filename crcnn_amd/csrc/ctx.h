@@ -203,5 +203,8 @@ void h_ntt_fwd(const HostNtt &T, u64 *a, int n);      // canonical in/out
 void h_ntt_inv(const HostNtt &T, u64 *a, int n);
 ModParams make_mod(u64 q, bool no_fold = false);
 int  evk_digits(u64 q, int dbc);
+// the gadget of a key-switching key at digit width dbc: L[l] = evk_digits(q_l, dbc) and qhat[l] = (q / q_l) mod q_l for l < k; returns P = Sum L[l], the pairs of a
+// blob (pair p = Sum_{l' < l} L[l'] + d has the factor qhat[l] 2^(dbc d) mod q_l).  One definition for the host twin and the device launchers of the seeded keys
+int  evk_gadget(const crc_ctx *c, int dbc, int L[CRC_MAXK], u64 qhat[CRC_MAXK]);
 // the decomposition bit counts SEAL accepts (keygenerator.cpp: 1..60); every entry point that takes a dbc refuses the others before it sizes anything
 static inline bool dbc_ok(int dbc) { return dbc >= 1 && dbc <= 60; }

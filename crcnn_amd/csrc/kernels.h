@@ -137,6 +137,12 @@ int k_slots_decompose_host(crc_ctx *c, const u64 *plain, size_t count, int slots
 int k_slots_rescale(crc_ctx *c, const u64 *d_in, size_t count, u64 divisor, u64 *d_out, hipStream_t st);
 int k_slots_rescale_host(crc_ctx *c, const u64 *plain_in, size_t count, u64 divisor, u64 *plain_out);
 
+// kernels_seeded_keys.hip: seeded key-switching keys (chacha.h CHACHA_DOM_KSK_*; ids is a HOST array of key ids: 0 = evaluation key, else a Galois element).
+// first / rows [n_ids][P][k][n] NTT form, formed in place without work space; out [n_ids][crc_evk_words]; the host twins are crc_gen_keys_seeded_key and
+// crc_seeded_keys_expand (client.cpp)
+bool k_seeded_keys_grid_ok(const crc_ctx *c, int dbc, int n_ids);
+int k_gen_keys_seeded(crc_ctx *c, const u64 *sk, int dbc, const u64 *ids, int n_ids, const ChaChaKey &key, const ChaChaKey &seed, u64 *first, hipStream_t st);
+int k_seeded_keys_expand(crc_ctx *c, const u64 *rows, const u64 *ids, int n_ids, int dbc, const ChaChaKey &seed, bool conjugate, u64 *out, hipStream_t st);
 // kernels_modswitch.hip: modulus switching from `from` to a context over a proper prefix of its moduli -- tensors of `polys` polynomials [polys][k][n] -> [polys][k'][n],
 // either side CRC_COEFF or CRC_NTT (work: k_mod_switch_work_bytes); *_host: the host twin
 bool   k_mod_switch_supported(const crc_ctx *from, const crc_ctx *to);

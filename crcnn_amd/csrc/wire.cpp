@@ -223,3 +223,56 @@ extern "C" int crc_seeded_ct_load(const crc_ctx *c, const void *buf, size_t byte
     r.get(h_c0, (size_t)cnt * row);
     return CRC_OK;
 }
+
+// Seeded key-switching keys (crc_gen_keys_seeded*): the same kind of container.  Little-endian:
+//   offset  0  8 bytes   magic "CRCSKEY\0"
+//           8  uint32    version = 1
+//          12  uint32    dbc
+//          16  32 bytes  crc_params_hash
+//          48  uint64    n_ids
+//          56  32 bytes  the PUBLIC seed
+//          88  n_ids uint64                the key ids (0: the evaluation key, else a Galois element)
+//              n_ids * P * k * n uint64    the first rows [n_ids][P][k][n], NTT form, P = crc_seeded_key_words / (k n)
+namespace {
+const char kSeededKeyMagic[8] = {'C', 'R', 'C', 'S', 'K', 'E', 'Y', 0};
+const size_t kSeededKeyHeader = 88;
+}
+extern "C" size_t crc_seeded_keys_bytes(const crc_ctx *c, int dbc, int n_ids)
+{
+    if (!c || !dbc_ok(dbc) || n_ids < 0) return 0;
+    return kSeededKeyHeader + 8 * (size_t)n_ids + 8 * (size_t)n_ids * crc_seeded_key_words(c, dbc);
+}
+extern "C" int crc_seeded_keys_save(const crc_ctx *c, const uint64_t *h_first, const uint64_t *ids, int n_ids, int dbc, const uint8_t *h_seed, void *buf, size_t cap,
+                                    size_t *written)
+{
+    if (!c || !dbc_ok(dbc) || n_ids < 0 || (n_ids && (!h_first || !ids)) || !h_seed || !buf) return CRC_ERR_INVALID_ARGUMENT;
+    for (int e = 0; e < n_ids; e++) if (ids[e] && !crc_galois_elt_valid(c, ids[e])) return CRC_ERR_INVALID_ARGUMENT;
+    const size_t need = crc_seeded_keys_bytes(c, dbc, n_ids);
+    if (written) *written = need;
+    if (cap < need) return CRC_ERR_INVALID_ARGUMENT;
+    uint8_t hash[32]; crc_params_hash(c, reinterpret_cast<uint64_t *>(hash));
+    Writer w{(uint8_t *)buf, cap};
+    const u64 cnt = (u64)n_ids; const uint32_t version = 1, d = (uint32_t)dbc;
+    w.put(kSeededKeyMagic, 8); w.put(&version, 4); w.put(&d, 4); w.put(hash, 32); w.put(&cnt, 8); w.put(h_seed, 32);
+    w.put(ids, 8 * (size_t)n_ids); w.put(h_first, need - kSeededKeyHeader - 8 * (size_t)n_ids);
+    return w.ok ? CRC_OK : CRC_ERR_INVALID_ARGUMENT;
+}
+extern "C" int crc_seeded_keys_load(const crc_ctx *c, const void *buf, size_t bytes, uint64_t *h_first, uint64_t *ids, int max_ids, int *n_ids, int *dbc,
+                                    uint8_t *h_seed)
+{
+    if (!c || !buf || !n_ids || !dbc) return CRC_ERR_INVALID_ARGUMENT;
+    uint8_t hash[32], h[32], seed[32]; char magic[8]; uint32_t version = 0, d = 0; u64 cnt = 0;
+    crc_params_hash(c, reinterpret_cast<uint64_t *>(hash));
+    Reader r{(const uint8_t *)buf, bytes};
+    r.get(magic, 8); r.get(&version, 4); r.get(&d, 4); r.get(h, 32); r.get(&cnt, 8); r.get(seed, 32);
+    if (!r.ok || std::memcmp(magic, kSeededKeyMagic, 8) || version != 1 || !dbc_ok((int)d) || std::memcmp(h, hash, 32)) return CRC_ERR_INVALID_ARGUMENT;
+    const size_t per = 8 + 8 * crc_seeded_key_words(c, (int)d);
+    if (cnt > 0x7fffffffULL || cnt > (bytes - kSeededKeyHeader) / per || bytes != kSeededKeyHeader + (size_t)cnt * per) return CRC_ERR_INVALID_ARGUMENT;
+    const u64 *idp = reinterpret_cast<const u64 *>((const uint8_t *)buf + kSeededKeyHeader);
+    for (u64 e = 0; e < cnt; e++) { u64 id; std::memcpy(&id, idp + e, 8); if (id && !crc_galois_elt_valid(c, id)) return CRC_ERR_INVALID_ARGUMENT; }
+    if (!h_first) { *n_ids = (int)cnt; *dbc = (int)d; return CRC_OK; }                // size query: nothing else is written
+    if (cnt > (u64)(max_ids < 0 ? 0 : max_ids) || !ids || !h_seed) return CRC_ERR_INVALID_ARGUMENT;
+    *n_ids = (int)cnt; *dbc = (int)d; std::memcpy(h_seed, seed, 32);
+    r.get(ids, 8 * (size_t)cnt); r.get(h_first, (size_t)cnt * (per - 8));
+    return CRC_OK;
+}

@@ -667,6 +667,97 @@ void generateGaloisKeys(int dbc)
     chk(crc_galois_default_elts(ctx(), elts.data(), (int)elts.size()), "crc_galois_default_elts");
     generateGaloisKeys(dbc, elts);
 }
+// ---- seeded Galois keys: the client makes the first rows, the server expands them on the device ----
+SeededKeys generateGaloisKeysSeeded(int dbc, vector<uint64_t> elts, bool on_device)
+{
+    if (secret_key.empty()) throw logic_error("cannot generate galois keys for unspecified secret key");
+    if (dbc < 1 || dbc > 60) throw invalid_argument("decomposition_bit_count is not in the valid range");
+    for (uint64_t g : elts) if (!crc_galois_elt_valid(ctx(), g)) throw invalid_argument("galois element is not valid");
+    SeededKeys out;
+    out.dbc = dbc; out.rows.resize(elts.size() * crc_seeded_key_words(ctx(), dbc));
+    const int ne = (int)elts.size();
+    // the streams carry the element, dbc and k in their nonce (chacha.h) and nothing per call: the PUBLIC seed must be the same whenever the master key serves an
+    // element again (a rotation set, then a layer's elements that share 3), or two sets would hold equal e around different A and first - first' = -(A - A') s
+    // is the secret key.  So the seed is a function of the master key -- the first half of its keystream block under CHACHA_DOM_KSK_SEED, a PRF output that says
+    // nothing about the key -- and a repeated element is the same key byte for byte, as it is under generateGaloisKeys.  (Deterministic mode: the seed's own.)
+    if (g_det) chk(crc_seeded_public_seed(g_det_seed + 2, out.seed), "crc_seeded_public_seed");
+    else {
+        const uint8_t nonce[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 11 /* CHACHA_DOM_KSK_SEED << 24, little-endian */};
+        uint8_t block[64];
+        chk(crc_chacha20_block(g_master_key, 0, nonce, block), "crc_chacha20_block");
+        memcpy(out.seed, block, 32);
+    }
+    if (on_device) {
+        DeviceBuffer d_first(out.rows.size() * 8 + 16);
+        const uint64_t *d_sk = deviceKey(g_d_sk, g_d_sk_fp, secret_key, "secret key");
+        if (g_det) chk(crc_gen_keys_seeded_dev(ctx(), g_det_seed + 2, d_sk, dbc, elts.data(), ne, (uint64_t *)d_first.ptr, stream()), "crc_gen_keys_seeded_dev");
+        else chk(crc_gen_keys_seeded_dev_key(ctx(), g_master_key, out.seed, d_sk, dbc, elts.data(), ne, (uint64_t *)d_first.ptr, stream()), "crc_gen_keys_seeded_dev_key");
+        if (!out.rows.empty()) chk(crc_memcpy_d2h(ctx(), out.rows.data(), d_first.ptr, out.rows.size() * 8, stream()), "crc_memcpy_d2h");
+        chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+    } else if (g_det) chk(crc_gen_keys_seeded(ctx(), g_det_seed + 2, secret_key.data(), dbc, elts.data(), ne, out.rows.data()), "crc_gen_keys_seeded");
+    else chk(crc_gen_keys_seeded_key(ctx(), g_master_key, out.seed, secret_key.data(), dbc, elts.data(), ne, out.rows.data()), "crc_gen_keys_seeded_key");
+    out.ids = std::move(elts);
+    return out;
+}
+void installGaloisKeys(const SeededKeys &keys)
+{
+    if (keys.dbc < 1 || keys.dbc > 60) throw invalid_argument("decomposition_bit_count is not in the valid range");
+    for (uint64_t g : keys.ids) if (!crc_galois_elt_valid(ctx(), g)) throw invalid_argument("galois element is not valid");
+    const size_t ne = keys.ids.size(), rw = crc_seeded_key_words(ctx(), keys.dbc), kw = crc_evk_words(ctx(), keys.dbc);
+    if (keys.rows.size() != ne * rw) throw invalid_argument("installGaloisKeys: rows do not match the elements");
+    DeviceBuffer d_rows(ne * rw * 8 + 16);
+    if (ne) chk(crc_memcpy_h2d(ctx(), d_rows.ptr, keys.rows.data(), ne * rw * 8, stream()), "crc_memcpy_h2d");
+    auto plain = make_shared<DeviceBuffer>(ne * kw * 8 + 8), conj = make_shared<DeviceBuffer>(ne * kw * 8 + 8);
+    chk(crc_seeded_keys_expand_dev(ctx(), (const uint64_t *)d_rows.ptr, keys.ids.data(), (int)ne, keys.dbc, keys.seed, 0, (uint64_t *)plain->ptr, stream()),
+        "crc_seeded_keys_expand_dev");
+    // the conjugated blobs beside them, run by run between the elements 1 (g = 1 has no key to conjugate: its blob is never read)
+    for (size_t e0 = 0; e0 < ne;) {
+        if (keys.ids[e0] == 1) { e0++; continue; }
+        size_t e1 = e0; while (e1 < ne && keys.ids[e1] != 1) e1++;
+        chk(crc_seeded_keys_expand_dev(ctx(), (const uint64_t *)d_rows.ptr + e0 * rw, keys.ids.data() + e0, (int)(e1 - e0), keys.dbc, keys.seed, 1,
+                                       (uint64_t *)conj->ptr + e0 * kw, stream()), "crc_seeded_keys_expand_dev");
+        e0 = e1;
+    }
+    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+    g_galois_keys = plain; g_galois_ckeys = conj; g_galois_pkeys.reset();
+    galois_elts = keys.ids; galois_keys_host.clear(); g_galois_dbc = keys.dbc;
+}
+void SeededKeys::save(ostream &os) const
+{
+    if (dbc < 1 || dbc > 60 || rows.size() != ids.size() * crc_seeded_key_words(ctx(), dbc)) throw invalid_argument("SeededKeys::save: rows do not match the elements");
+    vector<uint8_t> b(crc_seeded_keys_bytes(ctx(), dbc, (int)ids.size())); size_t w = 0;
+    chk(crc_seeded_keys_save(ctx(), rows.data(), ids.data(), (int)ids.size(), dbc, seed, b.data(), b.size(), &w), "crc_seeded_keys_save");
+    os.write((const char *)b.data(), (streamsize)b.size());
+    if (!os) throw runtime_error("SeededKeys::save: write failed");
+}
+void SeededKeys::load(istream &is)
+{
+    // the header says how long the container is (uint32 dbc at offset 12, uint64 n_ids at offset 48 of its 88 bytes), and it is not trusted: magic, version and
+    // parameter hash are checked before its count sizes anything, and the payload is read in bounded pieces, so memory follows the bytes that really arrive
+    vector<uint8_t> b(88);
+    is.read((char *)b.data(), 88);
+    if (!is) throw invalid_argument("SeededKeys::load: not a seeded key file");
+    uint32_t version = 0, d = 0; uint64_t cnt = 0, hash[4];
+    memcpy(&version, b.data() + 8, 4); memcpy(&d, b.data() + 12, 4); memcpy(&cnt, b.data() + 48, 8);
+    chk(crc_params_hash(ctx(), hash), "crc_params_hash");
+    if (memcmp(b.data(), "CRCSKEY\0", 8) || version != 1) throw invalid_argument("SeededKeys::load: not a seeded key file");
+    if (memcmp(b.data() + 16, hash, 32)) throw invalid_argument("seeded keys are not valid for encryption parameters");
+    const size_t total = cnt <= (1u << 24) ? crc_seeded_keys_bytes(ctx(), (int)d, (int)cnt) : 0;
+    if (total < 88) throw invalid_argument("SeededKeys::load: not a seeded key file");
+    for (size_t at = 88; at < total;) {
+        const size_t piece = min<size_t>(total - at, (size_t)64 << 20);
+        b.resize(at + piece);
+        is.read((char *)b.data() + at, (streamsize)piece);
+        if (!is) throw invalid_argument("SeededKeys::load: file shorter than its header says");
+        at += piece;
+    }
+    vector<uint64_t> r(cnt * crc_seeded_key_words(ctx(), (int)d)), id(cnt); int got = 0, gd = 0; uint8_t sd[32];
+    // (the size query first: an empty set has no rows to point at)
+    chk(crc_seeded_keys_load(ctx(), b.data(), b.size(), nullptr, nullptr, 0, &got, &gd, nullptr), "seeded keys are not valid for encryption parameters");
+    if (cnt) chk(crc_seeded_keys_load(ctx(), b.data(), b.size(), r.data(), id.data(), (int)cnt, &got, &gd, sd), "seeded keys are not valid for encryption parameters");
+    else memcpy(sd, b.data() + 56, 32);
+    dbc = gd; ids.swap(id); rows.swap(r); memcpy(seed, sd, 32);
+}
 // what the three operations share: the checks in the reference's order, the result tensor, the scratch.  mode 0 rotate_rows(steps), 1 rotate_columns, 2 the slot sum
 static ciphertext3D galoisOp(const char *what, const ciphertext3D &t, int mode, int steps, int out_form)
 {

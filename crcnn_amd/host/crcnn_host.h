@@ -202,6 +202,28 @@ std::vector<std::vector<double>> decryptImageSlots(const ciphertext3D &t, int S,
 void generateGaloisKeys(int dbc = 16);
 void generateGaloisKeys(int dbc, std::vector<uint64_t> elts);
 extern std::vector<uint64_t> galois_elts, galois_keys_host;             // the elements, and their key blobs [elts][crc_evk_words(dbc)]
+// SEEDED Galois keys (include/crcnn_hip.h, "SEEDED key-switching keys"): the second polynomial of every key pair is a function of a PUBLIC seed, so a client
+// sends the first rows, the elements and 32 bytes -- half of what the blobs take -- and the server regenerates the rest on the device.
+struct SeededKeys {
+    int dbc = 0;
+    std::vector<uint64_t> ids;                              // the Galois elements
+    uint8_t seed[32] = {0};                                 // PUBLIC
+    std::vector<uint64_t> rows;                             // [ids][P][k][n], NTT form (crc_seeded_key_words(dbc) per element)
+    // the container of crc_seeded_keys_save; load throws std::invalid_argument for anything else
+    void save(std::ostream &out) const;
+    void load(std::istream &in);
+};
+// the CLIENT side: the first rows of the keys of `elts` from the global secret_key, on the host threads or (`on_device`) on the installed stream under the cached
+// device copy of the secret key (crc_gen_keys_seeded[_dev]).  The PRIVATE key is the master key and the PUBLIC seed a function of it (half a keystream block under a domain of its
+// own), NOT a fresh draw: the keystreams are named by element, dbc and modulus count alone, so an element made again -- in another set, by another call -- must
+// meet the same seed, and is then the same key byte for byte, as under generateGaloisKeys (equal noise around two different masks would give the secret key
+// away).  Under setDeterministicSeed both derive from the deterministic seed as generateGaloisKeys' does.  Either way the two paths give the same SeededKeys.  Installs
+// nothing.  Exceptions as generateGaloisKeys
+SeededKeys generateGaloisKeysSeeded(int dbc, std::vector<uint64_t> elts, bool on_device = false);
+// the SERVER side: uploads the rows, expands the blobs and their conjugated forms on the device (crc_seeded_keys_expand_dev) and leaves the Galois key set as
+// generateGaloisKeys(keys.dbc, keys.ids) would: every rotation, matvecSlots*, convSlots and densePlanes call works unchanged.  No secret key is needed and none
+// is read; galois_keys_host stays empty (the blobs exist on the device only).  std::invalid_argument for a bad dbc, an invalid element or rows of another size
+void installGaloisKeys(const SeededKeys &keys);
 // Every ciphertext of the tensor rotated (CRC_COEFF / CRC_NTT in, out_form CRC_COEFF / CRC_NTT out; a new tensor of the same shape).  The n slots are a
 // 2 x n/2 matrix: rotateRows puts old slot (i + steps) mod n/2 of each row at slot i (to the left for positive steps), rotateColumns swaps the rows, sumSlots
 // leaves the sum of all n slots in every slot.  As in the reference: std::logic_error when the parameters do not support batching, std::invalid_argument for

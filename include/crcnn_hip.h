@@ -889,6 +889,69 @@ int crc_seeded_ct_load(const crc_ctx *ctx, const void *buf, size_t bytes, uint64
                        uint64_t *stream_base);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * SEEDED key-switching keys: evaluation and Galois keys in half the bytes, made on the host or on the device.  A key blob (crc_evk_words) is a list of pairs
+ * (first, second) with second = A uniform, so -- as for a seeded ciphertext -- A is a function of a PUBLIC seed and only the first rows travel.
+ *
+ *   key id     0 for the evaluation key (target w = s^2), or a valid Galois element g (target w = sigma_g(s)); no valid element is even, so 0 is free
+ *   pairs      numbered in the blob's own order, p = Sum_{l' < l} L_l' + d for modulus l and digit d; P = Sum_l L_l = crc_evk_words / (2 k n)
+ *   one key    its P first polynomials [P][k][n], NTT form: crc_seeded_key_words = P k n words, exactly half the blob
+ *   a key set  ids [n_ids], dbc, a 32-byte PUBLIC seed, the rows [n_ids][P][k][n]
+ * An EXPANDED seeded key IS an ordinary blob: every consumer (crc_relinearize*, crc_apply_galois_forms, crc_rotate_hoisted_forms, crc_diag_mac*, crc_conv_slots*,
+ * crc_dense_planes_forms, crc_galois_prepare_keys_dev) takes it unchanged.  The keys differ from those of crc_gen_evk* / crc_gen_galois_keys* (other
+ * keystreams); they decrypt the same.
+ *
+ * Keystreams, one per (id, pair, even slot s), nonce = (id, p | dbc << 16 | k << 24, domain << 24 | s):
+ *   mask,  PUBLIC seed,  domain CHACHA_DOM_KSK_A = 9: blocks and words exactly as domain 6 -- block j serves modulus 2j with its words 0..7 and modulus 2j + 1
+ *          with its words 8..15; the 128-bit z of words 4c .. 4c + 3 gives second[i][s + c] = z mod q_i
+ *   noise, PRIVATE key,  domain CHACHA_DOM_KSK_E = 10: one block (counter 0), words 0..4 as block 0 of domain 5 (two magnitude words against the 19 thresholds
+ *          of crc_encrypt_dev_noise_thresholds, sign bits in w[4]); e is a coefficient-form polynomial, the same integer under every modulus
+ * Definition (NTT form, pointwise):  first[j] = -(A[j] s[j] + NTT_j(e)) + [j == l] factor_{l,d} w[j],  factor_{l,d} = (q / q_l) 2^(dbc d) mod q_l,
+ * w = s^2 for id 0 and w[j][i] = s[j][pi_g(i)] for an element (pi_g: crc_galois_ntt_table(g); no inverse transform of s is needed).
+ *
+ * SECURITY.  Two domains and two keys for the reason given for domains 6 / 7.  dbc and k are part of the nonce because the streams are counter-based: without
+ * them one private key serving the same id at two digit widths, or on a context and on a prefix of its moduli (crc_mod_switch_*), would give equal A and equal e
+ * around DIFFERENT known factors, and first - first' = (factor - factor') sigma_g(s) would reveal the secret key.  Never generate the same id twice under one
+ * (private key, dbc, k) with different public seeds or secret keys.  (The host classes keep this by taking the public seed from the private master key itself: bytes 0..31 of
+ * block 0 of its stream nonce = (0, 0, CHACHA_DOM_KSK_SEED = 11 << 24), a PRF output that may be published -- an element generated again is the same key.)  The _key variants refuse a public seed byte-equal to the private key.  The uint64-seed
+ * variants (tests, bench; deterministic, NOT secure) derive private key = the expansion of `seed`, public seed = crc_seeded_public_seed(seed).
+ *
+ *   crc_seeded_key_words           P k n; 0 for a bad dbc
+ *   crc_gen_keys_seeded[_key]      on the host, any context, spread over the host threads by id: h_first [n_ids][P][k][n]
+ *   crc_seeded_keys_expand         on the host: h_first -> h_out [n_ids][crc_evk_words].  conjugate = 0: the blobs K; conjugate = 1: K' =
+ *                                  crc_galois_conjugate_keys of them, bit for bit (ids 0 and 1 are refused: they have no conjugated key)
+ *   crc_gen_keys_seeded_dev[_key]  d_sk_ntt [k][n] -> d_first, bit for bit the host rows.  Three steps on `stream`, in place, no work buffer: a sample kernel
+ *                                  writes e, the forward row transform runs over the n_ids P rows, a finish kernel regenerates A in registers, gathers the target
+ *                                  from the secret key's rows and stores first.  `ids` is a HOST array
+ *   crc_seeded_keys_expand_dev     d_first -> d_out blobs; one kernel copies the first rows and generates the second rows; with conjugate = 1 the same
+ *                                  kernel stores every residue at its conjugated place (equal to crc_seeded_keys_expand_dev + crc_galois_conjugate_keys_dev,
+ *                                  without the second buffer)
+ *   crc_seeded_keys_bytes / _save / _load   the container: 88 header bytes -- magic "CRCSKEY\0", uint32 version 1, uint32 dbc, crc_params_hash (32), uint64
+ *                                  n_ids, the seed (32) -- then the ids (n_ids uint64) and the rows (n_ids P k n uint64), little-endian: half the blobs' bytes
+ *                                  plus 88 + 8 n_ids.  _load refuses a wrong magic / version / hash / dbc / id, a short buffer and a count that does not match
+ *                                  the byte length, and then writes nothing; with h_first = NULL it only validates and reports *n_ids and *dbc
+ * Refusals (CRC_ERR_INVALID_ARGUMENT, nothing written, nothing launched): a host-only context for the _dev calls, NULL or (device) not 16-byte aligned
+ * pointers, d_first overlapping d_sk_ntt or d_out, an id that is neither 0 nor a valid element, dbc outside 1..60, a launch grid over 2^31 - 1.  n_ids = 0 is
+ * CRC_OK and writes nothing.
+ * ------------------------------------------------------------------------------------------------------------- */
+size_t crc_seeded_key_words(const crc_ctx *ctx, int dbc);
+int crc_gen_keys_seeded_key(const crc_ctx *ctx, const uint8_t *h_key /*PRIVATE*/, const uint8_t *h_seed /*PUBLIC*/, const uint64_t *h_sk_ntt, int dbc,
+                            const uint64_t *ids, int n_ids, uint64_t *h_first /*[n_ids][P][k][n]*/);
+int crc_gen_keys_seeded(const crc_ctx *ctx, uint64_t seed, const uint64_t *h_sk_ntt, int dbc, const uint64_t *ids, int n_ids, uint64_t *h_first);
+int crc_seeded_keys_expand(const crc_ctx *ctx, const uint64_t *h_first, const uint64_t *ids, int n_ids, int dbc, const uint8_t *h_seed, int conjugate,
+                           uint64_t *h_out /*[n_ids][crc_evk_words]*/);
+int crc_gen_keys_seeded_dev_key(crc_ctx *ctx, const uint8_t *h_key /*PRIVATE*/, const uint8_t *h_seed /*PUBLIC*/, const uint64_t *d_sk_ntt, int dbc,
+                                const uint64_t *ids /*host*/, int n_ids, uint64_t *d_first, void *stream);
+int crc_gen_keys_seeded_dev(crc_ctx *ctx, uint64_t seed, const uint64_t *d_sk_ntt, int dbc, const uint64_t *ids /*host*/, int n_ids, uint64_t *d_first,
+                            void *stream);
+int crc_seeded_keys_expand_dev(crc_ctx *ctx, const uint64_t *d_first, const uint64_t *ids /*host*/, int n_ids, int dbc, const uint8_t *h_seed, int conjugate,
+                               uint64_t *d_out, void *stream);
+size_t crc_seeded_keys_bytes(const crc_ctx *ctx, int dbc, int n_ids);
+int crc_seeded_keys_save(const crc_ctx *ctx, const uint64_t *h_first, const uint64_t *ids, int n_ids, int dbc, const uint8_t *h_seed, void *buf, size_t cap,
+                         size_t *written);
+int crc_seeded_keys_load(const crc_ctx *ctx, const void *buf, size_t bytes, uint64_t *h_first, uint64_t *ids, int max_ids, int *n_ids, int *dbc,
+                         uint8_t *h_seed);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Modulus switching: a ciphertext tensor continues over fewer coefficient moduli (SEAL 2.3.1 has no such operation; later SEALs call it
  * mod_switch_to_next).  `from` has the moduli q_0 .. q_{k-1}, `to` the first k' < k of them (d = k - k' are dropped), the same n and t.
  *
