@@ -294,6 +294,13 @@ def load():
     L.crc_mod_switch_work_bytes.restype = SZ; L.crc_mod_switch_work_bytes.argtypes = [VP, VP, SZ, CI, CI, CI]
     L.crc_mod_switch_forms.argtypes = [VP, VP, VP, CI, SZ, CI, VP, CI, VP, VP]
     L.crc_mod_switch.argtypes = [VP, VP, PU, CI, SZ, CI, PU, CI]
+    L.crc_ctx_create_level.argtypes = [VP, CI, CI, ctypes.POINTER(VP)]
+    L.crc_ctx_key_moduli.argtypes = [VP]
+    L.crc_keys_restrict_supported.argtypes = [VP, VP]
+    L.crc_keys_restrict.argtypes = [VP, VP, PU, CI, CI, PU]
+    L.crc_keys_restrict_dev.argtypes = [VP, VP, VP, CI, CI, VP, VP]
+    L.crc_seeded_keys_expand_level.argtypes = [VP, VP, PU, PU, CI, CI, PB, CI, PU]
+    L.crc_seeded_keys_expand_level_dev.argtypes = [VP, VP, VP, PU, CI, CI, PB, CI, VP, VP]
     _lib = L
     return L
 
@@ -586,12 +593,15 @@ class DBuf:
 class Engine:
     """One context = one (n, q[], t) parameter set on one device (device=-1: host-only, for encode/client/tables)."""
 
-    def __init__(self, n, q, t, device=0):
+    def __init__(self, n, q, t, device=0, _level_of=None):
         self.L = load()
         self.n, self.k, self.t, self.device = int(n), len(q), int(t), device
         self.q = np.array(q, dtype=np.uint64)
         c = VP()
-        _chk(self.L.crc_ctx_create(self.n, _pu(self.q), self.k, self.t, device, ctypes.byref(c)), "crc_ctx_create")
+        if _level_of is None:
+            _chk(self.L.crc_ctx_create(self.n, _pu(self.q), self.k, self.t, device, ctypes.byref(c)), "crc_ctx_create")
+        else:       # (derived_level: the first len(q) moduli of that engine, its key-switching gadget kept)
+            _chk(self.L.crc_ctx_create_level(_level_of.c, self.k, device, ctypes.byref(c)), "crc_ctx_create_level")
         self.c = c
         self.kbsk = self.L.crc_ctx_kbsk(self.c)
         self.stream = None
@@ -651,6 +661,47 @@ class Engine:
         if not 1 <= kept < self.k:
             raise ValueError(f"level({kept}): a level keeps 1 .. {self.k - 1} of the {self.k} moduli")
         return Engine(self.n, [int(v) for v in self.q[:kept]], self.t, device=self.device)
+
+    # ---- a level WITHOUT the secret key: the gadget of the key switch stays this engine's, and this engine's keys, restricted, are the level's (crc_keys_restrict*)
+    def derived_level(self, kept):
+        """an Engine over the first `kept` moduli made by crc_ctx_create_level: as level(kept) for everything but key switching, which takes this engine's evaluation
+        and Galois keys restricted to the level (keys_restrict[_dev], seeded_keys_expand_level[_dev]).  Key generation is refused on it"""
+        kept = int(kept)
+        if not 1 <= kept < self.k:
+            raise ValueError(f"derived_level({kept}): a level keeps 1 .. {self.k - 1} of the {self.k} moduli")
+        return Engine(self.n, [int(v) for v in self.q[:kept]], self.t, device=self.device, _level_of=self)
+
+    @property
+    def key_moduli(self):
+        """modulus count of the key-switching gadget: k, or on a derived level the top ancestor's k"""
+        return self.L.crc_ctx_key_moduli(self.c)
+
+    def keys_restrict_supported(self, to):
+        return bool(self.L.crc_keys_restrict_supported(self.c, to.c))
+
+    def keys_restrict(self, to, keys, dbc=16):
+        """host twin: blobs [n_keys][crc_evk_words] of this engine (evaluation, Galois or conjugated) -> [n_keys][crc_evk_words] of the derived level `to`"""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, self.L.crc_evk_words(self.c, dbc))
+        out = np.zeros((keys.shape[0], to.L.crc_evk_words(to.c, dbc)), dtype=np.uint64)
+        _chk(self.L.crc_keys_restrict(self.c, to.c, _pu(keys), keys.shape[0], dbc, _pu(out)), "crc_keys_restrict")
+        return out
+
+    def keys_restrict_dev(self, to, d_keys, n_keys, d_out, dbc=16):
+        _chk(self.L.crc_keys_restrict_dev(self.c, to.c, self.p(d_keys), n_keys, dbc, self.p(d_out), self.stream), "crc_keys_restrict_dev")
+
+    def seeded_keys_expand_level(self, to, first, ids, public_seed, dbc=16, conjugate=False):
+        """host twin: this engine's seeded rows -> the blobs of the derived level `to`, = keys_restrict(to, seeded_keys_expand(...))"""
+        ids = self._elts(ids)
+        first = np.ascontiguousarray(first, dtype=np.uint64).reshape(ids.size, self.seeded_key_words(dbc))
+        out = np.zeros((ids.size, to.L.crc_evk_words(to.c, dbc)), dtype=np.uint64)
+        _chk(self.L.crc_seeded_keys_expand_level(self.c, to.c, _pu(first), _pu(ids), ids.size, dbc, self._key(public_seed), 1 if conjugate else 0, _pu(out)),
+             "crc_seeded_keys_expand_level")
+        return out
+
+    def seeded_keys_expand_level_dev(self, to, d_first, ids, public_seed, d_out, dbc=16, conjugate=False):
+        ids = self._elts(ids)
+        _chk(self.L.crc_seeded_keys_expand_level_dev(self.c, to.c, self.p(d_first), _pu(ids), ids.size, dbc, self._key(public_seed), 1 if conjugate else 0,
+                                                     self.p(d_out), self.stream), "crc_seeded_keys_expand_level_dev")
 
     def mod_switch_supported(self, to):
         return bool(self.L.crc_mod_switch_supported(self.c, to.c))

@@ -1487,6 +1487,7 @@ static bool seeded_key_ids_ok(const crc_ctx *c, const uint64_t *ids, int n_ids, 
 static int gen_keys_seeded_dev_impl(crc_ctx *c, const ChaChaKey &key, const ChaChaKey &seed, const u64 *d_sk, int dbc, const uint64_t *ids, int n_ids, u64 *d_first,
                                     hipStream_t st)
 {
+    if (!own_gadget(c)) return CRC_ERR_PARAMETERS;                      // a level with an inherited gadget takes its keys from above (crc_keys_restrict*)
     if (!dbc_ok(dbc) || n_ids < 0) return CRC_ERR_INVALID_ARGUMENT;
     if (n_ids == 0) return CRC_OK;
     if (!ids || !d_first || !aligned16(d_sk) || !aligned16(d_first) || !k_seeded_keys_grid_ok(c, dbc, n_ids) || !seeded_key_ids_ok(c, ids, n_ids, false))
@@ -1521,6 +1522,30 @@ extern "C" int crc_seeded_keys_expand_dev(crc_ctx *c, const uint64_t *d_first, c
     const size_t kw = crc_evk_words(c, dbc);
     if (ranges_overlap(d_first, 4 * kw * n_ids, d_out, 8 * kw * n_ids)) return CRC_ERR_INVALID_ARGUMENT;
     return k_seeded_keys_expand(c, d_first, ids, n_ids, dbc, chacha_load_key(seed), conjugate != 0, d_out, S(stream));
+}
+// ---- keys of a level from the keys of the context above it (crc_ctx_create_level; kernels_seeded_keys.hip) ----
+extern "C" int crc_keys_restrict_supported(const crc_ctx *from, const crc_ctx *to) { return keys_level_of(from, to) ? 1 : 0; }
+extern "C" int crc_keys_restrict_dev(crc_ctx *from, const crc_ctx *to, const uint64_t *d_keys, int n_keys, int dbc, uint64_t *d_out, void *stream)
+{
+    CHECK_CTX(from);
+    if (!keys_level_of(from, to) || !dbc_ok(dbc) || n_keys < 0) return CRC_ERR_INVALID_ARGUMENT;
+    if (n_keys == 0) return CRC_OK;
+    if (!d_keys || !d_out || !aligned16(d_keys) || !aligned16(d_out) || !k_seeded_keys_grid_ok(from, dbc, n_keys) || !k_seeded_keys_grid_ok(to, dbc, n_keys))
+        return CRC_ERR_INVALID_ARGUMENT;
+    if (ranges_overlap(d_keys, 8 * crc_evk_words(from, dbc) * n_keys, d_out, 8 * crc_evk_words(to, dbc) * n_keys)) return CRC_ERR_INVALID_ARGUMENT;
+    return k_keys_restrict(from, to, d_keys, n_keys, dbc, d_out, S(stream));
+}
+extern "C" int crc_seeded_keys_expand_level_dev(crc_ctx *from, const crc_ctx *to, const uint64_t *d_first, const uint64_t *ids, int n_ids, int dbc,
+                                                const uint8_t *seed, int conjugate, uint64_t *d_out, void *stream)
+{
+    if (!seed || (conjugate != 0 && conjugate != 1)) return CRC_ERR_INVALID_ARGUMENT;
+    CHECK_CTX(from);
+    if (!keys_level_of(from, to) || !dbc_ok(dbc) || n_ids < 0) return CRC_ERR_INVALID_ARGUMENT;
+    if (n_ids == 0) return CRC_OK;
+    if (!d_first || !ids || !d_out || !aligned16(d_first) || !aligned16(d_out) || !k_seeded_keys_grid_ok(from, dbc, n_ids) || !k_seeded_keys_grid_ok(to, dbc, n_ids) ||
+        !seeded_key_ids_ok(from, ids, n_ids, conjugate != 0)) return CRC_ERR_INVALID_ARGUMENT;
+    if (ranges_overlap(d_first, 4 * crc_evk_words(from, dbc) * n_ids, d_out, 8 * crc_evk_words(to, dbc) * n_ids)) return CRC_ERR_INVALID_ARGUMENT;
+    return k_seeded_keys_expand_level(from, to, d_first, ids, n_ids, dbc, chacha_load_key(seed), conjugate != 0, d_out, S(stream));
 }
 extern "C" size_t crc_rotate_hoisted_work_bytes(const crc_ctx *c, size_t count, int R, int dbc) { return hoist_bytes(c, count, R, 2, dbc); }
 extern "C" int crc_rotate_hoisted_forms(crc_ctx *c, const uint64_t *d_x, int in_form, size_t count, const uint64_t *gs, int R, const uint64_t *d_cgk,

@@ -150,6 +150,7 @@ static void switch_key_impl(const crc_ctx *c, Rng &r, const uint64_t *sk, const 
 }
 static int gen_evk_impl(const crc_ctx *c, const ChaChaKey &ckey, const uint64_t *sk, int dbc, uint64_t *evk)
 {
+    if (!own_gadget(c)) return CRC_ERR_PARAMETERS;             // a level with an inherited gadget takes its keys from above (crc_keys_restrict*)
     if (!dbc_ok(dbc)) return CRC_ERR_INVALID_ARGUMENT;
     const int n = c->n, k = c->k;
     Rng r(ckey, 0, 0, (u32)CHACHA_DOM_EVK << 24);
@@ -233,6 +234,7 @@ static void galois_row(const u64 *in, u64 *out, int n, u64 g, u64 q)
 // (CHACHA_DOM_GALOIS, the element in the nonce): keys of different elements never share randomness, and a set's keys do not depend on its order
 static int gen_galois_impl(const crc_ctx *c, const ChaChaKey &ckey, const uint64_t *sk, int dbc, const uint64_t *elts, int n_elts, uint64_t *gk)
 {
+    if (!own_gadget(c)) return CRC_ERR_PARAMETERS;
     if (!dbc_ok(dbc) || n_elts < 0) return CRC_ERR_INVALID_ARGUMENT;
     for (int e = 0; e < n_elts; e++) if (!crc_galois_elt_valid(c, elts[e])) return CRC_ERR_INVALID_ARGUMENT;
     const int n = c->n, k = c->k;
@@ -569,6 +571,7 @@ void ksk_mask(const crc_ctx *c, const ChaChaKey &seed, u64 id, u32 n1, u64 *a)
 }
 int gen_keys_seeded_impl(const crc_ctx *c, const ChaChaKey &key, const ChaChaKey &seed, const uint64_t *sk, int dbc, const uint64_t *ids, int n_ids, uint64_t *first)
 {
+    if (!own_gadget(c)) return CRC_ERR_PARAMETERS;
     if (!dbc_ok(dbc) || n_ids < 0) return CRC_ERR_INVALID_ARGUMENT;
     for (int e = 0; e < n_ids; e++) if (!ksk_id_ok(c, ids[e])) return CRC_ERR_INVALID_ARGUMENT;
     const int n = c->n, k = c->k;
@@ -648,6 +651,54 @@ extern "C" int crc_seeded_keys_expand(const crc_ctx *c, const uint64_t *first, c
         }
         if (!conjugate) continue;
         crc_galois_ntt_table(c, galois_inverse(c, ids[e]), tab.data());
+        for (size_t r = 0; r < words / n; r++) {
+            const u64 *src = blob.data() + r * n; u64 *o = out + e * words + r * n;
+            for (size_t i = 0; i < n; i++) o[i] = src[tab[i]];
+        }
+    }
+    });
+    return CRC_OK;
+}
+
+// ---- keys of a level from the keys of the context above it (crc_ctx_create_level): the host twins of ksk_restrict_body / ksk_expand_level_body ----
+// A pair (l, d) of a key over Q = q_0 .. q_{K-1} holds E = (Q/q_l) 2^(dbc d) in row l alone; mod q_B = q_0 .. q_{k'-1} the pairs with l >= k' hold nothing, and the
+// others are the first P' = Sum_{l < k'} L_l pairs, of which rows [0, k') are a key at the level for the SAME gadget -- hence the level's ksk_inv_qhat
+static bool host_ranges_overlap(const void *a, size_t ab, const void *b, size_t bb) { const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b; return a0 < b0 + bb && b0 < a0 + ab; }
+extern "C" int crc_keys_restrict(const crc_ctx *from, const crc_ctx *to, const uint64_t *keys, int n_keys, int dbc, uint64_t *out)
+{
+    if (!keys_level_of(from, to) || !dbc_ok(dbc) || n_keys < 0) return CRC_ERR_INVALID_ARGUMENT;
+    if (n_keys == 0) return CRC_OK;
+    const size_t n = (size_t)from->n, skn = (size_t)from->k * n, kn = (size_t)to->k * n, in_w = crc_evk_words(from, dbc), out_w = crc_evk_words(to, dbc), P = out_w / (2 * kn);
+    if (!keys || !out || host_ranges_overlap(keys, 8 * in_w * n_keys, out, 8 * out_w * n_keys)) return CRC_ERR_INVALID_ARGUMENT;
+    crc_host::parallel_for((size_t)n_keys, 1, [&](size_t e0, size_t e1) {
+    for (size_t e = e0; e < e1; e++) for (size_t p = 0; p < P; p++) for (int poly = 0; poly < 2; poly++)
+        std::memcpy(out + e * out_w + (2 * p + poly) * kn, keys + e * in_w + (2 * p + poly) * skn, 8 * kn);
+    });
+    return CRC_OK;
+}
+extern "C" int crc_seeded_keys_expand_level(const crc_ctx *from, const crc_ctx *to, const uint64_t *first, const uint64_t *ids, int n_ids, int dbc, const uint8_t *seed,
+                                            int conjugate, uint64_t *out)
+{
+    if (!keys_level_of(from, to) || !seed || !dbc_ok(dbc) || n_ids < 0 || (conjugate != 0 && conjugate != 1)) return CRC_ERR_INVALID_ARGUMENT;
+    if (n_ids == 0) return CRC_OK;
+    if (!first || !ids || !out) return CRC_ERR_INVALID_ARGUMENT;
+    for (int e = 0; e < n_ids; e++) if (!ksk_id_ok(from, ids[e]) || (conjugate && ids[e] <= 1)) return CRC_ERR_INVALID_ARGUMENT;
+    const size_t n = (size_t)from->n, skn = (size_t)from->k * n, kn = (size_t)to->k * n, words = crc_evk_words(to, dbc), P = words / (2 * kn),
+        sP = crc_evk_words(from, dbc) / (2 * skn);
+    if (host_ranges_overlap(first, 8 * sP * skn * n_ids, out, 8 * words * n_ids)) return CRC_ERR_INVALID_ARGUMENT;
+    const int name_k = (int)from->key_q.size();                // the k of the stream names: the modulus count of the gadget the keys were generated over
+    const ChaChaKey sd = load_key(seed);
+    crc_host::parallel_for((size_t)n_ids, 1, [&](size_t e0, size_t e1) {
+    std::vector<u64> blob(conjugate ? words : 0);
+    std::vector<uint32_t> tab(conjugate ? n : 0);
+    for (size_t e = e0; e < e1; e++) {
+        u64 *dst = conjugate ? blob.data() : out + e * words;
+        for (size_t p = 0; p < P; p++) {
+            std::memcpy(dst + p * 2 * kn, first + (e * sP + p) * skn, 8 * kn);
+            ksk_mask(to, sd, ids[e], CHACHA_KSK_NONCE1(p, dbc, name_k), dst + p * 2 * kn + kn);      // (the first k' residues of a keystream are a prefix of it)
+        }
+        if (!conjugate) continue;
+        crc_galois_ntt_table(to, galois_inverse(to, ids[e]), tab.data());
         for (size_t r = 0; r < words / n; r++) {
             const u64 *src = blob.data() + r * n; u64 *o = out + e * words + r * n;
             for (size_t i = 0; i < n; i++) o[i] = src[tab[i]];

@@ -61,10 +61,16 @@ int evk_gadget(const crc_ctx *c, int dbc, int L[CRC_MAXK], u64 qhat[CRC_MAXK])
     int P = 0;
     for (int l = 0; l < c->k; l++) {
         u64 f = 1;
-        for (int j = 0; j < c->k; j++) if (j != l) f = h_mulmod(f, c->q[j] % c->q[l], c->q[l]);
+        for (size_t j = 0; j < c->key_q.size(); j++) if ((int)j != l) f = h_mulmod(f, c->key_q[j] % c->q[l], c->q[l]);
         qhat[l] = f; L[l] = evk_digits(c->q[l], dbc); P += L[l];
     }
     return P;
+}
+bool keys_level_of(const crc_ctx *from, const crc_ctx *to)
+{
+    if (!from || !to || to->n != from->n || to->k < 1 || to->k >= from->k || to->key_q != from->key_q) return false;
+    for (int i = 0; i < to->k; i++) if (to->q[i] != from->q[i]) return false;
+    return true;
 }
 
 static bool is_prime(u64 n)
@@ -286,6 +292,7 @@ extern "C" int crc_ctx_create(int n, const uint64_t *q, int k, uint64_t t, int d
     c->n = n; c->k = k; c->t = t; c->device = device;
     c->logn = 0; while ((1 << c->logn) < n) c->logn++;
     c->q.assign(q, q + k);
+    c->key_q = c->q;
 
     // aux base size rule, baseconverter.cpp:47-56
     int total = 0; for (int i = 0; i < k; i++) total += sigbits(q[i]);
@@ -343,6 +350,7 @@ extern "C" int crc_ctx_create(int n, const uint64_t *q, int k, uint64_t t, int d
     for (int i = 0; i < k; i++) {
         b.mt_inv_qhat_s[i] = shoup(b.mt_inv_qhat[i], q[i]); b.inv_qhat_s[i] = shoup(b.inv_qhat[i], q[i]);
         b.t_inv_qhat[i] = h_mulmod(t % q[i], b.inv_qhat[i], q[i]); b.t_inv_qhat_s[i] = shoup(b.t_inv_qhat[i], q[i]);
+        b.ksk_inv_qhat[i] = b.inv_qhat[i]; b.ksk_inv_qhat_s[i] = b.inv_qhat_s[i];
     }
     for (int j = 0; j < c->kb; j++) {
         b.t_mod_bsk[j] = t % bsk[j]; b.t_mod_bsk_s[j] = shoup(b.t_mod_bsk[j], bsk[j]);
@@ -493,6 +501,33 @@ extern "C" int crc_ctx_create(int n, const uint64_t *q, int k, uint64_t t, int d
     return CRC_OK;
 }
 
+// A context over the parent's first `kept` moduli whose key-switching gadget stays the parent's (and so the top ancestor's): everything crc_ctx_create builds for
+// the prefix, then the gadget list and the one constant that depends on it
+extern "C" int crc_ctx_create_level(const crc_ctx *parent, int kept, int device, crc_ctx **out)
+{
+    if (!out) return CRC_ERR_INVALID_ARGUMENT;
+    *out = nullptr;
+    if (!parent) return CRC_ERR_INVALID_ARGUMENT;
+    if (kept < 1 || kept >= parent->k) return CRC_ERR_PARAMETERS;
+    crc_ctx *c = nullptr;
+    const int rc = crc_ctx_create(parent->n, parent->q.data(), kept, parent->t, device, &c);
+    if (rc) return rc;
+    c->key_q = parent->key_q;
+    BehzParams &b = c->behz;
+    for (int i = 0; i < kept; i++) {
+        const u64 qi = c->q[i];
+        b.ksk_inv_qhat[i] = h_invmod(prod_mod(c->key_q.data(), (int)c->key_q.size(), i, qi), qi);
+        b.ksk_inv_qhat_s[i] = (u64)(((u128)b.ksk_inv_qhat[i] << 64) / qi);
+    }
+    if (device >= 0) {
+        const hipError_t e = hipMemcpy(c->d_behz, &c->behz, sizeof(BehzParams), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { crc_ctx_destroy(c); return crc_set_hip_error(e); }
+    }
+    *out = c;
+    return CRC_OK;
+}
+extern "C" int crc_ctx_key_moduli(const crc_ctx *c) { return c ? (int)c->key_q.size() : 0; }
+
 extern "C" void crc_ctx_destroy(crc_ctx *c)
 {
     if (!c) return;
@@ -598,6 +633,9 @@ extern "C" int crc_ctx_table(const crc_ctx *c, const char *name, uint64_t *out, 
     else if (s == "const_ratio") for (int i = 0; i < k; i++) { v.push_back(c->tabs[i].m.r0); v.push_back(c->tabs[i].m.r1); }
     else if (s == "delta") for (int i = 0; i < k; i++) v.push_back(c->plain.delta[i]);
     else if (s == "upper_half_increment") for (int i = 0; i < k; i++) v.push_back(c->plain.uhi[i]);
+    else if (s == "key_q") v = c->key_q;
+    else if (s == "inv_qhat") for (int i = 0; i < k; i++) v.push_back(c->behz.inv_qhat[i]);
+    else if (s == "ksk_inv_qhat") for (int i = 0; i < k; i++) v.push_back(c->behz.ksk_inv_qhat[i]);
     else if (s == "bsk") for (int j = 0; j < kb; j++) v.push_back(c->tabs[k + j].m.q);
     else if (s == "bsk_root") for (int j = 0; j < kb; j++) v.push_back(c->tabs[k + j].root);
     else if (s == "f64_primes") for (int m = 0; m < CRC_NF64; m++) v.push_back(c->f64_primes[m]);

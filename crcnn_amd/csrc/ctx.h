@@ -57,7 +57,11 @@ struct BehzParams {
     u64 lift_r[CRC_MAXB];                    // q m~^-1 mod Bsk_j                 the r q term of mont_rq (:614-618)
     u64 floor_x[CRC_MAXB];                   // t q^-1 mod Bsk_j                  x t (evaluator.cpp:856-871) then fast_floor's q^-1 (:646-660)
     u64 floor_c[CRC_MAXB][CRC_MAXK];         // -(q/q_i) q^-1 mod Bsk_j           minus fastbconv(x) times q^-1
-    u64 inv_qhat_s[CRC_MAXK];                // Shoup companion of inv_qhat (relinearisation digits are cut out of c2 (q/q_i)^-1, evaluator.cpp:984-985)
+    u64 inv_qhat_s[CRC_MAXK];                // Shoup companion of inv_qhat
+    // (Q_key/q_i)^-1 mod q_i over the moduli of the key-switching GADGET (crc_ctx.key_q) + Shoup companion: what a polynomial is multiplied by before the key
+    // switch cuts its digits (evaluator.cpp:984-985).  Equal to inv_qhat on every context of crc_ctx_create; on a level of crc_ctx_create_level the gadget is an
+    // ancestor's, so that the ancestor's keys, restricted (crc_keys_restrict), serve unchanged.  inv_qhat stays the level's own: BEHZ, decryption, the budget
+    u64 ksk_inv_qhat[CRC_MAXK], ksk_inv_qhat_s[CRC_MAXK];
 };
 
 // The engine's own fp64 NTT primes (f64mod.h): the largest primes below 2^47 that are 1 mod 2^16.  Relinearisation's key-switching inner products
@@ -160,6 +164,7 @@ struct crc_ctx {
     u64 t;
     int total_bits;
     std::vector<u64> q;
+    std::vector<u64> key_q;                  // the moduli of the key-switching gadget: q itself, or (crc_ctx_create_level) an ancestor's list, of which q is a proper prefix
     std::vector<HostNtt> tabs;               // k + kb entries
     PlainParams plain;
     BehzParams behz;
@@ -203,8 +208,13 @@ void h_ntt_fwd(const HostNtt &T, u64 *a, int n);      // canonical in/out
 void h_ntt_inv(const HostNtt &T, u64 *a, int n);
 ModParams make_mod(u64 q, bool no_fold = false);
 int  evk_digits(u64 q, int dbc);
-// the gadget of a key-switching key at digit width dbc: L[l] = evk_digits(q_l, dbc) and qhat[l] = (q / q_l) mod q_l for l < k; returns P = Sum L[l], the pairs of a
-// blob (pair p = Sum_{l' < l} L[l'] + d has the factor qhat[l] 2^(dbc d) mod q_l).  One definition for the host twin and the device launchers of the seeded keys
+// the gadget of a key-switching key at digit width dbc: L[l] = evk_digits(q_l, dbc) and qhat[l] = (Q_key / q_l) mod q_l for l < k, Q_key the product of c->key_q (q
+// itself except on a level of crc_ctx_create_level); returns P = Sum L[l], the pairs of a blob (pair p = Sum_{l' < l} L[l'] + d has the factor qhat[l] 2^(dbc d)
+// mod q_l).  One definition for the host twin and the device launchers of the seeded keys
 int  evk_gadget(const crc_ctx *c, int dbc, int L[CRC_MAXK], u64 qhat[CRC_MAXK]);
+// the context's gadget is its own: false on a level of crc_ctx_create_level, where every key GENERATION entry point answers CRC_ERR_PARAMETERS (crcnn_hip.h)
+static inline bool own_gadget(const crc_ctx *c) { return c->key_q.size() == (size_t)c->k; }
+// `to` is a level of `from` for key material: the same n, the same gadget list, moduli a proper prefix (crc_keys_restrict*, crc_seeded_keys_expand_level*)
+bool keys_level_of(const crc_ctx *from, const crc_ctx *to);
 // the decomposition bit counts SEAL accepts (keygenerator.cpp: 1..60); every entry point that takes a dbc refuses the others before it sizes anything
 static inline bool dbc_ok(int dbc) { return dbc >= 1 && dbc <= 60; }

@@ -143,6 +143,12 @@ int k_slots_rescale_host(crc_ctx *c, const u64 *plain_in, size_t count, u64 divi
 bool k_seeded_keys_grid_ok(const crc_ctx *c, int dbc, int n_ids);
 int k_gen_keys_seeded(crc_ctx *c, const u64 *sk, int dbc, const u64 *ids, int n_ids, const ChaChaKey &key, const ChaChaKey &seed, u64 *first, hipStream_t st);
 int k_seeded_keys_expand(crc_ctx *c, const u64 *rows, const u64 *ids, int n_ids, int dbc, const ChaChaKey &seed, bool conjugate, u64 *out, hipStream_t st);
+// keys of `from` for `to`, a level of it (ctx.h keys_level_of): expanded blobs restricted -- [n_keys][crc_evk_words(from)] -> [n_keys][crc_evk_words(to)] --, and
+// from's seeded rows expanded straight into to's blobs (= the restriction of k_seeded_keys_expand).  Launched on from's device; host twins: crc_keys_restrict,
+// crc_seeded_keys_expand_level (client.cpp)
+int k_keys_restrict(crc_ctx *from, const crc_ctx *to, const u64 *keys, int n_keys, int dbc, u64 *out, hipStream_t st);
+int k_seeded_keys_expand_level(crc_ctx *from, const crc_ctx *to, const u64 *rows, const u64 *ids, int n_ids, int dbc, const ChaChaKey &seed, bool conjugate, u64 *out,
+                               hipStream_t st);
 // kernels_modswitch.hip: modulus switching from `from` to a context over a proper prefix of its moduli -- tensors of `polys` polynomials [polys][k][n] -> [polys][k'][n],
 // either side CRC_COEFF or CRC_NTT (work: k_mod_switch_work_bytes); *_host: the host twin
 bool   k_mod_switch_supported(const crc_ctx *from, const crc_ctx *to);

@@ -26,7 +26,7 @@ __global__ void __launch_bounds__(256) galois_permute_kernel(const u64 *x, u64 *
     const u32 ct = row / (u32)k; const int i = (int)(row - ct * (u32)k);
     const u32 j = (part * 256u + threadIdx.x) * 2u;
     if (j >= (u32)n) return;                                   // n < 512: the tail of the one workgroup of a row
-    const u64 q = mods[i].q, inv = bp->inv_qhat[i], invs = bp->inv_qhat_s[i];
+    const u64 q = mods[i].q, inv = bp->ksk_inv_qhat[i], invs = bp->ksk_inv_qhat_s[i];
     const size_t kn = (size_t)k * n;
     const u64 *c0 = x + (size_t)ct * 2 * kn + (size_t)i * n, *c1 = c0 + kn;
     u64 *o0 = x3 + (size_t)ct * 3 * kn + (size_t)i * n, *o1 = o0 + kn, *o2 = o1 + kn;

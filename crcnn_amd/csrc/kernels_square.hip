@@ -124,7 +124,7 @@ __global__ void __launch_bounds__(256) sq_floor_kernel(const u64 *dq, const u64 
         if (neg) acc_mad(a, b.M_mod_q[i], b.m_sk - alpha);                                          // :553-559
         else acc_mad(a, mi.q - b.M_mod_q[i], alpha);                                                // :561-569
         u64 v = barrett128(a.lo, a.hi, mi);
-        if (premul_c2 && poly % 3 == 2) v = mulmod_shoup(v, b.inv_qhat[i], b.inv_qhat_s[i], mi.q);
+        if (premul_c2 && poly % 3 == 2) v = mulmod_shoup(v, b.ksk_inv_qhat[i], b.ksk_inv_qhat_s[i], mi.q);
         dst[(size_t)i * n] = v;
     }
 }
@@ -194,7 +194,7 @@ __global__ void __launch_bounds__(256) relin_premul_kernel(const u64 *x3, u64 *p
 {
     const size_t r = blockIdx.x;                 // ct*k + i
     const size_t ct = r / k; const int i = (int)(r % k);
-    const u64 q = mods[i].q, inv = bp->inv_qhat[i], invs = bp->inv_qhat_s[i];
+    const u64 q = mods[i].q, inv = bp->ksk_inv_qhat[i], invs = bp->ksk_inv_qhat_s[i];
     const u64 *src = x3 + ((ct * 3 + 2) * k + i) * (size_t)n;
     u64 *dst = pm + r * (size_t)n;
     for (int s = threadIdx.x; s < n; s += blockDim.x) dst[s] = mulmod_shoup(src[s], inv, invs, q);      // evaluator.cpp:984-985

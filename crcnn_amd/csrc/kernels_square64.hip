@@ -456,7 +456,7 @@ __global__ void __launch_bounds__(256) sq64_floor_kernel(const u64 *dq, const do
         const u64 l1 = P0 + (P1 << 28), t2 = P2 << 56, lo = l1 + t2;
         const u64 hi = (P1 >> 36) + (l1 < P0) + (P2 >> 8) + (lo < t2);
         u64 r = barrett128(lo, hi, mi);
-        if (premul_c2 && poly % 3 == 2) r = mulmod_shoup(r, b.inv_qhat[i], b.inv_qhat_s[i], mi.q);
+        if (premul_c2 && poly % 3 == 2) r = mulmod_shoup(r, b.ksk_inv_qhat[i], b.ksk_inv_qhat_s[i], mi.q);
         dst[(size_t)i * n] = r;
     }
 }

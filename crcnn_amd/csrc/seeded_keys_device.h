@@ -4,6 +4,10 @@
 // Streams, pair numbering and the definition of a first row: chacha.h (CHACHA_DOM_KSK_A / CHACHA_DOM_KSK_E); the host twin is crc_gen_keys_seeded_key /
 // crc_seeded_keys_expand (client.cpp).  One lane = one (key id, pair p, slot pair (s, s + 1)), as the seeded encryptor's lanes (kernels_client.hip): every
 // access to a row is 16 bytes wide except the gathers and scatters through pi_g, which are 8.  A launch serves up to KSK_IDS_MAX ids, which travel by value.
+//
+// Levels (crc_ctx_create_level): a key over the gadget of Q = q_0 .. q_{K-1} serves the level q_0 .. q_{k'-1} as its first P' = Sum_{l < k'} L_l pairs, rows
+// [0, k') of each polynomial.  ksk_restrict_body selects those words of expanded blobs; ksk_expand_level_body is ksk_expand_body writing them directly.  In both
+// KskArgs describes the DESTINATION (k, P, the lanes) and KskLevel the source; KskArgs itself is unchanged, for the callers that fill it field by field.
 #pragma once
 #include "ntt_device.h"
 #include "chacha.h"
@@ -26,6 +30,9 @@ struct KskArgs {
     u64 id[KSK_IDS_MAX];
     ChaChaKey key;                                         // sample kernel: the PRIVATE key; finish and expansion kernels: the PUBLIC seed
 };
+// The source of an expansion into a level, or of a restriction: KskArgs.rows then holds src_P pairs of src_k rows per key, and the streams are named with name_k,
+// the modulus count of the gadget the keys were generated over.  KskArgs.k and .P are the level's: the rows written and the pairs the lanes cover
+struct KskLevel { int name_k, src_k, src_P; };
 
 __device__ __forceinline__ u32 ksk_brev(u32 v)
 {
@@ -126,17 +133,19 @@ __device__ __forceinline__ void ksk_finish_body(const KskArgs &a)
 // ---- expansion: pair p of a blob = (first row p, A) ----------------------------------------------------------------------------------------------------------
 // CONJ = false: the blob K, both rows stored where they were read / generated.  CONJ = true: K' = sigma_g^-1(K), out[i] = K[pi_h(i)] with h = g^-1 -- the lane
 // owns the SOURCE pair (s, s + 1), reads and generates it once, and stores each residue at the one index i with pi_h(i) = s, which is pi_g(s): 16-byte loads,
-// 8-byte scattered stores into a row that the same few workgroups fill, and one keystream block per modulus pair as in the plain form
+// 8-byte scattered stores into a row that the same few workgroups fill, and one keystream block per modulus pair as in the plain form.
+// Into a level (lv.src_k > a.k): the lanes cover the level's P pairs, read rows at the source's strides and stop the block loop at the level's k -- the first k
+// residues of a keystream are a prefix of it, so the words are those of the source's blob, restricted
 template <bool CONJ>
-__device__ __forceinline__ void ksk_expand_body(const KskArgs &a)
+__device__ __forceinline__ void ksk_expand_core(const KskArgs &a, const KskLevel lv)
 {
     int e, p, s;
     if (!ksk_lane(a, e, p, s)) return;
     const u64 id = a.id[e];
-    const u32 n1 = CHACHA_KSK_NONCE1(p, a.dbc, a.k), n2 = ((u32)CHACHA_DOM_KSK_A << 24) | (u32)s;
-    const size_t kn = (size_t)a.k * a.n, m = (size_t)e * a.P + p;
-    const u64 *src = a.rows + m * kn + s;
-    u64 *dst = a.out + m * 2 * kn;
+    const u32 n1 = CHACHA_KSK_NONCE1(p, a.dbc, lv.name_k), n2 = ((u32)CHACHA_DOM_KSK_A << 24) | (u32)s;
+    const size_t kn = (size_t)a.k * a.n;
+    const u64 *src = a.rows + ((size_t)e * lv.src_P + p) * ((size_t)lv.src_k * a.n) + s;
+    u64 *dst = a.out + ((size_t)e * a.P + p) * 2 * kn;
     u32 d0 = (u32)s, d1 = (u32)s + 1u;
     if (CONJ) { const u32 m2 = 2u * (u32)a.n - 1u; const int sh = 32 - a.logn; d0 = ksk_ntt_src((u32)s, (u32)id, m2, sh); d1 = ksk_ntt_src((u32)s + 1u, (u32)id, m2, sh); }
     u32 b[16];
@@ -151,5 +160,25 @@ __device__ __forceinline__ void ksk_expand_body(const KskArgs &a)
         chacha20_block(a.key, (u32)j, (u32)id, n1, n2, b);
         emit(2 * j, b);
         if (2 * j + 1 < a.k) emit(2 * j + 1, b + 8);
+    }
+}
+template <bool CONJ>
+__device__ __forceinline__ void ksk_expand_body(const KskArgs &a) { ksk_expand_core<CONJ>(a, KskLevel{a.k, a.k, a.P}); }
+template <bool CONJ>
+__device__ __forceinline__ void ksk_expand_level_body(const KskArgs &a, const KskLevel &lv) { ksk_expand_core<CONJ>(a, lv); }
+
+// ---- restriction: blobs of a context -> blobs of one of its levels ------------------------------------------------------------------------------------------
+// a.rows: the source blobs [n_ids][src_P][2][src_k][n].  Word (key e, pair p < P, polynomial, row j < k, slot) of the source goes to the same coordinates at the destination's strides; nothing is computed, so the same
+// kernel serves evaluation keys, Galois keys and conjugated blobs (sigma_g^-1 acts inside a row).  16-byte loads and stores, 2 k of each per lane
+__device__ __forceinline__ void ksk_restrict_body(const KskArgs &a, const KskLevel &lv)
+{
+    int e, p, s;
+    if (!ksk_lane(a, e, p, s)) return;
+    const size_t skn = (size_t)lv.src_k * a.n, kn = (size_t)a.k * a.n;
+    const u64 *src = a.rows + ((size_t)e * lv.src_P + p) * 2 * skn + s;
+    u64 *dst = a.out + ((size_t)e * a.P + p) * 2 * kn + s;
+    for (int j = 0; j < a.k; j++) {
+        const ulonglong2 f = ld2(src + (size_t)j * a.n), g = ld2(src + skn + (size_t)j * a.n);
+        st2(dst + (size_t)j * a.n, f.x, f.y); st2(dst + kn + (size_t)j * a.n, g.x, g.y);
     }
 }

@@ -1303,7 +1303,7 @@ int minNoiseBudget(const ciphertext3D &t, size_t *where) { return minAndFirstBud
 // ---- levels: a tensor continues over the first `kept` moduli (crc_mod_switch_forms) --------------------------------------
 // A Level belongs to the parameters it was made under: setParameters() / delParameters() start a new generation, and a level of an older one is refused.
 Level::~Level() { if (ctx) crc_ctx_destroy(ctx); }
-shared_ptr<Level> makeLevel(int kept)
+shared_ptr<Level> makeLevel(int kept, bool derive_keys)
 {
     const int k = K(), n = N();
     if (kept < 1 || kept >= k) throw invalid_argument("makeLevel: a level keeps 1 .. k - 1 of the " + to_string(k) + " coefficient moduli");
@@ -1311,13 +1311,30 @@ shared_ptr<Level> makeLevel(int kept)
     vector<uint64_t> q(k);
     chk(crc_ctx_table(ctx(), "q", q.data(), k), "crc_ctx_table");
     auto L = make_shared<Level>();
-    chk(crc_ctx_create(n, q.data(), kept, g_plain_modulus, crc_ctx_device(ctx()), &L->ctx), "makeLevel: crc_ctx_create");
+    if (derive_keys) chk(crc_ctx_create_level(ctx(), kept, crc_ctx_device(ctx()), &L->ctx), "makeLevel: crc_ctx_create_level");
+    else chk(crc_ctx_create(n, q.data(), kept, g_plain_modulus, crc_ctx_device(ctx()), &L->ctx), "makeLevel: crc_ctx_create");
     if (!crc_mod_switch_supported(ctx(), L->ctx)) throw logic_error("makeLevel: the prefix context is not a level of the parameters");
     L->kept = kept; L->generation = g_generation;
     L->secret_key.assign(secret_key.begin(), secret_key.begin() + (size_t)kept * n);
     for (int p = 0; p < 2; p++) L->public_key.insert(L->public_key.end(), public_key.begin() + (size_t)p * k * n, public_key.begin() + ((size_t)p * k + kept) * n);
     L->d_secret_key = make_shared<DeviceBuffer>(L->secret_key.size() * 8);
     chk(crc_memcpy_h2d(L->ctx, L->d_secret_key->ptr, L->secret_key.data(), L->secret_key.size() * 8, stream()), "crc_memcpy_h2d");
+    if (derive_keys) {
+        // the global keys, which are public material, become the level's on the device: no secret key is read
+        if (!crc_keys_restrict_supported(ctx(), L->ctx)) throw logic_error("makeLevel: the derived context is not a level of the parameters");
+        L->derived = true;
+        auto restricted = [&](const shared_ptr<DeviceBuffer> &from, size_t n_keys, int dbc, const char *what) {
+            auto to = make_shared<DeviceBuffer>(n_keys * crc_evk_words(L->ctx, dbc) * 8 + 16);
+            chk(crc_keys_restrict_dev(ctx(), L->ctx, (const uint64_t *)from->ptr, (int)n_keys, dbc, (uint64_t *)to->ptr, stream()), what);
+            return to;
+        };
+        if (ev_keys16) L->d_ev_keys16 = restricted(ev_keys16, 1, 16, "makeLevel: crc_keys_restrict_dev (evaluation keys)");
+        if (g_galois_keys && !galois_elts.empty()) {
+            L->galois_elts = galois_elts; L->galois_dbc = g_galois_dbc ? g_galois_dbc : 16;
+            L->d_galois_keys = restricted(g_galois_keys, galois_elts.size(), L->galois_dbc, "makeLevel: crc_keys_restrict_dev (Galois keys)");
+            if (g_galois_ckeys) L->d_galois_ckeys = restricted(g_galois_ckeys, galois_elts.size(), L->galois_dbc, "makeLevel: crc_keys_restrict_dev (conjugated keys)");
+        }
+    }
     chk(crc_stream_sync(L->ctx, stream()), "crc_stream_sync");
     return L;
 }
@@ -1380,6 +1397,42 @@ LevelTensor modSwitch(const ciphertext3D &t, const shared_ptr<Level> &to, int ou
     out.buf = make_shared<DeviceBuffer>(t.count() * crc_ct_words(L.ctx, 2) * 8);
     ensure(g_scratch, crc_mod_switch_work_bytes(ctx(), L.ctx, t.count(), 2, t.form, out_form));
     chk(crc_mod_switch_forms(ctx(), L.ctx, t.data(), t.form, t.count(), 2, out.data(), out_form, g_scratch->ptr, stream()), "crc_mod_switch_forms");
+    return out;
+}
+static LevelTensor levelResult(const LevelTensor &t, const Level &L, int out_form)
+{
+    LevelTensor out; out.B = t.B; out.zd = t.zd; out.xd = t.xd; out.yd = t.yd; out.form = out_form; out.level = t.level;
+    out.buf = make_shared<DeviceBuffer>(t.count() * crc_ct_words(L.ctx, 2) * 8);
+    return out;
+}
+LevelTensor squareRelin(const LevelTensor &t, int out_form)
+{
+    const Level &L = levelOf(t, "squareRelin");
+    if (!L.derived || !L.d_ev_keys16) throw logic_error("squareRelin: the level holds no evaluation keys (makeLevel(kept, true))");
+    if ((t.form != CRC_COEFF && t.form != CRC_NTT) || (out_form != CRC_COEFF && out_form != CRC_NTT))
+        throw invalid_argument("squareRelin: ciphertext forms only (CRC_COEFF / CRC_NTT)");
+    LevelTensor out = levelResult(t, L, out_form);
+    ensure(g_scratch, crc_square_relin_work_bytes(L.ctx, t.count(), 16));
+    chk(crc_square_relin_forms(L.ctx, t.data(), t.form, t.count(), (const uint64_t *)L.d_ev_keys16->ptr, 16, out.data(), out_form, g_scratch->ptr, stream()),
+        "crc_square_relin_forms");
+    return out;
+}
+LevelTensor rotateRows(const LevelTensor &t, int steps, int out_form)
+{
+    const Level &L = levelOf(t, "rotateRows");
+    if (!crc_slots_supported(L.ctx)) throw logic_error("encryption parameters do not support batching");
+    if (!L.derived) throw logic_error("rotateRows: the level holds no Galois keys (makeLevel(kept, true))");
+    if ((t.form != CRC_COEFF && t.form != CRC_NTT) || (out_form != CRC_COEFF && out_form != CRC_NTT))
+        throw invalid_argument("rotateRows: ciphertext forms only (CRC_COEFF / CRC_NTT)");
+    const uint64_t g = crc_galois_elt_rows(L.ctx, steps);
+    if (!g) throw invalid_argument("step count too large");
+    const int ne = (int)L.galois_elts.size(), dbc = L.galois_dbc ? L.galois_dbc : 16;
+    int plan[64];
+    if (crc_galois_plan(L.ctx, g, L.galois_elts.data(), ne, plan, 64) < 0) throw invalid_argument("galois key not present");
+    LevelTensor out = levelResult(t, L, out_form);
+    ensure(g_scratch, crc_apply_galois_work_bytes(L.ctx, t.count(), dbc));
+    chk(crc_rotate_rows_forms(L.ctx, t.data(), t.form, t.count(), steps, L.d_galois_keys ? (const uint64_t *)L.d_galois_keys->ptr : nullptr, L.galois_elts.data(), ne,
+                              dbc, out.data(), out_form, g_scratch->ptr, stream()), "crc_rotate_rows_forms");
     return out;
 }
 vector<floatCube> decryptImages(const LevelTensor &t)

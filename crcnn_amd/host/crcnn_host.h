@@ -109,20 +109,28 @@ int minNoiseBudget(const ciphertext3D &t, size_t *where = nullptr);
 // ---- levels: modulus switching (include/crcnn_hip.h, "Modulus switching") ------------------------------------------------------------------------------------
 // A Level is the parameters of setParameters() over the first `kept` coefficient moduli: its own context, and the rows [0, kept) of the secret and the public
 // key, which are valid there as they stand (copies taken by makeLevel: a later assignment to the global keys does not reach a level).  Evaluation and Galois
-// keys do NOT carry over; nothing here generates them, the layers run at the full modulus.  A level belongs to the parameters it was made under: after the
-// next setParameters() / delParameters() every call that is handed it, or a LevelTensor of it, throws std::invalid_argument.
+// keys do NOT carry over to a plain level; nothing here generates them, the layers run at the full modulus.  A level belongs to the parameters it was made
+// under: after the next setParameters() / delParameters() every call that is handed it, or a LevelTensor of it, throws std::invalid_argument.
+// A DERIVED level (makeLevel(kept, true)) is made by crc_ctx_create_level: its key-switching gadget stays that of the parameters, and it holds device copies of
+// the evaluation keys, the installed Galois keys and their conjugated blobs RESTRICTED from the global ones on the device (crc_keys_restrict_dev) -- the secret
+// key is not touched for them, so a server that holds public material only can make one.  squareRelin and rotateRows run there.
 struct Level {
     crc_ctx *ctx = nullptr;                                 // owned
     int kept = 0;
     uint64_t generation = 0;
     std::vector<uint64_t> secret_key, public_key;           // [kept][n] and [2][kept][n], NTT form
     std::shared_ptr<DeviceBuffer> d_secret_key;
+    // a derived level's keys (null / empty on a plain one): what ev_keys16 and the Galois key set were when makeLevel ran
+    bool derived = false;
+    std::shared_ptr<DeviceBuffer> d_ev_keys16, d_galois_keys, d_galois_ckeys;
+    std::vector<uint64_t> galois_elts;
+    int galois_dbc = 0;
     Level() {}
     ~Level();
     Level(const Level &) = delete; Level &operator=(const Level &) = delete;
 };
 // valid after setParameters() / initFromKeys(); std::invalid_argument for `kept` outside 1 .. k - 1
-std::shared_ptr<Level> makeLevel(int kept);
+std::shared_ptr<Level> makeLevel(int kept, bool derive_keys = false);
 // a device tensor of size-2 ciphertexts of a level, [B][zd][xd][yd][2][kept][n] -- what a server sends back at a fraction of the bytes
 struct LevelTensor {
     int B = 0, zd = 0, xd = 0, yd = 0, form = CRC_COEFF;
@@ -140,6 +148,11 @@ struct LevelTensor {
 // crc_mod_switch_forms on the launch stream, work space from the layers' scratch area: a CRC_COEFF or CRC_NTT tensor of the global context -> the level `to`, in
 // out_form (CRC_COEFF / CRC_NTT).  Asynchronous.  The plaintexts are unchanged; the budget is at least floor(-log2(2^-b + t (n + 1) / q_to)) - 2 bits
 LevelTensor modSwitch(const ciphertext3D &t, const std::shared_ptr<Level> &to, int out_form = CRC_COEFF);
+// The two operations that make a DERIVED level worth visiting, on the launch stream with the level's restricted keys: relinearize(square(x)) elementwise, and
+// rotateRows' slot rotation (the planner's steps over the level's Galois key set).  CRC_COEFF or CRC_NTT in, out_form out.  std::logic_error for a level that
+// was not made with derive_keys (it has no keys) and, for rotateRows, parameters without batching; std::invalid_argument as their ciphertext3D namesakes
+LevelTensor squareRelin(const LevelTensor &t, int out_form = CRC_COEFF);
+LevelTensor rotateRows(const LevelTensor &t, int steps, int out_form = CRC_COEFF);
 // the client side at a level, under the level's secret-key rows: as their ciphertext3D namesakes
 std::vector<floatCube> decryptImages(const LevelTensor &t);
 std::vector<std::vector<int64_t>> decryptSlots(const LevelTensor &t, int S);

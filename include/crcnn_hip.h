@@ -110,7 +110,9 @@ size_t crc_evk_words(const crc_ctx *ctx, int dbc);     /* words of an evaluation
                                                           takes a dbc refuses those with CRC_ERR_INVALID_ARGUMENT, every size query gives 0) */
 /* named host-side table read-out (tests): "root","const_ratio","delta","upper_half_increment","bsk","bsk_root",
  * "root_powers:<i>","inv_root_powers_div_two:<i>", "slots_root", "slots_index_map" (slot batching, below), "f64_primes" (the two fp64 primes of relinearisation's key switching), "sq64_primes" (the fp64 primes that
- * carry the square's auxiliary base: B' = all but the last, m_sk' = the last; empty when the parameters do not fit twelve of them); returns word count */
+ * carry the square's auxiliary base: B' = all but the last, m_sk' = the last; empty when the parameters do not fit twelve of them), "key_q" (the moduli of the
+ * key-switching gadget: q, or an ancestor's list on a level of crc_ctx_create_level), "inv_qhat" ((q/q_i)^-1 mod q_i) and "ksk_inv_qhat" ((Q_key/q_i)^-1 mod
+ * q_i: what a polynomial is multiplied by before a key switch cuts its digits; equal to "inv_qhat" except on such a level); returns word count */
 int  crc_ctx_table(const crc_ctx *ctx, const char *name, uint64_t *h_out, int cap);
 /* Tuning switches of tools/ and the tests (none is needed for normal use).  The engine reads its environment (CRC_MFMA_VARIANT, CRC_CONV1_PASS_BYTES, ...)
  * exactly
@@ -967,7 +969,8 @@ int crc_seeded_keys_load(const crc_ctx *ctx, const void *buf, size_t bytes, uint
  *
  * What carries over to `to`: the per-modulus tables are those of `from` (same primes, same minimal roots), so the rows [0, k') of an NTT-form secret key
  * ([k][n]), of each public-key polynomial ([2][k][n]) and of an NTT-form plaintext row are valid there as they stand.  Evaluation keys and Galois keys do NOT
- * carry over (they hold (q / q_i) factors): generate them on `to` with crc_gen_evk* / crc_gen_galois_keys* from the prefix secret-key rows.
+ * carry over (they hold (q / q_i) factors): generate them on `to` with crc_gen_evk* / crc_gen_galois_keys* from the prefix secret-key rows -- or, without the
+ * secret key, make `to` with crc_ctx_create_level and restrict the keys of `from` (below: "Key-switching keys for a lower level").
  *
  *   crc_mod_switch_supported   1 if `to` is a proper prefix of `from` (1 <= k' < k, the same moduli in the same order, the same n and t), else 0
  *   crc_mod_switch_forms       d_in [count][size][k][n] of `from` in in_form -> d_out [count][size][k'][n] of `to` in out_form; size 2 or 3; forms CRC_COEFF or
@@ -986,6 +989,44 @@ size_t crc_mod_switch_work_bytes(const crc_ctx *from, const crc_ctx *to, size_t 
 int    crc_mod_switch_forms(crc_ctx *from, const crc_ctx *to, const uint64_t *d_in, int in_form, size_t count, int size, uint64_t *d_out, int out_form,
                             void *d_work, void *stream);
 int    crc_mod_switch(const crc_ctx *from, const crc_ctx *to, const uint64_t *h_in, int in_form, size_t count, int size, uint64_t *h_out, int out_form);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Key-switching keys for a lower level WITHOUT the secret key: the upper level's keys, which are public, become the level's keys.
+ *
+ * Pair p = (l, d) of a key blob over Q = q_0 .. q_{k-1} is  first = -(A s + e) + E w,  second = A,  E = (Q / q_l) 2^(dbc d) mod Q, which is non-zero in
+ * residue row l alone.  With q_B = q_0 .. q_{k'-1} dividing Q the identity holds mod q_B as it stands: pairs with l >= k' hold E = 0 and drop out, the others are
+ * the first P' = Sum_{l < k'} L_l pairs, and rows [0, k') of their polynomials are a valid key at the lower level -- for the gadget (Q / q_l) 2^(dbc d), not the
+ * level's own (q_B / q_l) 2^(dbc d).  The key switch therefore cuts digit l from [c (Q / q_l)^-1]_{q_l}; nothing else in it changes, and the noise term
+ * Sum digit e is that of a key generated at the level (same e, same digit width, P' pairs).
+ *
+ *   crc_ctx_create_level   a context over the first `kept` moduli of `parent` (1 <= kept < k, else CRC_ERR_PARAMETERS; same n and t) whose key-switching gadget is
+ *                          the parent's; a level of a level keeps the top one.  Everything else (tables, BEHZ, decryption, budget) is what crc_ctx_create gives
+ *                          for the prefix, so crc_mod_switch_supported(parent, level) holds as for a plain prefix context.  Every key switch on it
+ *                          (crc_square_relin*, crc_relinearize*, the Galois entry points, hoisted forms included) takes keys RESTRICTED from the parent's
+ *   crc_ctx_key_moduli     the modulus count of the context's gadget: k on a context of crc_ctx_create, the top ancestor's k on a level
+ *   Key GENERATION is refused on a level with an inherited gadget: crc_gen_evk*, crc_gen_galois_keys* and crc_gen_keys_seeded* (host and device) return
+ *   CRC_ERR_PARAMETERS and write nothing.  The stream names of the seeded keys carry k but not the gadget: two levels of equal k' under different parents would
+ *   put equal A and equal e around different known factors, and the difference of the two keys is a multiple of the secret key.
+ *
+ *   crc_keys_restrict_supported   1 if `to` is a level of `from` for key material: the same n, the same gadget moduli, to's moduli a proper prefix of from's
+ *   crc_keys_restrict_dev  d_keys [n_keys][crc_evk_words(from, dbc)] -> d_out [n_keys][crc_evk_words(to, dbc)]: word (key, pair p < P', polynomial, row j < k',
+ *                          slot) goes to the same coordinates at to's strides.  One copy kernel on from's device, asynchronous on `stream`; evaluation keys,
+ *                          Galois keys and conjugated blobs (crc_galois_conjugate_keys: the conjugation acts inside a row) alike
+ *   crc_keys_restrict      the host twin (any contexts)
+ *   crc_seeded_keys_expand_level[_dev]   from's seeded rows [n_ids][P][k][n] -> to's blobs [n_ids][crc_evk_words(to)], bit for bit crc_keys_restrict of
+ *                          crc_seeded_keys_expand(from, ...); from's blobs are never written
+ * CRC_ERR_INVALID_ARGUMENT, and nothing written, where crc_keys_restrict_supported is 0, for a bad dbc, a null or (device) not 16-byte aligned pointer and
+ * where input and output overlap; n_keys = 0 is CRC_OK.
+ * ------------------------------------------------------------------------------------------------------------- */
+int crc_ctx_create_level(const crc_ctx *parent, int kept, int device, crc_ctx **out);
+int crc_ctx_key_moduli(const crc_ctx *ctx);
+int crc_keys_restrict_supported(const crc_ctx *from, const crc_ctx *to);
+int crc_keys_restrict(const crc_ctx *from, const crc_ctx *to, const uint64_t *h_keys, int n_keys, int dbc, uint64_t *h_out);
+int crc_keys_restrict_dev(crc_ctx *from, const crc_ctx *to, const uint64_t *d_keys, int n_keys, int dbc, uint64_t *d_out, void *stream);
+int crc_seeded_keys_expand_level(const crc_ctx *from, const crc_ctx *to, const uint64_t *h_first, const uint64_t *ids, int n_ids, int dbc, const uint8_t *h_seed,
+                                 int conjugate, uint64_t *h_out);
+int crc_seeded_keys_expand_level_dev(crc_ctx *from, const crc_ctx *to, const uint64_t *d_first, const uint64_t *ids /*host*/, int n_ids, int dbc,
+                                     const uint8_t *h_seed, int conjugate, uint64_t *d_out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * multi-GPU (SURVEY 8e / 8b `crc_broadcast_weights`).  The reference has no analogue: its only parallelism is the
