@@ -208,6 +208,8 @@ void h_ntt_fwd(const HostNtt &T, u64 *a, int n);      // canonical in/out
 void h_ntt_inv(const HostNtt &T, u64 *a, int n);
 ModParams make_mod(u64 q, bool no_fold = false);
 int  evk_digits(u64 q, int dbc);
+// D = Sum_i evk_digits(q_i, dbc): the digit polynomials of one key switch (0 for a dbc evk_digits refuses)
+static inline int relin_digit_count(const crc_ctx *c, int dbc) { int D = 0; for (int i = 0; i < c->k; i++) D += evk_digits(c->q[i], dbc); return D; }
 // the gadget of a key-switching key at digit width dbc: L[l] = evk_digits(q_l, dbc) and qhat[l] = (Q_key / q_l) mod q_l for l < k, Q_key the product of c->key_q (q
 // itself except on a level of crc_ctx_create_level); returns P = Sum L[l], the pairs of a blob (pair p = Sum_{l' < l} L[l'] + d has the factor qhat[l] 2^(dbc d)
 // mod q_l).  One definition for the host twin and the device launchers of the seeded keys

@@ -19,8 +19,7 @@ int k_ntt_ct_head_add(crc_ctx *c, const u64 *src, int src_size, u64 *dst, size_t
 int k_spread_ntt(crc_ctx *c, const u64 *src, size_t items, u64 *dst, hipStream_t st);
 int k_digit_ntt(crc_ctx *c, const u64 *src, int src_size, int src_poly, size_t count, int D, const unsigned char *dig_i, const unsigned char *dig_shift, int dbc,
                 u64 *dst, hipStream_t st, int pack_out = 0);
-int k_square_intt(crc_ctx *c, const u64 *src, u64 *dst, size_t count, bool bsk, hipStream_t st, const u64 *opt_mul = nullptr, bool *applied = nullptr);
-int k_multiply_intt(crc_ctx *c, const u64 *x, const u64 *y, u64 *dst, size_t count, bool bsk, hipStream_t st, const u64 *opt_mul = nullptr, bool *applied = nullptr);
+int k_product_intt(crc_ctx *c, const u64 *x, const u64 *y, u64 *dst, size_t count, bool bsk, hipStream_t st, const u64 *opt_mul = nullptr, bool *applied = nullptr);     // y null: the square of x
 int k_ntt_ct_inv_scaled(crc_ctx *c, const u64 *src, u64 *dst, size_t count, int size, const u64 *mul, const u64 *mul_s, hipStream_t st);
 int k_plain_ntt(crc_ctx *c, const u64 *d_plain, size_t count, int mode, bool do_ntt, u64 *d_out, hipStream_t st);
 int k_plain_expand(crc_ctx *c, const u64 *d_compact, size_t count, u64 *d_plain, hipStream_t st);
@@ -32,7 +31,25 @@ int k_mac(crc_ctx *c, const u64 *x, const u64 *w, u64 *y, const int *d_xoff, con
           const u64 *bias_ntt, hipStream_t st, int xp = 0, int wp = 0, int yp = 0);
 int k_pack28(crc_ctx *c, u64 *rows, size_t nrows, bool unpack, hipStream_t st);
 int k_conv_offsets(crc_ctx *c, int *xoff, int *toff, unsigned *toffw, const LayerShape &s, hipStream_t st);
-size_t k_square_work_words(const crc_ctx *c, size_t cnt);
+// The work space of a ciphertext product (the square: one input, the multiply: two) whose auxiliary base has `rows` rows per polynomial: per input its NTT form
+// over q and its lifted rows (all QN before all LB: the lifted rows of both inputs are one array), then the three product polynomials in both bases.  Filled
+// on the caller's work space it gives the pointers, on a null base it only counts (work_arena.h's idea in plain word offsets: no rounding)
+struct ProductWork {
+    u64 *QN[2], *LB[2], *DQ, *DB;         // QN[h] [cnt][2][k][n] | LB[h] [cnt][2][rows][n] | DQ [cnt][3][k][n] | DB [cnt][3][rows][n]
+    size_t words;
+};
+static inline ProductWork product_work(const crc_ctx *c, size_t cnt, int inputs, size_t rows, u64 *work = nullptr)
+{
+    ProductWork w{};
+    const size_t n = c->n, k = c->k;
+    auto take = [&](size_t words) { u64 *p = work ? work + w.words : nullptr; w.words += words; return p; };
+    for (int h = 0; h < inputs; h++) w.QN[h] = take(cnt * 2 * k * n);
+    for (int h = 0; h < inputs; h++) w.LB[h] = take(cnt * 2 * rows * n);
+    w.DQ = take(cnt * 3 * k * n);
+    w.DB = take(cnt * 3 * rows * n);
+    return w;
+}
+size_t k_square_work_words(const crc_ctx *c, size_t cnt);            // product_work counted with the rows of the larger auxiliary base (61-bit or fp64)
 size_t k_multiply_work_words(const crc_ctx *c, size_t cnt);          // the product of two ciphertexts: four input polynomials per pair
 size_t k_relin_work_words(const crc_ctx *c, size_t cnt, int dbc);
 size_t k_relin_keys_words(const crc_ctx *c, int dbc);

@@ -877,26 +877,15 @@ int k_digit_ntt(crc_ctx *c, const u64 *src, int src_size, int src_poly, size_t c
     return ntt_launch(c, false, a, count * D * c->k, st);
 }
 
-// inverse NTT of the three dyadic products (a^2, 2ab, b^2) of size-2 NTT-form ciphertexts src [count][2][K][n] -> dst [count][3][K][n] (coefficient form),
-// K = k moduli of q or kb moduli of Bsk; the products are formed while the row is loaded (NttArgs prologue 4)
+// inverse NTT of the three dyadic products of size-2 NTT-form ciphertexts [count][2][K][n] -> dst [count][3][K][n] (coefficient form), K = k moduli of q or kb
+// moduli of Bsk; the products are formed while the row is loaded.  y null: the square (a^2, 2ab, b^2) of x = (a, b), which reads two rows (NttArgs prologue 4);
+// otherwise the tensor product (ac, ad + bc, bd) of x = (a, b) and y = (c, d) (prologue 6: prologue 4 with a second source, the pointer fma_k)
 // opt_mul (per modulus, may be null): constants the consumer of dst would multiply the rows by first thing; *applied says whether the transform took them into
 // its closing multiplication (the kernels that end in one: ntt_rows_wave_kernel's unscaled inverse) or left the rows as they are
-int k_square_intt(crc_ctx *c, const u64 *src, u64 *dst, size_t count, bool bsk, hipStream_t st, const u64 *opt_mul, bool *applied)
+int k_product_intt(crc_ctx *c, const u64 *x, const u64 *y, u64 *dst, size_t count, bool bsk, hipStream_t st, const u64 *opt_mul, bool *applied)
 {
     NttArgs a{};
-    a.src = src; a.dst = dst; a.mod_base = bsk ? c->k : 0; a.mod_count = bsk ? c->kb : c->k; a.prologue = 4;
-    a.rows_per_ct = 3 * a.mod_count; a.add_group = 1; a.pairs = count * a.mod_count;
-    if (opt_mul) { a.opt_mul = 1; for (int i = 0; i < a.mod_count; i++) a.post_mul[i] = opt_mul[i]; }
-    const int rc = ntt_launch(c, true, a, count * 3 * a.mod_count, st);
-    if (applied) *applied = a.opt_mul == 2;
-    return rc;
-}
-
-// the same for the tensor product (ac, ad + bc, bd) of two size-2 NTT-form ciphertext arrays x = (a, b), y = (c, d) (NttArgs prologue 6)
-int k_multiply_intt(crc_ctx *c, const u64 *x, const u64 *y, u64 *dst, size_t count, bool bsk, hipStream_t st, const u64 *opt_mul, bool *applied)
-{
-    NttArgs a{};
-    a.src = x; a.fma_k = y; a.dst = dst; a.mod_base = bsk ? c->k : 0; a.mod_count = bsk ? c->kb : c->k; a.prologue = 6;
+    a.src = x; a.fma_k = y; a.dst = dst; a.mod_base = bsk ? c->k : 0; a.mod_count = bsk ? c->kb : c->k; a.prologue = y ? 6 : 4;
     a.rows_per_ct = 3 * a.mod_count; a.add_group = 1; a.pairs = count * a.mod_count;
     if (opt_mul) { a.opt_mul = 1; for (int i = 0; i < a.mod_count; i++) a.post_mul[i] = opt_mul[i]; }
     const int rc = ntt_launch(c, true, a, count * 3 * a.mod_count, st);

@@ -16,6 +16,7 @@
 #include "ntt_device.h"
 
 #include "ntt_f64.h"
+#include "f64_launch.h"
 
 
 struct Relin64Tab { unsigned char L[CRC_MAXK], g0[CRC_MAXK]; };
@@ -709,11 +710,11 @@ __global__ void __launch_bounds__(CS == 2 ? 256 : CS == 3 ? 512 : 1024, 4) relin
 // ---- host side ----------------------------------------------------------------------------------------------------------------------------------------------
 // can this context / key set take the fp64 path?  2 |R_j| <= n D 2^dbc q_max must stay below p_0 p_1 / 2 (a factor 2 of slack for the floating CRT), the row
 // must fit the LDS image the transforms work on, and at most 48 products may be summed lazily
+static int relin64_qbits(const crc_ctx *c) { int b = 0; for (int i = 0; i < c->k; i++) if ((int)c->tabs[i].m.bits > b) b = c->tabs[i].m.bits; return b; }
 bool k_relin64_supported(const crc_ctx *c, int dbc)
 {
     if (c->n < 64 || c->n > 16384 || dbc < 1 || dbc > 32) return false;
-    int D = 0, qbits = 0;
-    for (int i = 0; i < c->k; i++) { D += evk_digits(c->q[i], dbc); if ((int)c->tabs[i].m.bits > qbits) qbits = c->tabs[i].m.bits; }
+    const int D = relin_digit_count(c, dbc), qbits = relin64_qbits(c);
     if (D > 48) return false;
     int dbits = 0; while ((1 << dbits) < D) dbits++;
     // log2(n D 2^dbc q_max) <= logn + dbits + dbc + qbits  must be <= 2 * 47 - 2 (p_m > 2^46.99)
@@ -723,9 +724,8 @@ bool k_relin64_supported(const crc_ctx *c, int dbc)
 bool k_relin64_pool_supported(const crc_ctx *c, int dbc, int window)
 {
     if (!k_relin64_supported(c, dbc) || window < 1 || window > 64 || dbc > 20) return false;
-    int D = 0, qbits = 0;
-    for (int i = 0; i < c->k; i++) { const int L = evk_digits(c->q[i], dbc); if (L > 4) return false; D += L;
-        if ((int)c->tabs[i].m.bits > qbits) qbits = c->tabs[i].m.bits; }
+    for (int i = 0; i < c->k; i++) if (evk_digits(c->q[i], dbc) > 4) return false;
+    const int D = relin_digit_count(c, dbc), qbits = relin64_qbits(c);
     int dbits = 0; while ((1 << dbits) < D) dbits++;
     int wbits = 0; while ((1 << wbits) < window) wbits++;
     // 2 |R| <= n D W 2^dbc q_max <= 2^92 leaves |R| <= 2^91 < p_0 p_1 / 2 / 3.9: the CRT's t = (a1 - a0) p_0^-1 mod p_1 stays below p_1 / 3.9 in magnitude,
@@ -733,26 +733,26 @@ bool k_relin64_pool_supported(const crc_ctx *c, int dbc, int window)
     return c->logn + dbits + wbits + dbc + qbits <= 2 * CRC_F64_PRIME_BITS - 2;
 }
 size_t k_relin64_keys_words(const crc_ctx *c, int dbc) { return (size_t)CRC_NF64 * crc_evk_words(c, dbc); }
-// scratch words: E [cnt][D][2][n] + A [cnt][2k][2][n] (+ PM [cnt][k][n] when the caller's c2 is not premultiplied); the key preparation borrows the same space
+// The work space of K1 to K3 for cnt ciphertexts, in words from its start: the D digit polynomials E [cnt][D][2][n], behind them the inner products
+// A [cnt][2k][2][n] of one key, and one more A, a_stride further, per further key applied to the same E.  Filled on the caller's work space it gives the
+// pointers, on a null base it only counts
+struct Relin64Work { int D; double *E, *A; size_t a_stride, words; };
+static Relin64Work relin64_work(const crc_ctx *c, size_t cnt, int dbc, u64 *work = nullptr)
+{
+    Relin64Work w{};
+    w.D = relin_digit_count(c, dbc);
+    const size_t e = cnt * w.D * CRC_NF64 * c->n;
+    w.a_stride = cnt * 2 * c->k * CRC_NF64 * c->n;
+    w.E = reinterpret_cast<double *>(work); w.A = work ? w.E + e : nullptr;
+    w.words = e + w.a_stride;
+    return w;
+}
+// scratch words: PM [cnt][k][n] in front of relin64_work where the caller's c2 is not premultiplied (k_relinearize); the key preparation borrows the same space
 size_t k_relin64_work_words(const crc_ctx *c, size_t cnt, int dbc)
 {
-    size_t D = 0; for (int i = 0; i < c->k; i++) D += evk_digits(c->q[i], dbc);
-    const size_t n = c->n, k = c->k;
-    const size_t run = cnt * n * (k + CRC_NF64 * D + CRC_NF64 * 2 * k), prep = crc_evk_words(c, dbc);
+    const size_t run = cnt * c->n * c->k + relin64_work(c, cnt, dbc).words, prep = crc_evk_words(c, dbc);
     return run > prep ? run : prep;
 }
-
-// threads per workgroup for passes of 2^RB values per thread
-static int f64_threads(const crc_ctx *c, int RB) { int nt = c->n >> RB; if (nt < 64) nt = 64; if (nt > (RB == 5 ? 512 : 1024)) nt = RB == 5 ? 512 : 1024;
-    return nt; }
-// 3 stages (8 values per thread) per LDS pass by default: measured on (8192, 3) the digit kernel runs 0.90 / 1.08 / 1.34 us per ciphertext with 3 / 4 / 5 --
-// the wider passes save LDS round trips and barriers but cost occupancy (76 / 134 registers), and the kernel is bound by instruction issue, not by LDS
-// (profiles/r03_square_relin.txt)
-static int f64_radix(const crc_ctx *c) { const int r = c->tune.f64_radix; return r >= 3 && r <= 5 ? r : 3; }
-// threads of the kernels that keep a row in registers
-// (16 points per thread at radix 8 and 16, 32 at radix 32: n / 16 threads, at least a wave, at most 1024)
-static int f64_hold_threads(const crc_ctx *c, int RB) { int nt = c->n >> (RB == 5 ? 5 : 4); if (nt < 64) nt = 64;
-    if (nt > (RB == 5 ? 512 : 1024)) nt = RB == 5 ? 512 : 1024; return nt; }
 
 // kp: k_relin64_keys_words; scratch: crc_evk_words (k_relin64_work_words covers it)
 int k_relin64_prepare_keys(crc_ctx *c, const u64 *evk, int dbc, u64 *kp, u64 *scratch, hipStream_t st)
@@ -764,14 +764,9 @@ int k_relin64_prepare_keys(crc_ctx *c, const u64 *evk, int dbc, u64 *kp, u64 *sc
     HIPCHK(hipGetLastError());
     int rc;
     if ((rc = k_ntt_ct(c, true, scratch, scratch, rows / c->k, 1, false, st, nullptr, 0, 0, 0))) return rc;
-    const size_t lds = (size_t)c->n * 8;
     const int RB = f64_radix(c);
-    auto kern = RB == 3 ? relin_keys_f64_kernel<3> : RB == 4 ? relin_keys_f64_kernel<4> : relin_keys_f64_kernel<5>;
-    { const int r2 = crc_ctx_ensure_lds(c, (const void *)kern, lds); if (r2) return r2; }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(rows * CRC_NF64)), dim3(f64_threads(c, RB)), lds, st, scratch, Kf, c->d_mods, c->d_f64_rp, c->f64, c->n, c->logn,
-        c->k);
-    HIPCHK(hipGetLastError());
-    return CRC_OK;
+    return f64_launch(c, RB == 3 ? relin_keys_f64_kernel<3> : RB == 4 ? relin_keys_f64_kernel<4> : relin_keys_f64_kernel<5>, rows * CRC_NF64, f64_threads(c, RB), st,
+                      scratch, Kf, c->d_mods, c->d_f64_rp, c->f64, c->n, c->logn, c->k);
 }
 
 template <int K, int BIGCT = 4>
@@ -802,27 +797,22 @@ static int relin64_mac2(crc_ctx *c, const double *E, const double *Kf0, const do
     return CRC_OK;
 }
 
-// the wave-local transforms (one workgroup barrier per transform) serve the two rings the bench configurations use; CRC_F64_WAVE=0 keeps the round-4 kernels
-// (bit 1: the digit kernel, bit 2: K3.  Measured, same box: K1 -17 % at n = 8192, -16 % at 16384; K3 +3 % / +14 % in its first form, which parked the first
-// prime's result in scratch, -0.3 % / -1.5 % of the whole sequence now -- its 64-bit forward transform is untouched: profiles/r05_square_pool_wave_local_*.txt)
-static bool f64_wave_path(const crc_ctx *c, int RB, int bit)
-{
-    if (RB != 3 || (c->logn != 12 && c->logn != 13 && c->logn != 14)) return false;      // (n = 4096 since round 6: CS = 2)
-    const int sel = c->tune.f64_wave < 0 ? 7 : c->tune.f64_wave;
-    return (sel >> bit) & 1;
-}
-
 // whether K3 can carry a polynomial activation's tail (tune.poly_tail = 0): at the default radix.  The radix-16 / -32 variants of the tuning switch "f64_radix"
 // would spill with it, so those take poly2_tail_kernel
 bool k_relin64_poly_fused(const crc_ctx *c) { return c->tune.poly_tail == 0 && f64_radix(c) == 3; }
 
+static const PoolGeom NO_POOL{0, 0, 0, 0, 0, 0, 0, 0};        // what a kernel that can pool takes when the call does not (xf = 0)
+
+// K3 at one transform radix (RB stages per LDS pass, NPT points per thread of the kernel that holds a row)
 template <int RB, int NPT>
-static int relin64_tail(crc_ctx *c, const double *A, const u64 *x3, int add_size, u64 *y, size_t cnt, bool out_ntt, hipStream_t st, const u64 *mul,
+static int relin64_tail_rb(crc_ctx *c, const double *A, const u64 *x3, int add_size, u64 *y, size_t cnt, bool out_ntt, hipStream_t st, const u64 *mul,
     const PoolGeom *pool, const PolyTail *poly)
 {
     bool lazy = true;
     for (int i = 0; i < c->k; i++) if (c->tabs[i].m.bits > 57 || c->tabs[i].m.bits < 45) lazy = false;
-    const size_t lds = (size_t)c->n * 8;
+    const size_t blocks = cnt * 2 * c->k;
+    const ulonglong2 *Wq = reinterpret_cast<const ulonglong2 *>(c->d_rp);
+    const PoolGeom pg = pool ? *pool : NO_POOL;
     // (a polynomial tail goes through relin_inv_crt_kernel at every ring: with it the wave-local kernels spill 4 / 14 / 24 registers per lane at n = 4096 / 8192 /
     // 16384, and what they gain over this kernel is 0.3 to 1.5 % of the sequence)
     if (!poly && f64_wave_path(c, RB, 2)) {
@@ -831,48 +821,46 @@ static int relin64_tail(crc_ctx *c, const double *A, const u64 *x3, int add_size
 #define K3W(A, B, C) (cs == 2 ? relin_inv_crt_wave_kernel<2, A, B, C> : cs == 3 ? relin_inv_crt_wave_kernel<3, A, B, C> : relin_inv_crt_wave_kernel<4, A, B, C>)
         auto kern = !out_ntt ? K3W(false, false, false) : lazy ? (u64w ? K3W(true, true, true) : K3W(true, true, false)) : K3W(true, false, false);
 #undef K3W
-        { const int rc = crc_ctx_ensure_lds(c, (const void *)kern, lds); if (rc) return rc; }
-        hipLaunchKernelGGL(kern, dim3((unsigned)(cnt * 2 * c->k)), dim3(c->n / 16), lds, st, A, x3, add_size, y, c->d_mods, c->d_f64_irp,
-                           reinterpret_cast<const ulonglong2 *>(c->d_rp), c->f64, c->n, c->logn, c->k, mul, pool ? *pool : PoolGeom{0, 0, 0, 0, 0, 0, 0, 0});
-        HIPCHK(hipGetLastError());
-        return CRC_OK;
+        return f64_launch(c, kern, blocks, c->n / 16, st, A, x3, add_size, y, c->d_mods, c->d_f64_irp, Wq, c->f64, c->n, c->logn, c->k, mul, pg);
     }
+    const int hold = f64_hold_threads(c, RB);
     auto kern = !out_ntt ? relin_inv_crt_kernel<RB, NPT, false, false> : lazy ? relin_inv_crt_kernel<RB, NPT, true, true> : relin_inv_crt_kernel<RB, NPT,
         true, false>;
     if constexpr (RB != 3) { if (poly) return CRC_ERR_UNSUPPORTED; }       // (k_relin64_poly_fused: the wider passes have no registers left for the tail)
-    else if (poly) {
-        auto kp = lazy ? relin_inv_crt_kernel<RB, NPT, true, true, PolyTail> : relin_inv_crt_kernel<RB, NPT, true, false, PolyTail>;
-        { const int rc = crc_ctx_ensure_lds(c, (const void *)kp, lds); if (rc) return rc; }
-        hipLaunchKernelGGL(kp, dim3((unsigned)(cnt * 2 * c->k)), dim3(f64_hold_threads(c, RB)), lds, st, A, x3, add_size, y, c->d_mods, c->d_f64_irp,
-                           reinterpret_cast<const ulonglong2 *>(c->d_rp), c->f64, c->n, c->logn, c->k, mul, pool ? *pool : PoolGeom{0, 0, 0, 0, 0, 0, 0, 0}, *poly);
-        HIPCHK(hipGetLastError());
-        return CRC_OK;
-    }
-    { const int rc = crc_ctx_ensure_lds(c, (const void *)kern, lds); if (rc) return rc; }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(cnt * 2 * c->k)), dim3(f64_hold_threads(c, RB)), lds, st, A, x3, add_size, y, c->d_mods, c->d_f64_irp,
-                       reinterpret_cast<const ulonglong2 *>(c->d_rp), c->f64, c->n, c->logn, c->k, mul, pool ? *pool : PoolGeom{0, 0, 0, 0, 0, 0, 0, 0});
-    HIPCHK(hipGetLastError());
-    return CRC_OK;
+    else if (poly)
+        return f64_launch(c, lazy ? relin_inv_crt_kernel<RB, NPT, true, true, PolyTail> : relin_inv_crt_kernel<RB, NPT, true, false, PolyTail>, blocks, hold, st, A, x3,
+                          add_size, y, c->d_mods, c->d_f64_irp, Wq, c->f64, c->n, c->logn, c->k, mul, pg, *poly);
+    return f64_launch(c, kern, blocks, hold, st, A, x3, add_size, y, c->d_mods, c->d_f64_irp, Wq, c->f64, c->n, c->logn, c->k, mul, pg);
 }
+// K3 (CRT lift, sum with (c0, c1), result form) of the inner products A at the radix in use.  (Defined behind k_relin64_from_digits, its first caller: the
+// compiler emits the kernels in the order in which the launchers first name them, and this keeps K2's in front of K3's as they have always been)
+static int relin64_tail(crc_ctx *c, const double *A, const u64 *x3, int add_size, u64 *y, size_t cnt, bool out_ntt, hipStream_t st, const u64 *mul = nullptr,
+    const PoolGeom *pool = nullptr, const PolyTail *poly = nullptr);
+// K2's launcher for the context's k: rc = MAC(k), MAC a macro that names the launcher's instantiation for a literal k; leaves the function where k has none
+#define RELIN64_MAC_BY_K(rc, MAC) \
+    switch (c->k) { \
+    case 1: rc = MAC(1); break; case 2: rc = MAC(2); break; case 3: rc = MAC(3); break; case 4: rc = MAC(4); break; \
+    case 5: rc = MAC(5); break; case 6: rc = MAC(6); break; case 7: rc = MAC(7); break; case 8: rc = MAC(8); break; \
+    default: return CRC_ERR_UNSUPPORTED; \
+    }
 
 // The key switch in two halves.  K1 (k_relin64_digits): the digit polynomials of c2 (q/q_i)^-1, transformed over the fp64 primes, into E at the front of `work`.
 // K2 + K3 (k_relin64_from_digits): the inner products of an E that is already there with one prepared key, the CRT lift, and the sum with (c0, c1).  E depends
 // on the ciphertext alone, so several keys can be applied to one K1 (the hoisted rotations); k_relinearize64 is the two in a row.
 // src / src_size / src_poly: where c2 (q/q_i)^-1 lives; x3 / add_size: the ciphertexts whose (c0, c1) are added; kp: the keys as k_relin64_prepare_keys left
-// them; work: cnt n (2 D + 4 k) words
+// them; work: relin64_work
 int k_relin64_digits(crc_ctx *c, const u64 *src, int src_size, int src_poly, size_t cnt, int dbc, u64 *work, hipStream_t st, const PoolGeom *pool)
 {
     if (cnt == 0) return CRC_OK;
     if (!k_relin64_supported(c, dbc)) return CRC_ERR_UNSUPPORTED;
     // (cnt counts POOLED ciphertexts then; src holds the unpooled ones)
     if (pool && !k_relin64_pool_supported(c, dbc, pool->xf * pool->yf)) return CRC_ERR_UNSUPPORTED;
-    const size_t n = c->n, k = c->k;
-    Relin64Tab tab{};
-    int D = 0;
-    for (int i = 0; i < c->k; i++) { tab.L[i] = (unsigned char)evk_digits(c->q[i], dbc); tab.g0[i] = (unsigned char)D; D += tab.L[i]; }
-    double *E = reinterpret_cast<double *>(work);
-    const size_t lds = n * 8;
-    const int RB = f64_radix(c);
+    const int D = relin_digit_count(c, dbc);
+    Relin64Tab tab{};                                              // digits of residue i and the index of its first one
+    for (int i = 0, g = 0; i < c->k; i++) { tab.L[i] = (unsigned char)evk_digits(c->q[i], dbc); tab.g0[i] = (unsigned char)g; g += tab.L[i]; }
+    double *E = relin64_work(c, cnt, dbc, work).E;
+    const size_t blocks = cnt * c->k;
+    const int RB = f64_radix(c), hold = f64_hold_threads(c, RB), cs = c->logn - 10;
     if (pool) {
         // all digit sums of a value in one word when they fit: fields of F = dbc + log2 W bits, the top digit of residue i has bits_i - (L_i - 1) dbc (+ log2
         // W) bits
@@ -881,35 +869,19 @@ int k_relin64_digits(crc_ctx *c, const u64 *src, int src_size, int src_poly, siz
         bool one = true;
         for (int i = 0; i < c->k; i++) { const int L = tab.L[i]; if ((L - 1) * F + ((int)c->tabs[i].m.bits - (L - 1) * dbc + wbits) > 64 || F > 32) one =
             false; }
-        if (one && f64_wave_path(c, RB, 1)) {
-            auto kw = c->logn == 12 ? relin_digits_wave_kernel<2, true> : c->logn == 13 ? relin_digits_wave_kernel<3, true> : relin_digits_wave_kernel<4, true>;
-            const int r3 = crc_ctx_ensure_lds(c, (const void *)kw, lds); if (r3) return r3;
-            hipLaunchKernelGGL(kw, dim3((unsigned)(cnt * k)), dim3(c->n / 16), lds, st, src, src_size, src_poly, E, c->d_f64_rp, c->f64, c->n, c->k, D, dbc,
-                tab, *pool, F);
-            HIPCHK(hipGetLastError());
-        } else {
+        if (one && f64_wave_path(c, RB, 1))
+            return f64_launch(c, cs == 2 ? relin_digits_wave_kernel<2, true> : cs == 3 ? relin_digits_wave_kernel<3, true> : relin_digits_wave_kernel<4, true>, blocks,
+                              c->n / 16, st, src, src_size, src_poly, E, c->d_f64_rp, c->f64, c->n, c->k, D, dbc, tab, *pool, F);
         auto kern = RB == 3 ? (one ? relin_digits_pool_f64_kernel<3, 16, true> : relin_digits_pool_f64_kernel<3, 16, false>)
                   : RB == 4 ? (one ? relin_digits_pool_f64_kernel<4, 16, true> : relin_digits_pool_f64_kernel<4, 16, false>)
                             : (one ? relin_digits_pool_f64_kernel<5, 32, true> : relin_digits_pool_f64_kernel<5, 32, false>);
-        const int r2 = crc_ctx_ensure_lds(c, (const void *)kern, lds); if (r2) return r2;
-        hipLaunchKernelGGL(kern, dim3((unsigned)(cnt * k)), dim3(f64_hold_threads(c, RB)), lds, st, src, src_size, src_poly, E, c->d_f64_rp, c->f64, c->n,
-            c->logn, c->k, D, dbc, tab, *pool, F);
-        HIPCHK(hipGetLastError());
-        }
-    } else if (f64_wave_path(c, RB, 1)) {
-        auto kw = c->logn == 12 ? relin_digits_wave_kernel<2, false> : c->logn == 13 ? relin_digits_wave_kernel<3, false> : relin_digits_wave_kernel<4, false>;
-        const int r3 = crc_ctx_ensure_lds(c, (const void *)kw, lds); if (r3) return r3;
-        hipLaunchKernelGGL(kw, dim3((unsigned)(cnt * k)), dim3(c->n / 16), lds, st, src, src_size, src_poly, E, c->d_f64_rp, c->f64, c->n, c->k, D, dbc, tab,
-                           PoolGeom{0, 0, 0, 0, 0, 0, 0, 0}, dbc);
-        HIPCHK(hipGetLastError());
-    } else {
-        auto kern = RB == 3 ? relin_digits_f64_kernel<3, 16> : RB == 4 ? relin_digits_f64_kernel<4, 16> : relin_digits_f64_kernel<5, 32>;
-        const int r2 = crc_ctx_ensure_lds(c, (const void *)kern, lds); if (r2) return r2;
-        hipLaunchKernelGGL(kern, dim3((unsigned)(cnt * k)), dim3(f64_hold_threads(c, RB)), lds, st, src, src_size, src_poly, E, c->d_f64_rp, c->f64, c->n,
-            c->logn, c->k, D, dbc, tab);
-        HIPCHK(hipGetLastError());
+        return f64_launch(c, kern, blocks, hold, st, src, src_size, src_poly, E, c->d_f64_rp, c->f64, c->n, c->logn, c->k, D, dbc, tab, *pool, F);
     }
-    return CRC_OK;
+    if (f64_wave_path(c, RB, 1))
+        return f64_launch(c, cs == 2 ? relin_digits_wave_kernel<2, false> : cs == 3 ? relin_digits_wave_kernel<3, false> : relin_digits_wave_kernel<4, false>, blocks,
+                          c->n / 16, st, src, src_size, src_poly, E, c->d_f64_rp, c->f64, c->n, c->k, D, dbc, tab, NO_POOL, dbc);
+    return f64_launch(c, RB == 3 ? relin_digits_f64_kernel<3, 16> : RB == 4 ? relin_digits_f64_kernel<4, 16> : relin_digits_f64_kernel<5, 32>, blocks, hold, st, src,
+                      src_size, src_poly, E, c->d_f64_rp, c->f64, c->n, c->logn, c->k, D, dbc, tab);
 }
 int k_relin64_from_digits(crc_ctx *c, const u64 *x3, int add_size, size_t cnt, int dbc, u64 *y, u64 *work, const u64 *kp, hipStream_t st, bool out_ntt,
                           const PoolGeom *pool, const u64 *mul, const PolyTail *poly)
@@ -917,25 +889,24 @@ int k_relin64_from_digits(crc_ctx *c, const u64 *x3, int add_size, size_t cnt, i
     if (cnt == 0) return CRC_OK;
     if (!k_relin64_supported(c, dbc)) return CRC_ERR_UNSUPPORTED;
     if (pool && !k_relin64_pool_supported(c, dbc, pool->xf * pool->yf)) return CRC_ERR_UNSUPPORTED;
-    const size_t n = c->n;
-    int D = 0;
-    for (int i = 0; i < c->k; i++) D += evk_digits(c->q[i], dbc);
+    const Relin64Work w = relin64_work(c, cnt, dbc, work);
     const double *Kf = reinterpret_cast<const double *>(kp);
     int rc;
-    double *E = reinterpret_cast<double *>(work), *A = E + cnt * D * CRC_NF64 * n;
-    const int RB = f64_radix(c);
-    switch (c->k) {
-#define MACK(KV) case KV: rc = c->tune.relin_mac_ct == 8 ? relin64_mac<KV, 8>(c, E, Kf, A, D, cnt, st) : relin64_mac<KV, 4>(c, E, Kf, A, D, cnt, st); break;
-    MACK(1) MACK(2) MACK(3) MACK(4) MACK(5) MACK(6) MACK(7) MACK(8)
-#undef MACK
-    default: return CRC_ERR_UNSUPPORTED;
-    }
+#define MAC(KV) (c->tune.relin_mac_ct == 8 ? relin64_mac<KV, 8>(c, w.E, Kf, w.A, w.D, cnt, st) : relin64_mac<KV, 4>(c, w.E, Kf, w.A, w.D, cnt, st))
+    RELIN64_MAC_BY_K(rc, MAC)
+#undef MAC
     if (rc) return rc;
     if ((mul || poly) && !out_ntt) return CRC_ERR_INVALID_ARGUMENT;
     // (pooled: x3 / add_size are the UNPOOLED ciphertexts whose (c0, c1) K3 adds up window by window)
-    return RB == 3 ? relin64_tail<3, 16>(c, A, x3, add_size, y, cnt, out_ntt, st, mul, pool, poly)
-         : RB == 4 ? relin64_tail<4, 16>(c, A, x3, add_size, y, cnt, out_ntt, st, mul, pool, poly) : relin64_tail<5, 32>(c, A, x3, add_size, y, cnt, out_ntt, st,
-             mul, pool, poly);
+    return relin64_tail(c, w.A, x3, add_size, y, cnt, out_ntt, st, mul, pool, poly);
+}
+static int relin64_tail(crc_ctx *c, const double *A, const u64 *x3, int add_size, u64 *y, size_t cnt, bool out_ntt, hipStream_t st, const u64 *mul, const PoolGeom *pool,
+    const PolyTail *poly)
+{
+    const int RB = f64_radix(c);
+    return RB == 3 ? relin64_tail_rb<3, 16>(c, A, x3, add_size, y, cnt, out_ntt, st, mul, pool, poly)
+         : RB == 4 ? relin64_tail_rb<4, 16>(c, A, x3, add_size, y, cnt, out_ntt, st, mul, pool, poly)
+                   : relin64_tail_rb<5, 32>(c, A, x3, add_size, y, cnt, out_ntt, st, mul, pool, poly);
 }
 int k_relinearize64(crc_ctx *c, const u64 *src, int src_size, int src_poly, const u64 *x3, int add_size, size_t cnt, int dbc, u64 *y, u64 *work, const u64 *kp,
                     hipStream_t st, bool out_ntt, const PoolGeom *pool, const u64 *mul, const PolyTail *poly)
@@ -947,7 +918,7 @@ int k_relinearize64(crc_ctx *c, const u64 *src, int src_size, int src_poly, cons
 // scratch of K2 + K3 for `keys` keys at once: one more A per further key behind k_relin64_work_words
 size_t k_relin64_work_words_multi(const crc_ctx *c, size_t cnt, int dbc, int keys)
 {
-    return k_relin64_work_words(c, cnt, dbc) + (size_t)(keys > 1 ? keys - 1 : 0) * cnt * c->n * CRC_NF64 * 2 * c->k;
+    return k_relin64_work_words(c, cnt, dbc) + (size_t)(keys > 1 ? keys - 1 : 0) * relin64_work(c, cnt, dbc).a_stride;
 }
 // K2 + K3 of TWO prepared keys on the E that is there (relin_mac_multi_f64_kernel): y0 / y1 what k_relin64_from_digits gives with kp0 / kp1, bit for bit.
 // work: k_relin64_work_words_multi(.., 2)
@@ -956,35 +927,20 @@ int k_relin64_from_digits2(crc_ctx *c, const u64 *x3, int add_size, size_t cnt, 
 {
     if (cnt == 0) return CRC_OK;
     if (!k_relin64_supported(c, dbc)) return CRC_ERR_UNSUPPORTED;
-    const size_t n = c->n;
-    int D = 0;
-    for (int i = 0; i < c->k; i++) D += evk_digits(c->q[i], dbc);
-    double *E = reinterpret_cast<double *>(work), *A = E + cnt * D * CRC_NF64 * n;
-    const size_t a_stride = cnt * 2 * c->k * CRC_NF64 * n;
+    const Relin64Work w = relin64_work(c, cnt, dbc, work);
     const double *K0 = reinterpret_cast<const double *>(kp0), *K1 = reinterpret_cast<const double *>(kp1);
     int rc;
-    switch (c->k) {
-#define MACK(KV) case KV: rc = relin64_mac2<KV>(c, E, K0, K1, A, a_stride, D, cnt, st); break;
-    MACK(1) MACK(2) MACK(3) MACK(4) MACK(5) MACK(6) MACK(7) MACK(8)
-#undef MACK
-    default: return CRC_ERR_UNSUPPORTED;
-    }
+#define MAC(KV) relin64_mac2<KV>(c, w.E, K0, K1, w.A, w.a_stride, w.D, cnt, st)
+    RELIN64_MAC_BY_K(rc, MAC)
+#undef MAC
     if (rc) return rc;
-    const int RB = f64_radix(c);
-    u64 *ys[2] = {y0, y1};
-    for (int r = 0; r < 2; r++) {
-        const double *Ar = A + r * a_stride;
-        rc = RB == 3 ? relin64_tail<3, 16>(c, Ar, x3, add_size, ys[r], cnt, out_ntt, st, nullptr, nullptr, nullptr)
-           : RB == 4 ? relin64_tail<4, 16>(c, Ar, x3, add_size, ys[r], cnt, out_ntt, st, nullptr, nullptr, nullptr)
-                     : relin64_tail<5, 32>(c, Ar, x3, add_size, ys[r], cnt, out_ntt, st, nullptr, nullptr, nullptr);
-        if (rc) return rc;
-    }
-    return CRC_OK;
+    if ((rc = relin64_tail(c, w.A, x3, add_size, y0, cnt, out_ntt, st))) return rc;
+    return relin64_tail(c, w.A + w.a_stride, x3, add_size, y1, cnt, out_ntt, st);
 }
 
 // K2 + K3 with one prepared key per STEP of the batch (relin_mac_keyed_f64_kernel): the cnt ciphertexts are [cnt / per_key][per_key], the ciphertexts of step j take
 // the key kp_table[j] -- a DEVICE array of cnt / per_key pointers to prepared keys (k_relin64_prepare_keys).  E is there (k_relin64_digits over all cnt); y what
-// k_relin64_from_digits gives for every step with its key, bit for bit.  work: k_relin64_work_words(cnt), laid out as there
+// k_relin64_from_digits gives for every step with its key, bit for bit.  work: relin64_work(cnt)
 template <int K>
 static int relin64_mac_keyed(crc_ctx *c, const double *E, const double *const *keys, double *A, int D, size_t steps, size_t per, hipStream_t st)
 {
@@ -1010,23 +966,13 @@ int k_relin64_from_digits_keyed(crc_ctx *c, const u64 *x3, int add_size, size_t 
     if (cnt == 0) return CRC_OK;
     if (!k_relin64_supported(c, dbc)) return CRC_ERR_UNSUPPORTED;
     if (per_key < 1 || cnt % per_key || !kp_table) return CRC_ERR_INVALID_ARGUMENT;
-    const size_t n = c->n;
-    int D = 0;
-    for (int i = 0; i < c->k; i++) D += evk_digits(c->q[i], dbc);
-    double *E = reinterpret_cast<double *>(work), *A = E + cnt * D * CRC_NF64 * n;
+    const Relin64Work w = relin64_work(c, cnt, dbc, work);
     const double *const *keys = reinterpret_cast<const double *const *>(kp_table);
     int rc;
-    switch (c->k) {
-#define MACK(KV) case KV: rc = relin64_mac_keyed<KV>(c, E, keys, A, D, cnt / per_key, per_key, st); break;
-    MACK(1) MACK(2) MACK(3) MACK(4) MACK(5) MACK(6) MACK(7) MACK(8)
-#undef MACK
-    default: return CRC_ERR_UNSUPPORTED;
-    }
-    if (rc) return rc;
-    const int RB = f64_radix(c);
-    return RB == 3 ? relin64_tail<3, 16>(c, A, x3, add_size, y, cnt, out_ntt, st, nullptr, nullptr, nullptr)
-         : RB == 4 ? relin64_tail<4, 16>(c, A, x3, add_size, y, cnt, out_ntt, st, nullptr, nullptr, nullptr)
-                   : relin64_tail<5, 32>(c, A, x3, add_size, y, cnt, out_ntt, st, nullptr, nullptr, nullptr);
+#define MAC(KV) relin64_mac_keyed<KV>(c, w.E, keys, w.A, w.D, cnt / per_key, per_key, st)
+    RELIN64_MAC_BY_K(rc, MAC)
+#undef MAC
+    return rc ? rc : relin64_tail(c, w.A, x3, add_size, y, cnt, out_ntt, st);
 }
 
 // kp_table for k_relin64_from_digits_keyed, built on the device: table[j] = base + slot[j] kpw words, null where slot[j] < 0 (a step without a key).  The slots

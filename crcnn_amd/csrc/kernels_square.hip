@@ -200,98 +200,56 @@ __global__ void __launch_bounds__(256) relin_premul_kernel(const u64 *x3, u64 *p
     for (int s = threadIdx.x; s < n; s += blockDim.x) dst[s] = mulmod_shoup(src[s], inv, invs, q);      // evaluator.cpp:984-985
 }
 
-size_t k_square_work_words(const crc_ctx *c, size_t cnt)
-{
-    const size_t n = c->n, k = c->k, kb = k_square64_supported(c) && (size_t)c->sq64.kf > (size_t)c->kb ? c->sq64.kf : c->kb;
-    // QN[2k] BS[2kb] DQ[3k] DB[3kb]   (kb: whichever auxiliary base has more rows -- SEAL's 61-bit one or the engine's fp64 primes, kernels_square64.hip)
-    return cnt * n * (2 * k + 2 * kb + 3 * k + 3 * kb);
-}
-size_t k_multiply_work_words(const crc_ctx *c, size_t cnt)
-{
-    const size_t n = c->n, k = c->k, kb = k_square64_supported(c) && (size_t)c->sq64.kf > (size_t)c->kb ? c->sq64.kf : c->kb;
-    // QN[2][2k] BS[2][2kb] DQ[3k] DB[3kb]: both inputs are lifted and transformed, the products are the square's three
-    return cnt * n * (4 * k + 4 * kb + 3 * k + 3 * kb);
-}
+// rows per polynomial of the larger auxiliary base -- SEAL's 61-bit one or the engine's fp64 primes (kernels_square64.hip): either path must fit the work space
+static size_t product_rows_max(const crc_ctx *c) { return k_square64_supported(c) && (size_t)c->sq64.kf > (size_t)c->kb ? c->sq64.kf : c->kb; }
+size_t k_square_work_words(const crc_ctx *c, size_t cnt) { return product_work(c, cnt, 1, product_rows_max(c)).words; }
+// (both inputs are lifted and transformed, the products are the square's three)
+size_t k_multiply_work_words(const crc_ctx *c, size_t cnt) { return product_work(c, cnt, 2, product_rows_max(c)).words; }
 size_t k_relin_work_words(const crc_ctx *c, size_t cnt, int dbc)
 {
-    const size_t n = c->n, k = c->k;
-    size_t D = 0; for (int i = 0; i < c->k; i++) D += evk_digits(c->q[i], dbc);
+    const size_t n = c->n, k = c->k, D = relin_digit_count(c, dbc);
     // PM[k] E[D*k] R[2k]   (the prepared keys live in front of the caller's work space: k_relin_keys_words more); either path must fit
     const size_t a = cnt * n * (k + D * k + 2 * k), b = k_relin64_work_words(c, cnt, dbc);
     return a > b ? a : b;
 }
 size_t k_relin_keys_words(const crc_ctx *c, int dbc) { return k_relin64_keys_words(c, dbc); }      // (>= crc_evk_words: the 28-bit packed keys of the other path fit too)
 
-int k_square(crc_ctx *c, const u64 *x, size_t cnt, u64 *y3, u64 *work, hipStream_t st, bool in_ntt, bool premul_c2)
+// The product of cnt ciphertexts on SEAL's 61-bit auxiliary base: the square of x (y null; Evaluator::square) or x . y of two arrays (Evaluator::multiply,
+// evaluator.cpp:356-700, for size-2 inputs).  One chain for both: every input is lifted and transformed, and the inverse transforms form (a^2, 2ab, b^2) from the
+// one input's two rows (NttArgs prologue 4) or the tensor product (ac, ad + bc, bd) from the two inputs' four (prologue 6) while they load their rows -- no
+// product tensors in memory
+static int product61(crc_ctx *c, const u64 *x, const u64 *y, size_t cnt, u64 *y3, u64 *work, hipStream_t st, bool in_ntt, bool premul_c2)
 {
     if (cnt == 0) return CRC_OK;
     // the auxiliary base over the engine's fp64 primes whenever the parameters fit (every set of the reference's does); tune.sq_path = 1 keeps SEAL's 61-bit base
-    if (c->tune.sq_path != 1 && k_square64_supported(c)) return k_square64(c, x, cnt, y3, work, st, in_ntt, premul_c2);
-    const size_t n = c->n, k = c->k, kb = c->kb;
-    u64 *QN = work, *BS = QN + cnt * 2 * k * n, *DQ = BS + cnt * 2 * kb * n, *DB = DQ + cnt * 3 * k * n;
-    const int threads = c->n < 256 ? c->n : 256, sblocks = c->n / threads;
-    int rc;
-    // the square needs x in both forms: coefficients for the base extension, NTT values (base q) for the products.  An NTT-resident
-    // caller hands over the latter, so one inverse transform replaces the forward one (and the caller's own conversion disappears)
-    const u64 *xc = x, *xn = QN;
-    if (in_ntt) { if ((rc = k_ntt_ct(c, true, x, QN, cnt, 2, false, st, nullptr, 0, 0, 0))) return rc; xc = QN; xn = x; }
-    {
-        const dim3 grid((unsigned)(cnt * 2 * sblocks)), blk(threads);
-        bool launched = false;
-#define LIFT(KV, KAV) if (c->k == KV && c->ka == KAV) { hipLaunchKernelGGL((sq_lift_kernel<KV, KAV + 1>), grid, blk, 0, st, xc, BS, c->d_mods, c->d_behz, c->n); launched = true; }
-        CRC_FOR_ALL_K_KA(LIFT)
-#undef LIFT
-        if (!launched) return CRC_ERR_UNSUPPORTED;
-        HIPCHK(hipGetLastError());
-    }
-    if (!in_ntt && (rc = k_ntt_ct(c, false, x, QN, cnt, 2, false, st, nullptr, 0, 0, 0))) return rc;
-    if ((rc = k_ntt_ct(c, false, BS, BS, cnt, 2, true, st, nullptr, 0, 0, 0))) return rc;
-    // a^2, 2ab, b^2 are formed while the inverse transforms load their rows (no product tensors in memory)
-    if ((rc = k_square_intt(c, xn, DQ, cnt, false, st))) return rc;
-    if ((rc = k_square_intt(c, BS, DB, cnt, true, st))) return rc;
-    {
-        const dim3 grid((unsigned)(cnt * 3 * sblocks)), blk(threads);
-        bool launched = false;
-#define FLOOR(KV, KAV) if (c->k == KV && c->ka == KAV) { hipLaunchKernelGGL((sq_floor_kernel<KV, KAV>), grid, blk, 0, st, DQ, DB, y3, c->d_mods, c->d_behz, c->n, premul_c2 ? 1 : 0); launched = true; }
-        CRC_FOR_ALL_K_KA(FLOOR)
-#undef FLOOR
-        if (!launched) return CRC_ERR_UNSUPPORTED;
-        HIPCHK(hipGetLastError());
-    }
-    return CRC_OK;
-}
-
-// Evaluator::multiply (evaluator.cpp:356-700) for size-2 inputs: k_square's chain with both inputs lifted and transformed and the tensor product
-// (ac, ad + bc, bd) formed where the square forms (a^2, 2ab, b^2) -- NttArgs prologue 6 over q and over Bsk
-int k_multiply(crc_ctx *c, const u64 *x, const u64 *y, size_t cnt, u64 *y3, u64 *work, hipStream_t st, bool in_ntt, bool premul_c2)
-{
-    if (cnt == 0) return CRC_OK;
-    if (c->tune.sq_path != 1 && k_square64_supported(c)) return k_multiply64(c, x, y, cnt, y3, work, st, in_ntt, premul_c2);
-    const size_t n = c->n, k = c->k, kb = c->kb;
-    u64 *QN = work, *BS = QN + cnt * 4 * k * n, *DQ = BS + cnt * 4 * kb * n, *DB = DQ + cnt * 3 * k * n;
+    if (c->tune.sq_path != 1 && k_square64_supported(c))
+        return y ? k_multiply64(c, x, y, cnt, y3, work, st, in_ntt, premul_c2) : k_square64(c, x, cnt, y3, work, st, in_ntt, premul_c2);
+    const int inputs = y ? 2 : 1;
+    const ProductWork w = product_work(c, cnt, inputs, c->kb, work);
     const int threads = c->n < 256 ? c->n : 256, sblocks = c->n / threads;
     int rc;
     const u64 *in[2] = {x, y}, *nt[2] = {nullptr, nullptr};
-    for (int h = 0; h < 2; h++) {
-        u64 *qn = QN + (size_t)h * cnt * 2 * k * n, *bs = BS + (size_t)h * cnt * 2 * kb * n;
-        const u64 *xc = in[h]; nt[h] = qn;
-        if (in_ntt) { if ((rc = k_ntt_ct(c, true, in[h], qn, cnt, 2, false, st, nullptr, 0, 0, 0))) return rc; xc = qn; nt[h] = in[h]; }
+    for (int h = 0; h < inputs; h++) {
+        // the product needs an input in both forms: coefficients for the base extension, NTT values (base q) for the products.  An NTT-resident
+        // caller hands over the latter, so one inverse transform replaces the forward one (and the caller's own conversion disappears)
+        const u64 *xc = in[h]; nt[h] = w.QN[h];
+        if (in_ntt) { if ((rc = k_ntt_ct(c, true, in[h], w.QN[h], cnt, 2, false, st, nullptr, 0, 0, 0))) return rc; xc = w.QN[h]; nt[h] = in[h]; }
         const dim3 grid((unsigned)(cnt * 2 * sblocks)), blk(threads);
         bool launched = false;
-#define LIFT(KV, KAV) if (c->k == KV && c->ka == KAV) { hipLaunchKernelGGL((sq_lift_kernel<KV, KAV + 1>), grid, blk, 0, st, xc, bs, c->d_mods, c->d_behz, c->n); launched = true; }
+#define LIFT(KV, KAV) if (c->k == KV && c->ka == KAV) { hipLaunchKernelGGL((sq_lift_kernel<KV, KAV + 1>), grid, blk, 0, st, xc, w.LB[h], c->d_mods, c->d_behz, c->n); launched = true; }
         CRC_FOR_ALL_K_KA(LIFT)
 #undef LIFT
         if (!launched) return CRC_ERR_UNSUPPORTED;
         HIPCHK(hipGetLastError());
-        if (!in_ntt && (rc = k_ntt_ct(c, false, in[h], qn, cnt, 2, false, st, nullptr, 0, 0, 0))) return rc;
+        if (!in_ntt && (rc = k_ntt_ct(c, false, in[h], w.QN[h], cnt, 2, false, st, nullptr, 0, 0, 0))) return rc;
     }
-    if ((rc = k_ntt_ct(c, false, BS, BS, 2 * cnt, 2, true, st, nullptr, 0, 0, 0))) return rc;
-    if ((rc = k_multiply_intt(c, nt[0], nt[1], DQ, cnt, false, st))) return rc;
-    if ((rc = k_multiply_intt(c, BS, BS + cnt * 2 * kb * n, DB, cnt, true, st))) return rc;
+    if ((rc = k_ntt_ct(c, false, w.LB[0], w.LB[0], inputs * cnt, 2, true, st, nullptr, 0, 0, 0))) return rc;
+    if ((rc = k_product_intt(c, nt[0], nt[1], w.DQ, cnt, false, st))) return rc;
+    if ((rc = k_product_intt(c, w.LB[0], w.LB[1], w.DB, cnt, true, st))) return rc;
     {
         const dim3 grid((unsigned)(cnt * 3 * sblocks)), blk(threads);
         bool launched = false;
-#define FLOOR(KV, KAV) if (c->k == KV && c->ka == KAV) { hipLaunchKernelGGL((sq_floor_kernel<KV, KAV>), grid, blk, 0, st, DQ, DB, y3, c->d_mods, c->d_behz, c->n, premul_c2 ? 1 : 0); launched = true; }
+#define FLOOR(KV, KAV) if (c->k == KV && c->ka == KAV) { hipLaunchKernelGGL((sq_floor_kernel<KV, KAV>), grid, blk, 0, st, w.DQ, w.DB, y3, c->d_mods, c->d_behz, c->n, premul_c2 ? 1 : 0); launched = true; }
         CRC_FOR_ALL_K_KA(FLOOR)
 #undef FLOOR
         if (!launched) return CRC_ERR_UNSUPPORTED;
@@ -299,6 +257,8 @@ int k_multiply(crc_ctx *c, const u64 *x, const u64 *y, size_t cnt, u64 *y3, u64 
     }
     return CRC_OK;
 }
+int k_square(crc_ctx *c, const u64 *x, size_t cnt, u64 *y3, u64 *work, hipStream_t st, bool in_ntt, bool premul_c2) { return product61(c, x, nullptr, cnt, y3, work, st, in_ntt, premul_c2); }
+int k_multiply(crc_ctx *c, const u64 *x, const u64 *y, size_t cnt, u64 *y3, u64 *work, hipStream_t st, bool in_ntt, bool premul_c2) { return product61(c, x, y, cnt, y3, work, st, in_ntt, premul_c2); }
 
 // c2_premul: the third polynomial of x3 already holds c2 (q/q_i)^-1 (k_square with premul_c2).  kp: crc_evk_words of space for the packed keys;
 // keys_ready: a previous call with the same evk has filled it.  poly (with its multiplier p2): a polynomial activation's ring-linear terms, joined to the

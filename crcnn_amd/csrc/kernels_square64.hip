@@ -22,6 +22,7 @@
 //   sq64_floor_kernel : x t, fast_floor, fastbconv_sk back to q (one lazy 128-bit sum + one reduction per q_i), optional (q/q_i)^-1 on c2 for relinearisation
 #include "kernels.h"
 #include "ntt_f64.h"
+#include "f64_launch.h"
 
 // every (k, kf) a context can have is not known at compile time (kf depends on t): instances for k = 1..8 with the kf range 3..12 the size rule can produce for
 // 40-60-bit q_i
@@ -462,20 +463,6 @@ __global__ void __launch_bounds__(256) sq64_floor_kernel(const u64 *dq, const do
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------------------------------
-static int sq64_threads(const crc_ctx *c, int RB) { int nt = c->n >> RB; if (nt < 64) nt = 64; if (nt > (RB == 5 ? 512 : 1024)) nt = RB == 5 ? 512 : 1024;
-    return nt; }
-// the wave-local transforms (one workgroup barrier per transform) serve the two rings the bench configurations use; CRC_F64_WAVE=0 keeps the round-4 kernels
-// (bit 0: sq64_inv_kernel -- -25 % at both rings --, bit 3: the lifting forward kernel -- +2 % / +31 %: it has no row to hold and the round-4 form runs it at
-// eight waves per SIMD; off by default)
-static bool sq64_wave_path(const crc_ctx *c, int RB, int bit)
-{
-    // (n = 4096 since round 6: CS = 2; the lifting forward kernel -- bit 3, off by default -- exists for n = 8192 / 16384 only)
-    if (RB != 3 || (c->logn != 12 && c->logn != 13 && c->logn != 14) || (bit == 3 && c->logn == 12)) return false;
-    const int sel = c->tune.f64_wave < 0 ? 7 : c->tune.f64_wave;
-    return (sel >> bit) & 1;
-}
-static int sq64_radix(const crc_ctx *c) { const int r = c->tune.f64_radix; return r >= 3 && r <= 5 ? r : 3; }
-
 bool k_square64_supported(const crc_ctx *c)
 {
     if (c->sq64.kf < 3 || c->n < 64 || c->n > 16384) return false;
@@ -485,19 +472,14 @@ bool k_square64_supported(const crc_ctx *c)
     return false;
 }
 
-// threads of the kernel that keeps a row in registers: 16 points per thread (32 at radix 32) -- kernels_relin64.hip relin_inv_crt_kernel
-static int sq64_hold_threads(const crc_ctx *c, int RB) { int nt = c->n >> (RB == 5 ? 5 : 4); if (nt < 64) nt = 64;
-    if (nt > (RB == 5 ? 512 : 1024)) nt = RB == 5 ? 512 : 1024; return nt; }
-
 // the lift and the forward transforms of cnt size-2 ciphertexts x: LB [cnt][2][kf][n] transformed rows under the fp64 primes; *xn_out: x in NTT form over q (x
 // itself for an NTT-resident caller, QN [cnt][2][k][n] otherwise)
 static int sq64_lift_forward(crc_ctx *c, const u64 *x, size_t cnt, u64 *QN, double *LB, hipStream_t st, bool in_ntt, const u64 **xn_out)
 {
-    const size_t n = c->n, kf = c->sq64.kf;
+    const size_t kf = c->sq64.kf;
     const int lthreads = c->n < 512 ? c->n / 2 : 256, lblocks = c->n / (2 * lthreads);         // (the lift kernel: two coefficients per thread)
     int rc;
-    const size_t lds = n * 8;
-    const int RB = sq64_radix(c), nt = sq64_threads(c, RB);
+    const int RB = f64_radix(c), nt = f64_threads(c, RB);
     const double *Wf = c->d_f64_rp;
     const u64 *xn = QN;
     // (fused up to k = 4: every one of the kf workgroups of a polynomial reads its k source rows, and at k = 8, kf = 11 that costs more than the lift kernel's
@@ -510,22 +492,20 @@ static int sq64_lift_forward(crc_ctx *c, const u64 *x, size_t cnt, u64 *QN, doub
         xn = x;
         bool launched = false;
         const unsigned grid = xcd_grid(cnt * 2, (unsigned)kf);
-        if (sq64_wave_path(c, RB, 3)) {
-#define LIFTW(KV) if (c->k == KV) { \
-            auto kern = c->logn == 13 ? sq64_liftfwd_wave_kernel<KV, 3> : sq64_liftfwd_wave_kernel<KV, 4>; \
-            if ((rc = crc_ctx_ensure_lds(c, (const void *)kern, lds))) return rc; \
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(c->n / 16), lds, st, QN, LB, Wf, c->d_behz, c->d_sq64, c->n, (int)kf, cnt * 2); launched = true; }
+        // (f64_wave bit 3; the wave-local lifting kernel exists for n = 8192 / 16384 only: the bit does not apply at n = 4096)
+        if (c->logn != 12 && f64_wave_path(c, RB, 3)) {
+#define LIFTW(KV) if (c->k == KV) { launched = true; \
+            if ((rc = f64_launch(c, c->logn == 13 ? sq64_liftfwd_wave_kernel<KV, 3> : sq64_liftfwd_wave_kernel<KV, 4>, grid, c->n / 16, st, QN, LB, Wf, c->d_behz, \
+                                 c->d_sq64, c->n, (int)kf, cnt * 2))) return rc; }
             LIFTW(1) LIFTW(2) LIFTW(3) LIFTW(4)
 #undef LIFTW
         }
-#define LIFTFWD(KV) if (!launched && c->k == KV) { \
-            auto kern = RB == 3 ? sq64_liftfwd_kernel<KV, 3> : RB == 4 ? sq64_liftfwd_kernel<KV, 4> : sq64_liftfwd_kernel<KV, 5>; \
-            if ((rc = crc_ctx_ensure_lds(c, (const void *)kern, lds))) return rc; \
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(nt), lds, st, QN, LB, Wf, c->d_behz, c->d_sq64, c->n, c->logn, (int)kf, cnt * 2); launched = true; }
+#define LIFTFWD(KV) if (!launched && c->k == KV) { launched = true; \
+            if ((rc = f64_launch(c, RB == 3 ? sq64_liftfwd_kernel<KV, 3> : RB == 4 ? sq64_liftfwd_kernel<KV, 4> : sq64_liftfwd_kernel<KV, 5>, grid, nt, st, QN, LB, Wf, \
+                                 c->d_behz, c->d_sq64, c->n, c->logn, (int)kf, cnt * 2))) return rc; }
         LIFTFWD(1) LIFTFWD(2) LIFTFWD(3) LIFTFWD(4) LIFTFWD(5) LIFTFWD(6) LIFTFWD(7) LIFTFWD(8)
 #undef LIFTFWD
         if (!launched) return CRC_ERR_UNSUPPORTED;
-        HIPCHK(hipGetLastError());
     } else {
         const u64 *xc = x;
         if (in_ntt) { if ((rc = k_ntt_ct(c, true, x, QN, cnt, 2, false, st, nullptr, 0, 0, 0))) return rc; xc = QN; xn = x; }
@@ -539,10 +519,8 @@ static int sq64_lift_forward(crc_ctx *c, const u64 *x, size_t cnt, u64 *QN, doub
             HIPCHK(hipGetLastError());
         }
         if (!in_ntt && (rc = k_ntt_ct(c, false, x, QN, cnt, 2, false, st, nullptr, 0, 0, 0))) return rc;
-        auto kern = RB == 3 ? sq64_fwd_kernel<3> : RB == 4 ? sq64_fwd_kernel<4> : sq64_fwd_kernel<5>;
-        if ((rc = crc_ctx_ensure_lds(c, (const void *)kern, lds))) return rc;
-        hipLaunchKernelGGL(kern, dim3((unsigned)(cnt * 2 * kf)), dim3(nt), lds, st, LB, Wf, c->d_sq64, c->n, c->logn, (int)kf);
-        HIPCHK(hipGetLastError());
+        if ((rc = f64_launch(c, RB == 3 ? sq64_fwd_kernel<3> : RB == 4 ? sq64_fwd_kernel<4> : sq64_fwd_kernel<5>, cnt * 2 * kf, nt, st, LB, Wf, c->d_sq64, c->n,
+                             c->logn, (int)kf))) return rc;
     }
     *xn_out = xn;
     return CRC_OK;
@@ -561,67 +539,42 @@ static int sq64_floor(crc_ctx *c, const u64 *DQ, const double *DB, u64 *y3, size
     return CRC_OK;
 }
 
-// work: QN [2k] | LB [2 kf] | DQ [3k] | DB [3 kf]   (k_square_work_words sizes the rows by max(kb, kf))
-int k_square64(crc_ctx *c, const u64 *x, size_t cnt, u64 *y3, u64 *work, hipStream_t st, bool in_ntt, bool premul_c2)
+// The product of cnt ciphertexts with the auxiliary base over the fp64 primes: the square of x (y null) or x . y of two ciphertext arrays -- the same chain with
+// the lift and the forward transforms run for every input and the tensor product (ac, ad + bc, bd) in place of (a^2, 2ab, b^2); floor, premultiplication of the
+// third polynomial and result form are the same.  Work space: product_work with kf rows
+static int product64(crc_ctx *c, const u64 *x, const u64 *y, size_t cnt, u64 *y3, u64 *work, hipStream_t st, bool in_ntt, bool premul_c2)
 {
     if (cnt == 0) return CRC_OK;
     if (!k_square64_supported(c)) return CRC_ERR_UNSUPPORTED;
-    const size_t n = c->n, k = c->k, kf = c->sq64.kf;
-    u64 *QN = work, *LBw = QN + cnt * 2 * k * n, *DQ = LBw + cnt * 2 * kf * n, *DBw = DQ + cnt * 3 * k * n;
-    double *LB = reinterpret_cast<double *>(LBw), *DB = reinterpret_cast<double *>(DBw);
+    const int inputs = y ? 2 : 1, kf = c->sq64.kf;
+    const ProductWork w = product_work(c, cnt, inputs, kf, work);
+    double *LB[2] = {reinterpret_cast<double *>(w.LB[0]), reinterpret_cast<double *>(w.LB[1])}, *DB = reinterpret_cast<double *>(w.DB);
     int rc;
-    const size_t lds = n * 8;
-    const int RB = sq64_radix(c);
-    const double *Wi = c->d_f64_irp;
-    const u64 *xn = nullptr;
-    if ((rc = sq64_lift_forward(c, x, cnt, QN, LB, st, in_ntt, &xn))) return rc;
-    // a^2, 2ab, b^2 over q are formed while the inverse transforms load their rows (kernels.hip); over the fp64 primes in sq64_inv_kernel
+    const u64 *in[2] = {x, y}, *nt[2] = {nullptr, nullptr};
+    for (int h = 0; h < inputs; h++)
+        if ((rc = sq64_lift_forward(c, in[h], cnt, w.QN[h], LB[h], st, in_ntt, &nt[h]))) return rc;
+    // the products over q are formed while the inverse transforms load their rows (kernels.hip); over the fp64 primes in the kernels below
     // (x t (q/q_i)^-1, the first thing the floor kernel does to these rows, goes into the transform's closing multiplication where it has one)
     bool dq_scaled = false;
-    if ((rc = k_square_intt(c, xn, DQ, cnt, false, st, c->behz.t_inv_qhat, &dq_scaled))) return rc;
-    if (sq64_wave_path(c, RB, 0)) {
-        auto kern = c->logn == 12 ? sq64_inv_wave_kernel<2> : c->logn == 13 ? sq64_inv_wave_kernel<3> : sq64_inv_wave_kernel<4>;
-        if ((rc = crc_ctx_ensure_lds(c, (const void *)kern, lds))) return rc;
-        hipLaunchKernelGGL(kern, dim3((unsigned)(cnt * kf)), dim3(c->n / 16), lds, st, LB, DB, Wi, c->d_sq64, c->n, (int)kf);
-        HIPCHK(hipGetLastError());
-    } else {
-        auto kern = RB == 3 ? sq64_inv_kernel<3, 16> : RB == 4 ? sq64_inv_kernel<4, 16> : sq64_inv_kernel<5, 32>;
-        if ((rc = crc_ctx_ensure_lds(c, (const void *)kern, lds))) return rc;
-        hipLaunchKernelGGL(kern, dim3((unsigned)(cnt * kf)), dim3(sq64_hold_threads(c, RB)), lds, st, LB, DB, Wi, c->d_sq64, c->n, c->logn, (int)kf);
-        HIPCHK(hipGetLastError());
-    }
-    return sq64_floor(c, DQ, DB, y3, cnt, st, premul_c2, dq_scaled);
-}
-
-// the product of two ciphertext arrays: the square's chain with the lift and the forward transforms run for both inputs and the tensor product (ac, ad + bc, bd)
-// in place of (a^2, 2ab, b^2); floor, premultiplication of the third polynomial and result form are the square's.
-// work: QN [2][2k] | LB [2][2 kf] | DQ [3k] | DB [3 kf]   (k_multiply_work_words)
-int k_multiply64(crc_ctx *c, const u64 *x, const u64 *y, size_t cnt, u64 *y3, u64 *work, hipStream_t st, bool in_ntt, bool premul_c2)
-{
-    if (cnt == 0) return CRC_OK;
-    if (!k_square64_supported(c)) return CRC_ERR_UNSUPPORTED;
-    const size_t n = c->n, k = c->k, kf = c->sq64.kf;
-    u64 *QN = work, *LBw = QN + cnt * 4 * k * n, *DQ = LBw + cnt * 4 * kf * n, *DBw = DQ + cnt * 3 * k * n;
-    double *LBx = reinterpret_cast<double *>(LBw), *LBy = LBx + cnt * 2 * kf * n, *DB = reinterpret_cast<double *>(DBw);
-    int rc;
-    const size_t lds = n * 8;
-    const int RB = sq64_radix(c);
+    if ((rc = k_product_intt(c, nt[0], nt[1], w.DQ, cnt, false, st, c->behz.t_inv_qhat, &dq_scaled))) return rc;
+    // the inverse kernel: the square's, which reads two rows per prime, or the multiply's, which reads six; wave-local (f64_wave bit 0) or the one that holds a
+    // row in registers at the radix in use
+    const int RB = f64_radix(c), cs = c->logn - 10, hold = f64_hold_threads(c, RB);
+    const bool wave = f64_wave_path(c, RB, 0);
+    const size_t blocks = cnt * kf;
     const double *Wi = c->d_f64_irp;
-    const u64 *xn = nullptr, *yn = nullptr;
-    if ((rc = sq64_lift_forward(c, x, cnt, QN, LBx, st, in_ntt, &xn))) return rc;
-    if ((rc = sq64_lift_forward(c, y, cnt, QN + cnt * 2 * k * n, LBy, st, in_ntt, &yn))) return rc;
-    bool dq_scaled = false;
-    if ((rc = k_multiply_intt(c, xn, yn, DQ, cnt, false, st, c->behz.t_inv_qhat, &dq_scaled))) return rc;
-    if (sq64_wave_path(c, RB, 0)) {
-        auto kern = c->logn == 12 ? mul64_inv_wave_kernel<2> : c->logn == 13 ? mul64_inv_wave_kernel<3> : mul64_inv_wave_kernel<4>;
-        if ((rc = crc_ctx_ensure_lds(c, (const void *)kern, lds))) return rc;
-        hipLaunchKernelGGL(kern, dim3((unsigned)(cnt * kf)), dim3(c->n / 16), lds, st, LBx, LBy, DB, Wi, c->d_sq64, c->n, (int)kf);
-        HIPCHK(hipGetLastError());
-    } else {
-        auto kern = RB == 3 ? mul64_inv_kernel<3, 16> : RB == 4 ? mul64_inv_kernel<4, 16> : mul64_inv_kernel<5, 32>;
-        if ((rc = crc_ctx_ensure_lds(c, (const void *)kern, lds))) return rc;
-        hipLaunchKernelGGL(kern, dim3((unsigned)(cnt * kf)), dim3(sq64_hold_threads(c, RB)), lds, st, LBx, LBy, DB, Wi, c->d_sq64, c->n, c->logn, (int)kf);
-        HIPCHK(hipGetLastError());
-    }
-    return sq64_floor(c, DQ, DB, y3, cnt, st, premul_c2, dq_scaled);
+    if (!y)
+        rc = wave ? f64_launch(c, cs == 2 ? sq64_inv_wave_kernel<2> : cs == 3 ? sq64_inv_wave_kernel<3> : sq64_inv_wave_kernel<4>, blocks, c->n / 16, st, LB[0], DB, Wi,
+                               c->d_sq64, c->n, kf)
+                  : f64_launch(c, RB == 3 ? sq64_inv_kernel<3, 16> : RB == 4 ? sq64_inv_kernel<4, 16> : sq64_inv_kernel<5, 32>, blocks, hold, st, LB[0], DB, Wi, c->d_sq64,
+                               c->n, c->logn, kf);
+    else
+        rc = wave ? f64_launch(c, cs == 2 ? mul64_inv_wave_kernel<2> : cs == 3 ? mul64_inv_wave_kernel<3> : mul64_inv_wave_kernel<4>, blocks, c->n / 16, st, LB[0], LB[1],
+                               DB, Wi, c->d_sq64, c->n, kf)
+                  : f64_launch(c, RB == 3 ? mul64_inv_kernel<3, 16> : RB == 4 ? mul64_inv_kernel<4, 16> : mul64_inv_kernel<5, 32>, blocks, hold, st, LB[0], LB[1], DB, Wi,
+                               c->d_sq64, c->n, c->logn, kf);
+    if (rc) return rc;
+    return sq64_floor(c, w.DQ, DB, y3, cnt, st, premul_c2, dq_scaled);
 }
+int k_square64(crc_ctx *c, const u64 *x, size_t cnt, u64 *y3, u64 *work, hipStream_t st, bool in_ntt, bool premul_c2) { return product64(c, x, nullptr, cnt, y3, work, st, in_ntt, premul_c2); }
+int k_multiply64(crc_ctx *c, const u64 *x, const u64 *y, size_t cnt, u64 *y3, u64 *work, hipStream_t st, bool in_ntt, bool premul_c2) { return product64(c, x, y, cnt, y3, work, st, in_ntt, premul_c2); }

@@ -14,9 +14,11 @@ pytestmark = pytest.mark.gpu
 SETS = sorted(glob.glob(os.path.join(GOLD, "ops_*.npz")))
 INVALID = -1
 FILL = 0xFFFFFFFFFFFFFFFF
-# the default kernels; the plain (round-4) fp64 kernels; the reference-order square chain and key switch (SEAL's 61-bit auxiliary base)
-CONFIGS = {"default": [], "no-wave": [("f64_wave", 0)], "reference-order": [("sq_path", 1), ("relin_path", 1)]}
-RESET = [("f64_wave", -1), ("sq_path", 0), ("relin_path", 0), ("sq_chunk", 0)]
+# the default kernels; the plain (round-4) fp64 kernels; the reference-order square chain and key switch (SEAL's 61-bit auxiliary base); the fp64 row kernels
+# with 4 and 5 stages per LDS pass (mul64_inv_kernel<4, 16> and <5, 32>, which no other selection reaches)
+CONFIGS = {"default": [], "no-wave": [("f64_wave", 0)], "reference-order": [("sq_path", 1), ("relin_path", 1)], "radix-16": [("f64_radix", 4)],
+           "radix-32": [("f64_radix", 5)]}
+RESET = [("f64_wave", -1), ("sq_path", 0), ("relin_path", 0), ("f64_radix", 0), ("sq_chunk", 0)]
 QUADS = [(1, 0, 0, 0), (-0.004, 0, 0.197, 0.5), (0.125, 0.25, 0.5, -1), (-2, 0.375, 0, 0)]
 
 
@@ -118,7 +120,7 @@ def test_multiply_pass_boundaries():
             E.multiply_relin(d_x, d_y, cnt, d_evk, d_o, d_w)
             E.multiply(d_x, d_y, cnt, d_o3, d_w)
             res[(chunk, cfg)] = (E.download(d_o, cts[:cnt].shape), E.download(d_o3, (cnt, 3, E.k, E.n)))
-            for k, v in RESET[:3]:
+            for k, v in RESET[:4]:                 # (everything but sq_chunk)
                 E.set_tuning(k, v)
     E.set_tuning("sq_chunk", 0)
     for cfg in CONFIGS:
