@@ -30,9 +30,11 @@
 #include "kernels.h"
 #include "limbred.h"
 #include "boxstage.h"
+#include "conv1_rowtab.h"
 #include <cstdlib>
 
 typedef int v4i __attribute__((ext_vector_type(4)));
+typedef unsigned v2u __attribute__((ext_vector_type(2)));
 typedef signed char i8;
 #define NPL 7
 #define MAXK 8                                   // coefficient moduli (kernel argument tables)
@@ -68,11 +70,13 @@ __device__ __forceinline__ void limb_digits1(u64 r, u64 q, int (&d)[NPL])
 }
 
 // the end of a tile's epilogue, shared by both forms of the kernel: four consecutive filters f0 .. f0 + 3 of output row mm (pixel mm >> 1, poly mm & 1) of image b,
-// given as centred representatives
-__device__ __forceinline__ void conv1_store4(const Conv1Args &a, i8 *stage, const long long (&cv)[4], int mm, int f0, int chan_bytes, u64 q, int slot, int b)
+// given as centred representatives; sp = the staging byte of (row mm, channel f0, plane 0), the planes pstride bytes apart (conv1_rowtab.h)
+__device__ __forceinline__ void conv1_store4(const Conv1Args &a, i8 *sp, unsigned pstride, const long long (&cv)[4], int mm, int f0, int chan_bytes, u64 q, int slot,
+                                             int b)
 {
     if (mm >= 2 * a.P) return;
-    // limb tensor of the next convolution, staged in LDS as it leaves: [row][plane][32 channels], or the flat form [plane][poly][pixel][zdc]
+    // limb tensor of the next convolution, staged in LDS as it leaves, in the tensor's own layout: [plane][row][32 channels], or the flat form
+    // [plane][poly][pixel][zdc]
     if (a.xl_out) {
         if (f0 >= chan_bytes) return;                                      // (flat form: channel padding is a multiple of 4, this group is past it)
         u32 lo[4], hi[4];
@@ -90,9 +94,6 @@ __device__ __forceinline__ void conv1_store4(const Conv1Args &a, i8 *stage, cons
         pl[2] = __builtin_amdgcn_perm(u1, t1, 0x05040100u); pl[3] = __builtin_amdgcn_perm(u1, t1, 0x07060302u);
         pl[4] = __builtin_amdgcn_perm(u2, t2, 0x05040100u); pl[5] = __builtin_amdgcn_perm(u2, t2, 0x07060302u);
         pl[6] = __builtin_amdgcn_perm(u3, t3, 0x05040100u);
-        i8 *sp; unsigned pstride;
-        if (a.out_zdc) { sp = stage + ((mm & 1) * a.P + (mm >> 1)) * a.out_zdc + f0; pstride = 2 * a.P * a.out_zdc; }
-        else { sp = stage + mm * (NPL * 32) + f0; pstride = 32; }
 #pragma unroll
         for (int l = 0; l < NPL; l++) *reinterpret_cast<u32 *>(sp + l * pstride) = pl[l];
     } else {
@@ -102,21 +103,12 @@ __device__ __forceinline__ void conv1_store4(const Conv1Args &a, i8 *stage, cons
             if (f0 + reg < a.F) a.ys[(((size_t)slot * a.B + b) * a.F + f0 + reg) * (2 * a.P) + mm] = (u64)(cv[reg] + ((cv[reg] >> 63) & (long long)q));
     }
 }
-// the staged limb result of image b leaves as one contiguous block (after a workgroup barrier)
+// the staged limb result of image b leaves as one contiguous block (after a workgroup barrier): the staging area IS the image's byte layout, for either consumer
 __device__ __forceinline__ void conv1_copy_out(const Conv1Args &a, const i8 *stage, int slot, int b)
 {
     i8 *dst = a.xl_out + ((size_t)slot * a.Bout + a.b0 + b) * a.out_img_bytes;
-    if (a.out_zdc) {              // the staging area IS the image's byte layout
-        for (unsigned o = threadIdx.x; o < a.out_img_bytes / 16; o += blockDim.x)
-            *reinterpret_cast<uint4 *>(dst + (size_t)o * 16) = *reinterpret_cast<const uint4 *>(stage + (size_t)o * 16);
-    } else {
-        const unsigned per_plane = a.out_img_bytes / (NPL * 16);      // 16-byte pieces of one plane: (row, half)
-        for (unsigned o = threadIdx.x; o < NPL * per_plane; o += blockDim.x) {
-            const unsigned l = o / per_plane, rem = o - l * per_plane;
-            *reinterpret_cast<uint4 *>(dst + (size_t)o * 16) = *reinterpret_cast<const uint4 *>(stage + (rem >> 1) * (NPL * 32) + l * 32 +
-                (rem & 1) * 16);
-        }
-    }
+    for (unsigned o = threadIdx.x * 16; o < a.out_img_bytes; o += blockDim.x * 16)
+        *reinterpret_cast<uint4 *>(dst + o) = *reinterpret_cast<const uint4 *>(stage + o);
 }
 
 __global__ void __launch_bounds__(768) mfma_conv1_kernel(Conv1Args a)
@@ -192,6 +184,7 @@ __global__ void __launch_bounds__(768) mfma_conv1_kernel(Conv1Args a)
         if (e >= (unsigned)(NPL * 2 * a.P * a.out_zdc)) stage[e] = 0; }
     issue_img(0);
     const int chan_bytes = a.out_zdc ? a.out_zdc : 32;          // channel bytes per (pixel, poly) position of a limb result
+    const unsigned pstride = conv1_stage_plane_stride(a.P, a.out_zdc);
     for (int b = 0; b < a.B; b++) {
         // this wave's pieces of image b have landed (and its stores of image b-1's staging copy have left) ...
         __builtin_amdgcn_s_waitcnt(0 | (7 << 4) | (15 << 8));
@@ -247,9 +240,7 @@ __global__ void __launch_bounds__(768) mfma_conv1_kernel(Conv1Args a)
                 if (a.xl_out) {
                     if (f >= chan_bytes) continue;
                     const u64 dg = f < a.F ? centred_digit_bytes(cvn) : 0;
-                    i8 *sp; unsigned pstride;
-                    if (a.out_zdc) { sp = stage + ((mm & 1) * a.P + (mm >> 1)) * a.out_zdc + f; pstride = 2 * a.P * a.out_zdc; }
-                    else { sp = stage + mm * (NPL * 32) + f; pstride = 32; }
+                    i8 *sp = stage + conv1_stage_row(mm, a.P, a.out_zdc) + f;
 #pragma unroll
                     for (int l = 0; l < NPL; l++) sp[l * pstride] = (i8)(dg >> (8 * l));
                 } else if (f < a.F) a.ys[(((size_t)slot * a.B + b) * a.F + f) * (2 * a.P) + mm] = (u64)(cvn + ((cvn >> 63) & (long long)q));
@@ -272,7 +263,7 @@ __global__ void __launch_bounds__(768) mfma_conv1_kernel(Conv1Args a)
                 // one pass from the diagonals to the centred representative, bias included
                 cv[reg] = diag_fold_short_centred(D, q, qbits, qfold, bvc[reg], PB);
             }
-            conv1_store4(a, stage, cv, mm, f0, chan_bytes, q, slot, b);
+            conv1_store4(a, stage + conv1_stage_row(mm, a.P, a.out_zdc) + f0, pstride, cv, mm, f0, chan_bytes, q, slot, b);
         }
         if (a.xl_out) {
             __syncthreads();
@@ -322,7 +313,6 @@ __global__ void __launch_bounds__(512) mfma_conv1_kernel_px(Conv1Args a)
         const u32 o0 = (u32)(t0 / a.px_yf) * a.px_rs + (u32)(t0 % a.px_yf) * 8, o1 = (u32)(t1 / a.px_yf) * a.px_rs + (u32)(t1 % a.px_yf) * 8;
         toff[j] = o0 | (o1 << 16);
     }
-    const u32 rcp_yo = (65536u + (u32)a.yo - 1) / (u32)a.yo;
     const int f0 = nt * 16 + 4 * g;
     long long bvc[4];
 #pragma unroll
@@ -332,6 +322,25 @@ __global__ void __launch_bounds__(512) mfma_conv1_kernel_px(Conv1Args a)
         bvc[reg] = bv > (q >> 1) ? (long long)(bv - q) : (long long)bv;
     }
     i8 *stage = lds + 2 * (size_t)a.img_stride;
+    // the row table behind the staging area (conv1_rowtab.h): where a row's window starts and where its digits are staged depends on the row alone, and this
+    // workgroup walks the same rows for every image -- one entry per row, filled here.  A tile's entry is read one tile ahead, under the MFMAs of the tile before
+    // (behind a wave's last tile comes its first one again, for the next image): read at the head of its own tile, the LDS round trip would stand in front of
+    // the window reads with nothing to cover it (two waves per SIMD, in step behind the image barrier).  The entries are an ext_vector_type, not HIP's uint2
+    // struct: through a uint2 pointer the compiler cannot tell the table from the LDS-DMA target of the next image and puts an s_waitcnt vmcnt(0) in front of
+    // the read, which holds the tile until that image has landed (both together: 26.4 ms per launch against 25.2 without a table)
+    const v2u *rowtab = reinterpret_cast<const v2u *>(stage + (a.xl_out ? a.out_img_bytes : 0));
+    {
+        const Conv1RowGeom geom{a.P, a.yo, a.xs, a.ystr, a.px_rs, a.poly_bytes, a.out_zdc};
+        for (int mm = threadIdx.x; mm < a.mtiles * 16; mm += blockDim.x) {
+            const Conv1RowEntry e = conv1_row_entry(mm, geom);
+            const_cast<v2u *>(rowtab)[mm] = v2u{e.win, e.stg};
+        }
+    }
+    const v2u *rowtab_lane = rowtab + r16;
+    __syncthreads();
+    v2u row = tile0 < a.mtiles ? rowtab_lane[tile0 * 16] : v2u{0u, 0u};
+    i8 *stage_lane = stage + f0;
+    const unsigned pstride = conv1_stage_plane_stride(a.P, a.out_zdc);
     const i8 *ximg = a.xr + (size_t)slot * a.B * a.img_stride;
     const int pieces = a.img_stride / 1024;
     auto issue_img = [&](int b) {
@@ -351,9 +360,10 @@ __global__ void __launch_bounds__(512) mfma_conv1_kernel_px(Conv1Args a)
         if (b + 1 < a.B) issue_img(b + 1);
         const i8 *img = lds + (b & 1) * (size_t)a.img_stride;
         for (int mt = tile0; mt < a.mtiles; mt += tile_step) {
-            // operand B = this lane's output row: pixel p, poly c (rows past 2P re-read the last one and are never stored)
-            const int mm = mt * 16 + r16, mrow = min(mm, 2 * a.P - 1), p = mrow >> 1, c = mrow & 1, ox = (int)(((u32)p * rcp_yo) >> 16), oy = p - ox * a.yo;
-            const i8 *win = img + c * a.poly_bytes + (u32)(ox * a.xs) * a.px_rs + (u32)(oy * a.ystr) * 8;
+            // operand B = this lane's output row mm (rows past 2P re-read the last one and are never stored): its table entry
+            const int mm = mt * 16 + r16;
+            const v2u cur = row;
+            const i8 *win = img + cur.x;
             v4i bv[NJ];
             if (a.px_pair) {
 #pragma unroll
@@ -365,6 +375,7 @@ __global__ void __launch_bounds__(512) mfma_conv1_kernel_px(Conv1Args a)
                     bv[j] = v4i{(int)t0.x, (int)t0.y, (int)t1.x, (int)t1.y};
                 }
             }
+            row = rowtab_lane[(mt + tile_step < a.mtiles ? mt + tile_step : tile0) * 16];
             v4i acc[NPL];
 #pragma unroll
             for (int m = 0; m < NPL; m++) acc[m] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wv[m][0], bv[0], v4i{0, 0, 0, 0}, 0, 0, 0);
@@ -381,7 +392,7 @@ __global__ void __launch_bounds__(512) mfma_conv1_kernel_px(Conv1Args a)
                 for (int m = 0; m < NPL; m++) E[m] = acc[m][reg];
                 cv[reg] = diag7_fold_centred(E, q, qbits, qfold, bvc[reg], PB);
             }
-            conv1_store4(a, stage, cv, mm, f0, chan_bytes, q, slot, b);
+            conv1_store4(a, stage_lane + cur.y, pstride, cv, mm, f0, chan_bytes, q, slot, b);
         }
         if (a.xl_out) {
             __syncthreads();
@@ -532,6 +543,7 @@ __global__ void __launch_bounds__(256) limb_pack_rows1_kernel_px(const u64 *x, i
 // cuts digits and stages them as the unboxed pass does; barrier; (3) the 32-slot transpose and the 16-byte stores of the unboxed pass.  The next group's loads
 // overwrite only rows this group's sums (before the second barrier) were the last to need, and its staging follows its own first barrier, after these stores.
 #define BOX_LD 16
+static_assert(CONV1_NPL == NPL, "conv1_rowtab.h describes these kernels' digit planes");
 static_assert(BOX_RG == RG && BOX_RSL == RSL, "boxstage.h describes this pack's workgroup");
 __global__ void __launch_bounds__(256) limb_pack_box_kernel_px(const u64 *x, i8 *xr, const ModParams *mods, int n, int k, int B, int xd, int yd, int packed,
                                                                unsigned img_stride, unsigned poly_bytes, unsigned rs, int xdo, int ydo, int bxf, int byf, int xs,
@@ -647,10 +659,11 @@ static inline unsigned conv1_img_stride(int xd) { const unsigned b = NPL * 2 * c
 static inline unsigned conv1_px_rs(int yd) { return ((unsigned)yd * 8 + 15) / 16 * 16; }
 static inline unsigned conv1_px_poly_bytes(int xd, int yd) { const unsigned b = (unsigned)xd * conv1_px_rs(yd); return b + (128 + 256 - b % 256) % 256; }
 static inline unsigned conv1_px_img_stride(int xd, int yd) { return (2 * conv1_px_poly_bytes(xd, yd) + 1023) / 1024 * 1024; }
-static bool conv1_fits(unsigned img_stride, const Window &w)
+static bool conv1_fits(unsigned img_stride, const Window &w, bool px)
 {
-    // two image buffers + the staging area of a limb result (at most 32 channel bytes per position) must fit the 160 KiB of LDS
-    return 2 * (size_t)img_stride + (size_t)NPL * w.xo() * w.yo() * 2 * 32 <= 160 * 1024;
+    // two image buffers + the staging area of a limb result (at most 32 channel bytes per position) + the pixel-major form's row table (conv1_rowtab.h) must fit
+    // the 160 KiB of LDS
+    return 2 * (size_t)img_stride + (size_t)NPL * w.xo() * w.yo() * 2 * 32 + (px ? conv1_rowtab_bytes(w.xo() * w.yo()) : 0) <= 160 * 1024;
 }
 // Which form a layer runs: 1 plane-major (mfma_conv1_kernel), 2 pixel-major (mfma_conv1_kernel_px).  Decided by the tuning switch, the window and the filter
 // count ALONE, so that the weights (packed without knowing the image) and every later launch agree; conv1_narrow does not enter (the tests flip it between
@@ -675,7 +688,8 @@ bool k_limb_conv1_shape(const crc_ctx *c, const LayerShape &s)
     for (int i = 0; i < c->k; i++) if (!conv1_fold_ok(c->tabs[i].m.q, c->tabs[i].m.bits, fold_constant(c->tabs[i].m.q, c->tabs[i].m.bits))) return false;
     if (s.w.P() > 1024) return false;                              // (the kernel's reciprocal division of a pixel index by yo <= 32 is exact below 2048)
     // (the pixel-major image is the smaller one up to 28 columns; wider than that it can be up to 14 % larger)
-    return conv1_fits(k_limb_conv1_form(c, xf, yf, nf) == 2 ? conv1_px_img_stride(xd, yd) : conv1_img_stride(xd), s.w);
+    const bool px = k_limb_conv1_form(c, xf, yf, nf) == 2;
+    return conv1_fits(px ? conv1_px_img_stride(xd, yd) : conv1_img_stride(xd), s.w, px);
 }
 // A box (input-side window sum, limb_pack_rows1_kernel_px) in front of a layer with base window xf x yf: the pixel-major form only, at most 9 terms (sum_reduce16's
 // bound with room to spare), and the SUMMED image must be a shape the kernel takes
@@ -727,7 +741,7 @@ int k_limb_conv1(crc_ctx *c, const u64 *x, bool packed, i8 *xr, const i8 *wl, u6
         a.mtiles = (2 * a.P + 15) / 16;
     // (the limb tensor of the convolution behind: its layout follows ITS channel count = this layer's filters)
     a.out_zdc = a.P > 1 ? k_limb_flat_zdc(nf) : 0;
-    a.out_img_bytes = a.out_zdc ? (unsigned)((NPL * 2 * a.P * a.out_zdc + 15) / 16 * 16) : (unsigned)(NPL * a.P * 2 * 32);
+    a.out_img_bytes = conv1_stage_bytes(a.P, a.out_zdc);
     conv1_tables(c, a);
     const size_t pack_blocks = (size_t)(c->n / RSL) * c->k * B * 2 * ((xd + RG - 1) / RG);
     if (pack_blocks > 0x7fffffffULL) return CRC_ERR_INVALID_ARGUMENT;
@@ -750,7 +764,7 @@ int k_limb_conv1(crc_ctx *c, const u64 *x, bool packed, i8 *xr, const i8 *wl, u6
                 B, xd_in, yd_in, packed ? 1 : 0, a.img_stride, a.poly_bytes, a.px_rs, xd, yd, 1, 1, xs, w.ys);
         HIPCHK(hipGetLastError());
         // (140 registers of resident weights: two waves per SIMD, whatever conv1_waves asks for)
-        const size_t lds = 2 * (size_t)a.img_stride + (xl_out ? a.out_img_bytes : 0);
+        const size_t lds = 2 * (size_t)a.img_stride + (xl_out ? a.out_img_bytes : 0) + conv1_rowtab_bytes(a.P);
         { const int rc = crc_ctx_ensure_lds(c, (const void *)mfma_conv1_kernel_px, lds); if (rc) return rc; }
         hipLaunchKernelGGL(mfma_conv1_kernel_px, dim3((unsigned)(c->n * c->k)), dim3(64 * 8), lds, st, a);
         HIPCHK(hipGetLastError());
