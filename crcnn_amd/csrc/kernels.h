@@ -2,9 +2,7 @@
 #pragma once
 #include "ctx.h"
 #include "window.h"
-
-// grid of a launch whose workgroups are mapped by xcd_group (ntt_device.h): `groups` groups of G workgroups, each group on one XCD
-static inline unsigned xcd_grid(size_t groups, unsigned G) { return (unsigned)((groups + 7) / 8 * 8 * G); }
+#include "xcd_grid.h"
 
 int k_ntt_ct(crc_ctx *c, bool inv, const u64 *src, u64 *dst, size_t count, int size, bool bsk, hipStream_t st,
              const u64 *addend, int add_sign, size_t add_group, int add_mod = 0, int pack_out = 0);

@@ -6,8 +6,10 @@
 // 512 B (8 B/lane) or 1 KiB (16 B/lane) wave transaction.
 #include "kernels.h"
 #include "nttbox.h"
+#include "ntt_select.h"
 #include <type_traits>
 #include <cstdlib>
+#include <algorithm>
 
 // ---------------------------------------------------------------------------------------------------------------
 // NTT: one workgroup per row, whole polynomial staged in LDS (32 KiB @ n=4096 ... 128 KiB @ n=16384).
@@ -27,27 +29,28 @@ struct NttArgs {
     int pack_out;                                              // forward only: store the result as 28-bit limb pairs (operand form of the MAC kernels)
     // both > 0: dst row r = (ct, j < dst_ct_rows) reads src row ct*src_ct_rows + j (leading polys of wider cts)
     int src_ct_rows, dst_ct_rows;
-    // 0 none, 1 plain lift, 2 delta scale, 3 relinearisation digit, 4 square products, 5 (inverse) scaled result, 6 products of two ciphertexts
+    // an NttPrologue (ntt_select.h): 0 none, 1 plain lift, 2 delta scale, 3 relinearisation digit, 4 square products, 5 (inverse) scaled result, 6 products of
+    // two ciphertexts
     int prologue;
-    // prologue 3 (forward): row = ((ct*D + g)*k + j); the source row is the premultiplied third polynomial c2 (q/q_i)^-1 mod q_i of ciphertext ct under
+    // NTT_PRO_DIGIT (forward): row = ((ct*D + g)*k + j); the source row is the premultiplied third polynomial c2 (q/q_i)^-1 mod q_i of ciphertext ct under
     //   modulus i = dig_i[g] (src = size-`src_size` ciphertexts, poly `src_poly`); the value fed to the transform is its digit (v >> dig_shift[g]) & dig_mask
     //   (relinearize_one_step, evaluator.cpp:984-1001) -- the digit polynomials never exist in memory
-    // prologue 4 (inverse): row = ((ct*3 + p)*mod_count + j); sources are the NTT-form rows a, b of polys 0 and 1 of ciphertext ct in `src`
+    // NTT_PRO_SQUARE (inverse): row = ((ct*3 + p)*mod_count + j); sources are the NTT-form rows a, b of polys 0 and 1 of ciphertext ct in `src`
     //   ([ct][2][mod_count][n]); the value fed to the transform is a^2, 2ab or b^2 (Evaluator::square's dyadic products, evaluator.cpp:798-852).
     //   The three products of one (ciphertext, modulus) pair run on ONE XCD, blockIdx -> row through xcd_group; `pairs` = ciphertexts x mod_count
-    // prologue 6 (inverse): prologue 4 for two DIFFERENT ciphertexts x = (a, b) in `src` and y = (c, d) in `fma_k` (an inverse transform has no other use for that
+    // NTT_PRO_PRODUCT (inverse): NTT_PRO_SQUARE for two DIFFERENT ciphertexts x = (a, b) in `src` and y = (c, d) in `fma_k` (an inverse transform has no other use for that
     //   pointer; both [ct][2][mod_count][n]): the value fed to the transform is ac, ad + bc or bd (Evaluator::multiply's tensor product, evaluator.cpp:398-700;
-    //   the reference forms the middle term as (a + b)(c + d) - ac - bd, the same residue).  Rows, XCD grouping, opt_mul as at prologue 4
-    // prologue 5 (inverse): the result leaves multiplied by the per-modulus constant post_mul (Shoup companion post_mul_s) -- the square's lift wants
+    //   the reference forms the middle term as (a + b)(c + d) - ac - bd, the same residue).  Rows, XCD grouping, opt_mul as at NTT_PRO_SQUARE
+    // NTT_PRO_SCALED (inverse): the result leaves multiplied by the per-modulus constant post_mul (Shoup companion post_mul_s) -- the square's lift wants
     //   x m~ (q/q_i)^-1 mod q_i (baseconverter.cpp:686-696), and the Shoup multiplication takes the lazy value in place of the final reduction
     int D, src_size, src_poly; unsigned long long dig_mask;
     size_t pairs;
     u64 post_mul[CRC_MAXK], post_mul_s[CRC_MAXK];
     // forward transforms of size-2 ciphertexts that leave as  NTT(row) + fma_u[ct][i] . fma_k[p][i]  (the device encryptor: noise rows + pk . NTT(u));
-    // null: off
+    // null: off.  Which of fma_u, fma_k and fma_neg are set names the fused product, an NttFma (ntt_select.h; ntt_request below)
     const u64 *fma_u, *fma_k;
     unsigned long long fma_group;                              // fma_u null, fma_k set: the rows leave multiplied by the plaintext row fma_k[ct / fma_group][i]
-    // host side only, prologue 4: 1 = post_mul is OFFERED -- a kernel that closes with a multiplication anyway takes it in (and says so: 2), the others
+    // host side only, NTT_PRO_SQUARE and NTT_PRO_PRODUCT: 1 = post_mul is OFFERED -- a kernel that closes with a multiplication anyway takes it in (and says so: 2), the others
     // ignore it
     int opt_mul;
     unsigned char dig_i[48], dig_shift[48];
@@ -200,10 +203,10 @@ __global__ void __launch_bounds__(1024) ntt_rows_kernel(NttArgs a) { ntt_rows_bo
 
 // ONE workgroup barrier per transform (round 5; ntt_f64.h: wave-local passes) for the lazy 64-bit transforms at n = 4096 / 8192 / 16384: n / 16 threads, wave w
 // owns the 1024-point block w.  Forward: 16-byte loads in the cross layout -> the three cross stages in registers -> image | barrier | three wave-local passes
-// -> block-local drain through the gap-1 stage.  Inverse: block-local fill through the gap-1 stage (PRO 4: the square's products formed on the way) -> three
-// wave-local passes | barrier | the cross stages from the image to registers -> final reduction (PRO 5: the scaled result) -> 16-byte stores.  Same butterflies
-// on the same values as ntt_rows_body, hence the same results.  Prologues 0 / 4 / 5 without an addend; everything else stays with ntt_rows_kernel.
-// BOX (forward, prologue 0, no FMA: k_ntt_ct_box): the row fed to the transform is the sum of the bxf byf source rows of a window (a.box, nttbox.h), taken while
+// -> block-local drain through the gap-1 stage.  Inverse: block-local fill through the gap-1 stage (PRO = NTT_PRO_SQUARE: the square's products formed on the way) -> three
+// wave-local passes | barrier | the cross stages from the image to registers -> final reduction (NTT_PRO_SCALED: the scaled result) -> 16-byte stores.  Same butterflies
+// on the same values as ntt_rows_body, hence the same results.  Prologues NONE, SQUARE, SCALED and PRODUCT without an addend; everything else stays with ntt_rows_kernel.
+// BOX (forward, NTT_PRO_NONE, no FMA: k_ntt_ct_box): the row fed to the transform is the sum of the bxf byf source rows of a window (a.box, nttbox.h), taken while
 // they are loaded: the terms are canonical residues below 2^55, at most 9 of them, summed in 64 bits (below 2^59) and reduced ONCE to [0, q) (sum_reduce16), so
 // the butterflies see what they see without a box and every operand bound holds as documented.  NTT(sum x_j) = sum NTT(x_j) mod q, both canonical: bit for
 // bit what transforming every term and summing afterwards gives.  The loads run in two halves of 8 points; within a half the next term's loads are issued before
@@ -374,7 +377,7 @@ __global__ void __launch_bounds__(CS == 1 ? 128 : CS == 2 ? 256 : CS == 3 ? 512 
         f64_wave_sync();
         if (UNS) u64_local_passes_inv_unscaled(sm, W, n, q, q2, rq); else u64_local_passes_inv<true>(sm, W, n, q, q2);
         __syncthreads();
-        // (UNS: every prologue ends in the multiplication -- by n^-1, times the caller's constant at prologue 5; the host put the product into post_mul)
+        // (UNS: every prologue ends in the multiplication -- by n^-1, times the caller's constant at NTT_PRO_SCALED; the host put the product into post_mul)
         const u64 pm = PRO == 5 || UNS ? a.post_mul[mloc] : 0, pms = PRO == 5 || UNS ? a.post_mul_s[mloc] : 0;
         u64 x[16];
 #pragma unroll
@@ -642,134 +645,101 @@ __global__ void __launch_bounds__(1024) ntt_rows_prefetch_kernel(NttArgs a)
     }
 }
 
-// lazy butterflies need (1 + 4 log2 n) q < 2^64 (and the float quotient estimate a q of 45+ bits): every coefficient modulus of the
-// reference's parameter sets qualifies (54..55 bits), the 61-bit auxiliary base of Square does not
-static bool ntt_lazy_moduli(const crc_ctx *c, int mod_base, int mod_count)
+// ---- host side: ntt_select (ntt_select.h) decides, ntt_launch launches ---------------------------------------------------------------------------------------
+typedef void (*NttKernel)(NttArgs);
+// a run-time bool / int as a compile-time one: f gets a std::integral_constant, pick_int of exactly the values listed (another: null)
+template <class F> static NttKernel pick_bool(bool v, F f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
+template <int... V, class F> static NttKernel pick_int(int v, F f) { NttKernel k = nullptr; (void)((v == V && ((k = f(std::integral_constant<int, V>{})), true)) || ...); return k; }
+// the choice's template arguments passed straight through, once per family; the constexpr rules of ntt_select.h say which combinations exist
+static NttKernel ntt_kernel_of(const NttChoice &k)
 {
-    for (int i = mod_base; i < mod_base + mod_count; i++) if (c->tabs[i].m.bits > 57 || c->tabs[i].m.bits < 45) return false;
-    return true;
+    if (k.family == NTT_FAM_WAVE)
+        return pick_int<1, 2, 3, 4>(k.cs, [&](auto CS) {
+        return pick_bool(k.inv, [&](auto INV) {
+        return pick_int<NTT_PRO_NONE, NTT_PRO_SQUARE, NTT_PRO_SCALED, NTT_PRO_PRODUCT>(k.pro, [&](auto PRO) {
+        return pick_bool(k.uns, [&](auto UNS) {
+        return pick_int<NTT_FMA_NONE, NTT_FMA_ADD, NTT_FMA_MUL, NTT_FMA_NEG>(k.fma, [&](auto FMA) {
+        return pick_bool(k.box, [&](auto BOX) -> NttKernel {
+            if constexpr (ntt_wave_instance(INV, PRO, UNS, FMA, BOX)) return ntt_rows_wave_kernel<INV, PRO, CS, UNS, FMA, BOX>;
+            else return nullptr;
+        }); }); }); }); }); });
+    if (k.family == NTT_FAM_INV61)
+        return pick_int<NTT_PRO_NONE, NTT_PRO_SQUARE, NTT_PRO_PRODUCT>(k.pro, [](auto PRO) -> NttKernel { return ntt_rows_inv61_kernel<PRO>; });
+    return pick_bool(k.inv, [&](auto INV) {
+    return pick_bool(k.lazy, [&](auto LAZY) -> NttKernel {
+        if (k.family == NTT_FAM_PREFETCH) return ntt_rows_prefetch_kernel<INV, LAZY>;
+        return pick_int<NTT_PRO_NONE, NTT_PRO_DIGIT, NTT_PRO_SQUARE, NTT_PRO_SCALED, NTT_PRO_PRODUCT>(k.pro, [&](auto PRO) -> NttKernel {
+            if constexpr (!ntt_prologue_dir_ok(INV, PRO)) return nullptr;
+            else if (k.family == NTT_FAM_SPLIT) return ntt_rows_split_kernel<INV, LAZY, PRO>;
+            else return ntt_rows_kernel<INV, LAZY, PRO>;
+        });
+    }); });
 }
-// the ring's bit of CRC_NTT_WAVE is on (ntt_launch below has the bits): the ring has a wave-local kernel and the tuning has not switched it off
-static bool ntt_wave_ring(const crc_ctx *c, bool with_prologue)
+static NttRing ntt_ring(const crc_ctx *c, int mod_base, int mod_count)
 {
-    const int sel = c->tune.ntt_wave < 0 ? 47 : c->tune.ntt_wave;
-    const int bit = c->n == 8192 ? 0 : c->n == 4096 ? 1 : c->n == 16384 ? (with_prologue ? 3 : 2) : c->n == 2048 ? 5 : -1;
-    return bit >= 0 && ((sel >> bit) & 1);
+    NttRing g{c->n, c->logn, c->cus, c->tune.ntt_wave, c->tune.ntt_split, c->tune.ntt_inv61_loose, mod_count, 64, 0, true};
+    for (int i = mod_base; i < mod_base + mod_count; i++) {
+        const ModParams &m = c->tabs[i].m;
+        g.min_bits = std::min(g.min_bits, (int)m.bits); g.max_bits = std::max(g.max_bits, (int)m.bits); g.below55 = g.below55 && m.q < (1ull << 55);
+    }
+    return g;
+}
+static NttRequest ntt_request(bool inv, const NttArgs &a, size_t rows)
+{
+    NttRequest r{}; r.inv = inv; r.prologue = a.prologue; r.addend = a.addend != nullptr; r.pack_out = a.pack_out != 0; r.box = a.box_images != 0; r.opt_mul = a.opt_mul != 0;
+    r.rows = rows; r.pairs = a.pairs; r.fma_u = a.fma_u != nullptr; r.in_place = a.src == a.dst; r.src_ct_rows = a.src_ct_rows; r.dst_ct_rows = a.dst_ct_rows;
+    // the fused product has no field of its own: the pointers say which (at NTT_PRO_PRODUCT fma_k is the second ciphertext, not an epilogue)
+    if (a.prologue != NTT_PRO_PRODUCT && (a.fma_u || a.fma_k)) r.fma = a.fma_neg ? NTT_FMA_NEG : a.fma_u ? NTT_FMA_ADD : NTT_FMA_MUL;
+    return r;
+}
+// the unscaled inverse ends in a multiplication by n^-1: times the constant already in post_mul where the kernel takes that in (and opt_mul says so: 2)
+static void ntt_fold_inv_n(const crc_ctx *c, NttArgs &a, bool takes_post_mul)
+{
+    for (int i = 0; i < a.mod_count; i++) {
+        const HostNtt &T = c->tabs[a.mod_base + i]; const u64 q = T.m.q, pm = takes_post_mul ? (u64)(((unsigned __int128)a.post_mul[i] * T.inv_n) % q) : T.inv_n;
+        a.post_mul[i] = pm; a.post_mul_s[i] = (u64)(((unsigned __int128)pm << 64) / q);
+    }
+    if (a.opt_mul) a.opt_mul = 2;
 }
 static int ntt_launch(crc_ctx *c, bool inv, NttArgs &a, size_t rows, hipStream_t st)
 {
-    if (rows == 0) return CRC_OK;
-    a.mods = c->d_mods; a.n = c->n; a.logn = c->logn;
-    a.w = reinterpret_cast<const ulonglong2 *>(inv ? c->d_irp2 : c->d_rp);
-    int nt = c->n / 8; if (nt < 64) nt = 64; if (nt > 1024) nt = 1024;
-    size_t lds = (size_t)c->n * 8;
-    if (lds > 128 * 1024) return CRC_ERR_UNSUPPORTED;                   // (n = 32768: the row does not fit one workgroup's LDS image, in halves or whole)
-    const bool lazy = ntt_lazy_moduli(c, a.mod_base, a.mod_count);
-    const int cus = c->cus;
-    if ((a.prologue == 3 && inv) || ((a.prologue == 4 || a.prologue == 5 || a.prologue == 6) && !inv)) return CRC_ERR_INVALID_ARGUMENT;
-    const bool two_src = a.prologue == 6;                               // (fma_k is the second ciphertext there, not an epilogue)
-    if (a.prologue == 4 || two_src) rows = xcd_grid(a.pairs, 3);                  // (the three products of a pair on one XCD: ntt_rows_body)
-    // wave-local passes (ntt_rows_wave_kernel): CRC_NTT_WAVE bit 0 n = 8192, bit 1 n = 4096, bit 2 n = 16384 (plain transforms), bit 3 n = 16384 with the
-    // Square prologues (slower than the split kernel with the halving butterflies, 11.9 against 11.7 us per squared ciphertext, faster with the ones that do
-    // not halve: 11.27 against 11.6 -- profiles/r05_ntt_u64_wave_local_ab.txt, r05_ntt_inverse_unscaled_ab.txt), bit 4: keep the halving butterflies; -1: bits
-    // 0 to 3 and 5
-    {
-        // (bit 5, round 6: n = 2048 -- one cross stage, two waves per workgroup)
-        const int sel = c->tune.ntt_wave < 0 ? 47 : c->tune.ntt_wave;
-        if (ntt_wave_ring(c, a.prologue != 0) && lazy && !a.addend && (a.prologue == 0 || a.prologue == 4 || a.prologue == 5 || two_src)) {
-            lds = (size_t)c->n * 8;
-            // inverse transforms over moduli below 2^55 take the butterflies that do not halve (inv_stages_unscaled; CRC_NTT_WAVE bit 4 switches them off): the
-            // table of plain inverse powers, and n^-1 in the constant of the closing multiplication
-            bool uns = inv && !(sel & 16);
-            for (int i = 0; i < a.mod_count; i++) uns = uns && c->tabs[a.mod_base + i].m.q < (1ull << 55);
-            if (uns) {
-                a.w = reinterpret_cast<const ulonglong2 *>(c->d_irp);
-                for (int i = 0; i < a.mod_count; i++) {
-                    const HostNtt &T = c->tabs[a.mod_base + i]; const u64 q = T.m.q;
-                    const u64 pm = a.prologue == 5 || a.opt_mul ? (u64)(((unsigned __int128)a.post_mul[i] * T.inv_n) % q) : T.inv_n;
-                    a.post_mul[i] = pm; a.post_mul_s[i] = (u64)(((unsigned __int128)pm << 64) / q);
-                }
-                if (a.opt_mul) a.opt_mul = 2;
-            }
-            const int cs = c->logn - 10;
-#define WAVEK(CSV, U) (two_src ? ntt_rows_wave_kernel<true, 6, CSV, U> : a.prologue == 4 ? ntt_rows_wave_kernel<true, 4, CSV, U> : a.prologue == 5 ? ntt_rows_wave_kernel<true, 5, CSV, U> \
-                       : inv ? ntt_rows_wave_kernel<true, 0, CSV, U> : ntt_rows_wave_kernel<false, 0, CSV, false>)
-#define WAVECS(U) (cs == 1 ? WAVEK(1, U) : cs == 2 ? WAVEK(2, U) : cs == 3 ? WAVEK(3, U) : WAVEK(4, U))
-#define WAVEF(FV) (cs == 1 ? ntt_rows_wave_kernel<false, 0, 1, false, FV> : cs == 2 ? ntt_rows_wave_kernel<false, 0, 2, false, FV> \
-                   : cs == 3 ? ntt_rows_wave_kernel<false, 0, 3, false, FV> : ntt_rows_wave_kernel<false, 0, 4, false, FV>)
-            auto kw = uns ? WAVECS(true) : WAVECS(false);
-            if (!two_src && (a.fma_u || a.fma_k)) {
-                if (inv || a.prologue || a.pack_out) return CRC_ERR_INVALID_ARGUMENT;
-                if (a.fma_neg && (a.fma_u || a.src != a.dst || a.dst_ct_rows != a.mod_count || a.src_ct_rows != 2 * a.mod_count)) return CRC_ERR_INVALID_ARGUMENT;
-                kw = a.fma_neg ? WAVEF(3) : a.fma_u ? WAVEF(1) : WAVEF(2);
-            }
-#undef WAVEF
-#undef WAVECS
-#undef WAVEK
-            { const int rc = crc_ctx_ensure_lds(c, (const void *)kw, lds); if (rc) return rc; }
-            hipLaunchKernelGGL(kw, dim3((unsigned)rows), dim3(c->n / 16), lds, st, a);
-            HIPCHK(hipGetLastError());
-            return CRC_OK;
-        }
-    }
-    // n = 16384: the row as two halves through a 64-KiB image -- two workgroups per CU (ntt_rows_split_body)
-    if (!two_src && (a.fma_u || a.fma_k)) return CRC_ERR_UNSUPPORTED;   // (only the wave-local kernel above has those epilogues; the caller runs the product as a pass of its own)
-    if (c->n == 16384 && nt == 1024 && c->tune.ntt_split != 0) {
-        lds /= 2;
-        auto ks = two_src ? (lazy ? ntt_rows_split_kernel<true, true, 6> : ntt_rows_split_kernel<true, false, 6>)
-                : a.prologue == 4 ? (lazy ? ntt_rows_split_kernel<true, true, 4> : ntt_rows_split_kernel<true, false, 4>)
-                : a.prologue == 5 ? (lazy ? ntt_rows_split_kernel<true, true, 5> : ntt_rows_split_kernel<true, false, 5>)
-                : a.prologue == 3 ? (lazy ? ntt_rows_split_kernel<false, true, 3> : ntt_rows_split_kernel<false, false, 3>)
-                : inv ? (lazy ? ntt_rows_split_kernel<true, true, 0> : ntt_rows_split_kernel<true, false, 0>) : (lazy ? ntt_rows_split_kernel<false, true,
-                    0> : ntt_rows_split_kernel<false, false, 0>);
-        hipLaunchKernelGGL(ks, dim3((unsigned)rows), dim3(nt), lds, st, a);
-        HIPCHK(hipGetLastError());
-        return CRC_OK;
-    }
-    if (c->n / nt == 16 && rows > (size_t)cus && a.prologue < 3) {     // n = 16384: one resident workgroup per CU, prefetching the next row
-        a.rows = rows;
-        auto pk = inv ? (lazy ? ntt_rows_prefetch_kernel<true, true> : ntt_rows_prefetch_kernel<true, false>) : (lazy ? ntt_rows_prefetch_kernel<false,
-            true> : ntt_rows_prefetch_kernel<false, false>);
-        { const int rc = crc_ctx_ensure_lds(c, (const void *)pk, lds); if (rc) return rc; }
-        hipLaunchKernelGGL(pk, dim3((unsigned)cus), dim3(nt), lds, st, a);
-        HIPCHK(hipGetLastError());
-        return CRC_OK;
-    }
-    if ((a.prologue == 3 && inv) || (a.prologue == 4 && !inv)) return CRC_ERR_INVALID_ARGUMENT;
-    const bool strict61 = !c->tune.ntt_inv61_loose;
-    auto kern = two_src ? (lazy ? ntt_rows_kernel<true, true, 6> : strict61 ? ntt_rows_inv61_kernel<6> : ntt_rows_kernel<true, false, 6>)
-              : a.prologue == 4 ? (lazy ? ntt_rows_kernel<true, true, 4> : strict61 ? ntt_rows_inv61_kernel<4> : ntt_rows_kernel<true, false, 4>)
-              : a.prologue == 5 ? (lazy ? ntt_rows_kernel<true, true, 5> : ntt_rows_kernel<true, false, 5>)
-              : a.prologue == 3 ? (lazy ? ntt_rows_kernel<false, true, 3> : ntt_rows_kernel<false, false, 3>)
-              : inv ? (lazy ? ntt_rows_kernel<true, true, 0> : strict61 ? ntt_rows_inv61_kernel<0> : ntt_rows_kernel<true, false, 0>) : (lazy ?
-                  ntt_rows_kernel<false, true, 0> : ntt_rows_kernel<false, false, 0>);
-    { const int rc = crc_ctx_ensure_lds(c, (const void *)kern, lds); if (rc) return rc; }
-    hipLaunchKernelGGL(kern, dim3((unsigned)rows), dim3(nt), lds, st, a);
+    a.mods = c->d_mods; a.n = c->n; a.logn = c->logn; a.rows = rows;
+    const NttChoice k = ntt_select(ntt_ring(c, a.mod_base, a.mod_count), ntt_request(inv, a, rows));
+    if (!k.launch) return k.status;
+    const NttKernel kern = ntt_kernel_of(k);
+    if (!kern) return CRC_ERR_INVALID_ARGUMENT;                  // (a choice without an instantiation: none today; `a` is still as the caller left it)
+    a.w = reinterpret_cast<const ulonglong2 *>(k.uns ? c->d_irp : inv ? c->d_irp2 : c->d_rp);   // (uns: the table of plain inverse powers)
+    if (k.uns) ntt_fold_inv_n(c, a, k.takes_post_mul);
+    { const int rc = crc_ctx_ensure_lds(c, (const void *)kern, k.lds); if (rc) return rc; }
+    hipLaunchKernelGGL(kern, dim3((unsigned)k.grid), dim3(k.block), k.lds, st, a);
     HIPCHK(hipGetLastError());
     return CRC_OK;
+}
+// the fields every caller of ntt_launch sets: rows src -> dst over q (bsk: over Bsk), `polys` polynomials to a ciphertext, an addend (if any) per ciphertext
+static NttArgs ntt_args(const crc_ctx *c, const u64 *src, u64 *dst, int polys, bool bsk = false)
+{
+    NttArgs a{}; a.src = src; a.dst = dst; a.mod_base = bsk ? c->k : 0; a.mod_count = bsk ? c->kb : c->k; a.rows_per_ct = polys * a.mod_count; a.add_group = 1; a.add_mode = 1;
+    return a;
 }
 
 int k_ntt_ct(crc_ctx *c, bool inv, const u64 *src, u64 *dst, size_t count, int size, bool bsk, hipStream_t st,
              const u64 *addend, int add_sign, size_t add_group, int add_mod, int pack_out)
 {
-    NttArgs a{};
-    a.pack_out = inv ? 0 : pack_out;
-    a.src = src; a.dst = dst;
-    a.mod_base = bsk ? c->k : 0; a.mod_count = bsk ? c->kb : c->k;
-    a.addend = addend; a.add_sign = add_sign; a.rows_per_ct = size * a.mod_count; a.add_group = (long long)(add_group ? add_group : 1);
-    a.add_mode = 1; a.add_mod = add_mod;
+    NttArgs a = ntt_args(c, src, dst, size, bsk);
+    a.pack_out = inv ? 0 : pack_out; a.addend = addend; a.add_sign = add_sign; a.add_group = (long long)(add_group ? add_group : 1); a.add_mod = add_mod;
     return ntt_launch(c, inv, a, count * size * a.mod_count, st);
 }
 
 // The boxed forward transform: src = B images of xd x yd coefficient-form size-2 ciphertexts, dst = B images of xdo x ydo NTT-form ones, each the transform of
 // the bxf x byf window sum of the input at dilation (xs, ys) (nttbox.h; ntt_rows_wave_kernel<.., BOX = true>); src != dst.  Only the wave-local kernel has the
-// box: CRC_ERR_UNSUPPORTED exactly where ntt_launch would not take that kernel for a plain forward transform, and for more than 9 terms.
+// box: CRC_ERR_UNSUPPORTED exactly where ntt_select does not take that kernel for a plain forward transform, and for more than 9 terms.
 // order: the block -> row map of nttbox.h (1: XCD-grouped, 0: plain).  NTT_BOX_ORDER is the one that measured faster (profiles/ntt_box.md); the tuning key
 // box_ntt = 2 runs the other
 #define NTT_BOX_ORDER 1
 bool k_ntt_ct_box_supported(const crc_ctx *c, int bxf, int byf)
 {
-    return bxf >= 1 && byf >= 1 && bxf * byf <= NTTBOX_MAX_TERMS && ntt_wave_ring(c, false) && ntt_lazy_moduli(c, 0, c->k);
+    NttRequest r{}; r.box = true; r.rows = 1;
+    return bxf >= 1 && byf >= 1 && bxf * byf <= NTTBOX_MAX_TERMS && ntt_select(ntt_ring(c, 0, c->k), r).status == CRC_OK;
 }
 int k_ntt_ct_box(crc_ctx *c, const u64 *src, u64 *dst, int B, int xd, int yd, int bxf, int byf, int xs, int ys, hipStream_t st)
 {
@@ -777,29 +747,18 @@ int k_ntt_ct_box(crc_ctx *c, const u64 *src, u64 *dst, int B, int xd, int yd, in
     if (B < 0 || !nttbox_ok(g) || src == dst) return CRC_ERR_INVALID_ARGUMENT;
     if (!k_ntt_ct_box_supported(c, bxf, byf)) return CRC_ERR_UNSUPPORTED;
     if (B == 0) return CRC_OK;
-    NttArgs a{};
-    a.src = src; a.dst = dst; a.mods = c->d_mods; a.n = c->n; a.logn = c->logn; a.w = reinterpret_cast<const ulonglong2 *>(c->d_rp);
-    a.mod_base = 0; a.mod_count = c->k;
-    a.box = g; a.box_images = (unsigned)B; a.box_order = c->tune.box_ntt == 2 ? 1 - NTT_BOX_ORDER : NTT_BOX_ORDER;
+    NttArgs a = ntt_args(c, src, dst, 2);
+    a.box = g; a.box_images = (unsigned)B; a.box_order = c->tune.box_ntt == 2 ? 1 - NTT_BOX_ORDER : NTT_BOX_ORDER;   // (box_images > 0: the request has a box)
     const size_t grid = nttbox_grid(a.box_order, (size_t)B, g, c->k);
     if (grid > 0x7fffffffULL) return CRC_ERR_INVALID_ARGUMENT;            // (blocks and rows fit 31 bits: nttbox_block_row)
-    const int cs = c->logn - 10;
-    auto kw = cs == 1 ? ntt_rows_wave_kernel<false, 0, 1, false, 0, true> : cs == 2 ? ntt_rows_wave_kernel<false, 0, 2, false, 0, true>
-            : cs == 3 ? ntt_rows_wave_kernel<false, 0, 3, false, 0, true> : ntt_rows_wave_kernel<false, 0, 4, false, 0, true>;
-    const size_t lds = (size_t)c->n * 8;
-    { const int rc = crc_ctx_ensure_lds(c, (const void *)kw, lds); if (rc) return rc; }
-    hipLaunchKernelGGL(kw, dim3((unsigned)grid), dim3(c->n / 16), lds, st, a);
-    HIPCHK(hipGetLastError());
-    return CRC_OK;
+    return ntt_launch(c, false, a, grid, st);
 }
 
 // forward NTT in place of size-2 ciphertexts that leave as NTT(row) + u[ct][i] . key[p][i] (u: [count][k][n], key: [2][k][n], both NTT form) -- the device
 // encryptor's last step.  CRC_ERR_UNSUPPORTED where the ring has no wave-local kernel: the caller then transforms and multiplies in two passes
 int k_ntt_ct_fwd_fma(crc_ctx *c, u64 *ct, size_t count, const u64 *u, const u64 *key, hipStream_t st)
 {
-    NttArgs a{};
-    a.src = ct; a.dst = ct; a.mod_base = 0; a.mod_count = c->k; a.rows_per_ct = 2 * c->k; a.add_group = 1; a.add_mode = 1;
-    a.fma_u = u; a.fma_k = key;
+    NttArgs a = ntt_args(c, ct, ct, 2); a.fma_u = u; a.fma_k = key;
     return ntt_launch(c, false, a, count * 2 * c->k, st);
 }
 
@@ -807,18 +766,15 @@ int k_ntt_ct_fwd_fma(crc_ctx *c, u64 *ct, size_t count, const u64 *u, const u64 
 // form) -- the secret-key encryptor's last step, k of a ciphertext's 2k rows.  CRC_ERR_UNSUPPORTED where the ring has no wave-local kernel
 int k_ntt_ct_fwd_negmul(crc_ctx *c, u64 *ct, size_t count, const u64 *sk, hipStream_t st)
 {
-    NttArgs a{};
-    a.src = ct; a.dst = ct; a.mod_base = 0; a.mod_count = c->k; a.rows_per_ct = 2 * c->k; a.add_group = 1; a.add_mode = 1;
-    a.src_ct_rows = 2 * c->k; a.dst_ct_rows = c->k;
-    a.fma_k = sk; a.fma_neg = 1;
+    NttArgs a = ntt_args(c, ct, ct, 2);
+    a.src_ct_rows = 2 * c->k; a.dst_ct_rows = c->k; a.fma_k = sk; a.fma_neg = 1;
     return ntt_launch(c, false, a, count * c->k, st);
 }
 
 // forward NTT of the c0 rows of size-2 ciphertexts src -> dense rows dst [count][k][n] (any ring: the two-pass form of the step above)
 int k_ntt_ct_poly0(crc_ctx *c, const u64 *src, u64 *dst, size_t count, hipStream_t st)
 {
-    NttArgs a{};
-    a.src = src; a.dst = dst; a.mod_base = 0; a.mod_count = c->k; a.rows_per_ct = c->k; a.add_group = 1; a.add_mode = 1;
+    NttArgs a = ntt_args(c, src, dst, 1);
     a.src_ct_rows = 2 * c->k; a.dst_ct_rows = c->k;
     return ntt_launch(c, false, a, count * c->k, st);
 }
@@ -827,18 +783,15 @@ int k_ntt_ct_poly0(crc_ctx *c, const u64 *src, u64 *dst, size_t count, hipStream
 // multiply_plain's three steps (evaluator.cpp:1193-1323) in one kernel.  CRC_ERR_UNSUPPORTED where the ring has no wave-local kernel
 int k_ntt_ct_fwd_mul(crc_ctx *c, u64 *ct, size_t count, const u64 *w, size_t group, hipStream_t st)
 {
-    NttArgs a{};
-    a.src = ct; a.dst = ct; a.mod_base = 0; a.mod_count = c->k; a.rows_per_ct = 2 * c->k; a.add_group = 1; a.add_mode = 1;
-    a.fma_k = w; a.fma_group = group ? group : 1;
+    NttArgs a = ntt_args(c, ct, ct, 2); a.fma_k = w; a.fma_group = group ? group : 1;
     return ntt_launch(c, false, a, count * 2 * c->k, st);
 }
 
 // inverse NTT of size-2 ciphertexts src -> dst, adding polys 0,1 of a size-`add_size` ciphertext array (relinearize tail)
 int k_ntt_ct_addct(crc_ctx *c, const u64 *src, u64 *dst, size_t count, const u64 *addct, int add_size, hipStream_t st)
 {
-    NttArgs a{};
-    a.src = src; a.dst = dst; a.mod_base = 0; a.mod_count = c->k;
-    a.addend = addct; a.add_sign = 1; a.rows_per_ct = 2 * c->k; a.add_group = 1; a.add_mode = 2; a.add_size = add_size;
+    NttArgs a = ntt_args(c, src, dst, 2);
+    a.addend = addct; a.add_sign = 1; a.add_mode = 2; a.add_size = add_size;
     return ntt_launch(c, true, a, count * 2 * c->k, st);
 }
 
@@ -846,64 +799,55 @@ int k_ntt_ct_addct(crc_ctx *c, const u64 *src, u64 *dst, size_t count, const u64
 // (relinearize tail when the result stays in NTT form: NTT(c0, c1) + key-switched c2)
 int k_ntt_ct_head_add(crc_ctx *c, const u64 *src, int src_size, u64 *dst, size_t count, const u64 *addrows, hipStream_t st)
 {
-    NttArgs a{};
-    a.src = src; a.dst = dst; a.mod_base = 0; a.mod_count = c->k;
+    NttArgs a = ntt_args(c, src, dst, 2);
     a.src_ct_rows = src_size * c->k; a.dst_ct_rows = 2 * c->k;
-    a.addend = addrows; a.add_sign = 1; a.rows_per_ct = 2 * c->k; a.add_group = 1;
+    a.addend = addrows; a.add_sign = 1;
     return ntt_launch(c, false, a, count * 2 * c->k, st);
 }
 
 // forward NTT of `items` polynomials under every q_j: src [items][n] -> dst [items][k][n]
 int k_spread_ntt(crc_ctx *c, const u64 *src, size_t items, u64 *dst, hipStream_t st)
 {
-    NttArgs a{};
-    a.src = src; a.dst = dst; a.mod_base = 0; a.mod_count = c->k; a.src_rows_per_item = 1; a.prologue = 0;
-    a.rows_per_ct = c->k; a.add_group = 1;
+    NttArgs a = ntt_args(c, src, dst, 1); a.src_rows_per_item = 1;
     return ntt_launch(c, false, a, items * c->k, st);
 }
 
 // relinearisation digits: forward NTT of digit g of c2 (premultiplied by (q/q_i)^-1, poly `src_poly` of the size-`src_size` ciphertexts `src`) under every q_j:
-// dst [count][D][k][n]; the digit is cut out of the source word while the row is loaded (NttArgs prologue 3)
+// dst [count][D][k][n]; the digit is cut out of the source word while the row is loaded (NTT_PRO_DIGIT)
 int k_digit_ntt(crc_ctx *c, const u64 *src, int src_size, int src_poly, size_t count, int D, const unsigned char *dig_i, const unsigned char *dig_shift,
-    int dbc,
-                u64 *dst, hipStream_t st, int pack_out)
+                int dbc, u64 *dst, hipStream_t st, int pack_out)
 {
     if (D > 48) return CRC_ERR_UNSUPPORTED;
-    NttArgs a{};
-    a.src = src; a.dst = dst; a.mod_base = 0; a.mod_count = c->k; a.prologue = 3; a.pack_out = pack_out;
+    NttArgs a = ntt_args(c, src, dst, 1);
+    a.prologue = NTT_PRO_DIGIT; a.pack_out = pack_out;
     a.D = D; a.src_size = src_size; a.src_poly = src_poly; a.dig_mask = (1ULL << dbc) - 1;
     for (int g = 0; g < D; g++) { a.dig_i[g] = dig_i[g]; a.dig_shift[g] = dig_shift[g]; }
-    a.rows_per_ct = c->k; a.add_group = 1;
     return ntt_launch(c, false, a, count * D * c->k, st);
 }
 
 // inverse NTT of the three dyadic products of size-2 NTT-form ciphertexts [count][2][K][n] -> dst [count][3][K][n] (coefficient form), K = k moduli of q or kb
-// moduli of Bsk; the products are formed while the row is loaded.  y null: the square (a^2, 2ab, b^2) of x = (a, b), which reads two rows (NttArgs prologue 4);
-// otherwise the tensor product (ac, ad + bc, bd) of x = (a, b) and y = (c, d) (prologue 6: prologue 4 with a second source, the pointer fma_k)
+// moduli of Bsk; the products are formed while the row is loaded.  y null: the square (a^2, 2ab, b^2) of x = (a, b), which reads two rows (NTT_PRO_SQUARE);
+// otherwise the tensor product (ac, ad + bc, bd) of x = (a, b) and y = (c, d) (NTT_PRO_PRODUCT: NTT_PRO_SQUARE with a second source, the pointer fma_k)
 // opt_mul (per modulus, may be null): constants the consumer of dst would multiply the rows by first thing; *applied says whether the transform took them into
 // its closing multiplication (the kernels that end in one: ntt_rows_wave_kernel's unscaled inverse) or left the rows as they are
 int k_product_intt(crc_ctx *c, const u64 *x, const u64 *y, u64 *dst, size_t count, bool bsk, hipStream_t st, const u64 *opt_mul, bool *applied)
 {
-    NttArgs a{};
-    a.src = x; a.fma_k = y; a.dst = dst; a.mod_base = bsk ? c->k : 0; a.mod_count = bsk ? c->kb : c->k; a.prologue = y ? 6 : 4;
-    a.rows_per_ct = 3 * a.mod_count; a.add_group = 1; a.pairs = count * a.mod_count;
+    NttArgs a = ntt_args(c, x, dst, 3, bsk);
+    a.fma_k = y; a.prologue = y ? NTT_PRO_PRODUCT : NTT_PRO_SQUARE; a.pairs = count * a.mod_count;
     if (opt_mul) { a.opt_mul = 1; for (int i = 0; i < a.mod_count; i++) a.post_mul[i] = opt_mul[i]; }
     const int rc = ntt_launch(c, true, a, count * 3 * a.mod_count, st);
     if (applied) *applied = a.opt_mul == 2;
     return rc;
 }
 
-// inverse NTT of size-`size` ciphertexts over q whose result leaves multiplied by mul[i] mod q_i (mul_s: Shoup companions) -- NttArgs prologue 5
+// inverse NTT of size-`size` ciphertexts over q whose result leaves multiplied by mul[i] mod q_i (mul_s: Shoup companions) -- NTT_PRO_SCALED
 int k_ntt_ct_inv_scaled(crc_ctx *c, const u64 *src, u64 *dst, size_t count, int size, const u64 *mul, const u64 *mul_s, hipStream_t st)
 {
-    NttArgs a{};
-    a.src = src; a.dst = dst; a.mod_base = 0; a.mod_count = c->k; a.prologue = 5;
-    a.rows_per_ct = size * c->k; a.add_group = 1;
+    NttArgs a = ntt_args(c, src, dst, size);
+    a.prologue = NTT_PRO_SCALED;
     for (int i = 0; i < c->k; i++) { a.post_mul[i] = mul[i]; a.post_mul_s[i] = mul_s[i]; }
     return ntt_launch(c, true, a, count * size * c->k, st);
 }
-
-int k_plain_ntt(crc_ctx *c, const u64 *d_plain, size_t count, int mode, bool do_ntt, u64 *d_out, hipStream_t st);
 
 // plaintext [count][n] -> [count][k][n]: lift (mode 1) or delta-scale (mode 2), then forward NTT (unless !do_ntt)
 __global__ void plain_prep_kernel(const u64 *plain, u64 *out, const ModParams *mods, int n, int k, int mode, PlainParams pp)
@@ -927,9 +871,8 @@ int k_plain_ntt(crc_ctx *c, const u64 *d_plain, size_t count, int mode, bool do_
 {
     if (count == 0) return CRC_OK;
     if (do_ntt) {
-        NttArgs a{};
-        a.src = d_plain; a.dst = d_out; a.mod_base = 0; a.mod_count = c->k; a.src_rows_per_item = 1; a.prologue = mode; a.pp = c->plain;
-        a.rows_per_ct = c->k; a.add_group = 1;
+        NttArgs a = ntt_args(c, d_plain, d_out, 1);
+        a.src_rows_per_item = 1; a.prologue = mode; a.pp = c->plain;            // (mode: NTT_PRO_LIFT or NTT_PRO_DELTA)
         return ntt_launch(c, false, a, count * c->k, st);
     }
     hipLaunchKernelGGL(plain_prep_kernel, dim3((unsigned)(count * c->k)), dim3(256), 0, st, d_plain, d_out, c->d_mods, c->n, c->k, mode, c->plain);

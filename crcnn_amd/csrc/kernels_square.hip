@@ -5,11 +5,11 @@
 // kernels (coalesced over s, tables in scalar registers); everything between them is the row NTT of kernels.hip.
 //   lift     : q -> Bsk U {m~} (fastbconv_mtilde) and small Montgomery reduction (mont_rq)        [sq_lift_kernel]
 //   NTT      : 2 polys in q and in Bsk                                                             [ntt_rows_kernel]
-//   products : c0^2, 2 c0 c1, c1^2 in both bases, formed while the inverse transform loads its row [ntt_rows_kernel, prologue 4]
+//   products : c0^2, 2 c0 c1, c1^2 in both bases, formed while the inverse transform loads its row [ntt_rows_kernel, NTT_PRO_SQUARE]
 //   INTT     : 3 polys in both bases
 //   floor    : x t, fast_floor (q U Bsk -> Bsk), fastbconv_sk (Bsk -> q); the third polynomial leaves
 //              premultiplied by (q/q_i)^-1 for the digit decomposition                             [sq_floor_kernel]
-//   relin    : digit g of c2 (q/q_i)^-1 cut out while the forward transform loads its row          [ntt_rows_kernel, prologue 3]
+//   relin    : digit g of c2 (q/q_i)^-1 cut out while the forward transform loads its row          [ntt_rows_kernel, NTT_PRO_DIGIT]
 //              lazy 28-bit-limb MAC against the (packed) keys, one folding reduction               [relin_mac28_kernel]
 //              INTT + (c0, c1), or NTT(c0, c1) + that for an NTT-resident result
 // Row transfers through HBM per ciphertext at (k, kb, D) = (3, 4, 12): 2k+2k | 2k+2kb | 2kb+2kb | 4k+3k, 4kb+3kb | 3k+3kb+3k | D+Dk | Dk+2k | 4k+2k = 198
@@ -216,7 +216,7 @@ size_t k_relin_keys_words(const crc_ctx *c, int dbc) { return k_relin64_keys_wor
 
 // The product of cnt ciphertexts on SEAL's 61-bit auxiliary base: the square of x (y null; Evaluator::square) or x . y of two arrays (Evaluator::multiply,
 // evaluator.cpp:356-700, for size-2 inputs).  One chain for both: every input is lifted and transformed, and the inverse transforms form (a^2, 2ab, b^2) from the
-// one input's two rows (NttArgs prologue 4) or the tensor product (ac, ad + bc, bd) from the two inputs' four (prologue 6) while they load their rows -- no
+// one input's two rows (NTT_PRO_SQUARE) or the tensor product (ac, ad + bc, bd) from the two inputs' four (NTT_PRO_PRODUCT) while they load their rows -- no
 // product tensors in memory
 static int product61(crc_ctx *c, const u64 *x, const u64 *y, size_t cnt, u64 *y3, u64 *work, hipStream_t st, bool in_ntt, bool premul_c2)
 {

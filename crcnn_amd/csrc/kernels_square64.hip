@@ -14,7 +14,7 @@
 //   sq64_fwd_kernel   : forward transform of every LB row in place
 //   sq64_liftfwd_kernel (round 4, NTT-resident callers): the two above in one -- the inverse transform that brings x to coefficient form leaves it multiplied
 //   by
-//                       m~ (q/q_i)^-1 (NttArgs prologue 5), and the forward transform under p_j lifts its row while it stages it: the kf workgroups of a
+//                       m~ (q/q_i)^-1 (NTT_PRO_SCALED), and the forward transform under p_j lifts its row while it stages it: the kf workgroups of a
 //                       polynomial
 //                       share their k source rows through one XCD's L2, LB is written once and never read back untransformed (-20 of 260 row transfers per
 //                       ciphertext at (8192, 3), one kernel less)

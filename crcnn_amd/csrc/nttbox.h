@@ -6,7 +6,7 @@
 // -- the box of limb_pack_rows1_kernel_px (kernels_mfma1.hip), taken in front of the transform instead of behind it (the transform is linear over Z_q).
 // One workgroup per output row = (image, pixel, poly, modulus).  Two maps from the block index to that row:
 //   order 0  the plain one, block = row;
-//   order 1  XCD-grouped (xcd_group / xcd_grid of ntt_device.h / kernels.h, the same arithmetic): a group is one (image, poly, modulus) PLANE, its xdo ydo members
+//   order 1  XCD-grouped (xcd_group / xcd_grid of ntt_device.h / xcd_grid.h, the same arithmetic): a group is one (image, poly, modulus) PLANE, its xdo ydo members
 //            are the plane's pixels in raster order, so one XCD walks a plane and the bxf byf users of an input row find it in that XCD's L2.  Blocks past
 //            the last plane return at once.
 #pragma once

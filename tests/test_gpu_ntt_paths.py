@@ -2,8 +2,9 @@
 and against the transform's definition in Python integers.  A class is the set [p, 0x3fffffff000001] (k = 2): the lazy butterflies run only when EVERY modulus of a
 launch has 45..57 bits, the inverse butterflies that do not halve only when every modulus is below 2^55, the lazily folded products only from 53 bits on.  Plain
 transforms on every ring from 64 to 16384, the fused forms (multiply_plain, both device encryptors, square / multiply with relinearisation, a convolution with bias)
-on 1024, 2048, 8192 and 16384.  Which kernel a case reaches is recorded in profiles/ntt_paths_kernels.md (the test cannot see it); the map from (ring, class,
-prologue) to kernel is in DESIGN.md.  Nothing is skipped: the engine admits every combination below.
+on 1024, 2048, 8192 and 16384.  Which kernel a case reaches is decided by ntt_select (crcnn_amd/csrc/ntt_select.h), whose map from (ring, class, request) to
+kernel tests/test_ntt_select_cpu.py checks row by row on the CPU; this test cannot see the choice, only its result -- profiles/ntt_paths_kernels.md records the
+instantiations it launched, DESIGN.md has the map as a table.  Nothing is skipped: the engine admits every combination below.
 
 Reference of the public-key device encryptor: crc_encrypt_dev_* has NO bit-exact host twin (include/crcnn_hip.h: "same laws as crc_encrypt, different bits"), so
 its NTT-form result (the fused product of the wave-local kernel, FMA 1) is pinned to the oracle's transform of its own coefficient-form result of the same (key,
