@@ -209,6 +209,15 @@ def load():
     L.crc_slots_refresh_sym_dev_work_bytes.restype = SZ; L.crc_slots_refresh_sym_dev_work_bytes.argtypes = [VP, SZ, CI]
     L.crc_slots_refresh_sym_dev.argtypes = [VP, VP, VP, SZ, CI, u64, u64, CI, VP, VP, VP]
     L.crc_slots_refresh_sym_dev_key.argtypes = [VP, VP, VP, SZ, CI, u64, PB, u64, CI, VP, VP, VP]
+    WIN = [CI] * 6                                             # xd, yd, xs, ys, xf, yf
+    L.crc_slots_act.argtypes = [VP, PU, SZ] + WIN + [u64, CI, u64, PU]
+    L.crc_slots_act_dev.argtypes = [VP, VP, SZ] + WIN + [u64, CI, u64, VP, VP]
+    L.crc_slots_refresh_act_dev_work_bytes.restype = SZ; L.crc_slots_refresh_act_dev_work_bytes.argtypes = [VP, SZ] + WIN + [CI]
+    L.crc_slots_refresh_act_dev.argtypes = [VP, VP, VP, VP, SZ] + WIN + [CI, u64, CI, u64, u64, CI, VP, VP, VP]
+    L.crc_slots_refresh_act_dev_key.argtypes = [VP, VP, VP, VP, SZ] + WIN + [CI, u64, CI, u64, PB, u64, CI, VP, VP, VP]
+    L.crc_slots_refresh_act_sym_dev_work_bytes.restype = SZ; L.crc_slots_refresh_act_sym_dev_work_bytes.argtypes = [VP, SZ] + WIN + [CI]
+    L.crc_slots_refresh_act_sym_dev.argtypes = [VP, VP, VP, SZ] + WIN + [CI, u64, CI, u64, u64, CI, VP, VP, VP]
+    L.crc_slots_refresh_act_sym_dev_key.argtypes = [VP, VP, VP, SZ] + WIN + [CI, u64, CI, u64, PB, u64, CI, VP, VP, VP]
     L.crc_encode_dev_f32.argtypes = [VP, VP, SZ, VP, VP]
     L.crc_encode_dev_f64.argtypes = [VP, VP, SZ, VP, VP]
     L.crc_refresh_dev_work_bytes.restype = SZ; L.crc_refresh_dev_work_bytes.argtypes = [VP, SZ, CI]
@@ -819,6 +828,48 @@ class Engine:
         else:
             _chk(self.L.crc_slots_refresh_sym_dev_key(self.c, self.p(d_sk), self.p(d_ct_in), count, in_form, int(divisor), self._key(key), stream_base, out_form,
                                                       self.p(d_ct_out), self.p(d_work), self.stream), "crc_slots_refresh_sym_dev_key")
+
+    # client-side activation: window = (xd, yd, xs, ys, xf, yf); outputs ((xd - xf) // xs + 1) x ((yd - yf) // ys + 1) rows per plane
+    def slots_act(self, plains, planes, window, divisor, relu=0, cap=0):
+        """host twin: plaintexts [planes][xd][yd][n] -> [planes][xo][yo][n]; per slot the window's maximum, floor(m / divisor + 1/2), ReLU, cap, recomposed"""
+        xd, yd, xs, ys, xf, yf = window
+        plains = np.ascontiguousarray(plains, dtype=np.uint64).reshape(planes * xd * yd, self.n)
+        xo, yo = ((xd - xf) // xs + 1, (yd - yf) // ys + 1) if xs > 0 and ys > 0 else (0, 0)
+        out = np.zeros((max(planes * xo * yo, 0), self.n), dtype=np.uint64)
+        _chk(self.L.crc_slots_act(self.c, _pu(plains), planes, xd, yd, xs, ys, xf, yf, int(divisor), int(relu), int(cap), _pu(out)), "crc_slots_act")
+        return out
+
+    def slots_act_dev(self, d_plain_in, planes, window, divisor, relu, cap, d_plain_out):
+        _chk(self.L.crc_slots_act_dev(self.c, self.p(d_plain_in), planes, *window, int(divisor), int(relu), int(cap), self.p(d_plain_out), self.stream),
+             "crc_slots_act_dev")
+
+    def slots_refresh_act_dev_work_bytes(self, planes, window, in_form=COEFF):
+        return self.L.crc_slots_refresh_act_dev_work_bytes(self.c, planes, *window, in_form)
+
+    def slots_refresh_act_dev(self, d_sk, d_pk, d_ct_in, planes, window, divisor, relu, cap, seed, d_ct_out, d_work, in_form=COEFF, out_form=COEFF, key=None,
+                              stream_base=0):
+        """decrypt planes * xd * yd ciphertexts -> slots_act_dev -> encrypt the planes * xo * yo outputs under the public key, as one call"""
+        if key is None:
+            _chk(self.L.crc_slots_refresh_act_dev(self.c, self.p(d_sk), self.p(d_pk), self.p(d_ct_in), planes, *window, in_form, int(divisor), int(relu), int(cap),
+                                                  seed, out_form, self.p(d_ct_out), self.p(d_work), self.stream), "crc_slots_refresh_act_dev")
+        else:
+            _chk(self.L.crc_slots_refresh_act_dev_key(self.c, self.p(d_sk), self.p(d_pk), self.p(d_ct_in), planes, *window, in_form, int(divisor), int(relu),
+                                                      int(cap), self._key(key), stream_base, out_form, self.p(d_ct_out), self.p(d_work), self.stream),
+                 "crc_slots_refresh_act_dev_key")
+
+    def slots_refresh_act_sym_dev_work_bytes(self, planes, window, in_form=COEFF):
+        return self.L.crc_slots_refresh_act_sym_dev_work_bytes(self.c, planes, *window, in_form)
+
+    def slots_refresh_act_sym_dev(self, d_sk, d_ct_in, planes, window, divisor, relu, cap, seed, d_ct_out, d_work, in_form=COEFF, out_form=COEFF, key=None,
+                                  stream_base=0):
+        """the same under the secret key"""
+        if key is None:
+            _chk(self.L.crc_slots_refresh_act_sym_dev(self.c, self.p(d_sk), self.p(d_ct_in), planes, *window, in_form, int(divisor), int(relu), int(cap), seed,
+                                                      out_form, self.p(d_ct_out), self.p(d_work), self.stream), "crc_slots_refresh_act_sym_dev")
+        else:
+            _chk(self.L.crc_slots_refresh_act_sym_dev_key(self.c, self.p(d_sk), self.p(d_ct_in), planes, *window, in_form, int(divisor), int(relu), int(cap),
+                                                          self._key(key), stream_base, out_form, self.p(d_ct_out), self.p(d_work), self.stream),
+                 "crc_slots_refresh_act_sym_dev_key")
 
     def keygen(self, seed):
         sk = np.zeros((self.k, self.n), dtype=np.uint64); pk = np.zeros((2, self.k, self.n), dtype=np.uint64)

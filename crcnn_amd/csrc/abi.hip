@@ -919,6 +919,111 @@ extern "C" int crc_slots_refresh_sym_dev_key(crc_ctx *c, const uint64_t *d_sk, c
     CHECK_CTX(c); if (!key) return crc_slots_supported(c) ? CRC_ERR_INVALID_ARGUMENT : CRC_ERR_PARAMETERS;
     return slots_refresh_impl(c, true, d_sk, nullptr, d_ct_in, count, in_form, divisor, chacha_load_key(key), stream_base, out_form, d_ct_out, d_work, S(stream));
 }
+// ---- client-side activation of a slot-batched tensor (kernels_slots.hip: k_slots_act) and the refresh that applies it between decrypt and encrypt ----
+// the checks of every act entry point, in the order of the rescale's: the context's slots, then the values; in / out are the two tensors
+static int slots_act_args_ok(const crc_ctx *c, const void *in, const void *out, size_t planes, const Window &w, uint64_t divisor, int relu, uint64_t cap)
+{
+    if (!crc_slots_supported(c)) return CRC_ERR_PARAMETERS;
+    if (!in || !out || divisor < 1 || divisor > ((uint64_t)1 << 62) || (relu != 0 && relu != 1) || cap > ((c->t - 1) >> 1) || !w.ok()) return CRC_ERR_INVALID_ARGUMENT;
+    if (((unsigned __int128)planes * (uint64_t)w.xd * (uint64_t)w.yd * (uint64_t)c->n) >> 60) return CRC_ERR_INVALID_ARGUMENT;
+    return CRC_OK;
+}
+static bool slots_act_in_place_ok(const Window &w) { return w.xf == 1 && w.yf == 1 && w.xs == 1 && w.ys == 1; }
+extern "C" int crc_slots_act(crc_ctx *c, const uint64_t *h_plain_in, size_t planes, int xd, int yd, int xs, int ys, int xf, int yf, uint64_t divisor, int relu,
+                             uint64_t cap, uint64_t *h_plain_out)
+{
+    if (!c) return CRC_ERR_INVALID_ARGUMENT;
+    const Window w{xd, yd, xs, ys, xf, yf};
+    RUN(slots_act_args_ok(c, h_plain_in, h_plain_out, planes, w, divisor, relu, cap));
+    return k_slots_act_host(c, h_plain_in, planes, w, divisor, relu, cap, h_plain_out);
+}
+extern "C" int crc_slots_act_dev(crc_ctx *c, const uint64_t *d_plain_in, size_t planes, int xd, int yd, int xs, int ys, int xf, int yf, uint64_t divisor, int relu,
+                                 uint64_t cap, uint64_t *d_plain_out, void *stream)
+{
+    CHECK_CTX(c);
+    const Window w{xd, yd, xs, ys, xf, yf};
+    RUN(slots_act_args_ok(c, d_plain_in, d_plain_out, planes, w, divisor, relu, cap));
+    if (((uintptr_t)d_plain_in & 15) || ((uintptr_t)d_plain_out & 15)) return CRC_ERR_INVALID_ARGUMENT;
+    // a workgroup reads window rows that other workgroups write as outputs unless every output row is its own only input row
+    const uintptr_t ib = (uintptr_t)d_plain_in, ie = ib + planes * (size_t)xd * yd * c->n * 8, ob = (uintptr_t)d_plain_out, oe = ob + planes * (size_t)w.P64() * c->n * 8;
+    if (ib < oe && ob < ie && !(ib == ob && slots_act_in_place_ok(w))) return CRC_ERR_INVALID_ARGUMENT;
+    return k_slots_act(c, d_plain_in, planes, w, divisor, relu, cap, d_plain_out, S(stream));
+}
+// Work: [decrypted plaintexts [planes xd yd][n]][activated plaintexts [planes xo yo][n]: none for a 1 x 1 window of stride 1, which works in place][the
+// decryptor's rows for the inputs, then the encryptor's (sym: the secret-key encryptor's) samples for the outputs]
+struct SlotsRefreshActWork { u64 *plain, *act, *w; };
+static SlotsRefreshActWork slots_refresh_act_layout(const crc_ctx *c, size_t planes, const Window &w, int in_form, bool sym, WorkArena &a)
+{
+    const size_t in_cts = planes * (size_t)w.xd * w.yd, out_cts = planes * (size_t)w.P64();
+    const size_t dec = k_decrypt_work_words(c, in_cts, 2, in_form == CRC_NTT), enc = sym ? k_encrypt_sym_work_words(c, out_cts) : k_encrypt_work_words(c, out_cts);
+    SlotsRefreshActWork L{};
+    L.plain = a.take<u64>(in_cts * (size_t)c->n);
+    L.act = slots_act_in_place_ok(w) ? L.plain : a.take<u64>(out_cts * (size_t)c->n);
+    L.w = a.take<u64>(dec > enc ? dec : enc);
+    return L;
+}
+static size_t slots_refresh_act_bytes(const crc_ctx *c, size_t planes, const Window &w, int in_form, bool sym)
+{
+    if (!c || !ct_form_ok(in_form) || !w.ok() || (((unsigned __int128)planes * (uint64_t)w.xd * (uint64_t)w.yd * (uint64_t)c->n) >> 60)) return 0;
+    WorkArena a;
+    slots_refresh_act_layout(c, planes, w, in_form, sym, a);
+    return a.bytes();
+}
+struct SlotsActParams { size_t planes; Window w; u64 divisor; int relu; u64 cap; };
+static int slots_refresh_act_impl(crc_ctx *c, bool sym, const u64 *d_sk, const u64 *d_pk, const u64 *d_in, const SlotsActParams &p, int in_form, const ChaChaKey &key,
+                                  u64 stream_base, int out_form, u64 *d_out, void *d_work, hipStream_t st)
+{
+    RUN(slots_act_args_ok(c, d_in, d_out, p.planes, p.w, p.divisor, p.relu, p.cap));
+    if (!d_sk || (!sym && !d_pk) || !d_work || !ct_form_ok(in_form) || !ct_form_ok(out_form)) return CRC_ERR_INVALID_ARGUMENT;
+    if (!p.planes) return CRC_OK;
+    WorkArena a(d_work);
+    const SlotsRefreshActWork L = slots_refresh_act_layout(c, p.planes, p.w, in_form, sym, a);
+    const size_t in_cts = p.planes * (size_t)p.w.xd * p.w.yd, out_cts = p.planes * (size_t)p.w.P64();
+    RUN(k_decrypt(c, d_sk, d_in, in_cts, 2, in_form == CRC_NTT, L.plain, L.w, st));
+    RUN(k_slots_act(c, L.plain, p.planes, p.w, p.divisor, p.relu, p.cap, L.act, st));
+    if (sym) return k_encrypt_sym(c, d_sk, L.act, out_cts, key, stream_base, d_out, L.w, st, out_form == CRC_NTT, false);
+    return k_encrypt(c, d_pk, L.act, out_cts, key, stream_base, d_out, L.w, st, out_form == CRC_NTT);
+}
+extern "C" size_t crc_slots_refresh_act_dev_work_bytes(const crc_ctx *c, size_t planes, int xd, int yd, int xs, int ys, int xf, int yf, int in_form)
+{
+    return slots_refresh_act_bytes(c, planes, Window{xd, yd, xs, ys, xf, yf}, in_form, false);
+}
+extern "C" size_t crc_slots_refresh_act_sym_dev_work_bytes(const crc_ctx *c, size_t planes, int xd, int yd, int xs, int ys, int xf, int yf, int in_form)
+{
+    return slots_refresh_act_bytes(c, planes, Window{xd, yd, xs, ys, xf, yf}, in_form, true);
+}
+extern "C" int crc_slots_refresh_act_dev(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_pk, const uint64_t *d_ct_in, size_t planes, int xd, int yd, int xs, int ys,
+                                         int xf, int yf, int in_form, uint64_t divisor, int relu, uint64_t cap, uint64_t seed, int out_form, uint64_t *d_ct_out,
+                                         void *d_work, void *stream)
+{
+    CHECK_CTX(c);
+    return slots_refresh_act_impl(c, false, d_sk, d_pk, d_ct_in, {planes, {xd, yd, xs, ys, xf, yf}, divisor, relu, cap}, in_form, chacha_seed_key(seed), 0, out_form,
+                                  d_ct_out, d_work, S(stream));
+}
+extern "C" int crc_slots_refresh_act_dev_key(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_pk, const uint64_t *d_ct_in, size_t planes, int xd, int yd, int xs,
+                                             int ys, int xf, int yf, int in_form, uint64_t divisor, int relu, uint64_t cap, const uint8_t *key, uint64_t stream_base,
+                                             int out_form, uint64_t *d_ct_out, void *d_work, void *stream)
+{
+    CHECK_CTX(c); if (!key) return crc_slots_supported(c) ? CRC_ERR_INVALID_ARGUMENT : CRC_ERR_PARAMETERS;
+    return slots_refresh_act_impl(c, false, d_sk, d_pk, d_ct_in, {planes, {xd, yd, xs, ys, xf, yf}, divisor, relu, cap}, in_form, chacha_load_key(key), stream_base,
+                                  out_form, d_ct_out, d_work, S(stream));
+}
+extern "C" int crc_slots_refresh_act_sym_dev(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_ct_in, size_t planes, int xd, int yd, int xs, int ys, int xf, int yf,
+                                             int in_form, uint64_t divisor, int relu, uint64_t cap, uint64_t seed, int out_form, uint64_t *d_ct_out, void *d_work,
+                                             void *stream)
+{
+    CHECK_CTX(c);
+    return slots_refresh_act_impl(c, true, d_sk, nullptr, d_ct_in, {planes, {xd, yd, xs, ys, xf, yf}, divisor, relu, cap}, in_form, chacha_seed_key(seed), 0, out_form,
+                                  d_ct_out, d_work, S(stream));
+}
+extern "C" int crc_slots_refresh_act_sym_dev_key(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_ct_in, size_t planes, int xd, int yd, int xs, int ys, int xf,
+                                                 int yf, int in_form, uint64_t divisor, int relu, uint64_t cap, const uint8_t *key, uint64_t stream_base, int out_form,
+                                                 uint64_t *d_ct_out, void *d_work, void *stream)
+{
+    CHECK_CTX(c); if (!key) return crc_slots_supported(c) ? CRC_ERR_INVALID_ARGUMENT : CRC_ERR_PARAMETERS;
+    return slots_refresh_act_impl(c, true, d_sk, nullptr, d_ct_in, {planes, {xd, yd, xs, ys, xf, yf}, divisor, relu, cap}, in_form, chacha_load_key(key), stream_base,
+                                  out_form, d_ct_out, d_work, S(stream));
+}
 // ---- seeded secret-key ciphertexts: the packed c0 rows and a public seed -> ordinary ciphertexts (kernels_client.hip: k_seeded_expand) ----
 extern "C" int crc_seeded_expand_dev(crc_ctx *c, const uint64_t *d_c0, size_t count, const uint8_t *seed, uint64_t stream_base, int out_form, uint64_t *d_ct,
                                      void *stream)

@@ -151,6 +151,9 @@ int k_slots_decompose_host(crc_ctx *c, const u64 *plain, size_t count, int slots
 // every slot of a plaintext -> floor(slot / divisor + 1/2), 1 <= divisor <= 2^62 (the caller checks); in == out allowed
 int k_slots_rescale(crc_ctx *c, const u64 *d_in, size_t count, u64 divisor, u64 *d_out, hipStream_t st);
 int k_slots_rescale_host(crc_ctx *c, const u64 *plain_in, size_t count, u64 divisor, u64 *plain_out);
+// client-side activation of plaintext rows [planes][w.xd][w.yd][n] -> [planes][w.xo()][w.yo()][n]: window maximum, division, ReLU, cap, slot by slot
+int k_slots_act(crc_ctx *c, const u64 *d_in, size_t planes, const Window &w, u64 divisor, int relu, u64 cap, u64 *d_out, hipStream_t st);
+int k_slots_act_host(crc_ctx *c, const u64 *plain_in, size_t planes, const Window &w, u64 divisor, int relu, u64 cap, u64 *plain_out);
 
 // kernels_seeded_keys.hip: seeded key-switching keys (chacha.h CHACHA_DOM_KSK_*; ids is a HOST array of key ids: 0 = evaluation key, else a Galois element).
 // first / rows [n_ids][P][k][n] NTT form, formed in place without work space; out [n_ids][crc_evk_words]; the host twins are crc_gen_keys_seeded_key and

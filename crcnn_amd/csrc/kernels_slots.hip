@@ -29,8 +29,14 @@ __global__ void __launch_bounds__(1024) slots_rescale_kernel(SlotRescaleArgs a)
     extern __shared__ u64 sm[];
     slots_rescale_body<LAZY>(a, sm);
 }
+template <bool LAZY, int PAIRS>                             // PAIRS = 4: a lane's share up to n = 8192; 8: of n = 16384 at 1024 threads; 0: the window is one row
+__global__ void __launch_bounds__(1024) slots_act_kernel(SlotActArgs a)
+{
+    extern __shared__ u64 sm[];
+    slots_act_body<LAZY, PAIRS>(a, sm);
+}
 
-// The launch rules of the three slot kernels in one place: t's tables, one workgroup of max(64, n / 8) threads per row with the row as its LDS image, the rows in
+// The launch rules of the slot kernels in one place: t's tables, one workgroup of max(64, n / 8) threads per row with the row as its LDS image, the rows in
 // XCD groups.  `tables` puts the table pointers the kernel reads into the argument block; the ring's fields and the kernel's variant are chosen here.
 template <class Args, class Tables>
 static int slots_launch(crc_ctx *c, void (*lazy)(Args), void (*strict)(Args), Args &a, Tables tables, hipStream_t st)
@@ -73,6 +79,23 @@ int k_slots_rescale(crc_ctx *c, const u64 *d_in, size_t count, u64 divisor, u64 
     a.D = divisor; a.recip = divisor == 1 ? ~(u64)0 : (u64)(((unsigned __int128)1 << 64) / divisor);
     a.hpos = divisor >> 1; a.hneg = (divisor - 1) >> 1;
     return slots_launch(c, slots_rescale_kernel<true>, slots_rescale_kernel<false>, a, [](SlotRescaleArgs &a, const SlotTables &T) { a.Wf = T.d_fwd; a.Wi = T.d_inv; }, st);
+}
+
+// the maximum over a window of plaintext rows, slot by slot, divided, ReLU, cap (slots_device.h): one workgroup per OUTPUT row, no work buffer.  The caller has
+// checked the window (Window::ok) and that the two tensors do not overlap, or coincide for a 1 x 1 window of stride 1
+int k_slots_act(crc_ctx *c, const u64 *d_in, size_t planes, const Window &w, u64 divisor, int relu, u64 cap, u64 *d_out, hipStream_t st)
+{
+    SlotActArgs a{};
+    a.plain_in = d_in; a.plain_out = d_out; a.count = planes * (size_t)w.P64();
+    a.D = divisor; a.recip = divisor == 1 ? ~(u64)0 : (u64)(((unsigned __int128)1 << 64) / divisor);
+    a.xd = w.xd; a.yd = w.yd; a.xs = w.xs; a.ys = w.ys; a.xf = w.xf; a.yf = w.yf; a.xo = w.xo(); a.yo = w.yo();
+    a.relu = relu; a.cap = cap;
+    auto tables = [](SlotActArgs &a, const SlotTables &T) { a.Wf = T.d_fwd; a.Wi = T.d_inv; };
+    // a window of one row at stride 1 (outputs and inputs have the same row index) needs no running maximum
+    if (w.xf == 1 && w.yf == 1 && w.xs == 1 && w.ys == 1) return slots_launch(c, slots_act_kernel<true, 0>, slots_act_kernel<false, 0>, a, tables, st);
+    // pairs a lane owns: n / (2 max(64, n / 8)), i.e. at most 4 up to n = 8192; 8 at n = 16384, where the workgroup stops at 1024 threads
+    if (c->n <= 8192) return slots_launch(c, slots_act_kernel<true, 4>, slots_act_kernel<false, 4>, a, tables, st);
+    return slots_launch(c, slots_act_kernel<true, 8>, slots_act_kernel<false, 8>, a, tables, st);
 }
 
 // ---- host twins (any context, device = -1 included): the reference transforms of ctx.cpp on the same tables ----------------------------------------------
@@ -124,6 +147,40 @@ int k_slots_rescale_host(crc_ctx *c, const u64 *plain_in, size_t count, u64 divi
             }
             h_ntt_inv(T->T, row.data(), n);
             for (int i = 0; i < n; i++) plain_out[m * (size_t)n + i] = row[i];
+        }
+    });
+    return CRC_OK;
+}
+int k_slots_act_host(crc_ctx *c, const u64 *plain_in, size_t planes, const Window &w, u64 divisor, int relu, u64 cap, u64 *plain_out)
+{
+    const SlotTables *T;
+    { const int rc = crc_slots_tables(c, &T); if (rc) return rc; }
+    const int n = c->n, xo = w.xo(), yo = w.yo(); const u64 t = c->t, half = (t - 1) >> 1;
+    const __int128 D = (__int128)divisor, h = (__int128)(divisor >> 1);
+    crc_host::parallel_for(planes * (size_t)w.P64(), 4, [&](size_t b, size_t e) {
+        std::vector<u64> row((size_t)n);
+        std::vector<long long> mx((size_t)n);
+        for (size_t m = b; m < e; m++) {
+            const size_t pl = m / ((size_t)xo * yo), ij = m % ((size_t)xo * yo);
+            const int i = (int)(ij / yo), j = (int)(ij % yo);
+            for (int wa = 0; wa < w.xf; wa++) for (int wb = 0; wb < w.yf; wb++) {
+                const u64 *src = plain_in + ((pl * w.xd + (size_t)(i * w.xs + wa)) * w.yd + (size_t)(j * w.ys + wb)) * (size_t)n;
+                for (int k = 0; k < n; k++) row[k] = src[k] % t;
+                h_ntt_fwd(T->T, row.data(), n);
+                for (int k = 0; k < n; k++) {
+                    const long long v = row[k] > half ? (long long)row[k] - (long long)t : (long long)row[k];
+                    if ((wa == 0 && wb == 0) || v > mx[k]) mx[k] = v;
+                }
+            }
+            for (int k = 0; k < n; k++) {
+                const __int128 num = (__int128)mx[k] + h;
+                __int128 q = num / D; if (num % D < 0) q--;                    // floor division
+                if (relu && q < 0) q = 0;
+                if (cap && q > (__int128)cap) q = (__int128)cap;
+                row[k] = (u64)(q < 0 ? q + (__int128)t : q);                   // |q| <= (t - 1) / 2
+            }
+            h_ntt_inv(T->T, row.data(), n);
+            for (int k = 0; k < n; k++) plain_out[m * (size_t)n + k] = row[k];
         }
     });
     return CRC_OK;

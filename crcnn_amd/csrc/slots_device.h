@@ -1,6 +1,6 @@
 // slots_device.h -- device side of slot batching (kernels_slots.hip): argument block, block -> item order, the bodies of slots_compose_kernel and
-// slots_decompose_kernel, and of slots_rescale_kernel.  A header so that tests/cpp/slots_kernel_check.cpp and slots_rescale_kernel_check.cpp can run the same
-// text on the CPU, one thread per workgroup, under sanitizers.
+// slots_decompose_kernel, of slots_rescale_kernel and of slots_act_kernel.  A header so that tests/cpp/slots_kernel_check.cpp, slots_rescale_kernel_check.cpp and
+// slots_act_kernel_check.cpp can run the same text on the CPU, one thread per workgroup, under sanitizers.
 #pragma once
 #include "ntt_device.h"
 
@@ -128,6 +128,123 @@ __device__ __forceinline__ void slots_rescale_body(const SlotRescaleArgs &a, u64
         v.y = slot_rescale_value(mulmod_shoup(v.y, 1, one_s, t), a, half);
         if (fuse1) inv_pair_stage<LAZY>(v, I1[s >> 1], t, t2);
         sm_store_pair64(sm, s, v.x, v.y);
+    }
+    __syncthreads();
+    ntt_row_passes<true, LAZY, 3, true>(sm, a.Wi, n, a.logn, t, t2);
+    u64 *dst = a.plain_out + item * (size_t)n;
+    for (int s = 2 * tid; s < n; s += 2 * nt) {
+        const ulonglong2 r = sm_load_pair64(sm, s);                    // below 16 t (lazy) / 2 t (strict)
+        st2(dst + s, mulmod_shoup(r.x, 1, one_s, t), mulmod_shoup(r.y, 1, one_s, t));
+    }
+}
+
+// ---- client-side activation: the maximum over a window of plaintext ROWS, slot by slot, then the rescale's division, ReLU and a cap ---------------------------
+// out[pl][i][j] = compose(act(max over a < xf, b < yf of the centred slots of in[pl][i xs + a][j ys + b])), act(m) = min(max(floor(m / D + 1/2), 0 if relu), cap if
+// cap).  Slot-wise and the same in every slot, so the slot -> position map cancels as it does for the rescale: everything happens in position order.  Rounding is
+// non-decreasing, hence one division per output, behind the maximum.
+struct SlotActArgs {
+    const u64 *plain_in; u64 *plain_out;                    // [planes][xd][yd][n] -> [planes][xo][yo][n]; the same pointer only for a 1 x 1 window of stride 1
+    const ulonglong2 *Wf, *Wi;
+    size_t count;                                           // output rows: planes * xo * yo
+    int n, logn;
+    u64 t, one_s;
+    u64 D, recip;                                           // as SlotRescaleArgs (what rounding adds, D >> 1 and (D - 1) >> 1, is formed where it is used)
+    int xd, yd, xs, ys, xf, yf, xo, yo;
+    int relu; u64 cap;                                      // cap = 0: none; otherwise 1 <= cap <= (t - 1) / 2
+};
+
+// centred maximum m -> the residue of act(m).  |m| <= (t - 1) / 2 and D <= 2^62: the sums stay below 2^63 as in slot_rescale_value.  A negative quotient is
+// below every cap (cap >= 1), and a ReLU leaves 0 of it
+__device__ __forceinline__ u64 slot_act_value(long long m, const SlotActArgs &a)
+{
+    const bool neg = m < 0;
+    const u64 mag = neg ? 0 - (u64)m : (u64)m;
+    u64 qv = slot_quotient(mag + ((a.D - (neg ? 1 : 0)) >> 1), a.D, a.recip);
+    if (neg) return a.relu || !qv ? 0 : a.t - qv;
+    if (a.cap && qv > a.cap) qv = a.cap;
+    return qv;
+}
+
+// PAIRS: the 16-byte slots of the image one lane owns at most (on the device 4 up to n = 8192 and 8 at n = 16384, where the workgroup stops at 1024 threads; the
+// CPU check, one thread per workgroup, passes n / 2).
+// PAIRS = 0 is the kernel of a window of ONE row (client_relu): no running maximum to keep, the activation sits between the two gap-1 stages in one pointwise
+// loop exactly as the rescale's division does, at that kernel's register count.
+// Barriers.  The fill and the two pointwise loops give a lane the same slots s = 2 tid + 2 k nt of the image, and ntt_row_passes returns synchronised.  So a
+// window row needs ONE barrier of its own, between its fill and its passes: the fold behind the passes reads only the lane's own slots, and the next row's fill
+// overwrites exactly those -- what other lanes read of them they read inside the passes, in front of the barrier that ends them.  For the same reason the last
+// fold, the activation and the store of the inverse transform's input run without one; the kernel's last barrier of its own stands in front of the inverse passes.
+template <bool LAZY, int PAIRS>
+__device__ __forceinline__ void slots_act_body(const SlotActArgs &a, u64 *sm)
+{
+    size_t item;
+    if (!slot_item(a.count, item)) return;
+    const int n = a.n, tid = threadIdx.x, nt = blockDim.x;
+    const u64 t = a.t, t2 = t + t, one_s = a.one_s, half = (t - 1) >> 1;
+    const bool fuse1 = ntt_fused_stage(a.logn);
+    const ulonglong2 *F1 = a.Wf + (n >> 1), *I1 = a.Wi + (n >> 1);
+    if (PAIRS == 0) {                                       // one input row per output row, the same row index: the rescale's structure
+        const u64 *src = a.plain_in + item * (size_t)n;
+        for (int s = 2 * tid; s < n; s += 2 * nt) {
+            const ulonglong2 p = ld2(src + s);
+            sm_store_pair64(sm, s, mulmod_shoup(p.x, 1, one_s, t), mulmod_shoup(p.y, 1, one_s, t));
+        }
+        __syncthreads();
+        ntt_row_passes<false, LAZY, 3, true>(sm, a.Wf, n, a.logn, t, t2);
+        for (int s = 2 * tid; s < n; s += 2 * nt) {          // a lane owns its 16-byte slot of the image: no barrier inside this loop
+            ulonglong2 v = sm_load_pair64(sm, s);
+            if (fuse1) fwd_pair_stage<LAZY>(v, F1[s >> 1], t, t2);
+            const u64 x = mulmod_shoup(v.x, 1, one_s, t), y = mulmod_shoup(v.y, 1, one_s, t);
+            v.x = slot_act_value(x > half ? (long long)x - (long long)t : (long long)x, a);
+            v.y = slot_act_value(y > half ? (long long)y - (long long)t : (long long)y, a);
+            if (fuse1) inv_pair_stage<LAZY>(v, I1[s >> 1], t, t2);
+            sm_store_pair64(sm, s, v.x, v.y);
+        }
+        __syncthreads();
+        ntt_row_passes<true, LAZY, 3, true>(sm, a.Wi, n, a.logn, t, t2);
+        u64 *dst = a.plain_out + item * (size_t)n;
+        for (int s = 2 * tid; s < n; s += 2 * nt) {
+            const ulonglong2 r = sm_load_pair64(sm, s);
+            st2(dst + s, mulmod_shoup(r.x, 1, one_s, t), mulmod_shoup(r.y, 1, one_s, t));
+        }
+        return;
+    }
+    const size_t per = (size_t)a.xo * a.yo, pl = item / per, ij = item - pl * per;
+    const int i = (int)(ij / a.yo), j = (int)(ij - (size_t)i * a.yo);
+    long long mx[2 * PAIRS + 1];                            // the running maxima of the lane's slots, centred
+#pragma unroll
+    for (int k = 0; k < 2 * PAIRS; k++) mx[k] = -0x7fffffffffffffffLL - 1;
+    // the window's rows: yf consecutive rows of the tensor, xf times at a distance of yd rows
+    const u64 *win = a.plain_in + ((pl * a.xd + (size_t)(i * a.xs)) * a.yd + (size_t)(j * a.ys)) * (size_t)n;
+    for (int wa = 0; wa < a.xf; wa++, win += (size_t)a.yd * n) for (int wb = 0; wb < a.yf; wb++) {
+        const u64 *src = win + (size_t)wb * n;
+        for (int s = 2 * tid; s < n; s += 2 * nt) {
+            const ulonglong2 p = ld2(src + s);
+            sm_store_pair64(sm, s, mulmod_shoup(p.x, 1, one_s, t), mulmod_shoup(p.y, 1, one_s, t));
+        }
+        __syncthreads();
+        ntt_row_passes<false, LAZY, 3, true>(sm, a.Wf, n, a.logn, t, t2);
+#pragma unroll
+        for (int k = 0; k < PAIRS; k++) {
+            const int s = 2 * tid + 2 * k * nt;
+            if (s < n) {                                     // (no break: eight independent conditions, not eight nested ones)
+                ulonglong2 v = sm_load_pair64(sm, s);
+                if (fuse1) fwd_pair_stage<LAZY>(v, F1[s >> 1], t, t2);
+                const u64 x = mulmod_shoup(v.x, 1, one_s, t), y = mulmod_shoup(v.y, 1, one_s, t);   // below (1 + 4 log2 n) t (lazy) / 4 t (strict) -> canonical
+                const long long cx = x > half ? (long long)x - (long long)t : (long long)x, cy = y > half ? (long long)y - (long long)t : (long long)y;
+                mx[2 * k] = cx > mx[2 * k] ? cx : mx[2 * k];
+                mx[2 * k + 1] = cy > mx[2 * k + 1] ? cy : mx[2 * k + 1];
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < PAIRS; k++) {
+        const int s = 2 * tid + 2 * k * nt;
+        if (s < n) {
+            ulonglong2 v;
+            v.x = slot_act_value(mx[2 * k], a); v.y = slot_act_value(mx[2 * k + 1], a);
+            if (fuse1) inv_pair_stage<LAZY>(v, I1[s >> 1], t, t2);
+            sm_store_pair64(sm, s, v.x, v.y);
+        }
     }
     __syncthreads();
     ntt_row_passes<true, LAZY, 3, true>(sm, a.Wi, n, a.logn, t, t2);

@@ -66,6 +66,7 @@ static size_t ctBytes() { return crc_ct_words(ctx(), 2) * 8; }
 // tensor -- but a hipMalloc / hipFree pair per layer and chunk (the free synchronises the device) would cost more than some of the layers.  Freed buffers wait
 // in a pool (bounded: beyond the cap they go back to the driver; an allocation that fails empties the pool and tries again); delParameters() empties it.
 namespace {
+bool windowOk(int xd, int yd, int xs, int ys, int xf, int yf);          // (with the description parser, below)
 struct BufferPool {
     std::mutex mu;
     std::list<std::pair<size_t, void *>> lru;               // oldest first
@@ -1243,6 +1244,66 @@ ciphertext3D SlotRescaleLayer::forward(ciphertext3D input)
     return rescaleSlots(input, divisor, out_form, symmetric);
 }
 void SlotRescaleLayer::printLayerStructure() { cerr << "SlotRescaleLayer " << name << " :bits " << bits << " divisor " << divisor << endl; }
+
+// rescaleSlots with the client-side activation between decrypt and encrypt (crc_slots_refresh_act_dev); a pass is a run of whole [xd][yd] planes
+ciphertext3D actSlots(const ciphertext3D &t, int xs, int ys, int xf, int yf, uint64_t divisor, int relu, uint64_t cap, int out_form, bool symmetric)
+{
+    if (!t.buf) throw invalid_argument("actSlots: empty tensor");
+    if ((t.form != CRC_COEFF && t.form != CRC_NTT) || (out_form != CRC_COEFF && out_form != CRC_NTT))
+        throw invalid_argument("actSlots: ciphertext forms only (CRC_COEFF / CRC_NTT)");
+    if (divisor < 1 || divisor > ((uint64_t)1 << 62)) throw invalid_argument("actSlots: the divisor must be in 1..2^62");
+    if (!crc_slots_supported(ctx())) throw invalid_argument("actSlots: the plain modulus must be a prime that is 1 mod 2n and none of the engine's moduli");
+    if (!windowOk(t.xd, t.yd, xs, ys, xf, yf)) throw invalid_argument("actSlots: the window does not fit the tensor");
+    if (relu != 0 && relu != 1) throw invalid_argument("actSlots: relu must be 0 or 1");
+    if (cap > (g_plain_modulus - 1) / 2) throw invalid_argument("actSlots: the cap must be at most (t - 1) / 2");
+    const uint64_t *d_sk = deviceKey(g_d_sk, g_d_sk_fp, secret_key, "secret key");
+    const uint64_t *d_pk = symmetric ? nullptr : deviceKey(g_d_pk, g_d_pk_fp, public_key, "public key");
+    const int xd = t.xd, yd = t.yd, xo = (xd - xf) / xs + 1, yo = (yd - yf) / ys + 1;
+    auto work_bytes = [&](size_t p) { return symmetric ? crc_slots_refresh_act_sym_dev_work_bytes(ctx(), p, xd, yd, xs, ys, xf, yf, t.form)
+                                                      : crc_slots_refresh_act_dev_work_bytes(ctx(), p, xd, yd, xs, ys, xf, yf, t.form); };
+    ciphertext3D out(t.B, t.zd, xo, yo, out_form);
+    const size_t planes = (size_t)t.B * t.zd, in_cts = (size_t)xd * yd, out_cts = (size_t)xo * yo, one = work_bytes(1);
+    size_t pass = ((size_t)4 << 30) / (one ? one : 1);
+    if (pass * in_cts < 1024) pass = (1024 + in_cts - 1) / in_cts;
+    if (pass > planes) pass = planes;
+    ensure(g_scratch, work_bytes(pass));
+    for (size_t o = 0; o < planes; o += pass) {
+        const size_t p = min(pass, planes - o);
+        const uint64_t *in = (const uint64_t *)((const char *)t.data() + o * in_cts * ctBytes());
+        uint64_t *dst = (uint64_t *)((char *)out.data() + o * out_cts * ctBytes());
+        const uint64_t seed = g_det_seed + 1000003 * (g_enc_counter + 1);
+        if (symmetric && g_det)
+            chk(crc_slots_refresh_act_sym_dev(ctx(), d_sk, in, p, xd, yd, xs, ys, xf, yf, t.form, divisor, relu, cap, seed, out_form, dst, g_scratch->ptr, stream()),
+                "crc_slots_refresh_act_sym_dev");
+        else if (symmetric)
+            chk(crc_slots_refresh_act_sym_dev_key(ctx(), d_sk, in, p, xd, yd, xs, ys, xf, yf, t.form, divisor, relu, cap, g_master_key, g_enc_counter, out_form, dst,
+                                                  g_scratch->ptr, stream()), "crc_slots_refresh_act_sym_dev_key");
+        else if (g_det)
+            chk(crc_slots_refresh_act_dev(ctx(), d_sk, d_pk, in, p, xd, yd, xs, ys, xf, yf, t.form, divisor, relu, cap, seed, out_form, dst, g_scratch->ptr, stream()),
+                "crc_slots_refresh_act_dev");
+        else
+            chk(crc_slots_refresh_act_dev_key(ctx(), d_sk, d_pk, in, p, xd, yd, xs, ys, xf, yf, t.form, divisor, relu, cap, g_master_key, g_enc_counter, out_form, dst,
+                                              g_scratch->ptr, stream()), "crc_slots_refresh_act_dev_key");
+        g_enc_counter += p * out_cts;
+    }
+    return out;
+}
+ciphertext3D SlotReluLayer::forward(ciphertext3D input)
+{
+    if (out_form != CRC_COEFF && out_form != CRC_NTT) throw invalid_argument("SlotReluLayer: ciphertext forms only (CRC_COEFF / CRC_NTT)");
+    return actSlots(input, 1, 1, 1, 1, divisor, 1, cap, out_form, symmetric);
+}
+void SlotReluLayer::printLayerStructure() { cerr << "SlotReluLayer " << name << " :bits " << bits << " divisor " << divisor << " cap " << cap << endl; }
+ciphertext3D SlotMaxPoolLayer::forward(ciphertext3D input)
+{
+    if (out_form != CRC_COEFF && out_form != CRC_NTT) throw invalid_argument("SlotMaxPoolLayer: ciphertext forms only (CRC_COEFF / CRC_NTT)");
+    return actSlots(input, xs, ys, xf, yf, divisor, relu ? 1 : 0, cap, out_form, symmetric);
+}
+void SlotMaxPoolLayer::printLayerStructure()
+{
+    cerr << "SlotMaxPoolLayer " << name << " :stride " << xs << " " << ys << " window " << xf << " " << yf << " bits " << bits << " divisor " << divisor << " relu "
+         << relu << " cap " << cap << endl;
+}
 
 // Decryptor::invariant_noise_budget of a whole tensor on the launch stream (crc_noise_budget_dev), in passes of bounded work that share the layers' scratch
 // area.  The result buffer: one {min, first index} pair per pass, then the budgets -- so the pairs and the first ciphertext's budget are one small copy
@@ -2613,8 +2674,9 @@ NetworkDescription NetworkDescription::parse(const string &text, const string &h
             pending_refresh = refresh_line = ln;
             continue;
         }
-        const bool windowed = kind == "conv" || kind == "pool" || kind == "avgpool";
-        if (!windowed && kind != "bn" && kind != "square" && kind != "fc" && kind != "pad" && kind != "poly" && kind != "poly3" && kind != "rescale") descError(ln, "unknown layer kind '" + kind + "'");
+        const bool windowed = kind == "conv" || kind == "pool" || kind == "avgpool" || kind == "client_maxpool";
+        if (!windowed && kind != "bn" && kind != "square" && kind != "fc" && kind != "pad" && kind != "poly" && kind != "poly3" && kind != "rescale" &&
+            kind != "client_relu") descError(ln, "unknown layer kind '" + kind + "'");
         if (tok.size() < 2) descError(ln, kind + ": the layer name is missing");
         LayerSpec L;
         L.kind = kind; L.name = tok[1]; L.line = ln; L.zd = zd; L.xd = xd; L.yd = yd;
@@ -2626,6 +2688,19 @@ NetworkDescription NetworkDescription::parse(const string &text, const string &h
         }
         if (flat && (windowed || kind == "pad" || kind == "poly" || kind == "poly3"))
             descError(ln, "a " + kind + " layer cannot follow a fully connected layer: the tensor is flat (" + to_string(xd) + " values)");
+        // what may follow the bit count of a client_relu / client_maxpool line: [relu] [cap C]; the cap in slot units is nearbyint(C 2^bits), at least 1 (its
+        // upper limit (t - 1) / 2 is the builder's to check: it needs the plain modulus)
+        auto clientTail = [&](size_t pos, bool with_relu) {
+            if (L.bits > 30) descError(ln, kind + ": the bit count must be in 0..30");
+            if (with_relu && pos < rest.size() && rest[pos] == "relu") { L.relu = true; pos++; }
+            if (pos < rest.size() && rest[pos] == "cap") {
+                if (pos + 1 >= rest.size()) descError(ln, kind + ": `cap` takes a value");
+                L.cap = descFloat(ln, rest[pos + 1], "cap"); L.has_cap = true;
+                if (nearbyint((double)L.cap * ldexp(1.0, L.bits)) < 1) descError(ln, kind + ": the cap " + rest[pos + 1] + " is below one unit of the scale 2^" + to_string(L.bits));
+                pos += 2;
+            }
+            if (pos != rest.size()) descError(ln, "unknown token '" + rest[pos] + "'");
+        };
         if (windowed) {
             size_t pos = 0;
             auto values = [&](const char *key, int *a, int *b) {
@@ -2638,6 +2713,7 @@ NetworkDescription NetworkDescription::parse(const string &text, const string &h
             values("stride", &L.xs, &L.ys);
             values(kind == "conv" ? "filter" : "window", &L.xf, &L.yf);
             if (kind == "conv") values("filters", &L.nf, nullptr);
+            if (kind == "client_maxpool") { values("bits", &L.bits, nullptr); clientTail(pos, true); pos = rest.size(); }
             if (pos != rest.size()) descError(ln, "unknown token '" + rest[pos] + "'");
             if (L.xs < 1 || L.ys < 1 || L.xf < 1 || L.yf < 1) descError(ln, kind + ": strides and window sizes must be positive");
             if (L.xf > xd || L.yf > yd)
@@ -2666,6 +2742,12 @@ NetworkDescription NetworkDescription::parse(const string &text, const string &h
             if (rest.size() != 1) descError(ln, rest.size() > 1 ? "unknown token '" + rest[1] + "'" : string("rescale: takes the scale's bit count"));
             L.bits = descInt(ln, rest[0], "rescale");
             if (L.bits > 30) descError(ln, "rescale: the bit count must be in 0..30");
+            L.zo = zd; L.xo = xd; L.yo = yd;
+        } else if (kind == "client_relu") {
+            if (rest.empty()) descError(ln, "client_relu: takes the scale's bit count");
+            L.bits = descInt(ln, rest[0], "client_relu");
+            clientTail(1, false);
+            L.relu = true;
             L.zo = zd; L.xo = xd; L.yo = yd;
         } else if (kind == "poly") {
             if (rest.size() != 3) descError(ln, rest.size() > 3 ? "unknown token '" + rest[3] + "'" : string("poly: takes c2 c1 c0"));
@@ -2715,6 +2797,10 @@ string NetworkDescription::str() const
         else if (L.kind == "fc") o << " " << L.out_dim;
         else if (L.kind == "pad") o << " " << L.px << " " << L.py;
         else if (L.kind == "rescale") o << " " << L.bits;
+        else if (L.kind == "client_relu") o << " " << L.bits << (L.has_cap ? " cap " + descFloatStr(L.cap) : string());
+        else if (L.kind == "client_maxpool")
+            o << " stride " << L.xs << " " << L.ys << " window " << L.xf << " " << L.yf << " bits " << L.bits << (L.relu ? " relu" : "")
+              << (L.has_cap ? " cap " + descFloatStr(L.cap) : string());
         else if (L.kind == "poly") o << " " << descFloatStr(L.c2) << " " << descFloatStr(L.c1) << " " << descFloatStr(L.c0);
         else if (L.kind == "poly3") o << " " << descFloatStr(L.c3) << " " << descFloatStr(L.c2) << " " << descFloatStr(L.c1) << " " << descFloatStr(L.c0);
         if (L.threads >= 0 && L.threads != 1) o << " threads " << L.threads;          // (1 is what a layer without the token is built with)
@@ -2742,6 +2828,9 @@ string Network::describe() const
             L.threads = p3->th_count; }
         else if (dynamic_pointer_cast<BatchNormLayer>(l)) L.kind = "bn";
         else if (auto rs = dynamic_pointer_cast<SlotRescaleLayer>(l)) { L.kind = "rescale"; L.bits = rs->bits; }
+        else if (auto cr = dynamic_pointer_cast<SlotReluLayer>(l)) { L.kind = "client_relu"; L.bits = cr->bits; L.has_cap = cr->cap_value != 0; L.cap = cr->cap_value; }
+        else if (auto cm = dynamic_pointer_cast<SlotMaxPoolLayer>(l)) { L.kind = "client_maxpool"; L.xs = cm->xs; L.ys = cm->ys; L.xf = cm->xf; L.yf = cm->yf;
+            L.bits = cm->bits; L.relu = cm->relu; L.has_cap = cm->cap_value != 0; L.cap = cm->cap_value; }
         else throw logic_error("Network::describe: layer " + l->name + " has no description");
         d.layers.push_back(L);
     }
@@ -2853,9 +2942,10 @@ vector<double> slotScales(const NetworkDescription &d, int input_bits, int weigh
         else if (L.kind == "square") s = scaleTimes(L.line, s, s);
         else if (L.kind == "poly") s = scaleTimes(L.line, scaleTimes(L.line, s, s), W);
         else if (L.kind == "poly3") s = scaleTimes(L.line, scaleTimes(L.line, scaleTimes(L.line, s, s), s), W);
-        else if (L.kind == "rescale") {                     // the client divides every slot by sigma / 2^bits: an integer >= 1, or the line is refused
+        else if (L.kind == "rescale" || L.kind == "client_relu" || L.kind == "client_maxpool") {
+            // the client divides every slot by sigma / 2^bits: an integer >= 1, or the line is refused
             const double target = ldexp(1.0, L.bits);
-            if (s < target || fmod(s, target) != 0) descError(L.line, "rescale: the scale 2^" + to_string(L.bits) + " does not divide the scale in front of it");
+            if (s < target || fmod(s, target) != 0) descError(L.line, L.kind + ": the scale 2^" + to_string(L.bits) + " does not divide the scale in front of it");
             s = target;
         }
     }
@@ -2889,6 +2979,17 @@ Network CnnBuilder::buildNetworkFromDescription(const string &path_or_text, stri
             SlotRescaleLayer *r = new SlotRescaleLayer(L.name, L.bits);
             r->divisor = (uint64_t)(s / ldexp(1.0, L.bits));
             add(r);
+        }
+        else if (L.kind == "client_relu" || L.kind == "client_maxpool") {
+            if (!g_slot_on) descError(L.line, L.kind + " needs slot encoding (setSlotEncoding)");
+            const double capq = L.has_cap ? nearbyint((double)L.cap * ldexp(1.0, L.bits)) : 0;
+            if (capq > (double)((g_plain_modulus - 1) / 2)) descError(L.line, L.kind + ": the cap exceeds (t - 1) / 2 at the scale 2^" + to_string(L.bits));
+            const uint64_t divisor = (uint64_t)(s / ldexp(1.0, L.bits));
+            if (L.kind == "client_relu") { SlotReluLayer *r = new SlotReluLayer(L.name, L.bits, L.has_cap ? L.cap : 0.0f); r->divisor = divisor; r->cap = (uint64_t)capq; add(r); }
+            else {
+                SlotMaxPoolLayer *r = new SlotMaxPoolLayer(L.name, L.xs, L.ys, L.xf, L.yf, L.bits, L.relu, L.has_cap ? L.cap : 0.0f);
+                r->divisor = divisor; r->cap = (uint64_t)capq; add(r);
+            }
         }
         else if (L.kind == "conv") add(buildConvolutionalLayer(L.name, L.xd, L.yd, L.zd, L.xs, L.ys, L.xf, L.yf, L.nf, th, in));
         else if (L.kind == "pool") add(buildPoolingLayer(L.name, L.xd, L.yd, L.zd, L.xs, L.ys, L.xf, L.yf));

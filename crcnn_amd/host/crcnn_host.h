@@ -169,6 +169,12 @@ ciphertext3D refreshImages(const ciphertext3D &encrypted, int out_form = CRC_COE
 // (crc_slots_rescale_dev), encrypt under fresh randomness -- crc_slots_refresh[_sym]_dev in bounded passes on the shared scratch, seed / key and counter as
 // refreshImages.  CRC_COEFF / CRC_NTT in and out; std::invalid_argument for other forms, a divisor out of range or a context without slots
 ciphertext3D rescaleSlots(const ciphertext3D &encrypted, uint64_t divisor, int out_form, bool symmetric = false);
+// rescaleSlots with a client-side activation between decrypt and encrypt (crc_slots_refresh_act[_sym]_dev): per slot the maximum over the xf x yf window of
+// stride (xs, ys) of every [xd][yd] plane, floor(m / divisor + 1/2), relu: max(., 0), cap (slot units, 0: none): min(., cap).  The result has the window's
+// output shape, so a 2 x 2 / 2 window re-encrypts a quarter of what it decrypts.  Same seed / key / counter discipline (the counter advances by the OUTPUT
+// ciphertexts) and the same bounded passes on the shared scratch, cut at whole planes.  std::invalid_argument as rescaleSlots, and for a window the library's
+// window test refuses, relu outside {0, 1} or a cap above (t - 1) / 2.  The key holder sees the activations at this point, as with every rescale
+ciphertext3D actSlots(const ciphertext3D &encrypted, int xs, int ys, int xf, int yf, uint64_t divisor, int relu, uint64_t cap, int out_form, bool symmetric = false);
 // encryptImage's sibling for a client that holds the secret key: the pixels of one image ([zd][xd][yd]) or of a batch ([B][zd][xd][yd] floats, B = size /
 // (zd xd yd)) encrypted under the secret key on the device (crc_encrypt_sym_dev); same keystream discipline as encryptImage
 ciphertext3D encryptImageSymmetric(const std::vector<float> &pixels, int zd, int xd, int yd, int out_form = CRC_COEFF);
@@ -522,6 +528,37 @@ public:
     void printLayerStructure() override;
 };
 
+// `client_relu NAME BITS [cap C]` and `client_maxpool NAME stride XS YS window XF YF bits BITS [relu] [cap C]` of a slot-batched network: where the client
+// re-encodes every slot to the scale 2^BITS it also applies max(x, 0) and / or takes the maximum over a window of ciphertexts, slot by slot (actSlots).  Forms,
+// divisor and `symmetric` as SlotRescaleLayer; `cap` is in slot units of the scale behind the layer (0: none), set by the builder from C.  Network::fuse pairs
+// neither with anything
+class SlotReluLayer : public Layer {
+public:
+    int bits;
+    float cap_value;                                        // C of the description (0: no cap)
+    uint64_t divisor = 1, cap = 0;
+    bool symmetric = false;
+    SlotReluLayer(std::string name, int bits, float cap_value = 0.0f) : Layer(name), bits(bits), cap_value(cap_value) {}
+    ciphertext3D forward(ciphertext3D input) override;
+    void savePlaintextParameters(std::ostream *) override {}
+    void loadPlaintextParameters(std::istream *) override {}
+    void printLayerStructure() override;
+};
+class SlotMaxPoolLayer : public Layer {
+public:
+    int xs, ys, xf, yf, bits;
+    bool relu;
+    float cap_value;
+    uint64_t divisor = 1, cap = 0;
+    bool symmetric = false;
+    SlotMaxPoolLayer(std::string name, int xs, int ys, int xf, int yf, int bits, bool relu = false, float cap_value = 0.0f)
+        : Layer(name), xs(xs), ys(ys), xf(xf), yf(yf), bits(bits), relu(relu), cap_value(cap_value) {}
+    ciphertext3D forward(ciphertext3D input) override;
+    void savePlaintextParameters(std::ostream *) override {}
+    void loadPlaintextParameters(std::istream *) override {}
+    void printLayerStructure() override;
+};
+
 // What the five activation layers share, as MacLayer does for conv / dense: the pooling window Network::fuse() may put behind the activation (a flat layer has
 // none: the fields are 0, any input shape goes in and comes out) with the pooling's divisor, the NTT-form coefficient rows with their upload at the first forward,
 // and what every forward starts with.  The classes add their constructor, their one C-ABI call and printLayerStructure.  Nothing to save or load
@@ -770,6 +807,9 @@ public:
 //   poly NAME c2 c1 c0   (c2 x^2 + c1 x + c0: decimal numbers, read as double and rounded to float32; c2 != 0, all finite; written back as %.9g)
 //   poly3 NAME c3 c2 c1 c0   (c3 x^3 + c2 x^2 + c1 x + c0, two key switches and depth 2; the same number rules, c3 != 0)
 //   rescale NAME BITS   (slot encoding only: the client re-encodes every slot to the scale 2^BITS in front of the next layer, BITS in 0..30; SlotRescaleLayer)
+//   client_relu NAME BITS [cap C]   (slot encoding only: as rescale, and the client applies max(x, 0) -- and min(x, C) -- to every slot; SlotReluLayer)
+//   client_maxpool NAME stride xs ys window xf yf bits BITS [relu] [cap C]   (slot encoding only: as rescale, on the maximum over the window, slot by slot;
+//       changes the shape like pool; SlotMaxPoolLayer).  C: a decimal number as in poly; nearbyint(C 2^BITS) must be in 1..(t - 1) / 2
 // conv, fc, square, poly and poly3 lines may end in `threads N` (the th_count the reference's constructors take).  NAME is the HDF5 dataset prefix.
 // Every error is a std::invalid_argument whose message starts with "line N:".
 struct LayerSpec {
@@ -781,7 +821,9 @@ struct LayerSpec {
     int px = 0, py = 0;                                     // pad
     float c2 = 1.0f, c1 = 0.0f, c0 = 0.0f;                  // poly
     float c3 = 1.0f;                                        // poly3 (with c2 c1 c0)
-    int bits = 0;                                           // rescale: the scale behind the layer is 2^bits
+    int bits = 0;                                           // rescale, client_relu, client_maxpool: the scale behind the layer is 2^bits
+    bool relu = false, has_cap = false;                     // client_maxpool (client_relu: relu is implied); `cap C` present
+    float cap = 0.0f;                                       // C
     int threads = -1;                                       // -1: no `threads` token (the layer is built with th_count 1)
     int zo = 0, xo = 0, yo = 0;                             // output shape
 };
@@ -806,6 +848,7 @@ struct NetworkDescription {
 //   poly        c2 at W, c1 at W sigma, c0 at W sigma^2                             -> sigma^2 W
 //   poly3       c3 at W, c2 at W sigma, c1 at W sigma^2, c0 at W sigma^3            -> sigma^3 W
 //   rescale     none: every slot divided by sigma / 2^BITS, an integer >= 1         -> 2^BITS
+//   client_relu, client_maxpool   as rescale                                        -> 2^BITS
 // Every scale must be an integer below 2^62 that a double holds exactly; std::invalid_argument ("line N: ...") otherwise, for a `rescale` whose 2^BITS does not
 // divide sigma, and for a `refresh` (the fractional re-encoding of a refresh is not a slot-wise one: `rescale` is).  Needs no context
 std::vector<double> slotScales(const NetworkDescription &d, int input_bits, int weight_bits);

@@ -19,6 +19,8 @@
 //     layer, then "slot_scale <sigma>".  No GPU work
 //   test_host slots_build <description> <h5> <dir> <S> <input_bits> <weight_bits> [reps]     see do_slots_build
 //   test_host slots_rescale_plan <description> <h5> <dir> <S> <input_bits> <weight_bits>     see do_slots_rescale_plan
+//   test_host slots_act_plan <description> <h5> <dir> <S> <input_bits> <weight_bits>         see do_slots_act_plan
+//   test_host build_plain <description>                                                      see do_build_plain
 //   test_host plan <model> <h5> <dir> <batch> <fuse 0|1> <head_chunk> <matrix_cores 0|1> <layer_before_reenc>     see do_plan
 //   test_host searchlogic <min> <max> <first_good> <last_good> <min_q>
 //     the plain-modulus search on a synthetic predicate (t < first_good: MISPREDICTED, t > last_good: OUT_OF_BUDGET); no GPU work.
@@ -630,6 +632,17 @@ static int do_slots_describe(int argc, char **argv)
     return 0;
 }
 
+// build_plain <description>: the builder on a description WITHOUT slot encoding and without an engine -- for the lines only slot encoding admits, which it
+// refuses ("exception: line N: ... needs slot encoding", status 10) before any layer in front of them needs a context when they come first
+static int do_build_plain(int argc, char **argv)
+{
+    if (argc < 3) return 1;
+    CnnBuilder builder("");
+    Network net = builder.buildNetworkFromDescription(argv[2]);
+    printf("build_plain ok %d layers\n", net.getNumLayers());
+    return 0;
+}
+
 // slots_build <description> <h5> <dir> <S> <input_bits> <weight_bits>: slot-batched inference through the host classes.  <dir>/params.u64 (n, k, t, q...: t a
 // slot prime), <dir>/images.f32 = [S][zd xd yd] float32 pixels.  Keys from a deterministic seed; the S images are encrypted into one tensor (encryptImageSlots),
 // run through Network::forward unfused and after Network::fuse(), decrypted and decomposed: slots_unfused.i64 / slots_fused.i64 = [S][outputs] int64.
@@ -749,6 +762,83 @@ static int do_slots_rescale_plan(int argc, char **argv)
         if (!thrown) { fprintf(stderr, "a rescale layer accepted a packed output form\n"); return 9; }
     }
     printf("slots_rescale_plan ok\n");
+    return 0;
+}
+
+// slots_act_plan <description> <h5> <dir> <S> <input_bits> <weight_bits>: slots_rescale_plan for a slot-batched network with client-side activation layers
+// (`client_relu` / `client_maxpool`: SlotReluLayer, SlotMaxPoolLayer) -- files as for slots_build.  The NTT-resident forward of one tensor is the yardstick; the same integers must come out of
+//   a profiled forward timed with events (profile_budget, time_with_events): every client layer is timed as a layer (last_reenc_ms stays 0), its producer
+//     hands over CRC_NTT, and its output has more noise budget than its input;
+//   two-level chunking (three tensors stacked into a batch, head_chunk = 1): the layer works per ciphertext, so every image of the batch gives the yardstick;
+//   a forward that is not NTT-resident; and one whose client layers re-encrypt under the secret key (their `symmetric`).
+// A client layer asked for a form that is no ciphertext form throws std::invalid_argument.  Prints "slots_act_plan ok"
+static int do_slots_act_plan(int argc, char **argv)
+{
+    if (argc < 8) return 1;
+    const string desc = argv[2], h5 = argv[3], dir = argv[4]; const int S = atoi(argv[5]), in_bits = atoi(argv[6]), w_bits = atoi(argv[7]);
+    // Every way out of this driver, a failed check's early return and an exception included, releases the engine first (declared in front of the network and the
+    // tensors, so it goes last): the library's global device buffers must not be freed by static destructors, after the HIP runtime's own exit handlers have run
+    struct Release { ~Release() { delParameters(); clearDeterministicSeed(); } } release;
+    setDeterministicSeed(20240613);
+    setup(dir);
+    setSlotEncoding(in_bits, w_bits);
+    CnnBuilder builder(h5);
+    Network net = builder.buildNetworkFromDescription(desc);
+    const size_t px = (size_t)net.input_zd * net.input_xd * net.input_yd;
+    vector<vector<float>> images(S, vector<float>(px));
+    { ifstream f(dir + "/images.f32", ios::binary); if (!f) { fprintf(stderr, "missing images.f32\n"); return 2; }
+      for (auto &im : images) f.read((char *)im.data(), px * 4);
+      if (!f) { fprintf(stderr, "images.f32 is too short\n"); return 2; } }
+    const ciphertext3D in = encryptImageSlots(images, net.input_zd, net.input_xd, net.input_yd);
+    vector<int> at;
+    for (int i = 0; i < net.getNumLayers(); i++) if (dynamic_pointer_cast<SlotReluLayer>(net.getLayers()[i]) || dynamic_pointer_cast<SlotMaxPoolLayer>(net.getLayers()[i])) at.push_back(i);
+    if (at.empty()) { fprintf(stderr, "the description has no client_relu or client_maxpool layer\n"); return 2; }
+    net.ntt_resident = true;
+    const vector<vector<int64_t>> ref = decryptSlots(net.forward(in), S);
+    // profiled, timed with events
+    net.profile_budget = true; net.time_with_events = true;
+    if (decryptSlots(net.forward(in), S) != ref) { fprintf(stderr, "the profiled forward differs\n"); return 5; }
+    if (net.last_reenc_ms != 0.0) { fprintf(stderr, "a client layer was timed as T_REENC\n"); return 5; }
+    for (int i : at) {
+        if (i == 0) continue;
+        const int before = net.last_layer_budget_min[i - 1], after = net.last_layer_budget_min[i];
+        printf("client layer %d: %.3f ms, budget %d -> %d, producer out_form %d\n", i, net.last_layer_ms[i], before, after, net.getLayers()[i - 1]->out_form);
+        if (!(net.last_layer_ms[i] > 0.0) || net.last_layer_launches[i] != 1) { fprintf(stderr, "client layer %d was not timed as a layer\n", i); return 5; }
+        if (net.getLayers()[i - 1]->out_form != CRC_NTT) { fprintf(stderr, "the producer of client layer %d does not hand over CRC_NTT\n", i); return 5; }
+        if (before < 0 || after <= before) { fprintf(stderr, "client layer %d: budget %d -> %d\n", i, before, after); return 5; }
+    }
+    net.profile_budget = false; net.time_with_events = false;
+    // two-level chunking: three tensors of the same images (fresh randomness each) as one batch, one image per chunk
+    {
+        vector<ciphertext3D> three = {in, encryptImageSlots(images, net.input_zd, net.input_xd, net.input_yd), encryptImageSlots(images, net.input_zd, net.input_xd, net.input_yd)};
+        const ciphertext3D batch = stackImages(three);
+        net.head_chunk = 1;
+        const ciphertext3D out = net.forward(batch);
+        net.head_chunk = 0;
+        if (out.B != 3) { fprintf(stderr, "the chunked forward returned %d images\n", out.B); return 6; }
+        const vector<vector<int64_t>> got = decryptSlots(out, S);
+        const size_t no = ref[0].size();
+        for (int s = 0; s < S; s++) for (int b = 0; b < 3; b++) for (size_t o = 0; o < no; o++)
+            if (got[s][b * no + o] != ref[s][o]) { fprintf(stderr, "the chunked forward differs at slot %d image %d output %zu\n", s, b, o); return 6; }
+    }
+    net.ntt_resident = false;
+    if (decryptSlots(net.forward(in), S) != ref) { fprintf(stderr, "the layerwise (coefficient-form) forward differs\n"); return 7; }
+    net.ntt_resident = true;
+    for (int i : at) {
+        if (auto r = dynamic_pointer_cast<SlotReluLayer>(net.getLayers()[i])) r->symmetric = true;
+        if (auto m = dynamic_pointer_cast<SlotMaxPoolLayer>(net.getLayers()[i])) m->symmetric = true;
+    }
+    if (decryptSlots(net.forward(in), S) != ref) { fprintf(stderr, "the forward with secret-key re-encryption differs\n"); return 8; }
+    {
+        SlotReluLayer r("r", 0);
+        SlotMaxPoolLayer m("m", 1, 1, 1, 1, 0);
+        r.out_form = m.out_form = CRC_NTTP;
+        int thrown = 0;
+        try { r.forward(in); } catch (const invalid_argument &) { thrown++; }
+        try { m.forward(in); } catch (const invalid_argument &) { thrown++; }
+        if (thrown != 2) { fprintf(stderr, "a client layer accepted a packed output form\n"); return 9; }
+    }
+    printf("slots_act_plan ok\n");
     return 0;
 }
 
@@ -980,6 +1070,8 @@ int main(int argc, char **argv)
         if (!strcmp(argv[1], "slots_describe")) return do_slots_describe(argc, argv);
         if (!strcmp(argv[1], "slots_build")) return do_slots_build(argc, argv);
         if (!strcmp(argv[1], "slots_rescale_plan")) return do_slots_rescale_plan(argc, argv);
+        if (!strcmp(argv[1], "slots_act_plan")) return do_slots_act_plan(argc, argv);
+        if (!strcmp(argv[1], "build_plain")) return do_build_plain(argc, argv);
     } catch (const exception &e) { fprintf(stderr, "exception: %s\n", e.what()); return 10; }
     return 1;
 }

@@ -70,7 +70,8 @@ def window_ok(xd, yd, xs, ys, xf, yf):
     return (xl + xs - 1) // xs == (xd - xf) // xs + 1 and (yl + ys - 1) // ys == (yd - yf) // ys + 1
 
 
-_KEYS = {"conv": (("stride", 2), ("filter", 2), ("filters", 1)), "pool": (("stride", 2), ("window", 2)), "avgpool": (("stride", 2), ("window", 2))}
+_KEYS = {"conv": (("stride", 2), ("filter", 2), ("filters", 1)), "pool": (("stride", 2), ("window", 2)), "avgpool": (("stride", 2), ("window", 2)),
+         "client_maxpool": (("stride", 2), ("window", 2), ("bits", 1))}
 _THREADED = ("conv", "fc", "square", "poly", "poly3")
 
 
@@ -106,6 +107,25 @@ def parse_description(text, dataset_count=None):
             raise ValueError(f"line {ln}: {what}: the coefficient must be finite, got '{t}'")
         return f
 
+    def client_tail(ln, kind, toks, bits, with_relu):
+        # what may follow the bit count of a client_relu / client_maxpool line: [relu] [cap C].  C is a decimal number like a poly coefficient; the cap in slot
+        # units is nearbyint(C 2^bits) and must be at least 1 (its upper limit (t - 1) / 2 is the builder's to check: it needs the plain modulus)
+        if bits > 30:
+            raise ValueError(f"line {ln}: {kind}: the bit count must be in 0..30")
+        relu, cap, pos = False, None, 0
+        if with_relu and pos < len(toks) and toks[pos] == "relu":
+            relu, pos = True, pos + 1
+        if pos < len(toks) and toks[pos] == "cap":
+            if pos + 1 >= len(toks):
+                raise ValueError(f"line {ln}: {kind}: `cap` takes a value")
+            cap = coef(ln, toks[pos + 1], "cap")
+            if float(np.rint(cap * float(1 << bits))) < 1:
+                raise ValueError(f"line {ln}: {kind}: the cap {toks[pos + 1]} is below one unit of the scale 2^{bits}")
+            pos += 2
+        if pos != len(toks):
+            raise ValueError(f"line {ln}: unknown token {toks[pos]!r}")
+        return relu, cap
+
     def check(ln, name, count):
         if dataset_count is None:
             return
@@ -135,7 +155,7 @@ def parse_description(text, dataset_count=None):
                 raise ValueError(f"line {ln}: a second refresh (line {pending_refresh or lines[refresh]} has the first)")
             pending_refresh = ln
             continue
-        if kind not in ("conv", "pool", "avgpool", "bn", "square", "fc", "pad", "poly", "poly3", "rescale"):
+        if kind not in ("conv", "pool", "avgpool", "bn", "square", "fc", "pad", "poly", "poly3", "rescale", "client_relu", "client_maxpool"):
             raise ValueError(f"line {ln}: unknown layer kind {kind!r}")
         if len(tok) < 2:
             raise ValueError(f"line {ln}: {kind}: the layer name is missing")
@@ -147,7 +167,7 @@ def parse_description(text, dataset_count=None):
             th = ints(ln, rest[-1:], "threads")[0]
             rest = rest[:-2]
         zd, xd, yd = shape
-        if flat and kind in ("conv", "pool", "avgpool", "pad", "poly", "poly3"):
+        if flat and kind in ("conv", "pool", "avgpool", "pad", "poly", "poly3", "client_maxpool"):
             raise ValueError(f"line {ln}: a {kind} layer cannot follow a fully connected layer: the tensor is flat ({xd} values)")
         if kind in _KEYS:
             vals, pos = {}, 0
@@ -158,6 +178,9 @@ def parse_description(text, dataset_count=None):
                 if len(vals[key]) != cnt:
                     raise ValueError(f"line {ln}: {kind}: `{key}` takes {cnt} value(s)")
                 pos += 1 + cnt
+            if kind == "client_maxpool":
+                relu, cap = client_tail(ln, kind, rest[pos:], vals["bits"][0], True)
+                pos = len(rest)
             if pos != len(rest):
                 raise ValueError(f"line {ln}: unknown token {rest[pos]!r}")
             (xs, ys), (xf, yf) = vals["stride"], vals["filter" if kind == "conv" else "window"]
@@ -168,6 +191,9 @@ def parse_description(text, dataset_count=None):
             if not window_ok(xd, yd, xs, ys, xf, yf):
                 raise ValueError(f"line {ln}: {kind}: stride {xs} x {ys} over a {xf} x {yf} window leaves a remainder of the {xd} x {yd} input without outputs")
             a = dict(xd=xd, yd=yd, zd=zd, xs=xs, ys=ys, xf=xf, yf=yf)
+            if kind == "client_maxpool":
+                # slot encoding only (the C++ Network): the client takes the window's maximum slot by slot where it re-encodes to the scale 2^bits
+                a.update(bits=vals["bits"][0], relu=relu, cap=cap)
             if kind == "conv":
                 a["nf"] = vals["filters"][0]
                 if a["nf"] < 1:
@@ -192,6 +218,12 @@ def parse_description(text, dataset_count=None):
             a = dict(bits=ints(ln, rest, "rescale")[0])
             if a["bits"] > 30:
                 raise ValueError(f"line {ln}: rescale: the bit count must be in 0..30")
+        elif kind == "client_relu":
+            # slot encoding only: the client applies max(x, 0) slot by slot where it re-encodes to the scale 2^bits; the shape passes through
+            if not rest:
+                raise ValueError(f"line {ln}: client_relu: takes the scale's bit count")
+            a = dict(bits=ints(ln, rest[:1], "client_relu")[0])
+            a["cap"] = client_tail(ln, kind, rest[1:], a["bits"], False)[1]
         elif kind == "poly":
             if len(rest) != 3:
                 raise ValueError(f"line {ln}: " + (f"unknown token {rest[3]!r}" if len(rest) > 3 else "poly: takes c2 c1 c0"))
@@ -241,6 +273,11 @@ def format_description(desc):
             ln = f"pad {name} {a['px']} {a['py']}"
         elif kind == "rescale":
             ln = f"rescale {name} {a['bits']}"
+        elif kind == "client_relu":
+            ln = f"client_relu {name} {a['bits']}" + ("" if a["cap"] is None else " cap %.9g" % a["cap"])
+        elif kind == "client_maxpool":
+            ln = (f"client_maxpool {name} stride {a['xs']} {a['ys']} window {a['xf']} {a['yf']} bits {a['bits']}" + (" relu" if a["relu"] else "") +
+                  ("" if a["cap"] is None else " cap %.9g" % a["cap"]))
         elif kind == "poly":
             ln = "poly %s %.9g %.9g %.9g" % (name, a["c2"], a["c1"], a["c0"])      # (%.9g of a float32 reads back as the same float32)
         elif kind == "poly3":
@@ -276,7 +313,7 @@ def out_shape(kind, a, in_shape):
         return (a["zd"], a["xd"] + 2 * a["px"], a["yd"] + 2 * a["py"])
     if kind == "conv":
         return (a["nf"], (a["xd"] - a["xf"]) // a["xs"] + 1, (a["yd"] - a["yf"]) // a["ys"] + 1)
-    if kind in ("pool", "avgpool"):
+    if kind in ("pool", "avgpool", "client_maxpool"):
         return (a["zd"], (a["xd"] - a["xf"]) // a["xs"] + 1, (a["yd"] - a["yf"]) // a["ys"] + 1)
     if kind == "fc":
         return (1, a["out_dim"], 1)
@@ -305,6 +342,9 @@ class Network:
         self.E, self.model, self.topo = eng, model, load_description(model, h5_path)
         if self.topo.layer_before_reenc >= 0:
             raise ValueError("this driver has no client side: a description with a refresh point runs through the C++ Network (crcnn_amd/host)")
+        if any(kind in ("client_relu", "client_maxpool") for kind, _, _ in self.topo):
+            raise ValueError("this driver has no slot mode: a description with a client_relu or client_maxpool layer runs through the C++ Network "
+                             "(crcnn_amd/host) under slot encoding")
         if any(kind == "rescale" for kind, _, _ in self.topo):
             raise ValueError("this driver has no slot mode: a description with a rescale layer runs through the C++ Network (crcnn_amd/host) under slot encoding")
         # conv / dense layers with long reductions run on the matrix cores (operand form CRC_NTTL, kernels_mfma.hip) unless CRC_MFMA=0

@@ -593,6 +593,43 @@ int crc_slots_refresh_sym_dev(crc_ctx *ctx, const uint64_t *d_sk_ntt, const uint
 int crc_slots_refresh_sym_dev_key(crc_ctx *ctx, const uint64_t *d_sk_ntt, const uint64_t *d_ct_in, size_t count, int in_form, uint64_t divisor,
                                   const uint8_t *h_key /*[32]*/, uint64_t stream_base, int out_form, uint64_t *d_ct_out, void *d_work, void *stream);
 
+/* act: the client-side ReLU and max pooling of a slot-batched network, taken where the rescale is taken -- while the slots are in the clear between decrypt and
+ * encrypt.  Input: plaintext rows p[planes][xd][yd][n], every word taken mod t; an xf x yf window of stride (xs, ys) the library's window test admits, outputs
+ * xo x yo = ((xd - xf) / xs + 1) x ((yd - yf) / ys + 1); 1 <= divisor D <= 2^62; relu 0 or 1; 0 <= cap <= (t - 1) / 2 (0: no cap).  For every output (pl, i, j)
+ * and every one of the n slots s:
+ *     m = max over a < xf, b < yf of the centred value of slot s of p[pl][i xs + a][j ys + b]
+ *     r = floor(m / D + 1/2) (floor division, ties towards +infinity, as the rescale);  relu: r = max(r, 0);  cap: r = min(r, cap)
+ *     out[pl][i][j] = the canonical coefficients of compose(r)
+ * Rounding is non-decreasing, so r is also the maximum of the individually rescaled values.  relu = 0, cap = 0 and a 1 x 1 window of stride 1 is
+ * crc_slots_rescale, bit for bit.  crc_slots_act: host memory, any context.  crc_slots_act_dev: device memory, asynchronous on `stream`, one kernel, one
+ * workgroup per output row, no work buffer; both pointers 16-byte aligned; d_plain_out may equal d_plain_in only for a 1 x 1 window of stride 1, any other overlap
+ * of the two tensors is CRC_ERR_INVALID_ARGUMENT and nothing is written; n <= 16384 (CRC_ERR_UNSUPPORTED above).  CRC_ERR_PARAMETERS on a context without slots
+ * comes first, then CRC_ERR_INVALID_ARGUMENT for a bad divisor, relu outside {0, 1}, cap > (t - 1) / 2, a refused window, a null or misaligned pointer;
+ * planes = 0 is CRC_OK.
+ *
+ * crc_slots_refresh_act_*: crc_decrypt_dev (size 2) of all planes * xd * yd ciphertexts, crc_slots_act_dev, crc_encrypt_dev[_key]_forms (public key) /
+ * crc_encrypt_sym_dev[_key]_forms (secret key) of the planes * xo * yo outputs, as one call on `stream`; by definition bit for bit what those three calls give
+ * with the same seed or key + stream_base.  A 2 x 2 window of stride 2 re-encrypts a quarter of the ciphertexts it decrypts.  d_ct_out may be d_ct_in (the whole
+ * input is decrypted into the work space before anything is written); d_work of crc_slots_refresh_act[_sym]_dev_work_bytes(...) bytes.
+ * Security is the rescale's: the key holder sees the activations at this point, nobody else does. */
+int crc_slots_act(crc_ctx *ctx, const uint64_t *h_plain_in /*[planes][xd][yd][n]*/, size_t planes, int xd, int yd, int xs, int ys, int xf, int yf, uint64_t divisor,
+                  int relu, uint64_t cap, uint64_t *h_plain_out /*[planes][xo][yo][n]*/);
+int crc_slots_act_dev(crc_ctx *ctx, const uint64_t *d_plain_in, size_t planes, int xd, int yd, int xs, int ys, int xf, int yf, uint64_t divisor, int relu,
+                      uint64_t cap, uint64_t *d_plain_out, void *stream);
+size_t crc_slots_refresh_act_dev_work_bytes(const crc_ctx *ctx, size_t planes, int xd, int yd, int xs, int ys, int xf, int yf, int in_form);
+int crc_slots_refresh_act_dev(crc_ctx *ctx, const uint64_t *d_sk_ntt, const uint64_t *d_pk, const uint64_t *d_ct_in, size_t planes, int xd, int yd, int xs, int ys,
+                              int xf, int yf, int in_form, uint64_t divisor, int relu, uint64_t cap, uint64_t seed, int out_form, uint64_t *d_ct_out, void *d_work,
+                              void *stream);
+int crc_slots_refresh_act_dev_key(crc_ctx *ctx, const uint64_t *d_sk_ntt, const uint64_t *d_pk, const uint64_t *d_ct_in, size_t planes, int xd, int yd, int xs,
+                                  int ys, int xf, int yf, int in_form, uint64_t divisor, int relu, uint64_t cap, const uint8_t *h_key /*[32]*/, uint64_t stream_base,
+                                  int out_form, uint64_t *d_ct_out, void *d_work, void *stream);
+size_t crc_slots_refresh_act_sym_dev_work_bytes(const crc_ctx *ctx, size_t planes, int xd, int yd, int xs, int ys, int xf, int yf, int in_form);
+int crc_slots_refresh_act_sym_dev(crc_ctx *ctx, const uint64_t *d_sk_ntt, const uint64_t *d_ct_in, size_t planes, int xd, int yd, int xs, int ys, int xf, int yf,
+                                  int in_form, uint64_t divisor, int relu, uint64_t cap, uint64_t seed, int out_form, uint64_t *d_ct_out, void *d_work, void *stream);
+int crc_slots_refresh_act_sym_dev_key(crc_ctx *ctx, const uint64_t *d_sk_ntt, const uint64_t *d_ct_in, size_t planes, int xd, int yd, int xs, int ys, int xf,
+                                      int yf, int in_form, uint64_t divisor, int relu, uint64_t cap, const uint8_t *h_key /*[32]*/, uint64_t stream_base,
+                                      int out_form, uint64_t *d_ct_out, void *d_work, void *stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Galois automorphisms: Evaluator::apply_galois / rotate_rows / rotate_columns (evaluator.cpp:1587-1834) and KeyGenerator::generate_galois_keys
  * (keygenerator.cpp:325-455) -- the operations that move data between the slots of a batched ciphertext.
