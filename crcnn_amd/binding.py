@@ -218,6 +218,16 @@ def load():
     L.crc_slots_refresh_act_sym_dev_work_bytes.restype = SZ; L.crc_slots_refresh_act_sym_dev_work_bytes.argtypes = [VP, SZ] + WIN + [CI]
     L.crc_slots_refresh_act_sym_dev.argtypes = [VP, VP, VP, SZ] + WIN + [CI, u64, CI, u64, u64, CI, VP, VP, VP]
     L.crc_slots_refresh_act_sym_dev_key.argtypes = [VP, VP, VP, SZ] + WIN + [CI, u64, CI, u64, PB, u64, CI, VP, VP, VP]
+    PVP = ctypes.POINTER(VP)                                   # a host array of r contexts / row pointers
+    L.crc_slots_crt_supported.argtypes = [PVP, CI]
+    L.crc_slots_crt_primes.argtypes = [CI, CI, CI, PU]
+    L.crc_slots_crt_decompose.argtypes = [PVP, CI, PVP, SZ, CI, PI64, SZ, SZ]
+    L.crc_slots_crt_decompose_dev.argtypes = [PVP, CI, PVP, SZ, CI, VP, SZ, SZ, VP]
+    L.crc_slots_crt_act.argtypes = [PVP, CI, PVP, SZ, u64, CI, u64, PVP]
+    L.crc_slots_crt_act_dev.argtypes = [PVP, CI, PVP, SZ, u64, CI, u64, PVP, VP]
+    L.crc_slots_crt_refresh_dev_work_bytes.restype = SZ; L.crc_slots_crt_refresh_dev_work_bytes.argtypes = [PVP, CI, SZ, CI]
+    L.crc_slots_crt_refresh_dev_key.argtypes = [PVP, CI, VP, VP, PVP, SZ, CI, u64, CI, u64, PB, u64, CI, PVP, VP, VP]
+    L.crc_slots_crt_refresh_sym_dev_key.argtypes = [PVP, CI, VP, PVP, SZ, CI, u64, CI, u64, PB, u64, CI, PVP, VP, VP]
     L.crc_encode_dev_f32.argtypes = [VP, VP, SZ, VP, VP]
     L.crc_encode_dev_f64.argtypes = [VP, VP, SZ, VP, VP]
     L.crc_refresh_dev_work_bytes.restype = SZ; L.crc_refresh_dev_work_bytes.argtypes = [VP, SZ, CI]
@@ -1702,3 +1712,88 @@ class Engine:
 
     def relinearize(self, d_x3, count, d_evk, d_y, d_work, dbc=16):
         _chk(self.L.crc_relinearize(self.c, self.p(d_x3), count, self.p(d_evk), dbc, self.p(d_y), self.p(d_work), self.stream), "crc_relinearize")
+
+
+class SlotsCrt:
+    """A residue base: r <= 4 Engines of one n, q and device whose slot primes t_j are pairwise distinct with T = prod t_j < 2**63 (crc_slots_crt_*).  The same
+    network runs under every engine; the slots recombine into centred integers mod T.  Keys do not involve t: one key set serves all engines"""
+    MAX = 4
+
+    def __init__(self, engines):
+        self.E = list(engines)
+        self.L = self.E[0].L
+        self.r, self.n = len(self.E), self.E[0].n
+        self.ts = [e.t for e in self.E]
+        self.T = int(np.prod([int(t) for t in self.ts], dtype=object))
+        self.stream = self.E[0].stream
+
+    def _ctxs(self):
+        return (VP * self.r)(*[e.c for e in self.E])
+
+    def _rows(self, bufs):
+        assert len(bufs) == self.r
+        return (VP * self.r)(*[Engine.p(b) for b in bufs])
+
+    @property
+    def supported(self):
+        return bool(self.L.crc_slots_crt_supported(self._ctxs(), self.r))
+
+    @staticmethod
+    def primes(n, r, bits):
+        """the r largest primes below 2**bits that are 1 mod 2n, descending"""
+        t = np.zeros(r, dtype=np.uint64)
+        _chk(load().crc_slots_crt_primes(int(n), int(r), int(bits), _pu(t)), "crc_slots_crt_primes")
+        return [int(x) for x in t]
+
+    def compose(self, values, count, slots, item_stride, slot_stride):
+        """host: the r existing calls on the same int64 values -> [r][count][n]"""
+        return np.stack([e.slots_compose(values, count, slots, item_stride, slot_stride) for e in self.E])
+
+    def compose_dev(self, d_values, count, slots, item_stride, slot_stride, d_plains):
+        for e, d in zip(self.E, d_plains):
+            e.slots_compose_dev(d_values, count, slots, item_stride, slot_stride, d)
+
+    def decompose(self, plains, slots, item_stride, slot_stride, size=None):
+        """host twin: plaintexts [r][count][n] -> flat int64 array, the centred integers mod T"""
+        plains = np.ascontiguousarray(plains, dtype=np.uint64).reshape(self.r, -1, self.n); count = plains.shape[1]
+        need = (count - 1) * item_stride + (slots - 1) * slot_stride + 1
+        out = np.zeros(need if size is None else size, dtype=np.int64)
+        assert out.size >= need
+        rows = (VP * self.r)(*[plains[j].ctypes.data for j in range(self.r)])
+        _chk(self.L.crc_slots_crt_decompose(self._ctxs(), self.r, rows, count, slots, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), item_stride, slot_stride),
+             "crc_slots_crt_decompose")
+        return out
+
+    def decompose_dev(self, d_plains, count, slots, d_values, item_stride, slot_stride):
+        _chk(self.L.crc_slots_crt_decompose_dev(self._ctxs(), self.r, self._rows(d_plains), count, slots, Engine.p(d_values), item_stride, slot_stride, self.stream),
+             "crc_slots_crt_decompose_dev")
+
+    def act(self, plains, divisor, relu=0, cap=0):
+        """host twin: plaintexts [r][count][n] -> [r][count][n]; per slot floor(V / divisor + 1/2) of the lifted integer V, ReLU, cap, reduced mod every t_j"""
+        plains = np.ascontiguousarray(plains, dtype=np.uint64).reshape(self.r, -1, self.n)
+        out = np.zeros_like(plains)
+        rin = (VP * self.r)(*[plains[j].ctypes.data for j in range(self.r)])
+        rout = (VP * self.r)(*[out[j].ctypes.data for j in range(self.r)])
+        _chk(self.L.crc_slots_crt_act(self._ctxs(), self.r, rin, plains.shape[1], int(divisor), int(relu), int(cap), rout), "crc_slots_crt_act")
+        return out
+
+    def act_dev(self, d_in, count, divisor, relu, cap, d_out):
+        _chk(self.L.crc_slots_crt_act_dev(self._ctxs(), self.r, self._rows(d_in), count, int(divisor), int(relu), int(cap), self._rows(d_out), self.stream),
+             "crc_slots_crt_act_dev")
+
+    def refresh_dev_work_bytes(self, count, in_form=COEFF):
+        return self.L.crc_slots_crt_refresh_dev_work_bytes(self._ctxs(), self.r, count, in_form)
+
+    refresh_sym_dev_work_bytes = refresh_dev_work_bytes           # one size serves either call
+
+    def refresh_dev(self, d_sk, d_pk, d_ct_in, count, divisor, relu, cap, key, stream_base, d_ct_out, d_work, in_form=COEFF, out_form=COEFF):
+        """on every engine: decrypt -> the CRT activation over the r plaintext tensors -> encrypt under the public key (stream base stream_base + j * count)"""
+        _chk(self.L.crc_slots_crt_refresh_dev_key(self._ctxs(), self.r, Engine.p(d_sk), Engine.p(d_pk), self._rows(d_ct_in), count, in_form, int(divisor), int(relu),
+                                                  int(cap), Engine._key(key), stream_base, out_form, self._rows(d_ct_out), Engine.p(d_work), self.stream),
+             "crc_slots_crt_refresh_dev_key")
+
+    def refresh_sym_dev(self, d_sk, d_ct_in, count, divisor, relu, cap, key, stream_base, d_ct_out, d_work, in_form=COEFF, out_form=COEFF):
+        """the same under the secret key"""
+        _chk(self.L.crc_slots_crt_refresh_sym_dev_key(self._ctxs(), self.r, Engine.p(d_sk), self._rows(d_ct_in), count, in_form, int(divisor), int(relu), int(cap),
+                                                      Engine._key(key), stream_base, out_form, self._rows(d_ct_out), Engine.p(d_work), self.stream),
+             "crc_slots_crt_refresh_sym_dev_key")

@@ -1024,6 +1024,148 @@ extern "C" int crc_slots_refresh_act_sym_dev_key(crc_ctx *c, const uint64_t *d_s
     return slots_refresh_act_impl(c, true, d_sk, nullptr, d_ct_in, {planes, {xd, yd, xs, ys, xf, yf}, divisor, relu, cap}, in_form, chacha_load_key(key), stream_base,
                                   out_form, d_ct_out, d_work, S(stream));
 }
+// ---- several plain moduli: the CRT lift of the slots of r plaintext tensors, the activation on the lifted integers, the refresh that applies it ----
+extern "C" int crc_slots_crt_supported(crc_ctx *const *ctxs, int r)
+{
+    if (!ctxs || r < 1 || r > CRC_SLOTS_CRT_MAX) return 0;
+    for (int j = 0; j < r; j++) if (!ctxs[j] || ctxs[j]->n != ctxs[0]->n || ctxs[j]->device != ctxs[0]->device || !crc_slots_supported(ctxs[j])) return 0;
+    SlotsCrtBase B;
+    return k_slots_crt_base(ctxs, r, &B) ? 1 : 0;
+}
+// the refusals every entry point shares, in the header's order: the base itself (invalid, then parameters), leaving its constants in B
+static int slots_crt_base_ok(crc_ctx *const *ctxs, int r, SlotsCrtBase &B)
+{
+    if (!ctxs || r < 1 || r > CRC_SLOTS_CRT_MAX) return CRC_ERR_INVALID_ARGUMENT;
+    for (int j = 0; j < r; j++) if (!ctxs[j]) return CRC_ERR_INVALID_ARGUMENT;
+    if (!crc_slots_crt_supported(ctxs, r) || !k_slots_crt_base(ctxs, r, &B)) return CRC_ERR_PARAMETERS;
+    return CRC_OK;
+}
+// an array of r row pointers: none null, none misaligned (align = 1 for host memory)
+static bool slots_crt_rows_ok(const uint64_t *const *rows, int r, uintptr_t align)
+{
+    if (!rows) return false;
+    for (int j = 0; j < r; j++) if (!rows[j] || ((uintptr_t)rows[j] & (align - 1))) return false;
+    return true;
+}
+static int slots_crt_decompose_args_ok(const crc_ctx *c, int r, const uint64_t *const *plain, const void *values, int slots, size_t item_stride, size_t slot_stride,
+                                       uintptr_t align)
+{
+    if (!slots_crt_rows_ok(plain, r, align) || !values || slots < 1 || slots > c->n || !item_stride || !slot_stride) return CRC_ERR_INVALID_ARGUMENT;
+    if (align > 1 && ((uintptr_t)values & 7)) return CRC_ERR_INVALID_ARGUMENT;
+    return CRC_OK;
+}
+// an output row tensor may be its own input; it overlaps nothing else
+static int slots_crt_act_args_ok(const crc_ctx *c, const SlotsCrtBase &B, const uint64_t *const *in, size_t count, uint64_t divisor, int relu, uint64_t cap,
+                                 uint64_t *const *out, uintptr_t align)
+{
+    if (divisor < 1 || divisor > ((uint64_t)1 << 62) || (relu != 0 && relu != 1) || cap > ((B.T - 1) >> 1)) return CRC_ERR_INVALID_ARGUMENT;
+    if (!slots_crt_rows_ok(in, B.r, align) || !slots_crt_rows_ok(out, B.r, align)) return CRC_ERR_INVALID_ARGUMENT;
+    if (((unsigned __int128)count * (uint64_t)c->n) >> 60) return CRC_ERR_INVALID_ARGUMENT;
+    const uintptr_t bytes = count * (size_t)c->n * 8;
+    for (int j = 0; j < B.r; j++) {
+        const uintptr_t ob = (uintptr_t)out[j], oe = ob + bytes;
+        for (int i = 0; i < B.r; i++) {
+            const uintptr_t ib = (uintptr_t)in[i], pb = (uintptr_t)out[i];
+            if (ib < oe && ob < ib + bytes && !(i == j && ib == ob)) return CRC_ERR_INVALID_ARGUMENT;
+            if (i != j && pb < oe && ob < pb + bytes) return CRC_ERR_INVALID_ARGUMENT;
+        }
+    }
+    return CRC_OK;
+}
+extern "C" int crc_slots_crt_decompose(crc_ctx *const *ctxs, int r, const uint64_t *const *h_plain, size_t count, int slots, int64_t *h_values, size_t item_stride,
+                                       size_t slot_stride)
+{
+    SlotsCrtBase B;
+    RUN(slots_crt_base_ok(ctxs, r, B));
+    RUN(slots_crt_decompose_args_ok(ctxs[0], r, h_plain, h_values, slots, item_stride, slot_stride, 1));
+    return k_slots_crt_decompose_host(ctxs, B, h_plain, count, slots, (long long *)h_values, item_stride, slot_stride);
+}
+extern "C" int crc_slots_crt_decompose_dev(crc_ctx *const *ctxs, int r, const uint64_t *const *d_plain, size_t count, int slots, int64_t *d_values,
+                                           size_t item_stride, size_t slot_stride, void *stream)
+{
+    SlotsCrtBase B;
+    if (!ctxs || r < 1 || r > CRC_SLOTS_CRT_MAX) return CRC_ERR_INVALID_ARGUMENT;
+    CHECK_CTX(ctxs[0]);
+    RUN(slots_crt_base_ok(ctxs, r, B));
+    RUN(slots_crt_decompose_args_ok(ctxs[0], r, d_plain, d_values, slots, item_stride, slot_stride, 16));
+    return k_slots_crt_decompose(ctxs, B, d_plain, count, slots, (long long *)d_values, item_stride, slot_stride, S(stream));
+}
+extern "C" int crc_slots_crt_act(crc_ctx *const *ctxs, int r, const uint64_t *const *h_in, size_t count, uint64_t divisor, int relu, uint64_t cap,
+                                 uint64_t *const *h_out)
+{
+    SlotsCrtBase B;
+    RUN(slots_crt_base_ok(ctxs, r, B));
+    RUN(slots_crt_act_args_ok(ctxs[0], B, h_in, count, divisor, relu, cap, h_out, 1));
+    return k_slots_crt_act_host(ctxs, B, h_in, count, divisor, relu, cap, h_out);
+}
+extern "C" int crc_slots_crt_act_dev(crc_ctx *const *ctxs, int r, const uint64_t *const *d_in, size_t count, uint64_t divisor, int relu, uint64_t cap,
+                                     uint64_t *const *d_out, void *stream)
+{
+    SlotsCrtBase B;
+    if (!ctxs || r < 1 || r > CRC_SLOTS_CRT_MAX) return CRC_ERR_INVALID_ARGUMENT;
+    CHECK_CTX(ctxs[0]);
+    RUN(slots_crt_base_ok(ctxs, r, B));
+    RUN(slots_crt_act_args_ok(ctxs[0], B, d_in, count, divisor, relu, cap, d_out, 16));
+    return k_slots_crt_act(ctxs, B, d_in, count, divisor, relu, cap, d_out, S(stream));
+}
+// Work: [decrypted plaintexts of modulus j [count][n], j < r: the activation works on them in place][the decryptor's rows, then the encryptor's samples: the
+// largest over the r contexts and over both encryptors, so that one size serves either call]
+struct SlotsCrtRefreshWork { u64 *plain[CRC_SLOTS_CRT_MAX]; u64 *w; };
+static SlotsCrtRefreshWork slots_crt_refresh_layout(crc_ctx *const *ctxs, int r, size_t count, int in_form, WorkArena &a)
+{
+    SlotsCrtRefreshWork L{};
+    size_t w = 0;
+    for (int j = 0; j < r; j++) {
+        const crc_ctx *c = ctxs[j];
+        L.plain[j] = a.take<u64>(count * (size_t)c->n);
+        for (const size_t s : {k_decrypt_work_words(c, count, 2, in_form == CRC_NTT), k_encrypt_sym_work_words(c, count), k_encrypt_work_words(c, count)}) w = s > w ? s : w;
+    }
+    L.w = a.take<u64>(w);
+    return L;
+}
+extern "C" size_t crc_slots_crt_refresh_dev_work_bytes(crc_ctx *const *ctxs, int r, size_t count, int in_form)
+{
+    SlotsCrtBase B;
+    if (slots_crt_base_ok(ctxs, r, B) || !ct_form_ok(in_form)) return 0;
+    WorkArena a;
+    slots_crt_refresh_layout(ctxs, r, count, in_form, a);
+    return a.bytes();
+}
+// sym: encrypt under the secret key (d_pk unused)
+static int slots_crt_refresh_impl(crc_ctx *const *ctxs, int r, bool sym, const u64 *d_sk, const u64 *d_pk, const uint64_t *const *d_in, size_t count, int in_form,
+                                  u64 divisor, int relu, u64 cap, const uint8_t *key, u64 stream_base, int out_form, uint64_t *const *d_out, void *d_work, hipStream_t st)
+{
+    SlotsCrtBase B;
+    if (!ctxs || r < 1 || r > CRC_SLOTS_CRT_MAX) return CRC_ERR_INVALID_ARGUMENT;
+    CHECK_CTX(ctxs[0]);
+    RUN(slots_crt_base_ok(ctxs, r, B));
+    if (divisor < 1 || divisor > ((uint64_t)1 << 62) || (relu != 0 && relu != 1) || cap > ((B.T - 1) >> 1)) return CRC_ERR_INVALID_ARGUMENT;
+    if (!slots_crt_rows_ok(d_in, r, 16) || !slots_crt_rows_ok(d_out, r, 16)) return CRC_ERR_INVALID_ARGUMENT;
+    if (!d_sk || (!sym && !d_pk) || !d_work || !key || !ct_form_ok(in_form) || !ct_form_ok(out_form)) return CRC_ERR_INVALID_ARGUMENT;
+    if (!count) return CRC_OK;
+    WorkArena a(d_work);
+    const SlotsCrtRefreshWork L = slots_crt_refresh_layout(ctxs, r, count, in_form, a);
+    const ChaChaKey k = chacha_load_key(key);
+    for (int j = 0; j < r; j++) RUN(k_decrypt(ctxs[j], d_sk, d_in[j], count, 2, in_form == CRC_NTT, L.plain[j], L.w, st));
+    RUN(k_slots_crt_act(ctxs, B, L.plain, count, divisor, relu, cap, L.plain, st));
+    for (int j = 0; j < r; j++) {
+        if (sym) RUN(k_encrypt_sym(ctxs[j], d_sk, L.plain[j], count, k, stream_base + (u64)j * count, d_out[j], L.w, st, out_form == CRC_NTT, false));
+        else RUN(k_encrypt(ctxs[j], d_pk, L.plain[j], count, k, stream_base + (u64)j * count, d_out[j], L.w, st, out_form == CRC_NTT));
+    }
+    return CRC_OK;
+}
+extern "C" int crc_slots_crt_refresh_dev_key(crc_ctx *const *ctxs, int r, const uint64_t *d_sk, const uint64_t *d_pk, const uint64_t *const *d_ct_in, size_t count,
+                                             int in_form, uint64_t divisor, int relu, uint64_t cap, const uint8_t *key, uint64_t stream_base, int out_form,
+                                             uint64_t *const *d_ct_out, void *d_work, void *stream)
+{
+    return slots_crt_refresh_impl(ctxs, r, false, d_sk, d_pk, d_ct_in, count, in_form, divisor, relu, cap, key, stream_base, out_form, d_ct_out, d_work, S(stream));
+}
+extern "C" int crc_slots_crt_refresh_sym_dev_key(crc_ctx *const *ctxs, int r, const uint64_t *d_sk, const uint64_t *const *d_ct_in, size_t count, int in_form,
+                                                 uint64_t divisor, int relu, uint64_t cap, const uint8_t *key, uint64_t stream_base, int out_form,
+                                                 uint64_t *const *d_ct_out, void *d_work, void *stream)
+{
+    return slots_crt_refresh_impl(ctxs, r, true, d_sk, nullptr, d_ct_in, count, in_form, divisor, relu, cap, key, stream_base, out_form, d_ct_out, d_work, S(stream));
+}
 // ---- seeded secret-key ciphertexts: the packed c0 rows and a public seed -> ordinary ciphertexts (kernels_client.hip: k_seeded_expand) ----
 extern "C" int crc_seeded_expand_dev(crc_ctx *c, const uint64_t *d_c0, size_t count, const uint8_t *seed, uint64_t stream_base, int out_form, uint64_t *d_ct,
                                      void *stream)

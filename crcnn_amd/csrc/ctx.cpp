@@ -573,6 +573,24 @@ extern "C" int crc_slots_prime(int n, int bits, uint64_t *t)
     for (u64 cand = (top - 2) / m * m + 1; cand > m; cand -= m) if (is_prime(cand)) { *t = cand; return CRC_OK; }
     return CRC_ERR_NOT_FOUND;
 }
+// the moduli of a residue base (crc_slots_crt_*): the r largest such primes below 2^bits, as long as their product stays below 2^63
+extern "C" int crc_slots_crt_primes(int n, int r, int bits, uint64_t *t)
+{
+    if (!t || n < 2 || (n & (n - 1)) || bits < 2 || bits > 60 || r < 1 || r > CRC_SLOTS_CRT_MAX) return CRC_ERR_INVALID_ARGUMENT;
+    const u64 m = 2 * (u64)n, top = (u64)1 << bits;
+    if (top <= m) return CRC_ERR_NOT_FOUND;
+    u64 found[CRC_SLOTS_CRT_MAX];
+    int have = 0;
+    u128 T = 1;
+    for (u64 cand = (top - 2) / m * m + 1; cand > m && have < r; cand -= m) if (is_prime(cand)) {
+        T *= cand;
+        if (T >> 63) return CRC_ERR_NOT_FOUND;
+        found[have++] = cand;
+    }
+    if (have < r) return CRC_ERR_NOT_FOUND;
+    for (int j = 0; j < r; j++) t[j] = found[j];
+    return CRC_OK;
+}
 int crc_slots_tables(crc_ctx *c, const SlotTables **out)
 {
     if (!crc_slots_supported(c)) return CRC_ERR_PARAMETERS;

@@ -154,6 +154,18 @@ int k_slots_rescale_host(crc_ctx *c, const u64 *plain_in, size_t count, u64 divi
 // client-side activation of plaintext rows [planes][w.xd][w.yd][n] -> [planes][w.xo()][w.yo()][n]: window maximum, division, ReLU, cap, slot by slot
 int k_slots_act(crc_ctx *c, const u64 *d_in, size_t planes, const Window &w, u64 divisor, int relu, u64 cap, u64 *d_out, hipStream_t st);
 int k_slots_act_host(crc_ctx *c, const u64 *plain_in, size_t planes, const Window &w, u64 divisor, int relu, u64 cap, u64 *plain_out);
+// several plain moduli: r <= CRC_SLOTS_CRT_MAX contexts of one n with pairwise distinct slot primes t_j, T = t_0 ... t_{r-1} < 2^63.  P[j] = t_0 ... t_{j-1},
+// Pinv[j] = P[j]^-1 mod t_j with its Shoup companion (Garner's mixed-radix constants).  k_slots_crt_base: false where the t_j are no such base
+struct SlotsCrtBase { int r; u64 t[CRC_SLOTS_CRT_MAX], P[CRC_SLOTS_CRT_MAX], Pinv[CRC_SLOTS_CRT_MAX], Pinv_s[CRC_SLOTS_CRT_MAX], T; };
+bool k_slots_crt_base(crc_ctx *const *ctxs, int r, SlotsCrtBase *B);
+// row tensors plain[j] [count][n] mod t_j -> the centred integers mod T of the first `slots` slots, strided as k_slots_decompose's values
+int k_slots_crt_decompose(crc_ctx *const *ctxs, const SlotsCrtBase &B, const u64 *const *d_plain, size_t count, int slots, long long *d_values, size_t item_stride,
+                          size_t slot_stride, hipStream_t st);
+int k_slots_crt_decompose_host(crc_ctx *const *ctxs, const SlotsCrtBase &B, const u64 *const *plain, size_t count, int slots, long long *values, size_t item_stride,
+                               size_t slot_stride);
+// every slot's integer V mod T -> min(max(floor(V / divisor + 1/2), 0 if relu), cap if cap), reduced mod every t_j again; out[j] == in[j] allowed
+int k_slots_crt_act(crc_ctx *const *ctxs, const SlotsCrtBase &B, const u64 *const *d_in, size_t count, u64 divisor, int relu, u64 cap, u64 *const *d_out, hipStream_t st);
+int k_slots_crt_act_host(crc_ctx *const *ctxs, const SlotsCrtBase &B, const u64 *const *plain_in, size_t count, u64 divisor, int relu, u64 cap, u64 *const *plain_out);
 
 // kernels_seeded_keys.hip: seeded key-switching keys (chacha.h CHACHA_DOM_KSK_*; ids is a HOST array of key ids: 0 = evaluation key, else a Galois element).
 // first / rows [n_ids][P][k][n] NTT form, formed in place without work space; out [n_ids][crc_evk_words]; the host twins are crc_gen_keys_seeded_key and

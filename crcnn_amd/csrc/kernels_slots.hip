@@ -36,26 +36,49 @@ __global__ void __launch_bounds__(1024) slots_act_kernel(SlotActArgs a)
     slots_act_body<LAZY, PAIRS>(a, sm);
 }
 
-// The launch rules of the slot kernels in one place: t's tables, one workgroup of max(64, n / 8) threads per row with the row as its LDS image, the rows in
-// XCD groups.  `tables` puts the table pointers the kernel reads into the argument block; the ring's fields and the kernel's variant are chosen here.
-template <class Args, class Tables>
-static int slots_launch(crc_ctx *c, void (*lazy)(Args), void (*strict)(Args), Args &a, Tables tables, hipStream_t st)
+template <bool LAZY, int PAIRS>                             // PAIRS: the pairs a lane keeps running values for -- 4 up to n = 4096, 8 above (k_slots_crt_decompose)
+__global__ void __launch_bounds__(1024) slots_crt_decompose_kernel(SlotCrtArgs a)
 {
-    const SlotTables *T;
-    { const int rc = crc_slots_tables(c, &T); if (rc) return rc; }
+    extern __shared__ u64 sm[];
+    slots_crt_decompose_body<LAZY, PAIRS>(a, sm);
+}
+template <bool LAZY, int PAIRS>
+__global__ void __launch_bounds__(1024) slots_crt_act_kernel(SlotCrtArgs a)
+{
+    extern __shared__ u64 sm[];
+    slots_crt_act_body<LAZY, PAIRS>(a, sm);
+}
+
+// The launch rules of the slot kernels in one place: the tables of every plain modulus the kernel visits (one context, or the r contexts of a residue base), one
+// workgroup of max(64, n / 8) threads per row with the row as its LDS image, the rows in XCD groups.  `tables(a, j, T)` puts what the kernel reads of modulus j
+// into the argument block; the ring's fields and the kernel's variant -- lazy where every modulus is below 2^57 -- are chosen here.  `threads` (0: the rule
+// above) is for the kernels that keep a lane's running values in registers and want fewer, wider lanes.
+template <class Args, class Tables>
+static int slots_launch(crc_ctx *const *ctxs, int r, void (*lazy)(Args), void (*strict)(Args), Args &a, Tables tables, hipStream_t st, int threads = 0)
+{
+    const SlotTables *T[CRC_SLOTS_CRT_MAX];
+    for (int j = 0; j < r; j++) { const int rc = crc_slots_tables(ctxs[j], &T[j]); if (rc) return rc; }
     if (a.count == 0) return CRC_OK;
+    crc_ctx *c = ctxs[0];
     const size_t lds = (size_t)c->n * 8;
     if (lds > 128 * 1024) return CRC_ERR_UNSUPPORTED;                 // (n = 32768: the row does not fit the LDS; the host twins serve it)
     const size_t groups = (a.count + CRC_SLOT_GROUP - 1) / CRC_SLOT_GROUP;
     if ((groups + 7) / 8 * 8 * CRC_SLOT_GROUP > 0x7fffffffULL) return CRC_ERR_INVALID_ARGUMENT;
-    tables(a, *T);
-    a.n = c->n; a.logn = c->logn; a.t = c->t; a.one_s = T->one_s;
-    int nt = c->n / 8; if (nt < 64) nt = 64; if (nt > 1024) nt = 1024;
-    auto kern = T->lazy ? lazy : strict;
+    bool all_lazy = true;
+    for (int j = 0; j < r; j++) { tables(a, j, *T[j]); all_lazy = all_lazy && T[j]->lazy; }
+    a.n = c->n; a.logn = c->logn;
+    int nt = threads ? threads : c->n / 8; if (nt < 64) nt = 64; if (nt > 1024) nt = 1024;
+    auto kern = all_lazy ? lazy : strict;
     { const int rc = crc_ctx_ensure_lds(c, (const void *)kern, lds); if (rc) return rc; }
     hipLaunchKernelGGL(kern, dim3(xcd_grid(groups, CRC_SLOT_GROUP)), dim3(nt), lds, st, a);
     HIPCHK(hipGetLastError());
     return CRC_OK;
+}
+// the kernels of one plain modulus: the context's t and its Shoup companion of 1 go into the argument block with the tables
+template <class Args, class Tables>
+static int slots_launch(crc_ctx *c, void (*lazy)(Args), void (*strict)(Args), Args &a, Tables tables, hipStream_t st)
+{
+    return slots_launch(&c, 1, lazy, strict, a, [&](Args &a, int, const SlotTables &T) { tables(a, T); a.t = c->t; a.one_s = T.one_s; }, st);
 }
 
 int k_slots_compose(crc_ctx *c, const long long *d_values, size_t count, int slots, size_t item_stride, size_t slot_stride, u64 *d_plain, hipStream_t st)
@@ -181,6 +204,116 @@ int k_slots_act_host(crc_ctx *c, const u64 *plain_in, size_t planes, const Windo
             }
             h_ntt_inv(T->T, row.data(), n);
             for (int k = 0; k < n; k++) plain_out[m * (size_t)n + k] = row[k];
+        }
+    });
+    return CRC_OK;
+}
+
+// ---- several plain moduli (slots_device.h: slots_crt_*) ------------------------------------------------------------------------------------------------------
+// The constants of a residue base: P_j = t_0 ... t_{j-1} and its inverse mod t_j.  false unless the t_j are pairwise distinct (primes: pairwise coprime) and
+// their product stays below 2^63; the caller has checked the contexts themselves (crc_slots_crt_supported)
+bool k_slots_crt_base(crc_ctx *const *ctxs, int r, SlotsCrtBase *B)
+{
+    if (r < 1 || r > CRC_SLOTS_CRT_MAX) return false;
+    B->r = r;
+    unsigned __int128 T = 1;
+    for (int j = 0; j < r; j++) {
+        const u64 t = ctxs[j]->t;
+        for (int i = 0; i < j; i++) if (B->t[i] == t) return false;
+        B->t[j] = t; B->P[j] = (u64)T;
+        T *= t;
+        if (T >> 63) return false;
+        B->Pinv[j] = j ? h_invmod(B->P[j] % t, t) : 1;
+        B->Pinv_s[j] = (u64)(((unsigned __int128)B->Pinv[j] << 64) / t);
+    }
+    B->T = (u64)T;
+    return true;
+}
+static void slots_crt_args(const SlotsCrtBase &B, SlotCrtArgs &a)
+{
+    a.r = B.r; a.T = B.T; a.half = (B.T - 1) >> 1;
+    for (int j = 0; j < B.r; j++) { a.m[j].P = B.P[j]; a.m[j].Pinv = B.Pinv[j]; a.m[j].Pinv_s = B.Pinv_s[j]; }
+}
+static const auto slots_crt_tables = [](SlotCrtArgs &a, int j, const SlotTables &T) {
+    a.m[j].Wf = T.d_fwd; a.m[j].Wi = T.d_inv; a.m[j].one_s = T.one_s; a.m[j].t = T.T.m.q;
+    if (j == 0) a.idx = T.d_idx;
+};
+// pairs a lane owns: at most 4 up to n = 4096; above that 8 -- at n = 8192 on 512 threads, so that two workgroups of 8 waves share a CU where one of 16 waves
+// would need 64 VGPRs or fewer to let a second one in; at n = 16384 the workgroup stops at 1024 threads anyway
+int k_slots_crt_decompose(crc_ctx *const *ctxs, const SlotsCrtBase &B, const u64 *const *d_plain, size_t count, int slots, long long *d_values, size_t item_stride,
+                          size_t slot_stride, hipStream_t st)
+{
+    SlotCrtArgs a{};
+    slots_crt_args(B, a);
+    for (int j = 0; j < B.r; j++) a.m[j].plain_in = d_plain[j];
+    a.vals_out = d_values; a.count = count; a.slots = slots; a.item_stride = item_stride; a.slot_stride = slot_stride;
+    if (ctxs[0]->n <= 4096) return slots_launch(ctxs, B.r, slots_crt_decompose_kernel<true, 4>, slots_crt_decompose_kernel<false, 4>, a, slots_crt_tables, st);
+    return slots_launch(ctxs, B.r, slots_crt_decompose_kernel<true, 8>, slots_crt_decompose_kernel<false, 8>, a, slots_crt_tables, st, ctxs[0]->n / 16);
+}
+int k_slots_crt_act(crc_ctx *const *ctxs, const SlotsCrtBase &B, const u64 *const *d_in, size_t count, u64 divisor, int relu, u64 cap, u64 *const *d_out, hipStream_t st)
+{
+    SlotCrtArgs a{};
+    slots_crt_args(B, a);
+    for (int j = 0; j < B.r; j++) { a.m[j].plain_in = d_in[j]; a.m[j].plain_out = d_out[j]; }
+    a.count = count; a.D = divisor; a.recip = divisor == 1 ? ~(u64)0 : (u64)(((unsigned __int128)1 << 64) / divisor);
+    a.relu = relu; a.cap = cap;
+    if (ctxs[0]->n <= 4096) return slots_launch(ctxs, B.r, slots_crt_act_kernel<true, 4>, slots_crt_act_kernel<false, 4>, a, slots_crt_tables, st);
+    return slots_launch(ctxs, B.r, slots_crt_act_kernel<true, 8>, slots_crt_act_kernel<false, 8>, a, slots_crt_tables, st, ctxs[0]->n / 16);
+}
+
+// host twins: the reference transforms per modulus, the same Garner steps in 128-bit arithmetic
+static void slots_crt_lift_host(const SlotsCrtBase &B, const SlotTables *const *T, const u64 *const *plain, size_t m, int n, std::vector<u64> &row, std::vector<u64> &x)
+{
+    for (int j = 0; j < B.r; j++) {
+        const u64 t = B.t[j];
+        for (int i = 0; i < n; i++) row[i] = plain[j][m * (size_t)n + i] % t;
+        h_ntt_fwd(T[j]->T, row.data(), n);
+        for (int i = 0; i < n; i++) {
+            if (!j) { x[i] = row[i]; continue; }
+            const u64 xr = x[i] % t, d = row[i] >= xr ? row[i] - xr : row[i] + t - xr;
+            x[i] += B.P[j] * (u64)((unsigned __int128)d * B.Pinv[j] % t);
+        }
+    }
+}
+int k_slots_crt_decompose_host(crc_ctx *const *ctxs, const SlotsCrtBase &B, const u64 *const *plain, size_t count, int slots, long long *values, size_t item_stride,
+                               size_t slot_stride)
+{
+    const SlotTables *T[CRC_SLOTS_CRT_MAX];
+    for (int j = 0; j < B.r; j++) { const int rc = crc_slots_tables(ctxs[j], &T[j]); if (rc) return rc; }
+    const int n = ctxs[0]->n; const u64 half = (B.T - 1) >> 1;
+    crc_host::parallel_for(count, 4, [&](size_t b, size_t e) {
+        std::vector<u64> row((size_t)n), x((size_t)n);
+        for (size_t m = b; m < e; m++) {
+            slots_crt_lift_host(B, T, plain, m, n, row, x);
+            for (int i = 0; i < slots; i++) { const u64 v = x[T[0]->idx[i]]; values[m * item_stride + (size_t)i * slot_stride] = (long long)(v > half ? v - B.T : v); }
+        }
+    });
+    return CRC_OK;
+}
+int k_slots_crt_act_host(crc_ctx *const *ctxs, const SlotsCrtBase &B, const u64 *const *plain_in, size_t count, u64 divisor, int relu, u64 cap, u64 *const *plain_out)
+{
+    const SlotTables *T[CRC_SLOTS_CRT_MAX];
+    for (int j = 0; j < B.r; j++) { const int rc = crc_slots_tables(ctxs[j], &T[j]); if (rc) return rc; }
+    const int n = ctxs[0]->n; const u64 half = (B.T - 1) >> 1;
+    const __int128 D = (__int128)divisor, h = (__int128)(divisor >> 1);
+    crc_host::parallel_for(count, 4, [&](size_t b, size_t e) {
+        std::vector<u64> row((size_t)n), x((size_t)n);
+        std::vector<__int128> rho((size_t)n);
+        for (size_t m = b; m < e; m++) {
+            slots_crt_lift_host(B, T, plain_in, m, n, row, x);          // all r input rows are read before an output row is written
+            for (int i = 0; i < n; i++) {
+                const __int128 num = (x[i] > half ? (__int128)x[i] - (__int128)B.T : (__int128)x[i]) + h;
+                __int128 q = num / D; if (num % D < 0) q--;                    // floor division
+                if (relu && q < 0) q = 0;
+                if (cap && q > (__int128)cap) q = (__int128)cap;
+                rho[i] = q;
+            }
+            for (int j = 0; j < B.r; j++) {
+                const __int128 t = (__int128)B.t[j];
+                for (int i = 0; i < n; i++) { __int128 v = rho[i] % t; if (v < 0) v += t; row[i] = (u64)v; }
+                h_ntt_inv(T[j]->T, row.data(), n);
+                for (int i = 0; i < n; i++) plain_out[j][m * (size_t)n + i] = row[i];
+            }
         }
     });
     return CRC_OK;

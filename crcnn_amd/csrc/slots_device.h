@@ -1,6 +1,7 @@
 // slots_device.h -- device side of slot batching (kernels_slots.hip): argument block, block -> item order, the bodies of slots_compose_kernel and
-// slots_decompose_kernel, of slots_rescale_kernel and of slots_act_kernel.  A header so that tests/cpp/slots_kernel_check.cpp, slots_rescale_kernel_check.cpp and
-// slots_act_kernel_check.cpp can run the same text on the CPU, one thread per workgroup, under sanitizers.
+// slots_decompose_kernel, of slots_rescale_kernel, of slots_act_kernel and of the two kernels over several plain moduli (slots_crt_*).  A header so that
+// tests/cpp/slots_kernel_check.cpp, slots_rescale_kernel_check.cpp, slots_act_kernel_check.cpp and slots_crt_kernel_check.cpp can run the same text on the CPU,
+// one thread per workgroup, under sanitizers.
 #pragma once
 #include "ntt_device.h"
 
@@ -252,5 +253,141 @@ __device__ __forceinline__ void slots_act_body(const SlotActArgs &a, u64 *sm)
     for (int s = 2 * tid; s < n; s += 2 * nt) {
         const ulonglong2 r = sm_load_pair64(sm, s);                    // below 16 t (lazy) / 2 t (strict)
         st2(dst + s, mulmod_shoup(r.x, 1, one_s, t), mulmod_shoup(r.y, 1, one_s, t));
+    }
+}
+
+// ---- several plain moduli: the slots of r plaintexts mod t_0 .. t_{r-1}, lifted by the Chinese remainder theorem to integers mod T = t_0 ... t_{r-1} < 2^63 --------
+// One workgroup per item as above, ONE row image in LDS, the moduli visited one after the other.  A lane keeps the running value of the positions it owns -- the
+// pairs s = 2 tid + 2 k nt, the ones the pointwise loops of the kernels above give it -- in registers and folds modulus j in by Garner's mixed-radix step:
+//     x_0 = a_0,   x_j = x_{j-1} + P_{j-1} ((a_j - x_{j-1}) P_{j-1}^-1 mod t_j),   P_j = t_0 ... t_j.
+// Bounds: 0 <= x_{j-1} < P_{j-1} and the digit is below t_j, so x_j <= P_{j-1} - 1 + P_{j-1} (t_j - 1) = P_j - 1 < T < 2^63: one u64, no carry.  x_{j-1} mod t_j is the
+// Shoup reduction of slot_residue (any 64-bit word -> canonical); the digit is one Shoup product with the constant P_{j-1}^-1 mod t_j.
+// Any t_j >= 2 n + 1 >= 129, so with two moduli or more every t_j < 2^63 / 129 < 2^57: only the lazy butterflies occur for r >= 2, the strict ones at r = 1 alone.
+#ifndef CRC_SLOTS_CRT_MAX
+#define CRC_SLOTS_CRT_MAX 4                                 // (crcnn_hip.h)
+#endif
+struct SlotCrtMod {
+    const u64 *plain_in; u64 *plain_out;                    // row tensor of this modulus, [count][n] (act: the same pointer is allowed)
+    const ulonglong2 *Wf, *Wi;                              // t_j's forward / inverse tables
+    u64 t, one_s;
+    u64 P;                                                  // t_0 ... t_{j-1} (1 for j = 0)
+    u64 Pinv, Pinv_s;                                       // P^-1 mod t_j and its Shoup companion (unused for j = 0)
+};
+struct SlotCrtArgs {
+    SlotCrtMod m[CRC_SLOTS_CRT_MAX];
+    int r;
+    long long *vals_out; const u32 *idx;                    // decompose: as SlotArgs (idx depends on n only)
+    size_t count, item_stride, slot_stride;
+    int n, logn, slots;
+    u64 T, half;                                            // t_0 ... t_{r-1} and (T - 1) / 2
+    u64 D, recip;                                           // act: as SlotActArgs
+    int relu; u64 cap;                                      // cap = 0: none; otherwise 1 <= cap <= (T - 1) / 2
+};
+
+// canonical a mod t_j -> the running value with modulus j folded in
+__device__ __forceinline__ u64 slot_crt_fold(u64 x, u64 a, const SlotCrtMod &m)
+{
+    const u64 xr = mulmod_shoup(x, 1, m.one_s, m.t);
+    const u64 d = a >= xr ? a - xr : a + m.t - xr;
+    return x + m.P * mulmod_shoup(d, m.Pinv, m.Pinv_s, m.t);
+}
+// centred V -> act(V) = min(max(floor(V / D + 1/2), 0 if relu), cap if cap), as an integer.  |V| <= (T - 1) / 2 < 2^62 and D <= 2^62: the sums stay below 2^63
+__device__ __forceinline__ long long slot_crt_act_value(long long m, const SlotCrtArgs &a)
+{
+    const bool neg = m < 0;
+    const u64 mag = neg ? 0 - (u64)m : (u64)m;
+    u64 qv = slot_quotient(mag + ((a.D - (neg ? 1 : 0)) >> 1), a.D, a.recip);
+    if (neg) return a.relu ? 0 : -(long long)qv;
+    if (a.cap && qv > a.cap) qv = a.cap;
+    return (long long)qv;
+}
+
+// The r forward transforms and the Garner fold of one item into x[2 PAIRS], canonical mod T.  FUSE1 as in the bodies above: off for decompose (drained in slot
+// order), on for the activation (position order).  Barriers as in slots_act_body: the fill and the fold give a lane the same slots of the image and
+// ntt_row_passes returns synchronised, so a modulus needs ONE barrier of its own, between its fill and its passes.
+template <bool LAZY, int PAIRS, bool FUSE1>
+__device__ __forceinline__ void slots_crt_lift(const SlotCrtArgs &a, size_t item, u64 *sm, u64 (&x)[2 * PAIRS])
+{
+    const int n = a.n, tid = threadIdx.x, nt = blockDim.x;
+    const bool fuse1 = FUSE1 && ntt_fused_stage(a.logn);
+    for (int j = 0; j < a.r; j++) {
+        const SlotCrtMod &m = a.m[j];
+        const u64 t = m.t, t2 = t + t, one_s = m.one_s;
+        const u64 *src = m.plain_in + item * (size_t)n;
+        for (int s = 2 * tid; s < n; s += 2 * nt) {
+            const ulonglong2 p = ld2(src + s);
+            sm_store_pair64(sm, s, mulmod_shoup(p.x, 1, one_s, t), mulmod_shoup(p.y, 1, one_s, t));
+        }
+        __syncthreads();
+        ntt_row_passes<false, LAZY, 3, FUSE1>(sm, m.Wf, n, a.logn, t, t2);
+#pragma unroll
+        for (int k = 0; k < PAIRS; k++) {
+            const int s = 2 * tid + 2 * k * nt;
+            if (s < n) {
+                ulonglong2 v = sm_load_pair64(sm, s);
+                if (fuse1) fwd_pair_stage<LAZY>(v, m.Wf[(n >> 1) + (s >> 1)], t, t2);
+                const u64 ax = mulmod_shoup(v.x, 1, one_s, t), ay = mulmod_shoup(v.y, 1, one_s, t);     // below (1 + 4 log2 n) t (lazy) / 4 t (strict) -> canonical
+                x[2 * k] = j ? slot_crt_fold(x[2 * k], ax, m) : ax;
+                x[2 * k + 1] = j ? slot_crt_fold(x[2 * k + 1], ay, m) : ay;
+            }
+        }
+    }
+}
+
+// Each lane writes its centred values over its own slots of the image; one barrier; the drain in slot order through idx, with the caller's strides.
+template <bool LAZY, int PAIRS>
+__device__ __forceinline__ void slots_crt_decompose_body(const SlotCrtArgs &a, u64 *sm)
+{
+    size_t item;
+    if (!slot_item(a.count, item)) return;
+    const int n = a.n, tid = threadIdx.x, nt = blockDim.x;
+    u64 x[2 * PAIRS];
+    slots_crt_lift<LAZY, PAIRS, false>(a, item, sm, x);
+#pragma unroll
+    for (int k = 0; k < PAIRS; k++) {
+        const int s = 2 * tid + 2 * k * nt;
+        if (s < n) sm_store_pair64(sm, s, x[2 * k] > a.half ? x[2 * k] - a.T : x[2 * k], x[2 * k + 1] > a.half ? x[2 * k + 1] - a.T : x[2 * k + 1]);
+    }
+    __syncthreads();
+    long long *out = a.vals_out + item * a.item_stride;
+    for (int i = tid; i < a.slots; i += nt) out[(size_t)i * a.slot_stride] = (long long)sm[lpad((int)a.idx[i])];
+}
+
+// The lift in position order, the activation on the centred integer, then for every modulus: the residue, t_j's inverse passes, the canonical store to output
+// row j.  The workgroup has read all r input rows before its first store, so input row j may be output row j.  The store of modulus j reads, and the fill of
+// modulus j + 1 writes, the lane's own slots: one barrier per modulus, in front of the inverse passes.
+template <bool LAZY, int PAIRS>
+__device__ __forceinline__ void slots_crt_act_body(const SlotCrtArgs &a, u64 *sm)
+{
+    size_t item;
+    if (!slot_item(a.count, item)) return;
+    const int n = a.n, tid = threadIdx.x, nt = blockDim.x;
+    const bool fuse1 = ntt_fused_stage(a.logn);
+    u64 x[2 * PAIRS];
+    slots_crt_lift<LAZY, PAIRS, true>(a, item, sm, x);
+#pragma unroll
+    for (int k = 0; k < 2 * PAIRS; k++) {
+        if (2 * tid + 2 * (k >> 1) * nt < n) x[k] = (u64)slot_crt_act_value((long long)(x[k] > a.half ? x[k] - a.T : x[k]), a);
+    }
+    for (int j = 0; j < a.r; j++) {
+        const SlotCrtMod &m = a.m[j];
+        const u64 t = m.t, t2 = t + t, one_s = m.one_s;
+#pragma unroll
+        for (int k = 0; k < PAIRS; k++) {
+            const int s = 2 * tid + 2 * k * nt;
+            if (s < n) {
+                ulonglong2 v;
+                v.x = slot_residue((long long)x[2 * k], t, one_s); v.y = slot_residue((long long)x[2 * k + 1], t, one_s);
+                if (fuse1) inv_pair_stage<LAZY>(v, m.Wi[(n >> 1) + (s >> 1)], t, t2);
+                sm_store_pair64(sm, s, v.x, v.y);
+            }
+        }
+        __syncthreads();
+        ntt_row_passes<true, LAZY, 3, true>(sm, m.Wi, n, a.logn, t, t2);
+        u64 *dst = m.plain_out + item * (size_t)n;
+        for (int s = 2 * tid; s < n; s += 2 * nt) {
+            const ulonglong2 r = sm_load_pair64(sm, s);                    // below 16 t (lazy) / 2 t (strict)
+            st2(dst + s, mulmod_shoup(r.x, 1, one_s, t), mulmod_shoup(r.y, 1, one_s, t));
+        }
     }
 }

@@ -1533,6 +1533,162 @@ static BudgetView budgetView(const LevelTensor &t, const char *who)
 vector<int> noiseBudgets(const LevelTensor &t) { return allBudgets(budgetView(t, "noiseBudgets"), "noiseBudgets"); }
 int minNoiseBudget(const LevelTensor &t, size_t *where) { return minAndFirstBudget(budgetView(t, "minNoiseBudget"), "minNoiseBudget", where, nullptr); }
 
+// ---- several plain moduli: r sibling contexts over the parameters' n, q and device, the slots recombined by the CRT (crc_slots_crt_*) ----
+// Like a Level, a PlainBase belongs to the parameters it was made under.
+PlainBase::~PlainBase() { for (size_t j = 1; j < ctxs.size(); j++) if (ctxs[j]) crc_ctx_destroy(ctxs[j]); }
+shared_ptr<PlainBase> makePlainBase(const vector<uint64_t> &ts)
+{
+    const int k = K(), n = N();
+    if (ts.empty() || ts.size() > CRC_SLOTS_CRT_MAX) throw invalid_argument("makePlainBase: a base has 1 .. " + to_string(CRC_SLOTS_CRT_MAX) + " plain moduli");
+    if (ts[0] != g_plain_modulus) throw invalid_argument("makePlainBase: the first modulus must be the plain modulus of the parameters");
+    if (secret_key.size() != (size_t)k * n || public_key.size() != (size_t)2 * k * n) throw logic_error("makePlainBase: the keys do not match the parameters");
+    vector<uint64_t> q(k);
+    chk(crc_ctx_table(ctx(), "q", q.data(), k), "crc_ctx_table");
+    auto B = make_shared<PlainBase>();
+    B->ts = ts; B->generation = g_generation;
+    B->ctxs.assign(ts.size(), nullptr);
+    B->ctxs[0] = ctx();
+    for (size_t j = 1; j < ts.size(); j++) chk(crc_ctx_create(n, q.data(), k, ts[j], crc_ctx_device(ctx()), &B->ctxs[j]), "makePlainBase: crc_ctx_create");
+    if (!crc_slots_crt_supported(B->ctxs.data(), (int)ts.size()))
+        throw invalid_argument("makePlainBase: the moduli must be pairwise distinct primes that are 1 mod 2n, none of the engine's moduli, with a product below 2^63");
+    B->T = 1;
+    for (uint64_t t : ts) B->T *= t;
+    // the keys live mod q alone: one device copy of each serves every member
+    B->d_secret_key = make_shared<DeviceBuffer>(secret_key.size() * 8);
+    B->d_public_key = make_shared<DeviceBuffer>(public_key.size() * 8);
+    chk(crc_memcpy_h2d(ctx(), B->d_secret_key->ptr, secret_key.data(), secret_key.size() * 8, stream()), "crc_memcpy_h2d");
+    chk(crc_memcpy_h2d(ctx(), B->d_public_key->ptr, public_key.data(), public_key.size() * 8, stream()), "crc_memcpy_h2d");
+    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+    return B;
+}
+static const PlainBase &baseOf(const shared_ptr<PlainBase> &B, const char *who)
+{
+    if (!B || B->ctxs.empty()) throw invalid_argument(string(who) + ": no plain base");
+    if (!context || B->generation != g_generation || B->ctxs[0] != context) throw invalid_argument(string(who) + ": the plain base was made under other parameters");
+    return *B;
+}
+// the base of a tensor whose r parts have one shape and one ciphertext form
+static const PlainBase &baseOf(const PlainBaseTensor &t, const char *who)
+{
+    const PlainBase &B = baseOf(t.base, who);
+    if (t.parts.size() != B.ts.size() || t.count() == 0) throw invalid_argument(string(who) + ": the tensor does not have one part per modulus");
+    for (const ciphertext3D &p : t.parts) {
+        if (!p.buf || p.B != t.parts[0].B || p.zd != t.parts[0].zd || p.xd != t.parts[0].xd || p.yd != t.parts[0].yd || p.form != t.parts[0].form)
+            throw invalid_argument(string(who) + ": the parts differ in shape or form");
+    }
+    if (t.form() != CRC_COEFF && t.form() != CRC_NTT) throw invalid_argument(string(who) + ": ciphertext forms only (CRC_COEFF / CRC_NTT)");
+    return B;
+}
+// under setDeterministicSeed: the public expansion of the seed encryptImage would have used (NOT secure, as every seeded run)
+static void crtKey(uint8_t key[CRC_KEY_BYTES], uint64_t &stream_base)
+{
+    if (g_det) { chk(crc_seeded_public_seed(g_det_seed + 1000003 * (g_enc_counter + 1), key), "crc_seeded_public_seed"); stream_base = 0; }
+    else { memcpy(key, g_master_key, CRC_KEY_BYTES); stream_base = g_enc_counter; }
+}
+PlainBaseTensor encryptImageSlotsCrt(const vector<vector<int64_t>> &images, int zd, int xd, int yd, const shared_ptr<PlainBase> &base, int out_form)
+{
+    const PlainBase &B = baseOf(base, "encryptImageSlotsCrt");
+    if (!g_slot_on) throw logic_error("encryptImageSlotsCrt: setSlotEncoding() must be called first");
+    const size_t per = (size_t)zd * xd * yd, S = images.size();
+    if (zd < 1 || xd < 1 || yd < 1 || S < 1 || S > (size_t)N()) throw invalid_argument("encryptImageSlotsCrt: 1 to n images of [zd][xd][yd] pixels");
+    if (out_form != CRC_COEFF && out_form != CRC_NTT) throw invalid_argument("encryptImageSlotsCrt: ciphertext forms only (CRC_COEFF / CRC_NTT)");
+    vector<int64_t> h(S * per);
+    for (size_t j = 0; j < S; j++) {
+        if (images[j].size() != per) throw invalid_argument("encryptImageSlotsCrt: every image must have zd xd yd pixels");
+        memcpy(h.data() + j * per, images[j].data(), per * 8);
+    }
+    DeviceBuffer d_v(h.size() * 8), d_pl(per * (size_t)N() * 8), d_work(crc_encrypt_dev_work_bytes(ctx(), per));
+    chk(crc_memcpy_h2d(ctx(), d_v.ptr, h.data(), h.size() * 8, stream()), "crc_memcpy_h2d");
+    PlainBaseTensor out;
+    out.base = base;
+    for (size_t j = 0; j < B.ts.size(); j++) {
+        crc_ctx *c = B.ctxs[j];
+        chk(crc_slots_compose_dev(c, (const int64_t *)d_v.ptr, per, (int)S, 1, per, (uint64_t *)d_pl.ptr, stream()), "crc_slots_compose_dev");
+        ciphertext3D part(1, zd, xd, yd, out_form);
+        uint8_t key[CRC_KEY_BYTES]; uint64_t stream_base;
+        crtKey(key, stream_base);
+        chk(crc_encrypt_dev_key_forms(c, (const uint64_t *)B.d_public_key->ptr, (const uint64_t *)d_pl.ptr, per, key, stream_base, out_form, part.data(), d_work.ptr,
+                                      stream()), "crc_encrypt_dev_key_forms");
+        g_enc_counter += per;
+        out.parts.push_back(part);
+    }
+    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+    return out;
+}
+vector<vector<int64_t>> decryptSlotsCrt(const PlainBaseTensor &t, int S)
+{
+    const PlainBase &B = baseOf(t, "decryptSlotsCrt");
+    if (S < 1 || S > N()) throw invalid_argument("decryptSlotsCrt: 1 to n slots");
+    const size_t cnt = t.count(), r = B.ts.size();
+    DeviceBuffer d_pl(r * cnt * (size_t)N() * 8), d_v(cnt * (size_t)S * 8), d_work(crc_decrypt_dev_work_bytes(ctx(), cnt, 2, t.form()));
+    const uint64_t *rows[CRC_SLOTS_CRT_MAX];
+    for (size_t j = 0; j < r; j++) {
+        uint64_t *pl = (uint64_t *)d_pl.ptr + j * cnt * (size_t)N();
+        chk(crc_decrypt_dev(B.ctxs[j], (const uint64_t *)B.d_secret_key->ptr, t.parts[j].data(), cnt, 2, t.form(), pl, d_work.ptr, stream()), "crc_decrypt_dev");
+        rows[j] = pl;
+    }
+    chk(crc_slots_crt_decompose_dev(B.ctxs.data(), (int)r, rows, cnt, S, (int64_t *)d_v.ptr, 1, cnt, stream()), "crc_slots_crt_decompose_dev");
+    vector<int64_t> h(cnt * (size_t)S);
+    chk(crc_memcpy_d2h(ctx(), h.data(), d_v.ptr, h.size() * 8, stream()), "crc_memcpy_d2h");
+    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
+    vector<vector<int64_t>> out(S);
+    for (int j = 0; j < S; j++) out[j].assign(h.begin() + (size_t)j * cnt, h.begin() + (size_t)(j + 1) * cnt);
+    return out;
+}
+PlainBaseTensor rescaleSlotsCrt(const PlainBaseTensor &t, uint64_t divisor, int relu, uint64_t cap, int out_form, bool symmetric)
+{
+    const PlainBase &B = baseOf(t, "rescaleSlotsCrt");
+    if (out_form != CRC_COEFF && out_form != CRC_NTT) throw invalid_argument("rescaleSlotsCrt: ciphertext forms only (CRC_COEFF / CRC_NTT)");
+    if (divisor < 1 || divisor > ((uint64_t)1 << 62)) throw invalid_argument("rescaleSlotsCrt: the divisor must be in 1..2^62");
+    if (relu != 0 && relu != 1) throw invalid_argument("rescaleSlotsCrt: relu must be 0 or 1");
+    if (cap > (B.T - 1) / 2) throw invalid_argument("rescaleSlotsCrt: the cap must be at most (T - 1) / 2");
+    const int r = (int)B.ts.size();
+    const ciphertext3D &p0 = t.parts[0];
+    PlainBaseTensor out;
+    out.base = t.base;
+    for (int j = 0; j < r; j++) out.parts.push_back(ciphertext3D(p0.B, p0.zd, p0.xd, p0.yd, out_form));
+    auto work_bytes = [&](size_t c) { return crc_slots_crt_refresh_dev_work_bytes(B.ctxs.data(), r, c, t.form()); };
+    const size_t cnt = t.count(), one = work_bytes(1);
+    size_t pass = ((size_t)4 << 30) / (one ? one : 1);
+    if (pass < 1024) pass = 1024;
+    if (pass > cnt) pass = cnt;
+    ensure(g_scratch, work_bytes(pass));
+    const uint64_t *d_sk = (const uint64_t *)B.d_secret_key->ptr, *d_pk = (const uint64_t *)B.d_public_key->ptr;
+    for (size_t o = 0; o < cnt; o += pass) {
+        const size_t c = min(pass, cnt - o);
+        const uint64_t *in[CRC_SLOTS_CRT_MAX]; uint64_t *dst[CRC_SLOTS_CRT_MAX];
+        for (int j = 0; j < r; j++) {
+            in[j] = (const uint64_t *)((const char *)t.parts[j].data() + o * ctBytes());
+            dst[j] = (uint64_t *)((char *)out.parts[j].data() + o * ctBytes());
+        }
+        uint8_t key[CRC_KEY_BYTES]; uint64_t stream_base;
+        crtKey(key, stream_base);
+        if (symmetric)
+            chk(crc_slots_crt_refresh_sym_dev_key(B.ctxs.data(), r, d_sk, in, c, t.form(), divisor, relu, cap, key, stream_base, out_form, dst, g_scratch->ptr, stream()),
+                "crc_slots_crt_refresh_sym_dev_key");
+        else
+            chk(crc_slots_crt_refresh_dev_key(B.ctxs.data(), r, d_sk, d_pk, in, c, t.form(), divisor, relu, cap, key, stream_base, out_form, dst, g_scratch->ptr,
+                                              stream()), "crc_slots_crt_refresh_dev_key");
+        g_enc_counter += (size_t)r * c;                       // member j took the stream ids stream_base + j c .. + c
+    }
+    return out;
+}
+ciphertext3D component(const PlainBaseTensor &t, int j)
+{
+    const PlainBase &B = baseOf(t, "component");
+    if (j < 0 || j >= (int)B.ts.size()) throw invalid_argument("component: no such member");
+    return t.parts[j];
+}
+void setComponent(PlainBaseTensor &t, int j, const ciphertext3D &part)
+{
+    const PlainBase &B = baseOf(t, "setComponent");
+    if (j < 0 || j >= (int)B.ts.size()) throw invalid_argument("setComponent: no such member");
+    const ciphertext3D &p = t.parts[j];
+    if (!part.buf || part.B != p.B || part.zd != p.zd || part.xd != p.xd || part.yd != p.yd || part.form != p.form)
+        throw invalid_argument("setComponent: the part must have the tensor's shape and form");
+    t.parts[j] = part;
+}
+
 static int g_expected_batch = 0;                            // images per Network::forward the caller announced (0: unknown)
 void setExpectedBatch(int images_per_forward) { g_expected_batch = images_per_forward > 0 ? images_per_forward : 0; }
 static bool tooLargeForHbm(size_t weights)

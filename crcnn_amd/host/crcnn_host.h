@@ -158,6 +158,44 @@ std::vector<floatCube> decryptImages(const LevelTensor &t);
 std::vector<std::vector<int64_t>> decryptSlots(const LevelTensor &t, int S);
 std::vector<int> noiseBudgets(const LevelTensor &t);
 int minNoiseBudget(const LevelTensor &t, size_t *where = nullptr);
+// ---- several plain moduli: a residue base (include/crcnn_hip.h, "Several plain moduli") -----------------------------------------------------------------------
+// A PlainBase is r <= CRC_SLOTS_CRT_MAX contexts over the n, q and device of setParameters() whose slot primes ts[j] are pairwise distinct with T = prod ts[j] <
+// 2^63: member 0 is the global context (ts[0] must be its plain modulus), the others are owned sibling contexts.  The keys do not involve t, so the base holds
+// device copies of the global secret and public key that serve every member.  The same network runs under every member -- each in a process of its own, whose
+// parameters have t = ts[j]: the host classes' process-global context stands in the way of more -- and the slots recombine into integers mod T.  Like a Level a
+// base belongs to the parameters it was made under: after the next setParameters() / delParameters() every call that is handed it throws std::invalid_argument.
+struct PlainBase {
+    std::vector<crc_ctx *> ctxs;                            // [0]: the global context; [1 ..]: owned
+    std::vector<uint64_t> ts;
+    uint64_t T = 0;
+    uint64_t generation = 0;
+    std::shared_ptr<DeviceBuffer> d_secret_key, d_public_key;
+    PlainBase() {}
+    ~PlainBase();
+    PlainBase(const PlainBase &) = delete; PlainBase &operator=(const PlainBase &) = delete;
+};
+// std::invalid_argument unless ts[0] is the plain modulus of the parameters and the contexts are a base (crc_slots_crt_supported)
+std::shared_ptr<PlainBase> makePlainBase(const std::vector<uint64_t> &ts);
+// r device tensors of one shape and form, member j under ts[j]
+struct PlainBaseTensor {
+    std::shared_ptr<PlainBase> base;
+    std::vector<ciphertext3D> parts;
+    int form() const { return parts.empty() ? CRC_COEFF : parts[0].form; }
+    size_t count() const { return parts.empty() ? 0 : parts[0].count(); }
+};
+// encryptImageSlots under every member: the same int64 pixels composed mod every ts[j] (r calls of crc_slots_compose_dev) and encrypted under the one public key,
+// keystream discipline as encryptImageSlots (the counter advances by r times the ciphertexts of one member)
+PlainBaseTensor encryptImageSlotsCrt(const std::vector<std::vector<int64_t>> &images, int zd, int xd, int yd, const std::shared_ptr<PlainBase> &base,
+                                     int out_form = CRC_COEFF);
+// the first S slots of every ciphertext as centred integers mod T, [S][count]: crc_decrypt_dev on every member, then ONE crc_slots_crt_decompose_dev
+std::vector<std::vector<int64_t>> decryptSlotsCrt(const PlainBaseTensor &t, int S);
+// the refresh over the base (crc_slots_crt_refresh[_sym]_dev_key): per slot the lifted integer V -> floor(V / divisor + 1/2), relu: max(., 0), cap (0: none):
+// min(., cap), reduced mod every ts[j] and encrypted again.  Key and counter discipline of rescaleSlots (under setDeterministicSeed the key is the public
+// expansion of the seed and the counter); bounded passes on the shared scratch.  std::invalid_argument as rescaleSlots, and for a cap above (T - 1) / 2
+PlainBaseTensor rescaleSlotsCrt(const PlainBaseTensor &t, uint64_t divisor, int relu, uint64_t cap, int out_form, bool symmetric = false);
+// member j as a ciphertext3D (a view, not a copy) for a process whose parameters have t = ts[j], and a tensor of that shape back in its place
+ciphertext3D component(const PlainBaseTensor &t, int j);
+void setComponent(PlainBaseTensor &t, int j, const ciphertext3D &part);
 // decryptImage -> encryptImage for every image of a batch (the refresh Network::forward runs in front of layer_before_reenc, network.cpp:30-34), on the
 // device and on the launch stream: the tensor may be in coefficient or NTT form, comes back in `out_form` (CRC_COEFF / CRC_NTT) under fresh randomness, and
 // `values` (optional) receives the floats the client saw, [B][zd][xd][yd] -- asking for them makes the call wait for the stream

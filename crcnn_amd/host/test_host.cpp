@@ -21,6 +21,7 @@
 //   test_host slots_rescale_plan <description> <h5> <dir> <S> <input_bits> <weight_bits>     see do_slots_rescale_plan
 //   test_host slots_act_plan <description> <h5> <dir> <S> <input_bits> <weight_bits>         see do_slots_act_plan
 //   test_host build_plain <description>                                                      see do_build_plain
+//   test_host plain_base <n> <S> <divisor> <cap> <t_0> [<t_1> ...]                           see do_plain_base
 //   test_host plan <model> <h5> <dir> <batch> <fuse 0|1> <head_chunk> <matrix_cores 0|1> <layer_before_reenc>     see do_plan
 //   test_host searchlogic <min> <max> <first_good> <last_good> <min_q>
 //     the plain-modulus search on a synthetic predicate (t < first_good: MISPREDICTED, t > last_good: OUT_OF_BUDGET); no GPU work.
@@ -844,6 +845,60 @@ static int do_slots_act_plan(int argc, char **argv)
 
 #define EXPECT_THROW(stmt, type) do { bool ok_ = false; try { stmt; } catch (const type &) { ok_ = true; } catch (...) {} if (!ok_) { fprintf(stderr, "expected " #type " from: " #stmt "\n"); return 3; } } while (0)
 
+// plain_base <n> <S> <divisor> <cap> <t_0> [<t_1> ...]: S images of 1 x 2 x 2 pixels through the host classes over a residue base -- encryptImageSlotsCrt,
+// decryptSlotsCrt, rescaleSlotsCrt (relu, cap) under the public and under the secret key, component / setComponent, the base of one modulus against
+// encryptImageSlots -> decryptSlots, and the refusal of a stale base.  Pixel p of image s is ((4 s + p) 0x9E3779B97F4A7C15 mod 2^64 mod T) - (T - 1) / 2;
+// image 0 is (T - 1) / 2, -(T - 1) / 2, 0, divisor / 2.  Prints the integers, one line per image.
+static int do_plain_base(int argc, char **argv)
+{
+    if (argc < 7) return 1;
+    const int n = atoi(argv[2]), S = atoi(argv[3]);
+    const uint64_t D = strtoull(argv[4], 0, 0), cap = strtoull(argv[5], 0, 0);
+    vector<uint64_t> ts;
+    for (int i = 6; i < argc; i++) ts.push_back(strtoull(argv[i], 0, 0));
+    setDeterministicSeed(1);
+    setParameters(n, ts[0]);
+    setSlotEncoding(4, 5);
+    auto base = makePlainBase(ts);
+    const int64_t half = (int64_t)((base->T - 1) / 2);
+    vector<vector<int64_t>> images(S, vector<int64_t>(4));
+    for (int s = 0; s < S; s++) for (int p = 0; p < 4; p++) images[s][p] = (int64_t)((uint64_t)(4 * s + p) * 0x9E3779B97F4A7C15ULL % base->T) - half;
+    images[0] = {half, -half, 0, (int64_t)(D / 2)};
+    auto show = [&](const char *what, const vector<vector<int64_t>> &v) {
+        for (size_t s = 0; s < v.size(); s++) { printf("%s %zu", what, s); for (int64_t x : v[s]) printf(" %lld", (long long)x); printf("\n"); }
+    };
+    PlainBaseTensor enc = encryptImageSlotsCrt(images, 1, 2, 2, base, CRC_NTT);
+    if (enc.parts.size() != ts.size() || enc.form() != CRC_NTT || enc.count() != 4) return 4;
+    show("lifted", decryptSlotsCrt(enc, S));
+    PlainBaseTensor act = rescaleSlotsCrt(enc, D, 1, cap, CRC_COEFF, false);
+    show("act", decryptSlotsCrt(act, S));
+    show("sym", decryptSlotsCrt(rescaleSlotsCrt(enc, D, 1, cap, CRC_NTT, true), S));
+    show("rescale", decryptSlotsCrt(rescaleSlotsCrt(enc, D, 0, 0, CRC_COEFF, false), S));
+    // member 0 is a tensor of the global context: its slots are the residues mod t_0; handed out and back, the tensor is what it was
+    ciphertext3D part = component(act, 0);
+    show("part0", decryptSlots(part, S));
+    setComponent(act, 0, part);
+    show("back", decryptSlotsCrt(act, S));
+    int refused = 0;
+    try { setComponent(act, 0, component(enc, 0)); } catch (const invalid_argument &) { refused++; }                  // another form
+    try { component(act, (int)ts.size()); } catch (const invalid_argument &) { refused++; }
+    try { rescaleSlotsCrt(enc, 0, 0, 0, CRC_COEFF); } catch (const invalid_argument &) { refused++; }
+    try { rescaleSlotsCrt(enc, D, 0, (uint64_t)half + 1, CRC_COEFF); } catch (const invalid_argument &) { refused++; }
+    try { makePlainBase({ts[0], ts[0]}); } catch (const invalid_argument &) { refused++; }
+    if (ts.size() > 1) try { makePlainBase(vector<uint64_t>(ts.rbegin(), ts.rend())); } catch (const invalid_argument &) { refused++; }      // t_0 is not the parameters'
+    // one modulus: encryptImageSlots -> decryptSlots
+    auto one = makePlainBase({ts[0]});
+    const bool same = decryptSlotsCrt(encryptImageSlotsCrt(images, 1, 2, 2, one), S) == decryptSlots(encryptImageSlots(images, 1, 2, 2), S);
+    printf("one_modulus_equal %d\n", (int)same);
+    printf("budget %d\n", minNoiseBudget(component(act, 0)));
+    delParameters();
+    setParameters(n, ts[0]);
+    try { decryptSlotsCrt(enc, S); } catch (const invalid_argument &) { refused++; }                                 // a base of other parameters
+    delParameters();
+    printf("plain_base ok refused %d\n", refused);
+    return 0;
+}
+
 static int do_api(int argc, char **argv)
 {
     if (argc < 4) return 1;
@@ -1072,6 +1127,7 @@ int main(int argc, char **argv)
         if (!strcmp(argv[1], "slots_rescale_plan")) return do_slots_rescale_plan(argc, argv);
         if (!strcmp(argv[1], "slots_act_plan")) return do_slots_act_plan(argc, argv);
         if (!strcmp(argv[1], "build_plain")) return do_build_plain(argc, argv);
+        if (!strcmp(argv[1], "plain_base")) return do_plain_base(argc, argv);
     } catch (const exception &e) { fprintf(stderr, "exception: %s\n", e.what()); return 10; }
     return 1;
 }

@@ -630,6 +630,46 @@ int crc_slots_refresh_act_sym_dev_key(crc_ctx *ctx, const uint64_t *d_sk_ntt, co
                                       int yf, int in_form, uint64_t divisor, int relu, uint64_t cap, const uint8_t *h_key /*[32]*/, uint64_t stream_base,
                                       int out_form, uint64_t *d_ct_out, void *d_work, void *stream);
 
+/* Several plain moduli.  One slot prime t has to hold the largest integer a slot-batched network forms, and every square costs about log2 t + log2 n bits of
+ * noise budget.  A residue base runs the same network under r small pairwise coprime plain moduli and recombines the slots by the Chinese remainder theorem
+ * into integers mod T = t_0 ... t_{r-1}.  The base is 1 <= r <= CRC_SLOTS_CRT_MAX contexts `ctxs[0 .. r-1]` of the same n and the same device, every one with
+ * crc_slots_supported, their t_j pairwise distinct and T < 2^63 (every centred integer mod T is an int64): crc_slots_crt_supported says 1 for exactly these.
+ * The keys do not involve t: one key set serves r contexts that share n and q.  Composing a batch is r calls of crc_slots_compose[_dev] on the same int64
+ * values.  What cannot be composed from the calls above -- a rescale or an activation does not commute with the reduction mod t_j -- is here:
+ *   crc_slots_crt_primes     the r largest primes below 2^bits that are 1 (mod 2n), descending; CRC_ERR_NOT_FOUND if fewer exist or their product is >= 2^63
+ *   crc_slots_crt_decompose  plain[j] = plaintext rows [count][n] of ctxs[j]; values (item c, slot i) at values[c item_stride + i slot_stride], i < slots: the
+ *                            centred integer mod T whose residue mod t_j is slot i of plain[j][c] for every j
+ *   crc_slots_crt_act        per slot, with V that centred integer: rho = floor(V / D + 1/2) (floor division, ties towards +infinity), 1 <= D <= 2^62; relu:
+ *                            rho = max(rho, 0); cap: rho = min(rho, cap), 0 <= cap <= (T - 1) / 2, 0 meaning none; out[j] = the canonical coefficients of
+ *                            compose(rho mod t_j) under ctxs[j].  out[j] may be in[j]; an output row tensor must not overlap anything else
+ *   crc_slots_crt_refresh_*  by definition, bit for bit: crc_decrypt_dev (size 2) on every ctxs[j], crc_slots_crt_act_dev on the r plaintext tensors,
+ *                            crc_encrypt_dev_key_forms / crc_encrypt_sym_dev_key_forms on every ctxs[j] with stream base stream_base + j count, on one stream.
+ *                            d_ct_out[j] may be d_ct_in[j]; d_work of crc_slots_crt_refresh_dev_work_bytes bytes serves either call
+ * The pointer arrays are HOST arrays of r host (crc_slots_crt_decompose / _act) or device (_dev, refresh) pointers, read before the call returns; every device
+ * row pointer is 16-byte aligned.  The host calls work on any context.  The _dev calls are one kernel each, one workgroup per item, no work buffer, asynchronous on
+ * `stream`.  Refusals, in this order, nothing written: CRC_ERR_INVALID_ARGUMENT for r outside [1, CRC_SLOTS_CRT_MAX] or a null entry of ctxs;
+ * CRC_ERR_PARAMETERS where crc_slots_crt_supported is 0; CRC_ERR_INVALID_ARGUMENT for a bad divisor, relu outside {0, 1}, cap > (T - 1) / 2, slots outside [1, n],
+ * a zero stride, a null or misaligned pointer, an output row tensor that overlaps any other than its own input; CRC_ERR_UNSUPPORTED for n > 16384 (device).
+ * count = 0 is CRC_OK.  At r = 1 the calls are crc_slots_decompose[_dev], crc_slots_act[_dev] on a 1 x 1 window and crc_slots_refresh_act[_sym]_dev_key, to the bit. */
+#define CRC_SLOTS_CRT_MAX 4
+int crc_slots_crt_supported(crc_ctx *const *ctxs, int r);
+int crc_slots_crt_primes(int n, int r, int bits, uint64_t *t /*[r]*/);
+int crc_slots_crt_decompose(crc_ctx *const *ctxs, int r, const uint64_t *const *h_plain /*[r] -> [count][n]*/, size_t count, int slots, int64_t *h_values,
+                            size_t item_stride, size_t slot_stride);
+int crc_slots_crt_decompose_dev(crc_ctx *const *ctxs, int r, const uint64_t *const *d_plain, size_t count, int slots, int64_t *d_values, size_t item_stride,
+                                size_t slot_stride, void *stream);
+int crc_slots_crt_act(crc_ctx *const *ctxs, int r, const uint64_t *const *h_in /*[r] -> [count][n]*/, size_t count, uint64_t divisor, int relu, uint64_t cap,
+                      uint64_t *const *h_out);
+int crc_slots_crt_act_dev(crc_ctx *const *ctxs, int r, const uint64_t *const *d_in, size_t count, uint64_t divisor, int relu, uint64_t cap, uint64_t *const *d_out,
+                          void *stream);
+size_t crc_slots_crt_refresh_dev_work_bytes(crc_ctx *const *ctxs, int r, size_t count, int in_form);
+int crc_slots_crt_refresh_dev_key(crc_ctx *const *ctxs, int r, const uint64_t *d_sk_ntt, const uint64_t *d_pk, const uint64_t *const *d_ct_in, size_t count,
+                                  int in_form, uint64_t divisor, int relu, uint64_t cap, const uint8_t *h_key /*[32]*/, uint64_t stream_base, int out_form,
+                                  uint64_t *const *d_ct_out, void *d_work, void *stream);
+int crc_slots_crt_refresh_sym_dev_key(crc_ctx *const *ctxs, int r, const uint64_t *d_sk_ntt, const uint64_t *const *d_ct_in, size_t count, int in_form,
+                                      uint64_t divisor, int relu, uint64_t cap, const uint8_t *h_key /*[32]*/, uint64_t stream_base, int out_form,
+                                      uint64_t *const *d_ct_out, void *d_work, void *stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Galois automorphisms: Evaluator::apply_galois / rotate_rows / rotate_columns (evaluator.cpp:1587-1834) and KeyGenerator::generate_galois_keys
  * (keygenerator.cpp:325-455) -- the operations that move data between the slots of a batched ciphertext.
