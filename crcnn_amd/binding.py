@@ -313,6 +313,14 @@ def load():
     L.crc_mod_switch_work_bytes.restype = SZ; L.crc_mod_switch_work_bytes.argtypes = [VP, VP, SZ, CI, CI, CI]
     L.crc_mod_switch_forms.argtypes = [VP, VP, VP, CI, SZ, CI, VP, CI, VP, VP]
     L.crc_mod_switch.argtypes = [VP, VP, PU, CI, SZ, CI, PU, CI]
+    L.crc_flood_supported.argtypes = [VP, CI]
+    L.crc_flood_bits.argtypes = [VP, CI, CI]
+    L.crc_flood_budget_bound.argtypes = [VP, CI, CI]
+    L.crc_flood_dev_work_bytes.restype = SZ; L.crc_flood_dev_work_bytes.argtypes = [VP, SZ, CI]
+    L.crc_flood_dev_key.argtypes = [VP, VP, VP, SZ, CI, CI, PB, u64, VP, VP]
+    L.crc_flood_dev.argtypes = [VP, VP, VP, SZ, CI, CI, u64, VP, VP]
+    L.crc_flood_key.argtypes = [VP, PU, PU, SZ, CI, CI, PB, u64]
+    L.crc_flood.argtypes = [VP, PU, PU, SZ, CI, CI, u64]
     L.crc_ctx_create_level.argtypes = [VP, CI, CI, ctypes.POINTER(VP)]
     L.crc_ctx_key_moduli.argtypes = [VP]
     L.crc_keys_restrict_supported.argtypes = [VP, VP]
@@ -738,6 +746,39 @@ class Engine:
         cts = np.ascontiguousarray(cts, dtype=np.uint64).reshape(-1, size, self.k, self.n)
         out = np.zeros((cts.shape[0], size, to.k, self.n), dtype=np.uint64)
         _chk(self.L.crc_mod_switch(self.c, to.c, _pu(cts), in_form, cts.shape[0], size, _pu(out), out_form), "crc_mod_switch")
+        return out
+
+    # ---- noise flooding: sanitise a response before it leaves (crc_flood*)
+    def flood_supported(self, flood_bits):
+        return bool(self.L.crc_flood_supported(self.c, flood_bits))
+
+    def flood_bits(self, budget_bits_in, lambda_bits=40):
+        """the smallest admitted B that covers, by lambda_bits, the noise of a ciphertext with budget_bits_in bits of budget -- the A-PRIORI budget of the
+        network, never a measured one"""
+        return _chk(self.L.crc_flood_bits(self.c, budget_bits_in, lambda_bits), "crc_flood_bits")
+
+    def flood_budget_bound(self, budget_bits_in, flood_bits):
+        return _chk(self.L.crc_flood_budget_bound(self.c, budget_bits_in, flood_bits), "crc_flood_budget_bound")
+
+    def flood_dev_work_bytes(self, count, form=COEFF):
+        return self.L.crc_flood_dev_work_bytes(self.c, count, form)
+
+    def flood_dev(self, d_pk, d_ct, count, flood_bits, d_work, form=COEFF, seed=None, key=None, stream_base=0):
+        """d_ct [count][2][k][n] in `form`, flooded in place on this engine's stream.  `key` (32 bytes) with `stream_base`, or a public `seed` (tests)"""
+        if key is not None:
+            _chk(self.L.crc_flood_dev_key(self.c, self.p(d_pk), self.p(d_ct), count, form, flood_bits, self._key(key), stream_base, self.p(d_work), self.stream),
+                 "crc_flood_dev_key")
+        else:
+            _chk(self.L.crc_flood_dev(self.c, self.p(d_pk), self.p(d_ct), count, form, flood_bits, seed, self.p(d_work), self.stream), "crc_flood_dev")
+
+    def flood(self, pk, cts, flood_bits, form=COEFF, seed=None, key=None, stream_base=0):
+        """host twin: a flooded copy of ciphertexts [count][2][k][n]"""
+        out = np.ascontiguousarray(cts, dtype=np.uint64).reshape(-1, 2, self.k, self.n).copy()
+        pk = np.ascontiguousarray(pk, dtype=np.uint64)
+        if key is not None:
+            _chk(self.L.crc_flood_key(self.c, _pu(pk), _pu(out), out.shape[0], form, flood_bits, self._key(key), stream_base), "crc_flood_key")
+        else:
+            _chk(self.L.crc_flood(self.c, _pu(pk), _pu(out), out.shape[0], form, flood_bits, seed), "crc_flood")
         return out
 
     # ---- host side: encode / client

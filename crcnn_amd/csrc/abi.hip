@@ -2196,3 +2196,50 @@ extern "C" int crc_mod_switch(const crc_ctx *from, const crc_ctx *to, const uint
     if (ranges_overlap(h_in, 8 * count * crc_ct_words(from, size), h_out, 8 * count * crc_ct_words(to, size))) return CRC_ERR_INVALID_ARGUMENT;
     return k_mod_switch_host(from, to, h_in, in_form, count * size, h_out, out_form);
 }
+
+// ---- noise flooding: a fresh encryption of zero with a wide uniform error joins every ciphertext of a response (kernels_flood.hip) ----
+extern "C" int crc_flood_supported(const crc_ctx *c, int flood_bits) { return k_flood_supported(c, flood_bits) ? 1 : 0; }
+extern "C" int crc_flood_bits(const crc_ctx *c, int budget_bits_in, int lambda_bits) { return k_flood_bits(c, budget_bits_in, lambda_bits); }
+extern "C" int crc_flood_budget_bound(const crc_ctx *c, int budget_bits_in, int flood_bits) { return k_flood_budget_bound(c, budget_bits_in, flood_bits); }
+extern "C" size_t crc_flood_dev_work_bytes(const crc_ctx *c, size_t count, int form) { return c && form_ok(form) ? k_flood_work_bytes(c, count) : 0; }
+static int flood_dev(crc_ctx *c, const uint64_t *d_pk, uint64_t *d_ct, size_t count, int form, int flood_bits, const ChaChaKey &key, uint64_t stream_base,
+                     void *d_work, void *stream)
+{
+    CHECK_CTX(c);
+    if (count == 0) return CRC_OK;
+    if (!d_pk || !d_ct || !d_work || !k_flood_supported(c, flood_bits)) return CRC_ERR_INVALID_ARGUMENT;
+    if (((uintptr_t)d_pk & 15) || ((uintptr_t)d_ct & 15)) return CRC_ERR_INVALID_ARGUMENT;
+    if (!form_ok(form)) return CRC_ERR_UNSUPPORTED;
+    const size_t ct_b = 8 * count * crc_ct_words(c, 2), pk_b = 8 * crc_ct_words(c, 2), wb = k_flood_work_bytes(c, count);
+    if (ranges_overlap(d_pk, pk_b, d_ct, ct_b) || ranges_overlap(d_work, wb, d_ct, ct_b) || ranges_overlap(d_work, wb, d_pk, pk_b)) return CRC_ERR_INVALID_ARGUMENT;
+    return k_flood(c, d_pk, d_ct, count, form == CRC_NTT, flood_bits, key, stream_base, d_work, S(stream));
+}
+extern "C" int crc_flood_dev_key(crc_ctx *c, const uint64_t *d_pk, uint64_t *d_ct, size_t count, int form, int flood_bits, const uint8_t *h_key,
+                                 uint64_t stream_base, void *d_work, void *stream)
+{
+    if (!h_key) return CRC_ERR_INVALID_ARGUMENT;
+    return flood_dev(c, d_pk, d_ct, count, form, flood_bits, chacha_load_key(h_key), stream_base, d_work, stream);
+}
+extern "C" int crc_flood_dev(crc_ctx *c, const uint64_t *d_pk, uint64_t *d_ct, size_t count, int form, int flood_bits, uint64_t seed, void *d_work, void *stream)
+{
+    return flood_dev(c, d_pk, d_ct, count, form, flood_bits, chacha_seed_key(seed), 0, d_work, stream);
+}
+static int flood_host(const crc_ctx *c, const uint64_t *h_pk, uint64_t *h_ct, size_t count, int form, int flood_bits, const ChaChaKey &key, uint64_t stream_base)
+{
+    if (!c) return CRC_ERR_INVALID_ARGUMENT;
+    if (count == 0) return CRC_OK;
+    if (!h_pk || !h_ct || !k_flood_supported(c, flood_bits)) return CRC_ERR_INVALID_ARGUMENT;
+    if (!form_ok(form)) return CRC_ERR_UNSUPPORTED;
+    if (ranges_overlap(h_pk, 8 * crc_ct_words(c, 2), h_ct, 8 * count * crc_ct_words(c, 2))) return CRC_ERR_INVALID_ARGUMENT;
+    return k_flood_host(c, h_pk, h_ct, count, form == CRC_NTT, flood_bits, key, stream_base);
+}
+extern "C" int crc_flood_key(const crc_ctx *c, const uint64_t *h_pk, uint64_t *h_ct, size_t count, int form, int flood_bits, const uint8_t *h_key,
+                             uint64_t stream_base)
+{
+    if (!h_key) return CRC_ERR_INVALID_ARGUMENT;
+    return flood_host(c, h_pk, h_ct, count, form, flood_bits, chacha_load_key(h_key), stream_base);
+}
+extern "C" int crc_flood(const crc_ctx *c, const uint64_t *h_pk, uint64_t *h_ct, size_t count, int form, int flood_bits, uint64_t seed)
+{
+    return flood_host(c, h_pk, h_ct, count, form, flood_bits, chacha_seed_key(seed), 0);
+}

@@ -72,7 +72,8 @@ inline ChaChaKey chacha_load_key(const uint8_t *key)
 
 // stream domains (nonce word 2 carries the domain in its top byte)
 enum { CHACHA_DOM_KEYGEN = 1, CHACHA_DOM_EVK = 2, CHACHA_DOM_ENC_HOST = 3, CHACHA_DOM_ENC_DEV = 4, CHACHA_DOM_ENC_SYM = 5, CHACHA_DOM_SEEDED_A = 6,
-       CHACHA_DOM_SEEDED_E = 7, CHACHA_DOM_GALOIS = 8, CHACHA_DOM_KSK_A = 9, CHACHA_DOM_KSK_E = 10, CHACHA_DOM_KSK_SEED = 11 };
+       CHACHA_DOM_SEEDED_E = 7, CHACHA_DOM_GALOIS = 8, CHACHA_DOM_KSK_A = 9, CHACHA_DOM_KSK_E = 10, CHACHA_DOM_KSK_SEED = 11,
+       CHACHA_DOM_FLOOD = 12 };
 
 // Streams of the secret-key encryptor (crc_encrypt_sym* on the host, enc_sym_sample_kernel on the device: the same bits).  One stream per (ciphertext,
 // coefficient pair), nonce = (stream id low, stream id high, CHACHA_DOM_ENC_SYM << 24 | even coefficient index s); its 32-bit words w[0], w[1], ... run
@@ -115,3 +116,13 @@ enum { CHACHA_DOM_KEYGEN = 1, CHACHA_DOM_EVK = 2, CHACHA_DOM_ENC_HOST = 3, CHACH
 // from the private (master) key itself -- bytes 0..31 of block 0 of the stream nonce = (0, 0, CHACHA_DOM_KSK_SEED << 24), a PRF output that can be published --
 // so that an element generated twice is the same key twice.
 #define CHACHA_KSK_NONCE1(p, dbc, k) ((uint32_t)(p) | ((uint32_t)(dbc) << 16) | ((uint32_t)(k) << 24))
+
+// Streams of the noise flood (crc_flood* on the host, flood_sample_kernel on the device: the same bits).  One stream per (ciphertext, coefficient pair), nonce =
+// (stream id low, stream id high, CHACHA_DOM_FLOOD << 24 | even coefficient index s), ONE block (counter 0).  Coefficient s + c (c = 0, 1) owns words
+// w[8 c .. 8 c + 7] of it:
+//   w[8c + 0 .. 1]        the ternary sample u: the 64-bit word as 2-bit fields from the low end, the first field that is not 3 (0, 1, 2 stand for 0, 1, -1; all
+//                         32 fields equal to 3 gives 0) -- the public-key encryptor's rule
+//   w[8c + 2 .. 3]        the magnitude word of e2 (low, high half): |e2| = the number of the 19 thresholds (crc_encrypt_dev_noise_thresholds) that it reaches
+//   w[8c + 4 .. 7]        the 128-bit integer X = w[+4] + 2^32 w[+5] + 2^64 w[+6] + 2^96 w[+7]:  x = X mod 2^(B + 1) (its low B + 1 bits, B = flood_bits <= 126) and
+//                         e1 = x - 2^B, uniform on [-2^B, 2^B);  bit 127 of X (the top bit of w[8c + 7]), which no x reaches, is the sign of e2 (set: negative)
+// A reused (key, stream id) gives the same u, e1 and e2 twice: the difference of the two floods is then exactly the difference of the two inputs.

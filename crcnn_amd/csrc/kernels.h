@@ -185,6 +185,14 @@ bool   k_mod_switch_supported(const crc_ctx *from, const crc_ctx *to);
 size_t k_mod_switch_work_bytes(const crc_ctx *from, const crc_ctx *to, size_t polys, int in_form, int out_form);
 int k_mod_switch(crc_ctx *from, const crc_ctx *to, const u64 *d_in, int in_form, size_t polys, u64 *d_out, int out_form, void *d_work, hipStream_t st);
 int k_mod_switch_host(const crc_ctx *from, const crc_ctx *to, const u64 *in, int in_form, size_t polys, u64 *out, int out_form);
+// kernels_flood.hip: noise flooding of size-2 ciphertext tensors [cnt][2][k][n], in place, CRC_NTT (ntt_form) or CRC_COEFF; B = flood_bits (k_flood_supported);
+// the pure arithmetic of crc_flood_bits / crc_flood_budget_bound (a negative status for what they refuse); *_host: the host twin
+bool   k_flood_supported(const crc_ctx *c, int B);
+int    k_flood_bits(const crc_ctx *c, int budget_in, int lambda);
+int    k_flood_budget_bound(const crc_ctx *c, int budget_in, int B);
+size_t k_flood_work_bytes(const crc_ctx *c, size_t cnt);
+int k_flood(crc_ctx *c, const u64 *d_pk, u64 *d_ct, size_t cnt, bool ntt_form, int B, const ChaChaKey &key, u64 stream_base, void *d_work, hipStream_t st);
+int k_flood_host(const crc_ctx *c, const u64 *pk, u64 *ct, size_t cnt, bool ntt_form, int B, const ChaChaKey &key, u64 stream_base);
 
 // kernels_mfma.hip: conv / dense multiply-accumulate as an int8 limb GEMM on the matrix cores (operand form CRC_NTTL)
 bool   k_limb_supported(const crc_ctx *c, int T);

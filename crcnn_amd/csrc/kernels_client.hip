@@ -9,33 +9,13 @@
 // decrypting them (tests/test_gpu_ops.py) and by their noise budget against the CPU encryptor's.
 #include "kernels.h"
 #include "chacha.h"
+#include "enc_sampler.h"
 #include <cmath>
 
 // One lane = one (ciphertext, coefficient PAIR): its own ChaCha20 stream, nonce = (ciphertext stream id, domain | even coefficient index), ONE block (round 5;
 // one block per coefficient and two Box-Muller draws before -- sampling was 40 % of an encryption).  Per coefficient six words: 64 bits for the ternary sample
 // (2-bit fields, rejecting 3: all 32 fields equal to 3 has probability 2^-64 and falls back to 0) and 64 bits for the magnitude of each noise term; the noise
-// signs are bits of word 12.
-//
-// The noise law, exactly: SEAL draws g ~ N(0, 3.19^2), redraws while |g| > 6 sigma = 19.14 (util/clipnormal.h) and keeps static_cast<int64_t>(g)
-// (encryptor.cpp:237-240) -- an integer in [-19, 19] with  P(0) = P(|g| < 1) / Z,  P(+-a) = P(a <= g < a + 1) / Z (a < 19),  P(+-19) = P(19 <= g <= 19.14) / Z,
-// Z = P(|g| <= 19.14).  Sampling that integer directly needs no logarithm, cosine or rejection loop: the magnitude is the number of thresholds
-// T_a = floor(2^64 P(|e| <= a)) (a = 0..18; enc_cdt, computed once on the host in long double) that a uniform 64-bit word reaches -- the law above to 2^-63.
-struct EncCdt { u64 t[19]; };
-__device__ __forceinline__ int cdt_noise(u32 lo, u32 hi, u32 sign, const EncCdt &T)
-{
-    const u64 x = ((u64)hi << 32) | lo;
-    int a = 0;
-#pragma unroll
-    for (int j = 0; j < 19; j++) a += x >= T.t[j] ? 1 : 0;
-    return sign ? -a : a;
-}
-__device__ __forceinline__ u32 ternary_field(u32 lo, u32 hi)
-{
-    const u64 w = (u64)lo | ((u64)hi << 32);
-    u32 v = 0;
-    for (int j = 0; j < 32; j++) { const u32 f = (u32)(w >> (2 * j)) & 3u; if (f != 3u) { v = f; break; } }
-    return v;
-}
+// signs are bits of word 12.  The noise law, cdt_noise and ternary_field: enc_sampler.h.
 
 // U: [count][k][n] ternary polynomial in RNS form (coefficient domain).  ROWS = false: E [count][2][n] signed noise bytes (the coefficient-form pipeline adds
 // them after its inverse transforms); ROWS = true: the rows e1 + Delta m (+ q mod t on the upper half, evaluator.cpp:1168-1191) and e2 of every ciphertext, as
@@ -219,14 +199,6 @@ int k_encrypt(crc_ctx *c, const u64 *pk, const u64 *plain, size_t cnt, const Cha
 //     c1 = A,   c0 = NTT(e + Delta m) - A . s
 // costs one forward transform per modulus (the public-key encryptor: three).  That NTT form is the definition; the coefficient form is its inverse transform.
 // Stream layout: chacha.h (CHACHA_DOM_ENC_SYM); crc_encrypt_sym on the host computes the same bits.
-
-// z = hi 2^64 + lo -> z mod q for ANY 128-bit z.  The generic Barrett path's quotient estimate is off by at most one only for z < 2^64 q: the high word is
-// reduced first there (the folding path takes any z)
-__device__ __forceinline__ u64 mod128_any(u64 lo, u64 hi, const ModParams &m)
-{
-    if (m.fold) return fold128(lo, hi, m);
-    return barrett128(lo, barrett128(hi, 0, m), m);
-}
 
 // One lane = one (ciphertext, coefficient pair), as enc_sample_kernel: ct [count][2][k][n] receives the residues of e + Delta m (+ q mod t on the upper half) in
 // the c0 rows -- coefficient form, transformed next -- and the uniform residues A in the c1 rows -- NTT form, final.  COMPACT as enc_sample_kernel

@@ -1460,6 +1460,50 @@ LevelTensor modSwitch(const ciphertext3D &t, const shared_ptr<Level> &to, int ou
     chk(crc_mod_switch_forms(ctx(), L.ctx, t.data(), t.form, t.count(), 2, out.data(), out_form, g_scratch->ptr, stream()), "crc_mod_switch_forms");
     return out;
 }
+// ---- noise flooding ---------------------------------------------------------------------------------------------------------------------------------------------
+int floodBits(int budget_in, int lambda)
+{
+    const int B = crc_flood_bits(ctx(), budget_in, lambda);
+    if (B < 0) throw invalid_argument("floodBits: no admissible flood width for this budget and lambda");
+    return B;
+}
+// count ciphertexts of context c under the device public key d_pk, in place; the keystream ids g_enc_counter .. + count - 1 are spent
+static void floodOn(crc_ctx *c, const uint64_t *d_pk, uint64_t *d_ct, size_t count, int form, int flood_bits, const char *who)
+{
+    if (form != CRC_COEFF && form != CRC_NTT) throw invalid_argument(string(who) + ": ciphertext forms only (CRC_COEFF / CRC_NTT)");
+    if (!crc_flood_supported(c, flood_bits)) throw invalid_argument(string(who) + ": flood_bits is not admissible for the encryption parameters");
+    ensure(g_scratch, crc_flood_dev_work_bytes(c, count, form));
+    if (g_det)
+        chk(crc_flood_dev(c, d_pk, d_ct, count, form, flood_bits, g_det_seed + 1000003 * (g_enc_counter + 1), g_scratch->ptr, stream()), "crc_flood_dev");
+    else                                                    // one keystream per ciphertext, never reused under this key
+        chk(crc_flood_dev_key(c, d_pk, d_ct, count, form, flood_bits, g_master_key, g_enc_counter, g_scratch->ptr, stream()), "crc_flood_dev_key");
+    g_enc_counter += count;
+}
+void floodImages(ciphertext3D &t, int flood_bits)
+{
+    if (!t.buf || t.count() == 0) throw invalid_argument("floodImages: empty tensor");
+    floodOn(ctx(), deviceKey(g_d_pk, g_d_pk_fp, public_key, "public key"), t.data(), t.count(), t.form, flood_bits, "floodImages");
+}
+void floodImages(LevelTensor &t, int flood_bits)
+{
+    const Level &L = levelOf(t, "floodImages");
+    if (!t.level->d_public_key) {
+        t.level->d_public_key = make_shared<DeviceBuffer>(L.public_key.size() * 8);
+        chk(crc_memcpy_h2d(L.ctx, t.level->d_public_key->ptr, L.public_key.data(), L.public_key.size() * 8, stream()), "crc_memcpy_h2d");
+    }
+    floodOn(L.ctx, (const uint64_t *)t.level->d_public_key->ptr, t.data(), t.count(), t.form, flood_bits, "floodImages");
+}
+LevelTensor sanitizeResponse(const ciphertext3D &t, int flood_bits, const shared_ptr<Level> &to, int out_form)
+{
+    levelOf(to, "sanitizeResponse");
+    if (!t.buf || t.count() == 0) throw invalid_argument("sanitizeResponse: empty tensor");
+    ciphertext3D own(t.B, t.zd, t.xd, t.yd, t.form);
+    chk(crc_memcpy_d2d(ctx(), own.data(), t.data(), t.count() * ctBytes(), stream()), "crc_memcpy_d2d");
+    floodImages(own, flood_bits);
+    LevelTensor out = modSwitch(own, to, out_form);
+    chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");       // (the flooded copy goes out of scope here)
+    return out;
+}
 static LevelTensor levelResult(const LevelTensor &t, const Level &L, int out_form)
 {
     LevelTensor out; out.B = t.B; out.zd = t.zd; out.xd = t.xd; out.yd = t.yd; out.form = out_form; out.level = t.level;
@@ -2530,6 +2574,9 @@ ciphertext3D Network::forward(ciphertext3D input)
 {   // network.cpp:22-47
     const int L = (int)layers.size();
     if (budget_scope != 0 && budget_scope != 1) throw invalid_argument("Network::budget_scope must be 0 or 1");
+    // a width the parameters refuse is refused before the first launch
+    if (flood_bits && !crc_flood_supported(ctx(), flood_bits)) throw invalid_argument("Network::flood_bits is not admissible for the encryption parameters");
+    const shared_ptr<DeviceBuffer> callers = input.buf;
     // the planning flag is this forward's only: layers called directly afterwards plan with the default again
     struct Restore { bool &ref; bool old; ~Restore() { ref = old; } } restore_matrix_cores{g_matrix_cores, g_matrix_cores};
     g_matrix_cores = matrix_cores;
@@ -2546,6 +2593,14 @@ ciphertext3D Network::forward(ciphertext3D input)
         if (f.chunked) input = runChunks(f, input);
         // (a network run chunk by chunk has no tail; under two-level chunking the tail starts behind a refresh that ran chunk by chunk)
         if (!f.per_chunk) input = runRange(f, f.chunked ? f.split : 0, L, input, true, !f.chunk_refresh);
+    }
+    if (flood_bits) {                                       // the response: sanitised before the caller sees it
+        if (input.buf == callers && (input.form == CRC_COEFF || input.form == CRC_NTT)) {                         // (a network whose output is its input's buffer: the caller's tensor is not forward's to write)
+            ciphertext3D own(input.B, input.zd, input.xd, input.yd, input.form);
+            chk(crc_memcpy_d2d(ctx(), own.data(), input.data(), input.count() * ctBytes(), stream()), "crc_memcpy_d2d");
+            input = own;
+        }
+        floodImages(input, flood_bits);
     }
     if (time_with_events) {
         chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");

@@ -120,6 +120,7 @@ struct Level {
     uint64_t generation = 0;
     std::vector<uint64_t> secret_key, public_key;           // [kept][n] and [2][kept][n], NTT form
     std::shared_ptr<DeviceBuffer> d_secret_key;
+    std::shared_ptr<DeviceBuffer> d_public_key;             // uploaded by the first floodImages at this level
     // a derived level's keys (null / empty on a plain one): what ev_keys16 and the Galois key set were when makeLevel ran
     bool derived = false;
     std::shared_ptr<DeviceBuffer> d_ev_keys16, d_galois_keys, d_galois_ckeys;
@@ -158,6 +159,21 @@ std::vector<floatCube> decryptImages(const LevelTensor &t);
 std::vector<std::vector<int64_t>> decryptSlots(const LevelTensor &t, int S);
 std::vector<int> noiseBudgets(const LevelTensor &t);
 int minNoiseBudget(const LevelTensor &t, size_t *where = nullptr);
+// ---- noise flooding: sanitise a response before it leaves (include/crcnn_hip.h, "Noise flooding") ------------------------------------------------------------
+// The noise of an evaluated ciphertext is a function of the model's weights, and the client who holds the secret key can read it (noiseBudgets).  floodImages
+// adds to every ciphertext of a CRC_COEFF or CRC_NTT tensor, in place and on the launch stream (crc_flood_dev, work space from the layers' scratch area), a fresh
+// public-key encryption of zero whose first error term is uniform on [-2^flood_bits, 2^flood_bits).  The plaintexts are unchanged; the budget afterwards is at
+// least crc_flood_budget_bound(ctx, b, flood_bits) - 2 bits.  A LevelTensor is flooded under its level's public-key rows and context.  Key and counter
+// discipline of encryptImage: the master key, a counter that advances by the ciphertext count, and the deterministic seed under setDeterministicSeed.
+// std::invalid_argument for a width crc_flood_supported refuses, an empty tensor and the packed and limb forms.
+void floodImages(ciphertext3D &t, int flood_bits);
+void floodImages(LevelTensor &t, int flood_bits);
+// crc_flood_bits on the parameters: the width that covers, by `lambda` bits, the noise of a ciphertext with budget_in bits of budget.  budget_in is the budget the
+// server knows A PRIORI for its network (the plain-modulus search's), never a measured one -- measuring needs the secret key, and the measured value is itself a
+// function of the weights.  std::invalid_argument where no admissible width exists
+int floodBits(int budget_in, int lambda = 40);
+// the server's last step: a flooded copy of `t` at the full modulus (t itself is not written), then modSwitch to `to` in out_form
+LevelTensor sanitizeResponse(const ciphertext3D &t, int flood_bits, const std::shared_ptr<Level> &to, int out_form = CRC_COEFF);
 // ---- several plain moduli: a residue base (include/crcnn_hip.h, "Several plain moduli") -----------------------------------------------------------------------
 // A PlainBase is r <= CRC_SLOTS_CRT_MAX contexts over the n, q and device of setParameters() whose slot primes ts[j] are pairwise distinct with T = prod ts[j] <
 // 2^63: member 0 is the global context (ts[0] must be its plain modulus), the others are owned sibling contexts.  The keys do not involve t, so the base holds
@@ -762,6 +778,11 @@ public:
     // per layer, -1 where the output is in a packed or limb form and cannot be measured (ntt_resident with matrix_cores; switch them off for a full profile).
     // Costs one stream synchronisation per layer call.
     bool profile_budget = false;
+    // non-zero: forward() floods its OUTPUT tensor with this width before it returns (floodImages: the response carries no trace of the weights in its noise;
+    // floodBits(a-priori budget) chooses it).  0 (default): off, and not one launch differs.  std::invalid_argument for a width the parameters refuse, before
+    // the first launch; for an output in a packed or limb form (which only the last layer decides), after it.  The caller's own tensor is never written: an
+    // output that shares the input's buffer is copied first
+    int flood_bits = 0;
     std::vector<int> last_layer_budget_min, last_layer_budget_first;
     std::vector<double> last_layer_ms;                      // per-layer wall milliseconds of the last forward (T_LAYER_i, mainparams.cpp:81)
     // true: last_layer_ms comes from HIP events recorded on the launch stream around every layer call -- no synchronisation between the layers, what a

@@ -58,7 +58,11 @@ int main(int argc, char **argv)
                 if (noiseBudget(encrypted_image) <= 0) ret_value = OUT_OF_BUDGET;
                 floatCube image;
                 if (response_level && ret_value == SUCCESS) {
-                    const LevelTensor response = modSwitch(encrypted_image, response_level);
+                    // ... and sanitised where the budget allows: flooded at the full modulus, then switched down.  This example holds both sides' keys and takes
+                    // the logits' measured budget for the width; a server takes the a-priori budget of its network instead (floodBits)
+                    const int budget = minNoiseBudget(encrypted_image), width = crc_flood_bits(context, budget, 40);
+                    const bool flood = width > 0 && crc_flood_budget_bound(context, budget, width) > 8;
+                    const LevelTensor response = flood ? sanitizeResponse(encrypted_image, width, response_level) : modSwitch(encrypted_image, response_level);
                     if (minNoiseBudget(response) > 0) image = decryptImages(response)[0];
                 }
                 if (image.empty()) image = decryptImage(encrypted_image);

@@ -1068,6 +1068,60 @@ int    crc_mod_switch_forms(crc_ctx *from, const crc_ctx *to, const uint64_t *d_
 int    crc_mod_switch(const crc_ctx *from, const crc_ctx *to, const uint64_t *h_in, int in_form, size_t count, int size, uint64_t *h_out, int out_form);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Noise flooding (smudging): sanitise a response before it leaves the server.  The noise of an evaluated ciphertext is a function of the model's weights, and
+ * a client who holds the secret key can read it (crc_noise_budget).  The server therefore adds to every ciphertext of a response a fresh public-key
+ * encryption of zero whose first error term is far wider than any noise the evaluation can have left.  Not in SEAL 2.3.1 nor in the reference: the
+ * engine's own, like modulus switching.  Opt-in; nothing else changes.  The server's last step is: flood, crc_mod_switch_forms, send.
+ *
+ * Definition.  For a size-2 ciphertext (c0, c1) under the public key (p0, p1) and flood_bits = B:
+ *      c0' = c0 + p0 u + e1,     c1' = c1 + p1 u + e2
+ *   u   uniform ternary (the encryptor's law and decoding rule)
+ *   e2  the encryptor's clipped normal (sigma 3.19 cut at 6 sigma, truncated: crc_encrypt_dev_noise_thresholds)
+ *   e1  UNIFORM on the integers [-2^B, 2^B): x = B + 1 uniform bits, e1 = x - 2^B; its residues are taken from a 128-bit word in exact integer arithmetic
+ * The samples are ChaCha20 under a domain of their own, one block per (ciphertext stream id, coefficient pair); csrc/chacha.h (CHACHA_DOM_FLOOD) has the word
+ * layout, which is a contract between the device and the host twin.  Ciphertext m of a call has the stream id stream_base + m.
+ *
+ * Admission.  1 <= B <= 126 and t (2^B + 38 n) < q / 2 (crc_flood_supported): the flood adds w = e1 - e_pk u + e2 s to c0 + c1 s, |w| <= 2^B + 38 n per
+ * coefficient under ternary u, s and errors in [-19, 19]; past the bound the flood alone could flip the plaintext.  The plaintext does not change.
+ *
+ * Noise.  The invariant noise grows by at most t (2^B + 38 n) / q: a ciphertext with b bits of budget keeps at least
+ * floor(-log2(2^-b + t (2^B + 38 n) / q)) bits (crc_flood_budget_bound; less up to 2 bits for the bit-count floors of the budget measurement).
+ *
+ *   crc_flood_supported      1 where B is admitted on this context, else 0
+ *   crc_flood_bits           pure arithmetic: the smallest B whose range 2^B exceeds, by lambda_bits, the largest noise |w| a ciphertext with
+ *                            budget_bits_in bits of budget can carry: B = lambda_bits + max(0, bits(q) - budget_bits_in - bits(t)).  A negative status
+ *                            (CRC_ERR_INVALID_ARGUMENT) where that B is not admitted or an argument is out of range (budget outside [0, bits(q)], lambda
+ *                            outside [0, 126]).  A SERVER HAS NO SECRET KEY: it calls this with the budget it knows A PRIORI for its network (the plain-modulus
+ *                            search's worst case), never a measured one -- a measured budget is itself a function of the weights and the input.
+ *   crc_flood_budget_bound   the lower bound above as an integer (not below 0); a negative status for a B that is not admitted or a budget outside [0, bits(q)]
+ *   crc_flood_dev_work_bytes the work space of the device call (0 for a form it refuses): 3 k n words per ciphertext
+ *   crc_flood_dev_key        d_ct [count][2][k][n] in `form` CRC_COEFF or CRC_NTT, flooded IN PLACE and in that form; d_pk [2][k][n] (NTT form, as crc_keygen
+ *                            makes it).  Asynchronous on `stream`.  An NTT-form tensor is never transformed back: the error rows are transformed forward and
+ *                            join the tensor, with p u, in that transform's last loop (three forward transforms per modulus; the tensor is read once and
+ *                            written once).  A coefficient-form tensor costs one forward and two inverse transforms per modulus.  n <= 16384
+ *                            (CRC_ERR_UNSUPPORTED above).  h_key: 32 bytes of host memory.  A REUSED (key, stream_base + m) IS A BREAK: the same u, e1, e2
+ *                            twice, so the difference of two floods is the difference of their inputs.  Callers advance stream_base by count per call.
+ *   crc_flood_dev            the same under the expansion of a PUBLIC 64-bit seed, stream_base 0 (tests, benchmarks; deterministic, NOT secure)
+ *   crc_flood_key, crc_flood the host twin: host memory, any context (device = -1 included); bit for bit the device call for the same (key, stream_base) / seed
+ * Both forms of one tensor under one key give the same ciphertexts (crc_ntt_fwd of the coefficient-form result is the NTT-form result).
+ * CRC_ERR_INVALID_ARGUMENT, nothing launched and the tensor untouched: a B that is not admitted, a null or (device) not 16-byte aligned pointer, a d_work or d_pk
+ * that overlaps d_ct.  CRC_ERR_UNSUPPORTED for a form other than the two.  count == 0 is CRC_OK on any context the call could serve (a null context, a host-only
+ * context for the _dev calls and a null h_key are still CRC_ERR_INVALID_ARGUMENT), whatever the other arguments.  No width is admitted on a context of more than
+ * 8 coefficient moduli (the kernels' argument block holds 8): crc_flood_supported is 0 there, for the host twin too.
+ * What flooding does not hide: the decrypted values themselves, which are the client's to see; and the bound is statistical in lambda_bits (2^-lambda).
+ * ------------------------------------------------------------------------------------------------------------- */
+int    crc_flood_supported(const crc_ctx *ctx, int flood_bits);
+int    crc_flood_bits(const crc_ctx *ctx, int budget_bits_in, int lambda_bits);
+int    crc_flood_budget_bound(const crc_ctx *ctx, int budget_bits_in, int flood_bits);
+size_t crc_flood_dev_work_bytes(const crc_ctx *ctx, size_t count, int form);
+int    crc_flood_dev_key(crc_ctx *ctx, const uint64_t *d_pk, uint64_t *d_ct, size_t count, int form, int flood_bits, const uint8_t *h_key, uint64_t stream_base,
+                         void *d_work, void *stream);
+int    crc_flood_dev(crc_ctx *ctx, const uint64_t *d_pk, uint64_t *d_ct, size_t count, int form, int flood_bits, uint64_t seed, void *d_work, void *stream);
+int    crc_flood_key(const crc_ctx *ctx, const uint64_t *h_pk, uint64_t *h_ct, size_t count, int form, int flood_bits, const uint8_t *h_key,
+                     uint64_t stream_base);
+int    crc_flood(const crc_ctx *ctx, const uint64_t *h_pk, uint64_t *h_ct, size_t count, int form, int flood_bits, uint64_t seed);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Key-switching keys for a lower level WITHOUT the secret key: the upper level's keys, which are public, become the level's keys.
  *
  * Pair p = (l, d) of a key blob over Q = q_0 .. q_{k-1} is  first = -(A s + e) + E w,  second = A,  E = (Q / q_l) 2^(dbc d) mod Q, which is non-zero in
