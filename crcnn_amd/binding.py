@@ -765,20 +765,13 @@ class Engine:
 
     def flood_dev(self, d_pk, d_ct, count, flood_bits, d_work, form=COEFF, seed=None, key=None, stream_base=0):
         """d_ct [count][2][k][n] in `form`, flooded in place on this engine's stream.  `key` (32 bytes) with `stream_base`, or a public `seed` (tests)"""
-        if key is not None:
-            _chk(self.L.crc_flood_dev_key(self.c, self.p(d_pk), self.p(d_ct), count, form, flood_bits, self._key(key), stream_base, self.p(d_work), self.stream),
-                 "crc_flood_dev_key")
-        else:
-            _chk(self.L.crc_flood_dev(self.c, self.p(d_pk), self.p(d_ct), count, form, flood_bits, seed, self.p(d_work), self.stream), "crc_flood_dev")
+        self._seeded_or_keyed("flood_dev", (self.c, self.p(d_pk), self.p(d_ct), count, form, flood_bits), seed, key, stream_base, (self.p(d_work), self.stream))
 
     def flood(self, pk, cts, flood_bits, form=COEFF, seed=None, key=None, stream_base=0):
         """host twin: a flooded copy of ciphertexts [count][2][k][n]"""
         out = np.ascontiguousarray(cts, dtype=np.uint64).reshape(-1, 2, self.k, self.n).copy()
         pk = np.ascontiguousarray(pk, dtype=np.uint64)
-        if key is not None:
-            _chk(self.L.crc_flood_key(self.c, _pu(pk), _pu(out), out.shape[0], form, flood_bits, self._key(key), stream_base), "crc_flood_key")
-        else:
-            _chk(self.L.crc_flood(self.c, _pu(pk), _pu(out), out.shape[0], form, flood_bits, seed), "crc_flood")
+        self._seeded_or_keyed("flood", (self.c, _pu(pk), _pu(out), out.shape[0], form, flood_bits), seed, key, stream_base, ())
         return out
 
     # ---- host side: encode / client
@@ -861,24 +854,16 @@ class Engine:
 
     def slots_refresh_dev(self, d_sk, d_pk, d_ct_in, count, divisor, seed, d_ct_out, d_work, in_form=COEFF, out_form=COEFF, key=None, stream_base=0):
         """decrypt -> rescale every slot by `divisor` -> encrypt under the public key: crc_decrypt_dev, crc_slots_rescale_dev, crc_encrypt_dev[_key]_forms as one call"""
-        if key is None:
-            _chk(self.L.crc_slots_refresh_dev(self.c, self.p(d_sk), self.p(d_pk), self.p(d_ct_in), count, in_form, int(divisor), seed, out_form, self.p(d_ct_out),
-                                              self.p(d_work), self.stream), "crc_slots_refresh_dev")
-        else:
-            _chk(self.L.crc_slots_refresh_dev_key(self.c, self.p(d_sk), self.p(d_pk), self.p(d_ct_in), count, in_form, int(divisor), self._key(key), stream_base,
-                                                  out_form, self.p(d_ct_out), self.p(d_work), self.stream), "crc_slots_refresh_dev_key")
+        self._seeded_or_keyed("slots_refresh_dev", (self.c, self.p(d_sk), self.p(d_pk), self.p(d_ct_in), count, in_form, int(divisor)), seed, key, stream_base,
+                              (out_form, self.p(d_ct_out), self.p(d_work), self.stream))
 
     def slots_refresh_sym_dev_work_bytes(self, count, in_form=COEFF):
         return self.L.crc_slots_refresh_sym_dev_work_bytes(self.c, count, in_form)
 
     def slots_refresh_sym_dev(self, d_sk, d_ct_in, count, divisor, seed, d_ct_out, d_work, in_form=COEFF, out_form=COEFF, key=None, stream_base=0):
         """the same under the secret key (crc_encrypt_sym_dev[_key]_forms)"""
-        if key is None:
-            _chk(self.L.crc_slots_refresh_sym_dev(self.c, self.p(d_sk), self.p(d_ct_in), count, in_form, int(divisor), seed, out_form, self.p(d_ct_out),
-                                                  self.p(d_work), self.stream), "crc_slots_refresh_sym_dev")
-        else:
-            _chk(self.L.crc_slots_refresh_sym_dev_key(self.c, self.p(d_sk), self.p(d_ct_in), count, in_form, int(divisor), self._key(key), stream_base, out_form,
-                                                      self.p(d_ct_out), self.p(d_work), self.stream), "crc_slots_refresh_sym_dev_key")
+        self._seeded_or_keyed("slots_refresh_sym_dev", (self.c, self.p(d_sk), self.p(d_ct_in), count, in_form, int(divisor)), seed, key, stream_base,
+                              (out_form, self.p(d_ct_out), self.p(d_work), self.stream))
 
     # client-side activation: window = (xd, yd, xs, ys, xf, yf); outputs ((xd - xf) // xs + 1) x ((yd - yf) // ys + 1) rows per plane
     def slots_act(self, plains, planes, window, divisor, relu=0, cap=0):
@@ -900,13 +885,8 @@ class Engine:
     def slots_refresh_act_dev(self, d_sk, d_pk, d_ct_in, planes, window, divisor, relu, cap, seed, d_ct_out, d_work, in_form=COEFF, out_form=COEFF, key=None,
                               stream_base=0):
         """decrypt planes * xd * yd ciphertexts -> slots_act_dev -> encrypt the planes * xo * yo outputs under the public key, as one call"""
-        if key is None:
-            _chk(self.L.crc_slots_refresh_act_dev(self.c, self.p(d_sk), self.p(d_pk), self.p(d_ct_in), planes, *window, in_form, int(divisor), int(relu), int(cap),
-                                                  seed, out_form, self.p(d_ct_out), self.p(d_work), self.stream), "crc_slots_refresh_act_dev")
-        else:
-            _chk(self.L.crc_slots_refresh_act_dev_key(self.c, self.p(d_sk), self.p(d_pk), self.p(d_ct_in), planes, *window, in_form, int(divisor), int(relu),
-                                                      int(cap), self._key(key), stream_base, out_form, self.p(d_ct_out), self.p(d_work), self.stream),
-                 "crc_slots_refresh_act_dev_key")
+        self._seeded_or_keyed("slots_refresh_act_dev", (self.c, self.p(d_sk), self.p(d_pk), self.p(d_ct_in), planes, *window, in_form, int(divisor), int(relu), int(cap)),
+                              seed, key, stream_base, (out_form, self.p(d_ct_out), self.p(d_work), self.stream))
 
     def slots_refresh_act_sym_dev_work_bytes(self, planes, window, in_form=COEFF):
         return self.L.crc_slots_refresh_act_sym_dev_work_bytes(self.c, planes, *window, in_form)
@@ -914,13 +894,8 @@ class Engine:
     def slots_refresh_act_sym_dev(self, d_sk, d_ct_in, planes, window, divisor, relu, cap, seed, d_ct_out, d_work, in_form=COEFF, out_form=COEFF, key=None,
                                   stream_base=0):
         """the same under the secret key"""
-        if key is None:
-            _chk(self.L.crc_slots_refresh_act_sym_dev(self.c, self.p(d_sk), self.p(d_ct_in), planes, *window, in_form, int(divisor), int(relu), int(cap), seed,
-                                                      out_form, self.p(d_ct_out), self.p(d_work), self.stream), "crc_slots_refresh_act_sym_dev")
-        else:
-            _chk(self.L.crc_slots_refresh_act_sym_dev_key(self.c, self.p(d_sk), self.p(d_ct_in), planes, *window, in_form, int(divisor), int(relu), int(cap),
-                                                          self._key(key), stream_base, out_form, self.p(d_ct_out), self.p(d_work), self.stream),
-                 "crc_slots_refresh_act_sym_dev_key")
+        self._seeded_or_keyed("slots_refresh_act_sym_dev", (self.c, self.p(d_sk), self.p(d_ct_in), planes, *window, in_form, int(divisor), int(relu), int(cap)),
+                              seed, key, stream_base, (out_form, self.p(d_ct_out), self.p(d_work), self.stream))
 
     def keygen(self, seed):
         sk = np.zeros((self.k, self.n), dtype=np.uint64); pk = np.zeros((2, self.k, self.n), dtype=np.uint64)
@@ -943,6 +918,12 @@ class Engine:
         key = bytes(key)
         assert len(key) == 32
         return (ctypes.c_uint8 * 32).from_buffer_copy(key)
+
+    def _seeded_or_keyed(self, name, head, seed, key, stream_base, tail):
+        """crc_<name>(*head, seed, *tail), or with `key` crc_<name>_key(*head, key, stream_base, *tail): the two randomness forms of one entry point"""
+        if key is None:
+            return _chk(getattr(self.L, "crc_" + name)(*head, seed, *tail), "crc_" + name)
+        return _chk(getattr(self.L, "crc_" + name + "_key")(*head, self._key(key), stream_base, *tail), "crc_" + name + "_key")
 
     def random_key(self):
         buf = (ctypes.c_uint8 * 32)()
@@ -968,11 +949,7 @@ class Engine:
         plains = np.ascontiguousarray(plains); lead = plains.shape[:-1]
         cnt = int(np.prod(lead)) if lead else 1
         ct = np.zeros((cnt, 2, self.k, self.n), dtype=np.uint64)
-        if key is None:
-            _chk(self.L.crc_encrypt_sym(self.c, _pu(sk), _pu(plains.reshape(cnt, self.n)), cnt, seed, out_form, _pu(ct)), "crc_encrypt_sym")
-        else:
-            _chk(self.L.crc_encrypt_sym_key(self.c, _pu(sk), _pu(plains.reshape(cnt, self.n)), cnt, self._key(key), stream_base, out_form, _pu(ct)),
-                 "crc_encrypt_sym_key")
+        self._seeded_or_keyed("encrypt_sym", (self.c, _pu(sk), _pu(plains.reshape(cnt, self.n)), cnt), seed, key, stream_base, (out_form, _pu(ct)))
         return ct.reshape(lead + (2, self.k, self.n))
 
     # seeded secret-key ciphertexts: the c0 rows [count][k][n] (NTT form) and a PUBLIC 32-byte seed; c1 is regenerated from the seed
@@ -1647,12 +1624,8 @@ class Engine:
         return self.L.crc_refresh_dev_work_bytes(self.c, count, in_form)
 
     def refresh_dev(self, d_sk, d_pk, d_ct_in, count, seed, d_ct_out, d_work, in_form=COEFF, out_form=COEFF, d_values=None, key=None, stream_base=0):
-        if key is None:
-            _chk(self.L.crc_refresh_dev(self.c, self.p(d_sk), self.p(d_pk), self.p(d_ct_in), count, in_form, seed, out_form, self.p(d_ct_out), self.p(d_values),
-                                        self.p(d_work), self.stream), "crc_refresh_dev")
-        else:
-            _chk(self.L.crc_refresh_dev_key(self.c, self.p(d_sk), self.p(d_pk), self.p(d_ct_in), count, in_form, self._key(key), stream_base, out_form,
-                                            self.p(d_ct_out), self.p(d_values), self.p(d_work), self.stream), "crc_refresh_dev_key")
+        self._seeded_or_keyed("refresh_dev", (self.c, self.p(d_sk), self.p(d_pk), self.p(d_ct_in), count, in_form), seed, key, stream_base,
+                              (out_form, self.p(d_ct_out), self.p(d_values), self.p(d_work), self.stream))
 
     # ---- encryption under the secret key on the device, and the refresh that uses it
     def seeded_expand_dev(self, d_c0, count, public_seed, stream_base, out_form, d_ct):
@@ -1704,12 +1677,8 @@ class Engine:
         return self.L.crc_refresh_sym_dev_work_bytes(self.c, count, in_form)
 
     def refresh_sym_dev(self, d_sk, d_ct_in, count, seed, d_ct_out, d_work, in_form=COEFF, out_form=COEFF, d_values=None, key=None, stream_base=0):
-        if key is None:
-            _chk(self.L.crc_refresh_sym_dev(self.c, self.p(d_sk), self.p(d_ct_in), count, in_form, seed, out_form, self.p(d_ct_out), self.p(d_values),
-                                            self.p(d_work), self.stream), "crc_refresh_sym_dev")
-        else:
-            _chk(self.L.crc_refresh_sym_dev_key(self.c, self.p(d_sk), self.p(d_ct_in), count, in_form, self._key(key), stream_base, out_form,
-                                                self.p(d_ct_out), self.p(d_values), self.p(d_work), self.stream), "crc_refresh_sym_dev_key")
+        self._seeded_or_keyed("refresh_sym_dev", (self.c, self.p(d_sk), self.p(d_ct_in), count, in_form), seed, key, stream_base,
+                              (out_form, self.p(d_ct_out), self.p(d_values), self.p(d_work), self.stream))
 
     def encrypt_dev_noise_thresholds(self):
         out = (ctypes.c_uint64 * 19)()

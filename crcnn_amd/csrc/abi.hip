@@ -784,16 +784,42 @@ extern "C" int crc_encode_dev_f64(crc_ctx *c, const double *d_values, size_t cou
     CHECK_CTX(c); if (!d_values || !d_plain) return CRC_ERR_INVALID_ARGUMENT;
     return k_fra_encode(c, d_values, 1, count, d_plain, nullptr, S(stream));
 }
-// Work of a refresh: [compact plaintexts [count][96]][dense plaintexts [count][n]: the public-key refresh's coefficient-form results only][the decryptor's
-// rows, then the encryptor's (sym: the secret-key encryptor's) samples]
+// ---- client-side refreshes: decrypt on the device, do something to the plaintexts, encrypt again under fresh randomness ----
+// Four families (fractional, slots rescale, slots activation, slots CRT), one frame: the family's check, nothing to do for no items (the slot activations), the
+// work carved by the family's layout, the decryptor, the family's middle kernel, Reenc::run.
+// Reenc: who encrypts a refresh's results (sym: the secret key, d_pk unused), with which randomness, into which form.  A null key pointer comes down as has_key =
+// false, for ok() to refuse where the family's check orders it
+struct Reenc {
+    const u64 *d_sk, *d_pk; bool sym; ChaChaKey key; u64 stream_base; int out_form; bool has_key;
+    static Reenc seeded(const u64 *d_sk, const u64 *d_pk, bool sym, u64 seed, int out_form) { return {d_sk, d_pk, sym, chacha_seed_key(seed), 0, out_form, true}; }
+    static Reenc keyed(const u64 *d_sk, const u64 *d_pk, bool sym, const uint8_t *key, u64 stream_base, int out_form)
+    {
+        return {d_sk, d_pk, sym, key ? chacha_load_key(key) : ChaChaKey{}, stream_base, out_form, key != nullptr};
+    }
+    bool ok() const { return d_sk && (sym || d_pk) && has_key && ct_form_ok(out_form); }
+    static size_t words(const crc_ctx *c, bool sym, size_t count) { return sym ? k_encrypt_sym_work_words(c, count) : k_encrypt_work_words(c, count); }
+    // plain: dense rows [count][n], or (compact) compact plaintexts; the keystream ids stream_base + id_offset .. + count
+    int run(crc_ctx *c, const u64 *plain, size_t count, bool compact, u64 id_offset, u64 *d_out, u64 *w, hipStream_t st) const
+    {
+        if (sym) return k_encrypt_sym(c, d_sk, plain, count, key, stream_base + id_offset, d_out, w, st, out_form == CRC_NTT, compact);
+        return k_encrypt(c, d_pk, plain, count, key, stream_base + id_offset, d_out, w, st, out_form == CRC_NTT, compact);
+    }
+};
+// the tail of every refresh's work: the decryptor's rows for dec_cts ciphertexts in in_form, then -- in the same words -- the encryptor's samples for enc_cts
+static size_t refresh_tail_words(const crc_ctx *c, size_t dec_cts, int in_form, bool sym, size_t enc_cts)
+{
+    const size_t dec = k_decrypt_work_words(c, dec_cts, 2, in_form == CRC_NTT), enc = Reenc::words(c, sym, enc_cts);
+    return dec > enc ? dec : enc;
+}
+
+// The fractional refresh.  Work: [compact plaintexts [count][96]][dense plaintexts [count][n]: the public-key refresh's coefficient-form results only][the tail]
 struct RefreshWork { u64 *compact, *dense, *w; };
 static RefreshWork refresh_layout(const crc_ctx *c, size_t count, int in_form, bool sym, WorkArena &a)
 {
-    const size_t dec = k_decrypt_work_words(c, count, 2, in_form == CRC_NTT), enc = sym ? k_encrypt_sym_work_words(c, count) : k_encrypt_work_words(c, count);
     RefreshWork L{};
     L.compact = a.take<u64>(count * (size_t)CRC_PLAIN_COMPACT_WORDS);
     if (!sym) L.dense = a.take<u64>(count * (size_t)c->n);
-    L.w = a.take<u64>(dec > enc ? dec : enc);
+    L.w = a.take<u64>(refresh_tail_words(c, count, in_form, sym, count));
     return L;
 }
 static size_t refresh_bytes(const crc_ctx *c, size_t count, int in_form, bool sym)
@@ -803,33 +829,29 @@ static size_t refresh_bytes(const crc_ctx *c, size_t count, int in_form, bool sy
     refresh_layout(c, count, in_form, sym, a);
     return a.bytes();
 }
-extern "C" size_t crc_refresh_dev_work_bytes(const crc_ctx *c, size_t count, int in_form) { return refresh_bytes(c, count, in_form, false); }
-static int refresh_impl(crc_ctx *c, const u64 *d_sk, const u64 *d_pk, const u64 *d_in, size_t count, int in_form, const ChaChaKey &key, u64 stream_base,
-                        int out_form, u64 *d_out, float *d_vals, void *d_work, hipStream_t st)
+static int refresh_impl(crc_ctx *c, const Reenc &R, const u64 *d_in, size_t count, int in_form, u64 *d_out, float *d_vals, void *d_work, hipStream_t st)
 {
+    CHECK_CTX(c); if (!R.ok() || !d_in || !d_out || !d_work || !ct_form_ok(in_form)) return CRC_ERR_INVALID_ARGUMENT;
     WorkArena a(d_work);
-    const RefreshWork L = refresh_layout(c, count, in_form, !d_pk, a);
-    // decrypt -> decode -> float -> encode leaves the 96-word compact plaintexts (only the 96 coefficients the decoder reads are ever scaled) ...
-    RUN(k_decrypt_recode(c, d_sk, d_in, count, in_form == CRC_NTT, L.compact, d_vals, L.w, st));
-    // ... which the secret-key encryptor (d_pk null) reads for either result form (the NTT form is its definition) ...
-    if (!d_pk) return k_encrypt_sym(c, d_sk, L.compact, count, key, stream_base, d_out, L.w, st, out_form == CRC_NTT, true);
-    // ... and the NTT-form public-key encryptor reads as they are; the coefficient-form one adds Delta m from dense rows
-    if (out_form == CRC_NTT) return k_encrypt(c, d_pk, L.compact, count, key, stream_base, d_out, L.w, st, true, true);
+    const RefreshWork L = refresh_layout(c, count, in_form, R.sym, a);
+    // decrypt -> decode -> float -> encode leaves the 96-word compact plaintexts (only the 96 coefficients the decoder reads are ever scaled), which the
+    // secret-key encryptor reads for either result form (the NTT form is its definition) and the NTT-form public-key encryptor reads as they are ...
+    RUN(k_decrypt_recode(c, R.d_sk, d_in, count, in_form == CRC_NTT, L.compact, d_vals, L.w, st));
+    if (R.sym || R.out_form == CRC_NTT) return R.run(c, L.compact, count, true, 0, d_out, L.w, st);
+    // ... the coefficient-form public-key encryptor adds Delta m from dense rows
     RUN(k_plain_expand(c, L.compact, count, L.dense, st));
-    return k_encrypt(c, d_pk, L.dense, count, key, stream_base, d_out, L.w, st, false);
+    return R.run(c, L.dense, count, false, 0, d_out, L.w, st);
 }
+extern "C" size_t crc_refresh_dev_work_bytes(const crc_ctx *c, size_t count, int in_form) { return refresh_bytes(c, count, in_form, false); }
 extern "C" int crc_refresh_dev(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_pk, const uint64_t *d_ct_in, size_t count, int in_form, uint64_t seed,
                                int out_form, uint64_t *d_ct_out, float *d_values_out, void *d_work, void *stream)
 {
-    CHECK_CTX(c); if (!d_sk || !d_pk || !d_ct_in || !d_ct_out || !d_work || !ct_form_ok(in_form) || !ct_form_ok(out_form)) return CRC_ERR_INVALID_ARGUMENT;
-    return refresh_impl(c, d_sk, d_pk, d_ct_in, count, in_form, chacha_seed_key(seed), 0, out_form, d_ct_out, d_values_out, d_work, S(stream));
+    return refresh_impl(c, Reenc::seeded(d_sk, d_pk, false, seed, out_form), d_ct_in, count, in_form, d_ct_out, d_values_out, d_work, S(stream));
 }
 extern "C" int crc_refresh_dev_key(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_pk, const uint64_t *d_ct_in, size_t count, int in_form,
                                    const uint8_t *key, uint64_t stream_base, int out_form, uint64_t *d_ct_out, float *d_values_out, void *d_work, void *stream)
 {
-    CHECK_CTX(c); if (!d_sk || !d_pk || !d_ct_in || !d_ct_out || !d_work || !key || !ct_form_ok(in_form) || !ct_form_ok(out_form))
-        return CRC_ERR_INVALID_ARGUMENT;
-    return refresh_impl(c, d_sk, d_pk, d_ct_in, count, in_form, chacha_load_key(key), stream_base, out_form, d_ct_out, d_values_out, d_work, S(stream));
+    return refresh_impl(c, Reenc::keyed(d_sk, d_pk, false, key, stream_base, out_form), d_ct_in, count, in_form, d_ct_out, d_values_out, d_work, S(stream));
 }
 // ---- encryption under the secret key and the refresh that uses it (kernels_client.hip: k_encrypt_sym) ----
 extern "C" size_t crc_encrypt_sym_dev_work_bytes(const crc_ctx *c, size_t count) { return c ? work_bytes(k_encrypt_sym_work_words(c, count)) : 0; }
@@ -851,26 +873,21 @@ extern "C" size_t crc_refresh_sym_dev_work_bytes(const crc_ctx *c, size_t count,
 extern "C" int crc_refresh_sym_dev(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_ct_in, size_t count, int in_form, uint64_t seed, int out_form,
                                    uint64_t *d_ct_out, float *d_values_out, void *d_work, void *stream)
 {
-    if (!d_sk || !d_ct_in || !d_ct_out || !d_work || !ct_form_ok(in_form) || !ct_form_ok(out_form)) return CRC_ERR_INVALID_ARGUMENT;
-    CHECK_CTX(c);
-    return refresh_impl(c, d_sk, nullptr, d_ct_in, count, in_form, chacha_seed_key(seed), 0, out_form, d_ct_out, d_values_out, d_work, S(stream));
+    return refresh_impl(c, Reenc::seeded(d_sk, nullptr, true, seed, out_form), d_ct_in, count, in_form, d_ct_out, d_values_out, d_work, S(stream));
 }
 extern "C" int crc_refresh_sym_dev_key(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_ct_in, size_t count, int in_form, const uint8_t *key,
                                        uint64_t stream_base, int out_form, uint64_t *d_ct_out, float *d_values_out, void *d_work, void *stream)
 {
-    if (!d_sk || !d_ct_in || !d_ct_out || !d_work || !key || !ct_form_ok(in_form) || !ct_form_ok(out_form)) return CRC_ERR_INVALID_ARGUMENT;
-    CHECK_CTX(c);
-    return refresh_impl(c, d_sk, nullptr, d_ct_in, count, in_form, chacha_load_key(key), stream_base, out_form, d_ct_out, d_values_out, d_work, S(stream));
+    return refresh_impl(c, Reenc::keyed(d_sk, nullptr, true, key, stream_base, out_form), d_ct_in, count, in_form, d_ct_out, d_values_out, d_work, S(stream));
 }
 // ---- the refresh of a slot-batched tensor: crc_decrypt_dev, the rescale kernel in place on the plaintexts, the matching encryptor ----
-// Work: [plaintexts [count][n]][the decryptor's rows, then the encryptor's (sym: the secret-key encryptor's) samples]
+// Work: [plaintexts [count][n]][the tail]
 struct SlotsRefreshWork { u64 *plain, *w; };
 static SlotsRefreshWork slots_refresh_layout(const crc_ctx *c, size_t count, int in_form, bool sym, WorkArena &a)
 {
-    const size_t dec = k_decrypt_work_words(c, count, 2, in_form == CRC_NTT), enc = sym ? k_encrypt_sym_work_words(c, count) : k_encrypt_work_words(c, count);
     SlotsRefreshWork L{};
     L.plain = a.take<u64>(count * (size_t)c->n);
-    L.w = a.take<u64>(dec > enc ? dec : enc);
+    L.w = a.take<u64>(refresh_tail_words(c, count, in_form, sym, count));
     return L;
 }
 static size_t slots_refresh_bytes(const crc_ctx *c, size_t count, int in_form, bool sym)
@@ -880,44 +897,38 @@ static size_t slots_refresh_bytes(const crc_ctx *c, size_t count, int in_form, b
     slots_refresh_layout(c, count, in_form, sym, a);
     return a.bytes();
 }
-// sym: encrypt under the secret key (d_pk unused)
-static int slots_refresh_impl(crc_ctx *c, bool sym, const u64 *d_sk, const u64 *d_pk, const u64 *d_in, size_t count, int in_form, u64 divisor, const ChaChaKey &key,
-                              u64 stream_base, int out_form, u64 *d_out, void *d_work, hipStream_t st)
+static int slots_refresh_impl(crc_ctx *c, const Reenc &R, const u64 *d_in, size_t count, int in_form, u64 divisor, u64 *d_out, void *d_work, hipStream_t st)
 {
+    CHECK_CTX(c);
     RUN(slots_rescale_args_ok(c, d_in, d_out, divisor));
-    if (!d_sk || (!sym && !d_pk) || !d_work || !ct_form_ok(in_form) || !ct_form_ok(out_form)) return CRC_ERR_INVALID_ARGUMENT;
+    if (!R.ok() || !d_work || !ct_form_ok(in_form)) return CRC_ERR_INVALID_ARGUMENT;
     WorkArena a(d_work);
-    const SlotsRefreshWork L = slots_refresh_layout(c, count, in_form, sym, a);
-    RUN(k_decrypt(c, d_sk, d_in, count, 2, in_form == CRC_NTT, L.plain, L.w, st));
+    const SlotsRefreshWork L = slots_refresh_layout(c, count, in_form, R.sym, a);
+    RUN(k_decrypt(c, R.d_sk, d_in, count, 2, in_form == CRC_NTT, L.plain, L.w, st));
     RUN(k_slots_rescale(c, L.plain, count, divisor, L.plain, st));
-    if (sym) return k_encrypt_sym(c, d_sk, L.plain, count, key, stream_base, d_out, L.w, st, out_form == CRC_NTT, false);
-    return k_encrypt(c, d_pk, L.plain, count, key, stream_base, d_out, L.w, st, out_form == CRC_NTT);
+    return R.run(c, L.plain, count, false, 0, d_out, L.w, st);
 }
 extern "C" size_t crc_slots_refresh_dev_work_bytes(const crc_ctx *c, size_t count, int in_form) { return slots_refresh_bytes(c, count, in_form, false); }
 extern "C" size_t crc_slots_refresh_sym_dev_work_bytes(const crc_ctx *c, size_t count, int in_form) { return slots_refresh_bytes(c, count, in_form, true); }
 extern "C" int crc_slots_refresh_dev(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_pk, const uint64_t *d_ct_in, size_t count, int in_form, uint64_t divisor,
                                      uint64_t seed, int out_form, uint64_t *d_ct_out, void *d_work, void *stream)
 {
-    CHECK_CTX(c);
-    return slots_refresh_impl(c, false, d_sk, d_pk, d_ct_in, count, in_form, divisor, chacha_seed_key(seed), 0, out_form, d_ct_out, d_work, S(stream));
+    return slots_refresh_impl(c, Reenc::seeded(d_sk, d_pk, false, seed, out_form), d_ct_in, count, in_form, divisor, d_ct_out, d_work, S(stream));
 }
 extern "C" int crc_slots_refresh_dev_key(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_pk, const uint64_t *d_ct_in, size_t count, int in_form,
                                          uint64_t divisor, const uint8_t *key, uint64_t stream_base, int out_form, uint64_t *d_ct_out, void *d_work, void *stream)
 {
-    CHECK_CTX(c); if (!key) return crc_slots_supported(c) ? CRC_ERR_INVALID_ARGUMENT : CRC_ERR_PARAMETERS;
-    return slots_refresh_impl(c, false, d_sk, d_pk, d_ct_in, count, in_form, divisor, chacha_load_key(key), stream_base, out_form, d_ct_out, d_work, S(stream));
+    return slots_refresh_impl(c, Reenc::keyed(d_sk, d_pk, false, key, stream_base, out_form), d_ct_in, count, in_form, divisor, d_ct_out, d_work, S(stream));
 }
 extern "C" int crc_slots_refresh_sym_dev(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_ct_in, size_t count, int in_form, uint64_t divisor, uint64_t seed,
                                          int out_form, uint64_t *d_ct_out, void *d_work, void *stream)
 {
-    CHECK_CTX(c);
-    return slots_refresh_impl(c, true, d_sk, nullptr, d_ct_in, count, in_form, divisor, chacha_seed_key(seed), 0, out_form, d_ct_out, d_work, S(stream));
+    return slots_refresh_impl(c, Reenc::seeded(d_sk, nullptr, true, seed, out_form), d_ct_in, count, in_form, divisor, d_ct_out, d_work, S(stream));
 }
 extern "C" int crc_slots_refresh_sym_dev_key(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_ct_in, size_t count, int in_form, uint64_t divisor,
                                              const uint8_t *key, uint64_t stream_base, int out_form, uint64_t *d_ct_out, void *d_work, void *stream)
 {
-    CHECK_CTX(c); if (!key) return crc_slots_supported(c) ? CRC_ERR_INVALID_ARGUMENT : CRC_ERR_PARAMETERS;
-    return slots_refresh_impl(c, true, d_sk, nullptr, d_ct_in, count, in_form, divisor, chacha_load_key(key), stream_base, out_form, d_ct_out, d_work, S(stream));
+    return slots_refresh_impl(c, Reenc::keyed(d_sk, nullptr, true, key, stream_base, out_form), d_ct_in, count, in_form, divisor, d_ct_out, d_work, S(stream));
 }
 // ---- client-side activation of a slot-batched tensor (kernels_slots.hip: k_slots_act) and the refresh that applies it between decrypt and encrypt ----
 // the checks of every act entry point, in the order of the rescale's: the context's slots, then the values; in / out are the two tensors
@@ -949,17 +960,16 @@ extern "C" int crc_slots_act_dev(crc_ctx *c, const uint64_t *d_plain_in, size_t 
     if (ib < oe && ob < ie && !(ib == ob && slots_act_in_place_ok(w))) return CRC_ERR_INVALID_ARGUMENT;
     return k_slots_act(c, d_plain_in, planes, w, divisor, relu, cap, d_plain_out, S(stream));
 }
-// Work: [decrypted plaintexts [planes xd yd][n]][activated plaintexts [planes xo yo][n]: none for a 1 x 1 window of stride 1, which works in place][the
-// decryptor's rows for the inputs, then the encryptor's (sym: the secret-key encryptor's) samples for the outputs]
+// Work: [decrypted plaintexts [planes xd yd][n]][activated plaintexts [planes xo yo][n]: none for a 1 x 1 window of stride 1, which works in place][the tail:
+// the decryptor's rows for the inputs, the encryptor's samples for the outputs]
 struct SlotsRefreshActWork { u64 *plain, *act, *w; };
 static SlotsRefreshActWork slots_refresh_act_layout(const crc_ctx *c, size_t planes, const Window &w, int in_form, bool sym, WorkArena &a)
 {
     const size_t in_cts = planes * (size_t)w.xd * w.yd, out_cts = planes * (size_t)w.P64();
-    const size_t dec = k_decrypt_work_words(c, in_cts, 2, in_form == CRC_NTT), enc = sym ? k_encrypt_sym_work_words(c, out_cts) : k_encrypt_work_words(c, out_cts);
     SlotsRefreshActWork L{};
     L.plain = a.take<u64>(in_cts * (size_t)c->n);
     L.act = slots_act_in_place_ok(w) ? L.plain : a.take<u64>(out_cts * (size_t)c->n);
-    L.w = a.take<u64>(dec > enc ? dec : enc);
+    L.w = a.take<u64>(refresh_tail_words(c, in_cts, in_form, sym, out_cts));
     return L;
 }
 static size_t slots_refresh_act_bytes(const crc_ctx *c, size_t planes, const Window &w, int in_form, bool sym)
@@ -970,19 +980,17 @@ static size_t slots_refresh_act_bytes(const crc_ctx *c, size_t planes, const Win
     return a.bytes();
 }
 struct SlotsActParams { size_t planes; Window w; u64 divisor; int relu; u64 cap; };
-static int slots_refresh_act_impl(crc_ctx *c, bool sym, const u64 *d_sk, const u64 *d_pk, const u64 *d_in, const SlotsActParams &p, int in_form, const ChaChaKey &key,
-                                  u64 stream_base, int out_form, u64 *d_out, void *d_work, hipStream_t st)
+static int slots_refresh_act_impl(crc_ctx *c, const Reenc &R, const u64 *d_in, const SlotsActParams &p, int in_form, u64 *d_out, void *d_work, hipStream_t st)
 {
+    CHECK_CTX(c);
     RUN(slots_act_args_ok(c, d_in, d_out, p.planes, p.w, p.divisor, p.relu, p.cap));
-    if (!d_sk || (!sym && !d_pk) || !d_work || !ct_form_ok(in_form) || !ct_form_ok(out_form)) return CRC_ERR_INVALID_ARGUMENT;
+    if (!R.ok() || !d_work || !ct_form_ok(in_form)) return CRC_ERR_INVALID_ARGUMENT;
     if (!p.planes) return CRC_OK;
     WorkArena a(d_work);
-    const SlotsRefreshActWork L = slots_refresh_act_layout(c, p.planes, p.w, in_form, sym, a);
-    const size_t in_cts = p.planes * (size_t)p.w.xd * p.w.yd, out_cts = p.planes * (size_t)p.w.P64();
-    RUN(k_decrypt(c, d_sk, d_in, in_cts, 2, in_form == CRC_NTT, L.plain, L.w, st));
+    const SlotsRefreshActWork L = slots_refresh_act_layout(c, p.planes, p.w, in_form, R.sym, a);
+    RUN(k_decrypt(c, R.d_sk, d_in, p.planes * (size_t)p.w.xd * p.w.yd, 2, in_form == CRC_NTT, L.plain, L.w, st));
     RUN(k_slots_act(c, L.plain, p.planes, p.w, p.divisor, p.relu, p.cap, L.act, st));
-    if (sym) return k_encrypt_sym(c, d_sk, L.act, out_cts, key, stream_base, d_out, L.w, st, out_form == CRC_NTT, false);
-    return k_encrypt(c, d_pk, L.act, out_cts, key, stream_base, d_out, L.w, st, out_form == CRC_NTT);
+    return R.run(c, L.act, p.planes * (size_t)p.w.P64(), false, 0, d_out, L.w, st);
 }
 extern "C" size_t crc_slots_refresh_act_dev_work_bytes(const crc_ctx *c, size_t planes, int xd, int yd, int xs, int ys, int xf, int yf, int in_form)
 {
@@ -996,33 +1004,29 @@ extern "C" int crc_slots_refresh_act_dev(crc_ctx *c, const uint64_t *d_sk, const
                                          int xf, int yf, int in_form, uint64_t divisor, int relu, uint64_t cap, uint64_t seed, int out_form, uint64_t *d_ct_out,
                                          void *d_work, void *stream)
 {
-    CHECK_CTX(c);
-    return slots_refresh_act_impl(c, false, d_sk, d_pk, d_ct_in, {planes, {xd, yd, xs, ys, xf, yf}, divisor, relu, cap}, in_form, chacha_seed_key(seed), 0, out_form,
+    return slots_refresh_act_impl(c, Reenc::seeded(d_sk, d_pk, false, seed, out_form), d_ct_in, {planes, {xd, yd, xs, ys, xf, yf}, divisor, relu, cap}, in_form,
                                   d_ct_out, d_work, S(stream));
 }
 extern "C" int crc_slots_refresh_act_dev_key(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_pk, const uint64_t *d_ct_in, size_t planes, int xd, int yd, int xs,
                                              int ys, int xf, int yf, int in_form, uint64_t divisor, int relu, uint64_t cap, const uint8_t *key, uint64_t stream_base,
                                              int out_form, uint64_t *d_ct_out, void *d_work, void *stream)
 {
-    CHECK_CTX(c); if (!key) return crc_slots_supported(c) ? CRC_ERR_INVALID_ARGUMENT : CRC_ERR_PARAMETERS;
-    return slots_refresh_act_impl(c, false, d_sk, d_pk, d_ct_in, {planes, {xd, yd, xs, ys, xf, yf}, divisor, relu, cap}, in_form, chacha_load_key(key), stream_base,
-                                  out_form, d_ct_out, d_work, S(stream));
+    return slots_refresh_act_impl(c, Reenc::keyed(d_sk, d_pk, false, key, stream_base, out_form), d_ct_in, {planes, {xd, yd, xs, ys, xf, yf}, divisor, relu, cap},
+                                  in_form, d_ct_out, d_work, S(stream));
 }
 extern "C" int crc_slots_refresh_act_sym_dev(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_ct_in, size_t planes, int xd, int yd, int xs, int ys, int xf, int yf,
                                              int in_form, uint64_t divisor, int relu, uint64_t cap, uint64_t seed, int out_form, uint64_t *d_ct_out, void *d_work,
                                              void *stream)
 {
-    CHECK_CTX(c);
-    return slots_refresh_act_impl(c, true, d_sk, nullptr, d_ct_in, {planes, {xd, yd, xs, ys, xf, yf}, divisor, relu, cap}, in_form, chacha_seed_key(seed), 0, out_form,
+    return slots_refresh_act_impl(c, Reenc::seeded(d_sk, nullptr, true, seed, out_form), d_ct_in, {planes, {xd, yd, xs, ys, xf, yf}, divisor, relu, cap}, in_form,
                                   d_ct_out, d_work, S(stream));
 }
 extern "C" int crc_slots_refresh_act_sym_dev_key(crc_ctx *c, const uint64_t *d_sk, const uint64_t *d_ct_in, size_t planes, int xd, int yd, int xs, int ys, int xf,
                                                  int yf, int in_form, uint64_t divisor, int relu, uint64_t cap, const uint8_t *key, uint64_t stream_base, int out_form,
                                                  uint64_t *d_ct_out, void *d_work, void *stream)
 {
-    CHECK_CTX(c); if (!key) return crc_slots_supported(c) ? CRC_ERR_INVALID_ARGUMENT : CRC_ERR_PARAMETERS;
-    return slots_refresh_act_impl(c, true, d_sk, nullptr, d_ct_in, {planes, {xd, yd, xs, ys, xf, yf}, divisor, relu, cap}, in_form, chacha_load_key(key), stream_base,
-                                  out_form, d_ct_out, d_work, S(stream));
+    return slots_refresh_act_impl(c, Reenc::keyed(d_sk, nullptr, true, key, stream_base, out_form), d_ct_in, {planes, {xd, yd, xs, ys, xf, yf}, divisor, relu, cap},
+                                  in_form, d_ct_out, d_work, S(stream));
 }
 // ---- several plain moduli: the CRT lift of the slots of r plaintext tensors, the activation on the lifted integers, the refresh that applies it ----
 extern "C" int crc_slots_crt_supported(crc_ctx *const *ctxs, int r)
@@ -1108,17 +1112,16 @@ extern "C" int crc_slots_crt_act_dev(crc_ctx *const *ctxs, int r, const uint64_t
     RUN(slots_crt_act_args_ok(ctxs[0], B, d_in, count, divisor, relu, cap, d_out, 16));
     return k_slots_crt_act(ctxs, B, d_in, count, divisor, relu, cap, d_out, S(stream));
 }
-// Work: [decrypted plaintexts of modulus j [count][n], j < r: the activation works on them in place][the decryptor's rows, then the encryptor's samples: the
-// largest over the r contexts and over both encryptors, so that one size serves either call]
+// Work: [decrypted plaintexts of modulus j [count][n], j < r: the activation works on them in place][the tail: the largest over the r contexts and over both
+// encryptors, so that one size serves either call]
 struct SlotsCrtRefreshWork { u64 *plain[CRC_SLOTS_CRT_MAX]; u64 *w; };
 static SlotsCrtRefreshWork slots_crt_refresh_layout(crc_ctx *const *ctxs, int r, size_t count, int in_form, WorkArena &a)
 {
     SlotsCrtRefreshWork L{};
     size_t w = 0;
     for (int j = 0; j < r; j++) {
-        const crc_ctx *c = ctxs[j];
-        L.plain[j] = a.take<u64>(count * (size_t)c->n);
-        for (const size_t s : {k_decrypt_work_words(c, count, 2, in_form == CRC_NTT), k_encrypt_sym_work_words(c, count), k_encrypt_work_words(c, count)}) w = s > w ? s : w;
+        L.plain[j] = a.take<u64>(count * (size_t)ctxs[j]->n);
+        for (const bool sym : {false, true}) { const size_t s = refresh_tail_words(ctxs[j], count, in_form, sym, count); w = s > w ? s : w; }
     }
     L.w = a.take<u64>(w);
     return L;
@@ -1131,9 +1134,9 @@ extern "C" size_t crc_slots_crt_refresh_dev_work_bytes(crc_ctx *const *ctxs, int
     slots_crt_refresh_layout(ctxs, r, count, in_form, a);
     return a.bytes();
 }
-// sym: encrypt under the secret key (d_pk unused)
-static int slots_crt_refresh_impl(crc_ctx *const *ctxs, int r, bool sym, const u64 *d_sk, const u64 *d_pk, const uint64_t *const *d_in, size_t count, int in_form,
-                                  u64 divisor, int relu, u64 cap, const uint8_t *key, u64 stream_base, int out_form, uint64_t *const *d_out, void *d_work, hipStream_t st)
+// member j takes the keystream ids stream_base + j count .. + count
+static int slots_crt_refresh_impl(crc_ctx *const *ctxs, int r, const Reenc &R, const uint64_t *const *d_in, size_t count, int in_form, u64 divisor, int relu, u64 cap,
+                                  uint64_t *const *d_out, void *d_work, hipStream_t st)
 {
     SlotsCrtBase B;
     if (!ctxs || r < 1 || r > CRC_SLOTS_CRT_MAX) return CRC_ERR_INVALID_ARGUMENT;
@@ -1141,30 +1144,28 @@ static int slots_crt_refresh_impl(crc_ctx *const *ctxs, int r, bool sym, const u
     RUN(slots_crt_base_ok(ctxs, r, B));
     if (divisor < 1 || divisor > ((uint64_t)1 << 62) || (relu != 0 && relu != 1) || cap > ((B.T - 1) >> 1)) return CRC_ERR_INVALID_ARGUMENT;
     if (!slots_crt_rows_ok(d_in, r, 16) || !slots_crt_rows_ok(d_out, r, 16)) return CRC_ERR_INVALID_ARGUMENT;
-    if (!d_sk || (!sym && !d_pk) || !d_work || !key || !ct_form_ok(in_form) || !ct_form_ok(out_form)) return CRC_ERR_INVALID_ARGUMENT;
+    if (!R.ok() || !d_work || !ct_form_ok(in_form)) return CRC_ERR_INVALID_ARGUMENT;
     if (!count) return CRC_OK;
     WorkArena a(d_work);
     const SlotsCrtRefreshWork L = slots_crt_refresh_layout(ctxs, r, count, in_form, a);
-    const ChaChaKey k = chacha_load_key(key);
-    for (int j = 0; j < r; j++) RUN(k_decrypt(ctxs[j], d_sk, d_in[j], count, 2, in_form == CRC_NTT, L.plain[j], L.w, st));
+    for (int j = 0; j < r; j++) RUN(k_decrypt(ctxs[j], R.d_sk, d_in[j], count, 2, in_form == CRC_NTT, L.plain[j], L.w, st));
     RUN(k_slots_crt_act(ctxs, B, L.plain, count, divisor, relu, cap, L.plain, st));
-    for (int j = 0; j < r; j++) {
-        if (sym) RUN(k_encrypt_sym(ctxs[j], d_sk, L.plain[j], count, k, stream_base + (u64)j * count, d_out[j], L.w, st, out_form == CRC_NTT, false));
-        else RUN(k_encrypt(ctxs[j], d_pk, L.plain[j], count, k, stream_base + (u64)j * count, d_out[j], L.w, st, out_form == CRC_NTT));
-    }
+    for (int j = 0; j < r; j++) RUN(R.run(ctxs[j], L.plain[j], count, false, (u64)j * count, d_out[j], L.w, st));
     return CRC_OK;
 }
 extern "C" int crc_slots_crt_refresh_dev_key(crc_ctx *const *ctxs, int r, const uint64_t *d_sk, const uint64_t *d_pk, const uint64_t *const *d_ct_in, size_t count,
                                              int in_form, uint64_t divisor, int relu, uint64_t cap, const uint8_t *key, uint64_t stream_base, int out_form,
                                              uint64_t *const *d_ct_out, void *d_work, void *stream)
 {
-    return slots_crt_refresh_impl(ctxs, r, false, d_sk, d_pk, d_ct_in, count, in_form, divisor, relu, cap, key, stream_base, out_form, d_ct_out, d_work, S(stream));
+    return slots_crt_refresh_impl(ctxs, r, Reenc::keyed(d_sk, d_pk, false, key, stream_base, out_form), d_ct_in, count, in_form, divisor, relu, cap, d_ct_out, d_work,
+                                  S(stream));
 }
 extern "C" int crc_slots_crt_refresh_sym_dev_key(crc_ctx *const *ctxs, int r, const uint64_t *d_sk, const uint64_t *const *d_ct_in, size_t count, int in_form,
                                                  uint64_t divisor, int relu, uint64_t cap, const uint8_t *key, uint64_t stream_base, int out_form,
                                                  uint64_t *const *d_ct_out, void *d_work, void *stream)
 {
-    return slots_crt_refresh_impl(ctxs, r, true, d_sk, nullptr, d_ct_in, count, in_form, divisor, relu, cap, key, stream_base, out_form, d_ct_out, d_work, S(stream));
+    return slots_crt_refresh_impl(ctxs, r, Reenc::keyed(d_sk, nullptr, true, key, stream_base, out_form), d_ct_in, count, in_form, divisor, relu, cap, d_ct_out, d_work,
+                                  S(stream));
 }
 // ---- seeded secret-key ciphertexts: the packed c0 rows and a public seed -> ordinary ciphertexts (kernels_client.hip: k_seeded_expand) ----
 extern "C" int crc_seeded_expand_dev(crc_ctx *c, const uint64_t *d_c0, size_t count, const uint8_t *seed, uint64_t stream_base, int out_form, uint64_t *d_ct,

@@ -1,6 +1,7 @@
 // crcnn_host.cpp -- implementation of the CrCNN-compatible C++ host classes on top of the C ABI (include/crcnn_hip.h).
 #include "crcnn_host.h"
 #include "diag_plan.h"
+#include "refresh_pass.h"
 #include "../csrc/host_parallel.h"          // std::thread ranges (header only; no other csrc internals are used here: the engine is reached through the C ABI)
 #include <algorithm>
 #include <atomic>
@@ -61,6 +62,26 @@ static crc_ctx *ctx()
 static int N() { return crc_ctx_n(ctx()); }
 static int K() { return crc_ctx_k(ctx()); }
 static size_t ctBytes() { return crc_ct_words(ctx(), 2) * 8; }
+static uint64_t *ctAt(const ciphertext3D &t, size_t i) { return t.data() + i * crc_ct_words(ctx(), 2); }
+
+// The randomness of `ids` keystream ids, drawn where they are spent.  Under setDeterministicSeed: a seed, fresh per draw.  Otherwise the master key from the
+// counter: one keystream per ciphertext, never reused under this key.  Either way the counter moves past the ids
+struct Randomness {
+    bool det; uint64_t seed, stream_base;
+    // one call of an entry point's seed / key pair: with(f, randomness...) puts the seed, or the key and its stream base, into f's argument list
+    template <class Seeded, class Keyed, class With> void call(Seeded seeded, const char *seeded_name, Keyed keyed, const char *keyed_name, With &&with) const
+    {
+        if (det) chk(with(seeded, seed), seeded_name);
+        else chk(with(keyed, (const uint8_t *)g_master_key, stream_base), keyed_name);
+    }
+};
+#define ABI(f) f, #f
+static Randomness drawRandomness(size_t ids)
+{
+    const Randomness r{g_det, g_det_seed + 1000003 * (g_enc_counter + 1), g_enc_counter};
+    g_enc_counter += ids;
+    return r;
+}
 
 // Device allocations are recycled by exact size: the reference passes its tensors by value and so do these classes -- every Layer::forward makes a new output
 // tensor -- but a hipMalloc / hipFree pair per layer and chunk (the free synchronises the device) would cost more than some of the layers.  Freed buffers wait
@@ -417,13 +438,8 @@ static ciphertext3D encryptPixels(const vector<float> &px, int zd, int xd, int y
     const uint64_t *d_pk = deviceKey(g_d_pk, g_d_pk_fp, public_key, "public key");
     chk(crc_memcpy_h2d(ctx(), d_pl.ptr, pl.data(), pl.size() * 8, stream()), "crc_memcpy_h2d");
     ciphertext3D out(1, zd, xd, yd, CRC_COEFF);
-    if (g_det)
-        chk(crc_encrypt_dev(ctx(), d_pk, (const uint64_t *)d_pl.ptr, px.size(), g_det_seed + 1000003 * (g_enc_counter + 1),
-                            (uint64_t *)out.buf->ptr, d_work.ptr, stream()), "crc_encrypt_dev");
-    else                                                    // one keystream per ciphertext, never reused under this key
-        chk(crc_encrypt_dev_key(ctx(), d_pk, (const uint64_t *)d_pl.ptr, px.size(), g_master_key, g_enc_counter,
-                                (uint64_t *)out.buf->ptr, d_work.ptr, stream()), "crc_encrypt_dev_key");
-    g_enc_counter += px.size();
+    drawRandomness(px.size()).call(ABI(crc_encrypt_dev), ABI(crc_encrypt_dev_key), [&](auto f, auto... rnd) {
+        return f(ctx(), d_pk, (const uint64_t *)d_pl.ptr, px.size(), rnd..., (uint64_t *)out.buf->ptr, d_work.ptr, stream()); });
     chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
     return out;
 }
@@ -455,13 +471,8 @@ ciphertext3D encryptImageSymmetric(const vector<float> &px, int zd, int xd, int 
     const uint64_t *d_sk = deviceKey(g_d_sk, g_d_sk_fp, secret_key, "secret key");
     chk(crc_memcpy_h2d(ctx(), d_pl.ptr, pl.data(), pl.size() * 8, stream()), "crc_memcpy_h2d");
     ciphertext3D out((int)(px.size() / per), zd, xd, yd, out_form);
-    if (g_det)
-        chk(crc_encrypt_sym_dev_forms(ctx(), d_sk, (const uint64_t *)d_pl.ptr, px.size(), g_det_seed + 1000003 * (g_enc_counter + 1), out_form,
-                                      (uint64_t *)out.buf->ptr, d_work.ptr, stream()), "crc_encrypt_sym_dev_forms");
-    else
-        chk(crc_encrypt_sym_dev_key_forms(ctx(), d_sk, (const uint64_t *)d_pl.ptr, px.size(), g_master_key, g_enc_counter, out_form,
-                                          (uint64_t *)out.buf->ptr, d_work.ptr, stream()), "crc_encrypt_sym_dev_key_forms");
-    g_enc_counter += px.size();
+    drawRandomness(px.size()).call(ABI(crc_encrypt_sym_dev_forms), ABI(crc_encrypt_sym_dev_key_forms), [&](auto f, auto... rnd) {
+        return f(ctx(), d_sk, (const uint64_t *)d_pl.ptr, px.size(), rnd..., out_form, (uint64_t *)out.buf->ptr, d_work.ptr, stream()); });
     chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
     return out;
 }
@@ -479,15 +490,15 @@ static void encryptSeededOnDevice(const vector<float> &px, SeededImages &out)
     DeviceBuffer d_px(px.size() * 4), d_c0(out.c0.size() * 8), d_work(crc_encrypt_f32_seeded_dev_work_bytes(ctx(), px.size()));
     const uint64_t *d_sk = deviceKey(g_d_sk, g_d_sk_fp, secret_key, "secret key");
     chk(crc_memcpy_h2d(ctx(), d_px.ptr, px.data(), px.size() * 4, stream()), "crc_memcpy_h2d");
-    if (g_det) {
-        const uint64_t seed = g_det_seed + 1000003 * (g_enc_counter + 1);
-        chk(crc_seeded_public_seed(seed, out.seed), "crc_seeded_public_seed");
+    const Randomness r = drawRandomness(px.size());
+    if (r.det) {
+        chk(crc_seeded_public_seed(r.seed, out.seed), "crc_seeded_public_seed");
         out.stream_base = 0;
-        chk(crc_encrypt_f32_seeded_dev(ctx(), d_sk, (const float *)d_px.ptr, px.size(), seed, (uint64_t *)d_c0.ptr, d_work.ptr, stream()),
+        chk(crc_encrypt_f32_seeded_dev(ctx(), d_sk, (const float *)d_px.ptr, px.size(), r.seed, (uint64_t *)d_c0.ptr, d_work.ptr, stream()),
             "crc_encrypt_f32_seeded_dev");
     } else {
         chk(crc_random_key(out.seed), "crc_random_key");
-        out.stream_base = g_enc_counter;
+        out.stream_base = r.stream_base;
         chk(crc_encrypt_f32_seeded_dev_key(ctx(), d_sk, (const float *)d_px.ptr, px.size(), g_master_key, out.seed, out.stream_base, (uint64_t *)d_c0.ptr,
                                            d_work.ptr, stream()), "crc_encrypt_f32_seeded_dev_key");
     }
@@ -504,23 +515,21 @@ SeededImages encryptImageSeeded(const vector<float> &px, int zd, int xd, int yd,
     out.c0.resize(px.size() * (size_t)K() * n);
     if (on_device) {
         encryptSeededOnDevice(px, out);
-        g_enc_counter += px.size();
         return out;
     }
     vector<uint64_t> pl(px.size() * n);
     chk(crc_encode_f32(ctx(), px.data(), px.size(), pl.data(), nullptr), "crc_encode_f32");
-    if (g_det) {
-        const uint64_t seed = g_det_seed + 1000003 * (g_enc_counter + 1);
-        chk(crc_seeded_public_seed(seed, out.seed), "crc_seeded_public_seed");
+    const Randomness r = drawRandomness(px.size());
+    if (r.det) {
+        chk(crc_seeded_public_seed(r.seed, out.seed), "crc_seeded_public_seed");
         out.stream_base = 0;
-        chk(crc_encrypt_sym_seeded(ctx(), secret_key.data(), pl.data(), px.size(), seed, out.c0.data()), "crc_encrypt_sym_seeded");
+        chk(crc_encrypt_sym_seeded(ctx(), secret_key.data(), pl.data(), px.size(), r.seed, out.c0.data()), "crc_encrypt_sym_seeded");
     } else {
         chk(crc_random_key(out.seed), "crc_random_key");
-        out.stream_base = g_enc_counter;
+        out.stream_base = r.stream_base;
         chk(crc_encrypt_sym_seeded_key(ctx(), secret_key.data(), pl.data(), px.size(), g_master_key, out.seed, out.stream_base, out.c0.data()),
             "crc_encrypt_sym_seeded_key");
     }
-    g_enc_counter += px.size();
     return out;
 }
 SeededImages encryptImageSeeded(floatCube image, bool on_device)
@@ -589,13 +598,8 @@ ciphertext3D encryptImageSlots(const vector<vector<int64_t>> &images, int zd, in
     // image-major: pixel c of image j at h[j per + c]
     chk(crc_slots_compose_dev(ctx(), (const int64_t *)d_v.ptr, per, (int)S, 1, per, (uint64_t *)d_pl.ptr, stream()), "crc_slots_compose_dev");
     ciphertext3D out(1, zd, xd, yd, out_form);
-    if (g_det)
-        chk(crc_encrypt_dev_forms(ctx(), d_pk, (const uint64_t *)d_pl.ptr, per, g_det_seed + 1000003 * (g_enc_counter + 1), out_form, (uint64_t *)out.data(),
-                                  d_work.ptr, stream()), "crc_encrypt_dev_forms");
-    else
-        chk(crc_encrypt_dev_key_forms(ctx(), d_pk, (const uint64_t *)d_pl.ptr, per, g_master_key, g_enc_counter, out_form, (uint64_t *)out.data(), d_work.ptr,
-                                      stream()), "crc_encrypt_dev_key_forms");
-    g_enc_counter += per;
+    drawRandomness(per).call(ABI(crc_encrypt_dev_forms), ABI(crc_encrypt_dev_key_forms), [&](auto f, auto... rnd) {
+        return f(ctx(), d_pk, (const uint64_t *)d_pl.ptr, per, rnd..., out_form, out.data(), d_work.ptr, stream()); });
     chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
     return out;
 }
@@ -931,13 +935,8 @@ ciphertext3D encryptImagePlanes(const vector<int64_t> &pixels, int zd, int xd, i
     chk(crc_memcpy_h2d(ctx(), d_v.ptr, h.data(), h.size() * 8, stream()), "crc_memcpy_h2d");
     chk(crc_slots_compose_dev(ctx(), (const int64_t *)d_v.ptr, zd, n, n, 1, (uint64_t *)d_pl.ptr, stream()), "crc_slots_compose_dev");
     ciphertext3D out(1, zd, 1, 1, out_form);
-    if (g_det)
-        chk(crc_encrypt_dev_forms(ctx(), d_pk, (const uint64_t *)d_pl.ptr, zd, g_det_seed + 1000003 * (g_enc_counter + 1), out_form, (uint64_t *)out.data(),
-                                  d_work.ptr, stream()), "crc_encrypt_dev_forms");
-    else
-        chk(crc_encrypt_dev_key_forms(ctx(), d_pk, (const uint64_t *)d_pl.ptr, zd, g_master_key, g_enc_counter, out_form, (uint64_t *)out.data(), d_work.ptr,
-                                      stream()), "crc_encrypt_dev_key_forms");
-    g_enc_counter += zd;
+    drawRandomness(zd).call(ABI(crc_encrypt_dev_forms), ABI(crc_encrypt_dev_key_forms), [&](auto f, auto... rnd) {
+        return f(ctx(), d_pk, (const uint64_t *)d_pl.ptr, zd, rnd..., out_form, out.data(), d_work.ptr, stream()); });
     chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
     return out;
 }
@@ -1155,6 +1154,18 @@ static void toForm(ciphertext3D &t, int form, const char *who)
     t.form = form;
 }
 
+// The pass driver of the client-side refreshes.  `items` items (ciphertexts, or whole planes) of in_cts input ciphertexts and `ids` keystream ids each go through
+// launch(first item, items, randomness) in passes of refresh_pass_len items, which share the layers' scratch area; every pass draws its randomness as it starts
+template <class WorkBytes, class Launch> static void refreshPasses(size_t items, size_t in_cts, size_t ids, WorkBytes &&work_bytes, Launch &&launch)
+{
+    const size_t pass = refresh_pass_len(work_bytes(1), items, in_cts);
+    ensure(g_scratch, work_bytes(pass));
+    for (size_t o = 0; o < items; o += pass) {
+        const size_t c = min(pass, items - o);
+        launch(o, c, drawRandomness(c * ids));
+    }
+}
+
 // The client-side refresh of network.cpp:30-34 -- `floatCube image = decryptImage(input); input = encryptImage(image);` -- for a whole batch on the launch
 // stream (crc_refresh_dev: decrypt, decode, round to float, encode, encrypt; nothing crosses PCIe and the host does not wait).  Passes of bounded size share the
 // layers' scratch area.  Fresh randomness per ciphertext exactly as encryptImage draws it (deterministic only under setDeterministicSeed)
@@ -1167,32 +1178,16 @@ ciphertext3D refreshImages(const ciphertext3D &t, int out_form, vector<float> *v
     const uint64_t *d_pk = symmetric ? nullptr : deviceKey(g_d_pk, g_d_pk_fp, public_key, "public key");
     auto work_bytes = [&](size_t c) { return symmetric ? crc_refresh_sym_dev_work_bytes(ctx(), c, t.form) : crc_refresh_dev_work_bytes(ctx(), c, t.form); };
     ciphertext3D out(t.B, t.zd, t.xd, t.yd, out_form);
-    const size_t cnt = t.count(), one = work_bytes(1);
-    size_t pass = ((size_t)4 << 30) / (one ? one : 1);
-    if (pass < 1024) pass = 1024;
-    if (pass > cnt) pass = cnt;
-    ensure(g_scratch, work_bytes(pass));
+    const size_t cnt = t.count();
     shared_ptr<DeviceBuffer> d_vals;
     if (values) d_vals = make_shared<DeviceBuffer>(cnt * sizeof(float));
-    for (size_t o = 0; o < cnt; o += pass) {
-        const size_t c = min(pass, cnt - o);
-        const uint64_t *in = (const uint64_t *)((const char *)t.data() + o * ctBytes());
-        uint64_t *dst = (uint64_t *)((char *)out.data() + o * ctBytes());
+    refreshPasses(cnt, 1, 1, work_bytes, [&](size_t o, size_t c, const Randomness &rnd) {
         float *dv = d_vals ? (float *)d_vals->ptr + o : nullptr;
-        if (symmetric && g_det)
-            chk(crc_refresh_sym_dev(ctx(), d_sk, in, c, t.form, g_det_seed + 1000003 * (g_enc_counter + 1), out_form, dst, dv, g_scratch->ptr, stream()),
-                "crc_refresh_sym_dev");
-        else if (symmetric)
-            chk(crc_refresh_sym_dev_key(ctx(), d_sk, in, c, t.form, g_master_key, g_enc_counter, out_form, dst, dv, g_scratch->ptr, stream()),
-                "crc_refresh_sym_dev_key");
-        else if (g_det)
-            chk(crc_refresh_dev(ctx(), d_sk, d_pk, in, c, t.form, g_det_seed + 1000003 * (g_enc_counter + 1), out_form, dst, dv, g_scratch->ptr, stream()),
-                "crc_refresh_dev");
-        else
-            chk(crc_refresh_dev_key(ctx(), d_sk, d_pk, in, c, t.form, g_master_key, g_enc_counter, out_form, dst, dv, g_scratch->ptr, stream()),
-                "crc_refresh_dev_key");
-        g_enc_counter += c;
-    }
+        if (symmetric) rnd.call(ABI(crc_refresh_sym_dev), ABI(crc_refresh_sym_dev_key), [&](auto f, auto... r) {
+            return f(ctx(), d_sk, ctAt(t, o), c, t.form, r..., out_form, ctAt(out, o), dv, g_scratch->ptr, stream()); });
+        else rnd.call(ABI(crc_refresh_dev), ABI(crc_refresh_dev_key), [&](auto f, auto... r) {
+            return f(ctx(), d_sk, d_pk, ctAt(t, o), c, t.form, r..., out_form, ctAt(out, o), dv, g_scratch->ptr, stream()); });
+    });
     if (values) {
         values->assign(cnt, 0.f);
         chk(crc_memcpy_d2h(ctx(), values->data(), d_vals->ptr, cnt * sizeof(float), stream()), "crc_memcpy_d2h");
@@ -1214,28 +1209,12 @@ ciphertext3D rescaleSlots(const ciphertext3D &t, uint64_t divisor, int out_form,
     const uint64_t *d_pk = symmetric ? nullptr : deviceKey(g_d_pk, g_d_pk_fp, public_key, "public key");
     auto work_bytes = [&](size_t c) { return symmetric ? crc_slots_refresh_sym_dev_work_bytes(ctx(), c, t.form) : crc_slots_refresh_dev_work_bytes(ctx(), c, t.form); };
     ciphertext3D out(t.B, t.zd, t.xd, t.yd, out_form);
-    const size_t cnt = t.count(), one = work_bytes(1);
-    size_t pass = ((size_t)4 << 30) / (one ? one : 1);
-    if (pass < 1024) pass = 1024;
-    if (pass > cnt) pass = cnt;
-    ensure(g_scratch, work_bytes(pass));
-    for (size_t o = 0; o < cnt; o += pass) {
-        const size_t c = min(pass, cnt - o);
-        const uint64_t *in = (const uint64_t *)((const char *)t.data() + o * ctBytes());
-        uint64_t *dst = (uint64_t *)((char *)out.data() + o * ctBytes());
-        const uint64_t seed = g_det_seed + 1000003 * (g_enc_counter + 1);
-        if (symmetric && g_det)
-            chk(crc_slots_refresh_sym_dev(ctx(), d_sk, in, c, t.form, divisor, seed, out_form, dst, g_scratch->ptr, stream()), "crc_slots_refresh_sym_dev");
-        else if (symmetric)
-            chk(crc_slots_refresh_sym_dev_key(ctx(), d_sk, in, c, t.form, divisor, g_master_key, g_enc_counter, out_form, dst, g_scratch->ptr, stream()),
-                "crc_slots_refresh_sym_dev_key");
-        else if (g_det)
-            chk(crc_slots_refresh_dev(ctx(), d_sk, d_pk, in, c, t.form, divisor, seed, out_form, dst, g_scratch->ptr, stream()), "crc_slots_refresh_dev");
-        else
-            chk(crc_slots_refresh_dev_key(ctx(), d_sk, d_pk, in, c, t.form, divisor, g_master_key, g_enc_counter, out_form, dst, g_scratch->ptr, stream()),
-                "crc_slots_refresh_dev_key");
-        g_enc_counter += c;
-    }
+    refreshPasses(t.count(), 1, 1, work_bytes, [&](size_t o, size_t c, const Randomness &rnd) {
+        if (symmetric) rnd.call(ABI(crc_slots_refresh_sym_dev), ABI(crc_slots_refresh_sym_dev_key), [&](auto f, auto... r) {
+            return f(ctx(), d_sk, ctAt(t, o), c, t.form, divisor, r..., out_form, ctAt(out, o), g_scratch->ptr, stream()); });
+        else rnd.call(ABI(crc_slots_refresh_dev), ABI(crc_slots_refresh_dev_key), [&](auto f, auto... r) {
+            return f(ctx(), d_sk, d_pk, ctAt(t, o), c, t.form, divisor, r..., out_form, ctAt(out, o), g_scratch->ptr, stream()); });
+    });
     return out;
 }
 ciphertext3D SlotRescaleLayer::forward(ciphertext3D input)
@@ -1262,30 +1241,15 @@ ciphertext3D actSlots(const ciphertext3D &t, int xs, int ys, int xf, int yf, uin
     auto work_bytes = [&](size_t p) { return symmetric ? crc_slots_refresh_act_sym_dev_work_bytes(ctx(), p, xd, yd, xs, ys, xf, yf, t.form)
                                                       : crc_slots_refresh_act_dev_work_bytes(ctx(), p, xd, yd, xs, ys, xf, yf, t.form); };
     ciphertext3D out(t.B, t.zd, xo, yo, out_form);
-    const size_t planes = (size_t)t.B * t.zd, in_cts = (size_t)xd * yd, out_cts = (size_t)xo * yo, one = work_bytes(1);
-    size_t pass = ((size_t)4 << 30) / (one ? one : 1);
-    if (pass * in_cts < 1024) pass = (1024 + in_cts - 1) / in_cts;
-    if (pass > planes) pass = planes;
-    ensure(g_scratch, work_bytes(pass));
-    for (size_t o = 0; o < planes; o += pass) {
-        const size_t p = min(pass, planes - o);
-        const uint64_t *in = (const uint64_t *)((const char *)t.data() + o * in_cts * ctBytes());
-        uint64_t *dst = (uint64_t *)((char *)out.data() + o * out_cts * ctBytes());
-        const uint64_t seed = g_det_seed + 1000003 * (g_enc_counter + 1);
-        if (symmetric && g_det)
-            chk(crc_slots_refresh_act_sym_dev(ctx(), d_sk, in, p, xd, yd, xs, ys, xf, yf, t.form, divisor, relu, cap, seed, out_form, dst, g_scratch->ptr, stream()),
-                "crc_slots_refresh_act_sym_dev");
-        else if (symmetric)
-            chk(crc_slots_refresh_act_sym_dev_key(ctx(), d_sk, in, p, xd, yd, xs, ys, xf, yf, t.form, divisor, relu, cap, g_master_key, g_enc_counter, out_form, dst,
-                                                  g_scratch->ptr, stream()), "crc_slots_refresh_act_sym_dev_key");
-        else if (g_det)
-            chk(crc_slots_refresh_act_dev(ctx(), d_sk, d_pk, in, p, xd, yd, xs, ys, xf, yf, t.form, divisor, relu, cap, seed, out_form, dst, g_scratch->ptr, stream()),
-                "crc_slots_refresh_act_dev");
-        else
-            chk(crc_slots_refresh_act_dev_key(ctx(), d_sk, d_pk, in, p, xd, yd, xs, ys, xf, yf, t.form, divisor, relu, cap, g_master_key, g_enc_counter, out_form, dst,
-                                              g_scratch->ptr, stream()), "crc_slots_refresh_act_dev_key");
-        g_enc_counter += p * out_cts;
-    }
+    const size_t in_cts = (size_t)xd * yd, out_cts = (size_t)xo * yo;
+    refreshPasses((size_t)t.B * t.zd, in_cts, out_cts, work_bytes, [&](size_t o, size_t p, const Randomness &rnd) {
+        if (symmetric) rnd.call(ABI(crc_slots_refresh_act_sym_dev), ABI(crc_slots_refresh_act_sym_dev_key), [&](auto f, auto... r) {
+            return f(ctx(), d_sk, ctAt(t, o * in_cts), p, xd, yd, xs, ys, xf, yf, t.form, divisor, relu, cap, r..., out_form, ctAt(out, o * out_cts), g_scratch->ptr,
+                     stream()); });
+        else rnd.call(ABI(crc_slots_refresh_act_dev), ABI(crc_slots_refresh_act_dev_key), [&](auto f, auto... r) {
+            return f(ctx(), d_sk, d_pk, ctAt(t, o * in_cts), p, xd, yd, xs, ys, xf, yf, t.form, divisor, relu, cap, r..., out_form, ctAt(out, o * out_cts), g_scratch->ptr,
+                     stream()); });
+    });
     return out;
 }
 ciphertext3D SlotReluLayer::forward(ciphertext3D input)
@@ -1473,11 +1437,8 @@ static void floodOn(crc_ctx *c, const uint64_t *d_pk, uint64_t *d_ct, size_t cou
     if (form != CRC_COEFF && form != CRC_NTT) throw invalid_argument(string(who) + ": ciphertext forms only (CRC_COEFF / CRC_NTT)");
     if (!crc_flood_supported(c, flood_bits)) throw invalid_argument(string(who) + ": flood_bits is not admissible for the encryption parameters");
     ensure(g_scratch, crc_flood_dev_work_bytes(c, count, form));
-    if (g_det)
-        chk(crc_flood_dev(c, d_pk, d_ct, count, form, flood_bits, g_det_seed + 1000003 * (g_enc_counter + 1), g_scratch->ptr, stream()), "crc_flood_dev");
-    else                                                    // one keystream per ciphertext, never reused under this key
-        chk(crc_flood_dev_key(c, d_pk, d_ct, count, form, flood_bits, g_master_key, g_enc_counter, g_scratch->ptr, stream()), "crc_flood_dev_key");
-    g_enc_counter += count;
+    drawRandomness(count).call(ABI(crc_flood_dev), ABI(crc_flood_dev_key), [&](auto f, auto... rnd) {
+        return f(c, d_pk, d_ct, count, form, flood_bits, rnd..., g_scratch->ptr, stream()); });
 }
 void floodImages(ciphertext3D &t, int flood_bits)
 {
@@ -1624,10 +1585,10 @@ static const PlainBase &baseOf(const PlainBaseTensor &t, const char *who)
     return B;
 }
 // under setDeterministicSeed: the public expansion of the seed encryptImage would have used (NOT secure, as every seeded run)
-static void crtKey(uint8_t key[CRC_KEY_BYTES], uint64_t &stream_base)
+static void crtKey(const Randomness &r, uint8_t key[CRC_KEY_BYTES], uint64_t &stream_base)
 {
-    if (g_det) { chk(crc_seeded_public_seed(g_det_seed + 1000003 * (g_enc_counter + 1), key), "crc_seeded_public_seed"); stream_base = 0; }
-    else { memcpy(key, g_master_key, CRC_KEY_BYTES); stream_base = g_enc_counter; }
+    if (r.det) { chk(crc_seeded_public_seed(r.seed, key), "crc_seeded_public_seed"); stream_base = 0; }
+    else { memcpy(key, g_master_key, CRC_KEY_BYTES); stream_base = r.stream_base; }
 }
 PlainBaseTensor encryptImageSlotsCrt(const vector<vector<int64_t>> &images, int zd, int xd, int yd, const shared_ptr<PlainBase> &base, int out_form)
 {
@@ -1650,10 +1611,9 @@ PlainBaseTensor encryptImageSlotsCrt(const vector<vector<int64_t>> &images, int 
         chk(crc_slots_compose_dev(c, (const int64_t *)d_v.ptr, per, (int)S, 1, per, (uint64_t *)d_pl.ptr, stream()), "crc_slots_compose_dev");
         ciphertext3D part(1, zd, xd, yd, out_form);
         uint8_t key[CRC_KEY_BYTES]; uint64_t stream_base;
-        crtKey(key, stream_base);
+        crtKey(drawRandomness(per), key, stream_base);
         chk(crc_encrypt_dev_key_forms(c, (const uint64_t *)B.d_public_key->ptr, (const uint64_t *)d_pl.ptr, per, key, stream_base, out_form, part.data(), d_work.ptr,
                                       stream()), "crc_encrypt_dev_key_forms");
-        g_enc_counter += per;
         out.parts.push_back(part);
     }
     chk(crc_stream_sync(ctx(), stream()), "crc_stream_sync");
@@ -1692,29 +1652,20 @@ PlainBaseTensor rescaleSlotsCrt(const PlainBaseTensor &t, uint64_t divisor, int 
     out.base = t.base;
     for (int j = 0; j < r; j++) out.parts.push_back(ciphertext3D(p0.B, p0.zd, p0.xd, p0.yd, out_form));
     auto work_bytes = [&](size_t c) { return crc_slots_crt_refresh_dev_work_bytes(B.ctxs.data(), r, c, t.form()); };
-    const size_t cnt = t.count(), one = work_bytes(1);
-    size_t pass = ((size_t)4 << 30) / (one ? one : 1);
-    if (pass < 1024) pass = 1024;
-    if (pass > cnt) pass = cnt;
-    ensure(g_scratch, work_bytes(pass));
     const uint64_t *d_sk = (const uint64_t *)B.d_secret_key->ptr, *d_pk = (const uint64_t *)B.d_public_key->ptr;
-    for (size_t o = 0; o < cnt; o += pass) {
-        const size_t c = min(pass, cnt - o);
+    // member j takes the stream ids stream_base + j c .. + c of its pass's r c
+    refreshPasses(t.count(), 1, r, work_bytes, [&](size_t o, size_t c, const Randomness &rnd) {
         const uint64_t *in[CRC_SLOTS_CRT_MAX]; uint64_t *dst[CRC_SLOTS_CRT_MAX];
-        for (int j = 0; j < r; j++) {
-            in[j] = (const uint64_t *)((const char *)t.parts[j].data() + o * ctBytes());
-            dst[j] = (uint64_t *)((char *)out.parts[j].data() + o * ctBytes());
-        }
+        for (int j = 0; j < r; j++) { in[j] = ctAt(t.parts[j], o); dst[j] = ctAt(out.parts[j], o); }
         uint8_t key[CRC_KEY_BYTES]; uint64_t stream_base;
-        crtKey(key, stream_base);
+        crtKey(rnd, key, stream_base);
         if (symmetric)
             chk(crc_slots_crt_refresh_sym_dev_key(B.ctxs.data(), r, d_sk, in, c, t.form(), divisor, relu, cap, key, stream_base, out_form, dst, g_scratch->ptr, stream()),
                 "crc_slots_crt_refresh_sym_dev_key");
         else
             chk(crc_slots_crt_refresh_dev_key(B.ctxs.data(), r, d_sk, d_pk, in, c, t.form(), divisor, relu, cap, key, stream_base, out_form, dst, g_scratch->ptr,
                                               stream()), "crc_slots_crt_refresh_dev_key");
-        g_enc_counter += (size_t)r * c;                       // member j took the stream ids stream_base + j c .. + c
-    }
+    });
     return out;
 }
 ciphertext3D component(const PlainBaseTensor &t, int j)
